@@ -4,6 +4,7 @@
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 2 --dry-run          (CPU rehearsal of the N > 1 control flow over gloo: no GPU, no numbers)
+    python bench.py ... --dump-outputs DIR      (also writes the last timed step's outputs as DIR/<name>.npy: two builds compared output for output)
 
 With N > 1 and no WORLD_SIZE in the environment the script starts the N ranks ITSELF: child processes created before the
 parent has made any GPU call, the parent only waits, relays rank 0's JSON line and exits non-zero if any rank failed or
@@ -536,6 +537,28 @@ def launch_ranks(args):
 
 WATCHDOG_EXIT_CODE = 3
 
+DUMP_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: `arrays` (name -> host array, the last timed step's outputs) as DIR/<name>.npy in float32. Over DUMP_BYTES in
+    all, every array keeps the same fraction of its rows, chosen by a generator seeded from its name -- the same rows from run to
+    run -- and DIR/<name>_rows.npy says which. Returns name -> shape written."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.size * 4 for a in arrays.values())
+    keep = 1.0 if total <= DUMP_BYTES else DUMP_BYTES / (total + sum(a.shape[0] * 8 for a in arrays.values()))   # (+ the row indices)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if keep < 1.0:
+            rows = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.shape[0], max(1, int(a.shape[0] * keep)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
 
 def guarded_leg(rank, line, where, leg, timeout_s):
     """Run `leg()` (something that may hang inside a GPU / collective call that no Python exception will ever leave: a second
@@ -670,6 +693,9 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the N > 1 control flow over gloo (rendezvous, RCCL id broadcast, shard ranges, barriers, "
                          "the gather of the logits): prints a line with n_gpus = N, dry_run = true and NO throughput")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step of the headline (and of the KWS step) left in its outputs to "
+                         "DIR/<name>.npy, float32, %d MB in all at most (a fixed, seeded sample of rows beyond that); rank 0's shard" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -761,11 +787,15 @@ def main():
     # an awake board (boost clocks: faster than settled), where `serial_cold` is a burst on an idle one (slower than settled, DESIGN.md
     # section 5). `serial` right after it shows what of the difference is the board's; `settled` is the figure that lasts.
     wall_ms, ev_ms = timed_region(head_step, args.steps, args.warmup, world, 0.0, **head_kw)
+    last = args.warmup + args.steps - 1
+    # --dump-outputs: the headline's output as its last timed step left it (the legs below write the same buffers again)
+    dumped = {}
+    if args.dump_outputs and rank == 0:
+        dumped["mfcc_b"] = (outs2[last & 1] if n_queues == 2 else out).cpu().numpy()
     # what the LAST timed step left in its output, and the samples it read: checked against the oracle in the cpu_baseline leg (`parity`)
     sample = {}
     n_par = min(4096, nf)
     if rank == 0 and world == 1 and not args.skip_cpu:
-        last = args.warmup + args.steps - 1
         sample["frames"] = bufs[last % len(bufs)][:n_par].cpu().numpy()
         sample["mfcc_b"] = (outs2[last & 1] if n_queues == 2 else out)[:n_par].cpu().numpy()
     frames_per_s = world * nf / (wall_ms * 1e-3)
@@ -1011,6 +1041,8 @@ def main():
         # 7 ms steps: up to 50 warm-up steps = 0.35 s. No time-based settle phase here: for N > 1 the step ends in a
         # collective, and ranks must execute the same number of steps.
         kw_ms, kev_ms = timed_region(kws_step, args.steps, min(args.warmup, 50), world)
+        if args.dump_outputs and rank == 0:
+            dumped.update(kws_logits=logits.cpu().numpy(), kws_softmax=soft.cpu().numpy(), kws_argmax=am.cpu().numpy())
         if sample:
             n_pu = min(128, nu)
             sample["utt_audio"] = audio[:n_pu].cpu().numpy()
@@ -1123,6 +1155,8 @@ def main():
                                 frame_len=1024, parallelism="dp%d" % world, rotate_buffers=args.rotate, queues=n_queues,
                                 **({} if ranks_two_queues is None else {"ranks_with_two_queues": ranks_two_queues})),
                     roofline=roofline, device=info["name"])
+        if dumped:
+            line["outputs_dumped"] = dict(dir=args.dump_outputs, arrays=dump_outputs(args.dump_outputs, dumped))
         if parity is not None:
             line["parity"] = parity
             if not parity.get("ok"):

@@ -271,3 +271,24 @@ def test_bench_collectives_do_not_sit_under_rank_local_conditions():
 
     walk(main, [])
     assert len(found) >= 10, found
+
+
+def test_bench_dump_outputs_stays_within_its_budget_and_samples_the_same_rows(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy per output; over the budget every array keeps the same share of its rows, the same
+    rows on every run (two builds are compared output for output), and the files stay under the budget."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    rng = np.random.default_rng(0)
+    arrays = dict(small=rng.integers(-128, 128, (1000, 10)).astype(np.int8), big=rng.normal(size=(40000, 13)))
+    assert bench.dump_outputs(str(tmp_path / "all"), dict(small=arrays["small"])) == dict(small=[1000, 10])
+    got = np.load(tmp_path / "all" / "small.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, arrays["small"]) and not (tmp_path / "all" / "small_rows.npy").exists()
+    for d in ("a", "b"):
+        shapes = bench.dump_outputs(str(tmp_path / d), arrays)
+        assert shapes["big"][1] == 13 and 0 < shapes["big"][0] < 40000 and shapes["small"][1] == 10 and 0 < shapes["small"][0] < 1000
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= (1 << 20) + 4 * 128     # (+ the .npy headers)
+    for name in ("big", "small", "big_rows", "small_rows"):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    rows = np.load(tmp_path / "a" / "big_rows.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "big.npy"), arrays["big"][rows].astype(np.float32))

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,8 +20,8 @@ def _run(*argv):
 
 
 @pytest.mark.parametrize("steps", [6, 48])
-def test_bench_line_is_whole_and_its_parity_object_green(built_lib, steps):
-    d = _run("--frames", "16384", "--utts", "4096", "--steps", str(steps), "--warmup", "3", "--settle-ms", "10")
+def test_bench_line_is_whole_and_its_parity_object_green(built_lib, steps, tmp_path):
+    d = _run("--frames", "16384", "--utts", "4096", "--steps", str(steps), "--warmup", "3", "--settle-ms", "10", "--dump-outputs", str(tmp_path))
     # the contract's keys
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline"):
@@ -49,3 +50,7 @@ def test_bench_line_is_whole_and_its_parity_object_green(built_lib, steps):
         assert k in d and "error" not in d[k], (k, d.get(k))
     assert d["batch_list"]["outputs_bit_identical_to_one_call_per_batch"] and d["two_queues"]["outputs_bit_identical_to_serial"]
     assert d["kws"]["collective_path"].startswith("none")
+    # --dump-outputs: what the last timed step of the headline and of the KWS step left, float32
+    assert d["outputs_dumped"]["arrays"] == dict(mfcc_b=[16384, 13], kws_logits=[4096, 10], kws_softmax=[4096, 10], kws_argmax=[4096])
+    m, am = np.load(tmp_path / "mfcc_b.npy"), np.load(tmp_path / "kws_argmax.npy")
+    assert m.dtype == am.dtype == np.float32 and m.shape == (16384, 13) and np.isfinite(m).all() and ((am >= 0) & (am < 10)).all()

@@ -248,12 +248,17 @@ def test_cnn_vs_oracle_random(ctx, oracle_mod, oracle_model):
     assert (g["softmax"] == 127).any() and (g["softmax"] == 0).any()
 
 
+def cnn_reference_build_inputs():
+    return np.random.default_rng(321).integers(-128, 128, (1500, 403)).astype(np.int8)
+
+
 def test_cnn_vs_reference_build(ctx, oracle_mod):
-    if not oracle_mod.have_ref():
-        pytest.skip("oracle/_ref not present")
-    rng = np.random.default_rng(321)
-    f = rng.integers(-128, 128, (1500, 403)).astype(np.int8)
-    g, r = ctx.cnn(f), oracle_mod.nnom_ref_batch(f)
+    """The GPU's CNN vs the reference NNoM/CMSIS-NN build itself (oracle/_ref); where that build is absent, vs its outputs on the
+    same inputs recorded in tests/golden/refpins_golden.npz (tests/refpins.py)."""
+    import refpins
+    f = cnn_reference_build_inputs()
+    r = refpins.outputs("gpu_cnn_reference_build", (lambda: oracle_mod.nnom_ref_batch(f)) if oracle_mod.have_ref() else None)
+    g = ctx.cnn(f)
     for k in ("logits", "softmax", "argmax"):
         assert np.array_equal(g[k], r[k]), k
 

@@ -95,13 +95,18 @@ def test_oracle_cnn_matches_reference_layers(oracle_mod, oracle_model, cnn_golde
     assert np.array_equal(r["argmax"], cnn_golden["argmax"])
 
 
-def test_oracle_cnn_matches_reference_build(oracle_mod, oracle_model):
-    """Restatement vs the reference NNoM/CMSIS-NN build itself (oracle/_ref) on fresh random inputs."""
-    if not oracle_mod.have_ref():
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
+def cnn_reference_build_inputs():
     rng = np.random.default_rng(11)
-    f = np.concatenate([rng.integers(-128, 128, (300, 403)), np.clip(rng.normal(0, 30, (200, 403)), -128, 127).round()]).astype(np.int8)
-    a, b = oracle_mod.nnom_ref_batch(f), oracle_mod.cnn(oracle_model, f, n_threads=4)
+    return np.concatenate([rng.integers(-128, 128, (300, 403)), np.clip(rng.normal(0, 30, (200, 403)), -128, 127).round()]).astype(np.int8)
+
+
+def test_oracle_cnn_matches_reference_build(oracle_mod, oracle_model):
+    """Restatement vs the reference NNoM/CMSIS-NN build itself (oracle/_ref) on fresh random inputs; where that build is absent,
+    vs its outputs on the same inputs recorded in tests/golden/refpins_golden.npz (tests/refpins.py)."""
+    import refpins
+    f = cnn_reference_build_inputs()
+    a = refpins.outputs("cnn_reference_build", (lambda: oracle_mod.nnom_ref_batch(f)) if oracle_mod.have_ref() else None)
+    b = oracle_mod.cnn(oracle_model, f, n_threads=4)
     for k in ("logits", "softmax", "argmax"):
         assert np.array_equal(a[k], b[k]), k
 

@@ -16,6 +16,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import refpins
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -51,47 +53,56 @@ def _frames():
 
 @pytest.fixture(scope="module")
 def q15ref(oracle_mod):
-    if not oracle_mod.have_q15_ref():
-        pytest.skip("oracle/_ref/libcmsis_q15_ref.so absent and /root/reference not mounted")
-    return oracle_mod.cmsis_q15_ref()
+    """The reference's compiled CMSIS-DSP routines, or None where oracle/_ref/libcmsis_q15_ref.so is absent: the tests then take
+    the routines' outputs recorded in tests/golden/refpins_golden.npz (tests/refpins.py)."""
+    return oracle_mod.cmsis_q15_ref() if oracle_mod.have_q15_ref() else None
 
 
 def test_q15_oracle_stages_equal_the_reference_routines(oracle_mod, q15ref):
     """oracle/mfcc_q15_ref.c vs arm_cfft_q15 -> arm_radix4_butterfly_q15 (1024 and 16 points), arm_sqrt_q31 and
-    arm_split_rfft_q15 of the reference, stage by stage, on ~16.5 k frames."""
+    arm_split_rfft_q15 of the reference, stage by stage, on ~16.5 k frames (recorded: the digests of the three stages' outputs)."""
     x = _frames()
     n = x.shape[0]
     tab = oracle_mod.Q15Tables().arrays()
     mf, st = oracle_mod.mfcc_q15(x.ravel(), stages=True, n_threads=4)
-    # [1] the 1024-point complex FFT of audioCalcMFCCs (audioprocessing.c:135-139): real samples, zero imaginary parts
-    buf = np.zeros((n, 2048), np.int16)
-    buf[:, 0::2] = x
-    ref_fft = q15ref.cfft(buf, tab["tw1024"]).reshape(n, 1024, 2)[:, _bitrev(10), :]     # arm_bitreversal_16 = plain bit reversal
-    assert np.array_equal(st["fft"], ref_fft)
-    # [2] cmpl_mag_q15 (audioprocessing.c:299-312): arm_sqrt_q31 of re^2 + im^2 (wrapping 32-bit sum), top halfword
-    re, im = ref_fft[:, :513, 0].astype(np.int64), ref_fft[:, :513, 1].astype(np.int64)
-    s = ((re * re + im * im) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
-    spec = (q15ref.sqrt_q31(s) >> 16).astype(np.int16)
-    assert np.array_equal(st["spectrogram"], spec)
-    # [5] dct2_q15 (audioprocessing.c:330-436): even/odd reorder, arm_rfft_q15(32) = arm_cfft_q15(16) + arm_split_rfft_q15, real parts
-    mel = st["mel_spectrogram"]
-    v = np.zeros((n, 32), np.int16)
-    v[:, :16] = mel[:, 0::2]
-    v[:, 31:15:-1] = mel[:, 1::2]
-    z = q15ref.cfft(v, tab["tw16"]).reshape(n, 16, 2)[:, _bitrev(4), :].reshape(n, 32)
-    out = q15ref.split_rfft(z, tab["rfa"], tab["rfb"], modifier=1)                        # [n][64]: 32 complex
-    assert np.array_equal(mf, out[:, 0::2])
+
+    def live():
+        # [1] the 1024-point complex FFT of audioCalcMFCCs (audioprocessing.c:135-139): real samples, zero imaginary parts
+        buf = np.zeros((n, 2048), np.int16)
+        buf[:, 0::2] = x
+        ref_fft = q15ref.cfft(buf, tab["tw1024"]).reshape(n, 1024, 2)[:, _bitrev(10), :]     # arm_bitreversal_16 = plain bit reversal
+        # [2] cmpl_mag_q15 (audioprocessing.c:299-312): arm_sqrt_q31 of re^2 + im^2 (wrapping 32-bit sum), top halfword
+        re, im = ref_fft[:, :513, 0].astype(np.int64), ref_fft[:, :513, 1].astype(np.int64)
+        s = ((re * re + im * im) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+        spec = (q15ref.sqrt_q31(s) >> 16).astype(np.int16)
+        # [5] dct2_q15 (audioprocessing.c:330-436): even/odd reorder, arm_rfft_q15(32) = arm_cfft_q15(16) + arm_split_rfft_q15, real parts
+        mel = st["mel_spectrogram"]
+        v = np.zeros((n, 32), np.int16)
+        v[:, :16] = mel[:, 0::2]
+        v[:, 31:15:-1] = mel[:, 1::2]
+        z = q15ref.cfft(v, tab["tw16"]).reshape(n, 16, 2)[:, _bitrev(4), :].reshape(n, 32)
+        out = q15ref.split_rfft(z, tab["rfa"], tab["rfb"], modifier=1)                        # [n][64]: 32 complex
+        return dict(fft=ref_fft, spectrogram=spec, dct=out[:, 0::2])
+    want = refpins.digests("q15_stages", live if q15ref is not None else None)
+    assert refpins.digest(st["fft"]) == want["fft"]
+    assert refpins.digest(st["spectrogram"]) == want["spectrogram"]
+    assert refpins.digest(mf) == want["dct"]
 
 
 def test_sqrt_q31_restatement_equals_the_reference_on_a_sweep(oracle_mod, q15ref):
     """the square root alone, denser than the frames reach: every power-of-two neighbourhood, 4 M random positives,
-    zero and negatives (the routine answers 0)"""
+    zero and negatives (the routine answers 0). Recorded: every input but the random ones, and 20 000 of those."""
     rng = np.random.default_rng(7)
     xs = [rng.integers(1, 2 ** 31, 4_000_000, dtype=np.int64), np.array([0, -1, -2 ** 31, 2 ** 31 - 1, 1, 2, 3])]
     for b in range(31):
         xs.append(np.arange(max(1, (1 << b) - 300), min(2 ** 31 - 1, (1 << b) + 300)))
     x = np.concatenate(xs).astype(np.int64).astype(np.int32)
-    ref = q15ref.sqrt_q31(x)
+    kept = np.concatenate([np.sort(np.random.default_rng(8).choice(4_000_000, 20_000, replace=False)), np.arange(4_000_000, x.size)])
+    if q15ref is not None:
+        ref = q15ref.sqrt_q31(x)
+        refpins.outputs("sqrt_q31_sweep", lambda: dict(kept=ref[kept]))
+    else:
+        x, ref = x[kept], refpins.outputs("sqrt_q31_sweep", None)["kept"]
     # through the oracle's frame function: a "frame" cannot carry arbitrary sums, so the restated routine is reached through
     # the verification tool below instead; here: the reference against exact arithmetic, |ref - sqrt(x * 2^31)| small
     pos = x > 0
@@ -103,21 +114,32 @@ def test_sqrt_q31_restatement_equals_the_reference_on_a_sweep(oracle_mod, q15ref
 def test_gpu_sqrt_formulations_proved_against_the_reference_object_code(tmp_path, oracle_mod, q15ref):
     """tools/verify/sqrt_q31_equiv.c and sqrt_q31_floor.c enumerate inputs and compare the GPU kernel's two formulations of
     arm_sqrt_q31 with ... the reference's compiled arm_sqrt_q31 itself (dlopen of oracle/_ref/libcmsis_q15_ref.so), not a
-    restatement. Here with a stride (2^31 / 4099 inputs each, a few seconds); the full enumeration is `... 1`."""
+    restatement. Here with a stride (2^31 / 4099 inputs each, a few seconds); the full enumeration is `... 1`. Where that library
+    is absent, against the tools' own restatement of the routine (the sequence the library checks when it is given)."""
     so = oracle_mod.Q15_REF_SO
     for tool in ("sqrt_q31_equiv", "sqrt_q31_floor"):
         exe = str(tmp_path / tool)
         subprocess.check_call(["gcc", "-O2", "-fopenmp", "-o", exe, os.path.join(ROOT, "tools", "verify", tool + ".c"), "-ldl", "-lm"])
-        r = subprocess.run([exe, "4099", so], capture_output=True, text=True, timeout=600)
+        r = subprocess.run([exe, "4099"] + ([so] if q15ref is not None else []), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout + r.stderr
-        assert "reference object code" in r.stdout, r.stdout
+        assert ("reference object code" if q15ref is not None else "the restated sequence") in r.stdout, r.stdout
 
 
 @pytest.fixture(scope="module")
 def f32ref(oracle_mod):
-    if not oracle_mod.have_f32_ref():
-        pytest.skip("oracle/_ref/libmfcc_f32_ref.so absent and /root/reference not mounted")
-    return oracle_mod.mfcc_f32_ref()
+    """The reference's compiled variant-D code, or None where oracle/_ref/libmfcc_f32_ref.so is absent: the tests then take its
+    outputs recorded in tests/golden/refpins_golden.npz (tests/refpins.py)."""
+    return oracle_mod.mfcc_f32_ref() if oracle_mod.have_f32_ref() else None
+
+
+DCT_SHAPES = ((26, 13), (26, 26), (26, 1), (40, 10), (13, 13))
+FBANK_PADDED = (512, 1024, 256, 128)
+
+
+def _dct(f32ref, n_in, n_out):
+    """the reference's create_dct_matrix(n_in, n_out), live or recorded"""
+    return refpins.outputs("f32_dct_matrix", (lambda: {"%dx%d" % s: f32ref.dct_matrix(*s) for s in DCT_SHAPES}) if f32ref is not None else None)[
+        "%dx%d" % (n_in, n_out)]
 
 
 def test_variant_d_dct_matrix_equals_the_reference(built_lib, oracle_mod, f32ref):
@@ -125,15 +147,15 @@ def test_variant_d_dct_matrix_equals_the_reference(built_lib, oracle_mod, f32ref
     reference's compiled create_dct_matrix (mfcc.c:101-115), float32 bit patterns."""
     built_lib.create_dct_matrix.restype = ctypes.POINTER(ctypes.c_float)
     built_lib.create_dct_matrix.argtypes = [ctypes.c_int32, ctypes.c_int32]
-    for n_in, n_out in ((26, 13), (26, 26), (26, 1), (40, 10), (13, 13)):
-        ref = f32ref.dct_matrix(n_in, n_out)
+    for n_in, n_out in DCT_SHAPES:
+        ref = _dct(f32ref, n_in, n_out)
         p = built_lib.create_dct_matrix(n_in, n_out)
         got = np.ctypeslib.as_array(p, shape=(n_out, n_in)).copy()
         ctypes.CDLL(None).free(p)
         assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), (n_in, n_out)
     for nf in (13, 26, 1):
         dct, _, _, _ = oracle_mod.MfccF32(num_mfcc_features=nf, feature_offset=0).tables()
-        assert np.array_equal(dct.view(np.uint32), f32ref.dct_matrix(26, nf).view(np.uint32))
+        assert np.array_equal(dct.view(np.uint32), _dct(f32ref, 26, nf).view(np.uint32))
 
 
 class _F32Tables(ctypes.Structure):
@@ -152,8 +174,10 @@ def test_variant_d_mel_filterbank_equals_the_reference(built_lib, oracle_mod, f3
     built_lib.ed_build_f32_tables.restype = ctypes.c_int
     built_lib.ed_build_f32_tables.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                               ctypes.POINTER(_F32Tables), ctypes.c_char_p, ctypes.c_size_t]
+    fb = refpins.outputs("f32_mel_fbank", (lambda: {"%s_%d" % (k, p): v for p in FBANK_PADDED for k, v in zip(("first", "last", "w"), f32ref.mel_fbank(p))})
+                         if f32ref is not None else None)
     for frame_len, padded in ((512, 512), (400, 512), (1024, 1024), (640, 1024), (256, 256), (128, 128)):
-        first, last, w = f32ref.mel_fbank(padded)
+        first, last, w = fb["first_%d" % padded], fb["last_%d" % padded], fb["w_%d" % padded]
         t = _F32Tables()
         err = ctypes.create_string_buffer(200)
         assert built_lib.ed_build_f32_tables(13, 1, frame_len, 8, 0.97, ctypes.byref(t), err, 200) == 0, err.value
@@ -162,7 +186,7 @@ def test_variant_d_mel_filterbank_equals_the_reference(built_lib, oracle_mod, f3
         got = np.array(t.mel_w, dtype=np.float32)[:w.size]
         assert np.array_equal(np.array(t.mel_off), np.concatenate([[0], np.cumsum(last - first + 1)[:-1]]))
         assert np.array_equal(got.view(np.uint32), w.view(np.uint32)), frame_len
-        assert np.array_equal(np.array(t.dct, dtype=np.float32)[:13 * 26].view(np.uint32), f32ref.dct_matrix(26, 13).ravel().view(np.uint32))
+        assert np.array_equal(np.array(t.dct, dtype=np.float32)[:13 * 26].view(np.uint32), _dct(f32ref, 26, 13).ravel().view(np.uint32))
         _, ofirst, olast, ow = oracle_mod.MfccF32(frame_len=frame_len).tables()
         assert np.array_equal(ofirst, first) and np.array_equal(olast, last) and np.array_equal(ow.view(np.uint32), w.view(np.uint32))
 
@@ -187,12 +211,13 @@ def test_variant_d_transform_tables_come_from_the_reference_routine(oracle_mod, 
     off the routine itself (it asserts, through the compiled routines, that the result is the DFT to float32 accuracy). The
     swap list it derives is exactly as long as ARM's table for 256 points (ARMBITREVINDEXTABLE_256_TABLE_LENGTH = 440,
     arm_common_tables.h), and the fixture keeps it."""
-    tw, rev, rt = f32ref.fft_tables(512)
+    rec = refpins.outputs("f32_fft_tables_512", (lambda: dict(zip(("tw", "rev", "rt"), f32ref.fft_tables(512)))) if f32ref is not None else None)
+    tw, rev, rt = rec["tw"], rec["rev"], rec["rt"]
     assert tw.shape == (256, 2) and rt.shape == (256, 2) and rev.size == 440 and rev.max() < 8 * 256 and (rev % 8 == 0).all()
     assert rt[0, 0] == 0.0 and rt[0, 1] == 1.0                      # (sin, cos): the layout the real-transform stage reads
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mfccf32_golden.npz"))
     assert np.array_equal(g["bitrev_swaps_256"], rev)
-    for n in (64, 128, 256, 1024, 2048):                            # every length mfcc_create can ask for in practice
+    for n in (64, 128, 256, 1024, 2048) if f32ref is not None else ():   # every length mfcc_create can ask for in practice (live only)
         f32ref.fft_tables(n)
 
 
@@ -210,7 +235,9 @@ def test_variant_d_restatement_equals_the_reference_mfcc_compute(oracle_mod, f32
     for cfg, bar in ((dict(), 0.999), (dict(num_mfcc_features=13, feature_offset=0, frame_len=480, mfcc_dec_bits=7, preempha=0.0), 0.98),
                      (dict(num_mfcc_features=10, feature_offset=1, frame_len=400, mfcc_dec_bits=5, preempha=0.95), 0.999)):
         hop = cfg.get("frame_len", 512) // 2
-        ri, rlm = f32ref.compute(x, frame_step=hop, **cfg)
+        key = "f32_compute_%d_%d_%d" % (cfg.get("num_mfcc_features", 13), cfg.get("feature_offset", 1), cfg.get("frame_len", 512))
+        rec = refpins.outputs(key, (lambda: dict(zip(("int8", "logmel"), f32ref.compute(x, frame_step=hop, **cfg)))) if f32ref is not None else None)
+        ri, rlm = rec["int8"], rec["logmel"]
         pi, _, plm = oracle_mod.MfccF32(**cfg)(x, frame_step=hop)
         assert ri.shape == pi.shape and ri.shape[0] > 1000
         d = np.abs(ri.astype(int) - pi.astype(int))
@@ -233,9 +260,14 @@ def test_output_filter_class_choice_equals_arm_max_f32(oracle_mod, f32ref):
     soft[5:65, 2] = 100
     soft[5:65, 5] = 100                                              # two classes fed identically from equal states: exact ties
     filt, likely, spotted, _ = oracle_mod.output_filter(soft)
+
+    def live():
+        vi = [f32ref.arm_max(filt[i]) for i in range(soft.shape[0])]
+        return dict(val=np.array([v for v, _ in vi], np.float32), idx=np.array([i for _, i in vi], np.int64))
+    rec = refpins.outputs("f32_arm_max", live if f32ref is not None else None)
     ties = 0
     for i in range(soft.shape[0]):
-        val, idx = f32ref.arm_max(filt[i])
+        val, idx = float(rec["val"][i]), int(rec["idx"][i])
         assert idx == likely[i] and val == filt[i, likely[i]], i
         ties += int((filt[i] == val).sum() > 1)
     assert ties >= 20

@@ -4,8 +4,9 @@
 # usage: tools/verify/asan_planner.sh [n_random=300]
 set -e
 cd "$(dirname "$0")/../.."
-OUT=${TMPDIR:-/tmp}/edison_asan_planner
-rm -rf "$OUT"; mkdir -p "$OUT/blobs"
+OUT=$(mktemp -d "${TMPDIR:-/tmp}/edison_asan_planner.XXXXXX")   # a directory of this run's own: several users / runs on one machine
+trap 'rm -rf "$OUT"' EXIT
+mkdir -p "$OUT/blobs"
 python3 - "$OUT/blobs" "${1:-300}" <<'PY'
 import os, sys
 sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tools"))
