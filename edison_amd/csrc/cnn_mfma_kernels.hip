@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "edison_internal.h"
+#include "edison_launch.h"
 #include "edison_fsm_core.h"
 
 /* ---- lab knobs: only a lab build (ED_LAB, tools/lab/mkvariant.py) may set them; the product build has none, and
@@ -783,10 +784,6 @@ extern "C" int ed_launch_kws1(const ed_mfcc_args_t *margs, const ed_mfcc_tables_
                               int8_t *logits, int8_t *softmax, int32_t *argmax, unsigned *done_flag, unsigned done_seq, const ed_out_filter_t *filter,
                               hipStream_t stream);
 
-/* "the kernel's dynamic-LDS limit has been raised" is a property of the function ON A DEVICE: one flag per device, so that
- * two contexts on different GPUs of one process both get it */
-static int g_cnn_mfma_ready[16] = {0};
-
 /* feat_stride = bytes between consecutive utterances' feature maps: 403 for packed utterances, 13 for the
  * sliding windows of a stream (window i = feature rows i..i+30 of one long [rows][13] buffer). */
 extern "C" int ed_launch_cnn_mfma_flag(const ed_cnn_mfma_model_t *dev_model, const int8_t *feat, int64_t n_utt,
@@ -809,16 +806,7 @@ extern "C" int ed_launch_cnn_mfma_flag(const ed_cnn_mfma_model_t *dev_model, con
 	if (flag_written) *flag_written = 0;
 	if (n_utt <= 0) return 0;
 	const size_t lds = sizeof(ed_cnn_mfma_model_t) + (size_t)EDM_WAVES * EDM_WAVE_LDS + 16 /* queue */;
-	int dev_ = 0;
-	(void)hipGetDevice(&dev_);
-	dev_ &= 15;
-	if (!g_cnn_mfma_ready[dev_])
-	{
-		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ed_cnn_mfma_kernel),
-		                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		if (e != hipSuccess) return (int)e;
-		g_cnn_mfma_ready[dev_] = 1;
-	}
+	{ const int e = ed_kernel_prepare((const void *)ed_cnn_mfma_kernel, EDM_THREADS, lds, NULL, NULL); if (e) return e; }
 	const int64_t n_groups = (n_utt + EDM_G - 1) / EDM_G;
 	int64_t blocks = (n_groups + EDM_WAVES - 1) / EDM_WAVES;
 	if (blocks > n_cu) blocks = n_cu; /* 157 KB of LDS: one workgroup per CU */
@@ -844,16 +832,7 @@ extern "C" int ed_launch_kws1(const ed_mfcc_args_t *margs, const ed_mfcc_tables_
 	const bool narrow = margs->mel_NLO == 2 && margs->mel_NHI == 5;
 	if (!narrow && !(margs->mel_NLO == ED_MEL_NLO_MAX && margs->mel_NHI == ED_MEL_NHI_MAX)) return (int)hipErrorInvalidValue;
 	const void *fn = narrow ? (const void *)ed_kws1_kernel<2, 5> : (const void *)ed_kws1_kernel<ED_MEL_NLO_MAX, ED_MEL_NHI_MAX>;
-	static int ready[16][2];
-	int dev_ = 0;
-	(void)hipGetDevice(&dev_);
-	dev_ &= 15;
-	if (!ready[dev_][narrow])
-	{
-		hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		if (e != hipSuccess) return (int)e;
-		ready[dev_][narrow] = 1;
-	}
+	{ const int e = ed_kernel_prepare(fn, EDM_THREADS, lds, NULL, NULL); if (e) return e; }
 	ed_out_filter_t f;
 	memset(&f, 0, sizeof(f));
 	if (filter) f = *filter;

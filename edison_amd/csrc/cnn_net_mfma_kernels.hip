@@ -1196,6 +1196,8 @@ extern "C" __global__ __launch_bounds__(64 * EMM_SM_waves) void ed_net_mfma_spec
 	emm_net_body<EMM_SM_frag_mode == 2>(P, M, frag, seeds, in, n, in_stride, logits, softmax, argmax, done_flag, done_seq);
 }
 #else
+#include "edison_launch.h"
+
 template <bool FRAG_LDS>
 __global__ __launch_bounds__(EMM_MAX_THREADS) void ed_net_mfma_kernel(const ed_net_plan_t *__restrict__ P, const ed_mm_plan_t *__restrict__ M,
                                                                  const int8_t *__restrict__ frag, const int32_t *__restrict__ seeds,
@@ -1222,17 +1224,8 @@ extern "C" int ed_launch_net_mfma(const ed_net_plan_t *dev_plan, const ed_mm_pla
 	if (blocks > (int64_t)n_cu * per_cu) blocks = (int64_t)n_cu * per_cu;
 	const int resident = frag_mode == 2;
 	const void *fn = resident ? (const void *)ed_net_mfma_kernel<true> : (const void *)ed_net_mfma_kernel<false>;
-	static int max_lds_set_dev[16][2]; /* per device: the attribute belongs to the function on the current device */
-	int dev_ = 0;
-	(void)hipGetDevice(&dev_);
-	int *max_lds_set = max_lds_set_dev[dev_ & 15];
-	if (lds_bytes > max_lds_set[resident])
-	{
-		/* more than 64 KB of dynamic LDS has to be asked for */
-		hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-		if (e != hipSuccess) return (int)e;
-		max_lds_set[resident] = lds_bytes;
-	}
+	/* raised as models with more LDS load */
+	{ const int e = ed_kernel_prepare(fn, 64 * waves, (size_t)lds_bytes, NULL, NULL); if (e) return e; }
 	/* done_flag: written by the kernel itself when the launch is one workgroup whose first wave takes every input */
 	unsigned *flag = (done_flag && n <= batch) ? done_flag : nullptr;
 	void *kargs[] = {(void *)&dev_plan, (void *)&dev_mm, (void *)&dev_frag, (void *)&dev_seeds, (void *)&in, (void *)&n, (void *)&in_stride,

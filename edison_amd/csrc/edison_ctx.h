@@ -108,6 +108,50 @@ static inline int ed_set_err(edison_ctx *ctx, int code, const char *msg)
 	return code;
 }
 
+/* a launcher's hipError_t: EDISON_OK, or EDISON_E_RUNTIME with "<what> launch failed: ..." in ctx->err */
+static inline int ed_launch_result(edison_ctx *ctx, int e, const char *what)
+{
+	if (e == 0) return EDISON_OK;
+	snprintf(ctx->err, sizeof(ctx->err), "%s launch failed: %s", what, hipGetErrorString((hipError_t)e));
+	return EDISON_E_RUNTIME;
+}
+
+/* one device allocation, freed with its owner; a zero-byte buffer still gets 1 byte */
+struct ed_dev_buf
+{
+	void *p = NULL;
+	ed_dev_buf() = default;
+	ed_dev_buf(const ed_dev_buf &) = delete;
+	ed_dev_buf &operator=(const ed_dev_buf &) = delete;
+	~ed_dev_buf() { if (p) (void)hipFree(p); }
+	hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
+};
+
+/* The device copies of a host-pointer call (edison_mfcc_batch, edison_cnn_batch, ...) on ctx->stream: each input is allocated
+ * and uploaded, each output allocated and downloaded by finish(). Counts are in elements of the host pointer's type. The first
+ * failure is kept (message in ctx->err) and makes every later call a no-op returning NULL, so a wrapper declares its buffers,
+ * runs its _dev twin only if ok(), and returns finish(). */
+struct ed_staging
+{
+	explicit ed_staging(edison_ctx *ctx); /* hipSetDevice(ctx->device) */
+	template <class T> const T *in(const T *host, size_t n) { return (const T *)stage(host, NULL, n * sizeof(T)); }
+	/* host == NULL: nothing allocated, NULL returned (the output is not computed) */
+	template <class T> T *out(T *host, size_t n) { return host ? (T *)stage(NULL, host, n * sizeof(T)) : NULL; }
+	/* always allocated, downloaded only if host != NULL (kws_host's features) */
+	template <class T> T *scratch(T *host, size_t n) { return (T *)stage(NULL, host, n * sizeof(T)); }
+	bool ok() const { return err == EDISON_OK; }
+	/* r: the _dev call's result. If everything so far succeeded, enqueue the downloads; then, once anything was staged,
+	 * synchronise ctx->stream on every path. Returns the first error. */
+	int finish(int r);
+
+private:
+	void *stage(const void *up, void *down, size_t bytes);
+	int fail(hipError_t e, const char *what);
+	edison_ctx *ctx;
+	int err = EDISON_OK, n = 0;
+	struct { ed_dev_buf d; void *down; size_t bytes; } buf[8];
+};
+
 /* The loaded model on 31x13x1 -> 10 features (the geometry of every kws / stream entry point): matrix-core kernel for
  * the kws_conv graph, the general kernel for any other graph of that shape. feat_stride = bytes between utterances. */
 int ed_ctx_kws_cnn_launch(edison_ctx *ctx, const int8_t *feat, int64_t n_utt, int64_t feat_stride, int8_t *logits,

@@ -77,23 +77,8 @@ extern "C" int edison_mfcc_f32_batch_dev(mfcc_t *mfcc, const int16_t *audio, int
 	int e = (mfcc->padded == 512 && ctx->d_tab[0] && !generic)
 	            ? ed_launch_mfcc_f32_fast(&a, mfcc->d_tab, ctx->d_tab[0], ctx->n_cu, ctx->stream)
 	            : ed_launch_mfcc_f32(&a, mfcc->d_tab, mfcc->padded, ctx->n_cu, ctx->stream);
-	if (e != 0)
-	{
-		snprintf(ctx->err, sizeof(ctx->err), "float32 MFCC kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-		return EDISON_E_RUNTIME;
-	}
-	return EDISON_OK;
+	return ed_launch_result(ctx, e, "float32 MFCC kernel");
 }
-
-namespace {
-struct dev_buf
-{
-	void *p;
-	dev_buf() : p(NULL) {}
-	~dev_buf() { if (p) (void)hipFree(p); }
-	hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-};
-} // namespace
 
 extern "C" int edison_mfcc_f32_batch(mfcc_t *mfcc, const int16_t *audio, int64_t n_frames, int64_t frame_step, int8_t *out,
                                      float *out_f32, float *logmel)
@@ -101,22 +86,12 @@ extern "C" int edison_mfcc_f32_batch(mfcc_t *mfcc, const int16_t *audio, int64_t
 	if (!mfcc || n_frames < 0 || frame_step < 0 || ((!audio || !out) && n_frames > 0)) return EDISON_E_ARGUMENT;
 	if (n_frames == 0) return EDISON_OK;
 	edison_ctx *ctx = mfcc->ctx;
-	ED_HIP(ctx, hipSetDevice(ctx->device));
-	dev_buf a, o, f, l;
+	ed_staging st(ctx);
 	const size_t n = (size_t)n_frames, no = (size_t)mfcc->n_out;
-	const size_t na = ((size_t)(n_frames - 1) * (size_t)frame_step + (size_t)mfcc->frame_len) * sizeof(int16_t);
-	ED_HIP(ctx, a.alloc(na));
-	ED_HIP(ctx, o.alloc(n * no));
-	if (out_f32) ED_HIP(ctx, f.alloc(n * no * sizeof(float)));
-	if (logmel) ED_HIP(ctx, l.alloc(n * ED_F32_NUM_FBANK * sizeof(float)));
-	ED_HIP(ctx, hipMemcpyAsync(a.p, audio, na, hipMemcpyHostToDevice, ctx->stream));
-	int r = edison_mfcc_f32_batch_dev(mfcc, (const int16_t *)a.p, n_frames, frame_step, (int8_t *)o.p, (float *)f.p, (float *)l.p);
-	if (r != EDISON_OK) return r;
-	ED_HIP(ctx, hipMemcpyAsync(out, o.p, n * no, hipMemcpyDeviceToHost, ctx->stream));
-	if (out_f32) ED_HIP(ctx, hipMemcpyAsync(out_f32, f.p, n * no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-	if (logmel) ED_HIP(ctx, hipMemcpyAsync(logmel, l.p, n * ED_F32_NUM_FBANK * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-	ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return EDISON_OK;
+	const int16_t *a = st.in(audio, (size_t)(n_frames - 1) * (size_t)frame_step + (size_t)mfcc->frame_len);
+	int8_t *o = st.out(out, n * no);
+	float *f = st.out(out_f32, n * no), *l = st.out(logmel, n * ED_F32_NUM_FBANK);
+	return st.finish(st.ok() ? edison_mfcc_f32_batch_dev(mfcc, a, n_frames, frame_step, o, f, l) : EDISON_OK);
 }
 
 /* ---- the firmware's own names, on the process-global context (created like aiInitialize does) ---- */
@@ -264,15 +239,8 @@ extern "C" int edison_f32_stream_push(edison_f32_stream *s, const int16_t *sampl
 	if (n_events == 0) return EDISON_OK;
 	edison_ctx *ctx = s->ctx;
 	if (n_events > s->max_events) return ed_set_err(ctx, EDISON_E_SIZE, "f32 stream: more events than the stream was created for");
-	ED_HIP(ctx, hipSetDevice(ctx->device));
-	dev_buf a, w;
-	const size_t na = (size_t)n_events * 512 * sizeof(int16_t), nw = (size_t)n_events * s->rows * s->n_out;
-	ED_HIP(ctx, a.alloc(na));
-	ED_HIP(ctx, w.alloc(nw));
-	ED_HIP(ctx, hipMemcpyAsync(a.p, samples, na, hipMemcpyHostToDevice, ctx->stream));
-	int r = edison_f32_stream_push_dev(s, (const int16_t *)a.p, n_events, (int8_t *)w.p);
-	if (r != EDISON_OK) return r;
-	ED_HIP(ctx, hipMemcpyAsync(windows, w.p, nw, hipMemcpyDeviceToHost, ctx->stream));
-	ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return EDISON_OK;
+	ed_staging st(ctx);
+	const int16_t *a = st.in(samples, (size_t)n_events * 512);
+	int8_t *w = st.out(windows, (size_t)n_events * s->rows * s->n_out);
+	return st.finish(st.ok() ? edison_f32_stream_push_dev(s, a, n_events, w) : EDISON_OK);
 }

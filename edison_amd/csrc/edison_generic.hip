@@ -106,23 +106,11 @@ extern "C" int edison_mfcc_generic_dev(edison_ctx *ctx, const int16_t *audio, in
 	a.fft = fft; a.spec = spec; a.mel = mel; a.logmel = logmel; a.mfcc = mfcc;
 	a.n_coef = n_coef; a.feat = feat; a.feat_scale = feat_scale;
 	const int e = ed_launch_mfcc_generic(&a, ctx->n_cu, ctx->stream);
-	if (e != 0)
-	{
-		snprintf(ctx->err, sizeof(ctx->err), "generic MFCC kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-		return EDISON_E_RUNTIME;
-	}
+	if (e != 0) return ed_launch_result(ctx, e, "generic MFCC kernel");
 	/* the tables are freed when this function returns: wait for the kernel (a generality path, not a pipeline stage) */
 	ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return EDISON_OK;
 }
-
-struct gbuf
-{
-	void *p;
-	gbuf() : p(NULL) {}
-	~gbuf() { if (p) (void)hipFree(p); }
-	hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-};
 
 extern "C" int edison_mfcc_generic(edison_ctx *ctx, const int16_t *audio, int64_t n_frames, int frame_len, int64_t frame_step, int variant, int mel_nbins,
                                    double sample_rate, double lower_edge_hertz, double upper_edge_hertz, double mel_mtx_scale, double *fft, double *spec,
@@ -131,28 +119,13 @@ extern "C" int edison_mfcc_generic(edison_ctx *ctx, const int16_t *audio, int64_
 	if (!ctx || (!audio && n_frames > 0)) return EDISON_E_ARGUMENT;
 	{ const int r = check_geometry(ctx, n_frames, frame_len, frame_step, variant, mel_nbins, sample_rate, lower_edge_hertz, upper_edge_hertz, mel_mtx_scale, n_coef); if (r != EDISON_OK) return r; }
 	if (n_frames == 0) return EDISON_OK;
-	ED_HIP(ctx, hipSetDevice(ctx->device));
-	const size_t n = (size_t)n_frames, na = ((size_t)(n_frames - 1) * (size_t)frame_step + (size_t)frame_len) * sizeof(int16_t);
-	const size_t fo = (size_t)((variant & 0xff) == EDISON_MFCC_A ? frame_len / 2 : ((variant & 0xff) == EDISON_MFCC_B ? frame_len : frame_len / 2 + 1));
-	gbuf a, f, s, m, l, c, q;
-	ED_HIP(ctx, a.alloc(na));
-	if (fft) ED_HIP(ctx, f.alloc(n * fo * 2 * sizeof(double)));
-	if (spec) ED_HIP(ctx, s.alloc(n * fo * sizeof(double)));
-	if (mel) ED_HIP(ctx, m.alloc(n * mel_nbins * sizeof(double)));
-	if (logmel) ED_HIP(ctx, l.alloc(n * mel_nbins * sizeof(double)));
-	if (mfcc) ED_HIP(ctx, c.alloc(n * mel_nbins * sizeof(double)));
-	if (feat) ED_HIP(ctx, q.alloc(n * (size_t)(n_coef > 0 ? n_coef : 1)));
-	ED_HIP(ctx, hipMemcpyAsync(a.p, audio, na, hipMemcpyHostToDevice, ctx->stream));
-	const int r = edison_mfcc_generic_dev(ctx, (const int16_t *)a.p, n_frames, frame_len, frame_step, variant, mel_nbins, sample_rate, lower_edge_hertz,
-	                                      upper_edge_hertz, mel_mtx_scale, (double *)f.p, (double *)s.p, (double *)m.p, (double *)l.p, (double *)c.p, n_coef,
-	                                      (int8_t *)q.p, feat_scale);
-	if (r != EDISON_OK) return r;
-	if (fft) ED_HIP(ctx, hipMemcpyAsync(fft, f.p, n * fo * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	if (spec) ED_HIP(ctx, hipMemcpyAsync(spec, s.p, n * fo * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	if (mel) ED_HIP(ctx, hipMemcpyAsync(mel, m.p, n * mel_nbins * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	if (logmel) ED_HIP(ctx, hipMemcpyAsync(logmel, l.p, n * mel_nbins * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	if (mfcc) ED_HIP(ctx, hipMemcpyAsync(mfcc, c.p, n * mel_nbins * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	if (feat) ED_HIP(ctx, hipMemcpyAsync(feat, q.p, n * (size_t)n_coef, hipMemcpyDeviceToHost, ctx->stream));
-	ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return EDISON_OK;
+	const size_t n = (size_t)n_frames, nm = n * mel_nbins;
+	const size_t fo = n * (size_t)((variant & 0xff) == EDISON_MFCC_A ? frame_len / 2 : ((variant & 0xff) == EDISON_MFCC_B ? frame_len : frame_len / 2 + 1));
+	ed_staging st(ctx);
+	const int16_t *a = st.in(audio, (size_t)(n_frames - 1) * (size_t)frame_step + (size_t)frame_len);
+	double *f = st.out(fft, fo * 2), *s = st.out(spec, fo), *m = st.out(mel, nm), *l = st.out(logmel, nm), *c = st.out(mfcc, nm);
+	int8_t *q = st.out(feat, n * (size_t)n_coef);
+	return st.finish(st.ok() ? edison_mfcc_generic_dev(ctx, a, n_frames, frame_len, frame_step, variant, mel_nbins, sample_rate, lower_edge_hertz,
+	                                                   upper_edge_hertz, mel_mtx_scale, f, s, m, l, c, n_coef, q, feat_scale)
+	                         : EDISON_OK);
 }

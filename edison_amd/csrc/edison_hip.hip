@@ -11,7 +11,12 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
+#include <mutex>
+#include <new>
+
 #include "edison_ctx.h"
+#include "edison_launch.h"
 
 static char g_init_err[512] = "";
 
@@ -368,27 +373,118 @@ static int ensure_scratch(edison_ctx *ctx, size_t bytes)
 	return EDISON_OK;
 }
 
-/* ---------------------------------------------------------------------------------------- hot path, device */
-static int mfcc_launch_on(edison_ctx *ctx, hipStream_t stream, const int16_t *audio, int64_t n_frames, int64_t fpg, int64_t group_stride,
-                          int64_t frame_step, int variant, int n_coef, float *mfcc, int8_t *feat, float feat_scale,
-                          int stages, float *fft, float *spec, float *mel, float *logmel);
-
-/* on the context's current stream */
-static int mfcc_launch(edison_ctx *ctx, const int16_t *audio, int64_t n_frames, int64_t fpg, int64_t group_stride,
-                       int64_t frame_step, int variant, int n_coef, float *mfcc, int8_t *feat, float feat_scale,
-                       int stages, float *fft, float *spec, float *mel, float *logmel)
+/* ---------------------------------------------------------------------------------------- host-pointer staging */
+ed_staging::ed_staging(edison_ctx *c) : ctx(c)
 {
-	if (!ctx) return EDISON_E_ARGUMENT;
-	return mfcc_launch_on(ctx, ctx->stream, audio, n_frames, fpg, group_stride, frame_step, variant, n_coef, mfcc, feat, feat_scale,
-	                      stages, fft, spec, mel, logmel);
+	const hipError_t e = hipSetDevice(ctx->device);
+	if (e != hipSuccess) fail(e, "hipSetDevice");
 }
 
+int ed_staging::fail(hipError_t e, const char *what)
+{
+	snprintf(ctx->err, sizeof(ctx->err), "%s failed: %s (host-pointer staging)", what, hipGetErrorString(e));
+	return err = EDISON_E_RUNTIME;
+}
+
+void *ed_staging::stage(const void *up, void *down, size_t bytes)
+{
+	if (err != EDISON_OK) return NULL;
+	if (n == (int)(sizeof(buf) / sizeof(buf[0]))) { err = set_err(ctx, EDISON_E_RUNTIME, "ed_staging: too many buffers"); return NULL; }
+	auto &b = buf[n++];
+	b.down = down;
+	b.bytes = bytes;
+	hipError_t e = b.d.alloc(bytes);
+	if (e != hipSuccess) { fail(e, "hipMalloc"); return NULL; }
+	if (up && (e = hipMemcpyAsync(b.d.p, up, bytes, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) { fail(e, "hipMemcpyAsync (upload)"); return NULL; }
+	return b.d.p;
+}
+
+int ed_staging::finish(int r)
+{
+	if (err != EDISON_OK) r = err;
+	for (int i = 0; i < n && r == EDISON_OK; i++)
+		if (buf[i].down)
+		{
+			const hipError_t e = hipMemcpyAsync(buf[i].down, buf[i].d.p, buf[i].bytes, hipMemcpyDeviceToHost, ctx->stream);
+			if (e != hipSuccess) r = fail(e, "hipMemcpyAsync (download)");
+		}
+	/* the device may still be reading the caller's input or writing its outputs: once anything was staged, never return before
+	 * the stream has drained */
+	if (n > 0)
+	{
+		const hipError_t e = hipStreamSynchronize(ctx->stream);
+		if (e != hipSuccess && r == EDISON_OK) r = fail(e, "hipStreamSynchronize");
+	}
+	return r;
+}
+
+/* ---------------------------------------------------------------------------------------- kernel launch preparation */
+/* What ed_kernel_prepare (edison_launch.h) knows per (function, device): a hash of append-only lists. An entry is published
+ * complete (release) under the mutex and never freed; its two values only grow, so a reader without the lock sees either the
+ * old value (and takes the lock) or the new one. */
+namespace {
+struct prep_entry
+{
+	const void *fn;
+	int device;
+	std::atomic<size_t> lds;          /* the dynamic-LDS limit raised so far */
+	std::atomic<int> blocks_per_cu;   /* 0: not computed yet */
+	prep_entry *next;
+};
+} // namespace
+static std::atomic<prep_entry *> g_prep[64];
+static std::mutex g_prep_mu;
+
+int ed_kernel_prepare(const void *fn, int threads, size_t lds_bytes, const char *cap_env, int *blocks_per_cu)
+{
+	int dev = 0;
+	(void)hipGetDevice(&dev);
+	std::atomic<prep_entry *> &head = g_prep[((uintptr_t)fn >> 4 ^ (uintptr_t)dev * 0x9e3779b9u) % 64];
+	auto find = [&](prep_entry *p) { while (p && (p->fn != fn || p->device != dev)) p = p->next; return p; };
+	prep_entry *p = find(head.load(std::memory_order_acquire));
+	if (p && p->lds.load(std::memory_order_acquire) >= lds_bytes && (!blocks_per_cu || p->blocks_per_cu.load(std::memory_order_acquire) > 0))
+	{
+		if (blocks_per_cu) *blocks_per_cu = p->blocks_per_cu.load(std::memory_order_relaxed);
+		return hipSuccess;
+	}
+	std::lock_guard<std::mutex> lock(g_prep_mu);
+	p = find(head.load(std::memory_order_relaxed));
+	if (!p)
+	{
+		p = new (std::nothrow) prep_entry{fn, dev, {0}, {0}, head.load(std::memory_order_relaxed)};
+		if (!p) return hipErrorOutOfMemory;
+		head.store(p, std::memory_order_release);
+	}
+	if (lds_bytes > p->lds.load(std::memory_order_relaxed))
+	{
+		const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+		if (e != hipSuccess) { (void)hipGetLastError(); return e; }
+		p->lds.store(lds_bytes, std::memory_order_release);
+	}
+	if (blocks_per_cu)
+	{
+		int nb = p->blocks_per_cu.load(std::memory_order_relaxed);
+		if (nb <= 0)
+		{
+			if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, threads, lds_bytes) != hipSuccess || nb < 1) nb = 1;
+			const char *env = cap_env ? getenv(cap_env) : NULL; /* tuning knob: cap the persistent grid */
+			if (env && atoi(env) > 0 && atoi(env) < nb) nb = atoi(env);
+			p->blocks_per_cu.store(nb, std::memory_order_release);
+		}
+		*blocks_per_cu = nb;
+	}
+	return hipSuccess;
+}
+
+/* ---------------------------------------------------------------------------------------- hot path, device */
+/* on the context's current stream */
 int ed_ctx_mfcc_launch(edison_ctx *ctx, const int16_t *audio, int64_t n_frames, int64_t fpg, int64_t group_stride,
                        int64_t frame_step, int variant, int n_coef, float *mfcc, int8_t *feat, float feat_scale,
                        int stages, float *fft, float *spec, float *mel, float *logmel)
 {
-	return mfcc_launch(ctx, audio, n_frames, fpg, group_stride, frame_step, variant, n_coef, mfcc, feat, feat_scale,
-	                   stages, fft, spec, mel, logmel);
+	if (!ctx) return EDISON_E_ARGUMENT;
+	return ed_ctx_mfcc_launch_on(ctx, ctx->stream, audio, n_frames, fpg, group_stride, frame_step, variant, n_coef, mfcc, feat, feat_scale,
+	                             stages, fft, spec, mel, logmel);
 }
 
 /* The one-frame microphone push in ONE launch (ed_kws1_kernel, cnn_mfma_kernels.hip): the MFCC (variant A / B, 13 int8 features,
@@ -410,25 +506,12 @@ int ed_ctx_kws1_launch_on(edison_ctx *ctx, hipStream_t stream, const int16_t *au
 	a.feat = feat_row; a.feat_scale = 1.0f;
 	const int e = ed_launch_kws1(&a, ctx->d_tab[v], ctx->d_model_mfma, window, logits, softmax, argmax, flag, seq, filter, stream);
 	if (e == (int)hipErrorInvalidValue) return EDISON_E_NO_IMPL;
-	if (e != 0)
-	{
-		snprintf(ctx->err, sizeof(ctx->err), "one-frame KWS kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-		return EDISON_E_RUNTIME;
-	}
-	return EDISON_OK;
+	return ed_launch_result(ctx, e, "one-frame KWS kernel");
 }
 
 /* the same on an explicit stream (edison_stream.hip: a stream object launches on its private stream without touching
  * ctx->stream, which another thread's call on the context may be reading) */
 int ed_ctx_mfcc_launch_on(edison_ctx *ctx, hipStream_t stream, const int16_t *audio, int64_t n_frames, int64_t fpg, int64_t group_stride,
-                          int64_t frame_step, int variant, int n_coef, float *mfcc, int8_t *feat, float feat_scale,
-                          int stages, float *fft, float *spec, float *mel, float *logmel)
-{
-	return mfcc_launch_on(ctx, stream, audio, n_frames, fpg, group_stride, frame_step, variant, n_coef, mfcc, feat, feat_scale,
-	                      stages, fft, spec, mel, logmel);
-}
-
-static int mfcc_launch_on(edison_ctx *ctx, hipStream_t stream, const int16_t *audio, int64_t n_frames, int64_t fpg, int64_t group_stride,
                           int64_t frame_step, int variant, int n_coef, float *mfcc, int8_t *feat, float feat_scale,
                           int stages, float *fft, float *spec, float *mel, float *logmel)
 {
@@ -460,19 +543,14 @@ static int mfcc_launch_on(edison_ctx *ctx, hipStream_t stream, const int16_t *au
 	a.fft = fft; a.spec = spec; a.mel = mel; a.logmel = logmel;
 	a.window = v == EDISON_MFCC_TF;
 	int e = ed_launch_mfcc(&a, ctx->d_tab[ti], stages, ctx->n_cu, stream);
-	if (e != 0)
-	{
-		snprintf(ctx->err, sizeof(ctx->err), "MFCC kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-		return EDISON_E_RUNTIME;
-	}
-	return EDISON_OK;
+	return ed_launch_result(ctx, e, "MFCC kernel");
 }
 
 extern "C" int edison_mfcc_batch_dev(edison_ctx *ctx, const int16_t *audio, int64_t n_frames, int64_t frame_step,
                                      int variant, int n_coef, float *mfcc, int8_t *feat, float feat_scale)
 {
-	return mfcc_launch(ctx, audio, n_frames, n_frames > 0 ? n_frames : 1, 0, frame_step, variant, n_coef, mfcc, feat,
-	                   feat_scale, 0, NULL, NULL, NULL, NULL);
+	return ed_ctx_mfcc_launch(ctx, audio, n_frames, n_frames > 0 ? n_frames : 1, 0, frame_step, variant, n_coef, mfcc, feat,
+	                          feat_scale, 0, NULL, NULL, NULL, NULL);
 }
 
 extern "C" int edison_mfcc_rows_dev(edison_ctx *ctx, const int16_t *audio, int64_t n_rows, int64_t row_stride,
@@ -482,8 +560,8 @@ extern "C" int edison_mfcc_rows_dev(edison_ctx *ctx, const int16_t *audio, int64
 	if (!ctx || n_rows < 0 || frames_per_row < 0 || row_stride < 0) return EDISON_E_ARGUMENT;
 	if (n_rows == 0 || frames_per_row == 0) return EDISON_OK;
 	if (n_rows > INT32_MAX / frames_per_row) return set_err(ctx, EDISON_E_SIZE, "edison_mfcc_rows: more than 2^31 frames in one call");
-	return mfcc_launch(ctx, audio, n_rows * frames_per_row, frames_per_row, row_stride, frame_step, variant, n_coef, mfcc, feat,
-	                   feat_scale, 0, NULL, NULL, NULL, NULL);
+	return ed_ctx_mfcc_launch(ctx, audio, n_rows * frames_per_row, frames_per_row, row_stride, frame_step, variant, n_coef, mfcc, feat,
+	                          feat_scale, 0, NULL, NULL, NULL, NULL);
 }
 
 /* Up to 16 INDEPENDENT batches -- any addresses, own outputs -- per launch; more than 16 go out as several launches. Variants A, B
@@ -518,22 +596,10 @@ extern "C" int edison_mfcc_batches_dev(edison_ctx *ctx, int n_batches, const int
 		a.mel_NHI = ctx->mel_NHI[v];
 		a.mfcc = list.mfcc[0]; a.feat = list.feat[0]; a.feat_scale = feat_scale; /* flags: which outputs the launch writes */
 		const int e = ed_launch_mfcc_list(&a, &list, nb, ctx->d_tab[v], ctx->n_cu, ctx->stream);
-		if (e != 0)
-		{
-			snprintf(ctx->err, sizeof(ctx->err), "MFCC list kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-			return EDISON_E_RUNTIME;
-		}
+		if (e != 0) return ed_launch_result(ctx, e, "MFCC list kernel");
 	}
 	return EDISON_OK;
 }
-
-struct dev_buf
-{
-	void *p;
-	dev_buf() : p(NULL) {}
-	~dev_buf() { if (p) (void)hipFree(p); }
-	hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-};
 
 /* ---- two queues for independent batches: the NEXT launch is in flight while this one drains -------------------------------------
  * A 65 536-frame launch idles ~15 % of its window (256 workgroups starting up, waves leaving over the last pair time) and the next
@@ -611,7 +677,7 @@ static int pipe_time_pair(edison_ctx *ctx, hipStream_t a, hipStream_t b, const i
 		const int m = timed ? n : 6;
 		for (int i = 0; i < m; i++)
 		{
-			const int r = mfcc_launch_on(ctx, q[i & 1], audio, n_frames, n_frames, 0, frame_step, variant, EDISON_NUM_MFCC, out[i & 1], NULL, 1.0f, 0, NULL, NULL, NULL, NULL);
+			const int r = ed_ctx_mfcc_launch_on(ctx, q[i & 1], audio, n_frames, n_frames, 0, frame_step, variant, EDISON_NUM_MFCC, out[i & 1], NULL, 1.0f, 0, NULL, NULL, NULL, NULL);
 			if (r != EDISON_OK) return r;
 		}
 		for (int k = 0; k < 2; k++)
@@ -649,7 +715,7 @@ extern "C" int edison_queues_calibrate(edison_ctx *ctx, const int16_t *audio, in
 	const int v = variant & 0xff;
 	if (v != EDISON_MFCC_A && v != EDISON_MFCC_B) return set_err(ctx, EDISON_E_NO_IMPL, "edison_queues_calibrate: variants A and B");
 	{ const int r = pipe_setup(ctx); if (r != EDISON_OK) return r; }
-	dev_buf o0, o1;
+	ed_dev_buf o0, o1;
 	const size_t ob = (size_t)n_frames * EDISON_NUM_MFCC * sizeof(float);
 	ED_HIP(ctx, o0.alloc(ob));
 	ED_HIP(ctx, o1.alloc(ob));
@@ -720,15 +786,15 @@ extern "C" int edison_mfcc_batch_queue_dev(edison_ctx *ctx, int queue, const int
 {
 	if (!ctx || queue < 0 || queue > 1) return EDISON_E_ARGUMENT;
 	if (!ctx->pipe_forked) return set_err(ctx, EDISON_E_ARGUMENT, "edison_mfcc_batch_queue_dev outside edison_queues_fork ... edison_queues_join");
-	return mfcc_launch_on(ctx, ctx->pipe_q[queue], audio, n_frames, n_frames > 0 ? n_frames : 1, 0, frame_step, variant, n_coef, mfcc, feat, feat_scale,
-	                      0, NULL, NULL, NULL, NULL);
+	return ed_ctx_mfcc_launch_on(ctx, ctx->pipe_q[queue], audio, n_frames, n_frames > 0 ? n_frames : 1, 0, frame_step, variant, n_coef, mfcc, feat, feat_scale,
+	                             0, NULL, NULL, NULL, NULL);
 }
 
 extern "C" int edison_mfcc_stages_dev(edison_ctx *ctx, const int16_t *audio, int64_t n_frames, int64_t frame_step,
                                       int variant, float *fft, float *spec, float *mel, float *logmel, float *mfcc32)
 {
-	return mfcc_launch(ctx, audio, n_frames, n_frames > 0 ? n_frames : 1, 0, frame_step, variant, EDISON_NUM_MEL,
-	                   mfcc32, NULL, 1.0f, 1, fft, spec, mel, logmel);
+	return ed_ctx_mfcc_launch(ctx, audio, n_frames, n_frames > 0 ? n_frames : 1, 0, frame_step, variant, EDISON_NUM_MEL,
+	                          mfcc32, NULL, 1.0f, 1, fft, spec, mel, logmel);
 }
 
 static int kws_shaped(const ed_net_plan_t *p)
@@ -784,12 +850,7 @@ int ed_ctx_kws_cnn_launch_flag(edison_ctx *ctx, hipStream_t stream, const int8_t
 	int e = ctx->fast_model
 	            ? ed_launch_cnn_mfma_flag(ctx->d_model_mfma, feat, n_utt, feat_stride, logits, softmax, argmax, ctx->n_cu, stream, flag, seq, flag_written)
 	            : ed_ctx_net_launch_flag(ctx, stream, feat, n_utt, feat_stride, logits, softmax, argmax, flag, seq, flag_written);
-	if (e != 0)
-	{
-		snprintf(ctx->err, sizeof(ctx->err), "CNN kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-		return EDISON_E_RUNTIME;
-	}
-	return EDISON_OK;
+	return ed_launch_result(ctx, e, "CNN kernel");
 }
 
 static int cnn_launch(edison_ctx *ctx, const int8_t *feat, int64_t n_utt, int8_t *logits, int8_t *softmax,
@@ -803,12 +864,7 @@ static int cnn_launch(edison_ctx *ctx, const int8_t *feat, int64_t n_utt, int8_t
 	if (!ctx->fast_model)
 		return set_err(ctx, EDISON_E_SIZE, "edison_cnn_layers dumps the kws_conv layout; use edison_net_layers for this model");
 	int e = ed_launch_cnn(ctx->d_model, feat, n_utt, logits, softmax, argmax, acts, ctx->n_cu, ctx->stream);
-	if (e != 0)
-	{
-		snprintf(ctx->err, sizeof(ctx->err), "CNN kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-		return EDISON_E_RUNTIME;
-	}
-	return EDISON_OK;
+	return ed_launch_result(ctx, e, "CNN kernel");
 }
 
 extern "C" int edison_cnn_batch_dev(edison_ctx *ctx, const int8_t *feat, int64_t n_utt, int8_t *logits,
@@ -839,8 +895,8 @@ static int kws_dev(edison_ctx *ctx, const int16_t *audio, int64_t n_utt, int64_t
 		f = (int8_t *)ctx->scratch;
 	}
 	/* first 13 coefficients, scale 1 (nnom_net_input_scale, audio/config.py:41; NNOM_INPUT_SCALE, weights.h:162) */
-	int r = mfcc_launch(ctx, audio, n_utt * EDISON_UTT_FRAMES, EDISON_UTT_FRAMES, utt_stride, EDISON_FRAME_LEN,
-	                    variant, EDISON_NUM_MFCC, NULL, f, 1.0f, 0, NULL, NULL, NULL, NULL);
+	int r = ed_ctx_mfcc_launch(ctx, audio, n_utt * EDISON_UTT_FRAMES, EDISON_UTT_FRAMES, utt_stride, EDISON_FRAME_LEN,
+	                           variant, EDISON_NUM_MFCC, NULL, f, 1.0f, 0, NULL, NULL, NULL, NULL);
 	if (r != EDISON_OK) return r;
 	return cnn_launch(ctx, f, n_utt, logits, softmax, argmax, NULL);
 }
@@ -859,10 +915,6 @@ extern "C" int edison_kws_batch_q15_dev(edison_ctx *ctx, const int16_t *audio, i
 
 /* ---------------------------------------------------------------------------------------- hot path, host  */
 
-#define ED_UP(ctx, dst, src, n) ED_HIP(ctx, hipMemcpyAsync((dst), (src), (n), hipMemcpyHostToDevice, (ctx)->stream))
-#define ED_DOWN(ctx, dst, src, n) \
-	do { if (dst) ED_HIP(ctx, hipMemcpyAsync((dst), (src), (n), hipMemcpyDeviceToHost, (ctx)->stream)); } while (0)
-
 static size_t audio_span(int64_t n_frames, int64_t frame_step) { return (size_t)((n_frames - 1) * frame_step + EDISON_FRAME_LEN); }
 
 extern "C" int edison_mfcc_batch(edison_ctx *ctx, const int16_t *audio, int64_t n_frames, int64_t frame_step,
@@ -871,20 +923,12 @@ extern "C" int edison_mfcc_batch(edison_ctx *ctx, const int16_t *audio, int64_t 
 	if (!ctx || n_frames < 0 || (!audio && n_frames > 0) || frame_step < 0) return EDISON_E_ARGUMENT;
 	if (n_frames == 0) return EDISON_OK;
 	if (n_coef < 1 || n_coef > EDISON_NUM_MEL) return set_err(ctx, EDISON_E_ARGUMENT, "n_coef must be 1..32");
-	ED_HIP(ctx, hipSetDevice(ctx->device));
-	dev_buf a, m, q;
-	const size_t na = audio_span(n_frames, frame_step) * sizeof(int16_t);
-	ED_HIP(ctx, a.alloc(na));
-	if (mfcc) ED_HIP(ctx, m.alloc((size_t)n_frames * n_coef * sizeof(float)));
-	if (feat) ED_HIP(ctx, q.alloc((size_t)n_frames * n_coef));
-	ED_UP(ctx, a.p, audio, na);
-	int r = edison_mfcc_batch_dev(ctx, (const int16_t *)a.p, n_frames, frame_step, variant, n_coef, (float *)m.p,
-	                              (int8_t *)q.p, feat_scale);
-	if (r != EDISON_OK) return r;
-	ED_DOWN(ctx, mfcc, m.p, (size_t)n_frames * n_coef * sizeof(float));
-	ED_DOWN(ctx, feat, q.p, (size_t)n_frames * n_coef);
-	ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return EDISON_OK;
+	ed_staging st(ctx);
+	const size_t n = (size_t)n_frames * n_coef;
+	const int16_t *a = st.in(audio, audio_span(n_frames, frame_step));
+	float *m = st.out(mfcc, n);
+	int8_t *q = st.out(feat, n);
+	return st.finish(st.ok() ? edison_mfcc_batch_dev(ctx, a, n_frames, frame_step, variant, n_coef, m, q, feat_scale) : EDISON_OK);
 }
 
 extern "C" int edison_mfcc_rows(edison_ctx *ctx, const int16_t *audio, int64_t n_rows, int64_t row_stride, int64_t frames_per_row,
@@ -896,24 +940,14 @@ extern "C" int edison_mfcc_rows(edison_ctx *ctx, const int16_t *audio, int64_t n
 	if (n_rows > INT32_MAX / frames_per_row) return set_err(ctx, EDISON_E_SIZE, "edison_mfcc_rows: more than 2^31 frames in one call");
 	/* the staging buffer spans (n_rows - 1) * row_stride + the frames of one row: computed in 128 bits, refused beyond 2^46
 	 * samples (a wrapped size_t would allocate a small buffer and let the kernel read past it) */
-	const size_t span = audio_span(frames_per_row, frame_step);
-	const unsigned __int128 na128 = ((unsigned __int128)(n_rows - 1) * (unsigned __int128)row_stride + span) * sizeof(int16_t);
-	if (na128 > ((unsigned __int128)1 << 47)) return set_err(ctx, EDISON_E_SIZE, "edison_mfcc_rows: row_stride x n_rows too large");
-	ED_HIP(ctx, hipSetDevice(ctx->device));
-	dev_buf a, m, q;
-	const size_t n = (size_t)(n_rows * frames_per_row);
-	const size_t na = (size_t)na128;
-	ED_HIP(ctx, a.alloc(na));
-	if (mfcc) ED_HIP(ctx, m.alloc(n * n_coef * sizeof(float)));
-	if (feat) ED_HIP(ctx, q.alloc(n * n_coef));
-	ED_UP(ctx, a.p, audio, na);
-	int r = edison_mfcc_rows_dev(ctx, (const int16_t *)a.p, n_rows, row_stride, frames_per_row, frame_step, variant, n_coef,
-	                             (float *)m.p, (int8_t *)q.p, feat_scale);
-	if (r != EDISON_OK) return r;
-	ED_DOWN(ctx, mfcc, m.p, n * n_coef * sizeof(float));
-	ED_DOWN(ctx, feat, q.p, n * n_coef);
-	ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return EDISON_OK;
+	const unsigned __int128 na128 = (unsigned __int128)(n_rows - 1) * (unsigned __int128)row_stride + audio_span(frames_per_row, frame_step);
+	if (na128 * sizeof(int16_t) > ((unsigned __int128)1 << 47)) return set_err(ctx, EDISON_E_SIZE, "edison_mfcc_rows: row_stride x n_rows too large");
+	ed_staging st(ctx);
+	const size_t n = (size_t)(n_rows * frames_per_row) * n_coef;
+	const int16_t *a = st.in(audio, (size_t)na128);
+	float *m = st.out(mfcc, n);
+	int8_t *q = st.out(feat, n);
+	return st.finish(st.ok() ? edison_mfcc_rows_dev(ctx, a, n_rows, row_stride, frames_per_row, frame_step, variant, n_coef, m, q, feat_scale) : EDISON_OK);
 }
 
 extern "C" int edison_mfcc_stages(edison_ctx *ctx, const int16_t *audio, int64_t n_frames, int64_t frame_step,
@@ -921,26 +955,11 @@ extern "C" int edison_mfcc_stages(edison_ctx *ctx, const int16_t *audio, int64_t
 {
 	if (!ctx || n_frames < 0 || (!audio && n_frames > 0) || frame_step < 0) return EDISON_E_ARGUMENT;
 	if (n_frames == 0) return EDISON_OK;
-	ED_HIP(ctx, hipSetDevice(ctx->device));
-	dev_buf a, f, s, m, l, c;
-	const size_t na = audio_span(n_frames, frame_step) * sizeof(int16_t), n = (size_t)n_frames;
-	ED_HIP(ctx, a.alloc(na));
-	if (fft) ED_HIP(ctx, f.alloc(n * 513 * 2 * sizeof(float)));
-	if (spec) ED_HIP(ctx, s.alloc(n * 513 * sizeof(float)));
-	if (mel) ED_HIP(ctx, m.alloc(n * 32 * sizeof(float)));
-	if (logmel) ED_HIP(ctx, l.alloc(n * 32 * sizeof(float)));
-	if (mfcc32) ED_HIP(ctx, c.alloc(n * 32 * sizeof(float)));
-	ED_UP(ctx, a.p, audio, na);
-	int r = edison_mfcc_stages_dev(ctx, (const int16_t *)a.p, n_frames, frame_step, variant, (float *)f.p, (float *)s.p,
-	                               (float *)m.p, (float *)l.p, (float *)c.p);
-	if (r != EDISON_OK) return r;
-	ED_DOWN(ctx, fft, f.p, n * 513 * 2 * sizeof(float));
-	ED_DOWN(ctx, spec, s.p, n * 513 * sizeof(float));
-	ED_DOWN(ctx, mel, m.p, n * 32 * sizeof(float));
-	ED_DOWN(ctx, logmel, l.p, n * 32 * sizeof(float));
-	ED_DOWN(ctx, mfcc32, c.p, n * 32 * sizeof(float));
-	ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return EDISON_OK;
+	ed_staging st(ctx);
+	const size_t n = (size_t)n_frames;
+	const int16_t *a = st.in(audio, audio_span(n_frames, frame_step));
+	float *f = st.out(fft, n * 513 * 2), *s = st.out(spec, n * 513), *m = st.out(mel, n * 32), *l = st.out(logmel, n * 32), *c = st.out(mfcc32, n * 32);
+	return st.finish(st.ok() ? edison_mfcc_stages_dev(ctx, a, n_frames, frame_step, variant, f, s, m, l, c) : EDISON_OK);
 }
 
 static int cnn_host(edison_ctx *ctx, const int8_t *feat, int64_t n_utt, int8_t *logits, int8_t *softmax,
@@ -949,25 +968,13 @@ static int cnn_host(edison_ctx *ctx, const int8_t *feat, int64_t n_utt, int8_t *
 	if (!ctx || n_utt < 0 || (!feat && n_utt > 0)) return EDISON_E_ARGUMENT;
 	if (!ctx->have_model) return set_err(ctx, EDISON_E_NO_MODEL, "no CNN model loaded (edison_model_load)");
 	if (n_utt == 0) return EDISON_OK;
-	ED_HIP(ctx, hipSetDevice(ctx->device));
-	dev_buf f, l, s, a, t;
+	ed_staging st(ctx);
 	const size_t n = (size_t)n_utt;
-	ED_HIP(ctx, f.alloc(n * EDISON_NET_IN));
-	if (logits) ED_HIP(ctx, l.alloc(n * EDISON_NET_OUT));
-	if (softmax) ED_HIP(ctx, s.alloc(n * EDISON_NET_OUT));
-	if (argmax) ED_HIP(ctx, a.alloc(n * sizeof(int32_t)));
-	if (acts) ED_HIP(ctx, t.alloc(n * EDISON_CNN_ACT_BYTES));
-	ED_UP(ctx, f.p, feat, n * EDISON_NET_IN);
-	int r = cnn_launch(ctx, (const int8_t *)f.p, n_utt, (int8_t *)l.p, (int8_t *)s.p, (int32_t *)a.p, (int8_t *)t.p);
-	if (r != EDISON_OK) return r;
-	ED_DOWN(ctx, logits, l.p, n * EDISON_NET_OUT);
-	ED_DOWN(ctx, softmax, s.p, n * EDISON_NET_OUT);
-	ED_DOWN(ctx, argmax, a.p, n * sizeof(int32_t));
-	ED_DOWN(ctx, acts, t.p, n * EDISON_CNN_ACT_BYTES);
-	ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return EDISON_OK;
+	const int8_t *f = st.in(feat, n * EDISON_NET_IN);
+	int8_t *l = st.out(logits, n * EDISON_NET_OUT), *s = st.out(softmax, n * EDISON_NET_OUT), *t = st.out(acts, n * EDISON_CNN_ACT_BYTES);
+	int32_t *a = st.out(argmax, n);
+	return st.finish(st.ok() ? cnn_launch(ctx, f, n_utt, l, s, a, t) : EDISON_OK);
 }
-
 extern "C" int edison_cnn_batch(edison_ctx *ctx, const int8_t *feat, int64_t n_utt, int8_t *logits, int8_t *softmax,
                                 int32_t *argmax)
 {
@@ -985,25 +992,12 @@ static int kws_host(edison_ctx *ctx, const int16_t *audio, int64_t n_utt, int64_
 {
 	if (!ctx || n_utt < 0 || (!audio && n_utt > 0) || utt_stride < 0) return EDISON_E_ARGUMENT;
 	if (n_utt == 0) return EDISON_OK;
-	ED_HIP(ctx, hipSetDevice(ctx->device));
-	dev_buf au, f, l, s, a;
+	ed_staging st(ctx);
 	const size_t n = (size_t)n_utt;
-	const size_t na = ((size_t)(n_utt - 1) * (size_t)utt_stride + (size_t)EDISON_UTT_FRAMES * EDISON_FRAME_LEN) * sizeof(int16_t);
-	ED_HIP(ctx, au.alloc(na));
-	ED_HIP(ctx, f.alloc(n * EDISON_NET_IN));
-	if (logits) ED_HIP(ctx, l.alloc(n * EDISON_NET_OUT));
-	if (softmax) ED_HIP(ctx, s.alloc(n * EDISON_NET_OUT));
-	if (argmax) ED_HIP(ctx, a.alloc(n * sizeof(int32_t)));
-	ED_UP(ctx, au.p, audio, na);
-	int r = kws_dev(ctx, (const int16_t *)au.p, n_utt, utt_stride, variant, (int8_t *)f.p, (int8_t *)l.p, (int8_t *)s.p,
-	                (int32_t *)a.p);
-	if (r != EDISON_OK) return r;
-	ED_DOWN(ctx, feat, f.p, n * EDISON_NET_IN);
-	ED_DOWN(ctx, logits, l.p, n * EDISON_NET_OUT);
-	ED_DOWN(ctx, softmax, s.p, n * EDISON_NET_OUT);
-	ED_DOWN(ctx, argmax, a.p, n * sizeof(int32_t));
-	ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return EDISON_OK;
+	const int16_t *au = st.in(audio, (size_t)(n_utt - 1) * (size_t)utt_stride + (size_t)EDISON_UTT_FRAMES * EDISON_FRAME_LEN);
+	int8_t *f = st.scratch(feat, n * EDISON_NET_IN), *l = st.out(logits, n * EDISON_NET_OUT), *s = st.out(softmax, n * EDISON_NET_OUT);
+	int32_t *a = st.out(argmax, n);
+	return st.finish(st.ok() ? kws_dev(ctx, au, n_utt, utt_stride, variant, f, l, s, a) : EDISON_OK);
 }
 
 extern "C" int edison_kws_batch(edison_ctx *ctx, const int16_t *audio, int64_t n_utt, int64_t utt_stride,

@@ -48,12 +48,7 @@ static int net_launch(edison_ctx *ctx, const int8_t *in, int64_t n, int8_t *logi
 	int e = acts ? ed_launch_net(ctx->d_net_plan, ctx->d_net_w, ctx->d_net_seeds, ctx->net.lds_bytes, in, n, ctx->net.in_n, logits, softmax,
 	                             argmax, acts, ctx->n_cu, ctx->stream)
 	             : ed_ctx_net_launch(ctx, in, n, ctx->net.in_n, logits, softmax, argmax);
-	if (e != 0)
-	{
-		snprintf(ctx->err, sizeof(ctx->err), "network kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-		return EDISON_E_RUNTIME;
-	}
-	return EDISON_OK;
+	return ed_launch_result(ctx, e, "network kernel");
 }
 
 extern "C" int edison_net_batch_dev(edison_ctx *ctx, const int8_t *in, int64_t n, int8_t *logits, int8_t *softmax, int32_t *argmax)
@@ -67,39 +62,17 @@ extern "C" int edison_net_layers_dev(edison_ctx *ctx, const int8_t *in, int64_t 
 	return net_launch(ctx, in, n, NULL, NULL, NULL, acts, 0);
 }
 
-namespace
-{
-struct net_buf
-{
-	void *p;
-	net_buf() : p(NULL) {}
-	~net_buf() { if (p) (void)hipFree(p); }
-	hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-};
-} // namespace
-
 static int net_host(edison_ctx *ctx, const int8_t *in, int64_t n, int8_t *logits, int8_t *softmax, int32_t *argmax, int8_t *acts)
 {
 	if (!ctx || n < 0 || (!in && n > 0)) return EDISON_E_ARGUMENT;
 	if (!ctx->have_model) return ed_set_err(ctx, EDISON_E_NO_MODEL, "no CNN model loaded (edison_model_load)");
 	if (n == 0) return EDISON_OK;
-	ED_HIP(ctx, hipSetDevice(ctx->device));
-	const size_t cnt = (size_t)n, in_n = (size_t)ctx->net.in_n, out_n = (size_t)ctx->net.out_n, acts_n = (size_t)ctx->net.acts_bytes;
-	net_buf f, l, s, a, t;
-	ED_HIP(ctx, f.alloc(cnt * in_n));
-	if (logits) ED_HIP(ctx, l.alloc(cnt * out_n));
-	if (softmax) ED_HIP(ctx, s.alloc(cnt * out_n));
-	if (argmax) ED_HIP(ctx, a.alloc(cnt * sizeof(int32_t)));
-	if (acts) ED_HIP(ctx, t.alloc(cnt * acts_n));
-	ED_HIP(ctx, hipMemcpyAsync(f.p, in, cnt * in_n, hipMemcpyHostToDevice, ctx->stream));
-	int r = net_launch(ctx, (const int8_t *)f.p, n, (int8_t *)l.p, (int8_t *)s.p, (int32_t *)a.p, (int8_t *)t.p, acts == NULL);
-	if (r != EDISON_OK) return r;
-	if (logits) ED_HIP(ctx, hipMemcpyAsync(logits, l.p, cnt * out_n, hipMemcpyDeviceToHost, ctx->stream));
-	if (softmax) ED_HIP(ctx, hipMemcpyAsync(softmax, s.p, cnt * out_n, hipMemcpyDeviceToHost, ctx->stream));
-	if (argmax) ED_HIP(ctx, hipMemcpyAsync(argmax, a.p, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-	if (acts) ED_HIP(ctx, hipMemcpyAsync(acts, t.p, cnt * acts_n, hipMemcpyDeviceToHost, ctx->stream));
-	ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return EDISON_OK;
+	const size_t cnt = (size_t)n, out_n = (size_t)ctx->net.out_n;
+	ed_staging st(ctx);
+	const int8_t *f = st.in(in, cnt * (size_t)ctx->net.in_n);
+	int8_t *l = st.out(logits, cnt * out_n), *s = st.out(softmax, cnt * out_n), *t = st.out(acts, cnt * (size_t)ctx->net.acts_bytes);
+	int32_t *a = st.out(argmax, cnt);
+	return st.finish(st.ok() ? net_launch(ctx, f, n, l, s, a, t, acts == NULL) : EDISON_OK);
 }
 
 extern "C" int edison_net_batch(edison_ctx *ctx, const int8_t *in, int64_t n, int8_t *logits, int8_t *softmax, int32_t *argmax)

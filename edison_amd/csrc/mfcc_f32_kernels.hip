@@ -19,6 +19,7 @@
 
 #include "../../include/edison_hip.h"
 #include "edison_internal.h"
+#include "edison_launch.h"
 
 #define EF_WPB 4
 
@@ -371,16 +372,7 @@ extern "C" int ed_launch_mfcc_f32_fast(const ed_mfcc_f32_args_t *args, const ed_
 {
 	if (args->n_frames <= 0) return 0;
 	const size_t lds = sizeof(float) * (EF2_TAB_FLOATS + EF2_WPB * EF2_XBUF_FLOATS) + 16;
-	static int ready_dev[16]; /* per device: the attribute belongs to the function on the current device */
-	int dev_ = 0;
-	(void)hipGetDevice(&dev_);
-	int &ready = ready_dev[dev_ & 15];
-	if (!ready)
-	{
-		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ed_mfcc_f32_fast_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		if (e != hipSuccess) return (int)e;
-		ready = 1;
-	}
+	{ const int e = ed_kernel_prepare((const void *)ed_mfcc_f32_fast_kernel, 64 * EF2_WPB, lds, NULL, NULL); if (e) return e; }
 	const int64_t n_pairs = (args->n_frames + 1) / 2;
 	int64_t blocks = (n_pairs + EF2_WPB - 1) / EF2_WPB;
 	if (blocks > n_cu) blocks = n_cu;

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "edison_internal.h"
+#include "edison_launch.h"
 
 __global__ __launch_bounds__(256) void ed_mfcc_generic_kernel(ed_mfcc_gen_args_t a)
 {
@@ -108,15 +109,9 @@ extern "C" int ed_launch_mfcc_generic(const ed_mfcc_gen_args_t *a, int n_cu, hip
 	const int N = a->frame_len;
 	if (N < 2 || N > ED_GEN_MAX_FRAME || a->n_mel < 1 || a->n_mel > ED_GEN_MAX_MEL) return (int)hipErrorInvalidValue;
 	const size_t lds = sizeof(double) * ((size_t)N + 2 * (size_t)N + 3 * ((size_t)N / 2 + 1) + (size_t)a->n_mel);
-	static bool attr_set[16];
-	int dev_ = 0;
-	(void)hipGetDevice(&dev_);
-	if (!attr_set[dev_ & 15])
-	{
-		if (hipFuncSetAttribute((const void *)ed_mfcc_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * (3 * ED_GEN_MAX_FRAME + 3 * (ED_GEN_MAX_FRAME / 2 + 1) + ED_GEN_MAX_MEL))) != hipSuccess)
-			return (int)hipGetLastError();
-		attr_set[dev_ & 15] = true;
-	}
+	/* raised once, to what the largest geometry needs */
+	const size_t lds_max = sizeof(double) * (3 * ED_GEN_MAX_FRAME + 3 * (ED_GEN_MAX_FRAME / 2 + 1) + ED_GEN_MAX_MEL);
+	{ const int e = ed_kernel_prepare((const void *)ed_mfcc_generic_kernel, 256, lds_max, NULL, NULL); if (e) return e; }
 	int64_t blocks = a->n_frames;
 	const int64_t cap = (int64_t)n_cu * 2;
 	if (blocks > cap) blocks = cap;

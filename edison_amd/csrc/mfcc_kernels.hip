@@ -41,6 +41,7 @@
 #include <hip/hip_ext.h>
 
 #include "edison_internal.h"
+#include "edison_launch.h"
 
 #include "mfcc_one_frame.h"
 
@@ -585,29 +586,15 @@ __global__ __launch_bounds__(64 * ED2_WPB) void ed_mfcc2_list_kernel(ed_mfcc_arg
 static int g_ed_lab_launch_flags = 0; /* lab: hipExtLaunchKernel flags of the fast path (hipExtAnyOrderLaunch = 1) */
 extern "C" void ed_lab_set_launch_flags(int f) { g_ed_lab_launch_flags = f; }
 #endif
-/* occupancy-derived grid sizes and "dynamic-LDS limit raised" flags, per DEVICE (0 = not asked yet; the attribute belongs to
- * the function on the current device, so two contexts on different GPUs of one process must each set it) */
-static int g_mfcc_blocks_per_cu[16][2];
-static int g_mfcc2_blocks_per_cu[16][16];
-
 template <int NLO, int NHI>
-static int ed_launch_mfcc_shape(const ed_mfcc_args_t *args, const ed_mfcc_tables_t *dev_tab, int stages, int n_cu,
-                                hipStream_t stream, int *blocks_per_cu)
+static int ed_launch_mfcc_shape(const ed_mfcc_args_t *args, const ed_mfcc_tables_t *dev_tab, int stages, int n_cu, hipStream_t stream)
 {
 	const size_t lds = sizeof(float) * (ED_FIXTAB_FLOATS + (NLO + NHI) * 256 + ED_WPB * ED_XBUF_FLOATS);
-	if (*blocks_per_cu <= 0)
-	{
-		/* persistent grid = exactly what is resident; sized once from the fast kernel's occupancy */
-		int nb = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ed_mfcc_kernel<false, true, NLO, NHI>, 64 * ED_WPB, lds) != hipSuccess || nb < 1)
-			nb = 1;
-		const char *env = getenv("ED_MFCC_BLOCKS_PER_CU"); /* tuning knob: cap the persistent grid */
-		if (env && atoi(env) > 0 && atoi(env) < nb) nb = atoi(env);
-		*blocks_per_cu = nb;
-	}
+	/* persistent grid = exactly what is resident; every one-frame instance is sized from the fast one's occupancy */
+	int blocks_per_cu = 1;
+	{ const int e = ed_kernel_prepare((const void *)ed_mfcc_kernel<false, true, NLO, NHI>, 64 * ED_WPB, lds, "ED_MFCC_BLOCKS_PER_CU", &blocks_per_cu); if (e) return e; }
 	int64_t blocks = (args->n_frames + ED_WPB - 1) / ED_WPB;
-	const int64_t cap = (int64_t)n_cu * *blocks_per_cu;
-	if (blocks > cap) blocks = cap;
+	if (blocks > (int64_t)n_cu * blocks_per_cu) blocks = (int64_t)n_cu * blocks_per_cu;
 	/* 4-byte loads need every frame start 4-byte aligned */
 	const bool aligned = ((reinterpret_cast<uintptr_t>(args->audio) & 3) == 0) && (args->frame_step % 2 == 0) &&
 	                     (args->group_stride % 2 == 0);
@@ -638,22 +625,11 @@ static int ed_launch_mfcc_shape(const ed_mfcc_args_t *args, const ed_mfcc_tables
 		if (args->window)
 			fn = aligned ? (plain ? (const void *)ed_mfcc2_window_kernel<true, true, NLO, NHI> : (const void *)ed_mfcc2_window_kernel<true, false, NLO, NHI>)
 			             : (plain ? (const void *)ed_mfcc2_window_kernel<false, true, NLO, NHI> : (const void *)ed_mfcc2_window_kernel<false, false, NLO, NHI>);
-		int dev_ = 0;
-		(void)hipGetDevice(&dev_);
-		int *bpc2 = &g_mfcc2_blocks_per_cu[dev_ & 15][(args->window ? 8 : 0) + (NLO == 2 ? 0 : 4) + (aligned ? 2 : 0) + (plain ? 1 : 0)];
-		if (*bpc2 <= 0)
-		{
-			/* more than 64 KB of dynamic LDS has to be asked for, once per kernel instance */
-			if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess) return (int)hipGetLastError();
-			int nb = 0;
-			if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * ED2_WPB, lds2) != hipSuccess || nb < 1) nb = 1;
-			const char *env = getenv("ED_MFCC_BLOCKS_PER_CU");
-			if (env && atoi(env) > 0 && atoi(env) < nb) nb = atoi(env);
-			*bpc2 = nb;
-		}
+		int bpc2 = 1;
+		{ const int e = ed_kernel_prepare(fn, 64 * ED2_WPB, lds2, "ED_MFCC_BLOCKS_PER_CU", &bpc2); if (e) return e; }
 		const int64_t n_pairs = (args->n_frames + 1) / 2;
 		int64_t blocks2 = (n_pairs + ED2_WPB - 1) / ED2_WPB;
-		if (blocks2 > (int64_t)n_cu * *bpc2) blocks2 = (int64_t)n_cu * *bpc2;
+		if (blocks2 > (int64_t)n_cu * bpc2) blocks2 = (int64_t)n_cu * bpc2;
 		void *kargs[] = {(void *)args, (void *)&dev_tab};
 #if defined(ED_LAB)
 		if (g_ed_lab_launch_flags)
@@ -675,8 +651,6 @@ static int ed_launch_mfcc_shape(const ed_mfcc_args_t *args, const ed_mfcc_tables
 	return (int)hipGetLastError();
 }
 
-static int g_mfcc2_list_blocks_per_cu[16][4];
-
 template <int NLO, int NHI>
 static int ed_launch_mfcc_list_shape(const ed_mfcc_args_t *args, const ed_mfcc_list_t *list, int n_batches, const ed_mfcc_tables_t *dev_tab, int n_cu, hipStream_t stream)
 {
@@ -684,19 +658,11 @@ static int ed_launch_mfcc_list_shape(const ed_mfcc_args_t *args, const ed_mfcc_l
 	bool aligned = args->frame_step % 2 == 0;
 	for (int b = 0; b < n_batches; b++) aligned = aligned && (reinterpret_cast<uintptr_t>(list->audio[b]) & 3) == 0;
 	const void *fn = aligned ? (const void *)ed_mfcc2_list_kernel<true, NLO, NHI> : (const void *)ed_mfcc2_list_kernel<false, NLO, NHI>;
-	int dev_ = 0;
-	(void)hipGetDevice(&dev_);
-	int *bpc = &g_mfcc2_list_blocks_per_cu[dev_ & 15][(NLO == 2 ? 0 : 2) + (aligned ? 1 : 0)];
-	if (*bpc <= 0)
-	{
-		if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess) return (int)hipGetLastError();
-		int nb = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * ED2_WPB, lds2) != hipSuccess || nb < 1) nb = 1;
-		*bpc = nb;
-	}
+	int bpc = 1;
+	{ const int e = ed_kernel_prepare(fn, 64 * ED2_WPB, lds2, NULL, &bpc); if (e) return e; } /* ED_MFCC_BLOCKS_PER_CU does not cap the list kernel */
 	const int64_t n_pairs = (args->n_frames + 1) / 2;
 	int64_t blocks = (n_pairs + ED2_WPB - 1) / ED2_WPB;
-	if (blocks > (int64_t)n_cu * *bpc) blocks = (int64_t)n_cu * *bpc;
+	if (blocks > (int64_t)n_cu * bpc) blocks = (int64_t)n_cu * bpc;
 	void *kargs[] = {(void *)args, (void *)&dev_tab, (void *)list};
 	return (int)hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64 * ED2_WPB), kargs, lds2, stream);
 }
@@ -719,13 +685,9 @@ extern "C" int ed_launch_mfcc(const ed_mfcc_args_t *args, const ed_mfcc_tables_t
                               hipStream_t stream)
 {
 	if (args->n_frames <= 0) return 0;
-	int dev_ = 0;
-	(void)hipGetDevice(&dev_);
-	dev_ &= 15;
 	/* the two table shapes tables.c produces */
-	if (args->mel_NLO == 2 && args->mel_NHI == 5)
-		return ed_launch_mfcc_shape<2, 5>(args, dev_tab, stages, n_cu, stream, &g_mfcc_blocks_per_cu[dev_][0]);
+	if (args->mel_NLO == 2 && args->mel_NHI == 5) return ed_launch_mfcc_shape<2, 5>(args, dev_tab, stages, n_cu, stream);
 	if (args->mel_NLO == ED_MEL_NLO_MAX && args->mel_NHI == ED_MEL_NHI_MAX)
-		return ed_launch_mfcc_shape<ED_MEL_NLO_MAX, ED_MEL_NHI_MAX>(args, dev_tab, stages, n_cu, stream, &g_mfcc_blocks_per_cu[dev_][1]);
+		return ed_launch_mfcc_shape<ED_MEL_NLO_MAX, ED_MEL_NHI_MAX>(args, dev_tab, stages, n_cu, stream);
 	return (int)hipErrorInvalidValue;
 }

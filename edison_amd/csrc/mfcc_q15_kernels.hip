@@ -37,6 +37,7 @@
 
 #include "../../include/edison_hip.h"
 #include "edison_internal.h"
+#include "edison_launch.h"
 
 /* ---- lab knobs: only a lab build (ED_LAB, tools/lab/mkvariant.py) may set them; the product build has none, and
  * tests/test_host_cpu.py checks the values below against what edison_amd/build.py compiles */
@@ -679,30 +680,18 @@ __global__ __launch_bounds__(64 * EQ_WPB) EQ_OCCUPANCY void ed_mfcc_q15_kernel(e
 	}
 }
 
-static int g_q15_blocks_per_cu[16][8]; /* per device (0 = not asked yet): the LDS attribute belongs to the function on the current device */
-
 template <int NLO, int NHI>
-static int ed_launch_q15_shape(const ed_mfcc_q15_args_t *args, const ed_q15_tables_t *dev_tab, int stages, int n_cu,
-                               hipStream_t stream, int *blocks_per_cu /* [4]: stages x aligned */)
+static int ed_launch_q15_shape(const ed_mfcc_q15_args_t *args, const ed_q15_tables_t *dev_tab, int stages, int n_cu, hipStream_t stream)
 {
 	/* 4-byte loads of sample pairs need every frame start 4-byte aligned */
 	const bool aligned = ((reinterpret_cast<uintptr_t>(args->audio) & 3) == 0) && (args->frame_step % 2 == 0) && (args->group_stride % 2 == 0);
 	const void *fn = stages ? (aligned ? (const void *)ed_mfcc_q15_kernel<true, true, NLO, NHI> : (const void *)ed_mfcc_q15_kernel<true, false, NLO, NHI>)
 	                        : (aligned ? (const void *)ed_mfcc_q15_kernel<false, true, NLO, NHI> : (const void *)ed_mfcc_q15_kernel<false, false, NLO, NHI>);
 	const size_t lds = sizeof(u32) * EQ_LDS_DWORDS(ED_Q15_PAIRS(NLO), ED_Q15_PAIRS(NHI));
-	int *bpc = &blocks_per_cu[(stages ? 2 : 0) + (aligned ? 1 : 0)];
-	if (*bpc <= 0)
-	{
-		/* more than 64 KB of dynamic LDS has to be asked for, once per kernel instance and device */
-		if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return (int)hipGetLastError();
-		int nb = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * EQ_WPB, lds) != hipSuccess || nb < 1) nb = 1;
-		const char *env = getenv("ED_Q15_BLOCKS_PER_CU"); /* tuning knob: cap the persistent grid */
-		if (env && atoi(env) > 0 && atoi(env) < nb) nb = atoi(env);
-		*bpc = nb;
-	}
+	int bpc = 1;
+	{ const int e = ed_kernel_prepare(fn, 64 * EQ_WPB, lds, "ED_Q15_BLOCKS_PER_CU", &bpc); if (e) return e; }
 	int64_t blocks = (args->n_frames + EQ_WPB - 1) / EQ_WPB;
-	const int64_t cap = (int64_t)n_cu * *bpc;
+	const int64_t cap = (int64_t)n_cu * bpc;
 	if (blocks > cap) blocks = cap;
 	if (blocks < 1) return 0;
 	void *kargs[] = {(void *)args, (void *)&dev_tab};
@@ -713,12 +702,8 @@ static int ed_launch_q15_shape(const ed_mfcc_q15_args_t *args, const ed_q15_tabl
 extern "C" int ed_launch_mfcc_q15(const ed_mfcc_q15_args_t *args, const ed_q15_tables_t *dev_tab, int mel_nlo, int mel_nhi,
                                   int stages, int n_cu, hipStream_t stream)
 {
-	int dev_ = 0;
-	(void)hipGetDevice(&dev_);
-	dev_ &= 15;
-	if (mel_nlo == 6 && mel_nhi == 18)
-		return ed_launch_q15_shape<6, 18>(args, dev_tab, stages, n_cu, stream, &g_q15_blocks_per_cu[dev_][0]);
+	if (mel_nlo == 6 && mel_nhi == 18) return ed_launch_q15_shape<6, 18>(args, dev_tab, stages, n_cu, stream);
 	if (mel_nlo == ED_Q15_NLO_MAX && mel_nhi == ED_Q15_NHI_MAX)
-		return ed_launch_q15_shape<ED_Q15_NLO_MAX, ED_Q15_NHI_MAX>(args, dev_tab, stages, n_cu, stream, &g_q15_blocks_per_cu[dev_][4]);
+		return ed_launch_q15_shape<ED_Q15_NLO_MAX, ED_Q15_NHI_MAX>(args, dev_tab, stages, n_cu, stream);
 	return (int)hipErrorInvalidValue;
 }

@@ -720,6 +720,45 @@ def test_product_library_is_not_a_lab_build_and_build_py_refuses_lab_flags(monke
     assert B.JIT_TEXTS[0][1].endswith("cnn_net_mfma_kernels.hip")
 
 
+# the host-pointer entry points: each stages its arrays through ed_staging (edison_ctx.h), none allocates its own device copies
+STAGING_WRAPPERS = {"edison_hip.hip": ["edison_mfcc_batch", "edison_mfcc_rows", "edison_mfcc_stages", "cnn_host", "kws_host"],
+                    "edison_q15.hip": ["q15_host"], "edison_net.hip": ["net_host"],
+                    "edison_f32.hip": ["edison_mfcc_f32_batch", "edison_f32_stream_push"], "edison_generic.hip": ["edison_mfcc_generic"]}
+
+
+def _function_body(text, name):
+    m = re.search(r"^(?:static |extern \"C\" )?int %s\([^)]*\)\s*\{" % name, text, flags=re.M)
+    assert m, name
+    depth, i = 1, m.end()
+    while depth:
+        depth += {"{": 1, "}": -1}.get(text[i], 0)
+        i += 1
+    return text[m.end():i]
+
+
+def test_kernel_preparation_and_host_staging_have_one_home():
+    """Raising a kernel's dynamic-LDS limit and sizing its grid from occupancy go through ed_kernel_prepare (edison_hip.hip), keyed
+    by device without a fixed slot count (a `dev & 15` slot once let device 16 share device 0's "already raised" flag); the one
+    exception is the hipModule function of edison_net_jit.hip, which an address-keyed cache must not see. The host-pointer
+    entry points allocate no device buffer of their own."""
+    from edison_amd import build as B
+    texts = {f: open(os.path.join(B.CSRC, f)).read() for f in os.listdir(B.CSRC) if f.endswith((".hip", ".h", ".c"))}
+    for f, t in texts.items():
+        for call in ("hipFuncSetAttribute", "hipOccupancyMaxActiveBlocksPerMultiprocessor"):
+            lines = [l.strip() for l in t.splitlines() if call + "(" in l]
+            if f == "edison_net_jit.hip" and call == "hipFuncSetAttribute":
+                assert len(lines) == 1 and "(const void *)fn" in lines[0], lines
+            else:
+                assert f == "edison_hip.hip" and len(lines) == 1 or not lines, (f, call, lines)
+        assert not re.search(r"\bdev\w*\s*&=?\s*15\b|static\s+\w+\s+\w+\s*\[16\]", t), (f, "per-device slot of a fixed table")
+    assert "int ed_kernel_prepare(" in texts["edison_hip.hip"] and "edison_launch.h" in B.HEADERS
+    for f, names in STAGING_WRAPPERS.items():
+        for name in names:
+            body = _function_body(texts[f], name)
+            assert "ed_staging" in body and "st.finish(" in body, (f, name)
+            assert "hipMalloc" not in body and ".alloc(" not in body and "hipMemcpy" not in body, (f, name)
+
+
 def test_cnn_column_tables_cover_every_column_and_meet_no_bank_conflict(built_lib):
     """csrc/cnn_mfma_cols.h (the order in which the lanes of a FULL group take the columns of conv1 / conv2 / conv3) and what model.c
     makes of it: every live column exactly once, the packed offsets are the columns' LDS addresses, idle lanes re-read a live
