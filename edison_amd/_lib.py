@@ -101,6 +101,9 @@ SIGNATURES = {
     "edison_cnn_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "edison_cnn_layers_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "edison_kws_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_kws_set_exact": (c_int, [c_void_p, c_int]),
+    "edison_kws_get_exact": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    "edison_kws_exact_stats": (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     "edison_mfcc_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_float]),
     "edison_mfcc_stages": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p]),

@@ -4,6 +4,7 @@ Host arrays (numpy) go through the synchronous host-pointer entry points; torch 
 ``*_dev`` entry points on torch's current stream (PyTorch supplies device memory and streams only -- every
 computation is a hand-written HIP kernel behind the C-ABI).
 """
+import contextlib
 import ctypes
 
 import numpy as np
@@ -231,9 +232,41 @@ class Context:
                                                    _np_ptr(mel), _np_ptr(mfcc)))
         return dict(fft=fft, spectrogram=spec, mel_spectrogram=mel, mfcc=mfcc)
 
-    def kws(self, audio, n_utt=None, utt_stride=32000, q15=False):
+    # ------------------------------------------------------------------ exact KWS mode (edison_kws_set_exact)
+    @property
+    def kws_exact(self):
+        """Exact KWS mode of this context: variant-B features, logits and argmax as the float64 host flow computes them."""
+        on = ctypes.c_int()
+        self._check(self._L.edison_kws_get_exact(self._h, ctypes.byref(on)))
+        return bool(on.value)
+
+    @kws_exact.setter
+    def kws_exact(self, on):
+        self._check(self._L.edison_kws_set_exact(self._h, 1 if on else 0))
+
+    def kws_exact_stats(self):
+        """(frames_flagged, frames_total) of the last exact KWS call; synchronises the context's stream."""
+        fl, tot = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._L.edison_kws_exact_stats(self._h, ctypes.byref(fl), ctypes.byref(tot)))
+        return fl.value, tot.value
+
+    @contextlib.contextmanager
+    def _exact_as(self, exact):
+        """exact=None: the context's setting; True / False: for this call only."""
+        if exact is None:
+            yield
+            return
+        before = self.kws_exact
+        self.kws_exact = exact
+        try:
+            yield
+        finally:
+            self.kws_exact = before
+
+    def kws(self, audio, n_utt=None, utt_stride=32000, q15=False, exact=None):
         """audio: int16, utterance u starts at u*utt_stride and uses 31*1024 samples. q15: the firmware's own
-        features (variant C) instead of the host float model (variant B)."""
+        features (variant C) instead of the host float model (variant B). exact: the exact KWS mode for this call
+        (None: the context's setting, see kws_exact)."""
         x = np.ascontiguousarray(audio, dtype=np.int16).ravel()
         used = UTT_FRAMES * FRAME_LEN
         if n_utt is None:
@@ -245,7 +278,8 @@ class Context:
         soft = np.zeros((n_utt, NET_OUT), np.int8)
         am = np.zeros(n_utt, np.int32)
         fn = self._L.edison_kws_batch_q15 if q15 else self._L.edison_kws_batch
-        self._check(fn(self._h, _np_ptr(x), n_utt, utt_stride, _np_ptr(feat), _np_ptr(logits), _np_ptr(soft), _np_ptr(am)))
+        with self._exact_as(exact):
+            self._check(fn(self._h, _np_ptr(x), n_utt, utt_stride, _np_ptr(feat), _np_ptr(logits), _np_ptr(soft), _np_ptr(am)))
         return dict(feat=feat, logits=logits, softmax=soft, argmax=am)
 
     # ------------------------------------------------------------------ device (torch tensor) entry points
@@ -313,10 +347,11 @@ class Context:
         """Any loaded graph on device tensors (edison_net_batch_dev)."""
         self._check(self._L.edison_net_batch_dev(self._h, _t_ptr(x), int(n), _t_ptr(logits), _t_ptr(softmax), _t_ptr(argmax)))
 
-    def kws_t(self, audio, n_utt, utt_stride, feat=None, logits=None, softmax=None, argmax=None, q15=False):
+    def kws_t(self, audio, n_utt, utt_stride, feat=None, logits=None, softmax=None, argmax=None, q15=False, exact=None):
         fn = self._L.edison_kws_batch_q15_dev if q15 else self._L.edison_kws_batch_dev
-        self._check(fn(self._h, _t_ptr(audio), int(n_utt), int(utt_stride), _t_ptr(feat), _t_ptr(logits),
-                       _t_ptr(softmax), _t_ptr(argmax)))
+        with self._exact_as(exact):
+            self._check(fn(self._h, _t_ptr(audio), int(n_utt), int(utt_stride), _t_ptr(feat), _t_ptr(logits),
+                           _t_ptr(softmax), _t_ptr(argmax)))
 
     # ------------------------------------------------------------------ multi-GPU (edison_dist_*: RCCL behind the C-ABI)
     def dist_init(self, id_bytes, rank, world_size):
@@ -338,13 +373,15 @@ class Context:
         """Shards cut by shard_range(n_total, rank, world): any n_total, one padded ncclAllGather inside."""
         self._check(self._L.edison_dist_allgather_logits_total(self._h, _t_ptr(local_logits), int(n_total), _t_ptr(out)))
 
-    def kws_sharded_total_t(self, audio, n_total, utt_stride, logits_all, feat=None, logits=None, softmax=None, argmax=None):
-        self._check(self._L.edison_kws_batch_sharded_total_dev(self._h, _t_ptr(audio), int(n_total), int(utt_stride), _t_ptr(feat),
-                                                               _t_ptr(logits), _t_ptr(softmax), _t_ptr(argmax), _t_ptr(logits_all)))
+    def kws_sharded_total_t(self, audio, n_total, utt_stride, logits_all, feat=None, logits=None, softmax=None, argmax=None, exact=None):
+        with self._exact_as(exact):
+            self._check(self._L.edison_kws_batch_sharded_total_dev(self._h, _t_ptr(audio), int(n_total), int(utt_stride), _t_ptr(feat),
+                                                                   _t_ptr(logits), _t_ptr(softmax), _t_ptr(argmax), _t_ptr(logits_all)))
 
-    def kws_sharded_t(self, audio, n_local, utt_stride, logits_all, feat=None, logits=None, softmax=None, argmax=None):
-        self._check(self._L.edison_kws_batch_sharded_dev(self._h, _t_ptr(audio), int(n_local), int(utt_stride), _t_ptr(feat),
-                                                         _t_ptr(logits), _t_ptr(softmax), _t_ptr(argmax), _t_ptr(logits_all)))
+    def kws_sharded_t(self, audio, n_local, utt_stride, logits_all, feat=None, logits=None, softmax=None, argmax=None, exact=None):
+        with self._exact_as(exact):
+            self._check(self._L.edison_kws_batch_sharded_dev(self._h, _t_ptr(audio), int(n_local), int(utt_stride), _t_ptr(feat),
+                                                             _t_ptr(logits), _t_ptr(softmax), _t_ptr(argmax), _t_ptr(logits_all)))
 
     def mfcc_q15_t(self, audio, n_frames, frame_step=FRAME_LEN, n_coef=NUM_MFCC, out=None, feat=None):
         """audio: int16 CUDA tensor; out: int16 [n_frames, n_coef] CUDA tensor or None; feat: int8 or None."""

@@ -34,6 +34,10 @@ extern "C" int ed_launch_net_mfma(const ed_net_plan_t *dev_plan, const ed_mm_pla
                                   int64_t in_stride, int8_t *logits, int8_t *softmax, int32_t *argmax, int n_cu, hipStream_t stream,
                                   unsigned *done_flag, unsigned done_seq, int *flag_written);
 
+/* exact KWS mode: the flagging instance of the fast MFCC kernel (mfcc_kernels.hip) and the float64 recompute (mfcc_exact_kernels.hip) */
+extern "C" int ed_launch_mfcc_flag(const ed_mfcc_args_t *args, const ed_mfcc_tables_t *dev_tab, ed_mfcc_flag_t flag, int n_cu, hipStream_t stream);
+extern "C" int ed_launch_mfcc_exact(const ed_exact_args_t *args, const ed_exact_tables_t *dev_tab, int n_cu, hipStream_t stream);
+
 extern "C" int ed_launch_mfcc_q15(const ed_mfcc_q15_args_t *args, const ed_q15_tables_t *dev_tab, int mel_nlo, int mel_nhi,
                                   int stages, int n_cu, hipStream_t stream);
 
@@ -86,6 +90,13 @@ struct edison_ctx
 	int pipe_ready, pipe_forked;
 	int pipe_pair[2];            /* indices into pipe_cand */
 	double pipe_cal_serial_us, pipe_cal_best_us; /* edison_queues_calibrate's findings (0: never calibrated) */
+	/* exact KWS mode (edison_kws_set_exact): variant B's float64 tables, the device list of flagged frames (word 0 = count, then one
+	 * entry per frame of capacity exact_cap) and the frame count of the last exact call */
+	ed_exact_tables_t *d_exact_tab;
+	int kws_exact;
+	uint32_t *exact_list;
+	int64_t exact_cap;
+	int64_t exact_last_frames;
 	void *dist_scratch; /* padded send + receive blocks of edison_dist_allgather_logits_total (unequal shards) */
 	size_t dist_scratch_bytes;
 	char err[512];

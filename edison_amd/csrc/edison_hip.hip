@@ -48,6 +48,26 @@ static int upload_tables(edison_ctx *ctx, double fs, double lo, double hi, doubl
 		free(h);
 		ED_HIP(ctx, e);
 	}
+	/* exact KWS mode: variant B's float64 tables (a filterbank with more taps than the table holds switches the mode's recompute off:
+	 * EDISON_E_NO_IMPL on use) */
+	{
+		ed_exact_tables_t *h = (ed_exact_tables_t *)malloc(sizeof(ed_exact_tables_t));
+		if (!h) return set_err(ctx, EDISON_E_NO_MEMORY, "host allocation failed");
+		const int r = ed_build_exact_tables(fs, lo, hi, scale, h);
+		if (r == EDISON_OK)
+		{
+			if (!ctx->d_exact_tab) ED_HIP(ctx, hipMalloc((void **)&ctx->d_exact_tab, sizeof(ed_exact_tables_t)));
+			const hipError_t e = hipMemcpy(ctx->d_exact_tab, h, sizeof(ed_exact_tables_t), hipMemcpyHostToDevice);
+			free(h);
+			ED_HIP(ctx, e);
+		}
+		else
+		{
+			free(h);
+			if (r != EDISON_E_NO_IMPL) return r;
+			if (ctx->d_exact_tab) { (void)hipFree(ctx->d_exact_tab); ctx->d_exact_tab = NULL; }
+		}
+	}
 	/* variant C: a filterbank / scale it cannot express only switches variant C off (EDISON_E_NO_IMPL on use) */
 	{
 		ed_q15_tables_t *h = (ed_q15_tables_t *)malloc(sizeof(ed_q15_tables_t));
@@ -114,6 +134,8 @@ extern "C" int edison_init(int device, edison_ctx **out)
 		if (hipSetDevice(device) != hipSuccess) { r = EDISON_E_RUNTIME; break; }
 		if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) { r = EDISON_E_RUNTIME; break; }
 		ctx->stream = ctx->own_stream;
+		const char *exact = getenv("EDISON_KWS_EXACT"); /* the exact KWS mode's default for this context */
+		ctx->kws_exact = exact && atoi(exact) > 0;
 		r = upload_tables(ctx, EDISON_FS, 80.0, 7600.0, 128.0); /* audio/config.py:14-15 */
 	} while (0);
 	if (r != EDISON_OK)
@@ -145,6 +167,8 @@ extern "C" void edison_shutdown(edison_ctx *ctx)
 	if (ctx->d_mm_frag) (void)hipFree(ctx->d_mm_frag);
 	if (ctx->d_mm_seeds) (void)hipFree(ctx->d_mm_seeds);
 	if (ctx->scratch) (void)hipFree(ctx->scratch);
+	if (ctx->d_exact_tab) (void)hipFree(ctx->d_exact_tab);
+	if (ctx->exact_list) (void)hipFree(ctx->exact_list);
 	if (ctx->pipe_ready)
 	{
 		for (int k = 0; k < 5; k++) (void)hipStreamDestroy(ctx->pipe_cand[k]);
@@ -879,6 +903,72 @@ extern "C" int edison_cnn_layers_dev(edison_ctx *ctx, const int8_t *feat, int64_
 	return cnn_launch(ctx, feat, n_utt, NULL, NULL, NULL, acts);
 }
 
+/* Exact KWS mode, variant B: the flagging MFCC launch lists the frames near a rounding boundary, the float64 kernel recomputes them
+ * and overwrites their rows of `feat`. Everything is enqueued on ctx->stream; the list grows like ensure_scratch. */
+static int kws_exact_features(edison_ctx *ctx, const int16_t *audio, int64_t n_utt, int64_t utt_stride, int8_t *feat)
+{
+	if (!ctx->d_exact_tab) return set_err(ctx, EDISON_E_NO_IMPL, "exact KWS mode: the configured filterbank has too many taps for the float64 kernel's table");
+	const int64_t n_frames = n_utt * EDISON_UTT_FRAMES;
+	if (n_frames > ctx->exact_cap)
+	{
+		ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		if (ctx->exact_list) ED_HIP(ctx, hipFree(ctx->exact_list));
+		ctx->exact_list = NULL; ctx->exact_cap = 0;
+		const hipError_t e = hipMalloc((void **)&ctx->exact_list, sizeof(uint32_t) * (size_t)(n_frames + 1));
+		if (e == hipErrorOutOfMemory) return set_err(ctx, EDISON_E_NO_MEMORY, "exact KWS list hipMalloc: out of HBM");
+		ED_HIP(ctx, e);
+		ctx->exact_cap = n_frames;
+	}
+	ED_HIP(ctx, hipMemsetAsync(ctx->exact_list, 0, sizeof(uint32_t), ctx->stream));
+	ctx->exact_last_frames = n_frames;
+	ed_mfcc_args_t a;
+	memset(&a, 0, sizeof(a));
+	a.audio = audio; a.n_frames = n_frames; a.frames_per_group = EDISON_UTT_FRAMES; a.group_stride = utt_stride;
+	a.frame_step = EDISON_FRAME_LEN; a.n_coef = EDISON_NUM_MFCC;
+	a.mel_NLO = ctx->mel_NLO[EDISON_MFCC_B];
+	a.mel_NHI = ctx->mel_NHI[EDISON_MFCC_B];
+	a.feat = feat; a.feat_scale = 1.0f;
+	const ed_mfcc_flag_t flag = {ctx->exact_list, ctx->exact_list + 1};
+	int e = ed_launch_mfcc_flag(&a, ctx->d_tab[EDISON_MFCC_B], flag, ctx->n_cu, ctx->stream);
+	if (e) return ed_launch_result(ctx, e, "MFCC flagging kernel");
+	ed_exact_args_t x;
+	memset(&x, 0, sizeof(x));
+	x.audio = audio; x.frames_per_group = EDISON_UTT_FRAMES; x.group_stride = utt_stride; x.frame_step = EDISON_FRAME_LEN;
+	x.feat = feat; x.n_coef = EDISON_NUM_MFCC; x.use_log = 0; x.feat_scale = 1.0f;
+	x.count = ctx->exact_list; x.list = ctx->exact_list + 1;
+	e = ed_launch_mfcc_exact(&x, ctx->d_exact_tab, ctx->n_cu, ctx->stream);
+	return ed_launch_result(ctx, e, "float64 MFCC recompute kernel");
+}
+
+extern "C" int edison_kws_set_exact(edison_ctx *ctx, int on)
+{
+	if (!ctx) return EDISON_E_ARGUMENT;
+	ctx->kws_exact = on ? 1 : 0;
+	return EDISON_OK;
+}
+
+extern "C" int edison_kws_get_exact(const edison_ctx *ctx, int *on)
+{
+	if (!ctx || !on) return EDISON_E_ARGUMENT;
+	*on = ctx->kws_exact;
+	return EDISON_OK;
+}
+
+extern "C" int edison_kws_exact_stats(edison_ctx *ctx, int64_t *frames_flagged, int64_t *frames_total)
+{
+	if (!ctx) return EDISON_E_ARGUMENT;
+	uint32_t n = 0;
+	if (ctx->exact_list && ctx->exact_last_frames > 0)
+	{
+		ED_HIP(ctx, hipSetDevice(ctx->device));
+		ED_HIP(ctx, hipMemcpyAsync(&n, ctx->exact_list, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
+		ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	}
+	if (frames_flagged) *frames_flagged = (int64_t)n;
+	if (frames_total) *frames_total = ctx->exact_last_frames;
+	return EDISON_OK;
+}
+
 static int kws_dev(edison_ctx *ctx, const int16_t *audio, int64_t n_utt, int64_t utt_stride, int variant, int8_t *feat,
                    int8_t *logits, int8_t *softmax, int32_t *argmax)
 {
@@ -895,8 +985,10 @@ static int kws_dev(edison_ctx *ctx, const int16_t *audio, int64_t n_utt, int64_t
 		f = (int8_t *)ctx->scratch;
 	}
 	/* first 13 coefficients, scale 1 (nnom_net_input_scale, audio/config.py:41; NNOM_INPUT_SCALE, weights.h:162) */
-	int r = ed_ctx_mfcc_launch(ctx, audio, n_utt * EDISON_UTT_FRAMES, EDISON_UTT_FRAMES, utt_stride, EDISON_FRAME_LEN,
-	                           variant, EDISON_NUM_MFCC, NULL, f, 1.0f, 0, NULL, NULL, NULL, NULL);
+	int r = ctx->kws_exact && variant == EDISON_MFCC_B
+	            ? kws_exact_features(ctx, audio, n_utt, utt_stride, f)
+	            : ed_ctx_mfcc_launch(ctx, audio, n_utt * EDISON_UTT_FRAMES, EDISON_UTT_FRAMES, utt_stride, EDISON_FRAME_LEN,
+	                                 variant, EDISON_NUM_MFCC, NULL, f, 1.0f, 0, NULL, NULL, NULL, NULL);
 	if (r != EDISON_OK) return r;
 	return cnn_launch(ctx, f, n_utt, logits, softmax, argmax, NULL);
 }

@@ -432,6 +432,43 @@ typedef struct {
 	const float *window; /* variant TF: [N] periodic Hann window in float32 (tf.signal.hann_window), multiplied into the float32 samples; NULL: none */
 } ed_mfcc_gen_args_t;
 
+/* ---- exact KWS mode (mfcc_exact_kernels.hip) ------------------------------------------------------------
+ * The flagging instance of the fast MFCC kernel (ed_mfcc2_flag_kernel) appends the global index of every frame whose int8 feature
+ * might differ from the float64 host flow's to a device list; ed_mfcc_exact_kernel recomputes those frames in float64 and
+ * overwrites their features. A frame is flagged when one of its in-range coefficients y = coef * feat_scale (fp32) lies within
+ * delta = ED_EXACT_K * 2^-24 * rms(x) * |feat_scale| of a rounding boundary x.5; rms(x) is the root mean square of the frame's 1024
+ * samples. ED_EXACT_K is calibrated on the kernel's own error (tools/fuzz_kws_exact.py), not proven. */
+#define ED_EXACT_K 10.0f
+typedef struct {
+	uint32_t *count; /* number of entries appended (reset to 0 before the launch) */
+	uint32_t *list;  /* [n_frames] global frame indices; the order is not defined */
+} ed_mfcc_flag_t;
+
+#define ED_EXACT_TAPS_MAX 1088 /* nonzero mel weights of all bands back to back (the bands overlap pairwise: < 2 x 513) */
+typedef struct {
+	double tw[512][2];                  /* exp(-2 pi i k / 1024), k = 0..511 */
+	double dct[32][32];                 /* 2 cos(pi c (2 n + 1) / 64): scipy.fftpack.dct type 2, norm None */
+	double mel_w[ED_EXACT_TAPS_MAX];    /* band j: mel_mtx_scale * W[k][j] for k = mel_k0[j] .. mel_k0[j] + mel_len[j] - 1 at mel_off[j] */
+	int32_t mel_off[32], mel_k0[32], mel_len[32]; /* 32 mel bands, the only count this path is built for */
+	double mel_div;                     /* mel_mtx_scale: the product is divided by it again (mfcc_utils.py:282,309) */
+} ed_exact_tables_t;
+
+typedef struct {
+	const int16_t *audio;
+	int64_t frames_per_group; /* frame f starts at (f / fpg) * group_stride + (f % fpg) * frame_step, as in ed_mfcc_args_t */
+	int64_t group_stride;
+	int64_t frame_step;
+	int8_t *feat;             /* [n_frames][n_coef]: the flagged frames' rows are overwritten */
+	int n_coef;
+	int use_log;
+	float feat_scale;
+	const uint32_t *count;    /* ed_mfcc_flag_t's, read on the device */
+	const uint32_t *list;
+} ed_exact_args_t;
+
+/* host: the float64 tables of variant B for the recompute kernel (tables.c) */
+int ed_build_exact_tables(double sample_rate, double lower_edge_hertz, double upper_edge_hertz, double mel_mtx_scale, ed_exact_tables_t *out);
+
 
 
 #ifdef __cplusplus

@@ -183,8 +183,9 @@ __device__ __forceinline__ void ed_pair_ptrs(const ed_mfcc_args_t &a, const ed_m
  * workgroups' finishing times and buys nothing -- the board sits at its power cap and takes the recovered idle time back as
  * clock (profiles/r04_mfcc_launch_structure_notes.txt).
  */
-template <bool ALIGNED, bool PLAIN, int NLO, int NHI, bool LIST, bool WINDOW = false>
-__device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const ed_mfcc_tables_t *__restrict__ tab, const ed_mfcc_list_t *list)
+template <bool ALIGNED, bool PLAIN, int NLO, int NHI, bool LIST, bool WINDOW = false, bool FLAG = false>
+__device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const ed_mfcc_tables_t *__restrict__ tab, const ed_mfcc_list_t *list,
+                                              ed_mfcc_flag_t flag = ed_mfcc_flag_t{nullptr, nullptr})
 {
 	extern __shared__ __attribute__((aligned(16))) float smem[];
 	const int lane = threadIdx.x & 63;
@@ -292,6 +293,19 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 	unsigned long long tlast = tfirst;
 #endif
 	ed_f2 re[8], im[8];
+	ed_f2 ssq = ed_splat(0.0f); /* FLAG: this lane's share of the sum of squared samples of both frames (the pair being computed) */
+	uint32_t pend_n = 0, pend_f = 0, pend_at = 0; /* FLAG: frames of the last flagged pair (bit 0: A, bit 1: B), its frame A, its reserved slot (lane 0) */
+	auto flush = [&]() {
+		if (pend_n)
+		{
+			if (lane == 0)
+			{
+				if (pend_n & 1u) flag.list[pend_at] = pend_f;
+				if (pend_n & 2u) flag.list[pend_at + (pend_n & 1u)] = pend_f + 1;
+			}
+			pend_n = 0;
+		}
+	};
 	if (i_cur < cnt)
 	{
 #pragma unroll
@@ -299,6 +313,7 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 		{
 			re[a] = ed_mk2((float)(int16_t)(rawA[a] & 0xffffu), (float)(int16_t)(rawB[a] & 0xffffu));
 			im[a] = ed_mk2((float)(int16_t)(rawA[a] >> 16), (float)(int16_t)(rawB[a] >> 16));
+			if (FLAG) ssq = ed_fma2(im[a], im[a], ed_fma2(re[a], re[a], ssq));
 		}
 		if (WINDOW) /* variant TF: tf.signal.stft's Hann window on the float32 samples, (w[2m], w[2m+1]) per packed point, the same for both frames */
 		{
@@ -343,6 +358,7 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 			ed_load_frame<ALIGNED>(pa, lane, rawA);
 			ed_load_frame<ALIGNED>(pb, lane, rawB);
 		}
+		if (FLAG) flush();
 		ED2_ST(1)
 		/* transpose 1 on the VALU (lane bits 3-5): with both transposes in LDS the LDS pipe saturates (-5.5 % with the priorities on) */
 		ed_transpose8_2<3, 4, 5>(re, lane);
@@ -525,6 +541,27 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 				if (args.feat) args.feat[at] = (int8_t)__float2int_rn(fminf(fmaxf(coef * args.feat_scale, -128.0f), 127.0f));
 			}
 		}
+		if (FLAG)
+		{
+			/* exact KWS mode: is any in-range feature of frame A (lanes 0..31) or B (32..63) within delta of a rounding boundary?
+			 * delta = K 2^-24 rms(x) |scale| (edison_internal.h); rms from the samples' squares, summed over the wave: after the
+			 * fold lanes 0..31 hold frame A's partial sums, 32..63 frame B's, which is the frame their coefficient belongs to. */
+			float s = ed_fold_halves(ssq.x, ssq.y);
+#pragma unroll
+			for (int o = 16; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+			const float y = coef * args.feat_scale;
+			const float delta = ED_EXACT_K * 0x1p-24f * (__builtin_amdgcn_sqrtf(s) * (1.0f / 32.0f)) * fabsf(args.feat_scale);
+			const bool near = c < args.n_coef && (lane < 32 || haveB) && y >= -128.0f && y < 127.0f && fabsf(y - floorf(y) - 0.5f) < delta;
+			const uint64_t m = __ballot(near);
+			if (m)
+			{
+				/* one exec-masked lane reserves the pair's entries; they are written behind the next pair's pass 1 (or behind the
+				 * loop), when the atomic's return has arrived: waiting for it here stalled the wave at every flagged pair */
+				pend_n = ((uint32_t)m ? 1u : 0u) | ((m >> 32) ? 2u : 0u);
+				pend_f = fA;
+				if (lane == 0) pend_at = __hip_atomic_fetch_add(flag.count, (pend_n & 1u) + (pend_n >> 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			}
+		}
 		ED2_ST(11)
 		/* the next pair's samples (requested at the top of this iteration) become the floats the next iteration starts from */
 #pragma unroll
@@ -538,9 +575,16 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 				im[a] = im[a] * ed_splat(wv[a].y);
 			}
 		}
+		if (FLAG)
+		{
+			ssq = ed_splat(0.0f);
+#pragma unroll
+			for (int a = 0; a < 8; a++) ssq = ed_fma2(im[a], im[a], ed_fma2(re[a], re[a], ssq));
+		}
 		i_cur = i_next;
 		if (LIST) { g_cur = g_nxt; gi_cur = gi_nxt; }
 	}
+	if (FLAG) flush();
 #if ED2_STAMP
 	asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt1) :: "memory");
 	ph[12] = ed2_now() - tfirst; ph[13] = rt1 - rt0; ph[14] = rt_entry; ph[15] = rt0; ph[16] = rt1;
@@ -572,6 +616,14 @@ template <bool ALIGNED, bool PLAIN, int NLO, int NHI>
 __global__ __launch_bounds__(64 * ED2_WPB) void ed_mfcc2_window_kernel(ed_mfcc_args_t args, const ed_mfcc_tables_t *__restrict__ tab)
 {
 	ed_mfcc2_body<ALIGNED, PLAIN, NLO, NHI, false, true>(args, tab, nullptr);
+}
+
+/* exact KWS mode (edison_kws_set_exact): the same loop and store, plus the list of frames the float64 kernel recomputes
+ * (ed_mfcc_exact_kernel, mfcc_exact_kernels.hip). Variant B without window only. */
+template <bool ALIGNED, bool PLAIN, int NLO, int NHI>
+__global__ __launch_bounds__(64 * ED2_WPB) void ed_mfcc2_flag_kernel(ed_mfcc_args_t args, const ed_mfcc_tables_t *__restrict__ tab, ed_mfcc_flag_t flag)
+{
+	ed_mfcc2_body<ALIGNED, PLAIN, NLO, NHI, false, false, true>(args, tab, nullptr, flag);
 }
 
 /* the same loop over a LIST of independent batches (edison_mfcc_batches_dev): one launch keeps the chip busy across them (what the
@@ -689,5 +741,34 @@ extern "C" int ed_launch_mfcc(const ed_mfcc_args_t *args, const ed_mfcc_tables_t
 	if (args->mel_NLO == 2 && args->mel_NHI == 5) return ed_launch_mfcc_shape<2, 5>(args, dev_tab, stages, n_cu, stream);
 	if (args->mel_NLO == ED_MEL_NLO_MAX && args->mel_NHI == ED_MEL_NHI_MAX)
 		return ed_launch_mfcc_shape<ED_MEL_NLO_MAX, ED_MEL_NHI_MAX>(args, dev_tab, stages, n_cu, stream);
+	return (int)hipErrorInvalidValue;
+}
+
+/* exact KWS mode: the fast path's launch with the flagging instance (variant B without window; no stage dumps). flag.count must be
+ * zero on the stream before this launch. */
+template <int NLO, int NHI>
+static int ed_launch_mfcc_flag_shape(const ed_mfcc_args_t *args, const ed_mfcc_tables_t *dev_tab, ed_mfcc_flag_t flag, int n_cu, hipStream_t stream)
+{
+	const size_t lds2 = sizeof(float) * (ED_FIXTAB_FLOATS + (NLO + NHI) * 256 + ED2_WPB * ED2_XBUF_FLOATS) + 16 /* queue */;
+	const bool aligned = ((reinterpret_cast<uintptr_t>(args->audio) & 3) == 0) && (args->frame_step % 2 == 0) && (args->group_stride % 2 == 0);
+	const bool plain = args->frames_per_group >= args->n_frames;
+	const void *fn = aligned ? (plain ? (const void *)ed_mfcc2_flag_kernel<true, true, NLO, NHI> : (const void *)ed_mfcc2_flag_kernel<true, false, NLO, NHI>)
+	                         : (plain ? (const void *)ed_mfcc2_flag_kernel<false, true, NLO, NHI> : (const void *)ed_mfcc2_flag_kernel<false, false, NLO, NHI>);
+	int bpc = 1;
+	{ const int e = ed_kernel_prepare(fn, 64 * ED2_WPB, lds2, "ED_MFCC_BLOCKS_PER_CU", &bpc); if (e) return e; }
+	const int64_t n_pairs = (args->n_frames + 1) / 2;
+	int64_t blocks = (n_pairs + ED2_WPB - 1) / ED2_WPB;
+	if (blocks > (int64_t)n_cu * bpc) blocks = (int64_t)n_cu * bpc;
+	void *kargs[] = {(void *)args, (void *)&dev_tab, (void *)&flag};
+	return (int)hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64 * ED2_WPB), kargs, lds2, stream);
+}
+
+extern "C" int ed_launch_mfcc_flag(const ed_mfcc_args_t *args, const ed_mfcc_tables_t *dev_tab, ed_mfcc_flag_t flag, int n_cu, hipStream_t stream)
+{
+	if (args->n_frames <= 0) return 0;
+	if (args->window || !flag.count || !flag.list) return (int)hipErrorInvalidValue;
+	if (args->mel_NLO == 2 && args->mel_NHI == 5) return ed_launch_mfcc_flag_shape<2, 5>(args, dev_tab, flag, n_cu, stream);
+	if (args->mel_NLO == ED_MEL_NLO_MAX && args->mel_NHI == ED_MEL_NHI_MAX)
+		return ed_launch_mfcc_flag_shape<ED_MEL_NLO_MAX, ED_MEL_NHI_MAX>(args, dev_tab, flag, n_cu, stream);
 	return (int)hipErrorInvalidValue;
 }

@@ -279,3 +279,39 @@ int ed_build_mfcc_tables(int variant, double sample_rate, double lower_edge_hert
 	}
 	return EDISON_OK;
 }
+
+/* --- exact KWS mode: variant B's float64 tables for ed_mfcc_exact_kernel (mfcc_exact_kernels.hip) -------------------------------
+ * The same twiddles, matrix and DCT the host flow uses (mfcc_utils.py:282-318; oracle/mfcc_ref.c restates it), kept in float64: the
+ * FFT twiddles exp(-2 pi i k / 1024), the mel matrix times mel_mtx_scale as banded runs of its nonzero weights, the DCT-II matrix. */
+int ed_build_exact_tables(double sample_rate, double lower_edge_hertz, double upper_edge_hertz, double mel_mtx_scale, ed_exact_tables_t *out)
+{
+	const int NMEL = EDISON_NUM_MEL, nbins = EDISON_FRAME_LEN / 2 + 1;
+	memset(out, 0, sizeof(*out));
+	for (int k = 0; k < 512; k++)
+	{
+		out->tw[k][0] = cos(-2.0 * M_PI * (double)k / 1024.0);
+		out->tw[k][1] = sin(-2.0 * M_PI * (double)k / 1024.0);
+	}
+	for (int c = 0; c < NMEL; c++)
+		for (int n = 0; n < NMEL; n++)
+			out->dct[c][n] = 2.0 * cos(M_PI * (double)c * (double)(2 * n + 1) / (double)(2 * NMEL));
+	double *W = (double *)malloc(sizeof(double) * (size_t)nbins * NMEL);
+	if (!W) return EDISON_E_NO_MEMORY;
+	int r = ed_gen_mel_weight_matrix(NMEL, nbins, sample_rate, lower_edge_hertz, upper_edge_hertz, W);
+	if (r != EDISON_OK) { free(W); return r; }
+	int off = 0;
+	for (int j = 0; j < NMEL; j++)
+	{
+		int first = -1, last = -1;
+		for (int k = 0; k < nbins; k++)
+			if (W[(size_t)k * NMEL + j] != 0.0) { if (first < 0) first = k; last = k; }
+		const int len = first < 0 ? 0 : last - first + 1; /* zeros inside the run add nothing */
+		if (off + len > ED_EXACT_TAPS_MAX) { free(W); return EDISON_E_NO_IMPL; }
+		out->mel_off[j] = off; out->mel_k0[j] = first < 0 ? 0 : first; out->mel_len[j] = len;
+		for (int t = 0; t < len; t++) out->mel_w[off + t] = mel_mtx_scale * W[(size_t)(first + t) * NMEL + j];
+		off += len;
+	}
+	out->mel_div = mel_mtx_scale;
+	free(W);
+	return EDISON_OK;
+}

@@ -38,11 +38,12 @@ def pad_or_cut(data, n=cfg.nSamples, mode="zero"):
     return data[:n]
 
 
-def infer_utterances(audio, ctx=None):
-    """audio: int16 [n_utt, >=31744] (or 1-D single utterance). Returns the dict of ``Context.kws``."""
+def infer_utterances(audio, ctx=None, exact=None):
+    """audio: int16 [n_utt, >=31744] (or 1-D single utterance). Returns the dict of ``Context.kws``. exact: True gives the
+    features, logits and argmax of the reference's float64 host flow (``Context.kws_exact``); None keeps the context's mode."""
     ctx = ctx or default_context()
     a = np.atleast_2d(np.asarray(audio, dtype=np.int16))
-    return ctx.kws(np.ascontiguousarray(a), n_utt=a.shape[0], utt_stride=a.shape[1])
+    return ctx.kws(np.ascontiguousarray(a), n_utt=a.shape[0], utt_stride=a.shape[1], exact=exact)
 
 
 def report(res, i=0, out=None):
@@ -56,9 +57,9 @@ def report(res, i=0, out=None):
     return KEYWORDS[k]
 
 
-def file_inference(path, pad_mode="zero", ctx=None, verbose=True):
+def file_inference(path, pad_mode="zero", ctx=None, verbose=True, exact=None):
     data = pad_or_cut(read_wav(path), mode=pad_mode)
-    res = infer_utterances(data, ctx)
+    res = infer_utterances(data, ctx, exact=exact)
     res["keyword"] = KEYWORDS[int(res["argmax"][0])]
     if verbose:
         print('net input (int8, 31x13):')
@@ -84,7 +85,7 @@ def compare(data_a, data_b, name, out=None):
     print('_________________________________________________________________', file=out)
 
 
-def frame_inference(path, ctx=None, out=None):
+def frame_inference(path, ctx=None, out=None, exact=None):
     """`kws mcu file <wav>` = kws_on_mcu.frameInference (:310-401): the wav (edge-padded to 2 s) through the host
     leg (MFCC variant B) and through the board's leg -- here the GPU's variant C, i.e. the firmware's own Q15
     arithmetic -- each followed by the int8 network, then the two comparison blocks the reference prints
@@ -94,7 +95,7 @@ def frame_inference(path, ctx=None, out=None):
     ctx = ctx or default_context()
     data = pad_or_cut(read_wav(path), mode="edge")
     np.set_printoptions(precision=3, suppress=True)
-    host = ctx.kws(data, n_utt=1, utt_stride=data.shape[0])
+    host = ctx.kws(data, n_utt=1, utt_stride=data.shape[0], exact=exact)
     mcu = ctx.kws(data, n_utt=1, utt_stride=data.shape[0], q15=True)
     host_pred = host["softmax"][0].astype(np.float32) / 127.0
     mcu_pred = mcu["softmax"][0].astype(np.float32) / 127.0

@@ -318,6 +318,27 @@ int edison_kws_batch_dev(edison_ctx *ctx, const int16_t *audio, int64_t n_utt, i
                          int8_t *feat, int8_t *logits, int8_t *softmax, int32_t *argmax);
 
 /*
+ * Exact KWS mode (off by default; EDISON_KWS_EXACT=1 in the environment at edison_init turns it on for that context).
+ * While it is on, every variant-B KWS call of the context -- edison_kws_batch, edison_kws_batch_dev and the sharded entry points --
+ * aims at features, logits and argmax identical to the host flow's float64 arithmetic (mfcc_mcu, then float32 * scale, clip,
+ * round half to even: kws_nnom.py:354-361) instead of the fp32 kernel's, which lands one int8 step off where a coefficient lies
+ * within its rounding error of x.5. On ctx's stream, asynchronously, the call runs: the fp32 MFCC kernel, which also lists every
+ * frame with an in-range feature within delta = K 2^-24 rms(frame) of x.5; a float64 kernel that recomputes the listed frames
+ * (FFT, mel, DCT as the host flow) and overwrites their features; the CNN. Variant C (edison_kws_batch_q15*) and the continuous
+ * streams are not affected.
+ * Limits of the guarantee:
+ *   - K is calibrated on the fp32 kernel's measured error with a margin, not proven: a frame whose fp32 error
+ *     exceeds the bound would keep the fp32 feature.
+ *   - the float64 recompute differs from numpy's pocketfft at about 1e-13 relative; that changes a feature only if float32(v64)
+ *     falls on the other side of a float32 rounding boundary lying exactly at an x.5.
+ * edison_kws_exact_stats covers the last exact call on the context: frames listed for the recompute and frames computed
+ * (31 per utterance). It synchronises ctx's stream; both are 0 before the first exact call.
+ */
+int edison_kws_set_exact(edison_ctx *ctx, int on);
+int edison_kws_get_exact(const edison_ctx *ctx, int *on);
+int edison_kws_exact_stats(edison_ctx *ctx, int64_t *frames_flagged, int64_t *frames_total);
+
+/*
  * Variant C with its native types: what the firmware keeps in bufDctInline / sends with audioDumpToHost
  * (audioprocessing.c:221-231). mfcc [n_frames][n_coef] int16; feat [n_frames][n_coef] int8 = mfccToNetInput's NNoM
  * branch (C division by NNOM_INPUT_SCALE = 1, clip to [-128,127], app.c:686-694). Stage dumps, all int16:
