@@ -39,6 +39,13 @@ class NetLayerInfo(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ("type", "out_h", "out_w", "out_c", "acts_offset", "relu")]
 
 
+class KwsGeom(ctypes.Structure):
+    """edison_kws_geom"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("variant", "frame_len", "frame_step", "n_samples", "frame_count", "mel_nbins", "first_mfcc",
+                                              "num_mfcc")] + \
+               [(k, c_double) for k in ("sample_rate", "lower_edge_hertz", "upper_edge_hertz", "mel_mtx_scale", "net_input_scale")]
+
+
 class Fsm(ctypes.Structure):
     """edison_fsm"""
     _fields_ = [("state", c_int), ("hot_timeout_ms", ctypes.c_uint32), ("wake_idx", c_int), ("loc_idx", c_int),
@@ -101,6 +108,9 @@ SIGNATURES = {
     "edison_cnn_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "edison_cnn_layers_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "edison_kws_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_kws_geom_default": (None, [ctypes.POINTER(KwsGeom)]),
+    "edison_kws_geom_batch_dev": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_kws_geom_batch": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "edison_kws_set_exact": (c_int, [c_void_p, c_int]),
     "edison_kws_get_exact": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "edison_kws_exact_stats": (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),

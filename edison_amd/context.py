@@ -282,6 +282,34 @@ class Context:
             self._check(fn(self._h, _np_ptr(x), n_utt, utt_stride, _np_ptr(feat), _np_ptr(logits), _np_ptr(soft), _np_ptr(am)))
         return dict(feat=feat, logits=logits, softmax=soft, argmax=am)
 
+    # ------------------------------------------------------------------ any MFCC geometry (edison_kws_geom_batch*)
+    def kws_geom(self, audio, geometry, n_utt=None, utt_stride=None):
+        """Audio to class index for the loaded graph at `geometry` (kws.geometry.KwsGeometry) in one call: utterance u starts at
+        u * utt_stride (default geometry.n_samples) and uses geometry.frame_count frames. Returns the dict of ``kws``: feat
+        [n_utt][frame_count * num_mfcc] int8, logits / softmax [n_utt][n_out] (softmax None for a graph without Softmax), argmax."""
+        x = np.ascontiguousarray(audio, dtype=np.int16).ravel()
+        stride = int(geometry.n_samples if utt_stride is None else utt_stride)
+        used = (geometry.frame_count - 1) * geometry.frame_step + geometry.frame_len
+        if n_utt is None:
+            n_utt = 0 if x.shape[0] < used else 1 + (x.shape[0] - used) // max(stride, 1)
+        if n_utt > 0 and (n_utt - 1) * stride + used > x.shape[0]:
+            raise ValueError("audio too short for %d utterances" % n_utt)
+        info = self.net_info()
+        feat = np.zeros((n_utt, geometry.n_features), np.int8)
+        logits = np.zeros((n_utt, info["n_out"]), np.int8)
+        soft = np.zeros((n_utt, info["n_out"]), np.int8) if info["has_softmax"] else None
+        am = np.zeros(n_utt, np.int32)
+        g = geometry.to_ctypes()
+        self._check(self._L.edison_kws_geom_batch(self._h, ctypes.byref(g), _np_ptr(x), int(n_utt), stride, _np_ptr(feat), _np_ptr(logits),
+                                                  _np_ptr(soft), _np_ptr(am)))
+        return dict(feat=feat, logits=logits, softmax=soft, argmax=am)
+
+    def kws_geom_t(self, audio, geometry, n_utt, utt_stride, feat=None, logits=None, softmax=None, argmax=None):
+        """edison_kws_geom_batch_dev on torch device tensors, enqueued on the context's stream (use_torch_stream), no host synchronisation."""
+        g = geometry.to_ctypes()
+        self._check(self._L.edison_kws_geom_batch_dev(self._h, ctypes.byref(g), _t_ptr(audio), int(n_utt), int(utt_stride), _t_ptr(feat),
+                                                      _t_ptr(logits), _t_ptr(softmax), _t_ptr(argmax)))
+
     # ------------------------------------------------------------------ device (torch tensor) entry points
     def mfcc_t(self, audio, n_frames, frame_step=FRAME_LEN, variant=MFCC_B, n_coef=NUM_MFCC, out=None, feat=None,
                feat_scale=1.0, use_log=False):

@@ -41,6 +41,8 @@ extern "C" int ed_launch_mfcc_exact(const ed_exact_args_t *args, const ed_exact_
 extern "C" int ed_launch_mfcc_q15(const ed_mfcc_q15_args_t *args, const ed_q15_tables_t *dev_tab, int mel_nlo, int mel_nhi,
                                   int stages, int n_cu, hipStream_t stream);
 
+struct ed_geom_cache; /* edison_kws_geom.hip */
+
 struct edison_ctx
 {
 	int device;
@@ -99,6 +101,7 @@ struct edison_ctx
 	int64_t exact_last_frames;
 	void *dist_scratch; /* padded send + receive blocks of edison_dist_allgather_logits_total (unequal shards) */
 	size_t dist_scratch_bytes;
+	ed_geom_cache *geom; /* edison_kws_geom_batch*: the tables of the last geometry (one entry) */
 	char err[512];
 };
 
@@ -162,6 +165,11 @@ private:
 	int err = EDISON_OK, n = 0;
 	struct { ed_dev_buf d; void *down; size_t bytes; } buf[8];
 };
+
+/* Grow ctx->scratch to at least `bytes` (synchronises the stream only when it grows). */
+int ed_ctx_ensure_scratch(edison_ctx *ctx, size_t bytes);
+/* Free the cached tables of edison_kws_geom_batch* (edison_shutdown). */
+void ed_ctx_geom_free(edison_ctx *ctx);
 
 /* The loaded model on 31x13x1 -> 10 features (the geometry of every kws / stream entry point): matrix-core kernel for
  * the kws_conv graph, the general kernel for any other graph of that shape. feat_stride = bytes between utterances. */

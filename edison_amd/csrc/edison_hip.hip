@@ -169,6 +169,7 @@ extern "C" void edison_shutdown(edison_ctx *ctx)
 	if (ctx->scratch) (void)hipFree(ctx->scratch);
 	if (ctx->d_exact_tab) (void)hipFree(ctx->d_exact_tab);
 	if (ctx->exact_list) (void)hipFree(ctx->exact_list);
+	ed_ctx_geom_free(ctx);
 	if (ctx->pipe_ready)
 	{
 		for (int k = 0; k < 5; k++) (void)hipStreamDestroy(ctx->pipe_cand[k]);
@@ -396,6 +397,8 @@ static int ensure_scratch(edison_ctx *ctx, size_t bytes)
 	ctx->scratch_bytes = bytes;
 	return EDISON_OK;
 }
+
+int ed_ctx_ensure_scratch(edison_ctx *ctx, size_t bytes) { return ensure_scratch(ctx, bytes); }
 
 /* ---------------------------------------------------------------------------------------- host-pointer staging */
 ed_staging::ed_staging(edison_ctx *c) : ctx(c)

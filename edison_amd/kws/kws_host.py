@@ -38,11 +38,16 @@ def pad_or_cut(data, n=cfg.nSamples, mode="zero"):
     return data[:n]
 
 
-def infer_utterances(audio, ctx=None, exact=None):
+def infer_utterances(audio, ctx=None, exact=None, geometry=None):
     """audio: int16 [n_utt, >=31744] (or 1-D single utterance). Returns the dict of ``Context.kws``. exact: True gives the
-    features, logits and argmax of the reference's float64 host flow (``Context.kws_exact``); None keeps the context's mode."""
+    features, logits and argmax of the reference's float64 host flow (``Context.kws_exact``); None keeps the context's mode.
+    geometry: a ``kws.geometry.KwsGeometry`` for a graph trained at another MFCC geometry -- each utterance is zero-padded or cut to
+    geometry.n_samples and goes through ``Context.kws_geom`` (float64 features already; `exact` does not apply)."""
     ctx = ctx or default_context()
     a = np.atleast_2d(np.asarray(audio, dtype=np.int16))
+    if geometry is not None:
+        a = np.stack([pad_or_cut(row, geometry.n_samples) for row in a])
+        return ctx.kws_geom(np.ascontiguousarray(a), geometry, n_utt=a.shape[0], utt_stride=geometry.n_samples)
     return ctx.kws(np.ascontiguousarray(a), n_utt=a.shape[0], utt_stride=a.shape[1], exact=exact)
 
 
@@ -57,7 +62,20 @@ def report(res, i=0, out=None):
     return KEYWORDS[k]
 
 
-def file_inference(path, pad_mode="zero", ctx=None, verbose=True, exact=None):
+def file_inference(path, pad_mode="zero", ctx=None, verbose=True, exact=None, geometry=None):
+    """One wav through the host flow. geometry: the MFCC geometry of a graph trained at another one (``kws.geometry.KwsGeometry``);
+    the wav is then padded or cut to geometry.n_samples and runs through ``Context.kws_geom``. None: audio/config.py's, as before."""
+    if geometry is not None:
+        data = pad_or_cut(read_wav(path), n=geometry.n_samples, mode=pad_mode)
+        res = infer_utterances(data, ctx, geometry=geometry)
+        k = int(res["argmax"][0])
+        res["keyword"] = KEYWORDS[k] if res["logits"].shape[1] == len(KEYWORDS) else str(k)
+        if verbose:
+            print('net input (int8, %dx%d):' % (geometry.frame_count, geometry.num_mfcc))
+            print(res["feat"].reshape(geometry.frame_count, geometry.num_mfcc))
+            if res["softmax"] is not None and res["softmax"].shape[1] == len(KEYWORDS):
+                report(res)
+        return res
     data = pad_or_cut(read_wav(path), mode=pad_mode)
     res = infer_utterances(data, ctx, exact=exact)
     res["keyword"] = KEYWORDS[int(res["argmax"][0])]

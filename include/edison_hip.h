@@ -318,6 +318,36 @@ int edison_kws_batch_dev(edison_ctx *ctx, const int16_t *audio, int64_t n_utt, i
                          int8_t *feat, int8_t *logits, int8_t *softmax, int32_t *argmax);
 
 /*
+ * Keyword spotting for a graph trained at ANY MFCC geometry: the general audio -> class path. The fixed-shape entry points above and
+ * below (edison_kws_batch*, the sharded and streaming calls) stay as they are: 1024-sample frames, 32 mel bins, 31x13x1 -> 10 graphs.
+ * The geometry is what the reference's training flow reads from audio/config.py (kws_keras.py:443-468, kws_nnom.py:352-361):
+ *   variant        EDISON_MFCC_A or EDISON_MFCC_B, B optionally | EDISON_MFCC_USE_LOG (TF and C: EDISON_E_NO_IMPL)
+ *   frame_len      4 .. 4096 (EDISON_E_NO_IMPL outside); frame_step >= 1; n_samples >= frame_len per utterance
+ *   frame_count    frames per utterance; 0: 1 + (n_samples - frame_len) / frame_step
+ *   mel_nbins      1 .. 256 (EDISON_E_NO_IMPL outside), with the filterbank sample_rate, lower / upper_edge_hertz, mel_mtx_scale
+ *   first_mfcc, num_mfcc  the coefficients handed to the network (first_mfcc + num_mfcc <= mel_nbins)
+ *   net_input_scale       feature = int8(round half even(clip((float)mfcc * scale, -128, 127)))
+ * Utterance u's frame f starts at audio + u * utt_stride + f * frame_step; its feature (f, c - first_mfcc) is element
+ * u * in_n + f * num_mfcc + (c - first_mfcc) of the network input (the reference's flat reshape, whatever the graph's h, w, c).
+ * frame_count * num_mfcc must equal the loaded graph's in_h * in_w * in_c (EDISON_E_SIZE otherwise). The MFCC runs in float64 like
+ * the reference (FFT radix 2/3/4/5 for frame_len = 2^a 3^b 5^c, a direct DFT for other lengths), so the features, logits, softmax
+ * and argmax are the reference host flow's; the graph runs on the network kernel edison_net_batch_dev picks for it. feat may be NULL
+ * (context scratch); softmax may be NULL and is not written for a graph without Softmax. The filterbank, twiddle and DCT tables are
+ * cached in the context for the last geometry: a call at that geometry allocates nothing and does not synchronise, a call at another
+ * one synchronises the stream once. edison_mfcc_configure and the exact KWS mode neither affect this call nor are affected by it.
+ */
+typedef struct edison_kws_geom {
+	int32_t variant;
+	int32_t frame_len, frame_step, n_samples, frame_count;
+	int32_t mel_nbins, first_mfcc, num_mfcc;
+	double sample_rate, lower_edge_hertz, upper_edge_hertz, mel_mtx_scale, net_input_scale;
+} edison_kws_geom;
+/* audio/config.py's values: variant B without log, 1024 / 1024, 32000 samples, 32 mel bins 80 .. 7600 Hz, scale 128, first 13, 1.0 */
+void edison_kws_geom_default(edison_kws_geom *g);
+int edison_kws_geom_batch_dev(edison_ctx *ctx, const edison_kws_geom *g, const int16_t *audio, int64_t n_utt, int64_t utt_stride,
+                              int8_t *feat, int8_t *logits, int8_t *softmax, int32_t *argmax);
+
+/*
  * Exact KWS mode (off by default; EDISON_KWS_EXACT=1 in the environment at edison_init turns it on for that context).
  * While it is on, every variant-B KWS call of the context -- edison_kws_batch, edison_kws_batch_dev and the sharded entry points --
  * aims at features, logits and argmax identical to the host flow's float64 arithmetic (mfcc_mcu, then float32 * scale, clip,
@@ -372,6 +402,8 @@ int edison_cnn_batch(edison_ctx *ctx, const int8_t *feat, int64_t n_utt, int8_t 
 int edison_cnn_layers(edison_ctx *ctx, const int8_t *feat, int64_t n_utt, int8_t *acts);
 int edison_kws_batch(edison_ctx *ctx, const int16_t *audio, int64_t n_utt, int64_t utt_stride, int8_t *feat,
                      int8_t *logits, int8_t *softmax, int32_t *argmax);
+int edison_kws_geom_batch(edison_ctx *ctx, const edison_kws_geom *g, const int16_t *audio, int64_t n_utt, int64_t utt_stride,
+                          int8_t *feat, int8_t *logits, int8_t *softmax, int32_t *argmax);
 
 /* ---- continuous-microphone mode ------------------------------------------------------------------------
  * The firmware's appMicMfccInfereContinuous / appAudioEvent loop (firmware/src/app.c:288-371, 635-663): every new
