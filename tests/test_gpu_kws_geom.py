@@ -67,18 +67,8 @@ def _signals(n_utt, n_samples, seed):
 
 def _oracle_feat(oracle, rows, g, starts=None):
     """The reference's int8 features of each utterance: rows [n][>= span] int16 (or a flat stream with `starts`)."""
-    ov = oracle.VARIANT_A if g.variant == 0 else oracle.VARIANT_B
-    F = g.frame_count
-    span = (F - 1) * g.frame_step + g.frame_len
-    n = len(starts) if starts is not None else rows.shape[0]
-    out = np.zeros((n, g.n_features), np.int8)
-    for u in range(n):
-        x = rows[starts[u]:starts[u] + span] if starts is not None else rows[u, :span]
-        m = oracle.mfcc_numpy(x, ov, g.frame_len, g.frame_step, n_frames=F, num_mel_bins=g.mel_nbins, sample_rate=g.sample_rate,
-                              lower_edge_hertz=g.lower_edge_hertz, upper_edge_hertz=g.upper_edge_hertz, mel_mtx_scale=g.mel_mtx_scale,
-                              use_log=g.use_log)
-        out[u] = oracle.net_input(m[:, g.first_mfcc:g.first_mfcc + g.num_mfcc], n_coef=g.num_mfcc, scale=g.net_input_scale).reshape(-1)
-    return out
+    import geom_sweep
+    return geom_sweep.oracle_feat(oracle, geom_sweep.oracle_mfcc(oracle, rows, g, starts), g)
 
 
 def _same(got, want, what):

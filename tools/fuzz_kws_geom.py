@@ -1,7 +1,11 @@
 """Fuzz of the any-geometry KWS features (edison_kws_geom_batch) against the reference host flow restated (oracle.mfcc_numpy, float64,
-then oracle.net_input), >= 1 M frames over the five geometries of tests/test_gpu_kws_geom.py and its signal mix.
+then oracle.net_input), >= 1 M frames over the five geometries of tests/test_gpu_kws_geom.py and its signal mix -- or, with --sweep,
+over the rows of tests/geom_sweep.py (every code path of the kernel; each row at the sensitive net_input_scale and with the one-Dense
+graph of tests/test_gpu_geom_sweep.py, its level-normalised signal mix).
 
-    python tools/fuzz_kws_geom.py [--frames-per-geometry 210000] [--seed 1] [--jobs 8]
+    python tools/fuzz_kws_geom.py [--sweep] [--frames-per-geometry N] [--seed 1] [--jobs 8]
+
+--frames-per-geometry defaults to 210 000 for the five geometries and to max(20 000, 1.05 M / rows) with --sweep.
 
 One JSON line per geometry: frames, features compared, differences. A difference is listed with its utterance, frame and coefficient,
 the two int8 values and the distance of the oracle's float32 value (mfcc * scale) to the nearest rounding boundary x.5 -- it is a
@@ -21,40 +25,65 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def _oracle_chunk(job):
-    name, lo, audio = job
+    g, lo, audio = job
     from oracle import oracle
-    from test_gpu_kws_geom import GEOMS, _geom, _oracle_feat
-    return lo, _oracle_feat(oracle, audio, _geom(**GEOMS[name]))
+    from test_gpu_kws_geom import _oracle_feat
+    return lo, _oracle_feat(oracle, audio, g)
+
+
+def _cases(args):
+    """name -> (geometry, audio [n_utt][n_samples], a function that loads the row's graph into a context)."""
+    from test_gpu_kws_geom import GEOMS, _geom, _header, _signals
+    out = {}
+    if not args.sweep:
+        for name in sorted(GEOMS):
+            g = _geom(**GEOMS[name])
+            n_utt = -(-args.frames_per_geometry // g.frame_count)
+            out[name] = (g, _signals(n_utt, g.n_samples, args.seed), lambda c, name=name: c.load_weights_h(_header(name)))
+        return out
+    from dataclasses import replace
+    from oracle import oracle
+    import geom_sweep as gs
+    for name in sorted(gs.ROWS):
+        g = gs.geometry(name)
+        # the scale of tests/test_gpu_geom_sweep.py: from the oracle's coefficients over the test's own audio of the row
+        g = replace(g, net_input_scale=gs.sensitive_scale(gs.oracle_mfcc(oracle, gs.signals(name, g, gs.min_frames(name)), g)))
+        out[name] = (g, gs.signals(name, g, args.frames_per_geometry, seed=args.seed),
+                     lambda c, name=name, g=g: c.load_model_bytes(gs.dense_graph(g, seed=sorted(gs.ROWS).index(name))))
+    return out
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--frames-per-geometry", type=int, default=210000)
+    ap.add_argument("--sweep", action="store_true", help="the rows of tests/geom_sweep.py instead of the five geometries")
+    ap.add_argument("--frames-per-geometry", type=int, default=0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--jobs", type=int, default=max(1, min(16, os.cpu_count() or 1)))
     args = ap.parse_args()
     from oracle import oracle
     oracle.build()
-    from test_gpu_kws_geom import GEOMS, _geom, _header, _signals
-    plan, want, audios = {}, {}, {}
-    for name in sorted(GEOMS):
-        g = _geom(**GEOMS[name])
-        n_utt = -(-args.frames_per_geometry // g.frame_count)
+    if not args.frames_per_geometry:
+        if args.sweep:
+            import geom_sweep as gs
+            args.frames_per_geometry = max(20000, -(-1050000 // len(gs.ROWS)))
+        else:
+            args.frames_per_geometry = 210000
+    cases = _cases(args)
+    plan, want = {}, {}
+    for name, (g, audio, _) in cases.items():
+        n_utt = audio.shape[0]
         plan[name] = n_utt
-        audios[name] = _signals(n_utt, g.n_samples, args.seed)
         step = -(-n_utt // (4 * args.jobs))
-        jobs = [(name, lo, audios[name][lo:lo + step]) for lo in range(0, n_utt, step)]
+        jobs = [(g, lo, audio[lo:lo + step]) for lo in range(0, n_utt, step)]
         want[name] = np.zeros((n_utt, g.n_features), np.int8)
         with ProcessPoolExecutor(args.jobs) as ex:
             for lo, f in ex.map(_oracle_chunk, jobs):
                 want[name][lo:lo + f.shape[0]] = f
     from edison_amd.context import Context
     total = 0
-    for name in sorted(GEOMS):
-        g = _geom(**GEOMS[name])
+    for name, (g, audio, load) in cases.items():
         c = Context(0, model_path=None)
-        c.load_weights_h(_header(name))
-        audio = audios[name]
+        load(c)
         got = c.kws_geom(audio, g)["feat"]
         bad = np.argwhere(got != want[name])
         finds = []
@@ -69,7 +98,8 @@ def main():
                               to_boundary=abs(abs(v - np.floor(v)) - 0.5)))
         frames = plan[name] * g.frame_count
         total += frames
-        print(json.dumps(dict(geometry=name, frame_len=g.frame_len, utts=plan[name], frames=frames, features=int(got.size),
+        print(json.dumps(dict(geometry=name, frame_len=g.frame_len, mel_nbins=g.mel_nbins, net_input_scale=g.net_input_scale, utts=plan[name],
+                              frames=frames, features=int(got.size),
                               differences=int(bad.shape[0]), findings=finds)), flush=True)
         c.close()
     print(json.dumps(dict(total_frames=total)), flush=True)
