@@ -46,6 +46,12 @@ class KwsGeom(ctypes.Structure):
                [(k, c_double) for k in ("sample_rate", "lower_edge_hertz", "upper_edge_hertz", "mel_mtx_scale", "net_input_scale")]
 
 
+class StreamGeomOpts(ctypes.Structure):
+    """edison_stream_geom_opts"""
+    _fields_ = [("chunk_frames", ctypes.c_int32), ("filter", ctypes.c_int32), ("fsm", ctypes.c_int32), ("filter_alpha", c_double),
+                ("true_threshold", c_double)]
+
+
 class Fsm(ctypes.Structure):
     """edison_fsm"""
     _fields_ = [("state", c_int), ("hot_timeout_ms", ctypes.c_uint32), ("wake_idx", c_int), ("loc_idx", c_int),
@@ -141,6 +147,18 @@ SIGNATURES = {
     "edison_stream_create_ex": (c_int, [c_void_p, ctypes.POINTER(StreamOpts), ctypes.POINTER(c_void_p)]),
     "edison_stream_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "edison_stream_filtered_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_geom_default_opts": (None, [ctypes.POINTER(StreamGeomOpts)]),
+    "edison_stream_geom_create": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), ctypes.POINTER(StreamGeomOpts), ctypes.POINTER(c_void_p)]),
+    "edison_stream_geom_destroy": (None, [c_void_p]),
+    "edison_stream_geom_reset": (c_int, [c_void_p]),
+    "edison_stream_geom_push": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_geom_push_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_geom_push_n_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_geom_frames_seen": (c_int64, [c_void_p]),
+    "edison_stream_geom_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_geom_filtered_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_geom_fsm": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "edison_stream_geom_fsm_dev": (c_int, [c_void_p, c_void_p]),
     "edison_fsm_init": (None, [ctypes.POINTER(Fsm)]),
     "edison_fsm_step": (c_int, [ctypes.POINTER(Fsm), c_float, ctypes.c_uint32, ctypes.c_uint32, c_double]),
     # legacy firmware call surface

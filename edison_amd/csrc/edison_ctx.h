@@ -170,6 +170,10 @@ private:
 int ed_ctx_ensure_scratch(edison_ctx *ctx, size_t bytes);
 /* Free the cached tables of edison_kws_geom_batch* (edison_shutdown). */
 void ed_ctx_geom_free(edison_ctx *ctx);
+/* edison_kws_geom.hip, shared with edison_stream_geom.hip: the geometry checks of edison_kws_geom (everything but the model; *frames =
+ * frames per utterance) and the table builder behind the context's cache (fills *c, whose d must be NULL; c->d stays NULL on failure). */
+int ed_kws_geom_check(edison_ctx *ctx, const edison_kws_geom *g, int *frames);
+int ed_geom_tables_build(edison_ctx *ctx, const edison_kws_geom *g, ed_geom_cache *c);
 
 /* The loaded model on 31x13x1 -> 10 features (the geometry of every kws / stream entry point): matrix-core kernel for
  * the kws_conv graph, the general kernel for any other graph of that shape. feat_stride = bytes between utterances. */

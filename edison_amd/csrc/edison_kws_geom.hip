@@ -18,15 +18,6 @@
 
 #define EDG_WAVE_TEAM_BYTES 20480 /* a frame's LDS slice that still runs on one wavefront (mfcc_geom_kernels.hip) */
 
-struct ed_geom_cache
-{
-	/* the key: everything the tables depend on */
-	int variant, N, n_mel, first, num;
-	double fs, lo, hi, scale;
-	void *d;            /* one device block: tw | taps | dct | band */
-	ed_geom_args_t tmpl; /* plan, LDS regions, scales and table pointers; the per-call fields are filled at launch */
-};
-
 extern "C" void edison_kws_geom_default(edison_kws_geom *g)
 {
 	if (!g) return;
@@ -56,7 +47,7 @@ void ed_ctx_geom_free(edison_ctx *ctx)
 }
 
 /* Checks everything but the model; *frames = frames per utterance. */
-static int check_geom(edison_ctx *ctx, const edison_kws_geom *g, int *frames)
+int ed_kws_geom_check(edison_ctx *ctx, const edison_kws_geom *g, int *frames)
 {
 	const int v = g->variant & 0xff;
 	if (v != EDISON_MFCC_A && v != EDISON_MFCC_B) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_kws_geom: variants A and B (TF and C are not on this path)");
@@ -90,18 +81,18 @@ static int plan_radices(int M, int32_t *radix)
 	return M == 1 ? n : 0;
 }
 
-/* The cached tables of g's geometry: kept when the key matches, else rebuilt (after one synchronisation, so no queued launch still
- * reads the old block). */
-static int geom_tables(edison_ctx *ctx, const edison_kws_geom *g, const ed_geom_cache **out)
+static bool geom_key_matches(const ed_geom_cache *c, const edison_kws_geom *g)
+{
+	return c->variant == (g->variant & 0xff) && c->N == g->frame_len && c->n_mel == g->mel_nbins && c->first == g->first_mfcc &&
+	       c->num == g->num_mfcc && c->fs == g->sample_rate && c->lo == g->lower_edge_hertz && c->hi == g->upper_edge_hertz &&
+	       c->scale == g->mel_mtx_scale;
+}
+
+/* Builds the tables of g's geometry into *c (key, device block, launch template); c->d must be NULL on entry. On failure c->d stays
+ * NULL. Synchronous (one upload from pageable memory). */
+int ed_geom_tables_build(edison_ctx *ctx, const edison_kws_geom *g, ed_geom_cache *c)
 {
 	const int v = g->variant & 0xff, N = g->frame_len, nm = g->mel_nbins, first = g->first_mfcc, num = g->num_mfcc;
-	ed_geom_cache *c = ctx->geom;
-	if (c && c->variant == v && c->N == N && c->n_mel == nm && c->first == first && c->num == num && c->fs == g->sample_rate &&
-	    c->lo == g->lower_edge_hertz && c->hi == g->upper_edge_hertz && c->scale == g->mel_mtx_scale)
-	{
-		*out = c;
-		return EDISON_OK;
-	}
 	const int nb = v == EDISON_MFCC_A ? N / 2 : N / 2 + 1;
 	double *W = (double *)malloc(sizeof(double) * (size_t)nb * nm);
 	if (!W) return ed_set_err(ctx, EDISON_E_NO_MEMORY, "host allocation failed");
@@ -146,22 +137,13 @@ static int geom_tables(edison_ctx *ctx, const edison_kws_geom *g, const ed_geom_
 	free(W);
 	free(band);
 
-	/* the old block may still be read by queued launches */
-	if (c)
-	{
-		const hipError_t e = hipStreamSynchronize(ctx->stream);
-		if (e != hipSuccess) { free(h); ED_HIP(ctx, e); }
-		ed_ctx_geom_free(ctx);
-	}
-	c = new (std::nothrow) ed_geom_cache();
-	if (!c) { free(h); return ed_set_err(ctx, EDISON_E_NO_MEMORY, "host allocation failed"); }
 	hipError_t e = hipMalloc(&c->d, bytes);
 	if (e == hipSuccess) e = hipMemcpy(c->d, h, bytes, hipMemcpyHostToDevice);
 	free(h);
 	if (e != hipSuccess)
 	{
 		if (c->d) (void)hipFree(c->d);
-		delete c;
+		c->d = NULL;
 		if (e == hipErrorOutOfMemory) return ed_set_err(ctx, EDISON_E_NO_MEMORY, "edison_kws_geom: table hipMalloc: out of HBM");
 		ED_HIP(ctx, e);
 	}
@@ -192,8 +174,31 @@ static int geom_tables(edison_ctx *ctx, const edison_kws_geom *g, const ed_geom_
 	a.taps = d + n_tw;
 	a.dct = d + n_tw + n_taps;
 	a.band = (const int32_t *)(d + n_tw + n_taps + n_dct);
-	ctx->geom = c;
-	*out = c;
+	return EDISON_OK;
+}
+
+/* The context's cached tables of g's geometry: kept when the key matches, else rebuilt (after one synchronisation, so no queued launch
+ * still reads the old block). */
+static int geom_tables(edison_ctx *ctx, const edison_kws_geom *g, const ed_geom_cache **out)
+{
+	ed_geom_cache *c = ctx->geom;
+	if (c && geom_key_matches(c, g))
+	{
+		*out = c;
+		return EDISON_OK;
+	}
+	ed_geom_cache *nc = new (std::nothrow) ed_geom_cache();
+	if (!nc) return ed_set_err(ctx, EDISON_E_NO_MEMORY, "host allocation failed");
+	{ const int r = ed_geom_tables_build(ctx, g, nc); if (r != EDISON_OK) { delete nc; return r; } }
+	/* the old block may still be read by queued launches */
+	if (c)
+	{
+		const hipError_t e = hipStreamSynchronize(ctx->stream);
+		if (e != hipSuccess) { (void)hipFree(nc->d); delete nc; ED_HIP(ctx, e); }
+		ed_ctx_geom_free(ctx);
+	}
+	ctx->geom = nc;
+	*out = nc;
 	return EDISON_OK;
 }
 
@@ -202,7 +207,7 @@ static int check_call(edison_ctx *ctx, const edison_kws_geom *g, const int16_t *
 {
 	if (!ctx || !g || n_utt < 0 || (!audio && n_utt > 0)) return EDISON_E_ARGUMENT;
 	if (utt_stride < 0) return ed_set_err(ctx, EDISON_E_ARGUMENT, "negative utterance stride");
-	{ const int r = check_geom(ctx, g, frames); if (r != EDISON_OK) return r; }
+	{ const int r = ed_kws_geom_check(ctx, g, frames); if (r != EDISON_OK) return r; }
 	if (!ctx->have_model) return ed_set_err(ctx, EDISON_E_NO_MODEL, "no CNN model loaded (edison_model_load)");
 	const int64_t n_feat = (int64_t)*frames * g->num_mfcc;
 	if (n_feat != ctx->net.in_n)

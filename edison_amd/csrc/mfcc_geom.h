@@ -34,6 +34,17 @@ typedef struct {
 	float feat_scale;
 } ed_geom_args_t;
 
+/* The filterbank / twiddle / DCT tables of one geometry on the device and the kernel's launch template (edison_kws_geom.hip builds
+ * them): the context's one-entry cache of edison_kws_geom_batch*, and a table set of its own in every edison_stream_geom. */
+struct ed_geom_cache
+{
+	/* the key: everything the tables depend on */
+	int variant, N, n_mel, first, num;
+	double fs, lo, hi, scale;
+	void *d;            /* one device block: tw | taps | dct | band */
+	ed_geom_args_t tmpl; /* plan, LDS regions, scales and table pointers; the per-call fields are filled at launch */
+};
+
 /* Enqueue the kernel on `stream` (mfcc_geom_kernels.hip). Returns a hipError_t. */
 extern "C" int ed_launch_mfcc_geom(const ed_geom_args_t *a, int n_cu, hipStream_t stream);
 

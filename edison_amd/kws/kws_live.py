@@ -12,7 +12,7 @@ import numpy as np
 
 from .. import config as cfg
 from ..context import KEYWORDS, default_context
-from ..stream import Fsm, Stream
+from ..stream import Fsm, GeomStream, Stream
 from .kws_host import read_wav
 
 
@@ -27,39 +27,50 @@ def netOutFilt(net_outs, alpha):
     return flt
 
 
-def run(path, q15=False, ctx=None, out=None, alpha=0.9, threshold=0.5):
+def run(path, q15=False, ctx=None, out=None, alpha=0.9, threshold=0.5, geometry=None):
+    """geometry (kws.geometry.KwsGeometry): a graph trained at that MFCC geometry, on a GeomStream whose hop is geometry.frame_step
+    (float64 features, q15 does not apply); the state machine runs, and its lines are printed, only for a graph with 10 outputs."""
     out = out or sys.stdout
     ctx = ctx or default_context()
     data = read_wav(path)
-    hop = cfg.frame_length
+    hop = cfg.frame_length if geometry is None else int(geometry.frame_step)
     n = -(-data.shape[0] // hop)
     data = np.pad(data, (0, n * hop - data.shape[0]))
     # the firmware's loop body behind the network (app.c:341-371) is part of the push: moving average, maximum, threshold and
     # edisonFSM run as the last GPU stages (Stream(fsm=True)); what comes back is the state after every inference
-    st = Stream(ctx, hop=hop, chunk_frames=n, q15=q15, output_filter=True, alpha=alpha, threshold=threshold, fsm=True)
+    if geometry is None:
+        st = Stream(ctx, hop=hop, chunk_frames=n, q15=q15, output_filter=True, alpha=alpha, threshold=threshold, fsm=True)
+        with_fsm, name = True, lambda i: KEYWORDS[i]
+    else:
+        with_fsm = ctx.net_info()["n_out"] == len(KEYWORDS)
+        st = GeomStream(ctx, geometry, chunk_frames=n, output_filter=True, alpha=alpha, threshold=threshold, fsm=with_fsm)
+        name = (lambda i: KEYWORDS[i]) if with_fsm else (lambda i: "class %d" % i)
     res = st.push(data)
     st.close()
+    shown = res["softmax"] if res["softmax"] is not None else res["logits"]   # what the filter averaged
     events = []
     before, loc, val = "RESET", -1, -1
     for i in range(n):
         likely, spotted = int(res["likely"][i]), int(res["spotted"][i])
-        line = "pred: [ " + " ".join("%2.2f" % float(v) for v in res["softmax"][i]) + " ] likely: %s" % KEYWORDS[likely]
+        line = "pred: [ " + " ".join("%2.2f" % float(v) for v in shown[i]) + " ] likely: %s" % name(likely)
         if spotted >= 0:
-            line += " spotted %s" % KEYWORDS[spotted]
-        after = Fsm.STATES[int(res["fsm_states"][i])]
-        if after != before:
-            line += "   [FSM %s -> %s]" % (before, after)
-        if before == "HOT" and after == "LOC":
-            loc = likely                                          # the location that was spotted (app.c:812-816)
-        if before == "LOC" and after == "SET":
-            val = likely                                          # ... and the value (app.c:836-840)
-        if before == "SET":                                       # the step that executes the command (app.c:850-872)
-            line += "   [%s %s]" % (KEYWORDS[loc], KEYWORDS[val])
-            events.append((KEYWORDS[loc], KEYWORDS[val]))
-        before = after
+            line += " spotted %s" % name(spotted)
+        if with_fsm:
+            after = Fsm.STATES[int(res["fsm_states"][i])]
+            if after != before:
+                line += "   [FSM %s -> %s]" % (before, after)
+            if before == "HOT" and after == "LOC":
+                loc = likely                                          # the location that was spotted (app.c:812-816)
+            if before == "LOC" and after == "SET":
+                val = likely                                          # ... and the value (app.c:836-840)
+            if before == "SET":                                       # the step that executes the command (app.c:850-872)
+                line += "   [%s %s]" % (KEYWORDS[loc], KEYWORDS[val])
+                events.append((KEYWORDS[loc], KEYWORDS[val]))
+            before = after
         print(line, file=out)
-    assert len(events) == res["fsm"]["commands"]
-    return dict(result=res, commands=events, state=before)
+    if with_fsm:
+        assert len(events) == res["fsm"]["commands"]
+    return dict(result=res, commands=events, state=before if with_fsm else None)
 
 
 def main(argv):

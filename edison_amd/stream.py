@@ -115,6 +115,93 @@ class Stream:
             self.ctx._check(self._L.edison_stream_filtered_dev(self._h, q(filtered), q(likely), q(spotted)))
 
 
+class GeomStream:
+    """Continuous keyword spotting for a graph trained at ANY MFCC geometry -- Python handle on ``edison_stream_geom_*``: the continuous
+    counterpart of ``Context.kws_geom``. The hop is ``geometry.frame_step``; the window is ``geometry.frame_count`` rows of
+    ``num_mfcc`` features, oldest first (the firmware's order, as ``Stream``). The features are the float64 host flow's at every
+    geometry, so for frames that fill a whole window the outputs equal ``Context.kws_geom`` on the same samples.
+
+    ``output_filter=True`` adds the firmware's post-processing over the graph's n_out outputs (the softmax, or the last layer's output
+    for a graph without Softmax); ``fsm=True`` puts edisonFSM behind it (graphs with 10 outputs only)."""
+
+    def __init__(self, ctx, geometry, chunk_frames=1, output_filter=False, alpha=0.9, threshold=0.5, fsm=False):
+        self.ctx = ctx or default_context()
+        self._L = _lib.lib()
+        o = _lib.StreamGeomOpts()
+        self._L.edison_stream_geom_default_opts(ctypes.byref(o))
+        o.chunk_frames = int(chunk_frames)
+        o.filter = 1 if (output_filter or fsm) else 0
+        o.fsm = 1 if fsm else 0
+        o.filter_alpha, o.true_threshold = float(alpha), float(threshold)
+        g = geometry.to_ctypes()
+        h = ctypes.c_void_p()
+        self.ctx._check(self._L.edison_stream_geom_create(self.ctx._h, ctypes.byref(g), ctypes.byref(o), ctypes.byref(h)))
+        self._h = h
+        info = self.ctx.net_info()
+        self.geometry = geometry
+        self.hop, self.chunk = int(geometry.frame_step), int(chunk_frames)
+        self.n_out, self.has_softmax = int(info["n_out"]), bool(info["has_softmax"])
+        self.output_filter, self.fsm = bool(output_filter or fsm), bool(fsm)
+        self._fsm = _lib.Fsm()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.edison_stream_geom_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self.ctx._check(self._L.edison_stream_geom_reset(self._h))
+
+    @property
+    def frames_seen(self):
+        return int(self._L.edison_stream_geom_frames_seen(self._h))
+
+    def push(self, samples):
+        """samples: chunk_frames * hop new int16 samples (host). Returns dict(logits, softmax, argmax) [chunk][n_out] / [chunk] (softmax
+        None for a graph without Softmax), ``keywords`` for a graph with 10 outputs, and with the filter filtered [chunk][n_out] fp32,
+        likely, spotted (-1 = below the threshold); with the state machine fsm_states and fsm (Stream.fsm_snapshot's dict)."""
+        x = np.ascontiguousarray(samples, dtype=np.int16).ravel()
+        if x.shape[0] != self.chunk * self.hop:
+            raise ValueError("push needs exactly chunk_frames*hop = %d samples" % (self.chunk * self.hop))
+        c, no = self.chunk, self.n_out
+        lo, am = np.zeros((c, no), np.int8), np.zeros(c, np.int32)
+        so = np.zeros((c, no), np.int8) if self.has_softmax else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self.ctx._check(self._L.edison_stream_geom_push(self._h, x.ctypes.data, lo.ctypes.data, ptr(so), am.ctypes.data))
+        out = dict(logits=lo, softmax=so, argmax=am)
+        if no == NET_OUT:
+            out["keywords"] = [KEYWORDS[i] for i in am]
+        if self.output_filter:
+            fl, li, sp = np.zeros((c, no), np.float32), np.zeros(c, np.int32), np.zeros(c, np.int32)
+            self.ctx._check(self._L.edison_stream_geom_filtered(self._h, fl.ctypes.data, li.ctypes.data, sp.ctypes.data))
+            out.update(filtered=fl, likely=li, spotted=sp)
+        if self.fsm:
+            st = np.zeros(c, np.int32)
+            self.ctx._check(self._L.edison_stream_geom_fsm(self._h, ctypes.byref(self._fsm), st.ctypes.data))
+            out.update(fsm_states=st, fsm=Stream.fsm_snapshot(self))
+        return out
+
+    def push_t(self, samples, logits=None, softmax=None, argmax=None, filtered=None, likely=None, spotted=None, n_frames=None):
+        """Device tensors (torch, int16 / int8 / int32 / fp32 on the context's GPU); asynchronous on the context's stream. n_frames <
+        chunk_frames: a ragged last push of n_frames * hop samples; every output is [n_frames][..]."""
+        n = self.chunk if n_frames is None else int(n_frames)
+        if samples.numel() != n * self.hop:
+            raise ValueError("push needs exactly n_frames*hop = %d samples" % (n * self.hop))
+        q = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        if n_frames is None:
+            self.ctx._check(self._L.edison_stream_geom_push_dev(self._h, q(samples), q(logits), q(softmax), q(argmax)))
+        else:
+            self.ctx._check(self._L.edison_stream_geom_push_n_dev(self._h, q(samples), n, q(logits), q(softmax), q(argmax)))
+        if filtered is not None or likely is not None or spotted is not None:
+            self.ctx._check(self._L.edison_stream_geom_filtered_dev(self._h, q(filtered), q(likely), q(spotted)))
+
+
 class Fsm:
     """edisonFSM (app.c:727-928): RESET -> IDLE -> HOT (wake word) -> LOC (location) -> SET (value) -> IDLE."""
     STATES = ("RESET", "IDLE", "HOT", "LOC", "SET")

@@ -465,6 +465,60 @@ struct edison_fsm;
 int edison_stream_fsm(edison_stream *s, struct edison_fsm *fsm /* host */, int32_t *states /* host */);
 int edison_stream_fsm_dev(edison_stream *s, int32_t *states /* device */);
 
+/* ---- continuous mode for a graph trained at ANY MFCC geometry ------------------------------------------
+ * The continuous counterpart of edison_kws_geom_batch*: the firmware's continuous loop (app.c:288-371, 706-719) for the loaded graph at
+ * the geometry g (variants A / B, float64 MFCC: the features, logits, softmax and argmax are the reference host flow's, at every
+ * geometry, the shipped one included). The fixed-shape edison_stream_* above is a separate object and stays as it is.
+ *   hop and window  the hop is g->frame_step: a push carries chunk_frames * frame_step new samples. The window is F = frame_count rows of
+ *                   num_mfcc int8 features (as edison_kws_geom); F * num_mfcc must equal the graph's in_h * in_w * in_c.
+ *   start state     T = max(0, frame_len - frame_step) samples of silence and F - 1 rows of int8 zeros (the firmware's static buffers).
+ *   frames          with z = the recording behind T zeros, global frame k is the MFCC of z[k * frame_step .. k * frame_step + frame_len);
+ *                   when frame_step > frame_len the rest of each hop is skipped.
+ *   outputs         output i of a push is the graph on rows k - F + 1 .. k, oldest first (the firmware's order and the batch call's
+ *                   flat reshape), k = the push's i-th new frame. For k >= F - 1 it is bit-identical to edison_kws_geom_batch on z at
+ *                   offset (k - F + 1) * frame_step. logits / softmax [n][n_out] int8, argmax [n] int32, each may be NULL; softmax is
+ *                   not written for a graph without Softmax.
+ *   filter          (opts.filter) the firmware's post-processing (app.c:332-356) over the graph's n_out outputs: float32 state starting at
+ *                   zero, state = (float)(alpha * state + (1 - alpha) * (float)x) with product and sum rounded separately in double,
+ *                   first maximum, spotted if that maximum > true_threshold. x = the softmax output, or the last layer's output for a
+ *                   graph without Softmax. n_out above 256 (one workgroup): EDISON_E_NO_IMPL.
+ *   fsm             (opts.fsm, needs filter) edisonFSM behind the filter (as edison_stream_opts.fsm) with dt_us = floor(frame_step *
+ *                   1e6 / sample_rate); only for a graph with 10 outputs, the keyword list its roles index (EDISON_E_NO_IMPL otherwise).
+ * Errors of create: the geometry checks and codes of edison_kws_geom; EDISON_E_NO_MODEL without a model; EDISON_E_SIZE when F * num_mfcc
+ * != in_n or chunk_frames * frame_step >= 2^30; EDISON_E_ARGUMENT for chunk_frames < 1, fsm without filter or alpha outside [0, 1].
+ * A push after a model reload fails with EDISON_E_ARGUMENT (create a new stream).
+ * A device push is asynchronous on the context's stream: it allocates nothing and does not synchronise (MFCC kernel on the sliding
+ * sample buffer, the network over the n overlapping windows at an input stride of num_mfcc bytes, the filter, and -- only when the next
+ * push would not fit -- the history shift). A host push stages through pinned memory on a private stream and synchronises it. Host and
+ * device pushes may alternate: they share one history. The stream owns its own tables: edison_kws_geom_batch* at another geometry on
+ * the same context neither frees them nor makes a push synchronise. */
+typedef struct edison_stream_geom edison_stream_geom;
+typedef struct edison_stream_geom_opts {
+	int32_t chunk_frames;          /* new frames per push, >= 1 */
+	int32_t filter;                /* 1: moving average, first maximum and threshold over the graph's n_out outputs */
+	int32_t fsm;                   /* 1 (needs filter): edisonFSM behind the filter; only for a graph with 10 outputs */
+	double filter_alpha, true_threshold;
+} edison_stream_geom_opts;
+/* chunk_frames 1, filter 0, fsm 0, alpha 0.9, threshold 0.5: the fixed stream's defaults */
+void edison_stream_geom_default_opts(edison_stream_geom_opts *o);
+int edison_stream_geom_create(edison_ctx *ctx, const edison_kws_geom *g, const edison_stream_geom_opts *o, edison_stream_geom **out);
+void edison_stream_geom_destroy(edison_stream_geom *s);
+int edison_stream_geom_reset(edison_stream_geom *s);
+/* chunk_frames * frame_step new samples; outputs [chunk_frames][..] */
+int edison_stream_geom_push(edison_stream_geom *s, const int16_t *samples /* host */, int8_t *logits, int8_t *softmax, int32_t *argmax);
+int edison_stream_geom_push_dev(edison_stream_geom *s, const int16_t *samples /* device */, int8_t *logits, int8_t *softmax, int32_t *argmax);
+/* 1 <= n_frames <= chunk_frames new frames (n_frames * frame_step samples, outputs [n_frames][..]): the ragged last push of a recording */
+int edison_stream_geom_push_n_dev(edison_stream_geom *s, const int16_t *samples /* device */, int n_frames, int8_t *logits, int8_t *softmax,
+                                  int32_t *argmax);
+int64_t edison_stream_geom_frames_seen(const edison_stream_geom *s);
+/* Filtered outputs of the LAST push (n = its frames): filt [n][n_out] fp32, likely [n], spotted [n] (-1 below the threshold); each
+ * may be NULL. Host form synchronous, device form ordered on the context's stream. */
+int edison_stream_geom_filtered(edison_stream_geom *s, float *filt, int32_t *likely, int32_t *spotted);
+int edison_stream_geom_filtered_dev(edison_stream_geom *s, float *filt, int32_t *likely, int32_t *spotted);
+/* The state machine after the LAST push (*fsm, host, may be NULL) and the state after each of its n inferences (states [n]) */
+int edison_stream_geom_fsm(edison_stream_geom *s, struct edison_fsm *fsm, int32_t *states);
+int edison_stream_geom_fsm_dev(edison_stream_geom *s, int32_t *states);
+
 /* ---- the firmware's home-automation state machine (edisonFSM, app.c:727-928), host side, without the LEDs -------
  * RESET -> IDLE -(wake word "edison" spotted)-> HOT -(a location spotted)-> LOC -(a value spotted)-> SET -> IDLE;
  * HOT and LOC fall back to IDLE after EDI_LOC_TIMEOUT = 5000 ms (app.c:48). Time advances by dt_us per call exactly
