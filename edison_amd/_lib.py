@@ -117,6 +117,8 @@ SIGNATURES = {
     "edison_kws_geom_default": (None, [ctypes.POINTER(KwsGeom)]),
     "edison_kws_geom_batch_dev": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "edison_kws_geom_batch": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_mfcc_geom_batch_dev": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), c_void_p, c_int64, c_int64, c_void_p]),
+    "edison_mfcc_geom_batch": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), c_void_p, c_int64, c_int64, c_void_p]),
     "edison_kws_set_exact": (c_int, [c_void_p, c_int]),
     "edison_kws_get_exact": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "edison_kws_exact_stats": (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),

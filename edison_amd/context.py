@@ -310,6 +310,28 @@ class Context:
         self._check(self._L.edison_kws_geom_batch_dev(self._h, ctypes.byref(g), _t_ptr(audio), int(n_utt), int(utt_stride), _t_ptr(feat),
                                                       _t_ptr(logits), _t_ptr(softmax), _t_ptr(argmax)))
 
+    def mfcc_geom(self, audio, geometry, n_utt=None, utt_stride=None):
+        """Float64 MFCC at `geometry` (kws.geometry.KwsGeometry) in one call, no model needed (edison_mfcc_geom_batch): utterances as in
+        ``kws_geom``. Returns float64 [n_utt][frame_count][num_mfcc], the unscaled coefficients first_mfcc .. first_mfcc + num_mfcc - 1
+        that ``kws_geom`` rounds to its int8 features (net_input_scale is not applied)."""
+        x = np.ascontiguousarray(audio, dtype=np.int16).ravel()
+        stride = int(geometry.n_samples if utt_stride is None else utt_stride)
+        used = (geometry.frame_count - 1) * geometry.frame_step + geometry.frame_len
+        if n_utt is None:
+            n_utt = 0 if x.shape[0] < used else 1 + (x.shape[0] - used) // max(stride, 1)
+        if n_utt > 0 and (n_utt - 1) * stride + used > x.shape[0]:
+            raise ValueError("audio too short for %d utterances" % n_utt)
+        out = np.zeros((n_utt, geometry.frame_count, geometry.num_mfcc), np.float64)
+        g = geometry.to_ctypes()
+        self._check(self._L.edison_mfcc_geom_batch(self._h, ctypes.byref(g), _np_ptr(x), int(n_utt), stride, _np_ptr(out)))
+        return out
+
+    def mfcc_geom_t(self, audio, geometry, n_utt, utt_stride, out):
+        """edison_mfcc_geom_batch_dev on torch device tensors: `out` float64 [n_utt][frame_count][num_mfcc], enqueued on the context's
+        stream (use_torch_stream), no host synchronisation."""
+        g = geometry.to_ctypes()
+        self._check(self._L.edison_mfcc_geom_batch_dev(self._h, ctypes.byref(g), _t_ptr(audio), int(n_utt), int(utt_stride), _t_ptr(out)))
+
     # ------------------------------------------------------------------ device (torch tensor) entry points
     def mfcc_t(self, audio, n_frames, frame_step=FRAME_LEN, variant=MFCC_B, n_coef=NUM_MFCC, out=None, feat=None,
                feat_scale=1.0, use_log=False):

@@ -202,12 +202,24 @@ static int geom_tables(edison_ctx *ctx, const edison_kws_geom *g, const ed_geom_
 	return EDISON_OK;
 }
 
-/* Argument, geometry and model checks shared by both forms; *frames = frames per utterance. */
-static int check_call(edison_ctx *ctx, const edison_kws_geom *g, const int16_t *audio, int64_t n_utt, int64_t utt_stride, int *frames)
+/* Argument and geometry checks shared by every form; *frames = frames per utterance. */
+static int check_audio(edison_ctx *ctx, const edison_kws_geom *g, const int16_t *audio, int64_t n_utt, int64_t utt_stride, int *frames)
 {
 	if (!ctx || !g || n_utt < 0 || (!audio && n_utt > 0)) return EDISON_E_ARGUMENT;
 	if (utt_stride < 0) return ed_set_err(ctx, EDISON_E_ARGUMENT, "negative utterance stride");
-	{ const int r = ed_kws_geom_check(ctx, g, frames); if (r != EDISON_OK) return r; }
+	return ed_kws_geom_check(ctx, g, frames);
+}
+
+static int check_n_frames(edison_ctx *ctx, int64_t n_utt, int frames)
+{
+	if (n_utt * (int64_t)frames >= ((int64_t)1 << 31)) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_kws_geom: more than 2^31 frames in one call");
+	return EDISON_OK;
+}
+
+/* Argument, geometry and model checks shared by both forms of edison_kws_geom_batch; *frames = frames per utterance. */
+static int check_call(edison_ctx *ctx, const edison_kws_geom *g, const int16_t *audio, int64_t n_utt, int64_t utt_stride, int *frames)
+{
+	{ const int r = check_audio(ctx, g, audio, n_utt, utt_stride, frames); if (r != EDISON_OK) return r; }
 	if (!ctx->have_model) return ed_set_err(ctx, EDISON_E_NO_MODEL, "no CNN model loaded (edison_model_load)");
 	const int64_t n_feat = (int64_t)*frames * g->num_mfcc;
 	if (n_feat != ctx->net.in_n)
@@ -216,7 +228,43 @@ static int check_call(edison_ctx *ctx, const edison_kws_geom *g, const int16_t *
 		         (long long)n_feat, ctx->net.in_n);
 		return EDISON_E_SIZE;
 	}
-	if (n_utt * (int64_t)*frames >= ((int64_t)1 << 31)) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_kws_geom: more than 2^31 frames in one call");
+	return check_n_frames(ctx, n_utt, *frames);
+}
+
+/* edison_mfcc_geom_batch*: no model; mfcc must be given when there is anything to compute. */
+static int check_mfcc_call(edison_ctx *ctx, const edison_kws_geom *g, const int16_t *audio, int64_t n_utt, int64_t utt_stride, const double *mfcc,
+                           int *frames)
+{
+	{ const int r = check_audio(ctx, g, audio, n_utt, utt_stride, frames); if (r != EDISON_OK) return r; }
+	if (!mfcc && n_utt > 0) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_mfcc_geom_batch: mfcc is NULL");
+	return check_n_frames(ctx, n_utt, *frames);
+}
+
+/* The kernel's arguments for n_utt utterances of F frames at g, on the cached tables c (feat / feat_scale left to the caller). */
+static ed_geom_args_t launch_args(const ed_geom_cache *c, const edison_kws_geom *g, const int16_t *audio, int64_t n_utt, int64_t utt_stride, int F)
+{
+	ed_geom_args_t a = c->tmpl;
+	a.audio = audio;
+	a.utt_stride = utt_stride;
+	a.frame_step = g->frame_step;
+	a.frames_per_utt = F;
+	a.n_frames = (int32_t)(n_utt * F);
+	a.take_log = (g->variant & 0xff) == EDISON_MFCC_A || (g->variant & EDISON_MFCC_USE_LOG);
+	return a;
+}
+
+/* Samples a host-pointer call stages: (n_utt - 1) * utt_stride + the frames of one utterance, computed in 128 bits, refused beyond 2^46
+ * samples (as edison_mfcc_rows). */
+static int staged_samples(edison_ctx *ctx, const edison_kws_geom *g, int64_t n_utt, int64_t utt_stride, int F, const char *who, size_t *n)
+{
+	const unsigned __int128 na128 = (unsigned __int128)(n_utt - 1) * (unsigned __int128)utt_stride +
+	                                (unsigned __int128)((int64_t)(F - 1) * g->frame_step + g->frame_len);
+	if (na128 * sizeof(int16_t) > ((unsigned __int128)1 << 47))
+	{
+		snprintf(ctx->err, sizeof(ctx->err), "%s: utt_stride x n_utt too large", who);
+		return EDISON_E_SIZE;
+	}
+	*n = (size_t)na128;
 	return EDISON_OK;
 }
 
@@ -236,13 +284,7 @@ extern "C" int edison_kws_geom_batch_dev(edison_ctx *ctx, const edison_kws_geom 
 		if (r != EDISON_OK) return r;
 		f = (int8_t *)ctx->scratch;
 	}
-	ed_geom_args_t a = c->tmpl;
-	a.audio = audio;
-	a.utt_stride = utt_stride;
-	a.frame_step = g->frame_step;
-	a.frames_per_utt = F;
-	a.n_frames = (int32_t)(n_utt * F);
-	a.take_log = (g->variant & 0xff) == EDISON_MFCC_A || (g->variant & EDISON_MFCC_USE_LOG);
+	ed_geom_args_t a = launch_args(c, g, audio, n_utt, utt_stride, F);
 	a.feat = f;
 	a.feat_scale = (float)g->net_input_scale;
 	const int e = ed_launch_mfcc_geom(&a, ctx->n_cu, ctx->stream);
@@ -257,16 +299,42 @@ extern "C" int edison_kws_geom_batch(edison_ctx *ctx, const edison_kws_geom *g, 
 	int F = 0;
 	{ const int r = check_call(ctx, g, audio, n_utt, utt_stride, &F); if (r != EDISON_OK) return r; }
 	if (n_utt == 0) return EDISON_OK;
-	/* the staged samples span (n_utt - 1) * utt_stride + the frames of one utterance: computed in 128 bits, refused beyond 2^46
-	 * samples (as edison_mfcc_rows) */
-	const unsigned __int128 na128 = (unsigned __int128)(n_utt - 1) * (unsigned __int128)utt_stride +
-	                                (unsigned __int128)((int64_t)(F - 1) * g->frame_step + g->frame_len);
-	if (na128 * sizeof(int16_t) > ((unsigned __int128)1 << 47)) return ed_set_err(ctx, EDISON_E_SIZE, "edison_kws_geom_batch: utt_stride x n_utt too large");
+	size_t na = 0;
+	{ const int r = staged_samples(ctx, g, n_utt, utt_stride, F, "edison_kws_geom_batch", &na); if (r != EDISON_OK) return r; }
 	const size_t n = (size_t)n_utt, out_n = (size_t)ctx->net.out_n;
 	ed_staging st(ctx);
-	const int16_t *au = st.in(audio, (size_t)na128);
+	const int16_t *au = st.in(audio, na);
 	int8_t *f = st.scratch(feat, n * (size_t)ctx->net.in_n), *l = st.out(logits, n * out_n);
 	int8_t *s = st.out(ctx->net.has_softmax ? softmax : (int8_t *)NULL, n * out_n);
 	int32_t *am = st.out(argmax, n);
 	return st.finish(st.ok() ? edison_kws_geom_batch_dev(ctx, g, au, n_utt, utt_stride, f, l, s, am) : EDISON_OK);
+}
+
+/* ---- float64 MFCC at any geometry: ed_mfcc_geom_kernel's frames and stages, y itself stored */
+extern "C" int edison_mfcc_geom_batch_dev(edison_ctx *ctx, const edison_kws_geom *g, const int16_t *audio, int64_t n_utt, int64_t utt_stride,
+                                          double *mfcc)
+{
+	int F = 0;
+	{ const int r = check_mfcc_call(ctx, g, audio, n_utt, utt_stride, mfcc, &F); if (r != EDISON_OK) return r; }
+	if (n_utt == 0) return EDISON_OK;
+	ED_HIP(ctx, hipSetDevice(ctx->device));
+	const ed_geom_cache *c = NULL;
+	{ const int r = geom_tables(ctx, g, &c); if (r != EDISON_OK) return r; }
+	const ed_geom_args_t a = launch_args(c, g, audio, n_utt, utt_stride, F);
+	const int e = ed_launch_mfcc_geom_f64(&a, mfcc, ctx->n_cu, ctx->stream);
+	return e != 0 ? ed_launch_result(ctx, e, "float64 MFCC geometry kernel") : EDISON_OK;
+}
+
+extern "C" int edison_mfcc_geom_batch(edison_ctx *ctx, const edison_kws_geom *g, const int16_t *audio, int64_t n_utt, int64_t utt_stride,
+                                      double *mfcc)
+{
+	int F = 0;
+	{ const int r = check_mfcc_call(ctx, g, audio, n_utt, utt_stride, mfcc, &F); if (r != EDISON_OK) return r; }
+	if (n_utt == 0) return EDISON_OK;
+	size_t na = 0;
+	{ const int r = staged_samples(ctx, g, n_utt, utt_stride, F, "edison_mfcc_geom_batch", &na); if (r != EDISON_OK) return r; }
+	ed_staging st(ctx);
+	const int16_t *au = st.in(audio, na);
+	double *m = st.out(mfcc, (size_t)n_utt * (size_t)F * (size_t)g->num_mfcc);
+	return st.finish(st.ok() ? edison_mfcc_geom_batch_dev(ctx, g, au, n_utt, utt_stride, m) : EDISON_OK);
 }

@@ -47,5 +47,8 @@ struct ed_geom_cache
 
 /* Enqueue the kernel on `stream` (mfcc_geom_kernels.hip). Returns a hipError_t. */
 extern "C" int ed_launch_mfcc_geom(const ed_geom_args_t *a, int n_cu, hipStream_t stream);
+/* The same frames, stages and launch; stage 6 stores the float64 DCT row value y (unscaled, unrounded) to mfcc + g * n_coef + row
+ * instead of the int8 feature (a->feat and a->feat_scale are not read). */
+extern "C" int ed_launch_mfcc_geom_f64(const ed_geom_args_t *a, double *mfcc, int n_cu, hipStream_t stream);
 
 #endif

@@ -12,6 +12,7 @@
  *   5. mel: band j = sum of its nonzero run of the filterbank in ascending k, / mel_div; ln(x + 1e-6) for A and B with use_log
  *   6. DCT-II rows first_mfcc .. first_mfcc + num_mfcc - 1 over dct_div (A sqrt(2 mel_nbins), B 64); feature = int8 of
  *      rint(clip((float)y * feat_scale, -128, 127)) (kws_nnom.py:359-361), written to feat + g * num_mfcc + row
+ *      -- or, in the float64 instance (ed_mfcc_geom_f64_kernel, edison_mfcc_geom_batch*), y itself to mfcc + g * num_mfcc + row
  *
  * Work split: a TEAM of threads owns one frame at a time and a private LDS slice of r0 + r1 + r2 doubles (two FFT buffers -- the
  * spectrum goes to the one the FFT's result is not in -- and the mel bands); teams take frames g = team, team + n_teams, ... of the
@@ -107,118 +108,26 @@ __device__ __forceinline__ void edg_stage(const double2 *src, double2 *dst, int 
 
 template <int TEAM> __global__ __launch_bounds__(EDG_BLOCK) void ed_mfcc_geom_kernel(ed_geom_args_t a)
 {
-	extern __shared__ __attribute__((aligned(16))) double edg_lds[];
-	constexpr int TEAMS = EDG_BLOCK / TEAM;
-	const int tid = TEAM == 64 ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
-	const int team = TEAM == 64 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
-	double *r0 = edg_lds + (size_t)team * (a.r0 + a.r1 + a.r2);
-	double *r1 = r0 + a.r0, *mel = r1 + a.r1;
-	const double2 *__restrict__ tw = reinterpret_cast<const double2 *>(a.tw);
-	const int N = a.N, M = a.M, tws = a.packed ? 2 : 1;
-
-	for (int g = blockIdx.x * TEAMS + team; g < a.n_frames; g += gridDim.x * TEAMS)
-	{
-		const int u = g / a.frames_per_utt, f = g - u * a.frames_per_utt;
-		const int16_t *x = a.audio + (int64_t)u * a.utt_stride + (int64_t)f * a.frame_step;
-		edg_sync<TEAM>(); /* the previous frame's DCT has read the mel bands */
-		double *spec;
-		if (M > 0)
-		{
-			/* ---- 1. load, 2. FFT */
-			double2 *src = reinterpret_cast<double2 *>(r0), *dst = reinterpret_cast<double2 *>(r1);
-			if (a.packed)
-				for (int n = tid; n < M; n += TEAM) src[n] = make_double2((double)x[2 * n], (double)x[2 * n + 1]);
-			else
-				for (int n = tid; n < M; n += TEAM) src[n] = make_double2((double)x[n], 0.0);
-			edg_sync<TEAM>();
-			int ns = 1;
-			for (int s = 0; s < a.n_stages; s++)
-			{
-				const int R = a.radix[s];
-				if (R == 4) edg_stage<4, TEAM>(src, dst, M, ns, tws, tw, tid);
-				else if (R == 2) edg_stage<2, TEAM>(src, dst, M, ns, tws, tw, tid);
-				else if (R == 3) edg_stage<3, TEAM>(src, dst, M, ns, tws, tw, tid);
-				else edg_stage<5, TEAM>(src, dst, M, ns, tws, tw, tid);
-				edg_sync<TEAM>();
-				double2 *t = src; src = dst; dst = t;
-				ns *= R;
-			}
-			/* ---- 3. split, 4. spectrum: into the buffer the result is not in */
-			spec = reinterpret_cast<double *>(dst);
-			for (int k = tid; k < a.n_bins; k += TEAM)
-			{
-				double xr, xi;
-				if (a.packed)
-				{
-					const double2 p = src[k < M ? k : k - M], q = src[k == 0 ? 0 : M - k]; /* Z[k mod M], Z[-k mod M] */
-					const double er = 0.5 * (p.x + q.x), ei = 0.5 * (p.y - q.y);      /* E = (Z[k] + conj Z[-k]) / 2  */
-					const double orr = 0.5 * (p.y + q.y), oi = -0.5 * (p.x - q.x);    /* O = (Z[k] - conj Z[-k]) / 2i */
-					const double2 w = tw[k];
-					xr = er + (orr * w.x - oi * w.y);
-					xi = ei + (orr * w.y + oi * w.x);
-				}
-				else
-				{
-					xr = src[k].x;
-					xi = src[k].y;
-				}
-				xr *= a.fft_scale;
-				xi *= a.fft_scale;
-				spec[k] = sqrt(xr * xr + xi * xi) * a.spec_scale;
-			}
-		}
-		else
-		{
-			/* ---- 1. load, 2. direct DFT of the real frame: X[k] = sum_n x[n] W_N^(k n mod N), the index kept by addition */
-			double *xs = r0;
-			spec = r1;
-			for (int n = tid; n < N; n += TEAM) xs[n] = (double)x[n];
-			edg_sync<TEAM>();
-			for (int k = tid; k < a.n_bins; k += TEAM)
-			{
-				double sr = 0.0, si = 0.0;
-				int j = 0;
-				for (int n = 0; n < N; n++)
-				{
-					const double v = xs[n];
-					const double2 w = tw[j];
-					sr = fma(v, w.x, sr);
-					si = fma(v, w.y, si);
-					j += k;
-					if (j >= N) j -= N;
-				}
-				sr *= a.fft_scale;
-				si *= a.fft_scale;
-				spec[k] = sqrt(sr * sr + si * si) * a.spec_scale;
-			}
-		}
-		edg_sync<TEAM>();
-
-		/* ---- 5. mel bands over their nonzero taps, [ln] */
-		for (int j = tid; j < a.n_mel; j += TEAM)
-		{
-			const int k0 = a.band[3 * j], len = a.band[3 * j + 1], off = a.band[3 * j + 2];
-			double acc = 0.0;
-			for (int t = 0; t < len; t++) acc = fma(spec[k0 + t], a.taps[off + t], acc);
-			const double e = acc / a.mel_div;
-			mel[j] = a.take_log ? log(e + 1e-6) : e;
-		}
-		edg_sync<TEAM>();
-
-		/* ---- 6. DCT-II rows, the int8 feature */
-		for (int c = tid; c < a.n_coef; c += TEAM)
-		{
-			const double *d = a.dct + (size_t)c * a.n_mel;
-			double y = 0.0;
-			for (int n = 0; n < a.n_mel; n++) y = fma(mel[n], d[n], y);
-			y = y / a.dct_div;
-			const float v = fminf(fmaxf((float)y * a.feat_scale, -128.0f), 127.0f);
-			a.feat[(int64_t)g * a.n_coef + c] = (int8_t)rintf(v);
-		}
+#define EDG_STORE(i, y)                                                                        \
+	{                                                                                          \
+		const float v = fminf(fmaxf((float)(y) * a.feat_scale, -128.0f), 127.0f);            \
+		a.feat[i] = (int8_t)rintf(v);                                                          \
 	}
+#include "mfcc_geom_frames.inc"
+#undef EDG_STORE
 }
 
-extern "C" int ed_launch_mfcc_geom(const ed_geom_args_t *a, int n_cu, hipStream_t stream)
+/* The float64 instance (edison_mfcc_geom_batch*): the same frames and stages; stage 6 stores y itself, unscaled
+ * and unrounded, to mfcc [n_frames][n_coef]. a.feat and a.feat_scale are not read. */
+template <int TEAM> __global__ __launch_bounds__(EDG_BLOCK) void ed_mfcc_geom_f64_kernel(ed_geom_args_t a, double *mfcc)
+{
+#define EDG_STORE(i, y) mfcc[i] = (y);
+#include "mfcc_geom_frames.inc"
+#undef EDG_STORE
+}
+
+/* mfcc == NULL: ed_mfcc_geom_kernel (int8 features to a->feat); else ed_mfcc_geom_f64_kernel (y to mfcc) */
+static int edg_launch(const ed_geom_args_t *a, double *mfcc, int n_cu, hipStream_t stream)
 {
 	if (a->n_frames <= 0) return 0;
 	if (a->team != 64 && a->team != EDG_BLOCK) return (int)hipErrorInvalidValue;
@@ -226,7 +135,8 @@ extern "C" int ed_launch_mfcc_geom(const ed_geom_args_t *a, int n_cu, hipStream_
 	const size_t lds = sizeof(double) * (size_t)teams * (size_t)(a->r0 + a->r1 + a->r2);
 	if (a->team == 64 && lds > 4 * (size_t)EDG_WAVE_LDS_MAX) return (int)hipErrorInvalidValue;
 	if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-	const void *fn = a->team == 64 ? (const void *)ed_mfcc_geom_kernel<64> : (const void *)ed_mfcc_geom_kernel<EDG_BLOCK>;
+	const void *fn = !mfcc ? (a->team == 64 ? (const void *)ed_mfcc_geom_kernel<64> : (const void *)ed_mfcc_geom_kernel<EDG_BLOCK>)
+	                       : (a->team == 64 ? (const void *)ed_mfcc_geom_f64_kernel<64> : (const void *)ed_mfcc_geom_f64_kernel<EDG_BLOCK>);
 	{ const int e = ed_kernel_prepare(fn, EDG_BLOCK, lds, NULL, NULL); if (e) return e; }
 	/* resident workgroups: as many as the LDS admits, at most 4 per CU (16 waves); the frames are grid-strided */
 	int64_t per_cu = (int64_t)(160 * 1024) / (int64_t)lds;
@@ -234,7 +144,21 @@ extern "C" int ed_launch_mfcc_geom(const ed_geom_args_t *a, int n_cu, hipStream_
 	if (per_cu < 1) per_cu = 1;
 	int64_t blocks = ((int64_t)a->n_frames + teams - 1) / teams;
 	if (blocks > per_cu * n_cu) blocks = per_cu * n_cu;
-	if (a->team == 64) hipLaunchKernelGGL(ed_mfcc_geom_kernel<64>, dim3((unsigned)blocks), dim3(EDG_BLOCK), lds, stream, *a);
-	else hipLaunchKernelGGL(ed_mfcc_geom_kernel<EDG_BLOCK>, dim3((unsigned)blocks), dim3(EDG_BLOCK), lds, stream, *a);
+	const dim3 grid((unsigned)blocks), block(EDG_BLOCK);
+	if (mfcc)
+	{
+		if (a->team == 64) hipLaunchKernelGGL(ed_mfcc_geom_f64_kernel<64>, grid, block, lds, stream, *a, mfcc);
+		else hipLaunchKernelGGL(ed_mfcc_geom_f64_kernel<EDG_BLOCK>, grid, block, lds, stream, *a, mfcc);
+	}
+	else if (a->team == 64) hipLaunchKernelGGL(ed_mfcc_geom_kernel<64>, grid, block, lds, stream, *a);
+	else hipLaunchKernelGGL(ed_mfcc_geom_kernel<EDG_BLOCK>, grid, block, lds, stream, *a);
 	return (int)hipGetLastError();
+}
+
+extern "C" int ed_launch_mfcc_geom(const ed_geom_args_t *a, int n_cu, hipStream_t stream) { return edg_launch(a, NULL, n_cu, stream); }
+
+extern "C" int ed_launch_mfcc_geom_f64(const ed_geom_args_t *a, double *mfcc, int n_cu, hipStream_t stream)
+{
+	if (!mfcc) return (int)hipErrorInvalidValue;
+	return edg_launch(a, mfcc, n_cu, stream);
 }

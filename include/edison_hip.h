@@ -346,6 +346,19 @@ typedef struct edison_kws_geom {
 void edison_kws_geom_default(edison_kws_geom *g);
 int edison_kws_geom_batch_dev(edison_ctx *ctx, const edison_kws_geom *g, const int16_t *audio, int64_t n_utt, int64_t utt_stride,
                               int8_t *feat, int8_t *logits, int8_t *softmax, int32_t *argmax);
+/*
+ * Float64 MFCC at the same geometry, without a model: the training-side features of a graph trained at g (the reference's load_data,
+ * kws_keras.py:443-468, before its net_input_scale and clip). Frame addressing, coefficient window and arithmetic are those of
+ * edison_kws_geom_batch*: mfcc [n_utt][frame_count][num_mfcc] (device pointer; edison_mfcc_geom_batch below takes host pointers)
+ * receives the unscaled coefficient first_mfcc + c of frame f of utterance u at [u][f][c] -- the very float64 value that
+ * edison_kws_geom_batch* and edison_stream_geom round to their int8 feature. net_input_scale is not used; first_mfcc = 0,
+ * num_mfcc = mel_nbins gives whole MFCC rows. No model is needed. Errors: the geometry checks and codes of edison_kws_geom,
+ * EDISON_E_ARGUMENT for more than 2^31 frames in one call or mfcc == NULL with n_utt > 0; n_utt == 0 does nothing. The call
+ * shares the context's table cache with edison_kws_geom_batch* (same key): at the cached geometry it allocates nothing and does not
+ * synchronise, at another one it synchronises the stream once. Tables owned by an edison_stream_geom are not touched.
+ */
+int edison_mfcc_geom_batch_dev(edison_ctx *ctx, const edison_kws_geom *g, const int16_t *audio, int64_t n_utt, int64_t utt_stride,
+                               double *mfcc);
 
 /*
  * Exact KWS mode (off by default; EDISON_KWS_EXACT=1 in the environment at edison_init turns it on for that context).
@@ -404,6 +417,8 @@ int edison_kws_batch(edison_ctx *ctx, const int16_t *audio, int64_t n_utt, int64
                      int8_t *logits, int8_t *softmax, int32_t *argmax);
 int edison_kws_geom_batch(edison_ctx *ctx, const edison_kws_geom *g, const int16_t *audio, int64_t n_utt, int64_t utt_stride,
                           int8_t *feat, int8_t *logits, int8_t *softmax, int32_t *argmax);
+int edison_mfcc_geom_batch(edison_ctx *ctx, const edison_kws_geom *g, const int16_t *audio, int64_t n_utt, int64_t utt_stride,
+                           double *mfcc);
 
 /* ---- continuous-microphone mode ------------------------------------------------------------------------
  * The firmware's appMicMfccInfereContinuous / appAudioEvent loop (firmware/src/app.c:288-371, 635-663): every new
