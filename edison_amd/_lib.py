@@ -46,6 +46,11 @@ class KwsGeom(ctypes.Structure):
                [(k, c_double) for k in ("sample_rate", "lower_edge_hertz", "upper_edge_hertz", "mel_mtx_scale", "net_input_scale")]
 
 
+class FnetInfo(ctypes.Structure):
+    """edison_fnet_info_t"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("in_h", "in_w", "in_c", "n_out", "n_layers", "acts_floats", "batch", "lds_bytes")]
+
+
 class StreamGeomOpts(ctypes.Structure):
     """edison_stream_geom_opts"""
     _fields_ = [("chunk_frames", ctypes.c_int32), ("filter", ctypes.c_int32), ("fsm", ctypes.c_int32), ("filter_alpha", c_double),
@@ -119,6 +124,17 @@ SIGNATURES = {
     "edison_kws_geom_batch": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "edison_mfcc_geom_batch_dev": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), c_void_p, c_int64, c_int64, c_void_p]),
     "edison_mfcc_geom_batch": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), c_void_p, c_int64, c_int64, c_void_p]),
+    "edison_fnet_load": (c_int, [c_void_p, c_char_p]),
+    "edison_fnet_load_mem": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "edison_fnet_info": (c_int, [c_void_p, ctypes.POINTER(FnetInfo)]),
+    "edison_fnet_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "edison_fnet_layers_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "edison_fnet_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "edison_fnet_layers": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "edison_kws_float_batch_dev": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), c_int, c_float, c_float, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]),
+    "edison_kws_float_batch": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), c_int, c_float, c_float, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
     "edison_kws_set_exact": (c_int, [c_void_p, c_int]),
     "edison_kws_get_exact": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "edison_kws_exact_stats": (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),

@@ -30,6 +30,10 @@ class KwsConfig:
     nnom_net_input_scale: float = 1.0
     nnom_net_input_clip_min: int = -128
     nnom_net_input_clip_max: int = 127
+    # X-CUBE-AI float32 input (config.py:45-48): scaled, clipped to int16 range, never rounded
+    net_input_scale: float = 1.0
+    net_input_clip_min: int = -2 ** 15
+    net_input_clip_max: int = 2 ** 15 - 1
 
     # ---- derived quantities, same names as the reference module ----
     @property

@@ -332,6 +332,84 @@ class Context:
         g = geometry.to_ctypes()
         self._check(self._L.edison_mfcc_geom_batch_dev(self._h, ctypes.byref(g), _t_ptr(audio), int(n_utt), int(utt_stride), _t_ptr(out)))
 
+    # ------------------------------------------------------------------ float32 X-CUBE-AI networks (edison_fnet_*, edison_kws_float_batch*)
+    def fnet_load(self, src):
+        """Load a float network: an .ednf path or its bytes (edison_amd/cube_import.py, tools/import_cube.py). The int8 model stays."""
+        if isinstance(src, (bytes, bytearray)):
+            buf = ctypes.create_string_buffer(bytes(src), len(src))
+            self._check(self._L.edison_fnet_load_mem(self._h, buf, len(src)))
+        else:
+            self._check(self._L.edison_fnet_load(self._h, str(src).encode()))
+
+    def fnet_info(self):
+        """dict of edison_fnet_info_t: in_h, in_w, in_c, n_out, n_layers, acts_floats, batch, lds_bytes."""
+        info = _lib.FnetInfo()
+        self._check(self._L.edison_fnet_info(self._h, ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in _lib.FnetInfo._fields_}
+
+    def _fnet_in(self, x):
+        info = self.fnet_info()
+        return info, np.ascontiguousarray(x, dtype=np.float32).reshape(-1, info["in_h"] * info["in_w"] * info["in_c"])
+
+    def fnet(self, x):
+        """The Cube aiRunInference for n inputs [n][in_h*in_w*in_c] float32 (HWC): logits, probs (softmax) float32 [n][n_out], argmax."""
+        info, f = self._fnet_in(x)
+        n = f.shape[0]
+        logits = np.zeros((n, info["n_out"]), np.float32)
+        probs = np.zeros((n, info["n_out"]), np.float32)
+        am = np.zeros(n, np.int32)
+        self._check(self._L.edison_fnet_batch(self._h, _np_ptr(f), n, _np_ptr(logits), _np_ptr(probs), _np_ptr(am)))
+        return dict(logits=logits, probs=probs, argmax=am)
+
+    def fnet_layers(self, x):
+        """Every conv / dense layer's output (after bias, ReLU, pool), back to back: float32 [n][acts_floats]."""
+        info, f = self._fnet_in(x)
+        acts = np.zeros((f.shape[0], info["acts_floats"]), np.float32)
+        self._check(self._L.edison_fnet_layers(self._h, _np_ptr(f), f.shape[0], _np_ptr(acts)))
+        return acts
+
+    def kws_float(self, audio, geometry=None, q15=False, n_utt=None, utt_stride=None, clip_min=None, clip_max=None):
+        """Audio to class with the float network in one call (edison_kws_float_batch). q15=False: the reference's host flow at
+        `geometry` (kws.geometry.KwsGeometry, default audio/config.py's): float64 MFCC -> float32 x net_input_scale -> clip to
+        [clip_min, clip_max] (default config.py's -32768, 32767). q15=True: the firmware's variant C -> (float), shipped framing.
+        Utterances as in ``kws_geom``. Returns feat float32 [n_utt][frame_count * num_mfcc], logits, probs, argmax."""
+        from . import config as cfg
+        from .kws.geometry import KwsGeometry
+        if geometry is None:
+            geometry = KwsGeometry.from_config(net_input_scale=cfg.net_input_scale)
+        lo = float(cfg.net_input_clip_min if clip_min is None else clip_min)
+        hi = float(cfg.net_input_clip_max if clip_max is None else clip_max)
+        x = np.ascontiguousarray(audio, dtype=np.int16).ravel()
+        stride = int(geometry.n_samples if utt_stride is None else utt_stride)
+        used = (geometry.frame_count - 1) * geometry.frame_step + geometry.frame_len
+        if n_utt is None:
+            n_utt = 0 if x.shape[0] < used else 1 + (x.shape[0] - used) // max(stride, 1)
+        if n_utt > 0 and (n_utt - 1) * stride + used > x.shape[0]:
+            raise ValueError("audio too short for %d utterances" % n_utt)
+        info = self.fnet_info()
+        feat = np.zeros((n_utt, geometry.n_features), np.float32)
+        logits = np.zeros((n_utt, info["n_out"]), np.float32)
+        probs = np.zeros((n_utt, info["n_out"]), np.float32)
+        am = np.zeros(n_utt, np.int32)
+        g = geometry.to_ctypes()
+        self._check(self._L.edison_kws_float_batch(self._h, ctypes.byref(g), 1 if q15 else 0, lo, hi, _np_ptr(x), int(n_utt), stride,
+                                                   _np_ptr(feat), _np_ptr(logits), _np_ptr(probs), _np_ptr(am)))
+        return dict(feat=feat, logits=logits, probs=probs, argmax=am)
+
+    def kws_float_t(self, audio, geometry, n_utt, utt_stride, feat=None, logits=None, probs=None, argmax=None, q15=False, clip_min=None,
+                    clip_max=None):
+        """edison_kws_float_batch_dev on torch device tensors, enqueued on the context's stream (use_torch_stream), no host synchronisation."""
+        from . import config as cfg
+        lo = float(cfg.net_input_clip_min if clip_min is None else clip_min)
+        hi = float(cfg.net_input_clip_max if clip_max is None else clip_max)
+        g = geometry.to_ctypes()
+        self._check(self._L.edison_kws_float_batch_dev(self._h, ctypes.byref(g), 1 if q15 else 0, lo, hi, _t_ptr(audio), int(n_utt), int(utt_stride),
+                                                       _t_ptr(feat), _t_ptr(logits), _t_ptr(probs), _t_ptr(argmax)))
+
+    def fnet_t(self, x, n, logits=None, probs=None, argmax=None):
+        """edison_fnet_batch_dev on torch device tensors (x float32 [n][in_n]), on the context's stream."""
+        self._check(self._L.edison_fnet_batch_dev(self._h, _t_ptr(x), int(n), _t_ptr(logits), _t_ptr(probs), _t_ptr(argmax)))
+
     # ------------------------------------------------------------------ device (torch tensor) entry points
     def mfcc_t(self, audio, n_frames, frame_step=FRAME_LEN, variant=MFCC_B, n_coef=NUM_MFCC, out=None, feat=None,
                feat_scale=1.0, use_log=False):

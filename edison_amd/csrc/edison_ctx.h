@@ -42,6 +42,7 @@ extern "C" int ed_launch_mfcc_q15(const ed_mfcc_q15_args_t *args, const ed_q15_t
                                   int stages, int n_cu, hipStream_t stream);
 
 struct ed_geom_cache; /* edison_kws_geom.hip */
+struct ed_fnet;       /* edison_fnet.hip */
 
 struct edison_ctx
 {
@@ -102,6 +103,7 @@ struct edison_ctx
 	void *dist_scratch; /* padded send + receive blocks of edison_dist_allgather_logits_total (unequal shards) */
 	size_t dist_scratch_bytes;
 	ed_geom_cache *geom; /* edison_kws_geom_batch*: the tables of the last geometry (one entry) */
+	ed_fnet *fnet;       /* edison_fnet_load*: the loaded float32 network (edison_fnet.hip), NULL before the first load */
 	char err[512];
 };
 
@@ -170,6 +172,8 @@ private:
 int ed_ctx_ensure_scratch(edison_ctx *ctx, size_t bytes);
 /* Free the cached tables of edison_kws_geom_batch* (edison_shutdown). */
 void ed_ctx_geom_free(edison_ctx *ctx);
+/* Free the loaded float32 network (edison_shutdown; edison_fnet.hip). */
+void ed_ctx_fnet_free(edison_ctx *ctx);
 /* edison_kws_geom.hip, shared with edison_stream_geom.hip: the geometry checks of edison_kws_geom (everything but the model; *frames =
  * frames per utterance) and the table builder behind the context's cache (fills *c, whose d must be NULL; c->d stays NULL on failure). */
 int ed_kws_geom_check(edison_ctx *ctx, const edison_kws_geom *g, int *frames);

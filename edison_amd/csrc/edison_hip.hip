@@ -170,6 +170,7 @@ extern "C" void edison_shutdown(edison_ctx *ctx)
 	if (ctx->d_exact_tab) (void)hipFree(ctx->d_exact_tab);
 	if (ctx->exact_list) (void)hipFree(ctx->exact_list);
 	ed_ctx_geom_free(ctx);
+	ed_ctx_fnet_free(ctx);
 	if (ctx->pipe_ready)
 	{
 		for (int k = 0; k < 5; k++) (void)hipStreamDestroy(ctx->pipe_cand[k]);

@@ -1,0 +1,56 @@
+/*
+ * fnet.h -- the launch plan of the float32 network kernel (fnet_kernels.hip), built by its host side (edison_fnet.hip) from an .ednf
+ * blob (edison_amd/cube_import.py). Not part of the public ABI.
+ */
+#ifndef EDISON_FNET_H
+#define EDISON_FNET_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define ED_FNET_MAX_LAYERS 16
+#define ED_FNET_THREADS 512
+#define ED_FNET_MAX_BATCH 16                  /* utterances per workgroup, at most */
+#define ED_FNET_LDS_BYTES (160 * 1024)
+
+/* One conv record (a dense layer is a conv whose kernel covers its whole input). Output row r of an utterance is element e = r % P of
+ * the pool window of pooled position q = r / P (q = y * out_w + x, P = ph * pw): the P rows of a window are adjacent, so they land in
+ * one lane's accumulator registers and the pool is a max over registers. */
+typedef struct {
+	int32_t in_n, out_c, out_n;     /* in_h * in_w * in_c, out channels, out_h * out_w * out_c */
+	int32_t P;                      /* pool window elements: 1, 2 or 4                          */
+	int32_t rows;                   /* out_h * out_w * P output rows per utterance              */
+	int32_t k_pad, n_pad;           /* K = kh * kw * in_c rounded up to 4, out_c up to 16       */
+	int32_t relu;
+	int32_t src, dst;               /* LDS activation buffer read / written (0 or 1)            */
+	int32_t koff_at, rowin_at;      /* int32 offsets into tab: koff[k_pad], rowin[rows]          */
+	int32_t acts_at;                /* float offset of this layer's output in a per-layer dump  */
+	int64_t w_at;                   /* float offset into w: B[k_pad][n_pad], then bias[n_pad]   */
+} ed_fnet_layer_t;
+
+typedef struct {
+	int32_t n_layers;               /* conv records; the last one's output goes through softmax */
+	int32_t in_n, n_out;            /* network input / output floats per utterance              */
+	int32_t batch;                  /* utterances per workgroup                                  */
+	int32_t buf_n[2];               /* floats per utterance of LDS activation buffers 0 and 1   */
+	int32_t w_lds, k_lds;           /* largest layer's B + koff in LDS (floats / ints)          */
+	int32_t acts_n;                 /* floats per utterance of a per-layer dump                 */
+	const float *w;
+	const int32_t *tab;
+	ed_fnet_layer_t L[ED_FNET_MAX_LAYERS];
+} ed_fnet_plan_t;
+
+/* Dynamic LDS bytes of the plan's workgroup. */
+static inline size_t ed_fnet_lds_bytes(const ed_fnet_plan_t *p)
+{
+	return sizeof(float) * ((size_t)p->batch * (size_t)(p->buf_n[0] + p->buf_n[1]) + (size_t)p->w_lds) + sizeof(int32_t) * (size_t)p->k_lds;
+}
+
+/* n utterances in[n][in_n] -> logits / probs [n][n_out] (NULL: not written), argmax [n] (NULL: not written); acts != NULL also dumps
+ * every layer's output [n][acts_n]. Returns a hipError_t. */
+extern "C" int ed_launch_fnet(const ed_fnet_plan_t *p, const float *in, int64_t n, float *logits, float *probs, int32_t *argmax, float *acts,
+                              hipStream_t stream);
+/* The host flow's net input: out[i] = min(max((float)y[i] * scale, lo), hi) for i < count. Returns a hipError_t. */
+extern "C" int ed_launch_fnet_input(const double *y, int64_t count, float scale, float lo, float hi, float *out, int n_cu, hipStream_t stream);
+
+#endif

@@ -140,6 +140,51 @@ def single_inference(repeat=1, ctx=None, out=None):
     return res
 
 
+def _float_keywords(net):
+    from ..cube_import import read_blob
+    with open(net, "rb") as f:
+        kw = read_blob(f.read())["keywords"]
+    return kw or list(KEYWORDS)
+
+
+def float_report(host_pred, mcu_pred=None, keywords=KEYWORDS, out=None):
+    """kws_on_mcu.report (:148-157) for the float network's probabilities; without an MCU leg only the host line."""
+    out = out or sys.stdout
+    np.set_printoptions(precision=3, suppress=True)
+    print('keywords:', list(keywords), file=out)
+    print('host prediction:', host_pred, keywords[int(host_pred.argmax())], file=out)
+    if mcu_pred is not None:
+        print('mcu prediction: ', mcu_pred, keywords[int(mcu_pred.argmax())], file=out)
+        print('rmse:', rmse(host_pred, mcu_pred), file=out)
+
+
+def float_file_inference(path, net, pad_mode="zero", ctx=None, out=None):
+    """`kws mcu fileinf|frame <wav> --net <file.ednf>`: the wav through the X-CUBE-AI float network's host flow (kws_on_mcu.py:343-348,
+    net_type 'cube'): float64 MFCC variant B -> first 13 -> float32 x net_input_scale -> clip(-32768, 32767) -> the network."""
+    ctx = ctx or default_context()
+    ctx.fnet_load(net)
+    data = pad_or_cut(read_wav(path), mode=pad_mode)
+    res = ctx.kws_float(data, n_utt=1)
+    kw = _float_keywords(net)
+    float_report(res["probs"][0], keywords=kw, out=out)
+    res["keyword"] = kw[int(res["argmax"][0])] if int(res["argmax"][0]) < len(kw) else str(int(res["argmax"][0]))
+    return res
+
+
+def float_frame_inference(path, net, ctx=None, out=None):
+    """`kws mcu file <wav> --net <file.ednf>`: the host flow and the firmware's (variant C -> (float), app.c:675-683) through the float
+    network, printed as kws_on_mcu.report (:148-157) prints them, then the comparison block of the predictions."""
+    out = out or sys.stdout
+    ctx = ctx or default_context()
+    ctx.fnet_load(net)
+    data = pad_or_cut(read_wav(path), mode="edge")
+    host = ctx.kws_float(data, n_utt=1)
+    mcu = ctx.kws_float(data, n_utt=1, q15=True)
+    float_report(host["probs"][0], mcu["probs"][0], _float_keywords(net), out)
+    compare(host["probs"][0], mcu["probs"][0], 'predictions', out)
+    return dict(host=host, mcu=mcu)
+
+
 # the reference's own function names and call conventions (kws_on_mcu.py:243,273,310: `args` = the CLI's remaining
 # arguments, args[0] = the wav file)
 def singleInference(repeat=1):
@@ -157,8 +202,16 @@ def frameInference(args):
 def main(argv):
     """``kws mcu <mode> [file]`` of the reference's CLI (main.py:146-165, kws_on_mcu.py:650-690). The modes that record
     from a microphone (mic, host, hostcont, hostsingle, miccont) are not part of this port."""
+    net = None
+    if "--net" in argv:
+        i = argv.index("--net")
+        if i + 1 >= len(argv):
+            print('--net needs an .ednf file')
+            return 1
+        net = argv[i + 1]
+        argv = argv[:i] + argv[i + 2:]
     if len(argv) < 2:
-        print('usage: kws mcu <single [n] | fileinf <wav> | file <wav> | frame <wav>>')
+        print('usage: kws mcu <single [n] | fileinf <wav> | file <wav> | frame <wav>> [--net <file.ednf>]')
         return 1
     mode = argv[1]
     print('Running mode', mode, 'with args', argv[2:])
@@ -169,6 +222,12 @@ def main(argv):
         if len(argv) < 3:
             print('need a wav file')
             return 1
+        if net is not None and mode != "host":
+            if mode == "file":
+                float_frame_inference(argv[2], net)
+            else:
+                float_file_inference(argv[2], net, pad_mode="edge" if mode == "frame" else "zero")
+            return 0
         if mode == "file":
             frame_inference(argv[2])
         else:

@@ -361,6 +361,51 @@ int edison_mfcc_geom_batch_dev(edison_ctx *ctx, const edison_kws_geom *g, const 
                                double *mfcc);
 
 /*
+ * Float32 X-CUBE-AI networks: the reference's default network type (firmware/src/ai/ai.h NET_TYPE_CUBE), imported from the generated
+ * <net>.c + <net>_data.c by edison_amd/cube_import.py into an .ednf blob. Accepted: conv2d / conv2d_nl_pool (groups 1, any stride,
+ * no padding, ReLU or none, max pool of 1, 2 or 4 elements), dense, ReLU, a final softmax; activations HWC. The blob's layer list,
+ * shapes and weights are checked at load (EDISON_E_SIZE: malformed; EDISON_E_NO_IMPL: a network this path does not run, e.g. one whose
+ * activations and largest layer do not fit the LDS). A load replaces the context's previous float network (synchronising the stream
+ * once); the int8 NNoM model (edison_model_load) is separate: a context may hold both.
+ *   edison_fnet_batch  = the Cube aiRunInference for n inputs: in [n][in_h*in_w*in_c] float32 HWC -> logits [n][n_out] (the last
+ *                        layer's output before softmax), probs [n][n_out] = exp(z - max) / sum, argmax [n] the first maximum of probs;
+ *                        any output may be NULL
+ *   edison_fnet_layers = every conv / dense layer's output (after bias, ReLU and pool), back to back: acts [n][acts_floats]
+ * Arithmetic: f32-input matrix cores, exact f32 products, each output a k-ordered f32 sum (DESIGN.md section 14 has the error bound).
+ * EDISON_E_NO_MODEL when no float network is loaded.
+ */
+typedef struct edison_fnet_info_t {
+	int32_t in_h, in_w, in_c; /* network input (rows = frames, columns = coefficients, channels)            */
+	int32_t n_out;
+	int32_t n_layers;         /* conv / dense layers (ReLU folded in, softmax not counted)                  */
+	int32_t acts_floats;      /* floats per input of edison_fnet_layers                                    */
+	int32_t batch;            /* utterances per workgroup of the kernel                                    */
+	int32_t lds_bytes;        /* LDS per workgroup                                                         */
+} edison_fnet_info_t;
+int edison_fnet_load(edison_ctx *ctx, const char *ednf_path);
+int edison_fnet_load_mem(edison_ctx *ctx, const void *blob, size_t blob_bytes);
+int edison_fnet_info(edison_ctx *ctx, edison_fnet_info_t *out);
+int edison_fnet_batch_dev(edison_ctx *ctx, const float *in, int64_t n, float *logits, float *probs, int32_t *argmax);
+int edison_fnet_layers_dev(edison_ctx *ctx, const float *in, int64_t n, float *acts);
+int edison_fnet_batch(edison_ctx *ctx, const float *in, int64_t n, float *logits, float *probs, int32_t *argmax);
+int edison_fnet_layers(edison_ctx *ctx, const float *in, int64_t n, float *acts);
+/*
+ * Audio -> class with the float network in one call (the Cube flow), utterances addressed as in edison_kws_geom_batch*:
+ *   q15 = 0  the reference's host flow (kws_on_mcu.py:343-348): the float64 MFCC of edison_mfcc_geom_batch at g (any geometry) ->
+ *            float32 -> x (float)net_input_scale -> clip to [clip_lo, clip_hi] (audio/config.py: -32768, 32767), never rounded
+ *   q15 = 1  the firmware's flow (app.c:675-683): variant C int16 coefficients 0 .. num_mfcc - 1 -> (float), no scale, no clip; the
+ *            shipped framing only (frame_len = frame_step = 1024, mel_nbins 32, first_mfcc 0; EDISON_E_NO_IMPL otherwise), on the
+ *            context's configured filterbank (edison_mfcc_configure); clip_lo / clip_hi and net_input_scale are not used
+ * feat [n_utt][frame_count * num_mfcc] float32 receives the network input (may be NULL: context scratch); logits / probs / argmax as
+ * edison_fnet_batch. frame_count * num_mfcc must equal the float network's input size (EDISON_E_SIZE otherwise); EDISON_E_NO_MODEL
+ * without a float network. Errors of the geometry as edison_kws_geom.
+ */
+int edison_kws_float_batch_dev(edison_ctx *ctx, const edison_kws_geom *g, int q15, float clip_lo, float clip_hi, const int16_t *audio,
+                               int64_t n_utt, int64_t utt_stride, float *feat, float *logits, float *probs, int32_t *argmax);
+int edison_kws_float_batch(edison_ctx *ctx, const edison_kws_geom *g, int q15, float clip_lo, float clip_hi, const int16_t *audio,
+                           int64_t n_utt, int64_t utt_stride, float *feat, float *logits, float *probs, int32_t *argmax);
+
+/*
  * Exact KWS mode (off by default; EDISON_KWS_EXACT=1 in the environment at edison_init turns it on for that context).
  * While it is on, every variant-B KWS call of the context -- edison_kws_batch, edison_kws_batch_dev and the sharded entry points --
  * aims at features, logits and argmax identical to the host flow's float64 arithmetic (mfcc_mcu, then float32 * scale, clip,
