@@ -99,6 +99,7 @@ static int parse(edison_ctx *ctx, const uint8_t *b, size_t nb, ed_fnet *f, float
 		if (v[11] > 1) return bad(ctx, "relu flag");
 		const int K = kh * kw * ic, oc = v[6];
 		if (v[14] != (K + 3) / 4 * 4 || v[15] != (oc + 15) / 16 * 16) return bad(ctx, "k_pad / n_pad");
+		/* not reachable while nl <= ED_FNET_MAX_LAYERS + 1 and the last record must be the softmax; kept beside p.L's bound */
 		if (n_conv == ED_FNET_MAX_LAYERS) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: at most 16 conv / dense layers");
 		ed_fnet_layer_t &L = p.L[n_conv];
 		L.in_n = ih * iw * ic;

@@ -7,8 +7,10 @@
  * largest layers are 72 KB: all of them would not fit beside the activations) and runs it as an implicit GEMM on
  * v_mfma_f32_16x16x4_f32: M = output rows of all utterances of the tile, N = output channels, K = kh * kw * in_c. Lane l of a wave
  * holds A[row l & 15][k l >> 4] -- the input element at the row's window origin (rowin, per row) plus the k-th window offset (koff,
- * per k, -1 in the padding) -- and B[k l >> 4][channel l & 15] from the layer's [k_pad][n_pad] weights. Exact f32: each output is a
- * k-ordered fmaf chain (cdna_hip_programming.md, "FP32-input MFMA"). The epilogue adds the bias, applies ReLU and max-pools over the
+ * per k, -1 in the padding) -- and B[k l >> 4][channel l & 15] from the layer's [k_pad][n_pad] weights. Exact f32: each output is the
+ * k-ordered fmaf chain acc = fmaf(a_k, w_k, acc) from acc = +0.0f over k = 0 .. K - 1, subnormals kept; then one f32 bias add, fmaxf
+ * ReLU and fmaxf pool. tests/fnet_exact.py models exactly that and the tests hold every layer to it bit for bit (DESIGN.md section 14,
+ * tests/fnet_sweep.py). The epilogue adds the bias, applies ReLU and max-pools over the
  * P adjacent rows of each window (all in one lane's accumulator registers), then writes the pooled value to the other buffer. After
  * the last layer, one thread per utterance computes softmax = exp(z - max) / sum and the first maximum.
  * No scratch memory: everything is registers and LDS.

@@ -366,12 +366,14 @@ int edison_mfcc_geom_batch_dev(edison_ctx *ctx, const edison_kws_geom *g, const 
  * no padding, ReLU or none, max pool of 1, 2 or 4 elements), dense, ReLU, a final softmax; activations HWC. The blob's layer list,
  * shapes and weights are checked at load (EDISON_E_SIZE: malformed; EDISON_E_NO_IMPL: a network this path does not run, e.g. one whose
  * activations and largest layer do not fit the LDS). A load replaces the context's previous float network (synchronising the stream
- * once); the int8 NNoM model (edison_model_load) is separate: a context may hold both.
+ * once); a refused load leaves the previous network loaded and answering as before. The int8 NNoM model (edison_model_load) is
+ * separate: a context may hold both.
  *   edison_fnet_batch  = the Cube aiRunInference for n inputs: in [n][in_h*in_w*in_c] float32 HWC -> logits [n][n_out] (the last
  *                        layer's output before softmax), probs [n][n_out] = exp(z - max) / sum, argmax [n] the first maximum of probs;
  *                        any output may be NULL
  *   edison_fnet_layers = every conv / dense layer's output (after bias, ReLU and pool), back to back: acts [n][acts_floats]
- * Arithmetic: f32-input matrix cores, exact f32 products, each output a k-ordered f32 sum (DESIGN.md section 14 has the error bound).
+ * Arithmetic: each conv / dense output is the k-ordered f32 fmaf chain from +0.0f over k = (ky kw + kx) in_c + ci, then one f32 bias
+ * add, fmaxf ReLU and fmaxf pool, subnormals kept: bit for bit what tests/fnet_exact.py computes.
  * EDISON_E_NO_MODEL when no float network is loaded.
  */
 typedef struct edison_fnet_info_t {

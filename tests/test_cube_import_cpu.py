@@ -88,6 +88,7 @@ def test_synth_network_round_trip():
     ("sigmoid_layer", "forward_sigmoid is not supported"),
     ("softmax_mid", "softmax is only supported as the last layer"),
     ("quantised", "only float32 networks"),
+    ("softmax_map", "softmax over a 9x7 map"),
 ])
 def test_unsupported_layer_refused(case, msg):
     specs = [("conv", 4, (3, 3), (1, 1), (2, 1), 1), ("dense", 5), ("softmax",)]
@@ -106,6 +107,8 @@ def test_unsupported_layer_refused(case, msg):
         ov = {"layer_1": dict(kind=("NL_TYPE", "nl", "forward_sigmoid"))}
     elif case == "softmax_mid":
         specs = [("conv", 4, (3, 3), (1, 1), (2, 1), 1), ("softmax",), ("dense", 5), ("softmax",)]
+    elif case == "softmax_map":
+        specs = [("conv", 4, (3, 3), (1, 1), (2, 1), 1), ("softmax",)]
     net_c, data_c = _synth(specs, overrides=ov)
     if case == "quantised":
         net_c = net_c.replace("layer_0_weights_array, AI_ARRAY_FORMAT_FLOAT", "layer_0_weights_array, AI_ARRAY_FORMAT_S8")
@@ -126,7 +129,8 @@ def test_cli_refuses_with_message(tmp_path, capsys):
 
 
 def test_kernel_compiles_without_scratch(tmp_path):
-    """fnet_kernels.hip for gfx950: no scratch memory, and the f32-input MFMA in the code object."""
+    """fnet_kernels.hip for gfx950: no scratch memory, the f32-input MFMA in the code object, and f32 subnormals kept by both kernels
+    (float_denorm_mode_32 3: no build flag flushes them; tests/fnet_exact.py models the kernel without flushing)."""
     hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
     src = os.path.join(ROOT, "edison_amd", "csrc", "fnet_kernels.hip")
     r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-fno-slp-vectorize", "-O3", "--cuda-device-only", "-S", src, "-o",
@@ -136,3 +140,5 @@ def test_kernel_compiles_without_scratch(tmp_path):
     assert len(scratch) == 2 and all(v == 0 for v in scratch), r.stderr
     asm = (tmp_path / "f.s").read_text()
     assert "v_mfma_f32_16x16x4_f32" in asm or "v_mfma_f32_16x16x4f32" in asm
+    modes = re.findall(r"\.amdhsa_float_denorm_mode_32 (\d+)", asm)
+    assert modes == ["3", "3"], modes

@@ -4,6 +4,7 @@ tests/fnet_ref.py, the float64 restatement of the Cube layers, on the .ednf fixt
 
 Bounds (DESIGN.md section 14 has what was measured):
   every layer, fed the kernel's own previous layer: |gpu - f64| <= K_BOUND 1e-7 S, S = sum |a| |w| + |bias| (f32 MFMA: a k-ordered fmaf chain)
+    and, on up to 266 inputs per call, bit-equal to the host model of that chain (tests/fnet_exact.py)
   probabilities: within 1e-6 of the float64 softmax of the kernel's logits
   argmax: equal to the float64 chain's wherever its top-2 logit margin exceeds MARGIN
   host-flow features: at most FEAT_FLIPS elements per utterance differ from the reference's float32 net input, by 1 ulp"""
@@ -16,6 +17,7 @@ import pytest
 from conftest import GOLDEN
 
 import cube_synth
+import fnet_exact
 import fnet_ref
 
 pytestmark = pytest.mark.gpu
@@ -54,9 +56,19 @@ def _inputs(golden, n=4096):
     return np.concatenate([x, np.stack(fx)])
 
 
+EXACT_N = 256       # inputs of a call checked bit for bit against fnet_exact (the first 256 and the last 10: the fixture inputs)
+
+
 def check_layers(ctx, model, x):
-    """Every layer of the kernel against the restatement fed the kernel's own previous layer; returns the largest err / (1e-7 S)."""
-    acts = ctx.fnet_layers(x).astype(np.float64)
+    """Every layer of the kernel against the restatement fed the kernel's own previous layer, and bit for bit against the host model
+    of the kernel (tests/fnet_exact.py: k-ordered fmaf chain, bias, ReLU, pool) on at most EXACT_N + 10 of the inputs; returns the
+    largest err / (1e-7 S)."""
+    acts32 = ctx.fnet_layers(x)
+    pick = np.arange(len(x)) if len(x) <= EXACT_N + 10 else np.r_[:EXACT_N, len(x) - 10:len(x)]
+    want, got = fnet_exact.layers_from(model, np.asarray(x, np.float32)[pick], acts32[pick])
+    for i, (w, g) in enumerate(zip(want, got)):
+        assert np.array_equal(w, g), "layer %d: %d of %d outputs differ from the fmaf chain" % (i, (w != g).sum(), w.size)
+    acts = acts32.astype(np.float64)
     prev, off, worst = np.asarray(x, np.float64), 0, 0.0
     for i, L in enumerate(fnet_ref.conv_records(model)):
         n_out = int(np.prod(L["out"]))
