@@ -57,6 +57,12 @@ class StreamGeomOpts(ctypes.Structure):
                 ("true_threshold", c_double)]
 
 
+class StreamFloatOpts(ctypes.Structure):
+    """edison_stream_float_opts"""
+    _fields_ = [("chunk_frames", ctypes.c_int32), ("q15", ctypes.c_int32), ("clip_lo", c_float), ("clip_hi", c_float), ("filter", ctypes.c_int32),
+                ("fsm", ctypes.c_int32), ("filter_alpha", c_double), ("true_threshold", c_double)]
+
+
 class Fsm(ctypes.Structure):
     """edison_fsm"""
     _fields_ = [("state", c_int), ("hot_timeout_ms", ctypes.c_uint32), ("wake_idx", c_int), ("loc_idx", c_int),
@@ -177,6 +183,18 @@ SIGNATURES = {
     "edison_stream_geom_filtered_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "edison_stream_geom_fsm": (c_int, [c_void_p, c_void_p, c_void_p]),
     "edison_stream_geom_fsm_dev": (c_int, [c_void_p, c_void_p]),
+    "edison_stream_float_default_opts": (None, [ctypes.POINTER(StreamFloatOpts)]),
+    "edison_stream_float_create": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), ctypes.POINTER(StreamFloatOpts), ctypes.POINTER(c_void_p)]),
+    "edison_stream_float_destroy": (None, [c_void_p]),
+    "edison_stream_float_reset": (c_int, [c_void_p]),
+    "edison_stream_float_push": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_float_push_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_float_push_n_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_float_frames_seen": (c_int64, [c_void_p]),
+    "edison_stream_float_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_float_filtered_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_float_fsm": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "edison_stream_float_fsm_dev": (c_int, [c_void_p, c_void_p]),
     "edison_fsm_init": (None, [ctypes.POINTER(Fsm)]),
     "edison_fsm_step": (c_int, [ctypes.POINTER(Fsm), c_float, ctypes.c_uint32, ctypes.c_uint32, c_double]),
     # legacy firmware call surface

@@ -340,6 +340,17 @@ class Context:
             self._check(self._L.edison_fnet_load_mem(self._h, buf, len(src)))
         else:
             self._check(self._L.edison_fnet_load(self._h, str(src).encode()))
+        self.fnet_keywords = self._ednf_keywords(src)
+
+    @staticmethod
+    def _ednf_keywords(src):
+        """The class names an .ednf carries (cube_import.py's keyword block), None when it has none."""
+        from . import cube_import
+        try:
+            data = bytes(src) if isinstance(src, (bytes, bytearray)) else open(str(src), "rb").read()
+            return cube_import.read_blob(data)["keywords"] or None
+        except (OSError, cube_import.CubeImportError):
+            return None
 
     def fnet_info(self):
         """dict of edison_fnet_info_t: in_h, in_w, in_c, n_out, n_layers, acts_floats, batch, lds_bytes."""

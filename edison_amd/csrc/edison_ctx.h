@@ -104,6 +104,7 @@ struct edison_ctx
 	size_t dist_scratch_bytes;
 	ed_geom_cache *geom; /* edison_kws_geom_batch*: the tables of the last geometry (one entry) */
 	ed_fnet *fnet;       /* edison_fnet_load*: the loaded float32 network (edison_fnet.hip), NULL before the first load */
+	int fnet_epoch;      /* counts float network loads (as model_epoch): an edison_stream_float serves the network of one load */
 	char err[512];
 };
 
@@ -178,6 +179,9 @@ void ed_ctx_fnet_free(edison_ctx *ctx);
  * frames per utterance) and the table builder behind the context's cache (fills *c, whose d must be NULL; c->d stays NULL on failure). */
 int ed_kws_geom_check(edison_ctx *ctx, const edison_kws_geom *g, int *frames);
 int ed_geom_tables_build(edison_ctx *ctx, const edison_kws_geom *g, ed_geom_cache *c);
+/* edison_fnet.hip, shared with edison_stream_float.hip: the checks of edison_kws_float_batch for geometry g, flow q15 and the clip
+ * range, the loaded float network's input size included (*frames = frames per window). */
+int ed_kws_float_geom_check(edison_ctx *ctx, const edison_kws_geom *g, int q15, float clip_lo, float clip_hi, int *frames);
 
 /* The loaded model on 31x13x1 -> 10 features (the geometry of every kws / stream entry point): matrix-core kernel for
  * the kws_conv graph, the general kernel for any other graph of that shape. feat_stride = bytes between utterances. */

@@ -36,6 +36,8 @@ void ed_ctx_fnet_free(edison_ctx *ctx)
 	ctx->fnet = NULL;
 }
 
+const ed_fnet_plan_t *ed_ctx_fnet_plan(const edison_ctx *ctx) { return ctx && ctx->fnet ? &ctx->fnet->plan : NULL; }
+
 static int32_t rd32(const uint8_t *p)
 {
 	int32_t v;
@@ -207,6 +209,7 @@ extern "C" int edison_fnet_load_mem(edison_ctx *ctx, const void *blob, size_t bl
 		ed_ctx_fnet_free(ctx);
 	}
 	ctx->fnet = f;
+	ctx->fnet_epoch++;
 	return EDISON_OK;
 }
 
@@ -253,7 +256,7 @@ static int run_on(edison_ctx *ctx, const float *in, int64_t n, float *logits, fl
 {
 	if (n == 0) return EDISON_OK;
 	ED_HIP(ctx, hipSetDevice(ctx->device));
-	const int e = ed_launch_fnet(&ctx->fnet->plan, in, n, logits, probs, argmax, acts, ctx->stream);
+	const int e = ed_launch_fnet(&ctx->fnet->plan, in, ctx->fnet->plan.in_n, n, logits, probs, argmax, acts, ctx->stream);
 	return ed_launch_result(ctx, e, "float network kernel");
 }
 
@@ -328,6 +331,11 @@ static int kws_float_check(edison_ctx *ctx, const edison_kws_geom *g, int q15, f
 	}
 	if (n_utt * (int64_t)*frames >= ((int64_t)1 << 31)) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_kws_float: more than 2^31 frames in one call");
 	return EDISON_OK;
+}
+
+int ed_kws_float_geom_check(edison_ctx *ctx, const edison_kws_geom *g, int q15, float clip_lo, float clip_hi, int *frames)
+{
+	return kws_float_check(ctx, g, q15, clip_lo, clip_hi, NULL, 0, 0, frames);
 }
 
 extern "C" int edison_kws_float_batch_dev(edison_ctx *ctx, const edison_kws_geom *g, int q15, float clip_lo, float clip_hi, const int16_t *audio,

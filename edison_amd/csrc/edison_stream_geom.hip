@@ -23,9 +23,8 @@
 
 #include "edison_ctx.h"
 #include "edison_fsm_core.h"
+#include "edison_stream_kernels.h"
 #include "mfcc_geom.h"
-
-#define EDSG_FILTER_MAX_OUT 256 /* classes the filter kernel serves: one lane each in one workgroup */
 
 struct edison_stream_geom
 {
@@ -81,23 +80,16 @@ __global__ __launch_bounds__(256) void ed_stream_geom_shift_kernel(int16_t *audi
 	}
 }
 
-/* the state machine behind the filter; fsm = NULL: none */
-struct edsg_fsm_stage_t
-{
-	edison_fsm *fsm;      /* device memory, read and written                       */
-	int32_t *states;      /* [n] out: the state after each inference               */
-	edison_fsm *copy;     /* out: the machine after the push (the host's view)     */
-	uint32_t dt_us;
-	ed_fsm_roles_t roles;
-};
-
 /*
  * The firmware's post-processing (app.c:332-356) over n_out classes, for the n inferences of a push:
  *   state[c] = (float)(alpha * (double)state[c] + (1 - alpha) * (double)x[c])   product and sum rounded separately, no contraction
  *   likely = first maximum of the state row, spotted = likely if that maximum > threshold, else -1
  * The recurrence is sequential in time; classes run on lanes, the per-frame maximum afterwards on frames. One workgroup.
+ * T = int8_t: the int8 graph's softmax / logits (this file); T = float: the float network's probabilities (edison_stream_float.hip).
+ * (double)x is exact for both.
  */
-__global__ __launch_bounds__(256) void ed_stream_geom_filter_kernel(const int8_t *x, int n, int n_out, double alpha, double one_minus_alpha,
+template <class T>
+__global__ __launch_bounds__(256) void ed_stream_geom_filter_kernel(const T *x, int n, int n_out, double alpha, double one_minus_alpha,
                                                                     double threshold, float *state, float *filt, int32_t *likely,
                                                                     int32_t *spotted, edsg_fsm_stage_t fs)
 {
@@ -138,6 +130,20 @@ __global__ __launch_bounds__(256) void ed_stream_geom_filter_kernel(const int8_t
 		*fs.fsm = m;
 		if (fs.copy) *fs.copy = m;
 	}
+}
+
+int ed_launch_stream_shift(hipStream_t q, int16_t *audio, int64_t a_src, int tail, void *feat, int64_t f_src, int feat_bytes)
+{
+	hipLaunchKernelGGL(ed_stream_geom_shift_kernel, dim3(1), dim3(256), 0, q, audio, a_src, tail, (int8_t *)feat, f_src, feat_bytes);
+	return (int)hipGetLastError();
+}
+
+int ed_launch_stream_filter_f32(hipStream_t q, const float *x, int n, int n_out, double alpha, double one_minus_alpha, double threshold,
+                                float *state, float *filt, int32_t *likely, int32_t *spotted, edsg_fsm_stage_t fs)
+{
+	hipLaunchKernelGGL(ed_stream_geom_filter_kernel<float>, dim3(1), dim3(256), 0, q, x, n, n_out, alpha, one_minus_alpha, threshold, state,
+	                   filt, likely, spotted, fs);
+	return (int)hipGetLastError();
 }
 
 /* Work the stream left unsynchronised on another HIP stream must be behind us before q touches the stream's state. */
@@ -182,7 +188,7 @@ static int enqueue_push(edison_stream_geom *s, hipStream_t q, int n, int8_t *log
 			fs.fsm = s->d_fsm; fs.states = (int32_t *)(fout + s->off_states); fs.copy = (edison_fsm *)(fout + s->off_fsm);
 			fs.dt_us = s->dt_us; fs.roles = s->roles;
 		}
-		hipLaunchKernelGGL(ed_stream_geom_filter_kernel, dim3(1), dim3(256), 0, q, fin, n, s->n_out, s->alpha, s->one_minus_alpha, s->threshold,
+		hipLaunchKernelGGL(ed_stream_geom_filter_kernel<int8_t>, dim3(1), dim3(256), 0, q, fin, n, s->n_out, s->alpha, s->one_minus_alpha, s->threshold,
 		                   s->d_state, (float *)(fout + s->off_filt), (int32_t *)(fout + s->off_likely), (int32_t *)(fout + s->off_spotted), fs);
 		if (hipGetLastError() != hipSuccess) return ed_set_err(ctx, EDISON_E_RUNTIME, "stream_geom: filter launch failed");
 	}
@@ -194,10 +200,9 @@ static int enqueue_push(edison_stream_geom *s, hipStream_t q, int n, int8_t *log
 static int make_room(edison_stream_geom *s, hipStream_t q, int n)
 {
 	if (s->pos + n <= s->slots * s->chunk || s->pos == 0) return EDISON_OK;
-	hipLaunchKernelGGL(ed_stream_geom_shift_kernel, dim3(1), dim3(256), 0, q, s->d_audio, (int64_t)s->pos * s->hop, s->tail, s->d_feat,
-	                   (int64_t)s->pos * s->nm, (s->F - 1) * s->nm);
+	const int e = ed_launch_stream_shift(q, s->d_audio, (int64_t)s->pos * s->hop, s->tail, s->d_feat, (int64_t)s->pos * s->nm, (s->F - 1) * s->nm);
 	s->pos = 0;
-	return hipGetLastError() == hipSuccess ? EDISON_OK : ed_set_err(s->ctx, EDISON_E_RUNTIME, "stream_geom: shift launch failed");
+	return e == 0 ? EDISON_OK : ed_set_err(s->ctx, EDISON_E_RUNTIME, "stream_geom: shift launch failed");
 }
 
 static int check_push(edison_stream_geom *s, const int16_t *samples)

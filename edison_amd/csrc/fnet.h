@@ -46,10 +46,14 @@ static inline size_t ed_fnet_lds_bytes(const ed_fnet_plan_t *p)
 	return sizeof(float) * ((size_t)p->batch * (size_t)(p->buf_n[0] + p->buf_n[1]) + (size_t)p->w_lds) + sizeof(int32_t) * (size_t)p->k_lds;
 }
 
-/* n utterances in[n][in_n] -> logits / probs [n][n_out] (NULL: not written), argmax [n] (NULL: not written); acts != NULL also dumps
- * every layer's output [n][acts_n]. Returns a hipError_t. */
-extern "C" int ed_launch_fnet(const ed_fnet_plan_t *p, const float *in, int64_t n, float *logits, float *probs, int32_t *argmax, float *acts,
-                              hipStream_t stream);
+/* n utterances -> logits / probs [n][n_out] (NULL: not written), argmax [n] (NULL: not written); acts != NULL also dumps every layer's
+ * output [n][acts_n]. Utterance u is the in_n floats at in + u * in_stride: in_stride = in_n for inputs back to back, num_mfcc for the
+ * overlapping windows of a stream's feature rows (edison_stream_float). Returns a hipError_t. */
+extern "C" int ed_launch_fnet(const ed_fnet_plan_t *p, const float *in, int64_t in_stride, int64_t n, float *logits, float *probs, int32_t *argmax,
+                              float *acts, hipStream_t stream);
+/* The context's loaded float network's plan, NULL when none is loaded (edison_fnet.hip). */
+struct edison_ctx;
+const ed_fnet_plan_t *ed_ctx_fnet_plan(const struct edison_ctx *ctx);
 /* The host flow's net input: out[i] = min(max((float)y[i] * scale, lo), hi) for i < count. Returns a hipError_t. */
 extern "C" int ed_launch_fnet_input(const double *y, int64_t count, float scale, float lo, float hi, float *out, int n_cu, hipStream_t stream);
 

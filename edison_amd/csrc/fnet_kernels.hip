@@ -81,7 +81,8 @@ __device__ __forceinline__ void edf_tile(const ed_fnet_layer_t &L, const float *
 	}
 }
 
-__global__ __launch_bounds__(ED_FNET_THREADS) void ed_fnet_kernel(ed_fnet_plan_t p, const float *__restrict__ in, int64_t n, float *__restrict__ logits,
+__global__ __launch_bounds__(ED_FNET_THREADS) void ed_fnet_kernel(ed_fnet_plan_t p, const float *__restrict__ in, int64_t in_stride, int64_t n,
+                                                                    float *__restrict__ logits,
                                                                     float *__restrict__ probs, int32_t *__restrict__ argmax, float *__restrict__ acts)
 {
 	extern __shared__ float lds[];
@@ -93,11 +94,12 @@ __global__ __launch_bounds__(ED_FNET_THREADS) void ed_fnet_kernel(ed_fnet_plan_t
 	const int64_t u0 = (int64_t)blockIdx.x * B;
 	const int nu = (int)(n - u0 < B ? n - u0 : B);
 
-	/* the network input of the tile's utterances into buffer 0 */
+	/* the network input of the tile's utterances into buffer 0; utterance u starts in_stride floats after u - 1 (in_n: back to back;
+	 * less: overlapping windows, edison_stream_float) */
 	for (int i = tid; i < nu * p.in_n; i += ED_FNET_THREADS)
 	{
-		const int u = i / p.in_n;
-		buf[0][u * p.buf_n[0] + (i - u * p.in_n)] = in[u0 * p.in_n + i];
+		const int u = i / p.in_n, e = i - u * p.in_n;
+		buf[0][u * p.buf_n[0] + e] = in[(u0 + u) * in_stride + e];
 	}
 
 	for (int l = 0; l < p.n_layers; l++)
@@ -155,16 +157,17 @@ __global__ __launch_bounds__(ED_FNET_THREADS) void ed_fnet_kernel(ed_fnet_plan_t
 	}
 }
 
-extern "C" int ed_launch_fnet(const ed_fnet_plan_t *p, const float *in, int64_t n, float *logits, float *probs, int32_t *argmax, float *acts,
-                              hipStream_t stream)
+extern "C" int ed_launch_fnet(const ed_fnet_plan_t *p, const float *in, int64_t in_stride, int64_t n, float *logits, float *probs, int32_t *argmax,
+                              float *acts, hipStream_t stream)
 {
 	if (n <= 0) return 0;
+	if (in_stride < 0) return (int)hipErrorInvalidValue;
 	const size_t lds = ed_fnet_lds_bytes(p);
 	if (lds > ED_FNET_LDS_BYTES || p->batch < 1 || p->n_layers < 1 || p->n_layers > ED_FNET_MAX_LAYERS) return (int)hipErrorInvalidValue;
 	{ const int e = ed_kernel_prepare((const void *)ed_fnet_kernel, ED_FNET_THREADS, lds, NULL, NULL); if (e) return e; }
 	const int64_t blocks = (n + p->batch - 1) / p->batch;
 	if (blocks > INT32_MAX) return (int)hipErrorInvalidValue;
-	hipLaunchKernelGGL(ed_fnet_kernel, dim3((unsigned)blocks), dim3(ED_FNET_THREADS), lds, stream, *p, in, n, logits, probs, argmax, acts);
+	hipLaunchKernelGGL(ed_fnet_kernel, dim3((unsigned)blocks), dim3(ED_FNET_THREADS), lds, stream, *p, in, in_stride, n, logits, probs, argmax, acts);
 	return (int)hipGetLastError();
 }
 

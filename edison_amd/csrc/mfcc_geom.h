@@ -50,5 +50,8 @@ extern "C" int ed_launch_mfcc_geom(const ed_geom_args_t *a, int n_cu, hipStream_
 /* The same frames, stages and launch; stage 6 stores the float64 DCT row value y (unscaled, unrounded) to mfcc + g * n_coef + row
  * instead of the int8 feature (a->feat and a->feat_scale are not read). */
 extern "C" int ed_launch_mfcc_geom_f64(const ed_geom_args_t *a, double *mfcc, int n_cu, hipStream_t stream);
+/* The same frames, stages and launch (mfcc_geom_fnet_kernels.hip); stage 6 stores the float network input
+ * fminf(fmaxf((float)y * scale, lo), hi) to out + g * n_coef + row (a->feat and a->feat_scale are not read). */
+extern "C" int ed_launch_mfcc_geom_fnet(const ed_geom_args_t *a, float *out, float scale, float lo, float hi, int n_cu, hipStream_t stream);
 
 #endif

@@ -13,98 +13,14 @@
  *   6. DCT-II rows first_mfcc .. first_mfcc + num_mfcc - 1 over dct_div (A sqrt(2 mel_nbins), B 64); feature = int8 of
  *      rint(clip((float)y * feat_scale, -128, 127)) (kws_nnom.py:359-361), written to feat + g * num_mfcc + row
  *      -- or, in the float64 instance (ed_mfcc_geom_f64_kernel, edison_mfcc_geom_batch*), y itself to mfcc + g * num_mfcc + row
+ *      -- or, in the float network-input instance (mfcc_geom_fnet_kernels.hip, edison_stream_float), min(max((float)y * scale, lo), hi)
  *
  * Work split: a TEAM of threads owns one frame at a time and a private LDS slice of r0 + r1 + r2 doubles (two FFT buffers -- the
  * spectrum goes to the one the FFT's result is not in -- and the mel bands); teams take frames g = team, team + n_teams, ... of the
  * whole call. TEAM = 64 (a wavefront; four per workgroup, no workgroup barrier) where the slice is at most 20 KiB, which covers every
  * even N <= 1024 and mel_nbins <= 256; TEAM = 256 (the workgroup) for the longer frames.
  */
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "edison_launch.h"
-#include "mfcc_fft.h"
-#include "mfcc_geom.h"
-
-#define EDG_BLOCK 256
-#define EDG_WAVE_LDS_MAX 20480 /* bytes of a wavefront team's slice: 4 per workgroup <= 80 KiB, two workgroups per CU */
-
-__device__ __forceinline__ double2 edg_cmul(double2 a, double2 w) { return make_double2(fma(a.x, w.x, -a.y * w.y), fma(a.x, w.y, a.y * w.x)); }
-__device__ __forceinline__ double2 edg_add(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 edg_sub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
-
-template <int TEAM> __device__ __forceinline__ void edg_sync()
-{
-	if (TEAM == 64) ed_wave_sync();
-	else __syncthreads();
-}
-
-/* V[q] = sum_r v[r] W_R^(r q) */
-template <int R> __device__ __forceinline__ void edg_dft(double2 *v)
-{
-	if (R == 2)
-	{
-		const double2 a = v[0], b = v[1];
-		v[0] = edg_add(a, b);
-		v[1] = edg_sub(a, b);
-	}
-	else if (R == 4)
-	{
-		const double2 s02 = edg_add(v[0], v[2]), d02 = edg_sub(v[0], v[2]), s13 = edg_add(v[1], v[3]), d13 = edg_sub(v[1], v[3]);
-		v[0] = edg_add(s02, s13);
-		v[2] = edg_sub(s02, s13);
-		v[1] = make_double2(d02.x + d13.y, d02.y - d13.x); /* d02 - i d13 */
-		v[3] = make_double2(d02.x - d13.y, d02.y + d13.x); /* d02 + i d13 */
-	}
-	else
-	{
-		/* R = 3, 5: W_R^m = cos(2 pi m / R) - i sin(2 pi m / R) */
-		const double c3[3] = {1.0, -0.5, -0.5}, s3[3] = {0.0, -0.86602540378443864676, 0.86602540378443864676};
-		const double c5[5] = {1.0, 0.30901699437494742410, -0.80901699437494742410, -0.80901699437494742410, 0.30901699437494742410};
-		const double s5[5] = {0.0, -0.95105651629515357212, -0.58778525229247312917, 0.58778525229247312917, 0.95105651629515357212};
-		double2 o[R];
-#pragma unroll
-		for (int q = 0; q < R; q++)
-		{
-			double2 acc = v[0];
-#pragma unroll
-			for (int r = 1; r < R; r++)
-			{
-				const int m = (r * q) % R;
-				const double2 w = R == 3 ? make_double2(c3[m], s3[m]) : make_double2(c5[m], s5[m]);
-				acc = edg_add(acc, edg_cmul(v[r], w));
-			}
-			o[q] = acc;
-		}
-#pragma unroll
-		for (int q = 0; q < R; q++) v[q] = o[q];
-	}
-}
-
-/* One Stockham stage of radix R: sub-transforms of length ns become length ns R (Govindaraju et al., SC'08, "High performance discrete
- * Fourier transforms on graphics processors"): butterfly j takes src[j + r M/R], twiddles by W_{ns R}^{(j mod ns) r}, writes
- * dst[(j - j mod ns) R + j mod ns + q ns]. */
-template <int R, int TEAM>
-__device__ __forceinline__ void edg_stage(const double2 *src, double2 *dst, int M, int ns, int tws, const double2 *__restrict__ tw, int tid)
-{
-	const int mr = M / R, tstep = (M / (ns * R)) * tws; /* W_{ns R}^m = W_N^(m tstep) */
-	for (int j = tid; j < mr; j += TEAM)
-	{
-		const int k = j % ns;
-		double2 v[R];
-#pragma unroll
-		for (int r = 0; r < R; r++) v[r] = src[j + r * mr];
-		if (ns > 1)
-		{
-#pragma unroll
-			for (int r = 1; r < R; r++) v[r] = edg_cmul(v[r], tw[k * r * tstep]);
-		}
-		edg_dft<R>(v);
-		const int base = (j - k) * R + k;
-#pragma unroll
-		for (int q = 0; q < R; q++) dst[base + q * ns] = v[q];
-	}
-}
+#include "mfcc_geom_device.h"
 
 template <int TEAM> __global__ __launch_bounds__(EDG_BLOCK) void ed_mfcc_geom_kernel(ed_geom_args_t a)
 {
@@ -130,21 +46,13 @@ template <int TEAM> __global__ __launch_bounds__(EDG_BLOCK) void ed_mfcc_geom_f6
 static int edg_launch(const ed_geom_args_t *a, double *mfcc, int n_cu, hipStream_t stream)
 {
 	if (a->n_frames <= 0) return 0;
-	if (a->team != 64 && a->team != EDG_BLOCK) return (int)hipErrorInvalidValue;
-	const int teams = EDG_BLOCK / a->team;
-	const size_t lds = sizeof(double) * (size_t)teams * (size_t)(a->r0 + a->r1 + a->r2);
-	if (a->team == 64 && lds > 4 * (size_t)EDG_WAVE_LDS_MAX) return (int)hipErrorInvalidValue;
-	if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
+	size_t lds = 0;
+	dim3 grid;
+	{ const int e = edg_launch_shape(a, n_cu, &lds, &grid); if (e) return e; }
 	const void *fn = !mfcc ? (a->team == 64 ? (const void *)ed_mfcc_geom_kernel<64> : (const void *)ed_mfcc_geom_kernel<EDG_BLOCK>)
 	                       : (a->team == 64 ? (const void *)ed_mfcc_geom_f64_kernel<64> : (const void *)ed_mfcc_geom_f64_kernel<EDG_BLOCK>);
 	{ const int e = ed_kernel_prepare(fn, EDG_BLOCK, lds, NULL, NULL); if (e) return e; }
-	/* resident workgroups: as many as the LDS admits, at most 4 per CU (16 waves); the frames are grid-strided */
-	int64_t per_cu = (int64_t)(160 * 1024) / (int64_t)lds;
-	if (per_cu > 4) per_cu = 4;
-	if (per_cu < 1) per_cu = 1;
-	int64_t blocks = ((int64_t)a->n_frames + teams - 1) / teams;
-	if (blocks > per_cu * n_cu) blocks = per_cu * n_cu;
-	const dim3 grid((unsigned)blocks), block(EDG_BLOCK);
+	const dim3 block(EDG_BLOCK);
 	if (mfcc)
 	{
 		if (a->team == 64) hipLaunchKernelGGL(ed_mfcc_geom_f64_kernel<64>, grid, block, lds, stream, *a, mfcc);

@@ -4,7 +4,8 @@ The reference's ``audio/edison/kws/kws_live.py`` listens to a microphone; the si
 what this module runs, frame by frame, on the GPU: 1024-sample frames -> MFCC -> 31-row sliding window -> int8 network
 -> moving average over the outputs -> maximum / threshold -> wake-word state machine. ``host`` uses the host float
 model of the features (variant B), ``mcu`` the firmware's own Q15 arithmetic (variant C). The printed lines follow the
-firmware's UART log (app.c:330-353).
+firmware's UART log (app.c:330-353). ``--net <file.ednf>`` runs the float32 X-CUBE-AI network instead of the int8 graph: the
+firmware's default build (NET_TYPE_CUBE), whose moving average uses alpha 0.5 (app.c:35-36).
 """
 import sys
 
@@ -12,7 +13,7 @@ import numpy as np
 
 from .. import config as cfg
 from ..context import KEYWORDS, default_context
-from ..stream import Fsm, GeomStream, Stream
+from ..stream import FloatStream, Fsm, GeomStream, Stream
 from .kws_host import read_wav
 
 
@@ -27,18 +28,33 @@ def netOutFilt(net_outs, alpha):
     return flt
 
 
-def run(path, q15=False, ctx=None, out=None, alpha=0.9, threshold=0.5, geometry=None):
+def run(path, q15=False, ctx=None, out=None, alpha=None, threshold=0.5, geometry=None, net=None):
     """geometry (kws.geometry.KwsGeometry): a graph trained at that MFCC geometry, on a GeomStream whose hop is geometry.frame_step
-    (float64 features, q15 does not apply); the state machine runs, and its lines are printed, only for a graph with 10 outputs."""
+    (float64 features, q15 does not apply); the state machine runs, and its lines are printed, only for a graph with 10 outputs.
+    net (an .ednf path or its bytes): the float32 X-CUBE-AI network, loaded on ctx, on a FloatStream (host flow at `geometry`, default
+    audio/config.py's; q15: the firmware's flow); class names from the .ednf. alpha: the moving average's, default 0.9 for the int8
+    graph (app.c:38) and 0.5 for the float network (app.c:35-36)."""
     out = out or sys.stdout
     ctx = ctx or default_context()
+    if alpha is None:
+        alpha = 0.9 if net is None else 0.5
     data = read_wav(path)
+    if net is not None:
+        ctx.fnet_load(net)
+        if geometry is None:
+            from ..kws.geometry import KwsGeometry
+            geometry = KwsGeometry.from_config(net_input_scale=cfg.net_input_scale)
     hop = cfg.frame_length if geometry is None else int(geometry.frame_step)
     n = -(-data.shape[0] // hop)
     data = np.pad(data, (0, n * hop - data.shape[0]))
     # the firmware's loop body behind the network (app.c:341-371) is part of the push: moving average, maximum, threshold and
     # edisonFSM run as the last GPU stages (Stream(fsm=True)); what comes back is the state after every inference
-    if geometry is None:
+    if net is not None:
+        with_fsm = ctx.fnet_info()["n_out"] == len(KEYWORDS)
+        st = FloatStream(ctx, geometry, q15=q15, chunk_frames=n, output_filter=True, alpha=alpha, threshold=threshold, fsm=with_fsm)
+        names = st.keywords or (list(KEYWORDS) if with_fsm else [])
+        name = lambda i: names[i] if i < len(names) else "class %d" % i
+    elif geometry is None:
         st = Stream(ctx, hop=hop, chunk_frames=n, q15=q15, output_filter=True, alpha=alpha, threshold=threshold, fsm=True)
         with_fsm, name = True, lambda i: KEYWORDS[i]
     else:
@@ -47,7 +63,10 @@ def run(path, q15=False, ctx=None, out=None, alpha=0.9, threshold=0.5, geometry=
         name = (lambda i: KEYWORDS[i]) if with_fsm else (lambda i: "class %d" % i)
     res = st.push(data)
     st.close()
-    shown = res["softmax"] if res["softmax"] is not None else res["logits"]   # what the filter averaged
+    if net is not None:
+        shown = res["probs"]
+    else:
+        shown = res["softmax"] if res["softmax"] is not None else res["logits"]   # what the filter averaged
     events = []
     before, loc, val = "RESET", -1, -1
     for i in range(n):
@@ -74,8 +93,17 @@ def run(path, q15=False, ctx=None, out=None, alpha=0.9, threshold=0.5, geometry=
 
 
 def main(argv):
+    net = None
+    if "--net" in argv:
+        i = argv.index("--net")
+        if i + 1 >= len(argv):
+            print("--net needs an .ednf file")
+            return 1
+        net = argv[i + 1]
+        argv = argv[:i] + argv[i + 2:]
     if len(argv) < 3 or argv[1] not in ("host", "mcu"):
-        print("usage: kws live <host|mcu> <wav>   (the microphone front end of the reference is not part of this port)")
+        print("usage: kws live <host|mcu> <wav> [--net <file.ednf>]   (--net: the float32 X-CUBE-AI network instead of the int8 graph; "
+              "the microphone front end of the reference is not part of this port)")
         return 0 if len(argv) >= 2 and argv[1] in ("host", "mcu") else 1
-    run(argv[2], q15=(argv[1] == "mcu"))
+    run(argv[2], q15=(argv[1] == "mcu"), net=net)
     return 0

@@ -5,7 +5,7 @@ on the keyword-spotting hot path:
     mfcc host [wav]                      audio/main.py:80-99,199     -> edison_amd.mfcc.mfcc
     mfcc mcu calc|single|file ...        mfcc_on_mcu.py:526-548      -> edison_amd.mfcc.mfcc_on_mcu
     kws  mcu single|fileinf|file|frame   kws_on_mcu.py:650-690       -> edison_amd.kws.kws_host
-    kws  live host|mcu <wav>             audio/main.py:231-233       -> edison_amd.kws.kws_live
+    kws  live host|mcu <wav> [--net f]   audio/main.py:231-233       -> edison_amd.kws.kws_live
 
 Where the reference talks to the STM32 board over the UART, the board's leg is computed by the GPU's bit-exact
 variant C. The remaining reference modules (mic, acquire, train, deploy, mcu) drive the board or Keras training and are
@@ -33,7 +33,8 @@ USAGE = """usage: edison <module> <command> [<args>]
   mfcc mcu calc [file]                   write the firmware's mel_constants.h
   mfcc mcu single [wav] | file <wav>     host model (variant B) against the firmware's arithmetic (variant C)
   kws  mcu single [n] | fileinf <wav> | file <wav> | frame <wav>
-  kws  live host|mcu <wav>               the firmware's continuous mode replayed on a wav
+  kws  live host|mcu <wav> [--net <file.ednf>]
+                                         the firmware's continuous mode replayed on a wav (--net: the float32 X-CUBE-AI network)
 """
 
 

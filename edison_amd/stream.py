@@ -202,6 +202,102 @@ class GeomStream:
             self.ctx._check(self._L.edison_stream_geom_filtered_dev(self._h, q(filtered), q(likely), q(spotted)))
 
 
+class FloatStream:
+    """Continuous keyword spotting with the float32 X-CUBE-AI network loaded on the context (``Context.fnet_load``) -- Python handle on
+    ``edison_stream_float_*``: the continuous counterpart of ``Context.kws_float``, and the loop the reference's board runs for its
+    default network type (app.c:288-371, 630-719). The hop is ``geometry.frame_step`` (``geometry=None``: what ``Context.kws_float``
+    uses by default); the window is ``geometry.frame_count`` float rows, oldest first. ``q15=False`` is the host flow (float64 MFCC ->
+    float32 x net_input_scale -> clip to [clip_min, clip_max], default audio/config.py's); ``q15=True`` the firmware's variant C ->
+    (float), shipped framing only. For frames that fill a whole window the outputs equal ``Context.kws_float`` on the same samples.
+
+    ``output_filter=True`` adds the firmware's moving average over the probabilities (alpha 0.5: the Cube build's, app.c:35-36), first
+    maximum and threshold; ``fsm=True`` puts edisonFSM behind it (networks with 10 outputs only)."""
+
+    def __init__(self, ctx, geometry=None, q15=False, chunk_frames=1, output_filter=False, alpha=0.5, threshold=0.5, fsm=False,
+                 clip_min=None, clip_max=None):
+        from . import config as cfg
+        from .kws.geometry import KwsGeometry
+        self.ctx = ctx or default_context()
+        self._L = _lib.lib()
+        if geometry is None:
+            geometry = KwsGeometry.from_config(net_input_scale=cfg.net_input_scale)
+        o = _lib.StreamFloatOpts()
+        self._L.edison_stream_float_default_opts(ctypes.byref(o))
+        o.chunk_frames = int(chunk_frames)
+        o.q15 = 1 if q15 else 0
+        o.clip_lo = float(cfg.net_input_clip_min if clip_min is None else clip_min)
+        o.clip_hi = float(cfg.net_input_clip_max if clip_max is None else clip_max)
+        o.filter = 1 if (output_filter or fsm) else 0
+        o.fsm = 1 if fsm else 0
+        o.filter_alpha, o.true_threshold = float(alpha), float(threshold)
+        g = geometry.to_ctypes()
+        h = ctypes.c_void_p()
+        self.ctx._check(self._L.edison_stream_float_create(self.ctx._h, ctypes.byref(g), ctypes.byref(o), ctypes.byref(h)))
+        self._h = h
+        self.geometry = geometry
+        self.hop, self.chunk = int(geometry.frame_step), int(chunk_frames)
+        self.n_out = int(self.ctx.fnet_info()["n_out"])
+        self.keywords = getattr(self.ctx, "fnet_keywords", None)   # the names of the loaded .ednf (Context.fnet_load)
+        self.output_filter, self.fsm = bool(output_filter or fsm), bool(fsm)
+        self._fsm = _lib.Fsm()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.edison_stream_float_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self.ctx._check(self._L.edison_stream_float_reset(self._h))
+
+    @property
+    def frames_seen(self):
+        return int(self._L.edison_stream_float_frames_seen(self._h))
+
+    def push(self, samples):
+        """samples: chunk_frames * hop new int16 samples (host). Returns dict(logits, probs) float32 [chunk][n_out], argmax [chunk],
+        ``keywords`` (the names of the network's .ednf, ``self.keywords``; KEYWORDS for a 10-output network without names), and with
+        the filter filtered [chunk][n_out] fp32, likely, spotted (-1 = below the threshold); with the state machine fsm_states and fsm."""
+        x = np.ascontiguousarray(samples, dtype=np.int16).ravel()
+        if x.shape[0] != self.chunk * self.hop:
+            raise ValueError("push needs exactly chunk_frames*hop = %d samples" % (self.chunk * self.hop))
+        c, no = self.chunk, self.n_out
+        lo, pr, am = np.zeros((c, no), np.float32), np.zeros((c, no), np.float32), np.zeros(c, np.int32)
+        self.ctx._check(self._L.edison_stream_float_push(self._h, x.ctypes.data, lo.ctypes.data, pr.ctypes.data, am.ctypes.data))
+        out = dict(logits=lo, probs=pr, argmax=am)
+        names = self.keywords or (list(KEYWORDS) if no == NET_OUT else None)
+        if names is not None:
+            out["keywords"] = [names[i] if i < len(names) else str(i) for i in am]
+        if self.output_filter:
+            fl, li, sp = np.zeros((c, no), np.float32), np.zeros(c, np.int32), np.zeros(c, np.int32)
+            self.ctx._check(self._L.edison_stream_float_filtered(self._h, fl.ctypes.data, li.ctypes.data, sp.ctypes.data))
+            out.update(filtered=fl, likely=li, spotted=sp)
+        if self.fsm:
+            st = np.zeros(c, np.int32)
+            self.ctx._check(self._L.edison_stream_float_fsm(self._h, ctypes.byref(self._fsm), st.ctypes.data))
+            out.update(fsm_states=st, fsm=Stream.fsm_snapshot(self))
+        return out
+
+    def push_t(self, samples, logits=None, probs=None, argmax=None, filtered=None, likely=None, spotted=None, n_frames=None):
+        """Device tensors (torch, int16 / fp32 / int32 on the context's GPU); asynchronous on the context's stream. n_frames <
+        chunk_frames: a ragged last push of n_frames * hop samples; every output is [n_frames][..]."""
+        n = self.chunk if n_frames is None else int(n_frames)
+        if samples.numel() != n * self.hop:
+            raise ValueError("push needs exactly n_frames*hop = %d samples" % (n * self.hop))
+        q = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        if n_frames is None:
+            self.ctx._check(self._L.edison_stream_float_push_dev(self._h, q(samples), q(logits), q(probs), q(argmax)))
+        else:
+            self.ctx._check(self._L.edison_stream_float_push_n_dev(self._h, q(samples), n, q(logits), q(probs), q(argmax)))
+        if filtered is not None or likely is not None or spotted is not None:
+            self.ctx._check(self._L.edison_stream_float_filtered_dev(self._h, q(filtered), q(likely), q(spotted)))
+
+
 class Fsm:
     """edisonFSM (app.c:727-928): RESET -> IDLE -> HOT (wake word) -> LOC (location) -> SET (value) -> IDLE."""
     STATES = ("RESET", "IDLE", "HOT", "LOC", "SET")

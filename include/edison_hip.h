@@ -581,6 +581,67 @@ int edison_stream_geom_filtered_dev(edison_stream_geom *s, float *filt, int32_t 
 int edison_stream_geom_fsm(edison_stream_geom *s, struct edison_fsm *fsm, int32_t *states);
 int edison_stream_geom_fsm_dev(edison_stream_geom *s, int32_t *states);
 
+/* ---- continuous mode for the float32 X-CUBE-AI network ------------------------------------------------------------------
+ * The continuous counterpart of edison_kws_float_batch*: the firmware's continuous loop for its default network type, NET_TYPE_CUBE
+ * (app.c:288-371, 630-719), on the float network loaded on the context (edison_fnet_load). A separate object: edison_stream_geom_* and
+ * edison_stream_* stay as they are.
+ *   features      q15 = 0: the host flow of edison_kws_float_batch -- the float64 MFCC at any geometry that call accepts ->
+ *                 (float)y * (float)net_input_scale -> clip to [clip_lo, clip_hi], never rounded. q15 = 1: the firmware flow --
+ *                 variant-C int16 coefficients -> (float), the shipped framing only (frame_len = frame_step = 1024, mel_nbins 32,
+ *                 first_mfcc 0), on the context's Q15 tables: exactly what edison_kws_float_batch(q15 = 1) does.
+ *   hop and window  the hop is g->frame_step: a push carries chunk_frames * frame_step new samples. The window is F = frame_count rows of
+ *                 num_mfcc float32 features; F * num_mfcc must equal the network's input size.
+ *   start state   T = max(0, frame_len - frame_step) samples of silence and F - 1 rows of float zeros (the firmware's static netInput).
+ *   frames        with z = the recording behind T zeros, global frame k is the MFCC of z[k * frame_step ..); when frame_step > frame_len
+ *                 the rest of each hop is skipped.
+ *   outputs       output i of a push is the network on rows k - F + 1 .. k, oldest first (the firmware's append order, not kws_live.py's
+ *                 prepend), k = the push's i-th new frame. logits / probs [n][n_out] float32 and argmax [n] int32 (the first maximum of
+ *                 probs), each may be NULL. For k >= F - 1 they are bit-identical to edison_kws_float_batch on z at offset
+ *                 (k - F + 1) * frame_step.
+ *   filter        (opts.filter) app.c:332-356 over the n_out probabilities p: float32 state starting at zero,
+ *                 state = (float)(alpha * (double)state + (1 - alpha) * (double)p) with the product and the sum rounded separately;
+ *                 then the first maximum, spotted if it is > true_threshold.
+ *   fsm           (opts.fsm, needs filter) edisonFSM behind the filter with dt_us = floor(frame_step * 1e6 / sample_rate); only for a
+ *                 network with 10 outputs.
+ * Errors of create: EDISON_E_NO_MODEL without a float network; EDISON_E_SIZE when F * num_mfcc != its input size or chunk_frames *
+ * frame_step >= 2^30; EDISON_E_NO_IMPL for q15 = 1 off the shipped framing (or without variant-C tables), a filter over more than 256
+ * classes, or fsm on a network without 10 outputs; EDISON_E_ARGUMENT for chunk_frames < 1, fsm without filter, filter_alpha outside
+ * [0, 1], clip_lo > clip_hi; the geometry checks and codes of edison_kws_float_batch otherwise. A push after edison_fnet_load has
+ * replaced the network fails with EDISON_E_ARGUMENT (create a new stream).
+ * A device push is asynchronous on the context's stream: it allocates nothing and does not synchronise. It enqueues one sample copy,
+ * the feature kernel writing the new rows behind the history, the network over the n overlapping windows read in place (an input stride
+ * of num_mfcc floats), the filter, and -- only when the next push would not fit -- the history shift. A host push stages through pinned
+ * memory on a private stream: one upload, one download of one output block, one synchronise. Host and device pushes may alternate: they
+ * share one history. The stream owns its own tables: batch calls at other geometries neither free them nor make a push synchronise. */
+typedef struct edison_stream_float edison_stream_float;
+typedef struct edison_stream_float_opts {
+	int32_t chunk_frames;          /* new frames per push, >= 1 */
+	int32_t q15;                   /* 0: host flow at any geometry; 1: the firmware's variant C, shipped framing */
+	float clip_lo, clip_hi;        /* host flow: the network input's clip range */
+	int32_t filter;                /* 1: moving average, first maximum and threshold over the network's n_out probabilities */
+	int32_t fsm;                   /* 1 (needs filter): edisonFSM behind the filter; only for a network with 10 outputs */
+	double filter_alpha, true_threshold;
+} edison_stream_float_opts;
+/* chunk_frames 1, q15 0, clip -32768 / 32767, filter 0, fsm 0, alpha 0.5 (the Cube build's NET_OUT_MOVING_AVG_ALPHA), threshold 0.5 */
+void edison_stream_float_default_opts(edison_stream_float_opts *o);
+int edison_stream_float_create(edison_ctx *ctx, const edison_kws_geom *g, const edison_stream_float_opts *o, edison_stream_float **out);
+void edison_stream_float_destroy(edison_stream_float *s);
+int edison_stream_float_reset(edison_stream_float *s);
+/* chunk_frames * frame_step new samples; outputs [chunk_frames][..] */
+int edison_stream_float_push(edison_stream_float *s, const int16_t *samples /* host */, float *logits, float *probs, int32_t *argmax);
+int edison_stream_float_push_dev(edison_stream_float *s, const int16_t *samples /* device */, float *logits, float *probs, int32_t *argmax);
+/* 1 <= n_frames <= chunk_frames new frames (n_frames * frame_step samples, outputs [n_frames][..]): the ragged last push of a recording */
+int edison_stream_float_push_n_dev(edison_stream_float *s, const int16_t *samples /* device */, int n_frames, float *logits, float *probs,
+                                   int32_t *argmax);
+int64_t edison_stream_float_frames_seen(const edison_stream_float *s);
+/* Filtered outputs of the LAST push (n = its frames): filt [n][n_out] fp32, likely [n], spotted [n] (-1 below the threshold); each
+ * may be NULL. Host form synchronous, device form ordered on the context's stream. */
+int edison_stream_float_filtered(edison_stream_float *s, float *filt, int32_t *likely, int32_t *spotted);
+int edison_stream_float_filtered_dev(edison_stream_float *s, float *filt, int32_t *likely, int32_t *spotted);
+/* The state machine after the LAST push (*fsm, host, may be NULL) and the state after each of its n inferences (states [n]) */
+int edison_stream_float_fsm(edison_stream_float *s, struct edison_fsm *fsm, int32_t *states);
+int edison_stream_float_fsm_dev(edison_stream_float *s, int32_t *states);
+
 /* ---- the firmware's home-automation state machine (edisonFSM, app.c:727-928), host side, without the LEDs -------
  * RESET -> IDLE -(wake word "edison" spotted)-> HOT -(a location spotted)-> LOC -(a value spotted)-> SET -> IDLE;
  * HOT and LOC fall back to IDLE after EDI_LOC_TIMEOUT = 5000 ms (app.c:48). Time advances by dt_us per call exactly
