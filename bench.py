@@ -5,13 +5,20 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 2 --dry-run          (CPU rehearsal of the N > 1 control flow over gloo: no GPU, no numbers)
     python bench.py ... --dump-outputs DIR      (also writes the last timed step's outputs as DIR/<name>.npy: two builds compared output for output)
+    python bench.py ... --full                  (also every side figure and check: see below)
+
+A plain run does what the headline needs and nothing else: it sets up (inputs, the queue calibration), runs the W warm-up and
+K timed steps of the primary workload, writes the outputs under --dump-outputs (running the KWS step for its part of them) and
+prints the line. Everything else -- `serial_cold`, `serial`, `settled`, the two-queue, rows and list launches, variants A, TF,
+C and D, the KWS figures and their CNN / general-kernel / Q15 legs, streaming, the C hosts, the CPU baselines, the parity check
+against the oracle and, for N > 1, the collective behind the C-ABI -- runs only with --full, in the same order as ever.
 
 With N > 1 and no WORLD_SIZE in the environment the script starts the N ranks ITSELF: child processes created before the
 parent has made any GPU call, the parent only waits, relays rank 0's JSON line and exits non-zero if any rank failed or
 if fewer than N devices are visible (it never prints an n_gpus = 1 line for --gpus 8).
 
 One rank per GPU; every rank works on its own shard (weak scaling: per-GPU work is fixed as N grows).
-Two workloads of BASELINE.json are timed in the same run and reported on ONE JSON line:
+Two workloads of BASELINE.json are timed in the same --full run and reported on ONE JSON line (a plain run reports the primary):
 
   * primary (`value`, `ms_per_step`, `roofline`): BASELINE configs[1] -- batched MFCC only, 65 536 x 1024-sample
     synthetic int16 frames per GPU, variant B, 13 fp32 coefficients out. A step = one pass over the batch.
@@ -23,7 +30,7 @@ Inputs are resident in HBM before the timed region. The MFCC batch (134 MB) woul
 Cache, so the bench rotates over several distinct batches to make every step read from HBM.
 Kernel time is taken with HIP events on the stream the kernels are launched on (torch's current stream, which
 the context is told to use); `roofline.achieved` = algorithmic bytes per launch / average launch duration.
-`cpu_baseline` times the oracle's C restatement (kind "port") on a bounded sample on rank 0 at N = 1 only.
+`cpu_baseline` (--full) times the oracle's C restatement (kind "port") on a bounded sample on rank 0 at N = 1 only.
 """
 import argparse
 import json
@@ -680,12 +687,20 @@ def main():
     ap.add_argument("--frames", type=int, default=65536, help="MFCC frames per GPU per step (BASELINE configs[1])")
     ap.add_argument("--utts", type=int, default=262144, help="KWS utterances per GPU per step (BASELINE configs[2])")
     ap.add_argument("--settle-ms", type=float, default=200.0,
-                    help="untimed repetition of each workload's step before its W warm-up steps, until the clocks have settled")
+                    help="untimed repetition of each side workload's step before its W warm-up steps, until the clocks have settled (--full; "
+                         "the headline has none)")
     ap.add_argument("--rotate", type=int, default=3, help="distinct MFCC input batches cycled through (defeats the 256 MiB L3)")
     ap.add_argument("--queues", type=int, default=0, choices=[0, 1, 2],
                     help="HIP queues of the headline MFCC step. 0 (default): edison_queues_calibrate decides -- two queues (the next batch's launch in flight while "
-                         "this one drains) when a pair of the context's streams beats the serial sequence by 1 %, else one; 1: the serial sequence; 2: two queues whatever "
+                         "this one drains) when a pair of the context's streams beats the serial sequence by 1 %%, else one; 1: the serial sequence; 2: two queues whatever "
                          "the calibration found")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side figure and check after the headline, in this order: serial_cold (before the calibration), serial, "
+                         "two_queues_same_wk, settled, rows_launch, batch_list, two_queues, variants A / TF / C / D, the KWS step with its CNN, "
+                         "general-kernel and Q15 legs, streaming and the C hosts, the CPU baselines and the parity check against the oracle "
+                         "(exit code 5 when it fails), and for N > 1 the collective behind the C-ABI. Without it: setup, the headline's W + K "
+                         "steps, --dump-outputs, the line")
+    # (the legs these skip run only with --full; --skip-kws also leaves the KWS outputs out of --dump-outputs)
     ap.add_argument("--skip-kws", action="store_true")
     ap.add_argument("--skip-cpu", action="store_true")
     ap.add_argument("--skip-stream", action="store_true")
@@ -748,13 +763,15 @@ def main():
     # calibration: 0.15-0.2 s of GPU work, which also wakes the board. (3) THE HEADLINE: W + K steps of the step the calibration chose.
     # (4) `serial`: the same W + K on one queue right after it -- the board in the same state, so headline vs `serial` is the queues'
     # doing and `serial` vs `serial_cold` is the board's. (5) `settled`, both ways.
+    # Without --full the run keeps (2) and (3) only.
     calibration = serial_cold = None
     if args.queues != 1:
-        cw_ms, cev_ms = timed_region(mfcc_step, args.steps, args.warmup, world, 0.0)
-        serial_cold = dict(value=round(world * nf / (cw_ms * 1e-3), 1), unit="frames/s", ms_per_step=round(cw_ms, 4), kernel_ms=round(cev_ms, 4),
-                           roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (cev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                           what="W + K steps, one call per batch on one queue, as the FIRST GPU work of the process: the measurement that was the headline of "
-                                "rounds 1-4 (BENCH_r01-r04), before the queue calibration has run")
+        if args.full:
+            cw_ms, cev_ms = timed_region(mfcc_step, args.steps, args.warmup, world, 0.0)
+            serial_cold = dict(value=round(world * nf / (cw_ms * 1e-3), 1), unit="frames/s", ms_per_step=round(cw_ms, 4), kernel_ms=round(cev_ms, 4),
+                               roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (cev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                               what="W + K steps, one call per batch on one queue, as the FIRST GPU work of the process: the measurement that was the headline of "
+                                    "rounds 1-4 (BENCH_r01-r04), before the queue calibration has run")
         t_c = time.perf_counter()
         try:
             calibration = ctx.queues_calibrate(bufs[0], nf)
@@ -792,10 +809,10 @@ def main():
     dumped = {}
     if args.dump_outputs and rank == 0:
         dumped["mfcc_b"] = (outs2[last & 1] if n_queues == 2 else out).cpu().numpy()
-    # what the LAST timed step left in its output, and the samples it read: checked against the oracle in the cpu_baseline leg (`parity`)
+    # what the LAST timed step left in its output, and the samples it read: checked against the oracle in the cpu_baseline leg (`parity`, --full)
     sample = {}
     n_par = min(4096, nf)
-    if rank == 0 and world == 1 and not args.skip_cpu:
+    if rank == 0 and world == 1 and args.full and not args.skip_cpu:
         sample["frames"] = bufs[last % len(bufs)][:n_par].cpu().numpy()
         sample["mfcc_b"] = (outs2[last & 1] if n_queues == 2 else out)[:n_par].cpu().numpy()
     frames_per_s = world * nf / (wall_ms * 1e-3)
@@ -806,207 +823,203 @@ def main():
     if n_queues == 2:
         roofline["kernel_ms_what"] = ("HIP-event time of the K steps / K = the pitch at which launches complete; with two launches in flight a launch's own "
                                       "duration (what rocprofv3 --kernel-trace reports per dispatch) is about twice that -- it includes the wait for the CUs the "
-                                      "other launch still holds. `serial.kernel_ms` is the one-queue figure that rocprofv3's average agrees with.")
-    serial = None
-    if args.queues != 1:
-        sw_ms, sev1_ms = timed_region(mfcc_step, args.steps, args.warmup, world, 0.0)
-        serial = dict(value=round(world * nf / (sw_ms * 1e-3), 1), unit="frames/s", ms_per_step=round(sw_ms, 4), kernel_ms=round(sev1_ms, 4),
-                      roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (sev1_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                      what="the same W + K steps as one call per batch on ONE queue (edison_mfcc_batch_dev), measured right after the headline (same board state)"
-                           + ("" if n_queues == 2 else "; the headline was this same serial step: the two differ by what a W + K burst scatters from run to run"))
-    # K too small for the queues to pay although a pair was kept: the same W + K on the two queues, right after `serial` -- what the headline would have read
-    # (N > 1: every rank runs this leg or none does -- timed_region holds barriers, and whether a pair was kept is each rank's own finding; a rank without
-    # a pair runs the queue calls on one stream, which is the serial sequence)
-    two_queues_same_wk = None
-    if (pair_kept and n_queues == 1) if world == 1 else (args.queues == 0 and args.steps < MIN_STEPS_TWO_QUEUES):
-        tw_ms, tev_ms = timed_region(q_step, args.steps, args.warmup, world, 0.0, **q_kw)
-        two_queues_same_wk = dict(value=round(world * nf / (tw_ms * 1e-3), 1), unit="frames/s", ms_per_step=round(tw_ms, 4), kernel_ms=round(tev_ms, 4),
-                                  roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (tev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                  what="the same W + K steps over the context's two queues (fork ... join inside the timed region): not the headline because K < %d -- "
-                                       "a fork / join pair costs ~25-30 us per region, the queues gain 1-2 us per step (profiles/r05_two_queues_region_length.txt)" % MIN_STEPS_TWO_QUEUES)
-    settled = None
-    if args.settle_ms > 0:
-        # at least 400 timed steps here whatever K is: a 20-step block of this 45 us step scatters by +-3 % from block to block (profiles/r03_bench_repeatability.txt),
-        # and `settled` is the figure meant to be compared from run to run. Over 400 steps the two queues pay whenever a pair was kept: `settled` uses them then,
-        # whatever the headline's K made it use.
-        n_settled = max(args.steps, 400)
-        set_step, set_kw = (q_step, q_kw) if pair_kept else (mfcc_step, {})
-        s_ms, sev_ms = timed_region(set_step, n_settled, args.warmup, world, args.settle_ms, **set_kw)
-        settled = dict(value=round(world * nf / (s_ms * 1e-3), 1), unit="frames/s", ms_per_step=round(s_ms, 4), kernel_ms=round(sev_ms, 4), steps=n_settled,
-                       roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (sev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), settle_ms=args.settle_ms,
-                       queues=2 if pair_kept else 1,
-                       what="the same workload after settle_ms of untimed repetition of the step in front of the W warm-up steps (clocks and "
-                            "power settled), on two queues when the calibration kept a pair; a side figure, the headline is the W + K run above")
-        # (N > 1: whether a pair was kept is each rank's own finding, and timed_region holds barriers -- every rank runs this leg or none does)
-        if pair_kept if world == 1 else (args.queues != 1):
-            s1_ms, s1ev_ms = timed_region(mfcc_step, n_settled, args.warmup, world, args.settle_ms)
-            settled["serial"] = dict(value=round(world * nf / (s1_ms * 1e-3), 1), ms_per_step=round(s1_ms, 4), kernel_ms=round(s1ev_ms, 4),
-                                     roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (s1ev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
-    # ---- the same batches, several per launch (edison_mfcc_rows_dev: batches that sit at a constant stride are the rows of ONE launch).
-    # The 65 536-frame launch above pays per launch what a longer one amortises -- 2.4 us until the median wave computes, then
-    # waves leaving over 4-5 us at the end: 15 % of the launch window idle, of which the power manager gives ~6 % back as clock
-    # (profiles/r04_mfcc_launch_structure_notes.txt) -- so a caller that streams config-2-sized batches gets the loop's own rate
-    # by handing over a few at a time. A side figure: the headline stays one batch per launch.
-    rows_launch = None
-    try:
-        n_b = 8
-        big = torch.empty((n_b, nf, 1024), dtype=torch.int16, device=dev)
-        for b in range(n_b):
-            big[b] = bufs[b % len(bufs)]
-        out_b = torch.empty((n_b * nf, 13), dtype=torch.float32, device=dev)
+                                      "other launch still holds. `serial.kernel_ms` (--full) is the one-queue figure that rocprofv3's average agrees with.")
+    # ------------------------------------------------------------------ the side figures of the primary workload (--full)
+    serial = two_queues_same_wk = settled = rows_launch = batch_list = two_queues = None
+    variant_a = variant_tf = q15 = variant_d = None
+    if args.full:
+        if args.queues != 1:
+            sw_ms, sev1_ms = timed_region(mfcc_step, args.steps, args.warmup, world, 0.0)
+            serial = dict(value=round(world * nf / (sw_ms * 1e-3), 1), unit="frames/s", ms_per_step=round(sw_ms, 4), kernel_ms=round(sev1_ms, 4),
+                          roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (sev1_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                          what="the same W + K steps as one call per batch on ONE queue (edison_mfcc_batch_dev), measured right after the headline (same board state)"
+                               + ("" if n_queues == 2 else "; the headline was this same serial step: the two differ by what a W + K burst scatters from run to run"))
+        # K too small for the queues to pay although a pair was kept: the same W + K on the two queues, right after `serial` -- what the headline would have read
+        # (N > 1: every rank runs this leg or none does -- timed_region holds barriers, and whether a pair was kept is each rank's own finding; a rank without
+        # a pair runs the queue calls on one stream, which is the serial sequence)
+        if (pair_kept and n_queues == 1) if world == 1 else (args.queues == 0 and args.steps < MIN_STEPS_TWO_QUEUES):
+            tw_ms, tev_ms = timed_region(q_step, args.steps, args.warmup, world, 0.0, **q_kw)
+            two_queues_same_wk = dict(value=round(world * nf / (tw_ms * 1e-3), 1), unit="frames/s", ms_per_step=round(tw_ms, 4), kernel_ms=round(tev_ms, 4),
+                                      roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (tev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                      what="the same W + K steps over the context's two queues (fork ... join inside the timed region): not the headline because K < %d -- "
+                                           "a fork / join pair costs ~25-30 us per region, the queues gain 1-2 us per step (profiles/r05_two_queues_region_length.txt)" % MIN_STEPS_TWO_QUEUES)
+        if args.settle_ms > 0:
+            # at least 400 timed steps here whatever K is: a 20-step block of this 45 us step scatters by +-3 % from block to block (profiles/r03_bench_repeatability.txt),
+            # and `settled` is the figure meant to be compared from run to run. Over 400 steps the two queues pay whenever a pair was kept: `settled` uses them then,
+            # whatever the headline's K made it use.
+            n_settled = max(args.steps, 400)
+            set_step, set_kw = (q_step, q_kw) if pair_kept else (mfcc_step, {})
+            s_ms, sev_ms = timed_region(set_step, n_settled, args.warmup, world, args.settle_ms, **set_kw)
+            settled = dict(value=round(world * nf / (s_ms * 1e-3), 1), unit="frames/s", ms_per_step=round(s_ms, 4), kernel_ms=round(sev_ms, 4), steps=n_settled,
+                           roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (sev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), settle_ms=args.settle_ms,
+                           queues=2 if pair_kept else 1,
+                           what="the same workload after settle_ms of untimed repetition of the step in front of the W warm-up steps (clocks and "
+                                "power settled), on two queues when the calibration kept a pair; a side figure, the headline is the W + K run above")
+            # (N > 1: whether a pair was kept is each rank's own finding, and timed_region holds barriers -- every rank runs this leg or none does)
+            if pair_kept if world == 1 else (args.queues != 1):
+                s1_ms, s1ev_ms = timed_region(mfcc_step, n_settled, args.warmup, world, args.settle_ms)
+                settled["serial"] = dict(value=round(world * nf / (s1_ms * 1e-3), 1), ms_per_step=round(s1_ms, 4), kernel_ms=round(s1ev_ms, 4),
+                                         roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (s1ev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
+        # ---- the same batches, several per launch (edison_mfcc_rows_dev: batches that sit at a constant stride are the rows of ONE launch).
+        # The 65 536-frame launch above pays per launch what a longer one amortises -- 2.4 us until the median wave computes, then
+        # waves leaving over 4-5 us at the end: 15 % of the launch window idle, of which the power manager gives ~6 % back as clock
+        # (profiles/r04_mfcc_launch_structure_notes.txt) -- so a caller that streams config-2-sized batches gets the loop's own rate
+        # by handing over a few at a time. A side figure: the headline stays one batch per launch.
+        try:
+            n_b = 8
+            big = torch.empty((n_b, nf, 1024), dtype=torch.int16, device=dev)
+            for b in range(n_b):
+                big[b] = bufs[b % len(bufs)]
+            out_b = torch.empty((n_b * nf, 13), dtype=torch.float32, device=dev)
 
-        def rows_step(i):
-            ctx.mfcc_rows_t(big, n_b, nf * 1024, nf, 1024, _lib.MFCC_B, 13, out=out_b)
-        r_ms, rev_ms = timed_region(rows_step, max(20, args.steps // n_b), max(3, min(args.warmup, 2000) // n_b), world, args.settle_ms)
-        rows_launch = dict(batches_per_launch=n_b, value=round(world * n_b * nf / (r_ms * 1e-3), 1), unit="frames/s", ms_per_launch=round(r_ms, 4),
-                           us_per_65536_frames=round(rev_ms * 1e3 / n_b * 65536 / nf, 2),
-                           roofline_frac=round(MFCC_BYTES_PER_FRAME * n_b * nf / (rev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                           what="%d batches of %d frames, %d samples apart, as the rows of one edison_mfcc_rows_dev launch (settled); the kernel is the grouped instantiation %s" % (n_b, nf, nf * 1024, MFCC_KERNEL_KWS))
-        del big, out_b
-    except Exception as e:  # a side figure must never cost the headline numbers
-        rows_launch = dict(error=repr(e))
+            def rows_step(i):
+                ctx.mfcc_rows_t(big, n_b, nf * 1024, nf, 1024, _lib.MFCC_B, 13, out=out_b)
+            r_ms, rev_ms = timed_region(rows_step, max(20, args.steps // n_b), max(3, min(args.warmup, 2000) // n_b), world, args.settle_ms)
+            rows_launch = dict(batches_per_launch=n_b, value=round(world * n_b * nf / (r_ms * 1e-3), 1), unit="frames/s", ms_per_launch=round(r_ms, 4),
+                               us_per_65536_frames=round(rev_ms * 1e3 / n_b * 65536 / nf, 2),
+                               roofline_frac=round(MFCC_BYTES_PER_FRAME * n_b * nf / (rev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                               what="%d batches of %d frames, %d samples apart, as the rows of one edison_mfcc_rows_dev launch (settled); the kernel is the grouped instantiation %s" % (n_b, nf, nf * 1024, MFCC_KERNEL_KWS))
+            del big, out_b
+        except Exception as e:  # a side figure must never cost the headline numbers
+            rows_launch = dict(error=repr(e))
 
-    # ---- ... and as a LIST of independent batches (edison_mfcc_batches_dev, round 5): separate allocations, own output each, no common
-    # stride -- what a caller has whose batches come from different producers. Same loop, one launch per list.
-    batch_list = None
-    try:
-        n_b = 8
-        pads, ins, outs_l = [], [], []
-        for b in range(n_b):
-            pads.append(torch.empty((4099 * (b + 1),), dtype=torch.int8, device=dev))   # keeps the allocations from lining up
-            ins.append(bufs[b % len(bufs)].clone())
-            outs_l.append(torch.empty((nf, 13), dtype=torch.float32, device=dev))
+        # ---- ... and as a LIST of independent batches (edison_mfcc_batches_dev, round 5): separate allocations, own output each, no common
+        # stride -- what a caller has whose batches come from different producers. Same loop, one launch per list.
+        try:
+            n_b = 8
+            pads, ins, outs_l = [], [], []
+            for b in range(n_b):
+                pads.append(torch.empty((4099 * (b + 1),), dtype=torch.int8, device=dev))   # keeps the allocations from lining up
+                ins.append(bufs[b % len(bufs)].clone())
+                outs_l.append(torch.empty((nf, 13), dtype=torch.float32, device=dev))
 
-        def list_step(i):
-            ctx.mfcc_batches_t(ins, nf, 1024, _lib.MFCC_B, 13, outs=outs_l)
-        l_ms, lev_ms = timed_region(list_step, max(20, args.steps // n_b), max(3, min(args.warmup, 2000) // n_b), world, args.settle_ms)
-        ctx.mfcc_t(ins[n_b - 1], nf, 1024, _lib.MFCC_B, 13, out=out)
-        same_l = bool(torch.equal(out, outs_l[n_b - 1]))
-        batch_list = dict(batches_per_launch=n_b, value=round(world * n_b * nf / (l_ms * 1e-3), 1), unit="frames/s", ms_per_launch=round(l_ms, 4),
-                          us_per_65536_frames=round(lev_ms * 1e3 / n_b * 65536 / nf, 2),
-                          roofline_frac=round(MFCC_BYTES_PER_FRAME * n_b * nf / (lev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                          outputs_bit_identical_to_one_call_per_batch=same_l,
-                          what="%d independent batches of %d frames (separate allocations, own outputs) as ONE edison_mfcc_batches_dev launch (settled); kernel ed_mfcc2_list_kernel<true, 2, 5>" % (n_b, nf))
-        del pads, ins, outs_l
-    except Exception as e:  # a side figure must never cost the headline numbers
-        batch_list = dict(error=repr(e))
+            def list_step(i):
+                ctx.mfcc_batches_t(ins, nf, 1024, _lib.MFCC_B, 13, outs=outs_l)
+            l_ms, lev_ms = timed_region(list_step, max(20, args.steps // n_b), max(3, min(args.warmup, 2000) // n_b), world, args.settle_ms)
+            ctx.mfcc_t(ins[n_b - 1], nf, 1024, _lib.MFCC_B, 13, out=out)
+            same_l = bool(torch.equal(out, outs_l[n_b - 1]))
+            batch_list = dict(batches_per_launch=n_b, value=round(world * n_b * nf / (l_ms * 1e-3), 1), unit="frames/s", ms_per_launch=round(l_ms, 4),
+                              us_per_65536_frames=round(lev_ms * 1e3 / n_b * 65536 / nf, 2),
+                              roofline_frac=round(MFCC_BYTES_PER_FRAME * n_b * nf / (lev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                              outputs_bit_identical_to_one_call_per_batch=same_l,
+                              what="%d independent batches of %d frames (separate allocations, own outputs) as ONE edison_mfcc_batches_dev launch (settled); kernel ed_mfcc2_list_kernel<true, 2, 5>" % (n_b, nf))
+            del pads, ins, outs_l
+        except Exception as e:  # a side figure must never cost the headline numbers
+            batch_list = dict(error=repr(e))
 
-    # ---- two queues against one, interleaved (8 blocks of 300 batches each, medians): the evidence behind `config.queues`, whatever the
-    # calibration chose. The library's own two queues (the calibrated pair, or one stream of each priority without a calibration).
-    two_queues = None
-    try:
-        if args.queues == 1:
-            raise RuntimeError("--queues 1: every launch of this run is on one queue (the profiled passes whose per-launch durations are quoted)")
-        ctx.queues_fork()
-        for i in range(4):
-            q_step(i)
-        ctx.queues_join()
-        ref_o = torch.empty((nf, 13), dtype=torch.float32, device=dev)
-        ctx.mfcc_t(bufs[2 % len(bufs)], nf, 1024, _lib.MFCC_B, 13, out=ref_o)
-        same = bool(torch.equal(outs2[0], ref_o))
-        ctx.mfcc_t(bufs[3 % len(bufs)], nf, 1024, _lib.MFCC_B, 13, out=ref_o)
-        same = same and bool(torch.equal(outs2[1], ref_o))
-        torch.cuda.synchronize()
-        n2 = 300     # batches per timed block; a 40-batch block of this step scatters by +-5 %
+        # ---- two queues against one, interleaved (8 blocks of 300 batches each, medians): the evidence behind `config.queues`, whatever the
+        # calibration chose. The library's own two queues (the calibrated pair, or one stream of each priority without a calibration).
+        try:
+            if args.queues == 1:
+                raise RuntimeError("--queues 1: every launch of this run is on one queue (the profiled passes whose per-launch durations are quoted)")
+            ctx.queues_fork()
+            for i in range(4):
+                q_step(i)
+            ctx.queues_join()
+            ref_o = torch.empty((nf, 13), dtype=torch.float32, device=dev)
+            ctx.mfcc_t(bufs[2 % len(bufs)], nf, 1024, _lib.MFCC_B, 13, out=ref_o)
+            same = bool(torch.equal(outs2[0], ref_o))
+            ctx.mfcc_t(bufs[3 % len(bufs)], nf, 1024, _lib.MFCC_B, 13, out=ref_o)
+            same = same and bool(torch.equal(outs2[1], ref_o))
+            torch.cuda.synchronize()
+            n2 = 300     # batches per timed block; a 40-batch block of this step scatters by +-5 %
 
-        def block(step, two):
-            for i in range(30):
-                if not two:
+            def block(step, two):
+                for i in range(30):
+                    if not two:
+                        step(i)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                if two:
+                    ctx.queues_fork()
+                for i in range(n2):
                     step(i)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            if two:
-                ctx.queues_fork()
-            for i in range(n2):
-                step(i)
-            if two:
-                ctx.queues_join()
-            e1.record(stream)
-            torch.cuda.synchronize()
-            return e0.elapsed_time(e1) / n2
-        t_end = time.perf_counter() + 0.2           # settle the clocks on the serial step
-        while time.perf_counter() < t_end:
-            for i in range(256):
-                mfcc_step(i)
-            torch.cuda.synchronize()
-        ts2, ts1 = [], []
-        for r in range(8):
-            for leg in ((1, 2) if r % 2 == 0 else (2, 1)):
-                (ts2 if leg == 2 else ts1).append(block(q_step, True) if leg == 2 else block(mfcc_step, False))
-        t2, t1 = sorted(ts2)[len(ts2) // 2], sorted(ts1)[len(ts1) // 2]
-        two_queues = dict(queues=2, ms_per_batch=round(t2, 4), serial_ms_per_batch=round(t1, 4), vs_serial=round(t1 / t2, 4),
-                          value=round(world * nf / (t2 * 1e-3), 1), unit="frames/s", outputs_bit_identical_to_serial=same,
-                          roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (t2 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                          what="one %d-frame batch per launch, own output each, launches alternating over the context's two queues (edison_queues_fork / "
-                               "edison_mfcc_batch_queue_dev / edison_queues_join); medians of 8 interleaved blocks of %d batches each, settled, the serial control beside it" % (nf, n2))
-        del ref_o
-    except Exception as e:  # a side figure must never cost the headline numbers
-        two_queues = dict(error=repr(e))
+                if two:
+                    ctx.queues_join()
+                e1.record(stream)
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1) / n2
+            t_end = time.perf_counter() + 0.2           # settle the clocks on the serial step
+            while time.perf_counter() < t_end:
+                for i in range(256):
+                    mfcc_step(i)
+                torch.cuda.synchronize()
+            ts2, ts1 = [], []
+            for r in range(8):
+                for leg in ((1, 2) if r % 2 == 0 else (2, 1)):
+                    (ts2 if leg == 2 else ts1).append(block(q_step, True) if leg == 2 else block(mfcc_step, False))
+            t2, t1 = sorted(ts2)[len(ts2) // 2], sorted(ts1)[len(ts1) // 2]
+            two_queues = dict(queues=2, ms_per_batch=round(t2, 4), serial_ms_per_batch=round(t1, 4), vs_serial=round(t1 / t2, 4),
+                              value=round(world * nf / (t2 * 1e-3), 1), unit="frames/s", outputs_bit_identical_to_serial=same,
+                              roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (t2 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                              what="one %d-frame batch per launch, own output each, launches alternating over the context's two queues (edison_queues_fork / "
+                                   "edison_mfcc_batch_queue_dev / edison_queues_join); medians of 8 interleaved blocks of %d batches each, settled, the serial control beside it" % (nf, n2))
+            del ref_o
+        except Exception as e:  # a side figure must never cost the headline numbers
+            two_queues = dict(error=repr(e))
 
-    # ------------------------------------------------------------------ variant A (log-mel, mfcc_utils.mfcc), same batch
-    def mfcc_a_step(i):
-        ctx.mfcc_t(bufs[i % len(bufs)], nf, 1024, _lib.MFCC_A, 13, out=out)
-    a_ms, aev_ms = timed_region(mfcc_a_step, args.steps, args.warmup, world, args.settle_ms)
-    if sample:
-        sample["frames_a"] = bufs[(args.warmup + args.steps - 1) % len(bufs)][:n_par].cpu().numpy()
-        sample["mfcc_a"] = out[:n_par].cpu().numpy()
-    variant_a = dict(metric="MFCC frames/sec, variant A (ln + DCT, mfcc_utils.mfcc)", unit="frames/s",
-                     value=round(world * nf / (a_ms * 1e-3), 1), ms_per_step=round(a_ms, 4), kernel_ms=round(aev_ms, 4),
-                     roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (aev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
-
-    # ------------------------------------------------------------------ variant TF (windowed frames: the TensorFlow curve of `main.py mfcc host`), same batch
-    def mfcc_tf_step(i):
-        ctx.mfcc_t(bufs[i % len(bufs)], nf, 1024, _lib.MFCC_TF, 13, out=out)
-    t_ms, tev_ms = timed_region(mfcc_tf_step, args.steps, args.warmup, world, args.settle_ms)
-    variant_tf = dict(metric="MFCC frames/sec, variant TF (Hann window + ln + DCT, mfcc_utils.mfcc_tf)", unit="frames/s",
-                      value=round(world * nf / (t_ms * 1e-3), 1), ms_per_step=round(t_ms, 4), kernel_ms=round(tev_ms, 4),
-                      roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (tev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                      parity="UNPINNED: TensorFlow is not in this image and the reference holds no output of it; checked against a float64 restatement of tf.signal's definitions only",
-                      what="the two-frame loop with the window multiplied in at the unpack (ed_mfcc2_window_kernel; round 5)")
-
-    # ------------------------------------------------------------------ variant C: the firmware's Q15 MFCC, same batch
-    q15 = None
-    if not args.skip_q15:
-        out16 = torch.empty((nf, 13), dtype=torch.int16, device=dev)
-
-        def q15_step(i):
-            ctx.mfcc_q15_t(bufs[i % len(bufs)], nf, 1024, 13, out=out16)
-        q_ms, qev_ms = timed_region(q15_step, args.steps, args.warmup, world, args.settle_ms)
+        # ------------------------------------------------------------------ variant A (log-mel, mfcc_utils.mfcc), same batch
+        def mfcc_a_step(i):
+            ctx.mfcc_t(bufs[i % len(bufs)], nf, 1024, _lib.MFCC_A, 13, out=out)
+        a_ms, aev_ms = timed_region(mfcc_a_step, args.steps, args.warmup, world, args.settle_ms)
         if sample:
-            sample["frames_q15"] = bufs[(args.warmup + args.steps - 1) % len(bufs)][:n_par].cpu().numpy()
-            sample["mfcc_q15"] = out16[:n_par].cpu().numpy()
-        qbytes = 2048 + 13 * 2
-        qach = qbytes * nf / (qev_ms * 1e-3) / 1e9
-        q15 = dict(metric="MFCC frames/sec, variant C (firmware Q15 arithmetic, bit-exact)", unit="frames/s",
-                   value=round(world * nf / (q_ms * 1e-3), 1), ms_per_step=round(q_ms, 4), dtype="q15/q31",
-                   config=dict(workload="mfcc_batch_%dx1024_int16_per_gpu_variantC_13coef" % nf, global_batch=world * nf),
-                   roofline=dict(bound="hbm", kernel="ed_mfcc_q15_kernel<false>", achieved=round(qach, 1), peak=HBM_PEAK_GBS,
-                                 unit="GB/s", frac=round(qach / HBM_PEAK_GBS, 4), traffic=None, bytes_per_unit=qbytes,
-                                 units_per_launch=nf, kernel_ms=round(qev_ms, 4)),
-                   )
-        q15["roofline"]["kernel"] = "ed_mfcc_q15_kernel<false, true, 6, 18>"
-        qtr = hbm_traffic_from_profiles("ed_mfcc_q15_kernel<false, true, 6, 18>:short") if nf == 65536 else None
-        if qtr is not None:
-            q15["roofline"]["traffic"] = qtr[0]
-            q15["roofline"]["traffic_source"] = qtr[1]
-    # ------------------------------------------------------------------ variant D: the firmware's float32 extractor, 512-sample frames at hop 256
-    variant_d = None
-    try:
-        from edison_amd.mfcc.mfcc_f32 import MfccF32
-        md = MfccF32(ctx=ctx)
-        flat = bufs[0].reshape(-1)
-        nfd = (flat.numel() - 512) // 256 + 1
-        outd = torch.empty((nfd, md.n_out), dtype=torch.int8, device=dev)
+            sample["frames_a"] = bufs[(args.warmup + args.steps - 1) % len(bufs)][:n_par].cpu().numpy()
+            sample["mfcc_a"] = out[:n_par].cpu().numpy()
+        variant_a = dict(metric="MFCC frames/sec, variant A (ln + DCT, mfcc_utils.mfcc)", unit="frames/s",
+                         value=round(world * nf / (a_ms * 1e-3), 1), ms_per_step=round(a_ms, 4), kernel_ms=round(aev_ms, 4),
+                         roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (aev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
 
-        def d_step(i):
-            md.compute_t(bufs[i % len(bufs)].reshape(-1), nfd, 256, outd)
-        d_ms, dev_ms = timed_region(d_step, max(20, args.steps // 4), min(args.warmup, 50), world)
-        variant_d = dict(metric="MFCC frames/sec, variant D (firmware float32 ML-KWS extractor, 512-sample frames, hop 256)", unit="frames/s",
-                         value=round(world * nfd / (d_ms * 1e-3), 1), ms_per_step=round(d_ms, 4), kernel_ms=round(dev_ms, 4),
-                         frames_per_step=nfd, parity="pinned on the reference's object code (mfcc_compute + CMSIS float transform; tests/golden/mfccf32_golden.npz)")
-        md.close()
-    except Exception as e:  # an extra workload must never cost the headline numbers
-        variant_d = dict(error=repr(e))
+        # ------------------------------------------------------------------ variant TF (windowed frames: the TensorFlow curve of `main.py mfcc host`), same batch
+        def mfcc_tf_step(i):
+            ctx.mfcc_t(bufs[i % len(bufs)], nf, 1024, _lib.MFCC_TF, 13, out=out)
+        t_ms, tev_ms = timed_region(mfcc_tf_step, args.steps, args.warmup, world, args.settle_ms)
+        variant_tf = dict(metric="MFCC frames/sec, variant TF (Hann window + ln + DCT, mfcc_utils.mfcc_tf)", unit="frames/s",
+                          value=round(world * nf / (t_ms * 1e-3), 1), ms_per_step=round(t_ms, 4), kernel_ms=round(tev_ms, 4),
+                          roofline_frac=round(MFCC_BYTES_PER_FRAME * nf / (tev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                          parity="UNPINNED: TensorFlow is not in this image and the reference holds no output of it; checked against a float64 restatement of tf.signal's definitions only",
+                          what="the two-frame loop with the window multiplied in at the unpack (ed_mfcc2_window_kernel; round 5)")
+
+        # ------------------------------------------------------------------ variant C: the firmware's Q15 MFCC, same batch
+        if not args.skip_q15:
+            out16 = torch.empty((nf, 13), dtype=torch.int16, device=dev)
+
+            def q15_step(i):
+                ctx.mfcc_q15_t(bufs[i % len(bufs)], nf, 1024, 13, out=out16)
+            q_ms, qev_ms = timed_region(q15_step, args.steps, args.warmup, world, args.settle_ms)
+            if sample:
+                sample["frames_q15"] = bufs[(args.warmup + args.steps - 1) % len(bufs)][:n_par].cpu().numpy()
+                sample["mfcc_q15"] = out16[:n_par].cpu().numpy()
+            qbytes = 2048 + 13 * 2
+            qach = qbytes * nf / (qev_ms * 1e-3) / 1e9
+            q15 = dict(metric="MFCC frames/sec, variant C (firmware Q15 arithmetic, bit-exact)", unit="frames/s",
+                       value=round(world * nf / (q_ms * 1e-3), 1), ms_per_step=round(q_ms, 4), dtype="q15/q31",
+                       config=dict(workload="mfcc_batch_%dx1024_int16_per_gpu_variantC_13coef" % nf, global_batch=world * nf),
+                       roofline=dict(bound="hbm", kernel="ed_mfcc_q15_kernel<false>", achieved=round(qach, 1), peak=HBM_PEAK_GBS,
+                                     unit="GB/s", frac=round(qach / HBM_PEAK_GBS, 4), traffic=None, bytes_per_unit=qbytes,
+                                     units_per_launch=nf, kernel_ms=round(qev_ms, 4)),
+                       )
+            q15["roofline"]["kernel"] = "ed_mfcc_q15_kernel<false, true, 6, 18>"
+            qtr = hbm_traffic_from_profiles("ed_mfcc_q15_kernel<false, true, 6, 18>:short") if nf == 65536 else None
+            if qtr is not None:
+                q15["roofline"]["traffic"] = qtr[0]
+                q15["roofline"]["traffic_source"] = qtr[1]
+        # ------------------------------------------------------------------ variant D: the firmware's float32 extractor, 512-sample frames at hop 256
+        try:
+            from edison_amd.mfcc.mfcc_f32 import MfccF32
+            md = MfccF32(ctx=ctx)
+            flat = bufs[0].reshape(-1)
+            nfd = (flat.numel() - 512) // 256 + 1
+            outd = torch.empty((nfd, md.n_out), dtype=torch.int8, device=dev)
+
+            def d_step(i):
+                md.compute_t(bufs[i % len(bufs)].reshape(-1), nfd, 256, outd)
+            d_ms, dev_ms = timed_region(d_step, max(20, args.steps // 4), min(args.warmup, 50), world)
+            variant_d = dict(metric="MFCC frames/sec, variant D (firmware float32 ML-KWS extractor, 512-sample frames, hop 256)", unit="frames/s",
+                             value=round(world * nfd / (d_ms * 1e-3), 1), ms_per_step=round(d_ms, 4), kernel_ms=round(dev_ms, 4),
+                             frames_per_step=nfd, parity="pinned on the reference's object code (mfcc_compute + CMSIS float transform; tests/golden/mfccf32_golden.npz)")
+            md.close()
+        except Exception as e:  # an extra workload must never cost the headline numbers
+            variant_d = dict(error=repr(e))
     del bufs, q_calls, outs2
     # HBM bytes per launch from the committed PMC passes (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE runs of
     # this command, FETCH_SIZE doubled as the gfx950 guide prescribes); only valid for the default batch size
@@ -1017,7 +1030,7 @@ def main():
 
     # ------------------------------------------------------------------ kws: MFCC + int8 CNN (+ all-gather) (configs[2]/[3])
     kws = None
-    if not args.skip_kws:
+    if not args.skip_kws and (args.full or args.dump_outputs):
         nu = args.utts
         audio = synth_utterances(nu, 21 + rank, dev)
         logits = torch.empty((nu, 10), dtype=torch.int8, device=dev)
@@ -1043,98 +1056,99 @@ def main():
         kw_ms, kev_ms = timed_region(kws_step, args.steps, min(args.warmup, 50), world)
         if args.dump_outputs and rank == 0:
             dumped.update(kws_logits=logits.cpu().numpy(), kws_softmax=soft.cpu().numpy(), kws_argmax=am.cpu().numpy())
-        if sample:
-            n_pu = min(128, nu)
-            sample["utt_audio"] = audio[:n_pu].cpu().numpy()
-            sample["utt_feat"], sample["utt_logits"] = feat[:n_pu].cpu().numpy(), logits[:n_pu].cpu().numpy()
-            sample["utt_softmax"], sample["utt_argmax"] = soft[:n_pu].cpu().numpy(), am[:n_pu].cpu().numpy()
-        inf_per_s = world * nu / (kw_ms * 1e-3)
-        kach = KWS_BYTES_PER_UTT * nu / (kev_ms * 1e-3) / 1e9
-        hist = torch.bincount(am.to(torch.int64), minlength=10).tolist()
-        kws = dict(metric="KWS inferences/sec (whole node)", value=round(inf_per_s, 1), unit="inferences/s",
-                   mfcc_frames_per_s=round(inf_per_s * 31, 1), ms_per_step=round(kw_ms, 4),
-                   config=dict(workload="kws_full_%d_utt_per_gpu_x31_frames_mfccB_int8cnn" % nu, global_batch=world * nu,
-                               collective=collective),
-                   roofline=dict(bound="hbm", kernel=MFCC_KERNEL_KWS + " + ed_cnn_mfma_kernel", achieved=round(kach, 1),
-                                 peak=HBM_PEAK_GBS, unit="GB/s", frac=round(kach / HBM_PEAK_GBS, 4), traffic=None,
-                                 bytes_per_unit=KWS_BYTES_PER_UTT, units_per_launch=nu, kernel_ms=round(kev_ms, 4)),
-                   class_histogram=hist,
-                   # which gather `value` used: the product's own (edison_kws_batch_sharded_dev: ncclAllGather behind the C-ABI) is the
-                   # guarded leg at the end of the run; when that leg returns ok its figure is `value_cabi` right here
-                   collective_path="torch.distributed" if world > 1 else "none (one rank: nothing to gather)")
-        # HBM bytes of the step's dominant kernel (the MFCC over 8.1 M frames: 95 % of the step) from the committed PMC pass;
-        # the CNN adds 403 B read + 24 B written per utterance (its counters: kws.cnn.roofline.counters)
-        ktr = hbm_traffic_from_profiles(MFCC_KERNEL_KWS + ":long") if nu == 262144 else None
-        if ktr is not None:
-            kws["roofline"]["traffic"] = ktr[0]
-            kws["roofline"]["traffic_source"] = ktr[1]
-            kws["roofline"]["traffic_what"] = "FETCH_SIZE x 2 + WRITE_SIZE of the MFCC kernel of the step; + 427 B per utterance for the CNN"
-        # ---- the CNN alone on the features of the last step: the matrix-core figure north_star asks for
-        def cnn_step(i):
-            ctx.cnn_t(feat, nu, logits=logits, softmax=soft, argmax=am)
-        c_ms, cev_ms = timed_region(cnn_step, max(100, min(args.steps, 200)), 20, 1 if world == 1 else world)  # 0.3 ms steps: 100 of them = 30 ms
-        useful = nu * CNN_MACS_PER_UTT * 2 / (cev_ms * 1e-3) / 1e12
-        issued = nu * CNN_MFMA_MACS_PER_UTT * 2 / (cev_ms * 1e-3) / 1e12
-        kws["cnn"] = dict(metric="int8 CNN alone (ed_cnn_mfma_kernel)", value=round(world * nu / (c_ms * 1e-3), 1), unit="inferences/s",
-                          ms_per_step=round(c_ms, 4),
-                          roofline=dict(bound="mfma_i8", kernel="ed_cnn_mfma_kernel", achieved=round(useful, 1), peak=round(MFMA_I8_PEAK_TOPS, 1),
-                                        unit="TOP/s", frac=round(useful / MFMA_I8_PEAK_TOPS, 4), kernel_ms=round(cev_ms, 4),
-                                        what="achieved = real network MACs (784 752 per utterance) x 2; issued = the MACs of the MFMA instructions issued (32 768 per 32x32x32, 16 384 per 16x16x64) x 2",
-                                        issued=round(issued, 1), issued_frac=round(issued / MFMA_I8_PEAK_TOPS, 4),
-                                        counters=cnn_counters_from_profiles()))
-        # ---- the same graph through the GENERAL matrix-core kernel (what any other retrained graph runs on)
-        os.environ["EDISON_NET_FORCE_GENERAL"] = "1"
-        try:
-            def net_step(i):
-                ctx.net_t(feat, nu, logits=logits, argmax=am)
-            g_ms, _ = timed_region(net_step, 10, 2, 1 if world == 1 else world)
-            kws["general_net_kernel"] = dict(value=round(world * nu / (g_ms * 1e-3), 1), unit="inputs/s", ms_per_step=round(g_ms, 4),
-                                             what="kws_conv graph forced onto ed_net_mfma_kernel (edison_net_batch_dev, EDISON_NET_FORCE_GENERAL=1)")
-            # ... and through the graph's OWN kernel: the same source compiled at run time with this graph's plan as constants
-            # (edison_net_specialize); checked bit for bit against the hand-written kernel's logits of the same features
-            # (N = 1 only: a per-GPU kernel figure, and a compiler that fails on ONE rank must not leave the others in a barrier)
+        if args.full:     # (without it the KWS step ran only for what --dump-outputs writes)
+            if sample:
+                n_pu = min(128, nu)
+                sample["utt_audio"] = audio[:n_pu].cpu().numpy()
+                sample["utt_feat"], sample["utt_logits"] = feat[:n_pu].cpu().numpy(), logits[:n_pu].cpu().numpy()
+                sample["utt_softmax"], sample["utt_argmax"] = soft[:n_pu].cpu().numpy(), am[:n_pu].cpu().numpy()
+            inf_per_s = world * nu / (kw_ms * 1e-3)
+            kach = KWS_BYTES_PER_UTT * nu / (kev_ms * 1e-3) / 1e9
+            hist = torch.bincount(am.to(torch.int64), minlength=10).tolist()
+            kws = dict(metric="KWS inferences/sec (whole node)", value=round(inf_per_s, 1), unit="inferences/s",
+                       mfcc_frames_per_s=round(inf_per_s * 31, 1), ms_per_step=round(kw_ms, 4),
+                       config=dict(workload="kws_full_%d_utt_per_gpu_x31_frames_mfccB_int8cnn" % nu, global_batch=world * nu,
+                                   collective=collective),
+                       roofline=dict(bound="hbm", kernel=MFCC_KERNEL_KWS + " + ed_cnn_mfma_kernel", achieved=round(kach, 1),
+                                     peak=HBM_PEAK_GBS, unit="GB/s", frac=round(kach / HBM_PEAK_GBS, 4), traffic=None,
+                                     bytes_per_unit=KWS_BYTES_PER_UTT, units_per_launch=nu, kernel_ms=round(kev_ms, 4)),
+                       class_histogram=hist,
+                       # which gather `value` used: the product's own (edison_kws_batch_sharded_dev: ncclAllGather behind the C-ABI) is the
+                       # guarded leg at the end of the run; when that leg returns ok its figure is `value_cabi` right here
+                       collective_path="torch.distributed" if world > 1 else "none (one rank: nothing to gather)")
+            # HBM bytes of the step's dominant kernel (the MFCC over 8.1 M frames: 95 % of the step) from the committed PMC pass;
+            # the CNN adds 403 B read + 24 B written per utterance (its counters: kws.cnn.roofline.counters)
+            ktr = hbm_traffic_from_profiles(MFCC_KERNEL_KWS + ":long") if nu == 262144 else None
+            if ktr is not None:
+                kws["roofline"]["traffic"] = ktr[0]
+                kws["roofline"]["traffic_source"] = ktr[1]
+                kws["roofline"]["traffic_what"] = "FETCH_SIZE x 2 + WRITE_SIZE of the MFCC kernel of the step; + 427 B per utterance for the CNN"
+            # ---- the CNN alone on the features of the last step: the matrix-core figure north_star asks for
+            def cnn_step(i):
+                ctx.cnn_t(feat, nu, logits=logits, softmax=soft, argmax=am)
+            c_ms, cev_ms = timed_region(cnn_step, max(100, min(args.steps, 200)), 20, 1 if world == 1 else world)  # 0.3 ms steps: 100 of them = 30 ms
+            useful = nu * CNN_MACS_PER_UTT * 2 / (cev_ms * 1e-3) / 1e12
+            issued = nu * CNN_MFMA_MACS_PER_UTT * 2 / (cev_ms * 1e-3) / 1e12
+            kws["cnn"] = dict(metric="int8 CNN alone (ed_cnn_mfma_kernel)", value=round(world * nu / (c_ms * 1e-3), 1), unit="inferences/s",
+                              ms_per_step=round(c_ms, 4),
+                              roofline=dict(bound="mfma_i8", kernel="ed_cnn_mfma_kernel", achieved=round(useful, 1), peak=round(MFMA_I8_PEAK_TOPS, 1),
+                                            unit="TOP/s", frac=round(useful / MFMA_I8_PEAK_TOPS, 4), kernel_ms=round(cev_ms, 4),
+                                            what="achieved = real network MACs (784 752 per utterance) x 2; issued = the MACs of the MFMA instructions issued (32 768 per 32x32x32, 16 384 per 16x16x64) x 2",
+                                            issued=round(issued, 1), issued_frac=round(issued / MFMA_I8_PEAK_TOPS, 4),
+                                            counters=cnn_counters_from_profiles()))
+            # ---- the same graph through the GENERAL matrix-core kernel (what any other retrained graph runs on)
+            os.environ["EDISON_NET_FORCE_GENERAL"] = "1"
             try:
-                if world > 1:
-                    raise RuntimeError("measured at N = 1 only")
-                ref_logits = logits.clone()
-                ctx.cnn_t(feat, nu, logits=ref_logits, softmax=soft, argmax=am)
-                t_c = time.perf_counter()
-                how = ctx.net_specialize()
-                t_c = time.perf_counter() - t_c
-                o_ms, _ = timed_region(net_step, 20, 3, 1 if world == 1 else world)
-                torch.cuda.synchronize()
-                kws["general_net_kernel"]["own_kernel"] = dict(
-                    value=round(world * nu / (o_ms * 1e-3), 1), unit="inputs/s", ms_per_step=round(o_ms, 4),
-                    how={1: "compiled by a hipcc child process", 2: "code object from the on-disk cache", 3: "compiled by hipRTC in this process"}[how],
-                    specialize_s=round(t_c, 2), logits_equal_hand_written_kernel=bool(torch.equal(logits, ref_logits)),
-                    what="ed_net_mfma_spec: ed_net_mfma_kernel's source with this graph's plan as constants (edison_net_specialize)")
-            except Exception as e:  # no compiler on this machine: the graph stays on the general kernel
-                kws["general_net_kernel"]["own_kernel"] = dict(value=None, error=str(e)[:200])
-        finally:
-            del os.environ["EDISON_NET_FORCE_GENERAL"]
-        if not args.skip_q15:
-            # the same utterances with the firmware's own features (variant C): what the board would answer, at GPU speed
-            def kws_q15_step(i):
-                ctx.kws_t(audio, nu, 31 * 1024, feat=feat, logits=logits, softmax=soft, argmax=am, q15=True)
-                if gather is not None:
-                    gather(logits)
-            qsteps = max(5, args.steps // 5)
-            kq_ms, _ = timed_region(kws_q15_step, qsteps, min(args.warmup, 3), world)
-            kws["q15_features"] = dict(value=round(world * nu / (kq_ms * 1e-3), 1), unit="inferences/s", steps=qsteps,
-                                       ms_per_step=round(kq_ms, 4),
-                                       class_histogram=torch.bincount(am.to(torch.int64), minlength=10).tolist())
+                def net_step(i):
+                    ctx.net_t(feat, nu, logits=logits, argmax=am)
+                g_ms, _ = timed_region(net_step, 10, 2, 1 if world == 1 else world)
+                kws["general_net_kernel"] = dict(value=round(world * nu / (g_ms * 1e-3), 1), unit="inputs/s", ms_per_step=round(g_ms, 4),
+                                                 what="kws_conv graph forced onto ed_net_mfma_kernel (edison_net_batch_dev, EDISON_NET_FORCE_GENERAL=1)")
+                # ... and through the graph's OWN kernel: the same source compiled at run time with this graph's plan as constants
+                # (edison_net_specialize); checked bit for bit against the hand-written kernel's logits of the same features
+                # (N = 1 only: a per-GPU kernel figure, and a compiler that fails on ONE rank must not leave the others in a barrier)
+                try:
+                    if world > 1:
+                        raise RuntimeError("measured at N = 1 only")
+                    ref_logits = logits.clone()
+                    ctx.cnn_t(feat, nu, logits=ref_logits, softmax=soft, argmax=am)
+                    t_c = time.perf_counter()
+                    how = ctx.net_specialize()
+                    t_c = time.perf_counter() - t_c
+                    o_ms, _ = timed_region(net_step, 20, 3, 1 if world == 1 else world)
+                    torch.cuda.synchronize()
+                    kws["general_net_kernel"]["own_kernel"] = dict(
+                        value=round(world * nu / (o_ms * 1e-3), 1), unit="inputs/s", ms_per_step=round(o_ms, 4),
+                        how={1: "compiled by a hipcc child process", 2: "code object from the on-disk cache", 3: "compiled by hipRTC in this process"}[how],
+                        specialize_s=round(t_c, 2), logits_equal_hand_written_kernel=bool(torch.equal(logits, ref_logits)),
+                        what="ed_net_mfma_spec: ed_net_mfma_kernel's source with this graph's plan as constants (edison_net_specialize)")
+                except Exception as e:  # no compiler on this machine: the graph stays on the general kernel
+                    kws["general_net_kernel"]["own_kernel"] = dict(value=None, error=str(e)[:200])
+            finally:
+                del os.environ["EDISON_NET_FORCE_GENERAL"]
+            if not args.skip_q15:
+                # the same utterances with the firmware's own features (variant C): what the board would answer, at GPU speed
+                def kws_q15_step(i):
+                    ctx.kws_t(audio, nu, 31 * 1024, feat=feat, logits=logits, softmax=soft, argmax=am, q15=True)
+                    if gather is not None:
+                        gather(logits)
+                qsteps = max(5, args.steps // 5)
+                kq_ms, _ = timed_region(kws_q15_step, qsteps, min(args.warmup, 3), world)
+                kws["q15_features"] = dict(value=round(world * nu / (kq_ms * 1e-3), 1), unit="inferences/s", steps=qsteps,
+                                           ms_per_step=round(kq_ms, 4),
+                                           class_histogram=torch.bincount(am.to(torch.int64), minlength=10).tolist())
         if world == 1:
             del audio
 
     # ------------------------------------------------------------------ streaming (configs[4]): rank 0, N = 1 only
     streaming = c_pipeline = None
-    if rank == 0 and world == 1 and not args.skip_stream:
+    if rank == 0 and world == 1 and args.full and not args.skip_stream:
         streaming = stream_bench(ctx, dev)
         c_pipeline = _c_host_pipeline()
 
     # ------------------------------------------------------------------ CPU baseline (rank 0, N = 1 only)
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.skip_cpu:
+    if rank == 0 and world == 1 and args.full and not args.skip_cpu:
         try:
             cpu = cpu_baseline()
         except Exception as e:  # the baseline is a report, never a reason to lose the GPU numbers
@@ -1180,8 +1194,9 @@ def main():
             line["batch_list"] = batch_list
         if two_queues is not None:
             line["two_queues"] = two_queues
-        line["mfcc_variant_a"] = variant_a
-        line["mfcc_variant_tf"] = variant_tf
+        if variant_a is not None:
+            line["mfcc_variant_a"] = variant_a
+            line["mfcc_variant_tf"] = variant_tf
         if variant_d is not None:
             line["mfcc_variant_d"] = variant_d
         if q15 is not None:
