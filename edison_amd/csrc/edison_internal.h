@@ -20,6 +20,14 @@ extern "C" {
 /* Which spectrum index a lane ends up with: lane l holds Z[ED_K0(l) + 64 r] in register r after the last pass (natural
  * order: the FFT's second digit transpose goes through LDS; an all-register FFT would leave a digit-reversed order). */
 #define ED_K0(l) (l)
+/* Wave-private LDS of the fast kernel (ed_mfcc2_body, mfcc_kernels.hip), in floats from the wave's base; the workgroup's LDS is
+ * ED2_TABLE_FLOATS of tables (dct4 | twp), (NLO + NHI) * 256 of mel weights, then ED2_XBUF_FLOATS per wave. Shared with the
+ * host-side model of the loop's LDS accesses (tables.c). */
+#define ED2_TABLE_FLOATS (2 * 64 * 4 + 4 * 64 * 2)
+#define ED2_T2_STRIDE 65     /* transpose 2: 16-byte slot ED2_T2_STRIDE c + p + 8q, 519 slots = 2076 floats                          */
+#define ED2_S_OFF 1088       /* the interleaved spectra float2[516]: their zero padding (from float 2114) lies beyond the transpose */
+#define ED2_L_OFF 2128       /* the DCT inputs of both frames, 64 floats                                                            */
+#define ED2_XBUF_FLOATS 2208
 
 typedef struct {
 	/* Per-lane register constants, lane-minor so that a wavefront loads each of them with one coalesced read.
@@ -59,6 +67,15 @@ int ed_gen_mel_weight_matrix(int num_mel_bins, int num_spectrogram_bins, double 
 /* Build the device tables of one variant (EDISON_MFCC_A, _B or _TF). */
 int ed_build_mfcc_tables(int variant, double sample_rate, double lower_edge_hertz, double upper_edge_hertz,
                          double mel_mtx_scale, ed_mfcc_tables_t *out, char *err, size_t err_cap);
+
+/* Host-side model of every LDS access of one iteration of the fast kernel's loop (tables.c): one row per instruction group,
+ * passes = LDS-array cycles; extra_passes are the bank conflicts. tests/test_lds_layout.py and tools/lds_account.py read it. */
+#define ED_LDS_ROWS_MAX 16
+typedef struct {
+	const char *name;
+	int32_t kind, instructions, free_passes, extra_passes;
+} ed_lds_row_t;
+int ed_mfcc2_lds_account(const ed_mfcc_tables_t *tab, int t2_stride, int wave, ed_lds_row_t *rows, int max_rows);
 
 /* ------------------------------------------------------------------ MFCC variant C (firmware Q15) tables */
 /* The compact mel matrix (mel_constants.h: melMtxCompact[915] + per-band first bin and count) is spread over the

@@ -67,12 +67,14 @@ __global__ ED_MFCC_BOUNDS void ed_mfcc_kernel(ed_mfcc_args_t args, const ed_mfcc
  * stage-dump kernel (the two agree to the last places -- the compiler fuses multiply-adds differently in the two texts --
  * and are held to the oracle with the same bars; the two-frame instances among themselves are bit-identical:
  * plain / grouped / list, aligned or not, one queue or two).
- * LDS per wave: 526 transpose slots of 16 B (re A, re B, im A, im B: register pairs stay pairs), the two spectra interleaved as float2[516]
- * behind them (aliased like above), the DCT inputs of both frames.
+ * LDS per wave: 519 transpose slots of 16 B (re A, re B, im A, im B: register pairs stay pairs), the two spectra interleaved as float2[516]
+ * behind them (aliased like above), the DCT inputs of both frames. The layout constants (ED2_T2_STRIDE, ED2_S_OFF, ED2_L_OFF,
+ * ED2_XBUF_FLOATS) are in edison_internal.h: the host-side model of this loop's LDS accesses (tables.c, ed_mfcc2_lds_account)
+ * works from the same values.
  */
-#define ED2_S_OFF 1088    /* float offset of the interleaved spectra: their zero padding lies beyond the 2104 transpose floats */
-#define ED2_L_OFF 2128
-#define ED2_XBUF_FLOATS 2208
+static_assert(ED2_TABLE_FLOATS == ED_FIXTAB_FLOATS, "the LDS model's table size is the kernel's");
+static_assert(4 * (ED2_T2_STRIDE * 7 + 64) <= ED2_S_OFF + 2 * 513 && ED2_S_OFF + 2 * 516 <= ED2_L_OFF && ED2_L_OFF + 64 <= ED2_XBUF_FLOATS,
+              "the transpose slots end in front of the spectra's zero padding, the spectra in front of the DCT inputs, those inside the wave's buffer");
 
 /* ---- what a lab build may change (tools/lab/mkvariant.py defines ED_LAB; the product build must not: tests/test_host_cpu.py
  * preprocesses this file as edison_amd/build.py compiles it and checks every value below). Everything that was measured and
@@ -377,15 +379,18 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 		}
 		ED2_ST(3)
 		/* transpose 2 through LDS, both frames in one 16-byte slot: (lane 8p+c, reg q) -> (lane p+8q, reg c); slot
-		 * 66c + p + 8q keeps the ds_write_b128 (8-lane groups, stride 66 slots = 8 banks mod 64) and the ds_read_b128
-		 * (consecutive slots) free of bank conflicts */
+		 * ED2_T2_STRIDE c + p + 8q. A ds_write_b128 is served in groups of 8 contiguous lanes (one p, c = 0..7) over 32
+		 * banks = 8 slots: the stride must be odd for the eight c to fall on eight slots mod 8 (65: c + p). With 66 the
+		 * lanes c and c + 4 met on one bank and every store took two passes per group, 64 LDS cycles per pair
+		 * (tables.c ed_mfcc2_lds_account, profiles/r06_mfcc_lds_account.txt). The ds_read_b128 reads consecutive slots
+		 * and is conflict-free at any stride. */
 #pragma unroll
-		for (int q = 0; q < 8; q++) xc4[66 * lo3 + hi3 + 8 * q] = make_float4(re[q].x, re[q].y, im[q].x, im[q].y); /* pairs stay pairs */
+		for (int q = 0; q < 8; q++) xc4[ED2_T2_STRIDE * lo3 + hi3 + 8 * q] = make_float4(re[q].x, re[q].y, im[q].x, im[q].y); /* pairs stay pairs */
 		ed_wave_sync();
 #pragma unroll
 		for (int c = 0; c < 8; c++)
 		{
-			const float4 v = xc4[66 * c + lane];
+			const float4 v = xc4[ED2_T2_STRIDE * c + lane];
 			re[c] = ed_mk2(v.x, v.y); im[c] = ed_mk2(v.z, v.w);
 		}
 		ed_wave_sync();
