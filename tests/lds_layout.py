@@ -20,8 +20,9 @@ def layout_constants():
     return out
 
 
-def build_tables(lib, variant, wide):
-    """(slo4, shi4, band, half, w4[nlo + nhi][64][4] as uint32 bit patterns, nlo, nhi) of one variant and table shape"""
+def build_tables(lib, variant, wide, sample_rate=16000.0, lower_edge_hertz=80.0, upper_edge_hertz=7600.0):
+    """(slo4, shi4, band, half, w4[nlo + nhi][64][4] as uint32 bit patterns, nlo, nhi) of one variant and table shape (wide: the 3+6
+    shape forced; a filterbank that needs it gets it either way), for the shipped filterbank or the one given"""
     lib.ed_build_mfcc_tables.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                          ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
     buf, err = (ctypes.c_char * 65536)(), ctypes.create_string_buffer(256)
@@ -29,7 +30,7 @@ def build_tables(lib, variant, wide):
     if wide:
         os.environ["EDISON_FORCE_WIDE_MEL"] = "1"
     try:
-        assert lib.ed_build_mfcc_tables(variant, 16000.0, 80.0, 7600.0, 128.0, buf, err, 256) == 0, err.value
+        assert lib.ed_build_mfcc_tables(variant, float(sample_rate), float(lower_edge_hertz), float(upper_edge_hertz), 128.0, buf, err, 256) == 0, err.value
     finally:
         os.environ.pop("EDISON_FORCE_WIDE_MEL", None)
         if old is not None:
