@@ -117,7 +117,7 @@ int oracle_f32_mfcc_tables_get(const oracle_f32_mfcc_t *m, float *dct, int32_t *
 	int pos = 0;
 	for (int b = 0; b < F32_NUM_FBANK; b++)
 	{
-		const int n = m->last[b] - m->first[b] + 1;
+		const int n = m->first[b] >= 0 ? m->last[b] - m->first[b] + 1 : 0; /* a band without a bin has no weights */
 		if (first) first[b] = m->first[b];
 		if (last) last[b] = m->last[b];
 		if (weights)
@@ -128,6 +128,14 @@ int oracle_f32_mfcc_tables_get(const oracle_f32_mfcc_t *m, float *dct, int32_t *
 		pos += n;
 	}
 	return pos;
+}
+
+/* the Hann window as mfcc_create holds it (mfcc.c:66-68): frame_len floats; returns their count */
+int oracle_f32_mfcc_window_get(const oracle_f32_mfcc_t *m, float *window, int cap)
+{
+	if (!m || !window || cap < m->frame_len) return -1;
+	memcpy(window, m->window, sizeof(float) * (size_t)m->frame_len);
+	return m->frame_len;
 }
 
 /* radix-2 FFT in double, natural order in/out */

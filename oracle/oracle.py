@@ -105,6 +105,8 @@ def port():
         L.oracle_f32_mfcc_n_out.argtypes = [ctypes.c_void_p]
         L.oracle_f32_mfcc_tables_get.restype = ctypes.c_int
         L.oracle_f32_mfcc_tables_get.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int]
+        L.oracle_f32_mfcc_window_get.restype = ctypes.c_int
+        L.oracle_f32_mfcc_window_get.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         L.oracle_f32_mfcc_run.restype = ctypes.c_int
         L.oracle_f32_mfcc_run.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
@@ -525,6 +527,12 @@ class MfccF32:
         n = port().oracle_f32_mfcc_tables_get(self.h, _p(dct), _p(first), _p(last), _p(w), w.size)
         assert n >= 0
         return dct, first, last, w[:n].copy()
+
+    def window(self):
+        """The Hann window as mfcc_create holds it: [frame_len] f32."""
+        w = np.zeros(self.frame_len, np.float32)
+        assert port().oracle_f32_mfcc_window_get(self.h, _p(w), w.size) == self.frame_len
+        return w
 
     def __del__(self):
         if getattr(self, "h", None):

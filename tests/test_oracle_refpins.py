@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import refpins
+from f32_sweep import F32Tables as _F32Tables     # ed_f32_tables_t, shared with tests/test_f32_sweep_cpu.py
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -156,15 +157,6 @@ def test_variant_d_dct_matrix_equals_the_reference(built_lib, oracle_mod, f32ref
     for nf in (13, 26, 1):
         dct, _, _, _ = oracle_mod.MfccF32(num_mfcc_features=nf, feature_offset=0).tables()
         assert np.array_equal(dct.view(np.uint32), _dct(f32ref, 26, nf).view(np.uint32))
-
-
-class _F32Tables(ctypes.Structure):
-    """ed_f32_tables_t (edison_amd/csrc/edison_internal.h)"""
-    _fields_ = [("n_features", ctypes.c_int32), ("offset", ctypes.c_int32), ("frame_len", ctypes.c_int32), ("padded", ctypes.c_int32),
-                ("log2p", ctypes.c_int32), ("dec_bits", ctypes.c_int32), ("preempha", ctypes.c_float), ("scale", ctypes.c_float),
-                ("window", ctypes.c_float * 1024), ("tw", ctypes.c_float * 1024),
-                ("mel_first", ctypes.c_int32 * 26), ("mel_last", ctypes.c_int32 * 26), ("mel_off", ctypes.c_int32 * 26),
-                ("mel_w", ctypes.c_float * 1100), ("dct", ctypes.c_float * (26 * 26))]
 
 
 def test_variant_d_mel_filterbank_equals_the_reference(built_lib, oracle_mod, f32ref):
