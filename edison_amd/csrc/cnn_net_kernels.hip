@@ -10,6 +10,10 @@
  *            on their portable branches), ReLU = arm_relu_q7 as a tail activation (nnom.c:986-989)
  *   MaxPool  maximum over the part of the window inside the image, starting from -129 (nnom_local.c:117-159,
  *            arm_pool_q7_HWC.c portable branch)
+ *   DW_Conv2D the Conv2D formula per channel, weights [ky][kx][ch], depth multiplier 1
+ *            (arm_depthwise_separable_conv_HWC_q7_nonsquare.c:376-401, portable branch)
+ *   AvgPool  (sum over the taps inside the image) / (their number), C division truncating toward zero (nnom_local.c:45-67,
+ *            arm_pool_q7_HWC.c:424-446; which window a square map gets: model_net.c)
  *   Dense    the same requantisation over the flattened HWC input (arm_fully_connected_q7_opt.c:374-473; the
  *            importer undoes the weight interleave)
  *   Softmax  arm_softmax_q7.c:215-260, portable branch; argmax = first maximum of the last layer (nnom_utils.c:275-284)
@@ -176,6 +180,60 @@ __device__ __forceinline__ void en_pool(const ed_net_layer_t &L, const int8_t *i
 	}
 }
 
+/* Depthwise convolution: a thread owns two neighbouring channels of an output pixel (the channel count is even: model_net.c), read
+ * as one 16-bit word per tap from the activations and from the [ky][kx][ch] weights; consecutive lanes take consecutive pairs. */
+__device__ __forceinline__ void en_dwconv(const ed_net_layer_t &L, const int8_t *in, int8_t *out, const int8_t *__restrict__ W,
+                                          const int32_t *__restrict__ S)
+{
+	const int c2n = L.in_c >> 1;
+	for (int idx = threadIdx.x; idx < (L.out_n >> 1); idx += EN_THREADS)
+	{
+		const int pix = idx / c2n, c = 2 * (idx - pix * c2n);
+		const int y = pix / L.out_w, x = pix - y * L.out_w;
+		int a0 = S[L.seed_off + c], a1 = S[L.seed_off + c + 1];
+		for (int ky = 0; ky < L.kh; ky++)
+		{
+			const int iy = y * L.sh - L.pad_h + ky;
+			if ((unsigned)iy >= (unsigned)L.in_h) continue;
+			for (int kx = 0; kx < L.kw; kx++)
+			{
+				const int ix = x * L.sw - L.pad_w + kx;
+				if ((unsigned)ix >= (unsigned)L.in_w) continue;
+				const int v = *reinterpret_cast<const short *>(in + (iy * L.in_w + ix) * L.in_c + c);
+				const int w = *reinterpret_cast<const short *>(W + L.w_off + (ky * L.kw + kx) * L.in_c + c);
+				a0 += (int)(int8_t)v * (int)(int8_t)w;
+				a1 += (v >> 8) * (w >> 8);
+			}
+		}
+		int r0 = en_ssat8(a0 >> L.rs), r1 = en_ssat8(a1 >> L.rs);
+		if (L.relu) { r0 = r0 < 0 ? 0 : r0; r1 = r1 < 0 ? 0 : r1; }
+		*reinterpret_cast<unsigned short *>(out + 2 * idx) = (unsigned short)((r0 & 0xff) | ((r1 & 0xff) << 8));
+	}
+}
+
+__device__ __forceinline__ void en_avgpool(const ed_net_layer_t &L, const int8_t *in, int8_t *out)
+{
+	for (int idx = threadIdx.x; idx < L.out_n; idx += EN_THREADS)
+	{
+		const int pix = idx / L.in_c, c = idx - pix * L.in_c;
+		const int y = pix / L.out_w, x = pix - y * L.out_w;
+		int sum = 0, count = 0;
+		for (int ky = 0; ky < L.kh; ky++)
+		{
+			const int iy = y * L.sh - L.pad_h + ky;
+			if ((unsigned)iy >= (unsigned)L.in_h) continue;
+			for (int kx = 0; kx < L.kw; kx++)
+			{
+				const int ix = x * L.sw - L.pad_w + kx;
+				if ((unsigned)ix >= (unsigned)L.in_w) continue;
+				sum += in[(iy * L.in_w + ix) * L.in_c + c];
+				count++;
+			}
+		}
+		out[idx] = (int8_t)(sum / (count > 0 ? count : 1)); /* C division: toward zero; a window always holds a tap (model_net.c) */
+	}
+}
+
 /* one wavefront per output unit, the input vector split over its lanes; integer sums are exact in any order */
 __device__ __forceinline__ void en_dense(const ed_net_layer_t &L, const int8_t *in, int8_t *out, const int8_t *__restrict__ W,
                                          const int32_t *__restrict__ S)
@@ -245,6 +303,8 @@ __global__ __launch_bounds__(EN_THREADS) void ed_net_kernel(const ed_net_plan_t 
 				else { if (padded) en_conv<false, true>(L, a, o, W, S); else en_conv<false, false>(L, a, o, W, S); }
 			}
 			else if (L.type == ED_NET_POOL) en_pool(L, a, o);
+			else if (L.type == ED_NET_DWCONV) en_dwconv(L, a, o, W, S);
+			else if (L.type == ED_NET_AVGPOOL) en_avgpool(L, a, o);
 			else if (L.type == ED_NET_DENSE) en_dense(L, a, o, W, S);
 			else en_softmax(L, a, o);
 			__syncthreads();

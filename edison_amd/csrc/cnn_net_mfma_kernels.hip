@@ -4,7 +4,8 @@
  * layer-by-layer kernel of cnn_net_kernels.hip stays for per-layer dumps and for graphs whose plan does not fit here.
  *
  * Arithmetic: exactly the reference's -- out = sat8((sum x*w + (bias << BL) + NN_ROUND(RS)) >> RS), ReLU as a tail
- * activation, max-pool over the part of the window inside the image, arm_softmax_q7's portable branch, first-maximum
+ * activation, max-pool over the part of the window inside the image, DW_Conv2D and AvgPool on the VALU between the matrix-core
+ * layers (ED_RUN_DW / ED_RUN_AVG below), arm_softmax_q7's portable branch, first-maximum
  * argmax (citations in cnn_net_kernels.hip); integer sums are exact in any order, so the results are bit-identical.
  *
  * Scheme (ed_mm_plan_t, model_net_mm.c): implicit GEMM D[out_channel][pixel] with k = (kernel row, 16-byte chunk of the
@@ -256,6 +257,22 @@ __device__ __forceinline__ uint32_t emm_image_dword(uint32_t raw, int in_n, int 
 	const int e = 4 * lane + 256 * k;
 	const int at = e + 4 <= in_n ? e : in_n - 4, sh = 8 * (e - at);
 	return sh < 32 ? raw >> sh : 0u; /* e - at >= 4: nothing of this lane's four bytes lies inside the image */
+}
+
+/* Four neighbouring channels of a pixel as one dword: an aligned ds_read_b32 when C % 4 == 0; otherwise C is even (model_net.c), the
+ * group starts on a 16-bit boundary and comes as two ds_read_u16 -- one when only two channels are left (`tail`), the rest zero. */
+__device__ __forceinline__ uint32_t emm_ld_c4(const lds8 *p, bool al4, bool tail)
+{
+	if (al4) return (uint32_t)EMM_LD32(p);
+	const uint32_t lo = *reinterpret_cast<const EMM_LDS uint16_t *>(p);
+	const uint32_t hi = tail ? 0u : *reinterpret_cast<const EMM_LDS uint16_t *>(p + 2);
+	return lo | (hi << 16);
+}
+__device__ __forceinline__ void emm_st_c4(lds8 *p, uint32_t v, bool al4, bool tail)
+{
+	if (al4) { EMM_ST32(p, v); return; }
+	*reinterpret_cast<EMM_LDS uint16_t *>(p) = (uint16_t)v;
+	if (!tail) *reinterpret_cast<EMM_LDS uint16_t *>(p + 2) = (uint16_t)(v >> 16);
 }
 
 struct emm_layout { int hp, wp, py, px, img; }; /* how an activation tensor lies in LDS: padded dims, origin, bytes per image */
@@ -1068,6 +1085,78 @@ __device__ __forceinline__ void emm_net_body(const ed_net_plan_t *__restrict__ P
 						}
 					}
 					o[b * R.o_img + R.o_origin + y * R.o_row + x * R.oc_pitch + c] = (int8_t)mx;
+				}
+			}
+			else if (R.kind == ED_RUN_DW)
+			{
+				/* DW_Conv2D (arm_depthwise_separable_conv_HWC_q7_nonsquare.c:376-401): a lane owns four neighbouring channels of one output
+				 * pixel; consecutive lanes take consecutive groups, then consecutive pixels. Per tap inside the image: one dword of
+				 * activations (the compact HWC image: consecutive lanes read consecutive dwords) and one dword of weights ([tap][group],
+				 * packed by the planner: lanes of one pixel read consecutive dwords, lanes of other pixels the same ones -- broadcast),
+				 * four multiply-adds into int32 accumulators that start as the seeds; then the epilogue's emm_pack4. */
+				const ed_net_layer_t L = EMM_NETL(li);
+				const int c4n = (L.in_c + 3) >> 2, per_img = L.out_h * L.out_w * c4n;
+				const bool al4 = (L.in_c & 3) == 0;
+				const float inv_img = __builtin_amdgcn_rcpf((float)per_img), inv_c4 = __builtin_amdgcn_rcpf((float)c4n), inv_ow = __builtin_amdgcn_rcpf((float)L.out_w);
+				const lds8 *sd = reinterpret_cast<const lds8 *>(seeds_l + R.seed_off);
+				const lds8 *wl = fragl + R.frag_off;
+				const int8_t *wg = frag + R.frag_off;
+				for (int i = lane_l; i < nb * per_img; i += 64)
+				{
+					int b, e, pix, c4, y, x;
+					emm_divmod(i, per_img, inv_img, b, e); emm_divmod(e, c4n, inv_c4, pix, c4); emm_divmod(pix, L.out_w, inv_ow, y, x);
+					const bool tail = !al4 && c4 == c4n - 1;
+					const v4i s4 = EMM_LD128(sd + 16 * c4);
+					int a0 = s4.x, a1 = s4.y, a2 = s4.z, a3 = s4.w;
+					for (int ky = 0; ky < L.kh; ky++)
+					{
+						const int iy = y * L.sh - L.pad_h + ky;
+						if ((unsigned)iy >= (unsigned)L.in_h) continue;
+						for (int kx = 0; kx < L.kw; kx++)
+						{
+							const int ix = x * L.sw - L.pad_w + kx;
+							if ((unsigned)ix >= (unsigned)L.in_w) continue;
+							const int v = (int)emm_ld_c4(a + b * R.in_img + (iy * L.in_w + ix) * L.in_c + 4 * c4, al4, tail);
+							const int wo = 4 * ((ky * L.kw + kx) * c4n + c4);
+							const int w = FRAG_LDS ? EMM_LD32(wl + wo) : *reinterpret_cast<const int *>(wg + wo);
+							a0 += (int)(int8_t)v * (int)(int8_t)w; a1 += (int)(int8_t)(v >> 8) * (int)(int8_t)(w >> 8);
+							a2 += (int)(int8_t)(v >> 16) * (int)(int8_t)(w >> 16); a3 += (v >> 24) * (w >> 24);
+						}
+					}
+					emm_st_c4(o + b * R.o_img + R.o_origin + y * R.o_row + x * R.oc_pitch + 4 * c4,
+					          emm_pack4(a0, a1, a2, a3, R.rs & ED_RUN_RS_MASK, R.lo_clamp), al4, tail);
+				}
+			}
+			else if (R.kind == ED_RUN_AVG)
+			{
+				/* AvgPool: four channels per lane as above; sum over the taps inside the image, C division by their number (toward zero:
+				 * nnom_local.c:64, arm_pool_q7_HWC.c:443; the window of a square map: model_net.c) */
+				const ed_net_layer_t L = EMM_NETL(li);
+				const int c4n = (L.in_c + 3) >> 2, per_img = L.out_h * L.out_w * c4n;
+				const bool al4 = (L.in_c & 3) == 0;
+				const float inv_img = __builtin_amdgcn_rcpf((float)per_img), inv_c4 = __builtin_amdgcn_rcpf((float)c4n), inv_ow = __builtin_amdgcn_rcpf((float)L.out_w);
+				for (int i = lane_l; i < nb * per_img; i += 64)
+				{
+					int b, e, pix, c4, y, x;
+					emm_divmod(i, per_img, inv_img, b, e); emm_divmod(e, c4n, inv_c4, pix, c4); emm_divmod(pix, L.out_w, inv_ow, y, x);
+					const bool tail = !al4 && c4 == c4n - 1;
+					int s0 = 0, s1 = 0, s2 = 0, s3 = 0, count = 0;
+					for (int ky = 0; ky < L.kh; ky++)
+					{
+						const int iy = y * L.sh - L.pad_h + ky;
+						if ((unsigned)iy >= (unsigned)L.in_h) continue;
+						for (int kx = 0; kx < L.kw; kx++)
+						{
+							const int ix = x * L.sw - L.pad_w + kx;
+							if ((unsigned)ix >= (unsigned)L.in_w) continue;
+							const int v = (int)emm_ld_c4(a + b * R.in_img + (iy * L.in_w + ix) * L.in_c + 4 * c4, al4, tail);
+							s0 += (int)(int8_t)v; s1 += (int)(int8_t)(v >> 8); s2 += (int)(int8_t)(v >> 16); s3 += v >> 24;
+							count++;
+						}
+					}
+					count = count > 0 ? count : 1; /* never 0 for a graph the planner accepted */
+					const uint32_t q = (uint32_t)(uint8_t)(s0 / count) | ((uint32_t)(uint8_t)(s1 / count) << 8) | ((uint32_t)(uint8_t)(s2 / count) << 16) | ((uint32_t)(uint8_t)(s3 / count) << 24);
+					emm_st_c4(o + b * R.o_img + R.o_origin + y * R.o_row + x * R.oc_pitch + 4 * c4, q, al4, tail);
 				}
 			}
 			else /* softmax: arm_softmax_q7.c:215-260 */

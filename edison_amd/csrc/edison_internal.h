@@ -234,11 +234,11 @@ int ed_parse_model(const void *blob, size_t blob_bytes, ed_cnn_model_t *out, ed_
 
 /* ------------------------------------------------------------------ any sequential NNoM int8 graph (cnn_net_kernels.hip)
  * The plan of the layer-by-layer kernel: what model_compile() (nnom.c:758-900) works out for the chain
- * Input -> {Conv2D [+ReLU] | MaxPool | Dense [+ReLU] | Flatten | Softmax}* -> Output. One workgroup owns an
+ * Input -> {Conv2D [+ReLU] | DW_Conv2D [+ReLU] | MaxPool | AvgPool | Dense [+ReLU] | Flatten | Softmax}* -> Output. One workgroup owns an
  * utterance; activations ping-pong between two LDS buffers; weights stay OHWI int8 in HBM/L2. */
 #define ED_NET_MAX_LAYERS 32
 #define ED_NET_MAX_LDS (64 * 1024 - 256) /* both activation buffers */
-enum { ED_NET_CONV = 1, ED_NET_POOL = 2, ED_NET_DENSE = 3, ED_NET_SOFTMAX = 4 };
+enum { ED_NET_CONV = 1, ED_NET_POOL = 2, ED_NET_DENSE = 3, ED_NET_SOFTMAX = 4, ED_NET_DWCONV = 5, ED_NET_AVGPOOL = 6 };
 
 typedef struct {
 	int32_t type, relu;
@@ -319,7 +319,10 @@ typedef struct {
 /* What one pass of the kernel's layer loop needs, worked out on the host: one 128-byte record per layer that the wave
  * reads with two scalar loads (the kernel used to derive it from ed_net_layer_t + ed_mm_layer_t + the consumer's record:
  * a chain of dependent scalar loads and ~100 scalar instructions per layer and input). */
-enum { ED_RUN_SKIP = 0, ED_RUN_MM = 1, ED_RUN_POOL4 = 2, ED_RUN_POOL1 = 3, ED_RUN_SOFTMAX = 4 };
+/* ED_RUN_DW / ED_RUN_AVG: DW_Conv2D and AvgPool on the VALU between the matrix-core layers, four channels per lane: they
+ * read a compact image like the MaxPool passes and store into the consumer's layout; a DW_Conv2D keeps its weights ([tap][group of
+ * four channels] dwords, zero beyond C) at frag_off of the fragment buffer and its seeds (a multiple of four) at seed_off */
+enum { ED_RUN_SKIP = 0, ED_RUN_MM = 1, ED_RUN_POOL4 = 2, ED_RUN_POOL1 = 3, ED_RUN_SOFTMAX = 4, ED_RUN_DW = 5, ED_RUN_AVG = 6 };
 /* ed_mm_run_t.rs: the planner found that sat8(v >> rs) may be taken as the high byte of sat16(v >> (rs - 8)) -- always for
  * rs >= 8, for rs < 8 when no accumulator of the layer can leave 32 bits under the left shift (model_net_mm.c) */
 #define ED_RUN_RS_MASK 0xff

@@ -362,6 +362,11 @@ static int specialize(edison_ctx *ctx, int cache_only)
 	if (!ctx->have_model) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_net_specialize: no model loaded");
 	if (!ctx->mm_ok || !ctx->h_mm_plan)
 		return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_net_specialize: this graph has no matrix-core plan (it runs on the layer-by-layer kernel)");
+	/* a graph with a DW_Conv2D or an AvgPool keeps the general kernel: its VALU layers gain nothing from constants, and the own kernel's
+	 * register budget is tuned for matrix-core layers only */
+	for (int i = 0; i < ctx->net.n_layers; i++)
+		if (ctx->net.L[i].type == ED_NET_DWCONV || ctx->net.L[i].type == ED_NET_AVGPOOL)
+			return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_net_specialize: a graph with DW_Conv2D or AvgPool layers is not specialised (it stays on the general kernel)");
 	if (ctx->spec_fn && ctx->spec_epoch == ctx->model_epoch) return EDISON_OK; /* already done for this load */
 	ED_HIP(ctx, hipSetDevice(ctx->device));
 	ED_HIP(ctx, hipDeviceSynchronize()); /* launches of the previous load's kernel may still be in flight */

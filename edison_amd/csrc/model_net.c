@@ -1,6 +1,6 @@
 /*
  * model_net.c -- host-side (plain C) planner for ANY sequential NNoM int8 graph the importer understands
- * (tools/import_weights_h.py): Input -> {Conv2D [+ReLU] | MaxPool | Dense [+ReLU] | Softmax}* -> Output.
+ * (tools/import_weights_h.py): Input -> {Conv2D [+ReLU] | DW_Conv2D [+ReLU] | MaxPool | AvgPool | Dense [+ReLU] | Softmax}* -> Output.
  *
  * It does for the GPU what model_compile() + the layers' build functions do in the reference (nnom.c:758-900,
  * nnom_conv2d.c:79-108, nnom_maxpool.c:80-106, nnom_dense.c:70-91): derive every tensor shape, decide where the
@@ -12,8 +12,12 @@
  * differently from the reference:
  *   - square images go to the CMSIS-NN "square" kernels, which are handed kernel.w / stride.w / pad.w only
  *     (nnom_conv2d.c:146-153,177-184, nnom_maxpool.c:124-134) and index with `signed char` (arm_convolve_HWC_q7_basic.c);
+ *   - DW_Conv2D with a depth multiplier other than 1 or an odd channel count returns NN_ARGUMENT_ERROR (nnom_dw_conv2d.c:88-89);
  *   - a 1x1 convolution with C_in % 4 == 0, C_out % 2 == 0 and a stride other than 1 makes
  *     arm_convolve_1x1_HWC_q7_fast_nonsquare return ARM_MATH_SIZE_MISMATCH (:204-209).
+ * One quirk of that dispatch IS restated, because a DS-CNN's pools meet it: an AvgPool whose input and output are both square goes
+ * to arm_avepool_q7_HWC with kernel.w / pad.w / stride.w only (nnom_avgpool.c:76-86), which uses them on both axes; the plan
+ * records that window (every tap is bounds-checked and the rows' windows equal the columns', so none is empty).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -72,7 +76,7 @@ int ed_plan_net(const void *blob, size_t blob_bytes, ed_net_plan_t *plan, int8_t
 		ed_net_layer_t *L = &plan->L[i];
 		L->type = v[0];
 		L->in_h = h; L->in_w = w; L->in_c = c; L->in_n = h * w * c;
-		if (v[0] == ED_NET_CONV || v[0] == ED_NET_POOL)
+		if (v[0] == ED_NET_CONV || v[0] == ED_NET_POOL || v[0] == ED_NET_DWCONV || v[0] == ED_NET_AVGPOOL)
 		{
 			const int same = (v[8] >> 1) & 1;
 			L->kh = v[2]; L->kw = v[3]; L->sh = v[4]; L->sw = v[5];
@@ -84,6 +88,8 @@ int ed_plan_net(const void *blob, size_t blob_bytes, ed_net_plan_t *plan, int8_t
 			L->out_w = same ? ceil_div(w, L->sw) : ceil_div(w - L->kw + 1, L->sw);
 			if (L->out_h < 1 || L->out_w < 1)
 			{ rc = fail(err, err_cap, EDISON_E_SIZE, "layer %d: kernel larger than its %d-row input", i, h); break; }
+			if (v[0] == ED_NET_AVGPOOL && h == w && L->out_h == L->out_w)
+			{ L->kh = L->kw; L->sh = L->sw; L->pad_h = L->pad_w; } /* arm_avepool_q7_HWC: see the head of this file */
 			L->check_taps = L->pad_h > 0 || L->pad_w > 0 || (L->out_h - 1) * L->sh - L->pad_h + L->kh > h ||
 			                (L->out_w - 1) * L->sw - L->pad_w + L->kw > w;
 			const int square_in = h == w;
@@ -117,6 +123,32 @@ int ed_plan_net(const void *blob, size_t blob_bytes, ed_net_plan_t *plan, int8_t
 				L->seed_off = s_used;
 				for (int o = 0; o < L->out_c; o++)
 					sbuf[s_used++] = (int32_t)((uint32_t)(int32_t)payload[v[10] + o] << v[6]) + (int32_t)((1u << v[7]) >> 1);
+			}
+			else if (v[0] == ED_NET_DWCONV)
+			{
+				/* weights stay [ky][kx][ch] (arm_depthwise_separable_conv_HWC_q7_nonsquare.c:392-393): consecutive lanes read consecutive
+				 * channels of a tap */
+				L->out_c = c; L->relu = v[8] & 1; L->rs = v[7];
+				if (v[1] != c || v[11] != c || (c & 1) || v[6] < 0 || v[6] > 23 || v[7] < 0 || v[7] > 30)
+				{ rc = fail(err, err_cap, EDISON_E_SIZE, "layer %d: DW_Conv2D needs depth multiplier 1, an even channel count and consistent shifts (input has %d channels)", i, c); break; }
+				const int64_t wn = (int64_t)L->kh * L->kw * c;
+				if (v[9] < 0 || v[10] < 0 || v[9] + wn > payload_bytes || (int64_t)v[10] + c > payload_bytes)
+				{ rc = fail(err, err_cap, EDISON_E_SIZE, "layer %d: DW_Conv2D weight tensor outside the payload", i, 0); break; }
+				w_used = (w_used + 15) & ~15;
+				if ((size_t)w_used + (size_t)wn > w_cap || (size_t)s_used + (size_t)c > s_cap)
+				{ rc = fail(err, err_cap, EDISON_E_SIZE, "layer %d: tensors overlap (their sizes exceed the %d-byte payload)", i, payload_bytes); break; }
+				L->w_off = w_used;
+				memcpy(wbuf + w_used, payload + v[9], (size_t)wn);
+				w_used += (int)wn;
+				L->seed_off = s_used;
+				for (int o = 0; o < c; o++)
+					sbuf[s_used++] = (int32_t)((uint32_t)(int32_t)payload[v[10] + o] << v[6]) + (int32_t)((1u << v[7]) >> 1);
+			}
+			else if (v[0] == ED_NET_AVGPOOL)
+			{
+				L->out_c = c;
+				if (v[7] != 0)
+				{ rc = fail(err, err_cap, EDISON_E_NO_IMPL, "layer %d: AvgPool with output_shift %d (only 0 is built)", i, v[7]); break; }
 			}
 			else
 			{

@@ -40,6 +40,16 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 		if (L->type != ED_NET_CONV && L->type != ED_NET_DENSE)
 		{
 			M->in_img = up16(L->in_n) + 16;
+			if (L->type == ED_NET_DWCONV)
+			{
+				/* VALU layer inside the launch (ED_RUN_DW): its weights travel with the fragments, one dword per (tap, group of four
+				 * channels), its seeds with the seeds, four per group (both zero beyond C: a group's spare lanes compute nothing stored) */
+				const int c4n = (L->in_c + 3) / 4;
+				M->frag_off = (int32_t)frag_bytes;
+				frag_bytes += (size_t)up16(4 * c4n * L->kh * L->kw);
+				M->seed_off = n_seeds;
+				n_seeds += 4 * c4n;
+			}
 			continue;
 		}
 		const int dense = L->type == ED_NET_DENSE;
@@ -294,6 +304,12 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 		for (int i = 0; i < n_layers; i++)
 		{
 			ed_mm_layer_t *M = &mm->L[i];
+			if (plan->L[i].type == ED_NET_DWCONV)
+			{
+				M->frag_off = (int32_t)fexact;
+				fexact += (size_t)up16(4 * ((plan->L[i].in_c + 3) / 4) * plan->L[i].kh * plan->L[i].kw);
+				continue;
+			}
 			if (!M->mm) continue;
 			M->frag_off = (int32_t)fexact;
 			fexact += (size_t)(M->small ? M->n_rt16 * M->n_ks16 : M->n_rt * M->n_ks) * 1024;
@@ -322,6 +338,18 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 	{
 		const ed_net_layer_t *L = &plan->L[i];
 		const ed_mm_layer_t *M = &mm->L[i];
+		if (L->type == ED_NET_DWCONV)
+		{
+			rec_t r;
+			memcpy(&r, p + 40 + (size_t)i * 48, sizeof(r));
+			const int c = L->in_c, c4n = (c + 3) / 4;
+			const int8_t *w = payload + r.v[9], *bias = payload + r.v[10]; /* [ky][kx][ch] */
+			for (int t = 0; t < L->kh * L->kw; t++)
+				for (int ch = 0; ch < c; ch++) fb[M->frag_off + (size_t)4 * c4n * t + ch] = w[(size_t)t * c + ch];
+			for (int ch = 0; ch < c; ch++)
+				sb[M->seed_off + ch] = (int32_t)((uint32_t)(int32_t)bias[ch] << r.v[6]) + (int32_t)((1u << r.v[7]) >> 1);
+			continue;
+		}
 		if (!M->mm) continue;
 		rec_t r;
 		memcpy(&r, p + 40 + (size_t)i * 48, sizeof(r));
@@ -458,7 +486,10 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 		/* the run record */
 		ed_mm_run_t *R = &mm->R[i];
 		const int dense = L->type == ED_NET_DENSE;
-		R->kind = M->mm ? ED_RUN_MM : (L->type == ED_NET_POOL ? ((L->in_c & 3) == 0 ? ED_RUN_POOL4 : ED_RUN_POOL1) : ED_RUN_SOFTMAX);
+		R->kind = M->mm ? ED_RUN_MM : L->type == ED_NET_POOL ? ((L->in_c & 3) == 0 ? ED_RUN_POOL4 : ED_RUN_POOL1)
+		          : L->type == ED_NET_DWCONV ? ED_RUN_DW : L->type == ED_NET_AVGPOOL ? ED_RUN_AVG : ED_RUN_SOFTMAX;
+		/* the two VALU layers store 16-bit words (dwords when C % 4 == 0) at the consumer's pixel pitch */
+		if ((R->kind == ED_RUN_DW || R->kind == ED_RUN_AVG) && ((opp & 1) || ((L->in_c & 3) == 0 && (opp & 3)))) { free(fb); free(sb); return EDISON_OK; }
 		R->zero_border = ohp != st_h || owp != st_w;
 		R->in_img = M->in_img; R->o_img = oimg;
 		R->oc_pitch = opp; R->o_origin = (opy * owp + opx) * opp; R->o_row = owp * opp;

@@ -24,13 +24,16 @@ Blob format (little endian):
   int32    payload_bytes
   int32    reserved[3]
   n_layers x int32[12] records:
-     [0] type  1=conv2d  2=maxpool  3=dense  4=softmax
+     [0] type  1=conv2d  2=maxpool  3=dense  4=softmax  5=dw_conv2d  6=avgpool
      conv2d : [1]=out_ch [2]=kh [3]=kw [4]=sh [5]=sw [6]=bias_lshift [7]=out_rshift
               [8]=flags (bit 0 ReLU tail activation, bit 1 PADDING_SAME)   [9]=weight_off [10]=bias_off [11]=in_ch
      maxpool: [2]=kh [3]=kw [4]=sh [5]=sw [8]=flags (bit 1 PADDING_SAME)
      dense  : [1]=out [6]=bias_lshift [7]=out_rshift [8]=flags (bit 0 ReLU) [9]=weight_off [10]=bias_off [11]=in
               (Flatten() is a no-op on HWC memory and leaves no record)
      softmax: -
+     dw_conv2d: as conv2d with [1]=[11]=channels (depth multiplier 1 only: in = out channels); weights stay
+              ``w[ky][kx][ch]`` as arm_depthwise_separable_conv_HWC_q7_nonsquare.c:392-393 indexes them
+     avgpool: as maxpool, and [7]=output_shift (nnom_avgpool.c:70,99; a generated header cannot set it: always 0)
   int8     payload[payload_bytes]   (offsets above index into it)
 
 Usage:  tools/import_weights_h.py /path/to/weights.h edison_amd/data/kws_nnom.ednn
@@ -42,7 +45,10 @@ import sys
 import numpy as np
 
 MAGIC = b"EDNNOM1\0"
-T_CONV, T_POOL, T_DENSE, T_SOFTMAX = 1, 2, 3, 4
+T_CONV, T_POOL, T_DENSE, T_SOFTMAX, T_DWCONV, T_AVGPOOL = 1, 2, 3, 4, 5, 6
+# layers of nnom_layers.h this importer names when it refuses them (the reference runs them, this path does not)
+REFUSED = ("GlobalMaxPool", "GlobalAvgPool", "GlobalSumPool", "SumPool", "ZeroPadding", "Cropping", "UpSample", "Add", "Sub",
+           "Mult", "Concat", "Lambda", "RNN", "Activation", "ReLU", "Sigmoid", "TanH", "BaseLayer")
 
 
 def _eval_int(expr, sym):
@@ -102,11 +108,37 @@ def parse_weights_h(text):
     in_shape = tuple(int(g) for g in m.groups())
 
     layers = []
+    c = in_shape[2]   # channels of the tensor the next layer reads (a depthwise layer's shape depends on it)
     for line in re.findall(r"layer\[\d+\]\s*=\s*(.*);", text):
-        mc = re.search(r"Conv2D\((\d+),\s*kernel\((\d+),\s*(\d+)\),\s*stride\((\d+),\s*(\d+)\),\s*(\w+),\s*&(\w+),\s*&(\w+)\)", line)
-        mp = re.search(r"MaxPool\(kernel\((\d+),\s*(\d+)\),\s*stride\((\d+),\s*(\d+)\),\s*(\w+)\)", line)
-        md = re.search(r"Dense\((\d+),\s*&(\w+),\s*&(\w+)\)", line)
-        if mc:
+        mw = re.search(r"\bDW_Conv2D\((\d+),\s*kernel\((\d+),\s*(\d+)\),\s*stride\((\d+),\s*(\d+)\),\s*(\w+),\s*&(\w+),\s*&(\w+)\)", line)
+        ma = re.search(r"\bAvgPool\(kernel\((\d+),\s*(\d+)\),\s*stride\((\d+),\s*(\d+)\),\s*(\w+)\)", line)
+        refused = re.search(r"\b(%s)\(" % "|".join(REFUSED), line)
+        mc = None if mw else re.search(r"\bConv2D\((\d+),\s*kernel\((\d+),\s*(\d+)\),\s*stride\((\d+),\s*(\d+)\),\s*(\w+),\s*&(\w+),\s*&(\w+)\)", line)
+        mp = re.search(r"\bMaxPool\(kernel\((\d+),\s*(\d+)\),\s*stride\((\d+),\s*(\d+)\),\s*(\w+)\)", line)
+        md = re.search(r"\bDense\((\d+),\s*&(\w+),\s*&(\w+)\)", line)
+        if refused:
+            raise ValueError("unsupported layer %s in weights.h: %s" % (refused.group(1), line))
+        if mw:
+            # nnom_dw_conv2d.c:88-89: with CMSIS-NN the reference returns NN_ARGUMENT_ERROR for these
+            if int(mw.group(1)) != 1:
+                raise ValueError("DW_Conv2D with depth multiplier %s: the reference's CMSIS-NN build runs multiplier 1 only" % mw.group(1))
+            if c % 2:
+                raise ValueError("DW_Conv2D over %d channels: the reference's CMSIS-NN build refuses an odd channel count" % c)
+            if mw.group(6) not in ("PADDING_VALID", "PADDING_SAME"):
+                raise ValueError("DW_Conv2D: unknown padding %s" % mw.group(6))
+            w, rs = tensor(mw.group(7))
+            b, bl = tensor(mw.group(8))
+            kh, kw = int(mw.group(2)), int(mw.group(3))
+            if w.size != kh * kw * c or b.size != c:
+                raise ValueError("DW_Conv2D: %d weights and %d biases for a %dx%d kernel over %d channels" % (w.size, b.size, kh, kw, c))
+            layers.append(dict(type=T_DWCONV, kh=kh, kw=kw, sh=int(mw.group(4)), sw=int(mw.group(5)), w=w, b=b,
+                               out_rshift=rs, bias_lshift=bl, relu=0, same=int(mw.group(6) == "PADDING_SAME")))
+        elif ma:
+            if ma.group(5) not in ("PADDING_VALID", "PADDING_SAME"):
+                raise ValueError("AvgPool: unknown padding %s" % ma.group(5))
+            layers.append(dict(type=T_AVGPOOL, kh=int(ma.group(1)), kw=int(ma.group(2)), sh=int(ma.group(3)), sw=int(ma.group(4)),
+                               same=int(ma.group(5) == "PADDING_SAME"), out_shift=0))
+        elif mc:
             if mc.group(6) not in ("PADDING_VALID", "PADDING_SAME"):
                 raise ValueError("unknown padding %s" % mc.group(6))
             w, rs = tensor(mc.group(7))
@@ -114,9 +146,10 @@ def parse_weights_h(text):
             layers.append(dict(type=T_CONV, out_ch=int(mc.group(1)), kh=int(mc.group(2)), kw=int(mc.group(3)),
                                sh=int(mc.group(4)), sw=int(mc.group(5)), w=w, b=b, out_rshift=rs, bias_lshift=bl,
                                relu=0, same=int(mc.group(6) == "PADDING_SAME")))
+            c = int(mc.group(1))
         elif "act_relu()" in line:
-            if not layers or layers[-1]["type"] not in (T_CONV, T_DENSE):
-                raise ValueError("ReLU tail activation is only supported after Conv2D or Dense")
+            if not layers or layers[-1]["type"] not in (T_CONV, T_DENSE, T_DWCONV):
+                raise ValueError("ReLU tail activation is only supported after Conv2D, DW_Conv2D or Dense")
             layers[-1]["relu"] = 1
         elif mp:
             if mp.group(5) not in ("PADDING_VALID", "PADDING_SAME"):
@@ -127,6 +160,7 @@ def parse_weights_h(text):
             w, rs = tensor(md.group(2))
             b, bl = tensor(md.group(3))
             layers.append(dict(type=T_DENSE, out=int(md.group(1)), w=w, b=b, out_rshift=rs, bias_lshift=bl, relu=0))
+            c = int(md.group(1))
         elif "Softmax()" in line:
             layers.append(dict(type=T_SOFTMAX))
         elif "Input(" in line or "Output(" in line or "Flatten()" in line:
@@ -190,6 +224,21 @@ def build_blob(in_shape, layers):
                         L["relu"] | (L["same"] << 1)]
             rec[9], rec[10], rec[11] = put(L["w"]), put(L["b"]), c
             h, w_, c = out_dim(h, L["kh"], L["sh"], L["same"]), out_dim(w_, L["kw"], L["sw"], L["same"]), L["out_ch"]
+        elif L["type"] == T_DWCONV:
+            if c % 2:
+                raise ValueError("DW_Conv2D over %d channels: the reference's CMSIS-NN build refuses an odd channel count" % c)
+            if L["w"].size != L["kh"] * L["kw"] * c or L["b"].size != c:
+                raise ValueError("DW_Conv2D: %d weights and %d biases for a %dx%d kernel over %d channels"
+                                 % (L["w"].size, L["b"].size, L["kh"], L["kw"], c))
+            rec[1:9] = [c, L["kh"], L["kw"], L["sh"], L["sw"], L["bias_lshift"], L["out_rshift"], L["relu"] | (L["same"] << 1)]
+            rec[9], rec[10], rec[11] = put(L["w"]), put(L["b"]), c
+            h, w_ = out_dim(h, L["kh"], L["sh"], L["same"]), out_dim(w_, L["kw"], L["sw"], L["same"])
+        elif L["type"] == T_AVGPOOL:
+            if L.get("out_shift", 0) != 0:
+                raise ValueError("AvgPool with output_shift %d: only 0 is supported" % L["out_shift"])
+            rec[2:6] = [L["kh"], L["kw"], L["sh"], L["sw"]]
+            rec[7], rec[8] = 0, L["same"] << 1
+            h, w_ = out_dim(h, L["kh"], L["sh"], L["same"]), out_dim(w_, L["kw"], L["sw"], L["same"])
         elif L["type"] == T_POOL:
             rec[2:6] = [L["kh"], L["kw"], L["sh"], L["sw"]]
             rec[8] = L["same"] << 1

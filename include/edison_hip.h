@@ -96,7 +96,8 @@ int edison_gen_mel_weight_matrix(int num_mel_bins, int num_spectrogram_bins, dou
 
 /* Load the int8 CNN (an .ednn blob written by tools/import_weights_h.py from an NNoM weights.h): the GPU's
  * nnom_model_create() + model_compile() (weights.h:138-161, nnom.c:758-900). Accepted: any chain
- * Input -> {Conv2D valid|same [+ReLU] | MaxPool valid|same | Dense [+ReLU] | Flatten | Softmax (last)}* -> Output whose
+ * Input -> {Conv2D valid|same [+ReLU] | DW_Conv2D valid|same [+ReLU] (depth multiplier 1, even channel count) | MaxPool valid|same |
+ * AvgPool valid|same | Dense [+ReLU] | Flatten | Softmax (last)}* -> Output whose
  * activations fit 2 x 32 KB. The shipped kws_conv graph (and any retrained model of that shape) runs on the matrix
  * cores; every other graph runs on the general layer-by-layer kernel. EDISON_E_SIZE: malformed graph or one the
  * reference itself would reject; EDISON_E_NO_IMPL: a layer/shape the reference runs but this path does not.  */
@@ -122,7 +123,7 @@ typedef struct edison_net_info {
 	                           * served by the general matrix-core kernel; 0: layer-by-layer VALU kernel only      */
 } edison_net_info;
 typedef struct edison_net_layer_info_t {
-	int32_t type;             /* 1 Conv2D, 2 MaxPool, 3 Dense, 4 Softmax                                        */
+	int32_t type;             /* 1 Conv2D, 2 MaxPool, 3 Dense, 4 Softmax, 5 DW_Conv2D, 6 AvgPool                 */
 	int32_t out_h, out_w, out_c;
 	int32_t acts_offset;      /* where this layer's output starts inside one input's acts record                */
 	int32_t relu;
@@ -142,7 +143,8 @@ int edison_net_layers(edison_ctx *ctx, const int8_t *in, int64_t n, int8_t *acts
  * compiler's identity. From then on every entry point that runs the general kernel for this load (edison_net_batch*, and
  * edison_cnn_* / edison_kws_* / edison_stream_* for graphs other than kws_conv) runs the graph's own: same arithmetic,
  * bit-identical outputs, 1.7-3 x the general kernel on the fixture graphs (profiles/r03_net_own_kernel_all_graphs.txt).
- * EDISON_E_NO_IMPL: the graph has no matrix-core plan, or neither hipcc nor libhiprtc.so is installed -- the graph stays on the general
+ * EDISON_E_NO_IMPL: the graph has no matrix-core plan, or it holds a DW_Conv2D / AvgPool layer (such graphs are not specialised: their
+ * VALU layers run inside the general kernel's one launch), or neither hipcc nor libhiprtc.so is installed -- the graph stays on the general
  * kernel. A model load by itself does NONE of this (no compiler, no file, no cached code object): it is this call, or the
  * caller's wish in the environment, read at every load -- EDISON_NET_SPECIALIZE=1: every load ends with this call (a failure
  * there never fails the load), =cache: a load takes the own kernel if an earlier call left it in the cache.
