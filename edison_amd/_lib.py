@@ -223,6 +223,13 @@ SIGNATURES = {
     "edison_mfcc_f32_n_out": (c_int, [c_void_p]),
     "edison_mfcc_f32_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "edison_mfcc_f32_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "edison_mfcc_f32_rows_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "edison_mfcc_f32_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "edison_kws_f32_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_kws_f32_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_f32_stream_predict_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_f32_stream_predict": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_nnom_predict": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "edison_f32_stream_create": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "edison_f32_stream_destroy": (None, [c_void_p]),
     "edison_f32_stream_reset": (c_int, [c_void_p]),

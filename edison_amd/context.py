@@ -417,6 +417,35 @@ class Context:
         self._check(self._L.edison_kws_float_batch_dev(self._h, ctypes.byref(g), 1 if q15 else 0, lo, hi, _t_ptr(audio), int(n_utt), int(utt_stride),
                                                        _t_ptr(feat), _t_ptr(logits), _t_ptr(probs), _t_ptr(argmax)))
 
+    # ------------------------------------------------------------------ variant D audio to label (edison_kws_f32_batch*)
+    def kws_f32(self, mfcc, audio, n_utt=None, utt_stride=None, hop=0, want_feat=True):
+        """Audio to label with the loaded int8 graph and a variant D extractor (mfcc.mfcc_f32.MfccF32 on this context) in one call: what
+        the firmware's NNoM example does per event (app.c:583,613). The graph's input rows x n_out x 1 gives the window; utterance u
+        starts at u * utt_stride (default: one utterance's samples) and holds `rows` frames `hop` apart (0: frame_len / 2). Returns
+        dict(feat [n_utt, rows * n_out] int8 -- None with want_feat=False --, logits, softmax [n_utt, n_out] (softmax None for a graph
+        without Softmax), label [n_utt] uint32, prob [n_utt] float32): nnom_predict's label and probability."""
+        info = self.net_info()
+        x = np.ascontiguousarray(audio, dtype=np.int16).ravel()
+        step = int(hop) if hop else mfcc.frame_len // 2
+        used = (info["in_h"] - 1) * step + mfcc.frame_len
+        stride = used if utt_stride is None else int(utt_stride)
+        if n_utt is None:
+            n_utt = 0 if x.shape[0] < used else 1 + (x.shape[0] - used) // max(stride, 1)
+        if n_utt > 0 and (n_utt - 1) * stride + used > x.shape[0]:
+            raise ValueError("audio too short for %d utterances" % n_utt)
+        feat = np.zeros((n_utt, info["in_h"] * info["in_w"] * info["in_c"]), np.int8) if want_feat else None
+        logits = np.zeros((n_utt, info["n_out"]), np.int8)
+        soft = np.zeros((n_utt, info["n_out"]), np.int8) if info["has_softmax"] else None
+        label, prob = np.zeros(n_utt, np.uint32), np.zeros(n_utt, np.float32)
+        self._check(self._L.edison_kws_f32_batch(self._h, mfcc._h, _np_ptr(x), int(n_utt), stride, int(hop), _np_ptr(feat), _np_ptr(logits),
+                                                 _np_ptr(soft), _np_ptr(label), _np_ptr(prob)))
+        return dict(feat=feat, logits=logits, softmax=soft, label=label, prob=prob)
+
+    def kws_f32_t(self, mfcc, audio, n_utt, utt_stride, label, hop=0, feat=None, logits=None, softmax=None, prob=None):
+        """edison_kws_f32_batch_dev on torch device tensors, enqueued on the context's stream (use_torch_stream), no host synchronisation."""
+        self._check(self._L.edison_kws_f32_batch_dev(self._h, mfcc._h, _t_ptr(audio), int(n_utt), int(utt_stride), int(hop), _t_ptr(feat),
+                                                     _t_ptr(logits), _t_ptr(softmax), _t_ptr(label), _t_ptr(prob)))
+
     def fnet_t(self, x, n, logits=None, probs=None, argmax=None):
         """edison_fnet_batch_dev on torch device tensors (x float32 [n][in_n]), on the context's stream."""
         self._check(self._L.edison_fnet_batch_dev(self._h, _t_ptr(x), int(n), _t_ptr(logits), _t_ptr(probs), _t_ptr(argmax)))

@@ -153,6 +153,10 @@ typedef struct {
 	int8_t *out;    /* [n][n_features - offset] q7 */
 	float *out_f32; /* same shape, before round / saturate, or NULL */
 	float *logmel;  /* [n][26] or NULL */
+	/* frames_per_row == 0: the flat form, frame f starts at audio + f * frame_step. Otherwise the rows form: frame f belongs to row
+	 * u = f / frames_per_row and starts at audio + u * row_stride + (f % frames_per_row) * frame_step; n_frames < 2^31. Outputs are
+	 * [f][..] back to back in both forms. */
+	int64_t frames_per_row, row_stride;
 } ed_mfcc_f32_args_t;
 
 /* ------------------------------------------------------------------ int8 CNN model (kws_conv topology)   */

@@ -21,6 +21,7 @@
 
 #include "../../include/edison_hip.h"
 #include "edison_fsm_core.h"
+#include "nnom_predict_core.h"
 
 /* firmware/src/ai/nnom/keywords.txt */
 static const char *const g_keywords[EDISON_NET_OUT] = {"edison", "cinema", "bedroom", "office", "livingroom",
@@ -143,6 +144,19 @@ void aiNnomTest(void)
 
 int aiRunInference(void *in_data, void *out_data) { return aiNnomRunInference(in_data, out_data); }
 
+/* nnom_predict's result rule (nnom_utils.c:272-302) on n outputs of n_out int8 values each, on the host: no GPU, no context */
+int edison_nnom_predict(const int8_t *out, int64_t n, int n_out, uint32_t *label, float *prob)
+{
+	if (n < 0 || n_out < 1 || (n > 0 && (!out || !label))) return EDISON_E_ARGUMENT;
+	for (int64_t i = 0; i < n; i++)
+	{
+		float p;
+		ed_nnom_predict_one(out + i * n_out, n_out, &label[i], &p);
+		if (prob) prob[i] = p;
+	}
+	return EDISON_OK;
+}
+
 int aiNnomPredict(uint32_t *label, float *prob)
 {
 	/* nnom_predict (nnom_utils.c:258-305) on the static input buffer: run, first-max label, prob = max/sum */
@@ -151,14 +165,9 @@ int aiNnomPredict(uint32_t *label, float *prob)
 		int r = aiInitialize();
 		if (r != EDISON_OK) return r;
 	}
-	int32_t am = 0;
-	int r = edison_cnn_batch(g_ctx, g_net_in, 1, NULL, g_net_out, &am);
+	int r = edison_cnn_batch(g_ctx, g_net_in, 1, NULL, g_net_out, NULL);
 	if (r != EDISON_OK) return r;
-	int sum = 0;
-	for (int i = 0; i < EDISON_NET_OUT; i++) sum += g_net_out[i];
-	*label = (uint32_t)am;
-	*prob = sum != 0 ? (float)g_net_out[am] / (float)sum : 0.0f;
-	return EDISON_OK;
+	return edison_nnom_predict(g_net_out, 1, EDISON_NET_OUT, label, prob);
 }
 
 int8_t *aiNnomGetInputBuffer(void) { return g_net_in; }

@@ -25,6 +25,17 @@
 
 __device__ __forceinline__ void ef_wave_sync() { __builtin_amdgcn_wave_barrier(); }
 
+/* Where frame f starts. ROWS = false is the flat form and compiles to what the kernels were before the rows form existed; ROWS = true
+ * divides in 32 bits (the rows entry point keeps n_frames below 2^31). Both kernels are instantiated for both forms. */
+template <bool ROWS>
+__device__ __forceinline__ const int16_t *ef_frame(const ed_mfcc_f32_args_t &a, int64_t f)
+{
+	if (!ROWS) return a.audio + f * a.frame_step;
+	const uint32_t fpr = (uint32_t)a.frames_per_row, u = (uint32_t)f / fpr, i = (uint32_t)f - u * fpr;
+	return a.audio + (int64_t)u * a.row_stride + (int64_t)i * a.frame_step;
+}
+
+template <bool ROWS>
 __global__ __launch_bounds__(64 * EF_WPB) void ed_mfcc_f32_kernel(ed_mfcc_f32_args_t a, const ed_f32_tables_t *__restrict__ T)
 {
 	extern __shared__ __attribute__((aligned(16))) float2 s_buf[]; /* [EF_WPB][padded]: sized by the launcher */
@@ -48,7 +59,7 @@ __global__ __launch_bounds__(64 * EF_WPB) void ed_mfcc_f32_kernel(ed_mfcc_f32_ar
 
 	for (int64_t f = (int64_t)blockIdx.x * EF_WPB + w; f < a.n_frames; f += (int64_t)gridDim.x * EF_WPB)
 	{
-		const int16_t *x = a.audio + f * a.frame_step;
+		const int16_t *x = ef_frame<ROWS>(a, f);
 		/* 1. pre-emphasis, window, padding; stored bit-reversed for the in-place decimation-in-time FFT */
 		for (int i = lane; i < P; i += 64)
 		{
@@ -139,7 +150,8 @@ extern "C" int ed_launch_mfcc_f32(const ed_mfcc_f32_args_t *args, const ed_f32_t
 	if (per_cu < 1) per_cu = 1;
 	const int64_t cap = (int64_t)n_cu * per_cu;
 	if (blocks > cap) blocks = cap;
-	hipLaunchKernelGGL(ed_mfcc_f32_kernel, dim3((unsigned)blocks), dim3(64 * EF_WPB), lds, stream, *args, dev_tab);
+	if (args->frames_per_row) hipLaunchKernelGGL(ed_mfcc_f32_kernel<true>, dim3((unsigned)blocks), dim3(64 * EF_WPB), lds, stream, *args, dev_tab);
+	else hipLaunchKernelGGL(ed_mfcc_f32_kernel<false>, dim3((unsigned)blocks), dim3(64 * EF_WPB), lds, stream, *args, dev_tab);
 	return (int)hipGetLastError();
 }
 
@@ -186,6 +198,7 @@ extern "C" { extern const int ed_lab_build_mfcc_f32; const int ed_lab_build_mfcc
 #else
 #define EF2_PR(p) ((void)0)
 #endif
+template <bool ROWS>
 __global__ __launch_bounds__(64 * EF2_WPB) void ed_mfcc_f32_fast_kernel(ed_mfcc_f32_args_t a, const ed_f32_tables_t *__restrict__ T,
                                                                       const ed_mfcc_tables_t *__restrict__ F)
 {
@@ -247,7 +260,8 @@ __global__ __launch_bounds__(64 * EF2_WPB) void ed_mfcc_f32_fast_kernel(ed_mfcc_
 
 	auto load_pair = [&](uint32_t pr, int (&xa)[8], int (&ya)[8], int (&xb)[8], int (&yb)[8]) {
 		const uint32_t fA = 2 * pr, fB = fA + 1 < n_frames ? fA + 1 : fA;
-		const int16_t *pa = a.audio + (int64_t)fA * a.frame_step, *pb = a.audio + (int64_t)fB * a.frame_step;
+		/* each frame's own address: in the rows form a pair straddles two rows when frames_per_row is odd */
+		const int16_t *pa = ef_frame<ROWS>(a, fA), *pb = ef_frame<ROWS>(a, fB);
 #pragma unroll
 		for (int q = 0; q < 8; q++) { xa[q] = pa[off0[q]]; ya[q] = pa[off1[q]]; xb[q] = pb[off0[q]]; yb[q] = pb[off1[q]]; }
 	};
@@ -372,10 +386,16 @@ extern "C" int ed_launch_mfcc_f32_fast(const ed_mfcc_f32_args_t *args, const ed_
 {
 	if (args->n_frames <= 0) return 0;
 	const size_t lds = sizeof(float) * (EF2_TAB_FLOATS + EF2_WPB * EF2_XBUF_FLOATS) + 16;
-	{ const int e = ed_kernel_prepare((const void *)ed_mfcc_f32_fast_kernel, 64 * EF2_WPB, lds, NULL, NULL); if (e) return e; }
+	const bool rows = args->frames_per_row != 0;
+	{
+		const int e = ed_kernel_prepare(rows ? (const void *)ed_mfcc_f32_fast_kernel<true> : (const void *)ed_mfcc_f32_fast_kernel<false>, 64 * EF2_WPB, lds,
+		                                NULL, NULL);
+		if (e) return e;
+	}
 	const int64_t n_pairs = (args->n_frames + 1) / 2;
 	int64_t blocks = (n_pairs + EF2_WPB - 1) / EF2_WPB;
 	if (blocks > n_cu) blocks = n_cu;
-	hipLaunchKernelGGL(ed_mfcc_f32_fast_kernel, dim3((unsigned)blocks), dim3(64 * EF2_WPB), lds, stream, *args, dev_tab, dev_fft_tab);
+	if (rows) hipLaunchKernelGGL(ed_mfcc_f32_fast_kernel<true>, dim3((unsigned)blocks), dim3(64 * EF2_WPB), lds, stream, *args, dev_tab, dev_fft_tab);
+	else hipLaunchKernelGGL(ed_mfcc_f32_fast_kernel<false>, dim3((unsigned)blocks), dim3(64 * EF2_WPB), lds, stream, *args, dev_tab, dev_fft_tab);
 	return (int)hipGetLastError();
 }

@@ -185,6 +185,37 @@ def float_frame_inference(path, net, ctx=None, out=None):
     return dict(host=host, mcu=mcu)
 
 
+def nnom_example(path, graph, labels=None, feature_offset=1, dec_bits=8, preemph=0.97, ctx=None, out=None):
+    """`kws mcu nnom <wav> --graph <weights.h | file.ednn> [--labels <file>]`: the firmware's NNoM keyword-spotting example
+    (appNnomKwsRun, app.c:545-623) over a wav file on the GPU. The graph's input rows x n x 1 gives the window and the extractor,
+    mfcc_create(n + feature_offset, feature_offset, 512, dec_bits, preemph); every 512 samples are one audio event (the last one
+    padded with zeros), and every event prints `label : pct%` as app.c:620 does. labels: one class name per line."""
+    from ..context import Context
+    from ..mfcc.mfcc_f32 import NnomKwsFrontEnd
+    out = out or sys.stdout
+    ctx = ctx or Context(model_path=None)
+    if str(graph).endswith(".h"):
+        ctx.load_weights_h(graph)
+    else:
+        ctx.load_model(graph)
+    info = ctx.net_info()
+    names = None
+    if labels is not None:
+        with open(labels) as f:
+            names = [line.strip() for line in f if line.strip()]
+    data = np.asarray(read_wav(path), dtype=np.int16).ravel()
+    data = np.concatenate([data, np.zeros(-data.size % 512, np.int16)])
+    fe = NnomKwsFrontEnd(ctx=ctx, window_rows=info["in_h"], num_mfcc_features=info["in_w"] + int(feature_offset), feature_offset=int(feature_offset),
+                         mfcc_dec_bits=int(dec_bits), preemph=float(preemph))
+    try:
+        res = fe.predict(data, labels=names)
+    finally:
+        fe.close()
+    for i, (lb, pr) in enumerate(zip(res["label"], res["prob"])):
+        print("%s : %d%%" % (res["names"][i] if names else int(lb), int(pr * 100)), file=out)
+    return res
+
+
 # the reference's own function names and call conventions (kws_on_mcu.py:243,273,310: `args` = the CLI's remaining
 # arguments, args[0] = the wav file)
 def singleInference(repeat=1):
@@ -210,11 +241,27 @@ def main(argv):
             return 1
         net = argv[i + 1]
         argv = argv[:i] + argv[i + 2:]
+    opts = {}
+    for flag in ("--graph", "--labels"):
+        if flag in argv:
+            i = argv.index(flag)
+            if i + 1 >= len(argv):
+                print('%s needs a file' % flag)
+                return 1
+            opts[flag] = argv[i + 1]
+            argv = argv[:i] + argv[i + 2:]
     if len(argv) < 2:
-        print('usage: kws mcu <single [n] | fileinf <wav> | file <wav> | frame <wav>> [--net <file.ednf>]')
+        print('usage: kws mcu <single [n] | fileinf <wav> | file <wav> | frame <wav>> [--net <file.ednf>]\n'
+              '       kws mcu nnom <wav> --graph <weights.h | file.ednn> [--labels <file>]')
         return 1
     mode = argv[1]
     print('Running mode', mode, 'with args', argv[2:])
+    if mode == "nnom":
+        if len(argv) < 3 or "--graph" not in opts:
+            print('need a wav file and --graph <weights.h | file.ednn>')
+            return 1
+        nnom_example(argv[2], opts["--graph"], labels=opts.get("--labels"))
+        return 0
     if mode == "single":
         single_inference(int(argv[2]) if len(argv) > 2 else 1)
         return 0

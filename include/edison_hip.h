@@ -692,6 +692,11 @@ void aiNnomInit(void);
 void aiNnomPrintInfo(void);
 int aiNnomRunInference(void *in_data, void *out_data);
 int aiNnomPredict(uint32_t *label, float *prob);
+/* nnom_predict's result rule (nnom_utils.c:272-302) alone, on the host (no GPU, no context, like edison_fsm_step): out [n][n_out] int8,
+ * the graph's last output (the softmax if it ends in one, else the logits). n_out > 1: label = first strict maximum, prob = (float)max /
+ * (float)(int32 sum of all n_out values), 0 when the sum is 0 (a negative sum keeps the C quotient); n_out == 1: prob = out / 127.f,
+ * label = prob >= 0.5f. prob may be NULL. aiNnomPredict is this on the shipped graph's softmax. */
+int edison_nnom_predict(const int8_t *out, int64_t n, int n_out, uint32_t *label, float *prob);
 int8_t *aiNnomGetInputBuffer(void);
 int8_t *aiNnomGetOutputBuffer(void);
 /* firmware/src/app.c:152-153: write / push one frame's MFCCs into the process-global 403-byte net input
@@ -725,6 +730,27 @@ int edison_mfcc_f32_batch_dev(mfcc_t *mfcc, const int16_t *audio, int64_t n_fram
                               float *out_f32, float *logmel);
 int edison_mfcc_f32_batch(mfcc_t *mfcc, const int16_t *audio, int64_t n_frames, int64_t frame_step, int8_t *out,
                           float *out_f32, float *logmel);
+/* Variant D over rows, mirroring edison_mfcc_rows: frame f belongs to row u = f / frames_per_row and starts at
+ * audio + u * row_stride + (f % frames_per_row) * frame_step; out [n_rows * frames_per_row][n_out] back to back (out_f32, logmel
+ * likewise, may be NULL). One launch; rows may overlap or leave gaps. The host form stages (n_rows - 1) * row_stride +
+ * (frames_per_row - 1) * frame_step + frame_len samples. EDISON_E_SIZE: 2^31 frames or more. */
+int edison_mfcc_f32_rows_dev(mfcc_t *mfcc, const int16_t *audio, int64_t n_rows, int64_t row_stride, int64_t frames_per_row,
+                             int64_t frame_step, int8_t *out, float *out_f32, float *logmel);
+int edison_mfcc_f32_rows(mfcc_t *mfcc, const int16_t *audio, int64_t n_rows, int64_t row_stride, int64_t frames_per_row,
+                         int64_t frame_step, int8_t *out, float *out_f32, float *logmel);
+/* Audio to label in one call with the loaded int8 graph (edison_model_load*: any graph the general path runs) and a variant D
+ * extractor: what the firmware's NNoM example does per audio event (mfcc_compute per row, aiNnomPredict: app.c:583,613), batched.
+ * The graph's input rows x n_out x 1 gives the window: n_out must be edison_mfcc_f32_n_out(mfcc); utterance u starts at
+ * audio + u * utt_stride and holds `rows` frames `hop` samples apart (hop = 0: frame_len / 2, the firmware's overlap), i.e.
+ * (rows - 1) * hop + frame_len samples. Three launches: the rows form above -> feat [n_utt][rows][n_out], the graph -> logits, softmax
+ * [n_utt][graph outputs] (softmax is left alone for a graph without Softmax), edison_nnom_predict's rule on the graph's last output ->
+ * label [n_utt] uint32, prob [n_utt] float. Every output but label may be NULL (a NULL feat goes to the context's scratch buffer).
+ * EDISON_E_ARGUMENT: no graph loaded, or an extractor of another context; EDISON_E_SIZE: another input shape (the message names
+ * both); both before anything is launched. The _dev form is asynchronous on the context's stream. */
+int edison_kws_f32_batch_dev(edison_ctx *ctx, mfcc_t *mfcc, const int16_t *audio, int64_t n_utt, int64_t utt_stride, int64_t hop,
+                             int8_t *feat, int8_t *logits, int8_t *softmax, uint32_t *label, float *prob);
+int edison_kws_f32_batch(edison_ctx *ctx, mfcc_t *mfcc, const int16_t *audio, int64_t n_utt, int64_t utt_stride, int64_t hop,
+                         int8_t *feat, int8_t *logits, int8_t *softmax, uint32_t *label, float *prob);
 
 /* The front end of the firmware's NNoM keyword-spotting example around mfcc_compute (appNnomKwsRun, app.c:545-623): every
  * audio event delivers 512 new samples behind the last 256 old ones (app.c:567-575), two frames are extracted at offsets 0
@@ -740,6 +766,14 @@ int edison_f32_stream_reset(edison_f32_stream *s);
 int64_t edison_f32_stream_events_seen(const edison_f32_stream *s);
 int edison_f32_stream_push_dev(edison_f32_stream *s, const int16_t *samples, int n_events, int8_t *windows);
 int edison_f32_stream_push(edison_f32_stream *s, const int16_t *samples, int n_events, int8_t *windows);
+/* The example's whole loop: a push that also runs the loaded int8 graph on the window after every event and nnom_predict's rule on
+ * its output: logits, softmax [n_events][graph outputs], label [n_events] uint32, prob [n_events] float; every output but label may
+ * be NULL. The graph reads the overlapping windows in place (no window copy). Its input must be window_rows x n_out x 1 (checked
+ * per call as in edison_kws_f32_batch). State, reset and events_seen as for push; push and predict may be mixed on one stream. */
+int edison_f32_stream_predict_dev(edison_f32_stream *s, const int16_t *samples, int n_events, int8_t *logits, int8_t *softmax,
+                                  uint32_t *label, float *prob);
+int edison_f32_stream_predict(edison_f32_stream *s, const int16_t *samples, int n_events, int8_t *logits, int8_t *softmax,
+                              uint32_t *label, float *prob);
 /* One 1024-sample frame through the GPU MFCC, any variant; out32 fp32. */
 int edison_mfcc_frame(const int16_t *frame1024, int variant, float *out32);
 edison_ctx *edison_global_ctx(void);
