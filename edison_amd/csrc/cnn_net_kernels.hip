@@ -1,8 +1,9 @@
 /*
- * cnn_net_kernels.hip -- layer-by-layer int8 inference of ANY sequential NNoM graph the planner accepts
+ * cnn_net_kernels.hip -- layer-by-layer int8 inference of ANY NNoM graph the planner accepts
  * (model_net.c), hand-written HIP for gfx950. It is the GPU's model_run() (nnom.c:975-1040): one workgroup owns an
- * utterance and walks the layer list; activations (HWC int8) ping-pong between two LDS buffers, weights (output
- * channel innermost, see model_net.c) and the accumulator seeds are read from L1/L2 where every workgroup shares them.
+ * utterance and walks the layer list; activations (HWC int8) ping-pong between two LDS buffers (a branching graph: one LDS
+ * area per live tensor, placed by the planner), weights (output channel innermost, see model_net.c) and the accumulator
+ * seeds are read from L1/L2 where every workgroup shares them.
  *
  * Arithmetic restated (all integer, results are bit-exact, not "within tolerance"):
  *   Conv2D   sat8((sum x*w + (bias << BL) + NN_ROUND(RS)) >> RS), zero padding by skipping taps outside the image
@@ -16,6 +17,10 @@
  *            arm_pool_q7_HWC.c:424-446; which window a square map gets: model_net.c)
  *   Dense    the same requantisation over the flattened HWC input (arm_fully_connected_q7_opt.c:374-473; the
  *            importer undoes the weight interleave)
+ *   Add/Sub/Mult  shift 0: sat8(a + b), sat8(a - b), sat8((a * b) >> 7) (arm_add_q7 / arm_sub_q7 / arm_mult_q7); otherwise
+ *            sat8((r + (1 << (shift - 1))) >> shift) with r = a + b, a - b, a * b (local_*_q7, nnom_local.c:1090-1145, rounding build);
+ *            a third and later input of Add is added to the OUTPUT, saturated each time (nnom_matrix.c:123-137); ReLU as a tail
+ *   Concat   the inputs' channels side by side per pixel (nnom_concat.c:197-214, inputs of one shape)
  *   Softmax  arm_softmax_q7.c:215-260, portable branch; argmax = first maximum of the last layer (nnom_utils.c:275-284)
  *
  * The shipped kws_conv graph does not come here: cnn_mfma_kernels.hip runs it on the matrix cores. This kernel trades
@@ -260,6 +265,62 @@ __device__ __forceinline__ void en_dense(const ed_net_layer_t &L, const int8_t *
 	}
 }
 
+/* where the k-th input of a merge layer lies in LDS (the network input stays at offset 0 for the whole pass of a branching graph) */
+__device__ __forceinline__ const int8_t *en_source(const ed_net_plan_t *P, const ed_net_layer_t &L, const int8_t *lds, int k)
+{
+	const int s = P->src[L.src_off + 1 + k];
+	return lds + (s < 0 ? 0 : P->L[s].out_buf);
+}
+
+__device__ __forceinline__ int en_merge1(int type, int rs, int a, int b)
+{
+	int r = type == ED_NET_ADD ? a + b : type == ED_NET_SUB ? a - b : a * b;
+	if (rs == 0) r = type == ED_NET_MULT ? r >> 7 : r;
+	else r = (r + (1 << (rs - 1))) >> rs;
+	return en_ssat8(r);
+}
+
+/* Add / Sub / Mult: four int8 values per lane and step, one dword from each input (the areas are 16-byte aligned and padded
+ * to 16 bytes, so the last dword of a tensor whose size is no multiple of four is read and written whole) */
+__device__ __forceinline__ void en_merge(const ed_net_plan_t *P, const ed_net_layer_t &L, const int8_t *lds, int8_t *out)
+{
+	const int n_in = P->src[L.src_off];
+	const uint32_t *a4 = reinterpret_cast<const uint32_t *>(en_source(P, L, lds, 0));
+	const uint32_t *b4 = reinterpret_cast<const uint32_t *>(en_source(P, L, lds, 1));
+	for (int idx = threadIdx.x; idx < (L.out_n + 3) >> 2; idx += EN_THREADS)
+	{
+		const uint32_t a = a4[idx], b = b4[idx];
+		int r[4];
+#pragma unroll
+		for (int j = 0; j < 4; j++) r[j] = en_merge1(L.type, L.rs, (int)(int8_t)(a >> (8 * j)), (int)(int8_t)(b >> (8 * j)));
+		for (int k = 2; k < n_in; k++) /* Add only (model_net.c): in_k + out */
+		{
+			const uint32_t c = reinterpret_cast<const uint32_t *>(en_source(P, L, lds, k))[idx];
+#pragma unroll
+			for (int j = 0; j < 4; j++) r[j] = en_merge1(L.type, L.rs, (int)(int8_t)(c >> (8 * j)), r[j]);
+		}
+		uint32_t q = 0;
+#pragma unroll
+		for (int j = 0; j < 4; j++) q |= (uint32_t)(uint8_t)(L.relu && r[j] < 0 ? 0 : r[j]) << (8 * j);
+		reinterpret_cast<uint32_t *>(out)[idx] = q;
+	}
+}
+
+__device__ __forceinline__ void en_concat(const ed_net_plan_t *P, const ed_net_layer_t &L, const int8_t *lds, int8_t *out)
+{
+	const int n_in = P->src[L.src_off], c = L.in_c;
+	for (int k = 0; k < n_in; k++)
+	{
+		const int8_t *in = en_source(P, L, lds, k);
+		for (int idx = threadIdx.x; idx < L.in_n; idx += EN_THREADS)
+		{
+			const int pix = idx / c, ch = idx - pix * c;
+			const int v = in[idx];
+			out[pix * L.out_c + k * c + ch] = (int8_t)(L.relu && v < 0 ? 0 : v);
+		}
+	}
+}
+
 __device__ __forceinline__ void en_softmax(const ed_net_layer_t &L, const int8_t *in, int8_t *out)
 {
 	if (threadIdx.x != 0) return;
@@ -306,6 +367,8 @@ __global__ __launch_bounds__(EN_THREADS) void ed_net_kernel(const ed_net_plan_t 
 			else if (L.type == ED_NET_DWCONV) en_dwconv(L, a, o, W, S);
 			else if (L.type == ED_NET_AVGPOOL) en_avgpool(L, a, o);
 			else if (L.type == ED_NET_DENSE) en_dense(L, a, o, W, S);
+			else if (L.type == ED_NET_CONCAT) en_concat(P, L, en_lds, o);
+			else if (ED_NET_IS_MERGE(L.type)) en_merge(P, L, en_lds, o);
 			else en_softmax(L, a, o);
 			__syncthreads();
 			if (acts)

@@ -817,7 +817,12 @@ __device__ __forceinline__ void emm_net_body(const ed_net_plan_t *__restrict__ P
 	lds32 *xtab_l = reinterpret_cast<lds32 *>(reinterpret_cast<lds8 *>(coltab_l) + ((8 * n_coltab + 15) & ~15));
 	EMM_LDS uint16_t *intab_l = reinterpret_cast<EMM_LDS uint16_t *>(reinterpret_cast<lds8 *>(xtab_l) + ((8 * n_xtab + 15) & ~15));
 	lds8 *fragl = tbl + EMM_MF(tbl_bytes);
-	lds8 *slice = fragl + EMM_MF(frag_lds) + wave * (2 * buf_bytes + EMM_MF(x_bytes));
+#if EMM_SPEC
+	EMM_CONST int hold_bytes = 0; /* a graph's own kernel is never built for a branching graph (edison_net_specialize) */
+#else
+	const int hold_bytes = M->hold_bytes;
+#endif
+	lds8 *slice = fragl + EMM_MF(frag_lds) + wave * (2 * buf_bytes + EMM_MF(x_bytes) + hold_bytes);
 	lds8 *xbuf = slice + 2 * buf_bytes; /* the activation region in front of it: a layer's input at one end, its output at the other */
 	lds8 *in0 = slice + EMM_RUN(0).in_off; /* (layer 0 always runs: a MaxPool is only skipped behind a convolution) */
 	{
@@ -1159,6 +1164,59 @@ __device__ __forceinline__ void emm_net_body(const ed_net_plan_t *__restrict__ P
 					emm_st_c4(o + b * R.o_img + R.o_origin + y * R.o_row + x * R.oc_pitch + 4 * c4, q, al4, tail);
 				}
 			}
+#if !EMM_SPEC
+			else if (R.kind == ED_RUN_MERGE)
+			{
+				/* Add / Sub / Mult (nnom_matrix.c; arm_*_q7 at shift 0, local_*_q7 otherwise): a lane owns four neighbouring channels of one
+				 * pixel, consecutive lanes consecutive groups, then consecutive pixels -- every input is read as consecutive dwords (16-bit
+				 * words) along a pixel, each input by an instruction of its own, so two inputs at the same channel offset never meet in a
+				 * bank within one read. A third and later input of Add combines with the result so far, saturated each time. */
+				const int c = R.out_c, c4n = (c + 3) >> 2, per_img = R.pix_per_img * c4n, ns = R.n_ks, op = R.ph, rs = R.rs & ED_RUN_RS_MASK;
+				const bool al4 = (c & 3) == 0;
+				const int32_t *ms = M->msrc + 5 * R.koff_off;
+				const float inv_img = __builtin_amdgcn_rcpf((float)per_img), inv_c4 = __builtin_amdgcn_rcpf((float)c4n), inv_ow = __builtin_amdgcn_rcpf((float)R.col_w);
+				for (int i = lane_l; i < nb * per_img; i += 64)
+				{
+					int b, e, pix, c4, y, x;
+					emm_divmod(i, per_img, inv_img, b, e); emm_divmod(e, c4n, inv_c4, pix, c4); emm_divmod(pix, R.col_w, inv_ow, y, x);
+					const bool tail = !al4 && c4 == c4n - 1;
+					int r[4];
+					for (int k = 0; k < ns; k++)
+					{
+						const uint32_t v = emm_ld_c4(slice + ms[5 * k] + b * ms[5 * k + 1] + ms[5 * k + 2] + y * ms[5 * k + 3] + x * ms[5 * k + 4] + 4 * c4, al4, tail);
+#pragma unroll
+						for (int j = 0; j < 4; j++)
+						{
+							const int a = (int)(int8_t)(v >> (8 * j));
+							if (k == 0) { r[j] = a; continue; }
+							/* the first pair is (input 0, input 1); a later input comes first and the result so far second */
+							const int p = k == 1 ? r[j] : a, q = k == 1 ? a : r[j];
+							int t = op == ED_NET_ADD ? p + q : op == ED_NET_SUB ? p - q : p * q;
+							t = rs == 0 ? (op == ED_NET_MULT ? t >> 7 : t) : (t + (1 << (rs - 1))) >> rs;
+							r[j] = emm_med3(t, -128, 127);
+						}
+					}
+					uint32_t q4 = 0;
+#pragma unroll
+					for (int j = 0; j < 4; j++) q4 |= (uint32_t)(uint8_t)(r[j] < R.lo_clamp ? R.lo_clamp : r[j]) << (8 * j);
+					emm_st_c4(o + b * R.o_img + R.o_origin + y * R.o_row + x * R.oc_pitch + 4 * c4, q4, al4, tail);
+				}
+			}
+			else if (R.kind == ED_RUN_CAT)
+			{
+				/* Concat over the channels (nnom_concat.c:197-214, inputs of one shape): input k's channels of a pixel go behind input
+				 * k - 1's; a lane moves one byte (the channel counts need not be even), consecutive lanes consecutive bytes of a pixel */
+				const int cs = R.pitch_x, per_img = R.pix_per_img * cs;
+				const int32_t *ms = M->msrc + 5 * R.koff_off;
+				for (int k = 0; k < R.n_ks; k++)
+					for (int i = lane_l; i < nb * per_img; i += 64)
+					{
+						const int b = i / per_img, e = i - b * per_img, pix = e / cs, ch = e - pix * cs, y = pix / R.col_w, x = pix - y * R.col_w;
+						const int v = slice[ms[5 * k] + b * ms[5 * k + 1] + ms[5 * k + 2] + y * ms[5 * k + 3] + x * ms[5 * k + 4] + ch];
+						o[b * R.o_img + R.o_origin + y * R.o_row + x * R.oc_pitch + k * cs + ch] = (int8_t)(v < R.lo_clamp ? R.lo_clamp : v);
+					}
+			}
+#endif
 			else /* softmax: arm_softmax_q7.c:215-260 */
 			{
 				const int in_n = (EMM_SKIP & 16) ? 0 : R.in_n;

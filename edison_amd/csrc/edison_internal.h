@@ -242,7 +242,13 @@ int ed_parse_model(const void *blob, size_t blob_bytes, ed_cnn_model_t *out, ed_
  * utterance; activations ping-pong between two LDS buffers; weights stay OHWI int8 in HBM/L2. */
 #define ED_NET_MAX_LAYERS 32
 #define ED_NET_MAX_LDS (64 * 1024 - 256) /* both activation buffers */
-enum { ED_NET_CONV = 1, ED_NET_POOL = 2, ED_NET_DENSE = 3, ED_NET_SOFTMAX = 4, ED_NET_DWCONV = 5, ED_NET_AVGPOOL = 6 };
+enum { ED_NET_CONV = 1, ED_NET_POOL = 2, ED_NET_DENSE = 3, ED_NET_SOFTMAX = 4, ED_NET_DWCONV = 5, ED_NET_AVGPOOL = 6,
+       ED_NET_ADD = 7, ED_NET_SUB = 8, ED_NET_MULT = 9, ED_NET_CONCAT = 10 };
+/* Branching graphs (a source table in the blob, nnom_import.py): a layer reads the layers its source list names instead of its
+ * predecessor. The merge layers -- Add, Sub, Mult (nnom_matrix.c) and Concat over the channel axis (nnom_concat.c) -- read two or more. */
+#define ED_NET_MAX_IN 8    /* inputs of one merge layer */
+#define ED_NET_MAX_SRC 128 /* entries of ed_net_plan_t.src: per layer its input count, then the layers it reads */
+#define ED_NET_IS_MERGE(t) ((t) >= ED_NET_ADD && (t) <= ED_NET_CONCAT)
 
 typedef struct {
 	int32_t type, relu;
@@ -256,7 +262,7 @@ typedef struct {
 	int32_t acts_off; /* offset of the layer's output inside one utterance's activation dump                  */
 	int32_t check_taps; /* some window reaches outside the image: padding, or SAME with an even kernel / stride (the
 	                     * output is ceil(in/stride) wide, so the last windows overhang the right / bottom edge)   */
-	int32_t pad_;
+	int32_t src_off;  /* index into ed_net_plan_t.src: this layer's input count n, then n layer indices (-1: the network input) */
 } ed_net_layer_t;
 
 typedef struct {
@@ -267,6 +273,9 @@ typedef struct {
 	int32_t has_softmax;
 	int32_t lds_bytes, acts_bytes, weights_bytes, n_seeds;
 	ed_net_layer_t L[ED_NET_MAX_LAYERS];
+	int32_t branching;    /* 1: some layer reads something else than its predecessor (the blob carries a source table)   */
+	int32_t n_src;
+	int32_t src[ED_NET_MAX_SRC];
 } ed_net_plan_t;
 
 /* Builds the plan, the device weight image and the seeds from an .ednn blob; *weights / *seeds are malloc'd.
@@ -326,7 +335,13 @@ typedef struct {
 /* ED_RUN_DW / ED_RUN_AVG: DW_Conv2D and AvgPool on the VALU between the matrix-core layers, four channels per lane: they
  * read a compact image like the MaxPool passes and store into the consumer's layout; a DW_Conv2D keeps its weights ([tap][group of
  * four channels] dwords, zero beyond C) at frag_off of the fragment buffer and its seeds (a multiple of four) at seed_off */
-enum { ED_RUN_SKIP = 0, ED_RUN_MM = 1, ED_RUN_POOL4 = 2, ED_RUN_POOL1 = 3, ED_RUN_SOFTMAX = 4, ED_RUN_DW = 5, ED_RUN_AVG = 6 };
+/* ED_RUN_MERGE / ED_RUN_CAT: Add, Sub, Mult and Concat of a branching graph on the VALU. Their inputs lie wherever the
+ * planner stored them -- the wave's ping-pong region or a HELD area behind its expansion buffer -- each in the layout of the one
+ * reader that demands a layout, so a pass reads every input through an (offset, image, origin, row, pixel pitch) entry of msrc[].
+ * Fields reused: n_ks = inputs, koff_off = first msrc entry, ph = the layer type (ED_NET_ADD ..), pitch_x = channels per input (CAT) */
+enum { ED_RUN_SKIP = 0, ED_RUN_MM = 1, ED_RUN_POOL4 = 2, ED_RUN_POOL1 = 3, ED_RUN_SOFTMAX = 4, ED_RUN_DW = 5, ED_RUN_AVG = 6,
+       ED_RUN_MERGE = 7, ED_RUN_CAT = 8 };
+#define ED_MM_MAX_MSRC 64 /* inputs of all merge layers together */
 /* ed_mm_run_t.rs: the planner found that sat8(v >> rs) may be taken as the high byte of sat16(v >> (rs - 8)) -- always for
  * rs >= 8, for rs < 8 when no accumulator of the layer can leave 32 bits under the left shift (model_net_mm.c) */
 #define ED_RUN_RS_MASK 0xff
@@ -368,7 +383,8 @@ typedef struct {
 	int32_t n_cols;             /* entries of coltab[] in use                                                          */
 	int32_t n_xtab;             /* entries of xtab[] in use                                                            */
 	int32_t n_intab;            /* entries of intab[] in use: in_n, or 0 (the kernel divides)                          */
-	int32_t pad_;
+	int32_t hold_bytes;         /* a wave's held areas (behind its expansion buffer): tensors of a branching graph that stay alive
+	                             * across several layers; 0 for a sequential graph                                          */
 	ed_mm_layer_t L[ED_NET_MAX_LAYERS];
 	ed_mm_run_t R[ED_NET_MAX_LAYERS];
 	int32_t koff[ED_MM_MAX_KOFF];
@@ -382,6 +398,8 @@ typedef struct {
 	int32_t xtab[2 * ED_MM_MAX_XTAB];
 	/* byte offset of input element e (HWC order) inside layer 0's LDS layout */
 	uint16_t intab[ED_MM_MAX_INTAB];
+	/* per input of a merge pass: byte offset of its images inside the wave's slice, bytes per image, origin, row pitch, pixel pitch */
+	int32_t msrc[5 * ED_MM_MAX_MSRC];
 } ed_mm_plan_t;
 
 /* Adds the matrix-core plan to a graph ed_plan_net accepted. *frag / *seeds are malloc'd when mm->ok. */

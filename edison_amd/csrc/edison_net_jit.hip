@@ -362,6 +362,9 @@ static int specialize(edison_ctx *ctx, int cache_only)
 	if (!ctx->have_model) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_net_specialize: no model loaded");
 	if (!ctx->mm_ok || !ctx->h_mm_plan)
 		return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_net_specialize: this graph has no matrix-core plan (it runs on the layer-by-layer kernel)");
+	/* a branching graph (Add, Sub, Mult, Concat, hooks from earlier layers) keeps the general kernel: the own kernel has no merge passes */
+	if (ctx->net.branching)
+		return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_net_specialize: a branching graph (Add, Sub, Mult, Concat or a hook from an earlier layer) is not specialised (it stays on the general kernel)");
 	/* a graph with a DW_Conv2D or an AvgPool keeps the general kernel: its VALU layers gain nothing from constants, and the own kernel's
 	 * register budget is tuned for matrix-core layers only */
 	for (int i = 0; i < ctx->net.n_layers; i++)

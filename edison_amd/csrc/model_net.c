@@ -1,6 +1,9 @@
 /*
- * model_net.c -- host-side (plain C) planner for ANY sequential NNoM int8 graph the importer understands
- * (tools/import_weights_h.py): Input -> {Conv2D [+ReLU] | DW_Conv2D [+ReLU] | MaxPool | AvgPool | Dense [+ReLU] | Softmax}* -> Output.
+ * model_net.c -- host-side (plain C) planner for ANY NNoM int8 graph the importer understands
+ * (tools/import_weights_h.py): Input -> {Conv2D [+ReLU] | DW_Conv2D [+ReLU] | MaxPool | AvgPool | Dense [+ReLU] | Softmax}* -> Output,
+ * and, wired by the blob's source table, the branching graphs of model.merge / model.mergex: Add, Sub, Mult [+ReLU] over tensors of
+ * one shape (nnom_matrix.c) and Concat [+ReLU] over the channel axis (nnom_concat.c). A sequential graph keeps its two ping-pong LDS
+ * buffers; a branching one gets an LDS area per tensor, placed by liveness (first fit).
  *
  * It does for the GPU what model_compile() + the layers' build functions do in the reference (nnom.c:758-900,
  * nnom_conv2d.c:79-108, nnom_maxpool.c:80-106, nnom_dense.c:70-91): derive every tensor shape, decide where the
@@ -58,6 +61,43 @@ int ed_plan_net(const void *blob, size_t blob_bytes, ed_net_plan_t *plan, int8_t
 		return fail(err, err_cap, EDISON_E_SIZE, "model input shape out of range", 0, 0);
 	plan->n_layers = n_layers;
 	plan->in_h = h; plan->in_w = w; plan->in_c = c; plan->in_n = h * w * c;
+	/* who reads whom: the blob's source table (header word 6: its payload offset), or every layer its predecessor */
+	{
+		const int32_t tab = head[6];
+		const unsigned char *t = (const unsigned char *)payload + tab;
+		int64_t left = (int64_t)payload_bytes - tab;
+		if (tab < 0 || (tab & 3) || tab > payload_bytes)
+			return fail(err, err_cap, EDISON_E_SIZE, "source table at %d outside the %d-byte payload", tab, payload_bytes);
+		plan->branching = tab != 0;
+		for (int i = 0; i < n_layers; i++)
+		{
+			int32_t cnt = 1, idx[ED_NET_MAX_IN] = {i - 1};
+			if (tab)
+			{
+				if (left < 4) return fail(err, err_cap, EDISON_E_SIZE, "layer %d: source table truncated", i, 0);
+				memcpy(&cnt, t, 4); t += 4; left -= 4;
+				if (cnt < 1 || cnt > ED_NET_MAX_IN || left < 4 * (int64_t)cnt)
+					return fail(err, err_cap, EDISON_E_SIZE, "layer %d: %d inputs in the source table (1 to 8, inside the payload)", i, cnt);
+				memcpy(idx, t, 4 * (size_t)cnt); t += 4 * cnt; left -= 4 * cnt;
+			}
+			if (plan->n_src + 1 + cnt > ED_NET_MAX_SRC) return fail(err, err_cap, EDISON_E_SIZE, "layer %d: source table too long", i, 0);
+			plan->L[i].src_off = plan->n_src;
+			plan->src[plan->n_src++] = cnt;
+			for (int k = 0; k < cnt; k++)
+			{
+				if (idx[k] < -1 || idx[k] >= i)
+					return fail(err, err_cap, EDISON_E_SIZE, "layer %d: reads layer %d, a source must point backwards", i, idx[k]);
+				plan->src[plan->n_src++] = idx[k];
+			}
+		}
+		for (int i = 0; i + 1 < n_layers; i++)
+		{
+			int read = 0;
+			for (int j = i + 1; j < n_layers && !read; j++)
+				for (int k = 0; k < plan->src[plan->L[j].src_off]; k++) read |= plan->src[plan->L[j].src_off + 1 + k] == i;
+			if (!read) return fail(err, err_cap, EDISON_E_SIZE, "layer %d: nothing reads its output", i, 0);
+		}
+	}
 
 	/* every tensor re-aligned to 16; one seed per bias byte at most. Tensors of a well-formed blob are disjoint, so their
 	 * sizes add up to at most the payload; records that point at overlapping ranges are refused when the sum outgrows
@@ -74,8 +114,13 @@ int ed_plan_net(const void *blob, size_t blob_bytes, ed_net_plan_t *plan, int8_t
 		memcpy(&r, p + 40 + (size_t)i * 48, sizeof(r));
 		const int32_t *v = r.v;
 		ed_net_layer_t *L = &plan->L[i];
+		const int32_t *src = &plan->src[L->src_off];
+		const int n_in = src[0], s0 = src[1];
+		h = s0 < 0 ? plan->in_h : plan->L[s0].out_h; w = s0 < 0 ? plan->in_w : plan->L[s0].out_w; c = s0 < 0 ? plan->in_c : plan->L[s0].out_c;
 		L->type = v[0];
 		L->in_h = h; L->in_w = w; L->in_c = c; L->in_n = h * w * c;
+		if (n_in != 1 && !ED_NET_IS_MERGE(v[0]))
+		{ rc = fail(err, err_cap, EDISON_E_SIZE, "layer %d: %d inputs to a layer that reads one", i, n_in); break; }
 		if (v[0] == ED_NET_CONV || v[0] == ED_NET_POOL || v[0] == ED_NET_DWCONV || v[0] == ED_NET_AVGPOOL)
 		{
 			const int same = (v[8] >> 1) & 1;
@@ -186,6 +231,27 @@ int ed_plan_net(const void *blob, size_t blob_bytes, ed_net_plan_t *plan, int8_t
 			L->out_h = h; L->out_w = w; L->out_c = c;
 			plan->has_softmax = 1;
 		}
+		else if (ED_NET_IS_MERGE(v[0]))
+		{
+			/* Add / Sub / Mult: elementwise over tensors of one shape, sat8 of the 16-bit result (arm_add_q7 / arm_sub_q7 / arm_mult_q7, the
+			 * product >> 7) at shift 0, sat8((r + (1 << (shift - 1))) >> shift) otherwise (local_*_q7, nnom_local.c:1090-1145); Concat: the
+			 * inputs' channels side by side per pixel, equal channel counts only (see nnom_import.py) */
+			if (n_in < 2) { rc = fail(err, err_cap, EDISON_E_SIZE, "layer %d: a merge layer with %d input", i, n_in); break; }
+			if ((v[0] == ED_NET_SUB || v[0] == ED_NET_MULT) && n_in != 2)
+			{ rc = fail(err, err_cap, EDISON_E_NO_IMPL, "layer %d: Sub / Mult over %d inputs (the reference's loop for a third input does not compute it)", i, n_in); break; }
+			int same = 1;
+			for (int k = 1; k < n_in; k++)
+			{
+				const int s = src[1 + k];
+				same &= (s < 0 ? plan->in_h : plan->L[s].out_h) == h && (s < 0 ? plan->in_w : plan->L[s].out_w) == w && (s < 0 ? plan->in_c : plan->L[s].out_c) == c;
+			}
+			if (!same) { rc = fail(err, err_cap, EDISON_E_SIZE, "layer %d: merge inputs of unequal shape (the first has %d channels)", i, c); break; }
+			L->out_h = h; L->out_w = w; L->out_c = v[0] == ED_NET_CONCAT ? c * n_in : c;
+			L->relu = v[8] & 1; L->rs = v[7];
+			L->kh = L->kw = L->sh = L->sw = 1;
+			if (v[1] != L->out_c || v[11] != n_in || v[7] < 0 || v[7] > 15 || (v[0] == ED_NET_CONCAT && v[7] != 0))
+			{ rc = fail(err, err_cap, EDISON_E_SIZE, "layer %d: merge record inconsistent with its %d inputs", i, n_in); break; }
+		}
 		else
 		{ rc = fail(err, err_cap, EDISON_E_NO_IMPL, "layer %d: layer type %d is not built on this path", i, v[0]); break; }
 		L->out_n = L->out_h * L->out_w * L->out_c;
@@ -196,14 +262,50 @@ int ed_plan_net(const void *blob, size_t blob_bytes, ed_net_plan_t *plan, int8_t
 		{ rc = fail(err, err_cap, EDISON_E_NO_IMPL, "layer %d: activations of %d bytes do not fit the two LDS buffers", i, L->out_n); break; }
 	}
 	if (rc != EDISON_OK) { free(wbuf); free(sbuf); return rc; }
-	for (int i = 0; i < n_layers; i++)
+	int lds = 2 * max_act;
+	if (!plan->branching)
+		for (int i = 0; i < n_layers; i++)
+		{
+			plan->L[i].in_buf = (i & 1) ? max_act : 0;
+			plan->L[i].out_buf = (i & 1) ? 0 : max_act;
+		}
+	else
 	{
-		plan->L[i].in_buf = (i & 1) ? max_act : 0;
-		plan->L[i].out_buf = (i & 1) ? 0 : max_act;
+		/* one LDS area per tensor, alive from the layer that writes it to the last layer that reads it (the network input: from
+		 * the start, at offset 0; the last layer's output: to the end). First fit, lowest offset, in the order the tensors appear. */
+		int last_use[ED_NET_MAX_LAYERS + 1], off[ED_NET_MAX_LAYERS + 1], size[ED_NET_MAX_LAYERS + 1]; /* tensor t + 1: t = -1 is the input */
+		for (int t = -1; t < n_layers; t++)
+		{
+			last_use[t + 1] = t == n_layers - 1 ? n_layers : t;
+			size[t + 1] = ((t < 0 ? plan->in_n : plan->L[t].out_n) + 15) & ~15;
+			for (int j = t + 1; j < n_layers; j++)
+				for (int k = 0; k < plan->src[plan->L[j].src_off]; k++)
+					if (plan->src[plan->L[j].src_off + 1 + k] == t) last_use[t + 1] = j;
+		}
+		off[0] = 0;
+		lds = size[0];
+		for (int i = 0; i < n_layers; i++)
+		{
+			int at = 0, moved = 1;
+			while (moved) /* push past every live tensor that overlaps [at, at + size) until none does */
+			{
+				moved = 0;
+				for (int t = -1; t < i; t++)
+					if (last_use[t + 1] >= i && at < off[t + 1] + size[t + 1] && off[t + 1] < at + size[i + 1]) { at = off[t + 1] + size[t + 1]; moved = 1; }
+			}
+			off[i + 1] = at;
+			if (at + size[i + 1] > lds) lds = at + size[i + 1];
+			plan->L[i].out_buf = at;
+			const int s0 = plan->src[plan->L[i].src_off + 1];
+			plan->L[i].in_buf = off[s0 + 1];
+		}
+		if (lds > ED_NET_MAX_LDS)
+		{ free(wbuf); free(sbuf); return fail(err, err_cap, EDISON_E_NO_IMPL, "the graph's live activations need %d bytes of LDS (%d available)", lds, ED_NET_MAX_LDS); }
 	}
-	plan->logits_layer = plan->has_softmax ? n_layers - 2 : n_layers - 1;
+	plan->logits_layer = plan->has_softmax ? plan->src[plan->L[n_layers - 1].src_off + 1] : n_layers - 1;
+	if (plan->logits_layer < 0) { free(wbuf); free(sbuf); return fail(err, err_cap, EDISON_E_NO_IMPL, "Softmax of the network input", 0, 0); }
 	plan->out_n = plan->L[n_layers - 1].out_n;
-	plan->lds_bytes = 2 * max_act;
+	plan->lds_bytes = lds;
 	plan->acts_bytes = acts;
 	plan->weights_bytes = (w_used + 15) & ~15;
 	plan->n_seeds = s_used;

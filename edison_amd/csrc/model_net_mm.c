@@ -24,6 +24,29 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 	*seeds = NULL;
 	if (blob_bytes < 40) return EDISON_E_SIZE;
 	const int n_layers = plan->n_layers;
+	/* A branching graph (a source table: Add, Sub, Mult, Concat, hooks from earlier layers): who reads each tensor. A sequential
+	 * graph takes none of the branches below that test `br`, so its plan is what it always was. */
+	const int br = plan->branching;
+#define SRC_N(j) (plan->src[plan->L[j].src_off])
+#define SRC(j, k) (plan->src[plan->L[j].src_off + 1 + (k)])
+	int nread[ED_NET_MAX_LAYERS], only[ED_NET_MAX_LAYERS], lastr[ED_NET_MAX_LAYERS]; /* reads of tensor t, its reader if there is one only, its last reader */
+	int cons[ED_NET_MAX_LAYERS];  /* the reader in whose LDS layout tensor t is stored; n_layers: compact */
+	int held[ED_NET_MAX_LAYERS];  /* 1: tensor t lives in a held area, not in the ping-pong region */
+	int hoff[ED_NET_MAX_LAYERS], timg[ED_NET_MAX_LAYERS], loc[ED_NET_MAX_LAYERS + 1]; /* held offset (per input), bytes per image, place in the slice */
+	int spass[ED_NET_MAX_LAYERS]; /* the pass that stores tensor t: t itself, or t - 1 for the output of a MaxPool fused into the convolution in front */
+	int hold_img = 0, n_msrc = 0;
+	loc[0] = 0;
+	for (int t = 0; t < n_layers; t++) { nread[t] = 0; only[t] = -1; lastr[t] = t; cons[t] = t + 1 < n_layers ? t + 1 : n_layers; spass[t] = t; held[t] = 0; hoff[t] = 0; timg[t] = 0; }
+	for (int j = 0; j < n_layers && br; j++)
+		for (int k = 0; k < SRC_N(j); k++)
+		{
+			const int t = SRC(j, k);
+			if (t < 0) { if (j != 0 || SRC_N(j) != 1) return EDISON_OK; continue; } /* the network input: layer 0 alone reads it on this path */
+			only[t] = nread[t] == 0 || only[t] == j ? j : -2;
+			nread[t]++;
+			lastr[t] = j;
+		}
+	if (br && SRC(0, 0) != -1) return EDISON_OK;
 	const int8_t *payload = (const int8_t *)(p + 40 + (size_t)n_layers * 48);
 
 	/* pass 1: shapes, counts */
@@ -133,9 +156,11 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 		if (Q->pad_h || Q->pad_w || Q->check_taps || Q->kh != Q->sh || Q->kw != Q->sw || (Q->kh * Q->kw != 2 && Q->kh * Q->kw != 4)) continue;
 		if (Q->out_h * Q->kh > C->out_h || Q->out_w * Q->kw > C->out_w) continue;
 		if (mm->L[i].toep && (Q->kw != 1 || Q->out_w != C->out_w)) continue; /* x lives in the GEMM's rows there: only windows along y fuse */
+		if (br && !(nread[i] == 1 && only[i] == i + 1 && SRC_N(i + 1) == 1)) continue; /* something else reads the unpooled tensor */
 		mm->L[i].pool_h = Q->kh; mm->L[i].pool_w = Q->kw;
 		mm->L[i + 1].skip = 1;
 		mm->L[i + 1].in_img = 0; /* the unpooled tensor never exists */
+		spass[i + 1] = i;        /* the pooled one is stored while pass i still reads its inputs */
 	}
 
 	/* LDS banks. A B fragment is 16 bytes per lane and neighbouring lanes are neighbouring pixels; the epilogue of the layer in
@@ -148,7 +173,7 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 	 * not for Dense (one column per image: nothing to conflict with). EDISON_NET_NO_PIXEL_GAP=1: A/B knob. */
 	{
 		const char *env = getenv("EDISON_NET_NO_PIXEL_GAP");
-		for (int i = 0; i < n_layers && !(env && atoi(env)); i++)
+		for (int i = 0; i < n_layers && !(env && atoi(env)) && !br; i++) /* (a branching graph: the producer is not the layer in front) */
 		{
 			const ed_net_layer_t *L = &plan->L[i];
 			ed_mm_layer_t *M = &mm->L[i];
@@ -164,6 +189,57 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 		}
 	}
 
+	/* A branching graph stores a tensor ONCE, in the layout of the one reader that demands one: a matrix-core convolution wants its zero
+	 * border (and reads an expanded copy from there), the pool / DW / AvgPool / Dense / Softmax passes a compact image, the merge passes
+	 * read any layout through msrc[]. Two readers that demand different layouts (an inception stem: a 1x1 and a padded 3x3 convolution)
+	 * keep the graph on the layer-by-layer kernel. */
+	for (int t = 0; t < n_layers && br; t++)
+	{
+		int first = -1, conv = -1, merge = -1;
+		for (int j = t + 1; j < n_layers; j++)
+			for (int k = 0; k < SRC_N(j); k++)
+			{
+				if (SRC(j, k) != t) continue;
+				if (ED_NET_IS_MERGE(plan->L[j].type)) { if (merge < 0) merge = j; continue; }
+				if (first < 0) first = j;
+				if (conv < 0 && plan->L[j].type == ED_NET_CONV) conv = j;
+			}
+		const int pick = conv >= 0 ? conv : first;
+		cons[t] = pick >= 0 ? pick : merge >= 0 ? merge : n_layers;
+		for (int j = t + 1; j < n_layers && pick >= 0; j++)
+		{
+			if (ED_NET_IS_MERGE(plan->L[j].type) || SRC(j, 0) != t || mm->L[j].skip) continue;
+			const ed_mm_layer_t *A = &mm->L[pick], *B = &mm->L[j];
+			const int pa = plan->L[pick].type == ED_NET_CONV ? A->pp : plan->L[t].out_c, pb = plan->L[j].type == ED_NET_CONV ? B->pp : plan->L[t].out_c;
+			if (A->in_hp != B->in_hp || A->in_wp != B->in_wp || A->in_py != B->in_py || A->in_px != B->in_px || A->in_img != B->in_img || pa != pb) return EDISON_OK;
+		}
+	}
+	/* which tensors are held: every one that something else than the very next pass reads (or that is read twice); then a place for
+	 * each in the held area by liveness, first fit, in bytes per input (the per-wave batch scales them). Tensor t lives from the pass
+	 * that stores it, spass[t], to its last reader, both included: a pass reads its inputs while it stores its output, so an earlier
+	 * tensor u is in t's way while lastr[u] >= spass[t] (stored tensors have distinct, increasing spass[]) */
+	for (int t = 0; t < n_layers && br; t++)
+	{
+		if (mm->L[t].pool_h > 0) continue;               /* never stored: its fused MaxPool's output is */
+		int next = t + 1;
+		while (next < n_layers && mm->L[next].skip) next++;
+		held[t] = nread[t] > 0 && !(nread[t] == 1 && only[t] == next);
+		timg[t] = cons[t] < n_layers ? mm->L[cons[t]].in_img : up16(plan->L[t].out_n) + 16;
+	}
+	for (int t = 0; t < n_layers && br; t++)
+	{
+		if (!held[t]) continue;
+		int at = 0, moved = 1;
+		while (moved)
+		{
+			moved = 0;
+			for (int u = 0; u < t; u++)
+				if (held[u] && lastr[u] >= spass[t] && at < hoff[u] + timg[u] && hoff[u] < at + timg[t]) { at = hoff[u] + timg[u]; moved = 1; }
+		}
+		hoff[t] = at;
+		if (at + timg[t] > hold_img) hold_img = at + timg[t];
+	}
+
 	/* column tables: (B offset, output offset) of every stored pixel, for the layers that fit ED_MM_MAX_COLS together */
 	int n_cols = 0;
 	for (int i = 0; i < n_layers; i++)
@@ -172,7 +248,7 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 		ed_mm_layer_t *M = &mm->L[i];
 		M->col_off = -1;
 		if (!M->mm) continue;
-		const int dense = L->type == ED_NET_DENSE, fused = M->pool_h > 0, nx = fused ? i + 2 : i + 1;
+		const int dense = L->type == ED_NET_DENSE, fused = M->pool_h > 0, nx = cons[fused ? i + 1 : i];
 		const int st_h = dense ? 1 : (fused ? plan->L[i + 1].out_h : L->out_h), st_w = dense || M->toep ? 1 : (fused ? plan->L[i + 1].out_w : L->out_w);
 		if (n_cols + st_h * st_w > ED_MM_MAX_COLS) continue;
 		const int ph = fused ? M->pool_h : 1, pw = fused ? M->pool_w : 1, sh = dense ? 1 : L->sh;
@@ -239,9 +315,19 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 	{
 		if (mm->L[i].x_img > max_x) max_x = mm->L[i].x_img;
 		if (mm->L[i].skip) continue;
-		const int nx = mm->L[i].pool_h > 0 ? i + 2 : i + 1;
+		const int nx = cons[mm->L[i].pool_h > 0 ? i + 1 : i];
 		const int st_h = mm->L[i].pool_h > 0 ? plan->L[i + 1].out_h : plan->L[i].out_h, st_w = mm->L[i].pool_h > 0 ? plan->L[i + 1].out_w : plan->L[i].out_w;
 		const int out_img = nx < n_layers ? mm->L[nx].in_img : up16(st_h * st_w * plan->L[i].out_c) + 16; /* the last layer's output is compact */
+		if (br)
+		{
+			/* of a pass's inputs at most one is in the region (the pass in front stored it there), the others are held; so may its output be */
+			int in_sz = i == 0 ? mm->L[0].in_img : 0;
+			for (int k = 0; k < SRC_N(i); k++)
+				if (SRC(i, k) >= 0 && !held[SRC(i, k)]) in_sz = timg[SRC(i, k)];
+			const int pair = in_sz + (held[mm->L[i].pool_h > 0 ? i + 1 : i] ? 0 : out_img);
+			if (pair > max_pair) max_pair = pair;
+			continue;
+		}
 		if (mm->L[i].in_img + out_img > max_pair) max_pair = mm->L[i].in_img + out_img;
 	}
 	const int max_img = (max_pair / 2 + 15) & ~15; /* half of the region per input */
@@ -264,7 +350,7 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 		for (int b = 4; b >= 1 && !batch; b >>= 1)
 		{
 			if (force_b > 0 && b != force_b) continue;
-			const int64_t per_wave = 2 * (int64_t)b * max_img + (int64_t)b * up16(max_x);
+			const int64_t per_wave = 2 * (int64_t)b * max_img + (int64_t)b * up16(max_x) + (int64_t)b * hold_img;
 			int64_t w = (lds_cap - tbl - fl) / per_wave;
 			if (w > 12) w = 12; /* the kernel is built for 768 threads: 168 VGPRs a wave */
 			if (w >= (min_w > 0 ? min_w : (b > 1 ? 8 : 4))) { batch = b; waves = (int)w; frag_lds = (int)fl; frag_mode = mode; }
@@ -275,10 +361,11 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 	mm->waves = waves;
 	mm->buf_bytes = batch * max_img;
 	mm->x_bytes = batch * up16(max_x);
+	mm->hold_bytes = batch * hold_img;
 	mm->frag_lds = frag_lds;
 	mm->frag_mode = frag_mode;
 	mm->tbl_bytes = tbl;
-	mm->lds_bytes = tbl + frag_lds + waves * (2 * mm->buf_bytes + mm->x_bytes);
+	mm->lds_bytes = tbl + frag_lds + waves * (2 * mm->buf_bytes + mm->x_bytes + mm->hold_bytes);
 	mm->frag_bytes = (int32_t)frag_bytes;
 	mm->n_seeds = n_seeds;
 	mm->n_koff = n_koff;
@@ -317,14 +404,14 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 		frag_bytes = fexact;
 		if (frag_mode == 2) frag_lds = (int)fexact;
 		{
-			const int64_t per_wave = 2 * (int64_t)batch * max_img + (int64_t)batch * up16(max_x);
+			const int64_t per_wave = 2 * (int64_t)batch * max_img + (int64_t)batch * up16(max_x) + (int64_t)batch * hold_img;
 			int64_t w = (lds_cap - tbl - frag_lds) / per_wave;
 			if (w > 12) w = 12;
 			if (w > waves) waves = (int)w;
 		}
 		mm->waves = waves;
 		mm->frag_lds = frag_lds;
-		mm->lds_bytes = tbl + frag_lds + waves * (2 * mm->buf_bytes + mm->x_bytes);
+		mm->lds_bytes = tbl + frag_lds + waves * (2 * mm->buf_bytes + mm->x_bytes + mm->hold_bytes);
 		mm->frag_bytes = (int32_t)frag_bytes;
 	}
 
@@ -438,15 +525,47 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 		const ed_mm_layer_t *M = &mm->L[i];
 		if (M->skip) continue; /* fused MaxPool: nothing runs for it */
 		int ohp, owp, opy, opx, oimg, opp; /* the consumer's layout = where this layer's epilogue stores */
-		const int fused = M->pool_h > 0, nx = fused ? i + 2 : i + 1;          /* the consumer */
+		const int fused = M->pool_h > 0, st = fused ? i + 1 : i, nx = cons[st]; /* the tensor this pass stores; the reader whose layout it gets */
 		const int st_h = fused ? plan->L[i + 1].out_h : L->out_h, st_w = fused ? plan->L[i + 1].out_w : L->out_w; /* what is stored */
 		if (nx < n_layers) { ohp = mm->L[nx].in_hp; owp = mm->L[nx].in_wp; opy = mm->L[nx].in_py; opx = mm->L[nx].in_px; oimg = mm->L[nx].in_img; opp = plan->L[nx].type == ED_NET_CONV ? mm->L[nx].pp : L->out_c; }
 		else { ohp = st_h; owp = st_w; opy = 0; opx = 0; oimg = up16(st_h * st_w * L->out_c) + 16; opp = L->out_c; }
 		const int64_t last_store = ((int64_t)(st_h - 1 + opy) * owp + (st_w - 1 + opx)) * opp + L->out_c;
 		/* input at one end of the region, output at the other */
-		const int o_off = in_off == 0 ? region - batch * oimg : 0;
-		int bad = last_store > oimg || ohp < st_h + opy || owp < st_w + opx || batch * (M->in_img + oimg) > region || o_off < 0 || (o_off & 15) || (in_off & 15);
-		bad |= in_off + batch * M->in_img > region || (in_off == 0 ? batch * M->in_img > o_off : batch * oimg > in_off);
+		const int hold0 = region + mm->x_bytes; /* the held areas lie behind the expansion buffer */
+		const int o_off = held[st] ? hold0 + batch * hoff[st] : in_off == 0 ? region - batch * oimg : 0;
+		int bad = last_store > oimg || ohp < st_h + opy || owp < st_w + opx || o_off < 0 || (o_off & 15) || (in_off & 15);
+		int pin = in_off; /* where this pass reads its (first) input */
+		if (!br)
+		{
+			bad |= batch * (M->in_img + oimg) > region;
+			bad |= in_off + batch * M->in_img > region || (in_off == 0 ? batch * M->in_img > o_off : batch * oimg > in_off);
+		}
+		else
+		{
+			/* every input where the pass that stored it left it; the one that lies in the region must not meet the output there */
+			pin = loc[SRC(i, 0) + 1];
+			bad |= held[st] ? (oimg != timg[st] || batch * (hoff[st] + oimg) > mm->hold_bytes) : batch * oimg > region;
+			for (int k = 0; k < SRC_N(i); k++)
+			{
+				const int t = SRC(i, k), at = loc[t + 1], sz = batch * (t < 0 ? M->in_img : timg[t]);
+				if (t >= 0 && held[t]) { bad |= at < hold0 || at + sz > hold0 + mm->hold_bytes; continue; }
+				bad |= at != in_off || at + sz > region; /* the region holds the tensor stored last, nothing older */
+				if (!held[st]) bad |= at == 0 ? sz > o_off : batch * oimg > at;
+			}
+			bad |= !ED_NET_IS_MERGE(L->type) && SRC(i, 0) >= 0 && timg[SRC(i, 0)] != M->in_img;
+			/* the output against everything it could destroy, whatever placed the two: every input of this pass wherever it lies, and
+			 * every held tensor stored earlier that this pass or a later one still reads */
+			for (int k = 0; k < SRC_N(i); k++)
+			{
+				const int t = SRC(i, k), at = loc[t + 1], sz = batch * (t < 0 ? M->in_img : timg[t]);
+				bad |= at < o_off + batch * oimg && o_off < at + sz;
+			}
+			for (int u = 0; u < st && held[st]; u++)
+				if (held[u] && spass[u] < i && lastr[u] >= i)
+					bad |= loc[u + 1] < o_off + batch * oimg && o_off < loc[u + 1] + batch * timg[u];
+		}
+		loc[st + 1] = o_off;
+		if (i == 0) loc[0] = 0;
 		if (M->mm)
 		{
 			const int dense = L->type == ED_NET_DENSE;
@@ -487,9 +606,30 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 		ed_mm_run_t *R = &mm->R[i];
 		const int dense = L->type == ED_NET_DENSE;
 		R->kind = M->mm ? ED_RUN_MM : L->type == ED_NET_POOL ? ((L->in_c & 3) == 0 ? ED_RUN_POOL4 : ED_RUN_POOL1)
-		          : L->type == ED_NET_DWCONV ? ED_RUN_DW : L->type == ED_NET_AVGPOOL ? ED_RUN_AVG : ED_RUN_SOFTMAX;
+		          : L->type == ED_NET_DWCONV ? ED_RUN_DW : L->type == ED_NET_AVGPOOL ? ED_RUN_AVG
+		          : L->type == ED_NET_CONCAT ? ED_RUN_CAT : ED_NET_IS_MERGE(L->type) ? ED_RUN_MERGE : ED_RUN_SOFTMAX;
+		int msrc0 = 0;
+		if (R->kind == ED_RUN_MERGE || R->kind == ED_RUN_CAT)
+		{
+			/* one msrc entry per input: where its images start in the slice, and the layout its own reader gave it. The merge pass
+			 * moves 16-bit words (dwords when C % 4 == 0), like the DW / AvgPool passes: every pitch must keep them aligned */
+			if (n_msrc + SRC_N(i) > ED_MM_MAX_MSRC || (R->kind == ED_RUN_MERGE && (L->out_c & 1))) { free(fb); free(sb); return EDISON_OK; }
+			const int al = R->kind == ED_RUN_CAT ? 1 : (L->in_c & 3) == 0 ? 4 : 2;
+			msrc0 = n_msrc;
+			for (int k = 0; k < SRC_N(i); k++)
+			{
+				const int t = SRC(i, k), cn = t < 0 ? 0 : cons[t];
+				if (t < 0) { free(fb); free(sb); return EDISON_OK; }
+				int32_t *e = &mm->msrc[5 * n_msrc++];
+				const int spp = cn < n_layers ? (plan->L[cn].type == ED_NET_CONV ? mm->L[cn].pp : L->in_c) : L->in_c;
+				const int swp = cn < n_layers ? mm->L[cn].in_wp : L->in_w, spy = cn < n_layers ? mm->L[cn].in_py : 0, spx = cn < n_layers ? mm->L[cn].in_px : 0;
+				e[0] = loc[t + 1]; e[1] = timg[t]; e[2] = (spy * swp + spx) * spp; e[3] = swp * spp; e[4] = spp;
+				const int64_t last_read = (int64_t)e[2] + (int64_t)(L->in_h - 1) * e[3] + (int64_t)(L->in_w - 1) * e[4] + ((L->in_c + al - 1) / al) * al;
+				if (last_read > e[1] || (e[2] % al) || (e[3] % al) || (e[4] % al) || (e[0] & 15) || (e[1] & 15)) { free(fb); free(sb); return EDISON_OK; }
+			}
+		}
 		/* the two VALU layers store 16-bit words (dwords when C % 4 == 0) at the consumer's pixel pitch */
-		if ((R->kind == ED_RUN_DW || R->kind == ED_RUN_AVG) && ((opp & 1) || ((L->in_c & 3) == 0 && (opp & 3)))) { free(fb); free(sb); return EDISON_OK; }
+		if ((R->kind == ED_RUN_DW || R->kind == ED_RUN_AVG || R->kind == ED_RUN_MERGE) && ((opp & 1) || ((L->in_c & 3) == 0 && (opp & 3)))) { free(fb); free(sb); return EDISON_OK; }
 		R->zero_border = ohp != st_h || owp != st_w;
 		R->in_img = M->in_img; R->o_img = oimg;
 		R->oc_pitch = opp; R->o_origin = (opy * owp + opx) * opp; R->o_row = owp * opp;
@@ -509,8 +649,13 @@ int ed_plan_net_mm(const void *blob, size_t blob_bytes, const ed_net_plan_t *pla
 		 * the layer's own weights and seeds. */
 		if (M->mm && L->rs >= 0 && L->rs <= 31 && (L->rs >= 8 || (acc_bound[i] << (8 - L->rs)) < ((int64_t)1 << 31))) R->rs |= ED_RUN_RS_HI;
 		R->in_n = L->in_n;
-		R->in_off = in_off; R->o_off = o_off;
-		in_off = o_off; /* the consumer reads where this layer stored */
+		R->in_off = pin; R->o_off = o_off;
+		if (R->kind == ED_RUN_MERGE || R->kind == ED_RUN_CAT)
+		{
+			R->n_ks = SRC_N(i); R->koff_off = msrc0; R->ph = L->type; R->pitch_x = L->in_c;
+			R->pix_per_img = st_h * st_w; R->col_w = st_w; R->out_c = L->out_c;
+		}
+		if (!held[st]) in_off = o_off; /* the consumer reads where this layer stored */
 	}
 	*frag = fb;
 	*seeds = sb;
