@@ -141,6 +141,12 @@ typedef float ed_f2 __attribute__((ext_vector_type(2)));
 /* NOT (ed_f2)(a, b): in C++ that is a cast of the comma expression, i.e. a splat of b */
 __device__ __forceinline__ ed_f2 ed_mk2(float a, float b) { ed_f2 r; r.x = a; r.y = b; return r; }
 __device__ __forceinline__ ed_f2 ed_splat(float x) { return ed_mk2(x, x); }
+/* The (z, w) half of a 16-byte quad as a register pair of its own, and the splats of its halves. Written as ed_splat(q.w) the
+ * compiler does not see that q.w is the upper half of the aligned pair (q.z, q.w) and copies it into an even register first (one
+ * v_mov_b32 per quad); through the (code-less) asm the pair is opaque, and both splats are the packed instruction's op_sel bits. */
+__device__ __forceinline__ ed_f2 ed_hi_pair(const float4 &q) { ed_f2 r = ed_mk2(q.z, q.w); asm("" : "+v"(r)); return r; }
+__device__ __forceinline__ ed_f2 ed_splat_lo(ed_f2 p) { return __builtin_shufflevector(p, p, 0, 0); }
+__device__ __forceinline__ ed_f2 ed_splat_hi(ed_f2 p) { return __builtin_shufflevector(p, p, 1, 1); }
 __device__ __forceinline__ ed_f2 ed_fma2(ed_f2 a, ed_f2 b, ed_f2 c) { return __builtin_elementwise_fma(a, b, c); }
 
 __device__ __forceinline__ void ed_dft4_2(ed_f2 y0r, ed_f2 y0i, ed_f2 y1r, ed_f2 y1i, ed_f2 y2r, ed_f2 y2i, ed_f2 y3r, ed_f2 y3i,

@@ -165,8 +165,11 @@ __device__ __forceinline__ void ed_pair_ptrs(const ed_mfcc_args_t &a, const ed_m
 		}
 		else
 		{
-			pa = a.audio + ((int64_t)g * a.group_stride + (int64_t)i * a.frame_step);
-			pb = !haveB ? pa : (i + 1 < fpg ? pa + a.frame_step : a.audio + (int64_t)(g + 1) * a.group_stride);
+			/* B relative to A (the next group's first frame is group_stride - i frame_step further on): three scalar selects and no
+			 * branch, so both pointers stay in SGPRs and the loads keep the plain kernel's form (scalar base + lane offset) */
+			const int64_t in_group = (int64_t)i * a.frame_step;
+			pa = a.audio + ((int64_t)g * a.group_stride + in_group);
+			pb = pa + (!haveB ? (int64_t)0 : (i + 1 < fpg ? (int64_t)a.frame_step : a.group_stride - in_group));
 		}
 	}
 }
@@ -184,6 +187,12 @@ __device__ __forceinline__ void ed_pair_ptrs(const ed_mfcc_args_t &a, const ed_m
  * Across CUs the slices are static: a rank-based pool at the end of the batch (one device atomic per workgroup) levels the
  * workgroups' finishing times and buys nothing -- the board sits at its power cap and takes the recovered idle time back as
  * clock (profiles/r04_mfcc_launch_structure_notes.txt).
+ *
+ * The loop in numbers (ISA of the 2+5 product instances, plain and grouped alike; profiles/r07_mfcc_loop_overhead_audit.txt has every
+ * non-packed instruction by source line): 487 vector instructions per frame pair -- 318 packed, 32 SDWA converts, 32 DPP moves, 37 lane
+ * swaps, 18 v_sqrt_f32, 25 moves (16 transpose-1 copies, 8 pair moves of the split's lane-0 block, 1 self-swap copy), 3 v_cndmask and
+ * 11 more of __logf, 5 of the int8 path behind its wave-uniform branch, 5 fold adds, v_readfirstlane, one LDS offset. Nothing in the loop
+ * forms a global address on the VALU: loads and stores are `scalar base + lane offset computed in front of the loop`.
  */
 template <bool ALIGNED, bool PLAIN, int NLO, int NHI, bool LIST, bool WINDOW = false, bool FLAG = false>
 __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const ed_mfcc_tables_t *__restrict__ tab, const ed_mfcc_list_t *list,
@@ -278,13 +287,22 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 	/* where this lane puts its DCT input (float index into Lb2 = float2 u[16] | v[16]): rows 0/1 hold frame A's
 	 * u/v of the column's band, rows 2/3 frame B's */
 	const int l_idx = 2 * (16 * ((lane >> 4) & 1) + band) + (lane >> 5);
-	const int k0 = ED_K0(lane);
+	int k0 = ED_K0(lane);
+	asm("" : "+v"(k0)); /* opaque: under `lane == 0` the compiler otherwise folds S2 + k0 to a constant and moves it into a VGPR every pair */
 	const int k0p = (64 - k0) & 63;
 	const int pull = k0p << 2;
 	const int hi3 = lane >> 3, lo3 = lane & 7;
 	float4 *xc4 = reinterpret_cast<float4 *>(xbuf);
 	ed_f2 *S2 = reinterpret_cast<ed_f2 *>(xbuf + ED2_S_OFF);
 	if (lane < 3) S2[513 + lane] = ed_splat(0.0f);
+	/* the store's lane part, once: coefficient c of frame A (lanes 0..31) or B (32..63) lies voff4 bytes (fp32; a quarter of it for int8)
+	 * behind frame A's row, whose address is scalar arithmetic from the wave-uniform fA */
+	const int c = lane & 31;
+	const bool c_ok = c < args.n_coef;
+	const uint32_t voff4 = 4u * ((uint32_t)(lane >> 5) * (uint32_t)args.n_coef + (uint32_t)c);
+	/* u = tb + to in the even lane rows, v = tb - to in the odd ones: one FMA with this factor (exact: the product is +-to) */
+	float sgn = (lane & 16) ? -1.0f : 1.0f;
+	asm("" : "+v"(sgn));
 
 #if ED2_STAMP
 	unsigned long long ph[ED2_NPH];
@@ -333,7 +351,8 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 		const uint32_t fA = 2 * (s0 + i_cur);
 		const bool haveB = fA + 1 < n_frames;
 		/* ---- 1. draw the next pair (read behind pass 1) */
-		uint32_t drawn = 0;
+		uint32_t drawn;
+		asm volatile("" : "=v"(drawn)); /* any value: only lane 0's is read (v_readfirstlane), and lane 0 draws */
 		if (lane == 0)
 			asm volatile("ds_add_rtn_u32 %0, %1, %2" : "=v"(drawn) : "v"(queue_addr), "v"(1u) : "memory");
 
@@ -418,8 +437,8 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 			pzi_[m].x = __int_as_float(__builtin_amdgcn_ds_bpermute(pull, __float_as_int(im[7 - m].x)));
 			pzi_[m].y = __int_as_float(__builtin_amdgcn_ds_bpermute(pull, __float_as_int(im[7 - m].y)));
 		}
-		/* lane 0 is its own partner, one register further up: ONE exec-masked block of 16 v_mov_b32 (2.5 cycles each)
-		 * instead of 16 v_cndmask_b32_e64 (4.4 each) -- the empty asm keeps the compiler from if-converting it back */
+		/* lane 0 is its own partner, one register further up: ONE exec-masked block of 8 v_mov_b64 (16 dwords)
+		 * instead of 16 v_cndmask_b32_e64 (4.4 cycles each) -- the empty asm keeps the compiler from if-converting it back */
 		if (lane == 0)
 		{
 			asm volatile("");
@@ -443,7 +462,8 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 			shi[m] = ed_mk2(__builtin_amdgcn_sqrtf(e1.x), __builtin_amdgcn_sqrtf(e1.y));
 		}
 		const ed_f2 e256 = re[4] * re[4] + im[4] * im[4];
-		const ed_f2 s256 = ed_mk2(2.0f * __builtin_amdgcn_sqrtf(e256.x), 2.0f * __builtin_amdgcn_sqrtf(e256.y));
+		const ed_f2 r256 = ed_mk2(__builtin_amdgcn_sqrtf(e256.x), __builtin_amdgcn_sqrtf(e256.y));
+		const ed_f2 s256 = r256 + r256; /* 2 |Z[256]|, both frames in one packed add */
 
 		ED2_ST(6)
 		/* ---- 4. both spectra to LDS, interleaved: S2[k] = (|2X_A[k]|, |2X_B[k]|) */
@@ -453,7 +473,7 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 			S2[k0 + 64 * m] = slo[m];
 			S2[512 - k0 - 64 * m] = shi[m];
 		}
-		if (lane == 0) S2[256] = s256;
+		if (lane == 0) S2[k0 + 256] = s256;
 		ed_wave_sync();
 
 		ED2_ST(7)
@@ -470,16 +490,18 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 		for (int t = 0; t < NLO; t++)
 		{
 			const float4 sa = S4[qlo_a + 2 * t], sb = S4[qlo_b + 2 * t], w = melw4[t * 64 + lane];
+			const ed_f2 wzw = ed_hi_pair(w);
 			alo0 = ed_fma2(ed_mk2(sa.x, sa.y), ed_splat(w.x), alo0); alo1 = ed_fma2(ed_mk2(sa.z, sa.w), ed_splat(w.y), alo1);
-			alo0 = ed_fma2(ed_mk2(sb.x, sb.y), ed_splat(w.z), alo0); alo1 = ed_fma2(ed_mk2(sb.z, sb.w), ed_splat(w.w), alo1);
+			alo0 = ed_fma2(ed_mk2(sb.x, sb.y), ed_splat_lo(wzw), alo0); alo1 = ed_fma2(ed_mk2(sb.z, sb.w), ed_splat_hi(wzw), alo1);
 		}
 #pragma unroll
 		for (int t = 0; t < NHI; t++)
 		{
 			if (t % 2 == 0) __builtin_amdgcn_sched_barrier(0); /* bounds the registers this stage holds in flight */
 			const float4 sa = S4[qhi_a + 2 * t], sb = S4[qhi_b + 2 * t], w = melw4[(NLO + t) * 64 + lane];
+			const ed_f2 wzw = ed_hi_pair(w);
 			ahi0 = ed_fma2(ed_mk2(sa.x, sa.y), ed_splat(w.x), ahi0); ahi1 = ed_fma2(ed_mk2(sa.z, sa.w), ed_splat(w.y), ahi1);
-			ahi0 = ed_fma2(ed_mk2(sb.x, sb.y), ed_splat(w.z), ahi0); ahi1 = ed_fma2(ed_mk2(sb.z, sb.w), ed_splat(w.w), ahi1);
+			ahi0 = ed_fma2(ed_mk2(sb.x, sb.y), ed_splat_lo(wzw), ahi0); ahi1 = ed_fma2(ed_mk2(sb.z, sb.w), ed_splat_hi(wzw), ahi1);
 		}
 		__builtin_amdgcn_sched_barrier(0);
 		/* The four row-quarters of a band are summed with the swap instructions, and because a swap exchanges halves
@@ -488,7 +510,9 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 		 * register ends up with  row 0: band b of A,  row 1: band 31-b of A,  row 2: b of B,  row 3: 31-b of B. */
 		ED2_ST(8)
 		const ed_f2 plo = alo0 + alo1, phi = ahi0 + ahi1;
-		float t = ed_fold_rows(ed_fold_halves(plo.x, plo.y), ed_fold_halves(phi.x, phi.y));
+		float plx = plo.x, ply = plo.y, phx = phi.x, phy = phi.y;
+		asm("" : "+v"(plx), "+v"(ply), "+v"(phx), "+v"(phy)); /* four registers of their own: the swaps below overwrite both operands */
+		float t = ed_fold_rows(ed_fold_halves(plx, ply), ed_fold_halves(phx, phy));
 		if (do_log) { asm volatile(""); t = __logf(t + log_offset); } /* the empty asm keeps this a branch (wave-uniform) */
 
 		ED2_ST(9)
@@ -507,16 +531,17 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 		{
 			const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(t), __float_as_uint(t), false, false);
 			const float tb = __uint_as_float(r[0]), to = __uint_as_float(r[1]); /* [r0 r0 r2 r2], [r1 r1 r3 r3] */
-			reinterpret_cast<float *>(Lb2)[l_idx] = (lane & 16) ? tb - to : tb + to;
+			reinterpret_cast<float *>(Lb2)[l_idx] = __builtin_fmaf(to, sgn, tb);
 		}
 		ed_wave_sync();
 		const float4 *L4 = reinterpret_cast<const float4 *>(Lb2 + 16 * (lane & 1) + 8 * (lane >> 5));
 		const float4 v0 = L4[0], v1 = L4[1], v2 = L4[2], v3 = L4[3];
 		const float4 w0 = dctl[lane], w1 = dctl[64 + lane];
+		const ed_f2 w0zw = ed_hi_pair(w0), w1zw = ed_hi_pair(w1);
 		ed_f2 d = ed_mk2(v0.x, v0.y) * ed_splat(w0.x), d1 = ed_mk2(v2.x, v2.y) * ed_splat(w1.x);
 		d = ed_fma2(ed_mk2(v0.z, v0.w), ed_splat(w0.y), d); d1 = ed_fma2(ed_mk2(v2.z, v2.w), ed_splat(w1.y), d1);
-		d = ed_fma2(ed_mk2(v1.x, v1.y), ed_splat(w0.z), d); d1 = ed_fma2(ed_mk2(v3.x, v3.y), ed_splat(w1.z), d1);
-		d = ed_fma2(ed_mk2(v1.z, v1.w), ed_splat(w0.w), d); d1 = ed_fma2(ed_mk2(v3.z, v3.w), ed_splat(w1.w), d1);
+		d = ed_fma2(ed_mk2(v1.x, v1.y), ed_splat_lo(w0zw), d); d1 = ed_fma2(ed_mk2(v3.x, v3.y), ed_splat_lo(w1zw), d1);
+		d = ed_fma2(ed_mk2(v1.z, v1.w), ed_splat_hi(w0zw), d); d1 = ed_fma2(ed_mk2(v3.z, v3.w), ed_splat_hi(w1zw), d1);
 		d = d + d1;
 		/* the two halves of the sum, again for both frames with one swap: lanes 0..31 get coefficient `lane` of
 		 * frame A, lanes 32..63 coefficient `lane - 32` of frame B */
@@ -525,8 +550,7 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 
 		ED2_ST(10)
 		/* ---- 7. store: A's and B's rows are adjacent in memory, one instruction writes both */
-		const int c = lane & 31;
-		if (c < args.n_coef && (lane < 32 || haveB))
+		if (c_ok && (lane < 32 || haveB))
 		{
 			if (LIST)
 			{
@@ -541,9 +565,14 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 			}
 			else
 			{
-				const int64_t at = (int64_t)(fA + (lane >> 5)) * args.n_coef + c;
-				if (args.mfcc) args.mfcc[at] = coef;
-				if (args.feat) args.feat[at] = (int8_t)__float2int_rn(fminf(fmaxf(coef * args.feat_scale, -128.0f), 127.0f));
+				/* frame A's row is scalar arithmetic; the store is `scalar base + 32-bit lane offset`, written as asm: from C++ the
+				 * compiler widens the loop-invariant lane offset to 64 bits in front of the loop (two registers) and adds the row to it
+				 * with a vector instruction every pair. The exec mask of the branch above applies; the "memory" clobber orders it. */
+				const int64_t rowA = (int64_t)fA * args.n_coef;
+				if (args.mfcc)
+					asm volatile("global_store_dword %0, %1, %2" :: "v"(voff4), "v"(coef), "s"(args.mfcc + rowA) : "memory");
+				if (args.feat)
+					asm volatile("global_store_byte %0, %1, %2" :: "v"(voff4 >> 2), "v"(__float2int_rn(fminf(fmaxf(coef * args.feat_scale, -128.0f), 127.0f))), "s"(args.feat + rowA) : "memory");
 			}
 		}
 		if (FLAG)
@@ -556,7 +585,7 @@ __device__ __forceinline__ void ed_mfcc2_body(const ed_mfcc_args_t &args, const 
 			for (int o = 16; o >= 1; o >>= 1) s += __shfl_xor(s, o);
 			const float y = coef * args.feat_scale;
 			const float delta = ED_EXACT_K * 0x1p-24f * (__builtin_amdgcn_sqrtf(s) * (1.0f / 32.0f)) * fabsf(args.feat_scale);
-			const bool near = c < args.n_coef && (lane < 32 || haveB) && y >= -128.0f && y < 127.0f && fabsf(y - floorf(y) - 0.5f) < delta;
+			const bool near = c_ok && (lane < 32 || haveB) && y >= -128.0f && y < 127.0f && fabsf(y - floorf(y) - 0.5f) < delta;
 			const uint64_t m = __ballot(near);
 			if (m)
 			{
