@@ -1,0 +1,83 @@
+/*
+ * edison_stream_core.h -- the sliding-window core that edison_stream_geom.hip and edison_stream_float.hip run on (edison_stream_core.hip,
+ * DESIGN.md section 12a): the state a continuous stream keeps between pushes and everything that does not depend on which MFCC and
+ * which network fill the window. An owner holds one core by value, launches its features and its network between begin_push and
+ * finish_push, and lays out the front of the output block. Not part of the public ABI.
+ *
+ * Two sliding buffers `slots` pushes long,
+ *     d_audio  [T + slots * chunk * hop] int16                   T = `tail` samples of history, then the new samples
+ *     d_feat   [F - 1 + slots * chunk][nm] of feat_elem bytes    F - 1 rows of history, then the new rows
+ * whose history starts at frame `pos` (samples pos * hop, rows pos): a push appends behind it and advances pos by its frames; window i
+ * of the push is rows pos + i .. pos + i + F - 1, read in place by the owner's network kernel. When the next push would run past the
+ * end, the shift kernel first moves the history back to the front.
+ */
+#ifndef EDISON_STREAM_CORE_H
+#define EDISON_STREAM_CORE_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "edison_ctx.h"
+#include "edison_fsm_core.h"
+
+#define EDSG_FILTER_MAX_OUT 256                       /* classes the filter kernel serves: one lane each in one workgroup */
+#define ED_STREAM_CORE_SLOTS 8                        /* pushes of room in the sliding buffers ...                         */
+#define ED_STREAM_CORE_SLOTS_BYTES ((size_t)64 << 20) /* ... while that many pushes of samples stay within 64 MB, else one */
+#define ED_STREAM_CORE_SLACK 64                       /* bytes allocated behind d_audio and behind d_feat                  */
+#define ED_STREAM_CORE_ALIGN 16                       /* alignment of the parts of the output block                        */
+
+static inline size_t ed_stream_core_align(size_t off) { return (off + (ED_STREAM_CORE_ALIGN - 1)) & ~(size_t)(ED_STREAM_CORE_ALIGN - 1); }
+
+struct ed_stream_core
+{
+	edison_ctx *ctx;
+	const char *who;               /* the owner's message prefix: "stream_geom", "stream_float" */
+	int feat_elem, out_elem;       /* bytes per feature element and per network output: 1 (the int8 graph) or 4 (the float network) */
+	int F, nm, hop, tail, chunk;   /* frames per window, coefficients per row, frame_step, T history samples, frames per push */
+	int n_out, filter, fsm;
+	double alpha, one_minus_alpha, threshold;
+	ed_fsm_roles_t roles;
+	uint32_t dt_us;
+	int slots, pos;                /* buffers of `slots` pushes; the history starts at frame pos */
+	int16_t *d_audio;
+	unsigned char *d_feat;
+	/* every output of a push in one block (device d_out, pinned h_out), so that a host push downloads once: the owner's in front */
+	unsigned char *d_out, *h_out;
+	size_t off_filt, off_likely, off_spotted, off_states, off_fsm, out_bytes;
+	int16_t *h_in;                 /* pinned [chunk * hop]: the host push's upload */
+	float *d_state;                /* [n_out] the filter state */
+	edison_fsm *d_fsm;
+	hipStream_t own;               /* host pushes run here */
+	hipEvent_t ev;
+	hipStream_t q_last;            /* where the last unsynchronised work on the stream's state went (device pushes: the caller's stream) */
+	int q_pending;
+	int last_n, last_staged;       /* frames of the last push; 1: its outputs are in h_out already (host push) */
+	int64_t frames_seen;
+};
+
+/* the options both public option structs carry */
+struct ed_stream_core_opts { int chunk_frames, filter, fsm; double filter_alpha, true_threshold; };
+
+/* create: the option checks that need no network, before the owner allocates; then, on a zeroed core for geometry g with F frames per
+ * window: the fields, hipSetDevice, the HIP stream, the event, every buffer (`front_bytes` of the owner's outputs lead the block) and a
+ * reset. free waits for the stream's work and frees whatever create got, also after it failed. */
+int ed_stream_core_check_opts(edison_ctx *ctx, const char *who, const edison_kws_geom *g, const ed_stream_core_opts *o);
+int ed_stream_core_create(ed_stream_core *c, edison_ctx *ctx, const char *who, int feat_elem, int out_elem, const edison_kws_geom *g, int F,
+                          int n_out, const ed_stream_core_opts *o, size_t front_bytes);
+void ed_stream_core_free(ed_stream_core *c);
+
+/* A push of n frames on q (host = 1: host samples, q = c->own; host = 0: device samples, q = the context's stream):
+ *   begin_push   waits for work left on another HIP stream, shifts the history when the push would not fit, uploads the samples to
+ *                d_audio + pos * hop + tail (the host's through h_in); the owner's feature rows and network follow
+ *   finish_push  where the stream has a filter: the filter (+ edisonFSM) over fin[n][n_out] (int8 for out_elem 1, float for 4) into the
+ *                block; pos += n; host: one download of the block to h_out and one wait; what the getters need to know of this push */
+int ed_stream_core_begin_push(ed_stream_core *c, hipStream_t q, const int16_t *samples, int n, int host);
+int ed_stream_core_finish_push(ed_stream_core *c, hipStream_t q, const void *fin, int n, int host);
+
+/* c = NULL: EDISON_E_ARGUMENT. The getters copy the last push's outputs (host = 1: host pointers, synchronous; host = 0: device
+ * pointers, ordered on the context's stream; NULL: not copied). */
+int ed_stream_core_reset(ed_stream_core *c);
+int ed_stream_core_filtered(ed_stream_core *c, float *filt, int32_t *likely, int32_t *spotted, int host);
+int ed_stream_core_fsm(ed_stream_core *c, edison_fsm *fsm, int32_t *states, int host);
+
+#endif

@@ -1,0 +1,303 @@
+/*
+ * edison_stream_core.hip -- the sliding-window core of the any-geometry streams (edison_stream_core.h): the two
+ * state kernels, and the host logic around them that edison_stream_geom.hip and edison_stream_float.hip share.
+ */
+#include <math.h>
+#include <string.h>
+
+#include "edison_stream_core.h"
+
+/* the state machine behind the filter; fsm = NULL: none */
+struct edsg_fsm_stage_t
+{
+	edison_fsm *fsm;      /* device memory, read and written                       */
+	int32_t *states;      /* [n] out: the state after each inference               */
+	edison_fsm *copy;     /* out: the machine after the push (the host's view)     */
+	uint32_t dt_us;
+	ed_fsm_roles_t roles;
+};
+
+/* The newest `tail` samples from audio + a_src and `feat_bytes` history bytes from feat + f_src to the front of their buffers. The
+ * destination lies BELOW the source and may overlap it: in rounds of 256 elements every lane reads, the workgroup waits, every lane
+ * writes. A write to element j clobbers source element j - src < j, which this round or an earlier one has already read. */
+__global__ __launch_bounds__(256) void ed_stream_geom_shift_kernel(int16_t *audio, int64_t a_src, int tail, int8_t *feat, int64_t f_src,
+                                                                   int feat_bytes)
+{
+	const int t = threadIdx.x;
+	for (int base = 0; base < tail; base += 256)
+	{
+		const int j = base + t;
+		const int16_t v = j < tail ? audio[a_src + j] : (int16_t)0;
+		__syncthreads();
+		if (j < tail) audio[j] = v;
+		__syncthreads();
+	}
+	for (int base = 0; base < feat_bytes; base += 256)
+	{
+		const int j = base + t;
+		const int8_t v = j < feat_bytes ? feat[f_src + j] : (int8_t)0;
+		__syncthreads();
+		if (j < feat_bytes) feat[j] = v;
+		__syncthreads();
+	}
+}
+
+/*
+ * The firmware's post-processing (app.c:332-356) over n_out classes, for the n inferences of a push:
+ *   state[c] = (float)(alpha * (double)state[c] + (1 - alpha) * (double)x[c])   product and sum rounded separately, no contraction
+ *   likely = first maximum of the state row, spotted = likely if that maximum > threshold, else -1
+ * The recurrence is sequential in time; classes run on lanes, the per-frame maximum afterwards on frames. One workgroup.
+ * T = int8_t: the int8 graph's softmax / logits (edison_stream_geom.hip); T = float: the float network's probabilities
+ * (edison_stream_float.hip). (double)x is exact for both.
+ */
+template <class T>
+__global__ __launch_bounds__(256) void ed_stream_geom_filter_kernel(const T *x, int n, int n_out, double alpha, double one_minus_alpha,
+                                                                    double threshold, float *state, float *filt, int32_t *likely,
+                                                                    int32_t *spotted, edsg_fsm_stage_t fs)
+{
+	const int t = threadIdx.x;
+	if (t < n_out)
+	{
+		float y = state[t];
+		for (int i = 0; i < n; i++)
+		{
+			/* as ed_stream_filter_kernel: the compiler's default contraction would fuse these into one v_fma_f64, a different double in
+			 * the last place (the Cortex-M4 rounds each operation) */
+#pragma clang fp contract(off)
+			const double a = alpha * (double)y;
+			const double b = one_minus_alpha * (double)x[(size_t)i * n_out + t];
+			y = (float)(a + b);
+			filt[(size_t)i * n_out + t] = y;
+		}
+		state[t] = y;
+	}
+	__syncthreads();
+	for (int i = t; i < n; i += 256)
+	{
+		const float *row = filt + (size_t)i * n_out;
+		float best = row[0];
+		int idx = 0;
+		for (int c = 1; c < n_out; c++)
+			if (best < row[c]) { best = row[c]; idx = c; }
+		likely[i] = idx;
+		spotted[i] = ((double)best > threshold) ? idx : -1;
+	}
+	if (!fs.fsm) return;
+	__syncthreads();
+	if (t == 0)
+	{
+		edison_fsm m = *fs.fsm;
+		for (int i = 0; i < n; i++)
+			fs.states[i] = ed_fsm_step_core(&m, spotted[i] >= 0, (uint32_t)likely[i], fs.dt_us, &fs.roles);
+		*fs.fsm = m;
+		if (fs.copy) *fs.copy = m;
+	}
+}
+
+/* `code` with "<who>: <what>" in ctx->err */
+static int core_err(edison_ctx *ctx, const char *who, int code, const char *what)
+{
+	snprintf(ctx->err, sizeof(ctx->err), "%s: %s", who, what);
+	return code;
+}
+
+/* Work the stream left unsynchronised on another HIP stream must be behind us before q touches the stream's state. */
+static int order_after(ed_stream_core *c, hipStream_t q)
+{
+	if (!c->q_pending || c->q_last == q) return EDISON_OK;
+	if (hipEventRecord(c->ev, c->q_last) == hipSuccess) ED_HIP(c->ctx, hipStreamWaitEvent(q, c->ev, 0));
+	else (void)hipGetLastError(); /* the caller destroyed that stream (which drains it) */
+	c->q_pending = 0;
+	return EDISON_OK;
+}
+
+/* Before a push of n frames: the history to the front when the push would run past the end of the buffers. */
+static int make_room(ed_stream_core *c, hipStream_t q, int n)
+{
+	if (c->pos + n <= c->slots * c->chunk || c->pos == 0) return EDISON_OK;
+	hipLaunchKernelGGL(ed_stream_geom_shift_kernel, dim3(1), dim3(256), 0, q, c->d_audio, (int64_t)c->pos * c->hop, c->tail, (int8_t *)c->d_feat,
+	                   (int64_t)c->pos * c->nm * c->feat_elem, c->feat_elem * (c->F - 1) * c->nm);
+	c->pos = 0;
+	return hipGetLastError() == hipSuccess ? EDISON_OK : core_err(c->ctx, c->who, EDISON_E_RUNTIME, "shift launch failed");
+}
+
+int ed_stream_core_check_opts(edison_ctx *ctx, const char *who, const edison_kws_geom *g, const ed_stream_core_opts *o)
+{
+	if (o->chunk_frames < 1) return core_err(ctx, who, EDISON_E_ARGUMENT, "chunk_frames >= 1");
+	/* positions and sample counts are ints in places (pos * hop, kernel arguments): as edison_stream_create_ex */
+	if ((int64_t)o->chunk_frames * g->frame_step >= ((int64_t)1 << 30))
+		return core_err(ctx, who, EDISON_E_SIZE, "chunk_frames x frame_step must stay below 2^30 samples per push");
+	if (o->fsm && !o->filter) return core_err(ctx, who, EDISON_E_ARGUMENT, "the state machine (fsm) works on the filtered outputs: filter = 1 too");
+	if (o->filter && !(o->filter_alpha >= 0.0 && o->filter_alpha <= 1.0))
+		return core_err(ctx, who, EDISON_E_ARGUMENT, "filter_alpha must be within [0, 1]");
+	return EDISON_OK;
+}
+
+int ed_stream_core_create(ed_stream_core *c, edison_ctx *ctx, const char *who, int feat_elem, int out_elem, const edison_kws_geom *g, int F,
+                          int n_out, const ed_stream_core_opts *o, size_t front_bytes)
+{
+	c->ctx = ctx; c->who = who; c->feat_elem = feat_elem; c->out_elem = out_elem;
+	c->F = F; c->nm = g->num_mfcc; c->hop = g->frame_step; c->chunk = o->chunk_frames;
+	c->tail = g->frame_len > g->frame_step ? g->frame_len - g->frame_step : 0;
+	c->n_out = n_out;
+	c->filter = o->filter ? 1 : 0; c->fsm = o->fsm ? 1 : 0;
+	c->alpha = o->filter_alpha;
+	c->one_minus_alpha = 1.0 - o->filter_alpha; /* folded in double, as the firmware's (1.0-NET_OUT_MOVING_AVG_ALPHA) */
+	c->threshold = o->true_threshold;
+	c->dt_us = (uint32_t)floor((double)g->frame_step * 1e6 / g->sample_rate);
+	edison_fsm_roles(&c->roles.wake_idx, &c->roles.loc_mask, &c->roles.val_mask);
+
+	ED_HIP(ctx, hipSetDevice(ctx->device));
+	hipError_t e = hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking);
+	if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev, hipEventDisableTiming);
+	/* eight pushes of room while that stays within 64 MB of samples, else one (then every push after the first shifts) */
+	const size_t n = (size_t)c->chunk, push_samples = n * (size_t)c->hop;
+	c->slots = push_samples * sizeof(int16_t) * ED_STREAM_CORE_SLOTS <= ED_STREAM_CORE_SLOTS_BYTES ? ED_STREAM_CORE_SLOTS : 1;
+	if (e == hipSuccess)
+		e = hipMalloc((void **)&c->d_audio, sizeof(int16_t) * ((size_t)c->tail + (size_t)c->slots * push_samples) + ED_STREAM_CORE_SLACK);
+	if (e == hipSuccess)
+		e = hipMalloc((void **)&c->d_feat, (size_t)c->feat_elem * ((size_t)(c->F - 1) + (size_t)c->slots * n) * c->nm + ED_STREAM_CORE_SLACK);
+	size_t off = ed_stream_core_align(front_bytes);
+	c->off_filt = off; off += c->filter ? n * (size_t)c->n_out * sizeof(float) : 0;
+	c->off_likely = off; off += c->filter ? n * sizeof(int32_t) : 0;
+	c->off_spotted = off; off += c->filter ? n * sizeof(int32_t) : 0;
+	c->off_states = off; off += c->fsm ? n * sizeof(int32_t) : 0;
+	off = ed_stream_core_align(off); c->off_fsm = off; off += c->fsm ? sizeof(edison_fsm) : 0;
+	c->out_bytes = off;
+	if (e == hipSuccess) e = hipMalloc((void **)&c->d_out, c->out_bytes);
+	if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_out, c->out_bytes, hipHostMallocDefault);
+	if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_in, sizeof(int16_t) * push_samples, hipHostMallocDefault);
+	if (e == hipSuccess && c->filter) e = hipMalloc((void **)&c->d_state, sizeof(float) * (size_t)c->n_out);
+	if (e == hipSuccess && c->fsm) e = hipMalloc((void **)&c->d_fsm, sizeof(edison_fsm));
+	if (e != hipSuccess) return core_err(ctx, who, e == hipErrorOutOfMemory ? EDISON_E_NO_MEMORY : EDISON_E_RUNTIME, "allocation failed");
+	return ed_stream_core_reset(c);
+}
+
+void ed_stream_core_free(ed_stream_core *c)
+{
+	if (c->own && c->ev) (void)order_after(c, c->own);
+	if (c->own) (void)hipStreamSynchronize(c->own);
+	if (c->d_audio) (void)hipFree(c->d_audio);
+	if (c->d_feat) (void)hipFree(c->d_feat);
+	if (c->d_out) (void)hipFree(c->d_out);
+	if (c->d_state) (void)hipFree(c->d_state);
+	if (c->d_fsm) (void)hipFree(c->d_fsm);
+	if (c->h_in) (void)hipHostFree(c->h_in);
+	if (c->h_out) (void)hipHostFree(c->h_out);
+	if (c->ev) (void)hipEventDestroy(c->ev);
+	if (c->own) (void)hipStreamDestroy(c->own);
+}
+
+int ed_stream_core_reset(ed_stream_core *c)
+{
+	if (!c) return EDISON_E_ARGUMENT;
+	edison_ctx *ctx = c->ctx;
+	{ const int r = order_after(c, c->own); if (r != EDISON_OK) return r; }
+	c->pos = 0;
+	if (c->tail) ED_HIP(ctx, hipMemsetAsync(c->d_audio, 0, sizeof(int16_t) * (size_t)c->tail, c->own));
+	if (c->F > 1) ED_HIP(ctx, hipMemsetAsync(c->d_feat, 0, (size_t)c->feat_elem * (size_t)(c->F - 1) * c->nm, c->own)); /* float: +0.0f rows */
+	ED_HIP(ctx, hipMemsetAsync(c->d_out, 0, c->out_bytes, c->own));
+	if (c->filter) ED_HIP(ctx, hipMemsetAsync(c->d_state, 0, sizeof(float) * (size_t)c->n_out, c->own));
+	if (c->fsm)
+	{
+		edison_fsm start;
+		edison_fsm_init(&start); /* EDI_RESET, as the firmware enters its continuous loop (app.c:288-300) */
+		ED_HIP(ctx, hipMemcpyAsync(c->d_fsm, &start, sizeof(start), hipMemcpyHostToDevice, c->own));
+	}
+	ED_HIP(ctx, hipStreamSynchronize(c->own));
+	memset(c->h_out, 0, c->out_bytes);
+	c->q_pending = 0;
+	c->last_n = c->chunk;
+	c->last_staged = 0;
+	c->frames_seen = 0;
+	return EDISON_OK;
+}
+
+int ed_stream_core_begin_push(ed_stream_core *c, hipStream_t q, const int16_t *samples, int n, int host)
+{
+	if (n < 1 || n > c->chunk) return core_err(c->ctx, c->who, EDISON_E_ARGUMENT, "n_frames must be 1 .. chunk_frames");
+	{ const int r = order_after(c, q); if (r != EDISON_OK) return r; }
+	{ const int r = make_room(c, q, n); if (r != EDISON_OK) return r; }
+	const size_t bytes = sizeof(int16_t) * (size_t)n * c->hop;
+	if (host) memcpy(c->h_in, samples, bytes);
+	ED_HIP(c->ctx, hipMemcpyAsync(c->d_audio + (size_t)c->pos * c->hop + c->tail, host ? c->h_in : samples, bytes,
+	                              host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, q));
+	return EDISON_OK;
+}
+
+int ed_stream_core_finish_push(ed_stream_core *c, hipStream_t q, const void *fin, int n, int host)
+{
+	if (c->filter)
+	{
+		unsigned char *o = c->d_out;
+		edsg_fsm_stage_t fs;
+		memset(&fs, 0, sizeof(fs));
+		if (c->fsm)
+		{
+			fs.fsm = c->d_fsm; fs.states = (int32_t *)(o + c->off_states); fs.copy = (edison_fsm *)(o + c->off_fsm);
+			fs.dt_us = c->dt_us; fs.roles = c->roles;
+		}
+		float *filt = (float *)(o + c->off_filt);
+		int32_t *likely = (int32_t *)(o + c->off_likely), *spotted = (int32_t *)(o + c->off_spotted);
+		if (c->out_elem == 1)
+			hipLaunchKernelGGL(ed_stream_geom_filter_kernel<int8_t>, dim3(1), dim3(256), 0, q, (const int8_t *)fin, n, c->n_out, c->alpha,
+			                   c->one_minus_alpha, c->threshold, c->d_state, filt, likely, spotted, fs);
+		else
+			hipLaunchKernelGGL(ed_stream_geom_filter_kernel<float>, dim3(1), dim3(256), 0, q, (const float *)fin, n, c->n_out, c->alpha,
+			                   c->one_minus_alpha, c->threshold, c->d_state, filt, likely, spotted, fs);
+		if (hipGetLastError() != hipSuccess) return core_err(c->ctx, c->who, EDISON_E_RUNTIME, "filter launch failed");
+	}
+	c->pos += n;
+	if (host)
+	{
+		ED_HIP(c->ctx, hipMemcpyAsync(c->h_out, c->d_out, c->out_bytes, hipMemcpyDeviceToHost, q));
+		ED_HIP(c->ctx, hipStreamSynchronize(q));
+	}
+	else c->q_last = q;
+	c->q_pending = !host;
+	c->last_n = n;
+	c->last_staged = host;
+	c->frames_seen += n;
+	return EDISON_OK;
+}
+
+/* Copy `count` pieces of the last push's output block to the caller: from h_out after a host push, else from d_out on the stream the
+ * work went to (host = 1: synchronously; host = 0: ordered on the context's stream). */
+struct edsg_piece { void *dst; size_t off, bytes; };
+static int copy_out(ed_stream_core *c, const edsg_piece *p, int count, int host)
+{
+	edison_ctx *ctx = c->ctx;
+	if (host && c->last_staged)
+	{
+		for (int i = 0; i < count; i++)
+			if (p[i].dst) memcpy(p[i].dst, c->h_out + p[i].off, p[i].bytes);
+		return EDISON_OK;
+	}
+	hipStream_t q = host ? c->own : ctx->stream;
+	{ const int r = order_after(c, q); if (r != EDISON_OK) return r; }
+	for (int i = 0; i < count; i++)
+		if (p[i].dst)
+			ED_HIP(ctx, hipMemcpyAsync(p[i].dst, c->d_out + p[i].off, p[i].bytes, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, q));
+	if (host) ED_HIP(ctx, hipStreamSynchronize(q));
+	else c->q_last = q;
+	c->q_pending = !host;
+	return EDISON_OK;
+}
+
+int ed_stream_core_filtered(ed_stream_core *c, float *filt, int32_t *likely, int32_t *spotted, int host)
+{
+	if (!c) return EDISON_E_ARGUMENT;
+	if (!c->filter) return core_err(c->ctx, c->who, EDISON_E_ARGUMENT, "created without the output filter");
+	const size_t n = (size_t)c->last_n;
+	const edsg_piece p[3] = {{filt, c->off_filt, n * (size_t)c->n_out * sizeof(float)}, {likely, c->off_likely, n * sizeof(int32_t)},
+	                         {spotted, c->off_spotted, n * sizeof(int32_t)}};
+	return copy_out(c, p, 3, host);
+}
+
+int ed_stream_core_fsm(ed_stream_core *c, edison_fsm *fsm, int32_t *states, int host)
+{
+	if (!c) return EDISON_E_ARGUMENT;
+	if (!c->fsm) return core_err(c->ctx, c->who, EDISON_E_ARGUMENT, "created without the state machine (opts.fsm)");
+	const edsg_piece p[2] = {{states, c->off_states, (size_t)c->last_n * sizeof(int32_t)}, {fsm, c->off_fsm, sizeof(edison_fsm)}};
+	return copy_out(c, p, host ? 2 : 1, host);
+}

@@ -20,7 +20,78 @@ from ._lib import FRAME_LEN, NET_OUT, EdisonError
 from .context import KEYWORDS, default_context
 
 
-class Stream:
+class _Handle:
+    """What the three stream classes share: the life of the handle ``_h`` on the C functions ``<_C>*`` and the state machine's view."""
+    _C = None    # "edison_stream_", "edison_stream_geom_", "edison_stream_float_"
+
+    def _c(self, name):
+        return getattr(self._L, self._C + name)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._c("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self.ctx._check(self._c("reset")(self._h))
+
+    @property
+    def frames_seen(self):
+        return int(self._c("frames_seen")(self._h))
+
+    def fsm_snapshot(self):
+        """The state machine as the last edison_stream*_fsm call saw it: dict(state, hot_timeout_ms, last_command, commands)."""
+        f = self._fsm
+        cmd = None if f.last_loc < 0 else (KEYWORDS[f.last_loc], KEYWORDS[f.last_val])
+        return dict(state=Fsm.STATES[f.state], hot_timeout_ms=int(f.hot_timeout_ms), last_command=cmd, commands=int(f.commands),
+                    raw=(f.state, f.hot_timeout_ms, f.wake_idx, f.loc_idx, f.val_idx, f.last_loc, f.last_val, f.commands))
+
+
+class _SlidingStream(_Handle):
+    """What GeomStream and FloatStream share around their own network outputs: in a host push the sample check in front and the filter's
+    and the state machine's outputs behind, and the device push."""
+
+    def _host_samples(self, samples):
+        x = np.ascontiguousarray(samples, dtype=np.int16).ravel()
+        if x.shape[0] != self.chunk * self.hop:
+            raise ValueError("push needs exactly chunk_frames*hop = %d samples" % (self.chunk * self.hop))
+        return x
+
+    def _filter_tail(self, out):
+        c, no = self.chunk, self.n_out
+        if self.output_filter:
+            fl, li, sp = np.zeros((c, no), np.float32), np.zeros(c, np.int32), np.zeros(c, np.int32)
+            self.ctx._check(self._c("filtered")(self._h, fl.ctypes.data, li.ctypes.data, sp.ctypes.data))
+            out.update(filtered=fl, likely=li, spotted=sp)
+        if self.fsm:
+            st = np.zeros(c, np.int32)
+            self.ctx._check(self._c("fsm")(self._h, ctypes.byref(self._fsm), st.ctypes.data))
+            out.update(fsm_states=st, fsm=self.fsm_snapshot())
+        return out
+
+    def _push_t(self, samples, logits, second, argmax, filtered, likely, spotted, n_frames):
+        """push_t behind either signature: `second` is the softmax or the probabilities."""
+        n = self.chunk if n_frames is None else int(n_frames)
+        if samples.numel() != n * self.hop:
+            raise ValueError("push needs exactly n_frames*hop = %d samples" % (n * self.hop))
+        q = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        if n_frames is None:
+            self.ctx._check(self._c("push_dev")(self._h, q(samples), q(logits), q(second), q(argmax)))
+        else:
+            self.ctx._check(self._c("push_n_dev")(self._h, q(samples), n, q(logits), q(second), q(argmax)))
+        if filtered is not None or likely is not None or spotted is not None:
+            self.ctx._check(self._c("filtered_dev")(self._h, q(filtered), q(likely), q(spotted)))
+
+
+class Stream(_Handle):
+    _C = "edison_stream_"
+
     def __init__(self, ctx=None, hop=FRAME_LEN, chunk_frames=1, q15=False, output_filter=False, alpha=0.9,
                  threshold=0.5, graph=None, fsm=False):
         self.ctx = ctx or default_context()
@@ -41,24 +112,6 @@ class Stream:
         self._fsm_states = np.zeros(self.chunk, np.int32)
         self._fsm = _lib.Fsm()
         self._bufs = None
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.edison_stream_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        self.ctx._check(self._L.edison_stream_reset(self._h))
-
-    @property
-    def frames_seen(self):
-        return int(self._L.edison_stream_frames_seen(self._h))
 
     def push(self, samples):
         """samples: chunk_frames*hop new int16 samples (host). Returns dict(logits, softmax, argmax, keywords) plus,
@@ -85,13 +138,6 @@ class Stream:
             out.update(fsm_states=self._fsm_states.copy(), fsm=self.fsm_snapshot())
         return out
 
-    def fsm_snapshot(self):
-        """The state machine as the last edison_stream_fsm call saw it: dict(state, hot_timeout_ms, last_command, commands)."""
-        f = self._fsm
-        cmd = None if f.last_loc < 0 else (KEYWORDS[f.last_loc], KEYWORDS[f.last_val])
-        return dict(state=Fsm.STATES[f.state], hot_timeout_ms=int(f.hot_timeout_ms), last_command=cmd, commands=int(f.commands),
-                    raw=(f.state, f.hot_timeout_ms, f.wake_idx, f.loc_idx, f.val_idx, f.last_loc, f.last_val, f.commands))
-
     def _make_bufs(self):
         c = self.chunk
         lo, so, am = np.zeros((c, NET_OUT), np.int8), np.zeros((c, NET_OUT), np.int8), np.zeros(c, np.int32)
@@ -115,7 +161,7 @@ class Stream:
             self.ctx._check(self._L.edison_stream_filtered_dev(self._h, q(filtered), q(likely), q(spotted)))
 
 
-class GeomStream:
+class GeomStream(_SlidingStream):
     """Continuous keyword spotting for a graph trained at ANY MFCC geometry -- Python handle on ``edison_stream_geom_*``: the continuous
     counterpart of ``Context.kws_geom``. The hop is ``geometry.frame_step``; the window is ``geometry.frame_count`` rows of
     ``num_mfcc`` features, oldest first (the firmware's order, as ``Stream``). The features are the float64 host flow's at every
@@ -123,6 +169,8 @@ class GeomStream:
 
     ``output_filter=True`` adds the firmware's post-processing over the graph's n_out outputs (the softmax, or the last layer's output
     for a graph without Softmax); ``fsm=True`` puts edisonFSM behind it (graphs with 10 outputs only)."""
+
+    _C = "edison_stream_geom_"
 
     def __init__(self, ctx, geometry, chunk_frames=1, output_filter=False, alpha=0.9, threshold=0.5, fsm=False):
         self.ctx = ctx or default_context()
@@ -144,31 +192,11 @@ class GeomStream:
         self.output_filter, self.fsm = bool(output_filter or fsm), bool(fsm)
         self._fsm = _lib.Fsm()
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.edison_stream_geom_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        self.ctx._check(self._L.edison_stream_geom_reset(self._h))
-
-    @property
-    def frames_seen(self):
-        return int(self._L.edison_stream_geom_frames_seen(self._h))
-
     def push(self, samples):
         """samples: chunk_frames * hop new int16 samples (host). Returns dict(logits, softmax, argmax) [chunk][n_out] / [chunk] (softmax
         None for a graph without Softmax), ``keywords`` for a graph with 10 outputs, and with the filter filtered [chunk][n_out] fp32,
         likely, spotted (-1 = below the threshold); with the state machine fsm_states and fsm (Stream.fsm_snapshot's dict)."""
-        x = np.ascontiguousarray(samples, dtype=np.int16).ravel()
-        if x.shape[0] != self.chunk * self.hop:
-            raise ValueError("push needs exactly chunk_frames*hop = %d samples" % (self.chunk * self.hop))
+        x = self._host_samples(samples)
         c, no = self.chunk, self.n_out
         lo, am = np.zeros((c, no), np.int8), np.zeros(c, np.int32)
         so = np.zeros((c, no), np.int8) if self.has_softmax else None
@@ -177,32 +205,15 @@ class GeomStream:
         out = dict(logits=lo, softmax=so, argmax=am)
         if no == NET_OUT:
             out["keywords"] = [KEYWORDS[i] for i in am]
-        if self.output_filter:
-            fl, li, sp = np.zeros((c, no), np.float32), np.zeros(c, np.int32), np.zeros(c, np.int32)
-            self.ctx._check(self._L.edison_stream_geom_filtered(self._h, fl.ctypes.data, li.ctypes.data, sp.ctypes.data))
-            out.update(filtered=fl, likely=li, spotted=sp)
-        if self.fsm:
-            st = np.zeros(c, np.int32)
-            self.ctx._check(self._L.edison_stream_geom_fsm(self._h, ctypes.byref(self._fsm), st.ctypes.data))
-            out.update(fsm_states=st, fsm=Stream.fsm_snapshot(self))
-        return out
+        return self._filter_tail(out)
 
     def push_t(self, samples, logits=None, softmax=None, argmax=None, filtered=None, likely=None, spotted=None, n_frames=None):
         """Device tensors (torch, int16 / int8 / int32 / fp32 on the context's GPU); asynchronous on the context's stream. n_frames <
         chunk_frames: a ragged last push of n_frames * hop samples; every output is [n_frames][..]."""
-        n = self.chunk if n_frames is None else int(n_frames)
-        if samples.numel() != n * self.hop:
-            raise ValueError("push needs exactly n_frames*hop = %d samples" % (n * self.hop))
-        q = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        if n_frames is None:
-            self.ctx._check(self._L.edison_stream_geom_push_dev(self._h, q(samples), q(logits), q(softmax), q(argmax)))
-        else:
-            self.ctx._check(self._L.edison_stream_geom_push_n_dev(self._h, q(samples), n, q(logits), q(softmax), q(argmax)))
-        if filtered is not None or likely is not None or spotted is not None:
-            self.ctx._check(self._L.edison_stream_geom_filtered_dev(self._h, q(filtered), q(likely), q(spotted)))
+        self._push_t(samples, logits, softmax, argmax, filtered, likely, spotted, n_frames)
 
 
-class FloatStream:
+class FloatStream(_SlidingStream):
     """Continuous keyword spotting with the float32 X-CUBE-AI network loaded on the context (``Context.fnet_load``) -- Python handle on
     ``edison_stream_float_*``: the continuous counterpart of ``Context.kws_float``, and the loop the reference's board runs for its
     default network type (app.c:288-371, 630-719). The hop is ``geometry.frame_step`` (``geometry=None``: what ``Context.kws_float``
@@ -212,6 +223,8 @@ class FloatStream:
 
     ``output_filter=True`` adds the firmware's moving average over the probabilities (alpha 0.5: the Cube build's, app.c:35-36), first
     maximum and threshold; ``fsm=True`` puts edisonFSM behind it (networks with 10 outputs only)."""
+
+    _C = "edison_stream_float_"
 
     def __init__(self, ctx, geometry=None, q15=False, chunk_frames=1, output_filter=False, alpha=0.5, threshold=0.5, fsm=False,
                  clip_min=None, clip_max=None):
@@ -241,31 +254,11 @@ class FloatStream:
         self.output_filter, self.fsm = bool(output_filter or fsm), bool(fsm)
         self._fsm = _lib.Fsm()
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.edison_stream_float_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        self.ctx._check(self._L.edison_stream_float_reset(self._h))
-
-    @property
-    def frames_seen(self):
-        return int(self._L.edison_stream_float_frames_seen(self._h))
-
     def push(self, samples):
         """samples: chunk_frames * hop new int16 samples (host). Returns dict(logits, probs) float32 [chunk][n_out], argmax [chunk],
         ``keywords`` (the names of the network's .ednf, ``self.keywords``; KEYWORDS for a 10-output network without names), and with
         the filter filtered [chunk][n_out] fp32, likely, spotted (-1 = below the threshold); with the state machine fsm_states and fsm."""
-        x = np.ascontiguousarray(samples, dtype=np.int16).ravel()
-        if x.shape[0] != self.chunk * self.hop:
-            raise ValueError("push needs exactly chunk_frames*hop = %d samples" % (self.chunk * self.hop))
+        x = self._host_samples(samples)
         c, no = self.chunk, self.n_out
         lo, pr, am = np.zeros((c, no), np.float32), np.zeros((c, no), np.float32), np.zeros(c, np.int32)
         self.ctx._check(self._L.edison_stream_float_push(self._h, x.ctypes.data, lo.ctypes.data, pr.ctypes.data, am.ctypes.data))
@@ -273,29 +266,12 @@ class FloatStream:
         names = self.keywords or (list(KEYWORDS) if no == NET_OUT else None)
         if names is not None:
             out["keywords"] = [names[i] if i < len(names) else str(i) for i in am]
-        if self.output_filter:
-            fl, li, sp = np.zeros((c, no), np.float32), np.zeros(c, np.int32), np.zeros(c, np.int32)
-            self.ctx._check(self._L.edison_stream_float_filtered(self._h, fl.ctypes.data, li.ctypes.data, sp.ctypes.data))
-            out.update(filtered=fl, likely=li, spotted=sp)
-        if self.fsm:
-            st = np.zeros(c, np.int32)
-            self.ctx._check(self._L.edison_stream_float_fsm(self._h, ctypes.byref(self._fsm), st.ctypes.data))
-            out.update(fsm_states=st, fsm=Stream.fsm_snapshot(self))
-        return out
+        return self._filter_tail(out)
 
     def push_t(self, samples, logits=None, probs=None, argmax=None, filtered=None, likely=None, spotted=None, n_frames=None):
         """Device tensors (torch, int16 / fp32 / int32 on the context's GPU); asynchronous on the context's stream. n_frames <
         chunk_frames: a ragged last push of n_frames * hop samples; every output is [n_frames][..]."""
-        n = self.chunk if n_frames is None else int(n_frames)
-        if samples.numel() != n * self.hop:
-            raise ValueError("push needs exactly n_frames*hop = %d samples" % (n * self.hop))
-        q = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        if n_frames is None:
-            self.ctx._check(self._L.edison_stream_float_push_dev(self._h, q(samples), q(logits), q(probs), q(argmax)))
-        else:
-            self.ctx._check(self._L.edison_stream_float_push_n_dev(self._h, q(samples), n, q(logits), q(probs), q(argmax)))
-        if filtered is not None or likely is not None or spotted is not None:
-            self.ctx._check(self._L.edison_stream_float_filtered_dev(self._h, q(filtered), q(likely), q(spotted)))
+        self._push_t(samples, logits, probs, argmax, filtered, likely, spotted, n_frames)
 
 
 class Fsm:

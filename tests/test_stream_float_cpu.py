@@ -54,13 +54,16 @@ def _compile(tmp_path, name, extra=()):
 
 
 def test_the_stream_is_built(tmp_path):
-    """build.HIP_SOURCES lists the host object and the new MFCC instance, and both cross-compile for gfx950 on the library's flags."""
+    """build.HIP_SOURCES lists the host object, the sliding-window core and the new MFCC instance, and all cross-compile for gfx950 on
+    the library's flags."""
     from edison_amd import build
-    for name in ("edison_stream_float.hip", "mfcc_geom_fnet_kernels.hip"):
+    for name in ("edison_stream_float.hip", "edison_stream_core.hip", "mfcc_geom_fnet_kernels.hip"):
         assert name in build.HIP_SOURCES
         _compile(tmp_path, name, ["-Wall", "-Wextra", "-Wno-unused-parameter", "-fPIC"])
-    for h in ("mfcc_geom_device.h", "edison_stream_kernels.h"):
+    for h in ("mfcc_geom_device.h", "edison_stream_core.h"):
         assert h in build.HEADERS
+        assert os.path.exists(os.path.join(build.CSRC, h))
+    assert "edison_stream_kernels.h" not in build.HEADERS
 
 
 def _scratch(text):
@@ -82,17 +85,31 @@ def test_hot_path_kernels_use_no_scratch(tmp_path):
 
 
 def test_one_frame_body_for_the_third_instance():
-    """The new instance computes y by the shared frame body and stores the float network input; the filter and shift kernels are not
-    copied: the float stream launches edison_stream_geom.hip's."""
+    """The new instance computes y by the shared frame body and stores the float network input; the filter and shift kernels exist once,
+    in the sliding-window core (edison_stream_core.hip): neither stream file defines a kernel, and both run their pushes through the
+    core's entry points, begin_push (which shifts) and finish_push (which filters)."""
     from edison_amd import build as B
     kern = open(os.path.join(B.CSRC, "mfcc_geom_fnet_kernels.hip")).read()
     assert kern.count('#include "mfcc_geom_frames.inc"') == 1 and "a.dct_div" not in kern
     assert "fminf(fmaxf((float)(y) * scale, lo), hi)" in kern
-    fs = open(os.path.join(B.CSRC, "edison_stream_float.hip")).read()
-    assert "__global__" not in fs
-    assert "ed_launch_stream_shift(" in fs and "ed_launch_stream_filter_f32(" in fs
-    geom = open(os.path.join(B.CSRC, "edison_stream_geom.hip")).read()
-    assert "#pragma clang fp contract(off)" in geom and "ed_stream_geom_filter_kernel<int8_t>" in geom
+    for name in ("edison_stream_float.hip", "edison_stream_geom.hip"):
+        text = open(os.path.join(B.CSRC, name)).read()
+        assert "__global__" not in text and "hipLaunchKernelGGL" not in text
+        assert "ed_stream_core_begin_push(" in text and "ed_stream_core_finish_push(" in text
+    core = open(os.path.join(B.CSRC, "edison_stream_core.hip")).read()
+    assert core.count("__global__") == 2 and core.count("#pragma clang fp contract(off)") == 1
+    assert core.count("void ed_stream_geom_shift_kernel(") == 1 and core.count("void ed_stream_geom_filter_kernel(") == 1
+    assert "ed_stream_geom_filter_kernel<int8_t>" in core and "ed_stream_geom_filter_kernel<float>" in core
+    # the shift is launched in one place, make_room, which begin_push calls; the filter in one place, finish_push
+    assert core.count("hipLaunchKernelGGL(ed_stream_geom_shift_kernel") == 1 and core.count("hipLaunchKernelGGL(ed_stream_geom_filter_kernel<") == 2
+    begin = core[core.index("int ed_stream_core_begin_push("):core.index("int ed_stream_core_finish_push(")]
+    assert "make_room(c, q, n)" in begin
+    assert "hipLaunchKernelGGL(ed_stream_geom_filter_kernel<" in core[core.index("int ed_stream_core_finish_push("):]
+    # nothing the core provides is defined a second time anywhere in the library's sources
+    texts = [open(os.path.join(B.CSRC, f)).read() for f in sorted(os.listdir(B.CSRC)) if f.endswith((".hip", ".h", ".c", ".inc"))]
+    for fn in ("order_after", "make_room", "copy_out", "ed_stream_core_filtered", "ed_stream_core_fsm", "ed_stream_core_reset",
+               "ed_stream_core_free"):
+        assert sum(len(re.findall(r"^(?:static )?(?:int|void) %s\(.*\)\n\{" % fn, x, re.M)) for x in texts) == 1, fn
 
 
 def _float_rows(oracle_mod, g, z, starts):
