@@ -57,6 +57,11 @@ class StreamGeomOpts(ctypes.Structure):
                 ("true_threshold", c_double)]
 
 
+class StreamBankOpts(ctypes.Structure):
+    """edison_stream_bank_opts"""
+    _fields_ = [("n_mics", c_int), ("stream", StreamGeomOpts)]
+
+
 class StreamFloatOpts(ctypes.Structure):
     """edison_stream_float_opts"""
     _fields_ = [("chunk_frames", ctypes.c_int32), ("q15", ctypes.c_int32), ("clip_lo", c_float), ("clip_hi", c_float), ("filter", ctypes.c_int32),
@@ -183,6 +188,19 @@ SIGNATURES = {
     "edison_stream_geom_filtered_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "edison_stream_geom_fsm": (c_int, [c_void_p, c_void_p, c_void_p]),
     "edison_stream_geom_fsm_dev": (c_int, [c_void_p, c_void_p]),
+    "edison_stream_bank_default_opts": (None, [ctypes.POINTER(StreamBankOpts)]),
+    "edison_stream_bank_create": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), ctypes.POINTER(StreamBankOpts), ctypes.POINTER(c_void_p)]),
+    "edison_stream_bank_destroy": (None, [c_void_p]),
+    "edison_stream_bank_reset": (c_int, [c_void_p]),
+    "edison_stream_bank_reset_mic": (c_int, [c_void_p, c_int]),
+    "edison_stream_bank_push": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_bank_push_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_bank_push_n_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_bank_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_bank_filtered_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_stream_bank_fsm": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "edison_stream_bank_fsm_dev": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "edison_stream_bank_frames_seen": (c_int, [c_void_p, ctypes.POINTER(c_int64)]),
     "edison_stream_float_default_opts": (None, [ctypes.POINTER(StreamFloatOpts)]),
     "edison_stream_float_create": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), ctypes.POINTER(StreamFloatOpts), ctypes.POINTER(c_void_p)]),
     "edison_stream_float_destroy": (None, [c_void_p]),

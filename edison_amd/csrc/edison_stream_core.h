@@ -10,6 +10,12 @@
  * whose history starts at frame `pos` (samples pos * hop, rows pos): a push appends behind it and advances pos by its frames; window i
  * of the push is rows pos + i .. pos + i + F - 1, read in place by the owner's network kernel. When the next push would run past the
  * end, the shift kernel first moves the history back to the front.
+ *
+ * A core serves n_mics microphones that advance in lockstep (1: edison_stream_geom / edison_stream_float; more: edison_stream_bank.hip,
+ * DESIGN.md section 12b). Each microphone has the two buffers above, mic_audio samples and mic_feat bytes behind its neighbour's, and all
+ * share one pos. A push carries [n_mics][n * hop] samples; everything it puts out is time-major: filt [n][n_mics][n_out], likely /
+ * spotted / states [n][n_mics], the machines [n_mics]. With n_mics = 1 the core issues the copies and launches it issued before it had
+ * the dimension; with more, one strided copy and the banked kernels of edison_stream_bank.hip (one workgroup per microphone).
  */
 #ifndef EDISON_STREAM_CORE_H
 #define EDISON_STREAM_CORE_H
@@ -27,6 +33,12 @@
 #define ED_STREAM_CORE_ALIGN 16                       /* alignment of the parts of the output block                        */
 
 static inline size_t ed_stream_core_align(size_t off) { return (off + (ED_STREAM_CORE_ALIGN - 1)) & ~(size_t)(ED_STREAM_CORE_ALIGN - 1); }
+/* one microphone's sliding buffers: samples of d_audio, bytes of d_feat */
+static inline size_t ed_stream_core_mic_audio(int tail, int slots, int chunk, int hop) { return (size_t)tail + (size_t)slots * chunk * hop; }
+static inline size_t ed_stream_core_mic_feat(int feat_elem, int F, int slots, int chunk, int nm)
+{
+	return (size_t)feat_elem * ((size_t)(F - 1) + (size_t)slots * chunk) * nm;
+}
 
 struct ed_stream_core
 {
@@ -35,6 +47,8 @@ struct ed_stream_core
 	int feat_elem, out_elem;       /* bytes per feature element and per network output: 1 (the int8 graph) or 4 (the float network) */
 	int F, nm, hop, tail, chunk;   /* frames per window, coefficients per row, frame_step, T history samples, frames per push */
 	int n_out, filter, fsm;
+	int n_mics;                    /* microphones in lockstep */
+	size_t mic_audio, mic_feat;    /* from one microphone's buffer to the next: samples of d_audio, bytes of d_feat */
 	double alpha, one_minus_alpha, threshold;
 	ed_fsm_roles_t roles;
 	uint32_t dt_us;
@@ -44,9 +58,9 @@ struct ed_stream_core
 	/* every output of a push in one block (device d_out, pinned h_out), so that a host push downloads once: the owner's in front */
 	unsigned char *d_out, *h_out;
 	size_t off_filt, off_likely, off_spotted, off_states, off_fsm, out_bytes;
-	int16_t *h_in;                 /* pinned [chunk * hop]: the host push's upload */
-	float *d_state;                /* [n_out] the filter state */
-	edison_fsm *d_fsm;
+	int16_t *h_in;                 /* pinned [n_mics][chunk * hop]: the host push's upload */
+	float *d_state;                /* [n_mics][n_out] the filter state */
+	edison_fsm *d_fsm;             /* [n_mics] */
 	hipStream_t own;               /* host pushes run here */
 	hipEvent_t ev;
 	hipStream_t q_last;            /* where the last unsynchronised work on the stream's state went (device pushes: the caller's stream) */
@@ -55,28 +69,49 @@ struct ed_stream_core
 	int64_t frames_seen;
 };
 
+/* the state machine behind the filter kernels; fsm = NULL: none */
+struct edsg_fsm_stage_t
+{
+	edison_fsm *fsm;      /* [n_mics] device memory, read and written                    */
+	int32_t *states;      /* [n][n_mics] out: the state after each inference             */
+	edison_fsm *copy;     /* [n_mics] out: the machines after the push (the host's view) */
+	uint32_t dt_us;
+	ed_fsm_roles_t roles;
+};
+
+/* The kernels of a core with more than one microphone, one workgroup per microphone (edison_stream_bank.hip): the shift of every
+ * microphone's history to the front of its buffers, a_stride samples and f_stride bytes apart, and the filter (+ edisonFSM) over the
+ * time-major int8 x [n][n_mics][n_out] with state [n_mics][n_out]. Enqueued on q; a failed launch shows in hipGetLastError. */
+void ed_stream_bank_launch_shift(hipStream_t q, int n_mics, int16_t *audio, int64_t a_stride, int64_t a_src, int tail, int8_t *feat, int64_t f_stride,
+                                 int64_t f_src, int feat_bytes);
+void ed_stream_bank_launch_filter(hipStream_t q, int n_mics, const int8_t *x, int n, int n_out, double alpha, double one_minus_alpha, double threshold,
+                                  float *state, float *filt, int32_t *likely, int32_t *spotted, edsg_fsm_stage_t fs);
+
 /* the options both public option structs carry */
 struct ed_stream_core_opts { int chunk_frames, filter, fsm; double filter_alpha, true_threshold; };
 
 /* create: the option checks that need no network, before the owner allocates; then, on a zeroed core for geometry g with F frames per
- * window: the fields, hipSetDevice, the HIP stream, the event, every buffer (`front_bytes` of the owner's outputs lead the block) and a
- * reset. free waits for the stream's work and frees whatever create got, also after it failed. */
+ * window and n_mics microphones: the fields, hipSetDevice, the HIP stream, the event, every buffer (`front_bytes` of the owner's outputs
+ * lead the block) and a reset. free waits for the stream's work and frees whatever create got, also after it failed. */
 int ed_stream_core_check_opts(edison_ctx *ctx, const char *who, const edison_kws_geom *g, const ed_stream_core_opts *o);
 int ed_stream_core_create(ed_stream_core *c, edison_ctx *ctx, const char *who, int feat_elem, int out_elem, const edison_kws_geom *g, int F,
-                          int n_out, const ed_stream_core_opts *o, size_t front_bytes);
+                          int n_out, int n_mics, const ed_stream_core_opts *o, size_t front_bytes);
 void ed_stream_core_free(ed_stream_core *c);
 
 /* A push of n frames on q (host = 1: host samples, q = c->own; host = 0: device samples, q = the context's stream):
  *   begin_push   waits for work left on another HIP stream, shifts the history when the push would not fit, uploads the samples to
- *                d_audio + pos * hop + tail (the host's through h_in); the owner's feature rows and network follow
- *   finish_push  where the stream has a filter: the filter (+ edisonFSM) over fin[n][n_out] (int8 for out_elem 1, float for 4) into the
- *                block; pos += n; host: one download of the block to h_out and one wait; what the getters need to know of this push */
+ *                d_audio + pos * hop + tail of every microphone (the host's through h_in); the owner's feature rows and network follow
+ *   finish_push  where the stream has a filter: the filter (+ edisonFSM) over fin[n][n_mics][n_out] (int8 for out_elem 1, float for 4;
+ *                more than one microphone: int8) into the block; pos += n; host: one download of the block to h_out and one wait; what the getters need to know of this push */
 int ed_stream_core_begin_push(ed_stream_core *c, hipStream_t q, const int16_t *samples, int n, int host);
 int ed_stream_core_finish_push(ed_stream_core *c, hipStream_t q, const void *fin, int n, int host);
 
 /* c = NULL: EDISON_E_ARGUMENT. The getters copy the last push's outputs (host = 1: host pointers, synchronous; host = 0: device
- * pointers, ordered on the context's stream; NULL: not copied). */
+ * pointers, ordered on the context's stream; NULL: not copied); fsm [n_mics]. */
 int ed_stream_core_reset(ed_stream_core *c);
+/* microphone `mic` alone back to a new stream's state, at the current pos: history, filter state, state machine. Waits for pushes left
+ * on another HIP stream and returns when it is done, as reset. */
+int ed_stream_core_reset_mic(ed_stream_core *c, int mic);
 int ed_stream_core_filtered(ed_stream_core *c, float *filt, int32_t *likely, int32_t *spotted, int host);
 int ed_stream_core_fsm(ed_stream_core *c, edison_fsm *fsm, int32_t *states, int host);
 

@@ -1,21 +1,12 @@
 /*
  * edison_stream_core.hip -- the sliding-window core of the any-geometry streams (edison_stream_core.h): the two
- * state kernels, and the host logic around them that edison_stream_geom.hip and edison_stream_float.hip share.
+ * state kernels, and the host logic around them that edison_stream_geom.hip and edison_stream_float.hip share. With more than one
+ * microphone (edison_stream_bank.hip, section 12b) the same logic runs on strided buffers and calls that file's banked kernels.
  */
 #include <math.h>
 #include <string.h>
 
 #include "edison_stream_core.h"
-
-/* the state machine behind the filter; fsm = NULL: none */
-struct edsg_fsm_stage_t
-{
-	edison_fsm *fsm;      /* device memory, read and written                       */
-	int32_t *states;      /* [n] out: the state after each inference               */
-	edison_fsm *copy;     /* out: the machine after the push (the host's view)     */
-	uint32_t dt_us;
-	ed_fsm_roles_t roles;
-};
 
 /* The newest `tail` samples from audio + a_src and `feat_bytes` history bytes from feat + f_src to the front of their buffers. The
  * destination lies BELOW the source and may overlap it: in rounds of 256 elements every lane reads, the workgroup waits, every lane
@@ -115,8 +106,13 @@ static int order_after(ed_stream_core *c, hipStream_t q)
 static int make_room(ed_stream_core *c, hipStream_t q, int n)
 {
 	if (c->pos + n <= c->slots * c->chunk || c->pos == 0) return EDISON_OK;
-	hipLaunchKernelGGL(ed_stream_geom_shift_kernel, dim3(1), dim3(256), 0, q, c->d_audio, (int64_t)c->pos * c->hop, c->tail, (int8_t *)c->d_feat,
-	                   (int64_t)c->pos * c->nm * c->feat_elem, c->feat_elem * (c->F - 1) * c->nm);
+	const int64_t a_src = (int64_t)c->pos * c->hop, f_src = (int64_t)c->pos * c->nm * c->feat_elem;
+	const int feat_bytes = c->feat_elem * (c->F - 1) * c->nm;
+	if (c->n_mics == 1)
+		hipLaunchKernelGGL(ed_stream_geom_shift_kernel, dim3(1), dim3(256), 0, q, c->d_audio, a_src, c->tail, (int8_t *)c->d_feat, f_src, feat_bytes);
+	else
+		ed_stream_bank_launch_shift(q, c->n_mics, c->d_audio, (int64_t)c->mic_audio, a_src, c->tail, (int8_t *)c->d_feat, (int64_t)c->mic_feat, f_src,
+		                            feat_bytes);
 	c->pos = 0;
 	return hipGetLastError() == hipSuccess ? EDISON_OK : core_err(c->ctx, c->who, EDISON_E_RUNTIME, "shift launch failed");
 }
@@ -134,9 +130,9 @@ int ed_stream_core_check_opts(edison_ctx *ctx, const char *who, const edison_kws
 }
 
 int ed_stream_core_create(ed_stream_core *c, edison_ctx *ctx, const char *who, int feat_elem, int out_elem, const edison_kws_geom *g, int F,
-                          int n_out, const ed_stream_core_opts *o, size_t front_bytes)
+                          int n_out, int n_mics, const ed_stream_core_opts *o, size_t front_bytes)
 {
-	c->ctx = ctx; c->who = who; c->feat_elem = feat_elem; c->out_elem = out_elem;
+	c->ctx = ctx; c->who = who; c->feat_elem = feat_elem; c->out_elem = out_elem; c->n_mics = n_mics;
 	c->F = F; c->nm = g->num_mfcc; c->hop = g->frame_step; c->chunk = o->chunk_frames;
 	c->tail = g->frame_len > g->frame_step ? g->frame_len - g->frame_step : 0;
 	c->n_out = n_out;
@@ -153,23 +149,28 @@ int ed_stream_core_create(ed_stream_core *c, edison_ctx *ctx, const char *who, i
 	/* eight pushes of room while that stays within 64 MB of samples, else one (then every push after the first shifts) */
 	const size_t n = (size_t)c->chunk, push_samples = n * (size_t)c->hop;
 	c->slots = push_samples * sizeof(int16_t) * ED_STREAM_CORE_SLOTS <= ED_STREAM_CORE_SLOTS_BYTES ? ED_STREAM_CORE_SLOTS : 1;
-	if (e == hipSuccess)
-		e = hipMalloc((void **)&c->d_audio, sizeof(int16_t) * ((size_t)c->tail + (size_t)c->slots * push_samples) + ED_STREAM_CORE_SLACK);
-	if (e == hipSuccess)
-		e = hipMalloc((void **)&c->d_feat, (size_t)c->feat_elem * ((size_t)(c->F - 1) + (size_t)c->slots * n) * c->nm + ED_STREAM_CORE_SLACK);
+	const size_t mics = (size_t)n_mics, nt = n * mics; /* entries per push of the time-major outputs */
+	c->mic_audio = ed_stream_core_mic_audio(c->tail, c->slots, c->chunk, c->hop);
+	c->mic_feat = ed_stream_core_mic_feat(c->feat_elem, c->F, c->slots, c->chunk, c->nm);
+	if (e == hipSuccess) e = hipMalloc((void **)&c->d_audio, sizeof(int16_t) * mics * c->mic_audio + ED_STREAM_CORE_SLACK);
+	if (e == hipSuccess) e = hipMalloc((void **)&c->d_feat, mics * c->mic_feat + ED_STREAM_CORE_SLACK);
 	size_t off = ed_stream_core_align(front_bytes);
-	c->off_filt = off; off += c->filter ? n * (size_t)c->n_out * sizeof(float) : 0;
-	c->off_likely = off; off += c->filter ? n * sizeof(int32_t) : 0;
-	c->off_spotted = off; off += c->filter ? n * sizeof(int32_t) : 0;
-	c->off_states = off; off += c->fsm ? n * sizeof(int32_t) : 0;
-	off = ed_stream_core_align(off); c->off_fsm = off; off += c->fsm ? sizeof(edison_fsm) : 0;
+	c->off_filt = off; off += c->filter ? nt * (size_t)c->n_out * sizeof(float) : 0;
+	c->off_likely = off; off += c->filter ? nt * sizeof(int32_t) : 0;
+	c->off_spotted = off; off += c->filter ? nt * sizeof(int32_t) : 0;
+	c->off_states = off; off += c->fsm ? nt * sizeof(int32_t) : 0;
+	off = ed_stream_core_align(off); c->off_fsm = off; off += c->fsm ? mics * sizeof(edison_fsm) : 0;
 	c->out_bytes = off;
 	if (e == hipSuccess) e = hipMalloc((void **)&c->d_out, c->out_bytes);
 	if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_out, c->out_bytes, hipHostMallocDefault);
-	if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_in, sizeof(int16_t) * push_samples, hipHostMallocDefault);
-	if (e == hipSuccess && c->filter) e = hipMalloc((void **)&c->d_state, sizeof(float) * (size_t)c->n_out);
-	if (e == hipSuccess && c->fsm) e = hipMalloc((void **)&c->d_fsm, sizeof(edison_fsm));
-	if (e != hipSuccess) return core_err(ctx, who, e == hipErrorOutOfMemory ? EDISON_E_NO_MEMORY : EDISON_E_RUNTIME, "allocation failed");
+	if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_in, sizeof(int16_t) * mics * push_samples, hipHostMallocDefault);
+	if (e == hipSuccess && c->filter) e = hipMalloc((void **)&c->d_state, sizeof(float) * mics * (size_t)c->n_out);
+	if (e == hipSuccess && c->fsm) e = hipMalloc((void **)&c->d_fsm, mics * sizeof(edison_fsm));
+	if (e != hipSuccess)
+	{
+		(void)hipGetLastError();
+		return core_err(ctx, who, e == hipErrorOutOfMemory ? EDISON_E_NO_MEMORY : EDISON_E_RUNTIME, "allocation failed");
+	}
 	return ed_stream_core_reset(c);
 }
 
@@ -188,22 +189,54 @@ void ed_stream_core_free(ed_stream_core *c)
 	if (c->own) (void)hipStreamDestroy(c->own);
 }
 
+/* On the stream's own HIP stream: the history of microphones m .. m + count - 1 at the current pos (`tail` samples, F - 1 rows; float
+ * rows: +0.0f), their filter states and their state machines to the start values. */
+static int start_state(ed_stream_core *c, int m, int count)
+{
+	edison_ctx *ctx = c->ctx;
+	int16_t *audio = c->d_audio + (size_t)m * c->mic_audio + (size_t)c->pos * c->hop;
+	unsigned char *feat = c->d_feat + (size_t)m * c->mic_feat + (size_t)c->pos * c->nm * c->feat_elem;
+	const size_t tail_bytes = sizeof(int16_t) * (size_t)c->tail, hist_bytes = (size_t)c->feat_elem * (size_t)(c->F - 1) * c->nm;
+	if (count == 1)
+	{
+		if (tail_bytes) ED_HIP(ctx, hipMemsetAsync(audio, 0, tail_bytes, c->own));
+		if (hist_bytes) ED_HIP(ctx, hipMemsetAsync(feat, 0, hist_bytes, c->own));
+	}
+	else
+	{
+		if (tail_bytes) ED_HIP(ctx, hipMemset2DAsync(audio, sizeof(int16_t) * c->mic_audio, 0, tail_bytes, (size_t)count, c->own));
+		if (hist_bytes) ED_HIP(ctx, hipMemset2DAsync(feat, c->mic_feat, 0, hist_bytes, (size_t)count, c->own));
+	}
+	if (c->filter) ED_HIP(ctx, hipMemsetAsync(c->d_state + (size_t)m * c->n_out, 0, sizeof(float) * (size_t)count * c->n_out, c->own));
+	if (c->fsm)
+	{
+		edison_fsm start;
+		edison_fsm_init(&start); /* EDI_RESET, as the firmware enters its continuous loop (app.c:288-300) */
+		for (int i = 0; i < count; i++)
+			ED_HIP(ctx, hipMemcpyAsync(c->d_fsm + m + i, &start, sizeof(start), hipMemcpyHostToDevice, c->own));
+	}
+	return EDISON_OK;
+}
+
+int ed_stream_core_reset_mic(ed_stream_core *c, int mic)
+{
+	if (!c) return EDISON_E_ARGUMENT;
+	if (mic < 0 || mic >= c->n_mics) return core_err(c->ctx, c->who, EDISON_E_ARGUMENT, "microphone index out of range");
+	{ const int r = order_after(c, c->own); if (r != EDISON_OK) return r; }
+	{ const int r = start_state(c, mic, 1); if (r != EDISON_OK) return r; }
+	ED_HIP(c->ctx, hipStreamSynchronize(c->own));
+	c->q_pending = 0;
+	return EDISON_OK;
+}
+
 int ed_stream_core_reset(ed_stream_core *c)
 {
 	if (!c) return EDISON_E_ARGUMENT;
 	edison_ctx *ctx = c->ctx;
 	{ const int r = order_after(c, c->own); if (r != EDISON_OK) return r; }
 	c->pos = 0;
-	if (c->tail) ED_HIP(ctx, hipMemsetAsync(c->d_audio, 0, sizeof(int16_t) * (size_t)c->tail, c->own));
-	if (c->F > 1) ED_HIP(ctx, hipMemsetAsync(c->d_feat, 0, (size_t)c->feat_elem * (size_t)(c->F - 1) * c->nm, c->own)); /* float: +0.0f rows */
+	{ const int r = start_state(c, 0, c->n_mics); if (r != EDISON_OK) return r; }
 	ED_HIP(ctx, hipMemsetAsync(c->d_out, 0, c->out_bytes, c->own));
-	if (c->filter) ED_HIP(ctx, hipMemsetAsync(c->d_state, 0, sizeof(float) * (size_t)c->n_out, c->own));
-	if (c->fsm)
-	{
-		edison_fsm start;
-		edison_fsm_init(&start); /* EDI_RESET, as the firmware enters its continuous loop (app.c:288-300) */
-		ED_HIP(ctx, hipMemcpyAsync(c->d_fsm, &start, sizeof(start), hipMemcpyHostToDevice, c->own));
-	}
 	ED_HIP(ctx, hipStreamSynchronize(c->own));
 	memset(c->h_out, 0, c->out_bytes);
 	c->q_pending = 0;
@@ -219,9 +252,12 @@ int ed_stream_core_begin_push(ed_stream_core *c, hipStream_t q, const int16_t *s
 	{ const int r = order_after(c, q); if (r != EDISON_OK) return r; }
 	{ const int r = make_room(c, q, n); if (r != EDISON_OK) return r; }
 	const size_t bytes = sizeof(int16_t) * (size_t)n * c->hop;
-	if (host) memcpy(c->h_in, samples, bytes);
-	ED_HIP(c->ctx, hipMemcpyAsync(c->d_audio + (size_t)c->pos * c->hop + c->tail, host ? c->h_in : samples, bytes,
-	                              host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, q));
+	if (host) memcpy(c->h_in, samples, bytes * (size_t)c->n_mics);
+	int16_t *dst = c->d_audio + (size_t)c->pos * c->hop + c->tail;
+	const int16_t *src = host ? c->h_in : samples;
+	const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+	if (c->n_mics == 1) ED_HIP(c->ctx, hipMemcpyAsync(dst, src, bytes, kind, q));
+	else ED_HIP(c->ctx, hipMemcpy2DAsync(dst, sizeof(int16_t) * c->mic_audio, src, bytes, bytes, (size_t)c->n_mics, kind, q)); /* a row per microphone */
 	return EDISON_OK;
 }
 
@@ -239,7 +275,10 @@ int ed_stream_core_finish_push(ed_stream_core *c, hipStream_t q, const void *fin
 		}
 		float *filt = (float *)(o + c->off_filt);
 		int32_t *likely = (int32_t *)(o + c->off_likely), *spotted = (int32_t *)(o + c->off_spotted);
-		if (c->out_elem == 1)
+		if (c->n_mics > 1)
+			ed_stream_bank_launch_filter(q, c->n_mics, (const int8_t *)fin, n, c->n_out, c->alpha, c->one_minus_alpha, c->threshold, c->d_state, filt,
+			                             likely, spotted, fs);
+		else if (c->out_elem == 1)
 			hipLaunchKernelGGL(ed_stream_geom_filter_kernel<int8_t>, dim3(1), dim3(256), 0, q, (const int8_t *)fin, n, c->n_out, c->alpha,
 			                   c->one_minus_alpha, c->threshold, c->d_state, filt, likely, spotted, fs);
 		else
@@ -288,7 +327,7 @@ int ed_stream_core_filtered(ed_stream_core *c, float *filt, int32_t *likely, int
 {
 	if (!c) return EDISON_E_ARGUMENT;
 	if (!c->filter) return core_err(c->ctx, c->who, EDISON_E_ARGUMENT, "created without the output filter");
-	const size_t n = (size_t)c->last_n;
+	const size_t n = (size_t)c->last_n * (size_t)c->n_mics;
 	const edsg_piece p[3] = {{filt, c->off_filt, n * (size_t)c->n_out * sizeof(float)}, {likely, c->off_likely, n * sizeof(int32_t)},
 	                         {spotted, c->off_spotted, n * sizeof(int32_t)}};
 	return copy_out(c, p, 3, host);
@@ -298,6 +337,7 @@ int ed_stream_core_fsm(ed_stream_core *c, edison_fsm *fsm, int32_t *states, int 
 {
 	if (!c) return EDISON_E_ARGUMENT;
 	if (!c->fsm) return core_err(c->ctx, c->who, EDISON_E_ARGUMENT, "created without the state machine (opts.fsm)");
-	const edsg_piece p[2] = {{states, c->off_states, (size_t)c->last_n * sizeof(int32_t)}, {fsm, c->off_fsm, sizeof(edison_fsm)}};
-	return copy_out(c, p, host ? 2 : 1, host);
+	const size_t mics = (size_t)c->n_mics;
+	const edsg_piece p[2] = {{states, c->off_states, (size_t)c->last_n * mics * sizeof(int32_t)}, {fsm, c->off_fsm, mics * sizeof(edison_fsm)}};
+	return copy_out(c, p, 2, host);
 }

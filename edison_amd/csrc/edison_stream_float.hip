@@ -126,7 +126,7 @@ extern "C" int edison_stream_float_create(edison_ctx *ctx, const edison_kws_geom
 	s->fnet_epoch = ctx->fnet_epoch;
 	s->off_probs = (size_t)o->chunk_frames * n_out * sizeof(float);          /* logits at 0 */
 	s->off_argmax = 2 * s->off_probs;
-	int r = ed_stream_core_create(&s->core, ctx, "stream_float", sizeof(float), sizeof(float), g, F, n_out, &co,
+	int r = ed_stream_core_create(&s->core, ctx, "stream_float", sizeof(float), sizeof(float), g, F, n_out, 1, &co,
 	                              s->off_argmax + (size_t)o->chunk_frames * sizeof(int32_t));
 	if (r == EDISON_OK && !s->q15) r = ed_geom_tables_build(ctx, g, &s->tab);
 	if (r != EDISON_OK) { edison_stream_float_destroy(s); return r; }

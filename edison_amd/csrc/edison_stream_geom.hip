@@ -17,23 +17,17 @@
 #include <new>
 
 #include "edison_ctx.h"
-#include "edison_stream_core.h"
-#include "mfcc_geom.h"
+#include "edison_stream_geom.h"
 
-struct edison_stream_geom
+struct edison_stream_geom : ed_stream_geom_part
 {
 	ed_stream_core core;           /* int8 rows, int8 outputs */
-	int has_softmax;
-	ed_geom_cache tab;             /* this stream's own tables (edison_kws_geom.hip builds them) */
-	ed_geom_args_t margs;          /* tab.tmpl with the per-geometry fields; audio, feat and the frame counts are set per push */
 	size_t off_soft, off_argmax;   /* the front of the core's output block: logits at 0, softmax (graphs that have one), argmax */
-	int model_epoch;
 };
 
 static ed_stream_core *core_of(edison_stream_geom *s) { return s ? &s->core : NULL; }
 
-/* the network on the kernel edison_net_batch_dev picks for the loaded graph, on hipStream q */
-static int net_on(edison_ctx *ctx, hipStream_t q, const int8_t *in, int n, int64_t stride, int8_t *logits, int8_t *softmax, int32_t *argmax)
+int ed_stream_geom_net_on(edison_ctx *ctx, hipStream_t q, const int8_t *in, int n, int64_t stride, int8_t *logits, int8_t *softmax, int32_t *argmax)
 {
 	const char *fg_ = getenv("EDISON_NET_FORCE_GENERAL"); /* read per call, as edison_net_batch_dev does */
 	const int force_general = fg_ ? atoi(fg_) : 0;
@@ -55,16 +49,21 @@ static int enqueue_push(edison_stream_geom *s, hipStream_t q, int n, int8_t *log
 	a.n_frames = n;
 	a.feat = win + (size_t)(c->F - 1) * c->nm;
 	{ const int e = ed_launch_mfcc_geom(&a, ctx->n_cu, q); if (e != 0) return ed_launch_result(ctx, e, "MFCC geometry kernel"); }
-	{ const int r = net_on(ctx, q, win, n, c->nm, logits, softmax, argmax); if (r != EDISON_OK) return r; }
+	{ const int r = ed_stream_geom_net_on(ctx, q, win, n, c->nm, logits, softmax, argmax); if (r != EDISON_OK) return r; }
 	return ed_stream_core_finish_push(c, q, fin, n, host);
 }
 
 static int check_push(edison_stream_geom *s, const int16_t *samples)
 {
 	if (!s || !samples) return EDISON_E_ARGUMENT;
-	if (s->model_epoch != s->core.ctx->model_epoch)
-		return ed_set_err(s->core.ctx, EDISON_E_ARGUMENT, "stream_geom: the model was reloaded after this stream was created; create a new stream");
-	return EDISON_OK;
+	return ed_stream_geom_part_check(s->core.ctx, "stream_geom", s);
+}
+
+int ed_stream_geom_part_check(edison_ctx *ctx, const char *who, const ed_stream_geom_part *p)
+{
+	if (p->model_epoch == ctx->model_epoch) return EDISON_OK;
+	snprintf(ctx->err, sizeof(ctx->err), "%s: the model was reloaded after this stream was created; create a new stream", who);
+	return EDISON_E_ARGUMENT;
 }
 
 extern "C" void edison_stream_geom_default_opts(edison_stream_geom_opts *o)
@@ -80,47 +79,73 @@ extern "C" void edison_stream_geom_destroy(edison_stream_geom *s)
 {
 	if (!s) return;
 	ed_stream_core_free(&s->core);
-	if (s->tab.d) (void)hipFree(s->tab.d);
+	ed_stream_geom_part_free(s);
 	delete s;
 }
 
 extern "C" int edison_stream_geom_reset(edison_stream_geom *s) { return ed_stream_core_reset(core_of(s)); }
+
+static int part_err(edison_ctx *ctx, const char *who, int code, const char *what)
+{
+	snprintf(ctx->err, sizeof(ctx->err), "%s: %s", who, what);
+	return code;
+}
+
+int ed_stream_geom_check_create(edison_ctx *ctx, const char *who, const edison_kws_geom *g, const edison_stream_geom_opts *o, int *F,
+                                ed_stream_core_opts *co)
+{
+	{ const int r = ed_kws_geom_check(ctx, g, F); if (r != EDISON_OK) return r; }
+	if (!ctx->have_model) return ed_set_err(ctx, EDISON_E_NO_MODEL, "no CNN model loaded (edison_model_load)");
+	if ((int64_t)*F * g->num_mfcc != ctx->net.in_n)
+	{
+		snprintf(ctx->err, sizeof(ctx->err), "%s: frame_count x num_mfcc = %lld features, the graph's input in_h x in_w x in_c = %d", who,
+		         (long long)*F * g->num_mfcc, ctx->net.in_n);
+		return EDISON_E_SIZE;
+	}
+	*co = {o->chunk_frames, o->filter, o->fsm, o->filter_alpha, o->true_threshold};
+	{ const int r = ed_stream_core_check_opts(ctx, who, g, co); if (r != EDISON_OK) return r; }
+	if (o->filter && ctx->net.out_n > EDSG_FILTER_MAX_OUT)
+		return part_err(ctx, who, EDISON_E_NO_IMPL, "the output filter serves graphs of at most 256 outputs");
+	if (o->fsm && ctx->net.out_n != EDISON_NET_OUT)
+		return part_err(ctx, who, EDISON_E_NO_IMPL, "the state machine needs a graph with 10 outputs (the keyword list its roles index)");
+	return EDISON_OK;
+}
+
+int ed_stream_geom_part_init(edison_ctx *ctx, const edison_kws_geom *g, ed_stream_geom_part *p)
+{
+	p->has_softmax = ctx->net.has_softmax;
+	p->model_epoch = ctx->model_epoch;
+	{ const int r = ed_geom_tables_build(ctx, g, &p->tab); if (r != EDISON_OK) return r; }
+	p->margs = p->tab.tmpl;
+	p->margs.utt_stride = 0;
+	p->margs.frame_step = g->frame_step;
+	p->margs.take_log = (g->variant & 0xff) == EDISON_MFCC_A || (g->variant & EDISON_MFCC_USE_LOG);
+	p->margs.feat_scale = (float)g->net_input_scale;
+	return EDISON_OK;
+}
+
+void ed_stream_geom_part_free(ed_stream_geom_part *p)
+{
+	if (p->tab.d) (void)hipFree(p->tab.d);
+	p->tab.d = NULL;
+}
 
 extern "C" int edison_stream_geom_create(edison_ctx *ctx, const edison_kws_geom *g, const edison_stream_geom_opts *o, edison_stream_geom **out)
 {
 	if (!ctx || !g || !o || !out) return EDISON_E_ARGUMENT;
 	*out = NULL;
 	int F = 0;
-	{ const int r = ed_kws_geom_check(ctx, g, &F); if (r != EDISON_OK) return r; }
-	if (!ctx->have_model) return ed_set_err(ctx, EDISON_E_NO_MODEL, "no CNN model loaded (edison_model_load)");
-	if ((int64_t)F * g->num_mfcc != ctx->net.in_n)
-	{
-		snprintf(ctx->err, sizeof(ctx->err), "stream_geom: frame_count x num_mfcc = %lld features, the graph's input in_h x in_w x in_c = %d",
-		         (long long)F * g->num_mfcc, ctx->net.in_n);
-		return EDISON_E_SIZE;
-	}
-	const ed_stream_core_opts co = {o->chunk_frames, o->filter, o->fsm, o->filter_alpha, o->true_threshold};
-	{ const int r = ed_stream_core_check_opts(ctx, "stream_geom", g, &co); if (r != EDISON_OK) return r; }
-	if (o->filter && ctx->net.out_n > EDSG_FILTER_MAX_OUT)
-		return ed_set_err(ctx, EDISON_E_NO_IMPL, "stream_geom: the output filter serves graphs of at most 256 outputs");
-	if (o->fsm && ctx->net.out_n != EDISON_NET_OUT)
-		return ed_set_err(ctx, EDISON_E_NO_IMPL, "stream_geom: the state machine needs a graph with 10 outputs (the keyword list its roles index)");
+	ed_stream_core_opts co;
+	{ const int r = ed_stream_geom_check_create(ctx, "stream_geom", g, o, &F, &co); if (r != EDISON_OK) return r; }
 
 	edison_stream_geom *s = new (std::nothrow) edison_stream_geom();
 	if (!s) return ed_set_err(ctx, EDISON_E_NO_MEMORY, "host allocation failed");
-	s->has_softmax = ctx->net.has_softmax;
-	s->model_epoch = ctx->model_epoch;
 	const size_t cn = (size_t)o->chunk_frames * ctx->net.out_n;               /* logits at 0 */
 	s->off_soft = cn;
-	s->off_argmax = ed_stream_core_align(cn + (s->has_softmax ? cn : 0));
-	int r = ed_stream_core_create(&s->core, ctx, "stream_geom", 1, 1, g, F, ctx->net.out_n, &co, s->off_argmax + (size_t)o->chunk_frames * sizeof(int32_t));
-	if (r == EDISON_OK) r = ed_geom_tables_build(ctx, g, &s->tab);
+	s->off_argmax = ed_stream_core_align(cn + (ctx->net.has_softmax ? cn : 0));
+	int r = ed_stream_core_create(&s->core, ctx, "stream_geom", 1, 1, g, F, ctx->net.out_n, 1, &co, s->off_argmax + (size_t)o->chunk_frames * sizeof(int32_t));
+	if (r == EDISON_OK) r = ed_stream_geom_part_init(ctx, g, s);
 	if (r != EDISON_OK) { edison_stream_geom_destroy(s); return r; }
-	s->margs = s->tab.tmpl;
-	s->margs.utt_stride = 0;
-	s->margs.frame_step = g->frame_step;
-	s->margs.take_log = (g->variant & 0xff) == EDISON_MFCC_A || (g->variant & EDISON_MFCC_USE_LOG);
-	s->margs.feat_scale = (float)g->net_input_scale;
 	*out = s;
 	return EDISON_OK;
 }

@@ -11,7 +11,8 @@
 /* ---- audio -> network input at any MFCC geometry (mfcc_geom_kernels.hip, edison_kws_geom.hip) ------------
  * Variants A / B, float64 throughout. Frame g of the call is frame f = g % frames_per_utt of utterance u = g / frames_per_utt: its
  * samples start at audio + u * utt_stride + f * frame_step, its int8 features land at feat + g * n_coef (the flat [frames][num_mfcc]
- * vector the reference reshapes to the graph's input). The transform is a Stockham FFT over M complex points with the radices in
+ * vector the reference reshapes to the graph's input) -- or, with feat_utt_stride != 0, at feat + u * feat_utt_stride + f * n_coef:
+ * every utterance's rows in a buffer of its own (the microphones of edison_stream_bank.hip). The transform is a Stockham FFT over M complex points with the radices in
  * `radix` (M = N/2 with the real frame packed into complex pairs when N is even, M = N when N is odd), or a direct DFT when M has a
  * prime factor above 5 (M = 0). */
 #define ED_GEOM_MAX_STAGES 16
@@ -32,6 +33,7 @@ typedef struct {
 	const double *dct;                 /* [n_coef][n_mel] 2 cos(pi c (2 n + 1) / (2 n_mel)), c = first_mfcc + row */
 	int8_t *feat;
 	float feat_scale;
+	int64_t feat_utt_stride;           /* int8 features only: bytes from one utterance's rows to the next's; 0: contiguous, frames_per_utt * n_coef */
 } ed_geom_args_t;
 
 /* The filterbank / twiddle / DCT tables of one geometry on the device and the kernel's launch template (edison_kws_geom.hip builds

@@ -11,7 +11,8 @@
  *   4. spectrum s[k] = |X[k] * fft_scale| * spec_scale for the variant's n_bins bins (A: N/2 bins, 1, 1; B: N/2 + 1 bins, 1/1024, 1/sqrt 2)
  *   5. mel: band j = sum of its nonzero run of the filterbank in ascending k, / mel_div; ln(x + 1e-6) for A and B with use_log
  *   6. DCT-II rows first_mfcc .. first_mfcc + num_mfcc - 1 over dct_div (A sqrt(2 mel_nbins), B 64); feature = int8 of
- *      rint(clip((float)y * feat_scale, -128, 127)) (kws_nnom.py:359-361), written to feat + g * num_mfcc + row
+ *      rint(clip((float)y * feat_scale, -128, 127)) (kws_nnom.py:359-361), written to feat + g * num_mfcc + row (utterance u's rows
+ *      to feat + u * feat_utt_stride where that stride is given)
  *      -- or, in the float64 instance (ed_mfcc_geom_f64_kernel, edison_mfcc_geom_batch*), y itself to mfcc + g * num_mfcc + row
  *      -- or, in the float network-input instance (mfcc_geom_fnet_kernels.hip, edison_stream_float), min(max((float)y * scale, lo), hi)
  *
@@ -24,10 +25,12 @@
 
 template <int TEAM> __global__ __launch_bounds__(EDG_BLOCK) void ed_mfcc_geom_kernel(ed_geom_args_t a)
 {
+	/* what utterance u's rows lie behind their contiguous place (u = the frame loop's utterance index); 0 for feat_utt_stride = 0 */
+	const int64_t feat_skip = a.feat_utt_stride ? a.feat_utt_stride - (int64_t)a.frames_per_utt * a.n_coef : 0;
 #define EDG_STORE(i, y)                                                                        \
 	{                                                                                          \
 		const float v = fminf(fmaxf((float)(y) * a.feat_scale, -128.0f), 127.0f);            \
-		a.feat[i] = (int8_t)rintf(v);                                                          \
+		a.feat[(i) + feat_skip * u] = (int8_t)rintf(v);                                        \
 	}
 #include "mfcc_geom_frames.inc"
 #undef EDG_STORE

@@ -13,7 +13,7 @@ import numpy as np
 
 from .. import config as cfg
 from ..context import KEYWORDS, default_context
-from ..stream import FloatStream, Fsm, GeomStream, Stream
+from ..stream import FloatStream, Fsm, GeomStream, Stream, StreamBank
 from .kws_host import read_wav
 
 
@@ -33,7 +33,12 @@ def run(path, q15=False, ctx=None, out=None, alpha=None, threshold=0.5, geometry
     (float64 features, q15 does not apply); the state machine runs, and its lines are printed, only for a graph with 10 outputs.
     net (an .ednf path or its bytes): the float32 X-CUBE-AI network, loaded on ctx, on a FloatStream (host flow at `geometry`, default
     audio/config.py's; q15: the firmware's flow); class names from the .ednf. alpha: the moving average's, default 0.9 for the int8
-    graph (app.c:38) and 0.5 for the float network (app.c:35-36)."""
+    graph (app.c:38) and 0.5 for the float network (app.c:35-36).
+    path may be a list of wav files, with geometry: the microphones of one StreamBank (run_bank)."""
+    if not isinstance(path, (str, bytes)) and hasattr(path, "__len__"):
+        if len(path) != 1:
+            return run_bank(path, ctx=ctx, out=out, alpha=alpha, threshold=threshold, geometry=geometry, net=net, q15=q15)
+        path = path[0]
     out = out or sys.stdout
     ctx = ctx or default_context()
     if alpha is None:
@@ -67,15 +72,23 @@ def run(path, q15=False, ctx=None, out=None, alpha=None, threshold=0.5, geometry
         shown = res["probs"]
     else:
         shown = res["softmax"] if res["softmax"] is not None else res["logits"]   # what the filter averaged
+    events, before = _print_hops(out, n, shown, res["likely"], res["spotted"], res["fsm_states"] if with_fsm else None, name)
+    if with_fsm:
+        assert len(events) == res["fsm"]["commands"]
+    return dict(result=res, commands=events, state=before if with_fsm else None)
+
+
+def _print_hops(out, n, shown, likelies, spotteds, fsm_states, name):
+    """One line per hop, the firmware's UART log (app.c:330-353); fsm_states None: no state machine. Returns (commands, last state)."""
     events = []
     before, loc, val = "RESET", -1, -1
     for i in range(n):
-        likely, spotted = int(res["likely"][i]), int(res["spotted"][i])
+        likely, spotted = int(likelies[i]), int(spotteds[i])
         line = "pred: [ " + " ".join("%2.2f" % float(v) for v in shown[i]) + " ] likely: %s" % name(likely)
         if spotted >= 0:
             line += " spotted %s" % name(spotted)
-        if with_fsm:
-            after = Fsm.STATES[int(res["fsm_states"][i])]
+        if fsm_states is not None:
+            after = Fsm.STATES[int(fsm_states[i])]
             if after != before:
                 line += "   [FSM %s -> %s]" % (before, after)
             if before == "HOT" and after == "LOC":
@@ -87,9 +100,36 @@ def run(path, q15=False, ctx=None, out=None, alpha=None, threshold=0.5, geometry
                 events.append((KEYWORDS[loc], KEYWORDS[val]))
             before = after
         print(line, file=out)
-    if with_fsm:
-        assert len(events) == res["fsm"]["commands"]
-    return dict(result=res, commands=events, state=before if with_fsm else None)
+    return events, before
+
+
+def run_bank(paths, ctx=None, out=None, alpha=None, threshold=0.5, geometry=None, net=None, q15=False):
+    """Several wav files as the microphones of one StreamBank at `geometry` (the int8 graph only): the shorter recordings are padded
+    with silence to the longest, all advance in one push. Per microphone a heading line ``mic <m>: <path>`` and then the lines run()
+    prints for that file alone, for the hops of its own recording. Returns dict(result, mics=[dict(commands, state)])."""
+    if geometry is None or net is not None or q15:
+        raise ValueError("several recordings run as one bank: the int8 graph at a geometry (geometry=..., no net, no q15)")
+    out = out or sys.stdout
+    ctx = ctx or default_context()
+    hop = int(geometry.frame_step)
+    datas = [read_wav(p) for p in paths]
+    hops = [-(-d.shape[0] // hop) for d in datas]
+    n = max(hops)
+    x = np.stack([np.pad(d, (0, n * hop - d.shape[0])) for d in datas])
+    with_fsm = ctx.net_info()["n_out"] == len(KEYWORDS)
+    bank = StreamBank(ctx, geometry, len(paths), chunk_frames=n, output_filter=True, alpha=0.9 if alpha is None else alpha,
+                      threshold=threshold, fsm=with_fsm)
+    res = bank.push(x)
+    bank.close()
+    shown = res["softmax"] if res["softmax"] is not None else res["logits"]
+    name = (lambda i: KEYWORDS[i]) if with_fsm else (lambda i: "class %d" % i)
+    mics = []
+    for m, p in enumerate(paths):
+        print("mic %d: %s" % (m, p), file=out)
+        events, before = _print_hops(out, hops[m], shown[:, m], res["likely"][:, m], res["spotted"][:, m],
+                                     res["fsm_states"][:, m] if with_fsm else None, name)
+        mics.append(dict(commands=events, state=before if with_fsm else None))
+    return dict(result=res, mics=mics)
 
 
 def main(argv):

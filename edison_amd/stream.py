@@ -47,10 +47,13 @@ class _Handle:
 
     def fsm_snapshot(self):
         """The state machine as the last edison_stream*_fsm call saw it: dict(state, hot_timeout_ms, last_command, commands)."""
-        f = self._fsm
-        cmd = None if f.last_loc < 0 else (KEYWORDS[f.last_loc], KEYWORDS[f.last_val])
-        return dict(state=Fsm.STATES[f.state], hot_timeout_ms=int(f.hot_timeout_ms), last_command=cmd, commands=int(f.commands),
-                    raw=(f.state, f.hot_timeout_ms, f.wake_idx, f.loc_idx, f.val_idx, f.last_loc, f.last_val, f.commands))
+        return _fsm_dict(self._fsm)
+
+
+def _fsm_dict(f):
+    cmd = None if f.last_loc < 0 else (KEYWORDS[f.last_loc], KEYWORDS[f.last_val])
+    return dict(state=Fsm.STATES[f.state], hot_timeout_ms=int(f.hot_timeout_ms), last_command=cmd, commands=int(f.commands),
+                raw=(f.state, f.hot_timeout_ms, f.wake_idx, f.loc_idx, f.val_idx, f.last_loc, f.last_val, f.commands))
 
 
 class _SlidingStream(_Handle):
@@ -211,6 +214,91 @@ class GeomStream(_SlidingStream):
         """Device tensors (torch, int16 / int8 / int32 / fp32 on the context's GPU); asynchronous on the context's stream. n_frames <
         chunk_frames: a ragged last push of n_frames * hop samples; every output is [n_frames][..]."""
         self._push_t(samples, logits, softmax, argmax, filtered, likely, spotted, n_frames)
+
+
+class StreamBank(_Handle):
+    """Many microphones through one graph -- Python handle on ``edison_stream_bank_*``: ``n_mics`` continuous streams at one geometry
+    on the loaded graph, advancing in lockstep. Microphone m behaves exactly as a ``GeomStream`` of its own fed microphone m's samples;
+    a push costs a number of launches that does not depend on ``n_mics``. Outputs are time-major, [frames of the push][n_mics][..]."""
+
+    _C = "edison_stream_bank_"
+
+    def __init__(self, ctx, geometry, n_mics, chunk_frames=1, output_filter=False, alpha=0.9, threshold=0.5, fsm=False):
+        self.ctx = ctx or default_context()
+        self._L = _lib.lib()
+        o = _lib.StreamBankOpts()
+        self._L.edison_stream_bank_default_opts(ctypes.byref(o))
+        o.n_mics = int(n_mics)
+        o.stream.chunk_frames = int(chunk_frames)
+        o.stream.filter = 1 if (output_filter or fsm) else 0
+        o.stream.fsm = 1 if fsm else 0
+        o.stream.filter_alpha, o.stream.true_threshold = float(alpha), float(threshold)
+        g = geometry.to_ctypes()
+        h = ctypes.c_void_p()
+        self.ctx._check(self._L.edison_stream_bank_create(self.ctx._h, ctypes.byref(g), ctypes.byref(o), ctypes.byref(h)))
+        self._h = h
+        info = self.ctx.net_info()
+        self.geometry = geometry
+        self.n_mics, self.hop, self.chunk = int(n_mics), int(geometry.frame_step), int(chunk_frames)
+        self.n_out, self.has_softmax = int(info["n_out"]), bool(info["has_softmax"])
+        self.output_filter, self.fsm = bool(output_filter or fsm), bool(fsm)
+        self._fsms = (_lib.Fsm * self.n_mics)()
+
+    def frames_seen(self):
+        """Frames pushed per microphone since the bank was made or reset."""
+        n = ctypes.c_int64()
+        self.ctx._check(self._c("frames_seen")(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def reset_mic(self, m):
+        """Microphone m alone back to a new stream's state; the others do not notice."""
+        self.ctx._check(self._c("reset_mic")(self._h, int(m)))
+
+    def fsm_snapshot(self):
+        """The state machines as the last host push saw them: one ``GeomStream.fsm_snapshot`` dict per microphone."""
+        return [_fsm_dict(f) for f in self._fsms]
+
+    def push(self, samples):
+        """samples: [n_mics, chunk_frames * hop] new int16 samples (host). Returns ``GeomStream.push``'s dict with the microphone axis
+        added: logits / softmax [chunk][n_mics][n_out] (softmax None for a graph without Softmax), argmax [chunk][n_mics], ``keywords``
+        [chunk][n_mics] for a graph with 10 outputs; with the filter filtered [chunk][n_mics][n_out] fp32, likely, spotted
+        [chunk][n_mics]; with the state machine fsm_states [chunk][n_mics] and fsm, a list of n_mics snapshots."""
+        x = np.ascontiguousarray(samples, dtype=np.int16)
+        if x.shape != (self.n_mics, self.chunk * self.hop):
+            raise ValueError("push needs [n_mics, chunk_frames*hop] = [%d, %d] samples" % (self.n_mics, self.chunk * self.hop))
+        c, m, no = self.chunk, self.n_mics, self.n_out
+        lo, am = np.zeros((c, m, no), np.int8), np.zeros((c, m), np.int32)
+        so = np.zeros((c, m, no), np.int8) if self.has_softmax else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self.ctx._check(self._c("push")(self._h, x.ctypes.data, lo.ctypes.data, ptr(so), am.ctypes.data))
+        out = dict(logits=lo, softmax=so, argmax=am)
+        if no == NET_OUT:
+            out["keywords"] = [[KEYWORDS[i] for i in row] for row in am]
+        if self.output_filter:
+            fl, li, sp = np.zeros((c, m, no), np.float32), np.zeros((c, m), np.int32), np.zeros((c, m), np.int32)
+            self.ctx._check(self._c("filtered")(self._h, fl.ctypes.data, li.ctypes.data, sp.ctypes.data))
+            out.update(filtered=fl, likely=li, spotted=sp)
+        if self.fsm:
+            st = np.zeros((c, m), np.int32)
+            self.ctx._check(self._c("fsm")(self._h, ctypes.byref(self._fsms), st.ctypes.data))
+            out.update(fsm_states=st, fsm=self.fsm_snapshot())
+        return out
+
+    def push_t(self, samples, logits=None, softmax=None, argmax=None, filtered=None, likely=None, spotted=None, fsm_states=None, n_frames=None):
+        """Device tensors (torch, int16 / int8 / int32 / fp32 on the context's GPU); asynchronous on the context's stream. samples
+        [n_mics][n * hop]; every output [n][n_mics][..] with n = chunk_frames, or n_frames <= chunk_frames for a ragged push."""
+        n = self.chunk if n_frames is None else int(n_frames)
+        if samples.numel() != self.n_mics * n * self.hop or not samples.is_contiguous():
+            raise ValueError("push needs contiguous [n_mics, n_frames*hop] = [%d, %d] samples" % (self.n_mics, n * self.hop))
+        q = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        if n_frames is None:
+            self.ctx._check(self._c("push_dev")(self._h, q(samples), q(logits), q(softmax), q(argmax)))
+        else:
+            self.ctx._check(self._c("push_n_dev")(self._h, q(samples), n, q(logits), q(softmax), q(argmax)))
+        if filtered is not None or likely is not None or spotted is not None:
+            self.ctx._check(self._c("filtered_dev")(self._h, q(filtered), q(likely), q(spotted)))
+        if fsm_states is not None:
+            self.ctx._check(self._c("fsm_dev")(self._h, None, q(fsm_states)))
 
 
 class FloatStream(_SlidingStream):

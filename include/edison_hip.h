@@ -583,6 +583,47 @@ int edison_stream_geom_filtered_dev(edison_stream_geom *s, float *filt, int32_t 
 int edison_stream_geom_fsm(edison_stream_geom *s, struct edison_fsm *fsm, int32_t *states);
 int edison_stream_geom_fsm_dev(edison_stream_geom *s, int32_t *states);
 
+/* ---- a bank of continuous streams: one push advances many microphones through one graph ----------------------------------
+ * n_mics independent continuous streams at ONE geometry on the loaded graph, advancing in lockstep: microphone m behaves exactly as an
+ * edison_stream_geom of its own, created with the same geometry, options and model and fed microphone m's samples -- logits, softmax,
+ * argmax, filtered outputs, likely, spotted, the state machine and frames_seen, byte for byte. One push carries n frames for every
+ * microphone and costs a number of launches that does not depend on n_mics (one MFCC launch, n network launches, one filter launch).
+ *   samples         [n_mics][n * frame_step] int16: each microphone's new samples contiguous, microphone after microphone.
+ *   outputs         time-major: logits / softmax [n][n_mics][n_out] int8, argmax [n][n_mics] int32; filt [n][n_mics][n_out] fp32,
+ *                   likely / spotted / states [n][n_mics] int32; the state machines fsm [n_mics]. For the usual n = 1 that is simply
+ *                   [n_mics][..]. Each may be NULL; softmax is not written for a graph without Softmax.
+ *   reset_mic       microphone `mic` alone back to a new stream's state (silent history, zero filter state, edisonFSM in RESET): from
+ *                   the next push on it equals a freshly created stream; the other microphones do not notice. Ordered like a push: it
+ *                   waits for device pushes still in flight and has taken effect when it returns. frames_seen is the bank's and stays.
+ * Errors of create: those of edison_stream_geom_create, and EDISON_E_ARGUMENT for n_mics outside 1 .. 4096; EDISON_E_NO_MEMORY when the
+ * buffers (n_mics times a stream's) cannot be allocated. A push after a model reload fails with EDISON_E_ARGUMENT; so does n_frames
+ * outside 1 .. chunk_frames and a microphone index outside 0 .. n_mics - 1. NULL handles: EDISON_E_ARGUMENT. Messages name stream_bank.
+ * Host and device pushes may alternate, as edison_stream_geom's; the getters copy the LAST push's outputs (n = its frames). */
+typedef struct edison_stream_bank edison_stream_bank;
+typedef struct edison_stream_bank_opts {
+	int n_mics;                      /* microphones, 1 .. 4096 */
+	edison_stream_geom_opts stream;  /* every microphone's options */
+} edison_stream_bank_opts;
+/* n_mics 1, stream = edison_stream_geom_default_opts */
+void edison_stream_bank_default_opts(edison_stream_bank_opts *o);
+int edison_stream_bank_create(edison_ctx *ctx, const edison_kws_geom *g, const edison_stream_bank_opts *o, edison_stream_bank **out);
+void edison_stream_bank_destroy(edison_stream_bank *b);
+int edison_stream_bank_reset(edison_stream_bank *b);
+int edison_stream_bank_reset_mic(edison_stream_bank *b, int mic);
+/* chunk_frames frames per microphone: samples [n_mics][chunk_frames * frame_step] */
+int edison_stream_bank_push(edison_stream_bank *b, const int16_t *samples /* host */, int8_t *logits, int8_t *softmax, int32_t *argmax);
+int edison_stream_bank_push_dev(edison_stream_bank *b, const int16_t *samples /* device */, int8_t *logits, int8_t *softmax, int32_t *argmax);
+/* 1 <= n_frames <= chunk_frames frames per microphone: samples [n_mics][n_frames * frame_step], outputs [n_frames][n_mics][..] */
+int edison_stream_bank_push_n_dev(edison_stream_bank *b, const int16_t *samples /* device */, int n_frames, int8_t *logits, int8_t *softmax,
+                                  int32_t *argmax);
+int edison_stream_bank_filtered(edison_stream_bank *b, float *filt, int32_t *likely, int32_t *spotted);
+int edison_stream_bank_filtered_dev(edison_stream_bank *b, float *filt, int32_t *likely, int32_t *spotted);
+/* the state machines after the LAST push (fsm [n_mics], may be NULL) and every microphone's state after each of its n inferences */
+int edison_stream_bank_fsm(edison_stream_bank *b, struct edison_fsm *fsm /* host */, int32_t *states);
+int edison_stream_bank_fsm_dev(edison_stream_bank *b, struct edison_fsm *fsm /* device */, int32_t *states);
+/* frames pushed per microphone since create or reset */
+int edison_stream_bank_frames_seen(edison_stream_bank *b, int64_t *out);
+
 /* ---- continuous mode for the float32 X-CUBE-AI network ------------------------------------------------------------------
  * The continuous counterpart of edison_kws_float_batch*: the firmware's continuous loop for its default network type, NET_TYPE_CUBE
  * (app.c:288-371, 630-719), on the float network loaded on the context (edison_fnet_load). A separate object: edison_stream_geom_* and
