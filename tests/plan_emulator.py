@@ -17,8 +17,9 @@ MM_LAYER = ("mm in_hp in_wp in_py in_px in_img expand x_img cpr n_ks n_rt pitch_
             "col_off xtab_off small n_ks16 n_rt16 pp toep").split()
 MM_RUN = ("kind zero_border in_img o_img o_origin o_row oc_pitch li_out expand x_img rec_per_img xtab_off pitch_x pitch_y sh ph pw n_ks n_rt "
           "frag_off seed_off koff_off col_off pix_per_img col_w out_c rs lo_clamp in_n small in_off o_off").split()
-MM_HEAD = "ok batch waves buf_bytes x_bytes lds_bytes frag_lds frag_mode tbl_bytes frag_bytes n_seeds n_koff n_cols n_xtab n_intab pad_".split()
-RUN_SKIP, RUN_MM, RUN_POOL4, RUN_POOL1, RUN_SOFTMAX = 0, 1, 2, 3, 4
+MM_HEAD = "ok batch waves buf_bytes x_bytes lds_bytes frag_lds frag_mode tbl_bytes frag_bytes n_seeds n_koff n_cols n_xtab n_intab hold_bytes".split()
+RUN_SKIP, RUN_MM, RUN_POOL4, RUN_POOL1, RUN_SOFTMAX, RUN_DW, RUN_AVG, RUN_MERGE, RUN_CAT = 0, 1, 2, 3, 4, 5, 6, 7, 8
+T_ADD, T_SUB, T_MULT = 7, 8, 9
 POISON = 0x55
 
 
@@ -37,7 +38,7 @@ class Plan:
     def __init__(self, blob):
         from edison_amd import _lib
         L = _lib.lib()
-        lay = [int(L.edison_net_plan_layout(i)) for i in range(12)]
+        lay = [int(L.edison_net_plan_layout(i)) for i in range(13)]
         assert lay[2] == 4 * len(NET_LAYER) and lay[3] == 4 * len(MM_LAYER) and lay[4] == 4 * len(MM_RUN), "struct layouts changed: update tests/plan_emulator.py"
         buf = ctypes.create_string_buffer(bytes(blob), len(blob))
         fneed, sneed = ctypes.c_size_t(), ctypes.c_size_t()
@@ -58,7 +59,10 @@ class Plan:
         self.koff = m32[lay[8] // 4:lay[9] // 4]
         self.coltab = m32[lay[9] // 4:lay[10] // 4]
         self.xtab = m32[lay[10] // 4:lay[11] // 4]
-        self.intab = np.frombuffer(mm.raw, np.uint16, offset=lay[11])
+        self.intab = np.frombuffer(mm.raw, np.uint16, count=(lay[12] - lay[11]) // 2, offset=lay[11])
+        self.msrc = m32[lay[12] // 4:]                    # five words per merge input: slice offset, image, origin, row, pixel pitch
+        import res_ref
+        self.src = res_ref.sources(bytes(blob))           # who reads what: the blob's own table, not the planner's reading of it
         self.frag = np.frombuffer(frag.raw[:fneed.value], np.int8)
         self.seeds = np.frombuffer(seeds.raw[:sneed.value], np.int32)
 
@@ -96,17 +100,114 @@ def _a_matrix(plan, R):
     return A, per
 
 
+def _c4(C):
+    """How the VALU passes move the C channels of a pixel (emm_ld_c4 / emm_st_c4): dwords when C % 4 == 0, else 16-bit words, the
+    last group of four a single one (`tail`) -- either way exactly the C bytes, at that alignment. An odd C has no such form."""
+    assert C % 2 == 0, "a VALU pass over an odd channel count"
+    return 4 if C % 4 == 0 else 2
+
+
+def _taps(n_out, n_in, s, pad, t):
+    """Output positions whose tap t lies inside the image, and the input positions they read (the kernel skips the others)."""
+    o = np.arange(n_out)
+    i = o * s - pad + t
+    keep = (i >= 0) & (i < n_in)
+    return o[keep], i[keep]
+
+
+def _valu(plan, S, li, R, a, o, nb):
+    """ED_RUN_DW / ED_RUN_AVG (cnn_net_mfma_kernels.hip:1095-1166): a compact input image, the output in o_origin / o_row / oc_pitch."""
+    L = plan.PL[li]
+    C, al = L.in_c, _c4(L.in_c)
+    c4n = (C + 3) // 4
+    ch = np.arange(C)
+    assert R.oc_pitch % al == 0 and R.o_row % al == 0 and R.o_origin % al == 0 and R.o_img % 16 == 0 and R.in_img % 16 == 0 and o % 16 == 0 and a % 16 == 0, \
+        "a VALU pass's %d-byte words are not aligned" % al
+    for b in range(nb):
+        acc = np.zeros((L.out_h, L.out_w, 4 * c4n), np.int64)
+        count = np.zeros((L.out_h, L.out_w, 1), np.int64)
+        if R.kind == RUN_DW:
+            acc += plan.seeds[R.seed_off:R.seed_off + 4 * c4n].astype(np.int64)
+        for ky in range(L.kh):
+            oy, iy = _taps(L.out_h, L.in_h, L.sh, L.pad_h, ky)
+            for kx in range(L.kw):
+                ox, ix = _taps(L.out_w, L.in_w, L.sw, L.pad_w, kx)
+                if not oy.size or not ox.size:
+                    continue
+                v = S.rd(a + b * R.in_img + ((iy[:, None] * L.in_w + ix[None, :]) * C)[:, :, None] + ch).astype(np.int64)
+                at = np.ix_(oy, ox, ch)
+                if R.kind == RUN_DW:                       # weights [tap][group of four] dwords at frag_off, zero beyond C
+                    w = plan.frag[R.frag_off + 4 * c4n * (ky * L.kw + kx):R.frag_off + 4 * c4n * (ky * L.kw + kx + 1)].astype(np.int64)
+                    assert w.size == 4 * c4n, "DW weights past the fragment buffer"
+                    acc[at] += v * w[:C]
+                else:
+                    acc[at] += v
+                    count[np.ix_(oy, ox, [0])] += 1
+        assert np.abs(acc).max() < 2 ** 31
+        if R.kind == RUN_DW:
+            out = np.clip(acc >> (R.rs & 0xff), R.lo_clamp, 127)          # emm_pack4
+        else:
+            count = np.maximum(count, 1)
+            out = np.sign(acc) * (np.abs(acc) // count)                   # C's division, toward zero
+        y, xx = np.arange(L.out_h), np.arange(L.out_w)
+        S.wr(o + b * R.o_img + R.o_origin + (y[:, None] * R.o_row + xx[None, :] * R.oc_pitch)[:, :, None] + ch, out[:, :, :C])
+
+
+def _msrc(plan, R, k, b, h, w):
+    """[h][w] byte offsets in the slice of the pixels of image b of input k of a merge pass."""
+    e = [int(v) for v in plan.msrc[5 * (R.koff_off + k):5 * (R.koff_off + k) + 5]]
+    return e[0] + b * e[1] + e[2] + np.arange(h)[:, None] * e[3] + np.arange(w)[None, :] * e[4], e
+
+
+def _merge(plan, S, li, R, o, nb):
+    """ED_RUN_MERGE / ED_RUN_CAT (1168-1218): every input through its msrc[] entry."""
+    h, w = R.pix_per_img // R.col_w, R.col_w
+    cat = R.kind == RUN_CAT
+    C = R.pitch_x if cat else R.out_c
+    al = 1 if cat else _c4(C)
+    ch = np.arange(C)
+    op, rs = R.ph, R.rs & 0xff
+    obase = R.o_origin + (np.arange(h)[:, None] * R.o_row + np.arange(w)[None, :] * R.oc_pitch)[:, :, None]
+    assert R.oc_pitch % al == 0 and R.o_row % al == 0 and R.o_origin % al == 0 and o % 16 == 0, "a merge pass's %d-byte words are not aligned" % al
+    for b in range(nb):
+        r = None
+        for k in range(R.n_ks):
+            at, e = _msrc(plan, R, k, b, h, w)
+            assert all(v % al == 0 for v in e), "merge input %d is not aligned to %d bytes" % (k, al)
+            v = S.rd(at[:, :, None] + ch).astype(np.int64)
+            if cat:
+                S.wr(o + b * R.o_img + obase + k * C + ch, np.maximum(v, R.lo_clamp))
+                continue
+            if k == 0:
+                r = v
+                continue
+            p, q = (r, v) if k == 1 else (v, r)            # the first pair is (input 0, input 1); later: (input k, result so far)
+            t = p + q if op == T_ADD else p - q if op == T_SUB else p * q
+            assert op in (T_ADD, T_SUB, T_MULT)
+            t = (t >> 7 if op == T_MULT else t) if rs == 0 else (t + (1 << (rs - 1))) >> rs
+            r = np.clip(t, -128, 127)
+        if not cat:
+            S.wr(o + b * R.o_img + obase + ch, np.maximum(r, R.lo_clamp))
+
+
+def _inside(lo, hi, areas):
+    return any(a <= lo and hi <= b for a, b in areas)
+
+
 def run(plan, x):
     """x [n][in_n] int8 -> dict(logits, softmax or None, argmax): `batch` inputs at a time through one LDS slice, as a wave does."""
     P, M = plan.P, plan.M
     x = np.ascontiguousarray(x, np.int8).reshape(-1, P.in_n)
     n, batch = x.shape[0], M.batch
     region = 2 * M.buf_bytes
+    hold0 = region + M.x_bytes                              # the held areas lie behind the expansion buffer
+    areas = ((0, region), (hold0, hold0 + M.hold_bytes))    # where a tensor may lie
+    src = plan.src
     logits = np.zeros((n, P.out_n), np.int8)
     last = np.zeros((n, P.out_n), np.int8)
     for u0 in range(0, n, batch):
         nb = min(batch, n - u0)
-        S = Slice(region + M.x_bytes)
+        S = Slice(region + M.x_bytes + M.hold_bytes)
         # ---- the inputs into layer 0's layout
         m0, in0 = plan.ML[0], plan.R[0].in_off
         if m0.in_hp != P.in_h or m0.in_wp != P.in_w:
@@ -119,13 +220,33 @@ def run(plan, x):
                 pix, c = e // P.in_c, e % P.in_c
                 at = ((pix // P.in_w + m0.in_py) * m0.in_wp + pix % P.in_w + m0.in_px) * P.in_c + c
             S.wr(in0 + b * m0.in_img + at, x[u0 + b])
+        where = {-1: (in0, in0 + batch * m0.in_img)}        # tensor -> its images' bytes in the slice, once a pass stored it
         for li in range(P.n_layers):
             R = plan.R[li]
             if R.kind == RUN_SKIP:
                 continue
             a, o = R.in_off, R.o_off
-            assert a + batch * R.in_img <= region and o + batch * R.o_img <= region, "a layer's images leave the activation region"
-            assert a + batch * R.in_img <= o or o + batch * R.o_img <= a, "a layer's input and output images overlap"
+            merge = R.kind in (RUN_MERGE, RUN_CAT)
+            # what the pass reads: one image per input, where the pass that stored the tensor left it
+            if merge:
+                assert R.n_ks == len(src[li]), "a merge pass over %d inputs, the graph names %d" % (R.n_ks, len(src[li]))
+                reads = []
+                for k, t in enumerate(src[li]):
+                    e = plan.msrc[5 * (R.koff_off + k):5 * (R.koff_off + k) + 5]
+                    reads.append((t, int(e[0]), int(e[0]) + batch * int(e[1])))
+            else:
+                assert len(src[li]) == 1
+                reads = [(src[li][0], a, a + batch * R.in_img)]
+            wlo, whi = o, o + batch * R.o_img
+            for t, lo, hi in reads:
+                assert _inside(lo, hi, areas), "a layer's images leave the activation region"
+                assert t in where and where[t] == (lo, hi), "pass %d reads tensor %d at %d..%d, it was stored at %s" % (li, t, lo, hi, where.get(t))
+                assert hi <= wlo or whi <= lo, "a layer's input and output images overlap"
+            assert _inside(wlo, whi, areas), "a layer's images leave the activation region"
+            for t, (lo, hi) in where.items():                # nothing this pass or a later one still reads is stored over
+                if any(t in src[j] for j in range(li, P.n_layers)):
+                    assert hi <= wlo or whi <= lo, "pass %d stores at %d..%d over tensor %d at %d..%d, which is still read" % (li, wlo, whi, t, lo, hi)
+            where[R.li_out] = (wlo, whi)
             if R.zero_border:
                 S.wr(o + np.arange(batch * R.o_img), 0)
             if R.kind == RUN_MM:
@@ -191,7 +312,12 @@ def run(plan, x):
                                     if 0 <= ix < L.in_w:
                                         m = np.maximum(m, S.rd(a + b * R.in_img + (iy * L.in_w + ix) * L.in_c + np.arange(L.in_c)).astype(np.int64))
                             S.wr(o + b * R.o_img + R.o_origin + y * R.o_row + xx * R.oc_pitch + np.arange(L.in_c), m)
+            elif R.kind in (RUN_DW, RUN_AVG):
+                _valu(plan, S, li, R, a, o, nb)
+            elif merge:
+                _merge(plan, S, li, R, o, nb)
             else:  # softmax: arm_softmax_q7.c:215-260
+                assert R.kind == RUN_SOFTMAX, R.kind
                 for b in range(nb):
                     v = S.rd(a + b * R.in_img + np.arange(R.in_n)).astype(np.int64)
                     base = int(v.max()) - 8

@@ -80,8 +80,9 @@ def _out_shape(v, shape):
     return shape
 
 
-def run(blob, x, wrong=None):
-    """As oracle.net_ref.run: dict(acts=[per-record (n, out_n) int8], logits, softmax (or None), argmax)."""
+def run(blob, x, wrong=None, corrupt=None):
+    """As oracle.net_ref.run: dict(acts=[per-record (n, out_n) int8], logits, softmax (or None), argmax). corrupt = (record, f): that
+    record's result is replaced by f(result) before anything reads it -- for the tests that show a record reaches the output."""
     in_shape, recs, payload = net_ref.parse_blob(blob)
     src = sources(blob)
     x = np.ascontiguousarray(x, dtype=np.int8).reshape(-1, in_shape[0] * in_shape[1] * in_shape[2])
@@ -122,6 +123,8 @@ def run(blob, x, wrong=None):
             shapes.append(_out_shape(v, shape(s[0])))
         if v[0] in (T_ADD, T_SUB, T_MULT, T_CONCAT) and v[8] & 1:
             out = np.maximum(out, 0)
+        if corrupt is not None and corrupt[0] == i:
+            out = np.asarray(corrupt[1](out.reshape(n, -1)))
         acts.append(out.reshape(n, -1).astype(np.int8))
     last = acts[-1]
     logits = acts[src[-1][0]] if has_softmax else last

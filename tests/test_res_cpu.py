@@ -144,7 +144,7 @@ def _check_slice(blob):
     import plan_emulator
     P = plan_emulator.Plan(blob)
     M = P.M
-    hold = M.pad_                                               # ed_mm_plan_t.hold_bytes: the word plan_emulator still calls pad_
+    hold = M.hold_bytes
     assert M.ok and hold > 0 and hold % 16 == 0
     assert M.lds_bytes == M.tbl_bytes + M.frag_lds + M.waves * (2 * M.buf_bytes + M.x_bytes + hold) <= 160 * 1024
     slice_bytes = 2 * M.buf_bytes + M.x_bytes + hold
