@@ -68,6 +68,11 @@ class StreamFloatOpts(ctypes.Structure):
                 ("fsm", ctypes.c_int32), ("filter_alpha", c_double), ("true_threshold", c_double)]
 
 
+class FloatBankOpts(ctypes.Structure):
+    """edison_float_bank_opts"""
+    _fields_ = [("n_mics", ctypes.c_int32), ("stream", StreamFloatOpts)]
+
+
 class Fsm(ctypes.Structure):
     """edison_fsm"""
     _fields_ = [("state", c_int), ("hot_timeout_ms", ctypes.c_uint32), ("wake_idx", c_int), ("loc_idx", c_int),
@@ -213,6 +218,19 @@ SIGNATURES = {
     "edison_stream_float_filtered_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "edison_stream_float_fsm": (c_int, [c_void_p, c_void_p, c_void_p]),
     "edison_stream_float_fsm_dev": (c_int, [c_void_p, c_void_p]),
+    "edison_float_bank_default_opts": (None, [ctypes.POINTER(FloatBankOpts)]),
+    "edison_float_bank_create": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), ctypes.POINTER(FloatBankOpts), ctypes.POINTER(c_void_p)]),
+    "edison_float_bank_destroy": (None, [c_void_p]),
+    "edison_float_bank_reset": (c_int, [c_void_p]),
+    "edison_float_bank_reset_mic": (c_int, [c_void_p, c_int]),
+    "edison_float_bank_push": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_float_bank_push_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_float_bank_push_n_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "edison_float_bank_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_float_bank_filtered_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_float_bank_fsm": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "edison_float_bank_fsm_dev": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "edison_float_bank_frames_seen": (c_int, [c_void_p, ctypes.POINTER(c_int64)]),
     "edison_fsm_init": (None, [ctypes.POINTER(Fsm)]),
     "edison_fsm_step": (c_int, [ctypes.POINTER(Fsm), c_float, ctypes.c_uint32, ctypes.c_uint32, c_double]),
     # legacy firmware call surface

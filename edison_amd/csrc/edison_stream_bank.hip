@@ -59,8 +59,10 @@ __global__ __launch_bounds__(256) void ed_stream_bank_shift_kernel(int16_t *audi
 /* The banked filter: workgroup m runs the firmware's post-processing for microphone m with the arithmetic of
  * ed_stream_geom_filter_kernel (edison_stream_core.hip) -- product and sum rounded separately in double, no contraction, first maximum,
  * edisonFSM on lane 0. Entry i of microphone m is row i * n_mics + m of the time-major arrays x / filt [n][n_mics][n_out] and likely /
- * spotted / fs.states [n][n_mics]; between pushes it keeps state [n_mics][n_out] and fs.fsm [n_mics]. */
-__global__ __launch_bounds__(256) void ed_stream_bank_filter_kernel(const int8_t *x, int n, int n_out, double alpha, double one_minus_alpha,
+ * spotted / fs.states [n][n_mics]; between pushes it keeps state [n_mics][n_out] and fs.fsm [n_mics]. T = int8_t: the int8 graph's softmax
+ * / logits (this file's bank); T = float: the float network's probabilities (edison_float_bank.hip). (double)x is exact for both. */
+template <class T>
+__global__ __launch_bounds__(256) void ed_stream_bank_filter_kernel(const T *x, int n, int n_out, double alpha, double one_minus_alpha,
                                                                     double threshold, float *state, float *filt, int32_t *likely,
                                                                     int32_t *spotted, edsg_fsm_stage_t fs)
 {
@@ -114,11 +116,15 @@ void ed_stream_bank_launch_shift(hipStream_t q, int n_mics, int16_t *audio, int6
 	hipLaunchKernelGGL(ed_stream_bank_shift_kernel, dim3(n_mics), dim3(256), 0, q, audio, a_stride, a_src, tail, feat, f_stride, f_src, feat_bytes);
 }
 
-void ed_stream_bank_launch_filter(hipStream_t q, int n_mics, const int8_t *x, int n, int n_out, double alpha, double one_minus_alpha, double threshold,
-                                  float *state, float *filt, int32_t *likely, int32_t *spotted, edsg_fsm_stage_t fs)
+void ed_stream_bank_launch_filter(hipStream_t q, int n_mics, int out_elem, const void *x, int n, int n_out, double alpha, double one_minus_alpha,
+                                  double threshold, float *state, float *filt, int32_t *likely, int32_t *spotted, edsg_fsm_stage_t fs)
 {
-	hipLaunchKernelGGL(ed_stream_bank_filter_kernel, dim3(n_mics), dim3(256), 0, q, x, n, n_out, alpha, one_minus_alpha, threshold, state, filt, likely,
-	                   spotted, fs);
+	if (out_elem == 1)
+		hipLaunchKernelGGL(ed_stream_bank_filter_kernel<int8_t>, dim3(n_mics), dim3(256), 0, q, (const int8_t *)x, n, n_out, alpha, one_minus_alpha,
+		                   threshold, state, filt, likely, spotted, fs);
+	else
+		hipLaunchKernelGGL(ed_stream_bank_filter_kernel<float>, dim3(n_mics), dim3(256), 0, q, (const float *)x, n, n_out, alpha, one_minus_alpha,
+		                   threshold, state, filt, likely, spotted, fs);
 }
 
 static ed_stream_core *core_of(edison_stream_bank *b) { return b ? &b->core : NULL; }

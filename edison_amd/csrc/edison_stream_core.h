@@ -11,8 +11,8 @@
  * of the push is rows pos + i .. pos + i + F - 1, read in place by the owner's network kernel. When the next push would run past the
  * end, the shift kernel first moves the history back to the front.
  *
- * A core serves n_mics microphones that advance in lockstep (1: edison_stream_geom / edison_stream_float; more: edison_stream_bank.hip,
- * DESIGN.md section 12b). Each microphone has the two buffers above, mic_audio samples and mic_feat bytes behind its neighbour's, and all
+ * A core serves n_mics microphones that advance in lockstep (1: edison_stream_geom / edison_stream_float; more: edison_stream_bank.hip and
+ * edison_float_bank.hip, DESIGN.md sections 12b and 15a). Each microphone has the two buffers above, mic_audio samples and mic_feat bytes behind its neighbour's, and all
  * share one pos. A push carries [n_mics][n * hop] samples; everything it puts out is time-major: filt [n][n_mics][n_out], likely /
  * spotted / states [n][n_mics], the machines [n_mics]. With n_mics = 1 the core issues the copies and launches it issued before it had
  * the dimension; with more, one strided copy and the banked kernels of edison_stream_bank.hip (one workgroup per microphone).
@@ -43,7 +43,7 @@ static inline size_t ed_stream_core_mic_feat(int feat_elem, int F, int slots, in
 struct ed_stream_core
 {
 	edison_ctx *ctx;
-	const char *who;               /* the owner's message prefix: "stream_geom", "stream_float" */
+	const char *who;               /* the owner's message prefix: "stream_geom", "stream_float", "stream_bank", "float_bank" */
 	int feat_elem, out_elem;       /* bytes per feature element and per network output: 1 (the int8 graph) or 4 (the float network) */
 	int F, nm, hop, tail, chunk;   /* frames per window, coefficients per row, frame_step, T history samples, frames per push */
 	int n_out, filter, fsm;
@@ -81,11 +81,11 @@ struct edsg_fsm_stage_t
 
 /* The kernels of a core with more than one microphone, one workgroup per microphone (edison_stream_bank.hip): the shift of every
  * microphone's history to the front of its buffers, a_stride samples and f_stride bytes apart, and the filter (+ edisonFSM) over the
- * time-major int8 x [n][n_mics][n_out] with state [n_mics][n_out]. Enqueued on q; a failed launch shows in hipGetLastError. */
+ * time-major x [n][n_mics][n_out] (int8 for out_elem 1, float for 4) with state [n_mics][n_out]. Enqueued on q; a failed launch shows in hipGetLastError. */
 void ed_stream_bank_launch_shift(hipStream_t q, int n_mics, int16_t *audio, int64_t a_stride, int64_t a_src, int tail, int8_t *feat, int64_t f_stride,
                                  int64_t f_src, int feat_bytes);
-void ed_stream_bank_launch_filter(hipStream_t q, int n_mics, const int8_t *x, int n, int n_out, double alpha, double one_minus_alpha, double threshold,
-                                  float *state, float *filt, int32_t *likely, int32_t *spotted, edsg_fsm_stage_t fs);
+void ed_stream_bank_launch_filter(hipStream_t q, int n_mics, int out_elem, const void *x, int n, int n_out, double alpha, double one_minus_alpha,
+                                  double threshold, float *state, float *filt, int32_t *likely, int32_t *spotted, edsg_fsm_stage_t fs);
 
 /* the options both public option structs carry */
 struct ed_stream_core_opts { int chunk_frames, filter, fsm; double filter_alpha, true_threshold; };
@@ -101,8 +101,8 @@ void ed_stream_core_free(ed_stream_core *c);
 /* A push of n frames on q (host = 1: host samples, q = c->own; host = 0: device samples, q = the context's stream):
  *   begin_push   waits for work left on another HIP stream, shifts the history when the push would not fit, uploads the samples to
  *                d_audio + pos * hop + tail of every microphone (the host's through h_in); the owner's feature rows and network follow
- *   finish_push  where the stream has a filter: the filter (+ edisonFSM) over fin[n][n_mics][n_out] (int8 for out_elem 1, float for 4;
- *                more than one microphone: int8) into the block; pos += n; host: one download of the block to h_out and one wait; what the getters need to know of this push */
+ *   finish_push  where the stream has a filter: the filter (+ edisonFSM) over fin[n][n_mics][n_out] (int8 for out_elem 1, float for 4,
+ *                with one microphone or more) into the block; pos += n; host: one download of the block to h_out and one wait; what the getters need to know of this push */
 int ed_stream_core_begin_push(ed_stream_core *c, hipStream_t q, const int16_t *samples, int n, int host);
 int ed_stream_core_finish_push(ed_stream_core *c, hipStream_t q, const void *fin, int n, int host);
 

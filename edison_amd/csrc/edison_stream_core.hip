@@ -276,7 +276,7 @@ int ed_stream_core_finish_push(ed_stream_core *c, hipStream_t q, const void *fin
 		float *filt = (float *)(o + c->off_filt);
 		int32_t *likely = (int32_t *)(o + c->off_likely), *spotted = (int32_t *)(o + c->off_spotted);
 		if (c->n_mics > 1)
-			ed_stream_bank_launch_filter(q, c->n_mics, (const int8_t *)fin, n, c->n_out, c->alpha, c->one_minus_alpha, c->threshold, c->d_state, filt,
+			ed_stream_bank_launch_filter(q, c->n_mics, c->out_elem, fin, n, c->n_out, c->alpha, c->one_minus_alpha, c->threshold, c->d_state, filt,
 			                             likely, spotted, fs);
 		else if (c->out_elem == 1)
 			hipLaunchKernelGGL(ed_stream_geom_filter_kernel<int8_t>, dim3(1), dim3(256), 0, q, (const int8_t *)fin, n, c->n_out, c->alpha,

@@ -1,5 +1,5 @@
 /*
- * fnet.h -- the launch plan of the float32 network kernel (fnet_kernels.hip), built by its host side (edison_fnet.hip) from an .ednf
+ * fnet.h -- the launch plan of the float32 network kernels (fnet_kernels.hip, fnet_windows_kernels.hip), built by its host side (edison_fnet.hip) from an .ednf
  * blob (edison_amd/cube_import.py). Not part of the public ABI.
  */
 #ifndef EDISON_FNET_H
@@ -51,6 +51,12 @@ static inline size_t ed_fnet_lds_bytes(const ed_fnet_plan_t *p)
  * overlapping windows of a stream's feature rows (edison_stream_float). Returns a hipError_t. */
 extern "C" int ed_launch_fnet(const ed_fnet_plan_t *p, const float *in, int64_t in_stride, int64_t n, float *logits, float *probs, int32_t *argmax,
                               float *acts, hipStream_t stream);
+/* The windows of a bank of microphones (fnet_windows_kernels.hip): utterance U < n * n_mics (< 2^31) is frame i = U / n_mics of
+ * microphone m = U % n_mics, the in_n floats at in + m * mic_stride + i * frame_stride; outputs [n][n_mics][..], row U (NULL: not written).
+ * One launch. per_frame != 0 (tools/bench_float_bank.py only; the library passes 0): n launches of ed_launch_fnet instead, one per frame
+ * over its n_mics windows, which computes the same outputs. Returns a hipError_t. */
+extern "C" int ed_launch_fnet_windows(const ed_fnet_plan_t *p, const float *in, int64_t mic_stride, int32_t n_mics, int64_t frame_stride, int32_t n,
+                                      float *logits, float *probs, int32_t *argmax, int per_frame, hipStream_t stream);
 /* The context's loaded float network's plan, NULL when none is loaded (edison_fnet.hip). */
 struct edison_ctx;
 const ed_fnet_plan_t *ed_ctx_fnet_plan(const struct edison_ctx *ctx);

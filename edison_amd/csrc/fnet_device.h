@@ -1,0 +1,150 @@
+/*
+ * fnet_device.h -- the device code of the float32 network kernels: the work item edf_tile and the body of a workgroup,
+ * EDF_NETWORK_BODY, shared by ed_fnet_kernel (fnet_kernels.hip: utterances one stride apart) and ed_fnet_windows_kernel
+ * (fnet_windows_kernels.hip: the windows of a bank of microphones, two strides). The tiling, the k-ordered fmaf chain, the epilogue, the
+ * softmax and the LDS plan exist once, here; a kernel differs only in how the utterances of its tile find their input.
+ * DESIGN.md sections 14 and 15a. Not part of the public ABI.
+ */
+#ifndef EDISON_FNET_DEVICE_H
+#define EDISON_FNET_DEVICE_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "fnet.h"
+
+typedef float ed_f4 __attribute__((ext_vector_type(4)));
+
+/* One work item: 16 output rows (M tile mt) x NT tiles of 16 channels starting at n0. */
+template <int NT>
+__device__ __forceinline__ void edf_tile(const ed_fnet_layer_t &L, const float *__restrict__ src, int src_n, float *__restrict__ dst, int dst_n,
+                                         const float *__restrict__ wl, const int32_t *__restrict__ kl, const int32_t *__restrict__ rowin,
+                                         const float *__restrict__ bias, int M, int mt, int n0, int lane, float *__restrict__ acts,
+                                         int64_t acts_n, int64_t u0)
+{
+	const int r = lane & 15, kq = lane >> 4;
+	const int m = mt * 16 + r;
+	int base = 0;
+	if (m < M)
+	{
+		const int u = m / L.rows;
+		base = u * src_n + rowin[m - u * L.rows];
+	}
+	ed_f4 acc[NT];
+#pragma unroll
+	for (int j = 0; j < NT; j++) acc[j] = (ed_f4){0.0f, 0.0f, 0.0f, 0.0f};
+	const float *wp = wl + kq * L.n_pad + n0 + r;
+#pragma unroll 4
+	for (int k0 = 0; k0 < L.k_pad; k0 += 4)
+	{
+		const int ko = kl[k0 + kq];
+		const float a = ko >= 0 ? src[base + ko] : 0.0f;
+#pragma unroll
+		for (int j = 0; j < NT; j++) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wp[j * 16], acc[j], 0, 0, 0);
+		wp += 4 * L.n_pad;
+	}
+	/* D: lane holds rows 4 kq + i (i = 0..3) of channel n0 + 16 j + r */
+	const int P = L.P;
+	const int m0 = mt * 16 + 4 * kq;
+#pragma unroll
+	for (int j = 0; j < NT; j++)
+	{
+		const int n = n0 + 16 * j + r;
+		if (n >= L.out_c) continue;
+		const float b = bias[n];
+		float v[4];
+#pragma unroll
+		for (int i = 0; i < 4; i++)
+		{
+			v[i] = acc[j][i] + b;
+			if (L.relu) v[i] = fmaxf(v[i], 0.0f);
+		}
+		for (int g = 0; g < 4; g += P)
+		{
+			const int mg = m0 + g;
+			if (mg >= M) break;
+			float x = v[g];
+			if (P >= 2) x = fmaxf(x, v[g + 1]);
+			if (P == 4) x = fmaxf(fmaxf(x, v[g + 2]), v[g + 3]);
+			const int u = mg / L.rows, q = (mg - u * L.rows) / P;
+			dst[u * dst_n + q * L.out_c + n] = x;
+			if (acts) acts[(u0 + u) * acts_n + L.acts_at + q * L.out_c + n] = x;
+		}
+	}
+}
+
+/* The body of a kernel `(ed_fnet_plan_t p, ..., int64_t n, float *logits, float *probs, int32_t *argmax, float *acts)`: the workgroup of
+ * blockIdx.x takes the tile of utterances u0 = blockIdx.x * batch .. u0 + nu - 1 of the launch's n through the network. The argument is
+ * the kernel's own statement that puts utterance u0 + u's p.in_n input floats at buf[0] + u * p.buf_n[0] for u < nu (it sees p, buf, u0,
+ * nu and tid); outputs go to rows u0 .. of logits / probs / argmax (NULL: not written) and, with acts, of the per-layer dump.
+ * Expanded textually, as mfcc_geom_frames.inc is included: as a __forceinline__ function template over a loader the same body compiled
+ * to another instruction order in ed_fnet_kernel (the compiler simplifies a callee on its own before it inlines it), and that kernel's
+ * instructions stay as they were. */
+#define EDF_NETWORK_BODY(...)                                                                                                              \
+	extern __shared__ float lds[];                                                                                                         \
+	const int B = p.batch;                                                                                                                 \
+	float *buf[2] = {lds, lds + B * p.buf_n[0]};                                                                                           \
+	float *wl = lds + B * (p.buf_n[0] + p.buf_n[1]);                                                                                       \
+	int32_t *kl = (int32_t *)(wl + p.w_lds);                                                                                               \
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = ED_FNET_THREADS / 64;                                         \
+	const int64_t u0 = (int64_t)blockIdx.x * B;                                                                                            \
+	const int nu = (int)(n - u0 < B ? n - u0 : B);                                                                                         \
+                                                                                                                                           \
+	/* the network input of the tile's utterances into buffer 0 */                                                                         \
+	__VA_ARGS__                                                                                                                            \
+                                                                                                                                           \
+	for (int l = 0; l < p.n_layers; l++)                                                                                                   \
+	{                                                                                                                                      \
+		const ed_fnet_layer_t &L = p.L[l];                                                                                                 \
+		const float *gw = p.w + L.w_at;                                                                                                    \
+		__syncthreads(); /* the previous layer's outputs are written and its weights no longer read */                                     \
+		{                                                                                                                                  \
+			const int nw = L.k_pad * L.n_pad; /* a multiple of 64: float4 copies */                                                        \
+			const float4 *g4 = (const float4 *)gw;                                                                                         \
+			float4 *l4 = (float4 *)wl;                                                                                                     \
+			for (int i = tid; i < nw / 4; i += ED_FNET_THREADS) l4[i] = g4[i];                                                             \
+			for (int i = tid; i < L.k_pad; i += ED_FNET_THREADS) kl[i] = p.tab[L.koff_at + i];                                             \
+		}                                                                                                                                  \
+		__syncthreads();                                                                                                                   \
+		const float *src = buf[L.src];                                                                                                     \
+		float *dst = buf[L.dst];                                                                                                           \
+		const int src_n = p.buf_n[L.src], dst_n = p.buf_n[L.dst];                                                                          \
+		const int32_t *rowin = p.tab + L.rowin_at;                                                                                         \
+		const float *bias = gw + (int64_t)L.k_pad * L.n_pad;                                                                               \
+		const int M = nu * L.rows;                                                                                                         \
+		const int MT = (M + 15) / 16, NT = L.n_pad / 16, NG = (NT + 3) / 4;                                                                \
+		for (int item = wave; item < MT * NG; item += n_waves)                                                                             \
+		{                                                                                                                                  \
+			const int mt = item / NG, g = item - mt * NG;                                                                                  \
+			const int n0 = g * 64, nt = NT - 4 * g < 4 ? NT - 4 * g : 4;                                                                   \
+			if (nt == 4) edf_tile<4>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);                 \
+			else if (nt == 3) edf_tile<3>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);            \
+			else if (nt == 2) edf_tile<2>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);            \
+			else edf_tile<1>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);                         \
+		}                                                                                                                                  \
+	}                                                                                                                                      \
+	__syncthreads();                                                                                                                       \
+                                                                                                                                           \
+	/* softmax (forward_sm: exp(z - max) / sum) and the first maximum of the probabilities, one thread per utterance */                    \
+	if (tid < nu)                                                                                                                          \
+	{                                                                                                                                      \
+		const ed_fnet_layer_t &L = p.L[p.n_layers - 1];                                                                                    \
+		const float *z = buf[L.dst] + tid * p.buf_n[L.dst];                                                                                \
+		const int64_t u = u0 + tid;                                                                                                        \
+		float mx = z[0];                                                                                                                   \
+		for (int j = 1; j < p.n_out; j++) mx = fmaxf(mx, z[j]);                                                                            \
+		float s = 0.0f;                                                                                                                    \
+		for (int j = 0; j < p.n_out; j++) s += expf(z[j] - mx);                                                                            \
+		int best = 0;                                                                                                                      \
+		float bp = -1.0f;                                                                                                                  \
+		for (int j = 0; j < p.n_out; j++)                                                                                                  \
+		{                                                                                                                                  \
+			const float pj = expf(z[j] - mx) / s;                                                                                          \
+			if (logits) logits[u * p.n_out + j] = z[j];                                                                                    \
+			if (probs) probs[u * p.n_out + j] = pj;                                                                                        \
+			if (pj > bp) { bp = pj; best = j; }                                                                                            \
+		}                                                                                                                                  \
+		if (argmax) argmax[u] = best;                                                                                                      \
+	}
+
+#endif

@@ -12,7 +12,8 @@
  * Variants A / B, float64 throughout. Frame g of the call is frame f = g % frames_per_utt of utterance u = g / frames_per_utt: its
  * samples start at audio + u * utt_stride + f * frame_step, its int8 features land at feat + g * n_coef (the flat [frames][num_mfcc]
  * vector the reference reshapes to the graph's input) -- or, with feat_utt_stride != 0, at feat + u * feat_utt_stride + f * n_coef:
- * every utterance's rows in a buffer of its own (the microphones of edison_stream_bank.hip). The transform is a Stockham FFT over M complex points with the radices in
+ * every utterance's rows in a buffer of its own (the microphones of edison_stream_bank.hip and edison_float_bank.hip; the unit is the
+ * instance's output element: bytes for the int8 features, floats for ed_launch_mfcc_geom_fnet's rows). The transform is a Stockham FFT over M complex points with the radices in
  * `radix` (M = N/2 with the real frame packed into complex pairs when N is even, M = N when N is odd), or a direct DFT when M has a
  * prime factor above 5 (M = 0). */
 #define ED_GEOM_MAX_STAGES 16
@@ -33,7 +34,7 @@ typedef struct {
 	const double *dct;                 /* [n_coef][n_mel] 2 cos(pi c (2 n + 1) / (2 n_mel)), c = first_mfcc + row */
 	int8_t *feat;
 	float feat_scale;
-	int64_t feat_utt_stride;           /* int8 features only: bytes from one utterance's rows to the next's; 0: contiguous, frames_per_utt * n_coef */
+	int64_t feat_utt_stride;           /* int8 and float-network instances: output elements (bytes / floats) from one utterance's rows to the next's; 0: contiguous, frames_per_utt * n_coef */
 } ed_geom_args_t;
 
 /* The filterbank / twiddle / DCT tables of one geometry on the device and the kernel's launch template (edison_kws_geom.hip builds
@@ -53,7 +54,8 @@ extern "C" int ed_launch_mfcc_geom(const ed_geom_args_t *a, int n_cu, hipStream_
  * instead of the int8 feature (a->feat and a->feat_scale are not read). */
 extern "C" int ed_launch_mfcc_geom_f64(const ed_geom_args_t *a, double *mfcc, int n_cu, hipStream_t stream);
 /* The same frames, stages and launch (mfcc_geom_fnet_kernels.hip); stage 6 stores the float network input
- * fminf(fmaxf((float)y * scale, lo), hi) to out + g * n_coef + row (a->feat and a->feat_scale are not read). */
+ * fminf(fmaxf((float)y * scale, lo), hi) to out + g * n_coef + row, or with a->feat_utt_stride != 0 (in floats) to out + u * feat_utt_stride
+ * + f * n_coef + row (a->feat and a->feat_scale are not read). */
 extern "C" int ed_launch_mfcc_geom_fnet(const ed_geom_args_t *a, float *out, float scale, float lo, float hi, int n_cu, hipStream_t stream);
 
 #endif

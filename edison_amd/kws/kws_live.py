@@ -5,7 +5,8 @@ what this module runs, frame by frame, on the GPU: 1024-sample frames -> MFCC ->
 -> moving average over the outputs -> maximum / threshold -> wake-word state machine. ``host`` uses the host float
 model of the features (variant B), ``mcu`` the firmware's own Q15 arithmetic (variant C). The printed lines follow the
 firmware's UART log (app.c:330-353). ``--net <file.ednf>`` runs the float32 X-CUBE-AI network instead of the int8 graph: the
-firmware's default build (NET_TYPE_CUBE), whose moving average uses alpha 0.5 (app.c:35-36).
+firmware's default build (NET_TYPE_CUBE), whose moving average uses alpha 0.5 (app.c:35-36). With ``--net``, several wav files run as
+the microphones of one bank (``stream.FloatBank``): ``kws live <host|mcu> a.wav b.wav ... --net <file.ednf>``.
 """
 import sys
 
@@ -13,7 +14,7 @@ import numpy as np
 
 from .. import config as cfg
 from ..context import KEYWORDS, default_context
-from ..stream import FloatStream, Fsm, GeomStream, Stream, StreamBank
+from ..stream import FloatBank, FloatStream, Fsm, GeomStream, Stream, StreamBank
 from .kws_host import read_wav
 
 
@@ -34,7 +35,7 @@ def run(path, q15=False, ctx=None, out=None, alpha=None, threshold=0.5, geometry
     net (an .ednf path or its bytes): the float32 X-CUBE-AI network, loaded on ctx, on a FloatStream (host flow at `geometry`, default
     audio/config.py's; q15: the firmware's flow); class names from the .ednf. alpha: the moving average's, default 0.9 for the int8
     graph (app.c:38) and 0.5 for the float network (app.c:35-36).
-    path may be a list of wav files, with geometry: the microphones of one StreamBank (run_bank)."""
+    path may be a list of wav files, with geometry or net: the microphones of one StreamBank or FloatBank (run_bank)."""
     if not isinstance(path, (str, bytes)) and hasattr(path, "__len__"):
         if len(path) != 1:
             return run_bank(path, ctx=ctx, out=out, alpha=alpha, threshold=threshold, geometry=geometry, net=net, q15=q15)
@@ -104,25 +105,42 @@ def _print_hops(out, n, shown, likelies, spotteds, fsm_states, name):
 
 
 def run_bank(paths, ctx=None, out=None, alpha=None, threshold=0.5, geometry=None, net=None, q15=False):
-    """Several wav files as the microphones of one StreamBank at `geometry` (the int8 graph only): the shorter recordings are padded
-    with silence to the longest, all advance in one push. Per microphone a heading line ``mic <m>: <path>`` and then the lines run()
-    prints for that file alone, for the hops of its own recording. Returns dict(result, mics=[dict(commands, state)])."""
-    if geometry is None or net is not None or q15:
-        raise ValueError("several recordings run as one bank: the int8 graph at a geometry (geometry=..., no net, no q15)")
+    """Several wav files as the microphones of one bank: the shorter recordings are padded with silence to the longest, all advance in
+    one push. Without net: a StreamBank at `geometry` on the int8 graph. With net (an .ednf path or its bytes): a FloatBank on the
+    float32 X-CUBE-AI network, loaded on ctx (host flow at `geometry`, default audio/config.py's; q15: the firmware's flow), as run()
+    with net. Per microphone a heading line ``mic <m>: <path>`` and then the lines run() prints for that file alone, for the hops of
+    its own recording. Returns dict(result, mics=[dict(commands, state)])."""
+    if net is None and (geometry is None or q15):
+        raise ValueError("several recordings run as one bank: the int8 graph at a geometry (geometry=..., no q15), or a float network (net=...)")
     out = out or sys.stdout
     ctx = ctx or default_context()
+    if net is not None:
+        ctx.fnet_load(net)
+        if geometry is None:
+            from ..kws.geometry import KwsGeometry
+            geometry = KwsGeometry.from_config(net_input_scale=cfg.net_input_scale)
     hop = int(geometry.frame_step)
     datas = [read_wav(p) for p in paths]
     hops = [-(-d.shape[0] // hop) for d in datas]
     n = max(hops)
     x = np.stack([np.pad(d, (0, n * hop - d.shape[0])) for d in datas])
-    with_fsm = ctx.net_info()["n_out"] == len(KEYWORDS)
-    bank = StreamBank(ctx, geometry, len(paths), chunk_frames=n, output_filter=True, alpha=0.9 if alpha is None else alpha,
-                      threshold=threshold, fsm=with_fsm)
+    if net is not None:
+        with_fsm = ctx.fnet_info()["n_out"] == len(KEYWORDS)
+        bank = FloatBank(ctx, len(paths), geometry, q15=q15, chunk_frames=n, output_filter=True, alpha=0.5 if alpha is None else alpha,
+                         threshold=threshold, fsm=with_fsm)
+        names = bank.keywords or (list(KEYWORDS) if with_fsm else [])
+        name = lambda i: names[i] if i < len(names) else "class %d" % i
+    else:
+        with_fsm = ctx.net_info()["n_out"] == len(KEYWORDS)
+        bank = StreamBank(ctx, geometry, len(paths), chunk_frames=n, output_filter=True, alpha=0.9 if alpha is None else alpha,
+                          threshold=threshold, fsm=with_fsm)
+        name = (lambda i: KEYWORDS[i]) if with_fsm else (lambda i: "class %d" % i)
     res = bank.push(x)
     bank.close()
-    shown = res["softmax"] if res["softmax"] is not None else res["logits"]
-    name = (lambda i: KEYWORDS[i]) if with_fsm else (lambda i: "class %d" % i)
+    if net is not None:
+        shown = res["probs"]
+    else:
+        shown = res["softmax"] if res["softmax"] is not None else res["logits"]
     mics = []
     for m, p in enumerate(paths):
         print("mic %d: %s" % (m, p), file=out)
@@ -141,9 +159,9 @@ def main(argv):
             return 1
         net = argv[i + 1]
         argv = argv[:i] + argv[i + 2:]
-    if len(argv) < 3 or argv[1] not in ("host", "mcu"):
-        print("usage: kws live <host|mcu> <wav> [--net <file.ednf>]   (--net: the float32 X-CUBE-AI network instead of the int8 graph; "
-              "the microphone front end of the reference is not part of this port)")
-        return 0 if len(argv) >= 2 and argv[1] in ("host", "mcu") else 1
-    run(argv[2], q15=(argv[1] == "mcu"), net=net)
+    if len(argv) < 3 or argv[1] not in ("host", "mcu") or (len(argv) > 3 and net is None):
+        print("usage: kws live <host|mcu> <wav> [<wav> ...] [--net <file.ednf>]   (--net: the float32 X-CUBE-AI network instead of the int8 "
+              "graph; several wavs with --net: the microphones of one bank; the microphone front end of the reference is not part of this port)")
+        return 0 if len(argv) == 2 and argv[1] in ("host", "mcu") else 1
+    run(argv[2:] if len(argv) > 3 else argv[2], q15=(argv[1] == "mcu"), net=net)
     return 0

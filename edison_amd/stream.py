@@ -21,8 +21,8 @@ from .context import KEYWORDS, default_context
 
 
 class _Handle:
-    """What the three stream classes share: the life of the handle ``_h`` on the C functions ``<_C>*`` and the state machine's view."""
-    _C = None    # "edison_stream_", "edison_stream_geom_", "edison_stream_float_"
+    """What the stream and bank classes share: the life of the handle ``_h`` on the C functions ``<_C>*`` and the state machine's view."""
+    _C = None    # "edison_stream_", "edison_stream_geom_", "edison_stream_bank_", "edison_stream_float_", "edison_float_bank_"
 
     def _c(self, name):
         return getattr(self._L, self._C + name)
@@ -360,6 +360,99 @@ class FloatStream(_SlidingStream):
         """Device tensors (torch, int16 / fp32 / int32 on the context's GPU); asynchronous on the context's stream. n_frames <
         chunk_frames: a ragged last push of n_frames * hop samples; every output is [n_frames][..]."""
         self._push_t(samples, logits, probs, argmax, filtered, likely, spotted, n_frames)
+
+
+class FloatBank(_Handle):
+    """Many microphones through one float32 X-CUBE-AI network -- Python handle on ``edison_float_bank_*``: ``n_mics`` continuous streams
+    at one geometry on the float network loaded on the context (``Context.fnet_load``), advancing in lockstep. Microphone m behaves
+    exactly as a ``FloatStream`` of its own (same geometry, flow and options) fed microphone m's samples; a push costs a number of
+    launches that depends neither on ``n_mics`` nor on its frames. Outputs are time-major, [frames of the push][n_mics][..]."""
+
+    _C = "edison_float_bank_"
+
+    def __init__(self, ctx, n_mics, geometry=None, q15=False, chunk_frames=1, output_filter=False, alpha=0.5, threshold=0.5, fsm=False,
+                 clip_min=None, clip_max=None):
+        from . import config as cfg
+        from .kws.geometry import KwsGeometry
+        self.ctx = ctx or default_context()
+        self._L = _lib.lib()
+        if geometry is None:
+            geometry = KwsGeometry.from_config(net_input_scale=cfg.net_input_scale)
+        o = _lib.FloatBankOpts()
+        self._L.edison_float_bank_default_opts(ctypes.byref(o))
+        o.n_mics = int(n_mics)
+        o.stream.chunk_frames = int(chunk_frames)
+        o.stream.q15 = 1 if q15 else 0
+        o.stream.clip_lo = float(cfg.net_input_clip_min if clip_min is None else clip_min)
+        o.stream.clip_hi = float(cfg.net_input_clip_max if clip_max is None else clip_max)
+        o.stream.filter = 1 if (output_filter or fsm) else 0
+        o.stream.fsm = 1 if fsm else 0
+        o.stream.filter_alpha, o.stream.true_threshold = float(alpha), float(threshold)
+        g = geometry.to_ctypes()
+        h = ctypes.c_void_p()
+        self.ctx._check(self._L.edison_float_bank_create(self.ctx._h, ctypes.byref(g), ctypes.byref(o), ctypes.byref(h)))
+        self._h = h
+        self.geometry = geometry
+        self.n_mics, self.hop, self.chunk = int(n_mics), int(geometry.frame_step), int(chunk_frames)
+        self.n_out = int(self.ctx.fnet_info()["n_out"])
+        self.keywords = getattr(self.ctx, "fnet_keywords", None)   # the names of the loaded .ednf (Context.fnet_load)
+        self.output_filter, self.fsm = bool(output_filter or fsm), bool(fsm)
+        self._fsms = (_lib.Fsm * self.n_mics)()
+
+    def frames_seen(self):
+        """Frames pushed per microphone since the bank was made or reset."""
+        n = ctypes.c_int64()
+        self.ctx._check(self._c("frames_seen")(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def reset_mic(self, m):
+        """Microphone m alone back to a new stream's state; the others do not notice."""
+        self.ctx._check(self._c("reset_mic")(self._h, int(m)))
+
+    def fsm_snapshot(self):
+        """The state machines as the last host push saw them: one ``FloatStream.fsm_snapshot`` dict per microphone."""
+        return [_fsm_dict(f) for f in self._fsms]
+
+    def push(self, samples):
+        """samples: [n_mics, chunk_frames * hop] new int16 samples (host). Returns ``FloatStream.push``'s dict with the microphone axis
+        added: logits / probs float32 [chunk][n_mics][n_out], argmax [chunk][n_mics], ``keywords`` [chunk][n_mics] (the names of the
+        network's .ednf; KEYWORDS for a 10-output network without names); with the filter filtered [chunk][n_mics][n_out] fp32, likely,
+        spotted [chunk][n_mics]; with the state machine fsm_states [chunk][n_mics] and fsm, a list of n_mics snapshots."""
+        x = np.ascontiguousarray(samples, dtype=np.int16)
+        if x.shape != (self.n_mics, self.chunk * self.hop):
+            raise ValueError("push needs [n_mics, chunk_frames*hop] = [%d, %d] samples" % (self.n_mics, self.chunk * self.hop))
+        c, m, no = self.chunk, self.n_mics, self.n_out
+        lo, pr, am = np.zeros((c, m, no), np.float32), np.zeros((c, m, no), np.float32), np.zeros((c, m), np.int32)
+        self.ctx._check(self._c("push")(self._h, x.ctypes.data, lo.ctypes.data, pr.ctypes.data, am.ctypes.data))
+        out = dict(logits=lo, probs=pr, argmax=am)
+        names = self.keywords or (list(KEYWORDS) if no == NET_OUT else None)
+        if names is not None:
+            out["keywords"] = [[names[i] if i < len(names) else str(i) for i in row] for row in am]
+        if self.output_filter:
+            fl, li, sp = np.zeros((c, m, no), np.float32), np.zeros((c, m), np.int32), np.zeros((c, m), np.int32)
+            self.ctx._check(self._c("filtered")(self._h, fl.ctypes.data, li.ctypes.data, sp.ctypes.data))
+            out.update(filtered=fl, likely=li, spotted=sp)
+        if self.fsm:
+            st = np.zeros((c, m), np.int32)
+            self.ctx._check(self._c("fsm")(self._h, ctypes.byref(self._fsms), st.ctypes.data))
+            out.update(fsm_states=st, fsm=self.fsm_snapshot())
+        return out
+
+    def push_t(self, samples, logits=None, probs=None, argmax=None, filtered=None, likely=None, spotted=None, fsm_states=None, n_frames=None):
+        """Device tensors (torch, int16 / fp32 / int32 on the context's GPU); asynchronous on the context's stream. samples
+        [n_mics][n * hop]; every output [n][n_mics][..] with n = chunk_frames, or n_frames <= chunk_frames for a ragged push."""
+        n = self.chunk if n_frames is None else int(n_frames)
+        if samples.numel() != self.n_mics * n * self.hop or not samples.is_contiguous():
+            raise ValueError("push needs contiguous [n_mics, n_frames*hop] = [%d, %d] samples" % (self.n_mics, n * self.hop))
+        q = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        if n_frames is None:
+            self.ctx._check(self._c("push_dev")(self._h, q(samples), q(logits), q(probs), q(argmax)))
+        else:
+            self.ctx._check(self._c("push_n_dev")(self._h, q(samples), n, q(logits), q(probs), q(argmax)))
+        if filtered is not None or likely is not None or spotted is not None:
+            self.ctx._check(self._c("filtered_dev")(self._h, q(filtered), q(likely), q(spotted)))
+        if fsm_states is not None:
+            self.ctx._check(self._c("fsm_dev")(self._h, None, q(fsm_states)))
 
 
 class Fsm:

@@ -685,6 +685,52 @@ int edison_stream_float_filtered_dev(edison_stream_float *s, float *filt, int32_
 int edison_stream_float_fsm(edison_stream_float *s, struct edison_fsm *fsm, int32_t *states);
 int edison_stream_float_fsm_dev(edison_stream_float *s, int32_t *states);
 
+/* ---- a bank of continuous streams on the float32 X-CUBE-AI network: one push advances many microphones ----------------------
+ * n_mics independent continuous streams at ONE geometry on the float network loaded on the context (edison_fnet_load), advancing in
+ * lockstep: microphone m behaves exactly as an edison_stream_float of its own, created with the same geometry, options and network and
+ * fed microphone m's samples -- logits, probs, argmax, filtered outputs, likely, spotted, the filter state, the state machine and
+ * frames_seen, bit for bit. One push carries n frames for every microphone and costs a number of launches that depends neither on n_mics
+ * nor on n: one feature launch over the n_mics * n frames (q15 = 1: plus one strided device copy), ONE network launch over the n * n_mics
+ * windows, one filter launch.
+ *   samples         [n_mics][n * frame_step] int16: each microphone's new samples contiguous, microphone after microphone.
+ *   outputs         time-major: logits / probs [n][n_mics][n_out] float32, argmax [n][n_mics] int32; filt [n][n_mics][n_out] fp32,
+ *                   likely / spotted / states [n][n_mics] int32; the state machines fsm [n_mics]. For the usual n = 1 that is simply
+ *                   [n_mics][..]. Each may be NULL.
+ *   reset_mic       microphone `mic` alone back to a new stream's state (silent history, float zero rows, zero filter state, edisonFSM in
+ *                   RESET): from the next push on it equals a freshly created stream; the other microphones do not notice. Ordered like a
+ *                   push: it waits for device pushes still in flight and has taken effect when it returns. frames_seen is the bank's and
+ *                   stays.
+ * Errors of create: those of edison_stream_float_create, EDISON_E_ARGUMENT for n_mics outside 1 .. 4096, EDISON_E_SIZE when n_mics *
+ * chunk_frames >= 2^31; EDISON_E_NO_MEMORY when the buffers (n_mics times a stream's) cannot be allocated. A push after edison_fnet_load
+ * has replaced the network fails with EDISON_E_ARGUMENT; so does n_frames outside 1 .. chunk_frames and a microphone index outside
+ * 0 .. n_mics - 1. NULL handles: EDISON_E_ARGUMENT. Messages name float_bank. Host and device pushes may alternate, as
+ * edison_stream_float's; the getters copy the LAST push's outputs (n = its frames). A bank of one microphone issues exactly
+ * edison_stream_float's copies and kernels. */
+typedef struct edison_float_bank edison_float_bank;
+typedef struct edison_float_bank_opts {
+	int32_t n_mics;                   /* microphones, 1 .. 4096 */
+	edison_stream_float_opts stream;  /* every microphone's options */
+} edison_float_bank_opts;
+/* n_mics 1, stream = edison_stream_float_default_opts */
+void edison_float_bank_default_opts(edison_float_bank_opts *o);
+int edison_float_bank_create(edison_ctx *ctx, const edison_kws_geom *g, const edison_float_bank_opts *o, edison_float_bank **out);
+void edison_float_bank_destroy(edison_float_bank *b);
+int edison_float_bank_reset(edison_float_bank *b);
+int edison_float_bank_reset_mic(edison_float_bank *b, int mic);
+/* chunk_frames frames per microphone: samples [n_mics][chunk_frames * frame_step] */
+int edison_float_bank_push(edison_float_bank *b, const int16_t *samples /* host */, float *logits, float *probs, int32_t *argmax);
+int edison_float_bank_push_dev(edison_float_bank *b, const int16_t *samples /* device */, float *logits, float *probs, int32_t *argmax);
+/* 1 <= n_frames <= chunk_frames frames per microphone: samples [n_mics][n_frames * frame_step], outputs [n_frames][n_mics][..] */
+int edison_float_bank_push_n_dev(edison_float_bank *b, const int16_t *samples /* device */, int n_frames, float *logits, float *probs,
+                                 int32_t *argmax);
+int edison_float_bank_filtered(edison_float_bank *b, float *filt, int32_t *likely, int32_t *spotted);
+int edison_float_bank_filtered_dev(edison_float_bank *b, float *filt, int32_t *likely, int32_t *spotted);
+/* the state machines after the LAST push (fsm [n_mics], may be NULL) and every microphone's state after each of its n inferences */
+int edison_float_bank_fsm(edison_float_bank *b, struct edison_fsm *fsm /* host */, int32_t *states);
+int edison_float_bank_fsm_dev(edison_float_bank *b, struct edison_fsm *fsm /* device */, int32_t *states);
+/* frames pushed per microphone since create or reset */
+int edison_float_bank_frames_seen(edison_float_bank *b, int64_t *out);
+
 /* ---- the firmware's home-automation state machine (edisonFSM, app.c:727-928), host side, without the LEDs -------
  * RESET -> IDLE -(wake word "edison" spotted)-> HOT -(a location spotted)-> LOC -(a value spotted)-> SET -> IDLE;
  * HOT and LOC fall back to IDLE after EDI_LOC_TIMEOUT = 5000 ms (app.c:48). Time advances by dt_us per call exactly
