@@ -206,6 +206,9 @@ SIGNATURES = {
     "edison_stream_bank_fsm": (c_int, [c_void_p, c_void_p, c_void_p]),
     "edison_stream_bank_fsm_dev": (c_int, [c_void_p, c_void_p, c_void_p]),
     "edison_stream_bank_frames_seen": (c_int, [c_void_p, ctypes.POINTER(c_int64)]),
+    "edison_bank_push_present": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_bank_push_present_n_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "edison_bank_frames_seen_mics": (c_int, [c_void_p, c_void_p]),
     "edison_stream_float_default_opts": (None, [ctypes.POINTER(StreamFloatOpts)]),
     "edison_stream_float_create": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), ctypes.POINTER(StreamFloatOpts), ctypes.POINTER(c_void_p)]),
     "edison_stream_float_destroy": (None, [c_void_p]),
@@ -231,6 +234,9 @@ SIGNATURES = {
     "edison_float_bank_fsm": (c_int, [c_void_p, c_void_p, c_void_p]),
     "edison_float_bank_fsm_dev": (c_int, [c_void_p, c_void_p, c_void_p]),
     "edison_float_bank_frames_seen": (c_int, [c_void_p, ctypes.POINTER(c_int64)]),
+    "edison_fbank_push_present": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_fbank_push_present_n_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "edison_fbank_frames_seen_mics": (c_int, [c_void_p, c_void_p]),
     "edison_fsm_init": (None, [ctypes.POINTER(Fsm)]),
     "edison_fsm_step": (c_int, [ctypes.POINTER(Fsm), c_float, ctypes.c_uint32, ctypes.c_uint32, c_double]),
     # legacy firmware call surface

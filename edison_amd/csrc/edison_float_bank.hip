@@ -14,6 +14,9 @@
  * d_feat + m * mic_feat + (pos + i) * num_mfcc floats: two strides, ed_fnet_windows_kernel (fnet_windows_kernels.hip). Where one stride
  * describes the windows -- one frame (mic_feat / 4 floats apart) or one microphone (num_mfcc apart) -- the launch is ed_fnet_kernel's, so
  * a bank of one microphone issues exactly edison_stream_float's copies and kernels. The checks are edison_stream_float_create's.
+ *
+ * A push with a mask (edison_fbank_push_present*) runs the same upload and launches over all microphones; the
+ * core then holds the absent ones (edison_bank_hold.hip): one launch more, whatever n_mics.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,8 +53,9 @@ static int bank_err(edison_ctx *ctx, int code, const char *what)
 }
 
 /* The device work of a push of n frames whose samples the core has uploaded: feature rows, network, the core's end of the push. The
- * outputs go where they are told (NULL: not written), time-major; the filter reads `probs`. */
-static int enqueue_push(edison_float_bank *b, hipStream_t q, int n, float *logits, float *probs, int32_t *argmax, int host)
+ * outputs go where they are told (NULL: not written), time-major; the filter reads `probs`. present: the push's mask (host = 1: host
+ * memory), NULL: every microphone. */
+static int enqueue_push(edison_float_bank *b, hipStream_t q, int n, float *logits, float *probs, int32_t *argmax, int host, const uint8_t *present)
 {
 	ed_stream_core *c = &b->core;
 	edison_ctx *ctx = c->ctx;
@@ -91,6 +95,7 @@ static int enqueue_push(edison_float_bank *b, hipStream_t q, int n, float *logit
 		else e = ed_launch_fnet_windows(p, win, mic_rows, c->n_mics, c->nm, n, logits, probs, argmax, b->per_frame, q);
 		if (e != 0) return ed_launch_result(ctx, e, "float network kernel");
 	}
+	if (present) return ed_stream_core_finish_push_present(c, q, probs, n, host, present, logits, probs, argmax);
 	return ed_stream_core_finish_push(c, q, probs, n, host);
 }
 
@@ -177,7 +182,8 @@ extern "C" int edison_float_bank_create(edison_ctx *ctx, const edison_kws_geom *
 	return EDISON_OK;
 }
 
-extern "C" int edison_float_bank_push_n_dev(edison_float_bank *b, const int16_t *samples, int n_frames, float *logits, float *probs, int32_t *argmax)
+extern "C" int edison_fbank_push_present_n_dev(edison_float_bank *b, const int16_t *samples, const uint8_t *present, int n_frames, float *logits,
+                                               float *probs, int32_t *argmax)
 {
 	{ const int r = check_push(b, samples); if (r != EDISON_OK) return r; }
 	ed_stream_core *c = &b->core;
@@ -185,7 +191,12 @@ extern "C" int edison_float_bank_push_n_dev(edison_float_bank *b, const int16_t 
 	{ const int r = ed_stream_core_begin_push(c, q, samples, n_frames, 0); if (r != EDISON_OK) return r; }
 	/* the filter's input: the caller's probs where given, else the bank's block */
 	if (c->filter && !probs) probs = (float *)(c->d_out + b->off_probs);
-	return enqueue_push(b, q, n_frames, logits, probs, argmax, 0);
+	return enqueue_push(b, q, n_frames, logits, probs, argmax, 0, present);
+}
+
+extern "C" int edison_float_bank_push_n_dev(edison_float_bank *b, const int16_t *samples, int n_frames, float *logits, float *probs, int32_t *argmax)
+{
+	return edison_fbank_push_present_n_dev(b, samples, NULL, n_frames, logits, probs, argmax);
 }
 
 extern "C" int edison_float_bank_push_dev(edison_float_bank *b, const int16_t *samples, float *logits, float *probs, int32_t *argmax)
@@ -194,14 +205,15 @@ extern "C" int edison_float_bank_push_dev(edison_float_bank *b, const int16_t *s
 }
 
 /* host pointers: one strided upload from pinned memory, the same launches on the private stream, one download of the output block, one wait */
-extern "C" int edison_float_bank_push(edison_float_bank *b, const int16_t *samples, float *logits, float *probs, int32_t *argmax)
+extern "C" int edison_fbank_push_present(edison_float_bank *b, const int16_t *samples, const uint8_t *present, float *logits, float *probs,
+                                         int32_t *argmax)
 {
 	{ const int r = check_push(b, samples); if (r != EDISON_OK) return r; }
 	ed_stream_core *c = &b->core;
 	hipStream_t q = c->own;
 	{ const int r = ed_stream_core_begin_push(c, q, samples, c->chunk, 1); if (r != EDISON_OK) return r; }
 	{
-		const int r = enqueue_push(b, q, c->chunk, (float *)c->d_out, (float *)(c->d_out + b->off_probs), (int32_t *)(c->d_out + b->off_argmax), 1);
+		const int r = enqueue_push(b, q, c->chunk, (float *)c->d_out, (float *)(c->d_out + b->off_probs), (int32_t *)(c->d_out + b->off_argmax), 1, present);
 		if (r != EDISON_OK) return r;
 	}
 	const size_t fb = b->off_probs; /* chunk * n_mics * n_out floats */
@@ -210,6 +222,13 @@ extern "C" int edison_float_bank_push(edison_float_bank *b, const int16_t *sampl
 	if (argmax) memcpy(argmax, c->h_out + b->off_argmax, (size_t)c->chunk * c->n_mics * sizeof(int32_t));
 	return EDISON_OK;
 }
+
+extern "C" int edison_float_bank_push(edison_float_bank *b, const int16_t *samples, float *logits, float *probs, int32_t *argmax)
+{
+	return edison_fbank_push_present(b, samples, NULL, logits, probs, argmax);
+}
+
+extern "C" int edison_fbank_frames_seen_mics(edison_float_bank *b, int64_t *counts) { return ed_stream_core_frames_seen_mics(core_of(b), counts); }
 
 extern "C" int edison_float_bank_frames_seen(edison_float_bank *b, int64_t *out)
 {

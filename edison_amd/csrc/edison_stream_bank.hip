@@ -10,6 +10,9 @@
  * network kernels are the ones edison_stream_geom runs, unchanged: for frame i of the push the windows of all microphones lie at
  * d_feat + (pos + i) * nm + m * mic_feat, one base and one stride, which is what they take. Launch i writes slab i of the time-major
  * outputs. The checks, the tables and the choice of the network kernel are edison_stream_geom.hip's (edison_stream_geom.h).
+ *
+ * A push with a mask (edison_bank_push_present*) runs the same upload and launches over all microphones; the core
+ * then holds the absent ones (edison_bank_hold.hip): one launch more, whatever n_mics.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -136,8 +139,9 @@ static int bank_err(edison_ctx *ctx, int code, const char *what)
 }
 
 /* The device work of a push of n frames whose samples the core has uploaded. The outputs go where they are told (NULL: not written),
- * time-major; the filter reads its input from `fin`. */
-static int enqueue_push(edison_stream_bank *b, hipStream_t q, int n, int8_t *logits, int8_t *softmax, int32_t *argmax, const int8_t *fin, int host)
+ * time-major; the filter reads its input from `fin`. present: the push's mask (host = 1: host memory), NULL: every microphone. */
+static int enqueue_push(edison_stream_bank *b, hipStream_t q, int n, int8_t *logits, int8_t *softmax, int32_t *argmax, const int8_t *fin, int host,
+                        const uint8_t *present)
 {
 	ed_stream_core *c = &b->core;
 	edison_ctx *ctx = c->ctx;
@@ -157,6 +161,7 @@ static int enqueue_push(edison_stream_bank *b, hipStream_t q, int n, int8_t *log
 		                                    softmax ? softmax + i * slab : NULL, argmax ? argmax + (size_t)i * c->n_mics : NULL);
 		if (r != EDISON_OK) return r;
 	}
+	if (present) return ed_stream_core_finish_push_present(c, q, fin, n, host, present, logits, softmax, argmax);
 	return ed_stream_core_finish_push(c, q, fin, n, host);
 }
 
@@ -208,8 +213,8 @@ extern "C" int edison_stream_bank_create(edison_ctx *ctx, const edison_kws_geom 
 	return EDISON_OK;
 }
 
-extern "C" int edison_stream_bank_push_n_dev(edison_stream_bank *b, const int16_t *samples, int n_frames, int8_t *logits, int8_t *softmax,
-                                             int32_t *argmax)
+extern "C" int edison_bank_push_present_n_dev(edison_stream_bank *b, const int16_t *samples, const uint8_t *present, int n_frames, int8_t *logits,
+                                              int8_t *softmax, int32_t *argmax)
 {
 	{ const int r = check_push(b, samples); if (r != EDISON_OK) return r; }
 	ed_stream_core *c = &b->core;
@@ -224,7 +229,13 @@ extern "C" int edison_stream_bank_push_n_dev(edison_stream_bank *b, const int16_
 		if (!src) src = (int8_t *)(c->d_out + (b->has_softmax ? b->off_soft : 0));
 		fin = src;
 	}
-	return enqueue_push(b, q, n_frames, logits, so, argmax, fin, 0);
+	return enqueue_push(b, q, n_frames, logits, so, argmax, fin, 0, present);
+}
+
+extern "C" int edison_stream_bank_push_n_dev(edison_stream_bank *b, const int16_t *samples, int n_frames, int8_t *logits, int8_t *softmax,
+                                             int32_t *argmax)
+{
+	return edison_bank_push_present_n_dev(b, samples, NULL, n_frames, logits, softmax, argmax);
 }
 
 extern "C" int edison_stream_bank_push_dev(edison_stream_bank *b, const int16_t *samples, int8_t *logits, int8_t *softmax, int32_t *argmax)
@@ -233,7 +244,8 @@ extern "C" int edison_stream_bank_push_dev(edison_stream_bank *b, const int16_t 
 }
 
 /* host pointers: one strided upload from pinned memory, the same launches on the private stream, one download of the output block, one wait */
-extern "C" int edison_stream_bank_push(edison_stream_bank *b, const int16_t *samples, int8_t *logits, int8_t *softmax, int32_t *argmax)
+extern "C" int edison_bank_push_present(edison_stream_bank *b, const int16_t *samples, const uint8_t *present, int8_t *logits, int8_t *softmax,
+                                        int32_t *argmax)
 {
 	{ const int r = check_push(b, samples); if (r != EDISON_OK) return r; }
 	ed_stream_core *c = &b->core;
@@ -242,7 +254,7 @@ extern "C" int edison_stream_bank_push(edison_stream_bank *b, const int16_t *sam
 	{ const int r = ed_stream_core_begin_push(c, q, samples, c->chunk, 1); if (r != EDISON_OK) return r; }
 	int8_t *dl = (int8_t *)c->d_out, *ds = b->has_softmax ? (int8_t *)(c->d_out + b->off_soft) : NULL;
 	{
-		const int r = enqueue_push(b, q, c->chunk, dl, ds, (int32_t *)(c->d_out + b->off_argmax), b->has_softmax ? ds : dl, 1);
+		const int r = enqueue_push(b, q, c->chunk, dl, ds, (int32_t *)(c->d_out + b->off_argmax), b->has_softmax ? ds : dl, 1, present);
 		if (r != EDISON_OK) return r;
 	}
 	if (logits) memcpy(logits, c->h_out, cn);
@@ -250,6 +262,13 @@ extern "C" int edison_stream_bank_push(edison_stream_bank *b, const int16_t *sam
 	if (argmax) memcpy(argmax, c->h_out + b->off_argmax, entries * sizeof(int32_t));
 	return EDISON_OK;
 }
+
+extern "C" int edison_stream_bank_push(edison_stream_bank *b, const int16_t *samples, int8_t *logits, int8_t *softmax, int32_t *argmax)
+{
+	return edison_bank_push_present(b, samples, NULL, logits, softmax, argmax);
+}
+
+extern "C" int edison_bank_frames_seen_mics(edison_stream_bank *b, int64_t *counts) { return ed_stream_core_frames_seen_mics(core_of(b), counts); }
 
 extern "C" int edison_stream_bank_frames_seen(edison_stream_bank *b, int64_t *out)
 {

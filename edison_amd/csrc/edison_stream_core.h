@@ -16,6 +16,9 @@
  * share one pos. A push carries [n_mics][n * hop] samples; everything it puts out is time-major: filt [n][n_mics][n_out], likely /
  * spotted / states [n][n_mics], the machines [n_mics]. With n_mics = 1 the core issues the copies and launches it issued before it had
  * the dimension; with more, one strided copy and the banked kernels of edison_stream_bank.hip (one workgroup per microphone).
+ *
+ * A push may leave microphones out (finish_push_present): pos advances for all of them, and the kernels of
+ * edison_bank_hold.hip carry an absent microphone's history forward to the new pos and leave everything else it owns as it was.
  */
 #ifndef EDISON_STREAM_CORE_H
 #define EDISON_STREAM_CORE_H
@@ -58,7 +61,7 @@ struct ed_stream_core
 	/* every output of a push in one block (device d_out, pinned h_out), so that a host push downloads once: the owner's in front */
 	unsigned char *d_out, *h_out;
 	size_t off_filt, off_likely, off_spotted, off_states, off_fsm, out_bytes;
-	int16_t *h_in;                 /* pinned [n_mics][chunk * hop]: the host push's upload */
+	int16_t *h_in;                 /* pinned [n_mics][chunk * hop]: the host push's upload; behind it h_present */
 	float *d_state;                /* [n_mics][n_out] the filter state */
 	edison_fsm *d_fsm;             /* [n_mics] */
 	hipStream_t own;               /* host pushes run here */
@@ -67,6 +70,10 @@ struct ed_stream_core
 	int q_pending;
 	int last_n, last_staged;       /* frames of the last push; 1: its outputs are in h_out already (host push) */
 	int64_t frames_seen;
+	/* pushes that leave microphones out (finish_push_present) */
+	int64_t *d_missed;             /* [n_mics] frames of the pushes a microphone was absent from; behind it d_present */
+	unsigned char *d_present;      /* [n_mics] where a host push's mask is uploaded */
+	unsigned char *h_present;      /* pinned [n_mics], the tail of h_in's allocation */
 };
 
 /* the state machine behind the filter kernels; fsm = NULL: none */
@@ -87,6 +94,32 @@ void ed_stream_bank_launch_shift(hipStream_t q, int n_mics, int16_t *audio, int6
 void ed_stream_bank_launch_filter(hipStream_t q, int n_mics, int out_elem, const void *x, int n, int n_out, double alpha, double one_minus_alpha,
                                   double threshold, float *state, float *filt, int32_t *likely, int32_t *spotted, edsg_fsm_stage_t fs);
 
+/* A push of n frames that left microphones out, after its feature and network launches (edison_bank_hold.hip; one workgroup per
+ * microphone, a microphone with present[m] != 0 is not touched). The absent microphone's garbage went to samples a_src + tail and later
+ * and to feature bytes f_src + feat_bytes and later, so its history at a_src / f_src is intact: the hold moves it UP by a_by samples and
+ * f_by bytes, to where the next push looks for it, zeroes its rows of the network outputs out0 / out1 [n][n_mics][row_bytes] (NULL: not
+ * written), puts -1 into its argmax [n][n_mics] (NULL: none) and adds n to missed[m]. */
+struct ed_bank_hold_t
+{
+	const unsigned char *present;  /* [n_mics] device memory */
+	int16_t *audio;                /* microphone 0's buffer; a_stride samples to the next */
+	int64_t a_stride, a_src, a_by;
+	int tail;
+	int8_t *feat;                  /* microphone 0's rows; f_stride bytes to the next */
+	int64_t f_stride, f_src, f_by;
+	int feat_bytes;
+	int n, row_bytes;
+	unsigned char *out0, *out1;
+	int32_t *argmax;
+	int64_t *missed;               /* [n_mics] */
+};
+void ed_bank_launch_hold(hipStream_t q, int n_mics, const ed_bank_hold_t *h);
+/* ed_stream_bank_launch_filter for such a push: a present microphone takes that kernel's path; an absent one gets zero bytes in its rows
+ * of filt, -1 in likely and spotted, its machine's unchanged state in fs.states and fs.copy[m] = fs.fsm[m]; state[m] and fs.fsm[m] stay. */
+void ed_bank_launch_filter_present(hipStream_t q, int n_mics, const unsigned char *present, int out_elem, const void *x, int n, int n_out,
+                                   double alpha, double one_minus_alpha, double threshold, float *state, float *filt, int32_t *likely,
+                                   int32_t *spotted, edsg_fsm_stage_t fs);
+
 /* the options both public option structs carry */
 struct ed_stream_core_opts { int chunk_frames, filter, fsm; double filter_alpha, true_threshold; };
 
@@ -105,6 +138,12 @@ void ed_stream_core_free(ed_stream_core *c);
  *                with one microphone or more) into the block; pos += n; host: one download of the block to h_out and one wait; what the getters need to know of this push */
 int ed_stream_core_begin_push(ed_stream_core *c, hipStream_t q, const int16_t *samples, int n, int host);
 int ed_stream_core_finish_push(ed_stream_core *c, hipStream_t q, const void *fin, int n, int host);
+/* finish_push for a push that carries a mask: present [n_mics], nonzero = this microphone's samples count (host = 1: host memory,
+ * uploaded through h_present; host = 0: device memory, read on q). out0 / out1 [n][n_mics][n_out] of out_elem bytes and argmax
+ * [n][n_mics] are where the owner's network wrote this push (NULL: nowhere). Runs the hold, then the masked filter at grid n_mics (also
+ * for one microphone), then what finish_push does behind its filter. */
+int ed_stream_core_finish_push_present(ed_stream_core *c, hipStream_t q, const void *fin, int n, int host, const unsigned char *present, void *out0,
+                                       void *out1, int32_t *argmax);
 
 /* c = NULL: EDISON_E_ARGUMENT. The getters copy the last push's outputs (host = 1: host pointers, synchronous; host = 0: device
  * pointers, ordered on the context's stream; NULL: not copied); fsm [n_mics]. */
@@ -112,6 +151,9 @@ int ed_stream_core_reset(ed_stream_core *c);
 /* microphone `mic` alone back to a new stream's state, at the current pos: history, filter state, state machine. Waits for pushes left
  * on another HIP stream and returns when it is done, as reset. */
 int ed_stream_core_reset_mic(ed_stream_core *c, int mic);
+/* counts [n_mics] (host): the frames each microphone was present for since create or reset, frames_seen minus what it missed. Waits for
+ * pushes left on another HIP stream and returns when it is done, as reset_mic. NULL: EDISON_E_ARGUMENT. */
+int ed_stream_core_frames_seen_mics(ed_stream_core *c, int64_t *counts);
 int ed_stream_core_filtered(ed_stream_core *c, float *filt, int32_t *likely, int32_t *spotted, int host);
 int ed_stream_core_fsm(ed_stream_core *c, edison_fsm *fsm, int32_t *states, int host);
 

@@ -163,7 +163,10 @@ int ed_stream_core_create(ed_stream_core *c, edison_ctx *ctx, const char *who, i
 	c->out_bytes = off;
 	if (e == hipSuccess) e = hipMalloc((void **)&c->d_out, c->out_bytes);
 	if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_out, c->out_bytes, hipHostMallocDefault);
-	if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_in, sizeof(int16_t) * mics * push_samples, hipHostMallocDefault);
+	if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_in, sizeof(int16_t) * mics * push_samples + mics, hipHostMallocDefault);
+	if (e == hipSuccess) c->h_present = (unsigned char *)(c->h_in + mics * push_samples);
+	if (e == hipSuccess) e = hipMalloc((void **)&c->d_missed, mics * sizeof(int64_t) + mics);
+	if (e == hipSuccess) c->d_present = (unsigned char *)(c->d_missed + mics);
 	if (e == hipSuccess && c->filter) e = hipMalloc((void **)&c->d_state, sizeof(float) * mics * (size_t)c->n_out);
 	if (e == hipSuccess && c->fsm) e = hipMalloc((void **)&c->d_fsm, mics * sizeof(edison_fsm));
 	if (e != hipSuccess)
@@ -183,6 +186,7 @@ void ed_stream_core_free(ed_stream_core *c)
 	if (c->d_out) (void)hipFree(c->d_out);
 	if (c->d_state) (void)hipFree(c->d_state);
 	if (c->d_fsm) (void)hipFree(c->d_fsm);
+	if (c->d_missed) (void)hipFree(c->d_missed);
 	if (c->h_in) (void)hipHostFree(c->h_in);
 	if (c->h_out) (void)hipHostFree(c->h_out);
 	if (c->ev) (void)hipEventDestroy(c->ev);
@@ -237,6 +241,7 @@ int ed_stream_core_reset(ed_stream_core *c)
 	c->pos = 0;
 	{ const int r = start_state(c, 0, c->n_mics); if (r != EDISON_OK) return r; }
 	ED_HIP(ctx, hipMemsetAsync(c->d_out, 0, c->out_bytes, c->own));
+	ED_HIP(ctx, hipMemsetAsync(c->d_missed, 0, (size_t)c->n_mics * sizeof(int64_t), c->own));
 	ED_HIP(ctx, hipStreamSynchronize(c->own));
 	memset(c->h_out, 0, c->out_bytes);
 	c->q_pending = 0;
@@ -261,18 +266,42 @@ int ed_stream_core_begin_push(ed_stream_core *c, hipStream_t q, const int16_t *s
 	return EDISON_OK;
 }
 
+/* the filter's state machine stage, writing into the output block; without opts.fsm: none */
+static edsg_fsm_stage_t fsm_stage(ed_stream_core *c)
+{
+	edsg_fsm_stage_t fs;
+	memset(&fs, 0, sizeof(fs));
+	if (c->fsm)
+	{
+		fs.fsm = c->d_fsm; fs.states = (int32_t *)(c->d_out + c->off_states); fs.copy = (edison_fsm *)(c->d_out + c->off_fsm);
+		fs.dt_us = c->dt_us; fs.roles = c->roles;
+	}
+	return fs;
+}
+
+/* behind the filter of a push of n frames: pos, the host push's download and wait, what the getters need to know */
+static int end_push(ed_stream_core *c, hipStream_t q, int n, int host)
+{
+	c->pos += n;
+	if (host)
+	{
+		ED_HIP(c->ctx, hipMemcpyAsync(c->h_out, c->d_out, c->out_bytes, hipMemcpyDeviceToHost, q));
+		ED_HIP(c->ctx, hipStreamSynchronize(q));
+	}
+	else c->q_last = q;
+	c->q_pending = !host;
+	c->last_n = n;
+	c->last_staged = host;
+	c->frames_seen += n;
+	return EDISON_OK;
+}
+
 int ed_stream_core_finish_push(ed_stream_core *c, hipStream_t q, const void *fin, int n, int host)
 {
 	if (c->filter)
 	{
 		unsigned char *o = c->d_out;
-		edsg_fsm_stage_t fs;
-		memset(&fs, 0, sizeof(fs));
-		if (c->fsm)
-		{
-			fs.fsm = c->d_fsm; fs.states = (int32_t *)(o + c->off_states); fs.copy = (edison_fsm *)(o + c->off_fsm);
-			fs.dt_us = c->dt_us; fs.roles = c->roles;
-		}
+		const edsg_fsm_stage_t fs = fsm_stage(c);
 		float *filt = (float *)(o + c->off_filt);
 		int32_t *likely = (int32_t *)(o + c->off_likely), *spotted = (int32_t *)(o + c->off_spotted);
 		if (c->n_mics > 1)
@@ -286,17 +315,48 @@ int ed_stream_core_finish_push(ed_stream_core *c, hipStream_t q, const void *fin
 			                   c->one_minus_alpha, c->threshold, c->d_state, filt, likely, spotted, fs);
 		if (hipGetLastError() != hipSuccess) return core_err(c->ctx, c->who, EDISON_E_RUNTIME, "filter launch failed");
 	}
-	c->pos += n;
+	return end_push(c, q, n, host);
+}
+
+int ed_stream_core_finish_push_present(ed_stream_core *c, hipStream_t q, const void *fin, int n, int host, const unsigned char *present, void *out0,
+                                       void *out1, int32_t *argmax)
+{
 	if (host)
 	{
-		ED_HIP(c->ctx, hipMemcpyAsync(c->h_out, c->d_out, c->out_bytes, hipMemcpyDeviceToHost, q));
-		ED_HIP(c->ctx, hipStreamSynchronize(q));
+		/* the pushes before this one on q have been waited for (a host push ends with a wait), so h_present is free */
+		memcpy(c->h_present, present, (size_t)c->n_mics);
+		ED_HIP(c->ctx, hipMemcpyAsync(c->d_present, c->h_present, (size_t)c->n_mics, hipMemcpyHostToDevice, q));
+		present = c->d_present;
 	}
-	else c->q_last = q;
-	c->q_pending = !host;
-	c->last_n = n;
-	c->last_staged = host;
-	c->frames_seen += n;
+	ed_bank_hold_t h;
+	memset(&h, 0, sizeof(h));
+	h.present = present;
+	h.audio = c->d_audio; h.a_stride = (int64_t)c->mic_audio; h.a_src = (int64_t)c->pos * c->hop; h.a_by = (int64_t)n * c->hop; h.tail = c->tail;
+	h.feat = (int8_t *)c->d_feat; h.f_stride = (int64_t)c->mic_feat;
+	h.f_src = (int64_t)c->pos * c->nm * c->feat_elem; h.f_by = (int64_t)n * c->nm * c->feat_elem; h.feat_bytes = c->feat_elem * (c->F - 1) * c->nm;
+	h.n = n; h.row_bytes = c->n_out * c->out_elem;
+	h.out0 = (unsigned char *)out0; h.out1 = (unsigned char *)out1; h.argmax = argmax;
+	h.missed = c->d_missed;
+	ed_bank_launch_hold(q, c->n_mics, &h);
+	if (hipGetLastError() != hipSuccess) return core_err(c->ctx, c->who, EDISON_E_RUNTIME, "hold launch failed");
+	if (c->filter)
+	{
+		unsigned char *o = c->d_out;
+		ed_bank_launch_filter_present(q, c->n_mics, present, c->out_elem, fin, n, c->n_out, c->alpha, c->one_minus_alpha, c->threshold, c->d_state,
+		                              (float *)(o + c->off_filt), (int32_t *)(o + c->off_likely), (int32_t *)(o + c->off_spotted), fsm_stage(c));
+		if (hipGetLastError() != hipSuccess) return core_err(c->ctx, c->who, EDISON_E_RUNTIME, "filter launch failed");
+	}
+	return end_push(c, q, n, host);
+}
+
+int ed_stream_core_frames_seen_mics(ed_stream_core *c, int64_t *counts)
+{
+	if (!c || !counts) return EDISON_E_ARGUMENT;
+	{ const int r = order_after(c, c->own); if (r != EDISON_OK) return r; }
+	ED_HIP(c->ctx, hipMemcpyAsync(counts, c->d_missed, (size_t)c->n_mics * sizeof(int64_t), hipMemcpyDeviceToHost, c->own));
+	ED_HIP(c->ctx, hipStreamSynchronize(c->own));
+	c->q_pending = 0;
+	for (int m = 0; m < c->n_mics; m++) counts[m] = c->frames_seen - counts[m];
 	return EDISON_OK;
 }
 

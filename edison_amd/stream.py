@@ -56,6 +56,76 @@ def _fsm_dict(f):
                 raw=(f.state, f.hot_timeout_ms, f.wake_idx, f.loc_idx, f.val_idx, f.last_loc, f.last_val, f.commands))
 
 
+class _Bank(_Handle):
+    """What StreamBank and FloatBank share: the per-microphone calls, and the mask of a push that leaves microphones out (``_P`` names
+    those C functions, ``_WHO`` is the bank's message prefix)."""
+    _P = _WHO = None
+
+    def frames_seen(self):
+        """Frames pushed per microphone since the bank was made or reset."""
+        n = ctypes.c_int64()
+        self.ctx._check(self._c("frames_seen")(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def frames_seen_mics(self):
+        """int64 [n_mics]: the frames each microphone was present for since the bank was made or reset (``reset_mic`` keeps the count).
+        Waits for pushes in flight."""
+        out = np.zeros(self.n_mics, np.int64)
+        self.ctx._check(getattr(self._L, self._P + "frames_seen_mics")(self._h, out.ctypes.data))
+        return out
+
+    def reset_mic(self, m):
+        """Microphone m alone back to a new stream's state; the others do not notice."""
+        self.ctx._check(self._c("reset_mic")(self._h, int(m)))
+
+    def _mask_error(self, what):
+        return EdisonError(_lib.E_ARGUMENT, "%s: present must be %s" % (self._WHO, what))
+
+    def _host_present(self, present):
+        """None, or the mask of a host push as contiguous uint8 [n_mics] (bool counts as uint8)."""
+        if present is None:
+            return None
+        p = np.asarray(present)
+        if p.dtype == np.bool_:
+            p = p.view(np.uint8)
+        if p.dtype != np.uint8 or p.shape != (self.n_mics,):
+            raise self._mask_error("uint8 [n_mics] = [%d], not %s %s" % (self.n_mics, p.dtype, list(p.shape)))
+        return np.ascontiguousarray(p)
+
+    def _push_t(self, samples, logits, second, argmax, filtered, likely, spotted, fsm_states, n_frames, present):
+        """push_t behind either signature: `second` is the softmax or the probabilities."""
+        n = self.chunk if n_frames is None else int(n_frames)
+        if samples.numel() != self.n_mics * n * self.hop or not samples.is_contiguous():
+            raise ValueError("push needs contiguous [n_mics, n_frames*hop] = [%d, %d] samples" % (self.n_mics, n * self.hop))
+        q = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        if present is not None:
+            if str(present.dtype) not in ("torch.uint8", "torch.bool") or tuple(present.shape) != (self.n_mics,) or not present.is_contiguous() \
+                    or present.device != samples.device:
+                raise self._mask_error("a contiguous uint8 [n_mics] = [%d] tensor on the samples' device" % self.n_mics)
+            self.ctx._check(getattr(self._L, self._P + "push_present_n_dev")(self._h, q(samples), q(present), n, q(logits), q(second), q(argmax)))
+        elif n_frames is None:
+            self.ctx._check(self._c("push_dev")(self._h, q(samples), q(logits), q(second), q(argmax)))
+        else:
+            self.ctx._check(self._c("push_n_dev")(self._h, q(samples), n, q(logits), q(second), q(argmax)))
+        if filtered is not None or likely is not None or spotted is not None:
+            self.ctx._check(self._c("filtered_dev")(self._h, q(filtered), q(likely), q(spotted)))
+        if fsm_states is not None:
+            self.ctx._check(self._c("fsm_dev")(self._h, None, q(fsm_states)))
+
+    def _filter_tail(self, out):
+        """The filter's and the state machine's outputs of a host push, behind the network's."""
+        c, m, no = self.chunk, self.n_mics, self.n_out
+        if self.output_filter:
+            fl, li, sp = np.zeros((c, m, no), np.float32), np.zeros((c, m), np.int32), np.zeros((c, m), np.int32)
+            self.ctx._check(self._c("filtered")(self._h, fl.ctypes.data, li.ctypes.data, sp.ctypes.data))
+            out.update(filtered=fl, likely=li, spotted=sp)
+        if self.fsm:
+            st = np.zeros((c, m), np.int32)
+            self.ctx._check(self._c("fsm")(self._h, ctypes.byref(self._fsms), st.ctypes.data))
+            out.update(fsm_states=st, fsm=self.fsm_snapshot())
+        return out
+
+
 class _SlidingStream(_Handle):
     """What GeomStream and FloatStream share around their own network outputs: in a host push the sample check in front and the filter's
     and the state machine's outputs behind, and the device push."""
@@ -216,12 +286,16 @@ class GeomStream(_SlidingStream):
         self._push_t(samples, logits, softmax, argmax, filtered, likely, spotted, n_frames)
 
 
-class StreamBank(_Handle):
+class StreamBank(_Bank):
     """Many microphones through one graph -- Python handle on ``edison_stream_bank_*``: ``n_mics`` continuous streams at one geometry
     on the loaded graph, advancing in lockstep. Microphone m behaves exactly as a ``GeomStream`` of its own fed microphone m's samples;
-    a push costs a number of launches that does not depend on ``n_mics``. Outputs are time-major, [frames of the push][n_mics][..]."""
+    a push costs a number of launches that does not depend on ``n_mics``. Outputs are time-major, [frames of the push][n_mics][..].
 
-    _C = "edison_stream_bank_"
+    A push may leave microphones out (``present``, uint8 [n_mics], nonzero = present): an absent microphone's stream stays untouched,
+    as if the push had not happened for it; its samples are ignored and its rows of the push hold a fill (zeros, -1 in argmax, likely
+    and spotted, the unchanged state in fsm_states). ``frames_seen_mics`` counts each microphone's own frames."""
+
+    _C, _P, _WHO = "edison_stream_bank_", "edison_bank_", "stream_bank"
 
     def __init__(self, ctx, geometry, n_mics, chunk_frames=1, output_filter=False, alpha=0.9, threshold=0.5, fsm=False):
         self.ctx = ctx or default_context()
@@ -244,61 +318,40 @@ class StreamBank(_Handle):
         self.output_filter, self.fsm = bool(output_filter or fsm), bool(fsm)
         self._fsms = (_lib.Fsm * self.n_mics)()
 
-    def frames_seen(self):
-        """Frames pushed per microphone since the bank was made or reset."""
-        n = ctypes.c_int64()
-        self.ctx._check(self._c("frames_seen")(self._h, ctypes.byref(n)))
-        return int(n.value)
-
-    def reset_mic(self, m):
-        """Microphone m alone back to a new stream's state; the others do not notice."""
-        self.ctx._check(self._c("reset_mic")(self._h, int(m)))
-
     def fsm_snapshot(self):
         """The state machines as the last host push saw them: one ``GeomStream.fsm_snapshot`` dict per microphone."""
         return [_fsm_dict(f) for f in self._fsms]
 
-    def push(self, samples):
+    def push(self, samples, present=None):
         """samples: [n_mics, chunk_frames * hop] new int16 samples (host). Returns ``GeomStream.push``'s dict with the microphone axis
         added: logits / softmax [chunk][n_mics][n_out] (softmax None for a graph without Softmax), argmax [chunk][n_mics], ``keywords``
         [chunk][n_mics] for a graph with 10 outputs; with the filter filtered [chunk][n_mics][n_out] fp32, likely, spotted
-        [chunk][n_mics]; with the state machine fsm_states [chunk][n_mics] and fsm, a list of n_mics snapshots."""
+        [chunk][n_mics]; with the state machine fsm_states [chunk][n_mics] and fsm, a list of n_mics snapshots. ``present``: uint8
+        [n_mics] (host), nonzero = this microphone's samples count; None: everyone. It comes back as ``present``; an absent
+        microphone's rows hold the fill and its keywords None."""
         x = np.ascontiguousarray(samples, dtype=np.int16)
         if x.shape != (self.n_mics, self.chunk * self.hop):
             raise ValueError("push needs [n_mics, chunk_frames*hop] = [%d, %d] samples" % (self.n_mics, self.chunk * self.hop))
+        p = self._host_present(present)
         c, m, no = self.chunk, self.n_mics, self.n_out
         lo, am = np.zeros((c, m, no), np.int8), np.zeros((c, m), np.int32)
         so = np.zeros((c, m, no), np.int8) if self.has_softmax else None
         ptr = lambda a: None if a is None else a.ctypes.data
-        self.ctx._check(self._c("push")(self._h, x.ctypes.data, lo.ctypes.data, ptr(so), am.ctypes.data))
-        out = dict(logits=lo, softmax=so, argmax=am)
-        if no == NET_OUT:
-            out["keywords"] = [[KEYWORDS[i] for i in row] for row in am]
-        if self.output_filter:
-            fl, li, sp = np.zeros((c, m, no), np.float32), np.zeros((c, m), np.int32), np.zeros((c, m), np.int32)
-            self.ctx._check(self._c("filtered")(self._h, fl.ctypes.data, li.ctypes.data, sp.ctypes.data))
-            out.update(filtered=fl, likely=li, spotted=sp)
-        if self.fsm:
-            st = np.zeros((c, m), np.int32)
-            self.ctx._check(self._c("fsm")(self._h, ctypes.byref(self._fsms), st.ctypes.data))
-            out.update(fsm_states=st, fsm=self.fsm_snapshot())
-        return out
-
-    def push_t(self, samples, logits=None, softmax=None, argmax=None, filtered=None, likely=None, spotted=None, fsm_states=None, n_frames=None):
-        """Device tensors (torch, int16 / int8 / int32 / fp32 on the context's GPU); asynchronous on the context's stream. samples
-        [n_mics][n * hop]; every output [n][n_mics][..] with n = chunk_frames, or n_frames <= chunk_frames for a ragged push."""
-        n = self.chunk if n_frames is None else int(n_frames)
-        if samples.numel() != self.n_mics * n * self.hop or not samples.is_contiguous():
-            raise ValueError("push needs contiguous [n_mics, n_frames*hop] = [%d, %d] samples" % (self.n_mics, n * self.hop))
-        q = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        if n_frames is None:
-            self.ctx._check(self._c("push_dev")(self._h, q(samples), q(logits), q(softmax), q(argmax)))
+        if p is None:
+            self.ctx._check(self._c("push")(self._h, x.ctypes.data, lo.ctypes.data, ptr(so), am.ctypes.data))
         else:
-            self.ctx._check(self._c("push_n_dev")(self._h, q(samples), n, q(logits), q(softmax), q(argmax)))
-        if filtered is not None or likely is not None or spotted is not None:
-            self.ctx._check(self._c("filtered_dev")(self._h, q(filtered), q(likely), q(spotted)))
-        if fsm_states is not None:
-            self.ctx._check(self._c("fsm_dev")(self._h, None, q(fsm_states)))
+            self.ctx._check(self._L.edison_bank_push_present(self._h, x.ctypes.data, p.ctypes.data, lo.ctypes.data, ptr(so), am.ctypes.data))
+        out = dict(logits=lo, softmax=so, argmax=am, present=p)
+        if no == NET_OUT:
+            out["keywords"] = [[KEYWORDS[i] if i >= 0 else None for i in row] for row in am]
+        return self._filter_tail(out)
+
+    def push_t(self, samples, logits=None, softmax=None, argmax=None, filtered=None, likely=None, spotted=None, fsm_states=None, n_frames=None,
+               present=None):
+        """Device tensors (torch, int16 / int8 / int32 / fp32 on the context's GPU); asynchronous on the context's stream. samples
+        [n_mics][n * hop]; every output [n][n_mics][..] with n = chunk_frames, or n_frames <= chunk_frames for a ragged push. ``present``:
+        a device uint8 [n_mics] tensor, read on the context's stream (keep it unchanged until the push has run); None: everyone."""
+        self._push_t(samples, logits, softmax, argmax, filtered, likely, spotted, fsm_states, n_frames, present)
 
 
 class FloatStream(_SlidingStream):
@@ -362,13 +415,15 @@ class FloatStream(_SlidingStream):
         self._push_t(samples, logits, probs, argmax, filtered, likely, spotted, n_frames)
 
 
-class FloatBank(_Handle):
+class FloatBank(_Bank):
     """Many microphones through one float32 X-CUBE-AI network -- Python handle on ``edison_float_bank_*``: ``n_mics`` continuous streams
     at one geometry on the float network loaded on the context (``Context.fnet_load``), advancing in lockstep. Microphone m behaves
     exactly as a ``FloatStream`` of its own (same geometry, flow and options) fed microphone m's samples; a push costs a number of
-    launches that depends neither on ``n_mics`` nor on its frames. Outputs are time-major, [frames of the push][n_mics][..]."""
+    launches that depends neither on ``n_mics`` nor on its frames. Outputs are time-major, [frames of the push][n_mics][..].
 
-    _C = "edison_float_bank_"
+    A push may leave microphones out (``present``), as ``StreamBank``'s: the absent microphone's stream stays untouched."""
+
+    _C, _P, _WHO = "edison_float_bank_", "edison_fbank_", "float_bank"
 
     def __init__(self, ctx, n_mics, geometry=None, q15=False, chunk_frames=1, output_filter=False, alpha=0.5, threshold=0.5, fsm=False,
                  clip_min=None, clip_max=None):
@@ -399,60 +454,39 @@ class FloatBank(_Handle):
         self.output_filter, self.fsm = bool(output_filter or fsm), bool(fsm)
         self._fsms = (_lib.Fsm * self.n_mics)()
 
-    def frames_seen(self):
-        """Frames pushed per microphone since the bank was made or reset."""
-        n = ctypes.c_int64()
-        self.ctx._check(self._c("frames_seen")(self._h, ctypes.byref(n)))
-        return int(n.value)
-
-    def reset_mic(self, m):
-        """Microphone m alone back to a new stream's state; the others do not notice."""
-        self.ctx._check(self._c("reset_mic")(self._h, int(m)))
-
     def fsm_snapshot(self):
         """The state machines as the last host push saw them: one ``FloatStream.fsm_snapshot`` dict per microphone."""
         return [_fsm_dict(f) for f in self._fsms]
 
-    def push(self, samples):
+    def push(self, samples, present=None):
         """samples: [n_mics, chunk_frames * hop] new int16 samples (host). Returns ``FloatStream.push``'s dict with the microphone axis
         added: logits / probs float32 [chunk][n_mics][n_out], argmax [chunk][n_mics], ``keywords`` [chunk][n_mics] (the names of the
         network's .ednf; KEYWORDS for a 10-output network without names); with the filter filtered [chunk][n_mics][n_out] fp32, likely,
-        spotted [chunk][n_mics]; with the state machine fsm_states [chunk][n_mics] and fsm, a list of n_mics snapshots."""
+        spotted [chunk][n_mics]; with the state machine fsm_states [chunk][n_mics] and fsm, a list of n_mics snapshots. ``present``:
+        uint8 [n_mics] (host), nonzero = this microphone's samples count; None: everyone. It comes back as ``present``; an absent
+        microphone's rows hold the fill and its keywords None."""
         x = np.ascontiguousarray(samples, dtype=np.int16)
         if x.shape != (self.n_mics, self.chunk * self.hop):
             raise ValueError("push needs [n_mics, chunk_frames*hop] = [%d, %d] samples" % (self.n_mics, self.chunk * self.hop))
+        p = self._host_present(present)
         c, m, no = self.chunk, self.n_mics, self.n_out
         lo, pr, am = np.zeros((c, m, no), np.float32), np.zeros((c, m, no), np.float32), np.zeros((c, m), np.int32)
-        self.ctx._check(self._c("push")(self._h, x.ctypes.data, lo.ctypes.data, pr.ctypes.data, am.ctypes.data))
-        out = dict(logits=lo, probs=pr, argmax=am)
+        if p is None:
+            self.ctx._check(self._c("push")(self._h, x.ctypes.data, lo.ctypes.data, pr.ctypes.data, am.ctypes.data))
+        else:
+            self.ctx._check(self._L.edison_fbank_push_present(self._h, x.ctypes.data, p.ctypes.data, lo.ctypes.data, pr.ctypes.data, am.ctypes.data))
+        out = dict(logits=lo, probs=pr, argmax=am, present=p)
         names = self.keywords or (list(KEYWORDS) if no == NET_OUT else None)
         if names is not None:
-            out["keywords"] = [[names[i] if i < len(names) else str(i) for i in row] for row in am]
-        if self.output_filter:
-            fl, li, sp = np.zeros((c, m, no), np.float32), np.zeros((c, m), np.int32), np.zeros((c, m), np.int32)
-            self.ctx._check(self._c("filtered")(self._h, fl.ctypes.data, li.ctypes.data, sp.ctypes.data))
-            out.update(filtered=fl, likely=li, spotted=sp)
-        if self.fsm:
-            st = np.zeros((c, m), np.int32)
-            self.ctx._check(self._c("fsm")(self._h, ctypes.byref(self._fsms), st.ctypes.data))
-            out.update(fsm_states=st, fsm=self.fsm_snapshot())
-        return out
+            out["keywords"] = [[None if i < 0 else names[i] if i < len(names) else str(i) for i in row] for row in am]
+        return self._filter_tail(out)
 
-    def push_t(self, samples, logits=None, probs=None, argmax=None, filtered=None, likely=None, spotted=None, fsm_states=None, n_frames=None):
+    def push_t(self, samples, logits=None, probs=None, argmax=None, filtered=None, likely=None, spotted=None, fsm_states=None, n_frames=None,
+               present=None):
         """Device tensors (torch, int16 / fp32 / int32 on the context's GPU); asynchronous on the context's stream. samples
-        [n_mics][n * hop]; every output [n][n_mics][..] with n = chunk_frames, or n_frames <= chunk_frames for a ragged push."""
-        n = self.chunk if n_frames is None else int(n_frames)
-        if samples.numel() != self.n_mics * n * self.hop or not samples.is_contiguous():
-            raise ValueError("push needs contiguous [n_mics, n_frames*hop] = [%d, %d] samples" % (self.n_mics, n * self.hop))
-        q = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        if n_frames is None:
-            self.ctx._check(self._c("push_dev")(self._h, q(samples), q(logits), q(probs), q(argmax)))
-        else:
-            self.ctx._check(self._c("push_n_dev")(self._h, q(samples), n, q(logits), q(probs), q(argmax)))
-        if filtered is not None or likely is not None or spotted is not None:
-            self.ctx._check(self._c("filtered_dev")(self._h, q(filtered), q(likely), q(spotted)))
-        if fsm_states is not None:
-            self.ctx._check(self._c("fsm_dev")(self._h, None, q(fsm_states)))
+        [n_mics][n * hop]; every output [n][n_mics][..] with n = chunk_frames, or n_frames <= chunk_frames for a ragged push. ``present``:
+        a device uint8 [n_mics] tensor, read on the context's stream (keep it unchanged until the push has run); None: everyone."""
+        self._push_t(samples, logits, probs, argmax, filtered, likely, spotted, fsm_states, n_frames, present)
 
 
 class Fsm:

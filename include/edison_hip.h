@@ -624,6 +624,28 @@ int edison_stream_bank_fsm_dev(edison_stream_bank *b, struct edison_fsm *fsm /* 
 /* frames pushed per microphone since create or reset */
 int edison_stream_bank_frames_seen(edison_stream_bank *b, int64_t *out);
 
+/* ---- a bank push may leave microphones out: their streams stay untouched --------------------------------------------------
+ * A late or lost packet, a muted device, a recording that has ended: the push carries a mask, present [n_mics] uint8, nonzero = this
+ * microphone's samples count, NULL = every microphone (then the call IS the push above). Push k carries the set P_k of present
+ * microphones and n_k frames; microphone m behaves exactly as an edison_stream_geom of its own that was pushed only the pushes k with m
+ * in P_k -- its rows of those pushes, its state machine and its frame count, byte for byte. For m outside P_k nothing of m changes:
+ * sample history, feature rows, filter state, state machine, frame count. Its samples in the push buffer are ignored and may hold
+ * anything (they must be readable). Its rows of the push's outputs hold a defined fill: zero bytes in logits, softmax and filt, -1 in
+ * argmax, likely and spotted, the machine's unchanged state in states, the unchanged machine in fsm [m]. The bank-wide frames_seen
+ * advances by n_k as before, also when nobody is present.
+ *   present         host memory for the host push, device memory for the device push, which reads it on the context's stream: it
+ *                   stays valid and unchanged until the push has run.
+ *   frames_seen_mics  counts [n_mics] int64 (host): the frames each microphone was present for since create or reset. Synchronous and
+ *                   ordered after pushes in flight, as reset_mic. reset zeroes the counts; reset_mic does not, as frames_seen.
+ * A push with a mask costs one launch more than without, whatever n_mics, and the host push one upload of n_mics bytes; an absent
+ * microphone still takes its share of the feature and network launches. Errors as the pushes above: EDISON_E_ARGUMENT for a NULL bank,
+ * NULL samples or counts and for n_frames outside 1 .. chunk_frames. Messages name stream_bank. */
+int edison_bank_push_present(edison_stream_bank *b, const int16_t *samples /* host */, const uint8_t *present /* host */, int8_t *logits,
+                             int8_t *softmax, int32_t *argmax);
+int edison_bank_push_present_n_dev(edison_stream_bank *b, const int16_t *samples /* device */, const uint8_t *present /* device */, int n_frames,
+                                   int8_t *logits, int8_t *softmax, int32_t *argmax);
+int edison_bank_frames_seen_mics(edison_stream_bank *b, int64_t *counts);
+
 /* ---- continuous mode for the float32 X-CUBE-AI network ------------------------------------------------------------------
  * The continuous counterpart of edison_kws_float_batch*: the firmware's continuous loop for its default network type, NET_TYPE_CUBE
  * (app.c:288-371, 630-719), on the float network loaded on the context (edison_fnet_load). A separate object: edison_stream_geom_* and
@@ -730,6 +752,15 @@ int edison_float_bank_fsm(edison_float_bank *b, struct edison_fsm *fsm /* host *
 int edison_float_bank_fsm_dev(edison_float_bank *b, struct edison_fsm *fsm /* device */, int32_t *states);
 /* frames pushed per microphone since create or reset */
 int edison_float_bank_frames_seen(edison_float_bank *b, int64_t *out);
+
+/* A float bank push may leave microphones out, as edison_bank_push_present*: the same mask, the same defining property with an
+ * edison_stream_float per microphone, the same fill (zero bytes in logits, probs and filt; -1 in argmax, likely and spotted; the
+ * unchanged state and machine), the same counts and the same cost of one launch more. Messages name float_bank. */
+int edison_fbank_push_present(edison_float_bank *b, const int16_t *samples /* host */, const uint8_t *present /* host */, float *logits,
+                              float *probs, int32_t *argmax);
+int edison_fbank_push_present_n_dev(edison_float_bank *b, const int16_t *samples /* device */, const uint8_t *present /* device */, int n_frames,
+                                    float *logits, float *probs, int32_t *argmax);
+int edison_fbank_frames_seen_mics(edison_float_bank *b, int64_t *counts);
 
 /* ---- the firmware's home-automation state machine (edisonFSM, app.c:727-928), host side, without the LEDs -------
  * RESET -> IDLE -(wake word "edison" spotted)-> HOT -(a location spotted)-> LOC -(a value spotted)-> SET -> IDLE;
