@@ -14,6 +14,7 @@ OK = 0
 E_ARGUMENT, E_LENGTH, E_SIZE, E_NO_MEMORY, E_MORE_TODO = -1, -2, -3, -7, -8
 E_RUNTIME, E_NO_IMPL, E_NO_DEVICE, E_NO_MODEL = -16, -17, -18, -19
 MFCC_A, MFCC_B, MFCC_C, MFCC_TF, MFCC_USE_LOG = 0, 1, 2, 3, 0x100
+EVAL_NNOM, EVAL_KERAS, EVAL_ARGMAX = 0, 1, 2
 
 FS, FRAME_LEN, NUM_MEL, NUM_MFCC, UTT_FRAMES, NET_IN, NET_OUT = 16000, 1024, 32, 13, 31, 403, 10
 DIST_ID_BYTES = 128
@@ -71,6 +72,16 @@ class StreamFloatOpts(ctypes.Structure):
 class FloatBankOpts(ctypes.Structure):
     """edison_float_bank_opts"""
     _fields_ = [("n_mics", ctypes.c_int32), ("stream", StreamFloatOpts)]
+
+
+class EvalOpts(ctypes.Structure):
+    """edison_eval_opts"""
+    _fields_ = [(k, c_int) for k in ("rule", "n_classes", "top_k", "max_blocks")]
+
+
+class EvalTotals(ctypes.Structure):
+    """edison_eval_totals"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("count", "skipped", "correct")]
 
 
 class Fsm(ctypes.Structure):
@@ -272,6 +283,19 @@ SIGNATURES = {
     "edison_f32_stream_predict_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "edison_f32_stream_predict": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "edison_nnom_predict": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "edison_eval_default_opts": (None, [ctypes.POINTER(EvalOpts)]),
+    "edison_eval_create": (c_int, [c_void_p, ctypes.POINTER(EvalOpts), ctypes.POINTER(c_void_p)]),
+    "edison_eval_destroy": (None, [c_void_p]),
+    "edison_eval_reset": (c_int, [c_void_p]),
+    "edison_eval_add_i8_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "edison_eval_add_f32_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "edison_eval_add_i8": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "edison_eval_add_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "edison_eval_result": (c_int, [c_void_p, ctypes.POINTER(EvalTotals), c_void_p, c_void_p]),
+    "edison_nnom_prediction_run": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           ctypes.POINTER(EvalTotals)]),
+    "edison_eval_f32_host": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     ctypes.POINTER(EvalTotals)]),
     "edison_f32_stream_create": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "edison_f32_stream_destroy": (None, [c_void_p]),
     "edison_f32_stream_reset": (c_int, [c_void_p]),

@@ -521,6 +521,30 @@ class Context:
             self._check(fn(self._h, _t_ptr(audio), int(n_utt), int(utt_stride), _t_ptr(feat), _t_ptr(logits),
                            _t_ptr(softmax), _t_ptr(argmax)))
 
+    # ------------------------------------------------------------------ scoring a labelled data set (edison_eval_*, evaluate.py)
+    def evaluator(self, rule=None, n_classes=None, top_k=2, max_blocks=0):
+        """An evaluate.Evaluator on this context: confusion matrix and top-k counters in device memory (edison_eval_create). rule: "nnom"
+        (int8 outputs, NNoM's prediction_run), "keras" (float32, first class above 0.5) or "argmax" (float32, first maximum). Defaults:
+        "nnom" and the loaded int8 graph's output count; with only a float network loaded, "keras" and that network's count."""
+        from . import evaluate as ev
+        if rule is None:
+            rule = "nnom"
+            if n_classes is None:
+                try:
+                    self.net_info()
+                except EdisonError:
+                    rule = "keras"
+        code = ev.RULES[rule] if isinstance(rule, str) else int(rule)
+        if n_classes is None:
+            n_classes = (self.net_info() if code == _lib.EVAL_NNOM else self.fnet_info())["n_out"]
+        return ev.Evaluator(self, code, n_classes, top_k=top_k, max_blocks=max_blocks)
+
+    def evaluate(self, audio, labels, flow="kws", chunk=16384, **kw):
+        """Score a labelled data set on the GPU, chunk by chunk: see evaluate.evaluate. flow: "kws", "kws_geom", "kws_f32" or "kws_float"
+        with the arguments of kws_t / kws_geom_t / kws_f32_t / kws_float_t; returns an evaluate.EvalResult."""
+        from . import evaluate as ev
+        return ev.evaluate(self, audio, labels, flow=flow, chunk=chunk, **kw)
+
     # ------------------------------------------------------------------ multi-GPU (edison_dist_*: RCCL behind the C-ABI)
     def dist_init(self, id_bytes, rank, world_size):
         buf = ctypes.create_string_buffer(bytes(id_bytes), _lib.DIST_ID_BYTES)

@@ -22,6 +22,7 @@
 #include "../../include/edison_hip.h"
 #include "edison_fsm_core.h"
 #include "nnom_predict_core.h"
+#include "nnom_eval_core.h"
 
 /* firmware/src/ai/nnom/keywords.txt */
 static const char *const g_keywords[EDISON_NET_OUT] = {"edison", "cinema", "bedroom", "office", "livingroom",
@@ -153,6 +154,56 @@ int edison_nnom_predict(const int8_t *out, int64_t n, int n_out, uint32_t *label
 		float p;
 		ed_nnom_predict_one(out + i * n_out, n_out, &label[i], &p);
 		if (prob) prob[i] = p;
+	}
+	return EDISON_OK;
+}
+
+/* what one evaluated output adds to the counters (nnom_eval_core.h); the device does the same in ed_eval_kernel */
+static void eval_count(const ed_eval_one_t *r, int32_t t, int64_t i, int n_out, int top_k, uint64_t *confusion, uint64_t *topk_hist, uint32_t *pred,
+                       float *prob, int32_t *rank, edison_eval_totals *totals)
+{
+	if (pred) pred[i] = r->pred;
+	if (prob) prob[i] = r->prob;
+	if (rank) rank[i] = r->rank;
+	if (!r->counted)
+	{
+		if (totals) totals->skipped++;
+		return;
+	}
+	if (totals) totals->count++;
+	if (r->rank < 0) return; /* a single NNoM output: no matrix, no top-k */
+	if (confusion) confusion[(size_t)t * (size_t)n_out + r->pred]++;
+	if (topk_hist && r->rank < top_k) topk_hist[r->rank]++;
+	if (totals && r->pred == (uint32_t)t) totals->correct++;
+}
+
+static int eval_host_args(const void *out, const int32_t *labels, int64_t n, int n_out, int top_k)
+{
+	return n >= 0 && n_out >= 1 && n_out <= 256 && top_k >= 0 && (n == 0 || (out && labels));
+}
+
+/* prediction_run (nnom_utils.c:88-164) over n labelled outputs on the host: no GPU, no context */
+int edison_nnom_prediction_run(const int8_t *out, const int32_t *labels, int64_t n, int n_out, int top_k, uint64_t *confusion,
+                               uint64_t *topk_hist, uint32_t *pred, float *prob, int32_t *rank, edison_eval_totals *totals)
+{
+	if (!eval_host_args(out, labels, n, n_out, top_k)) return EDISON_E_ARGUMENT;
+	for (int64_t i = 0; i < n; i++)
+	{
+		const ed_eval_one_t r = ed_eval_i8_one(out + i * n_out, n_out, labels[i]);
+		eval_count(&r, labels[i], i, n_out, top_k, confusion, topk_hist, pred, prob, rank, totals);
+	}
+	return EDISON_OK;
+}
+
+/* predictWithConfMatrix's rule (EDISON_EVAL_KERAS) or the first maximum (EDISON_EVAL_ARGMAX) over n labelled float32 outputs, host only */
+int edison_eval_f32_host(int rule, const float *probs, const int32_t *labels, int64_t n, int n_out, int top_k, uint64_t *confusion,
+                         uint64_t *topk_hist, uint32_t *pred, float *prob, int32_t *rank, edison_eval_totals *totals)
+{
+	if ((rule != EDISON_EVAL_KERAS && rule != EDISON_EVAL_ARGMAX) || !eval_host_args(probs, labels, n, n_out, top_k)) return EDISON_E_ARGUMENT;
+	for (int64_t i = 0; i < n; i++)
+	{
+		const ed_eval_one_t r = ed_eval_f32_one(probs + i * n_out, n_out, labels[i], rule);
+		eval_count(&r, labels[i], i, n_out, top_k, confusion, topk_hist, pred, prob, rank, totals);
 	}
 	return EDISON_OK;
 }

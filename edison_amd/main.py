@@ -6,6 +6,7 @@ on the keyword-spotting hot path:
     mfcc mcu calc|single|file ...        mfcc_on_mcu.py:526-548      -> edison_amd.mfcc.mfcc_on_mcu
     kws  mcu single|fileinf|file|frame   kws_on_mcu.py:650-690       -> edison_amd.kws.kws_host
     kws  live host|mcu <wav> [--net f]   audio/main.py:231-233       -> edison_amd.kws.kws_live
+    kws  eval <audio.npy> <labels.npy>   nnom_utils.c:178-254        -> edison_amd.kws.kws_eval
 
 Where the reference talks to the STM32 board over the UART, the board's leg is computed by the GPU's bit-exact
 variant C. The remaining reference modules (mic, acquire, train, deploy, mcu) drive the board or Keras training and are
@@ -24,6 +25,7 @@ COMMANDS = {
     "kws": {
         "mcu": ("edison_amd.kws.kws_host", 2),
         "live": ("edison_amd.kws.kws_live", 2),
+        "eval": ("edison_amd.kws.kws_eval", 2),
     },
 }
 
@@ -35,6 +37,8 @@ USAGE = """usage: edison <module> <command> [<args>]
   kws  mcu single [n] | fileinf <wav> | file <wav> | frame <wav>
   kws  live host|mcu <wav> [--net <file.ednf>]
                                          the firmware's continuous mode replayed on a wav (--net: the float32 X-CUBE-AI network)
+  kws  eval <audio.npy> <labels.npy> [--graph <f> | --net <file.ednf>] [--geometry k=v,...] [--top-k K] [--chunk N]
+                                         confusion matrix and top-k accuracy on a labelled data set, counted on the GPU
 """
 
 

@@ -817,6 +817,63 @@ int aiNnomPredict(uint32_t *label, float *prob);
 int edison_nnom_predict(const int8_t *out, int64_t n, int n_out, uint32_t *label, float *prob);
 int8_t *aiNnomGetInputBuffer(void);
 int8_t *aiNnomGetOutputBuffer(void);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Scoring a labelled data set: NNoM's evaluation API -- prediction_create / prediction_run / prediction_matrix /
+ * prediction_top_k (nnom_utils.c:20-254) -- and the float model's predictWithConfMatrix (kws_keras.py:503-517), with the counters in
+ * device memory. The data set goes in chunk by chunk behind the batch calls that produce the outputs; only the counts come back.
+ *
+ * rule  EDISON_EVAL_NNOM    int8 outputs (the softmax if the graph ends in one, else the logits): prediction_run. Predicted label =
+ *                           first strict maximum; prob = (float)max / (float)(uint32 sum of out[1 .. n_out - 1], element 0 left out,
+ *                           modulo 2^32), 0 when that sum is 0 -- the reference's quirk, kept; one output: prob = out / 127.f, label =
+ *                           prob >= 0.5f, only `count` moves.
+ *       EDISON_EVAL_KERAS   float32 probabilities: first class with p > 0.5f, class 0 when there is none; prob = p[label].
+ *       EDISON_EVAL_ARGMAX  float32: first maximum (edison_fnet_batch's argmax); prob = p[label].
+ * rank  of the true label t: the number of j != t with out[t] < out[j] plus the number of j < t with out[j] == out[t]; top_k[rank]
+ *       counts it when rank < top_k (top-k accuracy = (top_k[0] + ... + top_k[k - 1]) / count). For the float rules this is the
+ *       project's own extension.
+ * labels int32; one outside 0 .. n_classes - 1 (-1: unlabelled) adds to `skipped` only; its pred / prob are still written, its rank
+ *       is -1 (as is every rank of a one-output NNOM evaluation).
+ * The matrix is always n_classes x n_classes uint64, rows = actual label, columns = predicted (NNoM's cells are uint16 and wrap at
+ * 65 536; sklearn drops classes that never occur). All counting is in integers: the result does not depend on launch shape or order. */
+#define EDISON_EVAL_NNOM 0
+#define EDISON_EVAL_KERAS 1
+#define EDISON_EVAL_ARGMAX 2
+typedef struct edison_eval edison_eval;
+typedef struct edison_eval_opts {
+	int rule;       /* EDISON_EVAL_*; default EDISON_EVAL_NNOM */
+	int n_classes;  /* 1 .. 256: outputs per utterance; default 10 */
+	int top_k;      /* >= 0: entries of the top-k histogram (entries at n_classes and above stay 0); default 2 */
+	int max_blocks; /* workgroups of one add: min(ceil(n / 256), max_blocks); 0 (default): twice the compute units */
+} edison_eval_opts;
+typedef struct edison_eval_totals {
+	uint64_t count;   /* outputs counted (label in range) */
+	uint64_t skipped; /* outputs whose label was out of range */
+	uint64_t correct; /* the trace of the matrix */
+} edison_eval_totals;
+void edison_eval_default_opts(edison_eval_opts *o);
+/* EDISON_E_ARGUMENT (message in edison_last_error) for n_classes outside 1 .. 256, a negative top_k or max_blocks, an unknown rule. */
+int edison_eval_create(edison_ctx *ctx, const edison_eval_opts *o, edison_eval **out);
+void edison_eval_destroy(edison_eval *e);
+int edison_eval_reset(edison_eval *e); /* zero the counters, stream-ordered */
+/* Count n outputs [n][n_classes] against labels [n], stream-ordered on the context's stream: an add follows a *_batch_dev call on the
+ * same context with no synchronisation in between. pred [n] uint32, prob [n] float and rank [n] int32 are optional per-utterance
+ * outputs (NULL: not written). The element type must match the rule (i8: NNOM; f32: KERAS, ARGMAX), else EDISON_E_ARGUMENT. n == 0
+ * does nothing. The host forms stage their arrays and synchronise. */
+int edison_eval_add_i8_dev(edison_eval *e, const int8_t *out, const int32_t *labels, int64_t n, uint32_t *pred, float *prob, int32_t *rank);
+int edison_eval_add_f32_dev(edison_eval *e, const float *probs, const int32_t *labels, int64_t n, uint32_t *pred, float *prob, int32_t *rank);
+int edison_eval_add_i8(edison_eval *e, const int8_t *out, const int32_t *labels, int64_t n, uint32_t *pred, float *prob, int32_t *rank);
+int edison_eval_add_f32(edison_eval *e, const float *probs, const int32_t *labels, int64_t n, uint32_t *pred, float *prob, int32_t *rank);
+/* Synchronise and copy the counters out: confusion [n_classes * n_classes], top_k [opts.top_k]; each of the three may be NULL. May be
+ * called between adds: the counters go on. */
+int edison_eval_result(edison_eval *e, edison_eval_totals *t, uint64_t *confusion, uint64_t *top_k);
+/* The same rules on the host alone (no GPU, no context, like edison_nnom_predict): they ADD to confusion [n_out * n_out], topk_hist
+ * [top_k] and *totals, which the caller zeroes first; every output pointer may be NULL. EDISON_E_ARGUMENT: n_out outside 1 .. 256, a
+ * negative n or top_k, NULL out / labels with n > 0, a rule that is not a float one. */
+int edison_nnom_prediction_run(const int8_t *out, const int32_t *labels, int64_t n, int n_out, int top_k, uint64_t *confusion,
+                               uint64_t *topk_hist, uint32_t *pred, float *prob, int32_t *rank, edison_eval_totals *totals);
+int edison_eval_f32_host(int rule, const float *probs, const int32_t *labels, int64_t n, int n_out, int top_k, uint64_t *confusion,
+                         uint64_t *topk_hist, uint32_t *pred, float *prob, int32_t *rank, edison_eval_totals *totals);
 /* firmware/src/app.c:152-153: write / push one frame's MFCCs into the process-global 403-byte net input
  * (clip to [-128,127] after integer division by NNOM_INPUT_SCALE = 1, app.c:685-693).                    */
 void mfccToNetInput(int16_t *mfcc, uint16_t in_x, uint16_t in_y, uint32_t xoffset);
