@@ -41,7 +41,7 @@
 
 #include "edison_internal.h"
 #include "edison_launch.h"
-#include "edison_fsm_core.h"
+#include "edison_postproc_core.h"
 
 /* ---- lab knobs: only a lab build (ED_LAB, tools/lab/mkvariant.py) may set them; the product build has none, and
  * tests/test_host_cpu.py checks the values below against what edison_amd/build.py compiles */
@@ -689,11 +689,8 @@ __device__ __forceinline__ void edm_main(const int8_t *__restrict__ feat, int64_
 #pragma unroll
 						for (int i = 0; i < 10; i++)
 						{
-#pragma clang fp contract(off) /* separately rounded product and sum: see ed_stream_filter_kernel */
 							const int v = (int)(int8_t)(sw[i >> 2] >> (8 * (i & 3)));
-							/* separately rounded double multiply / add (the Cortex-M4 has no double FPU, nothing is fused) */
-							const double pa = flt.alpha * (double)flt.state[i], pb = flt.one_minus_alpha * (double)(float)v; /* (not __dmul_rn / __dadd_rn: see ed_stream_filter_kernel) */
-							const float y = (float)(pa + pb);
+							const float y = ed_filter_step(flt.alpha, flt.state[i], ed_filter_term(flt.one_minus_alpha, (double)(float)v)); /* rounded as edison_postproc_core.h says */
 							flt.state[i] = y;
 							flt.filt[i] = y;
 							if (i == 0 || ymax < y) { ymax = y; imax = i; } /* arm_max_f32: the first maximum */

@@ -25,7 +25,7 @@
 #include <immintrin.h>
 
 #include "edison_ctx.h"
-#include "edison_fsm_core.h"
+#include "edison_postproc_core.h"
 
 struct edison_stream
 {
@@ -123,39 +123,23 @@ __global__ void ed_stream_shift_kernel(int16_t *dst_audio, const int16_t *src_au
  *   spotted = predMax > TRUE_THRESHOLD
  * The recurrence rounds at every step, so it is sequential in time by definition; the ten classes run on ten
  * lanes, the products (1-ALPHA)*x come from a 256-entry table (x is an int8), and the per-frame maximum is taken in
- * parallel afterwards. One workgroup.
+ * parallel afterwards. One workgroup. The arithmetic and its rounding rule: edison_postproc_core.h.
  */
-/* the state machine behind the filter: where its state lives and what a step needs (edison_fsm_core.h); fsm = NULL: none */
-struct ed_fsm_stage_t
-{
-	edison_fsm *fsm;      /* device memory, read and written                       */
-	int32_t *states;      /* [chunk] out: the state after each inference           */
-	edison_fsm *copy;     /* out: the machine after the push (the host's view), or NULL */
-	uint32_t dt_us;
-	ed_fsm_roles_t roles;
-};
-
 __global__ __launch_bounds__(256) void ed_stream_filter_kernel(const int8_t *soft, int chunk, double alpha, double one_minus_alpha,
                                                                double threshold, float *state, float *filt, int32_t *likely,
                                                                int32_t *spotted, ed_fsm_stage_t fs)
 {
 	__shared__ double bx[256];
 	const int t = threadIdx.x;
-	bx[t] = one_minus_alpha * (double)(float)(int8_t)(t - 128);
+	bx[t] = ed_filter_term(one_minus_alpha, (double)(float)(int8_t)(t - 128));
 	__syncthreads();
 	if (t < EDISON_NET_OUT)
 	{
-		/* the product and the sum are rounded SEPARATELY (the Cortex-M4 computes doubles in software, nothing is fused): HIP's
-		 * __dmul_rn / __dadd_rn are plain * and +, which the compiler's default contraction turns into one v_fma_f64 -- a
-		 * different double in the last place, and a different float wherever that sum sits next to a float rounding boundary
-		 * (found in round 4 by scripted softmax streams: one value in ~4 000; network outputs of 0 and 127 never showed it) */
 		float y = state[t];
 		for (int i = 0; i < chunk; i++)
 		{
-#pragma clang fp contract(off)
 			const int x = soft[(size_t)i * EDISON_NET_OUT + t];
-			const double a = alpha * (double)y; /* (not __dmul_rn / __dadd_rn: their bodies are compiled with the header's own contraction) */
-			y = (float)(a + bx[x + 128]);
+			y = ed_filter_step(alpha, y, bx[x + 128]);
 			filt[(size_t)i * EDISON_NET_OUT + t] = y;
 		}
 		state[t] = y;

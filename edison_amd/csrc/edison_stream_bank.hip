@@ -3,10 +3,11 @@
  * microphones at one MFCC geometry on the graph loaded on the context, advancing in lockstep. Microphone m behaves as an
  * edison_stream_geom of its own fed microphone m's samples; a push of n frames for all of them runs
  *
- *     [banked shift, only when the push would not fit] -> one strided upload -> ONE MFCC launch over n_mics * n frames
- *     -> n network launches (one per frame of the push, each over the n_mics windows of that frame) -> [ONE banked filter (+ edisonFSM)]
+ *     [the shift, only when the push would not fit] -> one strided upload -> ONE MFCC launch over n_mics * n frames
+ *     -> n network launches (one per frame of the push, each over the n_mics windows of that frame) -> [ONE filter (+ edisonFSM)]
  *
- * on the sliding-window core with n_mics microphones (edison_stream_core.h): a number of launches that does not depend on n_mics. The
+ * on the sliding-window core with n_mics microphones (edison_stream_core.h), whose shift and filter run a workgroup per microphone: a
+ * number of launches that does not depend on n_mics. This file is a host object with no kernel of its own. The
  * network kernels are the ones edison_stream_geom runs, unchanged: for frame i of the push the windows of all microphones lie at
  * d_feat + (pos + i) * nm + m * mic_feat, one base and one stride, which is what they take. Launch i writes slab i of the time-major
  * outputs. The checks, the tables and the choice of the network kernel are edison_stream_geom.hip's (edison_stream_geom.h).
@@ -30,105 +31,6 @@ struct edison_stream_bank : ed_stream_geom_part
 	ed_stream_core core;           /* int8 rows, int8 outputs, n_mics microphones */
 	size_t off_soft, off_argmax;   /* the front of the core's output block: logits [chunk][n_mics][n_out] at 0, softmax, argmax [chunk][n_mics] */
 };
-
-/* The banked shift: workgroup m moves microphone m's history -- the newest `tail` samples from a_src and feat_bytes bytes from f_src --
- * to the front of its buffers, a_stride samples and f_stride bytes behind microphone m - 1's. The rounds are those of
- * ed_stream_geom_shift_kernel (edison_stream_core.hip): the destination lies below the source and may overlap it, so in rounds of 256
- * elements every lane reads, the workgroup waits, every lane writes. */
-__global__ __launch_bounds__(256) void ed_stream_bank_shift_kernel(int16_t *audio, int64_t a_stride, int64_t a_src, int tail, int8_t *feat,
-                                                                   int64_t f_stride, int64_t f_src, int feat_bytes)
-{
-	const int t = threadIdx.x;
-	audio += (int64_t)blockIdx.x * a_stride;
-	feat += (int64_t)blockIdx.x * f_stride;
-	for (int base = 0; base < tail; base += 256)
-	{
-		const int j = base + t;
-		const int16_t v = j < tail ? audio[a_src + j] : (int16_t)0;
-		__syncthreads();
-		if (j < tail) audio[j] = v;
-		__syncthreads();
-	}
-	for (int base = 0; base < feat_bytes; base += 256)
-	{
-		const int j = base + t;
-		const int8_t v = j < feat_bytes ? feat[f_src + j] : (int8_t)0;
-		__syncthreads();
-		if (j < feat_bytes) feat[j] = v;
-		__syncthreads();
-	}
-}
-
-/* The banked filter: workgroup m runs the firmware's post-processing for microphone m with the arithmetic of
- * ed_stream_geom_filter_kernel (edison_stream_core.hip) -- product and sum rounded separately in double, no contraction, first maximum,
- * edisonFSM on lane 0. Entry i of microphone m is row i * n_mics + m of the time-major arrays x / filt [n][n_mics][n_out] and likely /
- * spotted / fs.states [n][n_mics]; between pushes it keeps state [n_mics][n_out] and fs.fsm [n_mics]. T = int8_t: the int8 graph's softmax
- * / logits (this file's bank); T = float: the float network's probabilities (edison_float_bank.hip). (double)x is exact for both. */
-template <class T>
-__global__ __launch_bounds__(256) void ed_stream_bank_filter_kernel(const T *x, int n, int n_out, double alpha, double one_minus_alpha,
-                                                                    double threshold, float *state, float *filt, int32_t *likely,
-                                                                    int32_t *spotted, edsg_fsm_stage_t fs)
-{
-	const int t = threadIdx.x;
-	const size_t m = blockIdx.x, n_mics = gridDim.x;
-	if (t < n_out)
-	{
-		float y = state[m * n_out + t];
-		for (int i = 0; i < n; i++)
-		{
-			/* the compiler's default contraction would fuse these into one v_fma_f64 (the Cortex-M4 rounds each operation) */
-#pragma clang fp contract(off)
-			const size_t at = (i * n_mics + m) * n_out + t;
-			const double a = alpha * (double)y;
-			const double b = one_minus_alpha * (double)x[at];
-			y = (float)(a + b);
-			filt[at] = y;
-		}
-		state[m * n_out + t] = y;
-	}
-	__syncthreads();
-	for (int i = t; i < n; i += 256)
-	{
-		const size_t im = i * n_mics + m;
-		const float *row = filt + im * n_out;
-		float best = row[0];
-		int idx = 0;
-		for (int c = 1; c < n_out; c++)
-			if (best < row[c]) { best = row[c]; idx = c; }
-		likely[im] = idx;
-		spotted[im] = ((double)best > threshold) ? idx : -1;
-	}
-	if (!fs.fsm) return;
-	__syncthreads();
-	if (t == 0)
-	{
-		edison_fsm mach = fs.fsm[m];
-		for (int i = 0; i < n; i++)
-		{
-			const size_t im = i * n_mics + m;
-			fs.states[im] = ed_fsm_step_core(&mach, spotted[im] >= 0, (uint32_t)likely[im], fs.dt_us, &fs.roles);
-		}
-		fs.fsm[m] = mach;
-		if (fs.copy) fs.copy[m] = mach;
-	}
-}
-
-void ed_stream_bank_launch_shift(hipStream_t q, int n_mics, int16_t *audio, int64_t a_stride, int64_t a_src, int tail, int8_t *feat, int64_t f_stride,
-                                 int64_t f_src, int feat_bytes)
-{
-	hipLaunchKernelGGL(ed_stream_bank_shift_kernel, dim3(n_mics), dim3(256), 0, q, audio, a_stride, a_src, tail, feat, f_stride, f_src, feat_bytes);
-}
-
-void ed_stream_bank_launch_filter(hipStream_t q, int n_mics, int out_elem, const void *x, int n, int n_out, double alpha, double one_minus_alpha,
-                                  double threshold, float *state, float *filt, int32_t *likely, int32_t *spotted, edsg_fsm_stage_t fs)
-{
-	if (out_elem == 1)
-		hipLaunchKernelGGL(ed_stream_bank_filter_kernel<int8_t>, dim3(n_mics), dim3(256), 0, q, (const int8_t *)x, n, n_out, alpha, one_minus_alpha,
-		                   threshold, state, filt, likely, spotted, fs);
-	else
-		hipLaunchKernelGGL(ed_stream_bank_filter_kernel<float>, dim3(n_mics), dim3(256), 0, q, (const float *)x, n, n_out, alpha, one_minus_alpha,
-		                   threshold, state, filt, likely, spotted, fs);
-}
 
 static ed_stream_core *core_of(edison_stream_bank *b) { return b ? &b->core : NULL; }
 

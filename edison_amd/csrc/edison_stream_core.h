@@ -15,10 +15,11 @@
  * edison_float_bank.hip, DESIGN.md sections 12b and 15a). Each microphone has the two buffers above, mic_audio samples and mic_feat bytes behind its neighbour's, and all
  * share one pos. A push carries [n_mics][n * hop] samples; everything it puts out is time-major: filt [n][n_mics][n_out], likely /
  * spotted / states [n][n_mics], the machines [n_mics]. With n_mics = 1 the core issues the copies and launches it issued before it had
- * the dimension; with more, one strided copy and the banked kernels of edison_stream_bank.hip (one workgroup per microphone).
+ * the dimension, with more one strided copy; the two state kernels (edison_stream_core.hip) run one workgroup per microphone either way.
  *
- * A push may leave microphones out (finish_push_present): pos advances for all of them, and the kernels of
- * edison_bank_hold.hip carry an absent microphone's history forward to the new pos and leave everything else it owns as it was.
+ * A push may leave microphones out (finish_push_present): pos advances for all of them, the hold kernel of
+ * edison_bank_hold.hip carries an absent microphone's history forward to the new pos, and the filter kernel, given the mask, leaves
+ * everything else the microphone owns as it was.
  */
 #ifndef EDISON_STREAM_CORE_H
 #define EDISON_STREAM_CORE_H
@@ -27,7 +28,7 @@
 #include <stdint.h>
 
 #include "edison_ctx.h"
-#include "edison_fsm_core.h"
+#include "edison_postproc_core.h"
 
 #define EDSG_FILTER_MAX_OUT 256                       /* classes the filter kernel serves: one lane each in one workgroup */
 #define ED_STREAM_CORE_SLOTS 8                        /* pushes of room in the sliding buffers ...                         */
@@ -76,24 +77,6 @@ struct ed_stream_core
 	unsigned char *h_present;      /* pinned [n_mics], the tail of h_in's allocation */
 };
 
-/* the state machine behind the filter kernels; fsm = NULL: none */
-struct edsg_fsm_stage_t
-{
-	edison_fsm *fsm;      /* [n_mics] device memory, read and written                    */
-	int32_t *states;      /* [n][n_mics] out: the state after each inference             */
-	edison_fsm *copy;     /* [n_mics] out: the machines after the push (the host's view) */
-	uint32_t dt_us;
-	ed_fsm_roles_t roles;
-};
-
-/* The kernels of a core with more than one microphone, one workgroup per microphone (edison_stream_bank.hip): the shift of every
- * microphone's history to the front of its buffers, a_stride samples and f_stride bytes apart, and the filter (+ edisonFSM) over the
- * time-major x [n][n_mics][n_out] (int8 for out_elem 1, float for 4) with state [n_mics][n_out]. Enqueued on q; a failed launch shows in hipGetLastError. */
-void ed_stream_bank_launch_shift(hipStream_t q, int n_mics, int16_t *audio, int64_t a_stride, int64_t a_src, int tail, int8_t *feat, int64_t f_stride,
-                                 int64_t f_src, int feat_bytes);
-void ed_stream_bank_launch_filter(hipStream_t q, int n_mics, int out_elem, const void *x, int n, int n_out, double alpha, double one_minus_alpha,
-                                  double threshold, float *state, float *filt, int32_t *likely, int32_t *spotted, edsg_fsm_stage_t fs);
-
 /* A push of n frames that left microphones out, after its feature and network launches (edison_bank_hold.hip; one workgroup per
  * microphone, a microphone with present[m] != 0 is not touched). The absent microphone's garbage went to samples a_src + tail and later
  * and to feature bytes f_src + feat_bytes and later, so its history at a_src / f_src is intact: the hold moves it UP by a_by samples and
@@ -114,11 +97,6 @@ struct ed_bank_hold_t
 	int64_t *missed;               /* [n_mics] */
 };
 void ed_bank_launch_hold(hipStream_t q, int n_mics, const ed_bank_hold_t *h);
-/* ed_stream_bank_launch_filter for such a push: a present microphone takes that kernel's path; an absent one gets zero bytes in its rows
- * of filt, -1 in likely and spotted, its machine's unchanged state in fs.states and fs.copy[m] = fs.fsm[m]; state[m] and fs.fsm[m] stay. */
-void ed_bank_launch_filter_present(hipStream_t q, int n_mics, const unsigned char *present, int out_elem, const void *x, int n, int n_out,
-                                   double alpha, double one_minus_alpha, double threshold, float *state, float *filt, int32_t *likely,
-                                   int32_t *spotted, edsg_fsm_stage_t fs);
 
 /* the options both public option structs carry */
 struct ed_stream_core_opts { int chunk_frames, filter, fsm; double filter_alpha, true_threshold; };
@@ -140,8 +118,10 @@ int ed_stream_core_begin_push(ed_stream_core *c, hipStream_t q, const int16_t *s
 int ed_stream_core_finish_push(ed_stream_core *c, hipStream_t q, const void *fin, int n, int host);
 /* finish_push for a push that carries a mask: present [n_mics], nonzero = this microphone's samples count (host = 1: host memory,
  * uploaded through h_present; host = 0: device memory, read on q). out0 / out1 [n][n_mics][n_out] of out_elem bytes and argmax
- * [n][n_mics] are where the owner's network wrote this push (NULL: nowhere). Runs the hold, then the masked filter at grid n_mics (also
- * for one microphone), then what finish_push does behind its filter. */
+ * [n][n_mics] are where the owner's network wrote this push (NULL: nowhere). Runs the hold, then finish_push's filter with the mask -- a
+ * present microphone as there; an absent one gets zero bytes in its rows of filt, -1 in likely and spotted, its machine's unchanged
+ * state in states and the unchanged machine in the copy, and keeps its filter state and its machine -- then what finish_push does
+ * behind its filter. */
 int ed_stream_core_finish_push_present(ed_stream_core *c, hipStream_t q, const void *fin, int n, int host, const unsigned char *present, void *out0,
                                        void *out1, int32_t *argmax);
 

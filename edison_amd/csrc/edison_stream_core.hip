@@ -1,20 +1,24 @@
 /*
  * edison_stream_core.hip -- the sliding-window core of the any-geometry streams (edison_stream_core.h): the two
- * state kernels, and the host logic around them that edison_stream_geom.hip and edison_stream_float.hip share. With more than one
- * microphone (edison_stream_bank.hip, section 12b) the same logic runs on strided buffers and calls that file's banked kernels.
+ * state kernels, one workgroup per microphone, and the host logic around them that edison_stream_geom.hip, edison_stream_float.hip and
+ * the two banks (edison_stream_bank.hip, edison_float_bank.hip; sections 12b, 15a) share. The microphone count and a push's mask are
+ * data of the launch: a single stream runs the same kernels at grid 1.
  */
 #include <math.h>
 #include <string.h>
 
 #include "edison_stream_core.h"
 
-/* The newest `tail` samples from audio + a_src and `feat_bytes` history bytes from feat + f_src to the front of their buffers. The
- * destination lies BELOW the source and may overlap it: in rounds of 256 elements every lane reads, the workgroup waits, every lane
- * writes. A write to element j clobbers source element j - src < j, which this round or an earlier one has already read. */
-__global__ __launch_bounds__(256) void ed_stream_geom_shift_kernel(int16_t *audio, int64_t a_src, int tail, int8_t *feat, int64_t f_src,
-                                                                   int feat_bytes)
+/* Workgroup m moves microphone m's history -- the newest `tail` samples from a_src and feat_bytes bytes from f_src -- to the front of its
+ * buffers, a_stride samples and f_stride bytes behind microphone m - 1's. The destination lies BELOW the source and may overlap it: in
+ * rounds of 256 elements every lane reads, the workgroup waits, every lane writes. A write to element j clobbers source element
+ * j - src < j, which this round or an earlier one has already read. */
+__global__ __launch_bounds__(256) void ed_stream_core_shift_kernel(int16_t *audio, int64_t a_stride, int64_t a_src, int tail, int8_t *feat,
+                                                                   int64_t f_stride, int64_t f_src, int feat_bytes)
 {
 	const int t = threadIdx.x;
+	audio += (int64_t)blockIdx.x * a_stride;
+	feat += (int64_t)blockIdx.x * f_stride;
 	for (int base = 0; base < tail; base += 256)
 	{
 		const int j = base + t;
@@ -34,54 +38,75 @@ __global__ __launch_bounds__(256) void ed_stream_geom_shift_kernel(int16_t *audi
 }
 
 /*
- * The firmware's post-processing (app.c:332-356) over n_out classes, for the n inferences of a push:
- *   state[c] = (float)(alpha * (double)state[c] + (1 - alpha) * (double)x[c])   product and sum rounded separately, no contraction
- *   likely = first maximum of the state row, spotted = likely if that maximum > threshold, else -1
- * The recurrence is sequential in time; classes run on lanes, the per-frame maximum afterwards on frames. One workgroup.
- * T = int8_t: the int8 graph's softmax / logits (edison_stream_geom.hip); T = float: the float network's probabilities
- * (edison_stream_float.hip). (double)x is exact for both.
+ * The firmware's post-processing (app.c:332-356) over n_out classes, for the n inferences of a push; workgroup m serves microphone m:
+ *   state[c] = ed_filter_step(alpha, state[c], ed_filter_term(1 - alpha, x[c]))   the arithmetic and its rounding: edison_postproc_core.h
+ *   likely = first maximum of the state row, spotted = likely if that maximum > threshold, else -1;   then edisonFSM on lane 0
+ * The recurrence is sequential in time; classes run on lanes, the per-frame maximum afterwards on frames. Entry i of microphone m is row
+ * i * n_mics + m of the time-major arrays x / filt [n][n_mics][n_out] and likely / spotted / fs.states [n][n_mics]; between pushes the
+ * microphone keeps state [n_mics][n_out] and fs.fsm [n_mics]. A single stream is the bank of one: m = 0, n_mics = gridDim.x = 1.
+ * T = int8_t: the int8 graph's softmax / logits; T = float: the float network's probabilities. (double)x is exact for both.
+ * present [n_mics] (NULL: everyone): a microphone the push left out gets the fill -- zero bytes in its rows of filt, -1 in likely and
+ * spotted, its machine's unchanged state in fs.states, the unchanged machine in fs.copy -- and keeps state[m] and fs.fsm[m].
  */
 template <class T>
-__global__ __launch_bounds__(256) void ed_stream_geom_filter_kernel(const T *x, int n, int n_out, double alpha, double one_minus_alpha,
-                                                                    double threshold, float *state, float *filt, int32_t *likely,
-                                                                    int32_t *spotted, edsg_fsm_stage_t fs)
+__global__ __launch_bounds__(256) void ed_stream_core_filter_kernel(const unsigned char *present, const T *x, int n, int n_out, double alpha,
+                                                                    double one_minus_alpha, double threshold, float *state, float *filt,
+                                                                    int32_t *likely, int32_t *spotted, ed_fsm_stage_t fs)
 {
 	const int t = threadIdx.x;
+	const size_t m = blockIdx.x, n_mics = gridDim.x;
+	if (present && !present[m])
+	{
+		/* the rows of filt: 256 / n_out rows a round, a lane per element, so that a row's stores are adjacent (n_out <= 256, one
+		 * 32-bit division per lane); the machine is read in place, not into a local copy */
+		const int per = 256 / n_out, r = t / n_out, c = t % n_out;
+		for (int i = r; i < n && r < per; i += per) filt[(i * n_mics + m) * n_out + c] = 0.0f;
+		const int held = fs.fsm ? fs.fsm[m].state : 0;
+		for (int i = t; i < n; i += 256)
+		{
+			const size_t im = i * n_mics + m;
+			likely[im] = -1;
+			spotted[im] = -1;
+			if (fs.fsm) fs.states[im] = held;
+		}
+		if (fs.fsm && fs.copy && t == 0) fs.copy[m] = fs.fsm[m];
+		return;
+	}
 	if (t < n_out)
 	{
-		float y = state[t];
+		float y = state[m * n_out + t];
 		for (int i = 0; i < n; i++)
 		{
-			/* as ed_stream_filter_kernel: the compiler's default contraction would fuse these into one v_fma_f64, a different double in
-			 * the last place (the Cortex-M4 rounds each operation) */
-#pragma clang fp contract(off)
-			const double a = alpha * (double)y;
-			const double b = one_minus_alpha * (double)x[(size_t)i * n_out + t];
-			y = (float)(a + b);
-			filt[(size_t)i * n_out + t] = y;
+			const size_t at = (i * n_mics + m) * n_out + t;
+			y = ed_filter_step(alpha, y, ed_filter_term(one_minus_alpha, (double)x[at]));
+			filt[at] = y;
 		}
-		state[t] = y;
+		state[m * n_out + t] = y;
 	}
 	__syncthreads();
 	for (int i = t; i < n; i += 256)
 	{
-		const float *row = filt + (size_t)i * n_out;
+		const size_t im = i * n_mics + m;
+		const float *row = filt + im * n_out;
 		float best = row[0];
 		int idx = 0;
 		for (int c = 1; c < n_out; c++)
 			if (best < row[c]) { best = row[c]; idx = c; }
-		likely[i] = idx;
-		spotted[i] = ((double)best > threshold) ? idx : -1;
+		likely[im] = idx;
+		spotted[im] = ((double)best > threshold) ? idx : -1;
 	}
 	if (!fs.fsm) return;
 	__syncthreads();
 	if (t == 0)
 	{
-		edison_fsm m = *fs.fsm;
+		edison_fsm mach = fs.fsm[m];
 		for (int i = 0; i < n; i++)
-			fs.states[i] = ed_fsm_step_core(&m, spotted[i] >= 0, (uint32_t)likely[i], fs.dt_us, &fs.roles);
-		*fs.fsm = m;
-		if (fs.copy) *fs.copy = m;
+		{
+			const size_t im = i * n_mics + m;
+			fs.states[im] = ed_fsm_step_core(&mach, spotted[im] >= 0, (uint32_t)likely[im], fs.dt_us, &fs.roles);
+		}
+		fs.fsm[m] = mach;
+		if (fs.copy) fs.copy[m] = mach;
 	}
 }
 
@@ -108,11 +133,8 @@ static int make_room(ed_stream_core *c, hipStream_t q, int n)
 	if (c->pos + n <= c->slots * c->chunk || c->pos == 0) return EDISON_OK;
 	const int64_t a_src = (int64_t)c->pos * c->hop, f_src = (int64_t)c->pos * c->nm * c->feat_elem;
 	const int feat_bytes = c->feat_elem * (c->F - 1) * c->nm;
-	if (c->n_mics == 1)
-		hipLaunchKernelGGL(ed_stream_geom_shift_kernel, dim3(1), dim3(256), 0, q, c->d_audio, a_src, c->tail, (int8_t *)c->d_feat, f_src, feat_bytes);
-	else
-		ed_stream_bank_launch_shift(q, c->n_mics, c->d_audio, (int64_t)c->mic_audio, a_src, c->tail, (int8_t *)c->d_feat, (int64_t)c->mic_feat, f_src,
-		                            feat_bytes);
+	hipLaunchKernelGGL(ed_stream_core_shift_kernel, dim3(c->n_mics), dim3(256), 0, q, c->d_audio, (int64_t)c->mic_audio, a_src, c->tail,
+	                   (int8_t *)c->d_feat, (int64_t)c->mic_feat, f_src, feat_bytes);
 	c->pos = 0;
 	return hipGetLastError() == hipSuccess ? EDISON_OK : core_err(c->ctx, c->who, EDISON_E_RUNTIME, "shift launch failed");
 }
@@ -266,17 +288,28 @@ int ed_stream_core_begin_push(ed_stream_core *c, hipStream_t q, const int16_t *s
 	return EDISON_OK;
 }
 
-/* the filter's state machine stage, writing into the output block; without opts.fsm: none */
-static edsg_fsm_stage_t fsm_stage(ed_stream_core *c)
+/* Where the stream has a filter: the filter (+ edisonFSM, writing into the output block) over fin [n][n_mics][n_out], a workgroup per
+ * microphone; present: the push's mask in device memory, NULL: every microphone. */
+static int launch_filter(ed_stream_core *c, hipStream_t q, const unsigned char *present, const void *fin, int n)
 {
-	edsg_fsm_stage_t fs;
+	if (!c->filter) return EDISON_OK;
+	unsigned char *o = c->d_out;
+	ed_fsm_stage_t fs;
 	memset(&fs, 0, sizeof(fs));
 	if (c->fsm)
 	{
-		fs.fsm = c->d_fsm; fs.states = (int32_t *)(c->d_out + c->off_states); fs.copy = (edison_fsm *)(c->d_out + c->off_fsm);
+		fs.fsm = c->d_fsm; fs.states = (int32_t *)(o + c->off_states); fs.copy = (edison_fsm *)(o + c->off_fsm);
 		fs.dt_us = c->dt_us; fs.roles = c->roles;
 	}
-	return fs;
+	float *filt = (float *)(o + c->off_filt);
+	int32_t *likely = (int32_t *)(o + c->off_likely), *spotted = (int32_t *)(o + c->off_spotted);
+	if (c->out_elem == 1)
+		hipLaunchKernelGGL(ed_stream_core_filter_kernel<int8_t>, dim3(c->n_mics), dim3(256), 0, q, present, (const int8_t *)fin, n, c->n_out, c->alpha,
+		                   c->one_minus_alpha, c->threshold, c->d_state, filt, likely, spotted, fs);
+	else
+		hipLaunchKernelGGL(ed_stream_core_filter_kernel<float>, dim3(c->n_mics), dim3(256), 0, q, present, (const float *)fin, n, c->n_out, c->alpha,
+		                   c->one_minus_alpha, c->threshold, c->d_state, filt, likely, spotted, fs);
+	return hipGetLastError() == hipSuccess ? EDISON_OK : core_err(c->ctx, c->who, EDISON_E_RUNTIME, "filter launch failed");
 }
 
 /* behind the filter of a push of n frames: pos, the host push's download and wait, what the getters need to know */
@@ -298,23 +331,7 @@ static int end_push(ed_stream_core *c, hipStream_t q, int n, int host)
 
 int ed_stream_core_finish_push(ed_stream_core *c, hipStream_t q, const void *fin, int n, int host)
 {
-	if (c->filter)
-	{
-		unsigned char *o = c->d_out;
-		const edsg_fsm_stage_t fs = fsm_stage(c);
-		float *filt = (float *)(o + c->off_filt);
-		int32_t *likely = (int32_t *)(o + c->off_likely), *spotted = (int32_t *)(o + c->off_spotted);
-		if (c->n_mics > 1)
-			ed_stream_bank_launch_filter(q, c->n_mics, c->out_elem, fin, n, c->n_out, c->alpha, c->one_minus_alpha, c->threshold, c->d_state, filt,
-			                             likely, spotted, fs);
-		else if (c->out_elem == 1)
-			hipLaunchKernelGGL(ed_stream_geom_filter_kernel<int8_t>, dim3(1), dim3(256), 0, q, (const int8_t *)fin, n, c->n_out, c->alpha,
-			                   c->one_minus_alpha, c->threshold, c->d_state, filt, likely, spotted, fs);
-		else
-			hipLaunchKernelGGL(ed_stream_geom_filter_kernel<float>, dim3(1), dim3(256), 0, q, (const float *)fin, n, c->n_out, c->alpha,
-			                   c->one_minus_alpha, c->threshold, c->d_state, filt, likely, spotted, fs);
-		if (hipGetLastError() != hipSuccess) return core_err(c->ctx, c->who, EDISON_E_RUNTIME, "filter launch failed");
-	}
+	{ const int r = launch_filter(c, q, NULL, fin, n); if (r != EDISON_OK) return r; }
 	return end_push(c, q, n, host);
 }
 
@@ -339,13 +356,7 @@ int ed_stream_core_finish_push_present(ed_stream_core *c, hipStream_t q, const v
 	h.missed = c->d_missed;
 	ed_bank_launch_hold(q, c->n_mics, &h);
 	if (hipGetLastError() != hipSuccess) return core_err(c->ctx, c->who, EDISON_E_RUNTIME, "hold launch failed");
-	if (c->filter)
-	{
-		unsigned char *o = c->d_out;
-		ed_bank_launch_filter_present(q, c->n_mics, present, c->out_elem, fin, n, c->n_out, c->alpha, c->one_minus_alpha, c->threshold, c->d_state,
-		                              (float *)(o + c->off_filt), (int32_t *)(o + c->off_likely), (int32_t *)(o + c->off_spotted), fsm_stage(c));
-		if (hipGetLastError() != hipSuccess) return core_err(c->ctx, c->who, EDISON_E_RUNTIME, "filter launch failed");
-	}
+	{ const int r = launch_filter(c, q, present, fin, n); if (r != EDISON_OK) return r; }
 	return end_push(c, q, n, host);
 }
 

@@ -21,8 +21,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_CU = 256                      # MI355X; the GPU tests pass the context's value
-MAX_MICS = 4096                 # ED_STREAM_BANK_MAX_MICS, edison_stream_bank.hip:23
-SLOTS, SLOTS_BYTES, SLACK = 8, 64 << 20, 64   # edison_stream_core.h:30-32
+MAX_MICS = 4096                 # ED_STREAM_BANK_MAX_MICS, edison_stream_bank.hip:27
+SLOTS, SLOTS_BYTES, SLACK = 8, 64 << 20, 64   # edison_stream_core.h:34-36
 EDG_BLOCK, WAVE_TEAM_BYTES = 256, 20480       # mfcc_geom_device.h, edison_kws_geom.hip:19
 EDM_G, EDM_WAVES = 4, 8                       # cnn_mfma_kernels.hip:71-72
 BASES = 7                       # base recordings of a row with more than 8 microphones: coprime to 4, 8 and 16
@@ -43,7 +43,7 @@ GEOMS = {
     "odd_ov": ("odd_no_softmax", dict(variant="B", frame_len=675, frame_step=64, n_samples=675 + 26 * 64, mel_nbins=16, first_mfcc=0, num_mfcc=7)),
     # frame_len = 31 x frame_step: with the shift at pos = 30 = F - 1 source and destination touch, samples and rows
     "shipped_touch": ("shipped", dict(_SHIPPED, frame_len=3100, frame_step=100, n_samples=3100 + 30 * 100)),
-    # one slot: chunk x frame_step > 4 Mi samples. No check bounds frame_step but chunk x frame_step < 2^30 (edison_stream_core.hip:124),
+    # one slot: chunk x frame_step > 4 Mi samples. No check bounds frame_step but chunk x frame_step < 2^30 (edison_stream_core.hip:146),
     # so the step is the largest that still leaves a history to shift (below the largest frame_len, 4096) and a multiple of 256
     "shipped_slot1": ("shipped", dict(_SHIPPED, frame_len=4096, frame_step=2048, n_samples=4096 + 30 * 2048)),
     # one frame per window (189 coefficients): no feature history at all
@@ -126,11 +126,11 @@ def frame_count(g):
 
 def create_check(row):
     """The create checks that need no device, restated: None, or the reason the bank refuses the row.
-    edison_kws_geom.hip:52-69 (ed_kws_geom_check), edison_stream_geom.hip:99-110, edison_stream_core.hip:122-128,
-    edison_stream_bank.hip:185-191."""
+    edison_kws_geom.hip:52-69 (ed_kws_geom_check), edison_stream_geom.hip:99-110, edison_stream_core.hip:144-150,
+    edison_stream_bank.hip:98-104."""
     g, f = GEOMS[row["geom"]][1], graph_facts(row["graph"])
     if not 1 <= row["n_mics"] <= MAX_MICS:
-        return "n_mics must be 1 .. 4096"                                        # edison_stream_bank.hip:185
+        return "n_mics must be 1 .. 4096"                                        # edison_stream_bank.hip:98
     if not 4 <= g["frame_len"] <= 4096:
         return "frame_len 4 .. 4096"                                             # edison_kws_geom.hip:56
     if not 1 <= g["mel_nbins"] <= 256:
@@ -145,43 +145,43 @@ def create_check(row):
     if F * g["num_mfcc"] != f["in_n"]:
         return "frame_count x num_mfcc is not the graph's input"                 # edison_stream_geom.hip:99
     if row["chunk"] < 1:
-        return "chunk_frames >= 1"                                               # edison_stream_core.hip:122
+        return "chunk_frames >= 1"                                               # edison_stream_core.hip:144
     if row["chunk"] * g["frame_step"] >= 1 << 30:
-        return "chunk_frames x frame_step below 2^30"                            # :124
+        return "chunk_frames x frame_step below 2^30"                            # :146
     if row["fsm"] and not row["filt"]:
-        return "fsm needs the filter"                                            # :126
+        return "fsm needs the filter"                                            # :148
     if row["filt"] and not 0.0 <= row["alpha"] <= 1.0:
-        return "alpha within [0, 1]"                                             # :127
+        return "alpha within [0, 1]"                                             # :149
     if row["filt"] and f["n_out"] > 256:
         return "at most 256 outputs"                                             # edison_stream_geom.hip:107
     if row["fsm"] and f["n_out"] != 10:
         return "the state machine needs 10 outputs"                              # :109
     if row["n_mics"] * row["chunk"] >= 1 << 31:
-        return "n_mics x chunk_frames below 2^31"                                # edison_stream_bank.hip:190
+        return "n_mics x chunk_frames below 2^31"                                # edison_stream_bank.hip:103
     return None
 
 
 # ---- the core's sizes ------------------------------------------------------------------------------------------------------------
 def sizes(row):
-    """slots from the 64 MB rule, then one microphone's buffers: edison_stream_core.hip:137, 150-154, edison_stream_core.h:37-41."""
+    """slots from the 64 MB rule, then one microphone's buffers: edison_stream_core.hip:159, 172-176, edison_stream_core.h:41-45."""
     g = GEOMS[row["geom"]][1]
     hop, chunk, nm = g["frame_step"], row["chunk"], g["num_mfcc"]
     F = frame_count(g)
-    tail = g["frame_len"] - hop if g["frame_len"] > hop else 0                   # edison_stream_core.hip:137
-    slots = SLOTS if chunk * hop * 2 * SLOTS <= SLOTS_BYTES else 1               # :151
+    tail = g["frame_len"] - hop if g["frame_len"] > hop else 0                   # edison_stream_core.hip:159
+    slots = SLOTS if chunk * hop * 2 * SLOTS <= SLOTS_BYTES else 1               # :173
     return dict(F=F, nm=nm, hop=hop, N=g["frame_len"], tail=tail, chunk=chunk, slots=slots, n_mics=row["n_mics"],
-                mic_audio=tail + slots * chunk * hop,                            # edison_stream_core.h:37
-                mic_feat=(F - 1 + slots * chunk) * nm,                           # :38-41, feat_elem = 1
-                feat_bytes=(F - 1) * nm)                                         # edison_stream_core.hip:110
+                mic_audio=tail + slots * chunk * hop,                            # edison_stream_core.h:41
+                mic_feat=(F - 1 + slots * chunk) * nm,                           # :42-45, feat_elem = 1
+                feat_bytes=(F - 1) * nm)                                         # edison_stream_core.hip:135
 
 
 def window_addr(s, pos, i, m):
-    """Byte offset in d_feat of window i of a push for microphone m: edison_stream_bank.hip:138, 150 (win + i * nm, stride mic_feat)."""
+    """Byte offset in d_feat of window i of a push for microphone m: edison_stream_bank.hip:50, 62 (win + i * nm, stride mic_feat)."""
     return m * s["mic_feat"] + (pos + i) * s["nm"]
 
 
 def out_index(i, m, n_mics):
-    """Row of the time-major outputs: slab i of the push, microphone m (edison_stream_bank.hip:147-151, :61 `i * n_mics + m`)."""
+    """Row of the time-major outputs: slab i of the push, microphone m (edison_stream_bank.hip:59-63; the filter: edison_stream_core.hip:80 `i * n_mics + m`)."""
     return i * n_mics + m
 
 
@@ -240,7 +240,7 @@ POISON = -1
 
 
 def shift_rounds(buf, src, count):
-    """The kernels' rounds of 256 (edison_stream_core.hip:18-33, edison_stream_bank.hip:41-56): all read, barrier, all write."""
+    """The kernels' rounds of 256 (edison_stream_core.hip:22-37, a workgroup per microphone): all read, barrier, all write."""
     for base in range(0, count, 256):
         hi = min(base + 256, count)
         v = buf[src + base:src + hi].copy()
@@ -285,7 +285,7 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True):
     shifted = False                              # the push before this one moved the history
     fast = row["route"] == "fast"
 
-    def start_state(m):                          # start_state, edison_stream_core.hip:194-219, at the current pos
+    def start_state(m):                          # start_state, edison_stream_core.hip:220-245, at the current pos
         epoch[m] += 1
         start[m] = seen
         audio[m * A + pos * hop:m * A + pos * hop + tail] = _tok(m, epoch[m], 0, 0) + np.arange(tail)
@@ -318,7 +318,7 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True):
     for p, n in enumerate(row["sched"]):
         for who in resets.get(p, ()):
             will_shift = not (pos + n <= s["slots"] * s["chunk"] or pos == 0)
-            if who == "all":                     # ed_stream_core_reset, :232-247: pos = 0, every microphone, frames_seen = 0
+            if who == "all":                     # ed_stream_core_reset, :258-274: pos = 0, every microphone, frames_seen = 0
                 pos = seen = 0
                 for m in range(M):
                     start_state(m)
@@ -330,8 +330,8 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True):
                 if M % 4 and who >= M - M % 4:
                     items.add(("reset_mic", "in a ragged last group"))
                 items.add(("reset_mic", "right before a shift" if will_shift else "right after a shift" if shifted else "elsewhere"))
-        assert 1 <= n <= s["chunk"]              # begin_push, :251
-        # make_room, edison_stream_core.hip:106-118
+        assert 1 <= n <= s["chunk"]              # begin_push, :278
+        # make_room, edison_stream_core.hip:131-140
         if not (pos + n <= s["slots"] * s["chunk"] or pos == 0):
             a_src, f_src = pos * hop, pos * nm
             for what, src, count in (("samples", a_src, tail), ("rows", f_src, s["feat_bytes"])):
@@ -346,12 +346,12 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True):
             shifted = True
         else:
             shifted = False
-        # the upload: d_audio + pos * hop + tail of every microphone, :256-260
+        # the upload: d_audio + pos * hop + tail of every microphone, :281-287
         for m in range(M):
             at = m * A + pos * hop + tail
             assert at + n * hop <= (m + 1) * A
             audio[at:at + n * hop] = _tok(m, epoch[m], 0, tail + (seen - start[m]) * hop) + np.arange(n * hop)
-        # ONE MFCC launch over n_mics * n frames: edison_stream_bank.hip:139-146, mfcc_geom_frames.inc:19-22, mfcc_geom_kernels.hip:29-33
+        # ONE MFCC launch over n_mics * n frames: edison_stream_bank.hip:51-58, mfcc_geom_frames.inc:19-22, mfcc_geom_kernels.hip:29-33
         ml = mfcc_launch(g, M * n, n_cu)
         items |= {("mfcc", "team", ml["team"]), ("mfcc", "wraps" if ml["wraps"] else "one pass"), ("mfcc", "frames_per_utt", "1" if n == 1 else "chunk" if n == s["chunk"] else "ragged")}
         feat_skip = FB - n * nm
@@ -366,7 +366,7 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True):
             o = pos * nm + (F - 1) * nm + gi * nm + feat_skip * u
             assert u * FB <= o and o + nm <= (u + 1) * FB, "row outside its microphone's rows"
             feat[o:o + nm] = _tok(u, epoch[u], 1, (F - 1 + seen - start[u] + f) * nm) + np.arange(nm)
-        # n network launches over the n_mics windows of a frame: edison_stream_bank.hip:147-153
+        # n network launches over the n_mics windows of a frame: edison_stream_bank.hip:59-65
         stride = FB + (nm if variant == "window_stride" else 0)
         full = pos + n == s["slots"] * s["chunk"]
         for i in range(n):
@@ -389,7 +389,7 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True):
                     want = _tok(m, epoch[m], 1, (seen - start[m] + i) * nm) + np.arange(F * nm)
                     if not np.array_equal(feat[at:at + F * nm], want):
                         problems.append(("window", p, m, i))
-        # the banked filter (+ machine): edison_stream_bank.hip:63-109, over slab-major entries
+        # the filter (+ machine), a workgroup per microphone: edison_stream_core.hip:52-111, over slab-major entries
         items.add(("filter", "n", "1" if n == 1 else ">256" if n > 256 else "ragged" if n < s["chunk"] else "chunk"))
         if n > 1 and M > 1:
             assert n != M
@@ -398,7 +398,7 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True):
                 for m in range(M):
                     entry[out_index(i, m, M)] = m * (1 << 32) + seen + i
             for m in range(M):
-                # state[m * n_out + t] and fs.fsm[m], :71, :100
+                # state[m * n_out + t] and fs.fsm[m], :77, :102
                 if owner[0 if variant == "shared_state" else m] != m or owner[0 if variant == "one_machine" else m] != m:
                     problems.append(("state", p, m))
                 for i in range(n):
@@ -437,11 +437,11 @@ def full_set():
 # item -> the host check or launch rule that keeps every accepted bank from it
 EXCLUDED = {
     ("general", "blocks above the cap"): "cnn_net_mfma_kernels.hip:1371 caps the grid at n_cu x per_cu workgroups of batch x waves inputs; the smallest "
-                                         "batch x waves of a fixture graph is 22 (square), so with 256 CUs the cap is 5632 inputs and edison_stream_bank.hip:185 "
+                                         "batch x waves of a fixture graph is 22 (square), so with 256 CUs the cap is 5632 inputs and edison_stream_bank.hip:98 "
                                          "admits 4096 (general_cap() recomputes it for the CU count at hand)",
-    ("n_mics", ">4096"): "edison_stream_bank.hip:185 refuses n_mics outside 1 .. 4096 (tests/test_gpu_stream_bank.py::test_errors runs it)",
-    ("n_mics x chunk", ">=2^31"): "edison_stream_bank.hip:190 refuses it, and no allocation reaches it: 2^31 frames of at least one sample each are 4 GB of "
-                                  "samples per push, which edison_stream_core.hip:124 (chunk x frame_step < 2^30) and HBM rule out for 4096 microphones",
+    ("n_mics", ">4096"): "edison_stream_bank.hip:98 refuses n_mics outside 1 .. 4096 (tests/test_gpu_stream_bank.py::test_errors runs it)",
+    ("n_mics x chunk", ">=2^31"): "edison_stream_bank.hip:103 refuses it, and no allocation reaches it: 2^31 frames of at least one sample each are 4 GB of "
+                                  "samples per push, which edison_stream_core.hip:146 (chunk x frame_step < 2^30) and HBM rule out for 4096 microphones",
 }
 
 

@@ -1,5 +1,5 @@
 """CPU tests (no GPU) of bank pushes that leave microphones out: the C-ABI declares and the binding exposes the six entry points, the
-library builds and exports them, the new source cross-compiles for gfx950 without warnings and its kernels use no scratch, the calls that
+library builds and exports them, the hold's source cross-compiles for gfx950 without warnings and its kernel uses no scratch, the calls that
 need no device answer as the header says, and the hold kernel's rounds -- restated in numpy -- equal a memmove on rows whose source and
 destination overlap and on rows where they do not, where ascending rounds go wrong on exactly the former."""
 import ctypes
@@ -52,29 +52,31 @@ def _compile(tmp_path, extra):
 
 
 def test_the_source_is_built_without_warnings(tmp_path):
-    """build.HIP_SOURCES lists the new file; it holds the two kernels (the hold, and the masked filter with its own no-contraction
-    pragma) and their launchers, and cross-compiles for gfx950 with -Wall -Wextra."""
+    """build.HIP_SOURCES lists the file; it holds one kernel, the hold, and its launcher -- the masked filter is the core's filter kernel
+    given the mask, so no filter arithmetic and no pragma here -- and cross-compiles for gfx950 with -Wall -Wextra."""
     from edison_amd import build
     assert SOURCE in build.HIP_SOURCES and os.path.exists(os.path.join(build.CSRC, SOURCE))
     err = _compile(tmp_path, ["-Wall", "-Wextra", "-Wno-unused-parameter", "-fPIC", "-c"])
     assert not [ln for ln in err.splitlines() if "warning:" in ln and "argument unused" not in ln], err[-2000:]
     text = open(os.path.join(build.CSRC, SOURCE)).read()
-    assert text.count("__global__") == 2 and text.count("#pragma clang fp contract(off)") == 1
-    assert "void ed_bank_launch_hold(" in text and "void ed_bank_launch_filter_present(" in text
+    assert text.count("__global__") == 1 and "#pragma clang fp contract" not in text
+    assert "void ed_bank_launch_hold(" in text
+    texts = [open(os.path.join(build.CSRC, f)).read() for f in sorted(os.listdir(build.CSRC)) if f.endswith((".hip", ".h", ".c", ".inc"))]
+    assert not any("ed_bank_launch_filter_present" in x for x in texts)
     core = open(os.path.join(build.CSRC, "edison_stream_core.hip")).read()
-    masked = core[core.index("int ed_stream_core_finish_push_present("):]
-    assert "ed_bank_launch_hold(" in masked and "ed_bank_launch_filter_present(" in masked
+    masked = core[core.index("int ed_stream_core_finish_push_present("):core.index("int ed_stream_core_frames_seen_mics(")]
+    # the hold, then the shared filter launch with the mask
+    assert 0 < masked.index("ed_bank_launch_hold(") < masked.index("launch_filter(c, q, present, fin, n)")
 
 
-def test_both_kernels_use_no_scratch(tmp_path):
+def test_the_hold_kernel_uses_no_scratch(tmp_path):
+    """The masked filter's scratch: test_float_bank_cpu.py::test_both_banked_filters_use_no_scratch, on the core's kernels."""
     err = _compile(tmp_path, ["--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage"])
     seen = {}
     for b in re.split(r"remark: Function Name: ", err)[1:]:
         seen[b.split()[0]] = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))
-    filt = sorted(k for k in seen if "ed_bank_filter_present_kernel" in k)
-    assert len(filt) == 2 and [k.split("ed_bank_filter_present_kernel")[1][:2] for k in filt] == ["Ia", "If"], seen   # int8 and float inputs
     assert len([k for k in seen if "ed_bank_hold_kernel" in k]) == 1
-    assert len(seen) == 3 and all(v == 0 for v in seen.values()), seen
+    assert len(seen) == 1 and all(v == 0 for v in seen.values()), seen
 
 
 def test_calls_that_need_no_device(built_lib):

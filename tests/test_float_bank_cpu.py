@@ -79,9 +79,11 @@ def test_the_window_kernel_uses_no_scratch_and_keeps_subnormals(tmp_path):
 
 
 def test_both_banked_filters_use_no_scratch(tmp_path):
-    seen = _scratch(_compile(tmp_path, "edison_stream_bank.hip", ["--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage"]))
-    filt = sorted(k for k in seen if "ed_stream_bank_filter_kernel" in k)
-    assert len(filt) == 2 and filt[0].split("ed_stream_bank_filter_kernel")[1][:2] == "Ia" and filt[1].split("ed_stream_bank_filter_kernel")[1][:2] == "If", seen
+    """The core's kernels, which serve every stream and bank, masked pushes included: the shift and the filter's int8 and float instances."""
+    seen = _scratch(_compile(tmp_path, "edison_stream_core.hip", ["--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage"]))
+    filt = sorted(k for k in seen if "ed_stream_core_filter_kernel" in k)
+    assert len(filt) == 2 and filt[0].split("ed_stream_core_filter_kernel")[1][:2] == "Ia" and filt[1].split("ed_stream_core_filter_kernel")[1][:2] == "If", seen
+    assert len([k for k in seen if "ed_stream_core_shift_kernel" in k]) == 1
     assert len(seen) == 3 and all(v == 0 for v in seen.values()), seen
 
 

@@ -411,7 +411,7 @@ def test_reset_mic_of_an_absent_and_of_a_present_microphone(built_lib, kind, nam
 
 @pytest.mark.parametrize("kind,name", [("int8", "long"), ("float", "long"), ("float", "shipped_q15")])
 def test_a_bank_of_one_microphone_with_a_mask(built_lib, kind, name):
-    """n_mics 1: the mask-less push takes the single stream's kernels, the masked one the banked kernels at grid 1."""
+    """n_mics 1: the mask-less push and the masked one run the core's kernels at grid 1, the filter with a NULL mask and with the mask."""
     K = _Kind(kind, name)
     c, g = K.open()
     try:

@@ -97,19 +97,32 @@ def test_one_frame_body_for_the_third_instance():
         assert "__global__" not in text and "hipLaunchKernelGGL" not in text
         assert "ed_stream_core_begin_push(" in text and "ed_stream_core_finish_push(" in text
     core = open(os.path.join(B.CSRC, "edison_stream_core.hip")).read()
-    assert core.count("__global__") == 2 and core.count("#pragma clang fp contract(off)") == 1
-    assert core.count("void ed_stream_geom_shift_kernel(") == 1 and core.count("void ed_stream_geom_filter_kernel(") == 1
-    assert "ed_stream_geom_filter_kernel<int8_t>" in core and "ed_stream_geom_filter_kernel<float>" in core
-    # the shift is launched in one place, make_room, which begin_push calls; the filter in one place, finish_push
-    assert core.count("hipLaunchKernelGGL(ed_stream_geom_shift_kernel") == 1 and core.count("hipLaunchKernelGGL(ed_stream_geom_filter_kernel<") == 2
-    begin = core[core.index("int ed_stream_core_begin_push("):core.index("int ed_stream_core_finish_push(")]
+    assert core.count("__global__") == 2
+    # the filter's arithmetic and its one no-contraction pragma live in the shared header, not here
+    assert core.count("#pragma clang fp contract(off)") == 0
+    assert open(os.path.join(B.CSRC, "edison_postproc_core.h")).read().count("#pragma clang fp contract(off)") == 1
+    assert core.count("void ed_stream_core_shift_kernel(") == 1 and core.count("void ed_stream_core_filter_kernel(") == 1
+    assert "ed_stream_core_filter_kernel<int8_t>" in core and "ed_stream_core_filter_kernel<float>" in core
+    # the shift is launched in one place, make_room, which begin_push calls; the filter in one place, launch_filter, which both finish
+    # functions call
+    assert core.count("hipLaunchKernelGGL(ed_stream_core_shift_kernel") == 1 and core.count("hipLaunchKernelGGL(ed_stream_core_filter_kernel<") == 2
+    assert core.count("hipLaunchKernelGGL(") == 3
+    room = core[core.index("static int make_room("):core.index("int ed_stream_core_check_opts(")]
+    assert "hipLaunchKernelGGL(ed_stream_core_shift_kernel" in room
+    begin = core[core.index("int ed_stream_core_begin_push("):core.index("static int launch_filter(")]
     assert "make_room(c, q, n)" in begin
-    assert "hipLaunchKernelGGL(ed_stream_geom_filter_kernel<" in core[core.index("int ed_stream_core_finish_push("):]
+    helper = core[core.index("static int launch_filter("):core.index("static int end_push(")]
+    assert helper.count("hipLaunchKernelGGL(ed_stream_core_filter_kernel<") == 2
+    plain = core[core.index("int ed_stream_core_finish_push("):core.index("int ed_stream_core_finish_push_present(")]
+    masked = core[core.index("int ed_stream_core_finish_push_present("):core.index("int ed_stream_core_frames_seen_mics(")]
+    assert "launch_filter(c, q, NULL, fin, n)" in plain and "launch_filter(c, q, present, fin, n)" in masked
     # nothing the core provides is defined a second time anywhere in the library's sources
     texts = [open(os.path.join(B.CSRC, f)).read() for f in sorted(os.listdir(B.CSRC)) if f.endswith((".hip", ".h", ".c", ".inc"))]
     for fn in ("order_after", "make_room", "copy_out", "ed_stream_core_filtered", "ed_stream_core_fsm", "ed_stream_core_reset",
-               "ed_stream_core_free"):
+               "ed_stream_core_free", "launch_filter"):
         assert sum(len(re.findall(r"^(?:static )?(?:int|void) %s\(.*\)\n\{" % fn, x, re.M)) for x in texts) == 1, fn
+    for kernel in ("ed_stream_core_shift_kernel", "ed_stream_core_filter_kernel"):
+        assert sum(len(re.findall(r"\bvoid %s\(" % kernel, x)) for x in texts) == 1, kernel
 
 
 def _float_rows(oracle_mod, g, z, starts):
