@@ -13,7 +13,9 @@ What a push does on the host side is restated here with the source line of each 
 A row is a dict: graph, geom (a name of GEOMS), n_mics, chunk, sched (frames per push), push (dev / host / alt: full pushes from the
 host and from the device in turn, ragged ones from the device), alpha, thr (a number or "tie": the reference's own filtered maximum of
 one inference), fsm, route (fast / general / spec / lbl), outputs (all / no_softmax / no_logits / none), resets ((push index, microphone
-or "all"): done before that push), ref (streams: one GeomStream per base recording; independent: no sliding buffer at all)."""
+or "all"): done before that push), present (None, or per push None or who the push leaves out: first / last / inner / all / third --
+microphone m of push p with (m + p) % 3 == 0 -- or a tuple of microphones; edison_bank_hold.hip and the mask of the filter kernel),
+ref (streams: one GeomStream per base recording; independent: no sliding buffer at all)."""
 import functools
 import os
 
@@ -58,10 +60,12 @@ ROWS = {}
 
 
 def _row(name, geom, n_mics, chunk=1, sched=None, push="dev", alpha=0.9, thr=0.5, fsm=False, route=None, outputs="all", resets=(),
-         ref="streams"):
+         ref="streams", present=None):
     graph = GEOMS[geom][0]
     ROWS[name] = dict(graph=graph, geom=geom, n_mics=n_mics, chunk=chunk, sched=list(sched or [1] * 10), push=push, filt=True, alpha=alpha, thr=thr,
-                      fsm=fsm, route=route or ("fast" if graph == "shipped" else "general"), outputs=outputs, resets=tuple(resets), ref=ref)
+                      fsm=fsm, route=route or ("fast" if graph == "shipped" else "general"), outputs=outputs, resets=tuple(resets), ref=ref,
+                      present=None if present is None else tuple(present))
+    assert present is None or len(present) == len(ROWS[name]["sched"])
 
 
 # ---- the fast kernel: groups of four microphones per wavefront, eight wavefronts per workgroup
@@ -91,6 +95,15 @@ _row("filt_257", "even_same", 3, chunk=257, sched=[257, 1, 257], alpha=0.6, thr=
 _row("same_stride_5", "same_stride", 5, chunk=3, sched=[3, 3, 2, 3, 3, 1, 3, 3, 3, 3], alpha=0.5)
 _row("odd_f1", "odd_f1", 3)
 _row("square_f4", "square_f4", 3)
+# ---- pushes that leave microphones out: the hold kernel's rounds from the top down and the filter kernel's fill
+# 16 rows of 20 int8 coefficients: 300 history bytes, a push of n frames holds them up by 20 n -- overlapping below 15 frames, touching
+# at 15, disjoint from 16; 19 outputs: from 14 frames on the rows to zero pass 256 bytes and the fill 256 / 19 = 13 rows a round
+_row("mask_even", "even_same", 5, chunk=16, sched=[7, 15, 16, 14, 2, 16, 16, 16, 16, 16], push="alt", alpha=0.6, ref="independent",
+     resets=[(5, 1)], present=["first", "last", "inner", "all", None, (1, 3), "first", None, "last", "inner"])
+_row("mask_257", "even_same", 3, chunk=257, sched=[257, 257], alpha=0.6, ref="independent", present=["inner", "first"])
+# 3000 history samples, 100 a frame: held up over themselves by 7 frames, touching by 30 (as the 30 rows of history)
+_row("mask_touch", "shipped_touch", 3, chunk=30, sched=[7, 30, 30], fsm=True, ref="independent", present=["first", "last", "inner"])
+_row("mask_4096", "shipped", 4096, sched=[1] * 9, fsm=True, ref="independent", present=["third"] * 9)
 
 
 # ---- the graphs ------------------------------------------------------------------------------------------------------------------
@@ -111,11 +124,11 @@ def graph_facts(graph):
                 mm_lds=p.M.lds_bytes)
 
 
-def geometry(name):
-    """The KwsGeometry of GEOMS[name]."""
+def geometry(name, geoms=None):
+    """The KwsGeometry of GEOMS[name] (geoms: another table of the same form)."""
     from edison_amd import _lib
     from edison_amd.kws.geometry import KwsGeometry
-    kw = dict(GEOMS[name][1])
+    kw = dict((geoms or GEOMS)[name][1])
     kw["variant"] = _lib.MFCC_A if kw["variant"] == "A" else _lib.MFCC_B
     return KwsGeometry.from_config(**kw)
 
@@ -131,6 +144,24 @@ def create_check(row):
     g, f = GEOMS[row["geom"]][1], graph_facts(row["graph"])
     if not 1 <= row["n_mics"] <= MAX_MICS:
         return "n_mics must be 1 .. 4096"                                        # edison_stream_bank.hip:98
+    if geom_check(g):
+        return geom_check(g)
+    F = frame_count(g)
+    if F * g["num_mfcc"] != f["in_n"]:
+        return "frame_count x num_mfcc is not the graph's input"                 # edison_stream_geom.hip:99
+    if core_check(row, g):
+        return core_check(row, g)
+    if row["filt"] and f["n_out"] > 256:
+        return "at most 256 outputs"                                             # edison_stream_geom.hip:107
+    if row["fsm"] and f["n_out"] != 10:
+        return "the state machine needs 10 outputs"                              # :109
+    if row["n_mics"] * row["chunk"] >= 1 << 31:
+        return "n_mics x chunk_frames below 2^31"                                # edison_stream_bank.hip:103
+    return None
+
+
+def geom_check(g):
+    """ed_kws_geom_check, edison_kws_geom.hip:52-69."""
     if not 4 <= g["frame_len"] <= 4096:
         return "frame_len 4 .. 4096"                                             # edison_kws_geom.hip:56
     if not 1 <= g["mel_nbins"] <= 256:
@@ -142,8 +173,11 @@ def create_check(row):
         return "frames do not fit in n_samples"                                  # :62
     if g["first_mfcc"] < 0 or g["num_mfcc"] < 1 or g["first_mfcc"] + g["num_mfcc"] > g["mel_nbins"]:
         return "first_mfcc + num_mfcc <= mel_nbins"                              # :64
-    if F * g["num_mfcc"] != f["in_n"]:
-        return "frame_count x num_mfcc is not the graph's input"                 # edison_stream_geom.hip:99
+    return None
+
+
+def core_check(row, g):
+    """ed_stream_core_check_opts, edison_stream_core.hip:144-150."""
     if row["chunk"] < 1:
         return "chunk_frames >= 1"                                               # edison_stream_core.hip:144
     if row["chunk"] * g["frame_step"] >= 1 << 30:
@@ -152,27 +186,22 @@ def create_check(row):
         return "fsm needs the filter"                                            # :148
     if row["filt"] and not 0.0 <= row["alpha"] <= 1.0:
         return "alpha within [0, 1]"                                             # :149
-    if row["filt"] and f["n_out"] > 256:
-        return "at most 256 outputs"                                             # edison_stream_geom.hip:107
-    if row["fsm"] and f["n_out"] != 10:
-        return "the state machine needs 10 outputs"                              # :109
-    if row["n_mics"] * row["chunk"] >= 1 << 31:
-        return "n_mics x chunk_frames below 2^31"                                # edison_stream_bank.hip:103
     return None
 
 
 # ---- the core's sizes ------------------------------------------------------------------------------------------------------------
-def sizes(row):
-    """slots from the 64 MB rule, then one microphone's buffers: edison_stream_core.hip:159, 172-176, edison_stream_core.h:41-45."""
-    g = GEOMS[row["geom"]][1]
+def sizes(row, feat_elem=1, geoms=None):
+    """slots from the 64 MB rule, then one microphone's buffers: edison_stream_core.hip:159, 172-176, edison_stream_core.h:41-45.
+    feat_elem: bytes per feature element, 1 for the int8 graph, 4 for the float network (geoms: its table of geometries)."""
+    g = (geoms or GEOMS)[row["geom"]][1]
     hop, chunk, nm = g["frame_step"], row["chunk"], g["num_mfcc"]
     F = frame_count(g)
     tail = g["frame_len"] - hop if g["frame_len"] > hop else 0                   # edison_stream_core.hip:159
     slots = SLOTS if chunk * hop * 2 * SLOTS <= SLOTS_BYTES else 1               # :173
     return dict(F=F, nm=nm, hop=hop, N=g["frame_len"], tail=tail, chunk=chunk, slots=slots, n_mics=row["n_mics"],
                 mic_audio=tail + slots * chunk * hop,                            # edison_stream_core.h:41
-                mic_feat=(F - 1 + slots * chunk) * nm,                           # :42-45, feat_elem = 1
-                feat_bytes=(F - 1) * nm)                                         # edison_stream_core.hip:135
+                mic_feat=feat_elem * (F - 1 + slots * chunk) * nm,               # :42-45, in bytes
+                feat_bytes=feat_elem * (F - 1) * nm)                             # edison_stream_core.hip:135
 
 
 def window_addr(s, pos, i, m):
@@ -236,7 +265,7 @@ def _band(v):
 
 
 # ---- the emulator ------------------------------------------------------------------------------------------------------------------
-POISON = -1
+POISON, GARBAGE = -1, -2        # never written; the samples and rows of a microphone the push left out
 
 
 def shift_rounds(buf, src, count):
@@ -263,22 +292,102 @@ def shift_forward64(buf, src, count):
         buf[base:hi] = buf[src + base:src + hi].copy()
 
 
+def hold_rounds(buf, src, count, by):
+    """hold_up, edison_bank_hold.hip:20-30: `count` elements from src up by `by`, rounds of 256 from the top down, all read, barrier, all write."""
+    for top in range(count, 0, -256):
+        lo = max(0, top - 256)
+        v = buf[src + lo:src + top].copy()
+        buf[src + by + lo:src + by + top] = v
+
+
+def hold_ascending(buf, src, count, by):
+    """The same rounds from the bottom up, as the shift kernel runs its own: WRONG when the destination overlaps the source, for a
+    round's writes land on elements a later round has yet to read."""
+    for base in range(0, count, 256):
+        hi = min(base + 256, count)
+        v = buf[src + base:src + hi].copy()
+        buf[src + by + base:src + by + hi] = v
+
+
+def absent_of(row, p):
+    """The microphones push p of the row leaves out (sorted list; empty: the push carries no mask or an all-ones one)."""
+    pat, M = (row.get("present") or [None] * len(row["sched"]))[p], row["n_mics"]
+    if pat is None:
+        return []
+    if isinstance(pat, tuple):
+        return sorted(pat)
+    return {"first": [0], "last": [M - 1], "inner": [M // 2], "all": list(range(M)), "third": [m for m in range(M) if (m + p) % 3 == 0]}[pat]
+
+
+def fill_rows(n, n_out):
+    """The rows of filt the absent fill writes for one microphone, by the kernel's loop (edison_stream_core.hip:62-63): lane t serves
+    element t % n_out of rows t / n_out, + per, ... while t / n_out < per = 256 / n_out. Returns the [n][n_out] mask of written elements."""
+    done = np.zeros((n, n_out), bool)
+    per = 256 // n_out
+    for t in range(256):
+        r, c = divmod(t, n_out)
+        if r < per:
+            done[r:n:per, c] = True
+    return done
+
+
+def hold_and_fill(s, n_out, row_bytes, feat_elem, a_of, f_of, pos, n, absent, items, problems, p, hold, variant, shifted, reset_now):
+    """What a masked push does behind its launches, for both banks (ed_stream_core_finish_push_present, edison_stream_core.hip:338-361):
+    the hold of every absent microphone's history up by the push's advance, then the filter kernel's fill. Adds the items reached and
+    the problems: a row of the fill not written, or written for a present microphone. a_of(m) / f_of(m): microphone m's samples and
+    feature bytes (None: a microphone the walk does not keep)."""
+    M, A, FB, tail, hop, nm = s["n_mics"], s["mic_audio"], s["mic_feat"], s["tail"], s["hop"], s["nm"]
+    a_src, a_by, f_src, f_by = pos * hop, n * hop, pos * nm * feat_elem, n * nm * feat_elem         # :351-353
+    for what, count, by in (("samples", tail, a_by), ("rows", s["feat_bytes"], f_by)):
+        if count and absent:
+            items.add(("hold", what, "overlapping" if by < count else "touching" if by == count else "disjoint"))
+    for m in absent:
+        assert a_src + a_by + tail <= A and f_src + f_by + s["feat_bytes"] <= FB, "the hold leaves the microphone's buffers"
+        if a_of(m) is not None:
+            hold(a_of(m), a_src, tail, a_by)
+            hold(f_of(m), f_src, s["feat_bytes"], f_by)
+    if absent:
+        items.add(("hold zero", "<=256 bytes" if n * row_bytes <= 256 else ">256 bytes"))          # edison_bank_hold.hip:42
+        items.add(("fill", "n > 256" if n > 256 else "one round" if n <= 256 // n_out else "several rounds"))
+        if M == MAX_MICS:
+            items.add(("hold grid", "4096"))                                                         # edison_bank_hold.hip:55
+        for m in absent:
+            items.add(("absent", "first" if m == 0 else "last" if m == M - 1 else "inner"))
+        if len(absent) == M:
+            items.add(("absent", "everyone"))
+        if shifted:
+            items.add(("absent", "through a shift"))
+        if reset_now & set(absent):
+            items.add(("absent", "reset while absent"))
+        full = fill_rows(n, n_out)
+        assert all(i in range(n) for i in range(0, n, 256))                                          # :65-71 i = t, t + 256, ...
+        filled = set(absent) if variant != "fill_present" else set(range(M)) - set(absent)
+        for m in (range(M) if M <= 64 else sorted(set(absent[:2] + absent[-2:] + [0, 1, M - 2, M - 1]))):
+            if (m in filled) != (m in absent) or (m in absent and not full.all()):
+                problems.append(("fill", p, m))
+
+
+MASKED_ROW_ITEMS = ("hold", "hold zero", "hold grid", "fill", "absent", "masked filter", "shift", "overlap", "reset", "reset_mic", "residue")
+
+
 def _tok(m, epoch, kind, j):
     """An opaque value for element j of microphone m's zero-led stream since its reset number `epoch`: kind 0 a sample, 1 a feature."""
     return (((m * 64 + epoch) * 2 + kind) << 32) + j
 
 
-def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True):
+def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True, hold=hold_rounds):
     """Walks the row's push schedule through the core with numpy buffers of tokens. Returns (items, problems): the coverage items the
     walk reached, and what a consumer would have read wrong (empty for the real rules). `variant` swaps one rule for a mis-reading:
-    mic_major, shared_state, one_machine, window_stride. Reads outside a microphone's buffers plus the slack raise."""
+    mic_major, shared_state, one_machine, window_stride, fill_present (the fill written to the present microphones). A microphone's tokens
+    count the frames of its own stream -- those of the pushes it was present in -- so a push it was absent from must leave no trace. Reads
+    outside a microphone's buffers plus the slack raise."""
     s = sizes(row)
     g = GEOMS[row["geom"]][1]
     F, nm, hop, N, tail, M = s["F"], s["nm"], s["hop"], s["N"], s["tail"], s["n_mics"]
     A, FB = s["mic_audio"], s["mic_feat"]
     audio = np.full(M * A + SLACK // 2, POISON, np.int64)
     feat = np.full(M * FB + SLACK, POISON, np.int64)
-    epoch, start = [0] * M, [0] * M              # per microphone: resets so far, the frame it last started at
+    epoch, cnt = [0] * M, [0] * M                # per microphone: resets so far, frames of its own stream since the last one
     seen, pos = 0, 0
     items, problems = set(), []
     owner = np.arange(M)                         # whose filter state / machine entry m of d_state / d_fsm is
@@ -287,7 +396,7 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True):
 
     def start_state(m):                          # start_state, edison_stream_core.hip:220-245, at the current pos
         epoch[m] += 1
-        start[m] = seen
+        cnt[m] = 0
         audio[m * A + pos * hop:m * A + pos * hop + tail] = _tok(m, epoch[m], 0, 0) + np.arange(tail)
         feat[m * FB + pos * nm:m * FB + pos * nm + (F - 1) * nm] = _tok(m, epoch[m], 1, 0) + np.arange((F - 1) * nm)
 
@@ -316,6 +425,8 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True):
         items.add(("lbl", "block loop wraps"))
 
     for p, n in enumerate(row["sched"]):
+        absent, reset_now = absent_of(row, p), set()
+        gone = set(absent)
         for who in resets.get(p, ()):
             will_shift = not (pos + n <= s["slots"] * s["chunk"] or pos == 0)
             if who == "all":                     # ed_stream_core_reset, :258-274: pos = 0, every microphone, frames_seen = 0
@@ -325,6 +436,7 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True):
                 items.add(("reset", "all"))
             else:
                 start_state(who)
+                reset_now.add(who)
                 assert pos != 0
                 items.add(("reset_mic", "first" if who == 0 else "last" if who == M - 1 else "inner"))
                 if M % 4 and who >= M - M % 4:
@@ -350,7 +462,7 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True):
         for m in range(M):
             at = m * A + pos * hop + tail
             assert at + n * hop <= (m + 1) * A
-            audio[at:at + n * hop] = _tok(m, epoch[m], 0, tail + (seen - start[m]) * hop) + np.arange(n * hop)
+            audio[at:at + n * hop] = GARBAGE if m in gone else _tok(m, epoch[m], 0, tail + cnt[m] * hop) + np.arange(n * hop)
         # ONE MFCC launch over n_mics * n frames: edison_stream_bank.hip:51-58, mfcc_geom_frames.inc:19-22, mfcc_geom_kernels.hip:29-33
         ml = mfcc_launch(g, M * n, n_cu)
         items |= {("mfcc", "team", ml["team"]), ("mfcc", "wraps" if ml["wraps"] else "one pass"), ("mfcc", "frames_per_utt", "1" if n == 1 else "chunk" if n == s["chunk"] else "ragged")}
@@ -359,13 +471,13 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True):
             u, f = divmod(gi, n)
             x0 = pos * hop + u * A + f * hop
             assert u * A <= x0 and x0 + N <= (u + 1) * A, "frame outside its microphone's samples"
-            if check and (gi < 2 * n or gi >= (M - 2) * n):          # every frame of the first and last microphones
-                want = _tok(u, epoch[u], 0, (seen - start[u] + f) * hop) + np.arange(N)
+            if check and u not in gone and (gi < 2 * n or gi >= (M - 2) * n):          # every frame of the first and last microphones
+                want = _tok(u, epoch[u], 0, (cnt[u] + f) * hop) + np.arange(N)
                 if not np.array_equal(audio[x0:x0 + N], want):
                     problems.append(("samples", p, u, f))
             o = pos * nm + (F - 1) * nm + gi * nm + feat_skip * u
             assert u * FB <= o and o + nm <= (u + 1) * FB, "row outside its microphone's rows"
-            feat[o:o + nm] = _tok(u, epoch[u], 1, (F - 1 + seen - start[u] + f) * nm) + np.arange(nm)
+            feat[o:o + nm] = GARBAGE if u in gone else _tok(u, epoch[u], 1, (F - 1 + cnt[u] + f) * nm) + np.arange(nm)
         # n network launches over the n_mics windows of a frame: edison_stream_bank.hip:59-65
         stride = FB + (nm if variant == "window_stride" else 0)
         full = pos + n == s["slots"] * s["chunk"]
@@ -385,12 +497,13 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True):
                     problems.append(("window", p, m, i))
                     continue
                 assert 0 <= lo and hi <= M * FB + SLACK, "window outside the rows and their slack"
-                if check and (m < 2 or m >= M - 2 or m % 97 == 0):
-                    want = _tok(m, epoch[m], 1, (seen - start[m] + i) * nm) + np.arange(F * nm)
+                if check and m not in gone and (m < 2 or m >= M - 2 or m % 97 == 0):
+                    want = _tok(m, epoch[m], 1, (cnt[m] + i) * nm) + np.arange(F * nm)
                     if not np.array_equal(feat[at:at + F * nm], want):
                         problems.append(("window", p, m, i))
         # the filter (+ machine), a workgroup per microphone: edison_stream_core.hip:52-111, over slab-major entries
-        items.add(("filter", "n", "1" if n == 1 else ">256" if n > 256 else "ragged" if n < s["chunk"] else "chunk"))
+        masked = bool(row.get("present")) and row["present"][p] is not None      # the kernel's mask branch, edison_stream_core.hip:58
+        items.add(("masked filter" if masked else "filter", "n", "1" if n == 1 else ">256" if n > 256 else "ragged" if n < s["chunk"] else "chunk"))
         if n > 1 and M > 1:
             assert n != M
             entry = np.full(n * M, POISON, np.int64)
@@ -405,14 +518,36 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True):
                     if entry[m * n + i if variant == "mic_major" else out_index(i, m, M)] != m * (1 << 32) + seen + i:
                         problems.append(("filter", p, m, i))
                         break
+        if row.get("present") and row["present"][p] is not None:
+            f = graph_facts(row["graph"])
+            hold_and_fill(s, f["n_out"], f["n_out"], 1, lambda m: audio[m * A:(m + 1) * A], lambda m: feat[m * FB:(m + 1) * FB], pos, n, absent, items,
+                          problems, p, hold, variant, shifted, reset_now)
         pos += n
         seen += n
+        for m in range(M):
+            cnt[m] += 0 if m in gone else n
+    if row.get("present"):
+        # a row with masks is in the sweep for its holds and fills: what else it reaches, the rows without a mask are there for
+        items = {it for it in items if it[0] in MASKED_ROW_ITEMS}
     return items, problems
 
 
 def is_overlap_row(row):
     """Some shift of the row's schedule moves samples or rows onto their own source."""
     return any(it[0] == "shift" and it[3] == "overlapping" for it in walk(row, check=False)[0])
+
+
+def is_hold_overlap_row(row):
+    """Some masked push of the row holds samples or rows up onto their own source."""
+    return any(it[0] == "hold" and it[2] == "overlapping" for it in walk(row, check=False)[0])
+
+
+def mask_set():
+    """The items of pushes that leave microphones out."""
+    s = {("hold", w, k) for w in ("samples", "rows") for k in ("overlapping", "touching", "disjoint")}
+    s |= {("hold zero", "<=256 bytes"), ("hold zero", ">256 bytes"), ("hold grid", "4096")} | {("fill", v) for v in ("one round", "several rounds", "n > 256")}
+    s |= {("masked filter", "n", v) for v in ("1", "ragged", ">256", "chunk")}
+    return s | {("absent", v) for v in ("first", "last", "inner", "everyone", "through a shift", "reset while absent")}
 
 
 def full_set():
@@ -424,14 +559,14 @@ def full_set():
     s |= {("push", p) for p in ("dev", "host", "alt")} | {("ref", "independent", "large"), ("ref", "independent", "small"), ("ref", "streams", "large"), ("ref", "streams", "small")}
     s |= {("fast", v) for v in ("<4", "4", "ragged", "4096", "more than one workgroup", "last window ends the buffers")}
     s |= {("general", v) for v in ("under", "equal", "over ragged", "blocks above the cap")} | {("spec", "more than one workgroup"), ("lbl", "block loop wraps")}
-    s |= {("reset", "all")} | {("reset_mic", v) for v in ("first", "last", "in a ragged last group", "right before a shift", "right after a shift", "elsewhere")}
+    s |= {("reset", "all")} | {("reset_mic", v) for v in ("first", "last", "inner", "in a ragged last group", "right before a shift", "right after a shift", "elsewhere")}
     s |= {("shift", w, "bank", k) for w in ("samples", "rows") for k in ("overlapping", "touching", "disjoint")}
     s |= {("shift", w, "single", k) for w in ("samples", "rows") for k in ("overlapping", "disjoint")}
     s |= {("overlap", "samples", ">256"), ("overlap", "samples", "x256"), ("overlap", "rows", "<256"), ("overlap", "rows", ">256")}
     s |= {("mfcc", "team", 64), ("mfcc", "team", EDG_BLOCK), ("mfcc", "wraps"), ("mfcc", "one pass")} | {("mfcc", "frames_per_utt", v) for v in ("1", "ragged", "chunk")}
     s |= {("residue", r) for r in range(16)} | {("filter", "n", v) for v in ("1", "ragged", ">256", "chunk")}
     s |= {("n_mics", ">4096"), ("n_mics x chunk", ">=2^31")}
-    return s
+    return s | mask_set()
 
 
 # item -> the host check or launch rule that keeps every accepted bank from it

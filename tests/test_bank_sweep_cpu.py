@@ -3,7 +3,9 @@ those in bank_sweep.EXCLUDED, each row is needed for at least one of them, every
 sizes are the ones edison_stream_core.h computes, and every row's push schedule walks through the emulator of the core -- numpy
 buffers of opaque tokens, the shift in the kernels' rounds of 256 -- with every frame the MFCC reads and every window the network reads
 holding exactly that microphone's newest samples and rows, inside its buffers. The same walk with the shift's waves left unordered goes
-wrong on exactly the rows whose shift overlaps, and with one indexing rule swapped for a mis-reading on every row that can tell."""
+wrong on exactly the rows whose shift overlaps, and with one indexing rule swapped for a mis-reading on every row that can tell. Rows
+with masks add the hold of the absent microphones and the filter kernel's fill; the hold with its rounds from the bottom up goes wrong
+on exactly the rows whose hold overlaps."""
 import functools
 import os
 import subprocess
@@ -136,3 +138,32 @@ def test_mis_readings_are_told_apart(built_lib, variant):
         assert bool(bs.walk(row, variant=variant)[1]) == multi, (name, variant)
         if multi and variant != "window_stride":
             assert all(n != row["n_mics"] for n in row["sched"] if n > 1), name
+
+
+MASKED = [n for n, r in bs.ROWS.items() if r["present"]]
+
+
+def test_the_masked_rows_reach_every_item_of_a_masked_push(built_lib):
+    """The hold over overlapping, touching and disjoint samples and rows, more than 256 bytes of rows to zero, the fill in one round,
+    several and beyond 256 frames, 4096 workgroups: all from rows with masks, which are in the sweep for nothing else."""
+    reached = set().union(*(_walk(n)[0] for n in MASKED))
+    assert bs.mask_set() <= reached and all(it[0] in bs.MASKED_ROW_ITEMS for it in reached)
+    assert not any(it in bs.mask_set() for n in bs.ROWS if n not in MASKED for it in _walk(n)[0])
+    # 19 outputs: from 14 frames on the rows to zero pass 256 bytes and the fill its first round of 256 / 19 rows
+    assert bs.graph_facts("even_same")["n_out"] == 19 and 13 * 19 <= 256 < 14 * 19
+
+
+@pytest.mark.parametrize("name", MASKED)
+def test_ascending_rounds_go_wrong_on_exactly_the_rows_whose_hold_overlaps(built_lib, name):
+    """The hold moves the history UP, so its rounds run from the top down (edison_bank_hold.hip:22): from the bottom up a round's writes
+    land on what a later round has yet to read, wherever the destination overlaps the source."""
+    row = bs.ROWS[name]
+    bad = bs.walk(row, hold=bs.hold_ascending)[1]
+    assert bool(bad) == bs.is_hold_overlap_row(row), (name, bad[:3])
+    assert {p[0] for p in bad} <= {"samples", "window"}
+
+
+def test_the_fill_written_to_the_present_microphones_is_caught_on_every_masked_row(built_lib):
+    for name, row in bs.ROWS.items():
+        assert bool(bs.walk(row, variant="fill_present")[1]) == bool(row["present"]), name
+    assert {n for n in MASKED if bs.is_hold_overlap_row(bs.ROWS[n])} == {"mask_even", "mask_touch", "mask_4096"}

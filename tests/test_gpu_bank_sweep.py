@@ -7,7 +7,10 @@ many streams whatever the row's size. Two references:
   streams      one stream.GeomStream per base recording (and per reset: a new stream fed the rest), same options, same schedule
   independent  no sliding buffer and no shift kernel: every frame's int8 row from the batch float64 MFCC (Context.mfcc_geom) on the
                zero-led recording, the windows cut in numpy behind F - 1 zero rows, Context.net on them, the filter in numpy
-               (test_gpu_stream_geom._filter_ref) and edisonFSM from the host binding (stream.Fsm)."""
+               (test_gpu_stream_geom._filter_ref) and edisonFSM from the host binding (stream.Fsm).
+Rows with masks (present) use the independent reference: a microphone's expected stream is that reference on the concatenation of the
+pushes it was present in (since its last reset), the pushes it was absent from carry noise over the whole int16 range, and at those its
+rows must hold the fill exactly: zero bytes, -1, its machine's unchanged state; frames_seen_mics() counts the present frames."""
 import ctypes
 import os
 import subprocess
@@ -150,6 +153,109 @@ def _expected(c, g, row, xb, base):
     return exp, snaps, thr
 
 
+# ---- rows with masks -------------------------------------------------------------------------------------------------------------------
+def lives_of(row):
+    """Per microphone the lives of its stream, a new one at every reset: [[the pushes it was present in] per life]."""
+    M = row["n_mics"]
+    lives = [[[]] for _ in range(M)]
+    for p in range(len(row["sched"])):
+        for at, who in row["resets"]:
+            if at == p:
+                for m in (range(M) if who == "all" else [who]):
+                    lives[m].append([])
+        gone = set(bs.absent_of(row, p))
+        for m in range(M):
+            if m not in gone:
+                lives[m][-1].append(p)
+    return lives
+
+
+def present_counts(row):
+    """frames_seen_mics() after the schedule: the frames of the pushes a microphone was present in since the last reset of the bank."""
+    first = max([at for at, who in row["resets"] if who == "all"], default=0)
+    counts = np.zeros(row["n_mics"], np.int64)
+    for p, n in enumerate(row["sched"]):
+        if p >= first:
+            counts += n
+            counts[bs.absent_of(row, p)] -= n
+    return counts
+
+
+def garbage(row, x, hop, seed=11):
+    """The push buffers: x [n_mics][K * hop] with the samples of every absent microphone replaced by noise over the whole int16 range."""
+    rng = np.random.default_rng(seed)
+    y, k0 = x.copy(), 0
+    for p, n in enumerate(row["sched"]):
+        gone = bs.absent_of(row, p)
+        if gone:
+            y[gone, k0 * hop:(k0 + n) * hop] = rng.integers(-32768, 32768, (len(gone), n * hop)).astype(np.int16)
+        k0 += n
+    return y
+
+
+def masked_expected(row, xb, base, hop, net_of, finish, start):
+    """(dict of [K][n_mics][..], [final machine per microphone], threshold) for a row with masks or resets, for either bank.
+    net_of(x, life): the network's outputs for every frame of recording x, the pushes `life` of the schedule put together, with no
+    sliding buffer; finish(net, thr): (those with the filter's and the machine's behind them, the final machine); start: (a new
+    machine's state, its raw fields). Microphones that play the same base recording through the same lives share a reference."""
+    M, sched = row["n_mics"], row["sched"]
+    off = np.concatenate([[0], np.cumsum(sched)])
+    groups = {}
+    for m, lv in enumerate(lives_of(row)):
+        resets_at = tuple(sorted(at for at, who in row["resets"] if who in ("all", m)))
+        groups.setdefault((base[m], tuple(tuple(life) for life in lv), resets_at), []).append(m)
+    nets = {}
+    for b, lv, _ in groups:
+        for life in lv:
+            if life and (b, life) not in nets:
+                nets[(b, life)] = net_of(np.concatenate([xb[b][off[p] * hop:off[p + 1] * hop] for p in life]), life)
+    thr = row["thr"]
+    if thr == "tie":
+        # a threshold that a filtered maximum equals exactly: the middle one of the reference's own maxima (strict >: not spotted)
+        best = np.concatenate([_filter_ref(_filter_input(n), row["alpha"], 0.0)[0].max(axis=1) for n in nets.values()])
+        vals = np.unique(best)
+        thr = float(vals[len(vals) // 2])
+        assert (best == np.float32(thr)).any() and (best > thr).any(), "no tie to test"
+    refs = {k: finish(n, thr) for k, n in nets.items()}
+    some = next(iter(refs.values()))[0]
+    exp = {k: (None if v is None else np.full((off[-1], M) + v.shape[1:], -1 if k in ("argmax", "likely", "spotted", "fsm_states") else 0, v.dtype))
+           for k, v in some.items()}
+    snaps = [None] * M
+    for (b, lv, resets_at), mics in groups.items():
+        mics = np.array(mics)
+        li, at, state, snap = 0, 0, start[0], start[1]
+        for p, n in enumerate(sched):
+            for r in resets_at:
+                if r == p:
+                    li, at, state, snap = li + 1, 0, start[0], start[1]
+            sl = slice(off[p], off[p + 1])
+            if p in lv[li]:
+                out, snap = refs[(b, lv[li])]
+                for k, v in exp.items():
+                    if v is not None:
+                        v[sl, mics] = out[k][at:at + n][:, None]
+                at += n
+                if row["fsm"]:
+                    state = out["fsm_states"][at - 1]
+            elif row["fsm"]:
+                exp["fsm_states"][sl, mics] = state            # the fill: the machine's unchanged state
+        for m in mics:
+            snaps[m] = snap        # a life's reference gives its machine at the life's end, which is where the schedule leaves it
+    return exp, snaps, thr
+
+
+def _filter_input(net):
+    second = net.get("softmax", net.get("probs"))
+    return second if second is not None else net["logits"]
+
+
+def _start_machine(thr):
+    from edison_amd.stream import Fsm, _fsm_dict
+    f = Fsm(threshold=thr)
+    raw = _fsm_dict(f._f)["raw"]
+    return raw[0], raw
+
+
 # ---- the bank ------------------------------------------------------------------------------------------------------------------------
 def _bank(c, g, row, x, thr):
     """The bank on x [n_mics][K * hop] by the row's schedule, pushes, resets and outputs. Returns (dict of [K][n_mics][..] with None for
@@ -172,9 +278,19 @@ def _bank(c, g, row, x, thr):
                 host = row["push"] == "host" or (row["push"] == "alt" and n == row["chunk"] and fulls % 2 == 0)
                 fulls += n == row["chunk"]
                 sl = slice(k0, k0 + n)
+                mask = None
+                if row["present"] and row["present"][p] is not None:
+                    mask = np.ones(M, np.uint8)
+                    mask[bs.absent_of(row, p)] = 0
                 if host:
                     assert n == row["chunk"]
-                    host_parts.append((sl, b.push(x[:, k0 * hop:(k0 + n) * hop])))
+                    host_parts.append((sl, b.push(x[:, k0 * hop:(k0 + n) * hop], present=mask)))
+                elif mask is not None:
+                    kw = {k: (o[k][sl] if k in asked and o[k] is not None else None) for k in ("logits", "softmax", "argmax")}
+                    kw.update(filtered=o["filtered"][sl], likely=o["likely"][sl], spotted=o["spotted"][sl])
+                    if row["fsm"]:
+                        kw.update(fsm_states=o["fsm_states"][sl])
+                    b.push_t(X[:, k0 * hop:(k0 + n) * hop].contiguous(), n_frames=n, present=torch.from_numpy(mask).to(dev), **kw)
                 else:
                     kw = {k: (o[k][sl] if k in asked and o[k] is not None else None) for k in ("logits", "softmax", "argmax")}
                     kw.update(filtered=o["filtered"][sl], likely=o["likely"][sl], spotted=o["spotted"][sl])
@@ -189,6 +305,8 @@ def _bank(c, g, row, x, thr):
                 snaps = [s["raw"] for s in b.fsm_snapshot()]
             if not any(who == "all" for _, who in row["resets"]):
                 assert b.frames_seen() == k0
+            if row["present"]:
+                assert np.array_equal(b.frames_seen_mics(), present_counts(row)), name_of(row)
         finally:
             b.close()
     finally:
@@ -203,6 +321,10 @@ def _bank(c, g, row, x, thr):
             if k not in asked:
                 got[k] = None
     return got, snaps
+
+
+def name_of(row):
+    return next(n for n, r in bs.ROWS.items() if r is row)
 
 
 def _run_row(name, tmp=None):
@@ -221,8 +343,15 @@ def _run_row(name, tmp=None):
         base = [bs.base_of(m, M) for m in range(M)]
         assert all(base[m] != base[m + 1] for m in range(M - 1))
         xb = _recordings(g, max(base) + 1, K, 300 + len(name))
-        exp, exp_snaps, thr = _expected(c, g, row, xb, base)
-        got, snaps = _bank(c, g, row, xb[base], thr)
+        if row["present"]:
+            assert row["ref"] == "independent"
+            thr0 = row["thr"]
+            exp, exp_snaps, thr = masked_expected(row, xb, base, g.frame_step, lambda x, life: _net_ref(c, g, x), lambda net, t: _finish_ref(c, g, row, net, t),
+                                                  _start_machine(thr0 if thr0 != "tie" else 0.5))
+            got, snaps = _bank(c, g, row, garbage(row, xb[base], g.frame_step), thr)
+        else:
+            exp, exp_snaps, thr = _expected(c, g, row, xb, base)
+            got, snaps = _bank(c, g, row, xb[base], thr)
         compared = 0
         for k in KEYS:
             if k not in exp or exp[k] is None or got.get(k) is None:
