@@ -52,6 +52,11 @@ class FnetInfo(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ("in_h", "in_w", "in_c", "n_out", "n_layers", "acts_floats", "batch", "lds_bytes")]
 
 
+class FcalInfo(ctypes.Structure):
+    """edison_fcal_info_t"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("n_stats", "in_n", "batch", "lds_bytes")]
+
+
 class StreamGeomOpts(ctypes.Structure):
     """edison_stream_geom_opts"""
     _fields_ = [("chunk_frames", ctypes.c_int32), ("filter", ctypes.c_int32), ("fsm", ctypes.c_int32), ("filter_alpha", c_double),
@@ -283,6 +288,13 @@ SIGNATURES = {
     "edison_f32_stream_predict_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "edison_f32_stream_predict": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "edison_nnom_predict": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "edison_fcal_create": (c_int, [c_void_p, ctypes.POINTER(c_void_p)]),
+    "edison_fcal_destroy": (None, [c_void_p]),
+    "edison_fcal_info": (c_int, [c_void_p, ctypes.POINTER(FcalInfo)]),
+    "edison_fcal_reset": (c_int, [c_void_p]),
+    "edison_fcal_add_dev": (c_int, [c_void_p, c_void_p, c_int64]),
+    "edison_fcal_add": (c_int, [c_void_p, c_void_p, c_int64]),
+    "edison_fcal_result": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "edison_eval_default_opts": (None, [ctypes.POINTER(EvalOpts)]),
     "edison_eval_create": (c_int, [c_void_p, ctypes.POINTER(EvalOpts), ctypes.POINTER(c_void_p)]),
     "edison_eval_destroy": (None, [c_void_p]),

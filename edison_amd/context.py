@@ -33,6 +33,7 @@ class Context:
             raise EdisonError(r, (self._L.edison_last_error(None) or b"").decode())
         self._h = h
         self.device = int(device)
+        self._fnet_blob = None
         if model_path is not None:
             self.load_model(model_path)
 
@@ -341,6 +342,7 @@ class Context:
         else:
             self._check(self._L.edison_fnet_load(self._h, str(src).encode()))
         self.fnet_keywords = self._ednf_keywords(src)
+        self._fnet_blob = bytes(src) if isinstance(src, (bytes, bytearray)) else open(str(src), "rb").read()   # quantize() reads the weights
 
     @staticmethod
     def _ednf_keywords(src):
@@ -544,6 +546,20 @@ class Context:
         with the arguments of kws_t / kws_geom_t / kws_f32_t / kws_float_t; returns an evaluate.EvalResult."""
         from . import evaluate as ev
         return ev.evaluate(self, audio, labels, flow=flow, chunk=chunk, **kw)
+
+    # ------------------------------------------------------------------ quantising the float network (edison_fcal_*, calibrate.py, quantize.py)
+    def calibrator(self):
+        """A calibrate.Calibrator on this context, bound to the loaded float network: add / add_t inputs, result() gives the statistic
+        quantize.quantize takes (edison_fcal_create)."""
+        from . import calibrate
+        return calibrate.Calibrator(self)
+
+    def quantize(self, audio, geometry=None, q15=False, chunk=16384, method="max_min", saturate=0.0, **kw):
+        """Calibrate the loaded float network on the utterances of `audio` through the float flow's features (kws_float's geometry, q15
+        and clip arguments) and quantise it to an int8 NNoM graph: see calibrate.quantize_audio. Returns (ednn_blob, report);
+        load_model_bytes(blob) runs it, report["net_input_scale"] is the net_input_scale its kws_geom geometry needs."""
+        from . import calibrate
+        return calibrate.quantize_audio(self, audio, geometry=geometry, q15=q15, chunk=chunk, method=method, saturate=saturate, **kw)
 
     # ------------------------------------------------------------------ multi-GPU (edison_dist_*: RCCL behind the C-ABI)
     def dist_init(self, id_bytes, rank, world_size):

@@ -7,6 +7,7 @@ on the keyword-spotting hot path:
     kws  mcu single|fileinf|file|frame   kws_on_mcu.py:650-690       -> edison_amd.kws.kws_host
     kws  live host|mcu <wav> [--net f]   audio/main.py:231-233       -> edison_amd.kws.kws_live
     kws  eval <audio.npy> <labels.npy>   nnom_utils.c:178-254        -> edison_amd.kws.kws_eval
+    kws  quantize <net> <audio> <out>    kws_nnom.py:305             -> edison_amd.kws.kws_quantize
 
 Where the reference talks to the STM32 board over the UART, the board's leg is computed by the GPU's bit-exact
 variant C. The remaining reference modules (mic, acquire, train, deploy, mcu) drive the board or Keras training and are
@@ -26,6 +27,7 @@ COMMANDS = {
         "mcu": ("edison_amd.kws.kws_host", 2),
         "live": ("edison_amd.kws.kws_live", 2),
         "eval": ("edison_amd.kws.kws_eval", 2),
+        "quantize": ("edison_amd.kws.kws_quantize", 2),
     },
 }
 
@@ -39,6 +41,8 @@ USAGE = """usage: edison <module> <command> [<args>]
                                          the firmware's continuous mode replayed on a wav (--net: the float32 X-CUBE-AI network)
   kws  eval <audio.npy> <labels.npy> [--graph <f> | --net <file.ednf>] [--geometry k=v,...] [--top-k K] [--chunk N]
                                          confusion matrix and top-k accuracy on a labelled data set, counted on the GPU
+  kws  quantize <net.ednf> <audio.npy> <out.ednn> [--weights-h <out.h>] [--saturate <share>] [--geometry k=v,...] [--chunk N]
+                                         quantise a float32 network to an int8 NNoM graph, calibrated on the GPU over the audio
 """
 
 

@@ -282,7 +282,9 @@ def out_dim(n, k, s, same):
     return -(-n // s) if same else -(-(n - k + 1) // s)
 
 
-def build_blob(in_shape, layers):
+def build_blob(in_shape, layers, dense_plain=False):
+    """dense_plain: the dense matrices are already plain row-major [out][in] (edison_amd/quantize.py), not in
+    arm_fully_connected_q7_opt's storage order; the blob is the same either way."""
     payload = bytearray()
     records = []
     shapes = []   # every record's output; a layer without "src" reads its predecessor
@@ -334,7 +336,7 @@ def build_blob(in_shape, layers):
         elif L["type"] == T_DENSE:
             n_in = h * w_ * c
             assert L["w"].size == L["out"] * n_in, "dense weight size mismatch"
-            plain = deinterleave_dense_opt(L["w"], L["out"], n_in)
+            plain = np.asarray(L["w"], np.int8).reshape(L["out"], n_in) if dense_plain else deinterleave_dense_opt(L["w"], L["out"], n_in)
             rec[1], rec[6], rec[7], rec[8] = L["out"], L["bias_lshift"], L["out_rshift"], L["relu"]
             rec[9], rec[10], rec[11] = put(plain), put(L["b"]), n_in
             h, w_, c = 1, 1, L["out"]

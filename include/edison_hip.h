@@ -410,6 +410,42 @@ int edison_kws_float_batch(edison_ctx *ctx, const edison_kws_geom *g, int q15, f
                            int64_t n_utt, int64_t utt_stride, float *feat, float *logits, float *probs, int32_t *argmax);
 
 /*
+ * Calibrating the loaded float network for quantisation to an int8 NNoM graph (the rule that turns the statistic
+ * into formats and shifts is edison_amd/quantize.py). A calibrator is bound to the float network loaded when it is created and
+ * accumulates, over every utterance added, one statistic for the network input (index 0) and one per conv / dense layer (index i =
+ * layer i - 1), n_stats = n_layers + 1 in all:
+ *   absmax  the largest bit pattern of fabsf(v) as uint32: v runs over the in_n floats of each input, or over acc + bias in f32 of a
+ *           layer -- edison_fnet_batch's value before ReLU and before the pool, at the positions the network uses (those a truncating
+ *           pool drops are not computed). An Inf or NaN anywhere gives a pattern >= 0x7f800000.
+ *   hist    [256] uint64: how many v have biased exponent field (bits >> 23) & 0xff
+ *   count   uint64: how many v
+ * All counting is in integer atomics: the result does not depend on launch shape, on arrival order or on how the data set is split
+ * into adds, and equals tests/fcal_ref.py's bit for bit.
+ *   edison_fcal_add_dev  one kernel launch on the context's stream: it follows a feature stage on that stream with no synchronisation
+ *   edison_fcal_add      the host form: stages its array and synchronises
+ *   edison_fcal_result   synchronises and copies out absmax [n_stats], hist [n_stats][256], count [n_stats]; each may be NULL; the
+ *                        counters go on
+ *   edison_fcal_reset    zeroes the counters, stream-ordered
+ * EDISON_E_NO_MODEL: no float network loaded at create; or, from every call but destroy, another float network was loaded since
+ * (create a new calibrator). EDISON_E_NO_IMPL at create: the network fills the LDS so far that the statistic's 1028 bytes do not fit
+ * beside one utterance. The calibrator runs the network at its own batch (edison_fcal_info), at most the network's.
+ */
+typedef struct edison_fcal edison_fcal;
+typedef struct edison_fcal_info_t {
+	int32_t n_stats;   /* n_layers + 1 */
+	int32_t in_n;      /* floats per input */
+	int32_t batch;     /* utterances per workgroup of the calibration kernel */
+	int32_t lds_bytes; /* LDS per workgroup */
+} edison_fcal_info_t;
+int edison_fcal_create(edison_ctx *ctx, edison_fcal **out);
+void edison_fcal_destroy(edison_fcal *c);
+int edison_fcal_info(edison_fcal *c, edison_fcal_info_t *out);
+int edison_fcal_reset(edison_fcal *c);
+int edison_fcal_add_dev(edison_fcal *c, const float *in, int64_t n);
+int edison_fcal_add(edison_fcal *c, const float *in, int64_t n);
+int edison_fcal_result(edison_fcal *c, uint32_t *absmax, uint64_t *hist, uint64_t *count);
+
+/*
  * Exact KWS mode (off by default; EDISON_KWS_EXACT=1 in the environment at edison_init turns it on for that context).
  * While it is on, every variant-B KWS call of the context -- edison_kws_batch, edison_kws_batch_dev and the sharded entry points --
  * aims at features, logits and argmax identical to the host flow's float64 arithmetic (mfcc_mcu, then float32 * scale, clip,

@@ -1,0 +1,333 @@
+"""CPU tests of quantising a float32 network to an int8 NNoM graph (edison_amd/quantize.py): the rule at its
+edges, every refusal, the assembler and the header emitter against the importer, and the shipped fixture network calibrated on the
+five fixture rows with the host restatement of the statistic (tests/fcal_ref.py).
+
+The fixture table. Calibrated with fcal_ref's exact f32 chain, the shipped network gives input dec -3 and, per layer, w_dec / b_dec /
+out_dec -> BIAS_LSHIFT / OUTPUT_RSHIFT:
+    conv2d_1 13 / 8 / 3 -> 2 / 7     conv2d_2 8 / 7 / 2 -> 4 / 9     conv2d_3 8 / 5 / 3 -> 5 / 7     conv2d_4 9 / 5 / 3 -> 7 / 9
+    dense_1   8 / 10 / 2 -> 1 / 9
+No exact-f32 absmax lands on the other side of a power of two from the float64 figures the feature request quotes; its first four
+rows are these. Its last row reads "8 / 10 -> 5 (clamped) / 2 -> 0 / 9", which the rule it states cannot give: dense_1 reads conv2d_4's
+format, in_dec + w_dec = 3 + 8 = 11, so a bias dec of 10 is below the clamp and BIAS_LSHIFT = 11 - 10 = 1 (a bias dec of 5 would
+give 6, and a shift of 0 needs 11). The rule decides; the values above are what it gives."""
+import os
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, ROOT
+
+import fcal_ref
+import fnet_exact
+import fnet_ref
+from edison_amd import cube_import, nnom_import
+from edison_amd import quantize as qz
+from oracle import net_ref
+
+FIXTURE = os.path.join(GOLDEN, "cube_kws.ednf")
+TABLE = [("conv2d_1", 13, 8, 3, 2, 7), ("conv2d_2", 8, 7, 2, 4, 9), ("conv2d_3", 8, 5, 3, 5, 7), ("conv2d_4", 9, 5, 3, 7, 9),
+         ("dense_1", 8, 10, 2, 1, 9)]
+# the reference's own weights.h:5-68: dec bits of every kernel, bias and layer output (edison_amd/data/kws_nnom.ednn is its import)
+REF_W_DEC, REF_B_DEC, REF_OUT_DEC, REF_IN_DEC = [12, 8, 8, 9, 7], [8, 7, 5, 5, 10], [4, 4, 5, 5, 2], 0
+
+
+def _stats(values):
+    """One statistic per entry of `values` (float arrays)."""
+    s = fcal_ref.empty(len(values) - 1)
+    for i, v in enumerate(values):
+        s["absmax"][i], s["hist"][i], s["count"][i] = fcal_ref.of_values(np.asarray(v, np.float32))
+    return s
+
+
+def _tiny_model(w=0.5, b=0.25, relu=1):
+    """A 2 x 2 x 1 input, one 2 x 2 kernel covering it (a dense layer of 1 output), softmax."""
+    L = dict(type=cube_import.T_CONV, inp=(2, 2, 1), out=(1, 1, 1), k=(2, 2), s=(1, 1), p=(1, 1), relu=relu,
+             w=np.full((1, 2, 2, 1), w, np.float32), b=np.full(1, b, np.float32))
+    return dict(in_shape=(2, 2, 1), layers=[L, dict(type=cube_import.T_SOFTMAX, inp=(1, 1, 1), out=(1, 1, 1))])
+
+
+def _two_layer_model():
+    rng = np.random.default_rng(5)
+    c = dict(type=cube_import.T_CONV, inp=(6, 5, 1), out=(2, 3, 3), k=(3, 3), s=(1, 1), p=(2, 1), relu=1,
+             w=rng.normal(0, 0.4, (3, 3, 3, 1)).astype(np.float32), b=rng.normal(0, 0.1, 3).astype(np.float32))
+    d = dict(type=cube_import.T_CONV, inp=(2, 3, 3), out=(1, 1, 4), k=(2, 3), s=(1, 1), p=(1, 1), relu=0,
+             w=rng.normal(0, 0.3, (4, 2, 3, 3)).astype(np.float32), b=rng.normal(0, 0.1, 4).astype(np.float32))
+    return dict(in_shape=(6, 5, 1), layers=[c, d, dict(type=cube_import.T_SOFTMAX, inp=(1, 1, 4), out=(1, 1, 4))])
+
+
+# ---- the rule -------------------------------------------------------------------------------------------------------------------
+def test_power_of_two_edges():
+    one = np.float32(1.0)
+    above, below = np.nextafter(one, np.float32(2)), np.nextafter(one, np.float32(0))
+    assert (qz.int_bits_of(one), qz.dec_bits_of(one)) == (0, 7)
+    assert (qz.int_bits_of(above), qz.dec_bits_of(above)) == (1, 6)
+    assert (qz.int_bits_of(below), qz.dec_bits_of(below)) == (0, 7)
+    assert [qz.dec_bits_of(v) for v in (0.5, 0.75, 2.0, 3.0, 128.0, 129.0, 2.0 ** -20, 894.842)] == [8, 7, 6, 5, 0, -1, 27, -3]
+    # at exactly 1.0 the value itself clips: 1.0 * 2^7 = 128 -> 127; just below it rounds to 128 and clips too; just above, dec 6 holds it
+    assert qz.quantize_tensor([one, -one], 7)[0].tolist() == [127, -128]
+    assert qz.quantize_tensor([below], 7)[0].tolist() == [127]
+    assert qz.quantize_tensor([above, -above], 6)[0].tolist() == [64, -64]
+    # through quantize: the input's statistic decides the input dec
+    for v, dec in ((one, 7), (above, 6), (below, 7)):
+        _, rep = qz.quantize(_tiny_model(), _stats([[v, 0.1], [0.3]]))
+        assert rep["input"]["dec"] == dec and rep["net_input_scale"] == 2.0 ** dec
+
+
+def test_half_even_rounding_and_rms():
+    q, rms = qz.quantize_tensor([0.5, 1.5, 2.5, -0.5, -1.5, -2.5, 0.4999, 126.5, 127.5, -128.5, 300.0, -300.0], 0)
+    assert q.tolist() == [0, 2, 2, 0, -2, -2, 0, 126, 127, -128, 127, -128]
+    q, rms = qz.quantize_tensor([0.25, 0.75, 0.3], 1)          # x 2 = 0.5, 1.5, 0.6 -> 0, 2, 1
+    assert q.tolist() == [0, 2, 1]
+    assert rms == pytest.approx(np.sqrt((0.25 ** 2 + 0.25 ** 2 + 0.2 ** 2) / 3))
+    assert qz.quantize_input(np.array([[-8.0, 12.0, 11.9, 2000.0]], np.float32), -3).tolist() == [[-1, 2, 1, 127]]
+
+
+def test_shift_derivation_and_bias_clamp():
+    assert qz.shifts(0, 12, 8, 4) == (4, 8)                       # the reference's conv2d_1 (weights.h:72-73)
+    # in_dec 7 (input absmax 1), w_dec 8 (0.5): a bias of 2^-12 would get dec 19, clamped to 15 -> BIAS_LSHIFT 0
+    blob, rep = qz.quantize(_tiny_model(w=0.5, b=2.0 ** -12), _stats([[1.0], [0.9]]))
+    L = rep["layers"][0]
+    assert (L["w_dec"], L["b_dec"], L["b_clamped"], L["bias_lshift"]) == (8, 15, True, 0)
+    assert net_ref.parse_blob(blob)[1][0][6] == 0
+    # a large bias is not clamped
+    _, rep = qz.quantize(_tiny_model(w=0.5, b=3.0), _stats([[1.0], [3.5]]))
+    L = rep["layers"][0]
+    assert (L["b_dec"], L["b_clamped"], L["bias_lshift"]) == (5, False, 10)
+    # an all-zero bias gets in_dec + w_dec
+    _, rep = qz.quantize(_tiny_model(w=0.5, b=0.0), _stats([[1.0], [0.9]]))
+    L = rep["layers"][0]
+    assert (L["b_dec"], L["b_clamped"], L["bias_lshift"], L["b_rms"]) == (15, False, 0, 0.0)
+
+
+def test_refusals_name_the_layer():
+    m = _two_layer_model()
+    ok = [[1.0, -0.5], [2.0, -3.0], [1.5]]
+    qz.quantize(m, _stats(ok))
+
+    def refused(stats, *words, **kw):
+        with pytest.raises(qz.QuantizeError) as e:
+            qz.quantize(m, stats, **kw)
+        for w in words:
+            assert w in str(e.value), (w, str(e.value))
+
+    # OUTPUT_RSHIFT negative: input absmax 100 -> dec 0; weights < 1.5 -> w_dec at most 7...; an output of 2^-20 wants dec 27
+    refused(_stats([[100.0], [2.0 ** -20], [1.5]]), "conv2d_1", "OUTPUT_RSHIFT", "negative")
+    refused(_stats([[1.0], [2.0], [2.0 ** -30]]), "dense_1", "OUTPUT_RSHIFT", "negative")
+    # all-zero statistics
+    refused(_stats([[0.0, -0.0], [2.0], [1.5]]), "input", "zero")
+    refused(_stats([[1.0], [0.0], [1.5]]), "conv2d_1", "zero")
+    refused(_stats([[1.0], [2.0], [0.0]]), "dense_1", "zero")
+    # non-finite statistics: Inf and NaN win the integer maximum
+    for bad in (np.inf, -np.inf, np.nan):
+        refused(_stats([[1.0, bad], [2.0], [1.5]]), "input", "Inf or NaN")
+        refused(_stats([[1.0], [2.0, bad], [1.5]]), "conv2d_1", "Inf or NaN")
+        refused(_stats([[1.0], [2.0], [bad, 1.5]]), "dense_1", "Inf or NaN")
+        refused(_stats([[1.0], [2.0], [bad, 1.5]]), "dense_1", "Inf or NaN", method="saturate", saturate=0.5)
+    # nothing calibrated
+    for i, name in enumerate(("input", "conv2d_1", "dense_1")):
+        s = _stats(ok)
+        s["count"][i] = 0
+        refused(s, name, "count == 0")
+    refused(fcal_ref.empty(2), "input", "count == 0")
+    # statistics of another network, unknown method, a shift too large
+    refused(_stats(ok[:2]), "not those of this network")
+    refused(_stats(ok), "KLD", method="kld")
+    refused(_stats([[2.0 ** -30], [2.0], [1.5]]), "conv2d_1", "above 31")
+    # a non-finite weight
+    bad = _two_layer_model()
+    bad["layers"][1]["w"][0, 0, 0, 0] = np.inf
+    with pytest.raises(qz.QuantizeError, match="dense_1"):
+        qz.quantize(bad, _stats(ok))
+
+
+@pytest.mark.parametrize("saturate", [0.0, 0.001, 0.01, 0.1, 0.5])
+def test_saturate_against_brute_force(saturate):
+    rng = np.random.default_rng(int(saturate * 1000) + 3)
+    for scale in (1.0, 37.0, 2.0 ** -9):
+        v = (rng.standard_cauchy(20000) * scale).astype(np.float32)
+        _, hist, count = fcal_ref.of_values(v)
+        k = qz.int_bits_saturate(hist, count, saturate)
+        a = np.abs(v.astype(np.float64))
+        at_or_above = lambda kk: int((a >= 2.0 ** kk).sum())
+        assert at_or_above(k) <= saturate * v.size
+        assert at_or_above(k - 1) > saturate * v.size
+    # saturate = 0 keeps every value below 2^k: one more bit than max_min exactly at a power of two, the same elsewhere
+    for v, k in (([1.0, 0.1], 1), ([0.99, 0.1], 0), ([1.01], 1), ([3.0], 2)):
+        _, hist, count = fcal_ref.of_values(np.array(v, np.float32))
+        assert qz.int_bits_saturate(hist, count, 0.0) == k
+    # through quantize: a 1 % outlier 1000 times the rest no longer sets the format
+    x = np.concatenate([rng.uniform(-1, 1, 990), [900.0] * 10]).astype(np.float32)
+    s = _stats([x, [100.0]])
+    assert qz.quantize(_tiny_model(), s)[1]["input"]["dec"] == -3
+    assert qz.quantize(_tiny_model(), s, method="saturate", saturate=0.02)[1]["input"]["dec"] == 7
+
+
+# ---- the assembler and the emitter ----------------------------------------------------------------------------------------------------
+def _with_decs(layers, in_dec=0):
+    """Importer layers -> assembler layers: shifts replaced by dec bits that give them, dense matrices made plain."""
+    out, dec, shape = [], in_dec, None
+    for L in layers:
+        L = dict(L)
+        L.pop("src", None)
+        if L["type"] in (nnom_import.T_CONV, nnom_import.T_DENSE):
+            bl, rs = L.pop("bias_lshift"), L.pop("out_rshift")
+            L["w_dec"] = 9
+            L["b_dec"], L["out_dec"] = dec + 9 - bl, dec + 9 - rs
+            dec = L["out_dec"]
+            if L["type"] == nnom_import.T_DENSE:
+                L["w"] = nnom_import.deinterleave_dense_opt(L["w"], L["out"], L["w"].size // L["out"])
+        out.append(L)
+    return out
+
+
+SEQUENTIAL = [n for n in ("kws_small", "low_latency_small", "odd_no_softmax", "same_stride", "square", "tiny_conv", "even_same")]
+
+
+@pytest.mark.parametrize("name", SEQUENTIAL)
+def test_assembler_reproduces_the_importer_on_the_alt_models(name):
+    """Integer tensors and shifts of a committed header, restated as dec bits, through assemble(): the importer's bytes."""
+    with open(os.path.join(GOLDEN, "alt_models", name + ".h")) as f:
+        text = f.read()
+    shape, layers = nnom_import.parse_weights_h(text)
+    want = nnom_import.build_blob(shape, layers)
+    assert qz.assemble(shape, 0, _with_decs(layers)) == want
+    # and the emitter: header text of those layers -> the importer -> the same bytes
+    h = qz.write_weights_h(_with_decs(layers), shape, 0)
+    shape2, layers2 = nnom_import.parse_weights_h(h)
+    assert shape2 == shape and nnom_import.build_blob(shape2, layers2) == want
+
+
+def test_assembler_reproduces_the_reference_graph():
+    """The shipped int8 model is the importer's blob of the reference's own weights.h. Its integer tensors with the dec bits that
+    header declares (weights.h:5-68), through assemble(): the same bytes. This pins the shift derivation on the reference."""
+    with open(os.path.join(ROOT, "edison_amd", "data", "kws_nnom.ednn"), "rb") as f:
+        want = f.read()
+    shape, recs, payload = net_ref.parse_blob(want)
+    layers, i, (h, w, c) = [], 0, shape
+    for v in recs:
+        if v[0] == net_ref.T_CONV:
+            k = v[2] * v[3] * c
+            layers.append(dict(type=nnom_import.T_CONV, out_ch=v[1], kh=v[2], kw=v[3], sh=v[4], sw=v[5], same=(v[8] >> 1) & 1, relu=v[8] & 1,
+                               w=payload[v[9]:v[9] + v[1] * k].copy(), b=payload[v[10]:v[10] + v[1]].copy(), w_dec=REF_W_DEC[i], b_dec=REF_B_DEC[i],
+                               out_dec=REF_OUT_DEC[i]))
+            h, w, c = nnom_import.out_dim(h, v[2], v[4], 0), nnom_import.out_dim(w, v[3], v[5], 0), v[1]
+            i += 1
+        elif v[0] == net_ref.T_POOL:
+            layers.append(dict(type=nnom_import.T_POOL, kh=v[2], kw=v[3], sh=v[4], sw=v[5], same=(v[8] >> 1) & 1))
+            h, w = nnom_import.out_dim(h, v[2], v[4], 0), nnom_import.out_dim(w, v[3], v[5], 0)
+        elif v[0] == net_ref.T_DENSE:
+            layers.append(dict(type=nnom_import.T_DENSE, out=v[1], relu=v[8] & 1, w=payload[v[9]:v[9] + v[1] * v[11]].copy().reshape(v[1], v[11]),
+                               b=payload[v[10]:v[10] + v[1]].copy(), w_dec=REF_W_DEC[i], b_dec=REF_B_DEC[i], out_dec=REF_OUT_DEC[i]))
+            h, w, c = 1, 1, v[1]
+            i += 1
+        else:
+            layers.append(dict(type=nnom_import.T_SOFTMAX))
+    assert i == 5
+    assert qz.assemble(shape, REF_IN_DEC, layers) == want
+    # the shifts the reference's macros evaluate to (weights.h:72-105)
+    got = [(L["bias_lshift"], L["out_rshift"]) for L in (dict(zip(("bias_lshift", "out_rshift"), (v[6], v[7]))) for v in recs if v[0] in (1, 3))]
+    assert got == [(4, 8), (5, 8), (7, 7), (9, 9), (2, 10)]
+    # the emitter on the same layers: its header imports to the same bytes
+    shape2, layers2 = nnom_import.parse_weights_h(qz.write_weights_h(layers, shape, REF_IN_DEC))
+    assert shape2 == shape and nnom_import.build_blob(shape2, layers2) == want
+
+
+def test_interleave_inverts_deinterleave():
+    rng = np.random.default_rng(2)
+    for rows, cols in ((10, 480), (4, 4), (7, 9), (3, 5), (9, 2)):
+        w = rng.integers(-128, 128, (rows, cols)).astype(np.int8)
+        assert np.array_equal(nnom_import.deinterleave_dense_opt(qz.interleave_dense_opt(w), rows, cols), w)
+
+
+def test_build_blob_plain_switch_changes_nothing_for_its_callers():
+    with open(os.path.join(GOLDEN, "alt_models", "kws_small.h")) as f:
+        shape, layers = nnom_import.parse_weights_h(f.read())
+    plain = [dict(L, w=nnom_import.deinterleave_dense_opt(L["w"], L["out"], L["w"].size // L["out"])) if L["type"] == nnom_import.T_DENSE else L
+             for L in layers]
+    assert nnom_import.build_blob(shape, layers) == nnom_import.build_blob(shape, layers, dense_plain=False) == \
+        nnom_import.build_blob(shape, plain, dense_plain=True)
+
+
+def test_header_round_trip_of_a_quantised_network():
+    m = _two_layer_model()
+    x = np.random.default_rng(8).normal(0, 2, (7, 30)).astype(np.float32)
+    blob, rep = qz.quantize(m, fcal_ref.stats(m, x))
+    h = qz.write_weights_h(rep["graph"], rep["in_shape"], rep["input"]["dec"])
+    shape, layers = nnom_import.parse_weights_h(h)
+    assert nnom_import.build_blob(shape, layers) == blob
+    for word in ("CONV2D_1_KERNEL_0 ", "CONV2D_1_KERNEL_0_SHIFT", "CONV2D_1_BIAS_0 ", "CONV2D_1_BIAS_0_SHIFT", "CONV2D_1_OUTPUT_SHIFT", "CONV2D_1_OUTPUT_RSHIFT",
+                 "CONV2D_1_BIAS_LSHIFT", "MAX_POOLING2D_1_OUTPUT_SHIFT", "DENSE_1_KERNEL_0 ", "DENSE_1_OUTPUT_RSHIFT (MAX_POOLING2D_1_OUTPUT_SHIFT+",
+                 "INPUT_1_OUTPUT_SHIFT", "NNOM_INPUT_SCALE", "NNOM_INPUT_MIN", "NNOM_INPUT_MAX", "nnom_model_create(void)", "MaxPool(kernel(2, 1), stride(2, 1), PADDING_VALID)",
+                 "Dense(4, &dense_1_w, &dense_1_b)", "act_relu()", "Softmax()", "Output(shape(4,1,1), nnom_output_data)", "#error CONV2D_1_OUTPUT_RSHIFT"):
+        assert word in h, word
+    # the int8 graph follows the float one on the calibration inputs: logits within a few output steps
+    out_dec = rep["layers"][-1]["out_dec"]
+    q = net_ref.run(blob, qz.quantize_input(x, rep["input"]["dec"]))["logits"].astype(np.float64) * 2.0 ** -out_dec
+    f = fnet_ref.run(m, x)["logits"]
+    assert np.abs(q - f).max() <= 0.25 * np.abs(f).max()
+
+
+# ---- the statistic's host restatement ---------------------------------------------------------------------------------------------
+def test_fcal_ref_counts_what_the_network_uses():
+    m = _two_layer_model()
+    x = np.random.default_rng(9).normal(0, 1, (3, 30)).astype(np.float32)
+    s = fcal_ref.stats(m, x)
+    # conv 3 x 3 on 6 x 5 -> 4 x 3, pool (2, 1) keeps all 4 rows; dense 4 outputs
+    assert s["count"].tolist() == [3 * 30, 3 * 4 * 3 * 3, 3 * 4]
+    assert (s["hist"].sum(axis=1) == s["count"]).all()
+    pre = fcal_ref.pre_activation(fnet_exact.conv_records(m)[0], x)
+    assert s["absmax"][1] == np.abs(pre).max().view(np.uint32)
+    assert (pre < 0).any() and np.abs(pre).max() >= np.abs(fnet_exact.run(m, x)[0]).max()     # before ReLU: the negative side counts
+    # splitting the set changes nothing
+    a, b = fcal_ref.stats(m, x[:1]), fcal_ref.stats(m, x[1:])
+    merged = fcal_ref.merge(a, b)
+    assert all(np.array_equal(merged[k], s[k]) for k in s)
+    # within f32 rounding of the float64 restatement
+    r = fnet_ref.run(m, x)
+    assert np.float32(s["absmax"][2:3].view(np.float32)[0]) == pytest.approx(np.abs(r["logits"]).max(), rel=1e-5)
+
+
+# ---- the shipped network ----------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def shipped():
+    m = fnet_ref.load(FIXTURE)
+    g = np.load(os.path.join(GOLDEN, "cube_golden.npz"))
+    x = np.stack([g["net_in_" + str(n)] for n in g["names"]])
+    return m, x, [str(n) for n in g["names"]], fcal_ref.stats(m, x)
+
+
+def test_shipped_network_report_equals_the_table(shipped):
+    m, x, names, stats = shipped
+    _, rep = qz.quantize(m, stats)
+    assert rep["input"]["dec"] == -3 and rep["net_input_scale"] == 0.125
+    got = [(L["name"], L["w_dec"], L["b_dec"], L["out_dec"], L["bias_lshift"], L["out_rshift"]) for L in rep["layers"]]
+    assert got == TABLE
+    assert not any(L["b_clamped"] for L in rep["layers"])
+    assert all(L["bias_lshift"] >= 0 and L["out_rshift"] >= 0 for L in rep["layers"])
+    assert all(0 < L["w_rms"] <= 2.0 ** -L["w_dec"] and 0 < L["b_rms"] <= 2.0 ** -L["b_dec"] for L in rep["layers"])
+    assert "conv2d_3" in qz.format_report(rep)
+    # saturate = 0 differs from max_min only at an exact power of two: none here
+    _, rep0 = qz.quantize(m, stats, method="saturate", saturate=0.0)
+    assert [L["out_dec"] for L in rep0["layers"]] == [L["out_dec"] for L in rep["layers"]] and rep0["input"]["dec"] == -3
+
+
+def test_shipped_network_int8_argmax_equals_float(shipped):
+    m, x, names, stats = shipped
+    blob, rep = qz.quantize(m, stats)
+    f = fnet_ref.run(m, x)["argmax"]
+    q = net_ref.run(blob, qz.quantize_input(x, rep["input"]["dec"]))
+    assert f.tolist() == [0, 7, 9, 8, 8] and names[0] == "edison"
+    assert q["argmax"].tolist() == f.tolist()
+    # header round trip of the real thing
+    shape, layers = nnom_import.parse_weights_h(qz.write_weights_h(rep["graph"], rep["in_shape"], rep["input"]["dec"]))
+    assert nnom_import.build_blob(shape, layers) == blob
+
+
+# ---- the command line -------------------------------------------------------------------------------------------------------------
+def test_command_line_is_registered(capsys):
+    from edison_amd import main
+    from edison_amd.kws import kws_quantize
+    assert main.COMMANDS["kws"]["quantize"][0] == "edison_amd.kws.kws_quantize" and "kws  quantize" in main.USAGE
+    assert kws_quantize.main(["quantize", "net.ednf"]) == 1 and kws_quantize.main(["quantize", "a", "b", "c", "--saturate", "x"]) == 1
+    assert kws_quantize.main(["quantize", "a", "b", "c", "--chunk"]) == 1
+    assert "usage: kws quantize" in capsys.readouterr().out
