@@ -1,6 +1,6 @@
 /*
  * edison_fnet.hip -- C-ABI of the float32 X-CUBE-AI network path (include/edison_hip.h, edison_fnet_* and edison_kws_float_batch*;
- * DESIGN.md section 14): the .ednf blob (edison_amd/cube_import.py) is checked and turned into the kernel's plan (fnet.h), and the
+ * DESIGN.md sections 14 and 14b): the .ednf blob (edison_amd/cube_import.py; version 1, or version 2 with conv and pool pads) is checked and turned into the kernel's plan (fnet.h), and the
  * network runs on fnet_kernels.hip. edison_kws_float_batch* puts a feature stage in front of it: the float64 MFCC at any geometry
  * (mfcc_geom_kernels.hip) -> float32 x net_input_scale -> clip (the reference's host flow), or variant C -> (float) (the firmware's).
  * The int8 NNoM model of the context is not touched: a context may hold both.
@@ -17,7 +17,7 @@
 
 #define EDF_T_CONV 1
 #define EDF_T_SOFTMAX 2
-#define EDF_REC_INTS 16
+#define EDF_REC_INTS 24 /* version 2; version 1 has the first 16 and no pads */
 #define EDF_HDR_BYTES 32
 #define EDF_MAX_DIM 4096
 
@@ -55,13 +55,15 @@ static int bad(edison_ctx *ctx, const char *msg)
 static int parse(edison_ctx *ctx, const uint8_t *b, size_t nb, ed_fnet *f, float **w_out, size_t *nw_out, int32_t **tab_out, size_t *nt_out)
 {
 	if (nb < EDF_HDR_BYTES || memcmp(b, "EDNF", 4) != 0) return bad(ctx, "not an .ednf blob (magic)");
-	if (rd32(b + 4) != 1) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: .ednf version is not 1");
+	const int ver = rd32(b + 4);
+	if (ver != 1 && ver != 2) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: .ednf version is not 1 or 2");
+	const int ri = ver == 1 ? 16 : EDF_REC_INTS; /* ints per record */
 	const int nl = rd32(b + 8), in_h = rd32(b + 12), in_w = rd32(b + 16), in_c = rd32(b + 20), n_out = rd32(b + 24), kwb = rd32(b + 28);
 	if (nl < 2 || nl > ED_FNET_MAX_LAYERS + 1) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: 2 .. 17 layer records");
 	if (in_h < 1 || in_w < 1 || in_c < 1 || in_h > EDF_MAX_DIM || in_w > EDF_MAX_DIM || in_c > EDF_MAX_DIM || kwb < 0 || kwb % 4)
 		return bad(ctx, "bad header");
 	if ((int64_t)in_h * in_w * in_c > (1 << 20)) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: input too large");
-	size_t off = EDF_HDR_BYTES + (size_t)nl * EDF_REC_INTS * 4;
+	size_t off = EDF_HDR_BYTES + (size_t)nl * ri * 4;
 	if (off + (size_t)kwb > nb) return bad(ctx, "truncated records");
 	const uint8_t *rec0 = b + EDF_HDR_BYTES;
 	off += (size_t)kwb;
@@ -75,12 +77,15 @@ static int parse(edison_ctx *ctx, const uint8_t *b, size_t nb, ed_fnet *f, float
 	/* pass 1: shapes, sizes */
 	for (int i = 0; i < nl; i++)
 	{
-		const uint8_t *r = rec0 + (size_t)i * EDF_REC_INTS * 4;
-		int v[EDF_REC_INTS];
-		for (int j = 0; j < EDF_REC_INTS; j++) v[j] = rd32(r + 4 * j);
+		const uint8_t *r = rec0 + (size_t)i * ri * 4;
+		int v[EDF_REC_INTS] = {0};
+		for (int j = 0; j < ri; j++) v[j] = rd32(r + 4 * j);
 		if (v[0] != EDF_T_CONV && v[0] != EDF_T_SOFTMAX) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: unknown layer type");
 		for (int j = 1; j <= (v[0] == EDF_T_CONV ? 15 : 6); j++)
 			if (v[j] < (j == 11 ? 0 : 1) || v[j] > EDF_MAX_DIM * (j >= 14 ? 16 : 1)) return bad(ctx, "layer field out of range");
+		if (v[0] == EDF_T_CONV)
+			for (int j = 16; j < EDF_REC_INTS; j++)
+				if (v[j] < 0 || v[j] > EDF_MAX_DIM) return bad(ctx, "a pad is negative or out of range");
 		const int64_t cur = (int64_t)h * w * c;
 		if ((int64_t)v[1] * v[2] * v[3] != cur) return bad(ctx, "a layer's input size differs from the previous layer's output");
 		if (v[0] == EDF_T_SOFTMAX)
@@ -91,9 +96,16 @@ static int parse(edison_ctx *ctx, const uint8_t *b, size_t nb, ed_fnet *f, float
 		}
 		if (i == nl - 1) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: the network must end in a softmax");
 		const int ih = v[1], iw = v[2], ic = v[3], kh = v[7], kw = v[8], sh = v[9], sw = v[10], ph = v[12], pw = v[13];
-		if (kh > ih || kw > iw) return bad(ctx, "kernel larger than its input");
-		const int oh = (ih - kh) / sh + 1, ow = (iw - kw) / sw + 1;
-		if (v[4] != oh / ph || v[5] != ow / pw) return bad(ctx, "output shape does not follow from the conv and pool");
+		const int pt = v[16], pl = v[17], pb = v[18], pr = v[19], qt = v[20], ql = v[21], qb = v[22], qr = v[23];
+		/* a pad as large as its window's extent would give windows wholly in padding: refused, so every window has a real element */
+		if (pt >= kh || pb >= kh || pl >= kw || pr >= kw)
+			return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: a conv pad must be smaller than the kernel on its axis");
+		if (qt >= ph || qb >= ph || ql >= pw || qr >= pw)
+			return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: a pool pad must be smaller than the pool window on its axis");
+		if (kh > ih + pt + pb || kw > iw + pl + pr) return bad(ctx, "kernel larger than its padded input");
+		const int oh = (ih + pt + pb - kh) / sh + 1, ow = (iw + pl + pr - kw) / sw + 1;
+		const int Ph = oh + qt + qb >= ph ? (oh + qt + qb - ph) / ph + 1 : 0, Pw = ow + ql + qr >= pw ? (ow + ql + qr - pw) / pw + 1 : 0;
+		if (v[4] != Ph || v[5] != Pw) return bad(ctx, "output shape does not follow from the conv and pool");
 		if ((int64_t)v[4] * v[5] * v[6] * ph * pw > (1 << 20) || (int64_t)kh * kw * ic > (1 << 16))
 			return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: layer too large");
 		const int P = ph * pw;
@@ -116,17 +128,27 @@ static int parse(edison_ctx *ctx, const uint8_t *b, size_t nb, ed_fnet *f, float
 		L.dst = L.src ^ 1;
 		L.w_at = wfl;
 		L.koff_at = (int32_t)tabn;
-		L.rowin_at = (int32_t)(tabn + L.k_pad);
+		L.pad = (pt | pl | pb | pr | qt | ql | qb | qr) != 0;
+		L.in_h = ih; L.in_w = iw; L.in_c = ic;
+		const int kn = L.pad ? 2 * L.k_pad : L.k_pad; /* koff, and behind it a padded record's kyx */
+		L.rowin_at = (int32_t)(tabn + kn);
+		{
+			/* rows of the pool windows that lie on the conv's map: the others are absent */
+			int lh = 0, lw = 0;
+			for (int y = 0; y < Ph * ph; y++) lh += y >= qt && y - qt < oh;
+			for (int x = 0; x < Pw * pw; x++) lw += x >= ql && x - ql < ow;
+			L.live = lh * lw;
+		}
 		L.acts_at = (int32_t)acts;
 		const int64_t wl = (int64_t)L.k_pad * L.n_pad;
 		if (wl > ED_FNET_LDS_BYTES / 4) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: a layer's weights exceed the LDS");
 		wfl += wl + L.n_pad;
-		tabn += L.k_pad + L.rows;
+		tabn += kn + L.rows;
 		acts += L.out_n;
 		if ((int64_t)L.out_n > (1 << 20) || tabn > (1 << 26) || acts > (1 << 26)) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: network too large");
 		if (L.out_n > buf[L.dst]) buf[L.dst] = L.out_n;
 		if (wl > p.w_lds) p.w_lds = (int32_t)wl;
-		if (L.k_pad > p.k_lds) p.k_lds = L.k_pad;
+		if (kn > p.k_lds) p.k_lds = kn;
 		h = v[4]; w = v[5]; c = oc;
 		n_conv++;
 	}
@@ -153,23 +175,29 @@ static int parse(edison_ctx *ctx, const uint8_t *b, size_t nb, ed_fnet *f, float
 	memcpy(wh, b + off, (size_t)wfl * 4);
 	for (int i = 0, l = 0; i < nl; i++)
 	{
-		const uint8_t *r = rec0 + (size_t)i * EDF_REC_INTS * 4;
+		const uint8_t *r = rec0 + (size_t)i * ri * 4;
 		if (rd32(r) != EDF_T_CONV) continue;
-		int v[EDF_REC_INTS];
-		for (int j = 0; j < EDF_REC_INTS; j++) v[j] = rd32(r + 4 * j);
+		int v[EDF_REC_INTS] = {0};
+		for (int j = 0; j < ri; j++) v[j] = rd32(r + 4 * j);
 		const ed_fnet_layer_t &L = p.L[l++];
-		const int iw = v[2], ic = v[3], kh = v[7], kw = v[8], sh = v[9], sw = v[10], ph = v[12], pw = v[13], ow = v[5];
+		const int ih = v[1], iw = v[2], ic = v[3], kh = v[7], kw = v[8], sh = v[9], sw = v[10], ph = v[12], pw = v[13], ow = v[5];
 		int32_t *koff = th + L.koff_at, *rowin = th + L.rowin_at;
 		for (int k = 0; k < L.k_pad; k++)
 		{
-			if (k >= kh * kw * ic) { koff[k] = -1; continue; }
+			if (k >= kh * kw * ic) { koff[k] = -1; if (L.pad) koff[L.k_pad + k] = 0; continue; }
 			const int ci = k % ic, t = k / ic, kx = t % kw, ky = t / kw;
 			koff[k] = (ky * iw + kx) * ic + ci;
+			if (L.pad) koff[L.k_pad + k] = ky << 16 | kx;
 		}
+		/* the conv's map, before the pool */
+		const int ch = (ih + v[16] + v[18] - kh) / sh + 1, cw = (iw + v[17] + v[19] - kw) / sw + 1;
 		for (int rr = 0; rr < L.rows; rr++)
 		{
 			const int q = rr / L.P, e = rr % L.P, py = q / ow, px = q % ow, ey = e / pw, ex = e % pw;
-			rowin[rr] = ((py * ph + ey) * sh * iw + (px * pw + ex) * sw) * ic;
+			if (!L.pad) { rowin[rr] = ((py * ph + ey) * sh * iw + (px * pw + ex) * sw) * ic; continue; }
+			const int cy = py * ph + ey - v[20], cx = px * pw + ex - v[21];
+			if (cy < 0 || cy >= ch || cx < 0 || cx >= cw) { rowin[rr] = -1; continue; } /* absent: in the pool's padding */
+			rowin[rr] = (cy * sh - v[16] + ED_FNET_ORIGIN_BIAS) << 16 | (cx * sw - v[17] + ED_FNET_ORIGIN_BIAS);
 		}
 	}
 	*w_out = wh; *nw_out = (size_t)wfl; *tab_out = th; *nt_out = (size_t)tabn;

@@ -1,6 +1,7 @@
 /*
  * fnet.h -- the launch plan of the float32 network kernels (fnet_kernels.hip, fnet_windows_kernels.hip), built by its host side (edison_fnet.hip) from an .ednf
- * blob (edison_amd/cube_import.py). Not part of the public ABI.
+ * blob (edison_amd/cube_import.py: version 1 without pads, version 2 with a conv's and a pool's (top, left, bottom, right) pads in
+ * ints [16..23] of its 24-int records). Not part of the public ABI.
  */
 #ifndef EDISON_FNET_H
 #define EDISON_FNET_H
@@ -12,10 +13,16 @@
 #define ED_FNET_THREADS 512
 #define ED_FNET_MAX_BATCH 16                  /* utterances per workgroup, at most */
 #define ED_FNET_LDS_BYTES (160 * 1024)
+#define ED_FNET_ORIGIN_BIAS 4096              /* a padded record's rowin entry: (y0 + bias) << 16 | (x0 + bias) */
 
 /* One conv record (a dense layer is a conv whose kernel covers its whole input). Output row r of an utterance is element e = r % P of
  * the pool window of pooled position q = r / P (q = y * out_w + x, P = ph * pw): the P rows of a window are adjacent, so they land in
- * one lane's accumulator registers and the pool is a max over registers. */
+ * one lane's accumulator registers and the pool is a max over registers.
+ * A record with a conv or a pool pad (pad = 1) has two more things in its tables. Its rowin entry is the row's
+ * window origin (y0, x0) in input coordinates, packed with ED_FNET_ORIGIN_BIAS because a padded origin may be negative, or -1 for an
+ * absent row: an element of a pool window that lies in the pool's padding, which is never read, written or counted and is -inf in the
+ * window's max. And behind koff[k_pad] lies kyx[k_pad], (ky << 16 | kx) of every k: a tap is read only where (y0 + ky, x0 + kx) is
+ * inside the in_h x in_w image, any other tap is the operand +0.0f. */
 typedef struct {
 	int32_t in_n, out_c, out_n;     /* in_h * in_w * in_c, out channels, out_h * out_w * out_c */
 	int32_t P;                      /* pool window elements: 1, 2 or 4                          */
@@ -25,6 +32,9 @@ typedef struct {
 	int32_t src, dst;               /* LDS activation buffer read / written (0 or 1)            */
 	int32_t koff_at, rowin_at;      /* int32 offsets into tab: koff[k_pad], rowin[rows]          */
 	int32_t acts_at;                /* float offset of this layer's output in a per-layer dump  */
+	int32_t pad;                    /* 1: a padded record (origins in rowin, kyx behind koff)   */
+	int32_t in_h, in_w, in_c;       /* the input image (read by padded records only)            */
+	int32_t live;                   /* rows per utterance that are not absent (rows when pad = 0) */
 	int64_t w_at;                   /* float offset into w: B[k_pad][n_pad], then bias[n_pad]   */
 } ed_fnet_layer_t;
 
@@ -33,7 +43,7 @@ typedef struct {
 	int32_t in_n, n_out;            /* network input / output floats per utterance              */
 	int32_t batch;                  /* utterances per workgroup                                  */
 	int32_t buf_n[2];               /* floats per utterance of LDS activation buffers 0 and 1   */
-	int32_t w_lds, k_lds;           /* largest layer's B + koff in LDS (floats / ints)          */
+	int32_t w_lds, k_lds;           /* largest layer's B + koff (+ kyx) in LDS (floats / ints)  */
 	int32_t acts_n;                 /* floats per utterance of a per-layer dump                 */
 	const float *w;
 	const int32_t *tab;

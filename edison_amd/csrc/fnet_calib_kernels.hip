@@ -12,11 +12,12 @@
  * v runs over the in_n input floats of every utterance, and for a record over acc + bias in f32 -- the kernel's value before ReLU and
  * before the pool -- at rows < M and channels < out_c: the padding of the last M tile and of the last channel tile is not counted.
  * Rows a truncating pool drops are never computed (fnet.h: the rows of a layer are those of its pool windows), so they are not
- * counted either.
+ * counted either. In a padded record the absent elements of a pool window -- those in the pool's padding -- are
+ * not counted: the count is the record's live rows x out_c.
  *
  * Per work item every lane keeps a running maximum in a register and bumps a workgroup histogram in LDS (an LDS add without return).
  * Per layer and workgroup: the waves reduce their maxima (shuffles, then one LDS atomicMax per wave), then one global atomicMax, one
- * global add of the count -- M x out_c, known without counting -- and a flush of the non-zero histogram cells into the 64-bit
+ * global add of the count -- the tile's real rows x out_c, known without counting -- and a flush of the non-zero histogram cells into the 64-bit
  * device counters. Integer atomics only, as eval_kernels.hip and for its reason: the counters do not depend on the launch shape or on
  * the order the atomics arrive in. No scratch memory; no logits, no softmax.
  *
@@ -43,8 +44,9 @@ __device__ __forceinline__ void edfc_see(float v, uint32_t &amax, uint32_t *__re
 }
 
 /* edf_tile with the statistic in its epilogue: 16 output rows (M tile mt) x NT tiles of 16 channels starting at n0. The MFMA loop and
- * the order bias, ReLU, pool are edf_tile's; nothing is dumped. */
-template <int NT>
+ * the order bias, ReLU, pool are edf_tile's; nothing is dumped. PAD = true is a padded record (fnet.h): edf_tile's gather, and an absent
+ * row -- an element of a pool window in the pool's padding -- is not counted and is -inf in the window's max. */
+template <int NT, bool PAD = false>
 __device__ __forceinline__ void edfc_tile(const ed_fnet_layer_t &L, const float *__restrict__ src, int src_n, float *__restrict__ dst, int dst_n,
                                           const float *__restrict__ wl, const int32_t *__restrict__ kl, const int32_t *__restrict__ rowin,
                                           const float *__restrict__ bias, int M, int mt, int n0, int lane, uint32_t &amax, uint32_t *__restrict__ s_hist)
@@ -52,7 +54,9 @@ __device__ __forceinline__ void edfc_tile(const ed_fnet_layer_t &L, const float 
 	const int r = lane & 15, kq = lane >> 4;
 	const int m = mt * 16 + r;
 	int base = 0;
-	if (m < M)
+	[[maybe_unused]] int y0 = 0, x0 = 0;
+	if constexpr (PAD) edf_pad_row(L, rowin, src_n, M, m, base, y0, x0);
+	else if (m < M)
 	{
 		const int u = m / L.rows;
 		base = u * src_n + rowin[m - u * L.rows];
@@ -65,7 +69,9 @@ __device__ __forceinline__ void edfc_tile(const ed_fnet_layer_t &L, const float 
 	for (int k0 = 0; k0 < L.k_pad; k0 += 4)
 	{
 		const int ko = kl[k0 + kq];
-		const float a = ko >= 0 ? src[base + ko] : 0.0f;
+		float a;
+		if constexpr (PAD) a = edf_pad_tap(L, src, base, y0, x0, ko, kl[L.k_pad + k0 + kq]);
+		else a = ko >= 0 ? src[base + ko] : 0.0f;
 #pragma unroll
 		for (int j = 0; j < NT; j++) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wp[j * 16], acc[j], 0, 0, 0);
 		wp += 4 * L.n_pad;
@@ -73,6 +79,8 @@ __device__ __forceinline__ void edfc_tile(const ed_fnet_layer_t &L, const float 
 	/* D: lane holds rows 4 kq + i (i = 0..3) of channel n0 + 16 j + r */
 	const int P = L.P;
 	const int m0 = mt * 16 + 4 * kq;
+	[[maybe_unused]] bool live[4];
+	if constexpr (PAD) edf_pad_live(L, rowin, M, m0, live);
 #pragma unroll
 	for (int j = 0; j < NT; j++)
 	{
@@ -84,8 +92,13 @@ __device__ __forceinline__ void edfc_tile(const ed_fnet_layer_t &L, const float 
 		for (int i = 0; i < 4; i++)
 		{
 			v[i] = acc[j][i] + b;
-			if (m0 + i < M) edfc_see(v[i], amax, s_hist); /* before ReLU, before the pool; a padding row is not counted */
+			if constexpr (PAD)
+			{
+				if (live[i]) edfc_see(v[i], amax, s_hist); /* neither a padding row nor an absent one */
+			}
+			else if (m0 + i < M) edfc_see(v[i], amax, s_hist); /* before ReLU, before the pool; a padding row is not counted */
 			if (L.relu) v[i] = fmaxf(v[i], 0.0f);
+			if constexpr (PAD) { if (!live[i]) v[i] = -INFINITY; }
 		}
 		for (int g = 0; g < 4; g += P)
 		{
@@ -178,7 +191,8 @@ __global__ __launch_bounds__(ED_FNET_THREADS) void ed_fnet_calib_kernel(ed_fnet_
 			const float4 *g4 = (const float4 *)gw;
 			float4 *l4 = (float4 *)wl;
 			for (int i = tid; i < nw / 4; i += ED_FNET_THREADS) l4[i] = g4[i];
-			for (int i = tid; i < L.k_pad; i += ED_FNET_THREADS) kl[i] = p.tab[L.koff_at + i];
+			const int nk = L.pad ? 2 * L.k_pad : L.k_pad; /* a padded record: kyx behind koff */
+			for (int i = tid; i < nk; i += ED_FNET_THREADS) kl[i] = p.tab[L.koff_at + i];
 		}
 		__syncthreads();
 		const float *src = buf[L.src];
@@ -193,14 +207,21 @@ __global__ __launch_bounds__(ED_FNET_THREADS) void ed_fnet_calib_kernel(ed_fnet_
 		{
 			const int mt = item / NG, g = item - mt * NG;
 			const int n0 = g * 64, nt = NT - 4 * g < 4 ? NT - 4 * g : 4;
-			if (nt == 4) edfc_tile<4>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, amax, s_stat);
+			if (L.pad)
+			{
+				if (nt == 4) edfc_tile<4, true>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, amax, s_stat);
+				else if (nt == 3) edfc_tile<3, true>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, amax, s_stat);
+				else if (nt == 2) edfc_tile<2, true>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, amax, s_stat);
+				else edfc_tile<1, true>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, amax, s_stat);
+			}
+			else if (nt == 4) edfc_tile<4>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, amax, s_stat);
 			else if (nt == 3) edfc_tile<3>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, amax, s_stat);
 			else if (nt == 2) edfc_tile<2>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, amax, s_stat);
 			else edfc_tile<1>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, amax, s_stat);
 		}
 		edfc_wave_max(amax, lane, s_stat);
 		__syncthreads();
-		edfc_flush(l + 1, (unsigned long long)M * (unsigned long long)L.out_c, s_stat, counters, tid);
+		edfc_flush(l + 1, (unsigned long long)nu * (unsigned long long)L.live * (unsigned long long)L.out_c, s_stat, counters, tid);
 	}
 }
 

@@ -3,7 +3,7 @@
  * EDF_NETWORK_BODY, shared by ed_fnet_kernel (fnet_kernels.hip: utterances one stride apart) and ed_fnet_windows_kernel
  * (fnet_windows_kernels.hip: the windows of a bank of microphones, two strides). The tiling, the k-ordered fmaf chain, the epilogue, the
  * softmax and the LDS plan exist once, here; a kernel differs only in how the utterances of its tile find their input.
- * DESIGN.md sections 14 and 15a. Not part of the public ABI.
+ * DESIGN.md sections 14, 14b (padded records: PAD = true) and 15a. Not part of the public ABI.
  */
 #ifndef EDISON_FNET_DEVICE_H
 #define EDISON_FNET_DEVICE_H
@@ -15,8 +15,41 @@
 
 typedef float ed_f4 __attribute__((ext_vector_type(4)));
 
-/* One work item: 16 output rows (M tile mt) x NT tiles of 16 channels starting at n0. */
-template <int NT>
+/* A padded record's row m of the tile (fnet.h): its window origin and the offset of that origin in src. A row beyond M and an absent
+ * row get y0 = in_h, which puts every tap outside the image: the lane reads nothing and multiplies zeros. */
+__device__ __forceinline__ void edf_pad_row(const ed_fnet_layer_t &L, const int32_t *__restrict__ rowin, int src_n, int M, int m, int &base, int &y0, int &x0)
+{
+	base = 0; y0 = L.in_h; x0 = 0;
+	if (m >= M) return;
+	const int u = m / L.rows;
+	const int32_t o = rowin[m - u * L.rows];
+	if (o < 0) return;
+	y0 = (o >> 16) - ED_FNET_ORIGIN_BIAS;
+	x0 = (o & 0xffff) - ED_FNET_ORIGIN_BIAS;
+	base = u * src_n + (y0 * L.in_w + x0) * L.in_c;
+}
+
+/* A padded record's A operand at k: the tap (y0 + ky, x0 + kx) where it lies inside the image, else +0.0f (the K padding has ko < 0). */
+__device__ __forceinline__ float edf_pad_tap(const ed_fnet_layer_t &L, const float *__restrict__ src, int base, int y0, int x0, int32_t ko, int32_t kyx)
+{
+	const bool in = ko >= 0 && (unsigned)(y0 + (kyx >> 16)) < (unsigned)L.in_h && (unsigned)(x0 + (kyx & 0xffff)) < (unsigned)L.in_w;
+	return in ? src[base + ko] : 0.0f;
+}
+
+/* Which of the lane's four output rows m0 .. m0 + 3 of a padded record are real: below M and not absent. */
+__device__ __forceinline__ void edf_pad_live(const ed_fnet_layer_t &L, const int32_t *__restrict__ rowin, int M, int m0, bool live[4])
+{
+#pragma unroll
+	for (int i = 0; i < 4; i++)
+	{
+		const int m = m0 + i;
+		live[i] = m < M && rowin[m - m / L.rows * L.rows] >= 0;
+	}
+}
+
+/* One work item: 16 output rows (M tile mt) x NT tiles of 16 channels starting at n0. PAD = false is a record without pads; PAD = true
+ * reads the record's origins and kyx (kl + k_pad), gathers through edf_pad_tap and leaves absent rows out of the pool's max. */
+template <int NT, bool PAD = false>
 __device__ __forceinline__ void edf_tile(const ed_fnet_layer_t &L, const float *__restrict__ src, int src_n, float *__restrict__ dst, int dst_n,
                                          const float *__restrict__ wl, const int32_t *__restrict__ kl, const int32_t *__restrict__ rowin,
                                          const float *__restrict__ bias, int M, int mt, int n0, int lane, float *__restrict__ acts,
@@ -25,7 +58,9 @@ __device__ __forceinline__ void edf_tile(const ed_fnet_layer_t &L, const float *
 	const int r = lane & 15, kq = lane >> 4;
 	const int m = mt * 16 + r;
 	int base = 0;
-	if (m < M)
+	[[maybe_unused]] int y0 = 0, x0 = 0;
+	if constexpr (PAD) edf_pad_row(L, rowin, src_n, M, m, base, y0, x0);
+	else if (m < M)
 	{
 		const int u = m / L.rows;
 		base = u * src_n + rowin[m - u * L.rows];
@@ -38,7 +73,9 @@ __device__ __forceinline__ void edf_tile(const ed_fnet_layer_t &L, const float *
 	for (int k0 = 0; k0 < L.k_pad; k0 += 4)
 	{
 		const int ko = kl[k0 + kq];
-		const float a = ko >= 0 ? src[base + ko] : 0.0f;
+		float a;
+		if constexpr (PAD) a = edf_pad_tap(L, src, base, y0, x0, ko, kl[L.k_pad + k0 + kq]);
+		else a = ko >= 0 ? src[base + ko] : 0.0f;
 #pragma unroll
 		for (int j = 0; j < NT; j++) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wp[j * 16], acc[j], 0, 0, 0);
 		wp += 4 * L.n_pad;
@@ -46,6 +83,8 @@ __device__ __forceinline__ void edf_tile(const ed_fnet_layer_t &L, const float *
 	/* D: lane holds rows 4 kq + i (i = 0..3) of channel n0 + 16 j + r */
 	const int P = L.P;
 	const int m0 = mt * 16 + 4 * kq;
+	[[maybe_unused]] bool live[4];
+	if constexpr (PAD) edf_pad_live(L, rowin, M, m0, live);
 #pragma unroll
 	for (int j = 0; j < NT; j++)
 	{
@@ -58,6 +97,7 @@ __device__ __forceinline__ void edf_tile(const ed_fnet_layer_t &L, const float *
 		{
 			v[i] = acc[j][i] + b;
 			if (L.relu) v[i] = fmaxf(v[i], 0.0f);
+			if constexpr (PAD) { if (!live[i]) v[i] = -INFINITY; } /* absent: the max's identity; its window has a real element */
 		}
 		for (int g = 0; g < 4; g += P)
 		{
@@ -103,7 +143,8 @@ __device__ __forceinline__ void edf_tile(const ed_fnet_layer_t &L, const float *
 			const float4 *g4 = (const float4 *)gw;                                                                                         \
 			float4 *l4 = (float4 *)wl;                                                                                                     \
 			for (int i = tid; i < nw / 4; i += ED_FNET_THREADS) l4[i] = g4[i];                                                             \
-			for (int i = tid; i < L.k_pad; i += ED_FNET_THREADS) kl[i] = p.tab[L.koff_at + i];                                             \
+			const int nk = L.pad ? 2 * L.k_pad : L.k_pad; /* a padded record: kyx behind koff */                                           \
+			for (int i = tid; i < nk; i += ED_FNET_THREADS) kl[i] = p.tab[L.koff_at + i];                                                  \
 		}                                                                                                                                  \
 		__syncthreads();                                                                                                                   \
 		const float *src = buf[L.src];                                                                                                     \
@@ -117,7 +158,14 @@ __device__ __forceinline__ void edf_tile(const ed_fnet_layer_t &L, const float *
 		{                                                                                                                                  \
 			const int mt = item / NG, g = item - mt * NG;                                                                                  \
 			const int n0 = g * 64, nt = NT - 4 * g < 4 ? NT - 4 * g : 4;                                                                   \
-			if (nt == 4) edf_tile<4>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);                 \
+			if (L.pad)                                                                                                                     \
+			{                                                                                                                              \
+				if (nt == 4) edf_tile<4, true>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);       \
+				else if (nt == 3) edf_tile<3, true>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);  \
+				else if (nt == 2) edf_tile<2, true>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);  \
+				else edf_tile<1, true>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);               \
+			}                                                                                                                              \
+			else if (nt == 4) edf_tile<4>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);            \
 			else if (nt == 3) edf_tile<3>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);            \
 			else if (nt == 2) edf_tile<2>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);            \
 			else edf_tile<1>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);                         \

@@ -13,6 +13,9 @@
  * tests/fnet_sweep.py). The epilogue adds the bias, applies ReLU and max-pools over the
  * P adjacent rows of each window (all in one lane's accumulator registers), then writes the pooled value to the other buffer. After
  * the last layer, one thread per utterance computes softmax = exp(z - max) / sum and the first maximum.
+ * A record with a conv or a pool pad ('same' layers, .ednf version 2) takes the tile function's PAD = true
+ * instantiation: rowin holds the window's origin, a second k table (ky, kx), and a tap outside the image is the operand +0.0f of the
+ * same chain; an element of a pool window outside the conv's map is -inf in the max. Records without pads run PAD = false.
  * No scratch memory: everything is registers and LDS.
  */
 #include <hip/hip_runtime.h>

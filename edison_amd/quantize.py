@@ -15,6 +15,11 @@ at most saturate x count values at or above 2^k (counted by exponent: sum(hist[e
 A layer reads its predecessor's output format (ReLU, MaxPool and Flatten inherit it), and the shifts are the macros of the
 reference's header (weights.h:72-105): OUTPUT_RSHIFT = in_dec + w_dec - out_dec, BIAS_LSHIFT = in_dec + w_dec - b_dec. The bias dec is
 clamped to in_dec + w_dec so that its shift is not negative; an all-zero bias gets exactly that. An all-zero weight tensor gets dec 7.
+
+Padded records (``.ednf`` version 2). NNoM has one flag per layer, PADDING_SAME, and NNoM 0.3.0 computes with
+it: output ceil(in / stride) and a leading pad of (k - 1) // 2 on both axes, taps outside the image zero (a max pool: absent). A padded
+conv or pool maps to that flag only where the record computes the same thing on both axes at once (``nnom_same``); anything else
+raises a QuantizeError naming the layer and both pad sets: NNoM cannot express it.
 """
 import math
 
@@ -91,13 +96,28 @@ def _act_dec(name, absmax_bits, hist, count, method, saturate):
 
 
 # ---- the graph --------------------------------------------------------------------------------------------------------------------
+def nnom_same(name, what, in_hw, k, s, pads, out_hw):
+    """0 for a window without pads (PADDING_VALID), 1 where NNoM 0.3.0's PADDING_SAME computes what pads = (top, left, bottom, right)
+    do: on both axes out = ceil(in / s) and the leading pad is (k - 1) // 2. A QuantizeError naming the layer otherwise."""
+    if not any(pads):
+        return 0
+    nnom = tuple((k[a] - 1) // 2 for a in (0, 1))
+    ok = all(out_hw[a] == -(-in_hw[a] // s[a]) and pads[a] == nnom[a] for a in (0, 1))
+    if not ok:
+        raise QuantizeError("%s: its %s pads (top, left, bottom, right) = %s over %dx%d, window %dx%d, stride %dx%d give %dx%d; NNoM's PADDING_SAME "
+                            "pads (top, left) = %s and gives %dx%d: NNoM cannot express this layer"
+                            % (name, what, tuple(pads), in_hw[0], in_hw[1], k[0], k[1], s[0], s[1], out_hw[0], out_hw[1], nnom,
+                               -(-in_hw[0] // s[0]), -(-in_hw[1] // s[1])))
+    return 1
+
+
 def layer_names(model):
     """NNoM's names for the float network's conv records: conv2d_i, or dense_j for a record whose kernel covers its whole input."""
     names, nc, nd = [], 0, 0
     for L in model["layers"]:
         if L["type"] != cube_import.T_CONV:
             continue
-        if tuple(L["k"]) == tuple(L["inp"][:2]):
+        if tuple(L["k"]) == tuple(L["inp"][:2]) and not any(L.get("cpad", ())):
             nd += 1
             names.append("dense_%d" % nd)
         else:
@@ -157,13 +177,18 @@ def quantize(model, stats, method="max_min", saturate=0.0, scale=1.0):
         bq, b_rms = quantize_tensor(b, b_dec)
         oc, (kh, kw), (sh, sw), (ph, pw) = L["out"][2], L["k"], L["s"], L["p"]
         dense = name.startswith("dense")
+        cpad, ppad = tuple(L.get("cpad", (0, 0, 0, 0))), tuple(L.get("ppad", (0, 0, 0, 0)))
+        ih, iw = L["inp"][:2]
+        ch, cw = (ih + cpad[0] + cpad[2] - kh) // sh + 1, (iw + cpad[1] + cpad[3] - kw) // sw + 1      # the conv's map, before the pool
+        conv_same = nnom_same(name, "conv", (ih, iw), (kh, kw), (sh, sw), cpad, (ch, cw))
+        pool_same = nnom_same(name, "pool", (ch, cw), (ph, pw), (ph, pw), ppad, L["out"][:2])
         if dense:
             graph.append(dict(type=nnom_import.T_DENSE, out=oc, w=wq.reshape(oc, -1), b=bq, relu=int(L["relu"]), w_dec=w_dec, b_dec=b_dec, out_dec=out_dec))
         else:
-            graph.append(dict(type=nnom_import.T_CONV, out_ch=oc, kh=kh, kw=kw, sh=sh, sw=sw, same=0, w=wq.reshape(-1), b=bq, relu=int(L["relu"]),
+            graph.append(dict(type=nnom_import.T_CONV, out_ch=oc, kh=kh, kw=kw, sh=sh, sw=sw, same=conv_same, w=wq.reshape(-1), b=bq, relu=int(L["relu"]),
                               w_dec=w_dec, b_dec=b_dec, out_dec=out_dec))
             if (ph, pw) != (1, 1):
-                graph.append(dict(type=nnom_import.T_POOL, kh=ph, kw=pw, sh=ph, sw=pw, same=0))
+                graph.append(dict(type=nnom_import.T_POOL, kh=ph, kw=pw, sh=ph, sw=pw, same=pool_same))
         rep_layers.append(dict(name=name, kind="dense" if dense else "conv2d", absmax=_f32_from_bits(absmax[i + 1]), w_dec=w_dec, b_dec=b_dec,
                                b_clamped=b_dec != b_free, out_dec=out_dec, bias_lshift=bl, out_rshift=rs, w_rms=w_rms, b_rms=b_rms))
         dec = out_dec

@@ -365,7 +365,11 @@ int edison_mfcc_geom_batch_dev(edison_ctx *ctx, const edison_kws_geom *g, const 
 /*
  * Float32 X-CUBE-AI networks: the reference's default network type (firmware/src/ai/ai.h NET_TYPE_CUBE), imported from the generated
  * <net>.c + <net>_data.c by edison_amd/cube_import.py into an .ednf blob. Accepted: conv2d / conv2d_nl_pool (groups 1, any stride,
- * no padding, ReLU or none, max pool of 1, 2 or 4 elements), dense, ReLU, a final softmax; activations HWC. The blob's layer list,
+ * ReLU or none, max pool of 1, 2 or 4 elements with stride = size), dense, ReLU, a final softmax; activations HWC. An .ednf is version
+ * 1 (records of int32[16], no pads) or version 2 (records of int32[24]: [16..19] the conv's pads top, left, bottom, right, [20..23]
+ * the pool's): out = (in + before + after - k) / stride + 1, a tap outside the image is the operand +0.0f of the chain below, an
+ * element of a pool window outside the conv's map takes no part in the max; a pad as large as its window on that axis is
+ * EDISON_E_NO_IMPL. The blob's layer list,
  * shapes and weights are checked at load (EDISON_E_SIZE: malformed; EDISON_E_NO_IMPL: a network this path does not run, e.g. one whose
  * activations and largest layer do not fit the LDS). A load replaces the context's previous float network (synchronising the stream
  * once); a refused load leaves the previous network loaded and answering as before. The int8 NNoM model (edison_model_load) is
