@@ -57,6 +57,12 @@ class FcalInfo(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ("n_stats", "in_n", "batch", "lds_bytes")]
 
 
+class FtrainInfo(ctypes.Structure):
+    """edison_ftrain_info_t"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("n_layers", "in_n", "n_out", "batch", "lds_bytes", "grid")] + \
+               [(k, c_int64) for k in ("w_floats", "steps", "ignored")]
+
+
 class StreamGeomOpts(ctypes.Structure):
     """edison_stream_geom_opts"""
     _fields_ = [("chunk_frames", ctypes.c_int32), ("filter", ctypes.c_int32), ("fsm", ctypes.c_int32), ("filter_alpha", c_double),
@@ -295,6 +301,20 @@ SIGNATURES = {
     "edison_fcal_add_dev": (c_int, [c_void_p, c_void_p, c_int64]),
     "edison_fcal_add": (c_int, [c_void_p, c_void_p, c_int64]),
     "edison_fcal_result": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_ftrain_create": (c_int, [c_void_p, ctypes.POINTER(c_void_p)]),
+    "edison_ftrain_destroy": (None, [c_void_p]),
+    "edison_ftrain_info": (c_int, [c_void_p, ctypes.POINTER(FtrainInfo)]),
+    "edison_ftrain_layout": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                     ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "edison_ftrain_grad_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "edison_ftrain_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "edison_ftrain_grad_get": (c_int, [c_void_p, c_void_p]),
+    "edison_ftrain_logits_get": (c_int, [c_void_p, c_void_p]),
+    "edison_ftrain_step": (c_int, [c_void_p, c_double]),
+    "edison_ftrain_set_opt": (c_int, [c_void_p, c_int, c_double, c_double, c_double]),
+    "edison_ftrain_weights_get": (c_int, [c_void_p, c_void_p]),
+    "edison_ftrain_weights_set": (c_int, [c_void_p, c_void_p]),
+    "edison_ftrain_reset": (c_int, [c_void_p]),
     "edison_eval_default_opts": (None, [ctypes.POINTER(EvalOpts)]),
     "edison_eval_create": (c_int, [c_void_p, ctypes.POINTER(EvalOpts), ctypes.POINTER(c_void_p)]),
     "edison_eval_destroy": (None, [c_void_p]),

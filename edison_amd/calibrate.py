@@ -86,6 +86,7 @@ def quantize_audio(ctx, audio, geometry=None, q15=False, chunk=16384, method="ma
     from .kws.geometry import KwsGeometry
     if ctx._fnet_blob is None:
         raise ValueError("no float network loaded (fnet_load)")
+    ctx._fnet_refresh()                  # a trainer may have stepped the device weights past the blob
     g = geometry if geometry is not None else KwsGeometry.from_config(net_input_scale=cfg.net_input_scale)
     chunk = int(chunk)
     if chunk < 1:

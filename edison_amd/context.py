@@ -34,6 +34,7 @@ class Context:
         self._h = h
         self.device = int(device)
         self._fnet_blob = None
+        self._fnet_trainer = None   # a train.Trainer whose steps _fnet_blob does not hold yet
         if model_path is not None:
             self.load_model(model_path)
 
@@ -44,6 +45,8 @@ class Context:
 
     def close(self):
         if getattr(self, "_h", None):
+            if getattr(self, "_fnet_trainer", None) is not None:   # it refers to this context: closed before the context goes
+                self._fnet_trainer.close()
             self._L.edison_shutdown(self._h)
             self._h = None
 
@@ -341,6 +344,7 @@ class Context:
             self._check(self._L.edison_fnet_load_mem(self._h, buf, len(src)))
         else:
             self._check(self._L.edison_fnet_load(self._h, str(src).encode()))
+        self._fnet_trainer = None
         self.fnet_keywords = self._ednf_keywords(src)
         self._fnet_blob = bytes(src) if isinstance(src, (bytes, bytearray)) else open(str(src), "rb").read()   # quantize() reads the weights
 
@@ -560,6 +564,18 @@ class Context:
         load_model_bytes(blob) runs it, report["net_input_scale"] is the net_input_scale its kws_geom geometry needs."""
         from . import calibrate
         return calibrate.quantize_audio(self, audio, geometry=geometry, q15=q15, chunk=chunk, method=method, saturate=saturate, **kw)
+
+    # ------------------------------------------------------------------ training the float network (edison_ftrain_*, train.py)
+    def trainer(self):
+        """A train.Trainer on this context, bound to the loaded float network (no conv or pool pads): grad / grad_t, step, weights,
+        set_weights, model, fit (edison_ftrain_create). Its steps change the loaded network's device weights in place."""
+        from . import train
+        return train.Trainer(self)
+
+    def _fnet_refresh(self):
+        """Bring _fnet_blob up to the weights a trainer has stepped the loaded network to (quantize() reads the weights from it)."""
+        if self._fnet_trainer is not None:
+            self._fnet_trainer.export()
 
     # ------------------------------------------------------------------ multi-GPU (edison_dist_*: RCCL behind the C-ABI)
     def dist_init(self, id_bytes, rank, world_size):

@@ -1,0 +1,421 @@
+/*
+ * fnet_grad_kernels.hip -- training the loaded float32 network (edison_ftrain.hip, edison_amd/train.py): the
+ * gradient of the batch-mean cross entropy with respect to every weight and bias, and the optimiser step. Records without pads only.
+ *
+ * ed_ftrain_grad_kernel. A fixed grid of workgroups; workgroup g takes the tiles of utterances g, g + grid, g + 2 grid, ... in that
+ * order, each through a forward half and a backward half, and adds what the tile gives into its own gradient slab (the first tile
+ * stores, so a slab needs no zeroing; its padding entries are never written and stay the +0.0f they were allocated with).
+ * ed_ftrain_reduce_kernel then sums the slabs in index order. No float atomic anywhere: every slab element has one owner lane, and
+ * the order of every sum is fixed by (n, batch, grid), so a call repeated gives the same bits.
+ *
+ *   forward   ed_fnet_kernel's (fnet_device.h): the same LDS plan, the same tiling and edf_tile's k-ordered MFMA loop and epilogue
+ *             order in edg_tile, so the logits are edison_fnet_batch's bit for bit. edg_tile also writes every pooled output to the
+ *             workgroup's activation store in global memory (the A operand of dW) and beside it one mask byte: which element of the
+ *             pool window was the first maximum, and whether its gradient passes (no ReLU, or a pre-activation > 0).
+ *   loss      one thread per utterance: loss = log sum exp(z - max) + max - z[y], dz = (softmax(z) - onehot(y)) / n.
+ *   backward  per record, last to first, with LDS reused (the forward half is done with it):
+ *     dY   [rows of the tile][n_pad] in LDS, from the gradient of the pooled outputs and the mask bytes: the window's winner gets it,
+ *          every other element, every padding channel and every row beyond the tile is +0.0f. No second comparison.
+ *     dW   [k][c] = sum_r A[r][k] dY[r][c]: 16 k x 16 c tiles on v_mfma_f32_16x16x4_f32, four rows r per instruction in ascending
+ *          order; A is gathered through the plan's own rowin / koff. One more tile row with A = 1 gives the bias gradient.
+ *     dX   of the record's input (not for record 0) in gather form: [position][ci] = sum_t sum_c dY[inv[position][t]][c] W[t in_c + ci][c]
+ *          on the same instruction, through the inverse origin table of fnet_train.h; a position nothing reads gets +0.0f.
+ *
+ * ed_ftrain_step_kernel: Adam as Keras states it, or plain SGD, elementwise over the packed array.
+ */
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "edison_launch.h"
+#include "fnet.h"
+#include "fnet_device.h"
+#include "fnet_train.h"
+
+/* edf_tile (fnet_device.h, PAD = false) with the training epilogue: the MFMA loop and the order bias, ReLU, pool are edf_tile's; every
+ * pooled output also goes to acts (this workgroup's store, utterance-major) with its mask byte. */
+template <int NT>
+__device__ __forceinline__ void edg_tile(const ed_fnet_layer_t &L, const float *__restrict__ src, int src_n, float *__restrict__ dst, int dst_n,
+                                         const float *__restrict__ wl, const int32_t *__restrict__ kl, const int32_t *__restrict__ rowin,
+                                         const float *__restrict__ bias, int M, int mt, int n0, int lane, float *__restrict__ acts,
+                                         uint8_t *__restrict__ mask, int acts_n)
+{
+	const int r = lane & 15, kq = lane >> 4;
+	const int m = mt * 16 + r;
+	int base = 0;
+	if (m < M)
+	{
+		const int u = m / L.rows;
+		base = u * src_n + rowin[m - u * L.rows];
+	}
+	ed_f4 acc[NT];
+#pragma unroll
+	for (int j = 0; j < NT; j++) acc[j] = (ed_f4){0.0f, 0.0f, 0.0f, 0.0f};
+	const float *wp = wl + kq * L.n_pad + n0 + r;
+#pragma unroll 4
+	for (int k0 = 0; k0 < L.k_pad; k0 += 4)
+	{
+		const int ko = kl[k0 + kq];
+		const float a = ko >= 0 ? src[base + ko] : 0.0f;
+#pragma unroll
+		for (int j = 0; j < NT; j++) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wp[j * 16], acc[j], 0, 0, 0);
+		wp += 4 * L.n_pad;
+	}
+	/* D: lane holds rows 4 kq + i (i = 0..3) of channel n0 + 16 j + r */
+	const int P = L.P;
+	const int m0 = mt * 16 + 4 * kq;
+#pragma unroll
+	for (int j = 0; j < NT; j++)
+	{
+		const int n = n0 + 16 * j + r;
+		if (n >= L.out_c) continue;
+		const float b = bias[n];
+		float v[4];
+#pragma unroll
+		for (int i = 0; i < 4; i++)
+		{
+			v[i] = acc[j][i] + b;
+			if (L.relu) v[i] = fmaxf(v[i], 0.0f);
+		}
+		/* one pooled output: the window's maximum x at rows mg .., its first maximum e in element order; under ReLU a maximum of 0 is a
+		 * pre-activation <= 0 and passes nothing */
+		auto emit = [&](int mg, float x, int e) {
+			if (mg >= M) return;
+			const int pass = !L.relu || x > 0.0f ? EDFT_PASS : 0;
+			const int u = mg / L.rows, q = (mg - u * L.rows) / P;
+			dst[u * dst_n + q * L.out_c + n] = x;
+			const int o = u * acts_n + L.acts_at + q * L.out_c + n;
+			acts[o] = x;
+			mask[o] = (uint8_t)(e | pass);
+		};
+		if (P == 1)
+		{
+#pragma unroll
+			for (int i = 0; i < 4; i++) emit(m0 + i, v[i], 0);
+		}
+		else if (P == 2)
+		{
+#pragma unroll
+			for (int g = 0; g < 4; g += 2)
+			{
+				const float x = fmaxf(v[g], v[g + 1]);
+				emit(m0 + g, x, v[g] == x ? 0 : 1);
+			}
+		}
+		else
+		{
+			const float x = fmaxf(fmaxf(fmaxf(v[0], v[1]), v[2]), v[3]);
+			emit(m0, x, v[0] == x ? 0 : v[1] == x ? 1 : v[2] == x ? 2 : 3);
+		}
+	}
+}
+
+/* dW of 16 k rows (k tile kt; kt == KT is the bias row: A = 1 in row 0) x NT tiles of 16 channels from n0, summed over the tile's M rows
+ * four at a time in ascending order (rows beyond M multiply zeros), into the workgroup's slab. src: the record's input, utterance u at src + u * src_n. */
+template <int NT>
+__device__ __forceinline__ void edg_dw_tile(const ed_fnet_layer_t &L, int K, const float *__restrict__ src, const int32_t *__restrict__ koff,
+                                            const float *__restrict__ dy, const int32_t *__restrict__ rb, int M, int kt, int KT, int n0, int lane,
+                                            float *__restrict__ slab, bool first)
+{
+	const int r = lane & 15, kq = lane >> 4;
+	const bool is_bias = kt == KT;
+	const int k = kt * 16 + r;
+	const int ko = !is_bias && k < K ? koff[k] : -1;
+	ed_f4 acc[NT];
+#pragma unroll
+	for (int j = 0; j < NT; j++) acc[j] = (ed_f4){0.0f, 0.0f, 0.0f, 0.0f};
+	const float *dp = dy + kq * L.n_pad + n0 + r;
+	/* 16 rows a turn, their operands loaded before the four MFMA steps that take them in order: dY is +0.0f up to the next multiple of 16 */
+	for (int m0 = 0; m0 < M; m0 += 16)
+	{
+		float a[4], b[4][NT];
+#pragma unroll
+		for (int s = 0; s < 4; s++)
+		{
+			const int m = m0 + 4 * s + kq;
+			if (is_bias) a[s] = r == 0 ? 1.0f : 0.0f;
+			else a[s] = ko >= 0 && m < M ? src[rb[m] + ko] : 0.0f;
+#pragma unroll
+			for (int j = 0; j < NT; j++) b[s][j] = dp[4 * s * L.n_pad + j * 16];
+		}
+#pragma unroll
+		for (int s = 0; s < 4; s++)
+#pragma unroll
+			for (int j = 0; j < NT; j++) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b[s][j], acc[j], 0, 0, 0);
+		dp += 16 * L.n_pad;
+	}
+	/* D: lane holds k rows kt * 16 + 4 kq + i of channel n0 + 16 j + r */
+	float *gw = slab + L.w_at;
+#pragma unroll
+	for (int j = 0; j < NT; j++)
+	{
+		const int n = n0 + 16 * j + r;
+		if (n >= L.out_c) continue; /* a padding channel stays +0.0f */
+		if (is_bias)
+		{
+			if (kq == 0)
+			{
+				float *o = gw + (int64_t)L.k_pad * L.n_pad + n;
+				*o = first ? acc[j][0] : *o + acc[j][0];
+			}
+			continue;
+		}
+#pragma unroll
+		for (int i = 0; i < 4; i++)
+		{
+			const int kk = kt * 16 + 4 * kq + i;
+			if (kk >= K) continue; /* a padding k row stays +0.0f */
+			float *o = gw + (int64_t)kk * L.n_pad + n;
+			*o = first ? acc[j][i] : *o + acc[j][i];
+		}
+	}
+}
+
+/* dX of 16 (utterance, position) rows (tile mt of MX = nu * np) x 16 input channels from c0, into dprev: utterance u's gradient of the
+ * record's input at dprev + u * acts_n, HWC. Taps in ascending order, channels four at a time; a tap no row of the tile has is skipped
+ * (it would add +0.0f to every sum). w: the record's B[k_pad][n_pad] in global memory. */
+__device__ __forceinline__ void edg_dx_tile(const ed_fnet_layer_t &L, const ed_ftrain_layer_t &G, const int32_t *__restrict__ inv,
+                                            const float *__restrict__ w, const float *__restrict__ dy, int MX, int mt, int c0, int lane,
+                                            float *__restrict__ dprev, int acts_n)
+{
+	const int r = lane & 15, kq = lane >> 4;
+	const int m = mt * 16 + r;
+	const bool real = m < MX;
+	const int u = real ? m / G.np : 0, pos = real ? m - u * G.np : 0;
+	const int ci = c0 + r;
+	const int oc4 = (L.out_c + 3) & ~3;
+	ed_f4 acc = (ed_f4){0.0f, 0.0f, 0.0f, 0.0f};
+	for (int t = 0; t < G.T; t++)
+	{
+		const int row = real ? inv[pos * G.T + t] : -1;
+		if (__ballot(row >= 0) == 0) continue;
+		const float *dr = dy + (row >= 0 ? (u * L.rows + row) * L.n_pad : 0);
+		const float *wr = w + (int64_t)(t * L.in_c + (ci < L.in_c ? ci : 0)) * L.n_pad;
+		for (int n0 = 0; n0 < oc4; n0 += 4)
+		{
+			const int n = n0 + kq;
+			const float a = row >= 0 ? dr[n] : 0.0f;
+			const float b = ci < L.in_c && n < L.out_c ? wr[n] : 0.0f; /* the blob's padding channels are never read */
+			acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
+		}
+	}
+	if (ci >= L.in_c) return;
+#pragma unroll
+	for (int i = 0; i < 4; i++)
+	{
+		const int mm = mt * 16 + 4 * kq + i;
+		if (mm >= MX) break;
+		const int uu = mm / G.np, pp = mm - uu * G.np;
+		dprev[uu * acts_n + pp * L.in_c + ci] = acc[i];
+	}
+}
+
+__global__ __launch_bounds__(ED_FNET_THREADS) void ed_ftrain_grad_kernel(const ed_ftrain_plan_t *tp, const float *__restrict__ in,
+                                                                           const int32_t *__restrict__ labels, int64_t n, float *__restrict__ loss,
+                                                                           int32_t *__restrict__ argmax, float *__restrict__ logits,
+                                                                           unsigned long long *__restrict__ ignored)
+{
+	extern __shared__ float lds[];
+	const ed_ftrain_plan_t &t = *tp; /* in device memory, read where it is used: by value its fields stay live in SGPRs and spill */
+	const ed_fnet_plan_t &p = t.net;
+	const int B = p.batch;
+	/* forward half: ed_fnet_kernel's plan */
+	float *const buf0 = lds, *const buf1 = lds + B * p.buf_n[0];
+	float *wl = lds + B * (p.buf_n[0] + p.buf_n[1]);
+	int32_t *kl = (int32_t *)(wl + p.w_lds);
+	/* backward half, over it */
+	float *dy = lds;
+	int32_t *rb = (int32_t *)(lds + t.dy_lds);
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = ED_FNET_THREADS / 64;
+	const int acts_n = p.acts_n;
+	float *slab = t.slabs + (int64_t)blockIdx.x * t.w_floats;
+	float *acts = t.acts + (int64_t)blockIdx.x * B * acts_n;
+	float *dacts = t.dacts + (int64_t)blockIdx.x * B * acts_n;
+	uint8_t *mask = t.mask + (int64_t)blockIdx.x * B * acts_n;
+	const int64_t n_tiles = (n + B - 1) / B;
+	bool first = true;
+
+	for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x, first = false)
+	{
+		const int64_t u0 = tile * B;
+		const int nu = (int)(n - u0 < B ? n - u0 : B);
+		const float *x0 = in + u0 * (int64_t)p.in_n;
+		__syncthreads(); /* the previous tile's backward half no longer reads the LDS */
+		for (int i = tid; i < nu * p.in_n; i += ED_FNET_THREADS)
+		{
+			const int u = i / p.in_n, e = i - u * p.in_n;
+			buf0[u * p.buf_n[0] + e] = x0[i];
+		}
+
+		/* ---- forward ---- */
+		for (int l = 0; l < p.n_layers; l++)
+		{
+			const ed_fnet_layer_t &L = p.L[l];
+			const float *gw = p.w + L.w_at;
+			__syncthreads(); /* the previous layer's outputs are written and its weights no longer read */
+			{
+				const int nw = L.k_pad * L.n_pad; /* a multiple of 64: float4 copies */
+				const float4 *g4 = (const float4 *)gw;
+				float4 *l4 = (float4 *)wl;
+				for (int i = tid; i < nw / 4; i += ED_FNET_THREADS) l4[i] = g4[i];
+				for (int i = tid; i < L.k_pad; i += ED_FNET_THREADS) kl[i] = p.tab[L.koff_at + i];
+			}
+			__syncthreads();
+			const float *src = L.src ? buf1 : buf0;
+			float *dst = L.dst ? buf1 : buf0;
+			const int src_n = p.buf_n[L.src], dst_n = p.buf_n[L.dst];
+			const int32_t *rowin = p.tab + L.rowin_at;
+			const float *bias = gw + (int64_t)L.k_pad * L.n_pad;
+			const int M = nu * L.rows;
+			const int MT = (M + 15) / 16, NT = L.n_pad / 16, NG = (NT + 3) / 4;
+			for (int item = wave; item < MT * NG; item += n_waves)
+			{
+				const int mt = item / NG, g = item - mt * NG;
+				const int n0 = g * 64, nt = NT - 4 * g < 4 ? NT - 4 * g : 4;
+				if (nt == 4) edg_tile<4>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, mask, acts_n);
+				else if (nt == 3) edg_tile<3>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, mask, acts_n);
+				else if (nt == 2) edg_tile<2>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, mask, acts_n);
+				else edg_tile<1>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, mask, acts_n);
+			}
+		}
+		__syncthreads();
+
+		/* ---- loss and dL/dz, one thread per utterance (the softmax and the argmax are ed_fnet_kernel's) ---- */
+		if (tid < nu)
+		{
+			const ed_fnet_layer_t &L = p.L[p.n_layers - 1];
+			const float *z = (L.dst ? buf1 : buf0) + tid * p.buf_n[L.dst];
+			float *dz = dacts + tid * acts_n + L.acts_at;
+			const int64_t u = u0 + tid;
+			const int y = labels[u];
+			const bool labelled = (unsigned)y < (unsigned)p.n_out;
+			float mx = z[0];
+			for (int j = 1; j < p.n_out; j++) mx = fmaxf(mx, z[j]);
+			float s = 0.0f;
+			for (int j = 0; j < p.n_out; j++) s += expf(z[j] - mx);
+			const float nf = (float)n;
+			int best = 0;
+			float bp = -1.0f;
+			for (int j = 0; j < p.n_out; j++)
+			{
+				const float pj = expf(z[j] - mx) / s;
+				logits[u * p.n_out + j] = z[j];
+				if (pj > bp) { bp = pj; best = j; }
+				dz[j] = labelled ? (pj - (j == y ? 1.0f : 0.0f)) / nf : 0.0f;
+			}
+			if (argmax) argmax[u] = best;
+			if (loss) loss[u] = labelled ? logf(s) + mx - z[y] : 0.0f;
+			if (!labelled) atomicAdd(ignored, 1ull);
+		}
+
+		/* ---- backward ---- */
+		for (int l = p.n_layers - 1; l >= 0; l--)
+		{
+			const ed_fnet_layer_t &L = p.L[l];
+			const ed_ftrain_layer_t &G = t.G[l];
+			const int M = nu * L.rows, Mp = (M + 15) & ~15;
+			const int src_n = l ? acts_n : p.in_n;
+			const float *src = l ? acts + p.L[l - 1].acts_at : x0;
+			const int32_t *rowin = p.tab + L.rowin_at;
+			__syncthreads(); /* dz, or the next record's dX, is written; its dY no longer read */
+			for (int i = tid; i < Mp * L.n_pad; i += ED_FNET_THREADS)
+			{
+				const int m = i / L.n_pad, c = i - m * L.n_pad;
+				float v = 0.0f;
+				if (m < M && c < L.out_c)
+				{
+					const int u = m / L.rows, r = m - u * L.rows, q = r / L.P, e = r - q * L.P;
+					const int o = u * acts_n + L.acts_at + q * L.out_c + c;
+					const int mk = mask[o];
+					if ((mk & EDFT_PASS) && (mk & EDFT_WIN_MASK) == e) v = dacts[o];
+				}
+				dy[i] = v;
+			}
+			for (int m = tid; m < Mp; m += ED_FNET_THREADS)
+			{
+				const int u = m / L.rows;
+				rb[m] = m < M ? u * src_n + rowin[m - u * L.rows] : 0;
+			}
+			__syncthreads();
+			{
+				const int KT = (G.K + 15) / 16, NT = L.n_pad / 16, NG = (NT + 3) / 4;
+				const int32_t *koff = p.tab + L.koff_at;
+				for (int item = wave; item < (KT + 1) * NG; item += n_waves)
+				{
+					const int kt = item / NG, g = item - kt * NG;
+					const int n0 = g * 64, nt = NT - 4 * g < 4 ? NT - 4 * g : 4;
+					if (nt == 4) edg_dw_tile<4>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
+					else if (nt == 3) edg_dw_tile<3>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
+					else if (nt == 2) edg_dw_tile<2>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
+					else edg_dw_tile<1>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
+				}
+			}
+			if (l)
+			{
+				const int MX = nu * G.np, MT = (MX + 15) / 16, CT = (L.in_c + 15) / 16;
+				for (int item = wave; item < MT * CT; item += n_waves)
+				{
+					const int mt = item / CT, ct = item - mt * CT;
+					edg_dx_tile(L, G, t.inv + G.inv_at, p.w + L.w_at, dy, MX, mt, ct * 16, lane, dacts + p.L[l - 1].acts_at, acts_n);
+				}
+			}
+		}
+	}
+}
+
+/* grad[i] = slab 0's [i] + slab 1's [i] + ... in that order */
+__global__ __launch_bounds__(256) void ed_ftrain_reduce_kernel(const float *__restrict__ slabs, int n_slabs, int64_t w_floats, float *__restrict__ grad)
+{
+	const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= w_floats) return;
+	float s = slabs[i];
+	for (int g = 1; g < n_slabs; g++) s += slabs[g * w_floats + i];
+	grad[i] = s;
+}
+
+__global__ __launch_bounds__(256) void ed_ftrain_step_kernel(int kind, float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m,
+                                                              float *__restrict__ v, int64_t count, float factor, float b1, float omb1, float b2,
+                                                              float omb2, float eps)
+{
+	const int64_t stride = (int64_t)gridDim.x * 256;
+	for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += stride)
+	{
+		const float gi = g[i];
+		if (kind == EDFT_SGD)
+		{
+			w[i] -= factor * gi;
+			continue;
+		}
+		const float mi = b1 * m[i] + omb1 * gi;
+		const float vi = b2 * v[i] + omb2 * gi * gi;
+		m[i] = mi;
+		v[i] = vi;
+		w[i] -= factor * mi / (sqrtf(vi) + eps);
+	}
+}
+
+extern "C" int ed_launch_ftrain_grad(const ed_ftrain_plan_t *t, const ed_ftrain_plan_t *d_plan, const float *in, const int32_t *labels, int64_t n, float *loss, int32_t *argmax,
+                                     float *logits, float *grad, unsigned long long *ignored, int grid, hipStream_t stream)
+{
+	if (n <= 0) return 0;
+	const ed_fnet_plan_t *p = &t->net;
+	const size_t lds = ed_ftrain_lds_bytes(t);
+	if (lds > ED_FNET_LDS_BYTES || p->batch < 1 || p->n_layers < 1 || p->n_layers > ED_FNET_MAX_LAYERS || grid < 1) return (int)hipErrorInvalidValue;
+	{ const int e = ed_kernel_prepare((const void *)ed_ftrain_grad_kernel, ED_FNET_THREADS, lds, NULL, NULL); if (e) return e; }
+	const int64_t n_tiles = (n + p->batch - 1) / p->batch;
+	const int used = (int)(n_tiles < grid ? n_tiles : grid); /* a workgroup without a tile would leave its slab stale */
+	hipLaunchKernelGGL(ed_ftrain_grad_kernel, dim3((unsigned)used), dim3(ED_FNET_THREADS), lds, stream, d_plan, in, labels, n, loss, argmax, logits, ignored);
+	{ const int e = (int)hipGetLastError(); if (e) return e; }
+	hipLaunchKernelGGL(ed_ftrain_reduce_kernel, dim3((unsigned)((t->w_floats + 255) / 256)), dim3(256), 0, stream, t->slabs, used, t->w_floats, grad);
+	return (int)hipGetLastError();
+}
+
+extern "C" int ed_launch_ftrain_step(int kind, float *w, const float *g, float *m, float *v, int64_t count, float factor, float b1, float omb1, float b2,
+                                     float omb2, float eps, int n_cu, hipStream_t stream)
+{
+	if (count <= 0) return 0;
+	int64_t blocks = (count + 255) / 256;
+	const int64_t cap = (int64_t)(n_cu > 0 ? n_cu : 1) * 8;
+	if (blocks > cap) blocks = cap;
+	hipLaunchKernelGGL(ed_ftrain_step_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, kind, w, g, m, v, count, factor, b1, omb1, b2, omb2, eps);
+	return (int)hipGetLastError();
+}

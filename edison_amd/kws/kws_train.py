@@ -1,0 +1,79 @@
+"""``kws train <net.ednf> <x.npy> <y.npy> <out.ednf>`` -- train a float32 X-CUBE-AI network on the GPU (``Context.trainer``,
+edison_amd/train.py): what the reference does with ``kws_keras.train`` (kws_keras.py:400-416), for networks
+without conv or pool pads. The network file gives the architecture and the starting weights: an imported network to fine-tune, or
+``cube_import.build_blob`` of a freshly initialised model dict.
+
+    x.npy           float32 [n, in_h * in_w * in_c] (or [n, in_h, in_w, in_c]): the network inputs, the float flow's features
+    y.npy           integer class indices [n]
+    --epochs N      (30)      --batch N   (100)      --lr r   (0.0005, Adam)      --seed s   (0: the shuffle)
+    --val x.npy y.npy         a validation set: its loss drives ReduceLROnPlateau(0.5, patience 1) and EarlyStopping(patience 10)
+
+Prints the history per epoch and writes the trained network, which ``kws quantize`` takes.
+"""
+import sys
+
+import numpy as np
+
+USAGE = "usage: kws train <net.ednf> <x.npy> <y.npy> <out.ednf> [--epochs N] [--batch N] [--lr r] [--seed s] [--val <x.npy> <y.npy>]"
+
+
+def run(net, x_path, y_path, out_path, epochs=30, batch=100, lr=None, seed=0, val=None, ctx=None, out=None):
+    from .. import train
+    from ..context import default_context
+    out = out or sys.stdout
+    ctx = ctx or default_context()
+    x, y = np.load(x_path), np.load(y_path)
+    v = (np.load(val[0]), np.load(val[1])) if val else None
+    ctx.fnet_load(net)
+    with ctx.trainer() as tr:
+        hist = tr.fit(x, y, epochs, batch_size=batch, val=v, seed=seed, lr=train.LEARNING_RATE if lr is None else lr)
+        blob = tr.export()
+    for i, (l, a) in enumerate(zip(hist["loss"], hist["acc"])):
+        line = "epoch %3d  lr %.3g  loss %.6f  acc %.4f" % (i + 1, hist["lr"][i], l, a)
+        if v is not None:
+            line += "  val_loss %.6f  val_acc %.4f" % (hist["val_loss"][i], hist["val_acc"][i])
+        out.write(line + "\n")
+    if hist["stopped_early"]:
+        out.write("stopped early: the validation loss has not improved for 10 epochs\n")
+    with open(out_path, "wb") as f:
+        f.write(blob)
+    out.write("wrote %s: %d bytes after %d steps\n" % (out_path, len(blob), hist["steps"]))
+    return blob, hist
+
+
+def main(argv):
+    opts = {"--epochs": "30", "--batch": "100", "--lr": None, "--seed": "0"}
+    rest, val = [], None
+    i = 1
+    while i < len(argv):
+        if argv[i] == "--val":
+            if i + 2 >= len(argv):
+                print("--val needs two files")
+                return 1
+            val = (argv[i + 1], argv[i + 2])
+            i += 3
+        elif argv[i] in opts:
+            if i + 1 >= len(argv):
+                print("%s needs a value" % argv[i])
+                return 1
+            opts[argv[i]] = argv[i + 1]
+            i += 2
+        else:
+            rest.append(argv[i])
+            i += 1
+    if len(rest) != 4:
+        print(USAGE)
+        return 1
+    try:
+        epochs, batch, seed = int(opts["--epochs"]), int(opts["--batch"]), int(opts["--seed"])
+        lr = None if opts["--lr"] is None else float(opts["--lr"])
+    except ValueError:
+        print(USAGE)
+        return 1
+    from .._lib import EdisonError
+    try:
+        run(rest[0], rest[1], rest[2], rest[3], epochs=epochs, batch=batch, lr=lr, seed=seed, val=val)
+    except (EdisonError, ValueError) as e:
+        print("kws train: %s" % e)
+        return 1
+    return 0

@@ -8,11 +8,13 @@ on the keyword-spotting hot path:
     kws  live host|mcu <wav> [--net f]   audio/main.py:231-233       -> edison_amd.kws.kws_live
     kws  eval <audio.npy> <labels.npy>   nnom_utils.c:178-254        -> edison_amd.kws.kws_eval
     kws  quantize <net> <audio> <out>    kws_nnom.py:305             -> edison_amd.kws.kws_quantize
+    kws  train <net> <x> <y> <out>       kws_keras.py:400-416        -> edison_amd.kws.kws_train
 
 Where the reference talks to the STM32 board over the UART, the board's leg is computed by the GPU's bit-exact
-variant C. The remaining reference modules (mic, acquire, train, deploy, mcu) drive the board or Keras training and are
-out of scope. One deliberate difference: the reference's ``kws`` dispatcher runs ``live`` and then falls into the
-"Unrecognized command" branch of the next ``if`` (main.py:158-165, exit status 1); here ``kws live`` returns 0.
+variant C. The remaining reference modules (mic, acquire, deploy, mcu) drive the board and are out of scope; of
+``train`` the engine is here (``kws train``: Adam on a float32 network), not its Keras model zoo. One deliberate
+difference: the reference's ``kws`` dispatcher runs ``live`` and then falls into the "Unrecognized command" branch of
+the next ``if`` (main.py:158-165, exit status 1); here ``kws live`` returns 0.
 """
 import importlib
 import sys
@@ -28,6 +30,7 @@ COMMANDS = {
         "live": ("edison_amd.kws.kws_live", 2),
         "eval": ("edison_amd.kws.kws_eval", 2),
         "quantize": ("edison_amd.kws.kws_quantize", 2),
+        "train": ("edison_amd.kws.kws_train", 2),
     },
 }
 
@@ -43,6 +46,8 @@ USAGE = """usage: edison <module> <command> [<args>]
                                          confusion matrix and top-k accuracy on a labelled data set, counted on the GPU
   kws  quantize <net.ednf> <audio.npy> <out.ednn> [--weights-h <out.h>] [--saturate <share>] [--geometry k=v,...] [--chunk N]
                                          quantise a float32 network to an int8 NNoM graph, calibrated on the GPU over the audio
+  kws  train <net.ednf> <x.npy> <y.npy> <out.ednf> [--epochs N] [--batch N] [--lr r] [--seed s] [--val <x.npy> <y.npy>]
+                                         train a float32 network (no pads) on features and class indices: Adam on the GPU
 """
 
 

@@ -1,0 +1,321 @@
+"""Training the loaded float32 network on the GPU (``edison_ftrain_*``, include/edison_hip.h): what the reference
+does with ``kws_keras.train`` (kws_keras.py:400-416: Adam at 0.0005, batch 100, ReduceLROnPlateau and EarlyStopping on the validation
+loss). The gradient and the optimiser step are HIP kernels and the weights never leave the device between steps; the epochs, the
+shuffle, the history and the two callbacks are host code here, none of it hot.
+
+    ctx.fnet_load(blob)                       # imported, or cube_import.build_blob of a freshly initialised model dict
+    tr = ctx.trainer()
+    hist = tr.fit(x, y, epochs=30, val=(vx, vy))
+    trained = cube_import.build_blob(tr.model())
+
+After a step the context's float network *is* the trained one: fnet, kws_float, streams and the calibrator run the new weights.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib, cube_import
+
+ADAM, SGD = 0, 1          # EDISON_FTRAIN_ADAM, EDISON_FTRAIN_SGD
+LEARNING_RATE = 0.0005    # kws_keras.py:53 initial_learningrate
+BATCH_SIZE = 100          # kws_keras.py: batchSize
+
+
+def _np_ptr(a):
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _t_ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+# ---- the packed layout (host, no GPU) ---------------------------------------------------------------------------------------------
+def conv_records(model):
+    return [L for L in model["layers"] if L["type"] == cube_import.T_CONV]
+
+
+def layout(model):
+    """The packed weight array of a model dict, as the .ednf blob, the kernels and edison_ftrain_layout have it: per conv record
+    dict(w_at, K, k_pad, out_c, n_pad, shape=(out_c, kh, kw, in_c)); B[k_pad][n_pad] at w_at, then bias[n_pad]. Returns (records, w_floats)."""
+    out, at = [], 0
+    for L in conv_records(model):
+        (kh, kw), ic, oc = L["k"], L["inp"][2], L["out"][2]
+        K = kh * kw * ic
+        k_pad, n_pad = (K + 3) // 4 * 4, (oc + 15) // 16 * 16
+        out.append(dict(w_at=at, K=K, k_pad=k_pad, out_c=oc, n_pad=n_pad, shape=(oc, kh, kw, ic)))
+        at += k_pad * n_pad + n_pad
+    return out, at
+
+
+def unpack(packed, lay):
+    """A packed array -> [dict(w [out][kh][kw][in], b [out])] per record, in the array's dtype (the padding is dropped)."""
+    packed = np.asarray(packed)
+    out = []
+    for r in lay:
+        nb = r["k_pad"] * r["n_pad"]
+        B = packed[r["w_at"]:r["w_at"] + nb].reshape(r["k_pad"], r["n_pad"])
+        out.append(dict(w=B[:r["K"], :r["out_c"]].T.reshape(r["shape"]).copy(), b=packed[r["w_at"] + nb:r["w_at"] + nb + r["out_c"]].copy()))
+    return out
+
+
+def pack(tensors, lay, base=None, dtype=np.float32):
+    """[dict(w, b)] per record -> the packed array; the padding is `base`'s (a packed array), or zero."""
+    n = lay[-1]["w_at"] + lay[-1]["k_pad"] * lay[-1]["n_pad"] + lay[-1]["n_pad"]
+    packed = np.zeros(n, dtype) if base is None else np.array(base, dtype).reshape(n)
+    if len(tensors) != len(lay):
+        raise ValueError("%d records, the network has %d" % (len(tensors), len(lay)))
+    for t, r in zip(tensors, lay):
+        w, b = np.asarray(t["w"]), np.asarray(t["b"])
+        if w.shape != r["shape"] or b.shape != (r["out_c"],):
+            raise ValueError("a record's w %s / b %s, the network has %s / (%d,)" % (w.shape, b.shape, r["shape"], r["out_c"]))
+        nb = r["k_pad"] * r["n_pad"]
+        packed[r["w_at"]:r["w_at"] + nb].reshape(r["k_pad"], r["n_pad"])[:r["K"], :r["out_c"]] = w.reshape(r["out_c"], r["K"]).T
+        packed[r["w_at"] + nb:r["w_at"] + nb + r["out_c"]] = b
+    return packed
+
+
+# ---- the host side of fit: shuffle and callbacks ----------------------------------------------------------------------------------
+def epoch_order(n, seed, epoch):
+    """The order of the n rows in epoch `epoch` (from 0): a permutation that depends on (seed, epoch) only."""
+    return np.random.default_rng([int(seed), int(epoch)]).permutation(int(n))
+
+
+class ReduceLROnPlateau:
+    """keras.callbacks.ReduceLROnPlateau(factor=0.5, patience=1, min_lr=1e-9) on a loss (mode min, min_delta 1e-4, no cooldown): an
+    epoch that does not improve the best loss by more than min_delta counts; after `patience` such epochs the rate is multiplied by
+    factor, not below min_lr, and the count starts again."""
+
+    def __init__(self, factor=0.5, patience=1, min_lr=1e-9, min_delta=1e-4):
+        self.factor, self.patience, self.min_lr, self.min_delta = float(factor), int(patience), float(min_lr), float(min_delta)
+        self.best, self.wait = np.inf, 0
+
+    def update(self, loss, lr):
+        """The epoch's monitored loss and the current rate -> the rate of the next epoch."""
+        if loss < self.best - self.min_delta:
+            self.best, self.wait = loss, 0
+            return lr
+        self.wait += 1
+        if self.wait >= self.patience:
+            self.wait = 0
+            if lr > self.min_lr:
+                return max(lr * self.factor, self.min_lr)
+        return lr
+
+
+class EarlyStopping:
+    """keras.callbacks.EarlyStopping(patience=10) on a loss (min_delta 0): stop after `patience` epochs in a row that did not go
+    below the best loss so far."""
+
+    def __init__(self, patience=10):
+        self.patience, self.best, self.wait = int(patience), np.inf, 0
+
+    def update(self, loss):
+        """The epoch's monitored loss -> True when training stops here."""
+        if loss < self.best:
+            self.best, self.wait = loss, 0
+            return False
+        self.wait += 1
+        return self.wait >= self.patience
+
+
+def fit(trainer, x, y, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=LEARNING_RATE, max_steps=None, callbacks=True):
+    """Trainer.fit on anything with grad(x, y) -> dict(loss [n], argmax [n]) and step(lr): the GPU trainer, or a host restatement of it."""
+    x = np.asarray(x)
+    x = x.reshape(x.shape[0], -1)
+    y = np.asarray(y).astype(np.int32).reshape(-1)
+    if x.shape[0] != y.shape[0] or x.shape[0] == 0:
+        raise ValueError("x has %d rows, y %d" % (x.shape[0], y.shape[0]))
+    if int(batch_size) < 1 or int(epochs) < 0:
+        raise ValueError("batch_size must be at least 1 and epochs at least 0")
+    n, bs = x.shape[0], int(batch_size)
+    if val is not None:
+        vx, vy = np.asarray(val[0]), np.asarray(val[1]).astype(np.int32).reshape(-1)
+        vx = vx.reshape(vx.shape[0], -1)
+    plateau, stopper = ReduceLROnPlateau(), EarlyStopping()
+    hist = dict(loss=[], acc=[], val_loss=[], val_acc=[], lr=[], steps=0, stopped_early=False)
+    for epoch in range(int(epochs)):
+        order = epoch_order(n, seed, epoch)
+        loss_sum, hits, seen = 0.0, 0, 0
+        for b0 in range(0, n, bs):                       # the last batch may be short
+            if max_steps is not None and hist["steps"] >= max_steps:
+                break
+            rows = order[b0:b0 + bs]
+            r = trainer.grad(x[rows], y[rows])
+            trainer.step(lr)
+            hist["steps"] += 1
+            loss_sum += float(np.sum(r["loss"], dtype=np.float64))
+            hits += int((r["argmax"] == y[rows]).sum())
+            seen += len(rows)
+        if not seen:
+            break
+        hist["loss"].append(loss_sum / seen)             # as Keras: the mean over the epoch's batches, weights moving
+        hist["acc"].append(hits / seen)
+        hist["lr"].append(lr)
+        if val is not None:
+            vl, vh = 0.0, 0
+            for b0 in range(0, vx.shape[0], 4096):
+                r = trainer.grad(vx[b0:b0 + 4096], vy[b0:b0 + 4096])   # the gradient it leaves is not stepped
+                vl += float(np.sum(r["loss"], dtype=np.float64))
+                vh += int((r["argmax"] == vy[b0:b0 + 4096]).sum())
+            hist["val_loss"].append(vl / max(vx.shape[0], 1))
+            hist["val_acc"].append(vh / max(vx.shape[0], 1))
+            if callbacks:
+                lr = plateau.update(hist["val_loss"][-1], lr)
+                if stopper.update(hist["val_loss"][-1]):
+                    hist["stopped_early"] = True
+                    break
+        if max_steps is not None and hist["steps"] >= max_steps:
+            break
+    return hist
+
+
+# ---- the GPU trainer --------------------------------------------------------------------------------------------------------------
+class Trainer:
+    """edison_ftrain on `ctx`, bound to the float network loaded now; loading another one invalidates it (EdisonError). Networks
+    without conv or pool pads."""
+
+    def __init__(self, ctx):
+        self._ctx, self._L = ctx, ctx._L
+        if ctx._fnet_blob is None:
+            raise ValueError("no float network loaded (fnet_load)")
+        h = ctypes.c_void_p()
+        ctx._check(self._L.edison_ftrain_create(ctx._h, ctypes.byref(h)))
+        self._h = h
+        self._model = cube_import.read_blob(ctx._fnet_blob)
+        info = self.info()
+        self.in_n, self.n_out, self.w_floats, self.n_layers = info["in_n"], info["n_out"], info["w_floats"], info["n_layers"]
+        self.layout, n = layout(self._model)
+        for i, r in enumerate(self.layout):                       # the library's layout is the one unpack / pack restate
+            got = self.record_layout(i)
+            if any(got[k] != r[k] for k in ("w_at", "K", "k_pad", "out_c", "n_pad")) or n != self.w_floats:
+                raise RuntimeError("record %d: edison_ftrain_layout %s, the blob's %s" % (i, got, r))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if self._ctx._fnet_trainer is self:
+                self.export()
+            self._L.edison_ftrain_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        """dict of edison_ftrain_info_t: n_layers, in_n, n_out, batch, lds_bytes, grid, w_floats, steps, ignored (synchronises)."""
+        info = _lib.FtrainInfo()
+        self._ctx._check(self._L.edison_ftrain_info(self._h, ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in _lib.FtrainInfo._fields_}
+
+    def record_layout(self, record):
+        """edison_ftrain_layout: dict(w_at, K, k_pad, out_c, n_pad) of conv / dense record `record`."""
+        w_at = ctypes.c_int64()
+        v = [ctypes.c_int32() for _ in range(4)]
+        self._ctx._check(self._L.edison_ftrain_layout(self._h, int(record), ctypes.byref(w_at), *[ctypes.byref(a) for a in v]))
+        return dict(w_at=w_at.value, K=v[0].value, k_pad=v[1].value, out_c=v[2].value, n_pad=v[3].value)
+
+    # -- the gradient
+    def grad(self, x, y):
+        """Host inputs [n][in_n] float32 and labels [n] (class indices; one outside [0, n_out) is an EdisonError) -> dict(loss [n],
+        argmax [n]). The gradient stays on the device: gradient() / gradients() fetch it, step() applies it."""
+        f = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, self.in_n)
+        lab = np.ascontiguousarray(y, dtype=np.int32).reshape(-1)
+        if lab.shape[0] != f.shape[0]:
+            raise ValueError("%d inputs, %d labels" % (f.shape[0], lab.shape[0]))
+        loss = np.zeros(f.shape[0], np.float32)
+        am = np.zeros(f.shape[0], np.int32)
+        self._ctx._check(self._L.edison_ftrain_grad(self._h, _np_ptr(f), _np_ptr(lab), f.shape[0], _np_ptr(loss), _np_ptr(am)))
+        return dict(loss=loss, argmax=am)
+
+    def grad_t(self, x, y, n=None, loss=None, argmax=None):
+        """edison_ftrain_grad_dev on torch device tensors (x float32 [n][in_n], y int32 [n], contiguous; loss float32 [n] and argmax
+        int32 [n] optional), enqueued on the context's stream behind whatever produced them. A label outside [0, n_out) contributes
+        nothing and is counted in info()["ignored"]."""
+        n = int(x.shape[0] if n is None else n)
+        self._ctx._check(self._L.edison_ftrain_grad_dev(self._h, _t_ptr(x), _t_ptr(y), n, _t_ptr(loss), _t_ptr(argmax)))
+
+    def gradient(self):
+        """The last call's gradient, packed float32 [w_floats] (synchronises)."""
+        g = np.zeros(self.w_floats, np.float32)
+        self._ctx._check(self._L.edison_ftrain_grad_get(self._h, _np_ptr(g)))
+        return g
+
+    def gradients(self):
+        """The last call's gradient as [dict(w [out][kh][kw][in], b [out])] per conv / dense record."""
+        return unpack(self.gradient(), self.layout)
+
+    def logits(self, n):
+        """The last gradient call's logits float32 [n][n_out] (n: that call's); edison_fnet_batch's bit for bit."""
+        z = np.zeros((int(n), self.n_out), np.float32)
+        self._ctx._check(self._L.edison_ftrain_logits_get(self._h, _np_ptr(z)))
+        return z
+
+    # -- the optimiser
+    def set_opt(self, kind="adam", b1=0.9, b2=0.999, eps=1e-7):
+        """Adam (Keras's constants by default) or kind "sgd": w -= lr g."""
+        kinds = dict(adam=ADAM, sgd=SGD)
+        if kind not in kinds:
+            raise ValueError("kind is 'adam' or 'sgd'")
+        self._ctx._check(self._L.edison_ftrain_set_opt(self._h, kinds[kind], float(b1), float(b2), float(eps)))
+
+    def step(self, lr=LEARNING_RATE):
+        """One optimiser step with the last gradient, in place on the context's loaded network."""
+        self._ctx._check(self._L.edison_ftrain_step(self._h, float(lr)))
+        self._ctx._fnet_trainer = self          # the context's copy of the blob is behind the device weights now
+
+    def reset(self):
+        """Zero Adam's moments, its step count and the ignored-row counter."""
+        self._ctx._check(self._L.edison_ftrain_reset(self._h))
+
+    # -- the weights
+    def packed_weights(self):
+        w = np.zeros(self.w_floats, np.float32)
+        self._ctx._check(self._L.edison_ftrain_weights_get(self._h, _np_ptr(w)))
+        return w
+
+    def set_packed_weights(self, packed):
+        w = np.ascontiguousarray(packed, dtype=np.float32).reshape(-1)
+        if w.shape[0] != self.w_floats:
+            raise ValueError("%d floats, the network has %d" % (w.shape[0], self.w_floats))
+        self._ctx._check(self._L.edison_ftrain_weights_set(self._h, _np_ptr(w)))
+        self._ctx._fnet_trainer = self
+
+    def weights(self):
+        """The device weights now: [dict(w [out][kh][kw][in], b [out])] float32 per conv / dense record, the model dict's layout."""
+        return unpack(self.packed_weights(), self.layout)
+
+    def set_weights(self, tensors):
+        """weights()' inverse: every record's w and b onto the device; the packed array's padding stays what it is."""
+        self.set_packed_weights(pack(tensors, self.layout, base=self.packed_weights()))
+
+    def model(self):
+        """The cube_import model dict of the network with the device weights now: cube_import.build_blob(trainer.model(),
+        trainer.model()["keywords"]) is the trained .ednf."""
+        m = dict(self._model, layers=[dict(L) for L in self._model["layers"]])
+        for L, t in zip(conv_records(m), self.weights()):
+            L["w"], L["b"] = t["w"], t["b"]
+        return m
+
+    def export(self):
+        """The trained .ednf: cube_import.build_blob of model() with the network's keywords. The context keeps it as the loaded
+        network's blob, which Context.quantize reads the weights from."""
+        m = self.model()
+        blob = cube_import.build_blob(m, m.get("keywords"))
+        self._ctx._fnet_blob, self._ctx._fnet_trainer = blob, None
+        return blob
+
+    def fit(self, x, y, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=LEARNING_RATE, max_steps=None, callbacks=True):
+        """Train on x [n][in_n] and class indices y [n]: per epoch the rows in epoch_order(n, seed, epoch), batches of batch_size (the
+        last one short), one gradient call and one Adam step each. val = (x, y): after every epoch its loss and accuracy, and on that
+        loss the reference's two callbacks (callbacks=False: none). max_steps ends training after that many steps, inside an epoch if
+        need be. Returns the history: loss, acc (the means over each epoch's batches, as Keras), val_loss, val_acc, lr per epoch, steps,
+        stopped_early."""
+        return fit(self, x, y, epochs, batch_size=batch_size, val=val, seed=seed, lr=lr, max_steps=max_steps, callbacks=callbacks)

@@ -450,6 +450,60 @@ int edison_fcal_add(edison_fcal *c, const float *in, int64_t n);
 int edison_fcal_result(edison_fcal *c, uint32_t *absmax, uint64_t *hist, uint64_t *count);
 
 /*
+ * Training the loaded float network (the epochs, callbacks and the model dict are edison_amd/train.py). A trainer is
+ * bound to the float network loaded when it is created and updates that network's device weights in place: after a step the next
+ * edison_fnet_batch, stream push or calibration on the context runs the new weights. Networks whose records have no conv or pool pad.
+ *   edison_ftrain_grad_dev  n inputs [n][in_n] and int32 labels [n] in device memory -> loss [n] (log sum exp(z) - z[y] per row) and
+ *                           argmax [n] (edison_fnet_batch's), each NULL for not written, and, kept in the trainer, the logits [n][n_out]
+ *                           (edison_fnet_batch's bit for bit) and the gradient of the batch loss (1 / n) sum loss with respect to every
+ *                           weight and bias, in the packed layout below. Two launches on the context's stream, no synchronisation. A
+ *                           label outside [0, n_out) contributes nothing (loss 0) and is counted (edison_ftrain_info). The same call
+ *                           repeated gives the same bits. The weights are not changed.
+ *   edison_ftrain_grad      the host form: stages its arrays and synchronises; a label outside [0, n_out) is EDISON_E_ARGUMENT before
+ *                           any launch
+ *   edison_ftrain_grad_get / _logits_get  synchronise and copy out the last call's gradient [w_floats] / logits [n][n_out]
+ *   edison_ftrain_step      one optimiser step with the last gradient at learning rate lr, one launch. Adam as Keras states it, t from 1:
+ *                           m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g g, w -= lr sqrt(1 - b2^t) / (1 - b1^t) m / (sqrt(v) + eps); the
+ *                           scalar factor is computed in double. Or, kind EDISON_FTRAIN_SGD, w -= lr g.
+ *   edison_ftrain_set_opt   kind and Adam's constants (at create: Adam, 0.9, 0.999, 1e-7); edison_ftrain_reset zeroes m, v, t and the
+ *                           counter of ignored rows
+ *   edison_ftrain_weights_get / _set  copy the packed weights [w_floats] out / in (synchronising)
+ * The packed layout is the .ednf blob's and the kernels': per conv / dense record, at float offset w_at, B[k_pad][n_pad] with
+ * k = (ky kw + kx) in_c + ci, then bias[n_pad] (edison_ftrain_layout; K = the real k rows). Padding k rows and padding channels of the
+ * gradient are exactly +0.0f whatever the blob holds there, so a step leaves the weights' padding as it was.
+ * EDISON_E_NO_MODEL: no float network loaded at create; or, from every call but destroy, another float network was loaded since (create
+ * a new trainer). EDISON_E_NO_IMPL at create, the message naming the cause: a record with a pad, or a training workgroup (the network at
+ * batch 1 beside one utterance's dY) that does not fit the LDS.
+ */
+#define EDISON_FTRAIN_ADAM 0
+#define EDISON_FTRAIN_SGD 1
+typedef struct edison_ftrain edison_ftrain;
+typedef struct edison_ftrain_info_t {
+	int32_t n_layers;  /* conv / dense records */
+	int32_t in_n;      /* floats per input */
+	int32_t n_out;     /* logits */
+	int32_t batch;     /* utterances per workgroup tile of the gradient kernel */
+	int32_t lds_bytes; /* LDS per workgroup */
+	int32_t grid;      /* workgroups of the gradient kernel, at most: one gradient slab each */
+	int64_t w_floats;  /* the packed weight array */
+	int64_t steps;     /* optimiser steps since create / reset: Adam's t */
+	int64_t ignored;   /* rows with a label outside [0, n_out) since create / reset (synchronises) */
+} edison_ftrain_info_t;
+int edison_ftrain_create(edison_ctx *ctx, edison_ftrain **out);
+void edison_ftrain_destroy(edison_ftrain *t);
+int edison_ftrain_info(edison_ftrain *t, edison_ftrain_info_t *out);
+int edison_ftrain_layout(edison_ftrain *t, int record, int64_t *w_at, int32_t *K, int32_t *k_pad, int32_t *out_c, int32_t *n_pad);
+int edison_ftrain_grad_dev(edison_ftrain *t, const float *in, const int32_t *labels, int64_t n, float *loss, int32_t *argmax);
+int edison_ftrain_grad(edison_ftrain *t, const float *in, const int32_t *labels, int64_t n, float *loss, int32_t *argmax);
+int edison_ftrain_grad_get(edison_ftrain *t, float *packed);
+int edison_ftrain_logits_get(edison_ftrain *t, float *logits);
+int edison_ftrain_step(edison_ftrain *t, double lr);
+int edison_ftrain_set_opt(edison_ftrain *t, int kind, double b1, double b2, double eps);
+int edison_ftrain_weights_get(edison_ftrain *t, float *packed);
+int edison_ftrain_weights_set(edison_ftrain *t, const float *packed);
+int edison_ftrain_reset(edison_ftrain *t);
+
+/*
  * Exact KWS mode (off by default; EDISON_KWS_EXACT=1 in the environment at edison_init turns it on for that context).
  * While it is on, every variant-B KWS call of the context -- edison_kws_batch, edison_kws_batch_dev and the sharded entry points --
  * aims at features, logits and argmax identical to the host flow's float64 arithmetic (mfcc_mcu, then float32 * scale, clip,

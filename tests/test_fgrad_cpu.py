@@ -1,0 +1,212 @@
+"""The float64 restatement of training (tests/fgrad_ref.py) held to torch's float64 autograd and to central differences, the packed
+layout of edison_amd/train.py held to the plan's (fnet_exact.plan), the Adam restatement held to torch.optim.Adam, and the host side
+of fit: the shuffle and the two callbacks. No GPU."""
+import os
+
+import numpy as np
+import pytest
+
+from edison_amd import cube_import, train
+
+import fgrad_ref
+import fnet_exact
+import fnet_ref
+import fnet_sweep
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROWS = ["ladder_k5", "pool21_trunc_h", "pool12_trunc_w", "pool22_trunc_hw", "pool41_tail", "inc3_oc64_oc65_s21", "oc40_s32_span_h", "n_out_210",
+        "relu_logits", "conv_last_map", "layers16", "synth_pool12_relu"]
+
+
+def _case(name, n=5):
+    if name == "cube_kws":
+        model = fnet_ref.load(os.path.join(HERE, "golden", "cube_kws.ednf"))
+        g = np.load(os.path.join(HERE, "golden", "cube_golden.npz"))
+        rows = np.stack([g[k] for k in sorted(g.files) if k.startswith("net_in_")]).astype(np.float32)
+        x = rows[np.arange(n) % rows.shape[0]]
+    else:
+        model = fnet_sweep.model(name)
+        x = fgrad_ref.inputs(name, n, int(np.prod(model["in_shape"])))
+    n_out = int(np.prod(fnet_ref.conv_records(model)[-1]["out"]))
+    return model, x, (np.arange(n) % n_out).astype(np.int32)
+
+
+@pytest.mark.parametrize("name", ROWS + ["cube_kws"])
+def test_agrees_with_torch_float64_autograd(name):
+    import torch
+    model, x, y = _case(name)
+    ref = fgrad_ref.loss_grad(model, x, y)
+    tor = fgrad_ref.torch_grads(model, x, y, torch.float64)
+    assert np.allclose(ref["logits"], tor["logits"], rtol=1e-10, atol=1e-12)
+    assert np.allclose(ref["loss"], tor["loss"], rtol=1e-10, atol=1e-12)
+    for i, (a, b) in enumerate(zip(ref["grads"], tor["grads"])):
+        for k in ("w", "b"):
+            scale = max(np.abs(b[k]).max(), 1e-300)
+            assert np.abs(a[k] - b[k]).max() <= 1e-10 * scale, (name, i, k, np.abs(a[k] - b[k]).max() / scale)
+
+
+def test_inputs_leave_the_saturating_sets_out():
+    x = fgrad_ref.inputs("pool21_trunc_h", 9, 66)
+    assert x.shape == (9, 66) and np.abs(x).max() < 200          # n1, zero and neg (30 |g|) rows only
+    assert (x[1] == 0).all() and (x[2] <= 0).all() and (x[4] == 0).all()
+
+
+@pytest.mark.parametrize("name", ["ladder_k5", "pool21_trunc_h"])
+def test_agrees_with_central_differences(name):
+    model, x, y = _case(name, n=4)
+    ref = fgrad_ref.loss_grad(model, x, y)
+    base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_ref.conv_records(model)]
+    h = 1e-6
+    for i, t in enumerate(base):
+        for k in ("w", "b"):
+            num = np.zeros(t[k].size)
+            for j in range(t[k].size):
+                vals = []
+                for sgn in (1.0, -1.0):
+                    w = [dict(w=u["w"].copy(), b=u["b"].copy()) for u in base]
+                    w[i][k].reshape(-1)[j] += sgn * h
+                    vals.append(fgrad_ref.loss_grad(model, x, y, weights=w)["loss"].mean())
+                num[j] = (vals[0] - vals[1]) / (2 * h)
+            g = ref["grads"][i][k].reshape(-1)
+            # the loss is smooth between the kinks of ReLU and max: a central difference errs by O(h^2) |f'''| + rounding / h
+            assert np.abs(num - g).max() <= 1e-7 * max(np.abs(g).max(), 1.0), (name, i, k, np.abs(num - g).max())
+
+
+def test_first_maximum_and_relu_at_zero():
+    """One 1 x 2 pool window with a tie, under ReLU and without: the gradient goes to element 0, and a 0 / 0 tie under ReLU passes none."""
+    def net(relu, bias):
+        conv = dict(type=cube_import.T_CONV, inp=(1, 2, 1), out=(1, 1, 1), k=(1, 1), s=(1, 1), p=(1, 2), relu=relu,
+                    w=np.ones((1, 1, 1, 1), np.float32), b=np.full(1, bias, np.float32))
+        dense = dict(type=cube_import.T_CONV, inp=(1, 1, 1), out=(1, 1, 2), k=(1, 1), s=(1, 1), p=(1, 1), relu=0,
+                     w=np.array([1.0, -1.0], np.float32).reshape(2, 1, 1, 1), b=np.zeros(2, np.float32))
+        return dict(in_shape=(1, 2, 1), layers=[conv, dense, dict(type=cube_import.T_SOFTMAX, inp=(1, 1, 2), out=(1, 1, 2))])
+    tie = fgrad_ref.loss_grad(net(0, 0.5), np.array([[2.0, 2.0]]), [0])["grads"][0]
+    assert tie["w"].reshape(-1)[0] != 0                                    # x[0] = 2 reaches dW through element 0 ...
+    one = fgrad_ref.loss_grad(net(0, 0.5), np.array([[2.0, 1.0]]), [0])["grads"][0]
+    assert tie["w"].reshape(-1)[0] == one["w"].reshape(-1)[0]              # ... and element 1 adds nothing
+    dead = fgrad_ref.loss_grad(net(1, 0.0), np.array([[0.0, 0.0]]), [0])["grads"][0]
+    assert dead["w"].reshape(-1)[0] == 0 and dead["b"][0] == 0             # ReLU'(0) = 0
+
+
+@pytest.mark.parametrize("name", ["pool22_trunc_hw", "inc3_oc64_oc65_s21", "n_out_210", "ladder_k5"])
+def test_pack_round_trip_against_the_plan(name):
+    blob = fnet_sweep.blob(name)
+    model, plan = cube_import.read_blob(blob), fnet_exact.plan(blob)
+    lay, n = train.layout(model)
+    at = 0
+    for r, L in zip(lay, plan["layers"]):
+        assert (r["w_at"], r["K"], r["k_pad"], r["out_c"], r["n_pad"]) == (at, L["K"], L["k_pad"], L["out_c"], L["n_pad"])
+        at += L["k_pad"] * L["n_pad"] + L["n_pad"]
+    assert n == at
+    payload = np.frombuffer(blob, "<f4", n, len(blob) - 4 * n)            # the blob's weights are the packed array
+    tensors = train.unpack(payload, lay)
+    for t, L in zip(tensors, fnet_ref.conv_records(model)):
+        assert np.array_equal(t["w"], L["w"]) and np.array_equal(t["b"], L["b"])
+    assert np.array_equal(train.pack(tensors, lay), payload)
+    marked = np.where(payload == 0, np.float32(1e6), payload)             # the padding is kept from `base`, the real entries replaced
+    again = train.pack(tensors, lay, base=marked)
+    real = train.pack([dict(w=np.ones_like(t["w"]), b=np.ones_like(t["b"])) for t in tensors], lay) != 0
+    assert np.array_equal(again[real], payload[real]) and np.array_equal(again[~real], marked[~real])
+    with pytest.raises(ValueError):
+        train.pack(tensors[:-1] + [dict(w=tensors[-1]["w"][..., None], b=tensors[-1]["b"])], lay)
+
+
+def test_adam_restatement_against_torch():
+    import torch
+    rng = np.random.default_rng(5)
+    w0 = [rng.normal(0, 1, (4, 3)), rng.normal(0, 1, 7)]
+    ws = [w.copy() for w in w0]
+    tw = [torch.tensor(w, dtype=torch.float64, requires_grad=True) for w in w0]
+    opt = torch.optim.Adam(tw, lr=0.0005, betas=(0.9, 0.999), eps=1e-7)
+    adam = fgrad_ref.Adam()
+    for step in range(5):
+        gs = [rng.choice([-1.0, 1.0], w.shape) * rng.uniform(0.5, 2.0, w.shape) for w in w0]
+        for t, g in zip(tw, gs):
+            t.grad = torch.tensor(g, dtype=torch.float64)
+        opt.step()
+        adam.step(ws, gs, 0.0005)
+        for a, t in zip(ws, tw):
+            # torch puts eps beside sqrt(v) / sqrt(1 - b2^t), Keras beside sqrt(v): the denominators differ by less than eps. With
+            # |g| >= 0.5, sqrt(v) >= sqrt(0.001) 0.5 = 0.0158, so an update differs by at most 1e-7 / 0.0158 of itself, and an
+            # update is at most lr (1 - b1) / sqrt(1 - b2) = 3.2 lr: 5 steps x 3.2 lr x 6.4e-6
+            assert np.abs(a - t.detach().numpy()).max() <= 5 * 3.2 * 0.0005 * 6.4e-6, step
+    assert adam.t == 5
+
+
+def test_adam_first_step_is_lr_sized():
+    adam = fgrad_ref.Adam()
+    w = [np.array([1.0, -2.0, 3.0])]
+    adam.step(w, [np.array([0.5, -4.0, 0.0])], 0.01)
+    assert np.allclose(w[0], [1.0 - 0.01, -2.0 + 0.01, 3.0], atol=1e-7)  # m / sqrt(v) = sign(g) after bias correction
+
+
+def test_shuffle_is_reproducible_from_the_seed():
+    a, b = train.epoch_order(96, 0, 3), train.epoch_order(96, 0, 3)
+    assert np.array_equal(a, b) and np.array_equal(np.sort(a), np.arange(96))
+    assert not np.array_equal(a, train.epoch_order(96, 0, 4)) and not np.array_equal(a, train.epoch_order(96, 1, 3))
+
+
+class _Scripted:
+    """A trainer whose losses follow a script: fit's bookkeeping without a network."""
+
+    def __init__(self, val_losses, n_train):
+        self.val, self.n_train, self.lrs, self.batches, self.epoch = list(val_losses), n_train, [], [], 0
+
+    def grad(self, x, y):
+        if x.shape[1] == 2:                                               # the validation set is marked by its width
+            loss = np.full(len(y), self.val[self.epoch], np.float32)
+            self.epoch += 1
+        else:
+            self.batches.append(x[:, 0].astype(int).tolist())
+            loss = np.full(len(y), 1.0, np.float32)
+        return dict(loss=loss, argmax=np.zeros(len(y), np.int32))
+
+    def step(self, lr):
+        self.lrs.append(lr)
+
+
+def test_fit_batches_history_and_callbacks():
+    n = 7
+    x = np.arange(n, dtype=np.float32).reshape(n, 1)
+    y = np.zeros(n, np.int32)
+    val = (np.zeros((3, 2), np.float32), np.array([0, 1, 0]))
+    # improves, stalls (lr halves after one epoch without a gain above 1e-4), improves, then never again: stopped after 10 such epochs
+    script = [1.0, 1.0, 0.5, 0.49995] + [0.6] * 20
+    tr = _Scripted(script, n)
+    hist = train.fit(tr, x, y, epochs=50, batch_size=3, val=val, seed=4, lr=0.01)
+    assert [len(b) for b in tr.batches[:3]] == [3, 3, 1]                  # the last batch is short
+    assert sorted(sum(tr.batches[:3], [])) == list(range(n)) and sum(tr.batches[:3], []) == train.epoch_order(n, 4, 0).tolist()
+    assert hist["val_loss"][:4] == pytest.approx(script[:4]) and hist["loss"][0] == pytest.approx(1.0)
+    assert hist["acc"][0] == 1.0 and hist["val_acc"][0] == pytest.approx(2 / 3)
+    # epoch 1 stalls -> epoch 2 runs at 0.005; epoch 2 improves; epoch 3 gains under min_delta -> 0.0025; then a halving per epoch
+    assert hist["lr"][:6] == pytest.approx([0.01, 0.01, 0.005, 0.005, 0.0025, 0.00125])
+    assert hist["stopped_early"] and len(hist["val_loss"]) == 4 + 10     # best 0.49995 at epoch 3, ten epochs without a better one
+    assert hist["steps"] == 3 * 14 and len(tr.lrs) == 42
+    # without a validation set the callbacks have nothing to watch; max_steps ends inside an epoch
+    tr = _Scripted([], n)
+    hist = train.fit(tr, x, y, epochs=5, batch_size=3, seed=4, lr=0.01, max_steps=4)
+    assert hist["steps"] == 4 and len(hist["loss"]) == 2 and hist["val_loss"] == [] and not hist["stopped_early"]
+    assert set(tr.lrs) == {0.01}
+
+
+def test_reduce_lr_floor_and_early_stopping_reset():
+    p = train.ReduceLROnPlateau()
+    lr = 3e-9
+    for _ in range(4):
+        lr = p.update(1.0, lr)
+    assert lr == 1e-9                                                     # never below min_lr
+    s = train.EarlyStopping(patience=2)
+    assert [s.update(v) for v in (1.0, 1.0, 0.9, 0.9, 0.9)] == [False, False, False, False, True]
+
+
+def test_fit_replay_in_float64_meets_the_gpu_tests_thresholds():
+    """The condition tests/test_gpu_ftrain.py puts on the GPU's fit, met with room by the float64 replay: 40 Adam steps at batch 32,
+    lr 0.01, seed 0 on the synthetic set halve the train loss and reach 0.9 accuracy."""
+    x, y = fgrad_ref.fit_set()
+    host = fgrad_ref.HostTrainer(fnet_sweep.model(fgrad_ref.FIT_ROW))
+    hist = train.fit(host, x, y, epochs=100, batch_size=fgrad_ref.FIT_BATCH, seed=0, lr=fgrad_ref.FIT_LR, max_steps=fgrad_ref.FIT_STEPS)
+    assert hist["steps"] == 40
+    r = host.grad(x, y)
+    print("first epoch loss %.4f, last %.4f; final loss on the set %.4f, accuracy %.3f" % (hist["loss"][0], hist["loss"][-1], r["loss"].mean(),
+                                                                                           (r["argmax"] == y).mean()))
+    assert hist["loss"][-1] < 0.25 * hist["loss"][0] and (r["argmax"] == y).mean() >= 0.97

@@ -1,0 +1,319 @@
+"""GPU tests (-m gpu) of training the float32 network (edison_ftrain_*, Context.trainer, kws train) against
+tests/fgrad_ref.py, the float64 restatement on the float32 weights.
+
+The gradient bound is measured, not chosen: per tensor the metric is max |g - g64| / max |g64|; torch's CPU float32 autograd of the same
+network gets e32 by that metric at run time, and the GPU is allowed 4 e32 -- both are float32 sums of the same terms in different orders
+(MFMA four-deep chains and the slab reduce against torch's loops), a factor 4 covers the order, not a wrong term -- floored at
+8 x 2^-24 x sqrt(terms summed) so that a tensor where torch happens to be exact does not set a bound of zero. The loss per row is
+held the same way, its terms the k rows along the network plus the logits.
+
+Every network is loaded with 1e6 in the padding k rows, padding channels and padding biases of its blob: the packed gradient's padding
+must still be exactly +0.0f and a step must leave the weights' padding what it was.
+
+Measured on an MI355X, shipped network, n = 8 (GPU error / e32 per tensor, w then b): see DESIGN.md section 19."""
+import io
+import os
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN
+
+import fgrad_ref
+import fnet_pad
+import fnet_ref
+import fnet_sweep as fs
+from edison_amd import _lib, cube_import, train
+
+pytestmark = pytest.mark.gpu
+
+FIXTURE = os.path.join(GOLDEN, "cube_kws.ednf")
+ROWS = ["ladder_k5", "pool21_trunc_h", "pool12_trunc_w", "pool22_trunc_hw", "pool41_tail", "inc3_oc64_oc65_s21", "oc40_s32_span_h", "n_out_210",
+        "relu_logits", "conv_last_map", "layers16", "synth_pool12_relu", "cube_kws"]
+ALL_N = ("pool21_trunc_h", "inc3_oc64_oc65_s21")      # rows that run n over {1, batch - 1, batch, batch + 1, 3 batch + 2}
+EPS = 2.0 ** -24
+
+
+@pytest.fixture(scope="module")
+def ctx(built_lib):
+    from edison_amd.context import Context
+    c = Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def fresh(built_lib):
+    """A second context: a fresh load of an exported network."""
+    from edison_amd.context import Context
+    c = Context(0)
+    yield c
+    c.close()
+
+
+def poisoned(blob, value=1.0e6):
+    """The blob with `value` in every padding k row, padding channel and padding bias of its weights."""
+    model = cube_import.read_blob(blob)
+    lay, n = train.layout(model)
+    w = np.frombuffer(blob, "<f4", n, len(blob) - 4 * n).copy()
+    real = train.pack([dict(w=np.ones(r["shape"], np.float32), b=np.ones(r["out_c"], np.float32)) for r in lay], lay) != 0
+    w[~real] = value
+    return blob[:len(blob) - 4 * n] + w.astype("<f4").tobytes(), real
+
+
+_CASES = {}
+
+
+def case(name):
+    """(model, blob with poisoned padding, mask of the packed array's real entries) of a row, built once."""
+    if name not in _CASES:
+        if name == "cube_kws":
+            with open(FIXTURE, "rb") as f:
+                blob = f.read()
+        else:
+            blob = fs.blob(name)
+        bad, real = poisoned(blob)
+        _CASES[name] = (cube_import.read_blob(blob), bad, real)
+    return _CASES[name]
+
+
+def data(name, model, n):
+    in_n = int(np.prod(model["in_shape"]))
+    if name == "cube_kws":
+        g = np.load(os.path.join(GOLDEN, "cube_golden.npz"))
+        rows = np.stack([g["net_in_" + str(k)] for k in g["names"]]).astype(np.float32)
+        x = rows[np.arange(n) % len(rows)]
+    elif name == "relu_logits":
+        assert fs.ROWS[name][0]["sets"] == ["neg", "n1"]
+        x = np.ascontiguousarray(fs.inputs(name, 2 * n, in_n)[0::2])      # its all-negative inputs: every ReLU logit is zero
+    else:
+        x = fgrad_ref.inputs(name, n, in_n)
+    n_out = int(np.prod(fnet_ref.conv_records(model)[-1]["out"]))
+    return x, (np.arange(n) % n_out).astype(np.int32)
+
+
+def bounds(model, x, y, ref, n_total=None):
+    """Per record (bound of w, bound of b, e32 of w, e32 of b) and the loss's (bound, e32): 4 e32 floored at 8 x 2^-24 sqrt(terms)."""
+    import torch
+    t32 = fgrad_ref.torch_grads(model, x, y, torch.float32)
+    scale = 1.0 if n_total is None else len(y) / n_total               # torch's mean is over the rows it is given
+    out = []
+    for g32, g64, terms in zip(t32["grads"], ref["grads"], fgrad_ref.terms(model, len(y))):
+        floor = 8 * EPS * np.sqrt(terms)
+        e = [fgrad_ref.tensor_error(g32[k] * scale, g64[k]) for k in ("w", "b")]
+        out.append((max(4 * e[0], floor), max(4 * e[1], floor), e[0], e[1]))
+    chain = sum(int(np.prod(L["k"])) * L["inp"][2] for L in fnet_ref.conv_records(model)) + ref["logits"].shape[1]
+    el = fgrad_ref.tensor_error(t32["loss"], ref["loss"])
+    return out, (max(4 * el, 8 * EPS * np.sqrt(chain)), el)
+
+
+def check_gradient(name, tr, model, real, x, y, ref, n_total=None, report=None):
+    got = tr.gradients()
+    packed = tr.gradient()
+    assert not packed[~real].view(np.uint32).any(), "%s: a padding entry of the gradient is not +0.0f" % name
+    per, _ = bounds(model, x, y, ref, n_total)
+    for i, (g, g64, (bw, bb, ew, eb)) in enumerate(zip(got, ref["grads"], per)):
+        for k, bound, e32 in (("w", bw, ew), ("b", bb, eb)):
+            err = fgrad_ref.tensor_error(g[k], g64[k])
+            line = "%s n=%d record %d %s: gpu %.3g  e32 %.3g  bound %.3g" % (name, len(y), i, k, err, e32, bound)
+            print(line)
+            if report is not None:
+                report.append(line)
+            assert err <= bound, line
+
+
+@pytest.mark.parametrize("name", ROWS)
+def test_logits_loss_gradient_padding_repeat_and_no_side_effect(ctx, name):
+    model, blob, real = case(name)
+    ctx.fnet_load(blob)
+    with ctx.trainer() as tr:
+        info = tr.info()
+        b = info["batch"]
+        assert info["w_floats"] == len(real) and info["lds_bytes"] <= 160 * 1024 and info["grid"] >= 1 and info["steps"] == 0
+        ns = sorted({1, max(b - 1, 1), b, b + 1, 3 * b + 2}) if name in ALL_N else [b + 1]
+        w0 = tr.packed_weights()
+        for n in ns:
+            x, y = data(name, model, n)
+            ref = fgrad_ref.loss_grad(model, x, y)
+            before = ctx.fnet(x)
+            r = tr.grad(x, y)
+            # 1. the logits, bit for bit; the argmax is edison_fnet_batch's
+            assert np.array_equal(tr.logits(n).view(np.uint32), before["logits"].view(np.uint32)), (name, n)
+            assert np.array_equal(r["argmax"], before["argmax"])
+            # 2. the loss per row
+            _, (lb, le) = bounds(model, x, y, ref)
+            lerr = fgrad_ref.tensor_error(r["loss"], ref["loss"])
+            print("%s n=%d loss: gpu %.3g  e32 %.3g  bound %.3g" % (name, n, lerr, le, lb))
+            assert lerr <= lb, (name, n, lerr, lb)
+            # 3. every tensor's gradient, 4. the padding
+            check_gradient(name, tr, model, real, x, y, ref)
+            if name == "relu_logits":
+                assert not tr.gradient().any() and np.allclose(r["loss"], np.log(6.0), rtol=1e-6)
+            # 5. the same call again: the same bits
+            g1 = tr.gradient()
+            r2 = tr.grad(x, y)
+            assert np.array_equal(tr.gradient().view(np.uint32), g1.view(np.uint32)), (name, n)
+            assert np.array_equal(r2["loss"].view(np.uint32), r["loss"].view(np.uint32))
+            # 6. nothing else moved
+            assert np.array_equal(tr.packed_weights().view(np.uint32), w0.view(np.uint32))
+            after = ctx.fnet(x)
+            assert all(np.array_equal(before[k], after[k]) for k in before)
+
+
+def test_adam_steps_in_place_and_the_exported_network(ctx, fresh):
+    name = "pool21_trunc_h"
+    model, blob, real = case(name)
+    ctx.fnet_load(blob)
+    x, y = data(name, model, 17)
+    lr = 0.01
+    with ctx.trainer() as tr:
+        adam = fgrad_ref.Adam()
+        for step in range(3):
+            w_before = tr.packed_weights().astype(np.float64)
+            tr.grad(x, y)
+            g = tr.gradient().astype(np.float64)
+            tr.step(lr)
+            # the float64 restatement fed the GPU's own gradient and the weights the GPU stepped from; m and v run on in float64
+            want = [w_before.copy()]
+            adam.step(want, [g], lr)
+            got = tr.packed_weights()
+            for r in tr.layout:
+                nb = r["k_pad"] * r["n_pad"]
+                for lo, hi in ((r["w_at"], r["w_at"] + nb), (r["w_at"] + nb, r["w_at"] + nb + r["n_pad"])):
+                    m = real[lo:hi]
+                    err = np.abs(got[lo:hi][m] - want[0][lo:hi][m]).max() / np.abs(want[0][lo:hi][m]).max()
+                    print("step %d tensor at %d: %.3g (bound %.3g)" % (step + 1, lo, err, 4 * EPS))
+                    assert err <= 4 * EPS, (step, lo, err)
+            assert (got[~real] == np.float32(1.0e6)).all()          # zero gradient, zero m and v: the padding stays what it was
+            assert np.abs(got[real] - w_before[real]).max() > 0.5 * lr * 0.9    # and the step is lr-sized: Adam's first steps
+        assert tr.info()["steps"] == 3
+        # the context runs the new weights, and they are the exported network's
+        new = ctx.fnet(x)
+        exported = cube_import.build_blob(tr.model())
+        fresh.fnet_load(exported)
+        again = fresh.fnet(x)
+        assert np.array_equal(new["logits"].view(np.uint32), again["logits"].view(np.uint32))
+        assert not np.array_equal(new["logits"], fnet_logits_of(fresh, blob, x))
+        assert tr.export() == exported
+        # plain SGD, and reset
+        tr.set_opt("sgd")
+        w_before = tr.packed_weights().astype(np.float64)
+        tr.grad(x, y)
+        g = tr.gradient().astype(np.float64)
+        tr.step(0.1)
+        got = tr.packed_weights()
+        assert np.abs(got[real] - (w_before - 0.1 * g)[real]).max() <= 2 * EPS * np.abs(w_before[real]).max()
+        tr.reset()
+        assert tr.info()["steps"] == 0
+
+
+def fnet_logits_of(c, blob, x):
+    c.fnet_load(blob)
+    return c.fnet(x)["logits"]
+
+
+def test_refusals_and_the_ignored_counter(ctx):
+    torch = pytest.importorskip("torch")
+    # a padded network, by name
+    ctx.fnet_load(fnet_pad.blob("sym3x3"))
+    with pytest.raises(_lib.EdisonError) as e:
+        ctx.trainer()
+    assert e.value.code == _lib.E_NO_IMPL and "record 0" in str(e.value) and "pad" in str(e.value)
+    name = "pool21_trunc_h"
+    model, blob, real = case(name)
+    ctx.fnet_load(blob)
+    n = 9
+    x, y = data(name, model, n)
+    tr = ctx.trainer()
+    # a host label of n_out and of -1: refused before any launch, the gradient of the call before stays
+    tr.grad(x, y)
+    g0 = tr.gradient()
+    for bad in (3, -1):
+        yb = y.copy()
+        yb[4] = bad
+        with pytest.raises(_lib.EdisonError) as e:
+            tr.grad(x, yb)
+        assert e.value.code == _lib.E_ARGUMENT and "label" in str(e.value)
+    assert np.array_equal(tr.gradient(), g0)
+    # the device form: such rows contribute nothing and are counted
+    yb = y.copy()
+    yb[2], yb[7] = 3, -1
+    good = np.array([i for i in range(n) if i not in (2, 7)])
+    dev = torch.device("cuda", 0)
+    xt, yt = torch.from_numpy(x).to(dev), torch.from_numpy(yb).to(dev)
+    loss, am = torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
+    ctx.use_torch_stream()
+    try:
+        tr.grad_t(xt, yt, n, loss=loss, argmax=am)
+        assert tr.info()["ignored"] == 2
+        ref = fgrad_ref.loss_grad(model, x[good], y[good], n_total=n)
+        check_gradient(name, tr, model, real, x[good], y[good], ref, n_total=n)
+        lh = loss.cpu().numpy()
+        assert lh[2] == 0 and lh[7] == 0 and (lh[good] > 0).all()
+        assert np.array_equal(am.cpu().numpy(), ctx.fnet(x)["argmax"])
+        tr.reset()
+        assert tr.info()["ignored"] == 0
+    finally:
+        ctx.use_own_stream()
+    # a trainer after a reload
+    ctx.fnet_load(blob)
+    for call in (lambda: tr.grad(x, y), tr.gradient, lambda: tr.step(0.01), tr.info, tr.packed_weights, tr.reset, lambda: tr.set_opt("sgd")):
+        with pytest.raises(_lib.EdisonError) as e:
+            call()
+        assert e.value.code == _lib.E_NO_MODEL and "another float network was loaded" in str(e.value)
+    tr.close()
+    with ctx.trainer() as again:
+        again.grad(x, y)
+        assert np.array_equal(again.gradient(), g0)
+
+
+def test_a_network_that_fills_the_lds_trains_or_is_refused_by_name(ctx):
+    ctx.fnet_load(fs.blob("batch1_lds_max"))
+    try:
+        with ctx.trainer() as tr:
+            assert tr.info()["batch"] == 1 and tr.info()["lds_bytes"] <= 160 * 1024
+    except _lib.EdisonError as e:
+        assert e.code == _lib.E_NO_IMPL and "LDS" in str(e)
+
+
+def test_fit_learns_the_synthetic_set(ctx):
+    """40 Adam steps at batch 32, lr 0.01, seed 0 on three noisy class patterns: the train loss falls below half its first value and the
+    accuracy reaches 0.9 (conditions the float64 replay meets with room: tests/test_fgrad_cpu.py), and the last loss is the replay's."""
+    x, y = fgrad_ref.fit_set()
+    model = fs.model(fgrad_ref.FIT_ROW)
+    ctx.fnet_load(cube_import.build_blob(model))
+    kw = dict(epochs=100, batch_size=fgrad_ref.FIT_BATCH, seed=0, lr=fgrad_ref.FIT_LR, max_steps=fgrad_ref.FIT_STEPS)
+    with ctx.trainer() as tr:
+        hist = tr.fit(x, y, **kw)
+        assert hist["steps"] == 40 and tr.info()["steps"] == 40
+        acc = (ctx.fnet(x)["argmax"] == y).mean()
+    replay = train.fit(fgrad_ref.HostTrainer(model), x, y, **kw)
+    print("loss %.5f -> %.5f (float64 replay %.5f), accuracy %.3f" % (hist["loss"][0], hist["loss"][-1], replay["loss"][-1], acc))
+    assert hist["loss"][-1] < 0.5 * hist["loss"][0] and acc >= 0.9
+    assert abs(hist["loss"][-1] - replay["loss"][-1]) <= 1e-3 * replay["loss"][-1]
+    assert len(hist["loss"]) == len(replay["loss"]) == 14
+
+
+def test_kws_train_then_kws_quantize(ctx, tmp_path):
+    from edison_amd.kws import kws_quantize, kws_train
+    x, y = fgrad_ref.fit_set()
+    model = fs.model(fgrad_ref.FIT_ROW)
+    with open(tmp_path / "net.ednf", "wb") as f:
+        f.write(cube_import.build_blob(model, ["a", "b", "c"]))
+    np.save(tmp_path / "x.npy", x)
+    np.save(tmp_path / "y.npy", y)
+    out = io.StringIO()
+    blob, hist = kws_train.run(str(tmp_path / "net.ednf"), str(tmp_path / "x.npy"), str(tmp_path / "y.npy"), str(tmp_path / "out.ednf"), epochs=5,
+                               batch=32, lr=0.01, val=(str(tmp_path / "x.npy"), str(tmp_path / "y.npy")), ctx=ctx, out=out)
+    assert (tmp_path / "out.ednf").read_bytes() == blob and hist["steps"] == 15 and len(hist["val_loss"]) == 5
+    assert "epoch   5" in out.getvalue() and "val_loss" in out.getvalue() and "after 15 steps" in out.getvalue()
+    trained = cube_import.read_blob(blob)
+    assert trained["keywords"] == ["a", "b", "c"]
+    assert not np.array_equal(fnet_ref.conv_records(trained)[0]["w"], fnet_ref.conv_records(model)[0]["w"])
+    assert np.array_equal(ctx.fnet(x)["logits"], fnet_logits_of(ctx, blob, x))      # the context ran the trained weights already
+    # kws quantize takes it: 11 frames x 6 coefficients are the network's 11 x 6 x 1 input
+    rng = np.random.default_rng(8)
+    np.save(tmp_path / "audio.npy", np.clip(rng.normal(0, 3000, (6, 11 * 1024)), -32768, 32767).astype(np.int16))
+    qblob, rep = kws_quantize.run(str(tmp_path / "out.ednf"), str(tmp_path / "audio.npy"), str(tmp_path / "q.ednn"),
+                                  geometry="frame_count=11,num_mfcc=6,n_samples=11264", ctx=ctx, out=io.StringIO())
+    assert (tmp_path / "q.ednn").read_bytes() == qblob and len(rep["float_argmax"]) == 6

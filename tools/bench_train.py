@@ -1,0 +1,95 @@
+"""Training rate of the float32 network on the GPU (edison_ftrain_*): samples per second of one gradient call
+plus one Adam step on the shipped network (tests/golden/cube_kws.ednf) at batch 100 -- the reference's batch -- and at 4096, and beside
+them, from the same process, the forward-only rate of edison_fnet_batch on the same inputs: the yardstick a gradient is priced against.
+
+Device calls on the context's stream: inputs and labels are device tensors, nothing is staged. A region is `--region-ms` of calls
+between two host clock readings, ended by a device synchronise, so it holds the enqueue cost as well as the kernels; the legs alternate
+(train, forward, train, ...), `--repeats` regions each, after a warm-up of every shape. Reported per batch: the median over regions of
+samples per second, its minimum and maximum. The learning rate is 0, so the weights the forward leg runs never move.
+
+    python tools/bench_train.py [--batches 100,4096] [--repeats 7] [--region-ms 300] [--out FILE.json]
+
+One JSON line.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="100,4096")
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--region-ms", type=float, default=300.0)
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    import torch
+    from edison_amd.context import Context
+    if not torch.cuda.is_available():
+        sys.exit("bench_train: no GPU (there is no CPU path to time)")
+    ctx = Context(0)
+    ctx.fnet_load(os.path.join(ROOT, "tests", "golden", "cube_kws.ednf"))
+    info = ctx.fnet_info()
+    in_n, n_out = info["in_h"] * info["in_w"] * info["in_c"], info["n_out"]
+    dev = torch.device("cuda", 0)
+    ctx.use_torch_stream()
+    tr = ctx.trainer()
+    tinfo = tr.info()
+    rng = np.random.default_rng(19)
+    row = dict(network="cube_kws.ednf", device=torch.cuda.get_device_name(0), train_batch=tinfo["batch"], grid=tinfo["grid"], lds_bytes=tinfo["lds_bytes"],
+               w_floats=tinfo["w_floats"], repeats=args.repeats, region_ms=args.region_ms, results=[])
+    for n in [int(b) for b in args.batches.split(",")]:
+        x = torch.from_numpy(rng.normal(0, 30, (n, in_n)).astype(np.float32)).to(dev)
+        y = torch.from_numpy((np.arange(n) % n_out).astype(np.int32)).to(dev)
+        loss = torch.zeros(n, dtype=torch.float32, device=dev)
+        am = torch.zeros(n, dtype=torch.int32, device=dev)
+        logits = torch.zeros((n, n_out), dtype=torch.float32, device=dev)
+
+        def train_call():
+            tr.grad_t(x, y, n, loss=loss, argmax=am)
+            tr.step(0.0)
+
+        def forward_call():
+            ctx.fnet_t(x, n, logits=logits, argmax=am)
+
+        def region(call):
+            ctx.sync()
+            calls, t0 = 0, time.perf_counter()
+            while (time.perf_counter() - t0) * 1e3 < args.region_ms:
+                for _ in range(8):
+                    call()
+                calls += 8
+            ctx.sync()
+            return calls * n / (time.perf_counter() - t0)
+
+        for call in (train_call, forward_call):
+            for _ in range(5):
+                call()
+        ctx.sync()
+        rates = dict(train=[], forward=[])
+        for _ in range(args.repeats):
+            rates["train"].append(region(train_call))
+            rates["forward"].append(region(forward_call))
+        res = dict(batch=n)
+        for k, v in rates.items():
+            res[k + "_samples_per_s"] = dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v)))
+        res["train_over_forward"] = res["forward_samples_per_s"]["median"] / res["train_samples_per_s"]["median"]
+        row["results"].append(res)
+    tr.close()
+    ctx.use_own_stream()
+    ctx.close()
+    print(json.dumps(row), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(row, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
