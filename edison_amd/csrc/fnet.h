@@ -56,6 +56,12 @@ static inline size_t ed_fnet_lds_bytes(const ed_fnet_plan_t *p)
 	return sizeof(float) * ((size_t)p->batch * (size_t)(p->buf_n[0] + p->buf_n[1]) + (size_t)p->w_lds) + sizeof(int32_t) * (size_t)p->k_lds;
 }
 
+/* Whether a launcher may start the plan's workgroup with lds bytes of dynamic LDS (its own sum: ed_fnet_lds_bytes, or more behind it). */
+static inline int ed_fnet_plan_launchable(const ed_fnet_plan_t *p, size_t lds)
+{
+	return lds <= ED_FNET_LDS_BYTES && p->batch >= 1 && p->n_layers >= 1 && p->n_layers <= ED_FNET_MAX_LAYERS;
+}
+
 /* n utterances -> logits / probs [n][n_out] (NULL: not written), argmax [n] (NULL: not written); acts != NULL also dumps every layer's
  * output [n][acts_n]. Utterance u is the in_n floats at in + u * in_stride: in_stride = in_n for inputs back to back, num_mfcc for the
  * overlapping windows of a stream's feature rows (edison_stream_float). Returns a hipError_t. */

@@ -1,9 +1,17 @@
 /*
- * fnet_device.h -- the device code of the float32 network kernels: the work item edf_tile and the body of a workgroup,
- * EDF_NETWORK_BODY, shared by ed_fnet_kernel (fnet_kernels.hip: utterances one stride apart) and ed_fnet_windows_kernel
- * (fnet_windows_kernels.hip: the windows of a bank of microphones, two strides). The tiling, the k-ordered fmaf chain, the epilogue, the
- * softmax and the LDS plan exist once, here; a kernel differs only in how the utterances of its tile find their input.
- * DESIGN.md sections 14, 14b (padded records: PAD = true) and 15a. Not part of the public ABI.
+ * fnet_device.h -- the device code of every kernel that takes a tile of utterances through the float32 network in LDS. It exists once,
+ * here, in named pieces:
+ *   EDF_LDS_PLAN      the LDS pointers of a plan p
+ *   edf_tile          the work item: the tiling, the k-ordered fmaf chain, the epilogue of bias, ReLU and pool, the per-layer dump;
+ *                     its sink sees every value before ReLU (pre) and every pooled output (out)
+ *   EDF_LAYER_WALK    one record by the whole workgroup: staging into LDS, the two syncs, the item loop, the nt and pad dispatch
+ *   EDF_SOFTMAX       the softmax of one utterance and its first maximum
+ *   EDF_NETWORK_BODY  the body of a forward kernel on those pieces
+ * ed_fnet_kernel and ed_fnet_windows_kernel (EDF_NETWORK_BODY, edf_no_sink) differ in how the utterances of a tile find their input;
+ * ed_fnet_calib_kernel (fnet_calib_kernels.hip) walks with edfc_sink, its statistic in pre; ed_ftrain_grad_kernel
+ * (fnet_grad_kernels.hip) expands the plan, the walk and the softmax over a work item of its own. The plan, the walk and the softmax are
+ * textual and the tile is a function: DESIGN.md section 14 says why, and why the trainer keeps its work item.
+ * DESIGN.md sections 14, 14b (padded records: PAD = true), 15a, 18 and 19. Not part of the public ABI.
  */
 #ifndef EDISON_FNET_DEVICE_H
 #define EDISON_FNET_DEVICE_H
@@ -48,12 +56,18 @@ __device__ __forceinline__ void edf_pad_live(const ed_fnet_layer_t &L, const int
 }
 
 /* One work item: 16 output rows (M tile mt) x NT tiles of 16 channels starting at n0. PAD = false is a record without pads; PAD = true
- * reads the record's origins and kyx (kl + k_pad), gathers through edf_pad_tap and leaves absent rows out of the pool's max. */
-template <int NT, bool PAD = false>
+ * reads the record's origins and kyx (kl + k_pad), gathers through edf_pad_tap and leaves absent rows out of the pool's max.
+ * acts != NULL: every pooled output also goes to the per-layer dump of utterance u0 + u, acts_n floats per utterance. The dump is a
+ * __restrict__ parameter and not a sink's member on purpose: as a member the forward kernels compile to other instructions and measured
+ * 1.7 % slower.
+ * The sink sees what a kernel wants beside that: sink.pre(v, real) every accumulator element after the bias add and before ReLU (real:
+ * neither a padding row of the last M tile nor an absent one), sink.out(L, u, q, n, x, v) every pooled output x after its stores, with
+ * the window's P elements v[0 .. P - 1] as the max saw them. */
+template <int NT, bool PAD, class SINK>
 __device__ __forceinline__ void edf_tile(const ed_fnet_layer_t &L, const float *__restrict__ src, int src_n, float *__restrict__ dst, int dst_n,
                                          const float *__restrict__ wl, const int32_t *__restrict__ kl, const int32_t *__restrict__ rowin,
                                          const float *__restrict__ bias, int M, int mt, int n0, int lane, float *__restrict__ acts,
-                                         int64_t acts_n, int64_t u0)
+                                         int64_t acts_n, int64_t u0, SINK &sink)
 {
 	const int r = lane & 15, kq = lane >> 4;
 	const int m = mt * 16 + r;
@@ -89,13 +103,15 @@ __device__ __forceinline__ void edf_tile(const ed_fnet_layer_t &L, const float *
 	for (int j = 0; j < NT; j++)
 	{
 		const int n = n0 + 16 * j + r;
-		if (n >= L.out_c) continue;
+		if (n >= L.out_c) continue; /* a padding channel: not seen, not written */
 		const float b = bias[n];
 		float v[4];
 #pragma unroll
 		for (int i = 0; i < 4; i++)
 		{
 			v[i] = acc[j][i] + b;
+			if constexpr (PAD) sink.pre(v[i], live[i]);
+			else sink.pre(v[i], m0 + i < M);
 			if (L.relu) v[i] = fmaxf(v[i], 0.0f);
 			if constexpr (PAD) { if (!live[i]) v[i] = -INFINITY; } /* absent: the max's identity; its window has a real element */
 		}
@@ -109,89 +125,116 @@ __device__ __forceinline__ void edf_tile(const ed_fnet_layer_t &L, const float *
 			const int u = mg / L.rows, q = (mg - u * L.rows) / P;
 			dst[u * dst_n + q * L.out_c + n] = x;
 			if (acts) acts[(u0 + u) * acts_n + L.acts_at + q * L.out_c + n] = x;
+			sink.out(L, u, q, n, x, v + g);
 		}
 	}
 }
 
-/* The body of a kernel `(ed_fnet_plan_t p, ..., int64_t n, float *logits, float *probs, int32_t *argmax, float *acts)`: the workgroup of
- * blockIdx.x takes the tile of utterances u0 = blockIdx.x * batch .. u0 + nu - 1 of the launch's n through the network. The argument is
- * the kernel's own statement that puts utterance u0 + u's p.in_n input floats at buf[0] + u * p.buf_n[0] for u < nu (it sees p, buf, u0,
- * nu and tid); outputs go to rows u0 .. of logits / probs / argmax (NULL: not written) and, with acts, of the per-layer dump.
- * Expanded textually, as mfcc_geom_frames.inc is included: as a __forceinline__ function template over a loader the same body compiled
- * to another instruction order in ed_fnet_kernel (the compiler simplifies a callee on its own before it inlines it), and that kernel's
- * instructions stay as they were. */
-#define EDF_NETWORK_BODY(...)                                                                                                              \
+/* The sink of a kernel that wants nothing beside the tile's outputs: the forward kernels'. */
+struct edf_no_sink
+{
+	__device__ __forceinline__ void pre(float, bool) {}
+	__device__ __forceinline__ void out(const ed_fnet_layer_t &, int, int, int, float, const float *) {}
+};
+
+/* The plan's LDS, declared in a kernel whose plan is p (by value, or a reference into device memory): two activation buffers of
+ * p.batch utterances each, the record's weights wl, its k tables kl; and the thread's place in the workgroup. */
+#define EDF_LDS_PLAN                                                                                                                       \
 	extern __shared__ float lds[];                                                                                                         \
 	const int B = p.batch;                                                                                                                 \
 	float *buf[2] = {lds, lds + B * p.buf_n[0]};                                                                                           \
 	float *wl = lds + B * (p.buf_n[0] + p.buf_n[1]);                                                                                       \
 	int32_t *kl = (int32_t *)(wl + p.w_lds);                                                                                               \
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = ED_FNET_THREADS / 64;                                         \
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = ED_FNET_THREADS / 64;
+
+/* One work item of a walk: its nt <= 4 channel tiles pick the instantiation. */
+template <bool PAD, class SINK>
+__device__ __forceinline__ void edf_item(int nt, const ed_fnet_layer_t &L, const float *__restrict__ src, int src_n, float *__restrict__ dst, int dst_n,
+                                         const float *__restrict__ wl, const int32_t *__restrict__ kl, const int32_t *__restrict__ rowin,
+                                         const float *__restrict__ bias, int M, int mt, int n0, int lane, float *__restrict__ acts,
+                                         int64_t acts_n, int64_t u0, SINK &sink)
+{
+	if (nt == 4) edf_tile<4, PAD>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, acts_n, u0, sink);
+	else if (nt == 3) edf_tile<3, PAD>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, acts_n, u0, sink);
+	else if (nt == 2) edf_tile<2, PAD>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, acts_n, u0, sink);
+	else edf_tile<1, PAD>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, acts_n, u0, sink);
+}
+
+/* The walk of one record L by the whole workgroup: nu utterances from buf[L.src] to buf[L.dst], every work item through
+ * ITEM<pad>(nt, ..., acts, acts_n, u0, sink): edf_item, or a kernel's own with that signature. Expanded behind EDF_LDS_PLAN where nu is in
+ * scope. PADS is a constant: false leaves the padded instantiations out of a kernel that refuses padded records. The first __syncthreads
+ * stands behind everything the kernel did since its last walk. */
+#define EDF_LAYER_WALK(PADS, ITEM, L, acts, acts_n, u0, sink)                                                                              \
+	{                                                                                                                                      \
+		const float *gw = p.w + (L).w_at;                                                                                                  \
+		__syncthreads(); /* the previous layer's outputs are written and its weights no longer read */                                     \
+		{                                                                                                                                  \
+			const int nw = (L).k_pad * (L).n_pad; /* a multiple of 64: float4 copies */                                                    \
+			const float4 *g4 = (const float4 *)gw;                                                                                         \
+			float4 *l4 = (float4 *)wl;                                                                                                     \
+			for (int i = tid; i < nw / 4; i += ED_FNET_THREADS) l4[i] = g4[i];                                                             \
+			const int nk = (PADS) && (L).pad ? 2 * (L).k_pad : (L).k_pad; /* a padded record: kyx behind koff */                           \
+			for (int i = tid; i < nk; i += ED_FNET_THREADS) kl[i] = p.tab[(L).koff_at + i];                                                \
+		}                                                                                                                                  \
+		__syncthreads();                                                                                                                   \
+		const float *src = buf[(L).src];                                                                                                   \
+		float *dst = buf[(L).dst];                                                                                                         \
+		const int src_n = p.buf_n[(L).src], dst_n = p.buf_n[(L).dst];                                                                      \
+		const int32_t *rowin = p.tab + (L).rowin_at;                                                                                       \
+		const float *bias = gw + (int64_t)(L).k_pad * (L).n_pad;                                                                           \
+		const int M = nu * (L).rows;                                                                                                       \
+		const int MT = (M + 15) / 16, NT = (L).n_pad / 16, NG = (NT + 3) / 4;                                                              \
+		for (int item = wave; item < MT * NG; item += n_waves)                                                                             \
+		{                                                                                                                                  \
+			const int mt = item / NG, g = item - mt * NG;                                                                                  \
+			const int n0 = g * 64, nt = NT - 4 * g < 4 ? NT - 4 * g : 4;                                                                   \
+			if ((PADS) && (L).pad)                                                                                                         \
+			{                                                                                                                              \
+				if constexpr (PADS) ITEM<true>(nt, L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, acts_n, u0, sink); \
+			}                                                                                                                              \
+			else ITEM<false>(nt, L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, acts_n, u0, sink);                 \
+		}                                                                                                                                  \
+	}
+
+/* One utterance's softmax (forward_sm: exp(z - max) / sum) over the n_out logits at z: declares mx (the maximum), s (the sum of
+ * exp(z - mx)) and best (the first maximum of the probabilities); the argument is the statement that takes probability pj of class j. */
+#define EDF_SOFTMAX(z, n_out, ...)                                                                                                         \
+	float mx = (z)[0];                                                                                                                     \
+	for (int j = 1; j < (n_out); j++) mx = fmaxf(mx, (z)[j]);                                                                              \
+	float s = 0.0f;                                                                                                                        \
+	for (int j = 0; j < (n_out); j++) s += expf((z)[j] - mx);                                                                              \
+	int best = 0;                                                                                                                          \
+	float bp = -1.0f;                                                                                                                      \
+	for (int j = 0; j < (n_out); j++)                                                                                                      \
+	{                                                                                                                                      \
+		const float pj = expf((z)[j] - mx) / s;                                                                                            \
+		__VA_ARGS__                                                                                                                        \
+		if (pj > bp) { bp = pj; best = j; }                                                                                                \
+	}
+
+/* The body of a kernel `(ed_fnet_plan_t p, ..., int64_t n, float *logits, float *probs, int32_t *argmax, float *acts)`: the workgroup of
+ * blockIdx.x takes the tile of utterances u0 = blockIdx.x * batch .. u0 + nu - 1 of the launch's n through the network. The argument is
+ * the kernel's own statement that puts utterance u0 + u's p.in_n input floats at buf[0] + u * p.buf_n[0] for u < nu (it sees p, buf, u0,
+ * nu and tid); outputs go to rows u0 .. of logits / probs / argmax (NULL: not written) and, with acts, of the per-layer dump. */
+#define EDF_NETWORK_BODY(...)                                                                                                              \
+	EDF_LDS_PLAN                                                                                                                           \
 	const int64_t u0 = (int64_t)blockIdx.x * B;                                                                                            \
 	const int nu = (int)(n - u0 < B ? n - u0 : B);                                                                                         \
                                                                                                                                            \
 	/* the network input of the tile's utterances into buffer 0 */                                                                         \
 	__VA_ARGS__                                                                                                                            \
                                                                                                                                            \
-	for (int l = 0; l < p.n_layers; l++)                                                                                                   \
-	{                                                                                                                                      \
-		const ed_fnet_layer_t &L = p.L[l];                                                                                                 \
-		const float *gw = p.w + L.w_at;                                                                                                    \
-		__syncthreads(); /* the previous layer's outputs are written and its weights no longer read */                                     \
-		{                                                                                                                                  \
-			const int nw = L.k_pad * L.n_pad; /* a multiple of 64: float4 copies */                                                        \
-			const float4 *g4 = (const float4 *)gw;                                                                                         \
-			float4 *l4 = (float4 *)wl;                                                                                                     \
-			for (int i = tid; i < nw / 4; i += ED_FNET_THREADS) l4[i] = g4[i];                                                             \
-			const int nk = L.pad ? 2 * L.k_pad : L.k_pad; /* a padded record: kyx behind koff */                                           \
-			for (int i = tid; i < nk; i += ED_FNET_THREADS) kl[i] = p.tab[L.koff_at + i];                                                  \
-		}                                                                                                                                  \
-		__syncthreads();                                                                                                                   \
-		const float *src = buf[L.src];                                                                                                     \
-		float *dst = buf[L.dst];                                                                                                           \
-		const int src_n = p.buf_n[L.src], dst_n = p.buf_n[L.dst];                                                                          \
-		const int32_t *rowin = p.tab + L.rowin_at;                                                                                         \
-		const float *bias = gw + (int64_t)L.k_pad * L.n_pad;                                                                               \
-		const int M = nu * L.rows;                                                                                                         \
-		const int MT = (M + 15) / 16, NT = L.n_pad / 16, NG = (NT + 3) / 4;                                                                \
-		for (int item = wave; item < MT * NG; item += n_waves)                                                                             \
-		{                                                                                                                                  \
-			const int mt = item / NG, g = item - mt * NG;                                                                                  \
-			const int n0 = g * 64, nt = NT - 4 * g < 4 ? NT - 4 * g : 4;                                                                   \
-			if (L.pad)                                                                                                                     \
-			{                                                                                                                              \
-				if (nt == 4) edf_tile<4, true>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);       \
-				else if (nt == 3) edf_tile<3, true>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);  \
-				else if (nt == 2) edf_tile<2, true>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);  \
-				else edf_tile<1, true>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);               \
-			}                                                                                                                              \
-			else if (nt == 4) edf_tile<4>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);            \
-			else if (nt == 3) edf_tile<3>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);            \
-			else if (nt == 2) edf_tile<2>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);            \
-			else edf_tile<1>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, p.acts_n, u0);                         \
-		}                                                                                                                                  \
-	}                                                                                                                                      \
+	edf_no_sink sink;                                                                                                                      \
+	for (int l = 0; l < p.n_layers; l++) EDF_LAYER_WALK(true, edf_item, p.L[l], acts, p.acts_n, u0, sink)                                  \
 	__syncthreads();                                                                                                                       \
                                                                                                                                            \
-	/* softmax (forward_sm: exp(z - max) / sum) and the first maximum of the probabilities, one thread per utterance */                    \
+	/* one thread per utterance */                                                                                                         \
 	if (tid < nu)                                                                                                                          \
 	{                                                                                                                                      \
 		const ed_fnet_layer_t &L = p.L[p.n_layers - 1];                                                                                    \
 		const float *z = buf[L.dst] + tid * p.buf_n[L.dst];                                                                                \
 		const int64_t u = u0 + tid;                                                                                                        \
-		float mx = z[0];                                                                                                                   \
-		for (int j = 1; j < p.n_out; j++) mx = fmaxf(mx, z[j]);                                                                            \
-		float s = 0.0f;                                                                                                                    \
-		for (int j = 0; j < p.n_out; j++) s += expf(z[j] - mx);                                                                            \
-		int best = 0;                                                                                                                      \
-		float bp = -1.0f;                                                                                                                  \
-		for (int j = 0; j < p.n_out; j++)                                                                                                  \
-		{                                                                                                                                  \
-			const float pj = expf(z[j] - mx) / s;                                                                                          \
-			if (logits) logits[u * p.n_out + j] = z[j];                                                                                    \
-			if (probs) probs[u * p.n_out + j] = pj;                                                                                        \
-			if (pj > bp) { bp = pj; best = j; }                                                                                            \
-		}                                                                                                                                  \
+		EDF_SOFTMAX(z, p.n_out, if (logits) logits[u * p.n_out + j] = z[j]; if (probs) probs[u * p.n_out + j] = pj;)                       \
 		if (argmax) argmax[u] = best;                                                                                                      \
 	}
 

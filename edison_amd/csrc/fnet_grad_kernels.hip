@@ -8,11 +8,13 @@
  * ed_ftrain_reduce_kernel then sums the slabs in index order. No float atomic anywhere: every slab element has one owner lane, and
  * the order of every sum is fixed by (n, batch, grid), so a call repeated gives the same bits.
  *
- *   forward   ed_fnet_kernel's (fnet_device.h): the same LDS plan, the same tiling and edf_tile's k-ordered MFMA loop and epilogue
- *             order in edg_tile, so the logits are edison_fnet_batch's bit for bit. edg_tile also writes every pooled output to the
- *             workgroup's activation store in global memory (the A operand of dW) and beside it one mask byte: which element of the
- *             pool window was the first maximum, and whether its gradient passes (no ReLU, or a pre-activation > 0).
- *   loss      one thread per utterance: loss = log sum exp(z - max) + max - z[y], dz = (softmax(z) - onehot(y)) / n.
+ *   forward   ed_fnet_kernel's own LDS plan and layer walk (fnet_device.h: EDF_LDS_PLAN, EDF_LAYER_WALK) over the work item edg_tile:
+ *             edf_tile's k-ordered MFMA loop and epilogue order, so the logits are edison_fnet_batch's bit for bit, with an epilogue
+ *             specialised by P that also writes every pooled output to the workgroup's activation store in global memory (the A
+ *             operand of dW) and beside it one mask byte: which element of the pool window was the first maximum, and whether its
+ *             gradient passes (no ReLU, or a pre-activation > 0). The shared tile with these stores in a sink was measured 3 to 6 %
+ *             slower, so this one copy of the tile stays.
+ *   loss      one thread per utterance on the network's EDF_SOFTMAX: loss = log sum exp(z - max) + max - z[y], dz = (softmax(z) - onehot(y)) / n.
  *   backward  per record, last to first, with LDS reused (the forward half is done with it):
  *     dY   [rows of the tile][n_pad] in LDS, from the gradient of the pooled outputs and the mask bytes: the window's winner gets it,
  *          every other element, every padding channel and every row beyond the tile is +0.0f. No second comparison.
@@ -107,6 +109,26 @@ __device__ __forceinline__ void edg_tile(const ed_fnet_layer_t &L, const float *
 			emit(m0, x, v[0] == x ? 0 : v[1] == x ? 1 : v[2] == x ? 2 : 3);
 		}
 	}
+}
+
+/* The walk's work item for training (EDF_LAYER_WALK of fnet_device.h): edg_tile by the item's nt <= 4 channel tiles. */
+struct edg_stores
+{
+	float *__restrict__ acts;
+	uint8_t *__restrict__ mask;
+	int acts_n;
+};
+
+template <bool PAD>
+__device__ __forceinline__ void edg_item(int nt, const ed_fnet_layer_t &L, const float *__restrict__ src, int src_n, float *__restrict__ dst, int dst_n,
+                                         const float *__restrict__ wl, const int32_t *__restrict__ kl, const int32_t *__restrict__ rowin,
+                                         const float *__restrict__ bias, int M, int mt, int n0, int lane, float *, int64_t, int64_t, const edg_stores &st)
+{
+	static_assert(!PAD, "records without pads only");
+	if (nt == 4) edg_tile<4>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
+	else if (nt == 3) edg_tile<3>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
+	else if (nt == 2) edg_tile<2>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
+	else edg_tile<1>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
 }
 
 /* dW of 16 k rows (k tile kt; kt == KT is the bias row: A = 1 in row 0) x NT tiles of 16 channels from n0, summed over the tile's M rows
@@ -214,18 +236,12 @@ __global__ __launch_bounds__(ED_FNET_THREADS) void ed_ftrain_grad_kernel(const e
                                                                            int32_t *__restrict__ argmax, float *__restrict__ logits,
                                                                            unsigned long long *__restrict__ ignored)
 {
-	extern __shared__ float lds[];
 	const ed_ftrain_plan_t &t = *tp; /* in device memory, read where it is used: by value its fields stay live in SGPRs and spill */
 	const ed_fnet_plan_t &p = t.net;
-	const int B = p.batch;
-	/* forward half: ed_fnet_kernel's plan */
-	float *const buf0 = lds, *const buf1 = lds + B * p.buf_n[0];
-	float *wl = lds + B * (p.buf_n[0] + p.buf_n[1]);
-	int32_t *kl = (int32_t *)(wl + p.w_lds);
+	EDF_LDS_PLAN /* the forward half: ed_fnet_kernel's plan */
 	/* backward half, over it */
 	float *dy = lds;
 	int32_t *rb = (int32_t *)(lds + t.dy_lds);
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = ED_FNET_THREADS / 64;
 	const int acts_n = p.acts_n;
 	float *slab = t.slabs + (int64_t)blockIdx.x * t.w_floats;
 	float *acts = t.acts + (int64_t)blockIdx.x * B * acts_n;
@@ -243,65 +259,25 @@ __global__ __launch_bounds__(ED_FNET_THREADS) void ed_ftrain_grad_kernel(const e
 		for (int i = tid; i < nu * p.in_n; i += ED_FNET_THREADS)
 		{
 			const int u = i / p.in_n, e = i - u * p.in_n;
-			buf0[u * p.buf_n[0] + e] = x0[i];
+			buf[0][u * p.buf_n[0] + e] = x0[i];
 		}
 
-		/* ---- forward ---- */
-		for (int l = 0; l < p.n_layers; l++)
-		{
-			const ed_fnet_layer_t &L = p.L[l];
-			const float *gw = p.w + L.w_at;
-			__syncthreads(); /* the previous layer's outputs are written and its weights no longer read */
-			{
-				const int nw = L.k_pad * L.n_pad; /* a multiple of 64: float4 copies */
-				const float4 *g4 = (const float4 *)gw;
-				float4 *l4 = (float4 *)wl;
-				for (int i = tid; i < nw / 4; i += ED_FNET_THREADS) l4[i] = g4[i];
-				for (int i = tid; i < L.k_pad; i += ED_FNET_THREADS) kl[i] = p.tab[L.koff_at + i];
-			}
-			__syncthreads();
-			const float *src = L.src ? buf1 : buf0;
-			float *dst = L.dst ? buf1 : buf0;
-			const int src_n = p.buf_n[L.src], dst_n = p.buf_n[L.dst];
-			const int32_t *rowin = p.tab + L.rowin_at;
-			const float *bias = gw + (int64_t)L.k_pad * L.n_pad;
-			const int M = nu * L.rows;
-			const int MT = (M + 15) / 16, NT = L.n_pad / 16, NG = (NT + 3) / 4;
-			for (int item = wave; item < MT * NG; item += n_waves)
-			{
-				const int mt = item / NG, g = item - mt * NG;
-				const int n0 = g * 64, nt = NT - 4 * g < 4 ? NT - 4 * g : 4;
-				if (nt == 4) edg_tile<4>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, mask, acts_n);
-				else if (nt == 3) edg_tile<3>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, mask, acts_n);
-				else if (nt == 2) edg_tile<2>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, mask, acts_n);
-				else edg_tile<1>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, acts, mask, acts_n);
-			}
-		}
+		/* ---- forward: the network's own walk over edg_tile (records without pads only: the host refuses the others) ---- */
+		const edg_stores stores = {acts, mask, acts_n};
+		for (int l = 0; l < p.n_layers; l++) EDF_LAYER_WALK(false, edg_item, p.L[l], (float *)NULL, 0, 0, stores)
 		__syncthreads();
 
 		/* ---- loss and dL/dz, one thread per utterance (the softmax and the argmax are ed_fnet_kernel's) ---- */
 		if (tid < nu)
 		{
 			const ed_fnet_layer_t &L = p.L[p.n_layers - 1];
-			const float *z = (L.dst ? buf1 : buf0) + tid * p.buf_n[L.dst];
+			const float *z = buf[L.dst] + tid * p.buf_n[L.dst];
 			float *dz = dacts + tid * acts_n + L.acts_at;
 			const int64_t u = u0 + tid;
 			const int y = labels[u];
 			const bool labelled = (unsigned)y < (unsigned)p.n_out;
-			float mx = z[0];
-			for (int j = 1; j < p.n_out; j++) mx = fmaxf(mx, z[j]);
-			float s = 0.0f;
-			for (int j = 0; j < p.n_out; j++) s += expf(z[j] - mx);
 			const float nf = (float)n;
-			int best = 0;
-			float bp = -1.0f;
-			for (int j = 0; j < p.n_out; j++)
-			{
-				const float pj = expf(z[j] - mx) / s;
-				logits[u * p.n_out + j] = z[j];
-				if (pj > bp) { bp = pj; best = j; }
-				dz[j] = labelled ? (pj - (j == y ? 1.0f : 0.0f)) / nf : 0.0f;
-			}
+			EDF_SOFTMAX(z, p.n_out, logits[u * p.n_out + j] = z[j]; dz[j] = labelled ? (pj - (j == y ? 1.0f : 0.0f)) / nf : 0.0f;)
 			if (argmax) argmax[u] = best;
 			if (loss) loss[u] = labelled ? logf(s) + mx - z[y] : 0.0f;
 			if (!labelled) atomicAdd(ignored, 1ull);
@@ -399,7 +375,7 @@ extern "C" int ed_launch_ftrain_grad(const ed_ftrain_plan_t *t, const ed_ftrain_
 	if (n <= 0) return 0;
 	const ed_fnet_plan_t *p = &t->net;
 	const size_t lds = ed_ftrain_lds_bytes(t);
-	if (lds > ED_FNET_LDS_BYTES || p->batch < 1 || p->n_layers < 1 || p->n_layers > ED_FNET_MAX_LAYERS || grid < 1) return (int)hipErrorInvalidValue;
+	if (!ed_fnet_plan_launchable(p, lds) || grid < 1) return (int)hipErrorInvalidValue;
 	{ const int e = ed_kernel_prepare((const void *)ed_ftrain_grad_kernel, ED_FNET_THREADS, lds, NULL, NULL); if (e) return e; }
 	const int64_t n_tiles = (n + p->batch - 1) / p->batch;
 	const int used = (int)(n_tiles < grid ? n_tiles : grid); /* a workgroup without a tile would leave its slab stale */

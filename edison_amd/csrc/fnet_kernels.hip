@@ -17,6 +17,8 @@
  * instantiation: rowin holds the window's origin, a second k table (ky, kx), and a tap outside the image is the operand +0.0f of the
  * same chain; an element of a pool window outside the conv's map is -inf in the max. Records without pads run PAD = false.
  * No scratch memory: everything is registers and LDS.
+ * All of that is fnet_device.h's text (the LDS plan, the tile, the walk, the softmax), which the bank's, the calibrator's and the
+ * trainer's kernels expand too; this kernel's own is the statement that loads a tile's inputs.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,7 +44,7 @@ extern "C" int ed_launch_fnet(const ed_fnet_plan_t *p, const float *in, int64_t 
 	if (n <= 0) return 0;
 	if (in_stride < 0) return (int)hipErrorInvalidValue;
 	const size_t lds = ed_fnet_lds_bytes(p);
-	if (lds > ED_FNET_LDS_BYTES || p->batch < 1 || p->n_layers < 1 || p->n_layers > ED_FNET_MAX_LAYERS) return (int)hipErrorInvalidValue;
+	if (!ed_fnet_plan_launchable(p, lds)) return (int)hipErrorInvalidValue;
 	{ const int e = ed_kernel_prepare((const void *)ed_fnet_kernel, ED_FNET_THREADS, lds, NULL, NULL); if (e) return e; }
 	const int64_t blocks = (n + p->batch - 1) / p->batch;
 	if (blocks > INT32_MAX) return (int)hipErrorInvalidValue;

@@ -1,6 +1,6 @@
 /*
  * fnet_windows_kernels.hip -- the float32 X-CUBE-AI network over the windows of a bank of microphones (edison_float_bank.hip, DESIGN.md
- * section 15a): ed_fnet_kernel's workgroup (fnet_device.h: the same tiling, k-ordered fmaf chain, epilogue, softmax and LDS plan) whose
+ * section 15a): ed_fnet_kernel's workgroup (fnet_device.h's EDF_NETWORK_BODY: the one tile, walk, softmax and LDS plan) whose
  * utterances find their input by TWO strides. Utterance U of the launch is frame i = U / n_mics of microphone m = U % n_mics: its in_n
  * input floats start at in + m * mic_stride + i * frame_stride -- window i of the push in microphone m's sliding buffer, read in place --
  * and its outputs go to row U, the time-major order [n][n_mics] of every output of a bank. A tile of `batch` utterances may straddle
@@ -50,7 +50,7 @@ extern "C" int ed_launch_fnet_windows(const ed_fnet_plan_t *p, const float *in, 
 		return 0;
 	}
 	const size_t lds = ed_fnet_lds_bytes(p);
-	if (lds > ED_FNET_LDS_BYTES || p->batch < 1 || p->n_layers < 1 || p->n_layers > ED_FNET_MAX_LAYERS) return (int)hipErrorInvalidValue;
+	if (!ed_fnet_plan_launchable(p, lds)) return (int)hipErrorInvalidValue;
 	{ const int e = ed_kernel_prepare((const void *)ed_fnet_windows_kernel, ED_FNET_THREADS, lds, NULL, NULL); if (e) return e; }
 	const int64_t blocks = (total + p->batch - 1) / p->batch;
 	hipLaunchKernelGGL(ed_fnet_windows_kernel, dim3((unsigned)blocks), dim3(ED_FNET_THREADS), lds, stream, *p, in, mic_stride, n_mics, frame_stride,

@@ -32,6 +32,27 @@ def conv_records(model):
     return fnet_ref.conv_records(model)
 
 
+TIE_POOLS = ((1, 2), (2, 1), (2, 2), (4, 1), (1, 4))
+
+
+def tie_case(pool, n=17):
+    """(model, x [n][36], labels) whose pool windows tie exactly, without ReLU: a 2 x 2 conv to 3 channels on a 6 x 6 x 1 image, pool
+    `pool` over its 5 x 5 map (truncating), a dense layer to 3 logits. The image is 0 / 1, the conv weights are +-0.5 / +-1 and the
+    biases quarters, so every conv output is a sum that float32 holds exactly in any order and takes one of a few values: the first
+    maximum of a window is tied at every element position. Channel 2 has zero weights: all its windows tie in every element."""
+    rng = np.random.default_rng(77 + 10 * pool[0] + pool[1])
+    recs = fnet_sweep._records((6, 6, 1), [("conv", 3, (2, 2), (1, 1), tuple(pool), 0), ("dense", 3, 0)])
+    recs[0]["w"] = rng.choice([-1.0, -0.5, 0.5, 1.0], (3, 2, 2, 1)).astype(np.float32)
+    recs[0]["w"][2] = 0.0
+    recs[0]["b"] = np.array([0.25, -0.5, 0.75], np.float32)
+    k = int(np.prod(recs[1]["inp"]))
+    recs[1]["w"] = (rng.normal(0, 1, (3,) + tuple(recs[1]["k"]) + (3,)) / np.sqrt(k)).astype(np.float32)
+    recs[1]["b"] = rng.normal(0, 0.1, 3).astype(np.float32)
+    recs.append(dict(type=cube_import.T_SOFTMAX, inp=recs[1]["out"], out=recs[1]["out"]))
+    x = rng.integers(0, 2, (n, 36)).astype(np.float32)
+    return dict(in_shape=(6, 6, 1), layers=recs), x, (np.arange(n) % 3).astype(np.int32)
+
+
 def _cols(L, x):
     kh, kw = L["k"]
     sh, sw = L["s"]

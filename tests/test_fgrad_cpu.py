@@ -88,6 +88,56 @@ def test_first_maximum_and_relu_at_zero():
     assert dead["w"].reshape(-1)[0] == 0 and dead["b"][0] == 0             # ReLU'(0) = 0
 
 
+def _routed_dw(model, x, y, pick):
+    """Record 0's dW of a tie_case network, restated with loops: each pool window's gradient to the element `pick` chooses among
+    those equal to the window's maximum. Returns (dW, how often the first of several maxima was element e)."""
+    conv, dense = fnet_ref.conv_records(model)
+    w, b = conv["w"].astype(np.float64), conv["b"].astype(np.float64)
+    img = x.astype(np.float64).reshape(-1, 6, 6)
+    n = len(img)
+    ph, pw = conv["p"]
+    Ph, Pw, oc = conv["out"]
+    pre = np.array([[[[(img[u, r:r + 2, c:c + 2] * w[o, :, :, 0]).sum() + b[o] for o in range(oc)] for c in range(5)] for r in range(5)]
+                    for u in range(n)])
+    win = lambda u, py, px, o: [pre[u, py * ph + e // pw, px * pw + e % pw, o] for e in range(ph * pw)]
+    pooled = np.array([[[[max(win(u, py, px, o)) for o in range(oc)] for px in range(Pw)] for py in range(Ph)] for u in range(n)])
+    z = pooled.reshape(n, -1) @ dense["w"].astype(np.float64).reshape(3, -1).T + dense["b"]
+    pz = np.exp(z - z.max(axis=1, keepdims=True))
+    dz = (pz / pz.sum(axis=1, keepdims=True) - np.eye(3)[y]) / n
+    dpooled = (dz @ dense["w"].astype(np.float64).reshape(3, -1)).reshape(pooled.shape)
+    dw, tied_first = np.zeros_like(w), np.zeros(ph * pw, int)
+    for u in range(n):
+        for py in range(Ph):
+            for px in range(Pw):
+                for o in range(oc):
+                    v = win(u, py, px, o)
+                    at = [e for e in range(ph * pw) if v[e] == pooled[u, py, px, o]]
+                    tied_first[at[0]] += len(at) > 1
+                    e = pick(at)
+                    r, c = py * ph + e // pw, px * pw + e % pw
+                    dw[o, :, :, 0] += dpooled[u, py, px, o] * img[u, r:r + 2, c:c + 2]
+    return dw, tied_first
+
+
+@pytest.mark.parametrize("pool", fgrad_ref.TIE_POOLS, ids=lambda p: "pool%d%d" % p)
+def test_tied_windows_send_the_gradient_to_their_first_element(pool):
+    """The rows tests/test_gpu_ftrain.py holds the trainer's first-maximum choice to: windows tie exactly with their first maximum at
+    every element that can tie, the restatement sends a tied window's gradient to its first maximum only, and the last maximum
+    instead would move dW far beyond any rounding bound."""
+    import torch
+    model, x, y = fgrad_ref.tie_case(pool)
+    assert fnet_ref.conv_records(model)[0]["relu"] == 0
+    ref = fgrad_ref.loss_grad(model, x, y)
+    first, tied_first = _routed_dw(model, x, y, lambda at: at[0])
+    assert (tied_first[:-1] > 0).all(), tied_first                          # a window's last element is never the first of several
+    assert fgrad_ref.tensor_error(ref["grads"][0]["w"], first) <= 1e-12
+    last, _ = _routed_dw(model, x, y, lambda at: at[-1])
+    assert fgrad_ref.tensor_error(last, first) > 1e-2
+    tor = fgrad_ref.torch_grads(model, x, y, torch.float64)
+    for a, b in zip(ref["grads"], tor["grads"]):
+        assert fgrad_ref.tensor_error(a["w"], b["w"]) <= 1e-10 and fgrad_ref.tensor_error(a["b"], b["b"]) <= 1e-10
+
+
 @pytest.mark.parametrize("name", ["pool22_trunc_hw", "inc3_oc64_oc65_s21", "n_out_210", "ladder_k5"])
 def test_pack_round_trip_against_the_plan(name):
     blob = fnet_sweep.blob(name)

@@ -160,6 +160,25 @@ def test_logits_loss_gradient_padding_repeat_and_no_side_effect(ctx, name):
             assert all(np.array_equal(before[k], after[k]) for k in before)
 
 
+@pytest.mark.parametrize("pool", fgrad_ref.TIE_POOLS, ids=lambda p: "pool%d%d" % p)
+def test_tied_pool_windows_send_the_gradient_to_their_first_element(ctx, pool):
+    """Pool windows of 2 and of 4 elements without ReLU whose maxima tie exactly, the first of them at every element that can tie
+    (fgrad_ref.tie_case; tests/test_fgrad_cpu.py shows that sending a tied window's gradient to another of its maxima moves dW by
+    more than 1e-2 of its largest entry): the gradient is held to the float64 restatement by the bounds of every other row."""
+    model, x, y = fgrad_ref.tie_case(pool)
+    name = "tie_pool%d%d" % tuple(pool)
+    blob, real = poisoned(cube_import.build_blob(model))
+    ctx.fnet_load(blob)
+    ref = fgrad_ref.loss_grad(model, x, y)
+    before = ctx.fnet(x)
+    with ctx.trainer() as tr:
+        assert tr.info()["batch"] < len(y)                                  # more than one tile
+        r = tr.grad(x, y)
+        assert np.array_equal(tr.logits(len(y)).view(np.uint32), before["logits"].view(np.uint32))
+        assert np.array_equal(r["argmax"], before["argmax"])
+        check_gradient(name, tr, model, real, x, y, ref)
+
+
 def test_adam_steps_in_place_and_the_exported_network(ctx, fresh):
     name = "pool21_trunc_h"
     model, blob, real = case(name)
