@@ -175,11 +175,11 @@ int ed_ctx_ensure_scratch(edison_ctx *ctx, size_t bytes);
 void ed_ctx_geom_free(edison_ctx *ctx);
 /* Free the loaded float32 network (edison_shutdown; edison_fnet.hip). */
 void ed_ctx_fnet_free(edison_ctx *ctx);
-/* edison_kws_geom.hip, shared with edison_stream_geom.hip: the geometry checks of edison_kws_geom (everything but the model; *frames =
+/* edison_kws_geom.hip, shared with edison_stream_bank.hip: the geometry checks of edison_kws_geom (everything but the model; *frames =
  * frames per utterance) and the table builder behind the context's cache (fills *c, whose d must be NULL; c->d stays NULL on failure). */
 int ed_kws_geom_check(edison_ctx *ctx, const edison_kws_geom *g, int *frames);
 int ed_geom_tables_build(edison_ctx *ctx, const edison_kws_geom *g, ed_geom_cache *c);
-/* edison_fnet.hip, shared with edison_stream_float.hip: the checks of edison_kws_float_batch for geometry g, flow q15 and the clip
+/* edison_fnet.hip, shared with edison_float_bank.hip: the checks of edison_kws_float_batch for geometry g, flow q15 and the clip
  * range, the loaded float network's input size included (*frames = frames per window). */
 int ed_kws_float_geom_check(edison_ctx *ctx, const edison_kws_geom *g, int q15, float clip_lo, float clip_hi, int *frames);
 

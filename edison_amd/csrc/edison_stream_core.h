@@ -1,5 +1,5 @@
 /*
- * edison_stream_core.h -- the sliding-window core that edison_stream_geom.hip and edison_stream_float.hip run on (edison_stream_core.hip,
+ * edison_stream_core.h -- the sliding-window core that edison_stream_bank.hip and edison_float_bank.hip run on (edison_stream_core.hip,
  * DESIGN.md section 12a): the state a continuous stream keeps between pushes and everything that does not depend on which MFCC and
  * which network fill the window. An owner holds one core by value, launches its features and its network between begin_push and
  * finish_push, and lays out the front of the output block. Not part of the public ABI.
@@ -11,8 +11,8 @@
  * of the push is rows pos + i .. pos + i + F - 1, read in place by the owner's network kernel. When the next push would run past the
  * end, the shift kernel first moves the history back to the front.
  *
- * A core serves n_mics microphones that advance in lockstep (1: edison_stream_geom / edison_stream_float; more: edison_stream_bank.hip and
- * edison_float_bank.hip, DESIGN.md sections 12b and 15a). Each microphone has the two buffers above, mic_audio samples and mic_feat bytes behind its neighbour's, and all
+ * A core serves n_mics microphones that advance in lockstep (1: an edison_stream_geom / edison_stream_float, or a bank of one; more: an
+ * edison_stream_bank / edison_float_bank, DESIGN.md sections 12b and 15a). Each microphone has the two buffers above, mic_audio samples and mic_feat bytes behind its neighbour's, and all
  * share one pos. A push carries [n_mics][n * hop] samples; everything it puts out is time-major: filt [n][n_mics][n_out], likely /
  * spotted / states [n][n_mics], the machines [n_mics]. With n_mics = 1 the core issues the copies and launches it issued before it had
  * the dimension, with more one strided copy; the two state kernels (edison_stream_core.hip) run one workgroup per microphone either way.

@@ -1,8 +1,8 @@
 /*
  * edison_stream_core.hip -- the sliding-window core of the any-geometry streams (edison_stream_core.h): the two
- * state kernels, one workgroup per microphone, and the host logic around them that edison_stream_geom.hip, edison_stream_float.hip and
- * the two banks (edison_stream_bank.hip, edison_float_bank.hip; sections 12b, 15a) share. The microphone count and a push's mask are
- * data of the launch: a single stream runs the same kernels at grid 1.
+ * state kernels, one workgroup per microphone, and the host logic around them that the two front ends, one per network type
+ * (edison_stream_bank.hip, edison_float_bank.hip; sections 12b, 15a), share. The microphone count and a push's mask are
+ * data of the launch: a single stream is a bank of one microphone and runs the same kernels at grid 1.
  */
 #include <math.h>
 #include <string.h>

@@ -38,7 +38,7 @@ typedef struct {
 } ed_geom_args_t;
 
 /* The filterbank / twiddle / DCT tables of one geometry on the device and the kernel's launch template (edison_kws_geom.hip builds
- * them): the context's one-entry cache of edison_kws_geom_batch*, and a table set of its own in every edison_stream_geom. */
+ * them): the context's one-entry cache of edison_kws_geom_batch*, and a table set of its own in every stream and bank. */
 struct ed_geom_cache
 {
 	/* the key: everything the tables depend on */

@@ -1,6 +1,6 @@
 /*
  * mfcc_geom_fnet_kernels.hip -- audio -> float32 network-input rows at ANY MFCC geometry: the feature stage of edison_stream_float's host
- * flow (edison_stream_float.hip). The third instance of the any-geometry frame body (mfcc_geom_frames.inc), beside
+ * flow (edison_float_bank.hip). The third instance of the any-geometry frame body (mfcc_geom_frames.inc), beside
  * the int8 (ed_mfcc_geom_kernel) and float64 (ed_mfcc_geom_f64_kernel) instances of mfcc_geom_kernels.hip: the same frames, stages and
  * launch; stage 6 stores
  *     out[g * n_coef + row] = fminf(fmaxf((float)y * scale, lo), hi)

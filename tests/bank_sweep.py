@@ -23,13 +23,13 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_CU = 256                      # MI355X; the GPU tests pass the context's value
-MAX_MICS = 4096                 # ED_STREAM_BANK_MAX_MICS, edison_stream_bank.hip:27
+MAX_MICS = 4096                 # ED_STREAM_BANK_MAX_MICS, edison_stream_bank.hip:31
 SLOTS, SLOTS_BYTES, SLACK = 8, 64 << 20, 64   # edison_stream_core.h:34-36
 EDG_BLOCK, WAVE_TEAM_BYTES = 256, 20480       # mfcc_geom_device.h, edison_kws_geom.hip:19
 EDM_G, EDM_WAVES = 4, 8                       # cnn_mfma_kernels.hip:71-72
 BASES = 7                       # base recordings of a row with more than 8 microphones: coprime to 4, 8 and 16
 
-# ---- geometries: graph -> the MFCC geometry it is run at. The graph fixes frame_count x num_mfcc only (edison_stream_geom.hip:99).
+# ---- geometries: graph -> the MFCC geometry it is run at. The graph fixes frame_count x num_mfcc only (edison_stream_bank.hip:143).
 _SHIPPED = dict(variant="B", frame_len=1024, frame_step=1024, n_samples=32000, mel_nbins=32, first_mfcc=0, num_mfcc=13)
 GEOMS = {
     "shipped": ("shipped", _SHIPPED),
@@ -79,6 +79,10 @@ _row("gen_23", "shipped", 23, sched=[1] * 9, route="general", outputs="none")
 _row("gen_24", "shipped", 24, chunk=2, sched=[2] * 9, route="general", resets=[(5, "all")])
 _row("gen_49", "shipped", 49, sched=[1] * 9, route="general")
 _row("spec_49", "shipped", 49, sched=[1] * 9, route="spec")
+# one microphone runs ONE launch over a push's windows: a push of more windows than the grid's cap takes (the graph with the smallest
+# batch x waves, 22: 5632 at 256 CUs), so a workgroup's loop over inputs comes round; the second push reads behind the first's rows
+GEN_CAP_CHUNK = 22 * 256 + 1    # general_cap(N_CU) + 1: the CPU and GPU tests check that it exceeds the cap at their CU count
+_row("gen_cap", "square_ov", 1, chunk=GEN_CAP_CHUNK, sched=[GEN_CAP_CHUNK] * 2, ref="independent")
 # ---- the layer-by-layer kernel: a workgroup per input, capped at 8 per CU
 _row("lbl_4096", "odd_no_softmax", 4096, sched=[1] * 9, route="lbl", outputs="no_logits")
 # ---- the shift with overlapping source and destination
@@ -139,24 +143,23 @@ def frame_count(g):
 
 def create_check(row):
     """The create checks that need no device, restated: None, or the reason the bank refuses the row.
-    edison_kws_geom.hip:52-69 (ed_kws_geom_check), edison_stream_geom.hip:99-110, edison_stream_core.hip:144-150,
-    edison_stream_bank.hip:98-104."""
+    edison_kws_geom.hip:52-69 (ed_kws_geom_check), edison_stream_bank.hip:139-157, edison_stream_core.hip:144-150."""
     g, f = GEOMS[row["geom"]][1], graph_facts(row["graph"])
     if not 1 <= row["n_mics"] <= MAX_MICS:
-        return "n_mics must be 1 .. 4096"                                        # edison_stream_bank.hip:98
+        return "n_mics must be 1 .. 4096"                                        # edison_stream_bank.hip:139
     if geom_check(g):
         return geom_check(g)
     F = frame_count(g)
     if F * g["num_mfcc"] != f["in_n"]:
-        return "frame_count x num_mfcc is not the graph's input"                 # edison_stream_geom.hip:99
+        return "frame_count x num_mfcc is not the graph's input"                 # edison_stream_bank.hip:143
     if core_check(row, g):
         return core_check(row, g)
     if row["filt"] and f["n_out"] > 256:
-        return "at most 256 outputs"                                             # edison_stream_geom.hip:107
+        return "at most 256 outputs"                                             # :151
     if row["fsm"] and f["n_out"] != 10:
-        return "the state machine needs 10 outputs"                              # :109
+        return "the state machine needs 10 outputs"                              # :153
     if row["n_mics"] * row["chunk"] >= 1 << 31:
-        return "n_mics x chunk_frames below 2^31"                                # edison_stream_bank.hip:103
+        return "n_mics x chunk_frames below 2^31"                                # :156
     return None
 
 
@@ -205,12 +208,12 @@ def sizes(row, feat_elem=1, geoms=None):
 
 
 def window_addr(s, pos, i, m):
-    """Byte offset in d_feat of window i of a push for microphone m: edison_stream_bank.hip:50, 62 (win + i * nm, stride mic_feat)."""
+    """Byte offset in d_feat of window i of a push for microphone m: edison_stream_bank.hip:70, 89 (win + i * nm, stride mic_feat; one microphone: :81, win at a stride of nm)."""
     return m * s["mic_feat"] + (pos + i) * s["nm"]
 
 
 def out_index(i, m, n_mics):
-    """Row of the time-major outputs: slab i of the push, microphone m (edison_stream_bank.hip:59-63; the filter: edison_stream_core.hip:80 `i * n_mics + m`)."""
+    """Row of the time-major outputs: slab i of the push, microphone m (edison_stream_bank.hip:86-90; the filter: edison_stream_core.hip:80 `i * n_mics + m`)."""
     return i * n_mics + m
 
 
@@ -243,9 +246,10 @@ def mfcc_launch(g, n_frames, n_cu):
     return dict(team=team, blocks=blocks, wraps=n_frames > blocks * teams)
 
 
-def net_launch(row, n_cu):
-    """The network launch of one frame of a push over n = n_mics windows: grid and whether the kernel's loop over inputs wraps."""
-    f, n = graph_facts(row["graph"]), row["n_mics"]
+def net_launch(row, n_cu, frames=1):
+    """A network launch of a push of `frames` frames (edison_stream_bank.hip:79-93): one per frame over its n = n_mics windows, or, with
+    one microphone, ONE over the push's n = frames windows. Grid and whether the kernel's loop over inputs wraps."""
+    f, n = graph_facts(row["graph"]), row["n_mics"] if row["n_mics"] > 1 else frames
     if row["route"] == "fast":          # ed_launch_cnn_mfma_flag, cnn_mfma_kernels.hip:810-812; a wave draws groups from its workgroup's slice (:267)
         groups = -(-n // EDM_G)
         blocks = min(-(-groups // EDM_WAVES), n_cu)
@@ -409,20 +413,23 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True, hold=hold
               ("frame_len", "odd" if N % 2 else "even"), ("n_out", graph_facts(row["graph"])["n_out"]), ("alpha", {0.0: "0", 1.0: "1"}.get(row["alpha"], "interior")),
               ("threshold", "tie" if row["thr"] == "tie" else "plain"), ("fsm", row["fsm"]), ("outputs", row["outputs"]), ("push", row["push"]),
               ("ref", row["ref"], "large" if M > 8 else "small")}
-    nl = net_launch(row, n_cu)
-    if nl["kernel"] == "fast":
-        items.add(("fast", "<4" if M < 4 else "4" if M == 4 else "4096" if M == MAX_MICS else "ragged" if M % 4 else "whole"))
-        if -(-M // EDM_G) > EDM_WAVES:
-            items.add(("fast", "more than one workgroup"))
-    elif nl["kernel"] == "general":
-        items.add(("general", "under" if M < nl["unit"] else "equal" if M == nl["unit"] else "over ragged" if M % nl["unit"] else "over whole"))
-        if nl["wraps"]:
-            items.add(("general", "blocks above the cap"))
-    elif nl["kernel"] == "spec":
-        if nl["blocks"] > 1:
-            items.add(("spec", "more than one workgroup"))
-    elif nl["wraps"]:
-        items.add(("lbl", "block loop wraps"))
+    # the inputs of one network launch: the microphones, or one microphone's frames of the push
+    for k in ({M} if M > 1 else set(row["sched"])):
+        nl = net_launch(row, n_cu, k)
+        if nl["kernel"] == "fast":
+            items.add(("fast", "<4" if k < 4 else "4" if k == 4 else "4096" if k == MAX_MICS else "ragged" if k % 4 else "whole"))
+            if -(-k // EDM_G) > EDM_WAVES:
+                items.add(("fast", "more than one workgroup"))
+        elif nl["kernel"] == "general":
+            if nl["wraps"]:     # the grid at its cap, a workgroup's loop comes round: not the one-pass grids the other items tell apart
+                items.add(("general", "blocks above the cap"))
+            else:
+                items.add(("general", "under" if k < nl["unit"] else "equal" if k == nl["unit"] else "over ragged" if k % nl["unit"] else "over whole"))
+        elif nl["kernel"] == "spec":
+            if nl["blocks"] > 1:
+                items.add(("spec", "more than one workgroup"))
+        elif nl["wraps"]:
+            items.add(("lbl", "block loop wraps"))
 
     for p, n in enumerate(row["sched"]):
         absent, reset_now = absent_of(row, p), set()
@@ -463,7 +470,7 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True, hold=hold
             at = m * A + pos * hop + tail
             assert at + n * hop <= (m + 1) * A
             audio[at:at + n * hop] = GARBAGE if m in gone else _tok(m, epoch[m], 0, tail + cnt[m] * hop) + np.arange(n * hop)
-        # ONE MFCC launch over n_mics * n frames: edison_stream_bank.hip:51-58, mfcc_geom_frames.inc:19-22, mfcc_geom_kernels.hip:29-33
+        # ONE MFCC launch over n_mics * n frames: edison_stream_bank.hip:71-78, mfcc_geom_frames.inc:19-22, mfcc_geom_kernels.hip:29-33
         ml = mfcc_launch(g, M * n, n_cu)
         items |= {("mfcc", "team", ml["team"]), ("mfcc", "wraps" if ml["wraps"] else "one pass"), ("mfcc", "frames_per_utt", "1" if n == 1 else "chunk" if n == s["chunk"] else "ragged")}
         feat_skip = FB - n * nm
@@ -478,7 +485,7 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True, hold=hold
             o = pos * nm + (F - 1) * nm + gi * nm + feat_skip * u
             assert u * FB <= o and o + nm <= (u + 1) * FB, "row outside its microphone's rows"
             feat[o:o + nm] = GARBAGE if u in gone else _tok(u, epoch[u], 1, (F - 1 + cnt[u] + f) * nm) + np.arange(nm)
-        # n network launches over the n_mics windows of a frame: edison_stream_bank.hip:59-65
+        # n network launches over the n_mics windows of a frame, or one microphone's ONE over its n windows: edison_stream_bank.hip:79-93
         stride = FB + (nm if variant == "window_stride" else 0)
         full = pos + n == s["slots"] * s["chunk"]
         for i in range(n):
@@ -489,7 +496,7 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, variant=None, check=True, hold=hold
                 lo, hi = at, at + F * nm
                 if fast:                          # edm_load_rows, cnn_mfma_kernels.hip:170-186: 16 bytes per 13-byte row, the batch's last row 3 early
                     items.add(("residue", at % 16))
-                    hi = hi if m == M - 1 else hi + 3
+                    hi = hi if (m == M - 1 if M > 1 else i == n - 1) else hi + 3
                     if variant is None and full and i == n - 1 and m == M - 1:
                         assert hi == M * FB
                         items.add(("fast", "last window ends the buffers"))
@@ -571,15 +578,14 @@ def full_set():
 
 # item -> the host check or launch rule that keeps every accepted bank from it
 EXCLUDED = {
-    ("general", "blocks above the cap"): "cnn_net_mfma_kernels.hip:1371 caps the grid at n_cu x per_cu workgroups of batch x waves inputs; the smallest "
-                                         "batch x waves of a fixture graph is 22 (square), so with 256 CUs the cap is 5632 inputs and edison_stream_bank.hip:98 "
-                                         "admits 4096 (general_cap() recomputes it for the CU count at hand)",
-    ("n_mics", ">4096"): "edison_stream_bank.hip:98 refuses n_mics outside 1 .. 4096 (tests/test_gpu_stream_bank.py::test_errors runs it)",
-    ("n_mics x chunk", ">=2^31"): "edison_stream_bank.hip:103 refuses it, and no allocation reaches it: 2^31 frames of at least one sample each are 4 GB of "
+    ("n_mics", ">4096"): "edison_stream_bank.hip:139 refuses n_mics outside 1 .. 4096 (tests/test_gpu_stream_bank.py::test_errors runs it)",
+    ("n_mics x chunk", ">=2^31"): "edison_stream_bank.hip:156 refuses it, and no allocation reaches it: 2^31 frames of at least one sample each are 4 GB of "
                                   "samples per push, which edison_stream_core.hip:146 (chunk x frame_step < 2^30) and HBM rule out for 4096 microphones",
 }
 
 
 def general_cap(n_cu):
-    """The fewest inputs at which a fixture graph's general-kernel grid reaches its cap."""
+    """The fewest inputs at which a fixture graph's general-kernel grid reaches its cap (cnn_net_mfma_kernels.hip:1371: n_cu x per_cu
+    workgroups of batch x waves inputs): 5632 at 256 CUs, which a launch per frame stays under (edison_stream_bank.hip:139 admits 4096
+    microphones) and one microphone's launch over a push's windows passes where the push has more (row gen_cap)."""
     return min(net_launch(dict(graph=gname, n_mics=1, route="general"), n_cu)["cap"] for gname in ("shipped", "square", "odd_no_softmax", "same_stride", "even_same"))

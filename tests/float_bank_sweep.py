@@ -24,7 +24,7 @@ from bank_sweep import (BASES, GARBAGE, MAX_MICS, N_CU, POISON, SLACK, _band, _t
 
 ROOT = bs.ROOT
 FIXTURE = os.path.join(ROOT, "tests", "golden", "cube_kws.ednf")
-FEAT_ELEM = 4                   # sizeof(float): ed_stream_core_create(.., sizeof(float), sizeof(float), ..), edison_float_bank.hip:164
+FEAT_ELEM = 4                   # sizeof(float): ed_stream_core_create(.., sizeof(float), sizeof(float), ..), edison_float_bank.hip:182
 EQ_WPB = 16                     # frames in flight per workgroup of the variant C kernel, mfcc_q15_kernels.hip:52
 DEFAULT_CLIP = (-32768.0, 32767.0)
 
@@ -118,11 +118,11 @@ def sizes(row):
 
 
 def create_check(row):
-    """The create checks that need no device, restated: None, or the reason the bank refuses the row. edison_float_bank.hip:135-154,
+    """The create checks that need no device, restated: None, or the reason the bank refuses the row. edison_float_bank.hip:152-171,
     edison_fnet.hip:304-332 (kws_float_check), edison_kws_geom.hip:52-69, edison_stream_core.hip:144-150."""
     g, pl = GEOMS[row["geom"]][1], plan_of(row["net"], row["geom"])
     if not 1 <= row["n_mics"] <= MAX_MICS:
-        return "n_mics must be 1 .. 4096"                                        # edison_float_bank.hip:135
+        return "n_mics must be 1 .. 4096"                                        # edison_float_bank.hip:152
     if not row["clip"][0] <= row["clip"][1]:
         return "clip_lo > clip_hi"                                               # edison_fnet.hip:306
     if row["q15"] and not (g["frame_len"] == g["frame_step"] == 1024 and g["mel_nbins"] == 32 and g["first_mfcc"] == 0 and 1 <= g["num_mfcc"] <= 32):
@@ -132,7 +132,7 @@ def create_check(row):
     if frame_count(g) * g["num_mfcc"] != pl["in_n"]:
         return "frame_count x num_mfcc is not the network's input"               # :326
     if bs.core_check(row, g):
-        return bs.core_check(row, g)                                             # edison_float_bank.hip:148
+        return bs.core_check(row, g)                                             # edison_float_bank.hip:165
     if row["filt"] and pl["n_out"] > 256:
         return "at most 256 outputs"                                             # :149
     if row["fsm"] and pl["n_out"] != 10:
@@ -150,7 +150,7 @@ def q15_grid(n_frames, n_cu):
 
 
 def net_launch(row, n):
-    """edison_float_bank.hip:93-95: which launch serves a push of n frames, and its utterances in output order as (frame, microphone)."""
+    """edison_float_bank.hip:98-100: which launch serves a push of n frames, and its utterances in output order as (frame, microphone)."""
     M = row["n_mics"]
     if M == 1:
         return "by_frame", n                                                     # ed_launch_fnet over n windows num_mfcc floats apart
@@ -239,7 +239,7 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, hold=hold_rounds, variant=None, che
     epoch, cnt = [0] * M, [0] * M
     seen, pos, shifted = 0, 0, False
     items, problems = set(), []
-    mic_rows = FB // E                            # edison_float_bank.hip:62
+    mic_rows = FB // E                            # edison_float_bank.hip:67
 
     def start_state(m):                           # start_state, edison_stream_core.hip:220-245, at the current pos
         epoch[m] += 1
@@ -305,7 +305,7 @@ def walk(row, n_cu=N_CU, shift=shift_rounds, hold=hold_rounds, variant=None, che
             at = pos * hop + tail
             assert at + n * hop <= A
             audio.mic(m)[at:at + n * hop] = GARBAGE if m in gone else _tok(m, epoch[m], 0, tail + cnt[m] * hop) + np.arange(n * hop)
-        # ---- the feature rows of all n_mics * n frames, edison_float_bank.hip:63-89
+        # ---- the feature rows of all n_mics * n frames, edison_float_bank.hip:68-94
         rows0 = (pos + F - 1) * nm                # `rows` of microphone 0, in floats
         group = 0 if M == 1 else A                # utt_stride / group_stride: an utterance of the launch = a microphone
         items.add(("mfcc", "frames_per_utt", "1" if n == 1 else "chunk" if n == s["chunk"] else "ragged"))
@@ -437,9 +437,9 @@ def full_set():
 
 # item -> the host check or launch rule that keeps every accepted bank from it
 EXCLUDED = {
-    ("n_mics", ">4096"): "edison_float_bank.hip:135 refuses n_mics outside 1 .. 4096 (tests/test_gpu_float_bank.py::test_errors runs it)",
-    ("n_mics x chunk", ">=2^31"): "edison_float_bank.hip:153 refuses it",
-    ("n_out", "above 256"): "edison_float_bank.hip:149 refuses the filter for a network of more than 256 outputs, and every row filters",
+    ("n_mics", ">4096"): "edison_float_bank.hip:152 refuses n_mics outside 1 .. 4096 (tests/test_gpu_float_bank.py::test_errors runs it)",
+    ("n_mics x chunk", ">=2^31"): "edison_float_bank.hip:170 refuses it",
+    ("n_out", "above 256"): "edison_float_bank.hip:166 refuses the filter for a network of more than 256 outputs, and every row filters",
     ("flow", "q15", "a sample history"): "edison_fnet.hip:310 admits the firmware flow at frame_len = frame_step = 1024 only, so tail = 0 "
                                          "(edison_stream_core.hip:159) and its banks never shift or hold samples",
 }

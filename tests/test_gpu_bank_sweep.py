@@ -376,7 +376,7 @@ def test_rows_cover_every_item_at_this_gpus_cu_count():
         c.close()
     have = set().union(*(bs.walk(r, n_cu=n_cu, check=False)[0] for r in bs.ROWS.values()))
     assert sorted(bs.full_set() - set(bs.EXCLUDED) - have, key=str) == []
-    assert not set(bs.EXCLUDED) & have and bs.general_cap(n_cu) > bs.MAX_MICS
+    assert not set(bs.EXCLUDED) & have and bs.ROWS["gen_cap"]["chunk"] > bs.general_cap(n_cu)
 
 
 @pytest.mark.parametrize("name", IN_PROCESS)

@@ -57,7 +57,7 @@ def test_the_stream_is_built(tmp_path):
     """build.HIP_SOURCES lists the host object, the sliding-window core and the new MFCC instance, and all cross-compile for gfx950 on
     the library's flags."""
     from edison_amd import build
-    for name in ("edison_stream_float.hip", "edison_stream_core.hip", "mfcc_geom_fnet_kernels.hip"):
+    for name in ("edison_float_bank.hip", "edison_stream_core.hip", "mfcc_geom_fnet_kernels.hip"):
         assert name in build.HIP_SOURCES
         _compile(tmp_path, name, ["-Wall", "-Wextra", "-Wno-unused-parameter", "-fPIC"])
     for h in ("mfcc_geom_device.h", "edison_stream_core.h"):
@@ -86,16 +86,18 @@ def test_hot_path_kernels_use_no_scratch(tmp_path):
 
 def test_one_frame_body_for_the_third_instance():
     """The new instance computes y by the shared frame body and stores the float network input; the filter and shift kernels exist once,
-    in the sliding-window core (edison_stream_core.hip): neither stream file defines a kernel, and both run their pushes through the
-    core's entry points, begin_push (which shifts) and finish_push (which filters)."""
+    in the sliding-window core (edison_stream_core.hip): neither front end (one file per network type, stream and bank) defines a kernel,
+    and both run their pushes through the core's entry points, begin_push (which shifts) and finish_push (which filters)."""
     from edison_amd import build as B
     kern = open(os.path.join(B.CSRC, "mfcc_geom_fnet_kernels.hip")).read()
     assert kern.count('#include "mfcc_geom_frames.inc"') == 1 and "a.dct_div" not in kern
     assert "fminf(fmaxf((float)(y) * scale, lo), hi)" in kern
-    for name in ("edison_stream_float.hip", "edison_stream_geom.hip"):
+    for name in ("edison_float_bank.hip", "edison_stream_bank.hip"):
         text = open(os.path.join(B.CSRC, name)).read()
         assert "__global__" not in text and "hipLaunchKernelGGL" not in text
         assert "ed_stream_core_begin_push(" in text and "ed_stream_core_finish_push(" in text
+        # one device push and one host push per network type: the stream API forwards to the bank's and has no push of its own
+        assert text.count("ed_stream_core_begin_push(") == 2, name
     core = open(os.path.join(B.CSRC, "edison_stream_core.hip")).read()
     assert core.count("__global__") == 2
     # the filter's arithmetic and its one no-contraction pragma live in the shared header, not here

@@ -24,7 +24,7 @@ def test_header_and_binding_declare_the_stream():
 
 def test_the_stream_is_built():
     from edison_amd import build
-    for name in ("edison_stream_geom.hip", "edison_stream_core.hip"):
+    for name in ("edison_stream_bank.hip", "edison_stream_core.hip"):
         assert name in build.HIP_SOURCES
         assert os.path.exists(os.path.join(build.CSRC, name))
     assert "edison_stream_core.h" in build.HEADERS and os.path.exists(os.path.join(build.CSRC, "edison_stream_core.h"))
