@@ -12,6 +12,7 @@ import numpy as np
 
 from edison_amd import cube_import
 
+import fnet_exact
 import fnet_ref
 import fnet_sweep
 
@@ -171,6 +172,47 @@ def terms(model, n):
     for L in conv_records(model):
         ph, pw = L["p"]
         out.append(n * L["out"][0] * ph * L["out"][1] * pw)
+    return out
+
+
+# ---- the trainer's plan and the order of its sums ---------------------------------------------------------------------------------
+def train_lds_bytes(plan, batch):
+    """ed_ftrain_lds_bytes of a restated plan (fnet_exact.plan) at `batch` utterances per workgroup: the larger of the forward half's
+    LDS and the backward half's dY [16-padded batch x rows][n_pad] floats + row bases [16-padded batch x rows] ints, each the largest
+    record's (ftrain_size_lds)."""
+    fwd = 4 * (batch * sum(plan["buf_n"]) + plan["w_lds"]) + 4 * plan["k_lds"]
+    mp = [(batch * L["rows"] + 15) // 16 * 16 for L in plan["layers"]]
+    bwd = 4 * max(m * L["n_pad"] for m, L in zip(mp, plan["layers"])) + 4 * max(mp)
+    return max(fwd, bwd)
+
+
+def train_batch(plan, limit=None):
+    """The utterances per workgroup edison_ftrain_create trains a restated plan at: the network's own batch, lowered while the training
+    workgroup does not fit `limit` bytes of LDS (fnet_exact.LDS_BYTES); 0 for a plan it refuses, whose one utterance does not fit."""
+    limit = fnet_exact.LDS_BYTES if limit is None else limit
+    batch = plan["batch"]
+    while batch > 1 and train_lds_bytes(plan, batch) > limit:
+        batch -= 1
+    return batch if train_lds_bytes(plan, batch) <= limit else 0
+
+
+def fold_tiles(T, grid, scale):
+    """The order ed_ftrain_grad_kernel and ed_ftrain_reduce_kernel sum a call's tiles in, in float32: T [n_tiles][w_floats] float32,
+    tile j's packed gradient; workgroup g's slab is T[g] scale, then + T[g + grid] scale, then + T[g + 2 grid] scale ...; the result
+    is slab 0 + slab 1 + ... in index order over the min(n_tiles, grid) slabs. `scale` is a power of two, so T scale is exact."""
+    T = np.asarray(T)
+    assert T.dtype == np.float32 and T.ndim == 2 and len(T) >= 1 and grid >= 1
+    s = np.float32(scale)
+    assert float(s) == float(scale) and np.frexp(s)[0] == 0.5, "scale is not a power of two that float32 holds"
+    used = min(len(T), grid)
+    slabs = T[:used] * s
+    for j0 in range(grid, len(T), grid):
+        part = T[j0:j0 + grid]
+        slabs[:len(part)] += part * s
+    out = slabs[0].copy()
+    for g in range(1, used):
+        out += slabs[g]
+    assert out.dtype == np.float32
     return out
 
 

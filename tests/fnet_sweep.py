@@ -66,6 +66,10 @@ ROWS = {
                        "P=1 K4=0 nt=1 NG=1 batch=1 n_out=16; K = 2272 x 16: the largest weights that load at batch 1, LDS 163 648 bytes"),
     "batch5": (dict(in_shape=(40, 30, 2), layers=[("conv", 4, (3, 3), (1, 1), (1, 1), 1), ("conv", 8, (3, 3), (2, 2), (2, 2), 1), ("dense", 5, 0)]),
                "P=1,4 K4=2,0 nt=1 NG=1 batch=5; a middle batch: 4256 floats of activations per utterance"),
+    # the packed weight array: more floats than one pass of the optimiser's step kernel covers on 256 CUs (8 blocks of 256 a CU)
+    "dense16_wide": (dict(in_shape=(1, 1, 192), layers=[("dense", 192, (i + 1) % 2) for i in range(15)] + [("dense", 5, 0)]),
+                     "P=1 K4=0 nt=4,1 NG=3,1 batch=10 layers=16 n_out=5; fifteen dense 192 -> 192, ReLU on every other one, then 192 -> 5: "
+                     "558 928 packed floats, one row per utterance in every record"),
     # subnormal products and partial sums; zero bias so nothing hides them
     "subnormal": (dict(in_shape=(6, 4, 1), layers=[("conv", 16, (2, 2), (1, 1), (1, 1), 0), ("dense", 8, 0)], bias="zero", wscale=[S, 1.0],
                        sets=["tiny", "sub", "n1"]),
@@ -145,6 +149,14 @@ def path(p):
     L = p["layers"]
     return dict(P={x["P"] for x in L}, K4={x["K"] % 4 for x in L}, nt={x["nt_last"] for x in L}, NG={x["NG"] for x in L},
                 batch={p["batch"]}, layers={p["n_layers"]}, n_out={p["n_out"]})
+
+
+STEP_PASS = 2048     # floats a CU's 8 blocks of 256 threads cover in one pass of ed_ftrain_step_kernel (ed_launch_ftrain_step)
+
+
+def w_floats(p):
+    """The packed weight array of a plan, in floats: every record's B[k_pad][n_pad], then bias[n_pad]."""
+    return sum(L["k_pad"] * L["n_pad"] + L["n_pad"] for L in p["layers"])
 
 
 def claims(note):

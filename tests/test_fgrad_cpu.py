@@ -1,6 +1,8 @@
 """The float64 restatement of training (tests/fgrad_ref.py) held to torch's float64 autograd and to central differences, the packed
-layout of edison_amd/train.py held to the plan's (fnet_exact.plan), the Adam restatement held to torch.optim.Adam, and the host side
-of fit: the shuffle and the two callbacks. No GPU."""
+layout of edison_amd/train.py held to the plan's (fnet_exact.plan), the Adam restatement held to torch.optim.Adam, the host side
+of fit: the shuffle and the two callbacks; and what tests/test_gpu_ftrain_tiles.py rests on: the order of a multi-tile call's sums
+(fgrad_ref.fold_tiles), what that order is sensitive to, what the float64 bound sees at these sizes, and the trainer's batch
+(fgrad_ref.train_batch). No GPU."""
 import os
 
 import numpy as np
@@ -15,7 +17,7 @@ import fnet_sweep
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROWS = ["ladder_k5", "pool21_trunc_h", "pool12_trunc_w", "pool22_trunc_hw", "pool41_tail", "inc3_oc64_oc65_s21", "oc40_s32_span_h", "n_out_210",
-        "relu_logits", "conv_last_map", "layers16", "synth_pool12_relu"]
+        "relu_logits", "conv_last_map", "layers16", "batch5", "dense16_wide", "synth_pool12_relu"]
 
 
 def _case(name, n=5):
@@ -159,6 +161,118 @@ def test_pack_round_trip_against_the_plan(name):
     assert np.array_equal(again[real], payload[real]) and np.array_equal(again[~real], marked[~real])
     with pytest.raises(ValueError):
         train.pack(tensors[:-1] + [dict(w=tensors[-1]["w"][..., None], b=tensors[-1]["b"])], lay)
+
+
+# ---- the order of a multi-tile call's sums, and the trainer's batch ---------------------------------------------------------------
+FOLD_ROW, FOLD_TILES, FOLD_ROWS, FOLD_GRID = "pool21_trunc_h", 40, 16, 16
+
+
+@pytest.fixture(scope="module")
+def fold_case():
+    """(model, layout, x, y, the whole batch's float64 gradient, T [40][w_floats]: each tile's float64 gradient of the batch loss, cast)."""
+    n = FOLD_TILES * FOLD_ROWS
+    model, x, y = _case(FOLD_ROW, n)
+    lay, w = train.layout(model)
+    whole = fgrad_ref.loss_grad(model, x, y)
+    T = np.stack([train.pack(fgrad_ref.loss_grad(model, x[j:j + FOLD_ROWS], y[j:j + FOLD_ROWS], n_total=n)["grads"], lay)
+                  for j in range(0, n, FOLD_ROWS)])
+    assert T.shape == (FOLD_TILES, w) and T.dtype == np.float32
+    return model, lay, x, y, whole, T
+
+
+def test_fold_tiles_sums_a_batch_within_the_bound(fold_case):
+    """Per-tile float64 gradients rounded to float32 and folded in the kernels' order: the whole batch's gradient within the GPU
+    tests' bound (tests/test_gpu_ftrain.py: bounds)."""
+    import test_gpu_ftrain as gt
+    model, lay, x, y, whole, T = fold_case
+    got = train.unpack(fgrad_ref.fold_tiles(T, FOLD_GRID, 1.0), lay)
+    per, _ = gt.bounds(model, x, y, whole)
+    for g, g64, (bw, bb, _, _) in zip(got, whole["grads"], per):
+        for k, bound in (("w", bw), ("b", bb)):
+            err = fgrad_ref.tensor_error(g[k], g64[k])
+            print("%s: %.3g (bound %.3g)" % (k, err, bound))
+            assert err <= bound
+    one = fgrad_ref.fold_tiles(T[:3], FOLD_GRID, 1.0)                       # fewer tiles than workgroups: three slabs of one tile
+    assert np.array_equal(one, (T[0] + T[1]) + T[2])
+    with pytest.raises(AssertionError):
+        fgrad_ref.fold_tiles(T, FOLD_GRID, 3.0)
+    with pytest.raises(AssertionError):
+        fgrad_ref.fold_tiles(T.astype(np.float64), FOLD_GRID, 1.0)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def test_fold_tiles_sees_a_swapped_tile_and_a_flat_chain(fold_case):
+    """What the exact GPU check (tests/test_gpu_ftrain_tiles.py) relies on: the folded bits change when two tiles of different
+    workgroups change places, when a workgroup's tiles are taken in another order than its slab adds them, and when all tiles are
+    summed in one chain; a power-of-two scale changes nothing."""
+    T = fold_case[5]
+    want = fgrad_ref.fold_tiles(T, FOLD_GRID, 1.0)
+    swapped = T.copy()
+    swapped[[3, FOLD_GRID + 4]] = T[[FOLD_GRID + 4, 3]]                      # workgroup 3's first tile and workgroup 4's second
+    assert not np.array_equal(_bits(fgrad_ref.fold_tiles(swapped, FOLD_GRID, 1.0)), _bits(want))
+    flat = T[0].copy()
+    for j in range(1, len(T)):
+        flat += T[j]
+    assert not np.array_equal(_bits(flat), _bits(want))
+    assert not np.array_equal(_bits(fgrad_ref.fold_tiles(T, len(T), 1.0)), _bits(want))     # one tile per workgroup: the flat chain again
+    assert np.array_equal(_bits(fgrad_ref.fold_tiles(T, len(T), 1.0)), _bits(flat))
+    assert not np.array_equal(_bits(fgrad_ref.fold_tiles(T, FOLD_GRID // 2, 1.0)), _bits(want))   # another grid: another order
+    # the power-of-two argument on the host
+    assert np.array_equal(_bits(fgrad_ref.fold_tiles(T * np.float32(2.0 ** 9), FOLD_GRID, 2.0 ** -9)), _bits(want))
+
+
+def test_a_lost_tile_moves_every_tensor_by_more_than_the_bound():
+    """pool21_trunc_h at n = 8 229 on a grid of 256 workgroups of 16 rows: without workgroup 0's second tile (rows 4 096 .. 4 111)
+    every tensor of the float64 gradient moves by more than the GPU tests' bound (the inputs were chosen so: the lowest ratio is
+    record 0's bias, 9). A wrong row inside a tile or another order of the sum is far below it: the exact check is for those."""
+    import test_gpu_ftrain as gt
+    n, b, grid = 8229, 16, 256
+    model, x, y = _case(FOLD_ROW, n)
+    whole = fgrad_ref.loss_grad(model, x, y)
+    rows = slice(grid * b, grid * b + b)
+    lost = fgrad_ref.loss_grad(model, x[rows], y[rows], n_total=n)["grads"]
+    per, _ = gt.bounds(model, x, y, whole)
+    ratios = []
+    for i, (g64, t, (bw, bb, _, _)) in enumerate(zip(whole["grads"], lost, per)):
+        for k, bound in (("w", bw), ("b", bb)):
+            moved = fgrad_ref.tensor_error(g64[k] - t[k], g64[k])
+            print("record %d %s: moved %.3g, bound %.3g, ratio %.1f" % (i, k, moved, bound, moved / bound))
+            ratios.append(moved / bound)
+    assert min(ratios) > 1.0, ratios
+
+
+def _plans():
+    out = {name: fnet_exact.plan(fnet_sweep.blob(name)) for name in fnet_sweep.ROWS}
+    with open(os.path.join(HERE, "golden", "cube_kws.ednf"), "rb") as f:
+        out["cube_kws"] = fnet_exact.plan(f.read())
+    return out
+
+
+def test_train_batch_is_the_networks_except_where_dy_does_not_fit():
+    """fgrad_ref.train_batch (ftrain_size_lds and edison_ftrain_create's lowering loop restated) on every sweep row and the shipped
+    network: only batch5 trains below its forward batch, at 2 of 5 -- dY of its first record, 1 064 rows x 16 padded channels an
+    utterance, is 144 704 bytes with its row bases at 2 utterances and over the limit at 3."""
+    plans = _plans()
+    for name, p in plans.items():
+        tb = fgrad_ref.train_batch(p)
+        assert 1 <= tb <= p["batch"] and fgrad_ref.train_lds_bytes(p, tb) <= fnet_exact.LDS_BYTES, name
+        assert tb == (2 if name == "batch5" else p["batch"]), (name, tb, p["batch"])
+    assert plans["batch5"]["batch"] == 5 and fgrad_ref.train_batch(plans["cube_kws"]) == 7
+    p = plans["batch5"]
+    assert p["layers"][0]["rows"] == 1064 and p["layers"][0]["n_pad"] == 16
+    assert fgrad_ref.train_lds_bytes(p, 2) == 4 * 2128 * 16 + 4 * 2128 == 144704
+    assert fgrad_ref.train_lds_bytes(p, 3) > fnet_exact.LDS_BYTES
+    # where the forward half is the larger one the bytes are the forward plan's: the shipped network's 159 808
+    assert fgrad_ref.train_lds_bytes(plans["cube_kws"], 7) == plans["cube_kws"]["lds_bytes"] == 159808
+    # a plan whose one utterance does not fit is refused (0), and a limit between two batches lowers by one
+    assert fgrad_ref.train_batch(p, limit=fgrad_ref.train_lds_bytes(p, 1) - 1) == 0
+    assert fgrad_ref.train_batch(p, limit=fgrad_ref.train_lds_bytes(p, 1)) == 1
+    # the new sweep row: forward batch 10, more packed floats than one pass of the step kernel covers on 256 CUs
+    wide = plans["dense16_wide"]
+    assert (wide["batch"], wide["n_layers"], fnet_sweep.w_floats(wide)) == (10, 16, 558928) and 558928 > fnet_sweep.STEP_PASS * 256
 
 
 def test_adam_restatement_against_torch():

@@ -42,6 +42,10 @@ def _facts(name):
     f |= {("NG>=3",) for x in fs.path(p)["NG"] if x >= 3} | {("n_out>=200",) for x in fs.path(p)["n_out"] if x >= 200}
     if 1 < p["batch"] < 16:
         f.add(("batch_mid",))
+    if p["n_layers"] == fe.MAX_LAYERS and max(L["rows"] for L in p["layers"]) > 1:
+        f.add(("layers16_maps",))                 # the most records the plan holds, with maps of several rows per utterance
+    if fs.w_floats(p) > fs.STEP_PASS * 256:
+        f.add(("step_second_pass",))              # more packed weights than one pass of the optimiser's step kernel covers on 256 CUs
     K0 = recs[0]["k"][0] * recs[0]["k"][1] * recs[0]["inp"][2]
     if len(recs) == 1 and _dense(recs[0]) and not recs[0]["b"].any():
         f.add(("ladder", K0))
@@ -99,7 +103,7 @@ REQUIRED = (
     + [("out_c", v) for v in (1, 15, 16, 17, 64, 65)] + [("out_c>=129",)]
     + [("in_c>=3",), ("dense_only",), ("conv_last_map",), ("layers", 16), ("imported_relu_folded",)]
     + [("batch", 1), ("batch", 16), ("batch_mid",), ("batch_mid_by_activations",), ("lds_within_1k",), ("largest_weights_batch1",)]
-    + [("m_tail_P4",), ("subnormal_outputs",)]
+    + [("m_tail_P4",), ("subnormal_outputs",), ("layers16_maps",), ("step_second_pass",)]
 )
 
 

@@ -10,6 +10,9 @@ held the same way, its terms the k rows along the network plus the logits.
 Every network is loaded with 1e6 in the padding k rows, padding channels and padding biases of its blob: the packed gradient's padding
 must still be exactly +0.0f and a step must leave the weights' padding what it was.
 
+Calls of more tiles than workgroups are tests/test_gpu_ftrain_tiles.py's; the helpers here (case, data, poisoned, bounds,
+check_gradient, check_plan) are shared with it.
+
 Measured on an MI355X, shipped network, n = 8 (GPU error / e32 per tensor, w then b): see DESIGN.md section 19."""
 import io
 import os
@@ -20,6 +23,7 @@ import pytest
 from conftest import GOLDEN
 
 import fgrad_ref
+import fnet_exact
 import fnet_pad
 import fnet_ref
 import fnet_sweep as fs
@@ -29,9 +33,17 @@ pytestmark = pytest.mark.gpu
 
 FIXTURE = os.path.join(GOLDEN, "cube_kws.ednf")
 ROWS = ["ladder_k5", "pool21_trunc_h", "pool12_trunc_w", "pool22_trunc_hw", "pool41_tail", "inc3_oc64_oc65_s21", "oc40_s32_span_h", "n_out_210",
-        "relu_logits", "conv_last_map", "layers16", "synth_pool12_relu", "cube_kws"]
-ALL_N = ("pool21_trunc_h", "inc3_oc64_oc65_s21")      # rows that run n over {1, batch - 1, batch, batch + 1, 3 batch + 2}
+        "relu_logits", "conv_last_map", "layers16", "batch5", "synth_pool12_relu", "cube_kws"]
+ALL_N = ("pool21_trunc_h", "inc3_oc64_oc65_s21", "batch5")      # rows that run n over {1, batch - 1, batch, batch + 1, 3 batch + 2}
+LOWERED = ("batch5",)                                  # rows whose dY does not fit the LDS at the network's own batch
 EPS = 2.0 ** -24
+
+
+def check_plan(blob, info):
+    """The trainer's batch and LDS bytes are the restated plan's (fgrad_ref.train_batch: ftrain_size_lds and the lowering loop)."""
+    p = fnet_exact.plan(blob)
+    assert info["batch"] == fgrad_ref.train_batch(p) and info["lds_bytes"] == fgrad_ref.train_lds_bytes(p, info["batch"]), (info, p["batch"])
+    return p
 
 
 @pytest.fixture(scope="module")
@@ -130,6 +142,8 @@ def test_logits_loss_gradient_padding_repeat_and_no_side_effect(ctx, name):
         info = tr.info()
         b = info["batch"]
         assert info["w_floats"] == len(real) and info["lds_bytes"] <= 160 * 1024 and info["grid"] >= 1 and info["steps"] == 0
+        p = check_plan(blob, info)
+        assert (b < p["batch"]) == (name in LOWERED), (name, b, p["batch"])
         ns = sorted({1, max(b - 1, 1), b, b + 1, 3 * b + 2}) if name in ALL_N else [b + 1]
         w0 = tr.packed_weights()
         for n in ns:
@@ -173,6 +187,7 @@ def test_tied_pool_windows_send_the_gradient_to_their_first_element(ctx, pool):
     before = ctx.fnet(x)
     with ctx.trainer() as tr:
         assert tr.info()["batch"] < len(y)                                  # more than one tile
+        check_plan(blob, tr.info())
         r = tr.grad(x, y)
         assert np.array_equal(tr.logits(len(y)).view(np.uint32), before["logits"].view(np.uint32))
         assert np.array_equal(r["argmax"], before["argmax"])
@@ -229,6 +244,240 @@ def test_adam_steps_in_place_and_the_exported_network(ctx, fresh):
 def fnet_logits_of(c, blob, x):
     c.fnet_load(blob)
     return c.fnet(x)["logits"]
+
+
+def step_errors(tr, real, got, want):
+    """Per element of the packed array |got - want| / max |want| over the element's tensor (a record's w or its b), real entries
+    only; 0 at the padding."""
+    err = np.zeros(len(got))
+    for r in tr.layout:
+        nb = r["k_pad"] * r["n_pad"]
+        for lo, hi in ((r["w_at"], r["w_at"] + nb), (r["w_at"] + nb, r["w_at"] + nb + r["n_pad"])):
+            m = real[lo:hi]
+            err[lo:hi][m] = np.abs(got[lo:hi][m] - want[lo:hi][m]) / np.abs(want[lo:hi][m]).max()
+    return err
+
+
+def grad_and_step(tr, x, y, lr, replays):
+    """One gradient call and one step; every replay in `replays` (fgrad_ref.Adam, or None for SGD) takes the step in float64 from the
+    weights the GPU stepped from with the GPU's own gradient. Returns (the GPU's weights, each replay's weights, the weights before)."""
+    w_before = tr.packed_weights()
+    tr.grad(x, y)
+    g = tr.gradient().astype(np.float64)
+    tr.step(lr)
+    wants = []
+    for opt in replays:
+        want = [w_before.astype(np.float64)]
+        if opt is None:
+            want[0] -= lr * g
+        else:
+            opt.step(want, [g], lr)
+        wants.append(want[0])
+    return tr.packed_weights(), wants, w_before
+
+
+def test_a_network_the_step_kernel_takes_in_two_passes(ctx):
+    """dense16_wide has 558 928 packed floats; ed_launch_ftrain_step caps the grid at 8 blocks of 256 threads a CU, so on up to 272 CUs
+    its tail is the stride loop's second pass. One gradient at n = batch + 1 against float64, then three Adam steps and one SGD step
+    against the float64 restatement over every element, the second pass's reported apart."""
+    name = "dense16_wide"
+    model, blob, real = case(name)
+    ctx.fnet_load(blob)
+    with ctx.trainer() as tr:
+        info = tr.info()
+        check_plan(blob, info)
+        second = fs.STEP_PASS * info["grid"]
+        assert info["w_floats"] == len(real) == 558928 and info["w_floats"] > second, "the packed weights fit one pass of the step kernel on this device"
+        assert real[second:].sum() > 1000
+        n = info["batch"] + 1
+        x, y = data(name, model, n)
+        ref = fgrad_ref.loss_grad(model, x, y)
+        before = ctx.fnet(x)
+        r = tr.grad(x, y)
+        assert np.array_equal(tr.logits(n).view(np.uint32), before["logits"].view(np.uint32))
+        assert np.array_equal(r["argmax"], before["argmax"])
+        _, (lb, _) = bounds(model, x, y, ref)
+        assert fgrad_ref.tensor_error(r["loss"], ref["loss"]) <= lb
+        check_gradient(name, tr, model, real, x, y, ref)
+        assert np.count_nonzero(tr.gradient()[second:]) > 1000          # the second pass has gradients to apply
+        adam = fgrad_ref.Adam()
+        for step, (opt, lr) in enumerate([(adam, 0.001)] * 3 + [(None, 0.01)]):
+            if opt is None:
+                tr.set_opt("sgd")
+            got, (want,), w_before = grad_and_step(tr, x, y, lr, [opt])
+            err = step_errors(tr, real, got, want)
+            print("step %d (%s): first pass %.3g, second pass (from element %d) %.3g, bound %.3g" % (
+                step + 1, "sgd" if opt is None else "adam", err[:second].max(), second, err[second:].max(), 4 * EPS))
+            assert err.max() <= 4 * EPS, (step, int(err.argmax()), err.max())
+            assert (got[~real] == np.float32(1.0e6)).all()
+            moved = got != w_before
+            assert moved[:second].any() and moved[second:].sum() > 1000
+        assert tr.info()["steps"] == 4
+
+
+def test_adam_away_from_its_defaults_over_ten_steps(ctx):
+    """b1 = 0.5, b2 = 0.9, eps = 1e-2 at lr = 0.01, ten steps, each on other rows. The bound is the three-step test's 4 x 2^-24 of the
+    tensor's maximum: half an ulp of the weight plus an lr-sized update whose relative error is a few 2^-24 per step of drift in m and
+    v. At these constants eps is no rounding matter: the same replay at eps = 1e-7 misses the GPU's weights by more than the bound at
+    every step."""
+    name = "pool21_trunc_h"
+    model, blob, real = case(name)
+    ctx.fnet_load(blob)
+    xs, ys = data(name, model, 170)
+    lr = 0.01
+    with ctx.trainer() as tr:
+        check_plan(blob, tr.info())
+        tr.set_opt("adam", b1=0.5, b2=0.9, eps=1e-2)
+        adam, adam7 = fgrad_ref.Adam(0.5, 0.9, 1e-2), fgrad_ref.Adam(0.5, 0.9, 1e-7)
+        worst = 0.0
+        for step in range(10):
+            got, (want, want7), _ = grad_and_step(tr, xs[17 * step:17 * step + 17], ys[17 * step:17 * step + 17], lr, [adam, adam7])
+            err, err7 = step_errors(tr, real, got, want).max(), step_errors(tr, real, got, want7).max()
+            print("step %2d: %.3g (bound %.3g); the replay at eps 1e-7: %.3g" % (step + 1, err, 4 * EPS, err7))
+            assert err <= 4 * EPS, (step, err)
+            assert err7 > 4 * EPS, (step, err7)
+            assert (got[~real] == np.float32(1.0e6)).all()
+            worst = max(worst, err)
+        print("largest error over ten steps: %.3g" % worst)
+        assert tr.info()["steps"] == 10
+
+
+def test_a_step_at_lr_zero_moves_the_moments_only(ctx):
+    name = "pool21_trunc_h"
+    model, blob, real = case(name)
+    ctx.fnet_load(blob)
+    xs, ys = data(name, model, 34)
+    with ctx.trainer() as tr:
+        adam, skipped = fgrad_ref.Adam(), fgrad_ref.Adam()
+        got, _, w_before = grad_and_step(tr, xs[:17], ys[:17], 0.0, [adam])
+        assert np.array_equal(got.view(np.uint32), w_before.view(np.uint32)) and tr.info()["steps"] == 1
+        # the next step is the replay's that took the step at lr = 0 too; one that left it out is an lr-sized update away
+        got, (want, want_skipped), _ = grad_and_step(tr, xs[17:], ys[17:], 0.01, [adam, skipped])
+        err, err_skipped = step_errors(tr, real, got, want).max(), step_errors(tr, real, got, want_skipped).max()
+        print("after lr = 0: %.3g (bound %.3g); a replay without that step: %.3g" % (err, 4 * EPS, err_skipped))
+        assert err <= 4 * EPS and err_skipped > 4 * EPS and tr.info()["steps"] == 2
+
+
+def test_refused_optimiser_arguments_leave_the_state(ctx):
+    """set_opt with b1 = 1, b2 = -0.1, eps = 0 or a kind that does not exist, and step with a negative, NaN or infinite rate: each
+    EDISON_E_ARGUMENT, and the weights, the step count and the constants set before are what they were -- the next step is the
+    replay's at those constants."""
+    import ctypes
+    name = "pool21_trunc_h"
+    model, blob, real = case(name)
+    ctx.fnet_load(blob)
+    x, y = data(name, model, 17)
+    with ctx.trainer() as tr:
+        tr.set_opt("adam", b1=0.5, b2=0.9, eps=1e-2)
+        adam = fgrad_ref.Adam(0.5, 0.9, 1e-2)
+        got, (want,), _ = grad_and_step(tr, x, y, 0.01, [adam])
+        assert step_errors(tr, real, got, want).max() <= 4 * EPS
+        w1 = tr.packed_weights()
+        for kw in (dict(b1=1.0), dict(b2=-0.1), dict(eps=0.0), dict(b1=float("nan")), dict(eps=-1e-7)):
+            with pytest.raises(_lib.EdisonError) as e:
+                tr.set_opt("adam", **kw)
+            assert e.value.code == _lib.E_ARGUMENT and "Adam takes" in str(e.value), kw
+        code = tr._L.edison_ftrain_set_opt(tr._h, 7, ctypes.c_double(0.9), ctypes.c_double(0.999), ctypes.c_double(1e-7))
+        assert code == _lib.E_ARGUMENT
+        with pytest.raises(ValueError):
+            tr.set_opt("adadelta")
+        for lr in (-1.0, float("nan"), float("inf"), float("-inf")):
+            with pytest.raises(_lib.EdisonError) as e:
+                tr.step(lr)
+            assert e.value.code == _lib.E_ARGUMENT and "learning rate" in str(e.value), lr
+        assert tr.info()["steps"] == 1 and np.array_equal(tr.packed_weights().view(np.uint32), w1.view(np.uint32))
+        got, (want,), _ = grad_and_step(tr, x, y, 0.01, [adam])
+        err = step_errors(tr, real, got, want).max()
+        assert err <= 4 * EPS and tr.info()["steps"] == 2, err
+        assert np.array_equal(ctx.fnet(x)["logits"], fnet_logits_of_weights(ctx, tr, x))
+
+
+def fnet_logits_of_weights(c, tr, x):
+    """The logits a trainer's own forward half gives on its weights now."""
+    tr.grad(x, np.zeros(len(x), np.int32))
+    return tr.logits(len(x))
+
+
+def test_a_call_of_no_rows(ctx):
+    name = "pool21_trunc_h"
+    model, blob, real = case(name)
+    ctx.fnet_load(blob)
+    x, y = data(name, model, 17)
+    with ctx.trainer() as tr:
+        tr.set_opt("sgd")
+        tr.grad(x, y)
+        assert tr.gradient()[real].any()
+        r = tr.grad(np.zeros((0, tr.in_n), np.float32), np.zeros(0, np.int32))
+        assert r["loss"].shape == (0,) and r["argmax"].shape == (0,) and r["loss"].dtype == np.float32
+        assert not tr.gradient().view(np.uint32).any()                      # every entry +0.0f
+        z = tr.logits(0)
+        assert z.shape == (0, tr.n_out)
+        w0 = tr.packed_weights()
+        tr.step(0.1)
+        assert np.array_equal(tr.packed_weights().view(np.uint32), w0.view(np.uint32)) and tr.info()["steps"] == 1
+        # and the trainer goes on: the call after it is the call before it
+        tr.grad(x, y)
+        g = tr.gradient()
+    with ctx.trainer() as again:
+        again.grad(x, y)
+        assert np.array_equal(again.gradient().view(np.uint32), g.view(np.uint32))
+
+
+def test_a_small_call_after_a_large_one(ctx):
+    """After 2 grid batch + 1 rows every workgroup's slab holds a sum; a call of one row launches one workgroup and a call of
+    batch + 1 rows two, and only their slabs are summed: the bits are a fresh trainer's for the same rows."""
+    name = "pool21_trunc_h"
+    model, blob, real = case(name)
+    ctx.fnet_load(blob)
+    with ctx.trainer() as tr:
+        info = tr.info()
+        b, G = info["batch"], info["grid"]
+        x, y = data(name, model, 2 * G * b + 1)
+        tr.grad(x, y)
+        assert tr.gradient()[real].any()
+        got = []
+        for n in (1, b + 1):
+            r = tr.grad(x[:n], y[:n])
+            got.append((n, r, tr.gradient(), tr.logits(n)))
+    with ctx.trainer() as again:
+        for n, r, g, z in got:
+            r2 = again.grad(x[:n], y[:n])
+            assert np.array_equal(again.gradient().view(np.uint32), g.view(np.uint32)), n
+            assert np.array_equal(r2["loss"].view(np.uint32), r["loss"].view(np.uint32)) and np.array_equal(r2["argmax"], r["argmax"])
+            assert np.array_equal(again.logits(n).view(np.uint32), z.view(np.uint32))
+            assert not g[~real].view(np.uint32).any()
+
+
+def test_set_weights_round_trip(ctx, fresh):
+    name = "inc3_oc64_oc65_s21"
+    model, blob, real = case(name)
+    ctx.fnet_load(blob)
+    x, y = data(name, model, 9)
+    old = ctx.fnet(x)["logits"]
+    with ctx.trainer() as tr:
+        rng = np.random.default_rng(19)
+        new = [dict(w=(t["w"] * 1.25 + rng.normal(0, 0.01, t["w"].shape)).astype(np.float32),
+                    b=(t["b"] - rng.normal(0, 0.05, t["b"].shape)).astype(np.float32)) for t in tr.weights()]
+        tr.set_weights(new)
+        packed = tr.packed_weights()
+        assert (packed[~real] == np.float32(1.0e6)).all()                   # the padding stays what it was
+        assert np.array_equal(packed[real], train.pack(new, tr.layout)[real])
+        for a, t in zip(tr.weights(), new):
+            assert np.array_equal(a["w"], t["w"]) and np.array_equal(a["b"], t["b"])
+        now = ctx.fnet(x)["logits"]                                         # the context runs the new weights ...
+        assert not np.array_equal(now, old)
+        fresh.fnet_load(cube_import.build_blob(tr.model()))                 # ... the ones a fresh load of the exported network runs
+        assert np.array_equal(fresh.fnet(x)["logits"].view(np.uint32), now.view(np.uint32))
+        tr.grad(x, y)
+        assert np.array_equal(tr.logits(len(y)).view(np.uint32), now.view(np.uint32))
+        with pytest.raises(ValueError):
+            tr.set_packed_weights(packed[:-1])
+        with pytest.raises(ValueError):
+            tr.set_weights(new[:-1])
+        # set_packed_weights takes the whole array, padding included
+        tr.set_packed_weights(np.where(real, packed, np.float32(0)))
+        assert not tr.packed_weights()[~real].any()
+        assert np.array_equal(ctx.fnet(x)["logits"].view(np.uint32), now.view(np.uint32))
 
 
 def test_refusals_and_the_ignored_counter(ctx):
@@ -291,8 +540,10 @@ def test_a_network_that_fills_the_lds_trains_or_is_refused_by_name(ctx):
     try:
         with ctx.trainer() as tr:
             assert tr.info()["batch"] == 1 and tr.info()["lds_bytes"] <= 160 * 1024
+            check_plan(fs.blob("batch1_lds_max"), tr.info())
     except _lib.EdisonError as e:
         assert e.code == _lib.E_NO_IMPL and "LDS" in str(e)
+        assert fgrad_ref.train_batch(fnet_exact.plan(fs.blob("batch1_lds_max"))) == 0
 
 
 def test_fit_learns_the_synthetic_set(ctx):
