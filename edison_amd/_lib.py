@@ -302,6 +302,7 @@ SIGNATURES = {
     "edison_fcal_add": (c_int, [c_void_p, c_void_p, c_int64]),
     "edison_fcal_result": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "edison_ftrain_create": (c_int, [c_void_p, ctypes.POINTER(c_void_p)]),
+    "edison_ftrain_create_ex": (c_int, [c_void_p, ctypes.c_uint32, ctypes.POINTER(c_void_p)]),
     "edison_ftrain_destroy": (None, [c_void_p]),
     "edison_ftrain_info": (c_int, [c_void_p, ctypes.POINTER(FtrainInfo)]),
     "edison_ftrain_layout": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),

@@ -566,11 +566,12 @@ class Context:
         return calibrate.quantize_audio(self, audio, geometry=geometry, q15=q15, chunk=chunk, method=method, saturate=saturate, **kw)
 
     # ------------------------------------------------------------------ training the float network (edison_ftrain_*, train.py)
-    def trainer(self):
-        """A train.Trainer on this context, bound to the loaded float network (no conv or pool pads): grad / grad_t, step, weights,
-        set_weights, model, fit (edison_ftrain_create). Its steps change the loaded network's device weights in place."""
+    def trainer(self, padded=False):
+        """A train.Trainer on this context, bound to the loaded float network: grad / grad_t, step, weights, set_weights, model, fit
+        (edison_ftrain_create_ex). padded=True also takes networks with conv or pool pads (EDISON_FTRAIN_PADDED); without it such a
+        network is refused. Its steps change the loaded network's device weights in place."""
         from . import train
-        return train.Trainer(self)
+        return train.Trainer(self, padded=padded)
 
     def _fnet_refresh(self):
         """Bring _fnet_blob up to the weights a trainer has stepped the loaded network to (quantize() reads the weights from it)."""

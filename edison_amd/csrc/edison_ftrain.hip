@@ -3,7 +3,9 @@
  * trainer owns its copy of the network's plan at the training batch, the inverse origin tables of the backward half, one gradient slab
  * and one activation store per workgroup of the grid, the reduced gradient and Adam's moments. The weights it trains are the loaded
  * network's own device buffer. A gradient call is two launches on the context's stream (fnet_grad_kernels.hip), a step one. The trainer
- * serves the network of one load: after another edison_fnet_load* its calls fail with EDISON_E_NO_MODEL.
+ * serves the network of one load: after another edison_fnet_load* its calls fail with EDISON_E_NO_MODEL. edison_ftrain_create refuses a
+ * network with a conv or pool pad; edison_ftrain_create_ex with EDISON_FTRAIN_PADDED takes it (two ints per row base, the inverse
+ * origin table from the padded tables).
  */
 #include <math.h>
 #include <stdlib.h>
@@ -44,7 +46,7 @@ static int ftrain_live(edison_ftrain *t, const char *who)
 
 static float *ftrain_w(edison_ftrain *t) { return const_cast<float *>(t->plan.net.w); } /* the loaded network's device weights */
 
-/* dY and the row bases of the largest record at the plan's batch */
+/* dY and the row bases of the largest record at the plan's batch; a padded record's row has two ints: its utterance's base and its origin */
 static void ftrain_size_lds(ed_ftrain_plan_t *tp)
 {
 	int64_t dy = 0, rb = 0;
@@ -53,20 +55,23 @@ static void ftrain_size_lds(ed_ftrain_plan_t *tp)
 		const ed_fnet_layer_t &L = tp->net.L[l];
 		const int64_t mp = ((int64_t)tp->net.batch * L.rows + 15) & ~(int64_t)15;
 		if (mp * L.n_pad > dy) dy = mp * L.n_pad;
-		if (mp > rb) rb = mp;
+		if (mp * (L.pad ? 2 : 1) > rb) rb = mp * (L.pad ? 2 : 1);
 	}
 	tp->dy_lds = (int32_t)(dy < INT32_MAX ? dy : INT32_MAX);
 	tp->rb_lds = (int32_t)(rb < INT32_MAX ? rb : INT32_MAX);
 }
 
-extern "C" int edison_ftrain_create(edison_ctx *ctx, edison_ftrain **out)
+extern "C" int edison_ftrain_create(edison_ctx *ctx, edison_ftrain **out) { return edison_ftrain_create_ex(ctx, 0, out); }
+
+extern "C" int edison_ftrain_create_ex(edison_ctx *ctx, uint32_t flags, edison_ftrain **out)
 {
 	if (!ctx || !out) return EDISON_E_ARGUMENT;
 	*out = NULL;
+	if (flags & ~EDISON_FTRAIN_PADDED) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_create_ex: flags has a bit other than EDISON_FTRAIN_PADDED");
 	const ed_fnet_plan_t *net = ed_ctx_fnet_plan(ctx);
 	if (!net) return ed_set_err(ctx, EDISON_E_NO_MODEL, "no float network loaded (edison_fnet_load)");
 	for (int l = 0; l < net->n_layers; l++)
-		if (net->L[l].pad)
+		if (net->L[l].pad && !(flags & EDISON_FTRAIN_PADDED))
 		{
 			snprintf(ctx->err, sizeof(ctx->err), "edison_ftrain_create: record %d has a conv or pool pad; training runs networks without pads", l);
 			return EDISON_E_NO_IMPL;
@@ -90,7 +95,8 @@ extern "C" int edison_ftrain_create(edison_ctx *ctx, edison_ftrain **out)
 	}
 	if (hipSetDevice(ctx->device) != hipSuccess) { delete t; return ed_set_err(ctx, EDISON_E_RUNTIME, "edison_ftrain_create: hipSetDevice failed"); }
 
-	/* the inverse origin tables, from the plan's own koff / rowin: row r reads position (rowin[r] + koff[k]) / in_c through tap k / in_c */
+	/* the inverse origin tables, from the plan's own koff / rowin: row r reads position (rowin[r] + koff[k]) / in_c through tap k / in_c;
+	 * a padded record's row that is not absent reads (y0 + ky, x0 + kx) through tap (ky, kx) where that lies inside the image */
 	const size_t tabn = (size_t)last.rowin_at + (size_t)last.rows;
 	std::vector<int32_t> tab(tabn), inv;
 	if (hipMemcpy(tab.data(), net->tab, tabn * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
@@ -118,7 +124,21 @@ extern "C" int edison_ftrain_create(edison_ctx *ctx, edison_ftrain **out)
 		inv.resize(inv.size() + (size_t)G.np * G.T, -1);
 		int32_t *iv = inv.data() + G.inv_at;
 		for (int r = 0; r < L.rows; r++)
-			for (int tap = 0; tap < G.T; tap++) iv[(size_t)((rowin[r] + koff[tap * L.in_c]) / L.in_c) * G.T + tap] = r;
+		{
+			if (!L.pad)
+			{
+				for (int tap = 0; tap < G.T; tap++) iv[(size_t)((rowin[r] + koff[tap * L.in_c]) / L.in_c) * G.T + tap] = r;
+				continue;
+			}
+			if (rowin[r] < 0) continue; /* absent */
+			const int y0 = (rowin[r] >> 16) - ED_FNET_ORIGIN_BIAS, x0 = (rowin[r] & 0xffff) - ED_FNET_ORIGIN_BIAS;
+			for (int tap = 0; tap < G.T; tap++)
+			{
+				const int32_t kyx = koff[L.k_pad + tap * L.in_c];
+				const int y = y0 + (kyx >> 16), x = x0 + (kyx & 0xffff);
+				if (y >= 0 && y < L.in_h && x >= 0 && x < L.in_w) iv[(size_t)(y * L.in_w + x) * G.T + tap] = r;
+			}
+		}
 	}
 
 	const int64_t store = (int64_t)tp.net.batch * tp.net.acts_n;

@@ -1,6 +1,8 @@
 /*
  * fnet_grad_kernels.hip -- training the loaded float32 network (edison_ftrain.hip, edison_amd/train.py): the
- * gradient of the batch-mean cross entropy with respect to every weight and bias, and the optimiser step. Records without pads only.
+ * gradient of the batch-mean cross entropy with respect to every weight and bias, and the optimiser step. ed_ftrain_grad_kernel<false>
+ * is the kernel of a plan without padded records; <true> also holds the padded path of the forward tile and of
+ * the dW gather, taken by the records that have pad; dX reads the inverse origin table only and is the same for both.
  *
  * ed_ftrain_grad_kernel. A fixed grid of workgroups; workgroup g takes the tiles of utterances g, g + grid, g + 2 grid, ... in that
  * order, each through a forward half and a backward half, and adds what the tile gives into its own gradient slab (the first tile
@@ -33,9 +35,10 @@
 #include "fnet_device.h"
 #include "fnet_train.h"
 
-/* edf_tile (fnet_device.h, PAD = false) with the training epilogue: the MFMA loop and the order bias, ReLU, pool are edf_tile's; every
- * pooled output also goes to acts (this workgroup's store, utterance-major) with its mask byte. */
-template <int NT>
+/* edf_tile (fnet_device.h) with the training epilogue: the MFMA loop and the order bias, ReLU, pool are edf_tile's; every pooled output
+ * also goes to acts (this workgroup's store, utterance-major) with its mask byte. PAD = true takes edf_tile<NT, true>'s three
+ * differences: edf_pad_row, edf_pad_tap on the kyx behind koff, and edf_pad_live, an absent row being -inf before the window's max. */
+template <int NT, bool PAD>
 __device__ __forceinline__ void edg_tile(const ed_fnet_layer_t &L, const float *__restrict__ src, int src_n, float *__restrict__ dst, int dst_n,
                                          const float *__restrict__ wl, const int32_t *__restrict__ kl, const int32_t *__restrict__ rowin,
                                          const float *__restrict__ bias, int M, int mt, int n0, int lane, float *__restrict__ acts,
@@ -44,7 +47,9 @@ __device__ __forceinline__ void edg_tile(const ed_fnet_layer_t &L, const float *
 	const int r = lane & 15, kq = lane >> 4;
 	const int m = mt * 16 + r;
 	int base = 0;
-	if (m < M)
+	[[maybe_unused]] int y0 = 0, x0 = 0;
+	if constexpr (PAD) edf_pad_row(L, rowin, src_n, M, m, base, y0, x0);
+	else if (m < M)
 	{
 		const int u = m / L.rows;
 		base = u * src_n + rowin[m - u * L.rows];
@@ -57,7 +62,9 @@ __device__ __forceinline__ void edg_tile(const ed_fnet_layer_t &L, const float *
 	for (int k0 = 0; k0 < L.k_pad; k0 += 4)
 	{
 		const int ko = kl[k0 + kq];
-		const float a = ko >= 0 ? src[base + ko] : 0.0f;
+		float a;
+		if constexpr (PAD) a = edf_pad_tap(L, src, base, y0, x0, ko, kl[L.k_pad + k0 + kq]);
+		else a = ko >= 0 ? src[base + ko] : 0.0f;
 #pragma unroll
 		for (int j = 0; j < NT; j++) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wp[j * 16], acc[j], 0, 0, 0);
 		wp += 4 * L.n_pad;
@@ -65,6 +72,8 @@ __device__ __forceinline__ void edg_tile(const ed_fnet_layer_t &L, const float *
 	/* D: lane holds rows 4 kq + i (i = 0..3) of channel n0 + 16 j + r */
 	const int P = L.P;
 	const int m0 = mt * 16 + 4 * kq;
+	[[maybe_unused]] bool live[4];
+	if constexpr (PAD) edf_pad_live(L, rowin, M, m0, live);
 #pragma unroll
 	for (int j = 0; j < NT; j++)
 	{
@@ -77,9 +86,11 @@ __device__ __forceinline__ void edg_tile(const ed_fnet_layer_t &L, const float *
 		{
 			v[i] = acc[j][i] + b;
 			if (L.relu) v[i] = fmaxf(v[i], 0.0f);
+			if constexpr (PAD) { if (!live[i]) v[i] = -INFINITY; } /* absent: the max's identity; its window has a real element */
 		}
 		/* one pooled output: the window's maximum x at rows mg .., its first maximum e in element order; under ReLU a maximum of 0 is a
-		 * pre-activation <= 0 and passes nothing */
+		 * pre-activation <= 0 and passes nothing. A padded record's absent elements are -inf and x is a present element's finite value
+		 * (a pad is smaller than its window), so the v[g] == x chains below pick the first maximum among the present elements. */
 		auto emit = [&](int mg, float x, int e) {
 			if (mg >= M) return;
 			const int pass = !L.relu || x > 0.0f ? EDFT_PASS : 0;
@@ -124,16 +135,18 @@ __device__ __forceinline__ void edg_item(int nt, const ed_fnet_layer_t &L, const
                                          const float *__restrict__ wl, const int32_t *__restrict__ kl, const int32_t *__restrict__ rowin,
                                          const float *__restrict__ bias, int M, int mt, int n0, int lane, float *, int64_t, int64_t, const edg_stores &st)
 {
-	static_assert(!PAD, "records without pads only");
-	if (nt == 4) edg_tile<4>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
-	else if (nt == 3) edg_tile<3>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
-	else if (nt == 2) edg_tile<2>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
-	else edg_tile<1>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
+	if (nt == 4) edg_tile<4, PAD>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
+	else if (nt == 3) edg_tile<3, PAD>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
+	else if (nt == 2) edg_tile<2, PAD>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
+	else edg_tile<1, PAD>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
 }
 
 /* dW of 16 k rows (k tile kt; kt == KT is the bias row: A = 1 in row 0) x NT tiles of 16 channels from n0, summed over the tile's M rows
- * four at a time in ascending order (rows beyond M multiply zeros), into the workgroup's slab. src: the record's input, utterance u at src + u * src_n. */
-template <int NT>
+ * four at a time in ascending order (rows beyond M multiply zeros), into the workgroup's slab. src: the record's input, utterance u at src + u * src_n.
+ * PAD = false: rb[m] is row m's base in src. PAD = true: rb[2 m] is its utterance's base and rb[2 m + 1] its packed origin (fnet.h), -1
+ * for an absent row and for a row beyond M; the lane's k is one tap (ky, kx) for the whole tile (kyx behind koff), read where
+ * edf_pad_tap reads it: inside the image. The bias row needs neither: dY is +0.0f on absent rows. */
+template <int NT, bool PAD>
 __device__ __forceinline__ void edg_dw_tile(const ed_fnet_layer_t &L, int K, const float *__restrict__ src, const int32_t *__restrict__ koff,
                                             const float *__restrict__ dy, const int32_t *__restrict__ rb, int M, int kt, int KT, int n0, int lane,
                                             float *__restrict__ slab, bool first)
@@ -142,6 +155,13 @@ __device__ __forceinline__ void edg_dw_tile(const ed_fnet_layer_t &L, int K, con
 	const bool is_bias = kt == KT;
 	const int k = kt * 16 + r;
 	const int ko = !is_bias && k < K ? koff[k] : -1;
+	[[maybe_unused]] int ky = 0, kx = 0;
+	if constexpr (PAD)
+	{
+		const int32_t kyx = ko >= 0 ? koff[L.k_pad + k] : 0;
+		ky = kyx >> 16;
+		kx = kyx & 0xffff;
+	}
 	ed_f4 acc[NT];
 #pragma unroll
 	for (int j = 0; j < NT; j++) acc[j] = (ed_f4){0.0f, 0.0f, 0.0f, 0.0f};
@@ -155,6 +175,13 @@ __device__ __forceinline__ void edg_dw_tile(const ed_fnet_layer_t &L, int K, con
 		{
 			const int m = m0 + 4 * s + kq;
 			if (is_bias) a[s] = r == 0 ? 1.0f : 0.0f;
+			else if constexpr (PAD)
+			{
+				const int32_t o = rb[2 * m + 1]; /* m < the 16-padded M: the row-base array has it */
+				const int y0 = (o >> 16) - ED_FNET_ORIGIN_BIAS, x0 = (o & 0xffff) - ED_FNET_ORIGIN_BIAS;
+				const bool in = ko >= 0 && o >= 0 && (unsigned)(y0 + ky) < (unsigned)L.in_h && (unsigned)(x0 + kx) < (unsigned)L.in_w;
+				a[s] = in ? src[rb[2 * m] + (y0 * L.in_w + x0) * L.in_c + ko] : 0.0f;
+			}
 			else a[s] = ko >= 0 && m < M ? src[rb[m] + ko] : 0.0f;
 #pragma unroll
 			for (int j = 0; j < NT; j++) b[s][j] = dp[4 * s * L.n_pad + j * 16];
@@ -231,6 +258,7 @@ __device__ __forceinline__ void edg_dx_tile(const ed_fnet_layer_t &L, const ed_f
 	}
 }
 
+template <bool PADS>
 __global__ __launch_bounds__(ED_FNET_THREADS) void ed_ftrain_grad_kernel(const ed_ftrain_plan_t *tp, const float *__restrict__ in,
                                                                            const int32_t *__restrict__ labels, int64_t n, float *__restrict__ loss,
                                                                            int32_t *__restrict__ argmax, float *__restrict__ logits,
@@ -262,9 +290,9 @@ __global__ __launch_bounds__(ED_FNET_THREADS) void ed_ftrain_grad_kernel(const e
 			buf[0][u * p.buf_n[0] + e] = x0[i];
 		}
 
-		/* ---- forward: the network's own walk over edg_tile (records without pads only: the host refuses the others) ---- */
+		/* ---- forward: the network's own walk over edg_tile (PADS = false: the launcher starts it for plans without padded records) ---- */
 		const edg_stores stores = {acts, mask, acts_n};
-		for (int l = 0; l < p.n_layers; l++) EDF_LAYER_WALK(false, edg_item, p.L[l], (float *)NULL, 0, 0, stores)
+		for (int l = 0; l < p.n_layers; l++) EDF_LAYER_WALK(PADS, edg_item, p.L[l], (float *)NULL, 0, 0, stores)
 		__syncthreads();
 
 		/* ---- loss and dL/dz, one thread per utterance (the softmax and the argmax are ed_fnet_kernel's) ---- */
@@ -306,10 +334,16 @@ __global__ __launch_bounds__(ED_FNET_THREADS) void ed_ftrain_grad_kernel(const e
 				}
 				dy[i] = v;
 			}
+			const bool padded = PADS && L.pad;
 			for (int m = tid; m < Mp; m += ED_FNET_THREADS)
 			{
 				const int u = m / L.rows;
-				rb[m] = m < M ? u * src_n + rowin[m - u * L.rows] : 0;
+				if (padded)
+				{
+					rb[2 * m] = m < M ? u * src_n : 0;
+					rb[2 * m + 1] = m < M ? rowin[m - u * L.rows] : -1;
+				}
+				else rb[m] = m < M ? u * src_n + rowin[m - u * L.rows] : 0;
 			}
 			__syncthreads();
 			{
@@ -319,10 +353,20 @@ __global__ __launch_bounds__(ED_FNET_THREADS) void ed_ftrain_grad_kernel(const e
 				{
 					const int kt = item / NG, g = item - kt * NG;
 					const int n0 = g * 64, nt = NT - 4 * g < 4 ? NT - 4 * g : 4;
-					if (nt == 4) edg_dw_tile<4>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
-					else if (nt == 3) edg_dw_tile<3>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
-					else if (nt == 2) edg_dw_tile<2>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
-					else edg_dw_tile<1>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
+					if (padded)
+					{
+						if constexpr (PADS)
+						{
+							if (nt == 4) edg_dw_tile<4, true>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
+							else if (nt == 3) edg_dw_tile<3, true>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
+							else if (nt == 2) edg_dw_tile<2, true>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
+							else edg_dw_tile<1, true>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
+						}
+					}
+					else if (nt == 4) edg_dw_tile<4, false>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
+					else if (nt == 3) edg_dw_tile<3, false>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
+					else if (nt == 2) edg_dw_tile<2, false>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
+					else edg_dw_tile<1, false>(L, G.K, src, koff, dy, rb, M, kt, KT, n0, lane, slab, first);
 				}
 			}
 			if (l)
@@ -376,10 +420,13 @@ extern "C" int ed_launch_ftrain_grad(const ed_ftrain_plan_t *t, const ed_ftrain_
 	const ed_fnet_plan_t *p = &t->net;
 	const size_t lds = ed_ftrain_lds_bytes(t);
 	if (!ed_fnet_plan_launchable(p, lds) || grid < 1) return (int)hipErrorInvalidValue;
-	{ const int e = ed_kernel_prepare((const void *)ed_ftrain_grad_kernel, ED_FNET_THREADS, lds, NULL, NULL); if (e) return e; }
+	bool pads = false; /* a plan with a padded record runs the instantiation that holds the padded path, any other plan the one without */
+	for (int l = 0; l < p->n_layers; l++) pads = pads || p->L[l].pad;
+	const auto kernel = pads ? ed_ftrain_grad_kernel<true> : ed_ftrain_grad_kernel<false>;
+	{ const int e = ed_kernel_prepare((const void *)kernel, ED_FNET_THREADS, lds, NULL, NULL); if (e) return e; }
 	const int64_t n_tiles = (n + p->batch - 1) / p->batch;
 	const int used = (int)(n_tiles < grid ? n_tiles : grid); /* a workgroup without a tile would leave its slab stale */
-	hipLaunchKernelGGL(ed_ftrain_grad_kernel, dim3((unsigned)used), dim3(ED_FNET_THREADS), lds, stream, d_plan, in, labels, n, loss, argmax, logits, ignored);
+	hipLaunchKernelGGL(kernel, dim3((unsigned)used), dim3(ED_FNET_THREADS), lds, stream, d_plan, in, labels, n, loss, argmax, logits, ignored);
 	{ const int e = (int)hipGetLastError(); if (e) return e; }
 	hipLaunchKernelGGL(ed_ftrain_reduce_kernel, dim3((unsigned)((t->w_floats + 255) / 256)), dim3(256), 0, stream, t->slabs, used, t->w_floats, grad);
 	return (int)hipGetLastError();

@@ -29,7 +29,7 @@ typedef struct {
 	ed_ftrain_layer_t G[ED_FNET_MAX_LAYERS];
 	const int32_t *inv;
 	int32_t dy_lds;     /* floats of the backward half's dY[16-padded batch * rows][n_pad], the largest record's */
-	int32_t rb_lds;     /* ints of its row bases, the largest record's 16-padded batch * rows                 */
+	int32_t rb_lds;     /* ints of its row bases, the largest record's 16-padded batch * rows, two a row of a padded record */
 	int64_t w_floats;   /* the packed weight array: every record's B[k_pad][n_pad], then bias[n_pad]           */
 	/* per workgroup of the grid: a gradient slab [w_floats], and per utterance of its batch the records' outputs, their gradients
 	 * (both [acts_n] floats) and the mask bytes [acts_n] */

@@ -1,6 +1,6 @@
 """``kws train <net.ednf> <x.npy> <y.npy> <out.ednf>`` -- train a float32 X-CUBE-AI network on the GPU (``Context.trainer``,
-edison_amd/train.py): what the reference does with ``kws_keras.train`` (kws_keras.py:400-416), for networks
-without conv or pool pads. The network file gives the architecture and the starting weights: an imported network to fine-tune, or
+edison_amd/train.py): what the reference does with ``kws_keras.train`` (kws_keras.py:400-416), for every network
+the float path runs, 'same' convs and pools included. The network file gives the architecture and the starting weights: an imported network to fine-tune, or
 ``cube_import.build_blob`` of a freshly initialised model dict.
 
     x.npy           float32 [n, in_h * in_w * in_c] (or [n, in_h, in_w, in_c]): the network inputs, the float flow's features
@@ -25,7 +25,7 @@ def run(net, x_path, y_path, out_path, epochs=30, batch=100, lr=None, seed=0, va
     x, y = np.load(x_path), np.load(y_path)
     v = (np.load(val[0]), np.load(val[1])) if val else None
     ctx.fnet_load(net)
-    with ctx.trainer() as tr:
+    with ctx.trainer(padded=True) as tr:
         hist = tr.fit(x, y, epochs, batch_size=batch, val=v, seed=seed, lr=train.LEARNING_RATE if lr is None else lr)
         blob = tr.export()
     for i, (l, a) in enumerate(zip(hist["loss"], hist["acc"])):

@@ -4,7 +4,7 @@ loss). The gradient and the optimiser step are HIP kernels and the weights never
 shuffle, the history and the two callbacks are host code here, none of it hot.
 
     ctx.fnet_load(blob)                       # imported, or cube_import.build_blob of a freshly initialised model dict
-    tr = ctx.trainer()
+    tr = ctx.trainer(padded=True)             # padded: networks with 'same' convs and pools too
     hist = tr.fit(x, y, epochs=30, val=(vx, vy))
     trained = cube_import.build_blob(tr.model())
 
@@ -17,6 +17,7 @@ import numpy as np
 from . import _lib, cube_import
 
 ADAM, SGD = 0, 1          # EDISON_FTRAIN_ADAM, EDISON_FTRAIN_SGD
+FTRAIN_PADDED = 1         # EDISON_FTRAIN_PADDED: edison_ftrain_create_ex's flag
 LEARNING_RATE = 0.0005    # kws_keras.py:53 initial_learningrate
 BATCH_SIZE = 100          # kws_keras.py: batchSize
 
@@ -171,15 +172,15 @@ def fit(trainer, x, y, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=LEARN
 
 # ---- the GPU trainer --------------------------------------------------------------------------------------------------------------
 class Trainer:
-    """edison_ftrain on `ctx`, bound to the float network loaded now; loading another one invalidates it (EdisonError). Networks
-    without conv or pool pads."""
+    """edison_ftrain on `ctx`, bound to the float network loaded now; loading another one invalidates it (EdisonError).
+    padded=True (EDISON_FTRAIN_PADDED) also takes networks with conv or pool pads; without it they are refused."""
 
-    def __init__(self, ctx):
+    def __init__(self, ctx, padded=False):
         self._ctx, self._L = ctx, ctx._L
         if ctx._fnet_blob is None:
             raise ValueError("no float network loaded (fnet_load)")
         h = ctypes.c_void_p()
-        ctx._check(self._L.edison_ftrain_create(ctx._h, ctypes.byref(h)))
+        ctx._check(self._L.edison_ftrain_create_ex(ctx._h, FTRAIN_PADDED if padded else 0, ctypes.byref(h)))
         self._h = h
         self._model = cube_import.read_blob(ctx._fnet_blob)
         info = self.info()

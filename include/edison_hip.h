@@ -452,7 +452,12 @@ int edison_fcal_result(edison_fcal *c, uint32_t *absmax, uint64_t *hist, uint64_
 /*
  * Training the loaded float network (the epochs, callbacks and the model dict are edison_amd/train.py). A trainer is
  * bound to the float network loaded when it is created and updates that network's device weights in place: after a step the next
- * edison_fnet_batch, stream push or calibration on the context runs the new weights. Networks whose records have no conv or pool pad.
+ * edison_fnet_batch, stream push or calibration on the context runs the new weights.
+ *   edison_ftrain_create    a trainer for networks whose records have no conv or pool pad: a padded record is EDISON_E_NO_IMPL
+ *   edison_ftrain_create_ex the same with flags: EDISON_FTRAIN_PADDED also takes networks with 'same' convs and pools (DESIGN.md section
+ *                           14b), every network edison_fnet_load* loads; on a network without pads it makes edison_ftrain_create's
+ *                           trainer exactly. flags = 0 is edison_ftrain_create; any other bit is EDISON_E_ARGUMENT. Use this call with
+ *                           the flag unless a caller relies on the refusal.
  *   edison_ftrain_grad_dev  n inputs [n][in_n] and int32 labels [n] in device memory -> loss [n] (log sum exp(z) - z[y] per row) and
  *                           argmax [n] (edison_fnet_batch's), each NULL for not written, and, kept in the trainer, the logits [n][n_out]
  *                           (edison_fnet_batch's bit for bit) and the gradient of the batch loss (1 / n) sum loss with respect to every
@@ -472,11 +477,12 @@ int edison_fcal_result(edison_fcal *c, uint32_t *absmax, uint64_t *hist, uint64_
  * k = (ky kw + kx) in_c + ci, then bias[n_pad] (edison_ftrain_layout; K = the real k rows). Padding k rows and padding channels of the
  * gradient are exactly +0.0f whatever the blob holds there, so a step leaves the weights' padding as it was.
  * EDISON_E_NO_MODEL: no float network loaded at create; or, from every call but destroy, another float network was loaded since (create
- * a new trainer). EDISON_E_NO_IMPL at create, the message naming the cause: a record with a pad, or a training workgroup (the network at
- * batch 1 beside one utterance's dY) that does not fit the LDS.
+ * a new trainer). EDISON_E_NO_IMPL at create, the message naming the cause: a record with a pad (without EDISON_FTRAIN_PADDED), or a
+ * training workgroup (the network at batch 1 beside one utterance's dY) that does not fit the LDS.
  */
 #define EDISON_FTRAIN_ADAM 0
 #define EDISON_FTRAIN_SGD 1
+#define EDISON_FTRAIN_PADDED 1u
 typedef struct edison_ftrain edison_ftrain;
 typedef struct edison_ftrain_info_t {
 	int32_t n_layers;  /* conv / dense records */
@@ -490,6 +496,7 @@ typedef struct edison_ftrain_info_t {
 	int64_t ignored;   /* rows with a label outside [0, n_out) since create / reset (synchronises) */
 } edison_ftrain_info_t;
 int edison_ftrain_create(edison_ctx *ctx, edison_ftrain **out);
+int edison_ftrain_create_ex(edison_ctx *ctx, uint32_t flags, edison_ftrain **out);
 void edison_ftrain_destroy(edison_ftrain *t);
 int edison_ftrain_info(edison_ftrain *t, edison_ftrain_info_t *out);
 int edison_ftrain_layout(edison_ftrain *t, int record, int64_t *w_at, int32_t *K, int32_t *k_pad, int32_t *out_c, int32_t *n_pad);

@@ -7,7 +7,10 @@ between two host clock readings, ended by a device synchronise, so it holds the 
 (train, forward, train, ...), `--repeats` regions each, after a warm-up of every shape. Reported per batch: the median over regions of
 samples per second, its minimum and maximum. The learning rate is 0, so the weights the forward leg runs never move.
 
-    python tools/bench_train.py [--batches 100,4096] [--repeats 7] [--region-ms 300] [--out FILE.json]
+    python tools/bench_train.py [--net FILE.ednf] [--batches 100,4096] [--repeats 7] [--region-ms 300] [--out FILE.json]
+
+--net: another float network than the shipped one, 'same' convs and pools included (the trainer is created with padded=True; on a
+network without pads that is the plain trainer).
 
 One JSON line.
 """
@@ -25,6 +28,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--net", default=os.path.join(ROOT, "tests", "golden", "cube_kws.ednf"))
     ap.add_argument("--batches", default="100,4096")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--region-ms", type=float, default=300.0)
@@ -35,15 +39,15 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_train: no GPU (there is no CPU path to time)")
     ctx = Context(0)
-    ctx.fnet_load(os.path.join(ROOT, "tests", "golden", "cube_kws.ednf"))
+    ctx.fnet_load(args.net)
     info = ctx.fnet_info()
     in_n, n_out = info["in_h"] * info["in_w"] * info["in_c"], info["n_out"]
     dev = torch.device("cuda", 0)
     ctx.use_torch_stream()
-    tr = ctx.trainer()
+    tr = ctx.trainer(padded=True)
     tinfo = tr.info()
     rng = np.random.default_rng(19)
-    row = dict(network="cube_kws.ednf", device=torch.cuda.get_device_name(0), train_batch=tinfo["batch"], grid=tinfo["grid"], lds_bytes=tinfo["lds_bytes"],
+    row = dict(network=os.path.basename(args.net), device=torch.cuda.get_device_name(0), train_batch=tinfo["batch"], grid=tinfo["grid"], lds_bytes=tinfo["lds_bytes"],
                w_floats=tinfo["w_floats"], repeats=args.repeats, region_ms=args.region_ms, results=[])
     for n in [int(b) for b in args.batches.split(",")]:
         x = torch.from_numpy(rng.normal(0, 30, (n, in_n)).astype(np.float32)).to(dev)
