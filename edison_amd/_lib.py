@@ -316,6 +316,11 @@ SIGNATURES = {
     "edison_ftrain_weights_get": (c_int, [c_void_p, c_void_p]),
     "edison_ftrain_weights_set": (c_int, [c_void_p, c_void_p]),
     "edison_ftrain_reset": (c_int, [c_void_p]),
+    "edison_ftrain_set_dropout": (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_uint64]),
+    "edison_ftrain_set_dropout_call": (c_int, [c_void_p, ctypes.c_uint64]),
+    "edison_ftrain_dropout_get": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "edison_ftrain_grad_dev_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, ctypes.c_uint32]),
+    "edison_ftrain_grad_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, ctypes.c_uint32]),
     "edison_eval_default_opts": (None, [ctypes.POINTER(EvalOpts)]),
     "edison_eval_create": (c_int, [c_void_p, ctypes.POINTER(EvalOpts), ctypes.POINTER(c_void_p)]),
     "edison_eval_destroy": (None, [c_void_p]),

@@ -5,7 +5,9 @@
  * network's own device buffer. A gradient call is two launches on the context's stream (fnet_grad_kernels.hip), a step one. The trainer
  * serves the network of one load: after another edison_fnet_load* its calls fail with EDISON_E_NO_MODEL. edison_ftrain_create refuses a
  * network with a conv or pool pad; edison_ftrain_create_ex with EDISON_FTRAIN_PADDED takes it (two ints per row base, the inverse
- * origin table from the padded tables).
+ * origin table from the padded tables). Dropout (edison_ftrain_set_dropout) is a setting of the trainer: per
+ * record a rate and a position in the plan's device copy, a seed and a call counter here; a training call with a non-zero rate runs the
+ * kernel's instantiation with the mask of fnet_dropout.h and advances the counter.
  */
 #include <math.h>
 #include <stdlib.h>
@@ -14,6 +16,7 @@
 #include <vector>
 
 #include "edison_ctx.h"
+#include "fnet_dropout.h"
 #include "fnet_train.h"
 
 #define EDFT_MAX_INV (1 << 24) /* ints of inverse origin tables, all records */
@@ -31,6 +34,11 @@ struct edison_ftrain
 	int kind;
 	double b1, b2, eps;
 	int64_t steps;
+	/* dropout: the rates as set (all zero: off), the positions are the plan's drop_before; the mask of a training call is a function of
+	 * (drop_seed, drop_call) and the counter advances by one per such call */
+	double drop_rate[ED_FNET_MAX_LAYERS];
+	bool drop_on;
+	uint64_t drop_seed, drop_call;
 };
 
 static int ftrain_live(edison_ftrain *t, const char *who)
@@ -104,6 +112,7 @@ extern "C" int edison_ftrain_create_ex(edison_ctx *ctx, uint32_t flags, edison_f
 		delete t;
 		return ed_set_err(ctx, EDISON_E_RUNTIME, "edison_ftrain_create: cannot read the network's tables");
 	}
+	for (int l = 0; l < ED_FNET_MAX_LAYERS; l++) tp.drop_s[l] = 1.0f; /* dropout off: T 0, s 1 */
 	for (int l = 0; l < net->n_layers; l++)
 	{
 		const ed_fnet_layer_t &L = net->L[l];
@@ -151,6 +160,7 @@ extern "C" int edison_ftrain_create_ex(edison_ctx *ctx, uint32_t flags, edison_f
 	if (e == hipSuccess) e = hipMalloc((void **)&tp.acts, sizeof(float) * (size_t)store * (size_t)t->grid);
 	if (e == hipSuccess) e = hipMalloc((void **)&tp.dacts, sizeof(float) * (size_t)store * (size_t)t->grid);
 	if (e == hipSuccess) e = hipMalloc((void **)&tp.mask, (size_t)store * (size_t)t->grid);
+	if (e == hipSuccess) e = hipMalloc((void **)&tp.keys, sizeof(uint32_t) * 2 * (size_t)tp.net.batch * (size_t)tp.net.n_layers * (size_t)t->grid);
 	tp.inv = t->d_inv;
 	if (e == hipSuccess) e = hipMalloc((void **)&t->d_plan, sizeof(tp));
 	if (e == hipSuccess) e = hipMemcpy(t->d_plan, &tp, sizeof(tp), hipMemcpyHostToDevice);
@@ -177,7 +187,7 @@ extern "C" void edison_ftrain_destroy(edison_ftrain *t)
 	if (!t) return;
 	(void)hipSetDevice(t->ctx->device);
 	(void)hipStreamSynchronize(t->ctx->stream); /* a gradient call or a step may still be queued */
-	void *bufs[] = {t->d_plan, t->d_inv, t->plan.slabs, t->plan.acts, t->plan.dacts, t->plan.mask, t->d_grad, t->d_m, t->d_v, t->d_logits, t->d_ignored};
+	void *bufs[] = {t->d_plan, t->d_inv, t->plan.slabs, t->plan.acts, t->plan.dacts, t->plan.mask, t->plan.keys, t->d_grad, t->d_m, t->d_v, t->d_logits, t->d_ignored};
 	for (void *b : bufs)
 		if (b) (void)hipFree(b);
 	delete t;
@@ -217,10 +227,73 @@ extern "C" int edison_ftrain_layout(edison_ftrain *t, int record, int64_t *w_at,
 	return EDISON_OK;
 }
 
+extern "C" int edison_ftrain_set_dropout(edison_ftrain *t, const double *rate, const uint8_t *before_pool, int n_records, uint64_t seed)
+{
+	{ const int r = ftrain_live(t, "edison_ftrain_set_dropout"); if (r != EDISON_OK) return r; }
+	edison_ctx *ctx = t->ctx;
+	const int nl = t->plan.net.n_layers;
+	if (!rate || n_records != nl) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_set_dropout: NULL rates, or n_records is not the network's conv / dense records");
+	bool on = false;
+	for (int l = 0; l < nl; l++)
+	{
+		if (!(rate[l] >= 0.0 && rate[l] < 1.0)) /* NaN fails both */
+		{
+			snprintf(ctx->err, sizeof(ctx->err), "edison_ftrain_set_dropout: record %d's rate is not in [0, 1)", l);
+			return EDISON_E_ARGUMENT;
+		}
+		on = on || rate[l] > 0.0;
+	}
+	if (rate[nl - 1] != 0.0) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_set_dropout: the last record's output is the logits; its rate must be 0");
+	ED_HIP(ctx, hipSetDevice(ctx->device));
+	ED_HIP(ctx, hipStreamSynchronize(ctx->stream)); /* a queued gradient call reads the plan's device copy */
+	ed_ftrain_plan_t &tp = t->plan;
+	for (int l = 0; l < nl; l++)
+	{
+		t->drop_rate[l] = rate[l];
+		tp.drop_T[l] = rate[l] > 0.0 ? edd_threshold(rate[l]) : 0;
+		tp.drop_s[l] = rate[l] > 0.0 ? edd_scale(rate[l]) : 1.0f;
+		tp.drop_before[l] = before_pool && before_pool[l] ? 1 : 0;
+	}
+	t->drop_on = on;
+	t->drop_seed = seed;
+	t->drop_call = 0;
+	ED_HIP(ctx, hipMemcpy(t->d_plan, &tp, sizeof(tp), hipMemcpyHostToDevice));
+	return EDISON_OK;
+}
+
+extern "C" int edison_ftrain_set_dropout_call(edison_ftrain *t, uint64_t call)
+{
+	{ const int r = ftrain_live(t, "edison_ftrain_set_dropout_call"); if (r != EDISON_OK) return r; }
+	if (call >= (1ull << 60)) return ed_set_err(t->ctx, EDISON_E_ARGUMENT, "edison_ftrain_set_dropout_call: the counter is below 2^60");
+	t->drop_call = call;
+	return EDISON_OK;
+}
+
+extern "C" int edison_ftrain_dropout_get(edison_ftrain *t, double *rate, uint8_t *before_pool, uint64_t *seed, uint64_t *call)
+{
+	{ const int r = ftrain_live(t, "edison_ftrain_dropout_get"); if (r != EDISON_OK) return r; }
+	for (int l = 0; l < t->plan.net.n_layers; l++)
+	{
+		if (rate) rate[l] = t->drop_rate[l];
+		if (before_pool) before_pool[l] = t->plan.drop_before[l];
+	}
+	if (seed) *seed = t->drop_seed;
+	if (call) *call = t->drop_call;
+	return EDISON_OK;
+}
+
 extern "C" int edison_ftrain_grad_dev(edison_ftrain *t, const float *in, const int32_t *labels, int64_t n, float *loss, int32_t *argmax)
+{
+	return edison_ftrain_grad_dev_ex(t, in, labels, n, loss, argmax, 0);
+}
+
+extern "C" int edison_ftrain_grad_dev_ex(edison_ftrain *t, const float *in, const int32_t *labels, int64_t n, float *loss, int32_t *argmax, uint32_t flags)
 {
 	{ const int r = ftrain_live(t, "edison_ftrain_grad"); if (r != EDISON_OK) return r; }
 	edison_ctx *ctx = t->ctx;
+	if (flags & ~EDISON_FTRAIN_EVAL) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_grad_ex: flags has a bit other than EDISON_FTRAIN_EVAL");
+	const bool drop = t->drop_on && !(flags & EDISON_FTRAIN_EVAL);
+	if (drop && n > 0xffffffffll) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_grad: a training call with dropout takes fewer than 2^32 rows");
 	if (n < 0 || (n > 0 && (!in || !labels))) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_grad: negative n, or NULL inputs or labels");
 	ED_HIP(ctx, hipSetDevice(ctx->device));
 	t->n_last = n;
@@ -241,14 +314,23 @@ extern "C" int edison_ftrain_grad_dev(edison_ftrain *t, const float *in, const i
 		t->logits_cap = n;
 	}
 	/* the plan's w / tab are the loaded network's device buffers: the epoch check above says they are still those */
-	return ed_launch_result(ctx, ed_launch_ftrain_grad(&t->plan, t->d_plan, in, labels, n, loss, argmax, t->d_logits, t->d_grad, t->d_ignored, t->grid, ctx->stream),
-	                        "gradient kernel");
+	const int r = ed_launch_result(ctx, ed_launch_ftrain_grad(&t->plan, t->d_plan, in, labels, n, loss, argmax, t->d_logits, t->d_grad, t->d_ignored, t->grid,
+	                                                          drop, t->drop_seed, t->drop_call, ctx->stream),
+	                               "gradient kernel");
+	if (r == EDISON_OK && drop) t->drop_call++; /* the next training call draws another mask */
+	return r;
 }
 
 extern "C" int edison_ftrain_grad(edison_ftrain *t, const float *in, const int32_t *labels, int64_t n, float *loss, int32_t *argmax)
 {
+	return edison_ftrain_grad_ex(t, in, labels, n, loss, argmax, 0);
+}
+
+extern "C" int edison_ftrain_grad_ex(edison_ftrain *t, const float *in, const int32_t *labels, int64_t n, float *loss, int32_t *argmax, uint32_t flags)
+{
 	{ const int r = ftrain_live(t, "edison_ftrain_grad"); if (r != EDISON_OK) return r; }
 	edison_ctx *ctx = t->ctx;
+	if (flags & ~EDISON_FTRAIN_EVAL) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_grad_ex: flags has a bit other than EDISON_FTRAIN_EVAL");
 	if (n < 0 || (n > 0 && (!in || !labels))) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_grad: negative n, or NULL inputs or labels");
 	for (int64_t i = 0; i < n; i++)
 		if (labels[i] < 0 || labels[i] >= t->plan.net.n_out)
@@ -256,13 +338,13 @@ extern "C" int edison_ftrain_grad(edison_ftrain *t, const float *in, const int32
 			snprintf(ctx->err, sizeof(ctx->err), "edison_ftrain_grad: label %d of row %lld is outside 0 .. %d", labels[i], (long long)i, t->plan.net.n_out - 1);
 			return EDISON_E_ARGUMENT;
 		}
-	if (n == 0) return edison_ftrain_grad_dev(t, NULL, NULL, 0, NULL, NULL);
+	if (n == 0) return edison_ftrain_grad_dev_ex(t, NULL, NULL, 0, NULL, NULL, flags);
 	ed_staging st(ctx);
 	const float *x = st.in(in, (size_t)n * (size_t)t->plan.net.in_n);
 	const int32_t *y = st.in(labels, (size_t)n);
 	float *l = st.out(loss, (size_t)n);
 	int32_t *a = st.out(argmax, (size_t)n);
-	return st.finish(st.ok() ? edison_ftrain_grad_dev(t, x, y, n, l, a) : EDISON_OK);
+	return st.finish(st.ok() ? edison_ftrain_grad_dev_ex(t, x, y, n, l, a, flags) : EDISON_OK);
 }
 
 /* synchronising copies between the host and one of the trainer's device arrays */
@@ -336,5 +418,6 @@ extern "C" int edison_ftrain_reset(edison_ftrain *t)
 	ED_HIP(ctx, hipMemsetAsync(t->d_v, 0, sizeof(float) * (size_t)t->plan.w_floats, ctx->stream));
 	ED_HIP(ctx, hipMemsetAsync(t->d_ignored, 0, sizeof(unsigned long long), ctx->stream));
 	t->steps = 0;
+	t->drop_call = 0;
 	return EDISON_OK;
 }

@@ -1,8 +1,10 @@
 /*
  * fnet_grad_kernels.hip -- training the loaded float32 network (edison_ftrain.hip, edison_amd/train.py): the
- * gradient of the batch-mean cross entropy with respect to every weight and bias, and the optimiser step. ed_ftrain_grad_kernel<false>
- * is the kernel of a plan without padded records; <true> also holds the padded path of the forward tile and of
- * the dW gather, taken by the records that have pad; dX reads the inverse origin table only and is the same for both.
+ * gradient of the batch-mean cross entropy with respect to every weight and bias, and the optimiser step. ed_ftrain_grad_kernel<PADS, DROP>:
+ * PADS = false is the kernel of a plan without padded records; true also holds the padded path of the forward tile
+ * and of the dW gather, taken by the records that have pad; dX reads the inverse origin table only and is the same for both. DROP = true
+ * is a training call on a trainer with dropout: the mask of fnet_dropout.h in the forward epilogue and again
+ * where dY is built; every other call runs DROP = false, whose instructions are those of the kernel before dropout existed.
  *
  * ed_ftrain_grad_kernel. A fixed grid of workgroups; workgroup g takes the tiles of utterances g, g + grid, g + 2 grid, ... in that
  * order, each through a forward half and a backward half, and adds what the tile gives into its own gradient slab (the first tile
@@ -33,16 +35,46 @@
 #include "edison_launch.h"
 #include "fnet.h"
 #include "fnet_device.h"
+#include "fnet_dropout.h"
 #include "fnet_train.h"
 
 /* edf_tile (fnet_device.h) with the training epilogue: the MFMA loop and the order bias, ReLU, pool are edf_tile's; every pooled output
  * also goes to acts (this workgroup's store, utterance-major) with its mask byte. PAD = true takes edf_tile<NT, true>'s three
  * differences: edf_pad_row, edf_pad_tap on the kyx behind koff, and edf_pad_live, an absent row being -inf before the window's max. */
-template <int NT, bool PAD>
+/* What the training epilogue stores beside dst: the workgroup's activation store and mask bytes; with DROP (a training call on a trainer
+ * with dropout) also the record's threshold T, scale s and position, and its keys of the tile's utterances:
+ * utterance u's (kA, kB) at keys[2 u key_n]. */
+template <bool DROP>
+struct edg_stores;
+template <>
+struct edg_stores<false>
+{
+	float *__restrict__ acts;
+	uint8_t *__restrict__ mask;
+	int acts_n;
+};
+template <>
+struct edg_stores<true>
+{
+	float *__restrict__ acts;
+	uint8_t *__restrict__ mask;
+	int acts_n;
+	const uint32_t *__restrict__ keys;
+	int key_n;
+	uint32_t T;
+	float s;
+	bool before;
+};
+
+/* DROP: the mask of fnet_dropout.h in the epilogue. Before the pool (and P > 1) every present element after bias and ReLU becomes
+ * keep ? v s : +0.0f, then the max and the first-maximum chain run as without; after the pool, or P = 1, the pooled x does. The stored
+ * value is the dropped one; EDFT_DROPPED in the mask byte says the window's winner, or the pooled output, was dropped. T = 0 (rate 0)
+ * skips the hash. */
+template <int NT, bool PAD, bool DROP>
 __device__ __forceinline__ void edg_tile(const ed_fnet_layer_t &L, const float *__restrict__ src, int src_n, float *__restrict__ dst, int dst_n,
                                          const float *__restrict__ wl, const int32_t *__restrict__ kl, const int32_t *__restrict__ rowin,
                                          const float *__restrict__ bias, int M, int mt, int n0, int lane, float *__restrict__ acts,
-                                         uint8_t *__restrict__ mask, int acts_n)
+                                         uint8_t *__restrict__ mask, int acts_n, [[maybe_unused]] const edg_stores<DROP> &st)
 {
 	const int r = lane & 15, kq = lane >> 4;
 	const int m = mt * 16 + r;
@@ -88,13 +120,45 @@ __device__ __forceinline__ void edg_tile(const ed_fnet_layer_t &L, const float *
 			if (L.relu) v[i] = fmaxf(v[i], 0.0f);
 			if constexpr (PAD) { if (!live[i]) v[i] = -INFINITY; } /* absent: the max's identity; its window has a real element */
 		}
+		[[maybe_unused]] bool kept[4] = {true, true, true, true};
+		if constexpr (DROP)
+		{
+			if (st.T != 0 && st.before && P > 1)
+			{
+#pragma unroll
+				for (int i = 0; i < 4; i++)
+				{
+					const int mi = m0 + i;
+					bool real = mi < M;
+					if constexpr (PAD) real = live[i];
+					if (!real) continue; /* absent stays -inf; a row beyond M is not emitted */
+					const int u = mi / L.rows, row = mi - u * L.rows;
+					const uint32_t *k = st.keys + 2 * u * st.key_n;
+					kept[i] = edd_hash((uint32_t)(row * L.out_c + n), k[0], k[1]) >= st.T;
+					v[i] = kept[i] ? v[i] * st.s : 0.0f;
+				}
+			}
+		}
 		/* one pooled output: the window's maximum x at rows mg .., its first maximum e in element order; under ReLU a maximum of 0 is a
 		 * pre-activation <= 0 and passes nothing. A padded record's absent elements are -inf and x is a present element's finite value
 		 * (a pad is smaller than its window), so the v[g] == x chains below pick the first maximum among the present elements. */
-		auto emit = [&](int mg, float x, int e) {
+		auto emit = [&](int mg, float x, int e, [[maybe_unused]] bool winner_kept) {
 			if (mg >= M) return;
-			const int pass = !L.relu || x > 0.0f ? EDFT_PASS : 0;
+			int pass = !L.relu || x > 0.0f ? EDFT_PASS : 0;
 			const int u = mg / L.rows, q = (mg - u * L.rows) / P;
+			if constexpr (DROP)
+			{
+				if (st.T != 0)
+				{
+					if (!st.before || P == 1)
+					{
+						const uint32_t *k = st.keys + 2 * u * st.key_n;
+						winner_kept = edd_hash((uint32_t)(q * L.out_c + n), k[0], k[1]) >= st.T;
+						x = winner_kept ? x * st.s : 0.0f;
+					}
+					if (!winner_kept) pass |= EDFT_DROPPED;
+				}
+			}
 			dst[u * dst_n + q * L.out_c + n] = x;
 			const int o = u * acts_n + L.acts_at + q * L.out_c + n;
 			acts[o] = x;
@@ -103,7 +167,7 @@ __device__ __forceinline__ void edg_tile(const ed_fnet_layer_t &L, const float *
 		if (P == 1)
 		{
 #pragma unroll
-			for (int i = 0; i < 4; i++) emit(m0 + i, v[i], 0);
+			for (int i = 0; i < 4; i++) emit(m0 + i, v[i], 0, true);
 		}
 		else if (P == 2)
 		{
@@ -111,34 +175,29 @@ __device__ __forceinline__ void edg_tile(const ed_fnet_layer_t &L, const float *
 			for (int g = 0; g < 4; g += 2)
 			{
 				const float x = fmaxf(v[g], v[g + 1]);
-				emit(m0 + g, x, v[g] == x ? 0 : 1);
+				const int e = v[g] == x ? 0 : 1;
+				emit(m0 + g, x, e, e ? kept[g + 1] : kept[g]);
 			}
 		}
 		else
 		{
 			const float x = fmaxf(fmaxf(fmaxf(v[0], v[1]), v[2]), v[3]);
-			emit(m0, x, v[0] == x ? 0 : v[1] == x ? 1 : v[2] == x ? 2 : 3);
+			const int e = v[0] == x ? 0 : v[1] == x ? 1 : v[2] == x ? 2 : 3;
+			emit(m0, x, e, e == 0 ? kept[0] : e == 1 ? kept[1] : e == 2 ? kept[2] : kept[3]);
 		}
 	}
 }
 
 /* The walk's work item for training (EDF_LAYER_WALK of fnet_device.h): edg_tile by the item's nt <= 4 channel tiles. */
-struct edg_stores
-{
-	float *__restrict__ acts;
-	uint8_t *__restrict__ mask;
-	int acts_n;
-};
-
-template <bool PAD>
+template <bool PAD, bool DROP>
 __device__ __forceinline__ void edg_item(int nt, const ed_fnet_layer_t &L, const float *__restrict__ src, int src_n, float *__restrict__ dst, int dst_n,
                                          const float *__restrict__ wl, const int32_t *__restrict__ kl, const int32_t *__restrict__ rowin,
-                                         const float *__restrict__ bias, int M, int mt, int n0, int lane, float *, int64_t, int64_t, const edg_stores &st)
+                                         const float *__restrict__ bias, int M, int mt, int n0, int lane, float *, int64_t, int64_t, const edg_stores<DROP> &st)
 {
-	if (nt == 4) edg_tile<4, PAD>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
-	else if (nt == 3) edg_tile<3, PAD>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
-	else if (nt == 2) edg_tile<2, PAD>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
-	else edg_tile<1, PAD>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n);
+	if (nt == 4) edg_tile<4, PAD, DROP>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n, st);
+	else if (nt == 3) edg_tile<3, PAD, DROP>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n, st);
+	else if (nt == 2) edg_tile<2, PAD, DROP>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n, st);
+	else edg_tile<1, PAD, DROP>(L, src, src_n, dst, dst_n, wl, kl, rowin, bias, M, mt, n0, lane, st.acts, st.mask, st.acts_n, st);
 }
 
 /* dW of 16 k rows (k tile kt; kt == KT is the bias row: A = 1 in row 0) x NT tiles of 16 channels from n0, summed over the tile's M rows
@@ -258,11 +317,12 @@ __device__ __forceinline__ void edg_dx_tile(const ed_fnet_layer_t &L, const ed_f
 	}
 }
 
-template <bool PADS>
+/* DROP: a training call on a trainer with dropout. seed and call are read by that instantiation only. */
+template <bool PADS, bool DROP>
 __global__ __launch_bounds__(ED_FNET_THREADS) void ed_ftrain_grad_kernel(const ed_ftrain_plan_t *tp, const float *__restrict__ in,
                                                                            const int32_t *__restrict__ labels, int64_t n, float *__restrict__ loss,
                                                                            int32_t *__restrict__ argmax, float *__restrict__ logits,
-                                                                           unsigned long long *__restrict__ ignored)
+                                                                           unsigned long long *__restrict__ ignored, uint64_t seed, uint64_t call)
 {
 	const ed_ftrain_plan_t &t = *tp; /* in device memory, read where it is used: by value its fields stay live in SGPRs and spill */
 	const ed_fnet_plan_t &p = t.net;
@@ -275,6 +335,8 @@ __global__ __launch_bounds__(ED_FNET_THREADS) void ed_ftrain_grad_kernel(const e
 	float *acts = t.acts + (int64_t)blockIdx.x * B * acts_n;
 	float *dacts = t.dacts + (int64_t)blockIdx.x * B * acts_n;
 	uint8_t *mask = t.mask + (int64_t)blockIdx.x * B * acts_n;
+	[[maybe_unused]] uint32_t *keys = NULL;
+	if constexpr (DROP) keys = t.keys + (int64_t)blockIdx.x * B * p.n_layers * 2;
 	const int64_t n_tiles = (n + B - 1) / B;
 	bool first = true;
 
@@ -290,9 +352,28 @@ __global__ __launch_bounds__(ED_FNET_THREADS) void ed_ftrain_grad_kernel(const e
 			buf[0][u * p.buf_n[0] + e] = x0[i];
 		}
 
+		/* the dropout keys of (utterance of the tile, record): Philox once each, read by every element's hash after the walk's first sync */
+		if constexpr (DROP)
+			for (int i = tid; i < nu * p.n_layers; i += ED_FNET_THREADS)
+			{
+				const int u = i / p.n_layers;
+				edd_keys(seed, call, (uint32_t)(u0 + u), (uint32_t)(i - u * p.n_layers), keys + 2 * i, keys + 2 * i + 1);
+			}
+
 		/* ---- forward: the network's own walk over edg_tile (PADS = false: the launcher starts it for plans without padded records) ---- */
-		const edg_stores stores = {acts, mask, acts_n};
-		for (int l = 0; l < p.n_layers; l++) EDF_LAYER_WALK(PADS, edg_item, p.L[l], (float *)NULL, 0, 0, stores)
+		if constexpr (DROP)
+		{
+			for (int l = 0; l < p.n_layers; l++)
+			{
+				const edg_stores<true> stores = {acts, mask, acts_n, keys + 2 * l, p.n_layers, t.drop_T[l], t.drop_s[l], t.drop_before[l] != 0};
+				EDF_LAYER_WALK(PADS, edg_item, p.L[l], (float *)NULL, 0, 0, stores)
+			}
+		}
+		else
+		{
+			const edg_stores<false> stores = {acts, mask, acts_n};
+			for (int l = 0; l < p.n_layers; l++) EDF_LAYER_WALK(PADS, edg_item, p.L[l], (float *)NULL, 0, 0, stores)
+		}
 		__syncthreads();
 
 		/* ---- loss and dL/dz, one thread per utterance (the softmax and the argmax are ed_fnet_kernel's) ---- */
@@ -320,6 +401,8 @@ __global__ __launch_bounds__(ED_FNET_THREADS) void ed_ftrain_grad_kernel(const e
 			const int src_n = l ? acts_n : p.in_n;
 			const float *src = l ? acts + p.L[l - 1].acts_at : x0;
 			const int32_t *rowin = p.tab + L.rowin_at;
+			[[maybe_unused]] float ds = 1.0f;
+			if constexpr (DROP) ds = t.drop_s[l];
 			__syncthreads(); /* dz, or the next record's dX, is written; its dY no longer read */
 			for (int i = tid; i < Mp * L.n_pad; i += ED_FNET_THREADS)
 			{
@@ -330,7 +413,11 @@ __global__ __launch_bounds__(ED_FNET_THREADS) void ed_ftrain_grad_kernel(const e
 					const int u = m / L.rows, r = m - u * L.rows, q = r / L.P, e = r - q * L.P;
 					const int o = u * acts_n + L.acts_at + q * L.out_c + c;
 					const int mk = mask[o];
-					if ((mk & EDFT_PASS) && (mk & EDFT_WIN_MASK) == e) v = dacts[o];
+					if constexpr (DROP)
+					{
+						if ((mk & (EDFT_PASS | EDFT_DROPPED)) == EDFT_PASS && (mk & EDFT_WIN_MASK) == e) v = dacts[o] * ds;
+					}
+					else if ((mk & EDFT_PASS) && (mk & EDFT_WIN_MASK) == e) v = dacts[o];
 				}
 				dy[i] = v;
 			}
@@ -414,7 +501,7 @@ __global__ __launch_bounds__(256) void ed_ftrain_step_kernel(int kind, float *__
 }
 
 extern "C" int ed_launch_ftrain_grad(const ed_ftrain_plan_t *t, const ed_ftrain_plan_t *d_plan, const float *in, const int32_t *labels, int64_t n, float *loss, int32_t *argmax,
-                                     float *logits, float *grad, unsigned long long *ignored, int grid, hipStream_t stream)
+                                     float *logits, float *grad, unsigned long long *ignored, int grid, int drop, uint64_t seed, uint64_t call, hipStream_t stream)
 {
 	if (n <= 0) return 0;
 	const ed_fnet_plan_t *p = &t->net;
@@ -422,11 +509,14 @@ extern "C" int ed_launch_ftrain_grad(const ed_ftrain_plan_t *t, const ed_ftrain_
 	if (!ed_fnet_plan_launchable(p, lds) || grid < 1) return (int)hipErrorInvalidValue;
 	bool pads = false; /* a plan with a padded record runs the instantiation that holds the padded path, any other plan the one without */
 	for (int l = 0; l < p->n_layers; l++) pads = pads || p->L[l].pad;
-	const auto kernel = pads ? ed_ftrain_grad_kernel<true> : ed_ftrain_grad_kernel<false>;
+	/* drop: a training call with a non-zero rate; every other call runs the instantiations without the mask */
+	if (drop && (n > 0xffffffffll || !t->keys)) return (int)hipErrorInvalidValue;
+	const auto kernel = drop ? (pads ? ed_ftrain_grad_kernel<true, true> : ed_ftrain_grad_kernel<false, true>)
+	                         : (pads ? ed_ftrain_grad_kernel<true, false> : ed_ftrain_grad_kernel<false, false>);
 	{ const int e = ed_kernel_prepare((const void *)kernel, ED_FNET_THREADS, lds, NULL, NULL); if (e) return e; }
 	const int64_t n_tiles = (n + p->batch - 1) / p->batch;
 	const int used = (int)(n_tiles < grid ? n_tiles : grid); /* a workgroup without a tile would leave its slab stale */
-	hipLaunchKernelGGL(kernel, dim3((unsigned)used), dim3(ED_FNET_THREADS), lds, stream, d_plan, in, labels, n, loss, argmax, logits, ignored);
+	hipLaunchKernelGGL(kernel, dim3((unsigned)used), dim3(ED_FNET_THREADS), lds, stream, d_plan, in, labels, n, loss, argmax, logits, ignored, seed, call);
 	{ const int e = (int)hipGetLastError(); if (e) return e; }
 	hipLaunchKernelGGL(ed_ftrain_reduce_kernel, dim3((unsigned)((t->w_floats + 255) / 256)), dim3(256), 0, stream, t->slabs, used, t->w_floats, grad);
 	return (int)hipGetLastError();

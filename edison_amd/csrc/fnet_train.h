@@ -12,6 +12,7 @@
 
 #define EDFT_WIN_MASK 3 /* a mask byte: the pool window's first maximum, element e = r % P ... */
 #define EDFT_PASS 4     /* ... and whether its gradient passes: no ReLU, or a pre-activation > 0 */
+#define EDFT_DROPPED 8  /* ... unless the winner, or the pooled output, was dropped (dropout): it passes nothing */
 #define EDFT_SGD 1      /* edison_ftrain_set_opt's kind; 0 is Adam */
 
 /* What the backward half needs of record l beside ed_fnet_layer_t. inv is the inverse of the record's gather, row-at-offset: the input
@@ -35,6 +36,12 @@ typedef struct {
 	 * (both [acts_n] floats) and the mask bytes [acts_n] */
 	float *slabs, *acts, *dacts;
 	uint8_t *mask;
+	/* dropout (fnet_dropout.h), behind everything else so that no other field moves: per record the threshold (0: rate 0, no hash), the
+	 * scale 1 / (1 - rate) and whether the mask stands before the pool; per workgroup the keys [batch][n_layers][2] of its tile */
+	uint32_t drop_T[ED_FNET_MAX_LAYERS];
+	float drop_s[ED_FNET_MAX_LAYERS];
+	uint8_t drop_before[ED_FNET_MAX_LAYERS];
+	uint32_t *keys;
 } ed_ftrain_plan_t;
 
 /* Dynamic LDS bytes of the training workgroup: the forward half's plan, and over it (the forward half is done with it) dY and the row
@@ -47,9 +54,10 @@ static inline size_t ed_ftrain_lds_bytes(const ed_ftrain_plan_t *t)
 
 /* n inputs and labels -> loss [n], argmax [n] (NULL: not written), logits [n][n_out], and the batch-mean gradient of the cross entropy in
  * grad [w_floats]: `grid` workgroups (at most the plan's slabs) walk the batches, then the slabs of those that had one are summed in
- * index order. d_plan: *t in device memory, which the kernel reads. A label outside [0, n_out) bumps *ignored and contributes nothing. Returns a hipError_t. */
+ * index order. d_plan: *t in device memory, which the kernel reads. A label outside [0, n_out) bumps *ignored and contributes nothing.
+ * drop != 0: the instantiation with the dropout mask of (seed, call), n < 2^32. Returns a hipError_t. */
 extern "C" int ed_launch_ftrain_grad(const ed_ftrain_plan_t *t, const ed_ftrain_plan_t *d_plan, const float *in, const int32_t *labels, int64_t n, float *loss, int32_t *argmax,
-                                     float *logits, float *grad, unsigned long long *ignored, int grid, hipStream_t stream);
+                                     float *logits, float *grad, unsigned long long *ignored, int grid, int drop, uint64_t seed, uint64_t call, hipStream_t stream);
 /* One optimiser step over w [count], in place. Adam: m, v and `factor` = lr sqrt(1 - b2^t) / (1 - b1^t); SGD: w -= factor g. */
 extern "C" int ed_launch_ftrain_step(int kind, float *w, const float *g, float *m, float *v, int64_t count, float factor, float b1, float omb1, float b2,
                                      float omb2, float eps, int n_cu, hipStream_t stream);

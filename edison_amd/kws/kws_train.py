@@ -7,6 +7,10 @@ the float path runs, 'same' convs and pools included. The network file gives the
     y.npy           integer class indices [n]
     --epochs N      (30)      --batch N   (100)      --lr r   (0.0005, Adam)      --seed s   (0: the shuffle)
     --val x.npy y.npy         a validation set: its loss drives ReduceLROnPlateau(0.5, patience 1) and EarlyStopping(patience 10)
+    --dropout r0,r1,..        a Dropout rate behind each conv / dense record's output (the last is 0), e.g. 0,0,0.2,0.3,0
+    --dropout-before-pool b0,b1,..   1: that record's Dropout stands between ReLU and the pool, 0 (default): behind the pool
+    --dropout-arch NAME       the reference's placement for one of its architectures (train.KERAS_DROPOUT), e.g. kws_conv
+The masks are seeded by --seed; validation runs without dropout.
 
 Prints the history per epoch and writes the trained network, which ``kws quantize`` takes.
 """
@@ -14,18 +18,27 @@ import sys
 
 import numpy as np
 
-USAGE = "usage: kws train <net.ednf> <x.npy> <y.npy> <out.ednf> [--epochs N] [--batch N] [--lr r] [--seed s] [--val <x.npy> <y.npy>]"
+USAGE = "usage: kws train <net.ednf> <x.npy> <y.npy> <out.ednf> [--epochs N] [--batch N] [--lr r] [--seed s] [--val <x.npy> <y.npy>] [--dropout r,..] [--dropout-before-pool b,..] [--dropout-arch NAME]"
 
 
-def run(net, x_path, y_path, out_path, epochs=30, batch=100, lr=None, seed=0, val=None, ctx=None, out=None):
+def run(net, x_path, y_path, out_path, epochs=30, batch=100, lr=None, seed=0, val=None, ctx=None, out=None, dropout=None, before_pool=None,
+        dropout_arch=None):
     from .. import train
     from ..context import default_context
     out = out or sys.stdout
     ctx = ctx or default_context()
     x, y = np.load(x_path), np.load(y_path)
     v = (np.load(val[0]), np.load(val[1])) if val else None
+    if dropout_arch is not None:
+        if dropout is not None or dropout_arch not in train.KERAS_DROPOUT:
+            raise ValueError("--dropout-arch is one of %s, and not given beside --dropout" % ", ".join(sorted(train.KERAS_DROPOUT)))
+        dropout = train.KERAS_DROPOUT[dropout_arch]
+    if dropout is None and before_pool is not None:
+        raise ValueError("--dropout-before-pool needs --dropout")
     ctx.fnet_load(net)
     with ctx.trainer(padded=True) as tr:
+        if dropout is not None:
+            tr.set_dropout(dropout, before_pool, seed=seed)
         hist = tr.fit(x, y, epochs, batch_size=batch, val=v, seed=seed, lr=train.LEARNING_RATE if lr is None else lr)
         blob = tr.export()
     for i, (l, a) in enumerate(zip(hist["loss"], hist["acc"])):
@@ -42,7 +55,7 @@ def run(net, x_path, y_path, out_path, epochs=30, batch=100, lr=None, seed=0, va
 
 
 def main(argv):
-    opts = {"--epochs": "30", "--batch": "100", "--lr": None, "--seed": "0"}
+    opts = {"--epochs": "30", "--batch": "100", "--lr": None, "--seed": "0", "--dropout": None, "--dropout-before-pool": None, "--dropout-arch": None}
     rest, val = [], None
     i = 1
     while i < len(argv):
@@ -67,12 +80,15 @@ def main(argv):
     try:
         epochs, batch, seed = int(opts["--epochs"]), int(opts["--batch"]), int(opts["--seed"])
         lr = None if opts["--lr"] is None else float(opts["--lr"])
+        dropout = None if opts["--dropout"] is None else [float(v) for v in opts["--dropout"].split(",")]
+        before = None if opts["--dropout-before-pool"] is None else [int(v) for v in opts["--dropout-before-pool"].split(",")]
     except ValueError:
         print(USAGE)
         return 1
     from .._lib import EdisonError
     try:
-        run(rest[0], rest[1], rest[2], rest[3], epochs=epochs, batch=batch, lr=lr, seed=seed, val=val)
+        run(rest[0], rest[1], rest[2], rest[3], epochs=epochs, batch=batch, lr=lr, seed=seed, val=val, dropout=dropout, before_pool=before,
+            dropout_arch=opts["--dropout-arch"])
     except (EdisonError, ValueError) as e:
         print("kws train: %s" % e)
         return 1

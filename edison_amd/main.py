@@ -47,7 +47,8 @@ USAGE = """usage: edison <module> <command> [<args>]
   kws  quantize <net.ednf> <audio.npy> <out.ednn> [--weights-h <out.h>] [--saturate <share>] [--geometry k=v,...] [--chunk N]
                                          quantise a float32 network to an int8 NNoM graph, calibrated on the GPU over the audio
   kws  train <net.ednf> <x.npy> <y.npy> <out.ednf> [--epochs N] [--batch N] [--lr r] [--seed s] [--val <x.npy> <y.npy>]
-                                         train a float32 network (no pads) on features and class indices: Adam on the GPU
+             [--dropout r,.. [--dropout-before-pool b,..] | --dropout-arch NAME]
+                                         train a float32 network on features and class indices: Adam on the GPU, Dropout if asked
 """
 
 

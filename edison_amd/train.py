@@ -18,8 +18,36 @@ from . import _lib, cube_import
 
 ADAM, SGD = 0, 1          # EDISON_FTRAIN_ADAM, EDISON_FTRAIN_SGD
 FTRAIN_PADDED = 1         # EDISON_FTRAIN_PADDED: edison_ftrain_create_ex's flag
+FTRAIN_EVAL = 1           # EDISON_FTRAIN_EVAL: edison_ftrain_grad_ex's flag
 LEARNING_RATE = 0.0005    # kws_keras.py:53 initial_learningrate
 BATCH_SIZE = 100          # kws_keras.py: batchSize
+
+
+# Where the reference's architectures put Dropout (kws_keras.py:194-393), per conv / dense record: 0, a rate (behind the record's output)
+# or (rate, before_pool); before_pool = 1 is Conv(relu) -> Dropout -> MaxPool. The last record gives the logits: never a rate.
+KERAS_DROPOUT = {
+    "tiny_conv": [(0.25, 0), 0],
+    "medium_embedding_conv": [(0.25, 1), (0.25, 0), 0],
+    "tiny_embedding_conv": [(0.25, 1), (0.25, 0), 0],
+    "conv_model": [(0.25, 1), (0.25, 0), 0],
+    "low_latency_conv": [0.25, 0, 0.25, 0],
+    "simple_conv": [(0.25, 0), 0],           # after the pool
+    "kws_conv": [0, 0, 0.2, 0.3, 0],
+    "single_fc": [0],
+}
+
+
+def dropout_spec(spec, before_pool=None):
+    """A list of rates or (rate, before_pool) per record, and optionally the positions apart -> (rates [float], before [0 / 1])."""
+    rates, before = [], []
+    spec = list(spec)
+    if before_pool is not None and len(before_pool) != len(spec):
+        raise ValueError("%d rates, %d positions" % (len(spec), len(before_pool)))
+    for i, s in enumerate(spec):
+        r, b = s if isinstance(s, (tuple, list)) else (s, 0)
+        rates.append(float(r))
+        before.append(int(bool(b if before_pool is None else before_pool[i])))
+    return rates, before
 
 
 def _np_ptr(a):
@@ -133,6 +161,9 @@ def fit(trainer, x, y, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=LEARN
         vx, vy = np.asarray(val[0]), np.asarray(val[1]).astype(np.int32).reshape(-1)
         vx = vx.reshape(vx.shape[0], -1)
     plateau, stopper = ReduceLROnPlateau(), EarlyStopping()
+    # validation runs with dropout off: the keyword goes only to a trainer that reports dropout on, so anything without it keeps working
+    state = trainer.dropout() if hasattr(trainer, "dropout") else None
+    ev = dict(training=False) if state and state.get("on") else {}
     hist = dict(loss=[], acc=[], val_loss=[], val_acc=[], lr=[], steps=0, stopped_early=False)
     for epoch in range(int(epochs)):
         order = epoch_order(n, seed, epoch)
@@ -141,7 +172,7 @@ def fit(trainer, x, y, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=LEARN
             if max_steps is not None and hist["steps"] >= max_steps:
                 break
             rows = order[b0:b0 + bs]
-            r = trainer.grad(x[rows], y[rows])
+            r = trainer.grad(x[rows], y[rows])               # a training call: with dropout set, its mask and the counter's advance
             trainer.step(lr)
             hist["steps"] += 1
             loss_sum += float(np.sum(r["loss"], dtype=np.float64))
@@ -155,7 +186,7 @@ def fit(trainer, x, y, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=LEARN
         if val is not None:
             vl, vh = 0.0, 0
             for b0 in range(0, vx.shape[0], 4096):
-                r = trainer.grad(vx[b0:b0 + 4096], vy[b0:b0 + 4096])   # the gradient it leaves is not stepped
+                r = trainer.grad(vx[b0:b0 + 4096], vy[b0:b0 + 4096], **ev)   # the gradient it leaves is not stepped
                 vl += float(np.sum(r["loss"], dtype=np.float64))
                 vh += int((r["argmax"] == vy[b0:b0 + 4096]).sum())
             hist["val_loss"].append(vl / max(vx.shape[0], 1))
@@ -173,9 +204,10 @@ def fit(trainer, x, y, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=LEARN
 # ---- the GPU trainer --------------------------------------------------------------------------------------------------------------
 class Trainer:
     """edison_ftrain on `ctx`, bound to the float network loaded now; loading another one invalidates it (EdisonError).
-    padded=True (EDISON_FTRAIN_PADDED) also takes networks with conv or pool pads; without it they are refused."""
+    padded=True (EDISON_FTRAIN_PADDED) also takes networks with conv or pool pads; without it they are refused.
+    dropout: set_dropout's rates (None: off), with `seed`."""
 
-    def __init__(self, ctx, padded=False):
+    def __init__(self, ctx, padded=False, dropout=None, seed=0):
         self._ctx, self._L = ctx, ctx._L
         if ctx._fnet_blob is None:
             raise ValueError("no float network loaded (fnet_load)")
@@ -190,6 +222,8 @@ class Trainer:
             got = self.record_layout(i)
             if any(got[k] != r[k] for k in ("w_at", "K", "k_pad", "out_c", "n_pad")) or n != self.w_floats:
                 raise RuntimeError("record %d: edison_ftrain_layout %s, the blob's %s" % (i, got, r))
+        if dropout is not None:
+            self.set_dropout(dropout, seed=seed)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -223,25 +257,57 @@ class Trainer:
         self._ctx._check(self._L.edison_ftrain_layout(self._h, int(record), ctypes.byref(w_at), *[ctypes.byref(a) for a in v]))
         return dict(w_at=w_at.value, K=v[0].value, k_pad=v[1].value, out_c=v[2].value, n_pad=v[3].value)
 
+    # -- dropout
+    def set_dropout(self, rates, before_pool=None, seed=0):
+        """edison_ftrain_set_dropout: per conv / dense record a rate in [0, 1) behind its output, or (rate, before_pool) (KERAS_DROPOUT's
+        form); before_pool [n_layers] gives the positions apart (1: between ReLU and the pool). The last record's rate is 0. All rates
+        0 turns dropout off. Sets the call counter to 0."""
+        r, b = dropout_spec(rates, before_pool)
+        ra, ba = np.asarray(r, np.float64), np.asarray(b, np.uint8)
+        self._ctx._check(self._L.edison_ftrain_set_dropout(self._h, _np_ptr(ra), _np_ptr(ba), len(r), int(seed) & (2 ** 64 - 1)))
+
+    def dropout(self):
+        """edison_ftrain_dropout_get: dict(rates, before_pool, seed, call, on)."""
+        ra, ba = np.zeros(self.n_layers, np.float64), np.zeros(self.n_layers, np.uint8)
+        seed, call = ctypes.c_uint64(), ctypes.c_uint64()
+        self._ctx._check(self._L.edison_ftrain_dropout_get(self._h, _np_ptr(ra), _np_ptr(ba), ctypes.byref(seed), ctypes.byref(call)))
+        return dict(rates=[float(v) for v in ra], before_pool=[int(v) for v in ba], seed=seed.value, call=call.value, on=bool((ra > 0).any()))
+
+    @property
+    def dropout_call(self):
+        """The call counter: the mask of the next training call is a function of (seed, this); a training call advances it by one."""
+        return self.dropout()["call"]
+
+    @dropout_call.setter
+    def dropout_call(self, call):
+        self._ctx._check(self._L.edison_ftrain_set_dropout_call(self._h, int(call)))
+
     # -- the gradient
-    def grad(self, x, y):
+    def grad(self, x, y, training=True):
         """Host inputs [n][in_n] float32 and labels [n] (class indices; one outside [0, n_out) is an EdisonError) -> dict(loss [n],
-        argmax [n]). The gradient stays on the device: gradient() / gradients() fetch it, step() applies it."""
+        argmax [n]). The gradient stays on the device: gradient() / gradients() fetch it, step() applies it. With dropout set a call
+        applies the current counter's mask and advances the counter; training=False (EDISON_FTRAIN_EVAL) does neither."""
         f = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, self.in_n)
         lab = np.ascontiguousarray(y, dtype=np.int32).reshape(-1)
         if lab.shape[0] != f.shape[0]:
             raise ValueError("%d inputs, %d labels" % (f.shape[0], lab.shape[0]))
         loss = np.zeros(f.shape[0], np.float32)
         am = np.zeros(f.shape[0], np.int32)
-        self._ctx._check(self._L.edison_ftrain_grad(self._h, _np_ptr(f), _np_ptr(lab), f.shape[0], _np_ptr(loss), _np_ptr(am)))
+        if training:
+            self._ctx._check(self._L.edison_ftrain_grad(self._h, _np_ptr(f), _np_ptr(lab), f.shape[0], _np_ptr(loss), _np_ptr(am)))
+        else:
+            self._ctx._check(self._L.edison_ftrain_grad_ex(self._h, _np_ptr(f), _np_ptr(lab), f.shape[0], _np_ptr(loss), _np_ptr(am), FTRAIN_EVAL))
         return dict(loss=loss, argmax=am)
 
-    def grad_t(self, x, y, n=None, loss=None, argmax=None):
+    def grad_t(self, x, y, n=None, loss=None, argmax=None, training=True):
         """edison_ftrain_grad_dev on torch device tensors (x float32 [n][in_n], y int32 [n], contiguous; loss float32 [n] and argmax
         int32 [n] optional), enqueued on the context's stream behind whatever produced them. A label outside [0, n_out) contributes
-        nothing and is counted in info()["ignored"]."""
+        nothing and is counted in info()["ignored"]. training: as grad's."""
         n = int(x.shape[0] if n is None else n)
-        self._ctx._check(self._L.edison_ftrain_grad_dev(self._h, _t_ptr(x), _t_ptr(y), n, _t_ptr(loss), _t_ptr(argmax)))
+        if training:
+            self._ctx._check(self._L.edison_ftrain_grad_dev(self._h, _t_ptr(x), _t_ptr(y), n, _t_ptr(loss), _t_ptr(argmax)))
+        else:
+            self._ctx._check(self._L.edison_ftrain_grad_dev_ex(self._h, _t_ptr(x), _t_ptr(y), n, _t_ptr(loss), _t_ptr(argmax), FTRAIN_EVAL))
 
     def gradient(self):
         """The last call's gradient, packed float32 [w_floats] (synchronises)."""
@@ -273,7 +339,7 @@ class Trainer:
         self._ctx._fnet_trainer = self          # the context's copy of the blob is behind the device weights now
 
     def reset(self):
-        """Zero Adam's moments, its step count and the ignored-row counter."""
+        """Zero Adam's moments, its step count, the ignored-row counter and dropout's call counter."""
         self._ctx._check(self._L.edison_ftrain_reset(self._h))
 
     # -- the weights

@@ -473,6 +473,24 @@ int edison_fcal_result(edison_fcal *c, uint32_t *absmax, uint64_t *hist, uint64_
  *   edison_ftrain_set_opt   kind and Adam's constants (at create: Adam, 0.9, 0.999, 1e-7); edison_ftrain_reset zeroes m, v, t and the
  *                           counter of ignored rows
  *   edison_ftrain_weights_get / _set  copy the packed weights [w_floats] out / in (synchronising)
+ * Dropout, off at create:
+ *   edison_ftrain_set_dropout  rate [n_records] in [0, 1) behind each conv / dense record's output (n_records = n_layers; the last
+ *                           record's is 0: its output is the logits) and before_pool [n_records] (NULL: all 0): 1 puts the mask between
+ *                           ReLU and the pool (Keras's Conv -> Dropout -> MaxPool), 0 behind the pool; with no pool they coincide.
+ *                           All rates 0 turns dropout off. Sets the call counter to 0. Anything else is EDISON_E_ARGUMENT and leaves
+ *                           the previous setting. Synchronises.
+ *                           Whether element e of record l is kept for row u of a call is a pure function of (seed, call counter, u,
+ *                           l, e) -- Philox4x32-10 keys per (row, record), two MurmurHash3 finalisers per element, csrc/fnet_dropout.h
+ *                           -- and does not depend on the tile, the grid or the batch the trainer runs at. A kept value is multiplied
+ *                           by (float)(1 / (1 - rate)), a dropped one is +0.0f. The masks are this library's, not TensorFlow's.
+ *   edison_ftrain_set_dropout_call  position the call counter (< 2^60): resuming, or repeating a call
+ *   edison_ftrain_dropout_get  read the setting back: rate and before_pool [n_layers], seed, counter (each NULL for not wanted)
+ *   edison_ftrain_grad_dev_ex / edison_ftrain_grad_ex  the gradient calls with flags. EDISON_FTRAIN_EVAL: no dropout, the counter not
+ *                           advanced; the outputs are bit for bit those of a trainer on which dropout was never set (validation).
+ *                           flags = 0 is the plain call; any other bit is EDISON_E_ARGUMENT.
+ * With dropout set, edison_ftrain_grad_dev / edison_ftrain_grad (and flags 0) are training calls: they apply the mask of the current
+ * counter (n < 2^32 rows), then advance it by one; the logits and the loss they give are those of the masked network. Repeating a
+ * call at the same counter gives the same bits. edison_ftrain_reset also sets the counter to 0. With dropout never set nothing changes.
  * The packed layout is the .ednf blob's and the kernels': per conv / dense record, at float offset w_at, B[k_pad][n_pad] with
  * k = (ky kw + kx) in_c + ci, then bias[n_pad] (edison_ftrain_layout; K = the real k rows). Padding k rows and padding channels of the
  * gradient are exactly +0.0f whatever the blob holds there, so a step leaves the weights' padding as it was.
@@ -483,6 +501,7 @@ int edison_fcal_result(edison_fcal *c, uint32_t *absmax, uint64_t *hist, uint64_
 #define EDISON_FTRAIN_ADAM 0
 #define EDISON_FTRAIN_SGD 1
 #define EDISON_FTRAIN_PADDED 1u
+#define EDISON_FTRAIN_EVAL 1u /* edison_ftrain_grad_dev_ex / edison_ftrain_grad_ex */
 typedef struct edison_ftrain edison_ftrain;
 typedef struct edison_ftrain_info_t {
 	int32_t n_layers;  /* conv / dense records */
@@ -509,6 +528,11 @@ int edison_ftrain_set_opt(edison_ftrain *t, int kind, double b1, double b2, doub
 int edison_ftrain_weights_get(edison_ftrain *t, float *packed);
 int edison_ftrain_weights_set(edison_ftrain *t, const float *packed);
 int edison_ftrain_reset(edison_ftrain *t);
+int edison_ftrain_set_dropout(edison_ftrain *t, const double *rate, const uint8_t *before_pool, int n_records, uint64_t seed);
+int edison_ftrain_set_dropout_call(edison_ftrain *t, uint64_t call);
+int edison_ftrain_dropout_get(edison_ftrain *t, double *rate, uint8_t *before_pool, uint64_t *seed, uint64_t *call);
+int edison_ftrain_grad_dev_ex(edison_ftrain *t, const float *in, const int32_t *labels, int64_t n, float *loss, int32_t *argmax, uint32_t flags);
+int edison_ftrain_grad_ex(edison_ftrain *t, const float *in, const int32_t *labels, int64_t n, float *loss, int32_t *argmax, uint32_t flags);
 
 /*
  * Exact KWS mode (off by default; EDISON_KWS_EXACT=1 in the environment at edison_init turns it on for that context).

@@ -8,9 +8,12 @@ between two host clock readings, ended by a device synchronise, so it holds the 
 samples per second, its minimum and maximum. The learning rate is 0, so the weights the forward leg runs never move.
 
     python tools/bench_train.py [--net FILE.ednf] [--batches 100,4096] [--repeats 7] [--region-ms 300] [--out FILE.json]
+                                [--dropout 0,0,0.2,0.3,0 | --dropout-arch kws_conv] [--dropout-before-pool 0,1,..]
 
 --net: another float network than the shipped one, 'same' convs and pools included (the trainer is created with padded=True; on a
 network without pads that is the plain trainer).
+
+--dropout: the training leg runs with these Dropout rates per conv / dense record, a new mask every call.
 
 One JSON line.
 """
@@ -33,6 +36,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--region-ms", type=float, default=300.0)
     ap.add_argument("--out")
+    ap.add_argument("--dropout")
+    ap.add_argument("--dropout-before-pool")
+    ap.add_argument("--dropout-arch")
     args = ap.parse_args()
     import torch
     from edison_amd.context import Context
@@ -45,10 +51,14 @@ def main():
     dev = torch.device("cuda", 0)
     ctx.use_torch_stream()
     tr = ctx.trainer(padded=True)
+    from edison_amd import train
+    dropout = train.KERAS_DROPOUT[args.dropout_arch] if args.dropout_arch else [float(v) for v in args.dropout.split(",")] if args.dropout else None
+    if dropout is not None:
+        tr.set_dropout(dropout, [int(v) for v in args.dropout_before_pool.split(",")] if args.dropout_before_pool else None, seed=19)
     tinfo = tr.info()
     rng = np.random.default_rng(19)
     row = dict(network=os.path.basename(args.net), device=torch.cuda.get_device_name(0), train_batch=tinfo["batch"], grid=tinfo["grid"], lds_bytes=tinfo["lds_bytes"],
-               w_floats=tinfo["w_floats"], repeats=args.repeats, region_ms=args.region_ms, results=[])
+               w_floats=tinfo["w_floats"], dropout=tr.dropout()["rates"], dropout_before_pool=tr.dropout()["before_pool"], repeats=args.repeats, region_ms=args.region_ms, results=[])
     for n in [int(b) for b in args.batches.split(",")]:
         x = torch.from_numpy(rng.normal(0, 30, (n, in_n)).astype(np.float32)).to(dev)
         y = torch.from_numpy((np.arange(n) % n_out).astype(np.int32)).to(dev)
