@@ -321,6 +321,14 @@ SIGNATURES = {
     "edison_ftrain_dropout_get": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "edison_ftrain_grad_dev_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, ctypes.c_uint32]),
     "edison_ftrain_grad_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, ctypes.c_uint32]),
+    "edison_ftrain_set_batchnorm": (c_int, [c_void_p, c_void_p, c_int, c_double, c_double, c_int64, ctypes.c_uint32]),
+    "edison_ftrain_batchnorm_get": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_double), ctypes.POINTER(c_double), ctypes.POINTER(c_int64),
+                                            ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32)]),
+    "edison_ftrain_bn_get": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_ftrain_bn_set": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edison_ftrain_bn_batch_get": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "edison_ftrain_bn_grad_get": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "edison_ftrain_folded_get": (c_int, [c_void_p, c_void_p]),
     "edison_eval_default_opts": (None, [ctypes.POINTER(EvalOpts)]),
     "edison_eval_create": (c_int, [c_void_p, ctypes.POINTER(EvalOpts), ctypes.POINTER(c_void_p)]),
     "edison_eval_destroy": (None, [c_void_p]),

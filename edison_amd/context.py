@@ -566,13 +566,14 @@ class Context:
         return calibrate.quantize_audio(self, audio, geometry=geometry, q15=q15, chunk=chunk, method=method, saturate=saturate, **kw)
 
     # ------------------------------------------------------------------ training the float network (edison_ftrain_*, train.py)
-    def trainer(self, padded=False, dropout=None, seed=0):
+    def trainer(self, padded=False, dropout=None, seed=0, batchnorm=None):
         """A train.Trainer on this context, bound to the loaded float network: grad / grad_t, step, weights, set_weights, model, fit
         (edison_ftrain_create_ex). padded=True also takes networks with conv or pool pads (EDISON_FTRAIN_PADDED); without it such a
         network is refused. dropout: Trainer.set_dropout's rates per conv / dense record (train.KERAS_DROPOUT holds the reference's), with
-        `seed`. Its steps change the loaded network's device weights in place."""
+        `seed`. batchnorm: Trainer.set_batchnorm's records (train.KERAS_BATCHNORM holds the reference's), or a dict of its arguments. Its
+        steps change the loaded network's device weights in place."""
         from . import train
-        return train.Trainer(self, padded=padded, dropout=dropout, seed=seed)
+        return train.Trainer(self, padded=padded, dropout=dropout, seed=seed, batchnorm=batchnorm)
 
     def _fnet_refresh(self):
         """Bring _fnet_blob up to the weights a trainer has stepped the loaded network to (quantize() reads the weights from it)."""

@@ -25,6 +25,7 @@ struct ed_fnet
 {
 	ed_fnet_plan_t plan; /* w / tab point into d */
 	int32_t in_h, in_w, in_c;
+	ed_fnet_geom_t geom[ED_FNET_MAX_LAYERS];
 	void *d;
 };
 
@@ -37,6 +38,7 @@ void ed_ctx_fnet_free(edison_ctx *ctx)
 }
 
 const ed_fnet_plan_t *ed_ctx_fnet_plan(const edison_ctx *ctx) { return ctx && ctx->fnet ? &ctx->fnet->plan : NULL; }
+const ed_fnet_geom_t *ed_ctx_fnet_geom(const edison_ctx *ctx) { return ctx && ctx->fnet ? ctx->fnet->geom : NULL; }
 
 static int32_t rd32(const uint8_t *p)
 {
@@ -116,6 +118,7 @@ static int parse(edison_ctx *ctx, const uint8_t *b, size_t nb, ed_fnet *f, float
 		/* not reachable while nl <= ED_FNET_MAX_LAYERS + 1 and the last record must be the softmax; kept beside p.L's bound */
 		if (n_conv == ED_FNET_MAX_LAYERS) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: at most 16 conv / dense layers");
 		ed_fnet_layer_t &L = p.L[n_conv];
+		f->geom[n_conv] = (ed_fnet_geom_t){sh, sw, ph, pw, oh, ow, v[4], v[5]};
 		L.in_n = ih * iw * ic;
 		L.out_c = oc;
 		L.out_n = v[4] * v[5] * oc;

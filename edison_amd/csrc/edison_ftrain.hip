@@ -7,7 +7,10 @@
  * network with a conv or pool pad; edison_ftrain_create_ex with EDISON_FTRAIN_PADDED takes it (two ints per row base, the inverse
  * origin table from the padded tables). Dropout (edison_ftrain_set_dropout) is a setting of the trainer: per
  * record a rate and a position in the plan's device copy, a seed and a call counter here; a training call with a non-zero rate runs the
- * kernel's instantiation with the mask of fnet_dropout.h and advances the counter.
+ * kernel's instantiation with the mask of fnet_dropout.h and advances the counter. BatchNorm (edison_ftrain_set_batchnorm; DESIGN.md
+ * section 19c) turns the trainer into one that owns master weights, gamma, beta and moving statistics: a training call is the chain of
+ * launches of fnet_bn_kernels.hip over stores sized for max_rows rows, and after every change a fold kernel rewrites the loaded
+ * network's device buffer with the inference-mode network, which is what every other entry point, an EVAL call included, runs.
  */
 #include <math.h>
 #include <stdlib.h>
@@ -16,6 +19,7 @@
 #include <vector>
 
 #include "edison_ctx.h"
+#include "fnet_bn.h"
 #include "fnet_dropout.h"
 #include "fnet_train.h"
 
@@ -39,7 +43,19 @@ struct edison_ftrain
 	double drop_rate[ED_FNET_MAX_LAYERS];
 	bool drop_on;
 	uint64_t drop_seed, drop_call;
+	/* BatchNorm: off until edison_ftrain_set_batchnorm. d_master [w_floats] is what step and weights_get / _set see; d_bn holds every
+	 * per-channel array of the plan, d_bn_m / d_bn_v Adam's moments of gamma and beta. grad_stale: the last gradient call was an EVAL
+	 * call on the folded weights, whose gradient is not one of the master weights. */
+	bool bn_on, grad_stale;
+	uint8_t has_bn[ED_FNET_MAX_LAYERS];
+	double bn_momentum, bn_eps;
+	uint32_t bn_flags;
+	ed_fbn_plan_t bplan, *d_bplan;
+	float *d_master, *d_bn, *d_bn_m, *d_bn_v;
+	int32_t *d_rtab, *d_binv;
 };
+
+#define EDBN_DEFAULT_ROWS 1024
 
 static int ftrain_live(edison_ftrain *t, const char *who)
 {
@@ -187,7 +203,9 @@ extern "C" void edison_ftrain_destroy(edison_ftrain *t)
 	if (!t) return;
 	(void)hipSetDevice(t->ctx->device);
 	(void)hipStreamSynchronize(t->ctx->stream); /* a gradient call or a step may still be queued */
-	void *bufs[] = {t->d_plan, t->d_inv, t->plan.slabs, t->plan.acts, t->plan.dacts, t->plan.mask, t->plan.keys, t->d_grad, t->d_m, t->d_v, t->d_logits, t->d_ignored};
+	void *bufs[] = {t->d_plan, t->d_inv, t->plan.slabs, t->plan.acts, t->plan.dacts, t->plan.mask, t->plan.keys, t->d_grad, t->d_m, t->d_v, t->d_logits, t->d_ignored,
+	                t->d_bplan, t->d_master, t->d_bn, t->d_bn_m, t->d_bn_v, t->d_rtab, t->d_binv, t->bplan.zs, t->bplan.outs, t->bplan.douts, t->bplan.mask,
+	                t->bplan.part, t->bplan.keys};
 	for (void *b : bufs)
 		if (b) (void)hipFree(b);
 	delete t;
@@ -293,13 +311,29 @@ extern "C" int edison_ftrain_grad_dev_ex(edison_ftrain *t, const float *in, cons
 	edison_ctx *ctx = t->ctx;
 	if (flags & ~EDISON_FTRAIN_EVAL) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_grad_ex: flags has a bit other than EDISON_FTRAIN_EVAL");
 	const bool drop = t->drop_on && !(flags & EDISON_FTRAIN_EVAL);
+	const bool bn = t->bn_on && !(flags & EDISON_FTRAIN_EVAL);
+	if (bn && n > t->bplan.max_rows)
+	{
+		snprintf(ctx->err, sizeof(ctx->err), "edison_ftrain_grad: a training call with BatchNorm takes at most max_rows = %lld rows (edison_ftrain_set_batchnorm)",
+		         (long long)t->bplan.max_rows);
+		return EDISON_E_ARGUMENT;
+	}
+	if (bn && (t->bn_flags & EDISON_FTRAIN_BN_UNBIASED) && n > 0)
+		for (int l = 0; l < t->bplan.n_layers; l++)
+			if (t->has_bn[l] && n * t->bplan.R[l].R < 2)
+			{
+				snprintf(ctx->err, sizeof(ctx->err), "edison_ftrain_grad: record %d's statistics have N < 2 values; the unbiased variance needs two", l);
+				return EDISON_E_ARGUMENT;
+			}
 	if (drop && n > 0xffffffffll) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_grad: a training call with dropout takes fewer than 2^32 rows");
 	if (n < 0 || (n > 0 && (!in || !labels))) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_grad: negative n, or NULL inputs or labels");
 	ED_HIP(ctx, hipSetDevice(ctx->device));
 	t->n_last = n;
+	t->grad_stale = t->bn_on && !bn; /* an EVAL call runs the folded weights: what it leaves is no gradient of the master weights */
 	if (n == 0)
 	{
 		ED_HIP(ctx, hipMemsetAsync(t->d_grad, 0, sizeof(float) * (size_t)t->plan.w_floats, ctx->stream));
+		if (bn) ED_HIP(ctx, hipMemsetAsync(t->bplan.bng, 0, sizeof(float) * 2 * (size_t)t->bplan.bn_n, ctx->stream));
 		return EDISON_OK;
 	}
 	if (n > t->logits_cap)
@@ -312,6 +346,16 @@ extern "C" int edison_ftrain_grad_dev_ex(edison_ftrain *t, const float *in, cons
 		if (hipMalloc((void **)&t->d_logits, sizeof(float) * (size_t)n * (size_t)t->plan.net.n_out) != hipSuccess)
 			return ed_set_err(ctx, EDISON_E_NO_MEMORY, "edison_ftrain_grad: cannot allocate the logits");
 		t->logits_cap = n;
+	}
+	if (bn)
+	{
+		ed_fbn_drop_t dr[ED_FNET_MAX_LAYERS];
+		for (int l = 0; l < t->bplan.n_layers; l++) dr[l] = (ed_fbn_drop_t){drop ? t->plan.drop_T[l] : 0, t->plan.drop_s[l], t->plan.drop_before[l]};
+		const int r = ed_launch_result(ctx, ed_launch_fbn_train(&t->bplan, t->d_bplan, in, labels, n, loss, argmax, t->d_logits, t->d_grad, t->d_ignored, dr,
+		                                                         t->drop_seed, t->drop_call, t->bn_momentum, t->bn_eps, t->bn_flags, ctx->stream),
+		                               "BatchNorm training kernels");
+		if (r == EDISON_OK && drop) t->drop_call++;
+		return r;
 	}
 	/* the plan's w / tab are the loaded network's device buffers: the epoch check above says they are still those */
 	const int r = ed_launch_result(ctx, ed_launch_ftrain_grad(&t->plan, t->d_plan, in, labels, n, loss, argmax, t->d_logits, t->d_grad, t->d_ignored, t->grid,
@@ -359,9 +403,24 @@ static int ftrain_copy(edison_ftrain *t, const char *who, void *dst, const void 
 	return EDISON_OK;
 }
 
+/* BatchNorm: rewrite the loaded network's device buffer with the inference-mode network of the master weights and the moving statistics */
+static int ftrain_fold(edison_ftrain *t)
+{
+	edison_ctx *ctx = t->ctx;
+	return ed_launch_result(ctx, ed_launch_fbn_fold(&t->bplan, t->d_bplan, ftrain_w(t), t->bn_eps, ctx->stream), "BatchNorm fold kernel");
+}
+
+static int ftrain_stale(edison_ftrain *t, const char *who)
+{
+	snprintf(t->ctx->err, sizeof(t->ctx->err),
+	         "%s: the last gradient call was an EDISON_FTRAIN_EVAL call on the folded BatchNorm network; its gradient is not one of the trained weights (make a training call first)", who);
+	return EDISON_E_ARGUMENT;
+}
+
 extern "C" int edison_ftrain_grad_get(edison_ftrain *t, float *packed)
 {
 	if (!t) return EDISON_E_ARGUMENT;
+	if (t->grad_stale) return ftrain_stale(t, "edison_ftrain_grad_get");
 	return ftrain_copy(t, "edison_ftrain_grad_get", packed, t->d_grad, sizeof(float) * (size_t)t->plan.w_floats, hipMemcpyDeviceToHost);
 }
 
@@ -375,13 +434,14 @@ extern "C" int edison_ftrain_logits_get(edison_ftrain *t, float *logits)
 extern "C" int edison_ftrain_weights_get(edison_ftrain *t, float *packed)
 {
 	if (!t) return EDISON_E_ARGUMENT;
-	return ftrain_copy(t, "edison_ftrain_weights_get", packed, t->plan.net.w, sizeof(float) * (size_t)t->plan.w_floats, hipMemcpyDeviceToHost);
+	return ftrain_copy(t, "edison_ftrain_weights_get", packed, t->bn_on ? t->d_master : t->plan.net.w, sizeof(float) * (size_t)t->plan.w_floats, hipMemcpyDeviceToHost);
 }
 
 extern "C" int edison_ftrain_weights_set(edison_ftrain *t, const float *packed)
 {
 	if (!t) return EDISON_E_ARGUMENT;
-	return ftrain_copy(t, "edison_ftrain_weights_set", ftrain_w(t), packed, sizeof(float) * (size_t)t->plan.w_floats, hipMemcpyHostToDevice);
+	const int r = ftrain_copy(t, "edison_ftrain_weights_set", t->bn_on ? t->d_master : ftrain_w(t), packed, sizeof(float) * (size_t)t->plan.w_floats, hipMemcpyHostToDevice);
+	return r == EDISON_OK && t->bn_on ? ftrain_fold(t) : r;
 }
 
 extern "C" int edison_ftrain_set_opt(edison_ftrain *t, int kind, double b1, double b2, double eps)
@@ -400,13 +460,18 @@ extern "C" int edison_ftrain_step(edison_ftrain *t, double lr)
 	{ const int r = ftrain_live(t, "edison_ftrain_step"); if (r != EDISON_OK) return r; }
 	edison_ctx *ctx = t->ctx;
 	if (!(lr >= 0.0) || !isfinite(lr)) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_step: the learning rate is negative or not finite");
+	if (t->grad_stale) return ftrain_stale(t, "edison_ftrain_step");
 	ED_HIP(ctx, hipSetDevice(ctx->device));
 	const double tt = (double)(t->steps + 1);
 	const double factor = t->kind == EDISON_FTRAIN_SGD ? lr : lr * sqrt(1.0 - pow(t->b2, tt)) / (1.0 - pow(t->b1, tt));
-	const int e = ed_launch_ftrain_step(t->kind, ftrain_w(t), t->d_grad, t->d_m, t->d_v, t->plan.w_floats, (float)factor, (float)t->b1, (float)(1.0 - t->b1),
-	                                    (float)t->b2, (float)(1.0 - t->b2), (float)t->eps, ctx->n_cu, ctx->stream);
+	int e = ed_launch_ftrain_step(t->kind, t->bn_on ? t->d_master : ftrain_w(t), t->d_grad, t->d_m, t->d_v, t->plan.w_floats, (float)factor, (float)t->b1,
+	                              (float)(1.0 - t->b1), (float)t->b2, (float)(1.0 - t->b2), (float)t->eps, ctx->n_cu, ctx->stream);
+	if (e == 0 && t->bn_on) /* gamma and beta: the same optimiser, moments of their own; channels of records without BatchNorm have gradient 0 */
+		e = ed_launch_ftrain_step(t->kind, t->bplan.bnp, t->bplan.bng, t->d_bn_m, t->d_bn_v, 2 * (int64_t)t->bplan.bn_n, (float)factor, (float)t->b1,
+		                          (float)(1.0 - t->b1), (float)t->b2, (float)(1.0 - t->b2), (float)t->eps, ctx->n_cu, ctx->stream);
 	if (e == 0) t->steps++;
-	return ed_launch_result(ctx, e, "optimiser step kernel");
+	{ const int r = ed_launch_result(ctx, e, "optimiser step kernel"); if (r != EDISON_OK || !t->bn_on) return r; }
+	return ftrain_fold(t);
 }
 
 extern "C" int edison_ftrain_reset(edison_ftrain *t)
@@ -417,7 +482,250 @@ extern "C" int edison_ftrain_reset(edison_ftrain *t)
 	ED_HIP(ctx, hipMemsetAsync(t->d_m, 0, sizeof(float) * (size_t)t->plan.w_floats, ctx->stream));
 	ED_HIP(ctx, hipMemsetAsync(t->d_v, 0, sizeof(float) * (size_t)t->plan.w_floats, ctx->stream));
 	ED_HIP(ctx, hipMemsetAsync(t->d_ignored, 0, sizeof(unsigned long long), ctx->stream));
+	if (t->bn_on)
+	{
+		ED_HIP(ctx, hipMemsetAsync(t->d_bn_m, 0, sizeof(float) * 2 * (size_t)t->bplan.bn_n, ctx->stream));
+		ED_HIP(ctx, hipMemsetAsync(t->d_bn_v, 0, sizeof(float) * 2 * (size_t)t->bplan.bn_n, ctx->stream));
+	}
 	t->steps = 0;
 	t->drop_call = 0;
 	return EDISON_OK;
+}
+
+/* ---- BatchNorm ---- */
+extern "C" int edison_ftrain_set_batchnorm(edison_ftrain *t, const uint8_t *has_bn, int n_records, double momentum, double eps, int64_t max_rows, uint32_t flags)
+{
+	{ const int r = ftrain_live(t, "edison_ftrain_set_batchnorm"); if (r != EDISON_OK) return r; }
+	edison_ctx *ctx = t->ctx;
+	const ed_fnet_plan_t &net = t->plan.net;
+	const int nl = net.n_layers;
+	if (t->bn_on) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_set_batchnorm: BatchNorm is already on for this trainer; create a new trainer");
+	if (!has_bn || n_records != nl) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_set_batchnorm: NULL has_bn, or n_records is not the network's conv / dense records");
+	if (flags & ~EDISON_FTRAIN_BN_UNBIASED) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_set_batchnorm: flags has a bit other than EDISON_FTRAIN_BN_UNBIASED");
+	if (!(momentum >= 0.0 && momentum < 1.0)) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_set_batchnorm: momentum is not in [0, 1)");
+	if (!(eps > 0.0) || !isfinite(eps)) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_set_batchnorm: eps is not a finite value above 0");
+	if (has_bn[nl - 1]) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_set_batchnorm: the last record's output is the logits; it takes no BatchNorm");
+	for (int l = 0; l < nl; l++)
+		if (net.L[l].pad)
+		{
+			snprintf(ctx->err, sizeof(ctx->err), "edison_ftrain_set_batchnorm: record %d has a conv or pool pad; BatchNorm trains networks without pads", l);
+			return EDISON_E_NO_IMPL;
+		}
+	if (max_rows <= 0) max_rows = EDBN_DEFAULT_ROWS;
+	if (max_rows > (1 << 22)) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_set_batchnorm: max_rows is above 2^22");
+	const ed_fnet_geom_t *geom = ed_ctx_fnet_geom(ctx);
+	if (!geom) return ed_set_err(ctx, EDISON_E_NO_MODEL, "no float network loaded (edison_fnet_load)");
+
+	ed_fbn_plan_t bp = {};
+	bp.n_layers = nl;
+	bp.in_n = net.in_n;
+	bp.n_out = net.n_out;
+	bp.grid = t->grid;
+	bp.max_rows = max_rows;
+	bp.w_floats = t->plan.w_floats;
+	bp.tab = net.tab;
+	bp.slabs = t->plan.slabs;
+	const ed_fnet_layer_t &last = net.L[nl - 1];
+	const size_t tabn = (size_t)last.rowin_at + (size_t)last.rows;
+	std::vector<int32_t> tab(tabn), rtab, inv;
+	ED_HIP(ctx, hipSetDevice(ctx->device));
+	ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	ED_HIP(ctx, hipMemcpy(tab.data(), net.tab, tabn * sizeof(int32_t), hipMemcpyDeviceToHost));
+	int64_t z_at = 0, out_at = 0;
+	int bn_n = 0;
+	for (int l = 0; l < nl; l++)
+	{
+		const ed_fnet_layer_t &L = net.L[l];
+		const ed_fnet_geom_t &g = geom[l];
+		ed_fbn_layer_t &Q = bp.R[l];
+		Q.L = L;
+		Q.G = t->plan.G[l];
+		Q.rows = L.rows; Q.P = L.P; Q.relu = L.relu;
+		Q.R = g.ch * g.cw;
+		Q.L.rows = Q.R; Q.L.P = 1; Q.L.relu = 0; Q.L.live = Q.R;
+		Q.has_bn = has_bn[l] ? 1 : 0;
+		Q.rowin_at = (int32_t)rtab.size();
+		Q.bn_at = bn_n;
+		Q.in_n = L.in_n; Q.out_n = L.out_n;
+		Q.z_at = z_at; Q.out_at = out_at;
+		z_at += max_rows * (int64_t)Q.R * L.out_c;
+		out_at += max_rows * (int64_t)L.out_n;
+		bn_n += L.n_pad;
+		/* the row table: the plan's rows r = q P + e first, then the conv positions the pool's floor drops, which have no window */
+		const int32_t *rowin = tab.data() + L.rowin_at, *koff = tab.data() + L.koff_at;
+		for (int r = 0; r < L.rows; r++) rtab.push_back(rowin[r]);
+		for (int cy = 0; cy < g.ch; cy++)
+			for (int cx = 0; cx < g.cw; cx++)
+				if (cy >= g.oh * g.ph || cx >= g.ow * g.pw) rtab.push_back((cy * g.sh * L.in_w + cx * g.sw) * L.in_c);
+		if ((int)(rtab.size() - (size_t)Q.rowin_at) != Q.R) return ed_set_err(ctx, EDISON_E_RUNTIME, "edison_ftrain_set_batchnorm: a record's rows do not cover its conv map");
+		/* dX's inverse origin table over these rows: a truncated position reads its window too */
+		Q.G.inv_at = (int32_t)inv.size();
+		if (l == 0) continue;
+		if ((int64_t)Q.G.np * Q.G.T + (int64_t)inv.size() > EDFT_MAX_INV) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_ftrain_set_batchnorm: the inverse origin tables are too large");
+		inv.resize(inv.size() + (size_t)Q.G.np * Q.G.T, -1);
+		int32_t *iv = inv.data() + Q.G.inv_at;
+		const int32_t *rt = rtab.data() + Q.rowin_at;
+		for (int r = 0; r < Q.R; r++)
+			for (int tap = 0; tap < Q.G.T; tap++) iv[(size_t)((rt[r] + koff[tap * L.in_c]) / L.in_c) * Q.G.T + tap] = r;
+	}
+	bp.bn_n = bn_n;
+	/* utterances a tile: the trainer's, fewer while dZ over the whole conv map does not fit */
+	bp.batch = net.batch;
+	while (bp.batch > 1 && ed_fbn_lds_bytes(&bp, bp.batch) > ED_FNET_LDS_BYTES) bp.batch--;
+	if (ed_fbn_lds_bytes(&bp, bp.batch) > ED_FNET_LDS_BYTES)
+		return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_ftrain_set_batchnorm: one utterance's dZ of the largest record does not fit the LDS");
+	if ((int64_t)bp.batch * bp.R[0].R > INT32_MAX / 1024 || z_at > ((int64_t)1 << 33) || out_at > ((int64_t)1 << 33))
+		return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_ftrain_set_batchnorm: the stores of max_rows rows are too large");
+
+	const size_t wb = sizeof(float) * (size_t)bp.w_floats, cb = sizeof(float) * (size_t)bn_n;
+	float *d_bn = NULL;
+	hipError_t e = hipMalloc((void **)&t->d_master, wb);
+	if (e == hipSuccess) e = hipMemcpy(t->d_master, net.w, wb, hipMemcpyDeviceToDevice);
+	if (e == hipSuccess) e = hipMalloc((void **)&d_bn, 9 * cb);
+	t->d_bn = d_bn;
+	if (e == hipSuccess) e = hipMalloc((void **)&t->d_bn_m, 2 * cb);
+	if (e == hipSuccess) e = hipMalloc((void **)&t->d_bn_v, 2 * cb);
+	if (e == hipSuccess) e = hipMemset(t->d_bn_m, 0, 2 * cb);
+	if (e == hipSuccess) e = hipMemset(t->d_bn_v, 0, 2 * cb);
+	if (e == hipSuccess)
+	{
+		/* gamma 1, beta 0, gradients 0, moving mean 0, moving variance 1, batch statistics 0 / 0 / 1 */
+		std::vector<float> init(9 * (size_t)bn_n, 0.0f);
+		for (int i = 0; i < bn_n; i++) init[i] = init[5 * (size_t)bn_n + i] = init[8 * (size_t)bn_n + i] = 1.0f;
+		e = hipMemcpy(d_bn, init.data(), 9 * cb, hipMemcpyHostToDevice);
+	}
+	if (e == hipSuccess) e = hipMalloc((void **)&t->d_rtab, sizeof(int32_t) * rtab.size());
+	if (e == hipSuccess) e = hipMemcpy(t->d_rtab, rtab.data(), sizeof(int32_t) * rtab.size(), hipMemcpyHostToDevice);
+	if (e == hipSuccess) e = hipMalloc((void **)&t->d_binv, sizeof(int32_t) * (inv.size() ? inv.size() : 1));
+	if (e == hipSuccess && inv.size()) e = hipMemcpy(t->d_binv, inv.data(), sizeof(int32_t) * inv.size(), hipMemcpyHostToDevice);
+	if (e == hipSuccess) e = hipMalloc((void **)&bp.zs, sizeof(float) * (size_t)z_at);
+	if (e == hipSuccess) e = hipMalloc((void **)&bp.outs, sizeof(float) * (size_t)out_at);
+	if (e == hipSuccess) e = hipMalloc((void **)&bp.douts, sizeof(float) * (size_t)out_at);
+	if (e == hipSuccess) e = hipMalloc((void **)&bp.mask, (size_t)out_at);
+	if (e == hipSuccess) e = hipMalloc((void **)&bp.part, sizeof(double) * 2 * (size_t)bn_n * (size_t)t->grid);
+	if (e == hipSuccess) e = hipMalloc((void **)&bp.keys, sizeof(uint32_t) * 2 * (size_t)max_rows * (size_t)nl);
+	if (e == hipSuccess) e = hipMalloc((void **)&t->d_bplan, sizeof(bp));
+	if (e == hipSuccess)
+	{
+		bp.w = t->d_master;
+		bp.rtab = t->d_rtab;
+		bp.inv = t->d_binv;
+		bp.bnp = d_bn;
+		bp.bng = d_bn + 2 * (size_t)bn_n;
+		bp.mm = d_bn + 4 * (size_t)bn_n;
+		bp.mv = d_bn + 5 * (size_t)bn_n;
+		bp.mean = d_bn + 6 * (size_t)bn_n;
+		bp.var = d_bn + 7 * (size_t)bn_n;
+		bp.rstd = d_bn + 8 * (size_t)bn_n;
+		e = hipMemcpy(t->d_bplan, &bp, sizeof(bp), hipMemcpyHostToDevice);
+	}
+	t->bplan = bp; /* destroy frees whatever was allocated */
+	if (e != hipSuccess)
+	{
+		void **bufs[] = {(void **)&t->d_master, (void **)&t->d_bn, (void **)&t->d_bn_m, (void **)&t->d_bn_v, (void **)&t->d_rtab, (void **)&t->d_binv, (void **)&t->bplan.zs,
+		                 (void **)&t->bplan.outs, (void **)&t->bplan.douts, (void **)&t->bplan.mask, (void **)&t->bplan.part, (void **)&t->bplan.keys, (void **)&t->d_bplan};
+		for (void **b : bufs)
+		{
+			if (*b) (void)hipFree(*b);
+			*b = NULL;
+		}
+		return ed_set_err(ctx, e == hipErrorOutOfMemory ? EDISON_E_NO_MEMORY : EDISON_E_RUNTIME, "edison_ftrain_set_batchnorm: cannot allocate the stores of max_rows rows");
+	}
+	for (int l = 0; l < nl; l++) t->has_bn[l] = bp.R[l].has_bn;
+	t->bn_momentum = momentum;
+	t->bn_eps = eps;
+	t->bn_flags = flags;
+	t->bn_on = true;
+	t->grad_stale = false;
+	/* the copies and memsets above ran on the null stream and the context's stream does not wait for it: done before the fold reads them */
+	ED_HIP(ctx, hipDeviceSynchronize());
+	return ftrain_fold(t); /* gamma 1, beta 0, mean 0, variance 1: the loaded weights over sqrt(1 + eps) */
+}
+
+extern "C" int edison_ftrain_batchnorm_get(edison_ftrain *t, uint8_t *has_bn, double *momentum, double *eps, int64_t *max_rows, uint32_t *flags, int32_t *batch)
+{
+	{ const int r = ftrain_live(t, "edison_ftrain_batchnorm_get"); if (r != EDISON_OK) return r; }
+	if (has_bn)
+		for (int l = 0; l < t->plan.net.n_layers; l++) has_bn[l] = t->bn_on ? t->has_bn[l] : 0;
+	if (momentum) *momentum = t->bn_on ? t->bn_momentum : 0.0;
+	if (eps) *eps = t->bn_on ? t->bn_eps : 0.0;
+	if (max_rows) *max_rows = t->bn_on ? t->bplan.max_rows : 0;
+	if (flags) *flags = t->bn_on ? t->bn_flags : 0;
+	if (batch) *batch = t->bn_on ? t->bplan.batch : 0;
+	return EDISON_OK;
+}
+
+/* the BatchNorm record `record` of a trainer with BatchNorm on, or an error */
+static int ftrain_bn_record(edison_ftrain *t, const char *who, int record)
+{
+	{ const int r = ftrain_live(t, who); if (r != EDISON_OK) return r; }
+	if (!t->bn_on || record < 0 || record >= t->plan.net.n_layers || !t->has_bn[record])
+	{
+		snprintf(t->ctx->err, sizeof(t->ctx->err), "%s: record %d is not a BatchNorm record of this trainer", who, record);
+		return EDISON_E_ARGUMENT;
+	}
+	return EDISON_OK;
+}
+
+static int ftrain_bn_copy(edison_ftrain *t, int record, float *const host[], float *const dev[], int count, bool to_host)
+{
+	edison_ctx *ctx = t->ctx;
+	const ed_fbn_layer_t &Q = t->bplan.R[record];
+	ED_HIP(ctx, hipSetDevice(ctx->device));
+	for (int i = 0; i < count; i++)
+	{
+		if (!host[i]) continue;
+		if (to_host) ED_HIP(ctx, hipMemcpyAsync(host[i], dev[i] + Q.bn_at, sizeof(float) * (size_t)Q.L.out_c, hipMemcpyDeviceToHost, ctx->stream));
+		else ED_HIP(ctx, hipMemcpyAsync(dev[i] + Q.bn_at, host[i], sizeof(float) * (size_t)Q.L.out_c, hipMemcpyHostToDevice, ctx->stream));
+	}
+	ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return EDISON_OK;
+}
+
+extern "C" int edison_ftrain_bn_get(edison_ftrain *t, int record, float *gamma, float *beta, float *mean, float *var)
+{
+	{ const int r = ftrain_bn_record(t, "edison_ftrain_bn_get", record); if (r != EDISON_OK) return r; }
+	float *const host[] = {gamma, beta, mean, var};
+	float *const dev[] = {t->bplan.bnp, t->bplan.bnp + t->bplan.bn_n, t->bplan.mm, t->bplan.mv};
+	return ftrain_bn_copy(t, record, host, dev, 4, true);
+}
+
+extern "C" int edison_ftrain_bn_batch_get(edison_ftrain *t, int record, float *mean, float *var)
+{
+	{ const int r = ftrain_bn_record(t, "edison_ftrain_bn_batch_get", record); if (r != EDISON_OK) return r; }
+	float *const host[] = {mean, var};
+	float *const dev[] = {t->bplan.mean, t->bplan.var};
+	return ftrain_bn_copy(t, record, host, dev, 2, true);
+}
+
+extern "C" int edison_ftrain_bn_set(edison_ftrain *t, int record, const float *gamma, const float *beta, const float *mean, const float *var)
+{
+	{ const int r = ftrain_bn_record(t, "edison_ftrain_bn_set", record); if (r != EDISON_OK) return r; }
+	const int oc = t->bplan.R[record].L.out_c;
+	const float *all[] = {gamma, beta, mean, var};
+	for (const float *a : all)
+		for (int c = 0; a && c < oc; c++)
+			if (!isfinite(a[c])) return ed_set_err(t->ctx, EDISON_E_ARGUMENT, "edison_ftrain_bn_set: a value is not finite");
+	/* in the fold kernel's own arithmetic, float32: what passes here has a finite 1 / sqrtf(var + eps) there */
+	for (int c = 0; var && c < oc; c++)
+		if (!(var[c] + (float)t->bn_eps > 0.0f)) return ed_set_err(t->ctx, EDISON_E_ARGUMENT, "edison_ftrain_bn_set: a variance is not above -eps");
+	float *const host[] = {const_cast<float *>(gamma), const_cast<float *>(beta), const_cast<float *>(mean), const_cast<float *>(var)};
+	float *const dev[] = {t->bplan.bnp, t->bplan.bnp + t->bplan.bn_n, t->bplan.mm, t->bplan.mv};
+	{ const int r = ftrain_bn_copy(t, record, host, dev, 4, false); if (r != EDISON_OK) return r; }
+	return ftrain_fold(t);
+}
+
+extern "C" int edison_ftrain_bn_grad_get(edison_ftrain *t, int record, float *dgamma, float *dbeta)
+{
+	{ const int r = ftrain_bn_record(t, "edison_ftrain_bn_grad_get", record); if (r != EDISON_OK) return r; }
+	if (t->grad_stale) return ftrain_stale(t, "edison_ftrain_bn_grad_get");
+	float *const host[] = {dgamma, dbeta};
+	float *const dev[] = {t->bplan.bng, t->bplan.bng + t->bplan.bn_n};
+	return ftrain_bn_copy(t, record, host, dev, 2, true);
+}
+
+extern "C" int edison_ftrain_folded_get(edison_ftrain *t, float *packed)
+{
+	if (!t) return EDISON_E_ARGUMENT;
+	return ftrain_copy(t, "edison_ftrain_folded_get", packed, t->plan.net.w, sizeof(float) * (size_t)t->plan.w_floats, hipMemcpyDeviceToHost);
 }

@@ -76,6 +76,13 @@ extern "C" int ed_launch_fnet_windows(const ed_fnet_plan_t *p, const float *in, 
 /* The context's loaded float network's plan, NULL when none is loaded (edison_fnet.hip). */
 struct edison_ctx;
 const ed_fnet_plan_t *ed_ctx_fnet_plan(const struct edison_ctx *ctx);
+/* What the plan's tables leave out of a conv record's geometry, for host code that builds tables of its own (the BatchNorm trainer's
+ * rows over the whole conv map, edison_ftrain.hip): strides, the pool window, the conv's map ch x cw before the pool and the pooled
+ * map oh x ow. [n_layers] of the loaded network, NULL when none is loaded. */
+typedef struct {
+	int32_t sh, sw, ph, pw, ch, cw, oh, ow;
+} ed_fnet_geom_t;
+const ed_fnet_geom_t *ed_ctx_fnet_geom(const struct edison_ctx *ctx);
 /* The host flow's net input: out[i] = min(max((float)y[i] * scale, lo), hi) for i < count. Returns a hipError_t. */
 extern "C" int ed_launch_fnet_input(const double *y, int64_t count, float scale, float lo, float hi, float *out, int n_cu, hipStream_t stream);
 

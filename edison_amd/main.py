@@ -48,7 +48,8 @@ USAGE = """usage: edison <module> <command> [<args>]
                                          quantise a float32 network to an int8 NNoM graph, calibrated on the GPU over the audio
   kws  train <net.ednf> <x.npy> <y.npy> <out.ednf> [--epochs N] [--batch N] [--lr r] [--seed s] [--val <x.npy> <y.npy>]
              [--dropout r,.. [--dropout-before-pool b,..] | --dropout-arch NAME]
-                                         train a float32 network on features and class indices: Adam on the GPU, Dropout if asked
+             [--batchnorm b,.. | --batchnorm-arch NAME] [--bn-momentum m] [--bn-eps e] [--bn-unbiased]
+                                         train a float32 network on features and class indices: Adam on the GPU, Dropout and BatchNorm if asked
 """
 
 

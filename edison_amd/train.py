@@ -19,6 +19,8 @@ from . import _lib, cube_import
 ADAM, SGD = 0, 1          # EDISON_FTRAIN_ADAM, EDISON_FTRAIN_SGD
 FTRAIN_PADDED = 1         # EDISON_FTRAIN_PADDED: edison_ftrain_create_ex's flag
 FTRAIN_EVAL = 1           # EDISON_FTRAIN_EVAL: edison_ftrain_grad_ex's flag
+FTRAIN_BN_UNBIASED = 1    # EDISON_FTRAIN_BN_UNBIASED: edison_ftrain_set_batchnorm's flag
+BN_MOMENTUM, BN_EPS = 0.99, 1e-3   # keras.layers.BatchNormalization's defaults
 LEARNING_RATE = 0.0005    # kws_keras.py:53 initial_learningrate
 BATCH_SIZE = 100          # kws_keras.py: batchSize
 
@@ -33,6 +35,20 @@ KERAS_DROPOUT = {
     "low_latency_conv": [0.25, 0, 0.25, 0],
     "simple_conv": [(0.25, 0), 0],           # after the pool
     "kws_conv": [0, 0, 0.2, 0.3, 0],
+    "single_fc": [0],
+}
+
+
+# Which conv / dense records the reference follows with BatchNormalization (kws_keras.py:194-398): only kws_conv has any, behind each of
+# its four convolutions (Conv -> BatchNormalization -> ReLU -> MaxPool / Dropout). The last record gives the logits: never one.
+KERAS_BATCHNORM = {
+    "tiny_conv": [0, 0],
+    "medium_embedding_conv": [0, 0, 0],
+    "tiny_embedding_conv": [0, 0, 0],
+    "conv_model": [0, 0, 0],
+    "low_latency_conv": [0, 0, 0, 0],
+    "simple_conv": [0, 0],
+    "kws_conv": [1, 1, 1, 1, 0],
     "single_fc": [0],
 }
 
@@ -161,9 +177,11 @@ def fit(trainer, x, y, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=LEARN
         vx, vy = np.asarray(val[0]), np.asarray(val[1]).astype(np.int32).reshape(-1)
         vx = vx.reshape(vx.shape[0], -1)
     plateau, stopper = ReduceLROnPlateau(), EarlyStopping()
-    # validation runs with dropout off: the keyword goes only to a trainer that reports dropout on, so anything without it keeps working
+    # validation runs with dropout off and on BatchNorm's moving statistics: the keyword goes only to a trainer that reports one of them
+    # on, so anything without them keeps working
     state = trainer.dropout() if hasattr(trainer, "dropout") else None
-    ev = dict(training=False) if state and state.get("on") else {}
+    bn = trainer.batchnorm() if hasattr(trainer, "batchnorm") else None
+    ev = dict(training=False) if (state and state.get("on")) or (bn and bn.get("on")) else {}
     hist = dict(loss=[], acc=[], val_loss=[], val_acc=[], lr=[], steps=0, stopped_early=False)
     for epoch in range(int(epochs)):
         order = epoch_order(n, seed, epoch)
@@ -205,9 +223,9 @@ def fit(trainer, x, y, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=LEARN
 class Trainer:
     """edison_ftrain on `ctx`, bound to the float network loaded now; loading another one invalidates it (EdisonError).
     padded=True (EDISON_FTRAIN_PADDED) also takes networks with conv or pool pads; without it they are refused.
-    dropout: set_dropout's rates (None: off), with `seed`."""
+    dropout: set_dropout's rates (None: off), with `seed`. batchnorm: set_batchnorm's records (None: off), or a dict of its arguments."""
 
-    def __init__(self, ctx, padded=False, dropout=None, seed=0):
+    def __init__(self, ctx, padded=False, dropout=None, seed=0, batchnorm=None):
         self._ctx, self._L = ctx, ctx._L
         if ctx._fnet_blob is None:
             raise ValueError("no float network loaded (fnet_load)")
@@ -224,6 +242,8 @@ class Trainer:
                 raise RuntimeError("record %d: edison_ftrain_layout %s, the blob's %s" % (i, got, r))
         if dropout is not None:
             self.set_dropout(dropout, seed=seed)
+        if batchnorm is not None:
+            self.set_batchnorm(**batchnorm) if isinstance(batchnorm, dict) else self.set_batchnorm(batchnorm)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -281,6 +301,76 @@ class Trainer:
     @dropout_call.setter
     def dropout_call(self, call):
         self._ctx._check(self._L.edison_ftrain_set_dropout_call(self._h, int(call)))
+
+    # -- BatchNorm
+    def set_batchnorm(self, has_bn, momentum=BN_MOMENTUM, eps=BN_EPS, max_rows=None, unbiased=False):
+        """edison_ftrain_set_batchnorm: has_bn per conv / dense record, 1 where conv + bias is followed by BatchNorm (KERAS_BATCHNORM's
+        form; never the last record, and no record of the network may have a pad). Batch statistics over every row of a training call
+        and the whole conv map; the moving statistics move by `momentum` (unbiased=True: by var N / (N - 1), torch's rule). A training
+        call takes at most max_rows rows (None: 1024). From here on weights() / set_weights() are the master weights, gamma and beta
+        train beside them, and the context runs the folded inference-mode network, which model() and export() give. Once per trainer."""
+        hb = np.ascontiguousarray([1 if v else 0 for v in has_bn], dtype=np.uint8)
+        self._ctx._check(self._L.edison_ftrain_set_batchnorm(self._h, _np_ptr(hb), len(hb), float(momentum), float(eps),
+                                                             0 if max_rows is None else int(max_rows), FTRAIN_BN_UNBIASED if unbiased else 0))
+        self._ctx._fnet_trainer = self          # the device weights are the folded ones now: W / sqrt(1 + eps)
+
+    def batchnorm(self):
+        """edison_ftrain_batchnorm_get: dict(on: set_batchnorm was called, whatever it marked (the library reports max_rows 0 until then), has_bn, momentum, eps, max_rows, unbiased, batch: utterances per tile of a training call)."""
+        hb = np.zeros(self.n_layers, np.uint8)
+        m, e, rows, fl, batch = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64(), ctypes.c_uint32(), ctypes.c_int32()
+        self._ctx._check(self._L.edison_ftrain_batchnorm_get(self._h, _np_ptr(hb), ctypes.byref(m), ctypes.byref(e), ctypes.byref(rows), ctypes.byref(fl),
+                                                             ctypes.byref(batch)))
+        return dict(on=rows.value > 0, has_bn=[int(v) for v in hb], momentum=m.value, eps=e.value, max_rows=rows.value,
+                    unbiased=bool(fl.value & FTRAIN_BN_UNBIASED), batch=batch.value)
+
+    def _bn_records(self):
+        return [i for i, v in enumerate(self.batchnorm()["has_bn"]) if v]
+
+    def bn_state(self):
+        """Per conv / dense record None, or dict(gamma, beta, mean, var) float32 [out_c]: the moving statistics."""
+        out = [None] * self.n_layers
+        for i in self._bn_records():
+            a = {k: np.zeros(self.layout[i]["out_c"], np.float32) for k in ("gamma", "beta", "mean", "var")}
+            self._ctx._check(self._L.edison_ftrain_bn_get(self._h, i, *[_np_ptr(a[k]) for k in ("gamma", "beta", "mean", "var")]))
+            out[i] = a
+        return out
+
+    def set_bn_state(self, state):
+        """bn_state's inverse: per record None (unchanged) or a dict with any of gamma, beta, mean, var; refolds the network."""
+        if len(state) != self.n_layers:
+            raise ValueError("%d records, the network has %d" % (len(state), self.n_layers))
+        for i, st in enumerate(state):
+            if st is None:
+                continue
+            a = {k: np.ascontiguousarray(st[k], dtype=np.float32).reshape(-1) for k in ("gamma", "beta", "mean", "var") if st.get(k) is not None}
+            if any(v.shape[0] != self.layout[i]["out_c"] for v in a.values()):
+                raise ValueError("record %d has %d channels" % (i, self.layout[i]["out_c"]))
+            self._ctx._check(self._L.edison_ftrain_bn_set(self._h, i, *[_np_ptr(a.get(k)) for k in ("gamma", "beta", "mean", "var")]))
+            self._ctx._fnet_trainer = self
+
+    def bn_batch_stats(self):
+        """The last training call's batch statistics: per record None or dict(mean, var) float32 [out_c]."""
+        out = [None] * self.n_layers
+        for i in self._bn_records():
+            a = {k: np.zeros(self.layout[i]["out_c"], np.float32) for k in ("mean", "var")}
+            self._ctx._check(self._L.edison_ftrain_bn_batch_get(self._h, i, _np_ptr(a["mean"]), _np_ptr(a["var"])))
+            out[i] = a
+        return out
+
+    def bn_gradients(self):
+        """The last training call's gradient of gamma and beta: per record None or dict(gamma, beta) float32 [out_c]."""
+        out = [None] * self.n_layers
+        for i in self._bn_records():
+            a = {k: np.zeros(self.layout[i]["out_c"], np.float32) for k in ("gamma", "beta")}
+            self._ctx._check(self._L.edison_ftrain_bn_grad_get(self._h, i, _np_ptr(a["gamma"]), _np_ptr(a["beta"])))
+            out[i] = a
+        return out
+
+    def folded_weights(self):
+        """The loaded network's device weights as [dict(w, b)]: with BatchNorm on the folded inference-mode network, else weights()."""
+        w = np.zeros(self.w_floats, np.float32)
+        self._ctx._check(self._L.edison_ftrain_folded_get(self._h, _np_ptr(w)))
+        return unpack(w, self.layout)
 
     # -- the gradient
     def grad(self, x, y, training=True):
@@ -356,7 +446,8 @@ class Trainer:
         self._ctx._fnet_trainer = self
 
     def weights(self):
-        """The device weights now: [dict(w [out][kh][kw][in], b [out])] float32 per conv / dense record, the model dict's layout."""
+        """The trained weights now: [dict(w [out][kh][kw][in], b [out])] float32 per conv / dense record, the model dict's layout. With
+        BatchNorm on these are the master weights; folded_weights() are what the context runs."""
         return unpack(self.packed_weights(), self.layout)
 
     def set_weights(self, tensors):
@@ -364,10 +455,10 @@ class Trainer:
         self.set_packed_weights(pack(tensors, self.layout, base=self.packed_weights()))
 
     def model(self):
-        """The cube_import model dict of the network with the device weights now: cube_import.build_blob(trainer.model(),
-        trainer.model()["keywords"]) is the trained .ednf."""
+        """The cube_import model dict of the network with the device weights now (with BatchNorm: folded into the convolutions, as
+        X-CUBE-AI would see it): cube_import.build_blob(trainer.model(), trainer.model()["keywords"]) is the trained .ednf."""
         m = dict(self._model, layers=[dict(L) for L in self._model["layers"]])
-        for L, t in zip(conv_records(m), self.weights()):
+        for L, t in zip(conv_records(m), self.folded_weights()):
             L["w"], L["b"] = t["w"], t["b"]
         return m
 

@@ -533,6 +533,36 @@ int edison_ftrain_set_dropout_call(edison_ftrain *t, uint64_t call);
 int edison_ftrain_dropout_get(edison_ftrain *t, double *rate, uint8_t *before_pool, uint64_t *seed, uint64_t *call);
 int edison_ftrain_grad_dev_ex(edison_ftrain *t, const float *in, const int32_t *labels, int64_t n, float *loss, int32_t *argmax, uint32_t flags);
 int edison_ftrain_grad_ex(edison_ftrain *t, const float *in, const int32_t *labels, int64_t n, float *loss, int32_t *argmax, uint32_t flags);
+/*
+ * BatchNorm in the trainer: conv + bias = z -> BatchNorm -> ReLU -> dropout -> max pool, as the reference trains
+ * kws_conv. Batch statistics are taken over every row of a training call and the whole conv map, the positions a floor-mode pool drops
+ * included; mean and the population variance from centred values; y = gamma (z - mean) / sqrt(var + eps) + beta.
+ *   edison_ftrain_set_batchnorm  has_bn [n_records = n_layers]: which records normalise (never the last; no record of the network may
+ *                           have a pad: EDISON_E_NO_IMPL). momentum in [0, 1) and eps > 0 (Keras: 0.99, 1e-3); max_rows: the most rows
+ *                           a training call may have (<= 0: 1024), the trainer's stores are sized for it; flags:
+ *                           EDISON_FTRAIN_BN_UNBIASED moves the moving variance by var N / (N - 1) (torch's rule) instead of the
+ *                           population variance. Starts at gamma 1, beta 0, moving mean 0, moving variance 1. From here on the trainer
+ *                           trains a master copy of the weights with gamma and beta, and after every step, edison_ftrain_bn_set and
+ *                           edison_ftrain_weights_set folds them into the loaded network's device buffer (W s, (b - mean) s + beta,
+ *                           s = gamma / sqrt(var + eps) of the moving statistics), which every other entry point runs.
+ *                           edison_ftrain_weights_get / _set are the master weights, edison_ftrain_folded_get the folded ones. An
+ *                           EDISON_FTRAIN_EVAL call runs the folded network, moves no statistic, and leaves no gradient:
+ *                           edison_ftrain_grad_get and edison_ftrain_step are EDISON_E_ARGUMENT until the next training call. A
+ *                           second call on one trainer is EDISON_E_ARGUMENT. A BatchNorm record's bias gradient is +0.0f.
+ *   edison_ftrain_batchnorm_get  read the setting back (each NULL for not wanted); batch: utterances per tile of a training call
+ *   edison_ftrain_bn_get / _set  gamma, beta, moving mean and variance [out_c] of a BatchNorm record (NULL: not wanted / unchanged);
+ *                           _set refolds; a variance <= -eps is EDISON_E_ARGUMENT
+ *   edison_ftrain_bn_batch_get   the last training call's batch mean and variance [out_c]
+ *   edison_ftrain_bn_grad_get    the last training call's dgamma, dbeta [out_c]
+ */
+#define EDISON_FTRAIN_BN_UNBIASED 1u
+int edison_ftrain_set_batchnorm(edison_ftrain *t, const uint8_t *has_bn, int n_records, double momentum, double eps, int64_t max_rows, uint32_t flags);
+int edison_ftrain_batchnorm_get(edison_ftrain *t, uint8_t *has_bn, double *momentum, double *eps, int64_t *max_rows, uint32_t *flags, int32_t *batch);
+int edison_ftrain_bn_get(edison_ftrain *t, int record, float *gamma, float *beta, float *mean, float *var);
+int edison_ftrain_bn_set(edison_ftrain *t, int record, const float *gamma, const float *beta, const float *mean, const float *var);
+int edison_ftrain_bn_batch_get(edison_ftrain *t, int record, float *mean, float *var);
+int edison_ftrain_bn_grad_get(edison_ftrain *t, int record, float *dgamma, float *dbeta);
+int edison_ftrain_folded_get(edison_ftrain *t, float *packed);
 
 /*
  * Exact KWS mode (off by default; EDISON_KWS_EXACT=1 in the environment at edison_init turns it on for that context).

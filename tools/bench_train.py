@@ -9,11 +9,17 @@ samples per second, its minimum and maximum. The learning rate is 0, so the weig
 
     python tools/bench_train.py [--net FILE.ednf] [--batches 100,4096] [--repeats 7] [--region-ms 300] [--out FILE.json]
                                 [--dropout 0,0,0.2,0.3,0 | --dropout-arch kws_conv] [--dropout-before-pool 0,1,..]
+                                [--batchnorm [1,1,1,1,0]]
 
 --net: another float network than the shipped one, 'same' convs and pools included (the trainer is created with padded=True; on a
 network without pads that is the plain trainer).
 
 --dropout: the training leg runs with these Dropout rates per conv / dense record, a new mask every call.
+
+--batchnorm: the training leg runs with BatchNorm behind these records (without a value: kws_conv's
+1,1,1,1,0), on the network's geometry with its loaded weights as the starting master weights; the forward leg then runs the folded
+network. "launches" is the number of kernel launches of one training call plus one step (the fold included), which depends on the
+records and not on the batch.
 
 One JSON line.
 """
@@ -29,6 +35,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def dropout_on(spec):
+    return [(s[0] if isinstance(s, (tuple, list)) else s) > 0 for s in spec]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--net", default=os.path.join(ROOT, "tests", "golden", "cube_kws.ednf"))
@@ -39,6 +49,7 @@ def main():
     ap.add_argument("--dropout")
     ap.add_argument("--dropout-before-pool")
     ap.add_argument("--dropout-arch")
+    ap.add_argument("--batchnorm", nargs="?", const="1,1,1,1,0")
     args = ap.parse_args()
     import torch
     from edison_amd.context import Context
@@ -55,11 +66,20 @@ def main():
     dropout = train.KERAS_DROPOUT[args.dropout_arch] if args.dropout_arch else [float(v) for v in args.dropout.split(",")] if args.dropout else None
     if dropout is not None:
         tr.set_dropout(dropout, [int(v) for v in args.dropout_before_pool.split(",")] if args.dropout_before_pool else None, seed=19)
+    batches = [int(b) for b in args.batches.split(",")]
+    launches = 3                                            # the gradient kernel, the slab reduce, the step
+    if args.batchnorm:
+        has_bn = [int(v) for v in args.batchnorm.split(",")]
+        tr.set_batchnorm(has_bn, max_rows=max(batches))
+        n_bn, nl = sum(has_bn), len(has_bn)
+        # keys (with dropout), per record conv + apply and the backward launch, per BatchNorm record stats + two for dy's sums, the loss,
+        # the slab reduce, two steps (weights; gamma and beta) and the fold
+        launches = (1 if dropout is not None and any(dropout_on(dropout)) else 0) + 3 * nl + 3 * n_bn + 1 + 1 + 2 + 1
     tinfo = tr.info()
     rng = np.random.default_rng(19)
     row = dict(network=os.path.basename(args.net), device=torch.cuda.get_device_name(0), train_batch=tinfo["batch"], grid=tinfo["grid"], lds_bytes=tinfo["lds_bytes"],
-               w_floats=tinfo["w_floats"], dropout=tr.dropout()["rates"], dropout_before_pool=tr.dropout()["before_pool"], repeats=args.repeats, region_ms=args.region_ms, results=[])
-    for n in [int(b) for b in args.batches.split(",")]:
+               w_floats=tinfo["w_floats"], dropout=tr.dropout()["rates"], dropout_before_pool=tr.dropout()["before_pool"], batchnorm=tr.batchnorm()["has_bn"], bn_batch=tr.batchnorm()["batch"], launches=launches, repeats=args.repeats, region_ms=args.region_ms, results=[])
+    for n in batches:
         x = torch.from_numpy(rng.normal(0, 30, (n, in_n)).astype(np.float32)).to(dev)
         y = torch.from_numpy((np.arange(n) % n_out).astype(np.int32)).to(dev)
         loss = torch.zeros(n, dtype=torch.float32, device=dev)
