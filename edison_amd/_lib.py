@@ -63,6 +63,11 @@ class FtrainInfo(ctypes.Structure):
                [(k, c_int64) for k in ("w_floats", "steps", "ignored")]
 
 
+class FtrainEpoch(ctypes.Structure):
+    """edison_ftrain_epoch_t"""
+    _fields_ = [("loss_sum", c_double)] + [(k, c_int64) for k in ("hits", "seen", "steps")]
+
+
 class StreamGeomOpts(ctypes.Structure):
     """edison_stream_geom_opts"""
     _fields_ = [("chunk_frames", ctypes.c_int32), ("filter", ctypes.c_int32), ("fsm", ctypes.c_int32), ("filter_alpha", c_double),
@@ -329,6 +334,16 @@ SIGNATURES = {
     "edison_ftrain_bn_batch_get": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "edison_ftrain_bn_grad_get": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "edison_ftrain_folded_get": (c_int, [c_void_p, c_void_p]),
+    "edison_ftrain_data_create": (c_int, [c_void_p, ctypes.c_int32, ctypes.POINTER(c_void_p)]),
+    "edison_ftrain_data_destroy": (None, [c_void_p]),
+    "edison_ftrain_data_info": (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(ctypes.c_int32)]),
+    "edison_ftrain_data_set": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
+    "edison_ftrain_data_set_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
+    "edison_ftrain_data_get": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "edison_ftrain_data_audio": (c_int, [c_void_p, ctypes.POINTER(KwsGeom), c_int, c_float, c_float, c_void_p, c_int64, c_int64, c_void_p, c_int64]),
+    "edison_ftrain_epoch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_double, c_int64, ctypes.POINTER(FtrainEpoch)]),
+    "edison_ftrain_data_eval": (c_int, [c_void_p, c_void_p, ctypes.POINTER(FtrainEpoch)]),
+    "edison_ftrain_epoch_rows": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64)]),
     "edison_eval_default_opts": (None, [ctypes.POINTER(EvalOpts)]),
     "edison_eval_create": (c_int, [c_void_p, ctypes.POINTER(EvalOpts), ctypes.POINTER(c_void_p)]),
     "edison_eval_destroy": (None, [c_void_p]),

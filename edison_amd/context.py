@@ -6,6 +6,7 @@ computation is a hand-written HIP kernel behind the C-ABI).
 """
 import contextlib
 import ctypes
+import weakref
 
 import numpy as np
 
@@ -35,6 +36,7 @@ class Context:
         self.device = int(device)
         self._fnet_blob = None
         self._fnet_trainer = None   # a train.Trainer whose steps _fnet_blob does not hold yet
+        self._train_data = weakref.WeakSet()   # train.DeviceData on this context: device memory that goes before the context does
         if model_path is not None:
             self.load_model(model_path)
 
@@ -47,6 +49,8 @@ class Context:
         if getattr(self, "_h", None):
             if getattr(self, "_fnet_trainer", None) is not None:   # it refers to this context: closed before the context goes
                 self._fnet_trainer.close()
+            for d in list(getattr(self, "_train_data", ())):
+                d.close()
             self._L.edison_shutdown(self._h)
             self._h = None
 
@@ -574,6 +578,35 @@ class Context:
         steps change the loaded network's device weights in place."""
         from . import train
         return train.Trainer(self, padded=padded, dropout=dropout, seed=seed, batchnorm=batchnorm)
+
+    def train_data(self, x=None, y=None, audio=None, geometry=None, q15=False, clip_min=None, clip_max=None, chunk=16384):
+        """A train.DeviceData on this context: a data set in device memory for Trainer.fit_data (edison_ftrain_data_*). Either rows x
+        [n][in_n] (any shape with n first) and class indices y, uploaded once; or audio int16 [n][samples] and y, whose float-flow
+        features (kws_float's geometry, q15 and clip arguments) are computed on the device, `chunk` utterances at a time, straight into
+        the set. It has n, in_n, rows() and close(), is a context manager, and outlives trainers and network loads."""
+        from . import train
+        if y is None or (x is None) == (audio is None):
+            raise ValueError("train_data takes y and one of x, audio")
+        if audio is None:
+            f = np.asarray(x)
+            if f.ndim < 2 or f.shape[0] == 0:
+                raise ValueError("x is [n][in_n] with n > 0")
+            d = train.DeviceData(self, int(np.prod(f.shape[1:])))
+        else:
+            from . import config as cfg
+            from .kws.geometry import KwsGeometry
+            if geometry is None:
+                geometry = KwsGeometry.from_config(net_input_scale=cfg.net_input_scale)
+            d = train.DeviceData(self, geometry.n_features)
+        try:
+            if audio is None:
+                d.set(x, y)
+            else:
+                d.set_audio(audio, y, geometry=geometry, q15=q15, clip_min=clip_min, clip_max=clip_max, chunk=chunk)
+        except Exception:
+            d.close()
+            raise
+        return d
 
     def _fnet_refresh(self):
         """Bring _fnet_blob up to the weights a trainer has stepped the loaded network to (quantize() reads the weights from it)."""

@@ -182,6 +182,10 @@ int ed_geom_tables_build(edison_ctx *ctx, const edison_kws_geom *g, ed_geom_cach
 /* edison_fnet.hip, shared with edison_float_bank.hip: the checks of edison_kws_float_batch for geometry g, flow q15 and the clip
  * range, the loaded float network's input size included (*frames = frames per window). */
 int ed_kws_float_geom_check(edison_ctx *ctx, const edison_kws_geom *g, int q15, float clip_lo, float clip_hi, int *frames);
+/* edison_fnet.hip, for edison_ftrain.hip's data sets: the same checks without a loaded network (frame_count x num_mfcc != in_n is
+ * EDISON_E_SIZE), then edison_kws_float_batch_dev's feature launches on device audio into feat [n_utt][in_n] (NULL: the checks only). */
+int ed_kws_float_features_dev(edison_ctx *ctx, const edison_kws_geom *g, int q15, float clip_lo, float clip_hi, const int16_t *audio, int64_t n_utt,
+                              int64_t utt_stride, int in_n, float *feat, int *frames);
 
 /* The loaded model on 31x13x1 -> 10 features (the geometry of every kws / stream entry point): matrix-core kernel for
  * the kws_conv graph, the general kernel for any other graph of that shape. feat_stride = bytes between utterances. */

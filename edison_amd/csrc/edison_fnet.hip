@@ -329,8 +329,9 @@ extern "C" int edison_fnet_layers(edison_ctx *ctx, const float *in, int64_t n, f
 }
 
 /* ---- audio -> class with the float network (edison_kws_float_batch*) ---------------------------------------------------------- */
-static int kws_float_check(edison_ctx *ctx, const edison_kws_geom *g, int q15, float lo, float hi, const int16_t *audio, int64_t n_utt,
-                           int64_t utt_stride, int *frames)
+/* everything of kws_float_check that does not need the loaded network: the arguments, the flow and the geometry (*frames = frames per utterance) */
+static int kws_float_geom(edison_ctx *ctx, const edison_kws_geom *g, int q15, float lo, float hi, const int16_t *audio, int64_t n_utt,
+                          int64_t utt_stride, int *frames)
 {
 	if (!ctx || !g || n_utt < 0 || (!audio && n_utt > 0) || (q15 != 0 && q15 != 1)) return EDISON_E_ARGUMENT;
 	if (utt_stride < 0) return ed_set_err(ctx, EDISON_E_ARGUMENT, "negative utterance stride");
@@ -352,6 +353,13 @@ static int kws_float_check(edison_ctx *ctx, const edison_kws_geom *g, int q15, f
 		const int r = ed_kws_geom_check(ctx, g, frames);
 		if (r != EDISON_OK) return r;
 	}
+	return EDISON_OK;
+}
+
+static int kws_float_check(edison_ctx *ctx, const edison_kws_geom *g, int q15, float lo, float hi, const int16_t *audio, int64_t n_utt,
+                           int64_t utt_stride, int *frames)
+{
+	{ const int r = kws_float_geom(ctx, g, q15, lo, hi, audio, n_utt, utt_stride, frames); if (r != EDISON_OK) return r; }
 	if (!ctx->fnet) return ed_set_err(ctx, EDISON_E_NO_MODEL, "no float network loaded (edison_fnet_load)");
 	const int64_t n_feat = (int64_t)*frames * g->num_mfcc;
 	if (n_feat != ctx->fnet->plan.in_n)
@@ -369,14 +377,13 @@ int ed_kws_float_geom_check(edison_ctx *ctx, const edison_kws_geom *g, int q15, 
 	return kws_float_check(ctx, g, q15, clip_lo, clip_hi, NULL, 0, 0, frames);
 }
 
-extern "C" int edison_kws_float_batch_dev(edison_ctx *ctx, const edison_kws_geom *g, int q15, float clip_lo, float clip_hi, const int16_t *audio,
-                                          int64_t n_utt, int64_t utt_stride, float *feat, float *logits, float *probs, int32_t *argmax)
+/* The feature launches of edison_kws_float_batch*: n_utt utterances (F frames each, checked) -> in_n = F x num_mfcc floats a row in feat, or in
+ * the context's scratch when feat is NULL; *out = where they are. */
+static int kws_float_features(edison_ctx *ctx, const edison_kws_geom *g, int q15, float clip_lo, float clip_hi, const int16_t *audio, int64_t n_utt,
+                              int64_t utt_stride, int F, int in_n, float *feat, float **out)
 {
-	int F = 0;
-	{ const int r = kws_float_check(ctx, g, q15, clip_lo, clip_hi, audio, n_utt, utt_stride, &F); if (r != EDISON_OK) return r; }
-	if (n_utt == 0) return EDISON_OK;
 	ED_HIP(ctx, hipSetDevice(ctx->device));
-	const size_t n_feat = (size_t)n_utt * (size_t)ctx->fnet->plan.in_n;
+	const size_t n_feat = (size_t)n_utt * (size_t)in_n;
 	/* scratch: [the float64 MFCC (host flow)] then [the float features when the caller passes none] */
 	const size_t y_bytes = q15 ? 0 : sizeof(double) * n_feat, f_bytes = feat ? 0 : sizeof(float) * n_feat;
 	if (y_bytes + f_bytes)
@@ -384,7 +391,7 @@ extern "C" int edison_kws_float_batch_dev(edison_ctx *ctx, const edison_kws_geom
 		const int r = ed_ctx_ensure_scratch(ctx, y_bytes + f_bytes);
 		if (r != EDISON_OK) return r;
 	}
-	float *f = feat ? feat : (float *)((char *)ctx->scratch + y_bytes);
+	float *const f = feat ? feat : (float *)((char *)ctx->scratch + y_bytes);
 	if (q15)
 	{
 		/* variant C int16 -> (float), no scale, no clip (app.c:675-683): the Q15 kernel's float output */
@@ -399,6 +406,37 @@ extern "C" int edison_kws_float_batch_dev(edison_ctx *ctx, const edison_kws_geom
 		const int e = ed_launch_fnet_input(y, (int64_t)n_feat, (float)g->net_input_scale, clip_lo, clip_hi, f, ctx->n_cu, ctx->stream);
 		if (e != 0) return ed_launch_result(ctx, e, "float network input");
 	}
+	*out = f;
+	return EDISON_OK;
+}
+
+/* edison_ftrain.hip's edison_ftrain_data_audio: kws_float's checks without the loaded network, then its feature launches into feat [n_utt][in_n] */
+int ed_kws_float_features_dev(edison_ctx *ctx, const edison_kws_geom *g, int q15, float clip_lo, float clip_hi, const int16_t *audio, int64_t n_utt,
+                              int64_t utt_stride, int in_n, float *feat, int *frames)
+{
+	int F = 0;
+	{ const int r = kws_float_geom(ctx, g, q15, clip_lo, clip_hi, audio, n_utt, utt_stride, &F); if (r != EDISON_OK) return r; }
+	if (frames) *frames = F;
+	if ((int64_t)F * g->num_mfcc != in_n)
+	{
+		snprintf(ctx->err, sizeof(ctx->err), "edison_ftrain_data_audio: frame_count x num_mfcc = %lld features, the data set's rows have %d",
+		         (long long)F * g->num_mfcc, in_n);
+		return EDISON_E_SIZE;
+	}
+	if (n_utt * (int64_t)F >= ((int64_t)1 << 31)) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_kws_float: more than 2^31 frames in one call");
+	if (n_utt == 0 || !feat) return EDISON_OK;
+	float *f = NULL;
+	return kws_float_features(ctx, g, q15, clip_lo, clip_hi, audio, n_utt, utt_stride, F, in_n, feat, &f);
+}
+
+extern "C" int edison_kws_float_batch_dev(edison_ctx *ctx, const edison_kws_geom *g, int q15, float clip_lo, float clip_hi, const int16_t *audio,
+                                          int64_t n_utt, int64_t utt_stride, float *feat, float *logits, float *probs, int32_t *argmax)
+{
+	int F = 0;
+	{ const int r = kws_float_check(ctx, g, q15, clip_lo, clip_hi, audio, n_utt, utt_stride, &F); if (r != EDISON_OK) return r; }
+	if (n_utt == 0) return EDISON_OK;
+	float *f = NULL;
+	{ const int r = kws_float_features(ctx, g, q15, clip_lo, clip_hi, audio, n_utt, utt_stride, F, ctx->fnet->plan.in_n, feat, &f); if (r != EDISON_OK) return r; }
 	return run_on(ctx, f, n_utt, logits, probs, argmax, NULL);
 }
 

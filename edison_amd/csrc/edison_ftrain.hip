@@ -11,15 +11,20 @@
  * section 19c) turns the trainer into one that owns master weights, gamma, beta and moving statistics: a training call is the chain of
  * launches of fnet_bn_kernels.hip over stores sized for max_rows rows, and after every change a fold kernel rewrites the loaded
  * network's device buffer with the inference-mode network, which is what every other entry point, an EVAL call included, runs.
+ * Data sets on the device (edison_ftrain_data_*) belong to the context; edison_ftrain_epoch gathers an epoch's rows
+ * out of one into the trainer's epoch store and queues the gradient call and the step of every batch behind it, edison_ftrain_data_eval
+ * runs one through EVAL calls; both end in one reduction (fnet_data_kernels.hip), one copy back and one synchronisation.
  */
 #include <math.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <new>
 #include <vector>
 
 #include "edison_ctx.h"
 #include "fnet_bn.h"
+#include "fnet_data.h"
 #include "fnet_dropout.h"
 #include "fnet_train.h"
 
@@ -53,6 +58,24 @@ struct edison_ftrain
 	ed_fbn_plan_t bplan, *d_bplan;
 	float *d_master, *d_bn, *d_bn_m, *d_bn_v;
 	int32_t *d_rtab, *d_binv;
+	/* Adadelta's constants (EDISON_FTRAIN_ADADELTA): d_m is its average of g g, d_v its average of u u */
+	double rho, ad_eps;
+	/* the epoch store (edison_ftrain_epoch / edison_ftrain_data_eval): per row of the last such call its loss and argmax, and for an epoch
+	 * the order, the gathered labels (all [e_cap]) and the gathered rows [ex_cap][in_n]; e_n rows of the last call */
+	float *d_ex, *d_eloss;
+	int32_t *d_ey, *d_eam, *d_eorder;
+	ed_fdata_sums_t *d_esums;
+	int64_t e_cap, ex_cap, e_n;
+};
+
+struct edison_ftrain_data
+{
+	edison_ctx *ctx;
+	int32_t in_n;
+	int64_t n, cap;
+	float *d_x;    /* [cap][in_n] */
+	int32_t *d_y;  /* [cap]       */
+	std::vector<int32_t> y; /* the labels on the host: an epoch call checks them against the network's n_out before any launch */
 };
 
 #define EDBN_DEFAULT_ROWS 1024
@@ -106,6 +129,7 @@ extern "C" int edison_ftrain_create_ex(edison_ctx *ctx, uint32_t flags, edison_f
 	t->epoch = ctx->fnet_epoch;
 	t->kind = EDISON_FTRAIN_ADAM;
 	t->b1 = 0.9; t->b2 = 0.999; t->eps = 1e-7;
+	t->rho = 0.95; t->ad_eps = 1e-7;
 	ed_ftrain_plan_t &tp = t->plan;
 	tp.net = *net;
 	const ed_fnet_layer_t &last = net->L[net->n_layers - 1];
@@ -205,7 +229,7 @@ extern "C" void edison_ftrain_destroy(edison_ftrain *t)
 	(void)hipStreamSynchronize(t->ctx->stream); /* a gradient call or a step may still be queued */
 	void *bufs[] = {t->d_plan, t->d_inv, t->plan.slabs, t->plan.acts, t->plan.dacts, t->plan.mask, t->plan.keys, t->d_grad, t->d_m, t->d_v, t->d_logits, t->d_ignored,
 	                t->d_bplan, t->d_master, t->d_bn, t->d_bn_m, t->d_bn_v, t->d_rtab, t->d_binv, t->bplan.zs, t->bplan.outs, t->bplan.douts, t->bplan.mask,
-	                t->bplan.part, t->bplan.keys};
+	                t->bplan.part, t->bplan.keys, t->d_ex, t->d_eloss, t->d_ey, t->d_eam, t->d_eorder, t->d_esums};
 	for (void *b : bufs)
 		if (b) (void)hipFree(b);
 	delete t;
@@ -447,11 +471,15 @@ extern "C" int edison_ftrain_weights_set(edison_ftrain *t, const float *packed)
 extern "C" int edison_ftrain_set_opt(edison_ftrain *t, int kind, double b1, double b2, double eps)
 {
 	{ const int r = ftrain_live(t, "edison_ftrain_set_opt"); if (r != EDISON_OK) return r; }
-	if (kind != EDISON_FTRAIN_ADAM && kind != EDISON_FTRAIN_SGD) return ed_set_err(t->ctx, EDISON_E_ARGUMENT, "edison_ftrain_set_opt: kind is not Adam or SGD");
+	if (kind != EDISON_FTRAIN_ADAM && kind != EDISON_FTRAIN_SGD && kind != EDISON_FTRAIN_ADADELTA)
+		return ed_set_err(t->ctx, EDISON_E_ARGUMENT, "edison_ftrain_set_opt: kind is not Adam, SGD or Adadelta");
+	if (kind == EDISON_FTRAIN_ADADELTA && !(b1 >= 0.0 && b1 < 1.0 && eps > 0.0 && isfinite(eps)))
+		return ed_set_err(t->ctx, EDISON_E_ARGUMENT, "edison_ftrain_set_opt: Adadelta takes rho (b1) in [0, 1) and a finite eps > 0");
 	if (kind == EDISON_FTRAIN_ADAM && !(b1 >= 0.0 && b1 < 1.0 && b2 >= 0.0 && b2 < 1.0 && eps > 0.0))
 		return ed_set_err(t->ctx, EDISON_E_ARGUMENT, "edison_ftrain_set_opt: Adam takes b1 and b2 in [0, 1) and eps > 0");
 	t->kind = kind;
 	if (kind == EDISON_FTRAIN_ADAM) { t->b1 = b1; t->b2 = b2; t->eps = eps; }
+	if (kind == EDISON_FTRAIN_ADADELTA) { t->rho = b1; t->ad_eps = eps; }
 	return EDISON_OK;
 }
 
@@ -462,13 +490,25 @@ extern "C" int edison_ftrain_step(edison_ftrain *t, double lr)
 	if (!(lr >= 0.0) || !isfinite(lr)) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_step: the learning rate is negative or not finite");
 	if (t->grad_stale) return ftrain_stale(t, "edison_ftrain_step");
 	ED_HIP(ctx, hipSetDevice(ctx->device));
-	const double tt = (double)(t->steps + 1);
-	const double factor = t->kind == EDISON_FTRAIN_SGD ? lr : lr * sqrt(1.0 - pow(t->b2, tt)) / (1.0 - pow(t->b1, tt));
-	int e = ed_launch_ftrain_step(t->kind, t->bn_on ? t->d_master : ftrain_w(t), t->d_grad, t->d_m, t->d_v, t->plan.w_floats, (float)factor, (float)t->b1,
-	                              (float)(1.0 - t->b1), (float)t->b2, (float)(1.0 - t->b2), (float)t->eps, ctx->n_cu, ctx->stream);
-	if (e == 0 && t->bn_on) /* gamma and beta: the same optimiser, moments of their own; channels of records without BatchNorm have gradient 0 */
-		e = ed_launch_ftrain_step(t->kind, t->bplan.bnp, t->bplan.bng, t->d_bn_m, t->d_bn_v, 2 * (int64_t)t->bplan.bn_n, (float)factor, (float)t->b1,
-		                          (float)(1.0 - t->b1), (float)t->b2, (float)(1.0 - t->b2), (float)t->eps, ctx->n_cu, ctx->stream);
+	int e;
+	if (t->kind == EDISON_FTRAIN_ADADELTA)
+	{
+		/* a kernel of its own (fnet_data_kernels.hip) on the same two moment arrays; gamma and beta as the other kinds step them */
+		const float rho = (float)t->rho, omr = (float)(1.0 - t->rho), eps = (float)t->ad_eps;
+		e = ed_launch_ftrain_adadelta(t->bn_on ? t->d_master : ftrain_w(t), t->d_grad, t->d_m, t->d_v, t->plan.w_floats, (float)lr, rho, omr, eps, ctx->n_cu, ctx->stream);
+		if (e == 0 && t->bn_on)
+			e = ed_launch_ftrain_adadelta(t->bplan.bnp, t->bplan.bng, t->d_bn_m, t->d_bn_v, 2 * (int64_t)t->bplan.bn_n, (float)lr, rho, omr, eps, ctx->n_cu, ctx->stream);
+	}
+	else
+	{
+		const double tt = (double)(t->steps + 1);
+		const double factor = t->kind == EDISON_FTRAIN_SGD ? lr : lr * sqrt(1.0 - pow(t->b2, tt)) / (1.0 - pow(t->b1, tt));
+		e = ed_launch_ftrain_step(t->kind, t->bn_on ? t->d_master : ftrain_w(t), t->d_grad, t->d_m, t->d_v, t->plan.w_floats, (float)factor, (float)t->b1,
+		                              (float)(1.0 - t->b1), (float)t->b2, (float)(1.0 - t->b2), (float)t->eps, ctx->n_cu, ctx->stream);
+		if (e == 0 && t->bn_on) /* gamma and beta: the same optimiser, moments of their own; channels of records without BatchNorm have gradient 0 */
+			e = ed_launch_ftrain_step(t->kind, t->bplan.bnp, t->bplan.bng, t->d_bn_m, t->d_bn_v, 2 * (int64_t)t->bplan.bn_n, (float)factor, (float)t->b1,
+			                          (float)(1.0 - t->b1), (float)t->b2, (float)(1.0 - t->b2), (float)t->eps, ctx->n_cu, ctx->stream);
+	}
 	if (e == 0) t->steps++;
 	{ const int r = ed_launch_result(ctx, e, "optimiser step kernel"); if (r != EDISON_OK || !t->bn_on) return r; }
 	return ftrain_fold(t);
@@ -728,4 +768,331 @@ extern "C" int edison_ftrain_folded_get(edison_ftrain *t, float *packed)
 {
 	if (!t) return EDISON_E_ARGUMENT;
 	return ftrain_copy(t, "edison_ftrain_folded_get", packed, t->plan.net.w, sizeof(float) * (size_t)t->plan.w_floats, hipMemcpyDeviceToHost);
+}
+
+/* ---- data sets on the device and whole epochs ---- */
+extern "C" int edison_ftrain_data_create(edison_ctx *ctx, int32_t in_n, edison_ftrain_data **out)
+{
+	if (!ctx || !out) return EDISON_E_ARGUMENT;
+	*out = NULL;
+	if (in_n < 1) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_data_create: in_n is below 1");
+	edison_ftrain_data *d = new (std::nothrow) edison_ftrain_data();
+	if (!d) return ed_set_err(ctx, EDISON_E_NO_MEMORY, "edison_ftrain_data_create: out of host memory");
+	d->ctx = ctx;
+	d->in_n = in_n;
+	*out = d;
+	return EDISON_OK;
+}
+
+extern "C" void edison_ftrain_data_destroy(edison_ftrain_data *d)
+{
+	if (!d) return;
+	(void)hipSetDevice(d->ctx->device);
+	(void)hipStreamSynchronize(d->ctx->stream); /* an epoch's gather may still be queued */
+	if (d->d_x) (void)hipFree(d->d_x);
+	if (d->d_y) (void)hipFree(d->d_y);
+	delete d;
+}
+
+extern "C" int edison_ftrain_data_info(edison_ftrain_data *d, int64_t *n, int32_t *in_n)
+{
+	if (!d) return EDISON_E_ARGUMENT;
+	if (n) *n = d->n;
+	if (in_n) *in_n = d->in_n;
+	return EDISON_OK;
+}
+
+/* room for n rows; the contents are lost when it grows */
+static int fdata_reserve(edison_ftrain_data *d, const char *who, int64_t n)
+{
+	edison_ctx *ctx = d->ctx;
+	if (n > ((int64_t)1 << 31) - 1)
+	{
+		snprintf(ctx->err, sizeof(ctx->err), "%s: more than 2^31 - 1 rows", who);
+		return EDISON_E_SIZE;
+	}
+	ED_HIP(ctx, hipSetDevice(ctx->device));
+	if (n <= d->cap) return EDISON_OK;
+	ED_HIP(ctx, hipStreamSynchronize(ctx->stream)); /* a queued launch may still read the old arrays */
+	if (d->d_x) (void)hipFree(d->d_x);
+	if (d->d_y) (void)hipFree(d->d_y);
+	d->d_x = NULL; d->d_y = NULL;
+	d->cap = 0; d->n = 0;
+	hipError_t e = hipMalloc((void **)&d->d_x, sizeof(float) * (size_t)n * (size_t)d->in_n);
+	if (e == hipSuccess) e = hipMalloc((void **)&d->d_y, sizeof(int32_t) * (size_t)n);
+	if (e != hipSuccess)
+	{
+		if (d->d_x) (void)hipFree(d->d_x);
+		d->d_x = NULL;
+		snprintf(ctx->err, sizeof(ctx->err), "%s: cannot allocate %lld rows of %d floats", who, (long long)n, d->in_n);
+		return e == hipErrorOutOfMemory ? EDISON_E_NO_MEMORY : EDISON_E_RUNTIME;
+	}
+	d->cap = n;
+	return EDISON_OK;
+}
+
+static int fdata_labels_ok(edison_ctx *ctx, const char *who, const int32_t *y, int64_t n)
+{
+	for (int64_t i = 0; i < n; i++)
+		if (y[i] < 0)
+		{
+			snprintf(ctx->err, sizeof(ctx->err), "%s: label %d of row %lld is negative", who, y[i], (long long)i);
+			return EDISON_E_ARGUMENT;
+		}
+	return EDISON_OK;
+}
+
+static int fdata_set(edison_ftrain_data *d, const char *who, const float *x, const int32_t *y, int64_t n, bool dev)
+{
+	if (!d) return EDISON_E_ARGUMENT;
+	edison_ctx *ctx = d->ctx;
+	if (n < 0 || (n > 0 && (!x || !y))) { snprintf(ctx->err, sizeof(ctx->err), "%s: negative n, or NULL rows or labels", who); return EDISON_E_ARGUMENT; }
+	ED_HIP(ctx, hipSetDevice(ctx->device));
+	std::vector<int32_t> lab;
+	try { lab.resize((size_t)n); } catch (...) { return ed_set_err(ctx, EDISON_E_NO_MEMORY, "edison_ftrain_data_set: out of host memory"); }
+	if (n && dev)
+	{
+		ED_HIP(ctx, hipMemcpyAsync(lab.data(), y, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+		ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	}
+	else if (n) memcpy(lab.data(), y, sizeof(int32_t) * (size_t)n);
+	{ const int r = fdata_labels_ok(ctx, who, lab.data(), n); if (r != EDISON_OK) return r; }
+	{ const int r = fdata_reserve(d, who, n); if (r != EDISON_OK) return r; }
+	d->n = 0;
+	if (n)
+	{
+		const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+		ED_HIP(ctx, hipMemcpyAsync(d->d_x, x, sizeof(float) * (size_t)n * (size_t)d->in_n, kind, ctx->stream));
+		ED_HIP(ctx, hipMemcpyAsync(d->d_y, lab.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+		ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	}
+	d->y.swap(lab);
+	d->n = n;
+	return EDISON_OK;
+}
+
+extern "C" int edison_ftrain_data_set(edison_ftrain_data *d, const float *x, const int32_t *y, int64_t n) { return fdata_set(d, "edison_ftrain_data_set", x, y, n, false); }
+
+extern "C" int edison_ftrain_data_set_dev(edison_ftrain_data *d, const float *x, const int32_t *y, int64_t n)
+{
+	return fdata_set(d, "edison_ftrain_data_set_dev", x, y, n, true);
+}
+
+extern "C" int edison_ftrain_data_get(edison_ftrain_data *d, float *x, int32_t *y)
+{
+	if (!d) return EDISON_E_ARGUMENT;
+	edison_ctx *ctx = d->ctx;
+	ED_HIP(ctx, hipSetDevice(ctx->device));
+	if (x && d->n) ED_HIP(ctx, hipMemcpyAsync(x, d->d_x, sizeof(float) * (size_t)d->n * (size_t)d->in_n, hipMemcpyDeviceToHost, ctx->stream));
+	if (y && d->n) ED_HIP(ctx, hipMemcpyAsync(y, d->d_y, sizeof(int32_t) * (size_t)d->n, hipMemcpyDeviceToHost, ctx->stream));
+	ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return EDISON_OK;
+}
+
+extern "C" int edison_ftrain_data_audio(edison_ftrain_data *d, const edison_kws_geom *g, int q15, float clip_lo, float clip_hi, const int16_t *audio, int64_t n_utt,
+                                        int64_t utt_stride, const int32_t *labels, int64_t chunk)
+{
+	if (!d) return EDISON_E_ARGUMENT;
+	edison_ctx *ctx = d->ctx;
+	const char *who = "edison_ftrain_data_audio";
+	if (!g) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_data_audio: NULL geometry");
+	if (chunk < 1) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_data_audio: chunk is below 1");
+	if (n_utt > 0 && !labels) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_data_audio: NULL labels");
+	int F = 0;
+	/* the checks of edison_kws_float_batch without its network, and the row size; audio is only looked at for NULL here */
+	{ const int r = ed_kws_float_features_dev(ctx, g, q15, clip_lo, clip_hi, audio, n_utt, utt_stride, d->in_n, NULL, &F); if (r != EDISON_OK) return r; }
+	{ const int r = fdata_labels_ok(ctx, who, labels, n_utt); if (r != EDISON_OK) return r; }
+	std::vector<int32_t> lab;
+	try { lab.assign(labels, labels + (n_utt > 0 ? n_utt : 0)); } catch (...) { return ed_set_err(ctx, EDISON_E_NO_MEMORY, "edison_ftrain_data_audio: out of host memory"); }
+	{ const int r = fdata_reserve(d, who, n_utt); if (r != EDISON_OK) return r; }
+	d->n = 0;
+	if (n_utt == 0) { d->y.clear(); return EDISON_OK; }
+	const int64_t per = chunk < n_utt ? chunk : n_utt, used = (int64_t)(F - 1) * g->frame_step + g->frame_len;
+	const unsigned __int128 na = (unsigned __int128)(per - 1) * (unsigned __int128)utt_stride + (unsigned __int128)used;
+	if (na * sizeof(int16_t) > ((unsigned __int128)1 << 47)) return ed_set_err(ctx, EDISON_E_SIZE, "edison_ftrain_data_audio: utt_stride x chunk too large");
+	ed_dev_buf au;
+	if (au.alloc((size_t)na * sizeof(int16_t)) != hipSuccess) return ed_set_err(ctx, EDISON_E_NO_MEMORY, "edison_ftrain_data_audio: cannot allocate a chunk of audio");
+	int r = EDISON_OK;
+	for (int64_t u0 = 0; u0 < n_utt && r == EDISON_OK; u0 += per)
+	{
+		const int64_t m = n_utt - u0 < per ? n_utt - u0 : per;
+		/* the copy waits in stream order for the feature launch of the chunk before it, which reads the same buffer */
+		const hipError_t e = hipMemcpyAsync(au.p, audio + u0 * utt_stride, sizeof(int16_t) * (size_t)((m - 1) * utt_stride + used), hipMemcpyHostToDevice, ctx->stream);
+		if (e != hipSuccess) { r = ed_set_err(ctx, EDISON_E_RUNTIME, "edison_ftrain_data_audio: the audio upload failed"); break; }
+		r = ed_kws_float_features_dev(ctx, g, q15, clip_lo, clip_hi, (const int16_t *)au.p, m, utt_stride, d->in_n, d->d_x + u0 * (int64_t)d->in_n, NULL);
+	}
+	if (r == EDISON_OK && hipMemcpyAsync(d->d_y, lab.data(), sizeof(int32_t) * (size_t)n_utt, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+		r = ed_set_err(ctx, EDISON_E_RUNTIME, "edison_ftrain_data_audio: the label upload failed");
+	if (hipStreamSynchronize(ctx->stream) != hipSuccess && r == EDISON_OK) r = ed_set_err(ctx, EDISON_E_RUNTIME, "edison_ftrain_data_audio: hipStreamSynchronize failed");
+	if (r != EDISON_OK) return r; /* the set stays empty */
+	d->y.swap(lab);
+	d->n = n_utt;
+	return EDISON_OK;
+}
+
+/* room for `rows` rows of loss, argmax, order and labels, and for `xrows` gathered rows */
+static int ftrain_epoch_reserve(edison_ftrain *t, int64_t rows, int64_t xrows)
+{
+	edison_ctx *ctx = t->ctx;
+	if (!t->d_esums && hipMalloc((void **)&t->d_esums, sizeof(ed_fdata_sums_t)) != hipSuccess)
+		return ed_set_err(ctx, EDISON_E_NO_MEMORY, "edison_ftrain_epoch: cannot allocate the epoch store");
+	if (rows > t->e_cap || xrows > t->ex_cap) ED_HIP(ctx, hipStreamSynchronize(ctx->stream)); /* a queued call may still use the old arrays */
+	if (rows > t->e_cap)
+	{
+		void **bufs[] = {(void **)&t->d_eloss, (void **)&t->d_eam, (void **)&t->d_eorder, (void **)&t->d_ey};
+		t->e_cap = 0; t->e_n = 0;
+		hipError_t e = hipSuccess;
+		for (void **b : bufs)
+		{
+			if (*b) (void)hipFree(*b);
+			*b = NULL;
+			if (e == hipSuccess) e = hipMalloc(b, 4 * (size_t)rows);
+		}
+		if (e != hipSuccess) return ed_set_err(ctx, EDISON_E_NO_MEMORY, "edison_ftrain_epoch: cannot allocate the epoch store");
+		t->e_cap = rows;
+	}
+	if (xrows > t->ex_cap)
+	{
+		if (t->d_ex) (void)hipFree(t->d_ex);
+		t->d_ex = NULL;
+		t->ex_cap = 0;
+		if (hipMalloc((void **)&t->d_ex, sizeof(float) * (size_t)xrows * (size_t)t->plan.net.in_n) != hipSuccess)
+			return ed_set_err(ctx, EDISON_E_NO_MEMORY, "edison_ftrain_epoch: cannot allocate the epoch's copy of the rows");
+		t->ex_cap = xrows;
+	}
+	return EDISON_OK;
+}
+
+/* the checks an epoch and an eval share: a live trainer, a data set of this context and of the network's input size */
+static int ftrain_data_ok(edison_ftrain *t, edison_ftrain_data *d, const char *who)
+{
+	{ const int r = ftrain_live(t, who); if (r != EDISON_OK) return r; }
+	edison_ctx *ctx = t->ctx;
+	if (!d || d->ctx != ctx) { snprintf(ctx->err, sizeof(ctx->err), "%s: NULL data set, or one of another context", who); return EDISON_E_ARGUMENT; }
+	if (d->in_n != t->plan.net.in_n)
+	{
+		snprintf(ctx->err, sizeof(ctx->err), "%s: the data set's rows have %d floats, the network's input %d", who, d->in_n, t->plan.net.in_n);
+		return EDISON_E_SIZE;
+	}
+	return EDISON_OK;
+}
+
+static int ftrain_label_refused(edison_ftrain *t, const char *who, int32_t label, int64_t row)
+{
+	snprintf(t->ctx->err, sizeof(t->ctx->err), "%s: label %d of the data set's row %lld is outside 0 .. %d", who, label, (long long)row, t->plan.net.n_out - 1);
+	return EDISON_E_ARGUMENT;
+}
+
+/* the reduction over the first n rows of the epoch store against `labels`, one copy back, one synchronisation */
+static int ftrain_epoch_finish(edison_ftrain *t, const int32_t *labels, int64_t n, int64_t steps, edison_ftrain_epoch_t *out)
+{
+	edison_ctx *ctx = t->ctx;
+	ed_fdata_sums_t sums = {0.0, 0};
+	{ const int r = ed_launch_result(ctx, ed_launch_fdata_reduce(t->d_eloss, t->d_eam, labels, n, t->d_esums, ctx->stream), "epoch reduction kernel"); if (r != EDISON_OK) return r; }
+	ED_HIP(ctx, hipMemcpyAsync(&sums, t->d_esums, sizeof(sums), hipMemcpyDeviceToHost, ctx->stream));
+	ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	out->loss_sum = sums.loss_sum;
+	out->hits = sums.hits;
+	out->seen = n;
+	out->steps = steps;
+	return EDISON_OK;
+}
+
+extern "C" int edison_ftrain_epoch(edison_ftrain *t, edison_ftrain_data *d, const int32_t *order, int64_t n_order, int64_t batch, double lr, int64_t max_steps,
+                                   edison_ftrain_epoch_t *out)
+{
+	const char *who = "edison_ftrain_epoch";
+	{ const int r = ftrain_data_ok(t, d, who); if (r != EDISON_OK) return r; }
+	edison_ctx *ctx = t->ctx;
+	if (!out || n_order < 0 || (n_order > 0 && !order)) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_epoch: NULL out or order, or negative n_order");
+	if (batch < 1) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_epoch: batch is below 1");
+	if (!(lr >= 0.0) || !isfinite(lr)) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_epoch: the learning rate is negative or not finite");
+	if (n_order > ((int64_t)1 << 31) - 1) return ed_set_err(ctx, EDISON_E_SIZE, "edison_ftrain_epoch: more than 2^31 - 1 rows in one epoch");
+	if (t->bn_on && batch > t->bplan.max_rows)
+	{
+		snprintf(ctx->err, sizeof(ctx->err), "edison_ftrain_epoch: a training call with BatchNorm takes at most max_rows = %lld rows (edison_ftrain_set_batchnorm), batch is %lld",
+		         (long long)t->bplan.max_rows, (long long)batch);
+		return EDISON_E_ARGUMENT;
+	}
+	int64_t steps = (n_order + batch - 1) / batch; /* the last batch may be short */
+	if (max_steps >= 0 && steps > max_steps) steps = max_steps;
+	const int64_t rows = steps * batch < n_order ? steps * batch : n_order;
+	for (int64_t i = 0; i < rows; i++)
+	{
+		if (order[i] < 0 || order[i] >= d->n)
+		{
+			snprintf(ctx->err, sizeof(ctx->err), "edison_ftrain_epoch: order[%lld] = %d is no row of the data set (%lld rows)", (long long)i, order[i], (long long)d->n);
+			return EDISON_E_ARGUMENT;
+		}
+		const int32_t y = d->y[(size_t)order[i]];
+		if (y >= t->plan.net.n_out) return ftrain_label_refused(t, who, y, order[i]);
+	}
+	if (t->bn_on && (t->bn_flags & EDISON_FTRAIN_BN_UNBIASED) && rows > 0) /* what the last, shortest batch's gradient call would refuse */
+		for (int l = 0; l < t->bplan.n_layers; l++)
+			if (t->has_bn[l] && (rows - (steps - 1) * batch) * t->bplan.R[l].R < 2)
+				return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_epoch: the last batch gives a BatchNorm record N < 2 values; the unbiased variance needs two");
+	ED_HIP(ctx, hipSetDevice(ctx->device));
+	{ const int r = ftrain_epoch_reserve(t, rows, rows); if (r != EDISON_OK) return r; }
+	t->e_n = 0;
+	if (rows == 0) { *out = (edison_ftrain_epoch_t){0.0, 0, 0, 0}; return EDISON_OK; }
+	/* pageable host memory: the copy has left `order` when the call returns */
+	ED_HIP(ctx, hipMemcpyAsync(t->d_eorder, order, sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice, ctx->stream));
+	{
+		const int r = ed_launch_result(ctx, ed_launch_fdata_gather(d->d_x, d->d_y, t->d_eorder, rows, d->in_n, t->d_ex, t->d_ey, ctx->n_cu, ctx->stream), "epoch gather kernel");
+		if (r != EDISON_OK) return r;
+	}
+	const int64_t in_n = d->in_n;
+	for (int64_t s = 0; s < steps; s++)
+	{
+		const int64_t b0 = s * batch, m = rows - b0 < batch ? rows - b0 : batch;
+		int r = edison_ftrain_grad_dev_ex(t, t->d_ex + b0 * in_n, t->d_ey + b0, m, t->d_eloss + b0, t->d_eam + b0, 0);
+		if (r == EDISON_OK) r = edison_ftrain_step(t, lr);
+		if (r != EDISON_OK)
+		{
+			(void)hipStreamSynchronize(ctx->stream);
+			return r;
+		}
+	}
+	t->e_n = rows;
+	return ftrain_epoch_finish(t, t->d_ey, rows, steps, out);
+}
+
+#define EDFT_EVAL_ROWS 4096 /* rows an EVAL call of edison_ftrain_data_eval takes */
+
+extern "C" int edison_ftrain_data_eval(edison_ftrain *t, edison_ftrain_data *d, edison_ftrain_epoch_t *out)
+{
+	const char *who = "edison_ftrain_data_eval";
+	{ const int r = ftrain_data_ok(t, d, who); if (r != EDISON_OK) return r; }
+	edison_ctx *ctx = t->ctx;
+	if (!out) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_data_eval: NULL out");
+	for (int64_t i = 0; i < d->n; i++)
+		if (d->y[(size_t)i] >= t->plan.net.n_out) return ftrain_label_refused(t, who, d->y[(size_t)i], i);
+	ED_HIP(ctx, hipSetDevice(ctx->device));
+	{ const int r = ftrain_epoch_reserve(t, d->n, 0); if (r != EDISON_OK) return r; }
+	t->e_n = 0;
+	if (d->n == 0) { *out = (edison_ftrain_epoch_t){0.0, 0, 0, 0}; return EDISON_OK; }
+	for (int64_t b0 = 0; b0 < d->n; b0 += EDFT_EVAL_ROWS)
+	{
+		const int64_t m = d->n - b0 < EDFT_EVAL_ROWS ? d->n - b0 : EDFT_EVAL_ROWS;
+		const int r = edison_ftrain_grad_dev_ex(t, d->d_x + b0 * (int64_t)d->in_n, d->d_y + b0, m, t->d_eloss + b0, t->d_eam + b0, EDISON_FTRAIN_EVAL);
+		if (r != EDISON_OK)
+		{
+			(void)hipStreamSynchronize(ctx->stream);
+			return r;
+		}
+	}
+	t->e_n = d->n;
+	return ftrain_epoch_finish(t, d->d_y, d->n, 0, out);
+}
+
+extern "C" int edison_ftrain_epoch_rows(edison_ftrain *t, float *loss, int32_t *argmax, int64_t *n)
+{
+	{ const int r = ftrain_live(t, "edison_ftrain_epoch_rows"); if (r != EDISON_OK) return r; }
+	edison_ctx *ctx = t->ctx;
+	ED_HIP(ctx, hipSetDevice(ctx->device));
+	if (n) *n = t->e_n;
+	if (loss && t->e_n) ED_HIP(ctx, hipMemcpyAsync(loss, t->d_eloss, sizeof(float) * (size_t)t->e_n, hipMemcpyDeviceToHost, ctx->stream));
+	if (argmax && t->e_n) ED_HIP(ctx, hipMemcpyAsync(argmax, t->d_eam, sizeof(int32_t) * (size_t)t->e_n, hipMemcpyDeviceToHost, ctx->stream));
+	ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return EDISON_OK;
 }

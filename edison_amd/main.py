@@ -9,10 +9,12 @@ on the keyword-spotting hot path:
     kws  eval <audio.npy> <labels.npy>   nnom_utils.c:178-254        -> edison_amd.kws.kws_eval
     kws  quantize <net> <audio> <out>    kws_nnom.py:305             -> edison_amd.kws.kws_quantize
     kws  train <net> <x> <y> <out>       kws_keras.py:400-416        -> edison_amd.kws.kws_train
+    kws  train --arch NAME <x> <y> <out> kws_keras.py:170-416        -> edison_amd.kws.kws_train
 
 Where the reference talks to the STM32 board over the UART, the board's leg is computed by the GPU's bit-exact
 variant C. The remaining reference modules (mic, acquire, deploy, mcu) drive the board and are out of scope; of
-``train`` the engine is here (``kws train``: Adam on a float32 network), not its Keras model zoo. One deliberate
+``train`` the engine and the model zoo are here (``kws train``: Adam, SGD or Adadelta on a float32 network, which ``--arch`` builds from
+scratch as ``kws_keras.get_model`` does), not reading wav directories into data sets. One deliberate
 difference: the reference's ``kws`` dispatcher runs ``live`` and then falls into the "Unrecognized command" branch of
 the next ``if`` (main.py:158-165, exit status 1); here ``kws live`` returns 0.
 """
@@ -46,10 +48,14 @@ USAGE = """usage: edison <module> <command> [<args>]
                                          confusion matrix and top-k accuracy on a labelled data set, counted on the GPU
   kws  quantize <net.ednf> <audio.npy> <out.ednn> [--weights-h <out.h>] [--saturate <share>] [--geometry k=v,...] [--chunk N]
                                          quantise a float32 network to an int8 NNoM graph, calibrated on the GPU over the audio
-  kws  train <net.ednf> <x.npy> <y.npy> <out.ednf> [--epochs N] [--batch N] [--lr r] [--seed s] [--val <x.npy> <y.npy>]
+  kws  train <net.ednf> | --arch NAME [--classes N] [--in-shape h,w,c]  <x.npy> <y.npy> <out.ednf>
+             [--epochs N] [--batch N] [--lr r] [--seed s] [--val <x.npy> <y.npy>] [--opt adam|sgd|adadelta] [--rho r]
+             [--resident] [--audio [--geometry k=v,...]]
              [--dropout r,.. [--dropout-before-pool b,..] | --dropout-arch NAME]
              [--batchnorm b,.. | --batchnorm-arch NAME] [--bn-momentum m] [--bn-eps e] [--bn-unbiased]
-                                         train a float32 network on features and class indices: Adam on the GPU, Dropout and BatchNorm if asked
+                                         train a float32 network on features and class indices: Adam on the GPU, Dropout and BatchNorm if asked;
+                                         --arch: one of the reference's architectures from scratch; --resident / --audio: the data set
+                                         (features, or audio whose features are computed there) lives on the device, one call an epoch
 """
 
 

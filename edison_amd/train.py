@@ -3,12 +3,23 @@ does with ``kws_keras.train`` (kws_keras.py:400-416: Adam at 0.0005, batch 100, 
 loss). The gradient and the optimiser step are HIP kernels and the weights never leave the device between steps; the epochs, the
 shuffle, the history and the two callbacks are host code here, none of it hot.
 
-    ctx.fnet_load(blob)                       # imported, or cube_import.build_blob of a freshly initialised model dict
+    ctx.fnet_load(blob)                       # imported, or cube_import.build_blob(get_model("kws_conv")): a freshly initialised one
     tr = ctx.trainer(padded=True)             # padded: networks with 'same' convs and pools too
     hist = tr.fit(x, y, epochs=30, val=(vx, vy))
     trained = cube_import.build_blob(tr.model())
 
 After a step the context's float network *is* the trained one: fnet, kws_float, streams and the calibrator run the new weights.
+
+From scratch, on a data set that lives on the device: ``get_model`` builds the reference's architectures
+(kws_keras.py:170-403 ``get_model``) with Keras's default initialisation, ``Context.train_data`` puts rows and labels (or audio, whose
+features are computed there) into device memory once, and ``Trainer.fit_data`` is ``fit`` with each epoch one library call
+(``edison_ftrain_epoch``: one gather, a gradient call and a step per batch, one reduction, one synchronisation):
+
+    ctx.fnet_load(cube_import.build_blob(get_model("kws_conv")))
+    with ctx.train_data(x, y) as data, ctx.train_data(vx, vy) as val, ctx.trainer(padded=True) as tr:
+        hist = tr.fit_data(data, epochs=30, val=val)
+
+``set_opt("adadelta", rho=ADADELTA_RHO)`` is what ``kws_nnom.train`` compiles its model with (kws_nnom.py:121-123).
 """
 import ctypes
 
@@ -16,13 +27,15 @@ import numpy as np
 
 from . import _lib, cube_import
 
-ADAM, SGD = 0, 1          # EDISON_FTRAIN_ADAM, EDISON_FTRAIN_SGD
+ADAM, SGD, ADADELTA = 0, 1, 2   # EDISON_FTRAIN_ADAM, EDISON_FTRAIN_SGD, EDISON_FTRAIN_ADADELTA
 FTRAIN_PADDED = 1         # EDISON_FTRAIN_PADDED: edison_ftrain_create_ex's flag
 FTRAIN_EVAL = 1           # EDISON_FTRAIN_EVAL: edison_ftrain_grad_ex's flag
 FTRAIN_BN_UNBIASED = 1    # EDISON_FTRAIN_BN_UNBIASED: edison_ftrain_set_batchnorm's flag
 BN_MOMENTUM, BN_EPS = 0.99, 1e-3   # keras.layers.BatchNormalization's defaults
 LEARNING_RATE = 0.0005    # kws_keras.py:53 initial_learningrate
 BATCH_SIZE = 100          # kws_keras.py: batchSize
+# Keras 2.3.1's 'adadelta' as remembered: lr 1.0, rho 0.95, epsilon 1e-7. Unpinned: no Keras was at hand to read them from.
+ADADELTA_LR, ADADELTA_RHO, ADADELTA_EPS = 1.0, 0.95, 1e-7
 
 
 # Where the reference's architectures put Dropout (kws_keras.py:194-393), per conv / dense record: 0, a rate (behind the record's output)
@@ -51,6 +64,85 @@ KERAS_BATCHNORM = {
     "kws_conv": [1, 1, 1, 1, 0],
     "single_fc": [0],
 }
+
+
+# ---- the model zoo: kws_keras.get_model's architectures as model dicts ----------------------------------------------------------------
+ARCHS = ("tiny_conv", "medium_embedding_conv", "tiny_embedding_conv", "conv_model", "low_latency_conv", "single_fc", "simple_conv", "kws_conv")
+
+
+def _zoo(arch, in_shape, num_classes):
+    """kws_keras.py:176-398 as layer specs: ("conv", filters, (rows, columns), strides, padding, pool) with pool None or ((ph, pw),
+    padding), every one with ReLU (activation='relu', or kws_conv's ReLU layer), and ("dense", units); Dropout and BatchNorm are
+    KERAS_DROPOUT's and KERAS_BATCHNORM's."""
+    same22 = ((2, 2), "same")
+    return dict(
+        tiny_conv=[("conv", 8, (8, 10), (2, 2), "same", None), ("dense", num_classes)],
+        medium_embedding_conv=[("conv", 16, (8, 8), (2, 2), "same", same22), ("conv", 12, (4, 4), (1, 1), "same", None), ("dense", num_classes)],
+        tiny_embedding_conv=[("conv", 8, (8, 10), (2, 2), "same", same22), ("conv", 8, (8, 10), (8, 8), "same", None), ("dense", num_classes)],
+        conv_model=[("conv", 64, (8, 20), (1, 1), "same", same22), ("conv", 64, (4, 10), (1, 1), "same", None), ("dense", num_classes)],
+        low_latency_conv=[("conv", 186, (8, in_shape[0]), (1, 4), "same", None), ("dense", 128), ("dense", 128), ("dense", num_classes)],
+        single_fc=[("dense", num_classes)],
+        simple_conv=[("conv", 8, (8, 8), (1, 1), "same", ((2, 2), "valid")), ("dense", num_classes)],
+        kws_conv=[("conv", 16, (5, 5), (1, 1), "valid", ((2, 1), "valid")), ("conv", 32, (3, 3), (1, 1), "valid", ((2, 1), "valid")),
+                  ("conv", 64, (3, 3), (1, 1), "valid", None), ("conv", 32, (3, 3), (1, 1), "valid", None), ("dense", num_classes)],
+    )[arch]
+
+
+def _same4(h, w, k, s):
+    (t, b), (l, r) = cube_import.same_pads(h, k[0], s[0]), cube_import.same_pads(w, k[1], s[1])
+    return t, l, b, r
+
+
+def glorot_limit(L, dense):
+    """Keras's glorot_uniform limit sqrt(6 / (fan_in + fan_out)) of a conv / dense record: a conv's fans are kh kw in_c and kh kw out_c,
+    a dense layer's its inputs and outputs."""
+    (kh, kw), ic, oc = L["k"], L["inp"][2], L["out"][2]
+    fan_in, fan_out = (kh * kw * ic, oc) if dense else (kh * kw * ic, kh * kw * oc)
+    return float(np.sqrt(6.0 / (fan_in + fan_out)))
+
+
+def get_model(arch, in_shape=(31, 13, 1), num_classes=10, seed=0):
+    """One of the reference's eight architectures (ARCHS; kws_keras.py:170-403 get_model) as a cube_import model dict that
+    cube_import.build_blob takes: MaxPooling2D inside its conv's record (p / ppad), Dense as a conv record whose kernel k = (h, w) is
+    its whole input, which Flatten has made 1 x 1 x n (the records the X-CUBE-AI importer writes), 'same' pads from
+    cube_import.same_pads, a closing softmax. Keras's default initialisation: every kernel glorot_uniform, every
+    bias zero. Record r's kernel is drawn from np.random.default_rng([seed, r]) in float32: the random stream is this library's, not
+    TensorFlow's, so the same seed gives the same network here and another one than Keras would. Dropout and BatchNorm are settings of
+    the trainer (KERAS_DROPOUT[arch], KERAS_BATCHNORM[arch]), not of the dict. Which dicts the float path runs is the loader's business:
+    conv_model and low_latency_conv have layers whose weights exceed the LDS."""
+    if arch not in ARCHS:
+        raise ValueError("arch is one of %s" % ", ".join(ARCHS))
+    h, w, c = (int(v) for v in in_shape)
+    if min(h, w, c) < 1 or int(num_classes) < 1:
+        raise ValueError("in_shape and num_classes are positive")
+    layers = []
+    for r, spec in enumerate(_zoo(arch, (h, w, c), int(num_classes))):
+        if spec[0] == "dense":
+            h, w, c = 1, 1, h * w * c          # Flatten: a Dense reads its input as 1 x 1 x n, as the X-CUBE-AI importer's dense records do
+            L = dict(type=cube_import.T_CONV, inp=(h, w, c), out=(1, 1, spec[1]), k=(h, w), s=(1, 1), p=(1, 1), relu=0, cpad=(0, 0, 0, 0), ppad=(0, 0, 0, 0))
+        else:
+            _, oc, k, s, padding, pool = spec
+            cpad = _same4(h, w, k, s) if padding == "same" else (0, 0, 0, 0)
+            if k[0] > h + cpad[0] + cpad[2] or k[1] > w + cpad[1] + cpad[3]:
+                raise ValueError("%s: record %d's %dx%d kernel is larger than its %dx%d input" % (arch, r, k[0], k[1], h, w))
+            ch, cw = (h + cpad[0] + cpad[2] - k[0]) // s[0] + 1, (w + cpad[1] + cpad[3] - k[1]) // s[1] + 1
+            p, ppad = (1, 1), (0, 0, 0, 0)
+            if pool is not None:
+                p = pool[0]
+                ppad = _same4(ch, cw, p, p) if pool[1] == "same" else ppad
+            oh, ow = cube_import.pooled_dim(ch, ppad[0], ppad[2], p[0]), cube_import.pooled_dim(cw, ppad[1], ppad[3], p[1])
+            if min(oh, ow) < 1:
+                raise ValueError("%s: record %d has no output at input %dx%d" % (arch, r, h, w))
+            L = dict(type=cube_import.T_CONV, inp=(h, w, c), out=(oh, ow, oc), k=tuple(k), s=tuple(s), p=tuple(p), relu=1, cpad=cpad, ppad=ppad)
+        limit = np.float32(glorot_limit(L, spec[0] == "dense"))
+        rng = np.random.default_rng([int(seed), r])
+        shape = (L["out"][2],) + L["k"] + (c,)
+        L["w"] = ((rng.random(shape, dtype=np.float32) * np.float32(2) - np.float32(1)) * limit).astype(np.float32)   # in [-limit, limit)
+        L["b"] = np.zeros(L["out"][2], np.float32)
+        layers.append(L)
+        h, w, c = L["out"]
+    layers.append(dict(type=cube_import.T_SOFTMAX, inp=(h, w, c), out=(h, w, c)))
+    return dict(in_shape=tuple(int(v) for v in in_shape), layers=layers)
 
 
 def dropout_spec(spec, before_pool=None):
@@ -217,6 +309,127 @@ def fit(trainer, x, y, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=LEARN
         if max_steps is not None and hist["steps"] >= max_steps:
             break
     return hist
+
+
+def fit_data(trainer, data, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=LEARNING_RATE, max_steps=None, callbacks=True):
+    """fit on anything with epoch(data, order, batch, lr, max_steps) and evaluate(data), both -> dict(loss_sum, hits, seen, steps): the
+    same orders, callbacks and history, each epoch one call."""
+    if data.n == 0:
+        raise ValueError("the data set is empty")
+    if int(batch_size) < 1 or int(epochs) < 0:
+        raise ValueError("batch_size must be at least 1 and epochs at least 0")
+    n, bs = data.n, int(batch_size)
+    plateau, stopper = ReduceLROnPlateau(), EarlyStopping()
+    hist = dict(loss=[], acc=[], val_loss=[], val_acc=[], lr=[], steps=0, stopped_early=False)
+    for epoch in range(int(epochs)):
+        left = None if max_steps is None else max(int(max_steps) - hist["steps"], 0)
+        r = trainer.epoch(data, epoch_order(n, seed, epoch), bs, lr, left)
+        hist["steps"] += r["steps"]
+        if not r["seen"]:
+            break
+        hist["loss"].append(r["loss_sum"] / r["seen"])
+        hist["acc"].append(r["hits"] / r["seen"])
+        hist["lr"].append(lr)
+        if val is not None:
+            v = trainer.evaluate(val)
+            hist["val_loss"].append(v["loss_sum"] / max(val.n, 1))
+            hist["val_acc"].append(v["hits"] / max(val.n, 1))
+            if callbacks:
+                lr = plateau.update(hist["val_loss"][-1], lr)
+                if stopper.update(hist["val_loss"][-1]):
+                    hist["stopped_early"] = True
+                    break
+        if max_steps is not None and hist["steps"] >= max_steps:
+            break
+    return hist
+
+
+# ---- a data set on the device -----------------------------------------------------------------------------------------------------
+class DeviceData:
+    """edison_ftrain_data on `ctx` (Context.train_data): rows [n][in_n] float32 and labels [n] int32 in device memory, owned by the
+    context, not by a trainer: it outlives trainers and network loads, and Context.close closes it."""
+
+    def __init__(self, ctx, in_n):
+        self._ctx, self._L = ctx, ctx._L
+        h = ctypes.c_void_p()
+        ctx._check(self._L.edison_ftrain_data_create(ctx._h, int(in_n), ctypes.byref(h)))
+        self._h = h
+        ctx._train_data.add(self)                    # Context.close closes it first
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.edison_ftrain_data_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _info(self):
+        n, in_n = ctypes.c_int64(), ctypes.c_int32()
+        self._ctx._check(self._L.edison_ftrain_data_info(self._h, ctypes.byref(n), ctypes.byref(in_n)))
+        return n.value, in_n.value
+
+    @property
+    def n(self):
+        return self._info()[0]
+
+    @property
+    def in_n(self):
+        return self._info()[1]
+
+    def set(self, x, y):
+        """edison_ftrain_data_set: host rows [n][in_n] (any shape with n first) and class indices [n], uploaded once; replaces the contents."""
+        lab = np.ascontiguousarray(y).reshape(-1)
+        if lab.shape[0] and (lab.min() < 0 or lab.max() >= 2 ** 31):
+            raise ValueError("a label is outside [0, 2^31)")
+        lab = lab.astype(np.int32)
+        f = np.ascontiguousarray(x, dtype=np.float32).reshape(lab.shape[0], -1)
+        if lab.shape[0] and f.shape[1] != self.in_n:
+            raise ValueError("rows of %d floats, the data set's have %d" % (f.shape[1], self.in_n))
+        self._ctx._check(self._L.edison_ftrain_data_set(self._h, _np_ptr(f), _np_ptr(lab), lab.shape[0]))
+
+    def set_t(self, x, y, n=None):
+        """edison_ftrain_data_set_dev: torch device tensors x float32 [n][in_n], y int32 [n], contiguous."""
+        self._ctx._check(self._L.edison_ftrain_data_set_dev(self._h, _t_ptr(x), _t_ptr(y), int(x.shape[0] if n is None else n)))
+
+    def set_audio(self, audio, y, geometry=None, q15=False, clip_min=None, clip_max=None, chunk=16384, utt_stride=None):
+        """edison_ftrain_data_audio: int16 utterances [n][samples] (or flat, utt_stride apart) -> their float-flow features, computed on the
+        device chunk by chunk straight into the store: Context.kws_float's feat for the same arguments, bit for bit."""
+        from . import config as cfg
+        from .kws.geometry import KwsGeometry
+        if geometry is None:
+            geometry = KwsGeometry.from_config(net_input_scale=cfg.net_input_scale)
+        lo = float(cfg.net_input_clip_min if clip_min is None else clip_min)
+        hi = float(cfg.net_input_clip_max if clip_max is None else clip_max)
+        lab = np.ascontiguousarray(y).reshape(-1)
+        if lab.shape[0] and (lab.min() < 0 or lab.max() >= 2 ** 31):
+            raise ValueError("a label is outside [0, 2^31)")
+        lab = lab.astype(np.int32)
+        a = np.ascontiguousarray(audio, dtype=np.int16)
+        stride = int((a.shape[-1] if a.ndim == 2 else geometry.n_samples) if utt_stride is None else utt_stride)
+        a = a.ravel()
+        used = (geometry.frame_count - 1) * geometry.frame_step + geometry.frame_len
+        if lab.shape[0] and (lab.shape[0] - 1) * stride + used > a.shape[0]:
+            raise ValueError("audio too short for %d utterances" % lab.shape[0])
+        g = geometry.to_ctypes()
+        self._ctx._check(self._L.edison_ftrain_data_audio(self._h, ctypes.byref(g), 1 if q15 else 0, lo, hi, _np_ptr(a), lab.shape[0], stride,
+                                                          _np_ptr(lab), int(chunk)))
+
+    def rows(self):
+        """(x float32 [n][in_n], y int32 [n]) copied back (synchronises)."""
+        n, in_n = self._info()
+        x, y = np.zeros((n, in_n), np.float32), np.zeros(n, np.int32)
+        self._ctx._check(self._L.edison_ftrain_data_get(self._h, _np_ptr(x), _np_ptr(y)))
+        return x, y
 
 
 # ---- the GPU trainer --------------------------------------------------------------------------------------------------------------
@@ -416,11 +629,18 @@ class Trainer:
         return z
 
     # -- the optimiser
-    def set_opt(self, kind="adam", b1=0.9, b2=0.999, eps=1e-7):
-        """Adam (Keras's constants by default) or kind "sgd": w -= lr g."""
-        kinds = dict(adam=ADAM, sgd=SGD)
+    def set_opt(self, kind="adam", b1=0.9, b2=0.999, eps=1e-7, rho=None):
+        """Adam (Keras's constants by default), kind "sgd": w -= lr g, or kind "adadelta" with rho and eps (a = rho a + (1 - rho) g g,
+        u = g sqrt(d + eps) / sqrt(a + eps), w -= lr u, d = rho d + (1 - rho) u u; Keras's learning rate for it is ADADELTA_LR = 1.0).
+        Adadelta's rho has no default here: Keras's is unpinned (ADADELTA_RHO is what is remembered), so set_opt("adadelta", rho=...)
+        states it and a bare set_opt("adadelta") stays the ValueError it was before the kind existed. rho belongs to Adadelta alone."""
+        kinds = dict(adam=ADAM, sgd=SGD, adadelta=ADADELTA)
         if kind not in kinds:
-            raise ValueError("kind is 'adam' or 'sgd'")
+            raise ValueError("kind is 'adam', 'sgd' or 'adadelta'")
+        if (kind == "adadelta") != (rho is not None):
+            raise ValueError("kind 'adadelta' takes rho (train.ADADELTA_RHO is Keras's, unpinned), and no other kind does")
+        if kind == "adadelta":
+            b1, b2 = rho, 0.0
         self._ctx._check(self._L.edison_ftrain_set_opt(self._h, kinds[kind], float(b1), float(b2), float(eps)))
 
     def step(self, lr=LEARNING_RATE):
@@ -477,3 +697,37 @@ class Trainer:
         need be. Returns the history: loss, acc (the means over each epoch's batches, as Keras), val_loss, val_acc, lr per epoch, steps,
         stopped_early."""
         return fit(self, x, y, epochs, batch_size=batch_size, val=val, seed=seed, lr=lr, max_steps=max_steps, callbacks=callbacks)
+
+    # -- whole epochs on a data set on the device (DESIGN.md section 19d)
+    def epoch(self, data, order, batch_size=BATCH_SIZE, lr=LEARNING_RATE, max_steps=None):
+        """edison_ftrain_epoch: the rows order[i] of `data` (a DeviceData) in batches of batch_size, a gradient call and a step each, one
+        synchronisation -> dict(loss_sum, hits, seen, steps)."""
+        o = np.asarray(order).reshape(-1)
+        if o.shape[0] and (o.min() < -2 ** 31 or o.max() >= 2 ** 31):
+            raise ValueError("an index of order does not fit int32")
+        o = np.ascontiguousarray(o, dtype=np.int32)
+        out = _lib.FtrainEpoch()
+        self._ctx._check(self._L.edison_ftrain_epoch(self._h, data._h, _np_ptr(o), o.shape[0], int(batch_size), float(lr),
+                                                     -1 if max_steps is None else int(max_steps), ctypes.byref(out)))
+        if out.steps:
+            self._ctx._fnet_trainer = self          # the context's copy of the blob is behind the device weights now
+        return dict(loss_sum=out.loss_sum, hits=out.hits, seen=out.seen, steps=out.steps)
+
+    def evaluate(self, data):
+        """edison_ftrain_data_eval: every row of `data` through EDISON_FTRAIN_EVAL calls -> dict(loss_sum, hits, seen, steps = 0)."""
+        out = _lib.FtrainEpoch()
+        self._ctx._check(self._L.edison_ftrain_data_eval(self._h, data._h, ctypes.byref(out)))
+        return dict(loss_sum=out.loss_sum, hits=out.hits, seen=out.seen, steps=out.steps)
+
+    def epoch_rows(self):
+        """edison_ftrain_epoch_rows: dict(loss [n], argmax [n]) of the last epoch or evaluate call, in the order the rows were run."""
+        n = ctypes.c_int64()
+        self._ctx._check(self._L.edison_ftrain_epoch_rows(self._h, None, None, ctypes.byref(n)))
+        loss, am = np.zeros(n.value, np.float32), np.zeros(n.value, np.int32)
+        self._ctx._check(self._L.edison_ftrain_epoch_rows(self._h, _np_ptr(loss), _np_ptr(am), None))
+        return dict(loss=loss, argmax=am)
+
+    def fit_data(self, data, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=LEARNING_RATE, max_steps=None, callbacks=True):
+        """fit on a DeviceData (Context.train_data): the same epoch_order, callbacks and history, with each epoch's inner loop one
+        edison_ftrain_epoch call and the validation (val: a DeviceData) one edison_ftrain_data_eval call."""
+        return fit_data(self, data, epochs, batch_size=batch_size, val=val, seed=seed, lr=lr, max_steps=max_steps, callbacks=callbacks)

@@ -471,7 +471,10 @@ int edison_fcal_result(edison_fcal *c, uint32_t *absmax, uint64_t *hist, uint64_
  *                           m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g g, w -= lr sqrt(1 - b2^t) / (1 - b1^t) m / (sqrt(v) + eps); the
  *                           scalar factor is computed in double. Or, kind EDISON_FTRAIN_SGD, w -= lr g.
  *   edison_ftrain_set_opt   kind and Adam's constants (at create: Adam, 0.9, 0.999, 1e-7); edison_ftrain_reset zeroes m, v, t and the
- *                           counter of ignored rows
+ *                           counter of ignored rows. Kind EDISON_FTRAIN_ADADELTA: b1 carries rho in [0, 1), b2 is ignored, eps > 0
+ *                           (Keras's 'adadelta' is remembered as rho 0.95, eps 1e-7 at lr 1.0: unpinned); its step, a kernel of its own
+ *                           on the two moment arrays, is a = rho a + (1 - rho) g g, u = g sqrt(d + eps) / sqrt(a + eps), w -= lr u,
+ *                           d = rho d + (1 - rho) u u (Keras's and torch.optim.Adadelta's). A refused setting leaves the previous one.
  *   edison_ftrain_weights_get / _set  copy the packed weights [w_floats] out / in (synchronising)
  * Dropout, off at create:
  *   edison_ftrain_set_dropout  rate [n_records] in [0, 1) behind each conv / dense record's output (n_records = n_layers; the last
@@ -500,6 +503,7 @@ int edison_fcal_result(edison_fcal *c, uint32_t *absmax, uint64_t *hist, uint64_
  */
 #define EDISON_FTRAIN_ADAM 0
 #define EDISON_FTRAIN_SGD 1
+#define EDISON_FTRAIN_ADADELTA 2
 #define EDISON_FTRAIN_PADDED 1u
 #define EDISON_FTRAIN_EVAL 1u /* edison_ftrain_grad_dev_ex / edison_ftrain_grad_ex */
 typedef struct edison_ftrain edison_ftrain;
@@ -563,6 +567,50 @@ int edison_ftrain_bn_set(edison_ftrain *t, int record, const float *gamma, const
 int edison_ftrain_bn_batch_get(edison_ftrain *t, int record, float *mean, float *var);
 int edison_ftrain_bn_grad_get(edison_ftrain *t, int record, float *dgamma, float *dbeta);
 int edison_ftrain_folded_get(edison_ftrain *t, float *packed);
+/*
+ * Training from a data set that lives on the device: whole epochs with one synchronisation each.
+ *   edison_ftrain_data_create / _destroy  a store of rows [n][in_n] float32 and labels [n] int32 in device memory. It belongs to the
+ *                           context, not to a trainer: it outlives trainers and network loads. Destroy it before edison_shutdown.
+ *   edison_ftrain_data_set  host arrays, uploaded once; replaces the contents, regrows when needed. A negative label is
+ *                           EDISON_E_ARGUMENT naming the row; labels are checked against the network's n_out where it is known, at
+ *                           the epoch call. edison_ftrain_data_set_dev takes device pointers (it reads the labels back, synchronising).
+ *   edison_ftrain_data_audio  host int16 audio, n_utt utterances utt_stride samples apart, uploaded `chunk` utterances at a time; each
+ *                           chunk's features are written straight into the store by the feature launches of edison_kws_float_batch_dev
+ *                           (g, q15, clip_lo, clip_hi as there; no network need be loaded): the rows are bit for bit that call's feat.
+ *                           frame_count x num_mfcc != in_n is EDISON_E_SIZE; the geometry's errors are edison_kws_geom's.
+ *   edison_ftrain_data_info / _get  n and in_n / copy the rows and labels back (each NULL for not wanted)
+ *   edison_ftrain_epoch     one epoch over rows order[0 .. n_order) of d (any values in [0, n), repeats allowed), in batches of `batch`
+ *                           rows, the last one short: one launch gathers the rows and labels in that order into the trainer's epoch
+ *                           store, then per batch edison_ftrain_grad_dev_ex on its slice and edison_ftrain_step(lr), in stream order
+ *                           with nothing between them, then one launch sums the per-row losses (in double, in an order n alone fixes,
+ *                           no atomics: the same call gives the same bits) and counts the rows whose argmax is their label; one copy
+ *                           back, one synchronisation. max_steps >= 0 ends the epoch after that many batches (< 0: no limit). Dropout's
+ *                           counter and Adam's t advance as the same grad / step calls advance them. Before any launch: an order index
+ *                           outside [0, n), a label of such a row >= n_out, batch < 1, or with BatchNorm batch > max_rows, are
+ *                           EDISON_E_ARGUMENT; a data set of another in_n is EDISON_E_SIZE. n_order = 0 is zero steps and a zero result.
+ *   edison_ftrain_data_eval the whole store through EDISON_FTRAIN_EVAL calls of 4096 rows, then the same reduction: no weight, statistic
+ *                           or counter changes (with BatchNorm the next step needs a training call first, as after any EVAL call)
+ *   edison_ftrain_epoch_rows  the per-row loss and argmax of the last epoch or eval call, in the order the rows were run (*n: how many)
+ */
+typedef struct edison_ftrain_data edison_ftrain_data;
+typedef struct edison_ftrain_epoch_t {
+	double loss_sum; /* sum of the per-row losses of the rows run */
+	int64_t hits;    /* rows whose argmax equals their label      */
+	int64_t seen;    /* rows run                                   */
+	int64_t steps;   /* optimiser steps taken (an eval call: 0)    */
+} edison_ftrain_epoch_t;
+int edison_ftrain_data_create(edison_ctx *ctx, int32_t in_n, edison_ftrain_data **out);
+void edison_ftrain_data_destroy(edison_ftrain_data *d);
+int edison_ftrain_data_info(edison_ftrain_data *d, int64_t *n, int32_t *in_n);
+int edison_ftrain_data_set(edison_ftrain_data *d, const float *x, const int32_t *y, int64_t n);
+int edison_ftrain_data_set_dev(edison_ftrain_data *d, const float *x, const int32_t *y, int64_t n);
+int edison_ftrain_data_get(edison_ftrain_data *d, float *x, int32_t *y);
+int edison_ftrain_data_audio(edison_ftrain_data *d, const edison_kws_geom *g, int q15, float clip_lo, float clip_hi, const int16_t *audio, int64_t n_utt,
+                             int64_t utt_stride, const int32_t *labels, int64_t chunk);
+int edison_ftrain_epoch(edison_ftrain *t, edison_ftrain_data *d, const int32_t *order, int64_t n_order, int64_t batch, double lr, int64_t max_steps,
+                        edison_ftrain_epoch_t *out);
+int edison_ftrain_data_eval(edison_ftrain *t, edison_ftrain_data *d, edison_ftrain_epoch_t *out);
+int edison_ftrain_epoch_rows(edison_ftrain *t, float *loss, int32_t *argmax, int64_t *n);
 
 /*
  * Exact KWS mode (off by default; EDISON_KWS_EXACT=1 in the environment at edison_init turns it on for that context).

@@ -10,6 +10,7 @@ samples per second, its minimum and maximum. The learning rate is 0, so the weig
     python tools/bench_train.py [--net FILE.ednf] [--batches 100,4096] [--repeats 7] [--region-ms 300] [--out FILE.json]
                                 [--dropout 0,0,0.2,0.3,0 | --dropout-arch kws_conv] [--dropout-before-pool 0,1,..]
                                 [--batchnorm [1,1,1,1,0]]
+    python tools/bench_train.py --fit [--fit-rows 8192] [--fit-batch 100] [--repeats 7] [--out FILE.json]
 
 --net: another float network than the shipped one, 'same' convs and pools included (the trainer is created with padded=True; on a
 network without pads that is the plain trainer).
@@ -20,6 +21,12 @@ network without pads that is the plain trainer).
 1,1,1,1,0), on the network's geometry with its loaded weights as the starting master weights; the forward leg then runs the folded
 network. "launches" is the number of kernel launches of one training call plus one step (the fold included), which depends on the
 records and not on the batch.
+
+--fit: another measurement (report only, no threshold): wall-clock seconds of one epoch of Trainer.fit, which gathers each batch on the
+host and synchronises per batch, and of Trainer.fit_data on a device-resident data set, one library call and one synchronisation an
+epoch. A plain kws_conv built by train.get_model on the shipped geometry, --fit-rows rows (8192), batch
+--fit-batch (100), the two run alternately in one process after a warm-up epoch of each, median of --repeats; then the same pair with one
+validation pass over as many rows. The other options do not apply.
 
 One JSON line.
 """
@@ -39,6 +46,52 @@ def dropout_on(spec):
     return [(s[0] if isinstance(s, (tuple, list)) else s) > 0 for s in spec]
 
 
+def fit_main(args):
+    """Seconds an epoch of Trainer.fit against Trainer.fit_data, without and with a validation pass."""
+    import torch
+    from edison_amd import cube_import, train
+    from edison_amd.context import Context
+    if not torch.cuda.is_available():
+        sys.exit("bench_train: no GPU (there is no CPU path to time)")
+    ctx = Context(0)
+    model = train.get_model("kws_conv")
+    ctx.fnet_load(cube_import.build_blob(model))
+    n, bs = args.fit_rows, args.fit_batch
+    rng = np.random.default_rng(19)
+    x = rng.normal(0, 30, (n, int(np.prod(model["in_shape"])))).astype(np.float32)
+    y = (np.arange(n) % 10).astype(np.int32)
+    tr = ctx.trainer(padded=True)
+    data = ctx.train_data(x, y)
+    kw = dict(epochs=1, batch_size=bs, lr=0.0, callbacks=False)          # lr 0: every epoch of either leg runs the same weights
+
+    def timed(call):
+        ctx.sync()
+        t0 = time.perf_counter()
+        call()
+        ctx.sync()
+        return time.perf_counter() - t0
+
+    legs = dict(fit=lambda: tr.fit(x, y, **kw), fit_data=lambda: tr.fit_data(data, **kw),
+                fit_val=lambda: tr.fit(x, y, val=(x, y), **kw), fit_data_val=lambda: tr.fit_data(data, val=data, **kw))
+    for call in legs.values():
+        call()
+    secs = {k: [] for k in legs}
+    for _ in range(args.repeats):
+        for k, call in legs.items():
+            secs[k].append(timed(call))
+    row = dict(mode="fit", network="kws_conv (train.get_model)", device=torch.cuda.get_device_name(0), rows=n, batch=bs, steps_per_epoch=-(-n // bs),
+               repeats=args.repeats, seconds_per_epoch={k: dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v))) for k, v in secs.items()})
+    row["fit_over_fit_data"] = row["seconds_per_epoch"]["fit"]["median"] / row["seconds_per_epoch"]["fit_data"]["median"]
+    row["fit_over_fit_data_with_validation"] = row["seconds_per_epoch"]["fit_val"]["median"] / row["seconds_per_epoch"]["fit_data_val"]["median"]
+    data.close()
+    tr.close()
+    ctx.close()
+    print(json.dumps(row), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(row, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--net", default=os.path.join(ROOT, "tests", "golden", "cube_kws.ednf"))
@@ -50,7 +103,12 @@ def main():
     ap.add_argument("--dropout-before-pool")
     ap.add_argument("--dropout-arch")
     ap.add_argument("--batchnorm", nargs="?", const="1,1,1,1,0")
+    ap.add_argument("--fit", action="store_true")
+    ap.add_argument("--fit-rows", type=int, default=8192)
+    ap.add_argument("--fit-batch", type=int, default=100)
     args = ap.parse_args()
+    if args.fit:
+        return fit_main(args)
     import torch
     from edison_amd.context import Context
     if not torch.cuda.is_available():
