@@ -255,6 +255,35 @@ class EarlyStopping:
         return self.wait >= self.patience
 
 
+def _fit_epochs(run_epoch, run_val, epochs, batch_size, lr, max_steps, callbacks):
+    """The epoch loop of fit and fit_data: the history, the two callbacks on the validation loss, the max_steps cut. run_epoch(epoch, lr,
+    steps_left or None) -> (loss_sum, hits, seen, steps) trains one epoch, run_val() -> (loss_sum, hits, n) evaluates; run_val may be None."""
+    if int(batch_size) < 1 or int(epochs) < 0:
+        raise ValueError("batch_size must be at least 1 and epochs at least 0")
+    plateau, stopper = ReduceLROnPlateau(), EarlyStopping()
+    hist = dict(loss=[], acc=[], val_loss=[], val_acc=[], lr=[], steps=0, stopped_early=False)
+    for epoch in range(int(epochs)):
+        loss_sum, hits, seen, steps = run_epoch(epoch, lr, None if max_steps is None else max(max_steps - hist["steps"], 0))
+        hist["steps"] += steps
+        if not seen:
+            break
+        hist["loss"].append(loss_sum / seen)             # as Keras: the mean over the epoch's batches, weights moving
+        hist["acc"].append(hits / seen)
+        hist["lr"].append(lr)
+        if run_val is not None:
+            vl, vh, vn = run_val()
+            hist["val_loss"].append(vl / max(vn, 1))
+            hist["val_acc"].append(vh / max(vn, 1))
+            if callbacks:
+                lr = plateau.update(hist["val_loss"][-1], lr)
+                if stopper.update(hist["val_loss"][-1]):
+                    hist["stopped_early"] = True
+                    break
+        if max_steps is not None and hist["steps"] >= max_steps:
+            break
+    return hist
+
+
 def fit(trainer, x, y, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=LEARNING_RATE, max_steps=None, callbacks=True):
     """Trainer.fit on anything with grad(x, y) -> dict(loss [n], argmax [n]) and step(lr): the GPU trainer, or a host restatement of it."""
     x = np.asarray(x)
@@ -262,53 +291,40 @@ def fit(trainer, x, y, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=LEARN
     y = np.asarray(y).astype(np.int32).reshape(-1)
     if x.shape[0] != y.shape[0] or x.shape[0] == 0:
         raise ValueError("x has %d rows, y %d" % (x.shape[0], y.shape[0]))
-    if int(batch_size) < 1 or int(epochs) < 0:
-        raise ValueError("batch_size must be at least 1 and epochs at least 0")
     n, bs = x.shape[0], int(batch_size)
     if val is not None:
         vx, vy = np.asarray(val[0]), np.asarray(val[1]).astype(np.int32).reshape(-1)
         vx = vx.reshape(vx.shape[0], -1)
-    plateau, stopper = ReduceLROnPlateau(), EarlyStopping()
     # validation runs with dropout off and on BatchNorm's moving statistics: the keyword goes only to a trainer that reports one of them
     # on, so anything without them keeps working
     state = trainer.dropout() if hasattr(trainer, "dropout") else None
     bn = trainer.batchnorm() if hasattr(trainer, "batchnorm") else None
     ev = dict(training=False) if (state and state.get("on")) or (bn and bn.get("on")) else {}
-    hist = dict(loss=[], acc=[], val_loss=[], val_acc=[], lr=[], steps=0, stopped_early=False)
-    for epoch in range(int(epochs)):
+
+    def run_epoch(epoch, lr, steps_left):
         order = epoch_order(n, seed, epoch)
-        loss_sum, hits, seen = 0.0, 0, 0
+        loss_sum, hits, seen, steps = 0.0, 0, 0, 0
         for b0 in range(0, n, bs):                       # the last batch may be short
-            if max_steps is not None and hist["steps"] >= max_steps:
+            if steps_left is not None and steps >= steps_left:
                 break
             rows = order[b0:b0 + bs]
             r = trainer.grad(x[rows], y[rows])               # a training call: with dropout set, its mask and the counter's advance
             trainer.step(lr)
-            hist["steps"] += 1
+            steps += 1
             loss_sum += float(np.sum(r["loss"], dtype=np.float64))
             hits += int((r["argmax"] == y[rows]).sum())
             seen += len(rows)
-        if not seen:
-            break
-        hist["loss"].append(loss_sum / seen)             # as Keras: the mean over the epoch's batches, weights moving
-        hist["acc"].append(hits / seen)
-        hist["lr"].append(lr)
-        if val is not None:
-            vl, vh = 0.0, 0
-            for b0 in range(0, vx.shape[0], 4096):
-                r = trainer.grad(vx[b0:b0 + 4096], vy[b0:b0 + 4096], **ev)   # the gradient it leaves is not stepped
-                vl += float(np.sum(r["loss"], dtype=np.float64))
-                vh += int((r["argmax"] == vy[b0:b0 + 4096]).sum())
-            hist["val_loss"].append(vl / max(vx.shape[0], 1))
-            hist["val_acc"].append(vh / max(vx.shape[0], 1))
-            if callbacks:
-                lr = plateau.update(hist["val_loss"][-1], lr)
-                if stopper.update(hist["val_loss"][-1]):
-                    hist["stopped_early"] = True
-                    break
-        if max_steps is not None and hist["steps"] >= max_steps:
-            break
-    return hist
+        return loss_sum, hits, seen, steps
+
+    def run_val():
+        vl, vh = 0.0, 0
+        for b0 in range(0, vx.shape[0], 4096):
+            r = trainer.grad(vx[b0:b0 + 4096], vy[b0:b0 + 4096], **ev)   # the gradient it leaves is not stepped
+            vl += float(np.sum(r["loss"], dtype=np.float64))
+            vh += int((r["argmax"] == vy[b0:b0 + 4096]).sum())
+        return vl, vh, vx.shape[0]
+
+    return _fit_epochs(run_epoch, None if val is None else run_val, epochs, batch_size, lr, max_steps, callbacks)
 
 
 def fit_data(trainer, data, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=LEARNING_RATE, max_steps=None, callbacks=True):
@@ -316,32 +332,16 @@ def fit_data(trainer, data, epochs, batch_size=BATCH_SIZE, val=None, seed=0, lr=
     same orders, callbacks and history, each epoch one call."""
     if data.n == 0:
         raise ValueError("the data set is empty")
-    if int(batch_size) < 1 or int(epochs) < 0:
-        raise ValueError("batch_size must be at least 1 and epochs at least 0")
-    n, bs = data.n, int(batch_size)
-    plateau, stopper = ReduceLROnPlateau(), EarlyStopping()
-    hist = dict(loss=[], acc=[], val_loss=[], val_acc=[], lr=[], steps=0, stopped_early=False)
-    for epoch in range(int(epochs)):
-        left = None if max_steps is None else max(int(max_steps) - hist["steps"], 0)
-        r = trainer.epoch(data, epoch_order(n, seed, epoch), bs, lr, left)
-        hist["steps"] += r["steps"]
-        if not r["seen"]:
-            break
-        hist["loss"].append(r["loss_sum"] / r["seen"])
-        hist["acc"].append(r["hits"] / r["seen"])
-        hist["lr"].append(lr)
-        if val is not None:
-            v = trainer.evaluate(val)
-            hist["val_loss"].append(v["loss_sum"] / max(val.n, 1))
-            hist["val_acc"].append(v["hits"] / max(val.n, 1))
-            if callbacks:
-                lr = plateau.update(hist["val_loss"][-1], lr)
-                if stopper.update(hist["val_loss"][-1]):
-                    hist["stopped_early"] = True
-                    break
-        if max_steps is not None and hist["steps"] >= max_steps:
-            break
-    return hist
+
+    def run_epoch(epoch, lr, steps_left):
+        r = trainer.epoch(data, epoch_order(data.n, seed, epoch), int(batch_size), lr, steps_left)
+        return r["loss_sum"], r["hits"], r["seen"], r["steps"]
+
+    def run_val():
+        v = trainer.evaluate(val)
+        return v["loss_sum"], v["hits"], val.n
+
+    return _fit_epochs(run_epoch, None if val is None else run_val, epochs, batch_size, lr, max_steps, callbacks)
 
 
 # ---- a data set on the device -----------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""CPU tests of tests/fbn_ref.py, the restatement the GPU tests of BatchNorm in the float32 trainer are held to (DESIGN.md section
+"""CPU tests of tests/ftrain_ref.py with BatchNorm, the restatement the GPU tests of BatchNorm in the float32 trainer are held to (DESIGN.md section
 19c): against torch's float64 autograd and central differences; that leaving the truncated positions out of the statistics would be
 seen; the fold against BatchNorm in inference mode; the precondition of the GPU test's bound on the very inputs it draws; the new
 kws train options and the refusals that need no GPU; and the resources of the new kernels from the compiler's remarks."""
@@ -10,8 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
-import fbn_ref as fb
-import fgrad_ref
+import fnet_ref
+import ftrain_ref
+import ftrain_rows
 from edison_amd import build as B
 from edison_amd import train
 from edison_amd.kws import kws_train
@@ -24,15 +25,15 @@ def close(got, want, tol=1e-10):
     return np.abs(got - want).max() <= tol * max(1.0, np.abs(want).max())
 
 
-@pytest.mark.parametrize("name", fb.ROWS)
+@pytest.mark.parametrize("name", ftrain_rows.BN_ROWS)
 def test_the_restatement_is_torchs_float64_autograd(name):
-    c = fb.case(name)
+    c = ftrain_rows.bn_case(name)
     for call in (0, 1):
-        ref, after = fb.reference(name, call)
-        state = c["state0"] if call == 0 else fb.reference(name, call - 1)[1]
-        t = fb.torch_grads(c["model"], c["x"], c["y"], torch.float64, state, sp=c["sp"], seed=c["seed"], call=call)
+        ref, after = ftrain_rows.bn_reference(name, call)
+        state = ftrain_rows.bn_state(name, call)
+        t = ftrain_ref.torch_grads(c["model"], c["x"], c["y"], torch.float64, dropout=(c["sp"], c["seed"], call), bn=dict(state=state))
         assert close(ref["loss"], t["loss"]) and close(ref["logits"], t["logits"])
-        unb = fb.moved(state, ref["bn"], unbiased=True)
+        unb = ftrain_ref.moved(state, ref["bn"], unbiased=True)
         for i, (g, tg, b, tb) in enumerate(zip(ref["grads"], t["grads"], ref["bn"], t["bn"])):
             assert close(g["w"], tg["w"]), (name, call, i)
             assert close(g["b_sum"], tg["b"]), (name, call, i)
@@ -44,7 +45,7 @@ def test_the_restatement_is_torchs_float64_autograd(name):
             # torch's running statistics: the mean, and the variance with Bessel's correction (the unbiased flag's rule)
             assert close(unb[i]["mean"], tb["mean"]) and close(unb[i]["var"], tb["var"]), (name, call, i)
             # without the flag: the population variance, which is torch's with the correction taken out
-            m = fb.MOMENTUM
+            m = ftrain_ref.MOMENTUM
             pop = (tb["var"] - m * np.asarray(state[i]["var"], np.float64)) / (1.0 - m) * (b["N"] - 1.0) / b["N"]
             assert close(after[i]["var"], m * np.asarray(state[i]["var"], np.float64) + (1.0 - m) * pop), (name, call, i)
             assert close(after[i]["mean"], tb["mean"])
@@ -52,13 +53,13 @@ def test_the_restatement_is_torchs_float64_autograd(name):
 
 @pytest.mark.parametrize("name", ["bn_trunc", "bn_mixed"])
 def test_the_restatement_is_the_central_difference_of_its_loss(name):
-    c = fb.case(name)
-    ref, _ = fb.reference(name, 0)
-    base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fb.conv_records(c["model"])]
+    c = ftrain_rows.bn_case(name)
+    ref, _ = ftrain_rows.bn_reference(name, 0)
+    base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_ref.conv_records(c["model"])]
     state = [None if st is None else {k: np.asarray(v, np.float64).copy() for k, v in st.items()} for st in c["state0"]]
 
     def mean_loss(weights, st):
-        return fb.loss_grad(c["model"], c["x"], c["y"], st, sp=c["sp"], seed=c["seed"], call=0, weights=weights)["loss"].mean()
+        return ftrain_ref.loss_grad(c["model"], c["x"], c["y"], weights=weights, dropout=(c["sp"], c["seed"], 0), bn=dict(state=st))["loss"].mean()
 
     rng = np.random.default_rng(5)
     h = 1e-6
@@ -91,42 +92,42 @@ def test_the_restatement_is_the_central_difference_of_its_loss(name):
 def test_leaving_the_truncated_positions_out_would_be_seen(name):
     """The restatement with the truncated positions left out of the statistics and of dz differs from the right one by more than
     100 x the GPU test's bound on some tensor: the GPU test can see that mistake."""
-    c = fb.case(name)
-    ref, _ = fb.reference(name, 0)
-    wrong = fb.loss_grad(c["model"], c["x"], c["y"], c["state0"], sp=c["sp"], seed=c["seed"], call=0, trunc_in_stats=False)
-    per, _, _ = fb.bounds(name, 0)
+    c = ftrain_rows.bn_case(name)
+    ref, _ = ftrain_rows.bn_reference(name, 0)
+    wrong = ftrain_ref.loss_grad(c["model"], c["x"], c["y"], dropout=(c["sp"], c["seed"], 0), bn=dict(state=c["state0"], trunc_in_stats=False))
+    per, _, _ = ftrain_rows.bn_bounds(name, 0)
     ratios = []
     for g, gw, b, bw, bound in zip(ref["grads"], wrong["grads"], ref["bn"], wrong["bn"], per):
-        ratios.append(fgrad_ref.tensor_error(gw["w"], g["w"]) / bound["w"][0])
+        ratios.append(ftrain_ref.tensor_error(gw["w"], g["w"]) / bound["w"][0])
         if b is not None:
-            ratios += [fgrad_ref.tensor_error(bw[k], b[k]) / bound[k][0] for k in ("gamma", "beta")]
+            ratios += [ftrain_ref.tensor_error(bw[k], b[k]) / bound[k][0] for k in ("gamma", "beta")]
     print(name, "wrong / bound:", np.round(ratios, 1))
     assert max(ratios) > 100, ratios
 
 
 @pytest.mark.parametrize("name", ["bn_pool21_neg", "bn_mixed", "shipped"])
 def test_the_folded_network_is_batchnorm_in_inference_mode(name):
-    c = fb.case(name)
+    c = ftrain_rows.bn_case(name)
     rng = np.random.default_rng(31)
-    weights = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fb.conv_records(c["model"])]
+    weights = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_ref.conv_records(c["model"])]
     state = [None if st is None else dict(gamma=rng.normal(0, 1, len(st["gamma"])), beta=rng.normal(0, 1, len(st["gamma"])),
                                           mean=rng.normal(0, 1, len(st["gamma"])), var=rng.uniform(0.2, 3, len(st["gamma"]))) for st in c["state0"]]
-    want = fb.inference(c["model"], c["x"], weights, state)
-    got = fgrad_ref.loss_grad(c["model"], c["x"], c["y"], weights=fb.fold(weights, state))["logits"]
+    want = ftrain_ref.inference(c["model"], c["x"], weights, state)
+    got = ftrain_ref.loss_grad(c["model"], c["x"], c["y"], weights=ftrain_ref.fold(weights, state))["logits"]
     assert np.abs(got - want).max() <= 1e-12 * max(1.0, np.abs(want).max())
 
 
-@pytest.mark.parametrize("name", fb.ROWS)
+@pytest.mark.parametrize("name", ftrain_rows.BN_ROWS)
 def test_the_bounds_precondition_on_the_inputs_the_gpu_test_draws(name):
     """On both training calls: the float32 host model and float64 pick the same pool winner and agree on the sign under every ReLU, and
     the smallest softmax probability is above 1e-4."""
-    c = fb.case(name)
+    c = ftrain_rows.bn_case(name)
     for call in (0, 1):
-        ref, _ = fb.reference(name, call)
-        state = c["state0"] if call == 0 else fb.reference(name, call - 1)[1]
-        r32 = fb.loss_grad(c["model"], c["x"], c["y"], state, sp=c["sp"], seed=c["seed"], call=call, dtype=np.float32, detail=True)
+        ref, _ = ftrain_rows.bn_reference(name, call)
+        state = ftrain_rows.bn_state(name, call)
+        r32 = ftrain_ref.loss_grad(c["model"], c["x"], c["y"], dropout=(c["sp"], c["seed"], call), bn=dict(state=state), dtype=np.float32, detail=True)
         assert r32["logits"].dtype == np.float32
-        for L, d32, d64 in zip(fb.conv_records(c["model"]), r32["detail"], ref["detail"]):
+        for L, d32, d64 in zip(fnet_ref.conv_records(c["model"]), r32["detail"], ref["detail"]):
             assert np.array_equal(d32["first"], d64["first"]), (name, call)
             if L["relu"]:
                 assert np.array_equal(d32["y"] > 0, d64["y"] > 0), (name, call)

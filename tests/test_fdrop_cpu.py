@@ -1,4 +1,4 @@
-"""The dropout mask (csrc/fnet_dropout.h) and its restatement (tests/fdrop_ref.py) without a GPU: Philox's known answers, a stand-alone host
+"""The dropout mask (csrc/fnet_dropout.h), its restatement (tests/fdrop_ref.py) and training with it (tests/ftrain_ref.py) without a GPU: Philox's known answers, a stand-alone host
 program on the header, the mask's statistics, the restatement against torch's float64 autograd, central differences and the
 dropout-free restatement, the precondition of tests/test_gpu_ftrain_dropout.py's rounding bound on the very inputs it draws, fit's
 calls on a scripted trainer, and the compiler's resource remarks of all four instantiations of ed_ftrain_grad_kernel."""
@@ -12,8 +12,9 @@ import pytest
 from edison_amd import train
 
 import fdrop_ref as fd
-import fgrad_pad_ref as gp
-import fgrad_ref
+import fnet_ref
+import ftrain_ref
+import ftrain_rows
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "edison_amd", "csrc")
 
@@ -133,27 +134,27 @@ def test_every_element_of_a_small_tensor_is_kept_at_its_rate_over_samples():
 
 
 # ---- the restatement ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", fd.ROWS)
+@pytest.mark.parametrize("name", ftrain_rows.DROP_ROWS)
 def test_restatement_agrees_with_torch_float64_autograd(name):
     import torch
-    c = fd.case(name)
+    c = ftrain_rows.drop_case(name)
     x, y = c["x"][:5], c["y"][:5]
-    ref = fd.loss_grad(c["model"], x, y, c["sp"], c["seed"], 3)
-    tor = fd.torch_grads(c["model"], x, y, torch.float64, c["sp"], c["seed"], 3)
+    ref = ftrain_ref.loss_grad(c["model"], x, y, dropout=(c["sp"], c["seed"], 3))
+    tor = ftrain_ref.torch_grads(c["model"], x, y, torch.float64, dropout=(c["sp"], c["seed"], 3))
     assert np.allclose(ref["logits"], tor["logits"], rtol=1e-10, atol=1e-12) and np.allclose(ref["loss"], tor["loss"], rtol=1e-10, atol=1e-12)
     for i, (a, b) in enumerate(zip(ref["grads"], tor["grads"])):
         for k in ("w", "b"):
-            assert fgrad_ref.tensor_error(a[k], b[k]) <= 1e-10, (name, i, k)
-    plain = gp.loss_grad(c["model"], x, y)
+            assert ftrain_ref.tensor_error(a[k], b[k]) <= 1e-10, (name, i, k)
+    plain = ftrain_ref.loss_grad(c["model"], x, y)
     assert not np.array_equal(plain["logits"], ref["logits"])               # the mask does something
 
 
 @pytest.mark.parametrize("name", ["pool21_before", "pool21_after"])
 def test_restatement_agrees_with_central_differences(name):
-    c = fd.case(name)
+    c = ftrain_rows.drop_case(name)
     m, x, y = c["model"], c["x"][:4], c["y"][:4]
-    ref = fd.loss_grad(m, x, y, c["sp"], c["seed"], 0)
-    base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in gp.conv_records(m)]
+    ref = ftrain_ref.loss_grad(m, x, y, dropout=(c["sp"], c["seed"], 0))
+    base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_ref.conv_records(m)]
     h = 1e-6
     for i, t in enumerate(base):
         for k in ("w", "b"):
@@ -163,7 +164,7 @@ def test_restatement_agrees_with_central_differences(name):
                 for sgn in (1.0, -1.0):
                     w = [dict(w=u["w"].copy(), b=u["b"].copy()) for u in base]
                     w[i][k].reshape(-1)[j] += sgn * h
-                    vals.append(fd.loss_grad(m, x, y, c["sp"], c["seed"], 0, weights=w)["loss"].mean())
+                    vals.append(ftrain_ref.loss_grad(m, x, y, weights=w, dropout=(c["sp"], c["seed"], 0))["loss"].mean())
                 num[j] = (vals[0] - vals[1]) / (2 * h)
             g = ref["grads"][i][k].reshape(-1)
             # as tests/test_fgrad_pad_cpu.py: O(h^2) |f'''| + rounding / h between the kinks of ReLU and max
@@ -172,9 +173,9 @@ def test_restatement_agrees_with_central_differences(name):
 
 @pytest.mark.parametrize("name", ["pool21_before", "mid_pads_batch", "shipped_kws_conv"])
 def test_at_rate_zero_it_is_the_dropout_free_restatement_exactly(name):
-    c = fd.case(name)
+    c = ftrain_rows.drop_case(name)
     none = fd.spec(c["model"], [0] * len(c["sp"]))
-    a, b = fd.loss_grad(c["model"], c["x"][:5], c["y"][:5], none, 3, 9), gp.loss_grad(c["model"], c["x"][:5], c["y"][:5])
+    a, b = ftrain_ref.loss_grad(c["model"], c["x"][:5], c["y"][:5], dropout=(none, 3, 9)), ftrain_ref.loss_grad(c["model"], c["x"][:5], c["y"][:5])
     assert np.array_equal(a["loss"], b["loss"]) and np.array_equal(a["logits"], b["logits"])
     for s, t in zip(a["grads"], b["grads"]):
         assert np.array_equal(s["w"], t["w"]) and np.array_equal(s["b"], t["b"])
@@ -183,46 +184,46 @@ def test_at_rate_zero_it_is_the_dropout_free_restatement_exactly(name):
     assert all(np.array_equal(p, q) for p, q in zip(f32, fnet_pad.run(c["model"], c["x"][:5])))
 
 
-@pytest.mark.parametrize("name", fd.ROWS)
+@pytest.mark.parametrize("name", ftrain_rows.DROP_ROWS)
 def test_float32_and_float64_make_the_same_choices_on_the_gpu_tests_inputs(name):
     """The precondition of holding the GPU's gradient to float64 by a rounding bound, on the 17 rows and the counters (0 and 1)
     tests/test_gpu_ftrain_dropout.py uses: forward32 and float64 choose the same element of every window, the same sign under every
     ReLU and the same dropped-winner bit, and the smallest softmax probability is above 1e-4. If a row fails, give it another mask
-    seed in fdrop_ref.ROWS; never drop a row."""
+    seed in ftrain_rows.DROP_ROWS; never drop a row."""
     import fnet_pad
-    c = fd.case(name)
+    c = ftrain_rows.drop_case(name)
     m, x = c["model"], c["x"]
     for call in (0, 1):
-        ref = fd.reference(name, call)
+        ref = ftrain_rows.drop_reference(name, call)
         _, det = fd.forward32(m, x, c["sp"], c["seed"], call, detail=True)
-        for L, d, (first32, pos32, dropped32) in zip(gp.conv_records(m), ref["detail"], det):
+        for L, d, (first32, pos32, dropped32) in zip(fnet_ref.conv_records(m), ref["detail"], det):
             ph, pw = L["p"]
             Ph, Pw, oc = L["out"]
             assert np.array_equal(d["first"].reshape(len(x), -1, oc), first32), name
             assert np.array_equal(d["dropped"].reshape(len(x), -1, oc), dropped32), name
             if L["relu"]:
-                bordered = gp._border(d["pre"], fnet_pad.pads(L)[1], np.nan)[:, :Ph * ph, :Pw * pw]
+                bordered = ftrain_ref._border(d["pre"], fnet_pad.pads(L)[1], np.nan)[:, :Ph * ph, :Pw * pw]
                 pre64 = bordered.reshape(-1, Ph, ph, Pw, pw, oc).transpose(0, 1, 3, 2, 4, 5).reshape(len(x), -1, oc)
                 live = ~np.isnan(pre64[0, :, 0])
                 assert np.array_equal((pre64 > 0)[:, live], pos32[:, live]), name
         print("%s call %d: smallest softmax probability %.3g" % (name, call, ref["probs"].min()))
         assert ref["probs"].min() > 1e-4, (name, call, ref["probs"].min())
-    assert not np.array_equal(fd.reference(name, 0)["logits"], fd.reference(name, 1)["logits"])
+    assert not np.array_equal(ftrain_rows.drop_reference(name, 0)["logits"], ftrain_rows.drop_reference(name, 1)["logits"])
 
 
 def test_the_rows_cover_what_the_gpu_test_says_they_cover():
-    P = lambda name: [L["p"][0] * L["p"][1] for L in gp.conv_records(fd.case(name)["model"])]
+    P = lambda name: [L["p"][0] * L["p"][1] for L in fnet_ref.conv_records(ftrain_rows.drop_case(name)["model"])]
     assert set(P("p1_inc3")) == {1} and 2 in P("p2_pool12_no_relu_before") and 4 in P("p4_pool22_before") and 4 in P("p4_pool22_after")
-    c = fd.case("p2_pool12_no_relu_before")
-    assert not gp.conv_records(c["model"])[0]["relu"] and c["sp"][0] == (0.25, True)
-    c = fd.case("neg_no_relu_before")
-    assert not gp.conv_records(c["model"])[0]["relu"] and c["sp"][0][1]
-    d = fd.reference("neg_no_relu_before")["detail"][0]
+    c = ftrain_rows.drop_case("p2_pool12_no_relu_before")
+    assert not fnet_ref.conv_records(c["model"])[0]["relu"] and c["sp"][0] == (0.25, True)
+    c = ftrain_rows.drop_case("neg_no_relu_before")
+    assert not fnet_ref.conv_records(c["model"])[0]["relu"] and c["sp"][0][1]
+    d = ftrain_rows.drop_reference("neg_no_relu_before")["detail"][0]
     assert d["dropped"].any() and not d["dropped"].all()                    # with every value negative a dropped +0 wins its window
-    assert fd.case("pool21_before")["sp"][0][1] and not fd.case("pool21_after")["sp"][0][1]
-    rates = {r for name in fd.ROWS for r, _ in fd.case(name)["sp"]}
+    assert ftrain_rows.drop_case("pool21_before")["sp"][0][1] and not ftrain_rows.drop_case("pool21_after")["sp"][0][1]
+    rates = {r for name in ftrain_rows.DROP_ROWS for r, _ in ftrain_rows.drop_case(name)["sp"]}
     assert {0.25, 0.5, 0.2, 0.3} <= rates
-    assert len(fd.case("shipped_kws_conv")["sp"]) == 5
+    assert len(ftrain_rows.drop_case("shipped_kws_conv")["sp"]) == 5
     for name, spec in train.KERAS_DROPOUT.items():
         r, b = train.dropout_spec(spec)
         assert r[-1] == 0.0 and all(0 <= v < 1 for v in r) and len(r) == len(b), name
@@ -264,21 +265,32 @@ def test_fit_evaluates_validation_with_dropout_off_and_leaves_other_trainers_alo
     for t in (Scripted(on=False), Scripted(on=None), Scripted(on=None, keyword=False)):   # dropout off, or no such notion: today's calls
         train.fit(t, x, y, epochs=2, batch_size=4, val=(vx, vy))
         assert len(t.calls) == 8 and all(kw == {} for _, kw in t.calls)
-    host = fgrad_ref.HostTrainer(fd.case("pool21_after")["model"])          # no keyword, no dropout(): keeps working
-    c = fd.case("pool21_after")
+    c = ftrain_rows.drop_case("pool21_after")
+
+    class Minimal:                                                          # no keyword, no dropout(), no batchnorm(): keeps working
+        def __init__(self):
+            self.inner = ftrain_ref.HostTrainer(c["model"])
+
+        def grad(self, x, y):
+            return self.inner.grad(x, y)
+
+        def step(self, lr):
+            self.inner.step(lr)
+
+    host = Minimal()
     h = train.fit(host, c["x"], c["y"], epochs=1, batch_size=8, val=(c["x"], c["y"]))
     assert len(h["val_loss"]) == 1
 
 
 def test_host_trainer_counts_training_calls_only():
-    c = fd.case("pool21_before")
-    t = fd.HostTrainer(c["model"], c["dropout"], seed=c["seed"])
+    c = ftrain_rows.drop_case("pool21_before")
+    t = ftrain_ref.HostTrainer(c["model"], c["dropout"], seed=c["seed"])
     a = t.grad(c["x"], c["y"])
-    assert t.call == 1 and np.array_equal(a["loss"], fd.reference("pool21_before", 0)["loss"])
+    assert t.call == 1 and np.array_equal(a["loss"], ftrain_rows.drop_reference("pool21_before", 0)["loss"])
     e = t.grad(c["x"], c["y"], training=False)
-    assert t.call == 1 and np.array_equal(e["loss"], gp.loss_grad(c["model"], c["x"], c["y"])["loss"])
+    assert t.call == 1 and np.array_equal(e["loss"], ftrain_ref.loss_grad(c["model"], c["x"], c["y"])["loss"])
     b = t.grad(c["x"], c["y"])
-    assert t.call == 2 and np.array_equal(b["loss"], fd.reference("pool21_before", 1)["loss"])
+    assert t.call == 2 and np.array_equal(b["loss"], ftrain_rows.drop_reference("pool21_before", 1)["loss"])
 
 
 def test_all_four_gradient_kernels_use_no_scratch_and_fit_four_waves_a_simd(tmp_path):

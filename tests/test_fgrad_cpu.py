@@ -1,8 +1,8 @@
-"""The float64 restatement of training (tests/fgrad_ref.py) held to torch's float64 autograd and to central differences, the packed
+"""The float64 restatement of training (tests/ftrain_ref.py) held to torch's float64 autograd and to central differences, the packed
 layout of edison_amd/train.py held to the plan's (fnet_exact.plan), the Adam restatement held to torch.optim.Adam, the host side
 of fit: the shuffle and the two callbacks; and what tests/test_gpu_ftrain_tiles.py rests on: the order of a multi-tile call's sums
-(fgrad_ref.fold_tiles), what that order is sensitive to, what the float64 bound sees at these sizes, and the trainer's batch
-(fgrad_ref.train_batch). No GPU."""
+(ftrain_ref.fold_tiles), what that order is sensitive to, what the float64 bound sees at these sizes, and the trainer's batch
+(ftrain_ref.train_batch). No GPU."""
 import os
 
 import numpy as np
@@ -10,10 +10,11 @@ import pytest
 
 from edison_amd import cube_import, train
 
-import fgrad_ref
 import fnet_exact
 import fnet_ref
 import fnet_sweep
+import ftrain_ref
+import ftrain_rows
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROWS = ["ladder_k5", "pool21_trunc_h", "pool12_trunc_w", "pool22_trunc_hw", "pool41_tail", "inc3_oc64_oc65_s21", "oc40_s32_span_h", "n_out_210",
@@ -28,7 +29,7 @@ def _case(name, n=5):
         x = rows[np.arange(n) % rows.shape[0]]
     else:
         model = fnet_sweep.model(name)
-        x = fgrad_ref.inputs(name, n, int(np.prod(model["in_shape"])))
+        x = ftrain_ref.inputs(name, n, int(np.prod(model["in_shape"])))
     n_out = int(np.prod(fnet_ref.conv_records(model)[-1]["out"]))
     return model, x, (np.arange(n) % n_out).astype(np.int32)
 
@@ -37,8 +38,8 @@ def _case(name, n=5):
 def test_agrees_with_torch_float64_autograd(name):
     import torch
     model, x, y = _case(name)
-    ref = fgrad_ref.loss_grad(model, x, y)
-    tor = fgrad_ref.torch_grads(model, x, y, torch.float64)
+    ref = ftrain_ref.loss_grad(model, x, y)
+    tor = ftrain_ref.torch_grads(model, x, y, torch.float64)
     assert np.allclose(ref["logits"], tor["logits"], rtol=1e-10, atol=1e-12)
     assert np.allclose(ref["loss"], tor["loss"], rtol=1e-10, atol=1e-12)
     for i, (a, b) in enumerate(zip(ref["grads"], tor["grads"])):
@@ -48,7 +49,7 @@ def test_agrees_with_torch_float64_autograd(name):
 
 
 def test_inputs_leave_the_saturating_sets_out():
-    x = fgrad_ref.inputs("pool21_trunc_h", 9, 66)
+    x = ftrain_ref.inputs("pool21_trunc_h", 9, 66)
     assert x.shape == (9, 66) and np.abs(x).max() < 200          # n1, zero and neg (30 |g|) rows only
     assert (x[1] == 0).all() and (x[2] <= 0).all() and (x[4] == 0).all()
 
@@ -56,7 +57,7 @@ def test_inputs_leave_the_saturating_sets_out():
 @pytest.mark.parametrize("name", ["ladder_k5", "pool21_trunc_h"])
 def test_agrees_with_central_differences(name):
     model, x, y = _case(name, n=4)
-    ref = fgrad_ref.loss_grad(model, x, y)
+    ref = ftrain_ref.loss_grad(model, x, y)
     base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_ref.conv_records(model)]
     h = 1e-6
     for i, t in enumerate(base):
@@ -67,7 +68,7 @@ def test_agrees_with_central_differences(name):
                 for sgn in (1.0, -1.0):
                     w = [dict(w=u["w"].copy(), b=u["b"].copy()) for u in base]
                     w[i][k].reshape(-1)[j] += sgn * h
-                    vals.append(fgrad_ref.loss_grad(model, x, y, weights=w)["loss"].mean())
+                    vals.append(ftrain_ref.loss_grad(model, x, y, weights=w)["loss"].mean())
                 num[j] = (vals[0] - vals[1]) / (2 * h)
             g = ref["grads"][i][k].reshape(-1)
             # the loss is smooth between the kinks of ReLU and max: a central difference errs by O(h^2) |f'''| + rounding / h
@@ -82,11 +83,11 @@ def test_first_maximum_and_relu_at_zero():
         dense = dict(type=cube_import.T_CONV, inp=(1, 1, 1), out=(1, 1, 2), k=(1, 1), s=(1, 1), p=(1, 1), relu=0,
                      w=np.array([1.0, -1.0], np.float32).reshape(2, 1, 1, 1), b=np.zeros(2, np.float32))
         return dict(in_shape=(1, 2, 1), layers=[conv, dense, dict(type=cube_import.T_SOFTMAX, inp=(1, 1, 2), out=(1, 1, 2))])
-    tie = fgrad_ref.loss_grad(net(0, 0.5), np.array([[2.0, 2.0]]), [0])["grads"][0]
+    tie = ftrain_ref.loss_grad(net(0, 0.5), np.array([[2.0, 2.0]]), [0])["grads"][0]
     assert tie["w"].reshape(-1)[0] != 0                                    # x[0] = 2 reaches dW through element 0 ...
-    one = fgrad_ref.loss_grad(net(0, 0.5), np.array([[2.0, 1.0]]), [0])["grads"][0]
+    one = ftrain_ref.loss_grad(net(0, 0.5), np.array([[2.0, 1.0]]), [0])["grads"][0]
     assert tie["w"].reshape(-1)[0] == one["w"].reshape(-1)[0]              # ... and element 1 adds nothing
-    dead = fgrad_ref.loss_grad(net(1, 0.0), np.array([[0.0, 0.0]]), [0])["grads"][0]
+    dead = ftrain_ref.loss_grad(net(1, 0.0), np.array([[0.0, 0.0]]), [0])["grads"][0]
     assert dead["w"].reshape(-1)[0] == 0 and dead["b"][0] == 0             # ReLU'(0) = 0
 
 
@@ -121,23 +122,23 @@ def _routed_dw(model, x, y, pick):
     return dw, tied_first
 
 
-@pytest.mark.parametrize("pool", fgrad_ref.TIE_POOLS, ids=lambda p: "pool%d%d" % p)
+@pytest.mark.parametrize("pool", ftrain_ref.TIE_POOLS, ids=lambda p: "pool%d%d" % p)
 def test_tied_windows_send_the_gradient_to_their_first_element(pool):
     """The rows tests/test_gpu_ftrain.py holds the trainer's first-maximum choice to: windows tie exactly with their first maximum at
     every element that can tie, the restatement sends a tied window's gradient to its first maximum only, and the last maximum
     instead would move dW far beyond any rounding bound."""
     import torch
-    model, x, y = fgrad_ref.tie_case(pool)
+    model, x, y = ftrain_ref.tie_case(pool)
     assert fnet_ref.conv_records(model)[0]["relu"] == 0
-    ref = fgrad_ref.loss_grad(model, x, y)
+    ref = ftrain_ref.loss_grad(model, x, y)
     first, tied_first = _routed_dw(model, x, y, lambda at: at[0])
     assert (tied_first[:-1] > 0).all(), tied_first                          # a window's last element is never the first of several
-    assert fgrad_ref.tensor_error(ref["grads"][0]["w"], first) <= 1e-12
+    assert ftrain_ref.tensor_error(ref["grads"][0]["w"], first) <= 1e-12
     last, _ = _routed_dw(model, x, y, lambda at: at[-1])
-    assert fgrad_ref.tensor_error(last, first) > 1e-2
-    tor = fgrad_ref.torch_grads(model, x, y, torch.float64)
+    assert ftrain_ref.tensor_error(last, first) > 1e-2
+    tor = ftrain_ref.torch_grads(model, x, y, torch.float64)
     for a, b in zip(ref["grads"], tor["grads"]):
-        assert fgrad_ref.tensor_error(a["w"], b["w"]) <= 1e-10 and fgrad_ref.tensor_error(a["b"], b["b"]) <= 1e-10
+        assert ftrain_ref.tensor_error(a["w"], b["w"]) <= 1e-10 and ftrain_ref.tensor_error(a["b"], b["b"]) <= 1e-10
 
 
 @pytest.mark.parametrize("name", ["pool22_trunc_hw", "inc3_oc64_oc65_s21", "n_out_210", "ladder_k5"])
@@ -173,8 +174,8 @@ def fold_case():
     n = FOLD_TILES * FOLD_ROWS
     model, x, y = _case(FOLD_ROW, n)
     lay, w = train.layout(model)
-    whole = fgrad_ref.loss_grad(model, x, y)
-    T = np.stack([train.pack(fgrad_ref.loss_grad(model, x[j:j + FOLD_ROWS], y[j:j + FOLD_ROWS], n_total=n)["grads"], lay)
+    whole = ftrain_ref.loss_grad(model, x, y)
+    T = np.stack([train.pack(ftrain_ref.loss_grad(model, x[j:j + FOLD_ROWS], y[j:j + FOLD_ROWS], n_total=n)["grads"], lay)
                   for j in range(0, n, FOLD_ROWS)])
     assert T.shape == (FOLD_TILES, w) and T.dtype == np.float32
     return model, lay, x, y, whole, T
@@ -182,22 +183,22 @@ def fold_case():
 
 def test_fold_tiles_sums_a_batch_within_the_bound(fold_case):
     """Per-tile float64 gradients rounded to float32 and folded in the kernels' order: the whole batch's gradient within the GPU
-    tests' bound (tests/test_gpu_ftrain.py: bounds)."""
-    import test_gpu_ftrain as gt
+    tests' bound (ftrain_ref.bounds)."""
     model, lay, x, y, whole, T = fold_case
-    got = train.unpack(fgrad_ref.fold_tiles(T, FOLD_GRID, 1.0), lay)
-    per, _ = gt.bounds(model, x, y, whole)
-    for g, g64, (bw, bb, _, _) in zip(got, whole["grads"], per):
-        for k, bound in (("w", bw), ("b", bb)):
-            err = fgrad_ref.tensor_error(g[k], g64[k])
+    got = train.unpack(ftrain_ref.fold_tiles(T, FOLD_GRID, 1.0), lay)
+    per = ftrain_ref.bounds(model, x, y, whole)[0]
+    for g, g64, allowed in zip(got, whole["grads"], per):
+        for k in ("w", "b"):
+            bound = allowed[k][0]
+            err = ftrain_ref.tensor_error(g[k], g64[k])
             print("%s: %.3g (bound %.3g)" % (k, err, bound))
             assert err <= bound
-    one = fgrad_ref.fold_tiles(T[:3], FOLD_GRID, 1.0)                       # fewer tiles than workgroups: three slabs of one tile
+    one = ftrain_ref.fold_tiles(T[:3], FOLD_GRID, 1.0)                       # fewer tiles than workgroups: three slabs of one tile
     assert np.array_equal(one, (T[0] + T[1]) + T[2])
     with pytest.raises(AssertionError):
-        fgrad_ref.fold_tiles(T, FOLD_GRID, 3.0)
+        ftrain_ref.fold_tiles(T, FOLD_GRID, 3.0)
     with pytest.raises(AssertionError):
-        fgrad_ref.fold_tiles(T.astype(np.float64), FOLD_GRID, 1.0)
+        ftrain_ref.fold_tiles(T.astype(np.float64), FOLD_GRID, 1.0)
 
 
 def _bits(a):
@@ -209,36 +210,36 @@ def test_fold_tiles_sees_a_swapped_tile_and_a_flat_chain(fold_case):
     workgroups change places, when a workgroup's tiles are taken in another order than its slab adds them, and when all tiles are
     summed in one chain; a power-of-two scale changes nothing."""
     T = fold_case[5]
-    want = fgrad_ref.fold_tiles(T, FOLD_GRID, 1.0)
+    want = ftrain_ref.fold_tiles(T, FOLD_GRID, 1.0)
     swapped = T.copy()
     swapped[[3, FOLD_GRID + 4]] = T[[FOLD_GRID + 4, 3]]                      # workgroup 3's first tile and workgroup 4's second
-    assert not np.array_equal(_bits(fgrad_ref.fold_tiles(swapped, FOLD_GRID, 1.0)), _bits(want))
+    assert not np.array_equal(_bits(ftrain_ref.fold_tiles(swapped, FOLD_GRID, 1.0)), _bits(want))
     flat = T[0].copy()
     for j in range(1, len(T)):
         flat += T[j]
     assert not np.array_equal(_bits(flat), _bits(want))
-    assert not np.array_equal(_bits(fgrad_ref.fold_tiles(T, len(T), 1.0)), _bits(want))     # one tile per workgroup: the flat chain again
-    assert np.array_equal(_bits(fgrad_ref.fold_tiles(T, len(T), 1.0)), _bits(flat))
-    assert not np.array_equal(_bits(fgrad_ref.fold_tiles(T, FOLD_GRID // 2, 1.0)), _bits(want))   # another grid: another order
+    assert not np.array_equal(_bits(ftrain_ref.fold_tiles(T, len(T), 1.0)), _bits(want))     # one tile per workgroup: the flat chain again
+    assert np.array_equal(_bits(ftrain_ref.fold_tiles(T, len(T), 1.0)), _bits(flat))
+    assert not np.array_equal(_bits(ftrain_ref.fold_tiles(T, FOLD_GRID // 2, 1.0)), _bits(want))   # another grid: another order
     # the power-of-two argument on the host
-    assert np.array_equal(_bits(fgrad_ref.fold_tiles(T * np.float32(2.0 ** 9), FOLD_GRID, 2.0 ** -9)), _bits(want))
+    assert np.array_equal(_bits(ftrain_ref.fold_tiles(T * np.float32(2.0 ** 9), FOLD_GRID, 2.0 ** -9)), _bits(want))
 
 
 def test_a_lost_tile_moves_every_tensor_by_more_than_the_bound():
     """pool21_trunc_h at n = 8 229 on a grid of 256 workgroups of 16 rows: without workgroup 0's second tile (rows 4 096 .. 4 111)
     every tensor of the float64 gradient moves by more than the GPU tests' bound (the inputs were chosen so: the lowest ratio is
     record 0's bias, 9). A wrong row inside a tile or another order of the sum is far below it: the exact check is for those."""
-    import test_gpu_ftrain as gt
     n, b, grid = 8229, 16, 256
     model, x, y = _case(FOLD_ROW, n)
-    whole = fgrad_ref.loss_grad(model, x, y)
+    whole = ftrain_ref.loss_grad(model, x, y)
     rows = slice(grid * b, grid * b + b)
-    lost = fgrad_ref.loss_grad(model, x[rows], y[rows], n_total=n)["grads"]
-    per, _ = gt.bounds(model, x, y, whole)
+    lost = ftrain_ref.loss_grad(model, x[rows], y[rows], n_total=n)["grads"]
+    per = ftrain_ref.bounds(model, x, y, whole)[0]
     ratios = []
-    for i, (g64, t, (bw, bb, _, _)) in enumerate(zip(whole["grads"], lost, per)):
-        for k, bound in (("w", bw), ("b", bb)):
-            moved = fgrad_ref.tensor_error(g64[k] - t[k], g64[k])
+    for i, (g64, t, allowed) in enumerate(zip(whole["grads"], lost, per)):
+        for k in ("w", "b"):
+            bound = allowed[k][0]
+            moved = ftrain_ref.tensor_error(g64[k] - t[k], g64[k])
             print("record %d %s: moved %.3g, bound %.3g, ratio %.1f" % (i, k, moved, bound, moved / bound))
             ratios.append(moved / bound)
     assert min(ratios) > 1.0, ratios
@@ -252,24 +253,24 @@ def _plans():
 
 
 def test_train_batch_is_the_networks_except_where_dy_does_not_fit():
-    """fgrad_ref.train_batch (ftrain_size_lds and edison_ftrain_create's lowering loop restated) on every sweep row and the shipped
+    """ftrain_ref.train_batch (ftrain_size_lds and edison_ftrain_create's lowering loop restated) on every sweep row and the shipped
     network: only batch5 trains below its forward batch, at 2 of 5 -- dY of its first record, 1 064 rows x 16 padded channels an
     utterance, is 144 704 bytes with its row bases at 2 utterances and over the limit at 3."""
     plans = _plans()
     for name, p in plans.items():
-        tb = fgrad_ref.train_batch(p)
-        assert 1 <= tb <= p["batch"] and fgrad_ref.train_lds_bytes(p, tb) <= fnet_exact.LDS_BYTES, name
+        tb = ftrain_ref.train_batch(p)
+        assert 1 <= tb <= p["batch"] and ftrain_ref.train_lds_bytes(p, tb) <= fnet_exact.LDS_BYTES, name
         assert tb == (2 if name == "batch5" else p["batch"]), (name, tb, p["batch"])
-    assert plans["batch5"]["batch"] == 5 and fgrad_ref.train_batch(plans["cube_kws"]) == 7
+    assert plans["batch5"]["batch"] == 5 and ftrain_ref.train_batch(plans["cube_kws"]) == 7
     p = plans["batch5"]
     assert p["layers"][0]["rows"] == 1064 and p["layers"][0]["n_pad"] == 16
-    assert fgrad_ref.train_lds_bytes(p, 2) == 4 * 2128 * 16 + 4 * 2128 == 144704
-    assert fgrad_ref.train_lds_bytes(p, 3) > fnet_exact.LDS_BYTES
+    assert ftrain_ref.train_lds_bytes(p, 2) == 4 * 2128 * 16 + 4 * 2128 == 144704
+    assert ftrain_ref.train_lds_bytes(p, 3) > fnet_exact.LDS_BYTES
     # where the forward half is the larger one the bytes are the forward plan's: the shipped network's 159 808
-    assert fgrad_ref.train_lds_bytes(plans["cube_kws"], 7) == plans["cube_kws"]["lds_bytes"] == 159808
+    assert ftrain_ref.train_lds_bytes(plans["cube_kws"], 7) == plans["cube_kws"]["lds_bytes"] == 159808
     # a plan whose one utterance does not fit is refused (0), and a limit between two batches lowers by one
-    assert fgrad_ref.train_batch(p, limit=fgrad_ref.train_lds_bytes(p, 1) - 1) == 0
-    assert fgrad_ref.train_batch(p, limit=fgrad_ref.train_lds_bytes(p, 1)) == 1
+    assert ftrain_ref.train_batch(p, limit=ftrain_ref.train_lds_bytes(p, 1) - 1) == 0
+    assert ftrain_ref.train_batch(p, limit=ftrain_ref.train_lds_bytes(p, 1)) == 1
     # the new sweep row: forward batch 10, more packed floats than one pass of the step kernel covers on 256 CUs
     wide = plans["dense16_wide"]
     assert (wide["batch"], wide["n_layers"], fnet_sweep.w_floats(wide)) == (10, 16, 558928) and 558928 > fnet_sweep.STEP_PASS * 256
@@ -282,7 +283,7 @@ def test_adam_restatement_against_torch():
     ws = [w.copy() for w in w0]
     tw = [torch.tensor(w, dtype=torch.float64, requires_grad=True) for w in w0]
     opt = torch.optim.Adam(tw, lr=0.0005, betas=(0.9, 0.999), eps=1e-7)
-    adam = fgrad_ref.Adam()
+    adam = ftrain_ref.Adam()
     for step in range(5):
         gs = [rng.choice([-1.0, 1.0], w.shape) * rng.uniform(0.5, 2.0, w.shape) for w in w0]
         for t, g in zip(tw, gs):
@@ -298,7 +299,7 @@ def test_adam_restatement_against_torch():
 
 
 def test_adam_first_step_is_lr_sized():
-    adam = fgrad_ref.Adam()
+    adam = ftrain_ref.Adam()
     w = [np.array([1.0, -2.0, 3.0])]
     adam.step(w, [np.array([0.5, -4.0, 0.0])], 0.01)
     assert np.allclose(w[0], [1.0 - 0.01, -2.0 + 0.01, 3.0], atol=1e-7)  # m / sqrt(v) = sign(g) after bias correction
@@ -366,9 +367,9 @@ def test_reduce_lr_floor_and_early_stopping_reset():
 def test_fit_replay_in_float64_meets_the_gpu_tests_thresholds():
     """The condition tests/test_gpu_ftrain.py puts on the GPU's fit, met with room by the float64 replay: 40 Adam steps at batch 32,
     lr 0.01, seed 0 on the synthetic set halve the train loss and reach 0.9 accuracy."""
-    x, y = fgrad_ref.fit_set()
-    host = fgrad_ref.HostTrainer(fnet_sweep.model(fgrad_ref.FIT_ROW))
-    hist = train.fit(host, x, y, epochs=100, batch_size=fgrad_ref.FIT_BATCH, seed=0, lr=fgrad_ref.FIT_LR, max_steps=fgrad_ref.FIT_STEPS)
+    x, y = ftrain_rows.fit_set()
+    host = ftrain_ref.HostTrainer(fnet_sweep.model(ftrain_rows.FIT_ROW))
+    hist = train.fit(host, x, y, epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=ftrain_rows.FIT_STEPS)
     assert hist["steps"] == 40
     r = host.grad(x, y)
     print("first epoch loss %.4f, last %.4f; final loss on the set %.4f, accuracy %.3f" % (hist["loss"][0], hist["loss"][-1], r["loss"].mean(),

@@ -1,5 +1,5 @@
-"""The float64 restatement of training padded networks (tests/fgrad_pad_ref.py) held to torch's float64 autograd and to central
-differences, to fgrad_ref.loss_grad where every pad is zero, and to the first-present-maximum rule; what tests/test_gpu_ftrain_pad.py
+"""The float64 restatement of training (tests/ftrain_ref.py) on padded networks held to torch's float64 autograd and to central
+differences, to ftrain_ref.loss_grad where every pad is zero, and to the first-present-maximum rule; what tests/test_gpu_ftrain_pad.py
 rests on: that float32 and float64 choose the same pool winners and ReLU signs on the very inputs it uses, the trainer's batch with two
 ints per padded row, that the float64 replay of its fit meets its thresholds with room; and the compiler's resource remarks of both
 instantiations of ed_ftrain_grad_kernel. No GPU."""
@@ -12,20 +12,21 @@ import pytest
 
 from edison_amd import cube_import, train
 
-import fgrad_pad_ref as gp
-import fgrad_ref
 import fnet_exact
 import fnet_pad
+import fnet_ref
 import fnet_sweep
+import ftrain_ref
+import ftrain_rows
 
 
-@pytest.mark.parametrize("name", gp.ROWS)
+@pytest.mark.parametrize("name", ftrain_rows.PAD_ROWS)
 def test_agrees_with_torch_float64_autograd(name):
     import torch
-    m = gp.model(name)
-    x, y = gp.data(name, 5)
-    ref = gp.loss_grad(m, x, y)
-    tor = gp.torch_grads(m, x, y, torch.float64)
+    m = ftrain_rows.pad_model(name)
+    x, y = ftrain_rows.pad_data(name, 5)
+    ref = ftrain_ref.loss_grad(m, x, y)
+    tor = ftrain_ref.torch_grads(m, x, y, torch.float64)
     assert np.allclose(ref["logits"], tor["logits"], rtol=1e-10, atol=1e-12)
     assert np.allclose(ref["loss"], tor["loss"], rtol=1e-10, atol=1e-12)
     for i, (a, b) in enumerate(zip(ref["grads"], tor["grads"])):
@@ -39,10 +40,10 @@ def test_agrees_with_torch_float64_autograd(name):
 
 @pytest.mark.parametrize("name", ["asym_even", "pool41_lead"])
 def test_agrees_with_central_differences(name):
-    m = gp.model(name)
-    x, y = gp.data(name, 4)
-    ref = gp.loss_grad(m, x, y)
-    base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in gp.conv_records(m)]
+    m = ftrain_rows.pad_model(name)
+    x, y = ftrain_rows.pad_data(name, 4)
+    ref = ftrain_ref.loss_grad(m, x, y)
+    base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_ref.conv_records(m)]
     h = 1e-6
     for i, t in enumerate(base):
         for k in ("w", "b"):
@@ -52,7 +53,7 @@ def test_agrees_with_central_differences(name):
                 for sgn in (1.0, -1.0):
                     w = [dict(w=u["w"].copy(), b=u["b"].copy()) for u in base]
                     w[i][k].reshape(-1)[j] += sgn * h
-                    vals.append(gp.loss_grad(m, x, y, weights=w)["loss"].mean())
+                    vals.append(ftrain_ref.loss_grad(m, x, y, weights=w)["loss"].mean())
                 num[j] = (vals[0] - vals[1]) / (2 * h)
             g = ref["grads"][i][k].reshape(-1)
             # as tests/test_fgrad_cpu.py: O(h^2) |f'''| + rounding / h between the kinks of ReLU and max
@@ -61,30 +62,40 @@ def test_agrees_with_central_differences(name):
 
 @pytest.mark.parametrize("name", ["pool22_trunc_hw", "inc3_oc64_oc65_s21"])
 def test_without_pads_it_is_the_unpadded_restatement(name):
+    """One restatement serves padded and unpadded networks: a record without cpad / ppad borders nothing. The same bits with the keys
+    absent and with explicit zero pads, the forward half fnet_pad's own float64 one, the live rows the truncated map Ph ph x Pw pw,
+    and a plan without a padded record one int a row."""
     m = fnet_sweep.model(name)
-    x = fgrad_ref.inputs(name, 5, int(np.prod(m["in_shape"])))
-    y = (np.arange(5) % int(np.prod(gp.conv_records(m)[-1]["out"]))).astype(np.int32)
-    a, b = gp.loss_grad(m, x, y), fgrad_ref.loss_grad(m, x, y)
+    recs = fnet_ref.conv_records(m)
+    assert not any("cpad" in L or "ppad" in L for L in recs)
+    zeros = dict(m, layers=[dict(L, cpad=fnet_pad.Z4, ppad=fnet_pad.Z4) if L in recs else L for L in m["layers"]])
+    x = ftrain_ref.inputs(name, 5, int(np.prod(m["in_shape"])))
+    y = (np.arange(5) % int(np.prod(recs[-1]["out"]))).astype(np.int32)
+    a, b = ftrain_ref.loss_grad(zeros, x, y), ftrain_ref.loss_grad(m, x, y)
     assert np.array_equal(a["loss"], b["loss"]) and np.array_equal(a["logits"], b["logits"])
     for s, t in zip(a["grads"], b["grads"]):
         assert np.array_equal(s["w"], t["w"]) and np.array_equal(s["b"], t["b"])
-    assert gp.terms(m, 5) == fgrad_ref.terms(m, 5)
+    assert np.allclose(b["logits"], fnet_pad.run64(m, x)[-1], rtol=1e-12, atol=1e-12)
+    assert ftrain_ref.terms(zeros, 5) == ftrain_ref.terms(m, 5) == [5 * L["out"][0] * L["p"][0] * L["out"][1] * L["p"][1] for L in recs]
     p = fnet_exact.plan(fnet_sweep.blob(name))
-    for L in p["layers"]:
-        L["pad"] = False
-    assert gp.train_batch(p) == fgrad_ref.train_batch(p) and gp.train_lds_bytes(p, p["batch"]) == fgrad_ref.train_lds_bytes(p, p["batch"])
+    assert not any("pad" in L for L in p["layers"])
+    q = dict(p, layers=[dict(L, pad=False) for L in p["layers"]])
+    assert ftrain_ref.train_batch(q) == ftrain_ref.train_batch(p) and ftrain_ref.train_lds_bytes(q, p["batch"]) == ftrain_ref.train_lds_bytes(p, p["batch"])
+    mp = [(p["batch"] * L["rows"] + 15) // 16 * 16 for L in p["layers"]]
+    backward = dict(p, buf_n=[0] * len(p["buf_n"]), w_lds=0, k_lds=0)
+    assert ftrain_ref.train_lds_bytes(backward, p["batch"]) == 4 * max(r * L["n_pad"] for r, L in zip(mp, p["layers"])) + 4 * max(mp)
 
 
-@pytest.mark.parametrize("pool", gp.TIE_POOLS, ids=lambda p: "pool%d%d" % p)
+@pytest.mark.parametrize("pool", ftrain_ref.TIE_PADS, ids=lambda p: "pool%d%d" % p)
 def test_tied_windows_send_the_gradient_to_their_first_present_element(pool):
     """The rows tests/test_gpu_ftrain_pad.py holds the trainer's choice to: window 0 has an absent element leading, window 1 two
     trailing; channel 2's present elements all tie. The restatement sends such a window's gradient to its first present element
     only; the last maximum instead moves dW far beyond any rounding bound; an absent element never gets any."""
     import torch
-    m, x, y = gp.tie_case(pool)
-    conv = gp.conv_records(m)[0]
-    assert conv["relu"] == 0 and fnet_pad.conv_map(conv) == (5, 5) and gp.live(conv) == 25
-    ref = gp.loss_grad(m, x, y, detail=True)
+    m, x, y = ftrain_ref.tie_case(pool, ppad=ftrain_ref.TIE_PADS[pool])
+    conv = fnet_ref.conv_records(m)[0]
+    assert conv["relu"] == 0 and fnet_pad.conv_map(conv) == (5, 5) and ftrain_ref.live(conv) == 25
+    ref = ftrain_ref.loss_grad(m, x, y, detail=True)
     d = ref["detail"][0]
     axis = 0 if pool[0] == 4 else 1
     first = np.moveaxis(d["first"], 1 + axis, 1)                            # [n][window along the pooled axis][other][oc]
@@ -97,11 +108,11 @@ def test_tied_windows_send_the_gradient_to_their_first_present_element(pool):
         assert ((w0 == w0.max(axis=1, keepdims=True)).sum(axis=1) > 1).any() and ((w1 == w1.max(axis=1, keepdims=True)).sum(axis=1) > 1).any()
     dy = np.moveaxis(d["dy"], 1 + axis, 1)[..., 2]                          # channel 2: conv rows 0 and 3 take everything
     assert (dy[:, [1, 2, 4]] == 0).all() and (dy[:, [0, 3]] != 0).all()
-    last = gp.loss_grad(m, x, y, pick="last")
-    assert fgrad_ref.tensor_error(last["grads"][0]["w"], ref["grads"][0]["w"]) > 1e-2
-    tor = gp.torch_grads(m, x, y, torch.float64)
+    last = ftrain_ref.loss_grad(m, x, y, pick="last")
+    assert ftrain_ref.tensor_error(last["grads"][0]["w"], ref["grads"][0]["w"]) > 1e-2
+    tor = ftrain_ref.torch_grads(m, x, y, torch.float64)
     for a, b in zip(ref["grads"], tor["grads"]):
-        assert fgrad_ref.tensor_error(a["w"], b["w"]) <= 1e-10 and fgrad_ref.tensor_error(a["b"], b["b"]) <= 1e-10
+        assert ftrain_ref.tensor_error(a["w"], b["w"]) <= 1e-10 and ftrain_ref.tensor_error(a["b"], b["b"]) <= 1e-10
     # the blob of such a network is version 2 and the plan counts the absent rows
     p = fnet_pad.plan(cube_import.build_blob(m))
     assert p["layers"][0]["pad"] and p["layers"][0]["rows"] == 40 and p["layers"][0]["live"] == 25
@@ -111,7 +122,7 @@ def _float32_choices(m, x):
     """Per record (first [n][Ph][Pw][oc], positive [n][rows][oc], live [rows]) of the bit-exact float32 host model of the kernel
     (fnet_pad.pre_activation), each record fed the float32 output of the one before, rows in the kernel's order r = q P + e."""
     out, a = [], np.asarray(x, np.float32)
-    for L in gp.conv_records(m):
+    for L in fnet_ref.conv_records(m):
         Ph, Pw, oc = L["out"]
         P = L["p"][0] * L["p"][1]
         v, live = fnet_pad.pre_activation(L, a)
@@ -122,53 +133,53 @@ def _float32_choices(m, x):
     return out
 
 
-@pytest.mark.parametrize("name", gp.ROWS)
+@pytest.mark.parametrize("name", ftrain_rows.PAD_ROWS)
 def test_float32_and_float64_make_the_same_choices_on_the_gpu_tests_inputs(name):
     """The precondition of holding the GPU's gradient to float64 by a rounding bound: on the 17 rows tests/test_gpu_ftrain_pad.py uses
     (50 on the rows it also runs at 3 x batch + 2),
     the bit-exact float32 model of the kernel and float64 choose the same element of every pool window and the same sign under every
-    ReLU, and no softmax saturates. If a change of seeds breaks this, move the seed offset of fgrad_pad_ref.data; never drop a row."""
-    m = gp.model(name)
-    x, y = gp.data(name, gp.n_max(name))
-    ref = gp.loss_grad(m, x, y, detail=True)
-    for L, d, (first32, pos32, live) in zip(gp.conv_records(m), ref["detail"], _float32_choices(m, x)):
+    ReLU, and no softmax saturates. If a change of seeds breaks this, move the seed offset of ftrain_rows.pad_data; never drop a row."""
+    m = ftrain_rows.pad_model(name)
+    x, y = ftrain_rows.pad_data(name, ftrain_rows.n_max(name))
+    ref = ftrain_ref.loss_grad(m, x, y, detail=True)
+    for L, d, (first32, pos32, live) in zip(fnet_ref.conv_records(m), ref["detail"], _float32_choices(m, x)):
         ph, pw = L["p"]
         Ph, Pw, oc = L["out"]
         assert np.array_equal(d["first"], first32), name
-        bordered = gp._border(d["pre"], fnet_pad.pads(L)[1], np.nan)[:, :Ph * ph, :Pw * pw]
+        bordered = ftrain_ref._border(d["pre"], fnet_pad.pads(L)[1], np.nan)[:, :Ph * ph, :Pw * pw]
         pre64 = bordered.reshape(-1, Ph, ph, Pw, pw, oc).transpose(0, 1, 3, 2, 4, 5).reshape(len(x), -1, oc)
         assert np.array_equal(np.isnan(pre64[0, :, 0]), ~live)
         if L["relu"]:
             assert np.array_equal((pre64 > 0)[:, live], pos32[:, live]), name
-        if name == gp.NEG_T and L is gp.conv_records(m)[0]:
+        if name == ftrain_rows.NEG_T and L is fnet_ref.conv_records(m)[0]:
             assert (pre64[:, live] < 0).all()                               # an absent element that became 0 would win its window
     print("%s: smallest softmax probability %.3g" % (name, ref["probs"].min()))
     assert ref["probs"].min() > 1e-4, (name, ref["probs"].min())
 
 
 def test_neg_no_relu_t_is_negative_everywhere():
-    m = gp.model(gp.NEG_T)
-    x, y = gp.data(gp.NEG_T)
-    assert (x < 0).all() and not gp.conv_records(m)[0]["relu"]
-    ref = gp.loss_grad(m, x, y, detail=True)
+    m = ftrain_rows.pad_model(ftrain_rows.NEG_T)
+    x, y = ftrain_rows.pad_data(ftrain_rows.NEG_T)
+    assert (x < 0).all() and not fnet_ref.conv_records(m)[0]["relu"]
+    ref = ftrain_ref.loss_grad(m, x, y, detail=True)
     assert all((d["pre"] < 0).all() for d in ref["detail"])                 # every present pre-activation, the logits included
     assert ref["probs"].min() > 1e-4
-    zero = fnet_pad.layer(gp.conv_records(m)[0], x, absent=0.0)             # what an absent 0 would do: win the windows it is in
-    assert (zero == 0).any() and (fnet_pad.layer(gp.conv_records(m)[0], x) < 0).all()
+    zero = fnet_pad.layer(fnet_ref.conv_records(m)[0], x, absent=0.0)             # what an absent 0 would do: win the windows it is in
+    assert (zero == 0).any() and (fnet_pad.layer(fnet_ref.conv_records(m)[0], x) < 0).all()
 
 
 LOWERED = {"mid_pads_batch": 5, "simple_conv": 6}      # row -> the batch it trains at, where that is below its forward batch (7, 16)
 
 
 def test_train_batch_with_two_ints_per_padded_row():
-    """fgrad_pad_ref.train_batch on every row: all train at their forward batch but mid_pads_batch (5 of 7) and simple_conv (6 of 16:
+    """ftrain_ref.train_batch on every padded row: all train at their forward batch but mid_pads_batch (5 of 7) and simple_conv (6 of 16:
     its stride-1 'same' conv keeps the whole 31 x 13 map, 16 padded channels of dY and two ints a row); the rule itself on
     pool41_lead's plan and on a limit between two batches."""
-    for name in gp.ROWS:
-        p = fnet_pad.plan(gp.blob(name))
-        tb = gp.train_batch(p)
-        print("%s: forward batch %d, trains at %d, %d bytes" % (name, p["batch"], tb, gp.train_lds_bytes(p, tb)))
-        assert 1 <= tb <= p["batch"] and gp.train_lds_bytes(p, tb) <= fnet_exact.LDS_BYTES
+    for name in ftrain_rows.PAD_ROWS:
+        p = fnet_pad.plan(ftrain_rows.pad_blob(name))
+        tb = ftrain_ref.train_batch(p)
+        print("%s: forward batch %d, trains at %d, %d bytes" % (name, p["batch"], tb, ftrain_ref.train_lds_bytes(p, tb)))
+        assert 1 <= tb <= p["batch"] and ftrain_ref.train_lds_bytes(p, tb) <= fnet_exact.LDS_BYTES
         assert tb == LOWERED.get(name, p["batch"]), (name, tb, p["batch"])
     p = fnet_pad.plan(fnet_pad.blob("pool41_lead"))
     L = p["layers"][0]
@@ -177,19 +188,20 @@ def test_train_batch_with_two_ints_per_padded_row():
     # one int more per row than the unpadded rule counts, visible where the backward half is the larger one
     lim = 4 * mp * L["n_pad"] + 8 * mp
     fwd = 4 * (16 * sum(p["buf_n"]) + p["w_lds"]) + 4 * p["k_lds"]
-    assert gp.train_lds_bytes(p, 16) == max(fwd, lim)
+    assert ftrain_ref.train_lds_bytes(p, 16) == max(fwd, lim)
     small = dict(p, buf_n=[0, 0], w_lds=0, k_lds=0)                         # the backward half alone
-    assert gp.train_lds_bytes(small, 16) == lim and fgrad_ref.train_lds_bytes(small, 16) == lim - 4 * mp
-    assert gp.train_batch(small, limit=lim) == 16 and gp.train_batch(small, limit=lim - 1) == 15
-    assert gp.train_batch(small, limit=gp.train_lds_bytes(small, 1) - 1) == 0
+    unpadded = dict(small, layers=[dict(R, pad=False) for R in small["layers"]])
+    assert ftrain_ref.train_lds_bytes(small, 16) == lim and ftrain_ref.train_lds_bytes(unpadded, 16) == lim - 4 * mp
+    assert ftrain_ref.train_batch(small, limit=lim) == 16 and ftrain_ref.train_batch(small, limit=lim - 1) == 15
+    assert ftrain_ref.train_batch(small, limit=ftrain_ref.train_lds_bytes(small, 1) - 1) == 0
 
 
 def test_fit_replay_in_float64_meets_the_gpu_tests_thresholds():
     """The condition tests/test_gpu_ftrain_pad.py puts on the GPU's fit (loss below half its first value, accuracy 0.9), met with room
     by the float64 replay on the padded restatement: 40 Adam steps at batch 32, lr 0.01, seed 0."""
-    x, y = gp.fit_set()
-    host = gp.HostTrainer(gp.model(gp.FIT_ROW))
-    hist = train.fit(host, x, y, epochs=100, batch_size=fgrad_ref.FIT_BATCH, seed=0, lr=fgrad_ref.FIT_LR, max_steps=fgrad_ref.FIT_STEPS)
+    x, y = ftrain_rows.pad_fit_set()
+    host = ftrain_ref.HostTrainer(ftrain_rows.pad_model(ftrain_rows.PAD_FIT_ROW))
+    hist = train.fit(host, x, y, epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=ftrain_rows.FIT_STEPS)
     assert hist["steps"] == 40
     r = host.grad(x, y)
     print("first epoch loss %.4f, last %.4f; final loss on the set %.4f, accuracy %.3f" % (hist["loss"][0], hist["loss"][-1], r["loss"].mean(),

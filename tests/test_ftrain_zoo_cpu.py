@@ -1,5 +1,5 @@
 """CPU checks of training from scratch: train.get_model's eight architectures against the shapes the tests
-already compute, their initialisation, the blob round trip; the Adadelta restatements (fdata_ref) against torch and each other; the
+already compute, their initialisation, the blob round trip; the Adadelta restatements (ftrain_ref) against torch and each other; the
 float64 host trainer learning the synthetic set from a get_model network; the new options of ``kws train``."""
 import os
 
@@ -8,17 +8,17 @@ import pytest
 
 from conftest import GOLDEN
 
-import fdata_ref
-import fgrad_ref
 import fnet_pad
 import fnet_sweep as fs
+import ftrain_ref
+import ftrain_rows
 from edison_amd import cube_import, train
 from edison_amd.kws import kws_train
 
 SHAPE_KEYS = ("inp", "out", "k", "s", "p", "relu", "cpad", "ppad")
 # the from-scratch fit tests (here in float64, tests/test_gpu_ftrain_data.py on the GPU): the architecture and the steps at which the
-# float64 host trainer meets test_fit_learns_the_synthetic_set's conditions on fgrad_ref.fit_set()
-SCRATCH_ARCH, SCRATCH_STEPS = "single_fc", fgrad_ref.FIT_STEPS
+# float64 host trainer meets test_fit_learns_the_synthetic_set's conditions on ftrain_rows.fit_set()
+SCRATCH_ARCH, SCRATCH_STEPS = "single_fc", ftrain_rows.FIT_STEPS
 
 
 def shapes(model):
@@ -26,7 +26,7 @@ def shapes(model):
 
 
 def scratch_model():
-    return train.get_model(SCRATCH_ARCH, fs.model(fgrad_ref.FIT_ROW)["in_shape"], fgrad_ref.FIT_CLASSES)
+    return train.get_model(SCRATCH_ARCH, fs.model(ftrain_rows.FIT_ROW)["in_shape"], ftrain_rows.FIT_CLASSES)
 
 
 @pytest.mark.parametrize("name", fnet_pad.ZOO)
@@ -103,7 +103,7 @@ def test_the_adadelta_restatement_is_torchs():
     w0, gs = adadelta_case(5)
     p = torch.nn.Parameter(torch.tensor(w0, dtype=torch.float64))
     opt = torch.optim.Adadelta([p], lr=1.0, rho=0.95, eps=1e-7)
-    ref, w = fdata_ref.Adadelta(0.95, 1e-7), [w0.copy()]
+    ref, w = ftrain_ref.Adadelta(0.95, 1e-7), [w0.copy()]
     for g in gs:
         p.grad = torch.tensor(g, dtype=torch.float64)
         opt.step()
@@ -116,7 +116,7 @@ def test_the_adadelta_restatement_is_torchs():
 
 def test_the_float32_arithmetic_of_the_kernel_meets_the_gpu_tests_bound():
     w0, gs = adadelta_case(3)
-    ref, k32 = fdata_ref.Adadelta(0.95, 1e-7), fdata_ref.Adadelta32(0.95, 1e-7)
+    ref, k32 = ftrain_ref.Adadelta(0.95, 1e-7), ftrain_ref.Adadelta32(0.95, 1e-7)
     w32 = [w0.astype(np.float32)]
     for i, g in enumerate(gs):
         g32 = g.astype(np.float32)
@@ -124,22 +124,89 @@ def test_the_float32_arithmetic_of_the_kernel_meets_the_gpu_tests_bound():
         want = [w32[0].astype(np.float64)]
         ref.step(want, [g32.astype(np.float64)], 1.0)
         k32.step(w32, [g32], 1.0)
-        err = fdata_ref.tensor_error(w32[0], want[0])
-        print("step %d: %.3g (bound %.3g)" % (i + 1, err, 4 * fdata_ref.EPS32))
-        assert err <= 4 * fdata_ref.EPS32
+        err = ftrain_ref.tensor_error(w32[0], want[0])
+        print("step %d: %.3g (bound %.3g)" % (i + 1, err, 4 * ftrain_ref.EPS32))
+        assert err <= 4 * ftrain_ref.EPS32
 
 
 # ---- from scratch, in float64 ----------------------------------------------------------------------------------------------------------
 def test_the_host_trainer_learns_the_synthetic_set_from_a_get_model_network():
     """test_fit_learns_the_synthetic_set's set and conditions on a freshly initialised network: the GPU test's architecture and steps."""
-    x, y = fgrad_ref.fit_set()
+    x, y = ftrain_rows.fit_set()
     model = scratch_model()
-    host = fgrad_ref.HostTrainer(model)
-    hist = train.fit(host, x, y, epochs=100, batch_size=fgrad_ref.FIT_BATCH, seed=0, lr=fgrad_ref.FIT_LR, max_steps=SCRATCH_STEPS)
+    host = ftrain_ref.HostTrainer(model)
+    hist = train.fit(host, x, y, epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=SCRATCH_STEPS)
     acc = (host.grad(x, y)["argmax"] == y).mean()
     print("%s, %d steps: loss %.5f -> %.5f, accuracy %.3f" % (SCRATCH_ARCH, hist["steps"], hist["loss"][0], hist["loss"][-1], acc))
     assert hist["steps"] == SCRATCH_STEPS
     assert hist["loss"][-1] < 0.5 * hist["loss"][0] and acc >= 0.9
+
+
+# ---- fit and fit_data: one epoch loop ----------------------------------------------------------------------------------------------------
+FIT_SETTINGS = {
+    "validation_and_callbacks": dict(batch_size=32, epochs=3, val=True, steps=9, epochs_run=3),
+    "short_last_batch": dict(batch_size=40, epochs=2, steps=6, epochs_run=2),                     # 40 + 40 + 16 rows
+    "max_steps_inside_the_second_epoch": dict(batch_size=32, epochs=3, max_steps=4, steps=4, epochs_run=2),
+}
+
+
+@pytest.mark.parametrize("setting", sorted(FIT_SETTINGS))
+def test_fit_data_is_fit_on_the_host(setting):
+    """train.fit_data on a HostData gives train.fit's history, == on the float lists: the same epoch loop around a trainer whose epoch
+    and evaluate loop over grad and step in fit's order and sum as fit sums."""
+    kw = dict(FIT_SETTINGS[setting])
+    steps, epochs_run, with_val = kw.pop("steps"), kw.pop("epochs_run"), kw.pop("val", False)
+    x, y = ftrain_rows.fit_set()
+    m = fs.model(ftrain_rows.FIT_ROW)
+    val = (x[60:], y[60:]) if with_val else None
+    a, b = ftrain_ref.HostTrainer(m), ftrain_ref.HostTrainer(m)
+    ha = train.fit(a, x, y, val=val, seed=0, lr=ftrain_rows.FIT_LR, **kw)
+    hb = train.fit_data(b, ftrain_ref.HostData(x, y), val=ftrain_ref.HostData(*val) if with_val else None, seed=0, lr=ftrain_rows.FIT_LR, **kw)
+    assert ha == hb, (ha, hb)
+    assert set(ha) == {"loss", "acc", "val_loss", "val_acc", "lr", "steps", "stopped_early"}
+    assert ha["steps"] == steps and len(ha["loss"]) == len(ha["acc"]) == len(ha["lr"]) == epochs_run
+    assert len(ha["val_loss"]) == len(ha["val_acc"]) == (epochs_run if with_val else 0)
+    assert all(np.array_equal(s[k], t[k]) for s, t in zip(a.weights, b.weights) for k in ("w", "b"))
+    assert ha["loss"][-1] < ha["loss"][0]
+
+
+class Replayed:
+    """A trainer that replays fixed numbers through both interfaces: training loss 1.25 a row, validation loss 0.5 a row, every
+    prediction class 0."""
+
+    def __init__(self):
+        self.lrs = []
+
+    def grad(self, x, y, **kw):
+        return dict(loss=np.full(len(y), 0.5 if x.shape[1] == 2 else 1.25), argmax=np.zeros(len(y), np.int32))   # the validation set is marked by its width
+
+    def step(self, lr):
+        self.lrs.append(lr)
+
+    def epoch(self, data, order, batch, lr, max_steps):
+        steps = (len(order) + batch - 1) // batch
+        self.lrs += [lr] * steps
+        return dict(loss_sum=1.25 * len(order), hits=int((data.y[order] == 0).sum()), seen=len(order), steps=steps)
+
+    def evaluate(self, data):
+        return dict(loss_sum=0.5 * data.n, hits=int((data.y == 0).sum()), seen=data.n, steps=0)
+
+
+def test_a_constant_validation_loss_halves_the_rate_every_epoch_and_stops_after_eleven():
+    """The callbacks' paths through the shared loop, from their code: the first epoch sets the best loss; ReduceLROnPlateau (patience 1)
+    halves the rate after every later epoch; EarlyStopping (patience 10) stops on the tenth epoch in a row that does not improve."""
+    n, lr0 = 7, 0.01
+    x, y = np.arange(n, dtype=np.float32).reshape(n, 1), (np.arange(n) % 2).astype(np.int32)
+    vx, vy = np.zeros((3, 2), np.float32), np.array([0, 1, 0], np.int32)
+    a, b = Replayed(), Replayed()
+    ha = train.fit(a, x, y, epochs=20, batch_size=3, val=(vx, vy), seed=4, lr=lr0)
+    hb = train.fit_data(b, ftrain_ref.HostData(x, y), epochs=20, batch_size=3, val=ftrain_ref.HostData(vx, vy), seed=4, lr=lr0)
+    for h, t in ((ha, a), (hb, b)):
+        assert len(h["loss"]) == len(h["val_loss"]) == 11 and h["stopped_early"] and h["steps"] == 33
+        assert h["lr"] == [lr0 * 2.0 ** -max(k - 1, 0) for k in range(11)]
+        assert t.lrs == [v for v in h["lr"] for _ in range(3)]
+        assert h["loss"] == [1.25] * 11 and h["val_loss"] == [0.5] * 11 and h["acc"] == [4 / 7] * 11 and h["val_acc"] == [2 / 3] * 11
+    assert ha == hb
 
 
 # ---- the command line ------------------------------------------------------------------------------------------------------------------

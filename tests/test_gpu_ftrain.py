@@ -1,5 +1,5 @@
 """GPU tests (-m gpu) of training the float32 network (edison_ftrain_*, Context.trainer, kws train) against
-tests/fgrad_ref.py, the float64 restatement on the float32 weights.
+tests/ftrain_ref.py, the float64 restatement on the float32 weights.
 
 The gradient bound is measured, not chosen: per tensor the metric is max |g - g64| / max |g64|; torch's CPU float32 autograd of the same
 network gets e32 by that metric at run time, and the GPU is allowed 4 e32 -- both are float32 sums of the same terms in different orders
@@ -10,7 +10,7 @@ held the same way, its terms the k rows along the network plus the logits.
 Every network is loaded with 1e6 in the padding k rows, padding channels and padding biases of its blob: the packed gradient's padding
 must still be exactly +0.0f and a step must leave the weights' padding what it was.
 
-Calls of more tiles than workgroups are tests/test_gpu_ftrain_tiles.py's; the helpers here (case, data, poisoned, bounds,
+Calls of more tiles than workgroups are tests/test_gpu_ftrain_tiles.py's; the helpers here (case, data, poisoned,
 check_gradient, check_plan) are shared with it.
 
 Measured on an MI355X, shipped network, n = 8 (GPU error / e32 per tensor, w then b): see DESIGN.md section 19."""
@@ -22,11 +22,12 @@ import pytest
 
 from conftest import GOLDEN
 
-import fgrad_ref
 import fnet_exact
 import fnet_pad
 import fnet_ref
 import fnet_sweep as fs
+import ftrain_ref
+import ftrain_rows
 from edison_amd import _lib, cube_import, train
 
 pytestmark = pytest.mark.gpu
@@ -40,9 +41,9 @@ EPS = 2.0 ** -24
 
 
 def check_plan(blob, info):
-    """The trainer's batch and LDS bytes are the restated plan's (fgrad_ref.train_batch: ftrain_size_lds and the lowering loop)."""
+    """The trainer's batch and LDS bytes are the restated plan's (ftrain_ref.train_batch: ftrain_size_lds and the lowering loop)."""
     p = fnet_exact.plan(blob)
-    assert info["batch"] == fgrad_ref.train_batch(p) and info["lds_bytes"] == fgrad_ref.train_lds_bytes(p, info["batch"]), (info, p["batch"])
+    assert info["batch"] == ftrain_ref.train_batch(p) and info["lds_bytes"] == ftrain_ref.train_lds_bytes(p, info["batch"]), (info, p["batch"])
     return p
 
 
@@ -99,34 +100,20 @@ def data(name, model, n):
         assert fs.ROWS[name][0]["sets"] == ["neg", "n1"]
         x = np.ascontiguousarray(fs.inputs(name, 2 * n, in_n)[0::2])      # its all-negative inputs: every ReLU logit is zero
     else:
-        x = fgrad_ref.inputs(name, n, in_n)
+        x = ftrain_ref.inputs(name, n, in_n)
     n_out = int(np.prod(fnet_ref.conv_records(model)[-1]["out"]))
     return x, (np.arange(n) % n_out).astype(np.int32)
-
-
-def bounds(model, x, y, ref, n_total=None):
-    """Per record (bound of w, bound of b, e32 of w, e32 of b) and the loss's (bound, e32): 4 e32 floored at 8 x 2^-24 sqrt(terms)."""
-    import torch
-    t32 = fgrad_ref.torch_grads(model, x, y, torch.float32)
-    scale = 1.0 if n_total is None else len(y) / n_total               # torch's mean is over the rows it is given
-    out = []
-    for g32, g64, terms in zip(t32["grads"], ref["grads"], fgrad_ref.terms(model, len(y))):
-        floor = 8 * EPS * np.sqrt(terms)
-        e = [fgrad_ref.tensor_error(g32[k] * scale, g64[k]) for k in ("w", "b")]
-        out.append((max(4 * e[0], floor), max(4 * e[1], floor), e[0], e[1]))
-    chain = sum(int(np.prod(L["k"])) * L["inp"][2] for L in fnet_ref.conv_records(model)) + ref["logits"].shape[1]
-    el = fgrad_ref.tensor_error(t32["loss"], ref["loss"])
-    return out, (max(4 * el, 8 * EPS * np.sqrt(chain)), el)
 
 
 def check_gradient(name, tr, model, real, x, y, ref, n_total=None, report=None):
     got = tr.gradients()
     packed = tr.gradient()
     assert not packed[~real].view(np.uint32).any(), "%s: a padding entry of the gradient is not +0.0f" % name
-    per, _ = bounds(model, x, y, ref, n_total)
-    for i, (g, g64, (bw, bb, ew, eb)) in enumerate(zip(got, ref["grads"], per)):
-        for k, bound, e32 in (("w", bw, ew), ("b", bb, eb)):
-            err = fgrad_ref.tensor_error(g[k], g64[k])
+    per = ftrain_ref.bounds(model, x, y, ref, n_total)[0]
+    for i, (g, g64, allowed) in enumerate(zip(got, ref["grads"], per)):
+        for k in ("w", "b"):
+            bound, e32 = allowed[k]
+            err = ftrain_ref.tensor_error(g[k], g64[k])
             line = "%s n=%d record %d %s: gpu %.3g  e32 %.3g  bound %.3g" % (name, len(y), i, k, err, e32, bound)
             print(line)
             if report is not None:
@@ -148,15 +135,15 @@ def test_logits_loss_gradient_padding_repeat_and_no_side_effect(ctx, name):
         w0 = tr.packed_weights()
         for n in ns:
             x, y = data(name, model, n)
-            ref = fgrad_ref.loss_grad(model, x, y)
+            ref = ftrain_ref.loss_grad(model, x, y)
             before = ctx.fnet(x)
             r = tr.grad(x, y)
             # 1. the logits, bit for bit; the argmax is edison_fnet_batch's
             assert np.array_equal(tr.logits(n).view(np.uint32), before["logits"].view(np.uint32)), (name, n)
             assert np.array_equal(r["argmax"], before["argmax"])
             # 2. the loss per row
-            _, (lb, le) = bounds(model, x, y, ref)
-            lerr = fgrad_ref.tensor_error(r["loss"], ref["loss"])
+            lb, le = ftrain_ref.bounds(model, x, y, ref)[1]
+            lerr = ftrain_ref.tensor_error(r["loss"], ref["loss"])
             print("%s n=%d loss: gpu %.3g  e32 %.3g  bound %.3g" % (name, n, lerr, le, lb))
             assert lerr <= lb, (name, n, lerr, lb)
             # 3. every tensor's gradient, 4. the padding
@@ -174,16 +161,16 @@ def test_logits_loss_gradient_padding_repeat_and_no_side_effect(ctx, name):
             assert all(np.array_equal(before[k], after[k]) for k in before)
 
 
-@pytest.mark.parametrize("pool", fgrad_ref.TIE_POOLS, ids=lambda p: "pool%d%d" % p)
+@pytest.mark.parametrize("pool", ftrain_ref.TIE_POOLS, ids=lambda p: "pool%d%d" % p)
 def test_tied_pool_windows_send_the_gradient_to_their_first_element(ctx, pool):
     """Pool windows of 2 and of 4 elements without ReLU whose maxima tie exactly, the first of them at every element that can tie
-    (fgrad_ref.tie_case; tests/test_fgrad_cpu.py shows that sending a tied window's gradient to another of its maxima moves dW by
+    (ftrain_ref.tie_case; tests/test_fgrad_cpu.py shows that sending a tied window's gradient to another of its maxima moves dW by
     more than 1e-2 of its largest entry): the gradient is held to the float64 restatement by the bounds of every other row."""
-    model, x, y = fgrad_ref.tie_case(pool)
+    model, x, y = ftrain_ref.tie_case(pool)
     name = "tie_pool%d%d" % tuple(pool)
     blob, real = poisoned(cube_import.build_blob(model))
     ctx.fnet_load(blob)
-    ref = fgrad_ref.loss_grad(model, x, y)
+    ref = ftrain_ref.loss_grad(model, x, y)
     before = ctx.fnet(x)
     with ctx.trainer() as tr:
         assert tr.info()["batch"] < len(y)                                  # more than one tile
@@ -201,7 +188,7 @@ def test_adam_steps_in_place_and_the_exported_network(ctx, fresh):
     x, y = data(name, model, 17)
     lr = 0.01
     with ctx.trainer() as tr:
-        adam = fgrad_ref.Adam()
+        adam = ftrain_ref.Adam()
         for step in range(3):
             w_before = tr.packed_weights().astype(np.float64)
             tr.grad(x, y)
@@ -259,7 +246,7 @@ def step_errors(tr, real, got, want):
 
 
 def grad_and_step(tr, x, y, lr, replays):
-    """One gradient call and one step; every replay in `replays` (fgrad_ref.Adam, or None for SGD) takes the step in float64 from the
+    """One gradient call and one step; every replay in `replays` (ftrain_ref.Adam, or None for SGD) takes the step in float64 from the
     weights the GPU stepped from with the GPU's own gradient. Returns (the GPU's weights, each replay's weights, the weights before)."""
     w_before = tr.packed_weights()
     tr.grad(x, y)
@@ -291,16 +278,16 @@ def test_a_network_the_step_kernel_takes_in_two_passes(ctx):
         assert real[second:].sum() > 1000
         n = info["batch"] + 1
         x, y = data(name, model, n)
-        ref = fgrad_ref.loss_grad(model, x, y)
+        ref = ftrain_ref.loss_grad(model, x, y)
         before = ctx.fnet(x)
         r = tr.grad(x, y)
         assert np.array_equal(tr.logits(n).view(np.uint32), before["logits"].view(np.uint32))
         assert np.array_equal(r["argmax"], before["argmax"])
-        _, (lb, _) = bounds(model, x, y, ref)
-        assert fgrad_ref.tensor_error(r["loss"], ref["loss"]) <= lb
+        lb = ftrain_ref.bounds(model, x, y, ref)[1][0]
+        assert ftrain_ref.tensor_error(r["loss"], ref["loss"]) <= lb
         check_gradient(name, tr, model, real, x, y, ref)
         assert np.count_nonzero(tr.gradient()[second:]) > 1000          # the second pass has gradients to apply
-        adam = fgrad_ref.Adam()
+        adam = ftrain_ref.Adam()
         for step, (opt, lr) in enumerate([(adam, 0.001)] * 3 + [(None, 0.01)]):
             if opt is None:
                 tr.set_opt("sgd")
@@ -328,7 +315,7 @@ def test_adam_away_from_its_defaults_over_ten_steps(ctx):
     with ctx.trainer() as tr:
         check_plan(blob, tr.info())
         tr.set_opt("adam", b1=0.5, b2=0.9, eps=1e-2)
-        adam, adam7 = fgrad_ref.Adam(0.5, 0.9, 1e-2), fgrad_ref.Adam(0.5, 0.9, 1e-7)
+        adam, adam7 = ftrain_ref.Adam(0.5, 0.9, 1e-2), ftrain_ref.Adam(0.5, 0.9, 1e-7)
         worst = 0.0
         for step in range(10):
             got, (want, want7), _ = grad_and_step(tr, xs[17 * step:17 * step + 17], ys[17 * step:17 * step + 17], lr, [adam, adam7])
@@ -348,7 +335,7 @@ def test_a_step_at_lr_zero_moves_the_moments_only(ctx):
     ctx.fnet_load(blob)
     xs, ys = data(name, model, 34)
     with ctx.trainer() as tr:
-        adam, skipped = fgrad_ref.Adam(), fgrad_ref.Adam()
+        adam, skipped = ftrain_ref.Adam(), ftrain_ref.Adam()
         got, _, w_before = grad_and_step(tr, xs[:17], ys[:17], 0.0, [adam])
         assert np.array_equal(got.view(np.uint32), w_before.view(np.uint32)) and tr.info()["steps"] == 1
         # the next step is the replay's that took the step at lr = 0 too; one that left it out is an lr-sized update away
@@ -369,7 +356,7 @@ def test_refused_optimiser_arguments_leave_the_state(ctx):
     x, y = data(name, model, 17)
     with ctx.trainer() as tr:
         tr.set_opt("adam", b1=0.5, b2=0.9, eps=1e-2)
-        adam = fgrad_ref.Adam(0.5, 0.9, 1e-2)
+        adam = ftrain_ref.Adam(0.5, 0.9, 1e-2)
         got, (want,), _ = grad_and_step(tr, x, y, 0.01, [adam])
         assert step_errors(tr, real, got, want).max() <= 4 * EPS
         w1 = tr.packed_weights()
@@ -514,7 +501,7 @@ def test_refusals_and_the_ignored_counter(ctx):
     try:
         tr.grad_t(xt, yt, n, loss=loss, argmax=am)
         assert tr.info()["ignored"] == 2
-        ref = fgrad_ref.loss_grad(model, x[good], y[good], n_total=n)
+        ref = ftrain_ref.loss_grad(model, x[good], y[good], n_total=n)
         check_gradient(name, tr, model, real, x[good], y[good], ref, n_total=n)
         lh = loss.cpu().numpy()
         assert lh[2] == 0 and lh[7] == 0 and (lh[good] > 0).all()
@@ -543,21 +530,21 @@ def test_a_network_that_fills_the_lds_trains_or_is_refused_by_name(ctx):
             check_plan(fs.blob("batch1_lds_max"), tr.info())
     except _lib.EdisonError as e:
         assert e.code == _lib.E_NO_IMPL and "LDS" in str(e)
-        assert fgrad_ref.train_batch(fnet_exact.plan(fs.blob("batch1_lds_max"))) == 0
+        assert ftrain_ref.train_batch(fnet_exact.plan(fs.blob("batch1_lds_max"))) == 0
 
 
 def test_fit_learns_the_synthetic_set(ctx):
     """40 Adam steps at batch 32, lr 0.01, seed 0 on three noisy class patterns: the train loss falls below half its first value and the
     accuracy reaches 0.9 (conditions the float64 replay meets with room: tests/test_fgrad_cpu.py), and the last loss is the replay's."""
-    x, y = fgrad_ref.fit_set()
-    model = fs.model(fgrad_ref.FIT_ROW)
+    x, y = ftrain_rows.fit_set()
+    model = fs.model(ftrain_rows.FIT_ROW)
     ctx.fnet_load(cube_import.build_blob(model))
-    kw = dict(epochs=100, batch_size=fgrad_ref.FIT_BATCH, seed=0, lr=fgrad_ref.FIT_LR, max_steps=fgrad_ref.FIT_STEPS)
+    kw = dict(epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=ftrain_rows.FIT_STEPS)
     with ctx.trainer() as tr:
         hist = tr.fit(x, y, **kw)
         assert hist["steps"] == 40 and tr.info()["steps"] == 40
         acc = (ctx.fnet(x)["argmax"] == y).mean()
-    replay = train.fit(fgrad_ref.HostTrainer(model), x, y, **kw)
+    replay = train.fit(ftrain_ref.HostTrainer(model), x, y, **kw)
     print("loss %.5f -> %.5f (float64 replay %.5f), accuracy %.3f" % (hist["loss"][0], hist["loss"][-1], replay["loss"][-1], acc))
     assert hist["loss"][-1] < 0.5 * hist["loss"][0] and acc >= 0.9
     assert abs(hist["loss"][-1] - replay["loss"][-1]) <= 1e-3 * replay["loss"][-1]
@@ -566,8 +553,8 @@ def test_fit_learns_the_synthetic_set(ctx):
 
 def test_kws_train_then_kws_quantize(ctx, tmp_path):
     from edison_amd.kws import kws_quantize, kws_train
-    x, y = fgrad_ref.fit_set()
-    model = fs.model(fgrad_ref.FIT_ROW)
+    x, y = ftrain_rows.fit_set()
+    model = fs.model(ftrain_rows.FIT_ROW)
     with open(tmp_path / "net.ednf", "wb") as f:
         f.write(cube_import.build_blob(model, ["a", "b", "c"]))
     np.save(tmp_path / "x.npy", x)

@@ -1,5 +1,5 @@
 """GPU tests (-m gpu) of BatchNorm in the float32 trainer (edison_ftrain_set_batchnorm, Trainer.set_batchnorm, kws train --batchnorm;
-DESIGN.md section 19c) against tests/fbn_ref.py: on two consecutive training calls the loss, the logits and every gradient tensor (w,
+DESIGN.md section 19c) against tests/ftrain_ref.py: on two consecutive training calls the loss, the logits and every gradient tensor (w,
 b of records without BatchNorm, dgamma, dbeta) against the float64 restatement by section 19's metric and bound -- per tensor
 max |g - g64| / max |g64|, allowed 4 x the same error of torch's CPU float32 autograd on the same call, floored at
 8 x 2^-24 x sqrt(terms), terms counting N -- the +0.0f bias gradient of BatchNorm records and of all padding, repeatability, the batch
@@ -12,10 +12,10 @@ import io
 import numpy as np
 import pytest
 
-import fbn_ref as fb
-import fgrad_pad_ref as gp
-import fgrad_ref
+import fnet_ref
 import fnet_sweep
+import ftrain_ref
+import ftrain_rows
 import test_gpu_ftrain as gt
 from edison_amd import _lib, cube_import, train
 
@@ -45,8 +45,8 @@ _POISONED = {}
 
 
 def loaded(ctx, name):
-    """Row `name` of fbn_ref.ROWS loaded with poisoned padding -> (its case, the mask of the packed array's real entries)."""
-    c = fb.case(name)
+    """Row `name` of ftrain_rows.BN_ROWS loaded with poisoned padding -> (its case, the mask of the packed array's real entries)."""
+    c = ftrain_rows.bn_case(name)
     if name not in _POISONED:
         _POISONED[name] = gt.poisoned(c["blob"])
     bad, real = _POISONED[name]
@@ -56,12 +56,12 @@ def loaded(ctx, name):
 
 def trainer_of(ctx, name, **kw):
     """A trainer on the loaded row `name` with its BatchNorm records, its dropout and, where the row sets gamma and beta, its state."""
-    c = fb.case(name)
+    c = ftrain_rows.bn_case(name)
     tr = ctx.trainer()
     tr.set_batchnorm(c["bn"], **kw)
     if c["dropout"] is not None:
         tr.set_dropout(c["dropout"], seed=c["seed"])
-    if fb.ROWS[name].get("neg"):
+    if ftrain_rows.BN_ROWS[name].get("neg"):
         tr.set_bn_state(c["state0"])
     return tr
 
@@ -87,7 +87,7 @@ def check_call(name, call, tr, r, real, ref, bounds):
     per, (lb, le), (zb, ze) = bounds
     z = tr.logits(len(r["loss"]))
     for what, got, want, bound, e32 in (("loss", r["loss"], ref["loss"], lb, le), ("logits", z, ref["logits"], zb, ze)):
-        err = fgrad_ref.tensor_error(got, want)
+        err = ftrain_ref.tensor_error(got, want)
         line = "%s call %d %s: gpu %.3g  e32 %.3g  bound %.3g" % (name, call, what, err, e32, bound)
         print(line)
         assert err <= bound, line
@@ -104,7 +104,7 @@ def check_call(name, call, tr, r, real, ref, bounds):
             assert not g["b"].view(np.uint32).any(), "%s record %d: the bias gradient of a BatchNorm record is not +0.0f" % (name, i)
             checks += [("gamma", bng[i]["gamma"], b64["gamma"]), ("beta", bng[i]["beta"], b64["beta"])]
         for k, got, want in checks:
-            err = fgrad_ref.tensor_error(got, want)
+            err = ftrain_ref.tensor_error(got, want)
             line = "%s call %d record %d %s: gpu %.3g  e32 %.3g  bound %.3g" % (name, call, i, k, err, rec[k][1], rec[k][0])
             print(line)
             assert err <= rec[k][0], line
@@ -122,7 +122,7 @@ def check_stats(name, call, tr, ref, after):
             within(state[i][k], after[i][k], "%s call %d record %d moving %s" % (name, call, i, k))
 
 
-@pytest.mark.parametrize("name", fb.ROWS)
+@pytest.mark.parametrize("name", ftrain_rows.BN_ROWS)
 def test_two_training_calls_against_the_restatement(ctx, name):
     c, real = loaded(ctx, name)
     x, y = c["x"], c["y"]
@@ -137,8 +137,8 @@ def test_two_training_calls_against_the_restatement(ctx, name):
         w0 = tr.packed_weights()
         kept = {}
         for call in (0, 1):
-            ref, after = fb.reference(name, call)
-            kept[call] = check_call(name, call, tr, tr.grad(x, y), real, ref, fb.bounds(name, call))
+            ref, after = ftrain_rows.bn_reference(name, call)
+            kept[call] = check_call(name, call, tr, tr.grad(x, y), real, ref, ftrain_rows.bn_bounds(name, call))
         if c["dropout"] is not None:
             assert tr.dropout_call == 2 and not same_bits(kept[0][1], kept[1][1])    # another mask
             tr.dropout_call = 1
@@ -150,7 +150,7 @@ def test_two_training_calls_against_the_restatement(ctx, name):
         assert same_bits(tr.packed_weights(), w0)                              # a gradient call moves no weight
 
 
-@pytest.mark.parametrize("name", fb.ROWS)
+@pytest.mark.parametrize("name", ftrain_rows.BN_ROWS)
 def test_batch_and_moving_statistics_of_two_training_calls(ctx, name):
     """Batch mean / variance and the moving statistics after each of the two calls, within 4 x 2^-24 of the tensor's maximum of the
     float64 restatement's. The shipped row's deepest BatchNorm record is the hard one: its z has come through three convolutions and
@@ -159,7 +159,7 @@ def test_batch_and_moving_statistics_of_two_training_calls(ctx, name):
     c, _ = loaded(ctx, name)
     with trainer_of(ctx, name) as tr:
         for call in (0, 1):
-            ref, after = fb.reference(name, call)
+            ref, after = ftrain_rows.bn_reference(name, call)
             tr.grad(c["x"], c["y"])
             check_stats(name, call, tr, ref, after)
 
@@ -171,10 +171,10 @@ def test_the_unbiased_flag_moves_the_variance_by_torchs_rule(ctx, name):
         assert tr.batchnorm()["unbiased"] and tr.batchnorm()["momentum"] == 0.9
         state = c["state0"]
         for call in (0, 1):
-            ref, _ = fb.reference(name, call)                                  # the weights do not move: the batch statistics are the same
+            ref, _ = ftrain_rows.bn_reference(name, call)                                  # the weights do not move: the batch statistics are the same
             tr.grad(c["x"], c["y"])
-            state = fb.moved(state, ref["bn"], momentum=0.9, unbiased=True)
-        biased = fb.moved(fb.moved(c["state0"], ref["bn"], momentum=0.9), ref["bn"], momentum=0.9)
+            state = ftrain_ref.moved(state, ref["bn"], momentum=0.9, unbiased=True)
+        biased = ftrain_ref.moved(ftrain_ref.moved(c["state0"], ref["bn"], momentum=0.9), ref["bn"], momentum=0.9)
         for i, st in enumerate(tr.bn_state()):
             if st is None:
                 continue
@@ -186,37 +186,35 @@ def test_the_unbiased_flag_moves_the_variance_by_torchs_rule(ctx, name):
 def drawn(c, n, seed):
     rng = np.random.default_rng(seed)
     x = rng.normal(0, 1, (n, c["x"].shape[1])).astype(np.float32)
-    n_out = int(np.prod(fb.conv_records(c["model"])[-1]["out"]))
+    n_out = int(np.prod(fnet_ref.conv_records(c["model"])[-1]["out"]))
     return x, (np.arange(n) % n_out).astype(np.int32)
 
 
 def check_rows(ctx, name, tr, c, real, x, y):
     """A call of other rows than the case's: reference, bound and precondition computed here."""
-    import torch
     model, n = c["model"], len(y)
-    ref = fb.loss_grad(model, x, y, c["state0"], detail=True)
-    r32 = fb.loss_grad(model, x, y, c["state0"], dtype=np.float32, detail=True)
-    for L, d32, d64 in zip(fb.conv_records(model), r32["detail"], ref["detail"]):       # the bound's precondition on these rows
+    bn = dict(state=c["state0"])
+    ref = ftrain_ref.loss_grad(model, x, y, bn=bn, detail=True)
+    r32 = ftrain_ref.loss_grad(model, x, y, bn=bn, dtype=np.float32, detail=True)
+    for L, d32, d64 in zip(fnet_ref.conv_records(model), r32["detail"], ref["detail"]):       # the bound's precondition on these rows
         assert np.array_equal(d32["first"], d64["first"]) and (not L["relu"] or np.array_equal(d32["y"] > 0, d64["y"] > 0))
-    t32 = fb.torch_grads(model, x, y, torch.float32, c["state0"])
+    per = ftrain_ref.bounds(model, x, y, ref, bn=bn)[0]
     tr.grad(x, y)
     packed = tr.gradient()
     assert not packed[~real].view(np.uint32).any()
     bng = tr.bn_gradients()
-    for i, (g, g64, b64, t) in enumerate(zip(tr.gradients(), ref["grads"], ref["bn"], fb.terms(model, n))):
-        floor = 8 * EPS * np.sqrt(t)
-        checks = [("w", g["w"], g64["w"], t32["grads"][i]["w"])]
+    for i, (g, g64, b64) in enumerate(zip(tr.gradients(), ref["grads"], ref["bn"])):
+        checks = [("w", g["w"], g64["w"])]
         if b64 is None:
-            checks.append(("b", g["b"], g64["b"], t32["grads"][i]["b"]))
+            checks.append(("b", g["b"], g64["b"]))
         else:
             assert not g["b"].view(np.uint32).any()
-            checks += [(k, bng[i][k], b64[k], t32["bn"][i][k]) for k in ("gamma", "beta")]
+            checks += [(k, bng[i][k], b64[k]) for k in ("gamma", "beta")]
             bs = tr.bn_batch_stats()[i]
             within(bs["mean"], b64["mean"], "%s n=%d record %d batch mean" % (name, n, i))
             within(bs["var"], b64["var"], "%s n=%d record %d batch var" % (name, n, i))
-        for k, got, want, g32 in checks:
-            e32 = fgrad_ref.tensor_error(g32, want)
-            err, bound = fgrad_ref.tensor_error(got, want), max(4 * e32, floor)
+        for k, got, want in checks:
+            err, (bound, e32) = ftrain_ref.tensor_error(got, want), per[i][k]
             line = "%s n=%d record %d %s: gpu %.3g  e32 %.3g  bound %.3g" % (name, n, i, k, err, e32, bound)
             print(line)
             assert err <= bound, line
@@ -277,7 +275,7 @@ def test_the_fold_and_the_eval_call(ctx, fresh, name):
         z = ctx.fnet(x)["logits"]
         fresh.fnet_load(cube_import.build_blob(tr.model()))
         assert same_bits(z, fresh.fnet(x)["logits"])                           # the context runs the folded network
-        want = fb.fold(tr.weights(), state)
+        want = ftrain_ref.fold(tr.weights(), state)
         for i, (g, w64) in enumerate(zip(tr.folded_weights(), want)):
             within(g["w"], w64["w"], "%s record %d folded w" % (name, i))
             within(g["b"], w64["b"], "%s record %d folded b" % (name, i))
@@ -306,7 +304,7 @@ def test_the_fold_and_the_eval_call(ctx, fresh, name):
 def test_three_adam_steps_follow_the_host_trainer_on_the_gpus_gradients(ctx, fresh, name):
     c, real = loaded(ctx, name)
     x, y = c["x"], c["y"]
-    host = fb.HostTrainer(c["model"], c["bn"], c["dropout"], seed=c["seed"])
+    host = ftrain_ref.HostTrainer(c["model"], c["dropout"], seed=c["seed"], has_bn=c["bn"])
     with trainer_of(ctx, name) as tr:
         for step in range(3):
             tr.grad(x, y)
@@ -384,7 +382,7 @@ def test_refusals(ctx):
         assert tr.batchnorm()["on"] and tr.batchnorm()["has_bn"] == [0, 0] and tr.bn_state() == [None, None]
         assert code(tr, [1, 0]) == _lib.E_ARGUMENT and "new trainer" in last_error(ctx)
     # a network with a pad
-    ctx.fnet_load(gp.blob(gp.FIT_ROW))
+    ctx.fnet_load(ftrain_rows.pad_blob(ftrain_rows.PAD_FIT_ROW))
     with ctx.trainer(padded=True) as tr:
         nl = tr.n_layers
         with pytest.raises(_lib.EdisonError) as e:
@@ -406,7 +404,7 @@ def test_a_trainer_without_batchnorm_is_unchanged(ctx):
             assert not tr.batchnorm()["on"] and tr.bn_state() == [None, None]
     assert all(same_bits(a, b) for a, b in zip(*bits))
     assert same_bits(bits[0][1], ctx.fnet(x)["logits"])
-    ref = fgrad_ref.loss_grad(model, x, y)
+    ref = ftrain_ref.loss_grad(model, x, y)
     with ctx.trainer() as tr:
         tr.grad(x, y)
         gt.check_gradient(name, tr, model, real, x, y, ref)
@@ -416,12 +414,12 @@ def test_fit_with_batchnorm_and_dropout_follows_the_float64_replay(ctx):
     """Three noisy class patterns on pool21_trunc_h's shape, BatchNorm behind the conv and dropout 0.25 before its pool, 40 Adam steps
     at batch 32, lr 0.01: the loss history is the float64 HostTrainer replay's to 1e-3 per epoch and the accuracy 1.0; validation runs
     the folded network."""
-    x, y = fgrad_ref.fit_set()
-    model = fnet_sweep.model(fgrad_ref.FIT_ROW)
-    blob, _ = gt.poisoned(fnet_sweep.blob(fgrad_ref.FIT_ROW))
+    x, y = ftrain_rows.fit_set()
+    model = fnet_sweep.model(ftrain_rows.FIT_ROW)
+    blob, _ = gt.poisoned(fnet_sweep.blob(ftrain_rows.FIT_ROW))
     ctx.fnet_load(blob)
     bn, dropout = [1, 0], [(0.25, 1), 0]
-    kw = dict(epochs=100, batch_size=fgrad_ref.FIT_BATCH, seed=0, lr=fgrad_ref.FIT_LR, max_steps=fgrad_ref.FIT_STEPS, val=(x, y), callbacks=False)
+    kw = dict(epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=ftrain_rows.FIT_STEPS, val=(x, y), callbacks=False)
     with ctx.trainer(dropout=dropout, seed=3, batchnorm=bn) as tr:
         hist = tr.fit(x, y, **kw)
         assert hist["steps"] == 40 and tr.info()["steps"] == 40 and tr.dropout_call == 40
@@ -429,7 +427,7 @@ def test_fit_with_batchnorm_and_dropout_follows_the_float64_replay(ctx):
         acc = (out["argmax"] == y).mean()
         r = tr.grad(x, y, training=False)
         assert hist["val_acc"][-1] == (r["argmax"] == y).mean() == acc
-    host = fb.HostTrainer(model, bn, dropout, seed=3)
+    host = ftrain_ref.HostTrainer(model, dropout, seed=3, has_bn=bn)
     replay = train.fit(host, x, y, **kw)
     print("loss %s\nreplay %s\nval %s\nreplay %s\naccuracy %.3f" % (np.round(hist["loss"], 5), np.round(replay["loss"], 5), np.round(hist["val_loss"], 5),
                                                                     np.round(replay["val_loss"], 5), acc))
@@ -447,8 +445,8 @@ def test_kws_train_with_batchnorm_then_kws_quantize(ctx, tmp_path):
     from edison_amd import config as cfg
     from edison_amd.kws import kws_quantize, kws_train
     from edison_amd.kws.geometry import KwsGeometry
-    model = fb.case("shipped")["model"]
-    x, y = gp.kws_set()
+    model = ftrain_rows.bn_case("shipped")["model"]
+    x, y = ftrain_rows.kws_set()
     keywords = ["k%d" % i for i in range(10)]
     with open(tmp_path / "net.ednf", "wb") as f:
         f.write(cube_import.build_blob(model, keywords))

@@ -1,16 +1,16 @@
 """GPU checks of training from scratch on a device-resident data set (edison_ftrain_data_*, edison_ftrain_epoch, Adadelta; DESIGN.md
 section 19d): the gather and the store bit for bit against batch-by-batch gradient calls, the features computed from audio against
 Context.kws_float's, the reduction against the per-row arrays, Trainer.fit_data against Trainer.fit bit for bit, a get_model network
-learning the synthetic set, the Adadelta kernel against its float64 restatement (fdata_ref), the refusals and the command line."""
+learning the synthetic set, the Adadelta kernel against its float64 restatement (ftrain_ref.Adadelta), the refusals and the command line."""
 import io
 
 import numpy as np
 import pytest
 
-import fbn_ref
-import fdata_ref
-import fgrad_ref
+import fnet_ref
 import fnet_sweep as fs
+import ftrain_ref
+import ftrain_rows
 from edison_amd import _lib, cube_import, train
 from test_ftrain_zoo_cpu import SCRATCH_ARCH, SCRATCH_STEPS, scratch_model
 
@@ -185,8 +185,8 @@ def two_conv_model():
 
 
 FIT_TRAINERS = {
-    "plain": (lambda: fs.model(fgrad_ref.FIT_ROW), dict()),
-    "dropout": (lambda: fs.model(fgrad_ref.FIT_ROW), dict(dropout=[0.25, 0], seed=3)),
+    "plain": (lambda: fs.model(ftrain_rows.FIT_ROW), dict()),
+    "dropout": (lambda: fs.model(ftrain_rows.FIT_ROW), dict(dropout=[0.25, 0], seed=3)),
     "batchnorm_dropout": (two_conv_model, dict(dropout=[(0.25, 1), 0.25, 0], seed=3, batchnorm=dict(has_bn=[1, 1, 0], max_rows=5))),
 }
 
@@ -195,8 +195,8 @@ FIT_TRAINERS = {
 def test_fit_data_is_fit(ctx, fresh, kind):
     make, targs = FIT_TRAINERS[kind]
     blob = cube_import.build_blob(make())
-    assert len(fbn_ref.conv_records(make())) == len(targs.get("dropout", [0, 0]))
-    x, y = fgrad_ref.fit_set()
+    assert len(fnet_ref.conv_records(make())) == len(targs.get("dropout", [0, 0]))
+    x, y = ftrain_rows.fit_set()
     x, y, vx, vy = x[:23], y[:23], x[40:49], y[40:49]
     for extra in (dict(), dict(max_steps=7)):
         kw = dict(epochs=3, batch_size=5, seed=4, lr=0.01, callbacks=True, **extra)
@@ -228,16 +228,16 @@ def test_fit_data_is_fit(ctx, fresh, kind):
 def test_a_get_model_network_learns_the_synthetic_set_through_fit_data(ctx):
     """test_fit_learns_the_synthetic_set's set and conditions, the network built by get_model (single_fc at 40 steps: the float64 host
     trainer meets them there, tests/test_ftrain_zoo_cpu.py) and trained through fit_data."""
-    x, y = fgrad_ref.fit_set()
-    assert (SCRATCH_ARCH, SCRATCH_STEPS) == ("single_fc", fgrad_ref.FIT_STEPS)
+    x, y = ftrain_rows.fit_set()
+    assert (SCRATCH_ARCH, SCRATCH_STEPS) == ("single_fc", ftrain_rows.FIT_STEPS)
     model = scratch_model()
     ctx.fnet_load(cube_import.build_blob(model))
-    kw = dict(epochs=100, batch_size=fgrad_ref.FIT_BATCH, seed=0, lr=fgrad_ref.FIT_LR, max_steps=SCRATCH_STEPS)
+    kw = dict(epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=SCRATCH_STEPS)
     with ctx.train_data(x, y) as data, ctx.trainer() as tr:
         hist = tr.fit_data(data, **kw)
         assert hist["steps"] == SCRATCH_STEPS == tr.info()["steps"]
         acc = (ctx.fnet(x)["argmax"] == y).mean()
-    replay = train.fit(fgrad_ref.HostTrainer(model), x, y, **kw)
+    replay = train.fit(ftrain_ref.HostTrainer(model), x, y, **kw)
     print("loss %.5f -> %.5f (float64 replay %.5f), accuracy %.3f" % (hist["loss"][0], hist["loss"][-1], replay["loss"][-1], acc))
     assert hist["loss"][-1] < 0.5 * hist["loss"][0] and acc >= 0.9
     assert len(hist["loss"]) == len(replay["loss"])
@@ -276,7 +276,7 @@ def test_adadelta_steps_against_the_float64_restatement(ctx):
     x, y = gt.data(name, model, 17)
     with ctx.trainer() as tr:
         tr.set_opt("adadelta", rho=0.95, eps=1e-7)
-        replay = fdata_ref.Adadelta(0.95, 1e-7)
+        replay = ftrain_ref.Adadelta(0.95, 1e-7)
         for step in range(3):
             w_before, g, got = adadelta_step_checked(tr, real, x, y, replay, 1.0, "step %d" % (step + 1))
             moved = np.abs(got[real] - w_before[real])
@@ -285,11 +285,11 @@ def test_adadelta_steps_against_the_float64_restatement(ctx):
         # reset zeroes both averages: the next step is a first step again
         tr.reset()
         assert tr.info()["steps"] == 0
-        adadelta_step_checked(tr, real, x, y, fdata_ref.Adadelta(0.95, 1e-7), 1.0, "after reset")
+        adadelta_step_checked(tr, real, x, y, ftrain_ref.Adadelta(0.95, 1e-7), 1.0, "after reset")
         # other constants
         tr.reset()
         tr.set_opt("adadelta", rho=0.5, eps=1e-4)
-        replay = fdata_ref.Adadelta(0.5, 1e-4)
+        replay = ftrain_ref.Adadelta(0.5, 1e-4)
         for step in range(2):
             adadelta_step_checked(tr, real, x, y, replay, 0.5, "rho 0.5 step %d" % (step + 1))
         # refused settings leave the previous kind and constants
@@ -320,11 +320,11 @@ def test_adadelta_steps_gamma_and_beta_of_a_batchnorm_trainer(ctx):
     Why 8 and not the weights' 4: beta starts at 0, so after the first step it IS -u and the whole error is u's, not the rounding of
     w - lr u at w's size: u = g sqrt(d + eps) / sqrt(a + eps) takes up to nine float32 roundings (two of them under a square root)
     and the float values of rho, 1 - rho and eps, each at most 2^-24 relative: below 6 x 2^-24 together, 8 with room."""
-    c = fbn_ref.case("bn_p1")
+    c = ftrain_rows.bn_case("bn_p1")
     ctx.fnet_load(c["blob"])
     with ctx.trainer(batchnorm=c["bn"]) as tr:
         tr.set_opt("adadelta", rho=0.95)
-        replay = {k: fdata_ref.Adadelta() for k in ("gamma", "beta")}
+        replay = {k: ftrain_ref.Adadelta() for k in ("gamma", "beta")}
         for step in range(2):
             before = tr.bn_state()[0]
             tr.grad(c["x"], c["y"])
@@ -344,7 +344,7 @@ def test_adadelta_steps_gamma_and_beta_of_a_batchnorm_trainer(ctx):
 # ---- refusals --------------------------------------------------------------------------------------------------------------------------
 def test_refusals_leave_the_weights_the_counters_and_the_store(ctx):
     blob = cube_import.build_blob(two_conv_model())
-    x, y = fgrad_ref.fit_set()
+    x, y = ftrain_rows.fit_set()
     x, y = x[:23], y[:23]
     ctx.fnet_load(blob)
     with ctx.trainer(dropout=[0.25, 0, 0], seed=2, batchnorm=dict(has_bn=[1, 0, 0], max_rows=5)) as tr, ctx.train_data(x, y) as data, \

@@ -1,5 +1,5 @@
 """GPU tests (-m gpu) of dropout in the float32 trainer (edison_ftrain_set_dropout, Trainer.set_dropout, kws train --dropout; DESIGN.md
-section 19b) against tests/fdrop_ref.py: the logits bit for bit against the host model with the mask, the loss and every gradient
+section 19b) against tests/fdrop_ref.py and tests/ftrain_ref.py: the logits bit for bit against the host model with the mask, the loss and every gradient
 tensor against the float64 restatement with the mask by section 19's metric and bound -- per tensor max |g - g64| / max |g64|, allowed
 4 x the same error of torch's CPU float32 autograd with the same mask, floored at 8 x 2^-24 x sqrt(terms) -- the counter, the eval flag,
 the mask's independence of the tiling exactly, the refusals, fit and the CLI. tests/test_fdrop_cpu.py shows the bound's precondition
@@ -12,16 +12,15 @@ import numpy as np
 import pytest
 
 import fdrop_ref as fd
-import fgrad_pad_ref as gp
-import fgrad_ref
 import fnet_pad
+import ftrain_ref
+import ftrain_rows
 import test_gpu_ftrain as gt
 from edison_amd import _lib, cube_import, train
 
 pytestmark = pytest.mark.gpu
 
-EPS = gt.EPS
-N = fd.N_ROWS
+N = ftrain_rows.N_ROWS
 
 
 @pytest.fixture(scope="module")
@@ -36,8 +35,8 @@ _POISONED = {}
 
 
 def loaded(ctx, name):
-    """Row `name` of fdrop_ref.ROWS loaded with poisoned padding -> (its case, the mask of the packed array's real entries)."""
-    c = fd.case(name)
+    """Row `name` of ftrain_rows.DROP_ROWS loaded with poisoned padding -> (its case, the mask of the packed array's real entries)."""
+    c = ftrain_rows.drop_case(name)
     if name not in _POISONED:
         _POISONED[name] = gt.poisoned(c["blob"])
     bad, real = _POISONED[name]
@@ -49,21 +48,6 @@ def same_bits(a, b):
     return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
 
-def bounds(c, ref, call):
-    """test_gpu_ftrain_pad.bounds with the mask in torch's float32 run too."""
-    import torch
-    model, x, y = c["model"], c["x"], c["y"]
-    t32 = fd.torch_grads(model, x, y, torch.float32, c["sp"], c["seed"], call)
-    out = []
-    for g32, g64, terms in zip(t32["grads"], ref["grads"], gp.terms(model, len(y))):
-        floor = 8 * EPS * np.sqrt(terms)
-        e = [fgrad_ref.tensor_error(g32[k], g64[k]) for k in ("w", "b")]
-        out.append((max(4 * e[0], floor), max(4 * e[1], floor), e[0], e[1]))
-    chain = sum(int(np.prod(L["k"])) * L["inp"][2] for L in gp.conv_records(model)) + ref["logits"].shape[1]
-    el = fgrad_ref.tensor_error(t32["loss"], ref["loss"])
-    return out, (max(4 * el, 8 * EPS * np.sqrt(chain)), el)
-
-
 def plain_bits(ctx, c):
     """What a fresh trainer on which dropout was never set gives on the row: (loss, logits, gradient)."""
     with ctx.trainer(padded=True) as tr:
@@ -71,7 +55,7 @@ def plain_bits(ctx, c):
         return r["loss"], tr.logits(N), tr.gradient(), tr.info()
 
 
-@pytest.mark.parametrize("name", fd.ROWS)
+@pytest.mark.parametrize("name", ftrain_rows.DROP_ROWS)
 def test_logits_loss_gradient_counter_eval_flag_and_zero_rates(ctx, name):
     c, real = loaded(ctx, name)
     model, x, y = c["model"], c["x"], c["y"]
@@ -95,17 +79,18 @@ def test_logits_loss_gradient_counter_eval_flag_and_zero_rates(ctx, name):
             z = tr.logits(N)
             assert same_bits(z, want), "%s call %d: %d of %d logits differ from the host model with the mask" % (
                 name, call, int((z.view(np.uint32) != want.view(np.uint32)).sum()), z.size)
-            ref = fd.reference(name, call)
+            ref = ftrain_rows.drop_reference(name, call)
             assert np.array_equal(r["argmax"], np.argmax(want, axis=1))
-            per, (lb, le) = bounds(c, ref, call)
-            lerr = fgrad_ref.tensor_error(r["loss"], ref["loss"])
+            per, (lb, le), _ = ftrain_ref.bounds(model, x, y, ref, dropout=(c["sp"], c["seed"], call))
+            lerr = ftrain_ref.tensor_error(r["loss"], ref["loss"])
             print("%s call %d loss: gpu %.3g  e32 %.3g  bound %.3g" % (name, call, lerr, le, lb))
             assert lerr <= lb, (name, call, lerr, lb)
             packed = tr.gradient()
             assert not packed[~real].view(np.uint32).any(), "%s: a padding entry of the gradient is not +0.0f" % name
-            for i, (g, g64, (bw, bb, ew, eb)) in enumerate(zip(tr.gradients(), ref["grads"], per)):
-                for k, bound, e32 in (("w", bw, ew), ("b", bb, eb)):
-                    err = fgrad_ref.tensor_error(g[k], g64[k])
+            for i, (g, g64, allowed) in enumerate(zip(tr.gradients(), ref["grads"], per)):
+                for k in ("w", "b"):
+                    bound, e32 = allowed[k]
+                    err = ftrain_ref.tensor_error(g[k], g64[k])
                     line = "%s call %d record %d %s: gpu %.3g  e32 %.3g  bound %.3g" % (name, call, i, k, err, e32, bound)
                     print(line)
                     assert err <= bound, line
@@ -147,7 +132,7 @@ def test_mid_pads_batch_runs_both_tile_instantiations_in_two_to_four_tiles(ctx):
 def test_the_mask_does_not_depend_on_the_tiling_exactly(ctx):
     """batch5 at its training batch 2, N = 1024 rows in device form: 512 tiles on at most 256 workgroups. The full call against the
     fold of 512 calls of the same 1024 rows at the same counter, call j with only tile j's rows labelled (every other row -1: the
-    ordinals and n are the same, the other tiles contribute +0). fgrad_ref.fold_tiles of those terms is the full call's gradient
+    ordinals and n are the same, the other tiles contribute +0). ftrain_ref.fold_tiles of those terms is the full call's gradient
     element for element: a mask that depended on the tile, the workgroup or the lane that computes it would not fold."""
     import torch
     c, real = loaded(ctx, "batch5")
@@ -179,7 +164,7 @@ def test_the_mask_does_not_depend_on_the_tiling_exactly(ctx):
         assert same_bits(tr.logits(n), z)                                                      # the labels do not move the masks
         assert same_bits(z[:N], fd.forward32(c["model"], x[:N], c["sp"], c["seed"], counter)[-1])
         assert np.isfinite(T).all() and not T[:, ~real].view(np.uint32).any()
-        want = fgrad_ref.fold_tiles(T, G, 1)
+        want = ftrain_ref.fold_tiles(T, G, 1)
         nonzero = int(np.count_nonzero(big[real]))
         diff = np.flatnonzero(~(want == big))
         print("batch %d, grid %d, %d tiles; %d of %d real gradient entries are non-zero" % (b, G, n_tiles, nonzero, int(real.sum())))
@@ -229,12 +214,12 @@ def test_fit_follows_the_float64_replay_and_validates_without_dropout(ctx):
     """Three noisy class patterns on stride2_same's shape, dropout 0.25 behind the conv, 40 Adam steps at batch 32, lr 0.01: the loss
     history is the float64 HostTrainer replay's to 1e-3 (section 19's tolerance), the final accuracy at least the replay's, and the
     validation entries those of a dropout-free evaluation of the same weights."""
-    x, y = gp.fit_set()
-    model = gp.model(gp.FIT_ROW)
-    blob, _ = gt.poisoned(fnet_pad.blob(gp.FIT_ROW))
+    x, y = ftrain_rows.pad_fit_set()
+    model = ftrain_rows.pad_model(ftrain_rows.PAD_FIT_ROW)
+    blob, _ = gt.poisoned(fnet_pad.blob(ftrain_rows.PAD_FIT_ROW))
     ctx.fnet_load(blob)
     dropout = [(0.25, 1), 0]
-    kw = dict(epochs=100, batch_size=fgrad_ref.FIT_BATCH, seed=0, lr=fgrad_ref.FIT_LR, max_steps=fgrad_ref.FIT_STEPS, val=(x, y), callbacks=False)
+    kw = dict(epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=ftrain_rows.FIT_STEPS, val=(x, y), callbacks=False)
     with ctx.trainer(padded=True, dropout=dropout, seed=3) as tr:
         hist = tr.fit(x, y, **kw)
         assert hist["steps"] == 40 and tr.info()["steps"] == 40 and tr.dropout_call == 40    # validation did not advance the counter
@@ -245,7 +230,7 @@ def test_fit_follows_the_float64_replay_and_validates_without_dropout(ctx):
     with ctx.trainer(padded=True) as plain:                                    # a trainer that never heard of dropout, the same weights
         r0 = plain.grad(x, y)
         assert same_bits(r0["loss"], r["loss"]) and np.array_equal(r0["argmax"], r["argmax"])
-    host = fd.HostTrainer(model, dropout, seed=3)
+    host = ftrain_ref.HostTrainer(model, dropout, seed=3)
     replay = train.fit(host, x, y, **kw)
     racc = (host.grad(x, y, training=False)["argmax"] == y).mean()
     print("loss %s\nreplay %s\naccuracy %.3f (replay %.3f)" % (np.round(hist["loss"], 5), np.round(replay["loss"], 5), acc, racc))
@@ -262,8 +247,8 @@ def test_kws_train_with_dropout_then_kws_quantize(ctx, tmp_path):
     from edison_amd import config as cfg
     from edison_amd.kws import kws_quantize, kws_train
     from edison_amd.kws.geometry import KwsGeometry
-    model = gp.model("tiny_conv")
-    x, y = gp.kws_set()
+    model = ftrain_rows.pad_model("tiny_conv")
+    x, y = ftrain_rows.kws_set()
     keywords = ["k%d" % i for i in range(10)]
     with open(tmp_path / "net.ednf", "wb") as f:
         f.write(cube_import.build_blob(model, keywords))

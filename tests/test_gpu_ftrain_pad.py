@@ -1,5 +1,5 @@
 """GPU tests (-m gpu) of training padded float32 networks (edison_ftrain_create_ex with EDISON_FTRAIN_PADDED, Context.trainer(padded=True),
-kws train; DESIGN.md sections 14b and 19) against tests/fgrad_pad_ref.py, the float64 restatement with pads.
+kws train; DESIGN.md sections 14b and 19) against tests/ftrain_ref.py, the float64 restatement, with pads.
 
 The bounds are tests/test_gpu_ftrain.py's, measured the same way: per tensor max |g - g64| / max |g64|, allowed 4 x the same error of
 torch's CPU float32 autograd, floored at 8 x 2^-24 x sqrt(terms), terms = n x the record's live rows. tests/test_fgrad_pad_cpu.py shows
@@ -13,16 +13,16 @@ import struct
 import numpy as np
 import pytest
 
-import fgrad_pad_ref as gp
-import fgrad_ref
 import fnet_pad
+import ftrain_ref
+import ftrain_rows
 import test_gpu_ftrain as gt
 from edison_amd import _lib, cube_import, train
 
 pytestmark = pytest.mark.gpu
 
 EPS = gt.EPS
-ALL_N = gp.ALL_N                                         # rows that run n over {1, b - 1, b, b + 1, 3 b + 2}
+ALL_N = ftrain_rows.ALL_N                                         # rows that run n over {1, b - 1, b, b + 1, 3 b + 2}
 LOWERED = {"mid_pads_batch": 5, "simple_conv": 6}        # tests/test_fgrad_pad_cpu.py: rows that train below their forward batch
 
 
@@ -46,45 +46,17 @@ _CASES = {}
 
 
 def case(name):
-    """(model, blob with poisoned padding, mask of the packed array's real entries) of a row of fgrad_pad_ref.ROWS, built once."""
+    """(model, blob with poisoned padding, mask of the packed array's real entries) of a row of ftrain_rows.PAD_ROWS, built once."""
     if name not in _CASES:
-        bad, real = gt.poisoned(gp.blob(name))
-        _CASES[name] = (gp.model(name), bad, real)
+        bad, real = gt.poisoned(ftrain_rows.pad_blob(name))
+        _CASES[name] = (ftrain_rows.pad_model(name), bad, real)
     return _CASES[name]
 
 
 def check_plan(blob, info):
     p = fnet_pad.plan(blob)
-    assert info["batch"] == gp.train_batch(p) and info["lds_bytes"] == gp.train_lds_bytes(p, info["batch"]), (info, p["batch"])
+    assert info["batch"] == ftrain_ref.train_batch(p) and info["lds_bytes"] == ftrain_ref.train_lds_bytes(p, info["batch"]), (info, p["batch"])
     return p
-
-
-def bounds(model, x, y, ref, n_total=None):
-    """test_gpu_ftrain.bounds on the padded restatement and its terms."""
-    import torch
-    t32 = gp.torch_grads(model, x, y, torch.float32)
-    scale = 1.0 if n_total is None else len(y) / n_total
-    out = []
-    for g32, g64, terms in zip(t32["grads"], ref["grads"], gp.terms(model, len(y))):
-        floor = 8 * EPS * np.sqrt(terms)
-        e = [fgrad_ref.tensor_error(g32[k] * scale, g64[k]) for k in ("w", "b")]
-        out.append((max(4 * e[0], floor), max(4 * e[1], floor), e[0], e[1]))
-    chain = sum(int(np.prod(L["k"])) * L["inp"][2] for L in gp.conv_records(model)) + ref["logits"].shape[1]
-    el = fgrad_ref.tensor_error(t32["loss"], ref["loss"])
-    return out, (max(4 * el, 8 * EPS * np.sqrt(chain)), el)
-
-
-def check_gradient(name, tr, model, real, x, y, ref):
-    got = tr.gradients()
-    packed = tr.gradient()
-    assert not packed[~real].view(np.uint32).any(), "%s: a padding entry of the gradient is not +0.0f" % name
-    per, _ = bounds(model, x, y, ref)
-    for i, (g, g64, (bw, bb, ew, eb)) in enumerate(zip(got, ref["grads"], per)):
-        for k, bound, e32 in (("w", bw, ew), ("b", bb, eb)):
-            err = fgrad_ref.tensor_error(g[k], g64[k])
-            line = "%s n=%d record %d %s: gpu %.3g  e32 %.3g  bound %.3g" % (name, len(y), i, k, err, e32, bound)
-            print(line)
-            assert err <= bound, line
 
 
 def same_bits(a, b):
@@ -95,16 +67,16 @@ def check_call(ctx, tr, name, model, real, x, y, w0):
     """One host-form gradient call held in every way: logits and argmax edison_fnet_batch's bits, loss and every tensor by the float64
     bounds, padding +0.0f, a repeat the same bits, nothing else moved. Returns the packed gradient."""
     n = len(y)
-    ref = gp.loss_grad(model, x, y)
+    ref = ftrain_ref.loss_grad(model, x, y)
     before = ctx.fnet(x)
     r = tr.grad(x, y)
     assert same_bits(tr.logits(n), before["logits"]), (name, n)
     assert np.array_equal(r["argmax"], before["argmax"])
-    _, (lb, le) = bounds(model, x, y, ref)
-    lerr = fgrad_ref.tensor_error(r["loss"], ref["loss"])
+    lb, le = ftrain_ref.bounds(model, x, y, ref)[1]
+    lerr = ftrain_ref.tensor_error(r["loss"], ref["loss"])
     print("%s n=%d loss: gpu %.3g  e32 %.3g  bound %.3g" % (name, n, lerr, le, lb))
     assert lerr <= lb, (name, n, lerr, lb)
-    check_gradient(name, tr, model, real, x, y, ref)
+    gt.check_gradient(name, tr, model, real, x, y, ref)
     g = tr.gradient()
     r2 = tr.grad(x, y)
     assert same_bits(tr.gradient(), g), (name, n)
@@ -115,7 +87,7 @@ def check_call(ctx, tr, name, model, real, x, y, w0):
     return g
 
 
-@pytest.mark.parametrize("name", gp.ROWS)
+@pytest.mark.parametrize("name", ftrain_rows.PAD_ROWS)
 def test_logits_loss_gradient_padding_repeat_and_no_side_effect(ctx, name):
     model, blob, real = case(name)
     ctx.fnet_load(blob)
@@ -128,21 +100,21 @@ def test_logits_loss_gradient_padding_repeat_and_no_side_effect(ctx, name):
         assert any(L["pad"] for L in p["layers"])
         if name == "mid_pads_batch":                                        # a mixed network: the kernel runs both instantiations of the tile
             assert [L["pad"] for L in p["layers"]] == [False, True, True, False] and ("pad_layer", 1) in fnet_pad.facts(name)
-        ns = sorted({gp.N_ROWS} | ({1, max(b - 1, 1), b, b + 1, 3 * b + 2} if name in ALL_N else set()))
-        assert max(ns) <= gp.n_max(name)                                    # the rows the CPU test holds the precondition on
-        xs, ys = gp.data(name, max(ns))
-        if name == gp.NEG_T:
+        ns = sorted({ftrain_rows.N_ROWS} | ({1, max(b - 1, 1), b, b + 1, 3 * b + 2} if name in ALL_N else set()))
+        assert max(ns) <= ftrain_rows.n_max(name)                                    # the rows the CPU test holds the precondition on
+        xs, ys = ftrain_rows.pad_data(name, max(ns))
+        if name == ftrain_rows.NEG_T:
             assert (xs < 0).all()
         w0 = tr.packed_weights()
         for n in ns:
             check_call(ctx, tr, name, model, real, xs[:n], ys[:n], w0)
 
 
-@pytest.mark.parametrize("pool", gp.TIE_POOLS, ids=lambda p: "pool%d%d" % p)
+@pytest.mark.parametrize("pool", ftrain_ref.TIE_PADS, ids=lambda p: "pool%d%d" % p)
 def test_tied_pool_windows_send_the_gradient_to_their_first_present_element(ctx, pool):
-    """fgrad_pad_ref.tie_case: windows with absent elements leading and trailing whose present elements tie exactly
+    """ftrain_ref.tie_case with pool pads: windows with absent elements leading and trailing whose present elements tie exactly
     (tests/test_fgrad_pad_cpu.py shows that another choice moves dW by more than 1e-2 of its largest entry)."""
-    model, x, y = gp.tie_case(pool)
+    model, x, y = ftrain_ref.tie_case(pool, ppad=ftrain_ref.TIE_PADS[pool])
     name = "tie_pad_pool%d%d" % tuple(pool)
     blob, real = gt.poisoned(cube_import.build_blob(model))
     ctx.fnet_load(blob)
@@ -159,7 +131,7 @@ def pow2_at_least(v):
 def test_a_multi_tile_gradient_is_the_fold_of_its_tiles_exactly(ctx):
     """The method of tests/test_gpu_ftrain_tiles.py on sym3x3: N = 2 x grid x batch rounded up to a power of two, N(0, 1) inputs; every
     tile alone among fillers labelled -1 gives its term of the big call times N / n', exactly; the big call's gradient is
-    fgrad_ref.fold_tiles of those terms, element for element."""
+    ftrain_ref.fold_tiles of those terms, element for element."""
     import torch
     name = "sym3x3"
     model, blob, real = case(name)
@@ -199,7 +171,7 @@ def test_a_multi_tile_gradient_is_the_fold_of_its_tiles_exactly(ctx):
         assert len(digests) == n_tiles, "two tiles give the same gradient: a swapped order would not show"
         assert np.isfinite(T).all() and smallest * scale > 2.0 ** -100
         assert not T[:, ~real].view(np.uint32).any()
-        want = fgrad_ref.fold_tiles(T, G, scale)
+        want = ftrain_ref.fold_tiles(T, G, scale)
         diff = np.flatnonzero(~(want == big))
         assert diff.size == 0, "%s: %d of %d gradient entries are not the fold of the tiles' (first at %d: call %r, fold %r)" % (
             name, diff.size, w, diff[0], big[diff[0]], want[diff[0]])
@@ -211,10 +183,10 @@ def test_adam_steps_in_place_and_the_exported_network(ctx, fresh):
     name = "medium_embedding_conv"
     model, blob, real = case(name)
     ctx.fnet_load(blob)
-    x, y = gp.data(name)
+    x, y = ftrain_rows.pad_data(name)
     lr = 0.01
     with ctx.trainer(padded=True) as tr:
-        adam = fgrad_ref.Adam()
+        adam = ftrain_ref.Adam()
         for step in range(3):
             w_before = tr.packed_weights().astype(np.float64)
             tr.grad(x, y)
@@ -246,16 +218,16 @@ def test_fit_learns_the_synthetic_set(ctx):
     """40 Adam steps at batch 32, lr 0.01, seed 0 on three noisy class patterns at stride2_same's input shape: the train loss falls
     below half its first value and the accuracy reaches 0.9 (the float64 replay meets both with room: tests/test_fgrad_pad_cpu.py), and
     the last loss is the replay's."""
-    x, y = gp.fit_set()
-    model = gp.model(gp.FIT_ROW)
-    blob, _ = gt.poisoned(fnet_pad.blob(gp.FIT_ROW))
+    x, y = ftrain_rows.pad_fit_set()
+    model = ftrain_rows.pad_model(ftrain_rows.PAD_FIT_ROW)
+    blob, _ = gt.poisoned(fnet_pad.blob(ftrain_rows.PAD_FIT_ROW))
     ctx.fnet_load(blob)
-    kw = dict(epochs=100, batch_size=fgrad_ref.FIT_BATCH, seed=0, lr=fgrad_ref.FIT_LR, max_steps=fgrad_ref.FIT_STEPS)
+    kw = dict(epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=ftrain_rows.FIT_STEPS)
     with ctx.trainer(padded=True) as tr:
         hist = tr.fit(x, y, **kw)
         assert hist["steps"] == 40 and tr.info()["steps"] == 40
         acc = (ctx.fnet(x)["argmax"] == y).mean()
-    replay = train.fit(gp.HostTrainer(model), x, y, **kw)
+    replay = train.fit(ftrain_ref.HostTrainer(model), x, y, **kw)
     print("loss %.5f -> %.5f (float64 replay %.5f), accuracy %.3f" % (hist["loss"][0], hist["loss"][-1], replay["loss"][-1], acc))
     assert hist["loss"][-1] < 0.5 * hist["loss"][0] and acc >= 0.9
     assert abs(hist["loss"][-1] - replay["loss"][-1]) <= 1e-3 * replay["loss"][-1]
@@ -267,8 +239,8 @@ def test_kws_train_then_kws_quantize(ctx, tmp_path):
     from edison_amd import config as cfg
     from edison_amd.kws import kws_quantize, kws_train
     from edison_amd.kws.geometry import KwsGeometry
-    model = gp.model("tiny_conv")
-    x, y = gp.kws_set()
+    model = ftrain_rows.pad_model("tiny_conv")
+    x, y = ftrain_rows.kws_set()
     keywords = ["k%d" % i for i in range(10)]
     with open(tmp_path / "net.ednf", "wb") as f:
         f.write(cube_import.build_blob(model, keywords))

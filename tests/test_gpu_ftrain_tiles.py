@@ -6,7 +6,7 @@ The exact check. Everything after dz = (p - onehot) / n is linear in dz (the MFM
 row labelled -1 in the device form counts in n but has dz = +0.0f. So tile j of a call of N rows, run alone among fillers labelled -1
 in a call of n' rows, gives tile j's term of the big call times N / n', exactly where N and n' are powers of two and nothing leaves
 the normal range; the small calls have one tile per workgroup, the path tests/test_gpu_ftrain.py holds to float64. The big call's
-gradient must then be fgrad_ref.fold_tiles of those terms, element for element: the kernels' order restated in numpy. A tile dropped,
+gradient must then be ftrain_ref.fold_tiles of those terms, element for element: the kernels' order restated in numpy. A tile dropped,
 stored instead of added, added twice, taken in another order or read from a stale store changes floats (tests/test_fgrad_cpu.py holds
 the fold's sensitivity). The float64 bound at these sizes only sees a whole tile lost (there too).
 
@@ -16,7 +16,7 @@ import hashlib
 import numpy as np
 import pytest
 
-import fgrad_ref
+import ftrain_ref
 import fnet_exact
 import fnet_ref
 import test_gpu_ftrain as gt
@@ -68,13 +68,13 @@ def check_call(ctx, tr, name, model, real, x, y, w0):
     edison_fnet_batch's bits, loss and every tensor by the float64 bounds, padding +0.0f, a repeat the same bits, nothing else moved.
     Returns the packed gradient."""
     n = len(y)
-    ref = fgrad_ref.loss_grad(model, x, y)
+    ref = ftrain_ref.loss_grad(model, x, y)
     before = ctx.fnet(x)
     r = tr.grad(x, y)
     assert same_bits(tr.logits(n), before["logits"]), (name, n)
     assert np.array_equal(r["argmax"], before["argmax"])
-    _, (lb, le) = gt.bounds(model, x, y, ref)
-    lerr = fgrad_ref.tensor_error(r["loss"], ref["loss"])
+    lb, le = ftrain_ref.bounds(model, x, y, ref)[1]
+    lerr = ftrain_ref.tensor_error(r["loss"], ref["loss"])
     print("%s n=%d loss: gpu %.3g  e32 %.3g  bound %.3g" % (name, n, lerr, le, lb))
     assert lerr <= lb, (name, n, lerr, lb)
     gt.check_gradient(name, tr, model, real, x, y, ref)
@@ -137,7 +137,7 @@ def test_a_multi_tile_gradient_is_the_fold_of_its_tiles_exactly(ctx, name, per_w
         assert len(digests) == n_tiles, "two tiles give the same gradient: a swapped order would not show"
         assert np.isfinite(T).all() and smallest * scale > 2.0 ** -100
         assert not T[:, ~real].view(np.uint32).any()
-        want = fgrad_ref.fold_tiles(T, G, scale)
+        want = ftrain_ref.fold_tiles(T, G, scale)
         diff = np.flatnonzero(~(want == big))
         assert diff.size == 0, "%s: %d of %d gradient entries are not the fold of the tiles' (first at %d: call %r, fold %r)" % (
             name, diff.size, w, diff[0], big[diff[0]], want[diff[0]])
@@ -157,7 +157,7 @@ def test_ragged_tile_counts_against_float64(ctx, name, tail):
     with ctx.trainer() as tr:
         info = tr.info()
         b, G = info["batch"], info["grid"]
-        assert b == fgrad_ref.train_batch(fnet_exact.plan(blob)) and b >= 2
+        assert b == ftrain_ref.train_batch(fnet_exact.plan(blob)) and b >= 2
         assert b == 2 if name == "batch5" else b > 2                        # r = b - 1 is another case than r = 1
         r = 1 if tail == "1" else b - 1
         n = 2 * G * b + 2 * b + r
