@@ -15,6 +15,7 @@ E_ARGUMENT, E_LENGTH, E_SIZE, E_NO_MEMORY, E_MORE_TODO = -1, -2, -3, -7, -8
 E_RUNTIME, E_NO_IMPL, E_NO_DEVICE, E_NO_MODEL = -16, -17, -18, -19
 MFCC_A, MFCC_B, MFCC_C, MFCC_TF, MFCC_USE_LOG = 0, 1, 2, 3, 0x100
 EVAL_NNOM, EVAL_KERAS, EVAL_ARGMAX = 0, 1, 2
+FNET_LARGE, FNET_LAYERED = 1, 2   # edison_fnet_load_ex flags
 
 FS, FRAME_LEN, NUM_MEL, NUM_MFCC, UTT_FRAMES, NET_IN, NET_OUT = 16000, 1024, 32, 13, 31, 403, 10
 DIST_ID_BYTES = 128
@@ -170,6 +171,10 @@ SIGNATURES = {
     "edison_fnet_load": (c_int, [c_void_p, c_char_p]),
     "edison_fnet_load_mem": (c_int, [c_void_p, c_void_p, c_size_t]),
     "edison_fnet_info": (c_int, [c_void_p, ctypes.POINTER(FnetInfo)]),
+    "edison_fnet_load_ex": (c_int, [c_void_p, c_char_p, ctypes.c_uint]),
+    "edison_fnet_load_mem_ex": (c_int, [c_void_p, c_void_p, c_size_t, ctypes.c_uint]),
+    "edison_fnet_set_workspace": (c_int, [c_void_p, c_size_t]),
+    "edison_fnet_profile_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "edison_fnet_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "edison_fnet_layers_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "edison_fnet_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),

@@ -341,13 +341,17 @@ class Context:
         self._check(self._L.edison_mfcc_geom_batch_dev(self._h, ctypes.byref(g), _t_ptr(audio), int(n_utt), int(utt_stride), _t_ptr(out)))
 
     # ------------------------------------------------------------------ float32 X-CUBE-AI networks (edison_fnet_*, edison_kws_float_batch*)
-    def fnet_load(self, src):
-        """Load a float network: an .ednf path or its bytes (edison_amd/cube_import.py, tools/import_cube.py). The int8 model stays."""
+    def fnet_load(self, src, large=False, layered=False):
+        """Load a float network: an .ednf path or its bytes (edison_amd/cube_import.py, tools/import_cube.py). The int8 model stays.
+        large: a network the one-launch kernel cannot hold (a layer's weights, or one utterance's activations beside them, exceed the
+        LDS) runs layer by layer instead of being refused (edison_fnet_load_ex, EDISON_FNET_LARGE); a network that fits loads as
+        without it. layered: the layer road even for a network that fits (EDISON_FNET_LAYERED)."""
+        flags = (_lib.FNET_LARGE if large else 0) | (_lib.FNET_LAYERED if layered else 0)
         if isinstance(src, (bytes, bytearray)):
             buf = ctypes.create_string_buffer(bytes(src), len(src))
-            self._check(self._L.edison_fnet_load_mem(self._h, buf, len(src)))
+            self._check(self._L.edison_fnet_load_mem_ex(self._h, buf, len(src), flags))
         else:
-            self._check(self._L.edison_fnet_load(self._h, str(src).encode()))
+            self._check(self._L.edison_fnet_load_ex(self._h, str(src).encode(), flags))
         self._fnet_trainer = None
         self.fnet_keywords = self._ednf_keywords(src)
         self._fnet_blob = bytes(src) if isinstance(src, (bytes, bytearray)) else open(str(src), "rb").read()   # quantize() reads the weights
@@ -362,11 +366,19 @@ class Context:
         except (OSError, cube_import.CubeImportError):
             return None
 
+    def fnet_workspace(self, max_bytes):
+        """Cap the layer road's activation workspace at max_bytes (0: the default, 256 MiB): a layered network runs its utterances in
+        chunks of what the cap holds (edison_fnet_set_workspace)."""
+        self._check(self._L.edison_fnet_set_workspace(self._h, int(max_bytes)))
+
     def fnet_info(self):
-        """dict of edison_fnet_info_t: in_h, in_w, in_c, n_out, n_layers, acts_floats, batch, lds_bytes."""
+        """dict of edison_fnet_info_t: in_h, in_w, in_c, n_out, n_layers, acts_floats, batch, lds_bytes; and layered: the network runs
+        layer by layer (fnet_load's large / layered), which the struct reports as batch 0."""
         info = _lib.FnetInfo()
         self._check(self._L.edison_fnet_info(self._h, ctypes.byref(info)))
-        return {k: getattr(info, k) for k, _ in _lib.FnetInfo._fields_}
+        d = {k: getattr(info, k) for k, _ in _lib.FnetInfo._fields_}
+        d["layered"] = d["batch"] == 0
+        return d
 
     def _fnet_in(self, x):
         info = self.fnet_info()
@@ -455,6 +467,13 @@ class Context:
         """edison_kws_f32_batch_dev on torch device tensors, enqueued on the context's stream (use_torch_stream), no host synchronisation."""
         self._check(self._L.edison_kws_f32_batch_dev(self._h, mfcc._h, _t_ptr(audio), int(n_utt), int(utt_stride), int(hop), _t_ptr(feat),
                                                      _t_ptr(logits), _t_ptr(softmax), _t_ptr(label), _t_ptr(prob)))
+
+    def fnet_profile_t(self, x, n):
+        """A measurement aid (tools/bench_fnet_large.py): a layered network on n device inputs x, outputs dropped; returns float32
+        [n_layers + 1], each record's and the softmax's kernel milliseconds summed over the chunks (edison_fnet_profile_dev)."""
+        ms = np.zeros(self.fnet_info()["n_layers"] + 1, np.float32)
+        self._check(self._L.edison_fnet_profile_dev(self._h, _t_ptr(x), int(n), _np_ptr(ms)))
+        return ms
 
     def fnet_t(self, x, n, logits=None, probs=None, argmax=None):
         """edison_fnet_batch_dev on torch device tensors (x float32 [n][in_n]), on the context's stream."""

@@ -105,6 +105,10 @@ struct edison_ctx
 	ed_geom_cache *geom; /* edison_kws_geom_batch*: the tables of the last geometry (one entry) */
 	ed_fnet *fnet;       /* edison_fnet_load*: the loaded float32 network (edison_fnet.hip), NULL before the first load */
 	int fnet_epoch;      /* counts float network loads (as model_epoch): an edison_stream_float serves the network of one load */
+	/* the layer road's activation scratch (edison_fnet.hip): two buffers in one allocation, grown on demand up to fnet_ws_cap
+	 * (edison_fnet_set_workspace; 0: ED_FNET_WORKSPACE_DEFAULT) */
+	void *fnet_ws;
+	size_t fnet_ws_bytes, fnet_ws_cap;
 	char err[512];
 };
 

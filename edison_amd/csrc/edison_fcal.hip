@@ -38,6 +38,7 @@ extern "C" int edison_fcal_create(edison_ctx *ctx, edison_fcal **out)
 	*out = NULL;
 	const ed_fnet_plan_t *net = ed_ctx_fnet_plan(ctx);
 	if (!net) return ed_set_err(ctx, EDISON_E_NO_MODEL, "no float network loaded (edison_fnet_load)");
+	if (ed_ctx_fnet_layered(ctx)) return ed_fnet_refuse_layered(ctx, "edison_fcal_create");
 	edison_fcal *c = (edison_fcal *)calloc(1, sizeof(*c));
 	if (!c) return ed_set_err(ctx, EDISON_E_NO_MEMORY, "edison_fcal_create: out of host memory");
 	c->ctx = ctx;

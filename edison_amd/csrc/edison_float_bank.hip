@@ -151,6 +151,7 @@ static int create(edison_ctx *ctx, const char *who, const char *noun, const edis
 	*out = NULL;
 	if (n_mics < 1 || n_mics > ED_FLOAT_BANK_MAX_MICS) return bank_err(ctx, who, EDISON_E_ARGUMENT, "n_mics must be 1 .. 4096");
 	if (o->q15 != 0 && o->q15 != 1) return bank_err(ctx, who, EDISON_E_ARGUMENT, "q15 is 0 or 1");
+	if (ed_ctx_fnet_layered(ctx)) return ed_fnet_refuse_layered(ctx, who); /* the window launches are the in-LDS kernels' */
 	int F = 0;
 	/* the batch call's checks: clip range, geometry (q15 = 1: the shipped framing), a float network loaded, F * num_mfcc = its input */
 	{ const int r = ed_kws_float_geom_check(ctx, g, o->q15, o->clip_lo, o->clip_hi, &F); if (r != EDISON_OK) return r; }

@@ -4,6 +4,8 @@
  * network runs on fnet_kernels.hip. edison_kws_float_batch* puts a feature stage in front of it: the float64 MFCC at any geometry
  * (mfcc_geom_kernels.hip) -> float32 x net_input_scale -> clip (the reference's host flow), or variant C -> (float) (the firmware's).
  * The int8 NNoM model of the context is not touched: a context may hold both.
+ * A network the one-launch kernel cannot hold (edison_fnet_load_ex, EDISON_FNET_LARGE) is a layered one: plan.batch 0, run record by
+ * record on fnet_layer_kernels.hip between two buffers of the context's workspace (run_layered).
  */
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -27,6 +29,7 @@ struct ed_fnet
 	int32_t in_h, in_w, in_c;
 	ed_fnet_geom_t geom[ED_FNET_MAX_LAYERS];
 	void *d;
+	bool layered; /* runs on the layer road (fnet_layer_kernels.hip): plan.batch is 0 */
 };
 
 void ed_ctx_fnet_free(edison_ctx *ctx)
@@ -39,6 +42,38 @@ void ed_ctx_fnet_free(edison_ctx *ctx)
 
 const ed_fnet_plan_t *ed_ctx_fnet_plan(const edison_ctx *ctx) { return ctx && ctx->fnet ? &ctx->fnet->plan : NULL; }
 const ed_fnet_geom_t *ed_ctx_fnet_geom(const edison_ctx *ctx) { return ctx && ctx->fnet ? ctx->fnet->geom : NULL; }
+int ed_ctx_fnet_layered(const edison_ctx *ctx) { return ctx && ctx->fnet && ctx->fnet->layered; }
+
+int ed_fnet_refuse_layered(edison_ctx *ctx, const char *who)
+{
+	snprintf(ctx->err, sizeof(ctx->err), "%s: the loaded float network runs on the layer road (edison_fnet_load_ex), which this does not serve", who);
+	return EDISON_E_NO_IMPL;
+}
+
+static size_t ws_cap(const edison_ctx *ctx) { return ctx->fnet_ws_cap ? ctx->fnet_ws_cap : ED_FNET_WORKSPACE_DEFAULT; }
+
+/* Bytes of the layer road's scratch per utterance: one row of each of its two buffers. */
+static size_t ws_per_utt(const ed_fnet_plan_t &p) { return sizeof(float) * ((size_t)p.buf_n[0] + (size_t)p.buf_n[1]); }
+
+/* Utterances per chunk of a layered plan under a cap of `cap` bytes (0: one utterance does not fit): as many as the cap holds and the
+ * kernel's int indices allow, whole M blocks of a dense record where there are that many. */
+static int64_t ws_chunk(const ed_fnet_plan_t &p, size_t cap)
+{
+	int64_t chunk = (int64_t)(cap / ws_per_utt(p));
+	int64_t most = INT32_MAX / (p.buf_n[0] > p.buf_n[1] ? p.buf_n[0] : p.buf_n[1]);
+	for (int l = 0; l < p.n_layers; l++)
+		if (INT32_MAX / 16 / p.L[l].rows < most) most = INT32_MAX / 16 / p.L[l].rows;
+	if (chunk > most) chunk = most;
+	if (chunk > ED_FNET_LAYER_MB) chunk -= chunk % ED_FNET_LAYER_MB;
+	return chunk;
+}
+
+static int ws_too_small(edison_ctx *ctx, const char *who, const ed_fnet_plan_t &p, size_t cap)
+{
+	snprintf(ctx->err, sizeof(ctx->err), "%s: one utterance's activations (%zu bytes) exceed the workspace cap of %zu bytes (edison_fnet_set_workspace)",
+	         who, ws_per_utt(p), cap);
+	return EDISON_E_NO_MEMORY;
+}
 
 static int32_t rd32(const uint8_t *p)
 {
@@ -54,8 +89,12 @@ static int bad(edison_ctx *ctx, const char *msg)
 }
 
 /* Checks the blob and fills *f (plan with offsets, not yet device pointers) and the host images of the weights and the tables. */
-static int parse(edison_ctx *ctx, const uint8_t *b, size_t nb, ed_fnet *f, float **w_out, size_t *nw_out, int32_t **tab_out, size_t *nt_out)
+static int parse(edison_ctx *ctx, const uint8_t *b, size_t nb, unsigned flags, ed_fnet *f, float **w_out, size_t *nw_out, int32_t **tab_out, size_t *nt_out)
 {
+	/* EDISON_FNET_LARGE lifts the two LDS refusals and the EDF_MAX_DIM bound on a record's in_c (a dense record is inp = (1, 1, n)) up
+	 * to what kh kw ic <= 1 << 16 allows; a network it lets through, and any network under EDISON_FNET_LAYERED, is a layered one */
+	const bool large = (flags & EDISON_FNET_LARGE) != 0;
+	bool layered = (flags & EDISON_FNET_LAYERED) != 0;
 	if (nb < EDF_HDR_BYTES || memcmp(b, "EDNF", 4) != 0) return bad(ctx, "not an .ednf blob (magic)");
 	const int ver = rd32(b + 4);
 	if (ver != 1 && ver != 2) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: .ednf version is not 1 or 2");
@@ -84,7 +123,7 @@ static int parse(edison_ctx *ctx, const uint8_t *b, size_t nb, ed_fnet *f, float
 		for (int j = 0; j < ri; j++) v[j] = rd32(r + 4 * j);
 		if (v[0] != EDF_T_CONV && v[0] != EDF_T_SOFTMAX) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: unknown layer type");
 		for (int j = 1; j <= (v[0] == EDF_T_CONV ? 15 : 6); j++)
-			if (v[j] < (j == 11 ? 0 : 1) || v[j] > EDF_MAX_DIM * (j >= 14 ? 16 : 1)) return bad(ctx, "layer field out of range");
+			if (v[j] < (j == 11 ? 0 : 1) || v[j] > EDF_MAX_DIM * (j >= 14 || (j == 3 && large) ? 16 : 1)) return bad(ctx, "layer field out of range");
 		if (v[0] == EDF_T_CONV)
 			for (int j = 16; j < EDF_REC_INTS; j++)
 				if (v[j] < 0 || v[j] > EDF_MAX_DIM) return bad(ctx, "a pad is negative or out of range");
@@ -144,7 +183,11 @@ static int parse(edison_ctx *ctx, const uint8_t *b, size_t nb, ed_fnet *f, float
 		}
 		L.acts_at = (int32_t)acts;
 		const int64_t wl = (int64_t)L.k_pad * L.n_pad;
-		if (wl > ED_FNET_LDS_BYTES / 4) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: a layer's weights exceed the LDS");
+		if (wl > ED_FNET_LDS_BYTES / 4)
+		{
+			if (!large) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: a layer's weights exceed the LDS");
+			layered = true;
+		}
 		wfl += wl + L.n_pad;
 		tabn += kn + L.rows;
 		acts += L.out_n;
@@ -167,9 +210,15 @@ static int parse(edison_ctx *ctx, const uint8_t *b, size_t nb, ed_fnet *f, float
 	const int64_t fixed = 4 * ((int64_t)p.w_lds + p.k_lds), per = 4 * ((int64_t)p.buf_n[0] + p.buf_n[1]);
 	int64_t batch = (ED_FNET_LDS_BYTES - fixed) / per;
 	if (batch > ED_FNET_MAX_BATCH) batch = ED_FNET_MAX_BATCH;
-	if (batch < 1) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: one utterance's activations and the largest layer do not fit the LDS");
-	p.batch = (int32_t)batch;
+	if (batch < 1)
+	{
+		if (!large) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: one utterance's activations and the largest layer do not fit the LDS");
+		layered = true;
+	}
+	p.batch = layered ? 0 : (int32_t)batch; /* 0: ed_fnet_plan_launchable keeps every in-LDS launcher off a layered plan */
+	f->layered = layered;
 	if ((int64_t)p.batch * p.L[n_conv - 1].rows > INT32_MAX / 16) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_load: network too large");
+	if (layered && ws_chunk(p, ws_cap(ctx)) < 1) return ws_too_small(ctx, "edison_fnet_load", p, ws_cap(ctx));
 
 	/* pass 2: weights (already in the kernel's layout) and the koff / rowin tables */
 	float *wh = (float *)malloc(sizeof(float) * (size_t)(wfl ? wfl : 1));
@@ -207,15 +256,24 @@ static int parse(edison_ctx *ctx, const uint8_t *b, size_t nb, ed_fnet *f, float
 	return EDISON_OK;
 }
 
-extern "C" int edison_fnet_load_mem(edison_ctx *ctx, const void *blob, size_t blob_bytes)
+static int bad_flags(edison_ctx *ctx, unsigned flags)
+{
+	if (!(flags & ~(EDISON_FNET_LARGE | EDISON_FNET_LAYERED))) return EDISON_OK;
+	return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_fnet_load_ex: flags has a bit other than EDISON_FNET_LARGE and EDISON_FNET_LAYERED");
+}
+
+extern "C" int edison_fnet_load_mem(edison_ctx *ctx, const void *blob, size_t blob_bytes) { return edison_fnet_load_mem_ex(ctx, blob, blob_bytes, 0); }
+
+extern "C" int edison_fnet_load_mem_ex(edison_ctx *ctx, const void *blob, size_t blob_bytes, unsigned flags)
 {
 	if (!ctx || !blob) return EDISON_E_ARGUMENT;
+	{ const int r = bad_flags(ctx, flags); if (r != EDISON_OK) return r; }
 	ed_fnet *f = new (std::nothrow) ed_fnet();
 	if (!f) return ed_set_err(ctx, EDISON_E_NO_MEMORY, "host allocation failed");
 	float *wh = NULL;
 	int32_t *th = NULL;
 	size_t nw = 0, nt = 0;
-	{ const int r = parse(ctx, (const uint8_t *)blob, blob_bytes, f, &wh, &nw, &th, &nt); if (r != EDISON_OK) { delete f; return r; } }
+	{ const int r = parse(ctx, (const uint8_t *)blob, blob_bytes, flags, f, &wh, &nw, &th, &nt); if (r != EDISON_OK) { delete f; return r; } }
 	const size_t wbytes = (sizeof(float) * nw + 255) & ~(size_t)255, bytes = wbytes + sizeof(int32_t) * nt;
 	hipError_t e = hipSetDevice(ctx->device);
 	if (e == hipSuccess) e = hipMalloc(&f->d, bytes);
@@ -244,9 +302,12 @@ extern "C" int edison_fnet_load_mem(edison_ctx *ctx, const void *blob, size_t bl
 	return EDISON_OK;
 }
 
-extern "C" int edison_fnet_load(edison_ctx *ctx, const char *ednf_path)
+extern "C" int edison_fnet_load(edison_ctx *ctx, const char *ednf_path) { return edison_fnet_load_ex(ctx, ednf_path, 0); }
+
+extern "C" int edison_fnet_load_ex(edison_ctx *ctx, const char *ednf_path, unsigned flags)
 {
 	if (!ctx || !ednf_path) return EDISON_E_ARGUMENT;
+	{ const int r = bad_flags(ctx, flags); if (r != EDISON_OK) return r; }
 	FILE *fp = fopen(ednf_path, "rb");
 	if (!fp) { snprintf(ctx->err, sizeof(ctx->err), "edison_fnet_load: cannot open %s", ednf_path); return EDISON_E_ARGUMENT; }
 	fseek(fp, 0, SEEK_END);
@@ -257,7 +318,7 @@ extern "C" int edison_fnet_load(edison_ctx *ctx, const char *ednf_path)
 	if (!buf) { fclose(fp); return ed_set_err(ctx, EDISON_E_NO_MEMORY, "host allocation failed"); }
 	const size_t got = fread(buf, 1, (size_t)n, fp);
 	fclose(fp);
-	const int r = got == (size_t)n ? edison_fnet_load_mem(ctx, buf, (size_t)n) : bad(ctx, "short read");
+	const int r = got == (size_t)n ? edison_fnet_load_mem_ex(ctx, buf, (size_t)n, flags) : bad(ctx, "short read");
 	free(buf);
 	return r;
 }
@@ -272,8 +333,41 @@ extern "C" int edison_fnet_info(edison_ctx *ctx, edison_fnet_info_t *out)
 	out->n_layers = f->plan.n_layers;
 	out->acts_floats = f->plan.acts_n;
 	out->batch = f->plan.batch;
-	out->lds_bytes = (int32_t)ed_fnet_lds_bytes(&f->plan);
+	out->lds_bytes = f->layered ? ED_FNET_LAYER_LDS_BYTES : (int32_t)ed_fnet_lds_bytes(&f->plan);
 	return EDISON_OK;
+}
+
+extern "C" int edison_fnet_set_workspace(edison_ctx *ctx, size_t max_bytes)
+{
+	if (!ctx) return EDISON_E_ARGUMENT;
+	const size_t cap = max_bytes ? max_bytes : ED_FNET_WORKSPACE_DEFAULT;
+	if (ctx->fnet && ctx->fnet->layered && ws_chunk(ctx->fnet->plan, cap) < 1) return ws_too_small(ctx, "edison_fnet_set_workspace", ctx->fnet->plan, cap);
+	ctx->fnet_ws_cap = max_bytes;
+	return EDISON_OK;
+}
+
+/* The layer road for n utterances: the chunk the cap allows, the scratch grown to it (a growth synchronises the stream once). */
+static int run_layered(edison_ctx *ctx, const float *in, int64_t n, float *logits, float *probs, int32_t *argmax, float *acts, float *ms)
+{
+	const ed_fnet_plan_t &p = ctx->fnet->plan;
+	int64_t chunk = ws_chunk(p, ws_cap(ctx));
+	if (chunk < 1) return ws_too_small(ctx, "edison_fnet_batch", p, ws_cap(ctx));
+	if (chunk > n) chunk = n;
+	const size_t b0 = (sizeof(float) * (size_t)chunk * (size_t)p.buf_n[0] + 255) & ~(size_t)255, need = b0 + sizeof(float) * (size_t)chunk * (size_t)p.buf_n[1];
+	if (need > ctx->fnet_ws_bytes)
+	{
+		ED_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		if (ctx->fnet_ws) (void)hipFree(ctx->fnet_ws);
+		ctx->fnet_ws = NULL;
+		ctx->fnet_ws_bytes = 0;
+		const hipError_t e = hipMalloc(&ctx->fnet_ws, need);
+		if (e == hipErrorOutOfMemory) { ctx->fnet_ws = NULL; return ed_set_err(ctx, EDISON_E_NO_MEMORY, "edison_fnet_batch: hipMalloc of the layer road's workspace: out of HBM"); }
+		ED_HIP(ctx, e);
+		ctx->fnet_ws_bytes = need;
+	}
+	float *const ws[2] = {(float *)ctx->fnet_ws, (float *)((char *)ctx->fnet_ws + b0)};
+	const int e = ed_launch_fnet_layered(&p, in, n, chunk, ws, logits, probs, argmax, acts, ms, ctx->stream);
+	return ed_launch_result(ctx, e, "float network layer kernel");
 }
 
 static int need_net(edison_ctx *ctx, const void *in, int64_t n)
@@ -287,6 +381,7 @@ static int run_on(edison_ctx *ctx, const float *in, int64_t n, float *logits, fl
 {
 	if (n == 0) return EDISON_OK;
 	ED_HIP(ctx, hipSetDevice(ctx->device));
+	if (ctx->fnet->layered) return run_layered(ctx, in, n, logits, probs, argmax, acts, NULL);
 	const int e = ed_launch_fnet(&ctx->fnet->plan, in, ctx->fnet->plan.in_n, n, logits, probs, argmax, acts, ctx->stream);
 	return ed_launch_result(ctx, e, "float network kernel");
 }
@@ -295,6 +390,16 @@ extern "C" int edison_fnet_batch_dev(edison_ctx *ctx, const float *in, int64_t n
 {
 	{ const int r = need_net(ctx, in, n); if (r != EDISON_OK) return r; }
 	return run_on(ctx, in, n, logits, probs, argmax, NULL);
+}
+
+extern "C" int edison_fnet_profile_dev(edison_ctx *ctx, const float *in, int64_t n, float *ms)
+{
+	{ const int r = need_net(ctx, in, n); if (r != EDISON_OK) return r; }
+	if (!ms) return EDISON_E_ARGUMENT;
+	if (!ctx->fnet->layered) return ed_set_err(ctx, EDISON_E_NO_IMPL, "edison_fnet_profile_dev: the loaded float network is not a layered one");
+	if (n == 0) return EDISON_OK;
+	ED_HIP(ctx, hipSetDevice(ctx->device));
+	return run_layered(ctx, in, n, NULL, NULL, NULL, NULL, ms);
 }
 
 extern "C" int edison_fnet_layers_dev(edison_ctx *ctx, const float *in, int64_t n, float *acts)

@@ -117,6 +117,7 @@ extern "C" int edison_ftrain_create_ex(edison_ctx *ctx, uint32_t flags, edison_f
 	if (flags & ~EDISON_FTRAIN_PADDED) return ed_set_err(ctx, EDISON_E_ARGUMENT, "edison_ftrain_create_ex: flags has a bit other than EDISON_FTRAIN_PADDED");
 	const ed_fnet_plan_t *net = ed_ctx_fnet_plan(ctx);
 	if (!net) return ed_set_err(ctx, EDISON_E_NO_MODEL, "no float network loaded (edison_fnet_load)");
+	if (ed_ctx_fnet_layered(ctx)) return ed_fnet_refuse_layered(ctx, "edison_ftrain_create");
 	for (int l = 0; l < net->n_layers; l++)
 		if (net->L[l].pad && !(flags & EDISON_FTRAIN_PADDED))
 		{

@@ -167,6 +167,7 @@ extern "C" void edison_shutdown(edison_ctx *ctx)
 	if (ctx->d_mm_frag) (void)hipFree(ctx->d_mm_frag);
 	if (ctx->d_mm_seeds) (void)hipFree(ctx->d_mm_seeds);
 	if (ctx->scratch) (void)hipFree(ctx->scratch);
+	if (ctx->fnet_ws) (void)hipFree(ctx->fnet_ws);
 	if (ctx->d_exact_tab) (void)hipFree(ctx->d_exact_tab);
 	if (ctx->exact_list) (void)hipFree(ctx->exact_list);
 	ed_ctx_geom_free(ctx);

@@ -14,6 +14,15 @@
 #define ED_FNET_MAX_BATCH 16                  /* utterances per workgroup, at most */
 #define ED_FNET_LDS_BYTES (160 * 1024)
 #define ED_FNET_ORIGIN_BIAS 4096              /* a padded record's rowin entry: (y0 + bias) << 16 | (x0 + bias) */
+/* the layer road (fnet_layer_kernels.hip): a workgroup's tile of one record is MB rows x NB channels, its
+ * operands pass through LDS in chunks of KC k */
+#define ED_FNET_LAYER_MB 128
+#define ED_FNET_LAYER_NB 64
+#define ED_FNET_LAYER_KC 64
+#define ED_FNET_LAYER_SA (ED_FNET_LAYER_KC + 2)   /* LDS row strides of A and B: the operand reads are conflict-free */
+#define ED_FNET_LAYER_SB (ED_FNET_LAYER_NB + 16)
+#define ED_FNET_LAYER_LDS_BYTES (4 * (ED_FNET_LAYER_MB * ED_FNET_LAYER_SA + ED_FNET_LAYER_KC * ED_FNET_LAYER_SB + 3 * ED_FNET_LAYER_MB))
+#define ED_FNET_WORKSPACE_DEFAULT ((size_t)256 << 20) /* cap of the layer road's activation scratch (edison_fnet_set_workspace) */
 
 /* One conv record (a dense layer is a conv whose kernel covers its whole input). Output row r of an utterance is element e = r % P of
  * the pool window of pooled position q = r / P (q = y * out_w + x, P = ph * pw): the P rows of a window are adjacent, so they land in
@@ -73,9 +82,20 @@ extern "C" int ed_launch_fnet(const ed_fnet_plan_t *p, const float *in, int64_t 
  * over its n_mics windows, which computes the same outputs. Returns a hipError_t. */
 extern "C" int ed_launch_fnet_windows(const ed_fnet_plan_t *p, const float *in, int64_t mic_stride, int32_t n_mics, int64_t frame_stride, int32_t n,
                                       float *logits, float *probs, int32_t *argmax, int per_frame, hipStream_t stream);
+/* The layer road: a plan with batch = 0 (a layered network, edison_fnet_load_ex) runs one launch of ed_fnet_layer_kernel per record
+ * and one softmax launch per chunk of at most `chunk` utterances: (n_layers + 1) * ceil(n / chunk) launches. Record l reads
+ * [nu][buf_n[src]] from ws[src] and writes [nu][buf_n[dst]] to ws[dst]; the first record reads `in` in place. ws[i] holds
+ * chunk * buf_n[i] floats. ms != NULL (tools/bench_fnet_large.py): [n_layers + 1] receives each launch's milliseconds, summed over the
+ * chunks, and the stream is synchronised after every chunk. Returns a hipError_t. */
+extern "C" int ed_launch_fnet_layered(const ed_fnet_plan_t *p, const float *in, int64_t n, int64_t chunk, float *const ws[2], float *logits, float *probs,
+                                      int32_t *argmax, float *acts, float *ms, hipStream_t stream);
 /* The context's loaded float network's plan, NULL when none is loaded (edison_fnet.hip). */
 struct edison_ctx;
 const ed_fnet_plan_t *ed_ctx_fnet_plan(const struct edison_ctx *ctx);
+/* Whether the loaded network is a layered one (plan batch 0): every consumer of the plan that runs the in-LDS kernels refuses it by
+ * name with ed_fnet_refuse_layered (EDISON_E_NO_IMPL, "<who>: ... layer road ..."). */
+int ed_ctx_fnet_layered(const struct edison_ctx *ctx);
+int ed_fnet_refuse_layered(struct edison_ctx *ctx, const char *who);
 /* What the plan's tables leave out of a conv record's geometry, for host code that builds tables of its own (the BatchNorm trainer's
  * rows over the whole conv map, edison_ftrain.hip): strides, the pool window, the conv's map ch x cw before the pool and the pooled
  * map oh x ow. [n_layers] of the loaded network, NULL when none is loaded. */

@@ -7,6 +7,9 @@
  *   EDF_LAYER_WALK    one record by the whole workgroup: staging into LDS, the two syncs, the item loop, the nt and pad dispatch
  *   EDF_SOFTMAX       the softmax of one utterance and its first maximum
  *   EDF_NETWORK_BODY  the body of a forward kernel on those pieces
+ * and, for networks that LDS cannot hold (the layer road, fnet_layer_kernels.hip), one record per launch:
+ *   edf_layer_lds / edf_layer_fetch / edf_layer_tile   a workgroup's tile with its operands streamed through LDS in K chunks
+ *   edf_layer_epilogue                                  edf_tile's epilogue restated (why: at the function)
  * ed_fnet_kernel and ed_fnet_windows_kernel (EDF_NETWORK_BODY, edf_no_sink) differ in how the utterances of a tile find their input;
  * ed_fnet_calib_kernel (fnet_calib_kernels.hip) walks with edfc_sink, its statistic in pre; ed_ftrain_grad_kernel
  * (fnet_grad_kernels.hip) expands the plan, the walk and the softmax over a work item of its own. The plan, the walk and the softmax are
@@ -237,5 +240,168 @@ __device__ __forceinline__ void edf_item(int nt, const ed_fnet_layer_t &L, const
 		EDF_SOFTMAX(z, p.n_out, if (logits) logits[u * p.n_out + j] = z[j]; if (probs) probs[u * p.n_out + j] = pj;)                       \
 		if (argmax) argmax[u] = best;                                                                                                      \
 	}
+
+/* ---- the layer road (fnet_layer_kernels.hip): one record per launch, its operands streamed through LDS ------- */
+
+/* A workgroup's LDS: the gathered A[MB][KC] and B[KC][NB] of one K chunk (row strides SA, SB), and per row of the M block what
+ * edf_pad_row gives (a record without pads: its base, -1 for a row beyond M). */
+struct edf_layer_lds
+{
+	float A[ED_FNET_LAYER_MB * ED_FNET_LAYER_SA];
+	float B[ED_FNET_LAYER_KC * ED_FNET_LAYER_SB];
+	int32_t rb[ED_FNET_LAYER_MB], ry[ED_FNET_LAYER_MB], rx[ED_FNET_LAYER_MB];
+};
+static_assert(sizeof(edf_layer_lds) == ED_FNET_LAYER_LDS_BYTES, "fnet.h's ED_FNET_LAYER_LDS_BYTES");
+static_assert(ED_FNET_LAYER_MB == 16 * (ED_FNET_THREADS / 64) && ED_FNET_LAYER_KC == 64 && ED_FNET_LAYER_NB == 64, "the thread maps of edf_layer_fetch");
+
+/* The thread's share of the K chunk at kc0, from global memory into registers: A[wave + 8 i][lane] for i < 16 -- the operand edf_tile
+ * reads, +0.0f for K padding, for a tap outside the image and for a row that is absent or beyond M -- and B[(tid >> 4) + 32 i][4 (tid &
+ * 15) ..] for i < 2, of the NT tiles at n0. */
+template <int NT, bool PAD>
+__device__ __forceinline__ void edf_layer_fetch(const ed_fnet_layer_t &L, const float *__restrict__ gw, const int32_t *__restrict__ koff,
+                                                const float *__restrict__ src, const edf_layer_lds &S, int kc0, int n0, int tid, float (&pa)[16],
+                                                float4 (&pb)[2])
+{
+	const int lane = tid & 63, wave = tid >> 6, k = kc0 + lane;
+	int32_t ko = -1;
+	[[maybe_unused]] int32_t kyx = 0;
+	if (k < L.k_pad)
+	{
+		ko = koff[k];
+		if constexpr (PAD) kyx = koff[L.k_pad + k];
+	}
+#pragma unroll
+	for (int i = 0; i < 16; i++)
+	{
+		const int m = wave + 8 * i;
+		if constexpr (PAD) pa[i] = edf_pad_tap(L, src, S.rb[m], S.ry[m], S.rx[m], ko, kyx);
+		else
+		{
+			const int base = S.rb[m];
+			pa[i] = ko >= 0 && base >= 0 ? src[base + ko] : 0.0f;
+		}
+	}
+	const int c = 4 * (tid & 15);
+#pragma unroll
+	for (int i = 0; i < 2; i++)
+	{
+		const int kb = kc0 + (tid >> 4) + 32 * i;
+		pb[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+		if (kb < L.k_pad && c < 16 * NT) pb[i] = *(const float4 *)(gw + (int64_t)kb * L.n_pad + n0 + c);
+	}
+}
+
+/* edf_tile's epilogue (above, "D: lane holds rows ..."), restated for the layer road without a sink: factored into one function that
+ * both tiles call, the in-LDS kernels compiled to other instructions, so edf_tile keeps its text and this
+ * follows it line by line. Keep the two alike. */
+template <int NT, bool PAD>
+__device__ __forceinline__ void edf_layer_epilogue(const ed_fnet_layer_t &L, const ed_f4 (&acc)[NT], float *__restrict__ dst, int dst_n,
+                                                   const int32_t *__restrict__ rowin, const float *__restrict__ bias, int M, int mt, int n0, int r,
+                                                   int kq, float *__restrict__ acts, int64_t acts_n, int64_t u0)
+{
+	const int P = L.P;
+	const int m0 = mt * 16 + 4 * kq;
+	[[maybe_unused]] bool live[4];
+	if constexpr (PAD) edf_pad_live(L, rowin, M, m0, live);
+#pragma unroll
+	for (int j = 0; j < NT; j++)
+	{
+		const int n = n0 + 16 * j + r;
+		if (n >= L.out_c) continue; /* a padding channel: not written */
+		const float b = bias[n];
+		float v[4];
+#pragma unroll
+		for (int i = 0; i < 4; i++)
+		{
+			v[i] = acc[j][i] + b;
+			if (L.relu) v[i] = fmaxf(v[i], 0.0f);
+			if constexpr (PAD) { if (!live[i]) v[i] = -INFINITY; } /* absent: the max's identity; its window has a real element */
+		}
+		for (int g = 0; g < 4; g += P)
+		{
+			const int mg = m0 + g;
+			if (mg >= M) break;
+			float x = v[g];
+			if (P >= 2) x = fmaxf(x, v[g + 1]);
+			if (P == 4) x = fmaxf(fmaxf(x, v[g + 2]), v[g + 3]);
+			const int u = mg / L.rows, q = (mg - u * L.rows) / P;
+			dst[u * dst_n + q * L.out_c + n] = x;
+			if (acts) acts[(u0 + u) * acts_n + L.acts_at + q * L.out_c + n] = x;
+		}
+	}
+}
+
+/* One workgroup's tile of record L: the MB rows from blockIdx.x * MB of the launch's M = nu * rows (tiles straddle utterances; a dense
+ * record's rows are the utterances), the NT tiles of 16 channels from n0. K is walked in chunks of KC by the whole workgroup and never
+ * split: wave w holds the accumulators of rows 16 w .. 16 w + 15 in registers across the chunks and feeds them the same
+ * mfma_f32_16x16x4f32 steps in the same k order as edf_tile, so every output is the same fmaf chain. The next chunk's operands are
+ * fetched into registers before the current chunk's MFMAs and stored to LDS behind them. */
+template <int NT, bool PAD>
+__device__ __forceinline__ void edf_layer_tile(const ed_fnet_layer_t &L, const float *__restrict__ gw, const int32_t *__restrict__ tab,
+                                               const float *__restrict__ src, int src_n, float *__restrict__ dst, int dst_n, int M, int n0,
+                                               float *__restrict__ acts, int64_t acts_n, int64_t u0, edf_layer_lds &S)
+{
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const int r = lane & 15, kq = lane >> 4;
+	const int mb0 = blockIdx.x * ED_FNET_LAYER_MB;
+	const int32_t *koff = tab + L.koff_at, *rowin = tab + L.rowin_at;
+	if (tid < ED_FNET_LAYER_MB)
+	{
+		const int m = mb0 + tid;
+		int base = -1, y0 = 0, x0 = 0;
+		if constexpr (PAD) edf_pad_row(L, rowin, src_n, M, m, base, y0, x0);
+		else if (m < M)
+		{
+			const int u = m / L.rows;
+			base = u * src_n + rowin[m - u * L.rows];
+		}
+		S.rb[tid] = base; S.ry[tid] = y0; S.rx[tid] = x0;
+	}
+	__syncthreads();
+	ed_f4 acc[NT];
+#pragma unroll
+	for (int j = 0; j < NT; j++) acc[j] = (ed_f4){0.0f, 0.0f, 0.0f, 0.0f};
+	const int mt = blockIdx.x * (ED_FNET_LAYER_MB / 16) + wave;
+	const bool active = mt * 16 < M; /* a wave whose 16 rows lie beyond M stages and syncs, and computes nothing */
+	const float *ap = S.A + (16 * wave + r) * ED_FNET_LAYER_SA + kq;
+	const float *bp = S.B + kq * ED_FNET_LAYER_SB + r;
+	float pa[16];
+	float4 pb[2];
+	edf_layer_fetch<NT, PAD>(L, gw, koff, src, S, 0, n0, tid, pa, pb);
+	for (int kc0 = 0; kc0 < L.k_pad; kc0 += ED_FNET_LAYER_KC)
+	{
+		const int kc = L.k_pad - kc0 < ED_FNET_LAYER_KC ? L.k_pad - kc0 : ED_FNET_LAYER_KC; /* a multiple of 4 */
+		__syncthreads(); /* the previous chunk's operands are no longer read */
+#pragma unroll
+		for (int i = 0; i < 16; i++) S.A[(wave + 8 * i) * ED_FNET_LAYER_SA + lane] = pa[i];
+#pragma unroll
+		for (int i = 0; i < 2; i++) *(float4 *)(S.B + ((tid >> 4) + 32 * i) * ED_FNET_LAYER_SB + 4 * (tid & 15)) = pb[i];
+		__syncthreads();
+		if (kc0 + ED_FNET_LAYER_KC < L.k_pad) edf_layer_fetch<NT, PAD>(L, gw, koff, src, S, kc0 + ED_FNET_LAYER_KC, n0, tid, pa, pb);
+		if (active && kc == ED_FNET_LAYER_KC)
+		{
+#pragma unroll 4
+			for (int kk = 0; kk < ED_FNET_LAYER_KC; kk += 4)
+			{
+				const float a = ap[kk];
+#pragma unroll
+				for (int j = 0; j < NT; j++)
+					acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[kk * ED_FNET_LAYER_SB + 16 * j], acc[j], 0, 0, 0);
+			}
+		}
+		else if (active) /* the last chunk of a k_pad that is no multiple of KC: the same steps, a run-time count */
+		{
+			for (int kk = 0; kk < kc; kk += 4)
+			{
+				const float a = ap[kk];
+#pragma unroll
+				for (int j = 0; j < NT; j++)
+					acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[kk * ED_FNET_LAYER_SB + 16 * j], acc[j], 0, 0, 0);
+			}
+		}
+	}
+	if (active)
+		edf_layer_epilogue<NT, PAD>(L, acc, dst, dst_n, rowin, gw + (int64_t)L.k_pad * L.n_pad, M, mt, n0, r, kq, acts, acts_n, u0);
+}
 
 #endif

@@ -40,7 +40,7 @@ def run(audio_path, labels_path, graph=None, net=None, geometry=None, top_k=2, c
     ctx = ctx or default_context()
     audio, labels = np.load(audio_path), np.load(labels_path)
     if net is not None:
-        ctx.fnet_load(net)
+        ctx.fnet_load(net, large=True)   # a network that exceeds the LDS runs layer by layer; one that fits loads as ever
         g = parse_geometry(geometry, net_input_scale=cfg.net_input_scale) if geometry else None
         res = ctx.evaluate(audio, labels, flow="kws_float", chunk=chunk, top_k=top_k, geometry=g)
     else:

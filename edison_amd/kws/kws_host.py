@@ -162,7 +162,7 @@ def float_file_inference(path, net, pad_mode="zero", ctx=None, out=None):
     """`kws mcu fileinf|frame <wav> --net <file.ednf>`: the wav through the X-CUBE-AI float network's host flow (kws_on_mcu.py:343-348,
     net_type 'cube'): float64 MFCC variant B -> first 13 -> float32 x net_input_scale -> clip(-32768, 32767) -> the network."""
     ctx = ctx or default_context()
-    ctx.fnet_load(net)
+    ctx.fnet_load(net, large=True)   # a network that exceeds the LDS runs layer by layer; one that fits loads as ever
     data = pad_or_cut(read_wav(path), mode=pad_mode)
     res = ctx.kws_float(data, n_utt=1)
     kw = _float_keywords(net)
@@ -176,7 +176,7 @@ def float_frame_inference(path, net, ctx=None, out=None):
     network, printed as kws_on_mcu.report (:148-157) prints them, then the comparison block of the predictions."""
     out = out or sys.stdout
     ctx = ctx or default_context()
-    ctx.fnet_load(net)
+    ctx.fnet_load(net, large=True)   # a network that exceeds the LDS runs layer by layer; one that fits loads as ever
     data = pad_or_cut(read_wav(path), mode="edge")
     host = ctx.kws_float(data, n_utt=1)
     mcu = ctx.kws_float(data, n_utt=1, q15=True)

@@ -109,7 +109,7 @@ def get_model(arch, in_shape=(31, 13, 1), num_classes=10, seed=0):
     bias zero. Record r's kernel is drawn from np.random.default_rng([seed, r]) in float32: the random stream is this library's, not
     TensorFlow's, so the same seed gives the same network here and another one than Keras would. Dropout and BatchNorm are settings of
     the trainer (KERAS_DROPOUT[arch], KERAS_BATCHNORM[arch]), not of the dict. Which dicts the float path runs is the loader's business:
-    conv_model and low_latency_conv have layers whose weights exceed the LDS."""
+    conv_model and low_latency_conv have layers whose weights exceed the LDS, and load with Context.fnet_load(blob, large=True)."""
     if arch not in ARCHS:
         raise ValueError("arch is one of %s" % ", ".join(ARCHS))
     h, w, c = (int(v) for v in in_shape)

@@ -387,12 +387,41 @@ typedef struct edison_fnet_info_t {
 	int32_t n_out;
 	int32_t n_layers;         /* conv / dense layers (ReLU folded in, softmax not counted)                  */
 	int32_t acts_floats;      /* floats per input of edison_fnet_layers                                    */
-	int32_t batch;            /* utterances per workgroup of the kernel                                    */
+	int32_t batch;            /* utterances per workgroup of the kernel; 0: a layered network (below)      */
 	int32_t lds_bytes;        /* LDS per workgroup                                                         */
 } edison_fnet_info_t;
 int edison_fnet_load(edison_ctx *ctx, const char *ednf_path);
 int edison_fnet_load_mem(edison_ctx *ctx, const void *blob, size_t blob_bytes);
 int edison_fnet_info(edison_ctx *ctx, edison_fnet_info_t *out);
+/*
+ * Networks the one-launch kernel cannot hold. edison_fnet_load* stage a whole record's weights and a tile of
+ * utterances' activations in LDS and refuse a network that does not fit; the _ex loads take flags:
+ *   EDISON_FNET_LARGE    such a network loads and runs on the layer road: one launch per conv / dense record and one softmax launch per
+ *                        chunk of utterances, activations in a device workspace the context owns. The flag lifts only the two LDS
+ *                        refusals and the 4096 bound on a record's in_c (a dense record's input is (1, 1, n)), up to what
+ *                        kh kw in_c <= 65536 allows; every other check keeps its code and order. A network that fits gets the same plan
+ *                        and kernel as without the flag.
+ *   EDISON_FNET_LAYERED  the layer road even for a network that fits (A/B and tests).
+ * Flags 0 is the plain call; any other bit is EDISON_E_ARGUMENT. The layer road computes the same k-ordered fmaf chains: its outputs are
+ * bit for bit those of the one-launch kernel. edison_fnet_info reports batch = 0 for a layered network, and the layer kernel's LDS.
+ * edison_fnet_batch*, edison_fnet_layers* and edison_kws_float_batch* take a layered network; the calibrator, the trainer, the float
+ * stream and the float bank answer EDISON_E_NO_IMPL ("... layer road ...") at create.
+ *   edison_fnet_set_workspace  the cap in bytes of the layer road's workspace (0: the default, 256 MiB). n utterances run in
+ *                        ceil(n / chunk) chunks on the context's stream without synchronising between them, chunk = what the cap holds
+ *                        of one utterance's activations (two buffers); the workspace grows on demand (synchronising once) up to the
+ *                        cap. EDISON_E_NO_MEMORY, naming the cap, when one utterance of the loaded layered network exceeds it (the cap
+ *                        stays as it was), and from a load under a cap one utterance of the new network exceeds (the previous network
+ *                        stays).
+ *   edison_fnet_profile_dev    a measurement aid (tools/bench_fnet_large.py): the layer road for n device inputs, no outputs kept;
+ *                        ms [n_layers + 1] receives each record's and the softmax's kernel time in milliseconds between hipEvents,
+ *                        summed over the chunks; it synchronises after every chunk. EDISON_E_NO_IMPL for a network that is not layered.
+ */
+#define EDISON_FNET_LARGE 1u   /* a network the one-launch kernel cannot hold runs layer by layer instead of being refused */
+#define EDISON_FNET_LAYERED 2u /* take the layer road even when the network fits (A/B and tests) */
+int edison_fnet_load_ex(edison_ctx *ctx, const char *ednf_path, unsigned flags);
+int edison_fnet_load_mem_ex(edison_ctx *ctx, const void *blob, size_t blob_bytes, unsigned flags);
+int edison_fnet_set_workspace(edison_ctx *ctx, size_t max_bytes);
+int edison_fnet_profile_dev(edison_ctx *ctx, const float *in, int64_t n, float *ms);
 int edison_fnet_batch_dev(edison_ctx *ctx, const float *in, int64_t n, float *logits, float *probs, int32_t *argmax);
 int edison_fnet_layers_dev(edison_ctx *ctx, const float *in, int64_t n, float *acts);
 int edison_fnet_batch(edison_ctx *ctx, const float *in, int64_t n, float *logits, float *probs, int32_t *argmax);
