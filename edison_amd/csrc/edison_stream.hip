@@ -27,11 +27,15 @@
 #include "edison_ctx.h"
 #include "edison_postproc_core.h"
 
+/* where the last push left its output block: d_out, the staged graph's pinned h_out, or the host-mapped m_out */
+enum { ED_HOME_DEVICE, ED_HOME_STAGED, ED_HOME_MAPPED };
+
 struct edison_stream
 {
 	edison_ctx *ctx;
 	int hop, chunk, tail; /* tail = 1024 - hop samples of history */
 	int last_n;           /* inferences of the LAST push (chunk, or fewer after edison_stream_push_n_dev): what the filtered / state outputs hold */
+	int last_home;        /* ED_HOME_*: the block that holds them (push_done) */
 	int variant;          /* EDISON_MFCC_B or EDISON_MFCC_C */
 	int filter;
 	int use_graph;        /* edison_stream_opts.launch_mode */
@@ -66,7 +70,6 @@ struct edison_stream
 	size_t off_soft, off_argmax, off_filt, off_likely, off_spotted, off_fsm_states, off_fsm, h_out_bytes;
 	hipGraph_t graph_h;
 	hipGraphExec_t exec_h;
-	int last_push_staged;
 	/* host-pointer pushes of a few frames (the microphone case, one frame per push): NO copy nodes at all. The audio ring,
 	 * the feature rows and the outputs live in pinned host memory that the kernels read and write over the bus (2 KB of
 	 * samples, 403 feature bytes, 24 bytes of results per frame); the host shifts the ring and the rows itself. The device
@@ -91,7 +94,6 @@ struct edison_stream
 	hipStream_t q_last;
 	int q_pending;
 	int state_host;       /* 1: the newest tail samples / 30 feature rows are in m_audio / m_feat, 0: in d_audio / d_feat */
-	int last_push_mapped;
 	int64_t frames_seen;
 	int tables_epoch;     /* likewise for the MFCC tables (edison_mfcc_configure) */
 	int model_epoch;      /* the graphs hold the device addresses of the model that was loaded when they were captured */
@@ -327,15 +329,24 @@ extern "C" int edison_stream_reset(edison_stream *s)
 	ED_HIP(ctx, hipMemsetAsync(s->d_audio, 0, sizeof(int16_t) * ((size_t)s->tail + (size_t)s->chunk * s->hop), s->own));
 	ED_HIP(ctx, hipMemsetAsync(s->d_feat, 0, (size_t)(30 + s->chunk) * EDISON_NUM_MFCC, s->own));
 	if (s->filter) ED_HIP(ctx, hipMemsetAsync(s->d_filt_state, 0, sizeof(float) * EDISON_NET_OUT, s->own));
+	/* what the getters read before the next push: a whole chunk of zeros and the start machine, in every home of the block */
+	ED_HIP(ctx, hipMemsetAsync(s->d_out, 0, s->h_out_bytes, s->own));
+	if (s->h_out) memset(s->h_out, 0, s->h_out_bytes);
+	if (s->m_out) memset(s->m_out, 0, s->h_out_bytes);
 	if (s->fsm)
 	{
 		edison_fsm start;
 		edison_fsm_init(&start); /* EDI_RESET, as the firmware enters appMicMfccInfereContinuous (app.c:288-300) */
 		ED_HIP(ctx, hipMemcpyAsync(s->d_fsm, &start, sizeof(start), hipMemcpyHostToDevice, s->own));
+		ED_HIP(ctx, hipMemcpyAsync(s->d_out + s->off_fsm, &start, sizeof(start), hipMemcpyHostToDevice, s->own));
+		if (s->h_out) memcpy(s->h_out + s->off_fsm, &start, sizeof(start));
+		if (s->m_out) memcpy(s->m_out + s->off_fsm, &start, sizeof(start));
 	}
 	ED_HIP(ctx, hipStreamSynchronize(s->own));
 	if (s->m_audio) memset(s->m_audio, 0, sizeof(int16_t) * ((size_t)s->tail + (size_t)s->chunk * s->hop));
 	if (s->m_feat) memset(s->m_feat, 0, (size_t)(30 + s->chunk) * EDISON_NUM_MFCC);
+	s->last_n = s->chunk;
+	s->last_home = ED_HOME_DEVICE;
 	s->frames_seen = 0;
 	return EDISON_OK;
 }
@@ -353,6 +364,60 @@ static int stream_state_to(edison_stream *s, int host)
 	ED_HIP(ctx, hipMemcpyAsync(host ? (void *)s->m_feat : (void *)s->d_feat, host ? (void *)s->d_feat : (void *)s->m_feat, 30 * EDISON_NUM_MFCC, kind, s->own));
 	ED_HIP(ctx, hipStreamSynchronize(s->own));
 	s->state_host = host;
+	return EDISON_OK;
+}
+
+/* a push is refused once the model or the MFCC tables that the stream's graphs and buffers were made for have changed */
+static int stream_live(edison_stream *s)
+{
+	edison_ctx *ctx = s->ctx;
+	if (s->model_epoch != ctx->model_epoch) return ed_set_err(ctx, EDISON_E_ARGUMENT, "stream: the model was reloaded after this stream was created; create a new stream");
+	if (s->tables_epoch != ctx->tables_epoch) return ed_set_err(ctx, EDISON_E_ARGUMENT, "stream: edison_mfcc_configure was called after this stream was created; create a new stream");
+	return EDISON_OK;
+}
+
+/* every exit of a push: its n inferences are in the block `home` */
+static void push_done(edison_stream *s, int n, int home)
+{
+	s->last_n = n;
+	s->last_home = home;
+	s->frames_seen += n;
+}
+
+/* Copy `count` pieces of the block `home` to the caller (host = 1: host pointers, synchronous; host = 0: device pointers, ordered
+ * on the context's stream like a push). The mapped and the staged push left the block in host memory; whatever else wants it comes
+ * from d_out on the private stream, behind the work a device push left on the caller's. */
+struct eds_piece { void *dst; size_t off, bytes; };
+static int fetch(edison_stream *s, int home, const eds_piece *p, int count, int host)
+{
+	edison_ctx *ctx = s->ctx;
+	const unsigned char *h = home == ED_HOME_MAPPED ? s->m_out : (home == ED_HOME_STAGED && host) ? s->h_out : NULL;
+	if (h && host)
+	{
+		for (int i = 0; i < count; i++)
+			if (p[i].dst) memcpy(p[i].dst, h + p[i].off, p[i].bytes);
+		return EDISON_OK;
+	}
+	if (!h) { const int rq = drain_q(s, s->own); if (rq != EDISON_OK) return rq; }
+	const hipMemcpyKind kind = h ? hipMemcpyHostToDevice : host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+	for (int i = 0; i < count; i++)
+		if (p[i].dst) ED_HIP(ctx, hipMemcpyAsync(p[i].dst, (h ? h : s->d_out) + p[i].off, p[i].bytes, kind, s->own));
+	if (host) ED_HIP(ctx, hipStreamSynchronize(s->own));
+	else
+	{
+		ED_HIP(ctx, hipEventRecord(s->ev_out, s->own));
+		ED_HIP(ctx, hipStreamWaitEvent(ctx->stream, s->ev_out, 0));
+	}
+	return EDISON_OK;
+}
+
+/* the end of a push of n frames that left its block in `home`: the network's outputs to the caller (each may be NULL; host as in fetch) */
+static int push_out(edison_stream *s, int n, int home, int8_t *logits, int8_t *softmax, int32_t *argmax, int host)
+{
+	const size_t c = (size_t)n;
+	const eds_piece p[3] = {{logits, 0, c * EDISON_NET_OUT}, {softmax, s->off_soft, c * EDISON_NET_OUT}, {argmax, s->off_argmax, c * sizeof(int32_t)}};
+	{ const int r = fetch(s, home, p, 3, host); if (r != EDISON_OK) return r; }
+	push_done(s, n, home);
 	return EDISON_OK;
 }
 
@@ -394,7 +459,6 @@ extern "C" int edison_stream_create_ex(edison_ctx *ctx, const edison_stream_opts
 	edison_stream *s = (edison_stream *)calloc(1, sizeof(edison_stream));
 	if (!s) return ed_set_err(ctx, EDISON_E_NO_MEMORY, "host allocation failed");
 	s->ctx = ctx; s->hop = hop; s->chunk = chunk_frames; s->tail = EDISON_FRAME_LEN - hop;
-	s->last_n = chunk_frames; /* before the first push the (zeroed) blocks read as a whole chunk */
 	s->variant = o->mfcc_variant;
 	s->model_epoch = ctx->model_epoch;
 	s->tables_epoch = ctx->tables_epoch;
@@ -451,7 +515,6 @@ extern "C" int edison_stream_create_ex(edison_ctx *ctx, const edison_stream_opts
 	/* one eager push on silence: sizes the persistent grids / sets kernel attributes outside of graph capture */
 	if (r == EDISON_OK) r = enqueue_push(s);
 	if (r == EDISON_OK && hipStreamSynchronize(s->own) != hipSuccess) r = ed_set_err(ctx, EDISON_E_RUNTIME, "stream: warm-up failed");
-	if (r == EDISON_OK) r = edison_stream_reset(s);
 	if (r == EDISON_OK)
 	{
 		/* capture one push into a graph; every later push is a single hipGraphLaunch */
@@ -517,6 +580,8 @@ extern "C" int edison_stream_create_ex(edison_ctx *ctx, const edison_stream_opts
 			s->mapped = 0;
 		}
 	}
+	/* the warm-up push behind us and every home of the block allocated: a new stream is a reset one (the captures ran nothing) */
+	if (r == EDISON_OK) r = edison_stream_reset(s);
 	if (r != EDISON_OK) { edison_stream_destroy(s); return r; }
 	*out = s;
 	return EDISON_OK;
@@ -547,11 +612,9 @@ extern "C" int edison_stream_push_n_dev(edison_stream *s, const int16_t *samples
 	if (!s || !samples) return EDISON_E_ARGUMENT;
 	edison_ctx *ctx = s->ctx;
 	if (n_frames < 1 || n_frames > s->chunk) return ed_set_err(ctx, EDISON_E_ARGUMENT, "stream: n_frames must be 1 .. chunk_frames");
-	if (s->model_epoch != ctx->model_epoch) return ed_set_err(ctx, EDISON_E_ARGUMENT, "stream: the model was reloaded after this stream was created; create a new stream");
-	if (s->tables_epoch != ctx->tables_epoch) return ed_set_err(ctx, EDISON_E_ARGUMENT, "stream: edison_mfcc_configure was called after this stream was created; create a new stream");
+	{ const int rl = stream_live(s); if (rl != EDISON_OK) return rl; }
 	const size_t nnew = (size_t)n_frames * s->hop;
 	{ const int rs = stream_state_to(s, 0); if (rs != EDISON_OK) return rs; }
-	s->last_push_mapped = 0;
 	if (!s->use_graph)
 	{
 		/* direct launches, on the caller's stream: one copy + MFCC + CNN (+ filter) + shift, the CNN writing the caller's
@@ -565,9 +628,7 @@ extern "C" int edison_stream_push_n_dev(edison_stream *s, const int16_t *samples
 		if (s->filter && softmax) ED_HIP(ctx, hipMemcpyAsync(softmax, s->d_soft, (size_t)n_frames * EDISON_NET_OUT, hipMemcpyDeviceToDevice, q));
 		s->q_last = q;
 		s->q_pending = 1;
-		s->last_push_staged = 0;
-		s->last_n = n_frames;
-		s->frames_seen += n_frames;
+		push_done(s, n_frames, ED_HOME_DEVICE);
 		return EDISON_OK;
 	}
 	/* graph replay: on the private stream (a graph is captured on one stream), ordered against the caller's with events.
@@ -590,16 +651,8 @@ extern "C" int edison_stream_push_n_dev(edison_stream *s, const int16_t *samples
 		const int rd = enqueue_push_on(s, s->own, s->d_logits, s->d_soft, s->d_argmax, 0, n_frames);
 		if (rd != EDISON_OK) return rd;
 	}
-	s->last_push_staged = 0;
-	if (logits) ED_HIP(ctx, hipMemcpyAsync(logits, s->d_logits, (size_t)n_frames * EDISON_NET_OUT, hipMemcpyDeviceToDevice, s->own));
-	if (softmax) ED_HIP(ctx, hipMemcpyAsync(softmax, s->d_soft, (size_t)n_frames * EDISON_NET_OUT, hipMemcpyDeviceToDevice, s->own));
-	if (argmax) ED_HIP(ctx, hipMemcpyAsync(argmax, s->d_argmax, (size_t)n_frames * sizeof(int32_t), hipMemcpyDeviceToDevice, s->own));
 	/* ... and the context's stream continues only after the outputs are written */
-	ED_HIP(ctx, hipEventRecord(s->ev_out, s->own));
-	ED_HIP(ctx, hipStreamWaitEvent(ctx->stream, s->ev_out, 0));
-	s->last_n = n_frames;
-	s->frames_seen += n_frames;
-	return EDISON_OK;
+	return push_out(s, n_frames, ED_HOME_DEVICE, logits, softmax, argmax, 0);
 }
 
 /* the same with host pointers; synchronous */
@@ -607,13 +660,11 @@ extern "C" int edison_stream_push(edison_stream *s, const int16_t *samples, int8
 {
 	if (!s || !samples) return EDISON_E_ARGUMENT;
 	edison_ctx *ctx = s->ctx;
-	if (s->model_epoch != ctx->model_epoch) return ed_set_err(ctx, EDISON_E_ARGUMENT, "stream: the model was reloaded after this stream was created; create a new stream");
-	if (s->tables_epoch != ctx->tables_epoch) return ed_set_err(ctx, EDISON_E_ARGUMENT, "stream: edison_mfcc_configure was called after this stream was created; create a new stream");
+	{ const int rl = stream_live(s); if (rl != EDISON_OK) return rl; }
 	const size_t nnew = (size_t)s->chunk * s->hop;
 	static const int no_mapped = getenv("EDISON_STREAM_NO_MAPPED") ? atoi(getenv("EDISON_STREAM_NO_MAPPED")) : 0; /* A/B knob: the staged graph */
 	if (s->mapped && !no_mapped && !s->use_graph)
 	{
-		const size_t c = (size_t)s->chunk;
 		{ const int rs = stream_state_to(s, 1); if (rs != EDISON_OK) return rs; }
 		memcpy(s->m_audio + s->tail, samples, nnew * sizeof(int16_t));
 		const unsigned seq = ++s->flag_seq;
@@ -644,46 +695,24 @@ extern "C" int edison_stream_push(edison_stream *s, const int16_t *samples, int8
 				(void)hipGetLastError();
 			if (!waited) ED_HIP(ctx, hipStreamSynchronize(s->own));
 		}
-		if (logits) memcpy(logits, s->m_out, c * EDISON_NET_OUT);
-		if (softmax) memcpy(softmax, s->m_out + s->off_soft, c * EDISON_NET_OUT);
-		if (argmax) memcpy(argmax, s->m_out + s->off_argmax, c * sizeof(int32_t));
 		/* what the shift kernel does on the device path: the newest tail samples and 30 rows to the front */
 		if (s->tail) memmove(s->m_audio, s->m_audio + nnew, sizeof(int16_t) * (size_t)s->tail);
-		memmove(s->m_feat, s->m_feat + c * EDISON_NUM_MFCC, 30 * EDISON_NUM_MFCC);
-		s->last_push_staged = 0;
-		s->last_push_mapped = 1;
-		s->last_n = s->chunk;
-	s->frames_seen += s->chunk;
-		return EDISON_OK;
+		memmove(s->m_feat, s->m_feat + (size_t)s->chunk * EDISON_NUM_MFCC, 30 * EDISON_NUM_MFCC);
+		return push_out(s, s->chunk, ED_HOME_MAPPED, logits, softmax, argmax, 1);
 	}
 	{ const int rs = stream_state_to(s, 0); if (rs != EDISON_OK) return rs; }
 	{ const int rq = drain_q(s, s->own); if (rq != EDISON_OK) return rq; } /* device pushes may have left work on the caller's stream */
 	{ const int rf = history_to_front(s, s->own); if (rf != EDISON_OK) return rf; } /* ... and the history somewhere behind the front */
-	s->last_push_mapped = 0;
 	if (s->exec_h)
 	{
-		const size_t c = (size_t)s->chunk;
 		memcpy(s->h_in, samples, nnew * sizeof(int16_t));
 		ED_HIP(ctx, hipGraphLaunch(s->exec_h, s->own));
 		ED_HIP(ctx, hipStreamSynchronize(s->own));
-		if (logits) memcpy(logits, s->h_out, c * EDISON_NET_OUT);
-		if (softmax) memcpy(softmax, s->h_out + s->off_soft, c * EDISON_NET_OUT);
-		if (argmax) memcpy(argmax, s->h_out + s->off_argmax, c * sizeof(int32_t));
-		s->last_push_staged = 1;
-		s->last_n = s->chunk;
-	s->frames_seen += s->chunk;
-		return EDISON_OK;
+		return push_out(s, s->chunk, ED_HOME_STAGED, logits, softmax, argmax, 1);
 	}
-	s->last_push_staged = 0;
 	ED_HIP(ctx, hipMemcpyAsync(s->d_audio + s->tail, samples, nnew * sizeof(int16_t), hipMemcpyHostToDevice, s->own));
 	{ const int rd = enqueue_push(s); if (rd != EDISON_OK) return rd; } /* plain launches (see edison_stream_push_dev) */
-	if (logits) ED_HIP(ctx, hipMemcpyAsync(logits, s->d_logits, (size_t)s->chunk * EDISON_NET_OUT, hipMemcpyDeviceToHost, s->own));
-	if (softmax) ED_HIP(ctx, hipMemcpyAsync(softmax, s->d_soft, (size_t)s->chunk * EDISON_NET_OUT, hipMemcpyDeviceToHost, s->own));
-	if (argmax) ED_HIP(ctx, hipMemcpyAsync(argmax, s->d_argmax, (size_t)s->chunk * sizeof(int32_t), hipMemcpyDeviceToHost, s->own));
-	ED_HIP(ctx, hipStreamSynchronize(s->own));
-	s->last_n = s->chunk;
-	s->frames_seen += s->chunk;
-	return EDISON_OK;
+	return push_out(s, s->chunk, ED_HOME_DEVICE, logits, softmax, argmax, 1); /* the downloads and the wait */
 }
 
 /* Filtered outputs of the LAST push (filter enabled in the options): filt [n][10] fp32, likely / spotted [n], n = the frames of that
@@ -697,82 +726,20 @@ static int stream_filter_out(edison_stream *s, float *filt, int32_t *likely, int
 	/* entries of the last push only: after a ragged push (edison_stream_push_n_dev, n < chunk) the rows n.. of the stream's blocks
 	 * are an earlier push's, and a caller that sized its buffers [n][..] must not be written past them */
 	const size_t c = (size_t)s->last_n;
-	if (s->last_push_mapped)
-	{
-		/* the mapped push wrote them into pinned host memory */
-		if (host)
-		{
-			if (filt) memcpy(filt, s->m_out + s->off_filt, c * EDISON_NET_OUT * sizeof(float));
-			if (likely) memcpy(likely, s->m_out + s->off_likely, c * sizeof(int32_t));
-			if (spotted) memcpy(spotted, s->m_out + s->off_spotted, c * sizeof(int32_t));
-			return EDISON_OK;
-		}
-		if (filt) ED_HIP(ctx, hipMemcpyAsync(filt, s->m_out + s->off_filt, c * EDISON_NET_OUT * sizeof(float), hipMemcpyHostToDevice, s->own));
-		if (likely) ED_HIP(ctx, hipMemcpyAsync(likely, s->m_out + s->off_likely, c * sizeof(int32_t), hipMemcpyHostToDevice, s->own));
-		if (spotted) ED_HIP(ctx, hipMemcpyAsync(spotted, s->m_out + s->off_spotted, c * sizeof(int32_t), hipMemcpyHostToDevice, s->own));
-		ED_HIP(ctx, hipEventRecord(s->ev_out, s->own));
-		ED_HIP(ctx, hipStreamWaitEvent(ctx->stream, s->ev_out, 0));
-		return EDISON_OK;
-	}
-	{ const int rq = drain_q(s, s->own); if (rq != EDISON_OK) return rq; }
-	if (host && s->last_push_staged)
-	{
-		/* the staged push already brought them to the host */
-		if (filt) memcpy(filt, s->h_out + s->off_filt, c * EDISON_NET_OUT * sizeof(float));
-		if (likely) memcpy(likely, s->h_out + s->off_likely, c * sizeof(int32_t));
-		if (spotted) memcpy(spotted, s->h_out + s->off_spotted, c * sizeof(int32_t));
-		return EDISON_OK;
-	}
-	const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-	if (filt) ED_HIP(ctx, hipMemcpyAsync(filt, s->d_filt, sizeof(float) * c * EDISON_NET_OUT, kind, s->own));
-	if (likely) ED_HIP(ctx, hipMemcpyAsync(likely, s->d_likely, sizeof(int32_t) * c, kind, s->own));
-	if (spotted) ED_HIP(ctx, hipMemcpyAsync(spotted, s->d_spotted, sizeof(int32_t) * c, kind, s->own));
-	if (host) ED_HIP(ctx, hipStreamSynchronize(s->own));
-	else
-	{
-		ED_HIP(ctx, hipEventRecord(s->ev_out, s->own));
-		ED_HIP(ctx, hipStreamWaitEvent(ctx->stream, s->ev_out, 0));
-	}
-	return EDISON_OK;
+	const eds_piece p[3] = {{filt, s->off_filt, c * EDISON_NET_OUT * sizeof(float)}, {likely, s->off_likely, c * sizeof(int32_t)},
+	                        {spotted, s->off_spotted, c * sizeof(int32_t)}};
+	return fetch(s, s->last_home, p, 3, host);
 }
 
-/* the state machine after the LAST push and the state after each of its inferences */
+/* the state machine after the LAST push (the block's copy of it: the filter kernel and the one-launch kernel write it on every push,
+ * reset writes the start machine; d_fsm is the kernels' own) and the state after each of its inferences */
 static int stream_fsm_out(edison_stream *s, edison_fsm *fsm, int32_t *states, int host)
 {
 	if (!s) return EDISON_E_ARGUMENT;
-	edison_ctx *ctx = s->ctx;
-	if (!s->fsm) return ed_set_err(ctx, EDISON_E_ARGUMENT, "stream: created without the state machine (opts.fsm)");
-	const size_t c = (size_t)s->last_n; /* as in stream_filter_out: the last push's entries only */
-	if (s->last_push_mapped)
-	{
-		if (host)
-		{
-			if (fsm) memcpy(fsm, s->m_out + s->off_fsm, sizeof(*fsm));
-			if (states) memcpy(states, s->m_out + s->off_fsm_states, c * sizeof(int32_t));
-			return EDISON_OK;
-		}
-		if (states) ED_HIP(ctx, hipMemcpyAsync(states, s->m_out + s->off_fsm_states, c * sizeof(int32_t), hipMemcpyHostToDevice, s->own));
-		ED_HIP(ctx, hipEventRecord(s->ev_out, s->own));
-		ED_HIP(ctx, hipStreamWaitEvent(ctx->stream, s->ev_out, 0));
-		return EDISON_OK;
-	}
-	{ const int rq = drain_q(s, s->own); if (rq != EDISON_OK) return rq; }
-	if (host && s->last_push_staged)
-	{
-		if (fsm) memcpy(fsm, s->h_out + s->off_fsm, sizeof(*fsm));
-		if (states) memcpy(states, s->h_out + s->off_fsm_states, c * sizeof(int32_t));
-		return EDISON_OK;
-	}
-	const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-	if (states) ED_HIP(ctx, hipMemcpyAsync(states, s->d_out + s->off_fsm_states, c * sizeof(int32_t), kind, s->own));
-	if (host && fsm) ED_HIP(ctx, hipMemcpyAsync(fsm, s->d_fsm, sizeof(*fsm), hipMemcpyDeviceToHost, s->own));
-	if (host) ED_HIP(ctx, hipStreamSynchronize(s->own));
-	else
-	{
-		ED_HIP(ctx, hipEventRecord(s->ev_out, s->own));
-		ED_HIP(ctx, hipStreamWaitEvent(ctx->stream, s->ev_out, 0));
-	}
-	return EDISON_OK;
+	if (!s->fsm) return ed_set_err(s->ctx, EDISON_E_ARGUMENT, "stream: created without the state machine (opts.fsm)");
+	/* as in stream_filter_out: the last push's entries only */
+	const eds_piece p[2] = {{states, s->off_fsm_states, (size_t)s->last_n * sizeof(int32_t)}, {fsm, s->off_fsm, sizeof(*fsm)}};
+	return fetch(s, s->last_home, p, 2, host);
 }
 
 extern "C" int edison_stream_fsm(edison_stream *s, edison_fsm *fsm, int32_t *states) { return stream_fsm_out(s, fsm, states, 1); }

@@ -23,6 +23,7 @@ from .context import KEYWORDS, default_context
 class _Handle:
     """What the stream and bank classes share: the life of the handle ``_h`` on the C functions ``<_C>*`` and the state machine's view."""
     _C = None    # "edison_stream_", "edison_stream_geom_", "edison_stream_bank_", "edison_stream_float_", "edison_float_bank_"
+    n_mics = None    # a bank's microphones; None: one stream, whose pushes and outputs have no microphone axis
 
     def _c(self, name):
         return getattr(self._L, self._C + name)
@@ -48,6 +49,60 @@ class _Handle:
     def fsm_snapshot(self):
         """The state machine as the last edison_stream*_fsm call saw it: dict(state, hot_timeout_ms, last_command, commands)."""
         return _fsm_dict(self._fsm)
+
+    def _options(self, o, chunk_frames, output_filter, alpha, threshold, fsm):
+        """The options every stream has, into its struct ``o`` (a bank's ``o.stream``) and onto the handle."""
+        o.chunk_frames = int(chunk_frames)
+        o.filter = 1 if (output_filter or fsm) else 0
+        o.fsm = 1 if fsm else 0         # the firmware's state machine as the last GPU stage of every push (edison_stream*_fsm)
+        o.filter_alpha, o.true_threshold = float(alpha), float(threshold)
+        self.chunk, self.output_filter, self.fsm = int(chunk_frames), bool(output_filter or fsm), bool(fsm)
+
+    def _push_t(self, samples, logits, second, argmax, filtered, likely, spotted, n_frames, fsm_states=None, present=None):
+        """push_t behind every signature: `second` is the softmax or the probabilities; `fsm_states` and `present` are the banks'."""
+        n, m = self.chunk if n_frames is None else int(n_frames), self.n_mics
+        if m is None:
+            if samples.numel() != n * self.hop:
+                raise ValueError("push needs exactly n_frames*hop = %d samples" % (n * self.hop))
+        elif samples.numel() != m * n * self.hop or not samples.is_contiguous():
+            raise ValueError("push needs contiguous [n_mics, n_frames*hop] = [%d, %d] samples" % (m, n * self.hop))
+        q = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        if present is not None:
+            if str(present.dtype) not in ("torch.uint8", "torch.bool") or tuple(present.shape) != (m,) or not present.is_contiguous() \
+                    or present.device != samples.device:
+                raise self._mask_error("a contiguous uint8 [n_mics] = [%d] tensor on the samples' device" % m)
+            self.ctx._check(getattr(self._L, self._P + "push_present_n_dev")(self._h, q(samples), q(present), n, q(logits), q(second), q(argmax)))
+        elif n_frames is None:
+            self.ctx._check(self._c("push_dev")(self._h, q(samples), q(logits), q(second), q(argmax)))
+        else:
+            self.ctx._check(self._c("push_n_dev")(self._h, q(samples), n, q(logits), q(second), q(argmax)))
+        if filtered is not None or likely is not None or spotted is not None:
+            self.ctx._check(self._c("filtered_dev")(self._h, q(filtered), q(likely), q(spotted)))
+        if fsm_states is not None:
+            self.ctx._check(self._c("fsm_dev")(self._h, None, q(fsm_states)))
+
+    def _filter_tail(self, out, lead, machine):
+        """The filter's and the state machine's outputs of a host push, behind the network's: ``lead`` is their leading shape, (chunk,) or
+        (chunk, n_mics), ``machine`` the handle's edison_fsm or its array of them."""
+        if self.output_filter:
+            fl, li, sp = np.zeros(lead + (self.n_out,), np.float32), np.zeros(lead, np.int32), np.zeros(lead, np.int32)
+            self.ctx._check(self._c("filtered")(self._h, fl.ctypes.data, li.ctypes.data, sp.ctypes.data))
+            out.update(filtered=fl, likely=li, spotted=sp)
+        if self.fsm:
+            st = np.zeros(lead, np.int32)
+            self.ctx._check(self._c("fsm")(self._h, ctypes.byref(machine), st.ctypes.data))
+            out.update(fsm_states=st, fsm=self.fsm_snapshot())
+        return out
+
+
+def _float_options(o, geometry, q15, clip_min, clip_max):
+    """The float pair's own options into ``o``; returns the geometry (None: what ``Context.kws_float`` uses by default)."""
+    from . import config as cfg
+    from .kws.geometry import KwsGeometry
+    o.q15 = 1 if q15 else 0
+    o.clip_lo = float(cfg.net_input_clip_min if clip_min is None else clip_min)
+    o.clip_hi = float(cfg.net_input_clip_max if clip_max is None else clip_max)
+    return KwsGeometry.from_config(net_input_scale=cfg.net_input_scale) if geometry is None else geometry
 
 
 def _fsm_dict(f):
@@ -92,74 +147,19 @@ class _Bank(_Handle):
             raise self._mask_error("uint8 [n_mics] = [%d], not %s %s" % (self.n_mics, p.dtype, list(p.shape)))
         return np.ascontiguousarray(p)
 
-    def _push_t(self, samples, logits, second, argmax, filtered, likely, spotted, fsm_states, n_frames, present):
-        """push_t behind either signature: `second` is the softmax or the probabilities."""
-        n = self.chunk if n_frames is None else int(n_frames)
-        if samples.numel() != self.n_mics * n * self.hop or not samples.is_contiguous():
-            raise ValueError("push needs contiguous [n_mics, n_frames*hop] = [%d, %d] samples" % (self.n_mics, n * self.hop))
-        q = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        if present is not None:
-            if str(present.dtype) not in ("torch.uint8", "torch.bool") or tuple(present.shape) != (self.n_mics,) or not present.is_contiguous() \
-                    or present.device != samples.device:
-                raise self._mask_error("a contiguous uint8 [n_mics] = [%d] tensor on the samples' device" % self.n_mics)
-            self.ctx._check(getattr(self._L, self._P + "push_present_n_dev")(self._h, q(samples), q(present), n, q(logits), q(second), q(argmax)))
-        elif n_frames is None:
-            self.ctx._check(self._c("push_dev")(self._h, q(samples), q(logits), q(second), q(argmax)))
-        else:
-            self.ctx._check(self._c("push_n_dev")(self._h, q(samples), n, q(logits), q(second), q(argmax)))
-        if filtered is not None or likely is not None or spotted is not None:
-            self.ctx._check(self._c("filtered_dev")(self._h, q(filtered), q(likely), q(spotted)))
-        if fsm_states is not None:
-            self.ctx._check(self._c("fsm_dev")(self._h, None, q(fsm_states)))
-
-    def _filter_tail(self, out):
-        """The filter's and the state machine's outputs of a host push, behind the network's."""
-        c, m, no = self.chunk, self.n_mics, self.n_out
-        if self.output_filter:
-            fl, li, sp = np.zeros((c, m, no), np.float32), np.zeros((c, m), np.int32), np.zeros((c, m), np.int32)
-            self.ctx._check(self._c("filtered")(self._h, fl.ctypes.data, li.ctypes.data, sp.ctypes.data))
-            out.update(filtered=fl, likely=li, spotted=sp)
-        if self.fsm:
-            st = np.zeros((c, m), np.int32)
-            self.ctx._check(self._c("fsm")(self._h, ctypes.byref(self._fsms), st.ctypes.data))
-            out.update(fsm_states=st, fsm=self.fsm_snapshot())
-        return out
+    def fsm_snapshot(self):
+        """The state machines as the last host push saw them: one stream's ``fsm_snapshot`` dict per microphone."""
+        return [_fsm_dict(f) for f in self._fsms]
 
 
 class _SlidingStream(_Handle):
-    """What GeomStream and FloatStream share around their own network outputs: in a host push the sample check in front and the filter's
-    and the state machine's outputs behind, and the device push."""
+    """What GeomStream and FloatStream share in front of a host push: the sample check."""
 
     def _host_samples(self, samples):
         x = np.ascontiguousarray(samples, dtype=np.int16).ravel()
         if x.shape[0] != self.chunk * self.hop:
             raise ValueError("push needs exactly chunk_frames*hop = %d samples" % (self.chunk * self.hop))
         return x
-
-    def _filter_tail(self, out):
-        c, no = self.chunk, self.n_out
-        if self.output_filter:
-            fl, li, sp = np.zeros((c, no), np.float32), np.zeros(c, np.int32), np.zeros(c, np.int32)
-            self.ctx._check(self._c("filtered")(self._h, fl.ctypes.data, li.ctypes.data, sp.ctypes.data))
-            out.update(filtered=fl, likely=li, spotted=sp)
-        if self.fsm:
-            st = np.zeros(c, np.int32)
-            self.ctx._check(self._c("fsm")(self._h, ctypes.byref(self._fsm), st.ctypes.data))
-            out.update(fsm_states=st, fsm=self.fsm_snapshot())
-        return out
-
-    def _push_t(self, samples, logits, second, argmax, filtered, likely, spotted, n_frames):
-        """push_t behind either signature: `second` is the softmax or the probabilities."""
-        n = self.chunk if n_frames is None else int(n_frames)
-        if samples.numel() != n * self.hop:
-            raise ValueError("push needs exactly n_frames*hop = %d samples" % (n * self.hop))
-        q = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        if n_frames is None:
-            self.ctx._check(self._c("push_dev")(self._h, q(samples), q(logits), q(second), q(argmax)))
-        else:
-            self.ctx._check(self._c("push_n_dev")(self._h, q(samples), n, q(logits), q(second), q(argmax)))
-        if filtered is not None or likely is not None or spotted is not None:
-            self.ctx._check(self._c("filtered_dev")(self._h, q(filtered), q(likely), q(spotted)))
 
 
 class Stream(_Handle):
@@ -171,17 +171,14 @@ class Stream(_Handle):
         self._L = _lib.lib()
         o = _lib.StreamOpts()
         self._L.edison_stream_default_opts(ctypes.byref(o))
-        o.hop, o.chunk_frames = int(hop), int(chunk_frames)
+        self._options(o, chunk_frames, output_filter, alpha, threshold, fsm)
+        o.hop = self.hop = int(hop)
         o.mfcc_variant = _lib.MFCC_C if q15 else _lib.MFCC_B
-        o.filter = 1 if (output_filter or fsm) else 0
-        o.fsm = 1 if fsm else 0         # the firmware's state machine as the last GPU stage of every push (edison_stream_fsm)
-        o.filter_alpha, o.true_threshold = float(alpha), float(threshold)
         if graph is not None:    # None: the library's default (direct launches unless EDISON_STREAM_GRAPH=1)
             o.launch_mode = 1 if graph else 0
         h = ctypes.c_void_p()
         self.ctx._check(self._L.edison_stream_create_ex(self.ctx._h, ctypes.byref(o), ctypes.byref(h)))
         self._h = h
-        self.hop, self.chunk, self.output_filter, self.fsm = int(hop), int(chunk_frames), bool(output_filter or fsm), bool(fsm)
         self._fsm_states = np.zeros(self.chunk, np.int32)
         self._fsm = _lib.Fsm()
         self._bufs = None
@@ -222,16 +219,7 @@ class Stream(_Handle):
         """Device tensors (torch, int16 / int8 / int32 / fp32 on the context's GPU); asynchronous on the context's stream.
         n_frames < chunk_frames: a ragged last push (edison_stream_push_n_dev: n_frames * hop samples); every output -- logits, softmax,
         argmax, filtered, likely, spotted -- is [n_frames][..]: the stream copies the entries of THIS push only."""
-        n = self.chunk if n_frames is None else int(n_frames)
-        if samples.numel() != n * self.hop:
-            raise ValueError("push needs exactly n_frames*hop = %d samples" % (n * self.hop))
-        q = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        if n_frames is None:
-            self.ctx._check(self._L.edison_stream_push_dev(self._h, q(samples), q(logits), q(softmax), q(argmax)))
-        else:
-            self.ctx._check(self._L.edison_stream_push_n_dev(self._h, q(samples), n, q(logits), q(softmax), q(argmax)))
-        if filtered is not None or likely is not None or spotted is not None:
-            self.ctx._check(self._L.edison_stream_filtered_dev(self._h, q(filtered), q(likely), q(spotted)))
+        self._push_t(samples, logits, softmax, argmax, filtered, likely, spotted, n_frames)
 
 
 class GeomStream(_SlidingStream):
@@ -250,19 +238,14 @@ class GeomStream(_SlidingStream):
         self._L = _lib.lib()
         o = _lib.StreamGeomOpts()
         self._L.edison_stream_geom_default_opts(ctypes.byref(o))
-        o.chunk_frames = int(chunk_frames)
-        o.filter = 1 if (output_filter or fsm) else 0
-        o.fsm = 1 if fsm else 0
-        o.filter_alpha, o.true_threshold = float(alpha), float(threshold)
+        self._options(o, chunk_frames, output_filter, alpha, threshold, fsm)
         g = geometry.to_ctypes()
         h = ctypes.c_void_p()
         self.ctx._check(self._L.edison_stream_geom_create(self.ctx._h, ctypes.byref(g), ctypes.byref(o), ctypes.byref(h)))
         self._h = h
         info = self.ctx.net_info()
-        self.geometry = geometry
-        self.hop, self.chunk = int(geometry.frame_step), int(chunk_frames)
+        self.geometry, self.hop = geometry, int(geometry.frame_step)
         self.n_out, self.has_softmax = int(info["n_out"]), bool(info["has_softmax"])
-        self.output_filter, self.fsm = bool(output_filter or fsm), bool(fsm)
         self._fsm = _lib.Fsm()
 
     def push(self, samples):
@@ -278,7 +261,7 @@ class GeomStream(_SlidingStream):
         out = dict(logits=lo, softmax=so, argmax=am)
         if no == NET_OUT:
             out["keywords"] = [KEYWORDS[i] for i in am]
-        return self._filter_tail(out)
+        return self._filter_tail(out, (c,), self._fsm)
 
     def push_t(self, samples, logits=None, softmax=None, argmax=None, filtered=None, likely=None, spotted=None, n_frames=None):
         """Device tensors (torch, int16 / int8 / int32 / fp32 on the context's GPU); asynchronous on the context's stream. n_frames <
@@ -303,24 +286,15 @@ class StreamBank(_Bank):
         o = _lib.StreamBankOpts()
         self._L.edison_stream_bank_default_opts(ctypes.byref(o))
         o.n_mics = int(n_mics)
-        o.stream.chunk_frames = int(chunk_frames)
-        o.stream.filter = 1 if (output_filter or fsm) else 0
-        o.stream.fsm = 1 if fsm else 0
-        o.stream.filter_alpha, o.stream.true_threshold = float(alpha), float(threshold)
+        self._options(o.stream, chunk_frames, output_filter, alpha, threshold, fsm)
         g = geometry.to_ctypes()
         h = ctypes.c_void_p()
         self.ctx._check(self._L.edison_stream_bank_create(self.ctx._h, ctypes.byref(g), ctypes.byref(o), ctypes.byref(h)))
         self._h = h
         info = self.ctx.net_info()
-        self.geometry = geometry
-        self.n_mics, self.hop, self.chunk = int(n_mics), int(geometry.frame_step), int(chunk_frames)
+        self.geometry, self.n_mics, self.hop = geometry, int(n_mics), int(geometry.frame_step)
         self.n_out, self.has_softmax = int(info["n_out"]), bool(info["has_softmax"])
-        self.output_filter, self.fsm = bool(output_filter or fsm), bool(fsm)
         self._fsms = (_lib.Fsm * self.n_mics)()
-
-    def fsm_snapshot(self):
-        """The state machines as the last host push saw them: one ``GeomStream.fsm_snapshot`` dict per microphone."""
-        return [_fsm_dict(f) for f in self._fsms]
 
     def push(self, samples, present=None):
         """samples: [n_mics, chunk_frames * hop] new int16 samples (host). Returns ``GeomStream.push``'s dict with the microphone axis
@@ -344,14 +318,14 @@ class StreamBank(_Bank):
         out = dict(logits=lo, softmax=so, argmax=am, present=p)
         if no == NET_OUT:
             out["keywords"] = [[KEYWORDS[i] if i >= 0 else None for i in row] for row in am]
-        return self._filter_tail(out)
+        return self._filter_tail(out, (c, m), self._fsms)
 
     def push_t(self, samples, logits=None, softmax=None, argmax=None, filtered=None, likely=None, spotted=None, fsm_states=None, n_frames=None,
                present=None):
         """Device tensors (torch, int16 / int8 / int32 / fp32 on the context's GPU); asynchronous on the context's stream. samples
         [n_mics][n * hop]; every output [n][n_mics][..] with n = chunk_frames, or n_frames <= chunk_frames for a ragged push. ``present``:
         a device uint8 [n_mics] tensor, read on the context's stream (keep it unchanged until the push has run); None: everyone."""
-        self._push_t(samples, logits, softmax, argmax, filtered, likely, spotted, fsm_states, n_frames, present)
+        self._push_t(samples, logits, softmax, argmax, filtered, likely, spotted, n_frames, fsm_states, present)
 
 
 class FloatStream(_SlidingStream):
@@ -369,30 +343,19 @@ class FloatStream(_SlidingStream):
 
     def __init__(self, ctx, geometry=None, q15=False, chunk_frames=1, output_filter=False, alpha=0.5, threshold=0.5, fsm=False,
                  clip_min=None, clip_max=None):
-        from . import config as cfg
-        from .kws.geometry import KwsGeometry
         self.ctx = ctx or default_context()
         self._L = _lib.lib()
-        if geometry is None:
-            geometry = KwsGeometry.from_config(net_input_scale=cfg.net_input_scale)
         o = _lib.StreamFloatOpts()
         self._L.edison_stream_float_default_opts(ctypes.byref(o))
-        o.chunk_frames = int(chunk_frames)
-        o.q15 = 1 if q15 else 0
-        o.clip_lo = float(cfg.net_input_clip_min if clip_min is None else clip_min)
-        o.clip_hi = float(cfg.net_input_clip_max if clip_max is None else clip_max)
-        o.filter = 1 if (output_filter or fsm) else 0
-        o.fsm = 1 if fsm else 0
-        o.filter_alpha, o.true_threshold = float(alpha), float(threshold)
+        self._options(o, chunk_frames, output_filter, alpha, threshold, fsm)
+        geometry = _float_options(o, geometry, q15, clip_min, clip_max)
         g = geometry.to_ctypes()
         h = ctypes.c_void_p()
         self.ctx._check(self._L.edison_stream_float_create(self.ctx._h, ctypes.byref(g), ctypes.byref(o), ctypes.byref(h)))
         self._h = h
-        self.geometry = geometry
-        self.hop, self.chunk = int(geometry.frame_step), int(chunk_frames)
+        self.geometry, self.hop = geometry, int(geometry.frame_step)
         self.n_out = int(self.ctx.fnet_info()["n_out"])
         self.keywords = getattr(self.ctx, "fnet_keywords", None)   # the names of the loaded .ednf (Context.fnet_load)
-        self.output_filter, self.fsm = bool(output_filter or fsm), bool(fsm)
         self._fsm = _lib.Fsm()
 
     def push(self, samples):
@@ -407,7 +370,7 @@ class FloatStream(_SlidingStream):
         names = self.keywords or (list(KEYWORDS) if no == NET_OUT else None)
         if names is not None:
             out["keywords"] = [names[i] if i < len(names) else str(i) for i in am]
-        return self._filter_tail(out)
+        return self._filter_tail(out, (c,), self._fsm)
 
     def push_t(self, samples, logits=None, probs=None, argmax=None, filtered=None, likely=None, spotted=None, n_frames=None):
         """Device tensors (torch, int16 / fp32 / int32 on the context's GPU); asynchronous on the context's stream. n_frames <
@@ -427,36 +390,21 @@ class FloatBank(_Bank):
 
     def __init__(self, ctx, n_mics, geometry=None, q15=False, chunk_frames=1, output_filter=False, alpha=0.5, threshold=0.5, fsm=False,
                  clip_min=None, clip_max=None):
-        from . import config as cfg
-        from .kws.geometry import KwsGeometry
         self.ctx = ctx or default_context()
         self._L = _lib.lib()
-        if geometry is None:
-            geometry = KwsGeometry.from_config(net_input_scale=cfg.net_input_scale)
         o = _lib.FloatBankOpts()
         self._L.edison_float_bank_default_opts(ctypes.byref(o))
         o.n_mics = int(n_mics)
-        o.stream.chunk_frames = int(chunk_frames)
-        o.stream.q15 = 1 if q15 else 0
-        o.stream.clip_lo = float(cfg.net_input_clip_min if clip_min is None else clip_min)
-        o.stream.clip_hi = float(cfg.net_input_clip_max if clip_max is None else clip_max)
-        o.stream.filter = 1 if (output_filter or fsm) else 0
-        o.stream.fsm = 1 if fsm else 0
-        o.stream.filter_alpha, o.stream.true_threshold = float(alpha), float(threshold)
+        self._options(o.stream, chunk_frames, output_filter, alpha, threshold, fsm)
+        geometry = _float_options(o.stream, geometry, q15, clip_min, clip_max)
         g = geometry.to_ctypes()
         h = ctypes.c_void_p()
         self.ctx._check(self._L.edison_float_bank_create(self.ctx._h, ctypes.byref(g), ctypes.byref(o), ctypes.byref(h)))
         self._h = h
-        self.geometry = geometry
-        self.n_mics, self.hop, self.chunk = int(n_mics), int(geometry.frame_step), int(chunk_frames)
+        self.geometry, self.n_mics, self.hop = geometry, int(n_mics), int(geometry.frame_step)
         self.n_out = int(self.ctx.fnet_info()["n_out"])
         self.keywords = getattr(self.ctx, "fnet_keywords", None)   # the names of the loaded .ednf (Context.fnet_load)
-        self.output_filter, self.fsm = bool(output_filter or fsm), bool(fsm)
         self._fsms = (_lib.Fsm * self.n_mics)()
-
-    def fsm_snapshot(self):
-        """The state machines as the last host push saw them: one ``FloatStream.fsm_snapshot`` dict per microphone."""
-        return [_fsm_dict(f) for f in self._fsms]
 
     def push(self, samples, present=None):
         """samples: [n_mics, chunk_frames * hop] new int16 samples (host). Returns ``FloatStream.push``'s dict with the microphone axis
@@ -479,14 +427,14 @@ class FloatBank(_Bank):
         names = self.keywords or (list(KEYWORDS) if no == NET_OUT else None)
         if names is not None:
             out["keywords"] = [[None if i < 0 else names[i] if i < len(names) else str(i) for i in row] for row in am]
-        return self._filter_tail(out)
+        return self._filter_tail(out, (c, m), self._fsms)
 
     def push_t(self, samples, logits=None, probs=None, argmax=None, filtered=None, likely=None, spotted=None, fsm_states=None, n_frames=None,
                present=None):
         """Device tensors (torch, int16 / fp32 / int32 on the context's GPU); asynchronous on the context's stream. samples
         [n_mics][n * hop]; every output [n][n_mics][..] with n = chunk_frames, or n_frames <= chunk_frames for a ragged push. ``present``:
         a device uint8 [n_mics] tensor, read on the context's stream (keep it unchanged until the push has run); None: everyone."""
-        self._push_t(samples, logits, probs, argmax, filtered, likely, spotted, fsm_states, n_frames, present)
+        self._push_t(samples, logits, probs, argmax, filtered, likely, spotted, n_frames, fsm_states, present)
 
 
 class Fsm:

@@ -756,7 +756,9 @@ int edison_stream_create_ex(edison_ctx *ctx, const edison_stream_opts *o, edison
 int edison_stream_filtered(edison_stream *s, float *filt /* host */, int32_t *likely, int32_t *spotted);
 int edison_stream_filtered_dev(edison_stream *s, float *filt /* device */, int32_t *likely, int32_t *spotted);
 /* The state machine of a stream created with fsm = 1, after the LAST push: *fsm = the machine (may be NULL), states [n] int32 =
- * the state it was in after each of the n inferences of that push (may be NULL; n as for edison_stream_filtered). */
+ * the state it was in after each of the n inferences of that push (may be NULL; n as for edison_stream_filtered).
+ * Before the first push after edison_stream_create* or edison_stream_reset these four answer chunk_frames entries of zeros and the
+ * machine as edison_fsm_init leaves it. */
 struct edison_fsm;
 int edison_stream_fsm(edison_stream *s, struct edison_fsm *fsm /* host */, int32_t *states /* host */);
 int edison_stream_fsm_dev(edison_stream *s, int32_t *states /* device */);

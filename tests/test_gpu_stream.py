@@ -14,7 +14,7 @@ def _windows_from_features(rows):
     return np.stack([padded[i:i + 31].reshape(-1) for i in range(n)])
 
 
-@pytest.mark.parametrize("hop,chunk", [(1024, 1), (1024, 7), (512, 5), (512, 64)])
+@pytest.mark.parametrize("hop,chunk", [(1024, 1), (1024, 7), (512, 5), (512, 64), (1024, 513)])
 def test_stream_matches_batch_windows(ctx, oracle_mod, oracle_model, hop, chunk):
     from edison_amd import _lib
     from edison_amd.stream import Stream
@@ -484,7 +484,7 @@ def test_postproc_argument_checks(ctx):
     assert ok["fsm_states"].tolist() == [1, 1, 1, 1]
 
 
-@pytest.mark.parametrize("hop,chunk", [(512, 1), (512, 6), (1024, 64)])
+@pytest.mark.parametrize("hop,chunk", [(512, 1), (512, 6), (1024, 64), (1024, 513)])
 def test_stream_with_the_state_machine_as_its_last_stage(ctx, oracle_mod, hop, chunk):
     """A stream created with fsm = 1: host pushes (chunk 1: the one-launch kernel steps the machine itself; larger chunks: the filter
     kernel's last lane walks the push) and device pushes give, inference by inference, the states of the host chain run on the
@@ -525,3 +525,128 @@ def test_stream_with_the_state_machine_as_its_last_stage(ctx, oracle_mod, hop, c
     st.close()
     with pytest.raises(Exception):
         Stream(ctx, hop=hop, chunk_frames=chunk, fsm=True, output_filter=False, alpha=2.0)
+
+
+# The homes of a push's output block (edison_stream.hip), each reached by the smallest shape that gets there: host pushes of at most
+# 16 KB of samples run against the host-mapped block, up to 1 MB through the staged graph's pinned block (in graph mode from the
+# first byte), above that with plain copies from the device block; a device push leaves the device block (here a ragged one: n = 2).
+_ROADS = {"mapped": dict(hop=512, chunk=3, graph=False), "staged": dict(hop=512, chunk=17, graph=False),
+          "staged_graph": dict(hop=512, chunk=3, graph=True), "plain": dict(hop=1024, chunk=513, graph=False),
+          "device": dict(hop=512, chunk=3, graph=False, n=2)}
+_GUARD = -77
+
+
+def _road_stream(ctx, road):
+    from edison_amd.stream import Stream
+    r = _ROADS[road]
+    return Stream(ctx, hop=r["hop"], chunk_frames=r["chunk"], output_filter=True, fsm=True, graph=r["graph"])
+
+
+def _road_push(st, road, x, whole=False):
+    """One push of x down the road (the device road's: its ragged n frames of x, or with `whole` the chunk); returns (n, its logits /
+    softmax / argmax)."""
+    import torch
+    if "n" not in _ROADS[road]:
+        o = st.push(x)
+        return st.chunk, {k: o[k] for k in ("logits", "softmax", "argmax")}
+    n = st.chunk if whole else _ROADS[road]["n"]
+    dev = torch.device("cuda", 0)
+    lo, so = (torch.zeros((n, 10), dtype=torch.int8, device=dev) for _ in range(2))
+    am = torch.zeros((n,), dtype=torch.int32, device=dev)
+    st.push_t(torch.from_numpy(x[:n * st.hop].copy()).to(dev), logits=lo, softmax=so, argmax=am, n_frames=None if whole else n)
+    torch.cuda.synchronize()
+    return n, dict(logits=lo.cpu().numpy(), softmax=so.cpu().numpy(), argmax=am.cpu().numpy())
+
+
+def _getters(ctx, st):
+    """What the host and the device getters answer now, into buffers eight entries longer than a chunk and pre-filled with a guard:
+    two dicts of filtered, likely, spotted, fsm_states (whole buffers), the host one with the machine's raw fields as `fsm`."""
+    import ctypes
+    import torch
+    from edison_amd import _lib
+    L, c = st._L, st.chunk + 8
+    hf, hl, hs, hst = np.full((c, 10), _GUARD, np.float32), np.full(c, _GUARD, np.int32), np.full(c, _GUARD, np.int32), np.full(c, _GUARD, np.int32)
+    m = _lib.Fsm()
+    ctx._check(L.edison_stream_filtered(st._h, hf.ctypes.data, hl.ctypes.data, hs.ctypes.data))
+    ctx._check(L.edison_stream_fsm(st._h, ctypes.byref(m), hst.ctypes.data))
+    dev = torch.device("cuda", 0)
+    df = torch.full((c, 10), _GUARD, dtype=torch.float32, device=dev)
+    dl, ds, dst = (torch.full((c,), _GUARD, dtype=torch.int32, device=dev) for _ in range(3))
+    torch.cuda.synchronize()
+    ctx._check(L.edison_stream_filtered_dev(st._h, df.data_ptr(), dl.data_ptr(), ds.data_ptr()))
+    ctx._check(L.edison_stream_fsm_dev(st._h, dst.data_ptr()))
+    torch.cuda.synchronize()
+    host = dict(filtered=hf, likely=hl, spotted=hs, fsm_states=hst, fsm=tuple(getattr(m, f[0]) for f in m._fields_))
+    return host, dict(filtered=df.cpu().numpy(), likely=dl.cpu().numpy(), spotted=ds.cpu().numpy(), fsm_states=dst.cpu().numpy())
+
+
+def _assert_getters(ctx, st, n, want):
+    """Host and device getters answer exactly n entries, equal to each other and to `want` (filtered, likely, spotted, fsm_states
+    [n][..]); returns the machine the host getter answered."""
+    host, dev = _getters(ctx, st)
+    for k in ("filtered", "likely", "spotted", "fsm_states"):
+        for got in (host[k], dev[k]):
+            assert (got[n:] == _GUARD).all(), k
+            assert np.array_equal(got[:n].view(np.uint32), np.asarray(want[k], got.dtype).view(np.uint32)), k
+    return host["fsm"]
+
+
+def _start_machine():
+    import ctypes
+    from edison_amd import _lib
+    m = _lib.Fsm()
+    _lib.lib().edison_fsm_init(ctypes.byref(m))
+    return tuple(getattr(m, f[0]) for f in m._fields_)
+
+
+@pytest.mark.parametrize("road", list(_ROADS))
+def test_getters_answer_the_last_push_on_every_road(ctx, oracle_mod, road):
+    """edison_stream_filtered* / edison_stream_fsm* after each of two pushes, whichever block the push left its outputs in: host and
+    device getters agree, write exactly the n entries of that push, and equal the host chain (the oracle's filter, oracle/fsm_ref.py)
+    on the stream's own softmax, the machine included."""
+    r = _ROADS[road]
+    hop, chunk, thr = r["hop"], r["chunk"], 0.5
+    rng = np.random.default_rng(hop + chunk + len(road))
+    audio = np.clip(rng.normal(0, 2500, 2 * chunk * hop), -32768, 32767).astype(np.int16)
+    st = _road_stream(ctx, road)
+    soft = []
+    for i in range(2):
+        n, o = _road_push(st, road, audio[i * chunk * hop:(i + 1) * chunk * hop], whole=i == 0)   # the ragged push behind a whole one
+        soft.append(o["softmax"])
+        filt, likely, spotted, _, states, fsm = _host_chain(oracle_mod, np.concatenate(soft), 0.9, thr, hop * 1_000_000 // 16000)
+        machine = _assert_getters(ctx, st, n, dict(filtered=filt[-n:], likely=likely[-n:], spotted=spotted[-n:], fsm_states=states[-n:]))
+        assert _fsm_tuple(machine) == _fsm_tuple(fsm), i
+    st.close()
+
+
+@pytest.mark.parametrize("road", list(_ROADS))
+def test_reset_clears_what_the_getters_read(ctx, road):
+    """Before the first push after a create or a reset the getters answer chunk_frames entries of zeros and the edison_fsm_init machine
+    (not the create-time warm-up push on silence, not the previous recording's last push), in every home of the block; the first push
+    after a reset then answers what a new stream's first push answers."""
+    r = _ROADS[road]
+    hop, chunk = r["hop"], r["chunk"]
+    rng = np.random.default_rng(7 * hop + chunk + len(road))
+    audio = np.clip(rng.normal(0, 2500, 2 * chunk * hop), -32768, 32767).astype(np.int16)
+    zeros = dict(filtered=np.zeros((chunk, 10), np.float32), likely=np.zeros(chunk, np.int32), spotted=np.zeros(chunk, np.int32),
+                 fsm_states=np.zeros(chunk, np.int32))
+
+    def first_push(st):
+        n, o = _road_push(st, road, audio[:chunk * hop])
+        host, _ = _getters(ctx, st)
+        return dict(o, fsm=host.pop("fsm"), **{k: v[:n] for k, v in host.items()})
+
+    new = _road_stream(ctx, road)
+    assert _assert_getters(ctx, new, chunk, zeros) == _start_machine()
+    want = first_push(new)
+    new.close()
+    st = _road_stream(ctx, road)
+    _road_push(st, road, audio[chunk * hop:])
+    st.reset()
+    assert _assert_getters(ctx, st, chunk, zeros) == _start_machine()
+    got = first_push(st)
+    st.close()
+    assert got.keys() == want.keys() and got["fsm"] == want["fsm"]
+    for k in want:
+        if k != "fsm":
+            assert np.array_equal(got[k].view(np.uint8), want[k].view(np.uint8)), k
