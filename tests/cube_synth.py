@@ -2,16 +2,23 @@
 firmware/src/ai/cube/kws/kws.c and kws_data.c are laid out) from seeded random weights: the importer's input for networks at other
 geometries than the shipped one, and for layers it must refuse.
 
-Layer specs: ("conv", out_c, (kh, kw), (sh, sw), (ph, pw), relu) -- conv2d_nl_pool when (ph, pw) != (1, 1), else conv2d --
-("dense", n_out), ("relu",), ("softmax",). Returns (net_c, data_c)."""
+Layer specs: ("conv", out_c, (kh, kw), (sh, sw), (ph, pw), relu[, cpad, ppad]) -- conv2d_nl_pool when (ph, pw) != (1, 1), else
+conv2d; the pads (top, left, bottom, right), zeros when left out, are written as X-CUBE-AI's (x start, y start, x end, y end) --
+("dense", n_out), ("relu",), ("softmax",). weight_scale: the conv weights' deviation in place of 1 / sqrt(K); overrides: {layer name:
+fields of its layer declaration to replace}; declared: {layer index: (h, w)} writes another output shape than the computed one. The
+last two are for sources the importer must refuse. Returns (net_c, data_c)."""
 import numpy as np
+
+from edison_amd import cube_import
+
+from fnet_host import Z4, out_hw
 
 
 def _hwc(name, h, w, c, array=None):
     return dict(name=name, shape=(1, c, w, h), stride=(4, 4, 4 * c, 4 * c * w), array=array or name + "_array", n=h * w * c)
 
 
-def cube_sources(in_shape, specs, seed=0, name="net", weight_scale=None, overrides=None):
+def cube_sources(in_shape, specs, seed=0, name="net", weight_scale=None, overrides=None, declared=None):
     rng = np.random.default_rng(seed)
     overrides = overrides or {}
     h, w, c = in_shape
@@ -29,13 +36,16 @@ def cube_sources(in_shape, specs, seed=0, name="net", weight_scale=None, overrid
         blob.extend(np.asarray(vals, "<f4").tobytes())
         return tname
 
+    def shape4(p):
+        return "AI_SHAPE_INIT(4, %d, %d, %d, %d)" % (p[1], p[0], p[3], p[2])
+
     for i, s in enumerate(specs):
         lname = "layer_%d" % i
         if s[0] == "conv":
-            _, oc, (kh, kw), (sh, sw), (ph, pw), relu = s
+            _, oc, (kh, kw), (sh, sw), (ph, pw), relu, cp, pp = s if len(s) == 8 else s + (Z4, Z4)
             ic = cur["shape"][1]
             ch, cw = cur["shape"][3], cur["shape"][2]
-            oh, ow = ((ch - kh) // sh + 1) // ph, ((cw - kw) // sw + 1) // pw
+            oh, ow = (declared or {}).get(i) or out_hw((ch, cw), (kh, kw), (sh, sw), (ph, pw), cp, pp)
             sc = weight_scale or 1.0 / np.sqrt(kh * kw * ic)
             W = rng.normal(0, sc, (oc, kh, kw, ic)).astype(np.float32)       # [out][kh][kw][in]
             B = rng.normal(0, 0.1, oc).astype(np.float32)
@@ -45,10 +55,10 @@ def cube_sources(in_shape, specs, seed=0, name="net", weight_scale=None, overrid
             pool = (ph, pw) != (1, 1)
             fields = [".groups = 1", ".nl_func = %s" % ("nl_func_relu_array_f32" if relu else "NULL"),
                       ".filter_stride = AI_SHAPE_2D_INIT(%d, %d)" % (sw, sh), ".dilation = AI_SHAPE_2D_INIT(1, 1)",
-                      ".filter_pad = AI_SHAPE_INIT(4, 0, 0, 0, 0)"]
+                      ".filter_pad = " + shape4(cp)]
             if pool:
                 fields += [".pool_size = AI_SHAPE_2D_INIT(%d, %d)" % (pw, ph), ".pool_stride = AI_SHAPE_2D_INIT(%d, %d)" % (pw, ph),
-                           ".pool_pad = AI_SHAPE_INIT(4, 0, 0, 0, 0)", ".pool_func = pool_func_mp_array_f32"]
+                           ".pool_pad = " + shape4(pp), ".pool_func = pool_func_mp_array_f32"]
             kind = ("OPTIMIZED_CONV2D_TYPE", "conv2d_nl_pool", "forward_conv2d_nl_pool") if pool else ("CONV2D_TYPE", "conv2d", "forward_conv2d")
             layers.append(dict(name=lname, kind=kind, fields=fields, inp=cur, out=out, params=[wt, bt]))
         elif s[0] == "dense":
@@ -99,3 +109,8 @@ def cube_sources(in_shape, specs, seed=0, name="net", weight_scale=None, overrid
     data = ('#include "%s_data.h"\n\nai_handle ai_%s_data_weights_get(void)\n{\n  AI_ALIGNED(4)\n  static const ai_u8 s_%s_weights[ %d ] = {\n    %s\n  };\n'
             "  return AI_HANDLE_PTR(s_%s_weights);\n}\n" % (name, name, name, len(blob), ",\n    ".join(rows), name))
     return "\n\n".join(L), data
+
+
+def import_sources(net_c, data_c):
+    """The .ednf blob the importer makes of such sources."""
+    return cube_import.build_blob(cube_import.convert(cube_import.parse_net_c(net_c), cube_import.parse_data_c(data_c)))

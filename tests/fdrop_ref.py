@@ -15,8 +15,8 @@ import numpy as np
 
 from edison_amd import train
 
-import fnet_pad
-from fnet_ref import conv_records
+import fnet_host
+from fnet_host import conv_records
 
 M32 = np.uint64(0xffffffff)
 
@@ -100,8 +100,8 @@ def factors(model, sp, seed, call, n):
         k = kept(seed, call, n, l, rows * oc, rate).reshape(n, rows, oc)
         f = np.where(k, scale(rate), np.float32(0)).astype(np.float32)
         if before:
-            ch, cw = fnet_pad.conv_map(L)
-            pp = fnet_pad.pads(L)[1]
+            ch, cw = fnet_host.conv_map(L)
+            pp = fnet_host.pads(L)[1]
             bordered = np.ones((n, ch + pp[0] + pp[2], cw + pp[1] + pp[3], oc))
             bordered[:, :Ph * ph, :Pw * pw] = f.astype(np.float64).reshape(n, Ph, Pw, ph, pw, oc).transpose(0, 1, 3, 2, 4, 5).reshape(n, Ph * ph, Pw * pw, oc)
             image = bordered[:, pp[0]:pp[0] + ch, pp[1]:pp[1] + cw]
@@ -114,7 +114,7 @@ def factors(model, sp, seed, call, n):
 # ---- the bit-exact host model with the mask -----------------------------------------------------------------------------------------
 def forward32(model, x, sp, seed, call, detail=False):
     """The kernel's forward half with dropout: every record's stored output [n][out_n] float32, bit for bit (the last is the logits).
-    fnet_pad.pre_activation's values are the GPU's; ReLU, the mask, x s in float32 and the pool follow them. detail=True: per record
+    fnet_host.pre_activation's values are the GPU's; ReLU, the mask, x s in float32 and the pool follow them. detail=True: per record
     also (first [n][Ph Pw][oc], positive [n][rows][oc], dropped [n][Ph Pw][oc]: the winner, or the pooled output, was dropped)."""
     a = np.asarray(x, np.float32)
     n = len(a)
@@ -122,7 +122,7 @@ def forward32(model, x, sp, seed, call, detail=False):
     for L, F in zip(conv_records(model), factors(model, sp, seed, call, n)):
         Ph, Pw, oc = L["out"]
         P = L["p"][0] * L["p"][1]
-        v, live = fnet_pad.pre_activation(L, a)
+        v, live = fnet_host.pre_activation(L, a)
         pos = v > 0
         if L["relu"]:
             v = np.maximum(v, np.float32(0))

@@ -102,9 +102,9 @@ def blob_of(net, geom):
 
 @functools.lru_cache(maxsize=None)
 def plan_of(net, geom):
-    """fnet_exact.plan of the row's network: in_n, n_out, batch (the utterances of a tile)."""
-    import fnet_exact
-    p = fnet_exact.plan(blob_of(net, geom))
+    """fnet_plan.plan of the row's network: in_n, n_out, batch (the utterances of a tile)."""
+    import fnet_plan
+    p = fnet_plan.plan(blob_of(net, geom))
     assert "error" not in p, (net, geom, p)
     return p
 

@@ -1,5 +1,5 @@
 """Float64 restatement of training a float network (edison_amd/train.py, csrc/fnet_grad_kernels.hip, csrc/fnet_bn_kernels.hip,
-csrc/fnet_data_kernels.hip) on fnet_ref's and fnet_pad's conventions: the loss and its gradient with respect to
+csrc/fnet_data_kernels.hip) on fnet_host's conventions: the loss and its gradient with respect to
 every weight and bias in the model dict's layout, with 'same' pads, dropout and BatchNorm as options of ONE function; the same network
 through torch's autograd; the bound the GPU tests allow; the trainer's plan and the order of its sums; Adam and Adadelta as Keras states
 them; and a host trainer that edison_amd.train.fit and fit_data drive like the GPU one. Test infrastructure, not a test: the CPU
@@ -38,11 +38,11 @@ import numpy as np
 
 from edison_amd import cube_import, train
 
-import fnet_exact
-import fnet_pad
-import fnet_sweep
+import fnet_host
+import fnet_plan
+import fnet_rows
 from fdrop_ref import factors, spec
-from fnet_ref import conv_records
+from fnet_host import conv_records
 
 SATURATING = ("i16", "n60")   # input sets that saturate the softmax: they tell nothing about a gradient
 MOMENTUM, EPS_BN = train.BN_MOMENTUM, train.BN_EPS
@@ -50,11 +50,11 @@ EPS32 = 2.0 ** -24
 
 
 def inputs(name, n, in_n):
-    """n inputs of sweep row `name` as fnet_sweep.inputs draws them, without the rows of the i16 / n60 sets."""
-    sets = fnet_sweep.ROWS[name][0].get("sets", fnet_sweep.SETS)
+    """n inputs of sweep row `name` as fnet_rows.inputs draws them, without the rows of the i16 / n60 sets."""
+    sets = fnet_rows.SWEEP[name][0].get("sets", fnet_rows.SETS)
     keep = [i for i in range(len(sets)) if sets[i] not in SATURATING]
     m = (n + len(keep) - 1) // len(keep) * len(sets)
-    x = fnet_sweep.inputs(name, m, in_n)
+    x = fnet_rows.inputs(name, m, in_n)
     rows = [i for i in range(m) if i % len(sets) in keep][:n]
     return np.ascontiguousarray(x[rows])
 
@@ -73,9 +73,9 @@ def tie_case(pool, n=17, ppad=None):
     pool = tuple(pool)
     rng = np.random.default_rng((77 if ppad is None else 177) + 10 * pool[0] + pool[1])
     if ppad is None:
-        recs = fnet_sweep._records((6, 6, 1), [("conv", 3, (2, 2), (1, 1), pool, 0), ("dense", 3, 0)])
+        recs = fnet_rows._records((6, 6, 1), [("conv", 3, (2, 2), (1, 1), pool, 0), ("dense", 3, 0)], pad_keys=False)
     else:
-        recs = fnet_pad._records((6, 6, 1), [fnet_pad._c(3, (2, 2), p=pool, relu=0, ppad=ppad), ("dense", 3, 0)])
+        recs = fnet_rows._records((6, 6, 1), [fnet_rows._c(3, (2, 2), p=pool, relu=0, ppad=ppad), ("dense", 3, 0)])
     recs[0]["w"] = rng.choice([-1.0, -0.5, 0.5, 1.0], (3, 2, 2, 1)).astype(np.float32)
     recs[0]["w"][2] = 0.0
     recs[0]["b"] = np.array([0.25, -0.5, 0.75], np.float32)
@@ -150,11 +150,11 @@ def loss_grad(model, x, labels, weights=None, n_total=None, dropout=None, bn=Non
     eps, trunc = dtype(EPS_BN if bn is None else bn.get("eps", EPS_BN)), bn is None or bn.get("trunc_in_stats", True)
     keep = []
     for L, (wt, b), F, st in zip(recs, W, Fs, state):
-        cp, pp = fnet_pad.pads(L)
+        cp, pp = fnet_host.pads(L)
         a = a.reshape((-1,) + tuple(L["inp"]))
         cols = _cols(L, _border(a, cp, 0.0))                           # [n][ch][cw][K], zeros at the taps outside
         pre = cols @ wt.reshape(wt.shape[0], -1).T + b
-        assert pre.shape[1:3] == fnet_pad.conv_map(L)
+        assert pre.shape[1:3] == fnet_host.conv_map(L)
         ph, pw = L["p"]
         Ph, Pw, oc = L["out"]
         y, stats = pre, None
@@ -191,7 +191,7 @@ def loss_grad(model, x, labels, weights=None, n_total=None, dropout=None, bn=Non
     grads, bns, details = [None] * len(recs), [None] * len(recs), [None] * len(recs)
     for i in range(len(recs) - 1, -1, -1):
         L, (wt, b), F = recs[i], W[i], Fs[i]
-        cp, pp = fnet_pad.pads(L)
+        cp, pp = fnet_host.pads(L)
         cols, pre, y, first, win, bshape, stats = keep[i]
         ph, pw = L["p"]
         Ph, Pw, oc = L["out"]
@@ -261,7 +261,7 @@ def torch_grads(model, x, labels, dtype, weights=None, dropout=None, bn=None, mo
     state = [None] * len(recs) if bn is None else bn["state"]
     params, bnp = [], []
     for L, (wt, b), fac, st in zip(recs, W, _factors(model, dropout, a.shape[0]), state):
-        cp, pp = fnet_pad.pads(L)
+        cp, pp = fnet_host.pads(L)
         tw = torch.tensor(wt, dtype=dtype).permute(0, 3, 1, 2).contiguous().requires_grad_(True)   # [out][in][kh][kw]
         tb = torch.tensor(b, dtype=dtype).requires_grad_(True)
         params.append((tw, tb))
@@ -309,16 +309,16 @@ def tensor_error(got, want):
 
 def live(L):
     """Rows of record L per utterance that are not absent: the conv positions inside the pooled windows."""
-    (ph, pw), (_, q) = L["p"], fnet_pad.pads(L)
+    (ph, pw), (_, q) = L["p"], fnet_host.pads(L)
     Ph, Pw = L["out"][:2]
-    ch, cw = fnet_pad.conv_map(L)
+    ch, cw = fnet_host.conv_map(L)
     return sum(q[0] <= y < q[0] + ch for y in range(Ph * ph)) * sum(q[1] <= x < q[1] + cw for x in range(Pw * pw))
 
 
 def terms(model, n, whole_map=False):
     """Per conv record, how many terms the sums behind one element of dW and of db have at most: n rows x the live rows (Ph ph Pw pw
     without pads); whole_map: n rows x the whole conv map, what a BatchNorm record's sums run over."""
-    return [n * (int(np.prod(fnet_pad.conv_map(L))) if whole_map else live(L)) for L in conv_records(model)]
+    return [n * (int(np.prod(fnet_host.conv_map(L))) if whole_map else live(L)) for L in conv_records(model)]
 
 
 def bounds(model, x, y, ref, n_total=None, dropout=None, bn=None):
@@ -398,7 +398,7 @@ def inference(model, x, weights, state, eps=EPS_BN):
 
 # ---- the trainer's plan and the order of its sums -----------------------------------------------------------------------------------
 def train_lds_bytes(plan, batch):
-    """ed_ftrain_lds_bytes of a restated plan (fnet_exact.plan or fnet_pad.plan) at `batch` utterances per workgroup: the larger of
+    """ed_ftrain_lds_bytes of a restated plan (fnet_plan.plan) at `batch` utterances per workgroup: the larger of
     the forward half's LDS and the backward half's dY [16-padded batch x rows][n_pad] floats + row bases [16-padded batch x rows], one
     int a row and two on a padded record, each the largest record's (ftrain_size_lds)."""
     fwd = 4 * (batch * sum(plan["buf_n"]) + plan["w_lds"]) + 4 * plan["k_lds"]
@@ -409,8 +409,8 @@ def train_lds_bytes(plan, batch):
 
 def train_batch(plan, limit=None):
     """The utterances per workgroup edison_ftrain_create trains a restated plan at: the network's own batch, lowered while the training
-    workgroup does not fit `limit` bytes of LDS (fnet_exact.LDS_BYTES); 0 for a plan it refuses, whose one utterance does not fit."""
-    limit = fnet_exact.LDS_BYTES if limit is None else limit
+    workgroup does not fit `limit` bytes of LDS (fnet_plan.LDS_BYTES); 0 for a plan it refuses, whose one utterance does not fit."""
+    limit = fnet_plan.LDS_BYTES if limit is None else limit
     batch = plan["batch"]
     while batch > 1 and train_lds_bytes(plan, batch) > limit:
         batch -= 1

@@ -8,10 +8,9 @@ import numpy as np
 from edison_amd import cube_import, train
 
 import fdrop_ref
-import fnet_pad
-import fnet_sweep
+import fnet_rows
 import ftrain_ref
-from fnet_ref import conv_records
+from fnet_host import conv_records
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 N_ROWS = 17                      # rows of a gradient check: two tiles at a batch of 16, the second of one row
@@ -28,12 +27,12 @@ FIT_STEPS, FIT_BATCH, FIT_LR = 40, 32, 0.01
 
 def fit_set():
     """Three classes on pool21_trunc_h's input shape: a fixed N(0, 1) pattern per class + N(0, 0.3), 96 rows, labels i % 3."""
-    return ftrain_ref.class_set(int(np.prod(fnet_sweep.model(FIT_ROW)["in_shape"])), FIT_CLASSES, FIT_ROWS, 2024)
+    return ftrain_ref.class_set(int(np.prod(fnet_rows.model(FIT_ROW)["in_shape"])), FIT_CLASSES, FIT_ROWS, 2024)
 
 
 def pad_fit_set():
     """fit_set on stride2_same's input shape (its dense layer has 3 outputs)."""
-    return ftrain_ref.class_set(int(np.prod(fnet_pad.ROWS[PAD_FIT_ROW][0]["in_shape"])), FIT_CLASSES, FIT_ROWS, 2025)
+    return ftrain_ref.class_set(int(np.prod(fnet_rows.PAD[PAD_FIT_ROW][0]["in_shape"])), FIT_CLASSES, FIT_ROWS, 2025)
 
 
 def kws_set(in_n=403, classes=10, rows=96):
@@ -42,8 +41,8 @@ def kws_set(in_n=403, classes=10, rows=96):
 
 
 # ---- padded networks (test_fgrad_pad_cpu, test_gpu_ftrain_pad) ------------------------------------------------------------------------
-NEG_T = "neg_no_relu_t"          # fnet_pad's neg_no_relu with a bias that does not saturate the softmax
-PAD_ROWS = [NEG_T if name == "neg_no_relu" else name for name in fnet_pad.ROWS]
+NEG_T = "neg_no_relu_t"          # fnet_rows.PAD's neg_no_relu with a bias that does not saturate the softmax
+PAD_ROWS = [NEG_T if name == "neg_no_relu" else name for name in fnet_rows.PAD]
 ALL_N = ("sym3x3", "pool41_lead", "mid_pads_batch")      # rows the GPU test also runs at n = 1, b - 1, b, b + 1 and 3 b + 2 for the trainer's batch b
 _MODELS = {}
 
@@ -54,32 +53,25 @@ def n_max(name):
 
 
 def pad_model(name):
-    """fnet_pad.model; neg_no_relu_t: neg_no_relu's layers and pads with bias -3 and positive weights in every record."""
+    """fnet_rows.model; neg_no_relu_t: neg_no_relu's layers and pads with bias -3 and positive weights in every record."""
     if name not in _MODELS:
         if name == NEG_T:
-            spec = fnet_pad.ROWS["neg_no_relu"][0]
-            rng = np.random.default_rng(2000 + fnet_pad._seed(name))
-            recs = fnet_pad._records(spec["in_shape"], spec["layers"])
-            for L in recs:
-                oc, (kh, kw), ic = L["out"][2], L["k"], L["inp"][2]
-                L["w"] = np.abs(rng.normal(0, 1, (oc, kh, kw, ic)) / np.sqrt(kh * kw * ic)).astype(np.float32)
-                L["b"] = np.full(oc, -3.0, np.float32)
-            recs.append(dict(type=cube_import.T_SOFTMAX, inp=recs[-1]["out"], out=recs[-1]["out"]))
-            _MODELS[name] = dict(in_shape=spec["in_shape"], layers=recs)
+            spec = fnet_rows.PAD["neg_no_relu"][0]
+            _MODELS[name] = fnet_rows.seeded(fnet_rows.network(spec["in_shape"], spec["layers"]), 2000 + fnet_rows._seed(name), positive=True, bias=-3.0)
         else:
-            _MODELS[name] = fnet_pad.model(name)
+            _MODELS[name] = fnet_rows.model(name)
     return _MODELS[name]
 
 
 def pad_blob(name):
-    return cube_import.build_blob(pad_model(name)) if name == NEG_T else fnet_pad.blob(name)
+    return cube_import.build_blob(pad_model(name)) if name == NEG_T else fnet_rows.blob(name)
 
 
 def pad_data(name, n=N_ROWS):
     """(x [n][in_n] float32, labels i % n_out) of row `name`: N(0, 1); neg_no_relu_t: -|N(0, 1)| - 0.1, every input negative."""
     m = pad_model(name)
     in_n = int(np.prod(m["in_shape"]))
-    x = np.random.default_rng(5000 + fnet_pad._seed(name)).normal(0, 1, (n, in_n)).astype(np.float32)
+    x = np.random.default_rng(5000 + fnet_rows._seed(name)).normal(0, 1, (n, in_n)).astype(np.float32)
     if name == NEG_T:
         x = (-np.abs(x) - np.float32(0.1)).astype(np.float32)
     return x, _labels(m, n)
@@ -87,7 +79,7 @@ def pad_data(name, n=N_ROWS):
 
 # ---- dropout (test_fdrop_cpu, test_gpu_ftrain_dropout) --------------------------------------------------------------------------------
 SHIPPED = "cube_kws"
-# name -> (source: "sweep" (fnet_sweep), "pad" (PAD_ROWS) or "shipped", the row there, dropout, seed of the masks)
+# name -> (source: "sweep" (fnet_rows), "pad" (PAD_ROWS) or "shipped", the row there, dropout, seed of the masks)
 DROP_ROWS = {
     "p1_inc3": ("sweep", "inc3_oc64_oc65_s21", None, 11),                       # P = 1 everywhere: the two positions coincide
     "p2_pool12_no_relu_before": ("sweep", "pool12_trunc_w", [(0.25, 1), 0], 12),   # P = 2 without ReLU: the dropped-winner bit decides
@@ -118,9 +110,9 @@ def drop_case(name):
             with open(os.path.join(GOLDEN, "cube_kws.ednf"), "rb") as f:
                 blob = f.read()
         else:
-            blob = fnet_sweep.blob(row)
+            blob = fnet_rows.blob(row)
         model = cube_import.read_blob(blob)
-        # N(0, 1), as pad_data draws: fnet_sweep's own input sets and the shipped network's features saturate the softmax
+        # N(0, 1), as pad_data draws: fnet_rows' own input sets and the shipped network's features saturate the softmax
         x = np.random.default_rng(6000 + seed).normal(0, 1, (N_ROWS, int(np.prod(model["in_shape"])))).astype(np.float32)
         y = _labels(model, N_ROWS)
     if dropout is None:                                                        # every record but the last, rates 0.25 and 0.5 in turn
@@ -139,7 +131,7 @@ def drop_reference(name, call=0):
 
 
 # ---- BatchNorm (test_fbn_cpu, test_gpu_ftrain_bn) -------------------------------------------------------------------------------------
-# name -> dict(in_shape, layers (fnet_sweep._records' form), bn, dropout, n, seed: of the inputs, chosen so that test_fbn_cpu's bound
+# name -> dict(in_shape, layers (fnet_rows._records' form), bn, dropout, n, seed: of the inputs, chosen so that test_fbn_cpu's bound
 # precondition holds, bias0: added to record 0's bias, neg: gamma and beta set through set_bn_state)
 BN_ROWS = {
     "bn_p1": dict(in_shape=(6, 5, 2), layers=[("conv", 5, (2, 2), (1, 1), (1, 1), 1), ("dense", 4, 0)], bn=[1, 0], seed=1),
@@ -165,18 +157,11 @@ def bn_fresh_model(name):
         recs = [dict(L) for L in shipped["layers"]]
     else:
         in_shape = row["in_shape"]
-        recs = fnet_sweep._records(in_shape, row["layers"])
-        recs.append(dict(type=cube_import.T_SOFTMAX, inp=recs[-1]["out"], out=recs[-1]["out"]))
-    rng = np.random.default_rng(4000 + sum(map(ord, row.get("weights_of", name))))
-    for L in recs:
-        if L["type"] != cube_import.T_CONV:
-            continue
-        oc, (kh, kw), ic = L["out"][2], L["k"], L["inp"][2]
-        L["w"] = (rng.normal(0, 1, (oc, kh, kw, ic)) / np.sqrt(kh * kw * ic)).astype(np.float32)
-        L["b"] = rng.normal(0, 0.1, oc).astype(np.float32)
-    first = [L for L in recs if L["type"] == cube_import.T_CONV][0]
+        recs = fnet_rows.network(in_shape, row["layers"], pad_keys=False)["layers"]
+    m = fnet_rows.seeded(dict(in_shape=in_shape, layers=recs), 4000 + sum(map(ord, row.get("weights_of", name))))
+    first = conv_records(m)[0]
     first["b"] = (first["b"] + np.float32(row.get("bias0", 0.0))).astype(np.float32)
-    return dict(in_shape=in_shape, layers=recs)
+    return m
 
 
 def bn_case(name):

@@ -7,7 +7,7 @@ cube_golden.npz, for both reference wavs (edge-padded to 2 s, kws_on_mcu.py:330-
   audio_<s>      int16 [32000]
   net_in_<s>     float32 [403]: the host flow's net input -- the reference's own mfcc_mcu (variant B, first 13 coefficients) cast to
                  float32, times net_input_scale, clipped to [-2^15, 2^15 - 1] (kws_on_mcu.py:343-347, audio/config.py:46-48), never rounded
-  logits_<s>, probs_<s>   float64 [10]: tests/fnet_ref.py (the float64 restatement) on net_in_<s>
+  logits_<s>, probs_<s>   float64 [10]: tests/fnet_host.py (the float64 restatement) on net_in_<s>
   q15_<s>        int16 [31][13]: variant C (the firmware's audioCalcMFCCs, this repo's oracle, bit-exact to the firmware) on the first
                  31 744 samples; the firmware flow casts them to float with no scale and no clip (app.c:675-683)
   q15_logits_<s>, q15_probs_<s>  float64 [10]: the restatement on (float)q15_<s>
@@ -29,7 +29,7 @@ sys.path.insert(0, os.path.join(REF, "audio"))
 
 import config as refcfg                      # noqa: E402  (reference audio/config.py)
 import edison.mfcc.mfcc_utils as mfu         # noqa: E402  (reference implementation of variant B)
-import fnet_ref                              # noqa: E402
+import fnet_host  # noqa: E402
 from edison_amd import cube_import           # noqa: E402
 from oracle import oracle                    # noqa: E402
 
@@ -47,7 +47,7 @@ def main():
     blob = cube_import.import_files(os.path.join(CUBE, "kws.c"), os.path.join(CUBE, "kws_data.c"), os.path.join(CUBE, "keywords.txt"))
     with open(os.path.join(HERE, "cube_kws.ednf"), "wb") as f:
         f.write(blob)
-    model = fnet_ref.load(blob)
+    model = fnet_host.load(blob)
     oracle.build()
     n = refcfg.nSamples
     sources = {}
@@ -63,11 +63,11 @@ def main():
         out["audio_" + name] = data
         x = host_net_input(data)
         out["net_in_" + name] = x
-        r = fnet_ref.run(model, x[None])
+        r = fnet_host.run64(model, x[None])
         out["logits_" + name], out["probs_" + name] = r["logits"][0], r["probs"][0]
         q = oracle.mfcc_q15(data[:31 * 1024])[:, :13].astype(np.int16)
         out["q15_" + name] = q
-        rq = fnet_ref.run(model, q.astype(np.float32).reshape(1, -1))
+        rq = fnet_host.run64(model, q.astype(np.float32).reshape(1, -1))
         out["q15_logits_" + name], out["q15_probs_" + name] = rq["logits"][0], rq["probs"][0]
         print("%-8s host %-8s p=%.4f | firmware %-8s p=%.4f" % (name, model["keywords"][r["argmax"][0]], r["probs"][0].max(),
                                                              model["keywords"][rq["argmax"][0]], rq["probs"][0].max()))

@@ -1,5 +1,5 @@
 """X-CUBE-AI float networks without a GPU: the importer (edison_amd/cube_import.py) on the reference's kws.c / kws_data.c and on
-networks written in the same format, the float64 restatement (tests/fnet_ref.py) on the fixture, and the kernel's compile."""
+networks written in the same format, the float64 restatement (tests/fnet_host.py) on the fixture, and the kernel's compile."""
 import os
 import re
 import subprocess
@@ -11,7 +11,7 @@ from conftest import GOLDEN, ROOT
 from edison_amd import cube_import
 
 import cube_synth
-import fnet_ref
+import fnet_host
 
 CUBE = "/root/reference/firmware/src/ai/cube/kws"
 FIXTURE = os.path.join(GOLDEN, "cube_kws.ednf")
@@ -19,7 +19,7 @@ FIXTURE = os.path.join(GOLDEN, "cube_kws.ednf")
 
 @pytest.fixture(scope="module")
 def model():
-    return fnet_ref.load(FIXTURE)
+    return fnet_host.load(FIXTURE)
 
 
 @pytest.fixture(scope="module")
@@ -40,7 +40,7 @@ def test_fixture_layers(model):
     """kws.c's chain: conv2d_nl_pool x2, conv2d x2 (all ReLU), dense, softmax; HWC 31 x 13 x 1 in, 10 out."""
     assert model["in_shape"] == (31, 13, 1) and model["n_out"] == 10
     assert model["keywords"][0] == "edison" and len(model["keywords"]) == 10
-    convs = fnet_ref.conv_records(model)
+    convs = fnet_host.conv_records(model)
     assert [L["out"] for L in convs] == [(13, 9, 16), (5, 7, 32), (3, 5, 64), (1, 3, 32), (1, 1, 10)]
     assert [L["p"] for L in convs] == [(2, 1), (2, 1), (1, 1), (1, 1), (1, 1)]
     assert [L["relu"] for L in convs] == [1, 1, 1, 1, 0]
@@ -52,10 +52,10 @@ def test_fixture_layers(model):
 def test_restatement_pins_layout(model, golden):
     """The edison wav's host-flow features: class 0 ("edison") with p > 0.9; the kh / kw-swapped reading of the same weights does not."""
     x = golden["net_in_edison"][None]
-    r = fnet_ref.run(model, x)
+    r = fnet_host.run64(model, x)
     assert r["argmax"][0] == 0 and r["probs"][0, 0] > 0.9
     np.testing.assert_allclose(r["probs"][0], golden["probs_edison"], rtol=0, atol=1e-12)
-    s = fnet_ref.run(fnet_ref.swapped(model), x)
+    s = fnet_host.run64(fnet_host.swapped(model), x)
     assert not (s["argmax"][0] == 0 and s["probs"][0, 0] > 0.9)
 
 
@@ -69,14 +69,14 @@ def test_synth_network_round_trip():
     specs = [("conv", 6, (3, 2), (1, 1), (2, 2), 1), ("conv", 20, (2, 3), (2, 1), (1, 1), 0), ("dense", 12), ("relu",), ("dense", 5), ("softmax",)]
     net_c, data_c = _synth(specs)
     m = cube_import.read_blob(cube_import.build_blob(cube_import.convert(cube_import.parse_net_c(net_c), cube_import.parse_data_c(data_c))))
-    convs = fnet_ref.conv_records(m)
+    convs = fnet_host.conv_records(m)
     assert [L["out"] for L in convs] == [(9, 4, 6), (4, 2, 20), (1, 1, 12), (1, 1, 5)]
     assert [L["relu"] for L in convs] == [1, 0, 1, 0] and [L["k"] for L in convs[:2]] == [(3, 2), (2, 3)]
     # the weights come back in [out][kh][kw][in], the order the generator drew them in
     rng = np.random.default_rng(5)
     w0 = rng.normal(0, 1.0 / np.sqrt(6), (6, 3, 2, 1)).astype(np.float32)
     assert np.array_equal(convs[0]["w"], w0)
-    r = fnet_ref.run(m, np.random.default_rng(1).normal(0, 10, (3, 180)))
+    r = fnet_host.run64(m, np.random.default_rng(1).normal(0, 10, (3, 180)))
     np.testing.assert_allclose(r["probs"].sum(axis=1), 1.0, atol=1e-12)
 
 
@@ -130,7 +130,7 @@ def test_cli_refuses_with_message(tmp_path, capsys):
 
 def test_kernel_compiles_without_scratch(tmp_path):
     """fnet_kernels.hip for gfx950: no scratch memory, the f32-input MFMA in the code object, and f32 subnormals kept by both kernels
-    (float_denorm_mode_32 3: no build flag flushes them; tests/fnet_exact.py models the kernel without flushing)."""
+    (float_denorm_mode_32 3: no build flag flushes them; tests/fnet_host.py models the kernel without flushing)."""
     hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
     src = os.path.join(ROOT, "edison_amd", "csrc", "fnet_kernels.hip")
     r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-fno-slp-vectorize", "-O3", "--cuda-device-only", "-S", src, "-o",

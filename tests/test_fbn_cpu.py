@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
-import fnet_ref
+import fnet_host
 import ftrain_ref
 import ftrain_rows
 from edison_amd import build as B
@@ -55,7 +55,7 @@ def test_the_restatement_is_torchs_float64_autograd(name):
 def test_the_restatement_is_the_central_difference_of_its_loss(name):
     c = ftrain_rows.bn_case(name)
     ref, _ = ftrain_rows.bn_reference(name, 0)
-    base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_ref.conv_records(c["model"])]
+    base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_host.conv_records(c["model"])]
     state = [None if st is None else {k: np.asarray(v, np.float64).copy() for k, v in st.items()} for st in c["state0"]]
 
     def mean_loss(weights, st):
@@ -109,7 +109,7 @@ def test_leaving_the_truncated_positions_out_would_be_seen(name):
 def test_the_folded_network_is_batchnorm_in_inference_mode(name):
     c = ftrain_rows.bn_case(name)
     rng = np.random.default_rng(31)
-    weights = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_ref.conv_records(c["model"])]
+    weights = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_host.conv_records(c["model"])]
     state = [None if st is None else dict(gamma=rng.normal(0, 1, len(st["gamma"])), beta=rng.normal(0, 1, len(st["gamma"])),
                                           mean=rng.normal(0, 1, len(st["gamma"])), var=rng.uniform(0.2, 3, len(st["gamma"]))) for st in c["state0"]]
     want = ftrain_ref.inference(c["model"], c["x"], weights, state)
@@ -127,7 +127,7 @@ def test_the_bounds_precondition_on_the_inputs_the_gpu_test_draws(name):
         state = ftrain_rows.bn_state(name, call)
         r32 = ftrain_ref.loss_grad(c["model"], c["x"], c["y"], dropout=(c["sp"], c["seed"], call), bn=dict(state=state), dtype=np.float32, detail=True)
         assert r32["logits"].dtype == np.float32
-        for L, d32, d64 in zip(fnet_ref.conv_records(c["model"]), r32["detail"], ref["detail"]):
+        for L, d32, d64 in zip(fnet_host.conv_records(c["model"]), r32["detail"], ref["detail"]):
             assert np.array_equal(d32["first"], d64["first"]), (name, call)
             if L["relu"]:
                 assert np.array_equal(d32["y"] > 0, d64["y"] > 0), (name, call)

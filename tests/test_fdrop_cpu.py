@@ -12,7 +12,7 @@ import pytest
 from edison_amd import train
 
 import fdrop_ref as fd
-import fnet_ref
+import fnet_host
 import ftrain_ref
 import ftrain_rows
 
@@ -154,7 +154,7 @@ def test_restatement_agrees_with_central_differences(name):
     c = ftrain_rows.drop_case(name)
     m, x, y = c["model"], c["x"][:4], c["y"][:4]
     ref = ftrain_ref.loss_grad(m, x, y, dropout=(c["sp"], c["seed"], 0))
-    base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_ref.conv_records(m)]
+    base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_host.conv_records(m)]
     h = 1e-6
     for i, t in enumerate(base):
         for k in ("w", "b"):
@@ -180,8 +180,7 @@ def test_at_rate_zero_it_is_the_dropout_free_restatement_exactly(name):
     for s, t in zip(a["grads"], b["grads"]):
         assert np.array_equal(s["w"], t["w"]) and np.array_equal(s["b"], t["b"])
     f32 = fd.forward32(c["model"], c["x"][:5], none, 3, 9)
-    import fnet_pad
-    assert all(np.array_equal(p, q) for p, q in zip(f32, fnet_pad.run(c["model"], c["x"][:5])))
+    assert all(np.array_equal(p, q) for p, q in zip(f32, fnet_host.run(c["model"], c["x"][:5])))
 
 
 @pytest.mark.parametrize("name", ftrain_rows.DROP_ROWS)
@@ -190,19 +189,18 @@ def test_float32_and_float64_make_the_same_choices_on_the_gpu_tests_inputs(name)
     tests/test_gpu_ftrain_dropout.py uses: forward32 and float64 choose the same element of every window, the same sign under every
     ReLU and the same dropped-winner bit, and the smallest softmax probability is above 1e-4. If a row fails, give it another mask
     seed in ftrain_rows.DROP_ROWS; never drop a row."""
-    import fnet_pad
     c = ftrain_rows.drop_case(name)
     m, x = c["model"], c["x"]
     for call in (0, 1):
         ref = ftrain_rows.drop_reference(name, call)
         _, det = fd.forward32(m, x, c["sp"], c["seed"], call, detail=True)
-        for L, d, (first32, pos32, dropped32) in zip(fnet_ref.conv_records(m), ref["detail"], det):
+        for L, d, (first32, pos32, dropped32) in zip(fnet_host.conv_records(m), ref["detail"], det):
             ph, pw = L["p"]
             Ph, Pw, oc = L["out"]
             assert np.array_equal(d["first"].reshape(len(x), -1, oc), first32), name
             assert np.array_equal(d["dropped"].reshape(len(x), -1, oc), dropped32), name
             if L["relu"]:
-                bordered = ftrain_ref._border(d["pre"], fnet_pad.pads(L)[1], np.nan)[:, :Ph * ph, :Pw * pw]
+                bordered = ftrain_ref._border(d["pre"], fnet_host.pads(L)[1], np.nan)[:, :Ph * ph, :Pw * pw]
                 pre64 = bordered.reshape(-1, Ph, ph, Pw, pw, oc).transpose(0, 1, 3, 2, 4, 5).reshape(len(x), -1, oc)
                 live = ~np.isnan(pre64[0, :, 0])
                 assert np.array_equal((pre64 > 0)[:, live], pos32[:, live]), name
@@ -212,12 +210,12 @@ def test_float32_and_float64_make_the_same_choices_on_the_gpu_tests_inputs(name)
 
 
 def test_the_rows_cover_what_the_gpu_test_says_they_cover():
-    P = lambda name: [L["p"][0] * L["p"][1] for L in fnet_ref.conv_records(ftrain_rows.drop_case(name)["model"])]
+    P = lambda name: [L["p"][0] * L["p"][1] for L in fnet_host.conv_records(ftrain_rows.drop_case(name)["model"])]
     assert set(P("p1_inc3")) == {1} and 2 in P("p2_pool12_no_relu_before") and 4 in P("p4_pool22_before") and 4 in P("p4_pool22_after")
     c = ftrain_rows.drop_case("p2_pool12_no_relu_before")
-    assert not fnet_ref.conv_records(c["model"])[0]["relu"] and c["sp"][0] == (0.25, True)
+    assert not fnet_host.conv_records(c["model"])[0]["relu"] and c["sp"][0] == (0.25, True)
     c = ftrain_rows.drop_case("neg_no_relu_before")
-    assert not fnet_ref.conv_records(c["model"])[0]["relu"] and c["sp"][0][1]
+    assert not fnet_host.conv_records(c["model"])[0]["relu"] and c["sp"][0][1]
     d = ftrain_rows.drop_reference("neg_no_relu_before")["detail"][0]
     assert d["dropped"].any() and not d["dropped"].all()                    # with every value negative a dropped +0 wins its window
     assert ftrain_rows.drop_case("pool21_before")["sp"][0][1] and not ftrain_rows.drop_case("pool21_after")["sp"][0][1]

@@ -1,5 +1,5 @@
 """The float64 restatement of training (tests/ftrain_ref.py) held to torch's float64 autograd and to central differences, the packed
-layout of edison_amd/train.py held to the plan's (fnet_exact.plan), the Adam restatement held to torch.optim.Adam, the host side
+layout of edison_amd/train.py held to the plan's (fnet_plan.plan), the Adam restatement held to torch.optim.Adam, the host side
 of fit: the shuffle and the two callbacks; and what tests/test_gpu_ftrain_tiles.py rests on: the order of a multi-tile call's sums
 (ftrain_ref.fold_tiles), what that order is sensitive to, what the float64 bound sees at these sizes, and the trainer's batch
 (ftrain_ref.train_batch). No GPU."""
@@ -10,9 +10,9 @@ import pytest
 
 from edison_amd import cube_import, train
 
-import fnet_exact
-import fnet_ref
-import fnet_sweep
+import fnet_host
+import fnet_plan
+import fnet_rows
 import ftrain_ref
 import ftrain_rows
 
@@ -23,14 +23,14 @@ ROWS = ["ladder_k5", "pool21_trunc_h", "pool12_trunc_w", "pool22_trunc_hw", "poo
 
 def _case(name, n=5):
     if name == "cube_kws":
-        model = fnet_ref.load(os.path.join(HERE, "golden", "cube_kws.ednf"))
+        model = fnet_host.load(os.path.join(HERE, "golden", "cube_kws.ednf"))
         g = np.load(os.path.join(HERE, "golden", "cube_golden.npz"))
         rows = np.stack([g[k] for k in sorted(g.files) if k.startswith("net_in_")]).astype(np.float32)
         x = rows[np.arange(n) % rows.shape[0]]
     else:
-        model = fnet_sweep.model(name)
+        model = fnet_rows.model(name)
         x = ftrain_ref.inputs(name, n, int(np.prod(model["in_shape"])))
-    n_out = int(np.prod(fnet_ref.conv_records(model)[-1]["out"]))
+    n_out = int(np.prod(fnet_host.conv_records(model)[-1]["out"]))
     return model, x, (np.arange(n) % n_out).astype(np.int32)
 
 
@@ -58,7 +58,7 @@ def test_inputs_leave_the_saturating_sets_out():
 def test_agrees_with_central_differences(name):
     model, x, y = _case(name, n=4)
     ref = ftrain_ref.loss_grad(model, x, y)
-    base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_ref.conv_records(model)]
+    base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_host.conv_records(model)]
     h = 1e-6
     for i, t in enumerate(base):
         for k in ("w", "b"):
@@ -94,7 +94,7 @@ def test_first_maximum_and_relu_at_zero():
 def _routed_dw(model, x, y, pick):
     """Record 0's dW of a tie_case network, restated with loops: each pool window's gradient to the element `pick` chooses among
     those equal to the window's maximum. Returns (dW, how often the first of several maxima was element e)."""
-    conv, dense = fnet_ref.conv_records(model)
+    conv, dense = fnet_host.conv_records(model)
     w, b = conv["w"].astype(np.float64), conv["b"].astype(np.float64)
     img = x.astype(np.float64).reshape(-1, 6, 6)
     n = len(img)
@@ -129,7 +129,7 @@ def test_tied_windows_send_the_gradient_to_their_first_element(pool):
     instead would move dW far beyond any rounding bound."""
     import torch
     model, x, y = ftrain_ref.tie_case(pool)
-    assert fnet_ref.conv_records(model)[0]["relu"] == 0
+    assert fnet_host.conv_records(model)[0]["relu"] == 0
     ref = ftrain_ref.loss_grad(model, x, y)
     first, tied_first = _routed_dw(model, x, y, lambda at: at[0])
     assert (tied_first[:-1] > 0).all(), tied_first                          # a window's last element is never the first of several
@@ -143,8 +143,8 @@ def test_tied_windows_send_the_gradient_to_their_first_element(pool):
 
 @pytest.mark.parametrize("name", ["pool22_trunc_hw", "inc3_oc64_oc65_s21", "n_out_210", "ladder_k5"])
 def test_pack_round_trip_against_the_plan(name):
-    blob = fnet_sweep.blob(name)
-    model, plan = cube_import.read_blob(blob), fnet_exact.plan(blob)
+    blob = fnet_rows.blob(name)
+    model, plan = cube_import.read_blob(blob), fnet_plan.plan(blob)
     lay, n = train.layout(model)
     at = 0
     for r, L in zip(lay, plan["layers"]):
@@ -153,7 +153,7 @@ def test_pack_round_trip_against_the_plan(name):
     assert n == at
     payload = np.frombuffer(blob, "<f4", n, len(blob) - 4 * n)            # the blob's weights are the packed array
     tensors = train.unpack(payload, lay)
-    for t, L in zip(tensors, fnet_ref.conv_records(model)):
+    for t, L in zip(tensors, fnet_host.conv_records(model)):
         assert np.array_equal(t["w"], L["w"]) and np.array_equal(t["b"], L["b"])
     assert np.array_equal(train.pack(tensors, lay), payload)
     marked = np.where(payload == 0, np.float32(1e6), payload)             # the padding is kept from `base`, the real entries replaced
@@ -246,9 +246,9 @@ def test_a_lost_tile_moves_every_tensor_by_more_than_the_bound():
 
 
 def _plans():
-    out = {name: fnet_exact.plan(fnet_sweep.blob(name)) for name in fnet_sweep.ROWS}
+    out = {name: fnet_plan.plan(fnet_rows.blob(name)) for name in fnet_rows.SWEEP}
     with open(os.path.join(HERE, "golden", "cube_kws.ednf"), "rb") as f:
-        out["cube_kws"] = fnet_exact.plan(f.read())
+        out["cube_kws"] = fnet_plan.plan(f.read())
     return out
 
 
@@ -259,13 +259,13 @@ def test_train_batch_is_the_networks_except_where_dy_does_not_fit():
     plans = _plans()
     for name, p in plans.items():
         tb = ftrain_ref.train_batch(p)
-        assert 1 <= tb <= p["batch"] and ftrain_ref.train_lds_bytes(p, tb) <= fnet_exact.LDS_BYTES, name
+        assert 1 <= tb <= p["batch"] and ftrain_ref.train_lds_bytes(p, tb) <= fnet_plan.LDS_BYTES, name
         assert tb == (2 if name == "batch5" else p["batch"]), (name, tb, p["batch"])
     assert plans["batch5"]["batch"] == 5 and ftrain_ref.train_batch(plans["cube_kws"]) == 7
     p = plans["batch5"]
     assert p["layers"][0]["rows"] == 1064 and p["layers"][0]["n_pad"] == 16
     assert ftrain_ref.train_lds_bytes(p, 2) == 4 * 2128 * 16 + 4 * 2128 == 144704
-    assert ftrain_ref.train_lds_bytes(p, 3) > fnet_exact.LDS_BYTES
+    assert ftrain_ref.train_lds_bytes(p, 3) > fnet_plan.LDS_BYTES
     # where the forward half is the larger one the bytes are the forward plan's: the shipped network's 159 808
     assert ftrain_ref.train_lds_bytes(plans["cube_kws"], 7) == plans["cube_kws"]["lds_bytes"] == 159808
     # a plan whose one utterance does not fit is refused (0), and a limit between two batches lowers by one
@@ -273,7 +273,7 @@ def test_train_batch_is_the_networks_except_where_dy_does_not_fit():
     assert ftrain_ref.train_batch(p, limit=ftrain_ref.train_lds_bytes(p, 1)) == 1
     # the new sweep row: forward batch 10, more packed floats than one pass of the step kernel covers on 256 CUs
     wide = plans["dense16_wide"]
-    assert (wide["batch"], wide["n_layers"], fnet_sweep.w_floats(wide)) == (10, 16, 558928) and 558928 > fnet_sweep.STEP_PASS * 256
+    assert (wide["batch"], wide["n_layers"], fnet_rows.w_floats(wide)) == (10, 16, 558928) and 558928 > fnet_rows.STEP_PASS * 256
 
 
 def test_adam_restatement_against_torch():
@@ -368,7 +368,7 @@ def test_fit_replay_in_float64_meets_the_gpu_tests_thresholds():
     """The condition tests/test_gpu_ftrain.py puts on the GPU's fit, met with room by the float64 replay: 40 Adam steps at batch 32,
     lr 0.01, seed 0 on the synthetic set halve the train loss and reach 0.9 accuracy."""
     x, y = ftrain_rows.fit_set()
-    host = ftrain_ref.HostTrainer(fnet_sweep.model(ftrain_rows.FIT_ROW))
+    host = ftrain_ref.HostTrainer(fnet_rows.model(ftrain_rows.FIT_ROW))
     hist = train.fit(host, x, y, epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=ftrain_rows.FIT_STEPS)
     assert hist["steps"] == 40
     r = host.grad(x, y)

@@ -12,10 +12,9 @@ import pytest
 
 from edison_amd import cube_import, train
 
-import fnet_exact
-import fnet_pad
-import fnet_ref
-import fnet_sweep
+import fnet_host
+import fnet_plan
+import fnet_rows
 import ftrain_ref
 import ftrain_rows
 
@@ -33,8 +32,8 @@ def test_agrees_with_torch_float64_autograd(name):
         for k in ("w", "b"):
             scale = max(np.abs(b[k]).max(), 1e-300)
             assert np.abs(a[k] - b[k]).max() <= 1e-10 * scale, (name, i, k, np.abs(a[k] - b[k]).max() / scale)
-    # and the forward half is fnet_pad's own float64 restatement
-    for got, want in zip([ref["logits"]], fnet_pad.run64(m, x)[-1:]):
+    # and the forward half is fnet_host's float64 restatement
+    for got, want in zip([ref["logits"]], fnet_host.run64(m, x)["acts"][-1:]):
         assert np.allclose(got, want, rtol=1e-12, atol=1e-12)
 
 
@@ -43,7 +42,7 @@ def test_agrees_with_central_differences(name):
     m = ftrain_rows.pad_model(name)
     x, y = ftrain_rows.pad_data(name, 4)
     ref = ftrain_ref.loss_grad(m, x, y)
-    base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_ref.conv_records(m)]
+    base = [dict(w=np.asarray(L["w"], np.float64), b=np.asarray(L["b"], np.float64)) for L in fnet_host.conv_records(m)]
     h = 1e-6
     for i, t in enumerate(base):
         for k in ("w", "b"):
@@ -63,23 +62,23 @@ def test_agrees_with_central_differences(name):
 @pytest.mark.parametrize("name", ["pool22_trunc_hw", "inc3_oc64_oc65_s21"])
 def test_without_pads_it_is_the_unpadded_restatement(name):
     """One restatement serves padded and unpadded networks: a record without cpad / ppad borders nothing. The same bits with the keys
-    absent and with explicit zero pads, the forward half fnet_pad's own float64 one, the live rows the truncated map Ph ph x Pw pw,
+    absent and with explicit zero pads, the forward half fnet_host's float64 one, the live rows the truncated map Ph ph x Pw pw,
     and a plan without a padded record one int a row."""
-    m = fnet_sweep.model(name)
-    recs = fnet_ref.conv_records(m)
+    m = fnet_rows.model(name)
+    recs = fnet_host.conv_records(m)
     assert not any("cpad" in L or "ppad" in L for L in recs)
-    zeros = dict(m, layers=[dict(L, cpad=fnet_pad.Z4, ppad=fnet_pad.Z4) if L in recs else L for L in m["layers"]])
+    zeros = dict(m, layers=[dict(L, cpad=fnet_host.Z4, ppad=fnet_host.Z4) if L in recs else L for L in m["layers"]])
     x = ftrain_ref.inputs(name, 5, int(np.prod(m["in_shape"])))
     y = (np.arange(5) % int(np.prod(recs[-1]["out"]))).astype(np.int32)
     a, b = ftrain_ref.loss_grad(zeros, x, y), ftrain_ref.loss_grad(m, x, y)
     assert np.array_equal(a["loss"], b["loss"]) and np.array_equal(a["logits"], b["logits"])
     for s, t in zip(a["grads"], b["grads"]):
         assert np.array_equal(s["w"], t["w"]) and np.array_equal(s["b"], t["b"])
-    assert np.allclose(b["logits"], fnet_pad.run64(m, x)[-1], rtol=1e-12, atol=1e-12)
+    assert np.allclose(b["logits"], fnet_host.run64(m, x)["logits"], rtol=1e-12, atol=1e-12)
     assert ftrain_ref.terms(zeros, 5) == ftrain_ref.terms(m, 5) == [5 * L["out"][0] * L["p"][0] * L["out"][1] * L["p"][1] for L in recs]
-    p = fnet_exact.plan(fnet_sweep.blob(name))
-    assert not any("pad" in L for L in p["layers"])
-    q = dict(p, layers=[dict(L, pad=False) for L in p["layers"]])
+    q = fnet_plan.plan(fnet_rows.blob(name))
+    assert not any(L["pad"] for L in q["layers"])
+    p = dict(q, layers=[{k: v for k, v in L.items() if k != "pad"} for L in q["layers"]])       # a plan that never heard of pads
     assert ftrain_ref.train_batch(q) == ftrain_ref.train_batch(p) and ftrain_ref.train_lds_bytes(q, p["batch"]) == ftrain_ref.train_lds_bytes(p, p["batch"])
     mp = [(p["batch"] * L["rows"] + 15) // 16 * 16 for L in p["layers"]]
     backward = dict(p, buf_n=[0] * len(p["buf_n"]), w_lds=0, k_lds=0)
@@ -93,8 +92,8 @@ def test_tied_windows_send_the_gradient_to_their_first_present_element(pool):
     only; the last maximum instead moves dW far beyond any rounding bound; an absent element never gets any."""
     import torch
     m, x, y = ftrain_ref.tie_case(pool, ppad=ftrain_ref.TIE_PADS[pool])
-    conv = fnet_ref.conv_records(m)[0]
-    assert conv["relu"] == 0 and fnet_pad.conv_map(conv) == (5, 5) and ftrain_ref.live(conv) == 25
+    conv = fnet_host.conv_records(m)[0]
+    assert conv["relu"] == 0 and fnet_host.conv_map(conv) == (5, 5) and ftrain_ref.live(conv) == 25
     ref = ftrain_ref.loss_grad(m, x, y, detail=True)
     d = ref["detail"][0]
     axis = 0 if pool[0] == 4 else 1
@@ -114,18 +113,18 @@ def test_tied_windows_send_the_gradient_to_their_first_present_element(pool):
     for a, b in zip(ref["grads"], tor["grads"]):
         assert ftrain_ref.tensor_error(a["w"], b["w"]) <= 1e-10 and ftrain_ref.tensor_error(a["b"], b["b"]) <= 1e-10
     # the blob of such a network is version 2 and the plan counts the absent rows
-    p = fnet_pad.plan(cube_import.build_blob(m))
+    p = fnet_plan.plan(cube_import.build_blob(m))
     assert p["layers"][0]["pad"] and p["layers"][0]["rows"] == 40 and p["layers"][0]["live"] == 25
 
 
 def _float32_choices(m, x):
     """Per record (first [n][Ph][Pw][oc], positive [n][rows][oc], live [rows]) of the bit-exact float32 host model of the kernel
-    (fnet_pad.pre_activation), each record fed the float32 output of the one before, rows in the kernel's order r = q P + e."""
+    (fnet_host.pre_activation), each record fed the float32 output of the one before, rows in the kernel's order r = q P + e."""
     out, a = [], np.asarray(x, np.float32)
-    for L in fnet_ref.conv_records(m):
+    for L in fnet_host.conv_records(m):
         Ph, Pw, oc = L["out"]
         P = L["p"][0] * L["p"][1]
-        v, live = fnet_pad.pre_activation(L, a)
+        v, live = fnet_host.pre_activation(L, a)
         act = np.maximum(v, np.float32(0)) if L["relu"] else v
         act = np.where(live[:, None], act, np.float32(-np.inf)).reshape(-1, Ph, Pw, P, oc)
         out.append((act.argmax(axis=3), (v > 0).reshape(len(a), -1, oc), live[:Ph * Pw * P]))
@@ -142,16 +141,16 @@ def test_float32_and_float64_make_the_same_choices_on_the_gpu_tests_inputs(name)
     m = ftrain_rows.pad_model(name)
     x, y = ftrain_rows.pad_data(name, ftrain_rows.n_max(name))
     ref = ftrain_ref.loss_grad(m, x, y, detail=True)
-    for L, d, (first32, pos32, live) in zip(fnet_ref.conv_records(m), ref["detail"], _float32_choices(m, x)):
+    for L, d, (first32, pos32, live) in zip(fnet_host.conv_records(m), ref["detail"], _float32_choices(m, x)):
         ph, pw = L["p"]
         Ph, Pw, oc = L["out"]
         assert np.array_equal(d["first"], first32), name
-        bordered = ftrain_ref._border(d["pre"], fnet_pad.pads(L)[1], np.nan)[:, :Ph * ph, :Pw * pw]
+        bordered = ftrain_ref._border(d["pre"], fnet_host.pads(L)[1], np.nan)[:, :Ph * ph, :Pw * pw]
         pre64 = bordered.reshape(-1, Ph, ph, Pw, pw, oc).transpose(0, 1, 3, 2, 4, 5).reshape(len(x), -1, oc)
         assert np.array_equal(np.isnan(pre64[0, :, 0]), ~live)
         if L["relu"]:
             assert np.array_equal((pre64 > 0)[:, live], pos32[:, live]), name
-        if name == ftrain_rows.NEG_T and L is fnet_ref.conv_records(m)[0]:
+        if name == ftrain_rows.NEG_T and L is fnet_host.conv_records(m)[0]:
             assert (pre64[:, live] < 0).all()                               # an absent element that became 0 would win its window
     print("%s: smallest softmax probability %.3g" % (name, ref["probs"].min()))
     assert ref["probs"].min() > 1e-4, (name, ref["probs"].min())
@@ -160,12 +159,12 @@ def test_float32_and_float64_make_the_same_choices_on_the_gpu_tests_inputs(name)
 def test_neg_no_relu_t_is_negative_everywhere():
     m = ftrain_rows.pad_model(ftrain_rows.NEG_T)
     x, y = ftrain_rows.pad_data(ftrain_rows.NEG_T)
-    assert (x < 0).all() and not fnet_ref.conv_records(m)[0]["relu"]
+    assert (x < 0).all() and not fnet_host.conv_records(m)[0]["relu"]
     ref = ftrain_ref.loss_grad(m, x, y, detail=True)
     assert all((d["pre"] < 0).all() for d in ref["detail"])                 # every present pre-activation, the logits included
     assert ref["probs"].min() > 1e-4
-    zero = fnet_pad.layer(fnet_ref.conv_records(m)[0], x, absent=0.0)             # what an absent 0 would do: win the windows it is in
-    assert (zero == 0).any() and (fnet_pad.layer(fnet_ref.conv_records(m)[0], x) < 0).all()
+    zero = fnet_host.layer(fnet_host.conv_records(m)[0], x, absent=0.0)             # what an absent 0 would do: win the windows it is in
+    assert (zero == 0).any() and (fnet_host.layer(fnet_host.conv_records(m)[0], x) < 0).all()
 
 
 LOWERED = {"mid_pads_batch": 5, "simple_conv": 6}      # row -> the batch it trains at, where that is below its forward batch (7, 16)
@@ -176,12 +175,12 @@ def test_train_batch_with_two_ints_per_padded_row():
     its stride-1 'same' conv keeps the whole 31 x 13 map, 16 padded channels of dY and two ints a row); the rule itself on
     pool41_lead's plan and on a limit between two batches."""
     for name in ftrain_rows.PAD_ROWS:
-        p = fnet_pad.plan(ftrain_rows.pad_blob(name))
+        p = fnet_plan.plan(ftrain_rows.pad_blob(name))
         tb = ftrain_ref.train_batch(p)
         print("%s: forward batch %d, trains at %d, %d bytes" % (name, p["batch"], tb, ftrain_ref.train_lds_bytes(p, tb)))
-        assert 1 <= tb <= p["batch"] and ftrain_ref.train_lds_bytes(p, tb) <= fnet_exact.LDS_BYTES
+        assert 1 <= tb <= p["batch"] and ftrain_ref.train_lds_bytes(p, tb) <= fnet_plan.LDS_BYTES
         assert tb == LOWERED.get(name, p["batch"]), (name, tb, p["batch"])
-    p = fnet_pad.plan(fnet_pad.blob("pool41_lead"))
+    p = fnet_plan.plan(fnet_rows.blob("pool41_lead"))
     L = p["layers"][0]
     assert L["pad"] and L["rows"] == 24 and L["n_pad"] == 16 and p["batch"] == 16
     mp = 16 * 24
@@ -213,7 +212,7 @@ def test_model_dicts_keep_their_pads_through_a_blob():
     """What Trainer.model() / export() rest on: a model dict read from a version-2 blob carries cpad / ppad, and build_blob of it
     (with other weights) is version 2 with the same pads."""
     import struct
-    blob = fnet_pad.blob("medium_embedding_conv")
+    blob = fnet_rows.blob("medium_embedding_conv")
     m = cube_import.read_blob(blob)
     again = dict(m, layers=[dict(L) for L in m["layers"]])
     for L in train.conv_records(again):
@@ -221,8 +220,8 @@ def test_model_dicts_keep_their_pads_through_a_blob():
     out = cube_import.build_blob(again, again.get("keywords"))
     assert struct.unpack_from("<i", out, 4)[0] == 2 and len(out) == len(blob)
     back = cube_import.read_blob(out)
-    assert [fnet_pad.pads(L) for L in train.conv_records(back)] == [fnet_pad.pads(L) for L in train.conv_records(m)]
-    assert any(any(c) or any(q) for c, q in map(fnet_pad.pads, train.conv_records(back)))
+    assert [fnet_host.pads(L) for L in train.conv_records(back)] == [fnet_host.pads(L) for L in train.conv_records(m)]
+    assert any(any(c) or any(q) for c, q in map(fnet_host.pads, train.conv_records(back)))
 
 
 def test_both_gradient_kernels_use_no_scratch_and_fit_four_waves_a_simd(tmp_path):

@@ -1,72 +1,73 @@
-"""CPU tests of the rows of tests/fnet_large.py (float32 networks that exceed the LDS): the plain loader's
+"""CPU tests of the rows of tests/fnet_rows.py (float32 networks that exceed the LDS): the plain loader's
 restatement refuses every one of them, the rows cover between them what the layer kernel's tiling can do, and the bit-exact host model
-the GPU test compares with (fnet_pad.run) agrees with its float64 restatement within fnet_exact.bound."""
+the GPU test compares with (fnet_host.run) agrees with its float64 restatement within fnet_host.bound."""
 import numpy as np
 import pytest
 
-import fnet_exact as fe
-import fnet_large as fl
-import fnet_pad as fp
+import fnet_host as fh
+import fnet_plan as fpl
+import fnet_rows as fr
 
 
-@pytest.mark.parametrize("name", list(fl.ROWS))
+@pytest.mark.parametrize("name", list(fr.LARGE))
 def test_plain_loader_refuses(name):
-    """fnet_pad.plan is parse() without flags: E_NO_IMPL from one of the two LDS refusals; low_latency_conv's dense record has in_c above
+    """fnet_plan.plan is parse() without flags: E_NO_IMPL from one of the two LDS refusals; low_latency_conv's dense record has in_c above
     4096, which parse() meets first and answers E_SIZE ("layer field out of range")."""
-    spec = fl.ROWS[name][0]
-    assert fp.plan(fl.blob(name)) == dict(error=spec.get("plain", fe.E_NO_IMPL))
+    spec = fr.LARGE[name][0]
+    assert fpl.plan(fr.blob(name)) == dict(error=spec.get("plain", fpl.E_NO_IMPL))
     if "plain" not in spec:
-        assert fl.over_lds(fl.model(name)) in ("weights", "acts")
+        assert fr.plan_of(name, large=True)["lifted"] in ("weights", "acts")
     else:
-        assert max(L["inp"][2] for L in fe.conv_records(fl.model(name))) > fe.MAX_DIM
+        assert max(L["inp"][2] for L in fh.conv_records(fr.model(name))) > fpl.MAX_DIM
 
 
 def test_named_shapes():
     """The shapes the rows are named for."""
-    rec = {name: fl.records(fl.model(name))[0] for name in fl.ROWS}
+    rec = {name: fr.plan_of(name, large=True)["layers"] for name in fr.LARGE}
     assert [(L["k_pad"], L["n_pad"]) for L in rec["dense_over"]] == [(2564, 16)]
     assert [(L["k_pad"], L["n_pad"], L["out_c"]) for L in rec["dense_wide"]] == [(700, 80, 72), (72, 16, 10)]
     assert [(L["K"], L["out_c"], L["P"], L["pad"]) for L in rec["conv_valid_pool2"]][0] == (432, 96, 2, False)
     assert [(L["K"], L["out_c"], L["P"], L["pad"], L["live"] < L["rows"]) for L in rec["conv_same_pool4"]][0] == (768, 64, 4, True, True)
-    assert [L["k_pad"] * L["n_pad"] > fe.LDS_BYTES // 4 for L in rec["mixed"]] == [False, True, False]
+    assert [L["k_pad"] * L["n_pad"] > fpl.LDS_BYTES // 4 for L in rec["mixed"]] == [False, True, False]
     assert [(L["K"], L["out_c"]) for L in rec["conv_model"]][1] == (2560, 64)
     assert [(L["K"], L["out_c"]) for L in rec["low_latency_conv"]][1] == (11160, 128)
-    assert fl.over_lds(fl.model("acts_over")) == "acts" and fl.over_lds(fl.model("dense_over")) == "weights"
+    assert fr.plan_of("acts_over", large=True)["lifted"] == "acts" and fr.plan_of("dense_over", large=True)["lifted"] == "weights"
 
 
 def test_rows_cover_the_tiling():
-    have = {name: fl.facts(name) for name in fl.ROWS}
-    for fact in fl.REQUIRED:
+    have = {name: fr.large_facts(name) for name in fr.LARGE}
+    for fact in fr.REQUIRED:
         assert any(fact in f for f in have.values()), "no row covers %r" % (fact,)
 
 
 @pytest.mark.parametrize("fact", [("k", "multiple_of_KC_plus_4"), ("over", "acts"), ("PAD", False, "P", 2), ("absent_rows", 4)])
 def test_coverage_notices_a_missing_row(fact):
     """The coverage test is sensitive: with the rows that cover `fact` taken out, it is no longer covered."""
-    have = {name: fl.facts(name) for name in fl.ROWS}
+    have = {name: fr.large_facts(name) for name in fr.LARGE}
     sole = [name for name, f in have.items() if fact in f]
     assert sole
     assert not any(fact in f for name, f in have.items() if name not in sole)
 
 
 def test_chunks_and_launches():
-    for name in fl.ROWS:
-        m = fl.model(name)
-        cap = fl.cap_for(m, fl.CHUNK)
-        assert fl.chunk_of(m, cap) == fl.CHUNK and fl.chunk_of(m, cap - 4 * 2) == fl.CHUNK - 1
-        assert fl.launches(m, fl.N_CHUNKED, cap) == 3 * (len(fl.records(m)[0]) + 1)
-        assert fl.chunk_of(m, fl.cap_for(m, 1) - 8) == 0
-        assert fl.chunk_of(m) >= 128 and fl.chunk_of(m) % fl.MB == 0
-    assert fl.LAYER_LDS_BYTES == 55808
+    for name in fr.LARGE:
+        p = fr.plan_of(name, large=True)
+        assert p["layered"] and p["batch"] == 0 and p["n_layers"] == len(fh.conv_records(fr.model(name)))
+        cap = fpl.cap_for(p, fr.CHUNK)
+        assert fpl.chunk_of(p, cap) == fr.CHUNK and fpl.chunk_of(p, cap - 4 * 2) == fr.CHUNK - 1
+        assert fpl.launches(p, fr.N_CHUNKED, cap) == 3 * (p["n_layers"] + 1)
+        assert fpl.chunk_of(p, fpl.cap_for(p, 1) - 8) == 0
+        assert fpl.chunk_of(p) >= 128 and fpl.chunk_of(p) % fpl.MB == 0
+    assert fpl.LAYER_LDS_BYTES == 55808
 
 
-@pytest.mark.parametrize("name", list(fl.ROWS))
+@pytest.mark.parametrize("name", list(fr.LARGE))
 def test_host_model_against_float64(name):
-    m = fl.model(name)
-    x = fl.inputs(name, 3)
-    assert np.array_equal(x, fl.inputs(name, 5)[:3])
-    got, prev = fp.run(m, x), x
-    for i, (L, g) in enumerate(zip(fe.conv_records(m), got)):
-        w64, S = fp.layer_from(m, i, prev)
-        assert (np.abs(g - w64) <= fe.bound(L, S)).all(), (name, i)
+    m = fr.model(name)
+    x = fr.inputs(name, 3)
+    assert np.array_equal(x, fr.inputs(name, 5)[:3])
+    got, prev = fh.run(m, x), x
+    for i, (L, g) in enumerate(zip(fh.conv_records(m), got)):
+        w64, S = fh.layer_from(m, i, prev)
+        assert (np.abs(g - w64) <= fh.bound(L, S)).all(), (name, i)
         prev = g

@@ -1,6 +1,6 @@
-"""The float-network sweep without a GPU: the rows of tests/fnet_sweep.py cover every path of the restated plan
-(tests/fnet_exact.py plan = parse() in csrc/edison_fnet.hip), fma32 is glibc's fmaf bit for bit, the host model of the kernel stays
-within the GPU tests' bound of the float64 restatement (tests/fnet_ref.py), and the bit-exact check sees wrong arithmetic that the
+"""The float-network sweep without a GPU: the rows of tests/fnet_rows.py cover every path of the restated plan
+(tests/fnet_plan.py plan = parse() in csrc/edison_fnet.hip), fma32 is glibc's fmaf bit for bit, the host model of the kernel stays
+within the GPU tests' bound of the float64 restatement (tests/fnet_host.py), and the bit-exact check sees wrong arithmetic that the
 bound alone does not."""
 import ctypes
 import ctypes.util
@@ -13,17 +13,17 @@ import pytest
 from conftest import GOLDEN
 from edison_amd import cube_import
 
-import fnet_exact as fe
-import fnet_ref
-import fnet_sweep as fs
+import fnet_host as fh
+import fnet_plan as fpl
+import fnet_rows as fr
 
 VARIANTS = ("reversed", "rounded_product", "f64_sum", "drop_last")
-bound = fe.bound
+bound = fh.bound
 
 
 @pytest.fixture(scope="module")
 def plans():
-    return {name: fe.plan(fs.blob(name)) for name in fs.ROWS}
+    return {name: fpl.plan(fr.blob(name)) for name in fr.SWEEP}
 
 
 def _dense(L):
@@ -33,18 +33,18 @@ def _dense(L):
 @functools.lru_cache(maxsize=None)
 def _facts(name):
     """What row `name` takes, read from its plan, its model and the host model's outputs: a set of hashable facts."""
-    p, spec = fe.plan(fs.blob(name)), fs.ROWS[name][0]
-    m = fnet_ref.load(fs.blob(name))
-    recs = fe.conv_records(m)
+    p, spec = fpl.plan(fr.blob(name)), fr.SWEEP[name][0]
+    m = fh.load(fr.blob(name))
+    recs = fh.conv_records(m)
     f = set()
-    for k, v in fs.path(p).items():
+    for k, v in fr.path(p).items():
         f |= {(k, x) for x in v}
-    f |= {("NG>=3",) for x in fs.path(p)["NG"] if x >= 3} | {("n_out>=200",) for x in fs.path(p)["n_out"] if x >= 200}
+    f |= {("NG>=3",) for x in fr.path(p)["NG"] if x >= 3} | {("n_out>=200",) for x in fr.path(p)["n_out"] if x >= 200}
     if 1 < p["batch"] < 16:
         f.add(("batch_mid",))
-    if p["n_layers"] == fe.MAX_LAYERS and max(L["rows"] for L in p["layers"]) > 1:
+    if p["n_layers"] == fpl.MAX_LAYERS and max(L["rows"] for L in p["layers"]) > 1:
         f.add(("layers16_maps",))                 # the most records the plan holds, with maps of several rows per utterance
-    if fs.w_floats(p) > fs.STEP_PASS * 256:
+    if fr.w_floats(p) > fr.STEP_PASS * 256:
         f.add(("step_second_pass",))              # more packed weights than one pass of the optimiser's step kernel covers on 256 CUs
     K0 = recs[0]["k"][0] * recs[0]["k"][1] * recs[0]["inp"][2]
     if len(recs) == 1 and _dense(recs[0]) and not recs[0]["b"].any():
@@ -71,18 +71,18 @@ def _facts(name):
             f |= {("span_h",)} if kh == ih else set()
             f |= {("span_w",)} if kw == iw else set()
     for Lp in p["layers"]:
-        if Lp["k_pad"] * Lp["n_pad"] == p["w_lds"] and p["batch"] == 1 and p["lds_bytes"] + 4 * (4 * Lp["n_pad"] + 4 + 4) > fe.LDS_BYTES:
+        if Lp["k_pad"] * Lp["n_pad"] == p["w_lds"] and p["batch"] == 1 and p["lds_bytes"] + 4 * (4 * Lp["n_pad"] + 4 + 4) > fpl.LDS_BYTES:
             f.add(("largest_weights_batch1",))    # 4 more k rows would not load
         if Lp["P"] == 4 and any(nu * Lp["rows"] % 16 for nu in range(1, p["batch"] + 1)):
             f.add(("m_tail_P4",))
-    if 0 <= fe.LDS_BYTES - p["lds_bytes"] <= 1024:
+    if 0 <= fpl.LDS_BYTES - p["lds_bytes"] <= 1024:
         f.add(("lds_within_1k",))
-    if p["batch"] > 1 and 4 * p["batch"] * sum(p["buf_n"]) >= 0.75 * fe.LDS_BYTES:
+    if p["batch"] > 1 and 4 * p["batch"] * sum(p["buf_n"]) >= 0.75 * fpl.LDS_BYTES:
         f.add(("batch_mid_by_activations",))      # a tile of several utterances whose activations fill most of the LDS
     # from the host model's outputs: subnormals with zero bias; ReLU logits that are all 0 for some input
-    sets = spec.get("sets", fs.SETS)
-    x = fs.inputs(name, len(sets), p["in_n"])
-    outs = fe.run(m, x)
+    sets = spec.get("sets", fr.SETS)
+    x = fr.inputs(name, len(sets), p["in_n"])
+    outs = fh.run(m, x)
     if all(not L["b"].any() for L in recs):
         o = np.concatenate([a.ravel() for a in outs])
         if ((o != 0) & (np.abs(o) < np.finfo(np.float32).tiny)).sum() > 100:
@@ -113,44 +113,44 @@ def _missing(names):
 
 
 def test_the_rows_cover_every_path():
-    assert all("error" not in fe.plan(fs.blob(n)) for n in fs.ROWS)
-    assert _missing(fs.ROWS) == []
+    assert all("error" not in fpl.plan(fr.blob(n)) for n in fr.SWEEP)
+    assert _missing(fr.SWEEP) == []
     # the arithmetic ladder comes first, in order K = 4, 5, 8
-    assert [next(iter(k for k in _facts(n) if k[0] == "ladder"), None) for n in list(fs.ROWS)[:3]] == [("ladder", 4), ("ladder", 5), ("ladder", 8)]
+    assert [next(iter(k for k in _facts(n) if k[0] == "ladder"), None) for n in list(fr.SWEEP)[:3]] == [("ladder", 4), ("ladder", 5), ("ladder", 8)]
     # the loader's refusals, each with its code (test_refusal_code)
-    assert set(fs.REFUSALS) == {"pool31", "layers17", "weights_over_lds", "lds_batch1", "k_pad", "n_pad"}
+    assert set(fr.SWEEP_REFUSALS) == {"pool31", "layers17", "weights_over_lds", "lds_batch1", "k_pad", "n_pad"}
 
 
-@pytest.mark.parametrize("name", list(fs.ROWS))
+@pytest.mark.parametrize("name", list(fr.SWEEP))
 def test_every_row_is_needed(name):
     """Without this row some required item is no longer covered."""
-    assert _missing([n for n in fs.ROWS if n != name]), "%s adds nothing the other rows do not cover" % name
+    assert _missing([n for n in fr.SWEEP if n != name]), "%s adds nothing the other rows do not cover" % name
 
 
-@pytest.mark.parametrize("name", list(fs.ROWS))
+@pytest.mark.parametrize("name", list(fr.SWEEP))
 def test_note_agrees_with_the_plan(plans, name):
-    have = fs.path(plans[name])
-    for k, v in fs.claims(fs.ROWS[name][1]).items():
+    have = fr.path(plans[name])
+    for k, v in fr.claims(fr.SWEEP[name][1]).items():
         assert have[k] == v, (name, k, v, have[k])
 
 
-@pytest.mark.parametrize("name", list(fs.REFUSALS))
+@pytest.mark.parametrize("name", list(fr.SWEEP_REFUSALS))
 def test_refusal_code(name):
-    build, code, _ = fs.REFUSALS[name]
-    assert fe.plan(build()) == dict(error=code)
+    build, code, _ = fr.SWEEP_REFUSALS[name]
+    assert fpl.plan(build()) == dict(error=code)
 
 
 def test_shipped_plan():
     with open(os.path.join(GOLDEN, "cube_kws.ednf"), "rb") as f:
-        p = fe.plan(f.read())
+        p = fpl.plan(f.read())
     assert (p["batch"], p["lds_bytes"], p["n_layers"], p["n_out"]) == (7, 159808, 5, 10)
     assert p["acts_floats"] == 13 * 9 * 16 + 5 * 7 * 32 + 3 * 5 * 64 + 3 * 32 + 10
 
 
 def test_importer_blob_n_out_is_the_whole_output():
     """The header's n_out is out_h x out_w x out_c of the last conv (what the loader checks), not its channel count."""
-    p = fe.plan(fs.blob("conv_last_map"))
-    assert p["n_out"] == 16 and cube_import.read_blob(fs.blob("conv_last_map"))["n_out"] == 16
+    p = fpl.plan(fr.blob("conv_last_map"))
+    assert p["n_out"] == 16 and cube_import.read_blob(fr.blob("conv_last_map"))["n_out"] == 16
 
 
 # ---- fma32 ------------------------------------------------------------------------------------------------------------------------
@@ -203,7 +203,7 @@ def test_fma32_is_glibc_fmaf():
         for a, b, c in cases:
             keep = np.isfinite(a.astype(np.float64) * b + c) & (np.abs(a.astype(np.float64) * b + c) < 3.0e38)
             a, b, c = a[keep], b[keep], c[keep]
-            assert _same_bits(fe.fma32(a, b, c), fmaf(a, b, c))
+            assert _same_bits(fh.fma32(a, b, c), fmaf(a, b, c))
             total += a.size
     assert total >= 100000
 
@@ -223,47 +223,47 @@ def test_fma32_where_the_float64_sum_rounds_wrong():
         want = fmaf(a, b, c)
         naive = (a.astype(np.float64) * b + c).astype(np.float32)
         assert not (naive == want).any()          # every case: the naive route is wrong ...
-        assert _same_bits(fe.fma32(a, b, c), want)  # ... and fma32 is right
+        assert _same_bits(fh.fma32(a, b, c), want)  # ... and fma32 is right
 
 
 # ---- the host model against the float64 restatement, and what the bit check sees ----------------------------------------------
 def _row_inputs(name, p, n=None):
-    return fs.inputs(name, n or min(3 * p["batch"] + 2, 12), p["in_n"])
+    return fr.inputs(name, n or min(3 * p["batch"] + 2, 12), p["in_n"])
 
 
-@pytest.mark.parametrize("name", list(fs.ROWS))
+@pytest.mark.parametrize("name", list(fr.SWEEP))
 def test_model_within_the_bound(plans, name):
-    m = fnet_ref.load(fs.blob(name))
+    m = fh.load(fr.blob(name))
     x = _row_inputs(name, plans[name])
     prev = x
-    for i, (L, got) in enumerate(zip(fe.conv_records(m), fe.run(m, x))):
-        want, S = fnet_ref.layer_from(m, i, prev)
+    for i, (L, got) in enumerate(zip(fh.conv_records(m), fh.run(m, x))):
+        want, S = fh.layer_from(m, i, prev)
         assert (np.abs(got - want) <= bound(L, S)).all(), (name, i)
         prev = got
     if ("relu_logits_all_zero",) in _facts(name):
-        logits = fe.run(m, x)[-1]
+        logits = fh.run(m, x)[-1]
         zero = ~logits.any(axis=1)               # every logit 0: probs tie, the first maximum is class 0
-        assert (np.argmax(fnet_ref.softmax(logits[zero]), axis=1) == 0).all()
+        assert (np.argmax(fh.softmax(logits[zero]), axis=1) == 0).all()
 
 
-SENSITIVE_ROWS = [n for n in fs.ROWS if max(L["K"] for L in fe.plan(fs.blob(n))["layers"]) >= 8]
+SENSITIVE_ROWS = [n for n in fr.SWEEP if max(L["K"] for L in fpl.plan(fr.blob(n))["layers"]) >= 8]
 
 
 @functools.lru_cache(maxsize=None)
 def _variants(name):
     """variant -> (changes at least one output bit, stays within 8e-7 S at every layer), each layer fed the exact previous one."""
-    m = fnet_ref.load(fs.blob(name))
-    sets = fs.ROWS[name][0].get("sets", fs.SETS)
-    x = fs.inputs(name, 2 * len(sets), fe.plan(fs.blob(name))["in_n"])
+    m = fh.load(fr.blob(name))
+    sets = fr.SWEEP[name][0].get("sets", fr.SETS)
+    x = fr.inputs(name, 2 * len(sets), fpl.plan(fr.blob(name))["in_n"])
     x = x[[i for i in range(len(x)) if sets[i % len(sets)] in ("n1", "n60", "i16")]]
-    exact = fe.run(m, x)
+    exact = fh.run(m, x)
     out = {}
     for v in VARIANTS:
         prev, changed, within = x, False, True
-        for i, L in enumerate(fe.conv_records(m)):
-            got = fe.layer(L, prev, v)
+        for i, L in enumerate(fh.conv_records(m)):
+            got = fh.layer(L, prev, v)
             changed |= not np.array_equal(got, exact[i])
-            want, S = fnet_ref.layer_from(m, i, prev)
+            want, S = fh.layer_from(m, i, prev)
             within &= bool((np.abs(got - want) <= bound(L, S)).all())
             prev = exact[i]
         out[v] = (changed, within)

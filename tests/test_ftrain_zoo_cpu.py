@@ -8,8 +8,8 @@ import pytest
 
 from conftest import GOLDEN
 
-import fnet_pad
-import fnet_sweep as fs
+import cube_synth
+import fnet_rows as fr
 import ftrain_ref
 import ftrain_rows
 from edison_amd import cube_import, train
@@ -26,12 +26,12 @@ def shapes(model):
 
 
 def scratch_model():
-    return train.get_model(SCRATCH_ARCH, fs.model(ftrain_rows.FIT_ROW)["in_shape"], ftrain_rows.FIT_CLASSES)
+    return train.get_model(SCRATCH_ARCH, fr.model(ftrain_rows.FIT_ROW)["in_shape"], ftrain_rows.FIT_CLASSES)
 
 
-@pytest.mark.parametrize("name", fnet_pad.ZOO)
+@pytest.mark.parametrize("name", fr.ZOO)
 def test_the_padded_architectures_are_the_ones_the_tests_import(name):
-    want = cube_import.read_blob(fnet_pad.import_sources(*fnet_pad.cube_sources((31, 13, 1), fnet_pad.zoo_specs(name))))
+    want = cube_import.read_blob(cube_synth.import_sources(*cube_synth.cube_sources((31, 13, 1), fr.zoo_specs(name))))
     m = train.get_model(name)
     assert shapes(m) == shapes(want)
     assert m["in_shape"] == tuple(want["in_shape"]) and m["layers"][-1]["type"] == cube_import.T_SOFTMAX
@@ -157,7 +157,7 @@ def test_fit_data_is_fit_on_the_host(setting):
     kw = dict(FIT_SETTINGS[setting])
     steps, epochs_run, with_val = kw.pop("steps"), kw.pop("epochs_run"), kw.pop("val", False)
     x, y = ftrain_rows.fit_set()
-    m = fs.model(ftrain_rows.FIT_ROW)
+    m = fr.model(ftrain_rows.FIT_ROW)
     val = (x[60:], y[60:]) if with_val else None
     a, b = ftrain_ref.HostTrainer(m), ftrain_ref.HostTrainer(m)
     ha = train.fit(a, x, y, val=val, seed=0, lr=ftrain_rows.FIT_LR, **kw)

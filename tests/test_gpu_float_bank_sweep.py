@@ -7,7 +7,7 @@ final machines as raw fields.
 Rows with more than 8 microphones play bank_sweep.BASES seeded recordings (microphone m plays base_of(m)). Two references:
   independent  no stream, no bank, none of the core's kernels: every frame's float row from the batch call on the zero-led recording
                (Context.kws_float(..., utt_stride=frame_step)["feat"], in the row's flow, clip range and scale), the windows cut in
-               numpy behind F - 1 zero rows, Context.fnet on them, the logits also against the CPU fmaf chain (tests/fnet_exact.py:
+               numpy behind F - 1 zero rows, Context.fnet on them, the logits also against the CPU fmaf chain (tests/fnet_host.py:
                every window of a recording of at most 2048, else the first and last 64), the filter in numpy
                (test_gpu_stream_geom._filter_ref) and edisonFSM from the host binding (stream.Fsm)
   streams      one stream.FloatStream per base recording and per reset, same options, same schedule: rows with resets only
@@ -20,7 +20,7 @@ import pytest
 
 import bank_sweep as bs
 import float_bank_sweep as fs
-import fnet_exact
+import fnet_host
 from test_gpu_bank_sweep import _start_machine, garbage, masked_expected, present_counts
 from test_gpu_float_bank import KEYS, _empty_outputs, _same
 from test_gpu_stream_bank import _recordings, _to_host, _torch_stream
@@ -51,7 +51,7 @@ def _net_ref(c, g, row, model, x):
     win = np.ascontiguousarray(np.lib.stride_tricks.sliding_window_view(r, (F, nm))[:, 0].reshape(K, -1))
     out = c.fnet(win)
     idx = np.arange(K) if K <= 2048 else np.concatenate([np.arange(64), np.arange(K - 64, K)])
-    _same(out["logits"][idx], fnet_exact.run(model, win[idx])[-1], "the reference's logits against the fmaf chain")
+    _same(out["logits"][idx], fnet_host.run(model, win[idx])[-1], "the reference's logits against the fmaf chain")
     return out
 
 

@@ -1,10 +1,10 @@
 """GPU tests (-m gpu) of float32 X-CUBE-AI networks (edison_fnet_*, edison_kws_float_batch*). The reference answer is
-tests/fnet_ref.py, the float64 restatement of the Cube layers, on the .ednf fixture of the reference's own network
+tests/fnet_host.py, the float64 restatement of the Cube layers, on the .ednf fixture of the reference's own network
 (tests/golden/cube_kws.ednf) and on networks generated in the importer's input format (tests/cube_synth.py).
 
 Bounds (DESIGN.md section 14 has what was measured):
   every layer, fed the kernel's own previous layer: |gpu - f64| <= K_BOUND 1e-7 S, S = sum |a| |w| + |bias| (f32 MFMA: a k-ordered fmaf chain)
-    and, on up to 266 inputs per call, bit-equal to the host model of that chain (tests/fnet_exact.py)
+    and, on up to 266 inputs per call, bit-equal to the host model of that chain (tests/fnet_host.py)
   probabilities: within 1e-6 of the float64 softmax of the kernel's logits
   argmax: equal to the float64 chain's wherever its top-2 logit margin exceeds MARGIN
   host-flow features: at most FEAT_FLIPS elements per utterance differ from the reference's float32 net input, by 1 ulp"""
@@ -17,8 +17,7 @@ import pytest
 from conftest import GOLDEN
 
 import cube_synth
-import fnet_exact
-import fnet_ref
+import fnet_host
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +39,7 @@ def fctx(built_lib):
 
 @pytest.fixture(scope="module")
 def model():
-    return fnet_ref.load(FIXTURE)
+    return fnet_host.load(FIXTURE)
 
 
 @pytest.fixture(scope="module")
@@ -56,24 +55,24 @@ def _inputs(golden, n=4096):
     return np.concatenate([x, np.stack(fx)])
 
 
-EXACT_N = 256       # inputs of a call checked bit for bit against fnet_exact (the first 256 and the last 10: the fixture inputs)
+EXACT_N = 256       # inputs of a call checked bit for bit against fnet_host (the first 256 and the last 10: the fixture inputs)
 
 
 def check_layers(ctx, model, x):
     """Every layer of the kernel against the restatement fed the kernel's own previous layer, and bit for bit against the host model
-    of the kernel (tests/fnet_exact.py: k-ordered fmaf chain, bias, ReLU, pool) on at most EXACT_N + 10 of the inputs; returns the
+    of the kernel (tests/fnet_host.py: k-ordered fmaf chain, bias, ReLU, pool) on at most EXACT_N + 10 of the inputs; returns the
     largest err / (1e-7 S)."""
     acts32 = ctx.fnet_layers(x)
     pick = np.arange(len(x)) if len(x) <= EXACT_N + 10 else np.r_[:EXACT_N, len(x) - 10:len(x)]
-    want, got = fnet_exact.layers_from(model, np.asarray(x, np.float32)[pick], acts32[pick])
+    want, got = fnet_host.layers_from(model, np.asarray(x, np.float32)[pick], acts32[pick])
     for i, (w, g) in enumerate(zip(want, got)):
         assert np.array_equal(w, g), "layer %d: %d of %d outputs differ from the fmaf chain" % (i, (w != g).sum(), w.size)
     acts = acts32.astype(np.float64)
     prev, off, worst = np.asarray(x, np.float64), 0, 0.0
-    for i, L in enumerate(fnet_ref.conv_records(model)):
+    for i, L in enumerate(fnet_host.conv_records(model)):
         n_out = int(np.prod(L["out"]))
         got = acts[:, off:off + n_out]
-        want, S = fnet_ref.layer_from(model, i, prev)
+        want, S = fnet_host.layer_from(model, i, prev)
         err = np.abs(got - want)
         bad = err > K_BOUND * 1e-7 * S
         assert not bad.any(), "layer %d: %d outputs outside %g 1e-7 S (worst ratio %.3g)" % (i, bad.sum(), K_BOUND, (err / (1e-7 * S + 1e-300)).max())
@@ -96,10 +95,10 @@ def test_net_alone(fctx, model, golden):
     r = fctx.fnet(x)
     # logits = the last layer of the dump (same kernel, same arithmetic)
     assert np.array_equal(r["logits"], acts[:, -10:].astype(np.float32))
-    p64 = fnet_ref.softmax(r["logits"].astype(np.float64))
+    p64 = fnet_host.softmax(r["logits"].astype(np.float64))
     assert np.abs(r["probs"] - p64).max() <= 1e-6
     assert np.array_equal(r["argmax"], np.argmax(r["probs"], axis=1))
-    ref = fnet_ref.run(model, x)
+    ref = fnet_host.run64(model, x)
     top = np.sort(ref["logits"], axis=1)
     clear = top[:, -1] - top[:, -2] > MARGIN
     assert clear.mean() > 0.99
@@ -147,7 +146,7 @@ def test_firmware_flow(fctx, model, golden):
         assert np.array_equal(r["feat"][j], q.astype(np.float32).reshape(-1))
         assert np.array_equal(q, golden["q15_" + s])
     check_layers(fctx, model, r["feat"])
-    ref = fnet_ref.run(model, r["feat"])
+    ref = fnet_host.run64(model, r["feat"])
     assert np.abs(r["logits"] - ref["logits"]).max() <= 1e-4 * (1.0 + np.abs(ref["logits"]).max())
     for j, s in enumerate(SOURCES):
         np.testing.assert_allclose(r["logits"][j], golden["q15_logits_" + s], rtol=0, atol=1e-4 * (1.0 + np.abs(ref["logits"]).max()))
@@ -196,7 +195,7 @@ def test_second_geometry(built_lib, tmp_path):
     (tmp_path / "n.c").write_text(net_c)
     (tmp_path / "n_data.c").write_text(data_c)
     blob = cube_import.import_files(str(tmp_path / "n.c"), str(tmp_path / "n_data.c"))
-    m = fnet_ref.load(blob)
+    m = fnet_host.load(blob)
     ctx = Context(0)
     try:
         ctx.fnet_load(blob)
@@ -210,7 +209,7 @@ def test_second_geometry(built_lib, tmp_path):
         want = np.clip(y.astype(np.float32) * np.float32(0.5), np.float32(-40.0), np.float32(40.0))
         assert np.array_equal(r["feat"], want)
         check_layers(ctx, m, r["feat"])
-        np.testing.assert_allclose(r["probs"], fnet_ref.softmax(r["logits"].astype(np.float64)), rtol=0, atol=1e-6)
+        np.testing.assert_allclose(r["probs"], fnet_host.softmax(r["logits"].astype(np.float64)), rtol=0, atol=1e-6)
     finally:
         ctx.close()
 

@@ -1,5 +1,5 @@
 """GPU tests (-m gpu) of padded float32 networks ('same' convolutions and pools, .ednf version 2). The rows,
-the bit-exact host model and the float64 restatement are tests/fnet_pad.py's.
+the bit-exact host model and the float64 restatement are tests/fnet_host.py's.
 
 Per row, at 2 batch + 1 utterances (a full tile, a second one, a tile of one):
   fnet_info = the restated version-2 plan
@@ -19,10 +19,10 @@ from test_gpu_kws_geom import _geom
 from test_gpu_stream_bank import _recordings
 from test_gpu_stream_geom import _tail
 
-import fcal_pad_ref
-import fnet_exact as fe
-import fnet_pad as fp
-import fnet_ref
+import cube_synth
+import fnet_host as fh
+import fnet_plan as fpl
+import fnet_rows as fr
 from edison_amd import cube_import
 from edison_amd import quantize as qz
 from oracle import net_ref
@@ -49,9 +49,9 @@ def small():
     """(blob, model, geometry) of medium_embedding_conv at the small geometry, through the X-CUBE-AI source format and the importer."""
     g = _geom(**SMALL)
     assert (g.frame_count, g.num_mfcc, 1) == SMALL_IN
-    blob = fp.import_sources(*fp.cube_sources(SMALL_IN, fp.zoo_specs("medium_embedding_conv", SMALL_IN), seed=5))
+    blob = cube_synth.import_sources(*cube_synth.cube_sources(SMALL_IN, fr.zoo_specs("medium_embedding_conv", SMALL_IN), seed=5))
     m = cube_import.read_blob(blob)
-    assert [pads for L in fe.conv_records(m) for pads in (L["cpad"], L["ppad"])][:4] == [(3, 3, 3, 3), (0, 0, 1, 1), (1, 1, 2, 2), (0, 0, 0, 0)]
+    assert [pads for L in fh.conv_records(m) for pads in (L["cpad"], L["ppad"])][:4] == [(3, 3, 3, 3), (0, 0, 1, 1), (1, 1, 2, 2), (0, 0, 0, 0)]
     return blob, m, g
 
 
@@ -62,34 +62,34 @@ def _same(got, want, what):
     assert np.array_equal(v(got), v(want)), "%s: %d of %d differ" % (what, int((v(got) != v(want)).sum()), got.size)
 
 
-@pytest.mark.parametrize("name", list(fp.ROWS))
+@pytest.mark.parametrize("name", list(fr.PAD))
 def test_row_bit_exact(ctx, name):
-    blob = fp.blob(name)
-    p, m = fp.plan(blob), fp.model(name)
+    blob = fr.blob(name)
+    p, m = fpl.plan(blob), fr.model(name)
     ctx.fnet_load(blob)
     info = ctx.fnet_info()
     assert (info["batch"], info["lds_bytes"], info["acts_floats"], info["n_layers"], info["n_out"]) == \
         (p["batch"], p["lds_bytes"], p["acts_floats"], p["n_layers"], p["n_out"])
     n = 2 * p["batch"] + 1
-    x = fp.inputs(name, n, p["in_n"])
+    x = fr.inputs(name, n, p["in_n"])
     acts = ctx.fnet_layers(x)
-    want, got = fp.layers_from(m, x, acts)
+    want, got = fh.layers_from(m, x, acts)
     prev = x
-    for i, (L, w, g) in enumerate(zip(fe.conv_records(m), want, got)):
+    for i, (L, w, g) in enumerate(zip(fh.conv_records(m), want, got)):
         diff = w.view(np.uint32) != g.view(np.uint32)
         assert not diff.any(), "%s layer %d: %d of %d outputs differ from the model (first at %s: gpu %r, model %r)" % (
             name, i, diff.sum(), diff.size, np.argwhere(diff)[0], g[diff][0], w[diff][0])
-        w64, S = fp.layer_from(m, i, prev)
-        assert (np.abs(g - w64) <= fe.bound(L, S)).all(), (name, i)
+        w64, S = fh.layer_from(m, i, prev)
+        assert (np.abs(g - w64) <= fh.bound(L, S)).all(), (name, i)
         prev = g
     r = ctx.fnet(x)
     _same(r["logits"], want[-1], name + " logits")
-    assert np.abs(r["probs"] - fnet_ref.softmax(r["logits"].astype(np.float64))).max() <= 1e-6
+    assert np.abs(r["probs"] - fh.softmax(r["logits"].astype(np.float64))).max() <= 1e-6
     assert np.array_equal(r["argmax"], np.argmax(r["probs"], axis=1))
-    z64 = fp.run64(m, x)[-1]
+    z64 = fh.run64(m, x)["logits"]
     top = np.sort(z64, axis=1)
     clear = top[:, -1] - top[:, -2] > MARGIN if z64.shape[1] > 1 else np.ones(n, bool)
-    assert np.array_equal(r["argmax"][clear], np.argmax(fnet_ref.softmax(z64), axis=1)[clear])
+    assert np.array_equal(r["argmax"][clear], np.argmax(fh.softmax(z64), axis=1)[clear])
     # an utterance's answer does not depend on its neighbours in the tile
     one = ctx.fnet(x[n - 1:])
     _same(one["logits"], r["logits"][n - 1:], name + " last utterance alone")
@@ -99,11 +99,11 @@ def test_refusals_keep_the_loaded_network(ctx):
     """Every refusal returns its code and leaves the network loaded before it answering bit-identically."""
     from edison_amd import _lib
     name = "pool22_odd"
-    ctx.fnet_load(fp.blob(name))
-    p = fp.plan(fp.blob(name))
-    x = fp.inputs(name, p["batch"] + 1, p["in_n"])
+    ctx.fnet_load(fr.blob(name))
+    p = fpl.plan(fr.blob(name))
+    x = fr.inputs(name, p["batch"] + 1, p["in_n"])
     before, acts = ctx.fnet(x), ctx.fnet_layers(x)
-    for ref, (build, code, note) in fp.REFUSALS.items():
+    for ref, (build, code, note) in fr.PAD_REFUSALS.items():
         with pytest.raises(_lib.EdisonError) as e:
             ctx.fnet_load(build())
         assert e.value.code == code, (ref, note)
@@ -143,7 +143,7 @@ def test_stream_and_bank_on_a_padded_network(ctx, small):
             _same(streams[mic][k][F - 1:], want[k], "microphone %d stream against kws_float: %s" % (mic, k))
     # the batch call's features through the host model: the stream's logits are the padded chain's
     feat = _batch_call(ctx, g, xs[0])["feat"]
-    _same(streams[0]["logits"][F - 1:], fp.run(m, feat)[-1], "stream logits against the host model")
+    _same(streams[0]["logits"][F - 1:], fh.run(m, feat)[-1], "stream logits against the host model")
     b = FloatBank(ctx, 3, g)
     got = _pushes(b, xs)
     b.close()
@@ -155,22 +155,22 @@ def test_stream_and_bank_on_a_padded_network(ctx, small):
 @pytest.mark.parametrize("name", ["pool22_odd", "pool41_lead", "neg_no_relu", "mid_pads_batch"])
 def test_calibrator_counters(ctx, name):
     """absmax, hist and count equal the host restatement exactly: absent elements are counted nowhere, count = present rows x out_c."""
-    m, blob = fp.model(name), fp.blob(name)
-    p = fp.plan(blob)
+    m, blob = fr.model(name), fr.blob(name)
+    p = fpl.plan(blob)
     ctx.fnet_load(blob)
     with ctx.calibrator() as cal:
         batch = cal.batch
-        x = fp.inputs(name, 2 * batch + 1, p["in_n"])
+        x = fr.inputs(name, 2 * batch + 1, p["in_n"])
         for k in sorted({1, batch + 1, 2 * batch + 1}):
             cal.reset()
             cal.add(x[:k])
-            got, want = cal.result(), fcal_pad_ref.stats(m, x[:k])
+            got, want = cal.result(), fh.stats(m, x[:k])
             for key in ("count", "absmax", "hist"):
                 assert np.array_equal(got[key], want[key]), "%s, n = %d: %s differs at %s" % (name, k, key, np.argwhere(got[key] != want[key])[:4].tolist())
             assert (got["hist"].sum(axis=1) == got["count"]).all()
             assert got["count"].tolist() == [k * p["in_n"]] + [k * L["live"] * L["out_c"] for L in p["layers"]]
     if name == "neg_no_relu":
-        assert (fp.run(m, x)[0] < -30).all()          # every pooled value is a real one: none came from an absent 0
+        assert (fh.run(m, x)[0] < -30).all()          # every pooled value is a real one: none came from an absent 0
 
 
 def test_quantize_medium_embedding_conv(ctx, small):
@@ -181,7 +181,7 @@ def test_quantize_medium_embedding_conv(ctx, small):
     ctx.fnet_load(blob)
     audio = _recordings(g, 6, g.frame_count + 1, 7)[:, :g.n_samples]
     q, rep = ctx.quantize(audio.ravel(), geometry=g, chunk=4, return_features=True)
-    want_q, _ = qz.quantize(m, fcal_pad_ref.stats(m, rep["features"]))
+    want_q, _ = qz.quantize(m, fh.stats(m, rep["features"]))
     assert q == want_q
     assert [(L["type"], L["same"]) for L in rep["graph"] if "same" in L] == [(nnom_import.T_CONV, 1), (nnom_import.T_POOL, 1), (nnom_import.T_CONV, 1)]
     (_, recs, _) = net_ref.parse_blob(q)
@@ -192,11 +192,11 @@ def test_quantize_medium_embedding_conv(ctx, small):
     assert np.array_equal(got["logits"], ref["logits"]) and np.array_equal(got["softmax"], ref["softmax"])
     assert np.array_equal(got["argmax"], ref["argmax"])
     # a padded record NNoM cannot express is refused by name, with the context still usable
-    ctx.fnet_load(fp.blob("tiny_embedding_conv"))
+    ctx.fnet_load(fr.blob("tiny_embedding_conv"))
     with ctx.calibrator() as cal:
-        cal.add(fp.inputs("tiny_embedding_conv", 3, 403))
+        cal.add(fr.inputs("tiny_embedding_conv", 3, 403))
         with pytest.raises(qz.QuantizeError, match="^conv2d_2: its conv pads"):
-            qz.quantize(fp.model("tiny_embedding_conv"), cal.result())
+            qz.quantize(fr.model("tiny_embedding_conv"), cal.result())
 
 
 def test_shipped_network_unchanged_around_a_padded_load(ctx):
@@ -205,9 +205,9 @@ def test_shipped_network_unchanged_around_a_padded_load(ctx):
     x = rng.normal(0, 60, (40, 403)).astype(np.float32)
     ctx.fnet_load(FIXTURE)
     before, acts = ctx.fnet(x), ctx.fnet_layers(x[:9])
-    want, got = fe.layers_from(fnet_ref.load(FIXTURE), x[:9], acts)
+    want, got = fh.layers_from(fh.load(FIXTURE), x[:9], acts)
     assert all(np.array_equal(w, g) for w, g in zip(want, got))
-    ctx.fnet_load(fp.blob("medium_embedding_conv"))
+    ctx.fnet_load(fr.blob("medium_embedding_conv"))
     ctx.fnet(x)
     ctx.fnet_load(FIXTURE)
     after = ctx.fnet(x)

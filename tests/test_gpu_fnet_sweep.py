@@ -1,19 +1,19 @@
-"""GPU tests (-m gpu) of the float-network sweep (tests/fnet_sweep.py): every row's layers and logits bit for bit against the host
-model of the kernel (tests/fnet_exact.py), at utterance counts around the workgroup's tile; the loader's refusals; the device entry
+"""GPU tests (-m gpu) of the float-network sweep (tests/fnet_rows.py): every row's layers and logits bit for bit against the host
+model of the kernel (tests/fnet_host.py), at utterance counts around the workgroup's tile; the loader's refusals; the device entry
 point with one output at a time.
 
 Per row and count n in {1, batch - 1, batch, batch + 1, 3 batch + 2}:
   fnet_info = the restated plan (batch, lds_bytes, acts_floats, n_layers)
-  every layer of fnet_layers, layer i fed the kernel's own layer i - 1, and the logits of fnet: bit-equal to fnet_exact
-  every layer within 8e-7 S of the float64 restatement (tests/fnet_ref.py; plus the underflow term on the subnormal row)
+  every layer of fnet_layers, layer i fed the kernel's own layer i - 1, and the logits of fnet: bit-equal to fnet_host
+  every layer within 8e-7 S of the float64 restatement (tests/fnet_host.py; plus the underflow term on the subnormal row)
   probs within 1e-6 of the float64 softmax of the kernel's logits; argmax the first maximum of the kernel's probs
   each utterance's layers and answers independent of how many utterances share the call"""
 import numpy as np
 import pytest
 
-import fnet_exact as fe
-import fnet_ref
-import fnet_sweep as fs
+import fnet_host as fh
+import fnet_plan as fpl
+import fnet_rows as fr
 
 pytestmark = pytest.mark.gpu
 
@@ -30,25 +30,25 @@ def _counts(batch):
     return sorted({n for n in (1, batch - 1, batch, batch + 1, 3 * batch + 2) if n > 0})
 
 
-@pytest.mark.parametrize("name", list(fs.ROWS))
+@pytest.mark.parametrize("name", list(fr.SWEEP))
 def test_row_bit_exact(ctx, name):
-    blob = fs.blob(name)
-    p, m = fe.plan(blob), fnet_ref.load(blob)
+    blob = fr.blob(name)
+    p, m = fpl.plan(blob), fh.load(blob)
     ctx.fnet_load(blob)
     info = ctx.fnet_info()
     assert (info["batch"], info["lds_bytes"], info["acts_floats"], info["n_layers"], info["n_out"]) == \
         (p["batch"], p["lds_bytes"], p["acts_floats"], p["n_layers"], p["n_out"])
     counts = _counts(p["batch"])
-    x = fs.inputs(name, counts[-1], p["in_n"])
+    x = fr.inputs(name, counts[-1], p["in_n"])
     acts = ctx.fnet_layers(x)
-    want, got = fe.layers_from(m, x, acts)
+    want, got = fh.layers_from(m, x, acts)
     prev = x
-    for i, (L, w, g) in enumerate(zip(fe.conv_records(m), want, got)):
+    for i, (L, w, g) in enumerate(zip(fh.conv_records(m), want, got)):
         diff = w != g
         assert np.array_equal(w, g), "%s layer %d: %d of %d outputs differ from the fmaf chain (first at %s: gpu %r, model %r)" % (
             name, i, diff.sum(), diff.size, np.argwhere(diff)[0], g[diff][0], w[diff][0])
-        w64, S = fnet_ref.layer_from(m, i, prev)
-        assert (np.abs(g - w64) <= fe.bound(L, S)).all(), (name, i)
+        w64, S = fh.layer_from(m, i, prev)
+        assert (np.abs(g - w64) <= fh.bound(L, S)).all(), (name, i)
         prev = g
     full = ctx.fnet(x)
     assert np.array_equal(full["logits"], want[-1])
@@ -57,11 +57,11 @@ def test_row_bit_exact(ctx, name):
         assert np.array_equal(a, acts[:n]), (name, n)
         r = ctx.fnet(x[:n])
         assert np.array_equal(r["logits"], want[-1][:n]), (name, n)
-        assert np.abs(r["probs"] - fnet_ref.softmax(r["logits"].astype(np.float64))).max() <= 1e-6
+        assert np.abs(r["probs"] - fh.softmax(r["logits"].astype(np.float64))).max() <= 1e-6
         assert np.array_equal(r["argmax"], np.argmax(r["probs"], axis=1))
         assert np.array_equal(r["probs"], full["probs"][:n]) and np.array_equal(r["argmax"], full["argmax"][:n])
     zero = ~want[-1].any(axis=1)
-    if fe.conv_records(m)[-1]["relu"] and zero.any():
+    if fh.conv_records(m)[-1]["relu"] and zero.any():
         assert not full["logits"][zero].any() and not full["argmax"][zero].any()
 
 
@@ -69,11 +69,11 @@ def test_refusals_keep_the_loaded_network(ctx):
     """Every refusal returns its code and leaves the network loaded before it answering bit-identically."""
     from edison_amd import _lib
     name = "pool22_trunc_hw"
-    ctx.fnet_load(fs.blob(name))
-    p = fe.plan(fs.blob(name))
-    x = fs.inputs(name, 3 * p["batch"] + 2, p["in_n"])
+    ctx.fnet_load(fr.blob(name))
+    p = fpl.plan(fr.blob(name))
+    x = fr.inputs(name, 3 * p["batch"] + 2, p["in_n"])
     before, acts = ctx.fnet(x), ctx.fnet_layers(x)
-    for ref, (build, code, note) in fs.REFUSALS.items():
+    for ref, (build, code, note) in fr.SWEEP_REFUSALS.items():
         with pytest.raises(_lib.EdisonError) as e:
             ctx.fnet_load(build())
         assert e.value.code == code, (ref, note)
@@ -86,10 +86,10 @@ def test_device_one_output_at_a_time(ctx):
     """edison_fnet_batch_dev on a torch stream with only logits, only probs or only argmax equals the host call."""
     torch = pytest.importorskip("torch")
     name = "inc3_oc64_oc65_s21"
-    ctx.fnet_load(fs.blob(name))
-    p = fe.plan(fs.blob(name))
+    ctx.fnet_load(fr.blob(name))
+    p = fpl.plan(fr.blob(name))
     n = 3 * p["batch"] + 2
-    x = fs.inputs(name, n, p["in_n"])
+    x = fr.inputs(name, n, p["in_n"])
     want = ctx.fnet(x)
     dev = torch.device("cuda", 0)
     xt = torch.from_numpy(x).to(dev)

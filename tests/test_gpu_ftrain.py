@@ -22,10 +22,9 @@ import pytest
 
 from conftest import GOLDEN
 
-import fnet_exact
-import fnet_pad
-import fnet_ref
-import fnet_sweep as fs
+import fnet_host as fh
+import fnet_plan as fpl
+import fnet_rows as fr
 import ftrain_ref
 import ftrain_rows
 from edison_amd import _lib, cube_import, train
@@ -42,7 +41,7 @@ EPS = 2.0 ** -24
 
 def check_plan(blob, info):
     """The trainer's batch and LDS bytes are the restated plan's (ftrain_ref.train_batch: ftrain_size_lds and the lowering loop)."""
-    p = fnet_exact.plan(blob)
+    p = fpl.plan(blob)
     assert info["batch"] == ftrain_ref.train_batch(p) and info["lds_bytes"] == ftrain_ref.train_lds_bytes(p, info["batch"]), (info, p["batch"])
     return p
 
@@ -84,7 +83,7 @@ def case(name):
             with open(FIXTURE, "rb") as f:
                 blob = f.read()
         else:
-            blob = fs.blob(name)
+            blob = fr.blob(name)
         bad, real = poisoned(blob)
         _CASES[name] = (cube_import.read_blob(blob), bad, real)
     return _CASES[name]
@@ -97,11 +96,11 @@ def data(name, model, n):
         rows = np.stack([g["net_in_" + str(k)] for k in g["names"]]).astype(np.float32)
         x = rows[np.arange(n) % len(rows)]
     elif name == "relu_logits":
-        assert fs.ROWS[name][0]["sets"] == ["neg", "n1"]
-        x = np.ascontiguousarray(fs.inputs(name, 2 * n, in_n)[0::2])      # its all-negative inputs: every ReLU logit is zero
+        assert fr.SWEEP[name][0]["sets"] == ["neg", "n1"]
+        x = np.ascontiguousarray(fr.inputs(name, 2 * n, in_n)[0::2])      # its all-negative inputs: every ReLU logit is zero
     else:
         x = ftrain_ref.inputs(name, n, in_n)
-    n_out = int(np.prod(fnet_ref.conv_records(model)[-1]["out"]))
+    n_out = int(np.prod(fh.conv_records(model)[-1]["out"]))
     return x, (np.arange(n) % n_out).astype(np.int32)
 
 
@@ -273,7 +272,7 @@ def test_a_network_the_step_kernel_takes_in_two_passes(ctx):
     with ctx.trainer() as tr:
         info = tr.info()
         check_plan(blob, info)
-        second = fs.STEP_PASS * info["grid"]
+        second = fr.STEP_PASS * info["grid"]
         assert info["w_floats"] == len(real) == 558928 and info["w_floats"] > second, "the packed weights fit one pass of the step kernel on this device"
         assert real[second:].sum() > 1000
         n = info["batch"] + 1
@@ -470,7 +469,7 @@ def test_set_weights_round_trip(ctx, fresh):
 def test_refusals_and_the_ignored_counter(ctx):
     torch = pytest.importorskip("torch")
     # a padded network, by name
-    ctx.fnet_load(fnet_pad.blob("sym3x3"))
+    ctx.fnet_load(fr.blob("sym3x3"))
     with pytest.raises(_lib.EdisonError) as e:
         ctx.trainer()
     assert e.value.code == _lib.E_NO_IMPL and "record 0" in str(e.value) and "pad" in str(e.value)
@@ -523,21 +522,21 @@ def test_refusals_and_the_ignored_counter(ctx):
 
 
 def test_a_network_that_fills_the_lds_trains_or_is_refused_by_name(ctx):
-    ctx.fnet_load(fs.blob("batch1_lds_max"))
+    ctx.fnet_load(fr.blob("batch1_lds_max"))
     try:
         with ctx.trainer() as tr:
             assert tr.info()["batch"] == 1 and tr.info()["lds_bytes"] <= 160 * 1024
-            check_plan(fs.blob("batch1_lds_max"), tr.info())
+            check_plan(fr.blob("batch1_lds_max"), tr.info())
     except _lib.EdisonError as e:
         assert e.code == _lib.E_NO_IMPL and "LDS" in str(e)
-        assert ftrain_ref.train_batch(fnet_exact.plan(fs.blob("batch1_lds_max"))) == 0
+        assert ftrain_ref.train_batch(fpl.plan(fr.blob("batch1_lds_max"))) == 0
 
 
 def test_fit_learns_the_synthetic_set(ctx):
     """40 Adam steps at batch 32, lr 0.01, seed 0 on three noisy class patterns: the train loss falls below half its first value and the
     accuracy reaches 0.9 (conditions the float64 replay meets with room: tests/test_fgrad_cpu.py), and the last loss is the replay's."""
     x, y = ftrain_rows.fit_set()
-    model = fs.model(ftrain_rows.FIT_ROW)
+    model = fr.model(ftrain_rows.FIT_ROW)
     ctx.fnet_load(cube_import.build_blob(model))
     kw = dict(epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=ftrain_rows.FIT_STEPS)
     with ctx.trainer() as tr:
@@ -554,7 +553,7 @@ def test_fit_learns_the_synthetic_set(ctx):
 def test_kws_train_then_kws_quantize(ctx, tmp_path):
     from edison_amd.kws import kws_quantize, kws_train
     x, y = ftrain_rows.fit_set()
-    model = fs.model(ftrain_rows.FIT_ROW)
+    model = fr.model(ftrain_rows.FIT_ROW)
     with open(tmp_path / "net.ednf", "wb") as f:
         f.write(cube_import.build_blob(model, ["a", "b", "c"]))
     np.save(tmp_path / "x.npy", x)
@@ -566,7 +565,7 @@ def test_kws_train_then_kws_quantize(ctx, tmp_path):
     assert "epoch   5" in out.getvalue() and "val_loss" in out.getvalue() and "after 15 steps" in out.getvalue()
     trained = cube_import.read_blob(blob)
     assert trained["keywords"] == ["a", "b", "c"]
-    assert not np.array_equal(fnet_ref.conv_records(trained)[0]["w"], fnet_ref.conv_records(model)[0]["w"])
+    assert not np.array_equal(fh.conv_records(trained)[0]["w"], fh.conv_records(model)[0]["w"])
     assert np.array_equal(ctx.fnet(x)["logits"], fnet_logits_of(ctx, blob, x))      # the context ran the trained weights already
     # kws quantize takes it: 11 frames x 6 coefficients are the network's 11 x 6 x 1 input
     rng = np.random.default_rng(8)

@@ -12,8 +12,8 @@ import io
 import numpy as np
 import pytest
 
-import fnet_ref
-import fnet_sweep
+import fnet_host
+import fnet_rows
 import ftrain_ref
 import ftrain_rows
 import test_gpu_ftrain as gt
@@ -186,7 +186,7 @@ def test_the_unbiased_flag_moves_the_variance_by_torchs_rule(ctx, name):
 def drawn(c, n, seed):
     rng = np.random.default_rng(seed)
     x = rng.normal(0, 1, (n, c["x"].shape[1])).astype(np.float32)
-    n_out = int(np.prod(fnet_ref.conv_records(c["model"])[-1]["out"]))
+    n_out = int(np.prod(fnet_host.conv_records(c["model"])[-1]["out"]))
     return x, (np.arange(n) % n_out).astype(np.int32)
 
 
@@ -196,7 +196,7 @@ def check_rows(ctx, name, tr, c, real, x, y):
     bn = dict(state=c["state0"])
     ref = ftrain_ref.loss_grad(model, x, y, bn=bn, detail=True)
     r32 = ftrain_ref.loss_grad(model, x, y, bn=bn, dtype=np.float32, detail=True)
-    for L, d32, d64 in zip(fnet_ref.conv_records(model), r32["detail"], ref["detail"]):       # the bound's precondition on these rows
+    for L, d32, d64 in zip(fnet_host.conv_records(model), r32["detail"], ref["detail"]):       # the bound's precondition on these rows
         assert np.array_equal(d32["first"], d64["first"]) and (not L["relu"] or np.array_equal(d32["y"] > 0, d64["y"] > 0))
     per = ftrain_ref.bounds(model, x, y, ref, bn=bn)[0]
     tr.grad(x, y)
@@ -415,8 +415,8 @@ def test_fit_with_batchnorm_and_dropout_follows_the_float64_replay(ctx):
     at batch 32, lr 0.01: the loss history is the float64 HostTrainer replay's to 1e-3 per epoch and the accuracy 1.0; validation runs
     the folded network."""
     x, y = ftrain_rows.fit_set()
-    model = fnet_sweep.model(ftrain_rows.FIT_ROW)
-    blob, _ = gt.poisoned(fnet_sweep.blob(ftrain_rows.FIT_ROW))
+    model = fnet_rows.model(ftrain_rows.FIT_ROW)
+    blob, _ = gt.poisoned(fnet_rows.blob(ftrain_rows.FIT_ROW))
     ctx.fnet_load(blob)
     bn, dropout = [1, 0], [(0.25, 1), 0]
     kw = dict(epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=ftrain_rows.FIT_STEPS, val=(x, y), callbacks=False)

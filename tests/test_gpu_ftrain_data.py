@@ -7,8 +7,8 @@ import io
 import numpy as np
 import pytest
 
-import fnet_ref
-import fnet_sweep as fs
+import fnet_host as fh
+import fnet_rows as fr
 import ftrain_ref
 import ftrain_rows
 from edison_amd import _lib, cube_import, train
@@ -174,7 +174,7 @@ def test_eval_sums_the_rows_in_double_in_a_fixed_order(ctx, n):
 # ---- fit_data is fit -------------------------------------------------------------------------------------------------------------------
 def two_conv_model():
     """A two-conv network on the synthetic set's 11 x 6 x 1 input, of test_gpu_ftrain_bn.py's kind: conv, pool (2, 1); conv; dense."""
-    recs = fs._records((11, 6, 1), [("conv", 4, (3, 3), (1, 1), (2, 1), 1), ("conv", 6, (2, 2), (1, 1), (1, 1), 1), ("dense", 3, 0)])
+    recs = fr._records((11, 6, 1), [("conv", 4, (3, 3), (1, 1), (2, 1), 1), ("conv", 6, (2, 2), (1, 1), (1, 1), 1), ("dense", 3, 0)], pad_keys=False)
     rng = np.random.default_rng(99)
     for L in recs:
         oc, (kh, kw), ic = L["out"][2], L["k"], L["inp"][2]
@@ -185,8 +185,8 @@ def two_conv_model():
 
 
 FIT_TRAINERS = {
-    "plain": (lambda: fs.model(ftrain_rows.FIT_ROW), dict()),
-    "dropout": (lambda: fs.model(ftrain_rows.FIT_ROW), dict(dropout=[0.25, 0], seed=3)),
+    "plain": (lambda: fr.model(ftrain_rows.FIT_ROW), dict()),
+    "dropout": (lambda: fr.model(ftrain_rows.FIT_ROW), dict(dropout=[0.25, 0], seed=3)),
     "batchnorm_dropout": (two_conv_model, dict(dropout=[(0.25, 1), 0.25, 0], seed=3, batchnorm=dict(has_bn=[1, 1, 0], max_rows=5))),
 }
 
@@ -195,7 +195,7 @@ FIT_TRAINERS = {
 def test_fit_data_is_fit(ctx, fresh, kind):
     make, targs = FIT_TRAINERS[kind]
     blob = cube_import.build_blob(make())
-    assert len(fnet_ref.conv_records(make())) == len(targs.get("dropout", [0, 0]))
+    assert len(fh.conv_records(make())) == len(targs.get("dropout", [0, 0]))
     x, y = ftrain_rows.fit_set()
     x, y, vx, vy = x[:23], y[:23], x[40:49], y[40:49]
     for extra in (dict(), dict(max_steps=7)):

@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 import fdrop_ref as fd
-import fnet_pad
+import fnet_plan
+import fnet_rows
 import ftrain_ref
 import ftrain_rows
 import test_gpu_ftrain as gt
@@ -122,7 +123,7 @@ def test_logits_loss_gradient_counter_eval_flag_and_zero_rates(ctx, name):
 
 def test_mid_pads_batch_runs_both_tile_instantiations_in_two_to_four_tiles(ctx):
     c, _ = loaded(ctx, "mid_pads_batch")
-    p = fnet_pad.plan(c["blob"])
+    p = fnet_plan.plan(c["blob"])
     with ctx.trainer(padded=True, dropout=c["dropout"], seed=c["seed"]) as tr:
         b = tr.info()["batch"]
         assert [L["pad"] for L in p["layers"]] == [False, True, True, False] and 2 <= -(-N // b) <= 4
@@ -216,7 +217,7 @@ def test_fit_follows_the_float64_replay_and_validates_without_dropout(ctx):
     validation entries those of a dropout-free evaluation of the same weights."""
     x, y = ftrain_rows.pad_fit_set()
     model = ftrain_rows.pad_model(ftrain_rows.PAD_FIT_ROW)
-    blob, _ = gt.poisoned(fnet_pad.blob(ftrain_rows.PAD_FIT_ROW))
+    blob, _ = gt.poisoned(fnet_rows.blob(ftrain_rows.PAD_FIT_ROW))
     ctx.fnet_load(blob)
     dropout = [(0.25, 1), 0]
     kw = dict(epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=ftrain_rows.FIT_STEPS, val=(x, y), callbacks=False)

@@ -13,7 +13,9 @@ import struct
 import numpy as np
 import pytest
 
-import fnet_pad
+import fnet_host
+import fnet_plan
+import fnet_rows
 import ftrain_ref
 import ftrain_rows
 import test_gpu_ftrain as gt
@@ -54,7 +56,7 @@ def case(name):
 
 
 def check_plan(blob, info):
-    p = fnet_pad.plan(blob)
+    p = fnet_plan.plan(blob)
     assert info["batch"] == ftrain_ref.train_batch(p) and info["lds_bytes"] == ftrain_ref.train_lds_bytes(p, info["batch"]), (info, p["batch"])
     return p
 
@@ -99,7 +101,7 @@ def test_logits_loss_gradient_padding_repeat_and_no_side_effect(ctx, name):
         assert b == LOWERED.get(name, p["batch"]), (name, b, p["batch"])
         assert any(L["pad"] for L in p["layers"])
         if name == "mid_pads_batch":                                        # a mixed network: the kernel runs both instantiations of the tile
-            assert [L["pad"] for L in p["layers"]] == [False, True, True, False] and ("pad_layer", 1) in fnet_pad.facts(name)
+            assert [L["pad"] for L in p["layers"]] == [False, True, True, False] and ("pad_layer", 1) in fnet_rows.pad_facts(name)
         ns = sorted({ftrain_rows.N_ROWS} | ({1, max(b - 1, 1), b, b + 1, 3 * b + 2} if name in ALL_N else set()))
         assert max(ns) <= ftrain_rows.n_max(name)                                    # the rows the CPU test holds the precondition on
         xs, ys = ftrain_rows.pad_data(name, max(ns))
@@ -205,8 +207,8 @@ def test_adam_steps_in_place_and_the_exported_network(ctx, fresh):
         exported = cube_import.build_blob(tr.model())
         assert struct.unpack_from("<i", exported, 4)[0] == 2                # a version-2 blob ...
         back = cube_import.read_blob(exported)
-        assert [fnet_pad.pads(L) for L in train.conv_records(back)] == [fnet_pad.pads(L) for L in train.conv_records(model)]   # ... with the pads
-        assert any(any(c) or any(q) for c, q in map(fnet_pad.pads, train.conv_records(back)))
+        assert [fnet_host.pads(L) for L in train.conv_records(back)] == [fnet_host.pads(L) for L in train.conv_records(model)]   # ... with the pads
+        assert any(any(c) or any(q) for c, q in map(fnet_host.pads, train.conv_records(back)))
         fresh.fnet_load(exported)
         again = fresh.fnet(x)
         assert same_bits(new["logits"], again["logits"])
@@ -220,7 +222,7 @@ def test_fit_learns_the_synthetic_set(ctx):
     the last loss is the replay's."""
     x, y = ftrain_rows.pad_fit_set()
     model = ftrain_rows.pad_model(ftrain_rows.PAD_FIT_ROW)
-    blob, _ = gt.poisoned(fnet_pad.blob(ftrain_rows.PAD_FIT_ROW))
+    blob, _ = gt.poisoned(fnet_rows.blob(ftrain_rows.PAD_FIT_ROW))
     ctx.fnet_load(blob)
     kw = dict(epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=ftrain_rows.FIT_STEPS)
     with ctx.trainer(padded=True) as tr:
@@ -254,7 +256,7 @@ def test_kws_train_then_kws_quantize(ctx, tmp_path):
     assert hist["loss"][-1] < hist["loss"][0]
     trained = cube_import.read_blob(blob)
     assert trained["keywords"] == keywords and struct.unpack_from("<i", blob, 4)[0] == 2
-    assert [fnet_pad.pads(L) for L in train.conv_records(trained)] == [fnet_pad.pads(L) for L in train.conv_records(model)]
+    assert [fnet_host.pads(L) for L in train.conv_records(trained)] == [fnet_host.pads(L) for L in train.conv_records(model)]
     assert not np.array_equal(train.conv_records(trained)[0]["w"], train.conv_records(model)[0]["w"])
     assert np.array_equal(ctx.fnet(x)["logits"], gt.fnet_logits_of(ctx, blob, x))      # the context ran the trained weights already
     g = KwsGeometry.from_config(net_input_scale=cfg.net_input_scale)
@@ -267,7 +269,7 @@ def test_kws_train_then_kws_quantize(ctx, tmp_path):
 
 def test_refusals_and_the_flag_on_an_unpadded_network(ctx):
     import ctypes
-    ctx.fnet_load(fnet_pad.blob("sym3x3"))
+    ctx.fnet_load(fnet_rows.blob("sym3x3"))
     h = ctypes.c_void_p()
     for flags in (2, 3, 0x80000000):
         assert ctx._L.edison_ftrain_create_ex(ctx._h, flags, ctypes.byref(h)) == _lib.E_ARGUMENT and not h.value

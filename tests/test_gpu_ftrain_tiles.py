@@ -17,8 +17,8 @@ import numpy as np
 import pytest
 
 import ftrain_ref
-import fnet_exact
-import fnet_ref
+import fnet_host
+import fnet_plan
 import test_gpu_ftrain as gt
 
 pytestmark = pytest.mark.gpu
@@ -44,7 +44,7 @@ def rows(name, model, n, exact=False):
     if key not in _ROWS or len(_ROWS[key][1]) < n:
         rng = np.random.default_rng(586 + sum(map(ord, name)))
         if exact and name != "cube_kws":
-            n_out = int(np.prod(fnet_ref.conv_records(model)[-1]["out"]))
+            n_out = int(np.prod(fnet_host.conv_records(model)[-1]["out"]))
             x, y = rng.normal(0, 1, (n, int(np.prod(model["in_shape"])))).astype(np.float32), (np.arange(n) % n_out).astype(np.int32)
         else:
             x, y = gt.data(name, model, n)
@@ -157,7 +157,7 @@ def test_ragged_tile_counts_against_float64(ctx, name, tail):
     with ctx.trainer() as tr:
         info = tr.info()
         b, G = info["batch"], info["grid"]
-        assert b == ftrain_ref.train_batch(fnet_exact.plan(blob)) and b >= 2
+        assert b == ftrain_ref.train_batch(fnet_plan.plan(blob)) and b >= 2
         assert b == 2 if name == "batch5" else b > 2                        # r = b - 1 is another case than r = 1
         r = 1 if tail == "1" else b - 1
         n = 2 * G * b + 2 * b + r

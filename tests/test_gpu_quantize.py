@@ -1,8 +1,8 @@
 """GPU tests (-m gpu) of calibrating and quantising a float32 network (edison_fcal_*, Context.calibrator / Context.quantize; DESIGN.md
-section 18). The reference is tests/fcal_ref.py, the host restatement of the statistic on fnet_exact's bit-exact f32 chain: absmax,
+section 18). The reference is stats in tests/fnet_host.py, the host restatement of the statistic on its bit-exact f32 chain: absmax,
 the exponent histogram and the count are integers, so every comparison is for equality.
 
-The sweep networks are rows of tests/fnet_sweep.py, altered so that each catches one mistake of a calibration kernel:
+The sweep networks are rows of tests/fnet_rows.py, altered so that each catches one mistake of a calibration kernel:
   pad_rows_big_bias   24 rows per utterance and a bias of 40: at odd utterance counts the last M tile has padding rows, which compute
                       utterance 0's first window again; counting them moves hist and count (absmax only repeats a value it has)
   pad_channels        17 and 4 channels with 1e6 in the blob's bias padding: a counted padding channel is 1e6
@@ -18,10 +18,9 @@ import pytest
 
 from conftest import GOLDEN
 
-import fcal_ref
-import fnet_exact as fe
-import fnet_ref
-import fnet_sweep as fs
+import fnet_host as fh
+import fnet_plan as fpl
+import fnet_rows as fr
 from edison_amd import cube_import
 from edison_amd import quantize as qz
 from oracle import net_ref
@@ -30,7 +29,7 @@ pytestmark = pytest.mark.gpu
 
 FIXTURE = os.path.join(GOLDEN, "cube_kws.ednf")
 with open(FIXTURE, "rb") as _f:
-    SHIPPED_BATCH = fe.plan(_f.read())["batch"]      # 7: the calibrator's too, the histogram fits in the plan's slack
+    SHIPPED_BATCH = fpl.plan(_f.read())["batch"]      # 7: the calibrator's too, the histogram fits in the plan's slack
 N_SHIPPED = 3 * SHIPPED_BATCH + 2
 
 
@@ -55,18 +54,18 @@ def _fixture_rows(golden):
 def shipped(golden):
     """The shipped network, 3 batch + 2 inputs (the five fixture rows, then scaled and perturbed copies) and the reference statistic of every
     single input: the statistic of any set of them is the merge."""
-    m = fnet_ref.load(FIXTURE)
+    m = fh.load(FIXTURE)
     rows = _fixture_rows(golden)
     rng = np.random.default_rng(18)
     extra = [rows[i % 5] * rng.uniform(0.25, 2.0) + rng.normal(0, 8.0, rows.shape[1]) for i in range(N_SHIPPED - 5)]
     x = np.concatenate([rows, np.array(extra)]).astype(np.float32)
-    return m, x, [fcal_ref.stats(m, x[i:i + 1]) for i in range(len(x))]
+    return m, x, [fh.stats(m, x[i:i + 1]) for i in range(len(x))]
 
 
 def _merged(per, lo, hi):
     s = per[lo]
     for t in per[lo + 1:hi]:
-        s = fcal_ref.merge(s, t)
+        s = fh.merge(s, t)
     return s
 
 
@@ -181,8 +180,8 @@ def _sweep_case(name):
         m = dict(in_shape=(8, 280, 1), layers=[L, dict(type=cube_import.T_SOFTMAX, inp=(1, 1, 16), out=(1, 1, 16))])
         return cube_import.build_blob(m), "pool41_tail", 1
     row = dict(pad_rows_big_bias="pool41_tail", pad_channels="pool22_trunc_hw", neg_bias_relu="pool21_trunc_h", trunc_pool_no_relu="pool12_trunc_w")[name]
-    m = fs.model(row)
-    first = fe.conv_records(m)[0]
+    m = fr.model(row)
+    first = fh.conv_records(m)[0]
     if name == "pad_rows_big_bias":
         first["b"] = (first["b"] + 40.0).astype(np.float32)
     if name == "neg_bias_relu":
@@ -192,7 +191,7 @@ def _sweep_case(name):
         assert first["relu"] == 0 and first["p"] == (1, 2)
     blob = cube_import.build_blob(m)
     if name == "pad_channels":
-        assert [L["out"][2] for L in fe.conv_records(m)] == [17, 4]
+        assert [L["out"][2] for L in fh.conv_records(m)] == [17, 4]
         blob = _patch_bias_padding(blob, 1.0e6)
     return blob, row, 16
 
@@ -204,7 +203,7 @@ def test_sweep_network_stats_bit_equal(ctx, name):
     ctx.fnet_load(blob)
     in_n = int(np.prod(m["in_shape"]))
     n = 3 * batch + 2
-    x = fs.inputs(row, n, in_n) if name != "batch1" else np.random.default_rng(4).normal(0, 1, (n, in_n)).astype(np.float32)
+    x = fr.inputs(row, n, in_n) if name != "batch1" else np.random.default_rng(4).normal(0, 1, (n, in_n)).astype(np.float32)
     if name == "neg_bias_relu":
         x = np.clip(x, -3, 3)                                # |acc| stays below the bias: every output is negative before ReLU
     with ctx.calibrator() as cal:
@@ -212,11 +211,11 @@ def test_sweep_network_stats_bit_equal(ctx, name):
         for k in sorted({1, batch + 1, n}):
             cal.reset()
             cal.add(x[:k])
-            got, want = cal.result(), fcal_ref.stats(m, x[:k])
+            got, want = cal.result(), fh.stats(m, x[:k])
             _same(got, want, "%s, n = %d" % (name, k))
             assert (got["hist"].sum(axis=1) == got["count"]).all()
     if name == "neg_bias_relu":
-        assert not fe.run(m, x)[0].any() and want["absmax"][1] > np.float32(20).view(np.uint32)
+        assert not fh.run(m, x)[0].any() and want["absmax"][1] > np.float32(20).view(np.uint32)
     if name == "pad_channels":
         assert (want["absmax"][1:].view(np.float32) < 1.0e5).all()
     if name == "trunc_pool_no_relu":
@@ -225,24 +224,24 @@ def test_sweep_network_stats_bit_equal(ctx, name):
 
 def test_a_network_that_fills_the_lds_is_refused(ctx):
     from edison_amd import _lib
-    ctx.fnet_load(fs.blob("batch1_lds_max"))
+    ctx.fnet_load(fr.blob("batch1_lds_max"))
     assert ctx.fnet_info()["lds_bytes"] + 4 * 257 > 160 * 1024
     with pytest.raises(_lib.EdisonError) as e:
         ctx.calibrator()
-    assert e.value.code == fe.E_NO_IMPL and "histogram" in str(e.value)
+    assert e.value.code == fpl.E_NO_IMPL and "histogram" in str(e.value)
 
 
 # ---- end to end -------------------------------------------------------------------------------------------------------------------
 def test_fixture_rows_end_to_end(ctx, golden):
     """GPU statistic -> blob: byte-equal to the blob of the host statistic; the int8 kernel on it equals net_ref; its argmax is the
     float network's."""
-    m, x = fnet_ref.load(FIXTURE), _fixture_rows(golden)
+    m, x = fh.load(FIXTURE), _fixture_rows(golden)
     ctx.fnet_load(FIXTURE)
     with ctx.calibrator() as cal:
         cal.add(x)
         stats = cal.result()
     blob, rep = qz.quantize(m, stats)
-    want_blob, want_rep = qz.quantize(m, fcal_ref.stats(m, x))
+    want_blob, want_rep = qz.quantize(m, fh.stats(m, x))
     assert blob == want_blob and rep["input"]["dec"] == -3
     xi = qz.quantize_input(x, rep["input"]["dec"])
     ctx.load_model_bytes(blob)
@@ -262,7 +261,7 @@ def test_context_quantize_audio_to_class(ctx, golden):
     blob, rep = ctx.quantize(audio, chunk=2, return_features=True)
     assert np.array_equal(rep["features"], ctx.kws_float(audio.ravel())["feat"])
     assert rep["float_argmax"].tolist() == [0, 7, 9, 8, 8]
-    want_blob, _ = qz.quantize(fnet_ref.load(FIXTURE), fcal_ref.stats(fnet_ref.load(FIXTURE), rep["features"]))
+    want_blob, _ = qz.quantize(fh.load(FIXTURE), fh.stats(fh.load(FIXTURE), rep["features"]))
     assert blob == want_blob
     assert rep["net_input_scale"] == 0.125
     ctx.load_model_bytes(blob)

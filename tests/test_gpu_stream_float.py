@@ -2,7 +2,7 @@
 kws_live.run(..., net=)). Networks: the reference's own (tests/golden/cube_kws.ednf) in the host flow and in the firmware's q15 flow, and
 three networks generated in X-CUBE-AI's format (tests/cube_synth.py) at geometries of test_gpu_kws_geom.GEOMS: kws_small (hop longer
 than the frame), square (frame longer than the hop) and odd_no_softmax's (the direct-DFT path). The reference answers are the batch call
-(Context.kws_float) on the zero-led recording, and tests/fnet_exact.py on windows built on the host; everything is compared bit for bit."""
+(Context.kws_float) on the zero-led recording, and tests/fnet_host.py on windows built on the host; everything is compared bit for bit."""
 import functools
 import os
 
@@ -14,7 +14,7 @@ from test_gpu_kws_geom import GEOMS, _geom, _same
 from test_gpu_stream_geom import _filter_ref, _recording, _tail
 
 import cube_synth
-import fnet_exact
+import fnet_host
 
 pytestmark = pytest.mark.gpu
 
@@ -47,7 +47,7 @@ def _import(sources):
 
 
 def _open(name):
-    """(context with the float network loaded, geometry, q15, the model dict of fnet_exact)."""
+    """(context with the float network loaded, geometry, q15, the model dict of fnet_host)."""
     from edison_amd import cube_import
     from edison_amd.context import Context
     blob, g = _blob(name)
@@ -132,7 +132,7 @@ def test_full_windows_equal_the_batch_call(built_lib, name):
 
 @pytest.mark.parametrize("name", NETS)
 def test_every_output_equals_the_exact_model(built_lib, name):
-    """Every output, the F - 1 partial windows included, equals tests/fnet_exact.py on windows built on the host from F - 1 zero rows and
+    """Every output, the F - 1 partial windows included, equals tests/fnet_host.py on windows built on the host from F - 1 zero rows and
     the batch call's feature rows (logits); probs and argmax equal the network alone (Context.fnet) on those windows."""
     c, g, q15, model = _open(name)
     try:
@@ -145,7 +145,7 @@ def test_every_output_equals_the_exact_model(built_lib, name):
         assert rows.shape == (K, nm)
         r = np.concatenate([np.zeros((F - 1, nm), np.float32), rows])
         win = np.ascontiguousarray(np.lib.stride_tricks.sliding_window_view(r, (F, nm))[:, 0].reshape(K, -1))
-        _same(got["logits"], fnet_exact.run(model, win)[-1], name + " logits against the fmaf chain")
+        _same(got["logits"], fnet_host.run(model, win)[-1], name + " logits against the fmaf chain")
         alone = c.fnet(win)
         _same(got["probs"], alone["probs"], name + " probs")
         _same(got["argmax"], alone["argmax"], name + " argmax")

@@ -1,8 +1,8 @@
 """CPU tests of quantising a float32 network to an int8 NNoM graph (edison_amd/quantize.py): the rule at its
 edges, every refusal, the assembler and the header emitter against the importer, and the shipped fixture network calibrated on the
-five fixture rows with the host restatement of the statistic (tests/fcal_ref.py).
+five fixture rows with the host restatement of the statistic (tests/fnet_host.py).
 
-The fixture table. Calibrated with fcal_ref's exact f32 chain, the shipped network gives input dec -3 and, per layer, w_dec / b_dec /
+The fixture table. Calibrated with fnet_host's exact f32 chain, the shipped network gives input dec -3 and, per layer, w_dec / b_dec /
 out_dec -> BIAS_LSHIFT / OUTPUT_RSHIFT:
     conv2d_1 13 / 8 / 3 -> 2 / 7     conv2d_2 8 / 7 / 2 -> 4 / 9     conv2d_3 8 / 5 / 3 -> 5 / 7     conv2d_4 9 / 5 / 3 -> 7 / 9
     dense_1   8 / 10 / 2 -> 1 / 9
@@ -17,9 +17,7 @@ import pytest
 
 from conftest import GOLDEN, ROOT
 
-import fcal_ref
-import fnet_exact
-import fnet_ref
+import fnet_host
 from edison_amd import cube_import, nnom_import
 from edison_amd import quantize as qz
 from oracle import net_ref
@@ -33,9 +31,9 @@ REF_W_DEC, REF_B_DEC, REF_OUT_DEC, REF_IN_DEC = [12, 8, 8, 9, 7], [8, 7, 5, 5, 1
 
 def _stats(values):
     """One statistic per entry of `values` (float arrays)."""
-    s = fcal_ref.empty(len(values) - 1)
+    s = fnet_host.empty(len(values) - 1)
     for i, v in enumerate(values):
-        s["absmax"][i], s["hist"][i], s["count"][i] = fcal_ref.of_values(np.asarray(v, np.float32))
+        s["absmax"][i], s["hist"][i], s["count"][i] = fnet_host.of_values(np.asarray(v, np.float32))
     return s
 
 
@@ -128,7 +126,7 @@ def test_refusals_name_the_layer():
         s = _stats(ok)
         s["count"][i] = 0
         refused(s, name, "count == 0")
-    refused(fcal_ref.empty(2), "input", "count == 0")
+    refused(fnet_host.empty(2), "input", "count == 0")
     # statistics of another network, unknown method, a shift too large
     refused(_stats(ok[:2]), "not those of this network")
     refused(_stats(ok), "KLD", method="kld")
@@ -145,7 +143,7 @@ def test_saturate_against_brute_force(saturate):
     rng = np.random.default_rng(int(saturate * 1000) + 3)
     for scale in (1.0, 37.0, 2.0 ** -9):
         v = (rng.standard_cauchy(20000) * scale).astype(np.float32)
-        _, hist, count = fcal_ref.of_values(v)
+        _, hist, count = fnet_host.of_values(v)
         k = qz.int_bits_saturate(hist, count, saturate)
         a = np.abs(v.astype(np.float64))
         at_or_above = lambda kk: int((a >= 2.0 ** kk).sum())
@@ -153,7 +151,7 @@ def test_saturate_against_brute_force(saturate):
         assert at_or_above(k - 1) > saturate * v.size
     # saturate = 0 keeps every value below 2^k: one more bit than max_min exactly at a power of two, the same elsewhere
     for v, k in (([1.0, 0.1], 1), ([0.99, 0.1], 0), ([1.01], 1), ([3.0], 2)):
-        _, hist, count = fcal_ref.of_values(np.array(v, np.float32))
+        _, hist, count = fnet_host.of_values(np.array(v, np.float32))
         assert qz.int_bits_saturate(hist, count, 0.0) == k
     # through quantize: a 1 % outlier 1000 times the rest no longer sets the format
     x = np.concatenate([rng.uniform(-1, 1, 990), [900.0] * 10]).astype(np.float32)
@@ -251,7 +249,7 @@ def test_build_blob_plain_switch_changes_nothing_for_its_callers():
 def test_header_round_trip_of_a_quantised_network():
     m = _two_layer_model()
     x = np.random.default_rng(8).normal(0, 2, (7, 30)).astype(np.float32)
-    blob, rep = qz.quantize(m, fcal_ref.stats(m, x))
+    blob, rep = qz.quantize(m, fnet_host.stats(m, x))
     h = qz.write_weights_h(rep["graph"], rep["in_shape"], rep["input"]["dec"])
     shape, layers = nnom_import.parse_weights_h(h)
     assert nnom_import.build_blob(shape, layers) == blob
@@ -263,7 +261,7 @@ def test_header_round_trip_of_a_quantised_network():
     # the int8 graph follows the float one on the calibration inputs: logits within a few output steps
     out_dec = rep["layers"][-1]["out_dec"]
     q = net_ref.run(blob, qz.quantize_input(x, rep["input"]["dec"]))["logits"].astype(np.float64) * 2.0 ** -out_dec
-    f = fnet_ref.run(m, x)["logits"]
+    f = fnet_host.run64(m, x)["logits"]
     assert np.abs(q - f).max() <= 0.25 * np.abs(f).max()
 
 
@@ -271,29 +269,30 @@ def test_header_round_trip_of_a_quantised_network():
 def test_fcal_ref_counts_what_the_network_uses():
     m = _two_layer_model()
     x = np.random.default_rng(9).normal(0, 1, (3, 30)).astype(np.float32)
-    s = fcal_ref.stats(m, x)
+    s = fnet_host.stats(m, x)
     # conv 3 x 3 on 6 x 5 -> 4 x 3, pool (2, 1) keeps all 4 rows; dense 4 outputs
     assert s["count"].tolist() == [3 * 30, 3 * 4 * 3 * 3, 3 * 4]
     assert (s["hist"].sum(axis=1) == s["count"]).all()
-    pre = fcal_ref.pre_activation(fnet_exact.conv_records(m)[0], x)
+    pre, live = fnet_host.pre_activation(fnet_host.conv_records(m)[0], x)
+    assert live.all()
     assert s["absmax"][1] == np.abs(pre).max().view(np.uint32)
-    assert (pre < 0).any() and np.abs(pre).max() >= np.abs(fnet_exact.run(m, x)[0]).max()     # before ReLU: the negative side counts
+    assert (pre < 0).any() and np.abs(pre).max() >= np.abs(fnet_host.run(m, x)[0]).max()     # before ReLU: the negative side counts
     # splitting the set changes nothing
-    a, b = fcal_ref.stats(m, x[:1]), fcal_ref.stats(m, x[1:])
-    merged = fcal_ref.merge(a, b)
+    a, b = fnet_host.stats(m, x[:1]), fnet_host.stats(m, x[1:])
+    merged = fnet_host.merge(a, b)
     assert all(np.array_equal(merged[k], s[k]) for k in s)
     # within f32 rounding of the float64 restatement
-    r = fnet_ref.run(m, x)
+    r = fnet_host.run64(m, x)
     assert np.float32(s["absmax"][2:3].view(np.float32)[0]) == pytest.approx(np.abs(r["logits"]).max(), rel=1e-5)
 
 
 # ---- the shipped network ----------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def shipped():
-    m = fnet_ref.load(FIXTURE)
+    m = fnet_host.load(FIXTURE)
     g = np.load(os.path.join(GOLDEN, "cube_golden.npz"))
     x = np.stack([g["net_in_" + str(n)] for n in g["names"]])
-    return m, x, [str(n) for n in g["names"]], fcal_ref.stats(m, x)
+    return m, x, [str(n) for n in g["names"]], fnet_host.stats(m, x)
 
 
 def test_shipped_network_report_equals_the_table(shipped):
@@ -314,7 +313,7 @@ def test_shipped_network_report_equals_the_table(shipped):
 def test_shipped_network_int8_argmax_equals_float(shipped):
     m, x, names, stats = shipped
     blob, rep = qz.quantize(m, stats)
-    f = fnet_ref.run(m, x)["argmax"]
+    f = fnet_host.run64(m, x)["argmax"]
     q = net_ref.run(blob, qz.quantize_input(x, rep["input"]["dec"]))
     assert f.tolist() == [0, 7, 9, 8, 8] and names[0] == "edison"
     assert q["argmax"].tolist() == f.tolist()

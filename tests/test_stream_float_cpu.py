@@ -1,6 +1,6 @@
 """CPU tests of the float-network stream's plumbing (no GPU): the C-ABI declares and the binding exposes edison_stream_float_*, the
 library builds the new sources, the two kernels on its hot path use no scratch, and the reference answer the GPU tests build on the host
-(test_gpu_stream_float: F - 1 zero rows, then one row per frame, windows oldest first, the network by tests/fnet_exact.py) agrees with
+(test_gpu_stream_float: F - 1 zero rows, then one row per frame, windows oldest first, the network by tests/fnet_host.py) agrees with
 the batch form wherever a window is full."""
 import os
 import re
@@ -137,10 +137,10 @@ def _float_rows(oracle_mod, g, z, starts):
 @pytest.mark.parametrize("name", ["kws_small", "square", "odd_no_softmax"])
 def test_host_reference_agrees_with_the_batch_form(oracle_mod, name):
     """The GPU tests' reference: one row per frame of the zero-led recording, F - 1 zero rows in front, windows oldest first, the network
-    by fnet_exact. For k >= F - 1 window k is the batch form's features of the utterance at (k - F + 1) * frame_step, and the exact model
+    by fnet_host. For k >= F - 1 window k is the batch form's features of the utterance at (k - F + 1) * frame_step, and the exact model
     gives the same logits on it; window 0 is F - 1 zero rows and frame 0's row."""
     import cube_synth
-    import fnet_exact
+    import fnet_host
     from edison_amd import cube_import
     from test_gpu_kws_geom import GEOMS, _geom
     from test_gpu_stream_float import SYNTH, _import
@@ -159,4 +159,4 @@ def test_host_reference_agrees_with_the_batch_form(oracle_mod, name):
     assert np.array_equal(win[F - 1:], batch)
     assert not win[0, :(F - 1) * nm].any() and np.array_equal(win[0, (F - 1) * nm:], rows[0])
     model = cube_import.read_blob(_import(cube_synth.cube_sources((F, nm, 1), SYNTH, seed=len(name))))
-    assert np.array_equal(fnet_exact.run(model, win[F - 1:])[-1], fnet_exact.run(model, batch)[-1])
+    assert np.array_equal(fnet_host.run(model, win[F - 1:])[-1], fnet_host.run(model, batch)[-1])

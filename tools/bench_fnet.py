@@ -44,26 +44,26 @@ def timed(fn, steps, warmup):
 
 
 def accuracy(c, model, golden):
-    import fnet_ref
+    import fnet_host
     from test_gpu_fnet import SOURCES, _audio, _inputs
     x = _inputs(golden)
     acts = c.fnet_layers(x).astype(np.float64)
     prev, off, worst = np.asarray(x, np.float64), 0, []
-    for i, L in enumerate(fnet_ref.conv_records(model)):
+    for i, L in enumerate(fnet_host.conv_records(model)):
         n = int(np.prod(L["out"]))
-        want, S = fnet_ref.layer_from(model, i, prev)
+        want, S = fnet_host.layer_from(model, i, prev)
         got = acts[:, off:off + n]
         worst.append(round(float((np.abs(got - want) / (1e-7 * S + 1e-300)).max()), 3))
         prev, off = got, off + n
     r = c.fnet(x)
-    ref = fnet_ref.run(model, x)
+    ref = fnet_host.run64(model, x)
     a = _audio(golden)
     h = c.kws_float(a)
     flips = [int((h["feat"][j] != golden["net_in_" + s]).sum()) for j, s in enumerate(SOURCES)]
     top = np.sort(ref["logits"], axis=1)
     return dict(layer_err_over_1e7S=worst, logits_vs_f64_chain=float(np.abs(r["logits"] - ref["logits"]).max()),
                 probs_vs_f64_chain=float(np.abs(r["probs"] - ref["probs"]).max()),
-                probs_vs_f64_softmax_of_logits=float(np.abs(r["probs"] - fnet_ref.softmax(r["logits"].astype(np.float64))).max()),
+                probs_vs_f64_softmax_of_logits=float(np.abs(r["probs"] - fnet_host.softmax(r["logits"].astype(np.float64))).max()),
                 argmax_diff=int((r["argmax"] != ref["argmax"]).sum()), min_top2_margin=float((top[:, -1] - top[:, -2]).min()),
                 host_feature_flips=flips, edison_p=float(h["probs"][0, 0]), edison_p_fixture=float(golden["probs_edison"][0]))
 
@@ -75,7 +75,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     args = ap.parse_args()
     import torch
-    import fnet_ref
+    import fnet_host
     from edison_amd.context import Context
     from edison_amd.kws.geometry import KwsGeometry
     dev = torch.device("cuda", 0)
@@ -85,7 +85,7 @@ def main():
     c.fnet_load(fixture)
     board = c.device_info()["name"]
     info = c.fnet_info()
-    print(json.dumps(dict(board=board, what="accuracy", **accuracy(c, fnet_ref.load(fixture), golden))), flush=True)
+    print(json.dumps(dict(board=board, what="accuracy", **accuracy(c, fnet_host.load(fixture), golden))), flush=True)
 
     n = args.utts
     gen = torch.Generator(device=dev)

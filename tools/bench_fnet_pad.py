@@ -30,12 +30,11 @@ from bench_fnet import timed  # noqa: E402
 
 def macs_per_utt(model):
     """Real multiply-adds of one utterance: per conv output, its taps inside the image x in_c x out_c."""
-    import fnet_exact
-    import fnet_pad
+    import fnet_host
     total = 0
-    for L in fnet_exact.conv_records(model):
-        (ih, iw, ic), (kh, kw), (sh, sw), (c, _) = L["inp"], L["k"], L["s"], fnet_pad.pads(L)
-        ch, cw = fnet_pad.conv_map(L)
+    for L in fnet_host.conv_records(model):
+        (ih, iw, ic), (kh, kw), (sh, sw), (c, _) = L["inp"], L["k"], L["s"], fnet_host.pads(L)
+        ch, cw = fnet_host.conv_map(L)
         ty = sum(sum(0 <= y * sh - c[0] + ky < ih for ky in range(kh)) for y in range(ch))
         tx = sum(sum(0 <= x * sw - c[1] + kx < iw for kx in range(kw)) for x in range(cw))
         total += ty * tx * ic * L["out"][2]
@@ -44,14 +43,14 @@ def macs_per_utt(model):
 
 def unpadded_grown(m):
     """m without pads, its input grown to the smallest at which the last conv before the dense layers keeps its output shape."""
-    import fnet_pad
+    import fnet_rows
     from edison_amd import cube_import
     recs = [L for L in m["layers"] if L["type"] == cube_import.T_CONV]
     convs = [L for L in recs if tuple(L["k"]) != tuple(L["inp"][:2]) or any(L["cpad"])]
     h, w = convs[-1]["out"][:2]
     for L in reversed(convs):
         h, w = (h * L["p"][0] - 1) * L["s"][0] + L["k"][0], (w * L["p"][1] - 1) * L["s"][1] + L["k"][1]
-    out = fnet_pad.unpadded(dict(m, in_shape=(h, w, m["in_shape"][2])))
+    out = fnet_rows.unpadded(dict(m, in_shape=(h, w, m["in_shape"][2])))
     assert out is not None and tuple(out["layers"][len(convs) - 1]["out"]) == tuple(convs[-1]["out"])
     return out
 
@@ -63,12 +62,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     args = ap.parse_args()
     import torch
-    import fnet_pad
+    import fnet_rows
     from edison_amd import cube_import
     from edison_amd.context import Context
     dev = torch.device("cuda", 0)
-    padded = fnet_pad.model("medium_embedding_conv")
-    nets = [("padded", padded), ("unpadded", fnet_pad.unpadded(padded) or unpadded_grown(padded))]
+    padded = fnet_rows.model("medium_embedding_conv")
+    nets = [("padded", padded), ("unpadded", fnet_rows.unpadded(padded) or unpadded_grown(padded))]
     c = Context(0, model_path=None)
     board = c.device_info()["name"]
     n = args.utts
