@@ -10,7 +10,10 @@ tests/test_gpu_geom_sweep.py runs every row against the float64 oracle, tools/fu
 the three LDS regions r0 / r1 / r2 of a team's slice (in doubles) and the team (a wavefront while the slice is at most 20 KiB, the
 256-thread workgroup beyond). The note of each row names the path that plan gives it; the CPU test checks the notes against it.
 
-Every row keeps frame_count x num_mfcc <= 32 640, the largest graph input (ED_NET_MAX_LDS / 2)."""
+Every row keeps frame_count x num_mfcc <= 32 640, the largest graph input (ED_NET_MAX_LDS / 2).
+
+Also what the geometry tests and tools share besides the rows: GEOMS (the committed alt_models graphs' geometries), geom, header and the
+signal mix `signals`."""
 import functools
 import os
 
@@ -91,6 +94,60 @@ ROWS = {
     "count_lt_fit": (dict(variant="A", frame_len=400, frame_step=160, n_samples=16000, frame_count_=50, mel_nbins=40, first_mfcc=1, num_mfcc=13),
                      "wave, packed M=200 (4, 2, 5, 5), an explicit frame_count below the 98 that fit"),
 }
+
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+# committed alt_models graph -> the geometry it is run at (its input is frame_count x num_mfcc features)
+GEOMS = {
+    "kws_small": dict(variant="B", use_log=True, frame_len=512, frame_step=1024, n_samples=32000, mel_nbins=20, first_mfcc=0, num_mfcc=13),
+    "same_stride": dict(variant="B", frame_len=800, frame_step=800, n_samples=16000, mel_nbins=40, first_mfcc=1, num_mfcc=12,
+                        lower_edge_hertz=20.0, upper_edge_hertz=4000.0, mel_mtx_scale=64.0),
+    "square": dict(variant="A", frame_len=480, frame_step=240, n_samples=15600, mel_nbins=24, first_mfcc=0, num_mfcc=16),
+    "even_same": dict(variant="B", frame_len=1000, frame_step=500, n_samples=8500, mel_nbins=32, first_mfcc=0, num_mfcc=20, net_input_scale=0.5),
+    "odd_no_softmax": dict(variant="B", frame_len=441, frame_step=441, n_samples=11907, mel_nbins=16, first_mfcc=0, num_mfcc=7),
+}
+
+
+def geom(**kw):
+    """A KwsGeometry from audio/config.py's with these fields changed (variant "A" / "B" by name)."""
+    from edison_amd import _lib
+    from edison_amd.kws.geometry import KwsGeometry
+    kw = dict(kw)
+    if kw.get("variant") in ("A", "B"):
+        kw["variant"] = _lib.MFCC_A if kw["variant"] == "A" else _lib.MFCC_B
+    return KwsGeometry.from_config(**kw)
+
+
+def header(name):
+    return os.path.join(GOLDEN, "alt_models", name + ".h")
+
+
+def signals(n_utt, n_samples, seed):
+    """int16 [n_utt][n_samples]: silence, low-level noise, tones, clipping-loud noise and the reference's `edison` utterance (at a random
+    place and gain), in turn."""
+    rng = np.random.default_rng(seed)
+    edison = np.load(os.path.join(GOLDEN, "mfcc_geom_golden.npz"))["in_edison"].astype(np.float64)
+    t = np.arange(n_samples) / 16000.0
+    out = np.zeros((n_utt, n_samples), np.int16)
+    for u in range(n_utt):
+        kind = u % 5
+        if kind == 0:
+            x = np.zeros(n_samples)
+        elif kind == 1:
+            x = rng.normal(0, rng.uniform(0.5, 30.0), n_samples)
+        elif kind == 2:
+            f = rng.uniform(50.0, 7900.0, 2)
+            x = rng.uniform(100, 20000) * np.cos(2 * np.pi * f[0] * t + rng.random() * 6.3) + rng.uniform(0, 3000) * np.cos(2 * np.pi * f[1] * t)
+        elif kind == 3:
+            x = rng.normal(0, rng.uniform(20000, 60000), n_samples)
+        else:
+            x = rng.normal(0, 10.0, n_samples)
+            e = edison[:n_samples] * rng.uniform(0.3, 4.0)
+            at = int(rng.integers(0, max(1, n_samples - e.shape[0] + 1)))
+            x[at:at + e.shape[0]] += e
+        out[u] = np.clip(np.rint(x), -32768, 32767).astype(np.int16)
+    return out
 
 
 def geometry(name, **changes):
@@ -177,7 +234,7 @@ def row_data(name):
     from oracle import oracle
     oracle.build()
     g = geometry(name)
-    audio = signals(name, g, min_frames(name))
+    audio = row_signals(name, g, min_frames(name))
     y = oracle_mfcc(oracle, audio, g)
     g = replace(g, net_input_scale=sensitive_scale(y))
     return g, audio, y, oracle_feat(oracle, y, g)
@@ -216,18 +273,13 @@ def dense_graph(g, seed=0, n_out=4):
     return nnom_import.build_blob((g.frame_count, g.num_mfcc, 1), [layer])
 
 
-def signals(name, g, frames, seed=0):
-    """int16 [n_utt][n_samples]: the signal mix of tests/test_gpu_kws_geom.py (silence, quiet noise, tones, clipping-loud noise, the
-    `edison` utterance in noise, in turn), enough utterances for `frames` frames, each utterance brought to an RMS level between
-    1 500 and 6 000 (silence stays silence). The mix spans four decades of level; at one net_input_scale per row the quiet classes
-    would round to int8 zero and test nothing."""
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    if here not in sys.path:
-        sys.path.insert(0, here)
-    from test_gpu_kws_geom import _signals
+def row_signals(name, g, frames, seed=0):
+    """int16 [n_utt][n_samples]: the `signals` mix (silence, quiet noise, tones, clipping-loud noise, the `edison` utterance in noise,
+    in turn), enough utterances for `frames` frames, each utterance brought to an RMS level between 1 500 and 6 000 (silence stays
+    silence). The mix spans four decades of level; at one net_input_scale per row the quiet classes would round to int8 zero and test
+    nothing."""
     s = 1000 + 7 * seed + sorted(ROWS).index(name)
-    x = _signals(n_utterances(g, frames), g.n_samples, s).astype(np.float64)
+    x = signals(n_utterances(g, frames), g.n_samples, s).astype(np.float64)
     rms = np.sqrt(np.mean(x * x, axis=1))
     level = 3000.0 * 2.0 ** np.random.default_rng(s).uniform(-1.0, 1.0, x.shape[0])
     gain = np.where(rms > 0, level / np.maximum(rms, 1e-30), 0.0)

@@ -9,13 +9,13 @@ S_m.frames_seen; for m outside P_k the rows hold the fill. Every comparison is b
 tolerance. A stream that has not been pushed yet has no outputs to copy a machine from: its machine is edison_fsm_init's, which is what
 the stream starts its first push with."""
 import ctypes
-import functools
 
 import numpy as np
 import pytest
 
-from test_gpu_kws_geom import GEOMS, _geom
-from test_gpu_stream_bank import _recordings
+import stream_drive as sd
+from geom_sweep import GEOMS
+from stream_drive import HOST, DEV, DEV_NO_OUT, recordings, same, schedule, start_machine
 
 pytestmark = pytest.mark.gpu
 
@@ -30,122 +30,22 @@ FLOAT = {"shipped_q15": ("shipped_q15", None), "even_same": ("synth", GEOMS["eve
 CASES = [("int8", n) for n in INT8] + [("float", n) for n in FLOAT]
 
 
-class _Kind:
-    """One bank type and its single stream behind the same calls."""
-
-    def __init__(self, kind, name):
-        self.kind, self.name = kind, name
-        self.second = "softmax" if kind == "int8" else "probs"
-        self.who = "stream_bank" if kind == "int8" else "float_bank"
-        self.q15 = name == "shipped_q15"
-
-    def open(self):
-        """(context with the model loaded, geometry)."""
-        from edison_amd.context import Context
-        if self.kind == "int8":
-            from test_gpu_kws_geom import _header
-            model, geom = INT8[self.name]
-            if model == "shipped":
-                c, g = Context(0), _geom()
-            else:
-                c, g = Context(0, model_path=None), _geom(**geom)
-                c.load_weights_h(_header(model))
-            info = c.net_info()
-            self.n_out, self.has_second, self.dtype = int(info["n_out"]), bool(info["has_softmax"]), np.int8
-        else:
-            blob, g = _float_blob(self.name)
-            c = Context(0, model_path=None)
-            c.fnet_load(blob)
-            self.n_out, self.has_second, self.dtype = int(c.fnet_info()["n_out"]), True, np.float32
-        self.fsm = self.n_out == 10
-        return c, g
-
-    def stream(self, c, g, chunk):
-        from edison_amd.stream import FloatStream, GeomStream
-        if self.kind == "int8":
-            return GeomStream(c, g, chunk_frames=chunk, output_filter=True, fsm=self.fsm)
-        return FloatStream(c, g, q15=self.q15, chunk_frames=chunk, output_filter=True, fsm=self.fsm)
-
-    def bank(self, c, g, n_mics, chunk):
-        from edison_amd.stream import FloatBank, StreamBank
-        if self.kind == "int8":
-            return StreamBank(c, g, n_mics, chunk_frames=chunk, output_filter=True, fsm=self.fsm)
-        return FloatBank(c, n_mics, g, q15=self.q15, chunk_frames=chunk, output_filter=True, fsm=self.fsm)
-
-    def keys(self):
-        return ["logits"] + ([self.second] if self.has_second else []) + ["argmax", "filtered", "likely", "spotted"] + (["fsm_states"] if self.fsm else [])
+def _open(kind, name):
+    """(one bank type and its single stream behind the same calls, context with the model loaded, geometry)."""
+    K = sd.Kind(kind)
+    model, gk = (INT8 if kind == "int8" else FLOAT)[name]
+    c, g = K.open(name if model == "synth" else model, gk, SYNTH10)
+    return K, c, g
 
 
-@functools.lru_cache(maxsize=None)
-def _float_blob(name):
-    import cube_synth
-    from test_gpu_stream_float import _blob, _import
-    net, geom = FLOAT[name]
-    if net != "synth":
-        return _blob(net)
-    g = _geom(**geom)
-    return _import(cube_synth.cube_sources((g.frame_count, g.num_mfcc, 1), SYNTH10, seed=len(name))), g
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def _same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    bad = np.argwhere(_bits(got) != _bits(want))
-    assert bad.shape[0] == 0, "%s: %d of %d differ, first at %s: %r != %r" % (what, bad.shape[0], got.size, tuple(bad[0]), got[tuple(bad[0])],
-                                                                             want[tuple(bad[0])])
-
-
-def _torch_stream(c):
-    import torch
-    dev = torch.device("cuda", c.device)
-    c.use_torch_stream(torch.cuda.current_stream(dev))
-    return torch, dev
-
-
-def _tensors(K, torch, dev, shape, n):
-    """Device tensors for the outputs of a push of n frames: shape = () for a stream, (n_mics,) for a bank."""
-    tdt = torch.int8 if K.dtype == np.int8 else torch.float32
-    z = lambda tail, dt: torch.zeros((n,) + shape + tail, dtype=dt, device=dev)
-    o = dict(logits=z((K.n_out,), tdt), argmax=z((), torch.int32), filtered=z((K.n_out,), torch.float32), likely=z((), torch.int32),
-             spotted=z((), torch.int32))
-    if K.has_second:
-        o[K.second] = z((K.n_out,), tdt)
-    if K.fsm:
-        o["fsm_states"] = z((), torch.int32)
-    return o
-
-
-def _raw(f):
-    return (f.state, f.hot_timeout_ms, f.wake_idx, f.loc_idx, f.val_idx, f.last_loc, f.last_val, f.commands)
-
-
-def _start_machine():
-    from edison_amd import _lib
-    f = _lib.Fsm()
-    _lib.lib().edison_fsm_init(ctypes.byref(f))
-    return _raw(f)
+def _bank(K, c, g, n_mics, chunk):
+    return K.bank(c, g, n_mics, chunk, output_filter=True, fsm=K.fsm)
 
 
 # ---- the schedule ------------------------------------------------------------------------------------------------------------------
 def _frames(chunk, pushes, ragged):
     """Frames per push: full pushes, with ragged ones of 1 .. chunk - 1 frames in between where asked for."""
-    return [chunk if not ragged or chunk == 1 or i % 4 != 2 else 1 + (i // 4) % (chunk - 1) for i in range(pushes)]
-
-
-def _wraps(frames, chunk, slots=8):
-    """The pushes before which the core moves the history to the front (make_room: pos + n > slots * chunk)."""
-    pos, at = 0, []
-    for k, n in enumerate(frames):
-        if pos + n > slots * chunk and pos != 0:
-            at.append(k)
-            pos = 0
-        pos += n
-    return at
+    return schedule(chunk, pushes, sd.by_round if ragged else None)
 
 
 def _schedule(F, chunk, ragged, n_mics=M, seed=5):
@@ -158,7 +58,7 @@ def _schedule(F, chunk, ragged, n_mics=M, seed=5):
     long_gap = -(-(F + 1) // chunk) + 4                  # pushes that hold more than F frames even if some are ragged
     pushes = max(30, 6 + long_gap + 6)
     frames = _frames(chunk, pushes, ragged)
-    wraps = _wraps(frames, chunk)
+    wraps = sd.wraps(frames, chunk)
     assert len(wraps) >= 3, wraps
     rng = np.random.default_rng(seed)
     masks = (rng.random((pushes, n_mics)) < 0.6).astype(np.uint8)
@@ -186,40 +86,30 @@ def _present(p, m):
 def _reference(K, c, g, x, chunk, sched, resets=None):
     """Per microphone m, per push k: None where m is absent, else S_m's outputs of that push (dict of [n_k][..]); the machine and
     S_m.frames_seen after every push. resets {k: [m, ..]}: before push k these microphones start over as new streams (reset_mic)."""
-    torch, dev = _torch_stream(c)
     resets = resets or {}
+    on = dict(output_filter=True, fsm=K.fsm)
     outs, snaps, counts = [], [], []
-    try:
-        for m in range(x.shape[0]):
-            s = K.stream(c, g, chunk)
-            xt = torch.from_numpy(x[m]).to(dev)
-            o_m, s_m, c_m = [], [], []
-            snap, k0 = _start_machine(), 0
-            for k, (n, p) in enumerate(sched):
-                if m in resets.get(k, ()):
-                    s.close()
-                    s, snap = K.stream(c, g, chunk), _start_machine()
-                if _present(p, m):
-                    o = _tensors(K, torch, dev, (), n)
-                    s.push_t(xt[k0 * s.hop:(k0 + n) * s.hop], n_frames=None if n == chunk else n, logits=o["logits"], argmax=o["argmax"],
-                             filtered=o["filtered"], likely=o["likely"], spotted=o["spotted"], **{K.second: o.get(K.second)})
-                    if K.fsm:
-                        c._check(s._c("fsm_dev")(s._h, ctypes.c_void_p(o["fsm_states"].data_ptr())))
-                        c._check(s._c("fsm")(s._h, ctypes.byref(s._fsm), None))
-                        snap = _raw(s._fsm)
-                    o_m.append({key: v.cpu().numpy() for key, v in o.items()})
-                else:
-                    o_m.append(None)
-                s_m.append(snap)
-                c_m.append(s.frames_seen)
-                k0 += n
-            s.close()
-            outs.append(o_m)
-            snaps.append(s_m)
-            counts.append(c_m)
-        torch.cuda.synchronize(dev)
-    finally:
-        c.use_own_stream()
+    for m in range(x.shape[0]):
+        s = K.stream(c, g, chunk, **on)
+        o_m, s_m, c_m = [], [], []
+        snap, k0 = start_machine(), 0
+        for k, (n, p) in enumerate(sched):
+            if m in resets.get(k, ()):
+                s.close()
+                s, snap = K.stream(c, g, chunk, **on), start_machine()
+            if _present(p, m):
+                o, machine = sd.drive_stream(K, c, g, x[m, k0 * s.hop:(k0 + n) * s.hop], [n], chunk=chunk, stream=s, filt=True, fsm=K.fsm)
+                snap = machine if K.fsm else snap
+                o_m.append({key: v for key, v in o.items() if v is not None})
+            else:
+                o_m.append(None)
+            s_m.append(snap)
+            c_m.append(s.frames_seen)
+            k0 += n
+        s.close()
+        outs.append(o_m)
+        snaps.append(s_m)
+        counts.append(c_m)
     return outs, snaps, counts
 
 
@@ -236,33 +126,13 @@ def _garbage(x, sched, hop, seed=11):
 
 
 # ---- the bank ----------------------------------------------------------------------------------------------------------------------
-HOST, DEV, DEV_NO_OUT = "host", "device", "device, no output pointers"
-
-
 def _bank_push(K, c, b, y, k0, n, p, mode):
     """One push of the bank in `mode`. Returns the dict of this push's outputs [n][n_mics][..] (host arrays), `fsm` among them."""
-    seg = y[:, k0 * b.hop:(k0 + n) * b.hop]
-    if mode == HOST:
-        assert n == b.chunk
-        out = b.push(seg, present=p)
-        assert (out["present"] is None) if p is None else np.array_equal(out["present"], p)
-        got = {k: out[k] for k in K.keys()}
-    else:
-        torch, dev = _torch_stream(c)
-        try:
-            o = _tensors(K, torch, dev, (b.n_mics,), n)
-            pt = None if p is None else torch.from_numpy(p).to(dev)
-            kw = dict(filtered=o["filtered"], likely=o["likely"], spotted=o["spotted"], fsm_states=o.get("fsm_states"))
-            if mode == DEV:
-                kw.update(logits=o["logits"], argmax=o["argmax"], **{K.second: o.get(K.second)})
-            b.push_t(torch.from_numpy(np.ascontiguousarray(seg)).to(dev), n_frames=None if n == b.chunk and p is None else n, present=pt, **kw)
-            torch.cuda.synchronize(dev)
-            got = {k: o[k].cpu().numpy() for k in K.keys() if mode == DEV or k in ("filtered", "likely", "spotted", "fsm_states")}
-        finally:
-            c.use_own_stream()
+    got, machines = sd.drive_bank(K, c, b.geometry, y[:, k0 * b.hop:(k0 + n) * b.hop], [n], chunk=b.chunk, bank=b, filt=True, fsm=K.fsm,
+                                  present=[p], mode=mode)
+    got = {k: v for k, v in got.items() if v is not None}
     if K.fsm:
-        c._check(b._c("fsm")(b._h, ctypes.byref(b._fsms), None))
-        got["fsm"] = [_raw(f) for f in b._fsms]
+        got["fsm"] = machines
     return got
 
 
@@ -271,18 +141,18 @@ def _check_push(K, got, ref, k, n, p, n_mics, what):
     outs, snaps, _ = ref
     for m in range(n_mics):
         w = "%s push %d microphone %d " % (what, k, m)
-        before = snaps[m][k - 1] if k else _start_machine()
+        before = snaps[m][k - 1] if k else start_machine()
         for key, a in got.items():
             if key == "fsm":
                 assert a[m] == snaps[m][k], (w + "machine", a[m], snaps[m][k])
             elif _present(p, m):
-                _same(a[:, m], outs[m][k][key], w + key)
+                same(a[:, m], outs[m][k][key], w + key)
             elif key == "fsm_states":
-                _same(a[:, m], np.full(n, before[0], np.int32), w + "fill of fsm_states")
+                same(a[:, m], np.full(n, before[0], np.int32), w + "fill of fsm_states")
             elif key in ("argmax", "likely", "spotted"):
-                _same(a[:, m], np.full(n, -1, np.int32), w + "fill of " + key)
+                same(a[:, m], np.full(n, -1, np.int32), w + "fill of " + key)
             else:
-                _same(a[:, m], np.zeros((n, K.n_out), a.dtype), w + "fill of " + key)   # +0.0f: zero bytes
+                same(a[:, m], np.zeros((n, K.n_out), a.dtype), w + "fill of " + key)   # +0.0f: zero bytes
         if not _present(p, m) and K.fsm:
             assert snaps[m][k] == before
 
@@ -309,16 +179,15 @@ def test_masked_pushes_equal_streams_pushed_when_present(built_lib, kind, name, 
     """Filter and (10 outputs) machine on. Four phases on one bank with a reset in between, so that reset is tested with them: host
     pushes, device pushes into the caller's tensors, device pushes without output pointers, and the three alternating. The device
     phases of chunk 3 have ragged pushes; host pushes are always whole."""
-    K = _Kind(kind, name)
-    c, g = K.open()
+    K, c, g = _open(kind, name)
     try:
         F = g.frame_count
         assert F - 1 > chunk
         full, ragged = _schedule(F, chunk, False), _schedule(F, chunk, True)
-        x = _recordings(g, M, sum(n for n, _ in full), 300 + chunk)      # the ragged schedule has fewer frames
+        x = recordings(g, M, sum(n for n, _ in full), 300 + chunk)      # the ragged schedule has fewer frames
         ref_full = _reference(K, c, g, x, chunk, full)
         ref_ragged = ref_full if chunk == 1 else _reference(K, c, g, x, chunk, ragged)
-        b = K.bank(c, g, M, chunk)
+        b = _bank(K, c, g, M, chunk)
         assert np.array_equal(b.frames_seen_mics(), np.zeros(M, np.int64))
         for sched, ref, modes in ((full, ref_full, [HOST]), (ragged, ref_ragged, [DEV]), (ragged, ref_ragged, [DEV_NO_OUT]),
                                  (full, ref_full, [HOST, DEV, DEV_NO_OUT])):
@@ -335,14 +204,13 @@ def test_masked_pushes_equal_streams_pushed_when_present(built_lib, kind, name, 
 def test_all_ones_mask_equals_the_maskless_push(built_lib, kind, name):
     """Two banks on the same samples, 20 pushes of chunk 3 with ragged ones (two wraps): one with an all-ones mask in every push, one
     without a mask. Host and device pushes."""
-    K = _Kind(kind, name)
-    c, g = K.open()
+    K, c, g = _open(kind, name)
     try:
         chunk = 3
         for ragged, mode in ((False, HOST), (True, DEV)):
             frames = _frames(chunk, 20, ragged)
-            x = _recordings(g, 3, sum(frames), 71)
-            a, b = K.bank(c, g, 3, chunk), K.bank(c, g, 3, chunk)
+            x = recordings(g, 3, sum(frames), 71)
+            a, b = _bank(K, c, g, 3, chunk), _bank(K, c, g, 3, chunk)
             k0 = 0
             for k, n in enumerate(frames):
                 ga = _bank_push(K, c, a, x, k0, n, np.ones(3, np.uint8), mode)
@@ -351,7 +219,7 @@ def test_all_ones_mask_equals_the_maskless_push(built_lib, kind, name):
                     if key == "fsm":
                         assert ga[key] == gb[key]
                     else:
-                        _same(ga[key], gb[key], "%s push %d %s" % (mode, k, key))
+                        same(ga[key], gb[key], "%s push %d %s" % (mode, k, key))
                 k0 += n
             assert np.array_equal(a.frames_seen_mics(), b.frames_seen_mics()) and list(a.frames_seen_mics()) == [k0] * 3
             a.close()
@@ -364,8 +232,7 @@ def test_all_ones_mask_equals_the_maskless_push(built_lib, kind, name):
 def test_reset_mic_of_an_absent_and_of_a_present_microphone(built_lib, kind, name):
     """Before push 9 microphone 1 (absent in pushes 8 and 9) and microphone 2 (present in both) are reset: from then on each equals a new
     stream pushed the later pushes it is present in; microphones 0 and 3 do not notice. reset_mic keeps the per-microphone counts."""
-    K = _Kind(kind, name)
-    c, g = K.open()
+    K, c, g = _open(kind, name)
     try:
         chunk, cut = 1, 9
         sched = _schedule(g.frame_count, chunk, False, seed=9)[:30]
@@ -373,9 +240,9 @@ def test_reset_mic_of_an_absent_and_of_a_present_microphone(built_lib, kind, nam
             p = sched[k][1] if sched[k][1] is not None else np.ones(M, np.uint8)
             p[1], p[2] = 0, 1
             sched[k] = (sched[k][0], p)
-        x = _recordings(g, M, sum(n for n, _ in sched), 88)
+        x = recordings(g, M, sum(n for n, _ in sched), 88)
         ref = _reference(K, c, g, x, chunk, sched, resets={cut: [1, 2]})
-        b = K.bank(c, g, M, chunk)
+        b = _bank(K, c, g, M, chunk)
         _run(K, c, b, x, sched[:cut], ref, [DEV, HOST], "before reset_mic:")
         before = b.frames_seen_mics()
         b.reset_mic(1)
@@ -393,12 +260,12 @@ def test_reset_mic_of_an_absent_and_of_a_present_microphone(built_lib, kind, nam
                 assert not p[1] and p[2]
                 others = {key: ([a[0], a[3]] if key == "fsm" else a[:, [0, 3]]) for key, a in got.items()}
                 _check_push(K, others, tuple([r[0], r[3]] for r in ref), cut, n, p[[0, 3]], 2, "push after reset_mic:")
-                for key in K.keys():
-                    _same(got[key][:, 2], rest[0][2][0][key], "the reset present microphone " + key)
+                for key in K.keys(True, K.fsm):
+                    same(got[key][:, 2], rest[0][2][0][key], "the reset present microphone " + key)
                 if K.fsm:
-                    assert got["fsm"][2] == rest[1][2][0] and got["fsm"][1] == _start_machine() == rest[1][1][0]
-                    assert (got["fsm_states"][:, 1] == _start_machine()[0]).all()
-                assert (got["argmax"][:, 1] == -1).all() and not _bits(got["filtered"][:, 1]).any()
+                    assert got["fsm"][2] == rest[1][2][0] and got["fsm"][1] == start_machine() == rest[1][1][0]
+                    assert (got["fsm_states"][:, 1] == start_machine()[0]).all()
+                assert (got["argmax"][:, 1] == -1).all() and not sd.bits(got["filtered"][:, 1]).any()
             else:
                 _check_push(K, got, rest, k, n, p, M, "after reset_mic:")
             k0 += n
@@ -412,15 +279,14 @@ def test_reset_mic_of_an_absent_and_of_a_present_microphone(built_lib, kind, nam
 @pytest.mark.parametrize("kind,name", [("int8", "long"), ("float", "long"), ("float", "shipped_q15")])
 def test_a_bank_of_one_microphone_with_a_mask(built_lib, kind, name):
     """n_mics 1: the mask-less push and the masked one run the core's kernels at grid 1, the filter with a NULL mask and with the mask."""
-    K = _Kind(kind, name)
-    c, g = K.open()
+    K, c, g = _open(kind, name)
     try:
         chunk = 3
         sched = [(n, None if k % 4 == 3 else np.array([k % 3 != 1], np.uint8)) for k, n in enumerate(_frames(chunk, 24, True))]
-        assert len(_wraps([n for n, _ in sched], chunk)) >= 2
-        x = _recordings(g, 1, sum(n for n, _ in sched), 13)
+        assert len(sd.wraps([n for n, _ in sched], chunk)) >= 2
+        x = recordings(g, 1, sum(n for n, _ in sched), 13)
         ref = _reference(K, c, g, x, chunk, sched)
-        b = K.bank(c, g, 1, chunk)
+        b = _bank(K, c, g, 1, chunk)
         _run(K, c, b, x, sched, ref, [DEV, DEV_NO_OUT], "one microphone:")
         b.close()
     finally:
@@ -432,8 +298,7 @@ def test_errors(built_lib, kind, name):
     import torch
     from edison_amd import _lib
     L = _lib.lib()
-    K = _Kind(kind, name)
-    c, g = K.open()
+    K, c, g = _open(kind, name)
     try:
         P = "edison_bank_" if kind == "int8" else "edison_fbank_"
         push, push_n, seen = (getattr(L, P + n) for n in ("push_present", "push_present_n_dev", "frames_seen_mics"))
@@ -443,7 +308,7 @@ def test_errors(built_lib, kind, name):
                 call()
             assert e.value.code == _lib.E_ARGUMENT and K.who in str(e.value), str(e.value)
 
-        b = K.bank(c, g, 3, 2)
+        b = _bank(K, c, g, 3, 2)
         dev = torch.device("cuda", c.device)
         x = np.zeros((3, 2 * g.frame_step), np.int16)
         xt = torch.from_numpy(x).to(dev)

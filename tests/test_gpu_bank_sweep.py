@@ -7,11 +7,10 @@ many streams whatever the row's size. Two references:
   streams      one stream.GeomStream per base recording (and per reset: a new stream fed the rest), same options, same schedule
   independent  no sliding buffer and no shift kernel: every frame's int8 row from the batch float64 MFCC (Context.mfcc_geom) on the
                zero-led recording, the windows cut in numpy behind F - 1 zero rows, Context.net on them, the filter in numpy
-               (test_gpu_stream_geom._filter_ref) and edisonFSM from the host binding (stream.Fsm).
+               (stream_drive.filter_ref) and edisonFSM from the host binding (stream.Fsm).
 Rows with masks (present) use the independent reference: a microphone's expected stream is that reference on the concatenation of the
 pushes it was present in (since its last reset), the pushes it was absent from carry noise over the whole int16 range, and at those its
 rows must hold the fill exactly: zero bytes, -1, its machine's unchanged state; frames_seen_mics() counts the present frames."""
-import ctypes
 import os
 import subprocess
 import sys
@@ -21,15 +20,17 @@ import numpy as np
 import pytest
 
 import bank_sweep as bs
-from test_gpu_kws_geom import _header, _same
-from test_gpu_stream_bank import KEYS, _empty_outputs, _push_stream, _recordings, _to_host, _torch_stream
-from test_gpu_stream_geom import _filter_ref
+import stream_drive as sd
+from geom_sweep import header
+from stream_drive import filter_ref, recordings, same
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IN_PROCESS = [n for n, r in bs.ROWS.items() if r["route"] != "lbl"]
 LBL = [n for n, r in bs.ROWS.items() if r["route"] == "lbl"]
+KIND = sd.Kind("int8")
+ASKED = {"all": ("logits", "softmax", "argmax"), "no_softmax": ("logits", "argmax"), "no_logits": ("softmax", "argmax"), "none": ()}
 
 
 def _open(row):
@@ -37,7 +38,7 @@ def _open(row):
     if row["graph"] == "shipped":
         return Context(0), bs.geometry(row["geom"])
     c = Context(0, model_path=None)
-    c.load_weights_h(_header(row["graph"]))
+    c.load_weights_h(header(row["graph"]))
     return c, bs.geometry(row["geom"])
 
 
@@ -53,36 +54,6 @@ def _starts(row):
 
 
 # ---- the references ----------------------------------------------------------------------------------------------------------------
-def _stream_ref(c, g, row, x, p0, thr):
-    """A new GeomStream fed recording x from push p0 on, by the row's schedule: (dict of [frames][..], final machine)."""
-    from edison_amd import _lib
-    from edison_amd.stream import GeomStream
-    torch, dev = _torch_stream(c)
-    L = _lib.lib()
-    info = c.net_info()
-    sched = row["sched"][p0:]
-    f0 = sum(row["sched"][:p0])
-    try:
-        s = GeomStream(c, g, chunk_frames=row["chunk"], output_filter=True, alpha=row["alpha"], threshold=thr, fsm=row["fsm"])
-        try:
-            xt = torch.from_numpy(x[f0 * g.frame_step:]).to(dev)
-            o = _empty_outputs(torch, dev, (sum(sched),), info["n_out"], info["has_softmax"], True, row["fsm"])
-            k0 = 0
-            for n in sched:
-                _push_stream(s, L, xt, k0, n, o, True, row["fsm"])
-                k0 += n
-            torch.cuda.synchronize(dev)
-            snap = None
-            if row["fsm"]:
-                c._check(L.edison_stream_geom_fsm(s._h, ctypes.byref(s._fsm), None))
-                snap = s.fsm_snapshot()["raw"]
-        finally:
-            s.close()
-    finally:
-        c.use_own_stream()
-    return _to_host(o), snap
-
-
 def _net_ref(c, g, x):
     """The network's outputs for every frame of recording x without a sliding buffer (see the module text)."""
     K, F, nm = x.shape[0] // g.frame_step, g.frame_count, g.num_mfcc
@@ -99,7 +70,7 @@ def _finish_ref(c, g, row, net, thr):
     """The filter (numpy) and the state machine (host binding) behind the network outputs of one recording."""
     from edison_amd.stream import Fsm, _fsm_dict
     xin = net["softmax"] if net["softmax"] is not None else net["logits"]
-    filt, likely, spotted = _filter_ref(xin, row["alpha"], thr)
+    filt, likely, spotted = filter_ref(xin, row["alpha"], thr)
     out = dict(net, filtered=filt, likely=likely, spotted=spotted)
     snap = None
     if row["fsm"]:
@@ -123,7 +94,7 @@ def _expected(c, g, row, xb, base):
         nets = [_net_ref(c, g, x) for x in xb]
         if thr == "tie":
             # a threshold that a filtered maximum equals exactly: the middle one of the reference's own maxima (strict >: not spotted)
-            best = np.concatenate([_filter_ref(n["softmax"] if n["softmax"] is not None else n["logits"], row["alpha"], 0.0)[0].max(axis=1) for n in nets])
+            best = np.concatenate([filter_ref(n["softmax"] if n["softmax"] is not None else n["logits"], row["alpha"], 0.0)[0].max(axis=1) for n in nets])
             vals = np.unique(best)
             thr = float(vals[len(vals) // 2])
             assert (best == np.float32(thr)).any() and (best > thr).any(), "no tie to test"
@@ -132,7 +103,9 @@ def _expected(c, g, row, xb, base):
     else:
         assert thr != "tie"
         for key in sorted({(base[m], p0) for st in starts for m, p0 in st.items()}):
-            refs[key] = _stream_ref(c, g, row, xb[key[0]], key[1], thr)
+            # a new GeomStream fed the base recording from push key[1] on, by the row's schedule
+            refs[key] = sd.drive_stream(KIND, c, g, xb[key[0]], row["sched"], chunk=row["chunk"], filt=True, fsm=row["fsm"], alpha=row["alpha"],
+                                        threshold=thr, first_push=key[1])
     info = c.net_info()
     no = info["n_out"]
     exp = dict(logits=np.zeros((K, M, no), np.int8), softmax=np.zeros((K, M, no), np.int8) if info["has_softmax"] else None,
@@ -153,178 +126,12 @@ def _expected(c, g, row, xb, base):
     return exp, snaps, thr
 
 
-# ---- rows with masks -------------------------------------------------------------------------------------------------------------------
-def lives_of(row):
-    """Per microphone the lives of its stream, a new one at every reset: [[the pushes it was present in] per life]."""
-    M = row["n_mics"]
-    lives = [[[]] for _ in range(M)]
-    for p in range(len(row["sched"])):
-        for at, who in row["resets"]:
-            if at == p:
-                for m in (range(M) if who == "all" else [who]):
-                    lives[m].append([])
-        gone = set(bs.absent_of(row, p))
-        for m in range(M):
-            if m not in gone:
-                lives[m][-1].append(p)
-    return lives
-
-
-def present_counts(row):
-    """frames_seen_mics() after the schedule: the frames of the pushes a microphone was present in since the last reset of the bank."""
-    first = max([at for at, who in row["resets"] if who == "all"], default=0)
-    counts = np.zeros(row["n_mics"], np.int64)
-    for p, n in enumerate(row["sched"]):
-        if p >= first:
-            counts += n
-            counts[bs.absent_of(row, p)] -= n
-    return counts
-
-
-def garbage(row, x, hop, seed=11):
-    """The push buffers: x [n_mics][K * hop] with the samples of every absent microphone replaced by noise over the whole int16 range."""
-    rng = np.random.default_rng(seed)
-    y, k0 = x.copy(), 0
-    for p, n in enumerate(row["sched"]):
-        gone = bs.absent_of(row, p)
-        if gone:
-            y[gone, k0 * hop:(k0 + n) * hop] = rng.integers(-32768, 32768, (len(gone), n * hop)).astype(np.int16)
-        k0 += n
-    return y
-
-
-def masked_expected(row, xb, base, hop, net_of, finish, start):
-    """(dict of [K][n_mics][..], [final machine per microphone], threshold) for a row with masks or resets, for either bank.
-    net_of(x, life): the network's outputs for every frame of recording x, the pushes `life` of the schedule put together, with no
-    sliding buffer; finish(net, thr): (those with the filter's and the machine's behind them, the final machine); start: (a new
-    machine's state, its raw fields). Microphones that play the same base recording through the same lives share a reference."""
-    M, sched = row["n_mics"], row["sched"]
-    off = np.concatenate([[0], np.cumsum(sched)])
-    groups = {}
-    for m, lv in enumerate(lives_of(row)):
-        resets_at = tuple(sorted(at for at, who in row["resets"] if who in ("all", m)))
-        groups.setdefault((base[m], tuple(tuple(life) for life in lv), resets_at), []).append(m)
-    nets = {}
-    for b, lv, _ in groups:
-        for life in lv:
-            if life and (b, life) not in nets:
-                nets[(b, life)] = net_of(np.concatenate([xb[b][off[p] * hop:off[p + 1] * hop] for p in life]), life)
-    thr = row["thr"]
-    if thr == "tie":
-        # a threshold that a filtered maximum equals exactly: the middle one of the reference's own maxima (strict >: not spotted)
-        best = np.concatenate([_filter_ref(_filter_input(n), row["alpha"], 0.0)[0].max(axis=1) for n in nets.values()])
-        vals = np.unique(best)
-        thr = float(vals[len(vals) // 2])
-        assert (best == np.float32(thr)).any() and (best > thr).any(), "no tie to test"
-    refs = {k: finish(n, thr) for k, n in nets.items()}
-    some = next(iter(refs.values()))[0]
-    exp = {k: (None if v is None else np.full((off[-1], M) + v.shape[1:], -1 if k in ("argmax", "likely", "spotted", "fsm_states") else 0, v.dtype))
-           for k, v in some.items()}
-    snaps = [None] * M
-    for (b, lv, resets_at), mics in groups.items():
-        mics = np.array(mics)
-        li, at, state, snap = 0, 0, start[0], start[1]
-        for p, n in enumerate(sched):
-            for r in resets_at:
-                if r == p:
-                    li, at, state, snap = li + 1, 0, start[0], start[1]
-            sl = slice(off[p], off[p + 1])
-            if p in lv[li]:
-                out, snap = refs[(b, lv[li])]
-                for k, v in exp.items():
-                    if v is not None:
-                        v[sl, mics] = out[k][at:at + n][:, None]
-                at += n
-                if row["fsm"]:
-                    state = out["fsm_states"][at - 1]
-            elif row["fsm"]:
-                exp["fsm_states"][sl, mics] = state            # the fill: the machine's unchanged state
-        for m in mics:
-            snaps[m] = snap        # a life's reference gives its machine at the life's end, which is where the schedule leaves it
-    return exp, snaps, thr
-
-
-def _filter_input(net):
-    second = net.get("softmax", net.get("probs"))
-    return second if second is not None else net["logits"]
-
-
-def _start_machine(thr):
-    from edison_amd.stream import Fsm, _fsm_dict
-    f = Fsm(threshold=thr)
-    raw = _fsm_dict(f._f)["raw"]
-    return raw[0], raw
-
-
 # ---- the bank ------------------------------------------------------------------------------------------------------------------------
 def _bank(c, g, row, x, thr):
-    """The bank on x [n_mics][K * hop] by the row's schedule, pushes, resets and outputs. Returns (dict of [K][n_mics][..] with None for
+    """The bank on x [n_mics][K * hop] by the row's schedule, pushes, resets and outputs. Returns (dict of [K][n_mics][..] without
     what was not asked for, [final machine per microphone])."""
-    from edison_amd.stream import StreamBank
-    torch, dev = _torch_stream(c)
-    info = c.net_info()
-    M, hop = row["n_mics"], g.frame_step
-    asked = {"all": ("logits", "softmax", "argmax"), "no_softmax": ("logits", "argmax"), "no_logits": ("softmax", "argmax"), "none": ()}[row["outputs"]]
-    try:
-        b = StreamBank(c, g, M, chunk_frames=row["chunk"], output_filter=True, alpha=row["alpha"], threshold=thr, fsm=row["fsm"])
-        try:
-            X = torch.from_numpy(x).to(dev)
-            o = _empty_outputs(torch, dev, (sum(row["sched"]), M), info["n_out"], info["has_softmax"], True, row["fsm"])
-            k0, fulls, host_parts = 0, 0, []
-            for p, n in enumerate(row["sched"]):
-                for at, who in row["resets"]:
-                    if at == p:
-                        b.reset() if who == "all" else b.reset_mic(who)
-                host = row["push"] == "host" or (row["push"] == "alt" and n == row["chunk"] and fulls % 2 == 0)
-                fulls += n == row["chunk"]
-                sl = slice(k0, k0 + n)
-                mask = None
-                if row["present"] and row["present"][p] is not None:
-                    mask = np.ones(M, np.uint8)
-                    mask[bs.absent_of(row, p)] = 0
-                if host:
-                    assert n == row["chunk"]
-                    host_parts.append((sl, b.push(x[:, k0 * hop:(k0 + n) * hop], present=mask)))
-                elif mask is not None:
-                    kw = {k: (o[k][sl] if k in asked and o[k] is not None else None) for k in ("logits", "softmax", "argmax")}
-                    kw.update(filtered=o["filtered"][sl], likely=o["likely"][sl], spotted=o["spotted"][sl])
-                    if row["fsm"]:
-                        kw.update(fsm_states=o["fsm_states"][sl])
-                    b.push_t(X[:, k0 * hop:(k0 + n) * hop].contiguous(), n_frames=n, present=torch.from_numpy(mask).to(dev), **kw)
-                else:
-                    kw = {k: (o[k][sl] if k in asked and o[k] is not None else None) for k in ("logits", "softmax", "argmax")}
-                    kw.update(filtered=o["filtered"][sl], likely=o["likely"][sl], spotted=o["spotted"][sl])
-                    if row["fsm"]:
-                        kw.update(fsm_states=o["fsm_states"][sl])
-                    b.push_t(X[:, k0 * hop:(k0 + n) * hop].contiguous(), n_frames=None if n == row["chunk"] else n, **kw)
-                k0 += n
-            torch.cuda.synchronize(dev)
-            snaps = None
-            if row["fsm"]:
-                c._check(b._c("fsm")(b._h, ctypes.byref(b._fsms), None))
-                snaps = [s["raw"] for s in b.fsm_snapshot()]
-            if not any(who == "all" for _, who in row["resets"]):
-                assert b.frames_seen() == k0
-            if row["present"]:
-                assert np.array_equal(b.frames_seen_mics(), present_counts(row)), name_of(row)
-        finally:
-            b.close()
-    finally:
-        c.use_own_stream()
-    got = _to_host(o)
-    for sl, part in host_parts:
-        for k in got:
-            if got[k] is not None and part.get(k) is not None:
-                got[k][sl] = part[k]
-    if row["push"] != "host":                   # a host push returns every output
-        for k in ("logits", "softmax", "argmax"):
-            if k not in asked:
-                got[k] = None
-    return got, snaps
-
-
-def name_of(row):
-    return next(n for n, r in bs.ROWS.items() if r is row)
+    return sd.drive_bank(KIND, c, g, x, row["sched"], chunk=row["chunk"], filt=True, fsm=row["fsm"], alpha=row["alpha"], threshold=thr,
+                         asked=ASKED[row["outputs"]], counts=sd.present_counts(row) if row["present"] else None, **sd.pushes_of(row))
 
 
 def _run_row(name, tmp=None):
@@ -342,25 +149,23 @@ def _run_row(name, tmp=None):
         M, K = row["n_mics"], sum(row["sched"])
         base = [bs.base_of(m, M) for m in range(M)]
         assert all(base[m] != base[m + 1] for m in range(M - 1))
-        xb = _recordings(g, max(base) + 1, K, 300 + len(name))
+        xb = recordings(g, max(base) + 1, K, 300 + len(name))
         if row["present"]:
             assert row["ref"] == "independent"
-            thr0 = row["thr"]
-            exp, exp_snaps, thr = masked_expected(row, xb, base, g.frame_step, lambda x, life: _net_ref(c, g, x), lambda net, t: _finish_ref(c, g, row, net, t),
-                                                  _start_machine(thr0 if thr0 != "tie" else 0.5))
-            got, snaps = _bank(c, g, row, garbage(row, xb[base], g.frame_step), thr)
+            exp, exp_snaps, thr = sd.masked_expected(row, xb, base, g.frame_step, lambda x, life: _net_ref(c, g, x), lambda net, t: _finish_ref(c, g, row, net, t))
+            got, snaps = _bank(c, g, row, sd.garbage(row, xb[base], g.frame_step), thr)
         else:
             exp, exp_snaps, thr = _expected(c, g, row, xb, base)
             got, snaps = _bank(c, g, row, xb[base], thr)
         compared = 0
-        for k in KEYS:
+        for k in KIND.keys(True, True):
             if k not in exp or exp[k] is None or got.get(k) is None:
                 assert k in ("logits", "softmax", "argmax", "fsm_states"), (name, k)
                 continue
-            _same(got[k], exp[k], "%s %s" % (name, k))
+            same(got[k], exp[k], "%s %s" % (name, k))
             compared += 1
         assert compared >= 3 and (row["outputs"] != "all" or compared == len([k for k in exp if exp[k] is not None]))
-        assert snaps == (exp_snaps if row["fsm"] else None), name
+        assert snaps == (exp_snaps if row["fsm"] else []), name
         if len(xb) > 1:
             assert not np.array_equal(exp["logits"][:, 0], exp["logits"][:, 1])      # the recordings do differ
     finally:

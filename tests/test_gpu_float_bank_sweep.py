@@ -9,22 +9,18 @@ Rows with more than 8 microphones play bank_sweep.BASES seeded recordings (micro
                (Context.kws_float(..., utt_stride=frame_step)["feat"], in the row's flow, clip range and scale), the windows cut in
                numpy behind F - 1 zero rows, Context.fnet on them, the logits also against the CPU fmaf chain (tests/fnet_host.py:
                every window of a recording of at most 2048, else the first and last 64), the filter in numpy
-               (test_gpu_stream_geom._filter_ref) and edisonFSM from the host binding (stream.Fsm)
+               (stream_drive.filter_ref) and edisonFSM from the host binding (stream.Fsm)
   streams      one stream.FloatStream per base recording and per reset, same options, same schedule: rows with resets only
 A microphone's expected stream is the reference on the concatenation of the pushes it was present in since its last reset; the pushes
 it was absent from carry noise over the whole int16 range, and at those its rows must hold the fill exactly."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import bank_sweep as bs
 import float_bank_sweep as fs
 import fnet_host
-from test_gpu_bank_sweep import _start_machine, garbage, masked_expected, present_counts
-from test_gpu_float_bank import KEYS, _empty_outputs, _same
-from test_gpu_stream_bank import _recordings, _to_host, _torch_stream
-from test_gpu_stream_geom import _filter_ref
+import stream_drive as sd
+from stream_drive import filter_ref, recordings, same
 
 pytestmark = pytest.mark.gpu
 
@@ -51,14 +47,14 @@ def _net_ref(c, g, row, model, x):
     win = np.ascontiguousarray(np.lib.stride_tricks.sliding_window_view(r, (F, nm))[:, 0].reshape(K, -1))
     out = c.fnet(win)
     idx = np.arange(K) if K <= 2048 else np.concatenate([np.arange(64), np.arange(K - 64, K)])
-    _same(out["logits"][idx], fnet_host.run(model, win[idx])[-1], "the reference's logits against the fmaf chain")
+    same(out["logits"][idx], fnet_host.run(model, win[idx])[-1], "the reference's logits against the fmaf chain")
     return out
 
 
 def _finish_ref(g, row, net, thr):
     """The filter (numpy) and the state machine (host binding) behind the network outputs of one recording."""
     from edison_amd.stream import Fsm, _fsm_dict
-    filt, likely, spotted = _filter_ref(net["probs"], row["alpha"], thr)
+    filt, likely, spotted = filter_ref(net["probs"], row["alpha"], thr)
     out = dict(net, filtered=filt, likely=likely, spotted=spotted)
     snap = None
     if row["fsm"]:
@@ -70,108 +66,33 @@ def _finish_ref(g, row, net, thr):
     return out, snap
 
 
-def _stream_ref(c, g, row, x, sched, thr):
-    """A new FloatStream fed recording x by `sched`: (dict of [frames][..], final machine)."""
-    from edison_amd import _lib
-    from edison_amd.stream import FloatStream
-    torch, dev = _torch_stream(c)
-    L = _lib.lib()
-    try:
-        s = FloatStream(c, g, q15=row["q15"], chunk_frames=row["chunk"], output_filter=True, alpha=row["alpha"], threshold=thr, fsm=row["fsm"],
-                        clip_min=row["clip"][0], clip_max=row["clip"][1])
-        try:
-            xt = torch.from_numpy(x).to(dev)
-            o = _empty_outputs(torch, dev, (sum(sched),), s.n_out, True, row["fsm"])
-            k0 = 0
-            for n in sched:
-                sl = slice(k0, k0 + n)
-                s.push_t(xt[k0 * s.hop:(k0 + n) * s.hop], n_frames=None if n == row["chunk"] else n, logits=o["logits"][sl], probs=o["probs"][sl],
-                         argmax=o["argmax"][sl], filtered=o["filtered"][sl], likely=o["likely"][sl], spotted=o["spotted"][sl])
-                if row["fsm"]:
-                    c._check(L.edison_stream_float_fsm_dev(s._h, ctypes.c_void_p(o["fsm_states"][sl].data_ptr())))
-                k0 += n
-            torch.cuda.synchronize(dev)
-            snap = None
-            if row["fsm"]:
-                c._check(L.edison_stream_float_fsm(s._h, ctypes.byref(s._fsm), None))
-                snap = s.fsm_snapshot()["raw"]
-        finally:
-            s.close()
-    finally:
-        c.use_own_stream()
-    return _to_host(o), snap
+def _kind(row):
+    return sd.Kind("float", q15=row["q15"])
 
 
 def _expected(c, g, row, xb, base):
     """(dict of [K][n_mics][..], [final machine per microphone], threshold) from the row's reference."""
     from edison_amd import cube_import
-    start = _start_machine(0.5 if row["thr"] == "tie" else row["thr"])
     if row["ref"] == "streams":
         assert row["resets"] and not row["present"] and row["thr"] != "tie"
-        return masked_expected(row, xb, base, g.frame_step, lambda x, life: _stream_ref(c, g, row, x, [row["sched"][p] for p in life], row["thr"]),
-                               lambda net, thr: net, start)
+
+        def stream_of(x, life):
+            """A new FloatStream fed recording x by the pushes of `life`: (dict of [frames][..], final machine)."""
+            return sd.drive_stream(_kind(row), c, g, x, [row["sched"][p] for p in life], chunk=row["chunk"], filt=True, fsm=row["fsm"],
+                                   alpha=row["alpha"], threshold=row["thr"], clip_min=row["clip"][0], clip_max=row["clip"][1])
+
+        return sd.masked_expected(row, xb, base, g.frame_step, stream_of, lambda net, thr: net)
     model = cube_import.read_blob(fs.blob_of(row["net"], row["geom"]))
-    return masked_expected(row, xb, base, g.frame_step, lambda x, life: _net_ref(c, g, row, model, x), lambda net, thr: _finish_ref(g, row, net, thr), start)
+    return sd.masked_expected(row, xb, base, g.frame_step, lambda x, life: _net_ref(c, g, row, model, x), lambda net, thr: _finish_ref(g, row, net, thr))
 
 
 # ---- the bank ------------------------------------------------------------------------------------------------------------------------
 def _bank(c, g, row, x, thr):
-    """The bank on x [n_mics][K * hop] by the row's schedule, pushes, masks, resets and outputs. Returns (dict of [K][n_mics][..] with
-    None for what was not asked for, [final machine per microphone])."""
-    from edison_amd.stream import FloatBank
-    torch, dev = _torch_stream(c)
-    M, hop = row["n_mics"], g.frame_step
-    asked = ASKED[row["outputs"]]
-    try:
-        b = FloatBank(c, M, g, q15=row["q15"], chunk_frames=row["chunk"], output_filter=True, alpha=row["alpha"], threshold=thr, fsm=row["fsm"],
-                      clip_min=row["clip"][0], clip_max=row["clip"][1])
-        try:
-            X = torch.from_numpy(x).to(dev)
-            o = _empty_outputs(torch, dev, (sum(row["sched"]), M), b.n_out, True, row["fsm"])
-            k0, fulls, host_parts = 0, 0, []
-            for p, n in enumerate(row["sched"]):
-                for at, who in row["resets"]:
-                    if at == p:
-                        b.reset() if who == "all" else b.reset_mic(who)
-                host = row["push"] == "host" or (row["push"] == "alt" and n == row["chunk"] and fulls % 2 == 0)
-                fulls += n == row["chunk"]
-                sl = slice(k0, k0 + n)
-                mask = None
-                if row["present"] and row["present"][p] is not None:
-                    mask = np.ones(M, np.uint8)
-                    mask[bs.absent_of(row, p)] = 0
-                if host:
-                    assert n == row["chunk"]
-                    host_parts.append((sl, b.push(x[:, k0 * hop:(k0 + n) * hop], present=mask)))
-                else:
-                    kw = {k: (o[k][sl] if k in asked else None) for k in ("logits", "probs", "argmax")}
-                    kw.update(filtered=o["filtered"][sl], likely=o["likely"][sl], spotted=o["spotted"][sl])
-                    if row["fsm"]:
-                        kw.update(fsm_states=o["fsm_states"][sl])
-                    b.push_t(X[:, k0 * hop:(k0 + n) * hop].contiguous(), n_frames=None if n == row["chunk"] and mask is None else n,
-                             present=None if mask is None else torch.from_numpy(mask).to(dev), **kw)
-                k0 += n
-            torch.cuda.synchronize(dev)
-            snaps = None
-            if row["fsm"]:
-                c._check(b._c("fsm")(b._h, ctypes.byref(b._fsms), None))
-                snaps = [s["raw"] for s in b.fsm_snapshot()]
-            if not any(who == "all" for _, who in row["resets"]):
-                assert b.frames_seen() == k0
-            assert np.array_equal(b.frames_seen_mics(), present_counts(row))
-        finally:
-            b.close()
-    finally:
-        c.use_own_stream()
-    got = _to_host(o)
-    for sl, part in host_parts:
-        for k in got:
-            got[k][sl] = part[k]
-    if row["push"] != "host":                   # a host push returns every output
-        for k in ("logits", "probs", "argmax"):
-            if k not in asked:
-                got[k] = None
-    return got, snaps
+    """The bank on x [n_mics][K * hop] by the row's schedule, pushes, masks, resets and outputs. Returns (dict of [K][n_mics][..] without
+    what was not asked for, [final machine per microphone])."""
+    return sd.drive_bank(_kind(row), c, g, x, row["sched"], chunk=row["chunk"], filt=True, fsm=row["fsm"], alpha=row["alpha"], threshold=thr,
+                         asked=ASKED[row["outputs"]], counts=sd.present_counts(row), clip_min=row["clip"][0], clip_max=row["clip"][1],
+                         **sd.pushes_of(row))
 
 
 def _run_row(name):
@@ -183,19 +104,19 @@ def _run_row(name):
         M, K = row["n_mics"], sum(row["sched"])
         base = [bs.base_of(m, M) for m in range(M)]
         assert all(base[m] != base[m + 1] for m in range(M - 1))
-        xb = _recordings(g, max(base) + 1, K, 500 + len(name))
+        xb = recordings(g, max(base) + 1, K, 500 + len(name))
         exp, exp_snaps, thr = _expected(c, g, row, xb, base)
         x = xb[base]
-        got, snaps = _bank(c, g, row, garbage(row, x, g.frame_step) if row["present"] else x, thr)
+        got, snaps = _bank(c, g, row, sd.garbage(row, x, g.frame_step) if row["present"] else x, thr)
         compared = 0
-        for k in KEYS:
+        for k in sd.Kind("float").keys(True, True):
             if k not in exp or got.get(k) is None:
                 assert k in ("logits", "probs", "argmax", "fsm_states"), (name, k)
                 continue
-            _same(got[k], exp[k], "%s %s" % (name, k))
+            same(got[k], exp[k], "%s %s" % (name, k))
             compared += 1
         assert compared >= 3 and (row["outputs"] != "all" or compared == len(exp))
-        assert snaps == (exp_snaps if row["fsm"] else None), name
+        assert snaps == (exp_snaps if row["fsm"] else []), name
         if len(xb) > 1:
             assert not np.array_equal(exp["logits"][:, 0], exp["logits"][:, 1])      # the recordings do differ
         if tuple(row["clip"]) != fs.DEFAULT_CLIP:

@@ -17,8 +17,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from test_gpu_kws_geom import _geom
-from test_gpu_stream_bank import _recordings
+from geom_sweep import geom
+from stream_drive import recordings
 
 import fnet_host as fh
 import fnet_plan as fpl
@@ -166,12 +166,12 @@ def test_large_on_a_fitting_network_changes_nothing(ctx):
 
 
 def test_kws_float_and_evaluate(ctx):
-    g = _geom(**SMALL)
+    g = geom(**SMALL)
     name = "conv_model"
     assert (g.frame_count, g.num_mfcc, 1) == fr.LARGE[name][0]["in_shape"]
     ctx.fnet_load(fr.blob(name), large=True)
     n = 11
-    audio = _recordings(g, n, g.frame_count + 1, 7)[:, :g.n_samples]
+    audio = recordings(g, n, g.frame_count + 1, 7)[:, :g.n_samples]
     r = ctx.kws_float(audio.ravel(), g, n_utt=n)
     f = ctx.fnet(r["feat"])
     for k in ("logits", "probs", "argmax"):
@@ -197,7 +197,7 @@ def test_kws_float_and_evaluate(ctx):
 def test_consumers_refuse_a_layered_network_by_name(ctx):
     from edison_amd import _lib
     from edison_amd.stream import FloatBank, FloatStream
-    g = _geom(**SMALL)
+    g = geom(**SMALL)
     name = "conv_model"
     ctx.fnet_load(fr.blob(name), large=True)
     x = fr.inputs(name, 5)

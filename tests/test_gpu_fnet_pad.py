@@ -15,9 +15,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from test_gpu_kws_geom import _geom
-from test_gpu_stream_bank import _recordings
-from test_gpu_stream_geom import _tail
+from geom_sweep import geom
+from stream_drive import recordings, tail
 
 import cube_synth
 import fnet_host as fh
@@ -47,7 +46,7 @@ def ctx(built_lib):
 @pytest.fixture(scope="module")
 def small():
     """(blob, model, geometry) of medium_embedding_conv at the small geometry, through the X-CUBE-AI source format and the importer."""
-    g = _geom(**SMALL)
+    g = geom(**SMALL)
     assert (g.frame_count, g.num_mfcc, 1) == SMALL_IN
     blob = cube_synth.import_sources(*cube_synth.cube_sources(SMALL_IN, fr.zoo_specs("medium_embedding_conv", SMALL_IN), seed=5))
     m = cube_import.read_blob(blob)
@@ -114,7 +113,7 @@ def test_refusals_keep_the_loaded_network(ctx):
 
 def _batch_call(c, g, x):
     """Context.kws_float on the zero-led recording, one utterance per full window (utt_stride = frame_step)."""
-    z = np.concatenate([np.zeros(_tail(g), np.int16), x])
+    z = np.concatenate([np.zeros(tail(g), np.int16), x])
     return c.kws_float(z, g, n_utt=x.shape[0] // g.frame_step - g.frame_count + 1, utt_stride=g.frame_step)
 
 
@@ -131,7 +130,7 @@ def test_stream_and_bank_on_a_padded_network(ctx, small):
     blob, m, g = small
     ctx.fnet_load(blob)
     K, F = 30, g.frame_count
-    xs = _recordings(g, 3, K, 91)
+    xs = recordings(g, 3, K, 91)
     streams = []
     for mic in range(3):
         s = FloatStream(ctx, g)
@@ -179,7 +178,7 @@ def test_quantize_medium_embedding_conv(ctx, small):
     from edison_amd import nnom_import
     blob, m, g = small
     ctx.fnet_load(blob)
-    audio = _recordings(g, 6, g.frame_count + 1, 7)[:, :g.n_samples]
+    audio = recordings(g, 6, g.frame_count + 1, 7)[:, :g.n_samples]
     q, rep = ctx.quantize(audio.ravel(), geometry=g, chunk=4, return_features=True)
     want_q, _ = qz.quantize(m, fh.stats(m, rep["features"]))
     assert q == want_q

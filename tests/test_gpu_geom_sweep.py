@@ -190,7 +190,7 @@ def test_state_across_kernel_instances():
     from edison_amd.context import Context
     rows = {n: gs.row_data(n) for n in STATE_ROWS}
     cut = {n: rows[n][1][:10] for n in STATE_ROWS}
-    fixed = gs.signals("n1280", gs.geometry("n1280"), 62)[2, :].copy()
+    fixed = gs.row_signals("n1280", gs.geometry("n1280"), 62)[2, :].copy()
     fixed = np.concatenate([fixed, fixed])[:32000]
     gen_g = gs.geometry("n375", net_input_scale=rows["n1280"][0].net_input_scale)
 

@@ -4,65 +4,13 @@ numpy, pinned on the reference's own outputs in test_oracle.py), the coefficient
 net_input_scale, clip, round half to even (oracle.net_input), then the graph on those features through ctx.net (pinned bit-exact on
 NNoM elsewhere). Everything is compared bit for bit."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
+from geom_sweep import GEOMS, geom, header, signals
+
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-
-# graph -> geometry it is run at (its input is frame_count x num_mfcc features)
-GEOMS = {
-    "kws_small": dict(variant="B", use_log=True, frame_len=512, frame_step=1024, n_samples=32000, mel_nbins=20, first_mfcc=0, num_mfcc=13),
-    "same_stride": dict(variant="B", frame_len=800, frame_step=800, n_samples=16000, mel_nbins=40, first_mfcc=1, num_mfcc=12,
-                        lower_edge_hertz=20.0, upper_edge_hertz=4000.0, mel_mtx_scale=64.0),
-    "square": dict(variant="A", frame_len=480, frame_step=240, n_samples=15600, mel_nbins=24, first_mfcc=0, num_mfcc=16),
-    "even_same": dict(variant="B", frame_len=1000, frame_step=500, n_samples=8500, mel_nbins=32, first_mfcc=0, num_mfcc=20, net_input_scale=0.5),
-    "odd_no_softmax": dict(variant="B", frame_len=441, frame_step=441, n_samples=11907, mel_nbins=16, first_mfcc=0, num_mfcc=7),
-}
-
-
-def _geom(**kw):
-    from edison_amd import _lib
-    from edison_amd.kws.geometry import KwsGeometry
-    kw = dict(kw)
-    if kw.get("variant") in ("A", "B"):
-        kw["variant"] = _lib.MFCC_A if kw["variant"] == "A" else _lib.MFCC_B
-    return KwsGeometry.from_config(**kw)
-
-
-def _header(name):
-    return os.path.join(GOLDEN, "alt_models", name + ".h")
-
-
-def _signals(n_utt, n_samples, seed):
-    """int16 [n_utt][n_samples]: silence, low-level noise, tones, clipping-loud noise and the reference's `edison` utterance (at a random
-    place and gain), in turn."""
-    rng = np.random.default_rng(seed)
-    edison = np.load(os.path.join(GOLDEN, "mfcc_geom_golden.npz"))["in_edison"].astype(np.float64)
-    t = np.arange(n_samples) / 16000.0
-    out = np.zeros((n_utt, n_samples), np.int16)
-    for u in range(n_utt):
-        kind = u % 5
-        if kind == 0:
-            x = np.zeros(n_samples)
-        elif kind == 1:
-            x = rng.normal(0, rng.uniform(0.5, 30.0), n_samples)
-        elif kind == 2:
-            f = rng.uniform(50.0, 7900.0, 2)
-            x = rng.uniform(100, 20000) * np.cos(2 * np.pi * f[0] * t + rng.random() * 6.3) + rng.uniform(0, 3000) * np.cos(2 * np.pi * f[1] * t)
-        elif kind == 3:
-            x = rng.normal(0, rng.uniform(20000, 60000), n_samples)
-        else:
-            x = rng.normal(0, 10.0, n_samples)
-            e = edison[:n_samples] * rng.uniform(0.3, 4.0)
-            at = int(rng.integers(0, max(1, n_samples - e.shape[0] + 1)))
-            x[at:at + e.shape[0]] += e
-        out[u] = np.clip(np.rint(x), -32768, 32767).astype(np.int16)
-    return out
 
 
 def _oracle_feat(oracle, rows, g, starts=None):
@@ -94,9 +42,9 @@ def test_shipped_geometry_equals_exact_kws_and_oracle(oracle_mod):
     from edison_amd.context import Context
     c = Context(0)
     try:
-        g = _geom()
+        g = geom()
         assert (g.frame_count, g.num_mfcc, g.n_features) == (31, 13, 403)
-        audio = _signals(16384, 32000, 11)
+        audio = signals(16384, 32000, 11)
         r = c.kws_geom(audio, g)
         ex = c.kws(audio, n_utt=audio.shape[0], utt_stride=32000, exact=True)
         for k in ("feat", "logits", "softmax", "argmax"):
@@ -130,11 +78,11 @@ def test_retrained_graphs_at_their_geometry(oracle_mod, name):
     from edison_amd.context import Context, _np_ptr
     c = Context(0, model_path=None)
     try:
-        c.load_weights_h(_header(name))
+        c.load_weights_h(header(name))
         info = c.net_info()
-        g = _geom(**GEOMS[name])
+        g = geom(**GEOMS[name])
         assert g.n_features == info["in_h"] * info["in_w"] * info["in_c"]
-        audio = _signals(2048, g.n_samples, 100 + len(name))
+        audio = signals(2048, g.n_samples, 100 + len(name))
         r = c.kws_geom(audio, g)
         _check_against_oracle(c, r, _oracle_feat(oracle_mod, audio, g))
         assert (r["softmax"] is None) == (name == "odd_no_softmax")
@@ -163,9 +111,9 @@ def test_features_equal_the_generic_kernel(name):
     from edison_amd.context import Context
     c = Context(0, model_path=None)
     try:
-        c.load_weights_h(_header(name))
-        g = _geom(**GEOMS[name])
-        audio = _signals(160, g.n_samples, 7)
+        c.load_weights_h(header(name))
+        g = geom(**GEOMS[name])
+        audio = signals(160, g.n_samples, 7)
         r = c.kws_geom(audio, g)
         gc = g.to_ctypes()
         F = g.frame_count
@@ -187,9 +135,9 @@ def test_errors_and_recovery():
     from edison_amd.context import Context, _np_ptr
     c = Context(0, model_path=None)
     try:
-        c.load_weights_h(_header("kws_small"))
-        g = _geom(**GEOMS["kws_small"])
-        audio = _signals(20, g.n_samples, 5)
+        c.load_weights_h(header("kws_small"))
+        g = geom(**GEOMS["kws_small"])
+        audio = signals(20, g.n_samples, 5)
         good = c.kws_geom(audio, g)
 
         def code(gg, n_utt=2, stride=None, a=audio):
@@ -231,9 +179,9 @@ def test_state_isolation():
     """Two geometries in turn on one context, with kws() and edison_mfcc_configure calls in between: every result equals a fresh
     context's, and kws() is byte-identical before and after."""
     from edison_amd.context import Context
-    g1 = _geom()
-    g2 = _geom(**GEOMS["kws_small"])   # 31 x 13 as well: the shipped graph takes it
-    audio = _signals(300, 32000, 21)
+    g1 = geom()
+    g2 = geom(**GEOMS["kws_small"])   # 31 x 13 as well: the shipped graph takes it
+    audio = signals(300, 32000, 21)
 
     def fresh(fn):
         f = Context(0)
@@ -273,13 +221,13 @@ def test_ragged_and_odd_shapes(oracle_mod):
     from edison_amd.context import Context
     c = Context(0, model_path=None)
     try:
-        c.load_weights_h(_header("same_stride"))
-        g = _geom(**GEOMS["same_stride"])
-        stream = _signals(1, 300 * 16000, 3).reshape(-1)
+        c.load_weights_h(header("same_stride"))
+        g = geom(**GEOMS["same_stride"])
+        stream = signals(1, 300 * 16000, 3).reshape(-1)
         for stride, n in ((16000 + 37, 200), (16000 * 3 + 1, 90), (5003, 700), (800, 1000), (1, 500), (0, 3)):
             r = c.kws_geom(stream, g, n_utt=n, utt_stride=stride)
             _check_against_oracle(c, r, _oracle_feat(oracle_mod, stream, g, starts=[u * stride for u in range(n)]))
-        one = _signals(5, g.n_samples, 8)[4]
+        one = signals(5, g.n_samples, 8)[4]
         r = c.kws_geom(one, g, n_utt=1)
         _check_against_oracle(c, r, _oracle_feat(oracle_mod, one[None, :], g))
     finally:
@@ -294,9 +242,9 @@ def test_host_flow_with_a_geometry(tmp_path):
     from edison_amd.kws import kws_host
     c = Context(0, model_path=None)
     try:
-        c.load_weights_h(_header("square"))
-        g = _geom(**GEOMS["square"])
-        x = _signals(5, 20000, 4)[4]
+        c.load_weights_h(header("square"))
+        g = geom(**GEOMS["square"])
+        x = signals(5, 20000, 4)[4]
         path = str(tmp_path / "u.wav")
         wavfile.write(path, 16000, x)
         r = kws_host.file_inference(path, ctx=c, verbose=False, geometry=g)
@@ -311,7 +259,7 @@ def test_host_flow_with_a_geometry(tmp_path):
         c.close()
     d = Context(0)
     try:
-        x = _signals(5, 32000, 4)[4]
+        x = signals(5, 32000, 4)[4]
         path = str(tmp_path / "v.wav")
         wavfile.write(path, 16000, x)
         r = kws_host.file_inference(path, ctx=d, verbose=False)

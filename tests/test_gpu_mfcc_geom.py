@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 
 import geom_sweep as gs
+from geom_sweep import GEOMS, geom, signals
 from test_gpu_generic import GOLDEN, _near
-from test_gpu_kws_geom import GEOMS, _geom, _signals
 
 pytestmark = pytest.mark.gpu
 
@@ -37,21 +37,21 @@ def test_whole_rows_equal_the_reference(idx):
     len(x) samples: variants A, B and B with log equal the reference's own mfcc / mfcc_mcu outputs within the bar. No model is loaded."""
     from edison_amd import _lib
     from edison_amd.context import Context
-    geom = np.load(GOLDEN)
-    name = str(geom["names"][idx])
-    N, step, nm, lo, hi, scale = geom["configs"][idx]
+    golden = np.load(GOLDEN)
+    name = str(golden["names"][idx])
+    N, step, nm, lo, hi, scale = golden["configs"][idx]
     N, step, nm = int(N), int(step), int(nm)
     c = Context(0, model_path=None)
     try:
         for sname in ("edison", "noise"):
-            x = geom["in_" + sname]
+            x = golden["in_" + sname]
             k = "%s_%s_" % (name, sname)
             for tag, variant, use_log in (("A", _lib.MFCC_A, False), ("B", _lib.MFCC_B, False), ("Blog", _lib.MFCC_B, True)):
-                g = _geom(variant=variant, use_log=use_log, frame_len=N, frame_step=step, n_samples=len(x), mel_nbins=nm, first_mfcc=0,
-                          num_mfcc=nm, sample_rate=16000.0, lower_edge_hertz=float(lo), upper_edge_hertz=float(hi), mel_mtx_scale=float(scale))
+                g = geom(variant=variant, use_log=use_log, frame_len=N, frame_step=step, n_samples=len(x), mel_nbins=nm, first_mfcc=0,
+                         num_mfcc=nm, sample_rate=16000.0, lower_edge_hertz=float(lo), upper_edge_hertz=float(hi), mel_mtx_scale=float(scale))
                 got = c.mfcc_geom(x, g)
                 assert got.shape == (1, g.frame_count, nm) and got.dtype == np.float64
-                _near(got[0], geom[k + tag + "_mfcc"], k + tag + "_mfcc")
+                _near(got[0], golden[k + tag + "_mfcc"], k + tag + "_mfcc")
     finally:
         c.close()
 
@@ -121,8 +121,8 @@ def test_shipped_geometry_rounds_to_the_exact_kws_features():
     from edison_amd.context import Context
     c = Context(0)
     try:
-        g = _geom()
-        audio = _signals(16384, 32000, 11)
+        g = geom()
+        audio = signals(16384, 32000, 11)
         y = c.mfcc_geom(audio, g)
         assert y.shape == (16384, 31, 13)
         mine = _int8(y, g.net_input_scale).reshape(16384, 403)
@@ -136,7 +136,7 @@ CASES = ["shipped"] + sorted(GEOMS)
 
 
 def _case(name):
-    return _geom() if name == "shipped" else _geom(**GEOMS[name])
+    return geom() if name == "shipped" else geom(**GEOMS[name])
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -148,7 +148,7 @@ def test_dataset_features_in_one_call(oracle_mod, name):
     from edison_amd.context import Context
     from edison_amd.kws.features import dataset_features
     g = _case(name)
-    x = _signals(40, g.n_samples + 37, 5 + CASES.index(name))
+    x = signals(40, g.n_samples + 37, 5 + CASES.index(name))
     c = Context(0, model_path=None)
     try:
         got = dataset_features(x, geometry=g, ctx=c)
@@ -223,7 +223,7 @@ def test_errors_and_state():
         _near(want_b, y_b[:3], "n4093")
         x = np.zeros(50000, np.int16)
         out = np.zeros(50000 * 8)
-        base = _geom(frame_len=400, frame_step=160, n_samples=16000, mel_nbins=40, num_mfcc=13)
+        base = geom(frame_len=400, frame_step=160, n_samples=16000, mel_nbins=40, num_mfcc=13)
 
         def code(**changes):
             g = base.to_ctypes()
@@ -257,7 +257,7 @@ def test_errors_and_state():
         assert c._L.edison_mfcc_geom_batch_dev(c._h, ctypes.byref(gc), x.ctypes.data_as(ctypes.c_void_p), (1 << 31) // 98 + 1, 0,
                                                out.ctypes.data_as(ctypes.c_void_p)) == _lib.E_ARGUMENT
         with pytest.raises(_lib.EdisonError):
-            c.mfcc_geom(audio_a, _geom(frame_len=5000, frame_step=5000, n_samples=16000))
+            c.mfcc_geom(audio_a, geom(frame_len=5000, frame_step=5000, n_samples=16000))
         for _ in range(2):
             assert np.array_equal(c.mfcc_geom(audio_a, ga), want_a)
             assert np.array_equal(c.mfcc_geom(audio_b, gb), want_b)

@@ -2,7 +2,7 @@
 is the host flow restated frame by frame: with z = the recording behind T = max(0, frame_len - frame_step) zeros, frame k is
 oracle.mfcc_numpy on z[k * frame_step:], its int8 row oracle.net_input; window k is rows k - F + 1 .. k with zero rows in front of the
 recording; the graph runs on those windows through ctx.net. Graphs: the five committed alt_models at their geometry
-(test_gpu_kws_geom.GEOMS) and the shipped graph at edison_kws_geom_default. Everything is compared bit for bit."""
+(geom_sweep.GEOMS) and the shipped graph at edison_kws_geom_default. Everything is compared bit for bit."""
 import os
 import subprocess
 import sys
@@ -11,47 +11,18 @@ from dataclasses import replace
 import numpy as np
 import pytest
 
-from test_gpu_kws_geom import GEOMS, _geom, _header, _same, _signals
+from geom_sweep import GEOMS, geom, header, signals
+from stream_drive import Kind, drive_stream, filter_ref, oracle_rows, recording, same, tail, whole
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRAPHS = ["shipped"] + sorted(GEOMS)
-
-
-def _open(name):
-    """(context with the graph loaded, its geometry)."""
-    from edison_amd.context import Context
-    if name == "shipped":
-        return Context(0), _geom()
-    c = Context(0, model_path=None)
-    c.load_weights_h(_header(name))
-    return c, _geom(**GEOMS[name])
-
-
-def _tail(g):
-    return max(0, g.frame_len - g.frame_step)
-
-
-def _recording(g, n_frames, seed):
-    """n_frames hops of the _signals mix (silence, noise, tones, clipping, the `edison` utterance) back to back."""
-    n = n_frames * g.frame_step
-    per = max(g.n_samples, 8000)
-    return _signals(-(-n // per) + 1, per, seed).ravel()[:n].copy()
-
-
-def _oracle_rows(oracle_mod, g, x):
-    """int8 [K][num_mfcc]: the host flow's row of every frame of the stream on x."""
-    import geom_sweep
-    K = x.shape[0] // g.frame_step
-    z = np.concatenate([np.zeros(_tail(g), np.int16), x])
-    gk = replace(g, frame_count_=K, n_samples=z.shape[0])
-    y = geom_sweep.oracle_mfcc(oracle_mod, z[None, :], gk)
-    return geom_sweep.oracle_feat(oracle_mod, y, gk).reshape(K, g.num_mfcc)
+KIND = Kind("int8")
 
 
 def _oracle_outputs(c, oracle_mod, g, x):
-    rows = _oracle_rows(oracle_mod, g, x)
+    rows = oracle_rows(oracle_mod, g, x)
     F = g.frame_count
     r = np.concatenate([np.zeros((F - 1, g.num_mfcc), np.int8), rows])
     win = np.lib.stride_tricks.sliding_window_view(r, (F, g.num_mfcc))[:, 0].reshape(rows.shape[0], -1)
@@ -60,70 +31,24 @@ def _oracle_outputs(c, oracle_mod, g, x):
 
 def _dev_stream(c, g, x, chunk, s=None, filt=False):
     """Device pushes of `chunk` frames, a ragged last push through push_n_dev; returns the outputs (and the filtered ones)."""
-    import torch
-    from edison_amd.stream import GeomStream
-    dev = torch.device("cuda", c.device)
-    info = c.net_info()
-    no = info["n_out"]
-    own = s is None
-    s = s or GeomStream(c, g, chunk_frames=chunk, output_filter=filt)
-    K = x.shape[0] // g.frame_step
-    xt = torch.from_numpy(x).to(dev)
-    lo = torch.zeros((K, no), dtype=torch.int8, device=dev)
-    so = torch.zeros((K, no), dtype=torch.int8, device=dev) if info["has_softmax"] else None
-    am = torch.zeros(K, dtype=torch.int32, device=dev)
-    fl = torch.zeros((K, no), dtype=torch.float32, device=dev) if filt else None
-    li = torch.zeros(K, dtype=torch.int32, device=dev) if filt else None
-    sp = torch.zeros(K, dtype=torch.int32, device=dev) if filt else None
-    h = g.frame_step
-    c.use_torch_stream(torch.cuda.current_stream(dev))
-    try:
-        for k0 in range(0, K, chunk):
-            n = min(chunk, K - k0)
-            sl = slice(k0, k0 + n)
-            kw = dict(logits=lo[sl], softmax=None if so is None else so[sl], argmax=am[sl])
-            if filt:
-                kw.update(filtered=fl[sl], likely=li[sl], spotted=sp[sl])
-            s.push_t(xt[k0 * h:(k0 + n) * h], n_frames=None if n == chunk else n, **kw)
-        torch.cuda.synchronize(dev)
-    finally:
-        c.use_own_stream()
-    if own:
-        s.close()
-    out = dict(logits=lo.cpu().numpy(), softmax=None if so is None else so.cpu().numpy(), argmax=am.cpu().numpy())
-    if filt:
-        out.update(filtered=fl.cpu().numpy(), likely=li.cpu().numpy(), spotted=sp.cpu().numpy())
-    return out
+    return drive_stream(KIND, c, g, x, whole(x.shape[0] // g.frame_step, chunk), chunk=chunk, stream=s, filt=filt)[0]
 
 
 def _same_outputs(got, want, what):
-    _same(got["logits"], want["logits"], what + " logits")
-    _same(got["argmax"], want["argmax"], what + " argmax")
+    same(got["logits"], want["logits"], what + " logits")
+    same(got["argmax"], want["argmax"], what + " argmax")
     if want["softmax"] is None:
         assert got["softmax"] is None, what
     else:
-        _same(got["softmax"], want["softmax"], what + " softmax")
-
-
-def _filter_ref(x, alpha, threshold):
-    """The firmware's filter over n_out classes in numpy: float64 product, float64 sum (each rounded), float32 state; first maximum."""
-    y = np.zeros(x.shape[1], np.float32)
-    oma = 1.0 - alpha
-    filt = np.zeros(x.shape, np.float32)
-    for i in range(x.shape[0]):
-        y = (alpha * y.astype(np.float64) + oma * x[i].astype(np.float64)).astype(np.float32)
-        filt[i] = y
-    likely = np.argmax(filt, axis=1).astype(np.int32)
-    best = filt[np.arange(x.shape[0]), likely].astype(np.float64)
-    return filt, likely, np.where(best > threshold, likely, -1).astype(np.int32)
+        same(got["softmax"], want["softmax"], what + " softmax")
 
 
 @pytest.mark.parametrize("name", GRAPHS)
 def test_device_pushes_equal_the_host_flow(oracle_mod, name):
     """Chunks 1, 7 and 512 with a ragged last push; chunks 1 and 7 wrap the sliding buffers many times (the shift kernel runs)."""
-    c, g = _open(name)
+    c, g = KIND.open(name)
     try:
-        x = _recording(g, 300, 7 + len(name))
+        x = recording(g, 300, 7 + len(name))
         want = _oracle_outputs(c, oracle_mod, g, x)
         for chunk in (1, 7, 512):
             _same_outputs(_dev_stream(c, g, x, chunk), want, "%s chunk %d" % (name, chunk))
@@ -135,12 +60,12 @@ def test_device_pushes_equal_the_host_flow(oracle_mod, name):
 def test_outputs_of_full_windows_equal_the_batch_call(name):
     """Outputs F - 1 .. of a long stream (chunk 512, the buffers wrapped several times) equal one kws_geom batch call with utt_stride =
     frame_step on the same zero-led recording."""
-    c, g = _open(name)
+    c, g = KIND.open(name)
     try:
         K = 512 * 20 + 37
-        x = _recording(g, K, 31 + len(name))
+        x = recording(g, K, 31 + len(name))
         got = _dev_stream(c, g, x, 512)
-        z = np.concatenate([np.zeros(_tail(g), np.int16), x])
+        z = np.concatenate([np.zeros(tail(g), np.int16), x])
         F = g.frame_count
         n_utt = K - F + 1
         r = c.kws_geom(z, g, n_utt=n_utt, utt_stride=g.frame_step)
@@ -148,7 +73,7 @@ def test_outputs_of_full_windows_equal_the_batch_call(name):
             if r[k] is None:
                 assert got[k] is None
             else:
-                _same(got[k][F - 1:], r[k], "%s %s" % (name, k))
+                same(got[k][F - 1:], r[k], "%s %s" % (name, k))
     finally:
         c.close()
 
@@ -156,11 +81,11 @@ def test_outputs_of_full_windows_equal_the_batch_call(name):
 @pytest.mark.parametrize("name", ["shipped", "square", "odd_no_softmax"])
 def test_host_device_and_alternating_pushes_agree(oracle_mod, name):
     from edison_amd.stream import GeomStream
-    c, g = _open(name)
+    c, g = KIND.open(name)
     try:
         chunk = 7
         K = 7 * 40
-        x = _recording(g, K, 55)
+        x = recording(g, K, 55)
         want = _oracle_outputs(c, oracle_mod, g, x)
         h = g.frame_step * chunk
         s = GeomStream(c, g, chunk_frames=chunk)
@@ -194,9 +119,9 @@ def test_every_network_route(oracle_mod, name):
     """The default route, the general matrix-core kernel (EDISON_NET_FORCE_GENERAL for the shipped graph), the graph's own kernel
     (edison_net_specialize, where a compiler exists) and, in a child process with EDISON_NET_NO_MFMA=1, the layer-by-layer kernel."""
     from edison_amd import _lib
-    c, g = _open(name)
+    c, g = KIND.open(name)
     try:
-        x = _recording(g, 120, 77)
+        x = recording(g, 120, 77)
         want = _oracle_outputs(c, oracle_mod, g, x)
         _same_outputs(_route_outputs(c, g, x), want, name + " default route")
         os.environ["EDISON_NET_FORCE_GENERAL"] = "1"
@@ -220,8 +145,8 @@ sys.path.insert(0, %r); sys.path.insert(0, %r)
 import test_gpu_stream_geom as t
 out = {}
 for name in ("shipped", "square", "odd_no_softmax"):
-    c, g = t._open(name)
-    x = t._recording(g, 120, 77)
+    c, g = t.KIND.open(name)
+    x = t.recording(g, 120, 77)
     r = t._dev_stream(c, g, x, 7)
     for k, v in r.items():
         if v is not None:
@@ -235,9 +160,9 @@ print("child ok")
     assert r.returncode == 0 and "child ok" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
     got = np.load(tmp_path / "lbl.npz")
     for name in ("shipped", "square", "odd_no_softmax"):
-        c, g = _open(name)
+        c, g = KIND.open(name)
         try:
-            x = _recording(g, 120, 77)
+            x = recording(g, 120, 77)
             want = _oracle_outputs(c, oracle_mod, g, x)
             sub = {k: (got[name + "/" + k] if name + "/" + k in got else None) for k in ("logits", "softmax", "argmax")}
             _same_outputs(sub, want, name + " layer-by-layer kernel")
@@ -250,26 +175,26 @@ def test_output_filter(oracle_mod, name):
     """filtered / likely / spotted equal the numpy recurrence on the host flow's outputs (softmax, or logits without Softmax), for host
     pushes and device pushes; alpha and threshold away from the defaults too."""
     from edison_amd.stream import GeomStream
-    c, g = _open(name)
+    c, g = KIND.open(name)
     try:
         K = 7 * 30
-        x = _recording(g, K, 91)
+        x = recording(g, K, 91)
         want = _oracle_outputs(c, oracle_mod, g, x)
         xin = want["softmax"] if want["softmax"] is not None else want["logits"]
         for alpha, thr in ((0.9, 0.5), (0.6, 3.0)):
-            ref = _filter_ref(xin, alpha, thr)
+            ref = filter_ref(xin, alpha, thr)
             s = GeomStream(c, g, chunk_frames=7, output_filter=True, alpha=alpha, threshold=thr)
             h = 7 * g.frame_step
             outs = [s.push(x[i * h:(i + 1) * h]) for i in range(K // 7)]
             for k, r in zip(("filtered", "likely", "spotted"), ref):
-                _same(np.concatenate([o[k] for o in outs]), r, "%s host %s" % (name, k))
+                same(np.concatenate([o[k] for o in outs]), r, "%s host %s" % (name, k))
             assert ("keywords" in outs[0]) == (c.net_info()["n_out"] == 10)
             s.close()
             s = GeomStream(c, g, chunk_frames=7, output_filter=True, alpha=alpha, threshold=thr)
             d = _dev_stream(c, g, x, 7, s=s, filt=True)
             s.close()
             for k, r in zip(("filtered", "likely", "spotted"), ref):
-                _same(d[k], r, "%s device %s" % (name, k))
+                same(d[k], r, "%s device %s" % (name, k))
     finally:
         c.close()
 
@@ -279,17 +204,17 @@ def test_state_machine_at_the_shipped_geometry(oracle_mod):
     the machine."""
     from oracle import fsm_ref
     from edison_amd.stream import GeomStream
-    c, g = _open("shipped")
+    c, g = KIND.open("shipped")
     try:
         K = 4 * 250
-        x = _recording(g, K, 5)
+        x = recording(g, K, 5)
         s = GeomStream(c, g, chunk_frames=250, fsm=True)
         for _ in range(2):
             outs = [s.push(x[i * 250 * 1024:(i + 1) * 250 * 1024]) for i in range(4)]
             filt = np.concatenate([o["filtered"] for o in outs])
             likely = np.concatenate([o["likely"] for o in outs])
             states, _ = fsm_ref.walk(filt[np.arange(K), likely], likely, 64000)
-            _same(np.concatenate([o["fsm_states"] for o in outs]), np.array(states, np.int32), "fsm states")
+            same(np.concatenate([o["fsm_states"] for o in outs]), np.array(states, np.int32), "fsm states")
             s.reset()
         s.close()
     finally:
@@ -301,9 +226,9 @@ def test_reset_batch_calls_and_frames_seen(oracle_mod):
     frames_seen counts frames, ragged pushes included."""
     import torch
     from edison_amd.stream import GeomStream
-    c, g = _open("shipped")
+    c, g = KIND.open("shipped")
     try:
-        x = _recording(g, 70, 13)
+        x = recording(g, 70, 13)
         fresh = _dev_stream(c, g, x, 7)
         s = GeomStream(c, g, chunk_frames=7)
         _dev_stream(c, g, x[:33 * 1024], 7, s=s)
@@ -311,15 +236,15 @@ def test_reset_batch_calls_and_frames_seen(oracle_mod):
         s.reset()
         assert s.frames_seen == 0
         # a batch call at another geometry between every two pushes: the context's table cache flips, the stream's tables stay
-        other = _geom(frame_len=512, frame_step=256, n_samples=512 + 30 * 256, mel_nbins=20, num_mfcc=13)
-        noise = _signals(4, other.n_samples, 3)
+        other = geom(frame_len=512, frame_step=256, n_samples=512 + 30 * 256, mel_nbins=20, num_mfcc=13)
+        noise = signals(4, other.n_samples, 3)
         dev = torch.device("cuda", c.device)
         lo = []
         for i in range(10):
             seg = x[i * 7 * 1024:(i + 1) * 7 * 1024]
             lo.append(_dev_stream(c, g, seg, 7, s=s)["logits"])
             c.kws_geom(noise, other)
-        _same(np.concatenate(lo), fresh["logits"], "logits after reset with interleaved batch calls")
+        same(np.concatenate(lo), fresh["logits"], "logits after reset with interleaved batch calls")
         assert s.frames_seen == 70
         s.close()
         torch.cuda.synchronize(dev)
@@ -333,7 +258,7 @@ def test_errors():
     from edison_amd.stream import GeomStream
     c = Context(0, model_path=None)
     try:
-        g = _geom()
+        g = geom()
         with pytest.raises(_lib.EdisonError) as e:
             GeomStream(c, g)
         assert e.value.code == _lib.E_NO_MODEL
@@ -366,8 +291,8 @@ def test_errors():
         assert e.value.code == _lib.E_ARGUMENT
         s.close()
         # the state machine needs 10 outputs
-        c.load_weights_h(_header("same_stride"))    # 5 outputs
-        gs = _geom(**GEOMS["same_stride"])
+        c.load_weights_h(header("same_stride"))    # 5 outputs
+        gs = geom(**GEOMS["same_stride"])
         with pytest.raises(_lib.EdisonError) as e:
             GeomStream(c, gs, fsm=True)
         assert e.value.code == _lib.E_NO_IMPL
@@ -382,9 +307,9 @@ def test_kws_live_with_a_geometry(tmp_path):
     import wave
     from edison_amd.kws import kws_live
     for name in ("shipped", "odd_no_softmax"):
-        c, g = _open(name)
+        c, g = KIND.open(name)
         try:
-            x = _recording(g, 50, 2)
+            x = recording(g, 50, 2)
             p = str(tmp_path / (name + ".wav"))
             with wave.open(p, "wb") as w:
                 w.setnchannels(1)

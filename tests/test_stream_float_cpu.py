@@ -142,14 +142,13 @@ def test_host_reference_agrees_with_the_batch_form(oracle_mod, name):
     import cube_synth
     import fnet_host
     from edison_amd import cube_import
-    from test_gpu_kws_geom import GEOMS, _geom
-    from test_gpu_stream_float import SYNTH, _import
-    from test_gpu_stream_geom import _recording, _tail
-    g = _geom(**GEOMS[name])
+    from geom_sweep import GEOMS, geom
+    from stream_drive import SYNTH, import_sources, recording, tail
+    g = geom(**GEOMS[name])
     F, nm = g.frame_count, g.num_mfcc
     K = F + 5
-    x = _recording(g, K, 3)
-    z = np.concatenate([np.zeros(_tail(g), np.int16), x])
+    x = recording(g, K, 3)
+    z = np.concatenate([np.zeros(tail(g), np.int16), x])
     # one row per frame: frame k is the MFCC of z[k * frame_step ..)
     one = replace(g, frame_count_=1, n_samples=g.frame_len)
     rows = np.stack([_float_rows(oracle_mod, one, z, [k * g.frame_step])[0] for k in range(K)])
@@ -158,5 +157,5 @@ def test_host_reference_agrees_with_the_batch_form(oracle_mod, name):
     batch = _float_rows(oracle_mod, g, z, [(k - F + 1) * g.frame_step for k in range(F - 1, K)])
     assert np.array_equal(win[F - 1:], batch)
     assert not win[0, :(F - 1) * nm].any() and np.array_equal(win[0, (F - 1) * nm:], rows[0])
-    model = cube_import.read_blob(_import(cube_synth.cube_sources((F, nm, 1), SYNTH, seed=len(name))))
+    model = cube_import.read_blob(import_sources(cube_synth.cube_sources((F, nm, 1), SYNTH, seed=len(name))))
     assert np.array_equal(fnet_host.run(model, win[F - 1:])[-1], fnet_host.run(model, batch)[-1])

@@ -1,5 +1,5 @@
 """CPU tests of the any-geometry stream's plumbing (no GPU): the C-ABI declares and the binding exposes edison_stream_geom_*, and the
-reference answer the GPU tests build frame by frame (test_gpu_stream_geom) agrees with the batch form of the host flow wherever a
+reference answer the GPU tests build frame by frame (stream_drive.oracle_rows) agrees with the batch form of the host flow wherever a
 window is full."""
 import os
 import re
@@ -35,15 +35,15 @@ def test_frame_by_frame_rows_equal_the_batch_host_flow(oracle_mod, name):
     """The GPU tests' reference: rows of the zero-led recording, windowed oldest first. For k >= F - 1 window k equals the batch host
     flow's features of the utterance at (k - F + 1) * frame_step -- also where frame_step > frame_len (kws_small)."""
     import geom_sweep
-    from test_gpu_kws_geom import GEOMS, _geom
-    from test_gpu_stream_geom import _oracle_rows, _recording, _tail
-    g = _geom() if name == "shipped" else _geom(**GEOMS[name])
+    from geom_sweep import GEOMS, geom
+    from stream_drive import oracle_rows, recording, tail
+    g = geom() if name == "shipped" else geom(**GEOMS[name])
     F = g.frame_count
     K = F + 6
-    x = _recording(g, K, 3)
-    rows = _oracle_rows(oracle_mod, g, x)
+    x = recording(g, K, 3)
+    rows = oracle_rows(oracle_mod, g, x)
     r = np.concatenate([np.zeros((F - 1, g.num_mfcc), np.int8), rows])
-    z = np.concatenate([np.zeros(_tail(g), np.int16), x])
+    z = np.concatenate([np.zeros(tail(g), np.int16), x])
     starts = [(k - F + 1) * g.frame_step for k in range(F - 1, K)]
     want = geom_sweep.oracle_feat(oracle_mod, geom_sweep.oracle_mfcc(oracle_mod, z, g, starts), g)
     got = np.stack([r[k:k + F].reshape(-1) for k in range(F - 1, K)])   # rows k - F + 1 .. k

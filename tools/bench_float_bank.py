@@ -39,7 +39,7 @@ def one_run(args):
     from edison_amd.context import Context
     from edison_amd.kws.geometry import KwsGeometry
     from edison_amd.stream import FloatBank, FloatStream
-    from test_gpu_kws_geom import _signals
+    from geom_sweep import signals
     dev = torch.device("cuda", 0)
     c = Context(0, model_path=None)
     c.fnet_load(os.path.join(ROOT, "tests", "golden", "cube_kws.ednf"))
@@ -49,7 +49,7 @@ def one_run(args):
     M, n, q15 = args.mics, args.chunk, bool(args.q15)
     c.use_torch_stream()
     # eight pushes of samples, another stretch of the signal mix for every microphone
-    tile = _signals(16 + n, g.n_samples, 1).ravel()
+    tile = signals(16 + n, g.n_samples, 1).ravel()
     starts = (np.arange(M) * 7919) % (tile.shape[0] - 8 * n * hop)
     x = np.stack([tile[s:s + 8 * n * hop] for s in starts])                                    # [M][8 * n * hop]
     X = [torch.from_numpy(np.ascontiguousarray(x[:, k * n * hop:(k + 1) * n * hop])).to(dev) for k in range(8)]

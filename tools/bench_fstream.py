@@ -42,8 +42,8 @@ def latency(push, frames, args):
 
 
 def audio(n):
-    from test_gpu_kws_geom import _signals
-    return np.resize(_signals(16, 32000, 1).ravel(), n)
+    from geom_sweep import signals
+    return np.resize(signals(16, 32000, 1).ravel(), n)
 
 
 def trace(c, g, args):

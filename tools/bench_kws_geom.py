@@ -45,18 +45,18 @@ def main():
     import torch
     from edison_amd import _lib
     from edison_amd.context import Context
-    from test_gpu_kws_geom import GEOMS, _geom, _header, _signals
+    from geom_sweep import GEOMS, geom, header, signals
     dev = torch.device("cuda", 0)
-    cases = [("shipped", None, {})] + [(n, _header(n), GEOMS[n]) for n in sorted(GEOMS)]
+    cases = [("shipped", None, {})] + [(n, header(n), GEOMS[n]) for n in sorted(GEOMS)]
     for name, header, kw in cases:
         c = Context(0, model_path=None) if header else Context(0)
         if header:
             c.load_weights_h(header)
         info = c.net_info()
         board = c.device_info()["name"]
-        g = _geom(**kw)
+        g = geom(**kw)
         F, nu = g.frame_count, args.utts
-        audio_h = _signals(64, g.n_samples, 1)
+        audio_h = signals(64, g.n_samples, 1)
         audio = torch.from_numpy(np.tile(audio_h, (nu // 64, 1))).to(dev)
         feat = torch.empty((nu, g.n_features), dtype=torch.int8, device=dev)
         logits = torch.empty((nu, info["n_out"]), dtype=torch.int8, device=dev)

@@ -52,15 +52,15 @@ def main():
     import torch
     from edison_amd.context import Context
     from edison_amd.kws.features import dataset_features
-    from test_gpu_kws_geom import GEOMS, _geom, _signals
+    from geom_sweep import GEOMS, geom, signals
     dev = torch.device("cuda", 0)
     cases = [("shipped", {})] + [(n, GEOMS[n]) for n in sorted(GEOMS)]
     for name, kw in cases:
         c = Context(0, model_path=None)
         board = c.device_info()["name"]
-        g = _geom(**kw)
+        g = geom(**kw)
         F, nu = g.frame_count, args.utts
-        audio_h = np.tile(_signals(64, g.n_samples, 1), (nu // 64, 1))
+        audio_h = np.tile(signals(64, g.n_samples, 1), (nu // 64, 1))
         audio = torch.from_numpy(audio_h).to(dev)
         out = torch.empty((nu, F, g.num_mfcc), dtype=torch.float64, device=dev)
         c.use_torch_stream()

@@ -35,17 +35,17 @@ def main():
     import torch
     from edison_amd.context import Context
     from edison_amd.stream import GeomStream, StreamBank
-    from test_gpu_kws_geom import _geom, _signals
+    from geom_sweep import geom, signals
     dev = torch.device("cuda", 0)
     c = Context(0)
     board = c.device_info()["name"]
-    g = _geom()
+    g = geom()
     hop, no = g.frame_step, c.net_info()["n_out"]
     c.use_torch_stream()
     rows = []
     for M in [int(v) for v in args.mics.split(",")]:
         # eight hops of samples, another stretch of the signal mix for every microphone
-        tile = _signals(16, g.n_samples, 1).ravel()
+        tile = signals(16, g.n_samples, 1).ravel()
         starts = (np.arange(M) * 7919) % (tile.shape[0] - 8 * hop)
         x = np.stack([tile[s:s + 8 * hop] for s in starts])                                    # [M][8 * hop]
         X = [torch.from_numpy(np.ascontiguousarray(x[:, k * hop:(k + 1) * hop])).to(dev) for k in range(8)]

@@ -68,19 +68,19 @@ def main():
     import torch
     from edison_amd.context import Context
     from edison_amd.stream import GeomStream
-    from test_gpu_kws_geom import GEOMS, _geom, _header, _signals
+    from geom_sweep import GEOMS, geom, header, signals
     dev = torch.device("cuda", 0)
-    cases = [("shipped", None, {})] + [(n, _header(n), GEOMS[n]) for n in sorted(GEOMS)]
+    cases = [("shipped", None, {})] + [(n, header(n), GEOMS[n]) for n in sorted(GEOMS)]
     for name, header, kw in cases:
         c = Context(0, model_path=None) if header else Context(0)
         if header:
             c.load_weights_h(header)
         info = c.net_info()
         board = c.device_info()["name"]
-        g = _geom(**kw)
+        g = geom(**kw)
         hop, F, ch = g.frame_step, g.frame_count, args.chunk
         K = int(args.hours * 3600 * g.sample_rate) // hop // ch * ch   # whole pushes of one hour
-        tile = _signals(16, g.n_samples, 1).ravel()
+        tile = signals(16, g.n_samples, 1).ravel()
         x = torch.from_numpy(np.resize(tile, K * hop)).to(dev)
         lo = torch.empty((ch, info["n_out"]), dtype=torch.int8, device=dev)
         am = torch.empty(ch, dtype=torch.int32, device=dev)

@@ -27,19 +27,19 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 def _oracle_chunk(job):
     g, lo, audio = job
     from oracle import oracle
-    from test_gpu_kws_geom import _oracle_feat
-    return lo, _oracle_feat(oracle, audio, g)
+    import geom_sweep as gs
+    return lo, gs.oracle_feat(oracle, gs.oracle_mfcc(oracle, audio, g), g)
 
 
 def _cases(args):
     """name -> (geometry, audio [n_utt][n_samples], a function that loads the row's graph into a context)."""
-    from test_gpu_kws_geom import GEOMS, _geom, _header, _signals
+    from geom_sweep import GEOMS, geom, header, signals
     out = {}
     if not args.sweep:
         for name in sorted(GEOMS):
-            g = _geom(**GEOMS[name])
+            g = geom(**GEOMS[name])
             n_utt = -(-args.frames_per_geometry // g.frame_count)
-            out[name] = (g, _signals(n_utt, g.n_samples, args.seed), lambda c, name=name: c.load_weights_h(_header(name)))
+            out[name] = (g, signals(n_utt, g.n_samples, args.seed), lambda c, name=name: c.load_weights_h(header(name)))
         return out
     from dataclasses import replace
     from oracle import oracle
@@ -47,8 +47,8 @@ def _cases(args):
     for name in sorted(gs.ROWS):
         g = gs.geometry(name)
         # the scale of tests/test_gpu_geom_sweep.py: from the oracle's coefficients over the test's own audio of the row
-        g = replace(g, net_input_scale=gs.sensitive_scale(gs.oracle_mfcc(oracle, gs.signals(name, g, gs.min_frames(name)), g)))
-        out[name] = (g, gs.signals(name, g, args.frames_per_geometry, seed=args.seed),
+        g = replace(g, net_input_scale=gs.sensitive_scale(gs.oracle_mfcc(oracle, gs.row_signals(name, g, gs.min_frames(name)), g)))
+        out[name] = (g, gs.row_signals(name, g, args.frames_per_geometry, seed=args.seed),
                      lambda c, name=name, g=g: c.load_model_bytes(gs.dense_graph(g, seed=sorted(gs.ROWS).index(name))))
     return out
 
