@@ -35,6 +35,15 @@ def pad_fit_set():
     return ftrain_ref.class_set(int(np.prod(fnet_rows.PAD[PAD_FIT_ROW][0]["in_shape"])), FIT_CLASSES, FIT_ROWS, 2025)
 
 
+# the from-scratch fit tests (test_ftrain_zoo_cpu in float64, test_gpu_ftrain_data on the GPU): the architecture and the steps at which
+# the float64 host trainer meets test_fit_learns_the_synthetic_set's conditions on fit_set()
+SCRATCH_ARCH, SCRATCH_STEPS = "single_fc", FIT_STEPS
+
+
+def scratch_model():
+    return train.get_model(SCRATCH_ARCH, fnet_rows.model(FIT_ROW)["in_shape"], FIT_CLASSES)
+
+
 def kws_set(in_n=403, classes=10, rows=96):
     """The same for `kws train` on a zoo network at 31 x 13 x 1: ten classes, 96 rows."""
     return ftrain_ref.class_set(in_n, classes, rows, 2026)

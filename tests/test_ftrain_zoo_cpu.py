@@ -16,17 +16,11 @@ from edison_amd import cube_import, train
 from edison_amd.kws import kws_train
 
 SHAPE_KEYS = ("inp", "out", "k", "s", "p", "relu", "cpad", "ppad")
-# the from-scratch fit tests (here in float64, tests/test_gpu_ftrain_data.py on the GPU): the architecture and the steps at which the
-# float64 host trainer meets test_fit_learns_the_synthetic_set's conditions on ftrain_rows.fit_set()
-SCRATCH_ARCH, SCRATCH_STEPS = "single_fc", ftrain_rows.FIT_STEPS
+SCRATCH_ARCH, SCRATCH_STEPS, scratch_model = ftrain_rows.SCRATCH_ARCH, ftrain_rows.SCRATCH_STEPS, ftrain_rows.scratch_model
 
 
 def shapes(model):
     return [tuple(tuple(int(v) for v in np.ravel(L[k])) for k in SHAPE_KEYS) for L in train.conv_records(model)]
-
-
-def scratch_model():
-    return train.get_model(SCRATCH_ARCH, fr.model(ftrain_rows.FIT_ROW)["in_shape"], ftrain_rows.FIT_CLASSES)
 
 
 @pytest.mark.parametrize("name", fr.ZOO)

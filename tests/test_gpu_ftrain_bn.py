@@ -5,7 +5,7 @@ max |g - g64| / max |g64|, allowed 4 x the same error of torch's CPU float32 aut
 8 x 2^-24 x sqrt(terms), terms counting N -- the +0.0f bias gradient of BatchNorm records and of all padding, repeatability, the batch
 and the moving statistics, row counts around the tile and beyond the grid, the fold and the eval call bit for bit, Adam steps, the
 refusals, fit and the CLI. tests/test_fbn_cpu.py shows the bound's precondition on the very inputs used here. Every network is loaded
-with 1e6 in all its weight padding (test_gpu_ftrain.poisoned)."""
+with 1e6 in all its weight padding (ftrain_drive.poisoned)."""
 import ctypes
 import io
 
@@ -16,47 +16,29 @@ import fnet_host
 import fnet_rows
 import ftrain_ref
 import ftrain_rows
-import test_gpu_ftrain as gt
 from edison_amd import _lib, cube_import, train
+from ftrain_drive import (EPS, POISON, case, check_gradient, data, fit_kw, follows_replay, kws_files, kws_quantized, kws_trained, loaded, own_context, poisoned,
+                          same_bits)
+from ftrain_rows import bn_case
 
 pytestmark = pytest.mark.gpu
 
-EPS = gt.EPS
 ULP4 = 4 * EPS
 
 
 @pytest.fixture(scope="module")
 def ctx(built_lib):
-    from edison_amd.context import Context
-    c = Context(0)
-    yield c
-    c.close()
+    yield from own_context()
 
 
 @pytest.fixture(scope="module")
 def fresh(built_lib):
-    from edison_amd.context import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-_POISONED = {}
-
-
-def loaded(ctx, name):
-    """Row `name` of ftrain_rows.BN_ROWS loaded with poisoned padding -> (its case, the mask of the packed array's real entries)."""
-    c = ftrain_rows.bn_case(name)
-    if name not in _POISONED:
-        _POISONED[name] = gt.poisoned(c["blob"])
-    bad, real = _POISONED[name]
-    ctx.fnet_load(bad)
-    return c, real
+    yield from own_context()
 
 
 def trainer_of(ctx, name, **kw):
     """A trainer on the loaded row `name` with its BatchNorm records, its dropout and, where the row sets gamma and beta, its state."""
-    c = ftrain_rows.bn_case(name)
+    c = bn_case(name)
     tr = ctx.trainer()
     tr.set_batchnorm(c["bn"], **kw)
     if c["dropout"] is not None:
@@ -70,10 +52,6 @@ def last_error(ctx):
     return (ctx._L.edison_last_error(ctx._h) or b"").decode()
 
 
-def same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
-
-
 def within(got, want, what):
     """4 x 2^-24 of the tensor's maximum."""
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
@@ -82,7 +60,7 @@ def within(got, want, what):
     assert err <= ULP4 * scale, (what, err, scale)
 
 
-def check_call(name, call, tr, r, real, ref, bounds):
+def check_bn_call(name, call, tr, r, real, ref, bounds):
     """One training call's loss, logits, gradients and their padding against the restatement. Returns the bits to repeat."""
     per, (lb, le), (zb, ze) = bounds
     z = tr.logits(len(r["loss"]))
@@ -124,7 +102,7 @@ def check_stats(name, call, tr, ref, after):
 
 @pytest.mark.parametrize("name", ftrain_rows.BN_ROWS)
 def test_two_training_calls_against_the_restatement(ctx, name):
-    c, real = loaded(ctx, name)
+    c, real = loaded(ctx, bn_case(name))
     x, y = c["x"], c["y"]
     with trainer_of(ctx, name) as tr:
         bn = tr.batchnorm()
@@ -138,7 +116,7 @@ def test_two_training_calls_against_the_restatement(ctx, name):
         kept = {}
         for call in (0, 1):
             ref, after = ftrain_rows.bn_reference(name, call)
-            kept[call] = check_call(name, call, tr, tr.grad(x, y), real, ref, ftrain_rows.bn_bounds(name, call))
+            kept[call] = check_bn_call(name, call, tr, tr.grad(x, y), real, ref, ftrain_rows.bn_bounds(name, call))
         if c["dropout"] is not None:
             assert tr.dropout_call == 2 and not same_bits(kept[0][1], kept[1][1])    # another mask
             tr.dropout_call = 1
@@ -156,7 +134,7 @@ def test_batch_and_moving_statistics_of_two_training_calls(ctx, name):
     float64 restatement's. The shipped row's deepest BatchNorm record is the hard one: its z has come through three convolutions and
     three normalisations and N is only 27. With one float32 MFMA chain over the whole of K its batch variance was 5.07e-07 of its
     maximum away; with the chains of 16 k that edb_conv_tile sums in double it is 1.11e-07 (allowed 2.38e-07)."""
-    c, _ = loaded(ctx, name)
+    c, _ = loaded(ctx, bn_case(name))
     with trainer_of(ctx, name) as tr:
         for call in (0, 1):
             ref, after = ftrain_rows.bn_reference(name, call)
@@ -166,7 +144,7 @@ def test_batch_and_moving_statistics_of_two_training_calls(ctx, name):
 
 @pytest.mark.parametrize("name", ["bn_p1", "bn_trunc"])
 def test_the_unbiased_flag_moves_the_variance_by_torchs_rule(ctx, name):
-    c, _ = loaded(ctx, name)
+    c, _ = loaded(ctx, bn_case(name))
     with trainer_of(ctx, name, unbiased=True, momentum=0.9) as tr:
         assert tr.batchnorm()["unbiased"] and tr.batchnorm()["momentum"] == 0.9
         state = c["state0"]
@@ -223,25 +201,25 @@ def check_rows(ctx, name, tr, c, real, x, y):
 
 @pytest.mark.parametrize("name", ["bn_p1", "bn_trunc"])
 def test_row_counts_around_the_tile(ctx, name):
-    c, real = loaded(ctx, name)
+    c, real = loaded(ctx, bn_case(name))
     with ctx.trainer() as probe:
         probe.set_batchnorm(c["bn"])
         b = probe.batchnorm()["batch"]
     assert b >= 3
     for n in (2, b - 1, b, b + 1, 3 * b + 2):
-        loaded(ctx, name)                                                       # a fresh load: a BatchNorm trainer folds into the loaded network
+        loaded(ctx, bn_case(name))                                              # a fresh load: a BatchNorm trainer folds into the loaded network
         with ctx.trainer(batchnorm=c["bn"]) as tr:
             x, y = drawn(c, n, 900 + n)
             check_rows(ctx, name, tr, c, real, x, y)
 
 
 def test_more_tiles_than_workgroups_and_the_cap(ctx):
-    c, real = loaded(ctx, "bn_p1")
+    c, real = loaded(ctx, bn_case("bn_p1"))
     with ctx.trainer() as probe:
         probe.set_batchnorm(c["bn"])
         b, grid = probe.batchnorm()["batch"], probe.info()["grid"]
     cap = 2 * grid * b + b + 1
-    loaded(ctx, "bn_p1")
+    loaded(ctx, bn_case("bn_p1"))
     with ctx.trainer(batchnorm=dict(has_bn=c["bn"], max_rows=cap)) as tr:
         assert tr.batchnorm()["max_rows"] == cap
         x, y = drawn(c, cap, 77)
@@ -264,7 +242,7 @@ def random_state(c, seed):
 
 @pytest.mark.parametrize("name", ["bn_pool21_neg", "bn_mixed"])
 def test_the_fold_and_the_eval_call(ctx, fresh, name):
-    c, real = loaded(ctx, name)
+    c, real = loaded(ctx, bn_case(name))
     x, y = c["x"], c["y"]
     with trainer_of(ctx, name) as tr:
         state = random_state(c, 5)
@@ -302,7 +280,7 @@ def test_the_fold_and_the_eval_call(ctx, fresh, name):
 
 @pytest.mark.parametrize("name", ["bn_mixed", "shipped"])
 def test_three_adam_steps_follow_the_host_trainer_on_the_gpus_gradients(ctx, fresh, name):
-    c, real = loaded(ctx, name)
+    c, real = loaded(ctx, bn_case(name))
     x, y = c["x"], c["y"]
     host = ftrain_ref.HostTrainer(c["model"], c["dropout"], seed=c["seed"], has_bn=c["bn"])
     with trainer_of(ctx, name) as tr:
@@ -321,7 +299,7 @@ def test_three_adam_steps_follow_the_host_trainer_on_the_gpus_gradients(ctx, fre
                     within(state[i]["beta"], host.state[i]["beta"], "%s step %d record %d beta" % (name, step, i))
         assert tr.info()["steps"] == 3
         # the master array's padding is the blob's poison, untouched
-        assert same_bits(tr.packed_weights()[~real], np.full(int((~real).sum()), 1.0e6, np.float32))
+        assert same_bits(tr.packed_weights()[~real], np.full(int((~real).sum()), POISON))
         fresh.fnet_load(cube_import.build_blob(tr.model()))
         assert same_bits(ctx.fnet(x)["logits"], fresh.fnet(x)["logits"])       # the context runs the refolded network
         # reset zeroes the moments of gamma and beta too, and leaves the moving statistics
@@ -334,7 +312,7 @@ def test_three_adam_steps_follow_the_host_trainer_on_the_gpus_gradients(ctx, fre
 
 def test_refusals(ctx):
     L = ctx._L
-    c, _ = loaded(ctx, "bn_p1")
+    c, _ = loaded(ctx, bn_case("bn_p1"))
     ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
 
     def code(tr, has_bn, n=None, momentum=0.99, eps=1e-3, rows=0, flags=0):
@@ -370,14 +348,14 @@ def test_refusals(ctx):
         assert e.value.code == _lib.E_ARGUMENT and "max_rows = 20" in str(e.value)
         tr.grad(x[:20], y[:20])
         tr.grad(x, y, training=False)                                           # an eval call is not capped
-    cd, _ = loaded(ctx, "bn_dense")
+    cd, _ = loaded(ctx, bn_case("bn_dense"))
     with ctx.trainer(batchnorm=dict(has_bn=cd["bn"], unbiased=True)) as tr:
         with pytest.raises(_lib.EdisonError) as e:
             tr.grad(cd["x"][:1], cd["y"][:1])                                  # N = 1 with the unbiased flag
         assert e.value.code == _lib.E_ARGUMENT and "N < 2" in str(e.value)
         tr.grad(cd["x"], cd["y"])
     # a list that marks no record still turns the BatchNorm trainer on: master weights, the fold, once per trainer
-    loaded(ctx, "bn_p1")
+    loaded(ctx, bn_case("bn_p1"))
     with ctx.trainer(batchnorm=[0, 0]) as tr:
         assert tr.batchnorm()["on"] and tr.batchnorm()["has_bn"] == [0, 0] and tr.bn_state() == [None, None]
         assert code(tr, [1, 0]) == _lib.E_ARGUMENT and "new trainer" in last_error(ctx)
@@ -393,8 +371,8 @@ def test_refusals(ctx):
 
 def test_a_trainer_without_batchnorm_is_unchanged(ctx):
     name = "pool21_trunc_h"
-    model, blob, real = gt.case(name)
-    x, y = gt.data(name, model, 17)
+    model, blob, real = case(name)
+    x, y = data(name, model, 17)
     ctx.fnet_load(blob)
     bits = []
     for _ in range(2):
@@ -407,7 +385,7 @@ def test_a_trainer_without_batchnorm_is_unchanged(ctx):
     ref = ftrain_ref.loss_grad(model, x, y)
     with ctx.trainer() as tr:
         tr.grad(x, y)
-        gt.check_gradient(name, tr, model, real, x, y, ref)
+        check_gradient(name, tr, model, real, x, y, ref)
 
 
 def test_fit_with_batchnorm_and_dropout_follows_the_float64_replay(ctx):
@@ -416,10 +394,9 @@ def test_fit_with_batchnorm_and_dropout_follows_the_float64_replay(ctx):
     the folded network."""
     x, y = ftrain_rows.fit_set()
     model = fnet_rows.model(ftrain_rows.FIT_ROW)
-    blob, _ = gt.poisoned(fnet_rows.blob(ftrain_rows.FIT_ROW))
-    ctx.fnet_load(blob)
+    ctx.fnet_load(poisoned(fnet_rows.blob(ftrain_rows.FIT_ROW))[0])
     bn, dropout = [1, 0], [(0.25, 1), 0]
-    kw = dict(epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=ftrain_rows.FIT_STEPS, val=(x, y), callbacks=False)
+    kw = dict(fit_kw(), val=(x, y), callbacks=False)
     with ctx.trainer(dropout=dropout, seed=3, batchnorm=bn) as tr:
         hist = tr.fit(x, y, **kw)
         assert hist["steps"] == 40 and tr.info()["steps"] == 40 and tr.dropout_call == 40
@@ -431,42 +408,24 @@ def test_fit_with_batchnorm_and_dropout_follows_the_float64_replay(ctx):
     replay = train.fit(host, x, y, **kw)
     print("loss %s\nreplay %s\nval %s\nreplay %s\naccuracy %.3f" % (np.round(hist["loss"], 5), np.round(replay["loss"], 5), np.round(hist["val_loss"], 5),
                                                                     np.round(replay["val_loss"], 5), acc))
-    assert len(hist["loss"]) == len(replay["loss"]) and host.call == 40
-    for got, want in zip(hist["loss"], replay["loss"]):
-        assert abs(got - want) <= 1e-3 * want, (hist["loss"], replay["loss"])
-    for got, want in zip(hist["val_loss"], replay["val_loss"]):
-        assert abs(got - want) <= 1e-3 * want, (hist["val_loss"], replay["val_loss"])
+    assert host.call == 40
+    follows_replay(hist, replay)
     assert hist["loss"][-1] < 0.5 * hist["loss"][0]
     assert acc == 1.0
 
 
 def test_kws_train_with_batchnorm_then_kws_quantize(ctx, tmp_path):
     """kws train --batchnorm-arch kws_conv --dropout-arch kws_conv on the shipped geometry with fresh weights, then kws quantize."""
-    from edison_amd import config as cfg
-    from edison_amd.kws import kws_quantize, kws_train
-    from edison_amd.kws.geometry import KwsGeometry
-    model = ftrain_rows.bn_case("shipped")["model"]
+    from edison_amd.kws import kws_train
+    model = bn_case("shipped")["model"]
     x, y = ftrain_rows.kws_set()
     keywords = ["k%d" % i for i in range(10)]
-    with open(tmp_path / "net.ednf", "wb") as f:
-        f.write(cube_import.build_blob(model, keywords))
-    np.save(tmp_path / "x.npy", x)
-    np.save(tmp_path / "y.npy", y)
-    args = [str(tmp_path / "net.ednf"), str(tmp_path / "x.npy"), str(tmp_path / "y.npy")]
-    val = (str(tmp_path / "x.npy"), str(tmp_path / "y.npy"))
-    out = io.StringIO()
-    blob, hist = kws_train.run(*args, str(tmp_path / "out.ednf"), epochs=3, batch=32, lr=0.01, val=val, ctx=ctx, out=out, dropout_arch="kws_conv",
-                               batchnorm_arch="kws_conv")
-    assert (tmp_path / "out.ednf").read_bytes() == blob and hist["steps"] == 9 and len(hist["val_loss"]) == 3
-    assert "after 9 steps" in out.getvalue() and hist["loss"][-1] < hist["loss"][0]
+    args, val = kws_files(tmp_path, model, x, y, keywords)
+    blob, hist, _, trained = kws_trained(ctx, tmp_path, args, val, epochs=3, dropout_arch="kws_conv", batchnorm_arch="kws_conv")
+    assert hist["loss"][-1] < hist["loss"][0]
     plain, _ = kws_train.run(*args, str(tmp_path / "plain.ednf"), epochs=3, batch=32, lr=0.01, val=val, ctx=ctx, out=io.StringIO(), dropout_arch="kws_conv")
     assert plain != blob and len(plain) == len(blob)                        # BatchNorm took part, and the format did not change
     assert kws_train.main(["train"] + args + [str(tmp_path / "cli.ednf"), "--epochs", "1", "--batch", "32", "--batchnorm-arch", "kws_conv",
                                               "--dropout-arch", "kws_conv", "--bn-momentum", "0.9"]) == 0
-    trained = cube_import.read_blob(blob)
     assert trained["keywords"] == keywords
-    g = KwsGeometry.from_config(net_input_scale=cfg.net_input_scale)
-    rng = np.random.default_rng(8)
-    np.save(tmp_path / "audio.npy", np.clip(rng.normal(0, 3000, (6, g.n_samples)), -32768, 32767).astype(np.int16))
-    qblob, rep = kws_quantize.run(str(tmp_path / "out.ednf"), str(tmp_path / "audio.npy"), str(tmp_path / "q.ednn"), ctx=ctx, out=io.StringIO())
-    assert (tmp_path / "q.ednn").read_bytes() == qblob and len(rep["float_argmax"]) == 6
+    kws_quantized(ctx, tmp_path)

@@ -9,35 +9,26 @@ import pytest
 
 import fnet_host as fh
 import fnet_rows as fr
+import ftrain_drive
 import ftrain_ref
 import ftrain_rows
 from edison_amd import _lib, cube_import, train
-from test_ftrain_zoo_cpu import SCRATCH_ARCH, SCRATCH_STEPS, scratch_model
+from ftrain_drive import EPS, fit_kw, kws_audio, kws_quantized, own_context, same_bits, sgd_step_checked, step_checked
+from ftrain_rows import SCRATCH_ARCH, SCRATCH_STEPS, scratch_model
 
 pytestmark = pytest.mark.gpu
 
-EPS = 2.0 ** -24
 SMALL_GEOMETRY = "frame_count=11,num_mfcc=6,n_samples=11264"       # test_kws_train_then_kws_quantize's: 11 x 6 features
 
 
 @pytest.fixture(scope="module")
 def ctx(built_lib):
-    from edison_amd.context import Context
-    c = Context(0)
-    yield c
-    c.close()
+    yield from own_context()
 
 
 @pytest.fixture(scope="module")
 def fresh(built_lib):
-    from edison_amd.context import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+    yield from own_context()
 
 
 def fc_case(in_shape, classes, n, seed=11):
@@ -53,8 +44,8 @@ def small_geometry():
     return parse_geometry(SMALL_GEOMETRY, net_input_scale=cfg.net_input_scale)
 
 
-def small_audio(n=6, seed=8):
-    return np.clip(np.random.default_rng(seed).normal(0, 3000, (n, 11 * 1024)), -32768, 32767).astype(np.int16)
+def small_audio():
+    return kws_audio(11 * 1024)
 
 
 # ---- the gather and the store ----------------------------------------------------------------------------------------------------------
@@ -68,7 +59,7 @@ def test_an_epoch_at_lr_zero_is_the_gradient_calls_batch_by_batch(ctx, in_shape,
     with ctx.train_data(x, y) as data, ctx.trainer() as tr, ctx.trainer() as other:
         assert data.n == n and data.in_n == x.shape[1] == tr.in_n
         gx, gy = data.rows()
-        assert np.array_equal(bits(gx), bits(x)) and np.array_equal(gy, y)
+        assert same_bits(gx, x) and np.array_equal(gy, y)
         w0 = tr.packed_weights()
         steps = 0
         for order in orders:
@@ -81,12 +72,12 @@ def test_an_epoch_at_lr_zero_is_the_gradient_calls_batch_by_batch(ctx, in_shape,
                 for b0 in range(0, len(order), bs):
                     pick = order[b0:b0 + bs]
                     want = other.grad(x[pick], y[pick])
-                    assert np.array_equal(bits(rows["loss"][b0:b0 + bs]), bits(want["loss"])), (len(order), bs, b0)
+                    assert same_bits(rows["loss"][b0:b0 + bs], want["loss"]), (len(order), bs, b0)
                     assert np.array_equal(rows["argmax"][b0:b0 + bs], want["argmax"]), (len(order), bs, b0)
                 assert r["hits"] == int((rows["argmax"] == y[order]).sum())
                 total = float(np.sum(rows["loss"].astype(np.float64)))
                 assert abs(r["loss_sum"] - total) <= len(order) * 2.0 ** -52 * float(np.abs(rows["loss"]).astype(np.float64).sum())
-        assert tr.info()["steps"] == steps and np.array_equal(bits(tr.packed_weights()), bits(w0))      # lr 0: the weights stay, Adam's t runs
+        assert tr.info()["steps"] == steps and same_bits(tr.packed_weights(), w0)      # lr 0: the weights stay, Adam's t runs
         # max_steps ends the epoch early; no rows, no steps
         r = tr.epoch(data, orders[0], 5, lr=0.0, max_steps=2)
         assert (r["seen"], r["steps"]) == (10, 2) and len(tr.epoch_rows()["loss"]) == 10
@@ -98,11 +89,11 @@ def test_an_epoch_at_lr_zero_is_the_gradient_calls_batch_by_batch(ctx, in_shape,
             by = (np.arange(m)[::-1] % classes).astype(np.int32)
             data.set(bx, by)
             gx, gy = data.rows()
-            assert data.n == m and np.array_equal(bits(gx), bits(bx)) and np.array_equal(gy, by)
+            assert data.n == m and same_bits(gx, bx) and np.array_equal(gy, by)
             order = np.arange(m)[::-1]
             tr.epoch(data, order, 16, lr=0.0)
             want = other.grad(bx[order[:16]], by[order[:16]])
-            assert np.array_equal(bits(tr.epoch_rows()["loss"][:16]), bits(want["loss"]))
+            assert same_bits(tr.epoch_rows()["loss"][:16], want["loss"])
         with pytest.raises(ValueError):
             data.set(bx, -by - 1)                                   # a label outside [0, 2^31)
         bad = by.copy()
@@ -119,7 +110,7 @@ def test_a_data_set_from_torch_device_tensors(ctx):
         data.set_t(torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda())
         torch.cuda.synchronize()
         gx, gy = data.rows()
-        assert data.n == 23 and np.array_equal(bits(gx), bits(x)) and np.array_equal(gy, y)
+        assert data.n == 23 and same_bits(gx, x) and np.array_equal(gy, y)
         assert tr.evaluate(data) == tr.evaluate(host)
 
 
@@ -135,7 +126,7 @@ def test_features_from_audio_are_kws_floats(ctx, q15):
         with ctx.train_data(audio=audio, y=labels, geometry=g, q15=q15, chunk=chunk) as data:
             gx, gy = data.rows()
             assert data.n == 6 and data.in_n == 66
-            assert np.array_equal(bits(gx), bits(want)), chunk
+            assert same_bits(gx, want), chunk
             assert np.array_equal(gy, labels)
     with train.DeviceData(ctx, 66) as data:
         from dataclasses import replace
@@ -167,8 +158,8 @@ def test_eval_sums_the_rows_in_double_in_a_fixed_order(ctx, n):
         assert np.float64(again["loss_sum"]).view(np.uint64) == np.float64(r["loss_sum"]).view(np.uint64) and again == r
         for b0 in range(0, n, 4096):                                 # 4097 crosses the 4096-row chunk
             want = tr.grad(3.0 * x[b0:b0 + 4096], y[b0:b0 + 4096], training=False)
-            assert np.array_equal(bits(rows["loss"][b0:b0 + 4096]), bits(want["loss"])) and np.array_equal(rows["argmax"][b0:b0 + 4096], want["argmax"])
-        assert np.array_equal(bits(tr.packed_weights()), bits(w0)) and tr.info() == info0
+            assert same_bits(rows["loss"][b0:b0 + 4096], want["loss"]) and np.array_equal(rows["argmax"][b0:b0 + 4096], want["argmax"])
+        assert same_bits(tr.packed_weights(), w0) and tr.info() == info0
 
 
 # ---- fit_data is fit -------------------------------------------------------------------------------------------------------------------
@@ -206,13 +197,13 @@ def test_fit_data_is_fit(ctx, fresh, kind):
             ha = a.fit(x, y, val=(vx, vy), **kw)
             hb = b.fit_data(data, val=val, **kw)
             assert ha["steps"] == hb["steps"] == (7 if extra else 15) == a.info()["steps"] == b.info()["steps"]
-            assert np.array_equal(bits(a.packed_weights()), bits(b.packed_weights()))
+            assert same_bits(a.packed_weights(), b.packed_weights())
             assert not np.array_equal(a.packed_weights(), train.pack([dict(w=L["w"], b=L["b"]) for L in train.conv_records(make())], a.layout))
             assert a.dropout()["call"] == b.dropout()["call"] == (ha["steps"] if "dropout" in targs else 0)
             for sa, sb in zip(a.bn_state(), b.bn_state()):
                 assert (sa is None) == (sb is None)
                 for k in sa or ():
-                    assert np.array_equal(bits(sa[k]), bits(sb[k])), k
+                    assert same_bits(sa[k], sb[k]), k
             for k in ("acc", "val_acc", "lr", "steps", "stopped_early"):
                 assert ha[k] == hb[k], (k, ha[k], hb[k])
             assert len(ha["loss"]) == len(hb["loss"]) == (2 if extra else 3) == len(hb["val_loss"])
@@ -220,7 +211,7 @@ def test_fit_data_is_fit(ctx, fresh, kind):
                 for va, vb in zip(ha[k], hb[k]):
                     assert abs(va - vb) <= 1e-12 * abs(va), (k, ha[k], hb[k])
             # the context runs the trained network, and the export is the host loop's
-            assert np.array_equal(bits(ctx.fnet(vx)["logits"]), bits(fresh.fnet(vx)["logits"]))
+            assert same_bits(ctx.fnet(vx)["logits"], fresh.fnet(vx)["logits"])
             assert a.export() == b.export()
 
 
@@ -232,7 +223,7 @@ def test_a_get_model_network_learns_the_synthetic_set_through_fit_data(ctx):
     assert (SCRATCH_ARCH, SCRATCH_STEPS) == ("single_fc", ftrain_rows.FIT_STEPS)
     model = scratch_model()
     ctx.fnet_load(cube_import.build_blob(model))
-    kw = dict(epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=SCRATCH_STEPS)
+    kw = fit_kw()
     with ctx.train_data(x, y) as data, ctx.trainer() as tr:
         hist = tr.fit_data(data, **kw)
         assert hist["steps"] == SCRATCH_STEPS == tr.info()["steps"]
@@ -244,54 +235,29 @@ def test_a_get_model_network_learns_the_synthetic_set_through_fit_data(ctx):
 
 
 # ---- Adadelta ----------------------------------------------------------------------------------------------------------------------------
-def tensors(tr, real):
-    for r in tr.layout:
-        nb = r["k_pad"] * r["n_pad"]
-        for lo, hi in ((r["w_at"], r["w_at"] + nb), (r["w_at"] + nb, r["w_at"] + nb + r["n_pad"])):
-            yield lo, hi, real[lo:hi]
-
-
-def adadelta_step_checked(tr, real, x, y, replay, lr, what):
-    """One gradient call and one step; the float64 replay takes it from the weights the GPU stepped from with the GPU's own gradient."""
-    w_before = tr.packed_weights().astype(np.float64)
-    tr.grad(x, y)
-    g = tr.gradient().astype(np.float64)
-    tr.step(lr)
-    want = [w_before.copy()]
-    replay.step(want, [g], lr)
-    got = tr.packed_weights()
-    for lo, hi, m in tensors(tr, real):
-        err = np.abs(got[lo:hi][m] - want[0][lo:hi][m]).max() / np.abs(want[0][lo:hi][m]).max()
-        print("%s tensor at %d: %.3g (bound %.3g)" % (what, lo, err, 4 * EPS))
-        assert err <= 4 * EPS, (what, lo, err)
-    assert (got[~real] == np.float32(1.0e6)).all()                    # zero gradient: the padding stays what it was
-    return w_before, g, got
-
-
 def test_adadelta_steps_against_the_float64_restatement(ctx):
-    import test_gpu_ftrain as gt
     name = "pool21_trunc_h"
-    model, blob, real = gt.case(name)
+    model, blob, real = ftrain_drive.case(name)
     ctx.fnet_load(blob)
-    x, y = gt.data(name, model, 17)
+    x, y = ftrain_drive.data(name, model, 17)
     with ctx.trainer() as tr:
         tr.set_opt("adadelta", rho=0.95, eps=1e-7)
         replay = ftrain_ref.Adadelta(0.95, 1e-7)
         for step in range(3):
-            w_before, g, got = adadelta_step_checked(tr, real, x, y, replay, 1.0, "step %d" % (step + 1))
-            moved = np.abs(got[real] - w_before[real])
+            s = step_checked(tr, real, x, y, [replay], 1.0, "step %d" % (step + 1))
+            moved = np.abs(s.got[real] - s.before.astype(np.float64)[real])
             assert moved.max() > 1e-4 and moved.max() < 0.1          # sqrt(eps / (1 - rho)) a step at first, growing slowly
         assert tr.info()["steps"] == 3
         # reset zeroes both averages: the next step is a first step again
         tr.reset()
         assert tr.info()["steps"] == 0
-        adadelta_step_checked(tr, real, x, y, ftrain_ref.Adadelta(0.95, 1e-7), 1.0, "after reset")
+        step_checked(tr, real, x, y, [ftrain_ref.Adadelta(0.95, 1e-7)], 1.0, "after reset")
         # other constants
         tr.reset()
         tr.set_opt("adadelta", rho=0.5, eps=1e-4)
         replay = ftrain_ref.Adadelta(0.5, 1e-4)
         for step in range(2):
-            adadelta_step_checked(tr, real, x, y, replay, 0.5, "rho 0.5 step %d" % (step + 1))
+            step_checked(tr, real, x, y, [replay], 0.5, "rho 0.5 step %d" % (step + 1))
         # refused settings leave the previous kind and constants
         for bad in (dict(rho=1.0), dict(rho=-0.1), dict(rho=float("nan")), dict(rho=0.95, eps=0.0), dict(rho=0.95, eps=-1e-7),
                     dict(rho=0.95, eps=float("inf"))):
@@ -304,15 +270,11 @@ def test_adadelta_steps_against_the_float64_restatement(ctx):
         for args, kw in ((("adadelta",), {}), (("adam",), dict(rho=0.9)), (("sgd",), dict(rho=0.9)), (("rmsprop",), {})):
             with pytest.raises(ValueError):                          # rho is stated for Adadelta and belongs to no other kind
                 tr.set_opt(*args, **kw)
-        adadelta_step_checked(tr, real, x, y, replay, 0.5, "after refusals")      # still Adadelta at rho 0.5, its state running on
+        step_checked(tr, real, x, y, [replay], 0.5, "after refusals")      # still Adadelta at rho 0.5, its state running on
         tr.set_opt("sgd")
         with pytest.raises(_lib.EdisonError):
             tr.set_opt("adadelta", rho=1.0)
-        w_before = tr.packed_weights().astype(np.float64)
-        tr.grad(x, y)
-        g = tr.gradient().astype(np.float64)
-        tr.step(0.1)
-        assert np.abs(tr.packed_weights()[real] - (w_before - 0.1 * g)[real]).max() <= 2 * EPS * np.abs(w_before[real]).max()      # still SGD
+        sgd_step_checked(tr, real, x, y, 0.1)                        # still SGD
 
 
 def test_adadelta_steps_gamma_and_beta_of_a_batchnorm_trainer(ctx):
@@ -357,11 +319,11 @@ def test_refusals_leave_the_weights_the_counters_and_the_store(ctx):
             with pytest.raises(_lib.EdisonError) as e:
                 call()
             assert e.value.code == code and all(w in str(e.value) for w in words), str(e.value)
-            assert np.array_equal(bits(tr.packed_weights()), bits(w0)) and tr.info() == info0 and tr.dropout()["call"] == call0
-            assert all(np.array_equal(bits(bn0[0][k]), bits(tr.bn_state()[0][k])) for k in bn0[0])
+            assert same_bits(tr.packed_weights(), w0) and tr.info() == info0 and tr.dropout()["call"] == call0
+            assert all(same_bits(bn0[0][k], tr.bn_state()[0][k]) for k in bn0[0])
             for d, (wx, wy) in ((data, (x, y)), (labelled, (x, y + 1))):
                 gx, gy = d.rows()
-                assert np.array_equal(bits(gx), bits(wx)) and np.array_equal(gy, wy)
+                assert same_bits(gx, wx) and np.array_equal(gy, wy)
 
         refused(_lib.E_ARGUMENT, ["max_rows = 5"], lambda: tr.epoch(data, np.arange(23), 6, lr=0.01))
         refused(_lib.E_ARGUMENT, ["batch"], lambda: tr.epoch(data, np.arange(23), 0, lr=0.01))
@@ -381,15 +343,14 @@ def test_refusals_leave_the_weights_the_counters_and_the_store(ctx):
                 call()
             assert e.value.code == _lib.E_NO_MODEL
         with ctx.trainer() as new:
-            assert np.array_equal(bits(new.packed_weights()), bits(train.pack([dict(w=L["w"], b=L["b"]) for L in train.conv_records(two_conv_model())],
-                                                                              new.layout)))
+            assert same_bits(new.packed_weights(), train.pack([dict(w=L["w"], b=L["b"]) for L in train.conv_records(two_conv_model())], new.layout))
             assert new.evaluate(data)["seen"] == 23 and not np.array_equal(w1, new.packed_weights())
 
 
 # ---- the command line ------------------------------------------------------------------------------------------------------------------
 def test_kws_train_from_scratch_resident_then_kws_quantize(ctx, tmp_path):
     from edison_amd import config as cfg
-    from edison_amd.kws import kws_quantize, kws_train
+    from edison_amd.kws import kws_train
     from edison_amd.kws.geometry import KwsGeometry
     rng = np.random.default_rng(12)
     y = (np.arange(64) % 10).astype(np.int32)
@@ -407,13 +368,11 @@ def test_kws_train_from_scratch_resident_then_kws_quantize(ctx, tmp_path):
     ctx.fnet_load(str(tmp_path / "out.ednf"))
     assert ctx.fnet_info()["n_out"] == 10 and ctx.fnet(x)["logits"].shape == (64, 10)
     g = KwsGeometry.from_config(net_input_scale=cfg.net_input_scale)
-    np.save(tmp_path / "audio.npy", np.clip(rng.normal(0, 3000, (6, g.n_samples)), -32768, 32767).astype(np.int16))
-    qblob, rep = kws_quantize.run(str(tmp_path / "out.ednf"), str(tmp_path / "audio.npy"), str(tmp_path / "q.ednn"), ctx=ctx, out=io.StringIO())
-    assert (tmp_path / "q.ednn").read_bytes() == qblob and len(rep["float_argmax"]) == 6
+    kws_quantized(ctx, tmp_path, np.clip(rng.normal(0, 3000, (6, g.n_samples)), -32768, 32767).astype(np.int16))     # this test's own draw
 
 
 def test_kws_train_from_audio_with_adadelta_then_kws_quantize(ctx, tmp_path):
-    from edison_amd.kws import kws_quantize, kws_train
+    from edison_amd.kws import kws_train
     audio = small_audio()
     np.save(tmp_path / "audio.npy", audio)
     np.save(tmp_path / "y.npy", (np.arange(6) % 3).astype(np.int32))
@@ -427,7 +386,5 @@ def test_kws_train_from_audio_with_adadelta_then_kws_quantize(ctx, tmp_path):
     assert len(adam) == len(ada) == len(start) and adam != start and ada != start and adam != ada
     ctx.fnet_load(adam)
     assert ctx.fnet_info()["n_out"] == 3
-    qblob, rep = kws_quantize.run(str(tmp_path / "out.ednf"), str(tmp_path / "audio.npy"), str(tmp_path / "q.ednn"), geometry=SMALL_GEOMETRY, ctx=ctx,
-                                  out=io.StringIO())
-    assert (tmp_path / "q.ednn").read_bytes() == qblob and len(rep["float_argmax"]) == 6
+    kws_quantized(ctx, tmp_path, audio, geometry=SMALL_GEOMETRY)
     assert kws_train.main(args + [str(tmp_path / "bad.ednf")] + opts[:6] + ["--audio", "--geometry", "frame_count=11,num_mfcc=5,n_samples=11264"]) == 1

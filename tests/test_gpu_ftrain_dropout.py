@@ -3,7 +3,7 @@ section 19b) against tests/fdrop_ref.py and tests/ftrain_ref.py: the logits bit 
 tensor against the float64 restatement with the mask by section 19's metric and bound -- per tensor max |g - g64| / max |g64|, allowed
 4 x the same error of torch's CPU float32 autograd with the same mask, floored at 8 x 2^-24 x sqrt(terms) -- the counter, the eval flag,
 the mask's independence of the tiling exactly, the refusals, fit and the CLI. tests/test_fdrop_cpu.py shows the bound's precondition
-on the very inputs used here. Every network is loaded with 1e6 in all its weight padding (test_gpu_ftrain.poisoned)."""
+on the very inputs used here. Every network is loaded with 1e6 in all its weight padding (ftrain_drive.poisoned)."""
 import ctypes
 import io
 import struct
@@ -16,8 +16,9 @@ import fnet_plan
 import fnet_rows
 import ftrain_ref
 import ftrain_rows
-import test_gpu_ftrain as gt
-from edison_amd import _lib, cube_import, train
+from edison_amd import _lib, train
+from ftrain_drive import fit_kw, follows_replay, kws_files, kws_quantized, kws_trained, loaded, own_context, poisoned, same_bits
+from ftrain_rows import drop_case
 
 pytestmark = pytest.mark.gpu
 
@@ -26,27 +27,7 @@ N = ftrain_rows.N_ROWS
 
 @pytest.fixture(scope="module")
 def ctx(built_lib):
-    from edison_amd.context import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-_POISONED = {}
-
-
-def loaded(ctx, name):
-    """Row `name` of ftrain_rows.DROP_ROWS loaded with poisoned padding -> (its case, the mask of the packed array's real entries)."""
-    c = ftrain_rows.drop_case(name)
-    if name not in _POISONED:
-        _POISONED[name] = gt.poisoned(c["blob"])
-    bad, real = _POISONED[name]
-    ctx.fnet_load(bad)
-    return c, real
-
-
-def same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+    yield from own_context()
 
 
 def plain_bits(ctx, c):
@@ -58,7 +39,7 @@ def plain_bits(ctx, c):
 
 @pytest.mark.parametrize("name", ftrain_rows.DROP_ROWS)
 def test_logits_loss_gradient_counter_eval_flag_and_zero_rates(ctx, name):
-    c, real = loaded(ctx, name)
+    c, real = loaded(ctx, drop_case(name))
     model, x, y = c["model"], c["x"], c["y"]
     loss0, z0, g0, info0 = plain_bits(ctx, c)
     with ctx.trainer(padded=True) as tr:
@@ -122,7 +103,7 @@ def test_logits_loss_gradient_counter_eval_flag_and_zero_rates(ctx, name):
 
 
 def test_mid_pads_batch_runs_both_tile_instantiations_in_two_to_four_tiles(ctx):
-    c, _ = loaded(ctx, "mid_pads_batch")
+    c, _ = loaded(ctx, drop_case("mid_pads_batch"))
     p = fnet_plan.plan(c["blob"])
     with ctx.trainer(padded=True, dropout=c["dropout"], seed=c["seed"]) as tr:
         b = tr.info()["batch"]
@@ -136,7 +117,7 @@ def test_the_mask_does_not_depend_on_the_tiling_exactly(ctx):
     ordinals and n are the same, the other tiles contribute +0). ftrain_ref.fold_tiles of those terms is the full call's gradient
     element for element: a mask that depended on the tile, the workgroup or the lane that computes it would not fold."""
     import torch
-    c, real = loaded(ctx, "batch5")
+    c, real = loaded(ctx, drop_case("batch5"))
     n = 1024
     rng = np.random.default_rng(77)
     x = rng.normal(0, 1, (n, int(np.prod(c["model"]["in_shape"])))).astype(np.float32)
@@ -176,7 +157,7 @@ def test_the_mask_does_not_depend_on_the_tiling_exactly(ctx):
 
 
 def test_refusals_leave_the_previous_setting(ctx):
-    c, _ = loaded(ctx, "pool21_before")
+    c, _ = loaded(ctx, drop_case("pool21_before"))
     L = ctx._L
     with ctx.trainer(padded=True) as tr:
         tr.set_dropout(c["dropout"], seed=9)
@@ -217,10 +198,9 @@ def test_fit_follows_the_float64_replay_and_validates_without_dropout(ctx):
     validation entries those of a dropout-free evaluation of the same weights."""
     x, y = ftrain_rows.pad_fit_set()
     model = ftrain_rows.pad_model(ftrain_rows.PAD_FIT_ROW)
-    blob, _ = gt.poisoned(fnet_rows.blob(ftrain_rows.PAD_FIT_ROW))
-    ctx.fnet_load(blob)
+    ctx.fnet_load(poisoned(fnet_rows.blob(ftrain_rows.PAD_FIT_ROW))[0])
     dropout = [(0.25, 1), 0]
-    kw = dict(epochs=100, batch_size=ftrain_rows.FIT_BATCH, seed=0, lr=ftrain_rows.FIT_LR, max_steps=ftrain_rows.FIT_STEPS, val=(x, y), callbacks=False)
+    kw = dict(fit_kw(), val=(x, y), callbacks=False)
     with ctx.trainer(padded=True, dropout=dropout, seed=3) as tr:
         hist = tr.fit(x, y, **kw)
         assert hist["steps"] == 40 and tr.info()["steps"] == 40 and tr.dropout_call == 40    # validation did not advance the counter
@@ -235,32 +215,20 @@ def test_fit_follows_the_float64_replay_and_validates_without_dropout(ctx):
     replay = train.fit(host, x, y, **kw)
     racc = (host.grad(x, y, training=False)["argmax"] == y).mean()
     print("loss %s\nreplay %s\naccuracy %.3f (replay %.3f)" % (np.round(hist["loss"], 5), np.round(replay["loss"], 5), acc, racc))
-    assert len(hist["loss"]) == len(replay["loss"]) == 14 and host.call == 40
-    for got, want in zip(hist["loss"], replay["loss"]):
-        assert abs(got - want) <= 1e-3 * want, (hist["loss"], replay["loss"])
-    for got, want in zip(hist["val_loss"], replay["val_loss"]):
-        assert abs(got - want) <= 1e-3 * want, (hist["val_loss"], replay["val_loss"])
+    assert len(hist["loss"]) == 14 and host.call == 40
+    follows_replay(hist, replay)
     assert acc >= racc
 
 
 def test_kws_train_with_dropout_then_kws_quantize(ctx, tmp_path):
     """kws train --dropout-arch tiny_conv on tiny_conv at 31 x 13 x 1, 5 epochs, then kws quantize of what it wrote."""
-    from edison_amd import config as cfg
-    from edison_amd.kws import kws_quantize, kws_train
-    from edison_amd.kws.geometry import KwsGeometry
+    from edison_amd.kws import kws_train
     model = ftrain_rows.pad_model("tiny_conv")
     x, y = ftrain_rows.kws_set()
     keywords = ["k%d" % i for i in range(10)]
-    with open(tmp_path / "net.ednf", "wb") as f:
-        f.write(cube_import.build_blob(model, keywords))
-    np.save(tmp_path / "x.npy", x)
-    np.save(tmp_path / "y.npy", y)
-    args = [str(tmp_path / "net.ednf"), str(tmp_path / "x.npy"), str(tmp_path / "y.npy")]
-    val = (str(tmp_path / "x.npy"), str(tmp_path / "y.npy"))
-    out = io.StringIO()
-    blob, hist = kws_train.run(*args, str(tmp_path / "out.ednf"), epochs=5, batch=32, lr=0.01, val=val, ctx=ctx, out=out, dropout_arch="tiny_conv")
-    assert (tmp_path / "out.ednf").read_bytes() == blob and hist["steps"] == 15 and len(hist["val_loss"]) == 5
-    assert "after 15 steps" in out.getvalue() and hist["loss"][-1] < hist["loss"][0]
+    args, val = kws_files(tmp_path, model, x, y, keywords)
+    blob, hist, _, trained = kws_trained(ctx, tmp_path, args, val, dropout_arch="tiny_conv")
+    assert hist["loss"][-1] < hist["loss"][0]
     plain, _ = kws_train.run(*args, str(tmp_path / "plain.ednf"), epochs=5, batch=32, lr=0.01, val=val, ctx=ctx, out=io.StringIO())
     assert plain != blob                                                    # the masks took part
     again, _ = kws_train.run(*args, str(tmp_path / "again.ednf"), epochs=5, batch=32, lr=0.01, val=val, ctx=ctx, out=io.StringIO(), dropout=[0.25, 0],
@@ -270,10 +238,5 @@ def test_kws_train_with_dropout_then_kws_quantize(ctx, tmp_path):
         with pytest.raises(ValueError):
             kws_train.run(*args, str(tmp_path / "bad.ednf"), epochs=1, ctx=ctx, out=io.StringIO(), **bad)
     assert kws_train.main(["train"] + args + [str(tmp_path / "bad.ednf"), "--dropout", "x"]) == 1
-    trained = cube_import.read_blob(blob)
     assert trained["keywords"] == keywords and struct.unpack_from("<i", blob, 4)[0] == 2
-    g = KwsGeometry.from_config(net_input_scale=cfg.net_input_scale)
-    rng = np.random.default_rng(8)
-    np.save(tmp_path / "audio.npy", np.clip(rng.normal(0, 3000, (6, g.n_samples)), -32768, 32767).astype(np.int16))
-    qblob, rep = kws_quantize.run(str(tmp_path / "out.ednf"), str(tmp_path / "audio.npy"), str(tmp_path / "q.ednn"), ctx=ctx, out=io.StringIO())
-    assert (tmp_path / "q.ednn").read_bytes() == qblob and len(rep["float_argmax"]) == 6
+    kws_quantized(ctx, tmp_path)
