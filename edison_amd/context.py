@@ -667,6 +667,11 @@ class Context:
         self._check(self._L.edison_mfcc_q15_batch_dev(self._h, _t_ptr(audio), int(n_frames), int(frame_step), int(n_coef),
                                                       _t_ptr(out), _t_ptr(feat)))
 
+    def mfcc_q15_stages_t(self, audio, n_frames, frame_step=FRAME_LEN, fft=None, spec=None, mel=None, mfcc=None):
+        """audio: int16 CUDA tensor; int16 CUDA tensors or None: fft [n_frames, 513, 2], spec [n_frames, 513], mel and mfcc [n_frames, 32]."""
+        self._check(self._L.edison_mfcc_q15_stages_dev(self._h, _t_ptr(audio), int(n_frames), int(frame_step), _t_ptr(fft), _t_ptr(spec),
+                                                       _t_ptr(mel), _t_ptr(mfcc)))
+
 
 _default = None
 

@@ -7,6 +7,7 @@
  * edison_init fails with EDISON_E_NO_DEVICE when there is none.
  */
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -218,8 +219,11 @@ extern "C" int edison_mfcc_configure(edison_ctx *ctx, double sample_rate, double
                                      double upper_edge_hertz, double mel_mtx_scale)
 {
 	if (!ctx) return EDISON_E_ARGUMENT;
-	if (!(sample_rate > 0) || !(lower_edge_hertz >= 0) || !(upper_edge_hertz > lower_edge_hertz) ||
-	    !(upper_edge_hertz <= sample_rate / 2.0) || !(mel_mtx_scale > 0))
+	/* an upper edge above sample_rate / 2 is taken as gen_mel_weight_matrix takes it (mfcc_utils.py:36-73 has no such check, nor have
+	 * edison_mfcc_generic and edison_kws_geom): the top bands are cut off at the last bin, which then carries a non-zero weight --
+	 * the one way variant C's Nyquist bin is switched on (tables_q15.c: need_nyquist) */
+	if (!(sample_rate > 0) || !(lower_edge_hertz >= 0) || !(upper_edge_hertz > lower_edge_hertz) || !(mel_mtx_scale > 0) ||
+	    !isfinite(sample_rate) || !isfinite(upper_edge_hertz) || !isfinite(mel_mtx_scale))
 		return set_err(ctx, EDISON_E_ARGUMENT, "edison_mfcc_configure: bad filterbank edges");
 	ED_HIP(ctx, hipSetDevice(ctx->device));
 	return upload_tables(ctx, sample_rate, lower_edge_hertz, upper_edge_hertz, mel_mtx_scale);

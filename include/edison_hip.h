@@ -86,7 +86,8 @@ int edison_sync(edison_ctx *ctx);
 int edison_device_info(edison_ctx *ctx, char *name, int name_cap, int *n_cu, int64_t *hbm_bytes);
 
 /* Mel filterbank parameters (defaults = audio/config.py). Rebuilds the device tables of both variants.
- * num_mel_bins must be 32 and the frame length 1024 on this path (EDISON_E_NO_IMPL otherwise).          */
+ * num_mel_bins must be 32 and the frame length 1024 on this path (EDISON_E_NO_IMPL otherwise). An upper edge above
+ * sample_rate / 2 is accepted, as gen_mel_weight_matrix accepts it: the top bands end at the last spectrum bin.  */
 int edison_mfcc_configure(edison_ctx *ctx, double sample_rate, double lower_edge_hertz, double upper_edge_hertz,
                           double mel_mtx_scale);
 

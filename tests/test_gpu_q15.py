@@ -152,15 +152,17 @@ def test_q15_kws_is_what_the_board_answers(ctx, oracle_mod, oracle_model, q15_go
 
 
 def test_q15_other_filterbanks(built_lib, oracle_mod, mfcc_golden):
-    """edison_mfcc_configure rebuilds the compact mel tables; a band that reaches bin 512 switches the Nyquist bin on;
-    a scale the firmware format cannot hold switches variant C off without touching A/B."""
+    """edison_mfcc_configure rebuilds the compact mel tables. The first four filterbanks do NOT switch the Nyquist bin on, not even
+    the one whose upper edge is fs / 2: a triangle that ends on bin 512 has weight 0 there. The last one does (upper edge above
+    fs / 2: tap 19 on bin 512, ed_build_q15_tables' need_nyquist = 1; tests/test_q15_sweep_cpu.py reads the tables); the sweep of
+    tests/test_gpu_q15_sweep.py runs more of them. A scale the firmware format cannot hold switches variant C off without touching A/B."""
     from edison_amd import _lib
     from edison_amd.context import Context
     x = np.concatenate([mfcc_golden["in_edison"], mfcc_golden["in_extremes"]])
     c = Context(0)
     try:
         for fs, lo, hi, scale in ((16000, 20.0, 8000.0, 128), (16000, 300.0, 3400.0, 64), (8000, 80.0, 3800.0, 128),
-                                  (16000, 80.0, 7600.0, 1000)):
+                                  (16000, 80.0, 7600.0, 1000), (16000, 80.0, 8100.0, 128)):
             c.configure_mfcc(fs, lo, hi, scale)
             t = oracle_mod.Q15Tables(sample_rate=fs, lower_edge_hertz=lo, upper_edge_hertz=hi, mel_mtx_scale=scale)
             assert np.array_equal(c.mfcc_q15(x), oracle_mod.mfcc_q15(x, tables=t)), (fs, lo, hi, scale)
